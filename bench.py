@@ -13,9 +13,10 @@ data are replicated; every rank accumulates a private gradient texture and the t
 all-reduce per step, issued asynchronously so that it overlaps the next step's forward + adjoint (double-
 buffered texture).  `--scaling weak` keeps the round-1 mode (every rank traces its own 64 spp of the image).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes the last timed step's outputs (dump_outputs) as .npy
+files, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import ctypes as C
@@ -34,6 +35,11 @@ ADJ_BYTES_PER_RAY = 128.0   # 28 ray + 16 pi + 72 upstream in + 12 atomically ad
 GRID_BYTES_PER_TEXEL = 20.0 / 3.0  # heights 4 B + mips ~8/3 B, read once per pass
 HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0       # same guide: measured float4 copy (79 % of spec)
+# --dump-outputs: per-ray outputs of at most DUMP_RAYS rays (24 MB) and at most DUMP_TEXELS texels of dL/dheight
+# (16 MB), so that a dump stays under 64 MB at every size
+DUMP_RAYS = 1 << 18
+DUMP_TEXELS = 1 << 22
+DUMP_SEED = 20240607
 
 
 def parse():
@@ -47,7 +53,15 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline time (0 = skip)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1: strong = image tiles of ONE wavefront (configs[3]); weak = a full wavefront per rank")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0's rays; "
+                         "finite float32 / float64: the hit mask `valid` and the outputs of the rays that hit, of a "
+                         "fixed seeded sample of at most %d rays, and at most %d gradient texels)"
+                         % (DUMP_RAYS, DUMP_TEXELS))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -220,6 +234,8 @@ def main():
     ms_step = 1e3 * elapsed / args.steps
     grad_h = grads[(step_no[0] - 1) % len(grads)]
     grad_sample = grad_h.clone()          # the reduced gradient of the last timed step (checksums below)
+    if args.dump_outputs and rank == 0:   # before the serial steps (N > 1) and the other launches overwrite pi / si
+        dump_outputs(args.dump_outputs, si, t, uv, prim, grad_sample)
     # N > 1: the same steps with the all-reduce waited for inside the step (no overlap with the next forward) --
     # reported beside the headline, which overlaps it
     serial_ms = None
@@ -329,6 +345,49 @@ def library_id(_capi):
     return {"path": os.path.relpath(path, ROOT) if path.startswith(ROOT) else path,
             "sha256_16": hashlib.sha256(open(path, "rb").read()).hexdigest()[:16],
             "hf_lib_override": bool(os.environ.get("HF_LIB"))}
+
+
+def _sample(n, k):
+    """sorted indices of a fixed, seeded sample of k of range(n); None (take all) when n <= k"""
+    import numpy as np
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, si, t, uv, prim, grad):
+    """What the timed path hands its caller after the last timed step, as DIR/<name>.npy, every value finite.
+    Rays: all of them or a seeded sample of DUMP_RAYS, in wavefront order.  `valid` [k] is 1 where the ray hit
+    (si.is_valid(): a miss is t = inf, with zeros in the other fields); the surface interaction (hf_si_t rows t, p,
+    n, uv, sh_n, dp_du, dp_dv) and the preliminary intersection (pi_t, prim_uv, prim_index as float64 of the uint32)
+    are those of the valid rays, [m] / [c, m].  dL/dheight: the [N, N] texture, or a seeded sample of DUMP_TEXELS
+    texels in row-major order."""
+    import numpy as np
+    import torch
+    from hf_amd.shape import _DIFF_ROWS
+    os.makedirs(out_dir, exist_ok=True)
+    idx = _sample(t.shape[0], DUMP_RAYS)
+    idx = None if idx is None else torch.from_numpy(idx).to(t.device)
+
+    def pick(a):   # the sampled rays (last axis) of a device tensor, on the host
+        return (a if idx is None else a.index_select(a.dim() - 1, idx)).cpu().numpy()
+
+    out, k = {}, 0
+    si_h = pick(si)
+    hit = np.isfinite(si_h[0])
+    for name, c in _DIFF_ROWS:
+        out[name] = si_h[k] if c == 1 else si_h[k:k + c]
+        k += c
+    out["pi_t"] = pick(t)
+    out["prim_uv"] = pick(uv)
+    out["prim_index"] = pick(prim).view(np.uint32).astype(np.float64)
+    out = {name: a[..., hit] for name, a in out.items()}
+    out["valid"] = hit.astype(np.float32)
+    gidx = _sample(grad.numel(), DUMP_TEXELS)
+    g = grad.cpu().numpy()
+    out["grad_heights"] = g if gidx is None else g.reshape(-1)[gidx]
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _rows_of(buf, n):
