@@ -21,6 +21,7 @@
 //   ray_intersect_preliminary(_scalar/_packet), ray_test(...)   include/mitsuba/render/shape.h:137-153,220-240,594-641
 //   compute_surface_interaction        include/mitsuba/render/shape.h:179-183 (analog src/render/mesh.cpp:672-903)
 //   reverse mode of the above          Dr.Jit AD over mesh.cpp:672-903 (prb_reparam.py:586-587) -> dr::CustomOp -> hf_adjoint
+//   forward mode of the above          dr.forward / render_forward over mesh.cpp:672-903 -> dr::CustomOp::forward -> hf_tangent
 //   class / plugin registration        include/mitsuba/core/class.h:195-211, src/core/plugin.cpp:93-127
 #include <mitsuba/core/bitmap.h>
 #include <mitsuba/core/fwd.h>
@@ -98,10 +99,12 @@ enum : size_t {
 template <typename Float, typename Spectrum> class Heightfield;
 
 // ---------------------------------------------------------------------------------------------------------
-// Differentiable surface interaction: primal = hf_compute_surface_interaction, reverse mode = hf_adjoint.
+// Differentiable surface interaction: primal = hf_compute_surface_interaction, reverse mode = hf_adjoint,
+// forward mode = hf_tangent.
 // Inputs that carry gradients: the height tensor's array, ray.o, ray.d.  Output: the 18 differentiable
 // rows of the record packed as one array of 18 n floats (t, p, n, uv, sh_frame.n, dp_du, dp_dv).
-// (Dr.Jit 0.4.2 drjit/custom.h: CustomOp<DiffType, Output, Input...>::eval / backward / grad_out / set_grad_in.)
+// (Dr.Jit 0.4.2 drjit/custom.h: CustomOp<DiffType, Output, Input...>::eval / backward / grad_out / set_grad_in,
+// forward / grad_in / set_grad_out.)
 // ---------------------------------------------------------------------------------------------------------
 template <typename Float, typename Spectrum>
 struct HeightfieldSIOp
@@ -147,8 +150,31 @@ struct HeightfieldSIOp
     }
 
     void forward() override {
-        Throw("heightfield: forward-mode AD through the HIP surface interaction is not provided "
-              "(use reverse mode: dr.backward / prb-style integrators)");
+        const size_t n = call.n, texels = (size_t) call.shape->width() * call.shape->height();
+        // tangents of the inputs; an input without one is handed to hf_tangent as NULL (zero tangent)
+        std::vector<float> dh, dod;
+        if (Base::template grad_enabled_in<0>()) {
+            Float g = Base::template grad_in<0>();
+            dr::eval(g); dr::sync_thread();
+            dh.assign(texels, 0.f);
+            if (dr::width(g) == texels) dr::store(dh.data(), g);
+        }
+        if (Base::template grad_enabled_in<1>() || Base::template grad_enabled_in<2>()) {
+            dod.assign(6 * n, 0.f);
+            if (Base::template grad_enabled_in<1>()) {
+                Float g = Base::template grad_in<1>();
+                dr::eval(g); dr::sync_thread();
+                if (dr::width(g) == 3 * n) dr::store(dod.data(), g);
+            }
+            if (Base::template grad_enabled_in<2>()) {
+                Float g = Base::template grad_in<2>();
+                dr::eval(g); dr::sync_thread();
+                if (dr::width(g) == 3 * n) dr::store(dod.data() + 3 * n, g);
+            }
+        }
+        std::vector<float> tangent_rows(18 * n);
+        call.shape->si_tangent(call, dh.empty() ? nullptr : dh.data(), dod.empty() ? nullptr : dod.data(), tangent_rows.data());
+        Base::set_grad_out(dr::load<Float>(tangent_rows.data(), 18 * n));
     }
 
     const char *name() const override { return "HeightfieldSI"; }
@@ -440,6 +466,32 @@ public:
         m_stage.download(grad_od, god, 6 * n);
         m_stage.sync();
         HfStaging::hip_check(hipFree(grad_dev));
+    }
+
+    void si_tangent(const typename SIOp::Call &op, const float *dheights /* host, H W, may be NULL */,
+                    const float *dod /* host, 6 n: d_o then d_d, may be NULL */, float *tangent_rows /* host, 18 n */) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *dev = m_stage.reserve(ROWS_TOTAL, n);
+        upload_call(dev, op);
+        float *tg = dev + ROW_GRAD * n, *dod_dev = tg + 18 * n; // the gradient rows of si_adjoint hold the tangents
+        if (dod) m_stage.upload(dod_dev, dod, 6 * n);
+        float *dh_dev = nullptr;
+        if (dheights) {
+            HfStaging::hip_check(hipMalloc((void **) &dh_dev, texels * sizeof(float)));
+            m_stage.upload(dh_dev, dheights, texels);
+        }
+        hf_rays_t rays = rays_at(dev, n);
+        hf_pi_const_t pic = { dev + ROW_T * n, { dev + ROW_U * n, dev + ROW_V * n }, (const uint32_t *) (dev + ROW_PRIM * n) };
+        hf_si_tangent_t ts = { tg, { tg + n, tg + 2 * n, tg + 3 * n }, { tg + 4 * n, tg + 5 * n, tg + 6 * n }, { tg + 7 * n, tg + 8 * n },
+                               { tg + 9 * n, tg + 10 * n, tg + 11 * n }, { tg + 12 * n, tg + 13 * n, tg + 14 * n },
+                               { tg + 15 * n, tg + 16 * n, tg + 17 * n } };
+        const float *d_o[3] = { dod_dev, dod_dev + n, dod_dev + 2 * n }, *d_d[3] = { dod_dev + 3 * n, dod_dev + 4 * n, dod_dev + 5 * n };
+        hf_check(hf_tangent(m_hf, n, &rays, &pic, op.ray_flags, (const uint8_t *) (dev + ROW_ACTIVE * n), dh_dev,
+                            dod ? d_o : nullptr, dod ? d_d : nullptr, &ts, m_stage.stream()));
+        m_stage.download(tangent_rows, tg, 18 * n);
+        m_stage.sync();
+        if (dh_dev) HfStaging::hip_check(hipFree(dh_dev));
     }
 
     std::string to_string() const override {

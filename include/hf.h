@@ -39,6 +39,8 @@
  *         synchronise the replay's stream before hf_bbox, hf_get_mip, the packet entry points or hf_destroy;
  *       * a captured launch snapshots the transform (to_world / to_object) by value: hf_set_transform after the
  *         capture does not reach the replays -- re-capture.
+ *     The forward-mode entry points (hf_tangent, hf_direct_lighting_weighted_tangent, hf_point_lighting_tangent) are
+ *     capturable as well: they reserve no scratch block, allocate nothing and never synchronise the host.
  *     Not capturable: hf_create / hf_destroy, hf_set_heights_host, hf_bbox, hf_get_mip and the host-pointer packet
  *     entry (they synchronise).
  */
@@ -162,6 +164,17 @@ typedef struct hf_si_grad {
     const float *dp_du[3];
     const float *dp_dv[3];
 } hf_si_grad_t;
+
+/* Tangent (forward-mode derivative) of the same 18 differentiable fields; NULL pointer = row not written. */
+typedef struct hf_si_tangent {
+    float *t;
+    float *p[3];
+    float *n[3];
+    float *uv[2];
+    float *sh_n[3];
+    float *dp_du[3];
+    float *dp_dv[3];
+} hf_si_tangent_t;
 
 /* ---- lifetime / parameters ------------------------------------------------ */
 
@@ -303,6 +316,20 @@ int hf_adjoint_rows(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
                     const hf_si_grad_t *grad_si, float *grad_heights,
                     float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hf_stream_t stream);
 
+/* Replaces: the Dr.Jit FORWARD-mode traversal of the attached surface interaction of mesh.cpp:672-903 that
+ * dr.forward / dr.forward_to trigger (src/render/tests/test_mesh.py:380-422, 458-531, 674-735; the integrators'
+ * render_forward, src/python/python/ad/integrators/common.py:120, 587, 977): for a perturbation of the heights
+ * (dheights: width*height floats, row-major, the layout of hf_adjoint's grad_heights) and of the rays (d_o, d_d: 3
+ * arrays of n floats each), the tangent of the 18 fields of hf_si_tangent_t per lane (overwritten; NULL rows are not
+ * written).  Any of dheights / d_o / d_d may be NULL (zero tangent; a non-NULL d_o / d_d may have NULL rows).
+ * The exact transpose of hf_adjoint, mode for mode: default = Moeller-Trumbore re-intersection with attached vertices
+ * (t = replace_grad(pi.t, t_d), mesh.cpp:728-735); HF_RAY_FOLLOWSHAPE = frozen barycentrics, t = sqrt(|p-o|^2/|d|^2)
+ * (mesh.cpp:748-752); HF_RAY_DETACHSHAPE = the heights contribute nothing, the rays still do.  Missed and inactive lanes
+ * get exactly zero tangents.  No atomics: the result is bitwise the same from launch to launch. */
+int hf_tangent(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi, uint32_t ray_flags,
+               const uint8_t *active, const float *dheights, const float *const d_o[3], const float *const d_d[3],
+               const hf_si_tangent_t *tangent_si, hf_stream_t stream);
+
 /* ---- next row: minimal direct lighting on the wavefront ------- */
 
 /* A directional emitter (src/emitters/directional.cpp:82,174): unit direction TOWARDS the light, scalar irradiance. */
@@ -354,6 +381,16 @@ int hf_direct_lighting_weighted_adjoint(size_t n, uint32_t spp, const float *con
  *   grad_sh_n[i] = sum_k w_k / r^2 * l,   grad_p[i] = sum_k w_k / r^3 * (3 <sh_n, l> l - sh_n),
  *   w_k = 1/spp * albedo/pi * intensity_k * vis_k * grad_image[k][i / spp]            (same masks)
  * both overwritten; feed them to hf_adjoint as hf_si_grad_t.sh_n / .p. */
+/* Forward mode of hf_direct_lighting_weighted (the transpose of its adjoint; dr.forward through the term of
+ * direct_reparam.py:149-175): for tangents dsh_n (3 arrays of n floats) and dweight (n floats), either may be NULL
+ * (zero), the tangent image dimage[k][i / spp] (device, n_lights * (n / spp) floats, overwritten):
+ *   dimage[k][i / spp] = 1/spp * sum_s  albedo/pi * E_k * vis_k * (weight <dsh_n, l_k> + dweight <sh_n, l_k>)   (same masks) */
+int hf_direct_lighting_weighted_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                        const float *t, const float *weight, uint32_t n_lights,
+                                        const hf_dir_light_t *lights, float albedo, const uint8_t *const *vis,
+                                        const float *const dsh_n[3], const float *dweight, float *dimage,
+                                        hf_stream_t stream);
+
 typedef struct {
     float position[3];
     float intensity; /* radiant intensity (W/sr) */
@@ -366,6 +403,14 @@ int hf_point_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3]
                               const hf_point_light_t *lights, float albedo, const uint8_t *const *vis,
                               const float *grad_image, float *const grad_sh_n[3], float *const grad_p[3],
                               hf_stream_t stream);
+/* Forward mode of hf_point_lighting (the transpose of hf_point_lighting_adjoint; the term of point.cpp:106-123 under
+ * dr.forward): tangents dsh_n and dp (3 arrays of n floats each, either may be NULL = zero) give
+ *   dimage[k][i / spp] = sum_s w_k / r^2 (<dsh_n, l> + <dp, 3 <sh_n, l> l - sh_n> / r),  w_k = 1/spp albedo/pi intensity_k vis_k
+ * (same masks; dimage overwritten). */
+int hf_point_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                              const float *const p[3], uint32_t n_lights, const hf_point_light_t *lights, float albedo,
+                              const uint8_t *const *vis, const float *const dsh_n[3], const float *const dp[3],
+                              float *dimage, hf_stream_t stream);
 
 /* Film with a Gaussian reconstruction filter (the reference's default rfilter, src/rfilters/gaussian.cpp:48-101:
  * w(x) = max(0, exp(-x^2 / (2 stddev^2)) - exp(-r^2 / (2 stddev^2))), r = 4 stddev), splatted as ImageBlock::put does

@@ -35,6 +35,11 @@ class hf_si_grad_t(C.Structure):
                 ("dp_du", _fp * 3), ("dp_dv", _fp * 3)]
 
 
+class hf_si_tangent_t(C.Structure):
+    _fields_ = [("t", _fp), ("p", _fp * 3), ("n", _fp * 3), ("uv", _fp * 2), ("sh_n", _fp * 3),
+                ("dp_du", _fp * 3), ("dp_dv", _fp * 3)]
+
+
 # every symbol include/hf.h declares: name -> (restype, argtypes)
 HF_MAX_LIGHTS = 8
 
@@ -74,6 +79,8 @@ SYMBOLS = {
     "hf_adjoint_rows": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(hf_rays_t), C.POINTER(hf_pi_t),
                              C.c_uint32, _fp, C.POINTER(hf_si_grad_t), _fp,
                              C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p, C.c_void_p]),
+    "hf_tangent": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(hf_rays_t), C.POINTER(hf_pi_t), C.c_uint32, _fp, _fp,
+                             C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(hf_si_tangent_t), C.c_void_p]),
     "hf_direct_lighting": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_uint32,
                                      C.POINTER(hf_dir_light_t), C.c_float, C.POINTER(_fp), _fp, C.c_void_p]),
     "hf_direct_lighting_adjoint": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
@@ -85,11 +92,17 @@ SYMBOLS = {
     "hf_direct_lighting_weighted_adjoint": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
                                                       _fp, C.c_uint32, C.POINTER(hf_dir_light_t), C.c_float,
                                                       C.POINTER(_fp), _fp, C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    "hf_direct_lighting_weighted_tangent": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
+                                                      _fp, C.c_uint32, C.POINTER(hf_dir_light_t), C.c_float,
+                                                      C.POINTER(_fp), C.POINTER(_fp * 3), _fp, _fp, C.c_void_p]),
     "hf_point_lighting": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 3),
                                     C.c_uint32, C.POINTER(hf_dir_light_t), C.c_float, C.POINTER(_fp), _fp, C.c_void_p]),
     "hf_point_lighting_adjoint": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
                                             C.POINTER(_fp * 3), C.c_uint32, C.POINTER(hf_dir_light_t), C.c_float,
                                             C.POINTER(_fp), _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_point_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
+                                            C.POINTER(_fp * 3), C.c_uint32, C.POINTER(hf_dir_light_t), C.c_float,
+                                            C.POINTER(_fp), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_void_p]),
     "hf_film_splat": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp), _fp, _fp, C.c_uint32, C.c_uint32, C.c_float, _fp, _fp,
                                 C.c_void_p]),
     "hf_film_splat_adjoint": (C.c_int, [C.c_size_t, C.c_uint32, _fp, _fp, C.c_uint32, C.c_uint32, C.c_float, _fp,

@@ -523,6 +523,19 @@ extern "C" int hf_adjoint(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
     return hf_adjoint_rows(hf, n, rays, pi, ray_flags, active, grad_si, grad_heights, grad_o, grad_d, nullptr, stream);
 }
 
+extern "C" int hf_tangent(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
+                          uint32_t ray_flags, const uint8_t *active, const float *dheights, const float *const d_o[3],
+                          const float *const d_d[3], const hf_si_tangent_t *tangent_si, hf_stream_t stream) {
+    int rc = check_rays("hf_tangent", hf, n, rays);
+    if (rc) return rc;
+    if ((rc = check_flags("hf_tangent", ray_flags))) return rc;
+    if ((rc = check_pi("hf_tangent", n, pi))) return rc;
+    if (!tangent_si) return fail(HF_EINVAL, "hf_tangent: NULL output");
+    hf_launch_tangent(hf->dev, n, rays, pi, active, ray_flags, dheights, d_o, d_d, tangent_si, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- minimal direct lighting --------------------------------------------------
 static int pack_lights(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                        const float *t, uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
@@ -586,6 +599,23 @@ extern "C" int hf_direct_lighting_adjoint(size_t n, uint32_t spp, const float *c
                                                grad_sh_n, nullptr, stream);
 }
 
+extern "C" int hf_direct_lighting_weighted_tangent(size_t n, uint32_t spp, const float *const sh_n[3],
+                                                   const float *const d[3], const float *t, const float *weight,
+                                                   uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
+                                                   const uint8_t *const *vis, const float *const dsh_n[3],
+                                                   const float *dweight, float *dimage, hf_stream_t stream) {
+    hf_lights_dev L;
+    const int rc = pack_lights("hf_direct_lighting_weighted_tangent", n, spp, sh_n, d, t, n_lights, lights, albedo, vis, L);
+    if (rc != HF_OK) return rc;
+    if (!dimage) return fail(HF_EINVAL, "hf_direct_lighting_weighted_tangent: NULL image");
+    if (dsh_n && (!dsh_n[0] || !dsh_n[1] || !dsh_n[2]))
+        return fail(HF_EINVAL, "hf_direct_lighting_weighted_tangent: NULL dsh_n component array");
+    L.weight = weight;
+    hf_launch_direct_tangent(n, spp, sh_n, d, t, nullptr, L, dsh_n, nullptr, dweight, dimage, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 static bool all3(const float *const p[3]) { return p && p[0] && p[1] && p[2]; }
 
 // point lights: same packing (hf_point_light_t has hf_dir_light_t's layout: three floats + one)
@@ -618,6 +648,24 @@ extern "C" int hf_point_lighting_adjoint(size_t n, uint32_t spp, const float *co
         !grad_p[1] || !grad_p[2])
         return fail(HF_EINVAL, "hf_point_lighting_adjoint: NULL gradient array");
     hf_launch_direct_adjoint(n, spp, sh_n, d, t, p, L, grad_image, grad_sh_n, grad_p, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_point_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                         const float *t, const float *const p[3], uint32_t n_lights,
+                                         const hf_point_light_t *lights, float albedo, const uint8_t *const *vis,
+                                         const float *const dsh_n[3], const float *const dp[3], float *dimage,
+                                         hf_stream_t stream) {
+    hf_lights_dev L;
+    const int rc = pack_lights("hf_point_lighting_tangent", n, spp, sh_n, d, t, n_lights, (const hf_dir_light_t *) lights,
+                               albedo, vis, L);
+    if (rc != HF_OK) return rc;
+    if (!all3(p)) return fail(HF_EINVAL, "hf_point_lighting_tangent: NULL position array");
+    if (!dimage) return fail(HF_EINVAL, "hf_point_lighting_tangent: NULL image");
+    if ((dsh_n && !all3(dsh_n)) || (dp && !all3(dp)))
+        return fail(HF_EINVAL, "hf_point_lighting_tangent: NULL tangent component array");
+    hf_launch_direct_tangent(n, spp, sh_n, d, t, p, L, dsh_n, dp, nullptr, dimage, (hipStream_t) stream);
     HF_HIP(hipGetLastError());
     return HF_OK;
 }

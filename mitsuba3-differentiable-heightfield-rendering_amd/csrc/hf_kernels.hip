@@ -2248,6 +2248,184 @@ void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
 }
 
 // ---------------------------------------------------------------------------------
+// tangent: forward mode of compute_si (the transpose of hf_adjoint_kernel, term for term), no scatter
+// ---------------------------------------------------------------------------------
+// Shaped like hf_si_kernel (one block per 256 rays, arguments from the kernarg segment where they are used, every row
+// stored as soon as it is final): a hit lane issues one batch of independent loads (the rest of pi, o, d and the ray
+// tangents), then one round trip for the three heights and three height tangents of its triangle.  A missed lane reads
+// pi.t (and active) and stores zeros.
+struct hf_tan_dev {
+    float *t, *p[3], *n[3], *uv[2], *sh_n[3], *dp_du[3], *dp_dv[3];
+};
+struct hf_tangent_args {
+    hf_dev_field f;
+    size_t n;
+    hf_rays_dev rays;
+    hf_pi_cdev pi;
+    const uint8_t *active;
+    const float *dh;            // [H*W] height tangent, NULL = zero
+    const float *d_o[3], *d_d[3]; // per-ray tangents, NULL rows = zero
+    hf_tan_dev out;             // NULL rows are not written
+    uint32_t flags;
+};
+typedef const __attribute__((address_space(4))) hf_tangent_args *hf_tan_kargs;
+
+// RAYTAN: d_o or d_d is given (without them the ray terms are dead code)
+template <bool RAYTAN>
+__global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_) {
+    (void) a_;
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u);; ub += stride) {
+        hf_tan_kargs ka = (hf_tan_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka)); // opaque: keeps the loads that follow where they are written
+        const size_t n = ka->n;
+        if (ub >= n) break; // wave-uniform
+        if (lane >= n - ub) continue;
+        const uint32_t lo = lane;
+        const float t_in = (ka->pi.t + ub)[lo];
+        const uint8_t *active = ka->active;
+        const bool act = (active ? ((active + ub)[lo] != 0) : true) && (t_in != __builtin_inff());
+        const v3 z3 = mk3(0.f, 0.f, 0.f);
+        if (!act) { // missed / inactive: exactly zero tangents
+            st(ka->out.t, ub, lo, 0.f); st3(ka->out.p, ub, lo, z3); st3(ka->out.n, ub, lo, z3);
+            st(ka->out.uv[0], ub, lo, 0.f); st(ka->out.uv[1], ub, lo, 0.f); st3(ka->out.sh_n, ub, lo, z3);
+            st3(ka->out.dp_du, ub, lo, z3); st3(ka->out.dp_dv, ub, lo, z3);
+            continue;
+        }
+        const uint32_t flags = ka->flags;
+        const bool follow = (flags & 0x80u) != 0, detach = (flags & 0x100u) != 0;
+        // ONE batch of independent loads: pi, the ray, the ray tangents
+        const float b1 = (ka->pi.u + ub)[lo], b2 = (ka->pi.v + ub)[lo], b0 = 1.f - b1 - b2;
+        const uint32_t prim = (ka->pi.prim + ub)[lo];
+        const v3 o = mk3((ka->rays.o[0] + ub)[lo], (ka->rays.o[1] + ub)[lo], (ka->rays.o[2] + ub)[lo]);
+        const v3 d = mk3((ka->rays.d[0] + ub)[lo], (ka->rays.d[1] + ub)[lo], (ka->rays.d[2] + ub)[lo]);
+        v3 dO = z3, dD = z3;
+        if (RAYTAN) {
+            dO = mk3(ldu(ka->d_o[0], ub, lo), ldu(ka->d_o[1], ub, lo), ldu(ka->d_o[2], ub, lo));
+            dD = mk3(ldu(ka->d_d[0], ub, lo), ldu(ka->d_d[1], ub, lo), ldu(ka->d_d[2], ub, lo));
+        }
+        // then the three heights and their three tangents: one round trip
+        const hf_dev_field f = load_field(&ka->f);
+        int vi[3], vj[3];
+        prim_vertex_ids(f, prim, vi, vj);
+        const float *dh = detach ? nullptr : ka->dh; // DetachShape: the heights carry no tangent
+        float hz[3], dz[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const size_t idx = (size_t) vi[k] * f.W + vj[k];
+            hz[k] = f.h[idx];
+            dz[k] = dh ? dh[idx] : 0.f;
+        }
+        v3 P[3];
+        float U[3], V[3];
+        const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s); // dP_k/dh_k
+        v3 dP[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const v3 q = mk3(__builtin_fmaf((float) vj[k], f.sx, -1.0f), __builtin_fmaf((float) vi[k], f.sy, -1.0f), hz[k] * f.s);
+            P[k] = xform_point(f.to_world, q);
+            U[k] = (float) vj[k] * f.iu;
+            V[k] = (float) vi[k] * f.iv;
+            dP[k] = ez * dz[k];
+        }
+        const v3 e1 = P[1] - P[0], e2 = P[2] - P[0];
+        const v3 de1 = dP[1] - dP[0], de2 = dP[2] - dP[0];
+        // n = sh_n = +-normalize(cross(e1, e2))
+        {
+            const v3 N = cross3(e1, e2);
+            const float r = rsqrt_ieee(dot3(N, N));
+            const v3 nn = N * r;
+            const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);
+            const v3 dN = mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
+            const float proj = dot3(nn, dN);
+            const float sr = f.flip ? -r : r;
+            const v3 dn = mk3((dN.x - nn.x * proj) * sr, (dN.y - nn.y * proj) * sr, (dN.z - nn.z * proj) * sr);
+            st3(ka->out.n, ub, lo, dn);
+            st3(ka->out.sh_n, ub, lo, dn);
+        }
+        // dp_du / dp_dv: linear in the edges (the texcoord differences are constant); zero without dPdUV
+        {
+            v3 ddu = z3, ddv = z3;
+            if (flags & 0x4u) {
+                const float du0 = U[1] - U[0], dv0 = V[1] - V[0], du1 = U[2] - U[0], dv1 = V[2] - V[0];
+                const float det = __builtin_fmaf(du0, dv1, -(dv0 * du1));
+                const float inv_det = rcp_ieee(det);
+                if (det != 0.f) {
+                    const float a0 = dv1 * inv_det, a1 = -dv0 * inv_det, c0 = -du1 * inv_det, c1 = du0 * inv_det;
+                    ddu = mk3(a0 * de1.x + a1 * de2.x, a0 * de1.y + a1 * de2.y, a0 * de1.z + a1 * de2.z);
+                    ddv = mk3(c0 * de1.x + c1 * de2.x, c0 * de1.y + c1 * de2.y, c0 * de1.z + c1 * de2.z);
+                }
+            }
+            st3(ka->out.dp_du, ub, lo, ddu);
+            st3(ka->out.dp_dv, ub, lo, ddv);
+        }
+        // barycentric tangents: the differentiable Moeller-Trumbore (default) or frozen (FollowShape)
+        float du = 0.f, dv = 0.f, dt = 0.f;
+        if (!follow) {
+            const v3 pvec = cross3(d, e2);
+            const float inv = rcp_ieee(dot3(e1, pvec));
+            const v3 tvec = o - P[0];
+            const v3 qvec = cross3(tvec, e1);
+            const float a_u = dot3(tvec, pvec), a_v = dot3(d, qvec), a_t = dot3(e2, qvec);
+            const v3 p1 = cross3(dD, e2), p2 = cross3(d, de2);
+            const v3 dpvec = mk3(p1.x + p2.x, p1.y + p2.y, p1.z + p2.z);
+            const v3 dtv = dO - dP[0];
+            const v3 q1 = cross3(dtv, e1), q2 = cross3(tvec, de1);
+            const v3 dqvec = mk3(q1.x + q2.x, q1.y + q2.y, q1.z + q2.z);
+            const float dinv = -(dot3(de1, pvec) + dot3(e1, dpvec)) * inv * inv;
+            du = (dot3(dtv, pvec) + dot3(tvec, dpvec)) * inv + a_u * dinv;
+            dv = (dot3(dD, qvec) + dot3(d, dqvec)) * inv + a_v * dinv;
+            dt = (dot3(de2, qvec) + dot3(e2, dqvec)) * inv + a_t * dinv;
+        }
+        // p = sum b_k P_k:  dp = du e1 + dv e2 + sum b_k dP_k
+        const v3 dp = mk3(du * e1.x + dv * e2.x + (b0 * dP[0].x + b1 * dP[1].x + b2 * dP[2].x),
+                          du * e1.y + dv * e2.y + (b0 * dP[0].y + b1 * dP[1].y + b2 * dP[2].y),
+                          du * e1.z + dv * e2.z + (b0 * dP[0].z + b1 * dP[1].z + b2 * dP[2].z));
+        if (follow) { // t = sqrt(|p - o|^2 / |d|^2)
+            const v3 p = mk3(__builtin_fmaf(P[0].x, b0, __builtin_fmaf(P[1].x, b1, P[2].x * b2)),
+                             __builtin_fmaf(P[0].y, b0, __builtin_fmaf(P[1].y, b1, P[2].y * b2)),
+                             __builtin_fmaf(P[0].z, b0, __builtin_fmaf(P[1].z, b1, P[2].z * b2)));
+            const v3 po = p - o;
+            const float dd = dot3(d, d), tt = __builtin_sqrtf(dot3(po, po) / dd);
+            dt = dot3(po, dp - dO) / (tt * dd) - (tt / dd) * dot3(d, dD);
+        }
+        st(ka->out.t, ub, lo, dt);
+        st3(ka->out.p, ub, lo, dp);
+        float duv0 = du, duv1 = dv;
+        if (flags & (0x2u | 0x4u)) {
+            duv0 = du * (U[1] - U[0]) + dv * (U[2] - U[0]);
+            duv1 = du * (V[1] - V[0]) + dv * (V[2] - V[0]);
+        }
+        st(ka->out.uv[0], ub, lo, duv0);
+        st(ka->out.uv[1], ub, lo, duv1);
+    }
+}
+
+void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
+                       const uint8_t *active, uint32_t flags, const float *dh, const float *const d_o[3],
+                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream) {
+    if (n == 0) return;
+    hf_tangent_args a;
+    a.f = f; a.n = n; a.rays = to_dev(rays);
+    a.pi.t = pi->t; a.pi.u = pi->prim_uv[0]; a.pi.v = pi->prim_uv[1]; a.pi.prim = pi->prim_index;
+    a.active = active; a.dh = dh; a.flags = flags;
+    bool raytan = false;
+    for (int k = 0; k < 3; ++k) {
+        a.d_o[k] = d_o ? d_o[k] : nullptr; a.d_d[k] = d_d ? d_d[k] : nullptr;
+        raytan = raytan || a.d_o[k] || a.d_d[k];
+    }
+    a.out.t = out->t; a.out.uv[0] = out->uv[0]; a.out.uv[1] = out->uv[1];
+    for (int k = 0; k < 3; ++k) {
+        a.out.p[k] = out->p[k]; a.out.n[k] = out->n[k]; a.out.sh_n[k] = out->sh_n[k];
+        a.out.dp_du[k] = out->dp_du[k]; a.out.dp_dv[k] = out->dp_dv[k];
+    }
+    const dim3 grid(grid_for(n, HF_SI_GRID_CAP)), block(HF_BLOCK);
+    if (raytan) hipLaunchKernelGGL(hf_tangent_kernel<true>, grid, block, 0, stream, a);
+    else        hipLaunchKernelGGL(hf_tangent_kernel<false>, grid, block, 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
 // Backward of the warped-area reparameterisation with respect to the heights, all auxiliary samples of a ray in ONE
 // pass (reparam.py:224-333 for the shape parameter): the weights of the samples and their sums Z, dZ (first loop,
 // :236-256), then for every auxiliary HIT the gradient of its V_direct = (si.p - o) / si.t through the FollowShape
@@ -2635,6 +2813,67 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_direct_adjoint_kernel(size_t n, u
     if (!POINT && L.grad_weight) L.grad_weight[i] = gw;
 }
 
+// Forward mode of hf_direct_kernel (the transpose of hf_direct_adjoint_kernel): the tangent of every sample's value for
+// tangents dsh_n (and dweight: directional lights; dp: point lights), reduced over the samples of a pixel as the primal
+// film is.  NULL tangent rows are zero.  Same masks and visibility as the primal (piecewise constant).
+//   directional: dc = w_k (wgt <dn, l> + co dweight)
+//   point:       dc = wgt w_k |v|^-2 (<dn, l> + |v|^-1 (3 co <l, dp> - <n, dp>)),  v = pos - p
+template <bool POINT>
+__global__ __launch_bounds__(HF_BLOCK) void hf_direct_tangent_kernel(size_t n, uint32_t spp, hf_f3ptr sn, hf_f3ptr dd,
+                                                                    const float *__restrict__ t, hf_f3ptr pp, hf_lights_dev L,
+                                                                    hf_f3ptr dsn, hf_f3ptr dpp, const float *__restrict__ dweight,
+                                                                    float *__restrict__ dimage) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const size_t npix = n / spp;
+    const bool in = i < n;
+    const size_t ii = in ? i : n - 1;
+    const v3 nn = mk3(sn.p[0][ii], sn.p[1][ii], sn.p[2][ii]);
+    const v3 d = mk3(dd.p[0][ii], dd.p[1][ii], dd.p[2][ii]);
+    const bool lit = in && (t[ii] != __builtin_inff()) && (-dot3(nn, d) > 0.f);
+    const v3 dn = dsn.p[0] ? mk3(dsn.p[0][ii], dsn.p[1][ii], dsn.p[2][ii]) : mk3(0.f, 0.f, 0.f);
+    const bool pow2 = (spp & (spp - 1u)) == 0u;
+    const uint32_t g = spp < 64u ? spp : 64u;
+    const float inv_spp = 1.0f / (float) spp;
+    const float wgt = L.weight ? L.weight[ii] : 1.f;
+    const float dwgt = (!POINT && dweight) ? dweight[ii] : 0.f;
+    v3 p = mk3(0.f, 0.f, 0.f), dq = mk3(0.f, 0.f, 0.f);
+    if (POINT) {
+        p = mk3(pp.p[0][ii], pp.p[1][ii], pp.p[2][ii]);
+        if (dpp.p[0]) dq = mk3(dpp.p[0][ii], dpp.p[1][ii], dpp.p[2][ii]);
+    }
+    for (uint32_t k = 0; k < L.n; ++k) {
+        v3 l = mk3(L.l[k][0], L.l[k][1], L.l[k][2]);
+        float wk = L.w[k], ir = 1.f;
+        if (POINT) {
+            const v3 v = l - p;
+            ir = 1.0f / __builtin_sqrtf(dot3(v, v));
+            l = v * ir;
+            wk = wk * (ir * ir);
+        }
+        const float co = dot3(nn, l);
+        float c = 0.f;
+        if (lit && co > 0.f && (L.vis[k] ? L.vis[k][ii] != 0 : true)) {
+            float s = dot3(dn, l);
+            if (POINT) s = __builtin_fmaf(ir, __builtin_fmaf(3.f * co, dot3(l, dq), -dot3(nn, dq)), s);
+            c = wk * __builtin_fmaf(wgt, s, co * dwgt);
+        }
+        if (pow2) { // the primal's butterfly over the lanes of a pixel (hf_direct_kernel)
+            if (g > 1u) c += HF_DPP_ADD(c, 0xB1);
+            if (g > 2u) c += HF_DPP_ADD(c, 0x4E);
+            if (g > 4u) c += HF_DPP_ADD(c, 0x141);
+            if (g > 8u) c += HF_DPP_ADD(c, 0x140);
+            if (g > 16u) c += __shfl_xor(c, 16);
+            if (g > 32u) c += __shfl_xor(c, 32);
+            if (in && (threadIdx.x & (g - 1u)) == 0u) {
+                if (spp <= 64u) dimage[k * npix + i / spp] = c * inv_spp;
+                else            atomicAdd(&dimage[k * npix + i / spp], c * inv_spp);
+            }
+        } else if (in) {
+            atomicAdd(&dimage[k * npix + i / spp], c * inv_spp);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // Gaussian reconstruction filter, splatted the way ImageBlock::put does (src/render/imageblock.cpp:258-330 with
 // src/rfilters/gaussian.cpp:48-101): a sample at film position pos adds  w_x(px) w_y(py) value  to every pixel
@@ -2723,6 +2962,28 @@ void hf_launch_direct_adjoint(size_t n, uint32_t spp, const float *const sh_n[3]
     } else {
         hipLaunchKernelGGL(hf_direct_adjoint_kernel<false>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t,
                            pp, lights, grad_image, gn, gp);
+    }
+}
+
+void hf_launch_direct_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                              const float *t, const float *const p[3], const hf_lights_dev &lights,
+                              const float *const dsh_n[3], const float *const dp[3], const float *dweight, float *dimage,
+                              hipStream_t stream) {
+    if (n == 0) return;
+    const bool pow2 = (spp & (spp - 1u)) == 0u;
+    if (!pow2 || spp > 64u) (void) hipMemsetAsync(dimage, 0, sizeof(float) * lights.n * (n / spp), stream); // atomic paths
+    hf_f3ptr sn = { { sh_n[0], sh_n[1], sh_n[2] } }, dd = { { d[0], d[1], d[2] } }, pp = { { nullptr, nullptr, nullptr } };
+    hf_f3ptr dsn = { { nullptr, nullptr, nullptr } }, dpp = { { nullptr, nullptr, nullptr } };
+    if (dsh_n) dsn = { { dsh_n[0], dsh_n[1], dsh_n[2] } };
+    if (dp) dpp = { { dp[0], dp[1], dp[2] } };
+    const size_t blocks = (n + HF_BLOCK - 1) / HF_BLOCK;
+    if (p) {
+        pp = { { p[0], p[1], p[2] } };
+        hipLaunchKernelGGL(hf_direct_tangent_kernel<true>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t,
+                           pp, lights, dsn, dpp, dweight, dimage);
+    } else {
+        hipLaunchKernelGGL(hf_direct_tangent_kernel<false>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t,
+                           pp, lights, dsn, dpp, dweight, dimage);
     }
 }
 

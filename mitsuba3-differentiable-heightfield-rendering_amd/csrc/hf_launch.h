@@ -20,6 +20,10 @@ void hf_launch_si(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const 
 void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, const hf_si_grad_t *gs, uint32_t flags, float *grad_h,
                        float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream);
+// forward mode of compute_si (hf_tangent): dh / d_o / d_d may be NULL (zero tangents)
+void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
+                       const uint8_t *active, uint32_t flags, const float *dh, const float *const d_o[3],
+                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream);
 // c1 = (float)(1 - beta1), c2 = (float)(1 - beta2): the differences are Python doubles in optimizers.py:279-280,
 // rounded once when they meet the float32 gradient
 hipError_t hf_launch_adam(size_t n, float *h, const float *g, float *m, float *v, float lr_t, float beta1, float beta2,
@@ -40,6 +44,11 @@ void hf_launch_direct(size_t n, uint32_t spp, const float *const sh_n[3], const 
 void hf_launch_direct_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                               const float *t, const float *const p[3], const hf_lights_dev &lights,
                               const float *grad_image, float *const grad_sh_n[3], float *const grad_p[3],
+                              hipStream_t stream);
+// forward mode of the two above: dsh_n, dp (point lights only), dweight (directional only) may be NULL (zero)
+void hf_launch_direct_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                              const float *t, const float *const p[3], const hf_lights_dev &lights,
+                              const float *const dsh_n[3], const float *const dp[3], const float *dweight, float *dimage,
                               hipStream_t stream);
 struct hf_splat_args {
     size_t n;

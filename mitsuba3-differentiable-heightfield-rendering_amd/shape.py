@@ -12,9 +12,10 @@ import enum
 import math
 
 import torch
+import torch.autograd.forward_ad as fwAD
 
 from . import _capi
-from ._capi import check, hf_desc_t, hf_pi_t, hf_rays_t, hf_si_grad_t, hf_si_t
+from ._capi import check, hf_desc_t, hf_pi_t, hf_rays_t, hf_si_grad_t, hf_si_t, hf_si_tangent_t
 
 
 class RayFlags(enum.IntFlag):
@@ -160,6 +161,11 @@ def _rows(buf, n):
     return [base + 4 * n * k for k in range(buf.shape[0])]
 
 
+def _has_tangent(x):
+    """a forward-mode AD tangent is attached to x (torch.autograd.forward_ad; False outside a dual level)"""
+    return isinstance(x, torch.Tensor) and fwAD.unpack_dual(x).tangent is not None
+
+
 def _fill(struct, layout, addrs):
     k = 0
     for name, c in layout:
@@ -174,14 +180,23 @@ def _fill(struct, layout, addrs):
 
 
 class _SurfaceInteractionOp(torch.autograd.Function):
-    """Differentiable SI block [18, n]; backward = hf_adjoint (atomic scatter of dL/dheight)."""
+    """Differentiable SI block [18, n]; backward = hf_adjoint (atomic scatter of dL/dheight), jvp = hf_tangent."""
 
     @staticmethod
     def forward(ctx, shape, heights, o, d, maxt, t, uv, prim, flags, active, diff_block):
         ctx.shape, ctx.flags, ctx.active = shape, flags, active
         ctx.save_for_backward(o, d, maxt, t, uv, prim)
+        ctx.save_for_forward(o, d, maxt, t, uv, prim)
         ctx.h_version = shape._heights_version
         return diff_block
+
+    @staticmethod
+    def jvp(ctx, _shape, dh, do, dd, *_):
+        shape = ctx.shape
+        o, d, maxt, t, uv, prim = ctx.saved_tensors
+        if ctx.h_version != shape._heights_version:
+            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
+        return shape._tangent_raw(o, d, maxt, t, uv, prim, ctx.flags, ctx.active, dh, do, dd)
 
     @staticmethod
     def backward(ctx, g):
@@ -472,7 +487,7 @@ class Heightfield:
         si.dp_du, si.dp_dv = diff[12:15], diff[15:18]
         si.boundary_test = aux[0] if (ray_flags & RayFlags.BoundaryTest) else torch.zeros(n, device=self.device)
         sh_s, sh_t, wi = aux[1:4], aux[4:7], aux[7:10]
-        if diff.requires_grad and (ray_flags & RayFlags.ShadingFrame):
+        if (diff.requires_grad or _has_tangent(diff)) and (ray_flags & RayFlags.ShadingFrame):
             # finalize_surface_interaction is AD-attached in the reference (interaction.h:257-267, 476-499):
             # sh_frame.s = normalize(dp_du - n <n, dp_du>), t = cross(n, s), wi = to_local(-d).  The kernel's rows are
             # plain outputs, so when gradients are wanted these three are rebuilt here from the differentiable rows
@@ -497,9 +512,13 @@ class Heightfield:
         return si
 
     def _wants_grad(self, ray, ray_flags):
+        detach = bool(ray_flags & RayFlags.DetachShape)
+        # forward mode (torch.autograd.forward_ad): a tangent on the heights or the rays, whatever the grad mode
+        if (_has_tangent(self.heightfield) and not detach) or _has_tangent(ray.o) or _has_tangent(ray.d):
+            return True
         if not torch.is_grad_enabled():
             return False
-        h_live = self.heightfield.requires_grad and not (ray_flags & RayFlags.DetachShape)
+        h_live = self.heightfield.requires_grad and not detach
         return bool(h_live or ray.o.requires_grad or ray.d.requires_grad)
 
     def compute_surface_interaction(self, ray, pi, ray_flags=RayFlags.All, recursion_depth=0, active=True):
@@ -564,6 +583,41 @@ class Heightfield:
                                           C.byref(go) if go is not None else None,
                                           C.byref(gd) if gd is not None else None,
                                           row_band.data_ptr() if row_band is not None else None, self._stream()))
+
+    # ---- tangent (forward mode) ------------------------------------------------------------------
+    def _tangent_raw(self, o, d, maxt, t, uv, prim, ray_flags, active_u8, dh, do, dd):
+        n = o.shape[1]
+        out = torch.empty((18, n), dtype=torch.float32, device=self.device)
+        ts = _fill(hf_si_tangent_t(), _DIFF_ROWS, _rows(out, n))
+        keep = []
+
+        def rows3(x):
+            if x is None:
+                return None
+            x, p = _f3(torch.as_tensor(x, device=self.device).detach().reshape(3, n))
+            keep.append(x)
+            return p
+        if dh is not None:
+            dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
+            assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
+        op, dp = rows3(do), rows3(dd)
+        rays = self._rays_struct(o, d, maxt)
+        pis = self._pi_struct(t, uv, prim)
+        check(_capi.lib().hf_tangent(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
+                                     active_u8.data_ptr() if active_u8 is not None else None,
+                                     dh.data_ptr() if dh is not None else None,
+                                     C.byref(op) if op is not None else None, C.byref(dp) if dp is not None else None,
+                                     C.byref(ts), self._stream()))
+        return out
+
+    def tangent(self, ray, pi, dheights=None, d_o=None, d_d=None, ray_flags=RayFlags.All, active=True):
+        """Explicit forward mode (``hf_tangent``), the mirror of ``adjoint``: the tangent [18, n] (t, p, n, uv,
+        sh_frame.n, dp_du, dp_dv) of the surface interaction for a perturbation ``dheights`` ([H, W]) of the heights
+        and ``d_o`` / ``d_d`` ([3, n]) of the rays; any of them may be None (zero).  Missed and inactive lanes: 0."""
+        self._check_ray(ray)
+        keep, _ = self._mask(active, len(ray))
+        return self._tangent_raw(ray.o.detach(), ray.d.detach(), ray.maxt, pi.t, pi.prim_uv, pi.prim_index, ray_flags, keep,
+                                 dheights, d_o, d_d)
 
     def new_row_band(self):
         """{height, 0} as int32[2] on the device: the initial value of hf_adjoint_rows' row band."""
@@ -672,8 +726,27 @@ class _DirectLightingOp(torch.autograd.Function):
                                                       ww.data_ptr() if ww is not None else None, K, L, albedo,
                                                       vis_p, image.data_ptr(), stream))
         ctx.save_for_backward(sn, dd, tt, *([ww] if ww is not None else []))
+        ctx.save_for_forward(sn, dd, tt, *([ww] if ww is not None else []))
         ctx.misc = (L, K, albedo, spp, vis, vis_p, ww is not None)
         return image
+
+    @staticmethod
+    def jvp(ctx, dsh_n, _dd, _dt, _dl, _da, _ds, _dv, dweight):
+        L, K, albedo, spp, vis, vis_p, weighted = ctx.misc
+        sn, dd, tt = ctx.saved_tensors[:3]
+        ww = ctx.saved_tensors[3] if weighted else None
+        n = sn.shape[1]
+        _, sn_p = _f3(sn)
+        _, dd_p = _f3(dd)
+        dn, dn_p = _f3(dsh_n) if dsh_n is not None else (None, None)
+        dw = dweight.to(dtype=torch.float32).contiguous() if (weighted and dweight is not None) else None
+        dimage = torch.empty((K, n // spp), dtype=torch.float32, device=sn.device)
+        stream = torch.cuda.current_stream(sn.device).cuda_stream
+        check(_capi.lib().hf_direct_lighting_weighted_tangent(
+            n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), ww.data_ptr() if weighted else None, K, L, albedo,
+            vis_p, C.byref(dn_p) if dn is not None else None, dw.data_ptr() if dw is not None else None,
+            dimage.data_ptr(), stream))
+        return dimage
 
     @staticmethod
     def backward(ctx, grad_image):
@@ -728,8 +801,26 @@ class _PointLightingOp(torch.autograd.Function):
         check(_capi.lib().hf_point_lighting(n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), C.byref(pp_p), K, L,
                                             albedo, vis_p, image.data_ptr(), stream))
         ctx.save_for_backward(sn, pp, dd, tt)
+        ctx.save_for_forward(sn, pp, dd, tt)
         ctx.misc = (L, K, albedo, spp, vis, vis_p)
         return image
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dp, *_):
+        sn, pp, dd, tt = ctx.saved_tensors
+        L, K, albedo, spp, vis, vis_p = ctx.misc
+        n = sn.shape[1]
+        _, sn_p = _f3(sn)
+        _, pp_p = _f3(pp)
+        _, dd_p = _f3(dd)
+        dn, dn_p = _f3(dsh_n) if dsh_n is not None else (None, None)
+        dq, dq_p = _f3(dp) if dp is not None else (None, None)
+        dimage = torch.empty((K, n // spp), dtype=torch.float32, device=sn.device)
+        stream = torch.cuda.current_stream(sn.device).cuda_stream
+        check(_capi.lib().hf_point_lighting_tangent(n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), C.byref(pp_p), K,
+                                                    L, albedo, vis_p, C.byref(dn_p) if dn is not None else None,
+                                                    C.byref(dq_p) if dq is not None else None, dimage.data_ptr(), stream))
+        return dimage
 
     @staticmethod
     def backward(ctx, grad_image):
@@ -769,7 +860,24 @@ class _FilmGaussianOp(torch.autograd.Function):
         check(_capi.lib().hf_film_splat(n, K, vp, ps[0].data_ptr(), ps[1].data_ptr(), width, height, stddev,
                                         image.data_ptr(), weight.data_ptr(), stream))
         ctx.save_for_backward(ps, weight)
+        ctx.save_for_forward(ps, weight)
         ctx.misc = (K, n, width, height, stddev)
+        covered = weight > 0
+        return torch.where(covered[None], image / torch.where(covered, weight, torch.ones_like(weight))[None],
+                           torch.zeros_like(image))
+
+    @staticmethod
+    def jvp(ctx, dvalues, *_):
+        # the film is linear in the values: its tangent is the splat of the tangent values over the primal weights
+        ps, weight = ctx.saved_tensors
+        K, n, width, height, stddev = ctx.misc
+        dv = dvalues.to(dtype=torch.float32).contiguous()
+        image = torch.zeros((K, height * width), dtype=torch.float32, device=ps.device)
+        wscratch = torch.zeros(height * width, dtype=torch.float32, device=ps.device)
+        vp = (C.c_void_p * K)(*[dv[k].data_ptr() for k in range(K)])
+        stream = torch.cuda.current_stream(ps.device).cuda_stream
+        check(_capi.lib().hf_film_splat(n, K, vp, ps[0].data_ptr(), ps[1].data_ptr(), width, height, stddev,
+                                        image.data_ptr(), wscratch.data_ptr(), stream))
         covered = weight > 0
         return torch.where(covered[None], image / torch.where(covered, weight, torch.ones_like(weight))[None],
                            torch.zeros_like(image))
