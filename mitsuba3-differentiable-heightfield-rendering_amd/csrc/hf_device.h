@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/hf.h" // HF_RAY_* flag bits
 
 #define HF_MAX_LEVELS 24
 
@@ -247,21 +248,88 @@ __device__ __forceinline__ float boundary_test_flat(v3 p, v3 p0, v3 dp0, v3 dp1,
     return dist;
 }
 
-// world-space vertices + texcoords of a primitive
+// ---- Hit geometry: the quantities that compute_si_to, its adjoint (hf_adjoint_kernel), its tangent
+// (hf_tangent_kernel) and hf_reparam_backward_kernel share, each written once.  Every call site gets exactly the
+// operations it had inline (same order, same fmas), so the results are bit for bit those of the inline forms. ----
+
+// World-space vertices + texcoords of a primitive.  With dP: also the vertices' tangents dP_k = dh_k s (third column
+// of to_world) for the height tangent dh (nullptr: zero).  No load depends on another: the three heights and the
+// three height tangents go out as one batch.
 __device__ __forceinline__ void prim_world(const hf_dev_field &f, uint32_t prim, v3 P[3], float U[3], float V[3],
-                                           int vi[3], int vj[3]) {
+                                           int vi[3], int vj[3], v3 *dP = nullptr, const float *dh = nullptr) {
     prim_vertex_ids(f, prim, vi, vj);
+    const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s); // dP_k/dh_k
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const v3 q = mk3(__builtin_fmaf((float) vj[k], f.sx, -1.0f), __builtin_fmaf((float) vi[k], f.sy, -1.0f),
-                         f.h[(size_t) vi[k] * f.W + vj[k]] * f.s);
+        const size_t idx = (size_t) vi[k] * f.W + vj[k];
+        const float dz = dh ? dh[idx] : 0.f;
+        const v3 q = mk3(__builtin_fmaf((float) vj[k], f.sx, -1.0f), __builtin_fmaf((float) vi[k], f.sy, -1.0f), f.h[idx] * f.s);
         P[k] = xform_point(f.to_world, q);
         U[k] = (float) vj[k] * f.iu;
         V[k] = (float) vi[k] * f.iv;
+        if (dP) dP[k] = ez * dz;
     }
 }
 
-// Shape::compute_surface_interaction + finalize_surface_interaction for one valid hit.
+// p = sum_k b_k P_k
+__device__ __forceinline__ v3 bary_point(const v3 P[3], float b0, float b1, float b2) {
+    return mk3(__builtin_fmaf(P[0].x, b0, __builtin_fmaf(P[1].x, b1, P[2].x * b2)),
+               __builtin_fmaf(P[0].y, b0, __builtin_fmaf(P[1].y, b1, P[2].y * b2)),
+               __builtin_fmaf(P[0].z, b0, __builtin_fmaf(P[1].z, b1, P[2].z * b2)));
+}
+
+// FollowShape: t re-derived from the glued point p, tt = sqrt(|p - o|^2 / |d|^2) (mesh.cpp:748-752)
+struct hf_follow {
+    v3 po;    // p - o
+    float dd; // |d|^2
+    float tt;
+};
+__device__ __forceinline__ hf_follow follow_t(v3 p, v3 o, v3 d) {
+    const v3 po = p - o;
+    const float tt = __builtin_sqrtf(dot3(po, po) / dot3(d, d));
+    return hf_follow{ po, dot3(d, d), tt }; // (|d|^2 is computed once: the second dot3(d, d) is the same value)
+}
+
+// texcoord differences of the triangle and the inverse determinant of their 2x2 matrix (dp_du / dp_dv); inv_det is
+// only meaningful when det != 0
+struct hf_uv_diff {
+    float du0, dv0, du1, dv1, det, inv_det;
+};
+__device__ __forceinline__ hf_uv_diff uv_diff(const float U[3], const float V[3]) {
+    const float du0 = U[1] - U[0], dv0 = V[1] - V[0], du1 = U[2] - U[0], dv1 = V[2] - V[0];
+    const float det = __builtin_fmaf(du0, dv1, -(dv0 * du1));
+    return hf_uv_diff{ du0, dv0, du1, dv1, det, rcp_ieee(det) };
+}
+
+// unit normal of edges e1, e2: n = N r with N = cross(e1, e2), r = 1 / |N|
+struct hf_unit_normal {
+    v3 n;
+    float r;
+};
+__device__ __forceinline__ hf_unit_normal unit_normal(v3 e1, v3 e2) {
+    const v3 N = cross3(e1, e2);
+    const float r = rsqrt_ieee(dot3(N, N));
+    return hf_unit_normal{ N * r, r };
+}
+
+// intermediates of the differentiable Moeller-Trumbore (mesh.h:357-380) for vertex p0 and edges e1, e2:
+// u = a_u inv, v = a_v inv, t = a_t inv
+struct hf_mt {
+    v3 pvec, tvec, qvec;
+    float inv, a_u, a_v, a_t;
+};
+__device__ __forceinline__ hf_mt mt_terms(v3 o, v3 d, v3 p0, v3 e1, v3 e2) {
+    hf_mt m;
+    m.pvec = cross3(d, e2);
+    m.inv = rcp_ieee(dot3(e1, m.pvec));
+    m.tvec = o - p0;
+    m.qvec = cross3(m.tvec, e1);
+    m.a_u = dot3(m.tvec, m.pvec); m.a_v = dot3(d, m.qvec); m.a_t = dot3(e2, m.qvec);
+    return m;
+}
+
+// Shape::compute_surface_interaction + finalize_surface_interaction for one valid hit, from the hit-geometry helpers
+// above (hf_adjoint_kernel and hf_tangent_kernel differentiate the same quantities).
 // The fields are handed to `out` as soon as they are final (out.t(..), out.p(..), ...): the record sink below collects
 // them into an hf_si_rec; the fused traversal kernel stores each one straight away, so that the whole record is
 // never live in registers at once.
@@ -274,40 +342,33 @@ __device__ __forceinline__ void compute_si_to(const hf_dev_field &f, v3 o, v3 d,
     prim_world(f, prim, P, U, V, vi, vj);
     const float b0 = 1.f - b1 - b2;
     const v3 dp0 = P[1] - P[0], dp1 = P[2] - P[0];
-    const v3 p = mk3(__builtin_fmaf(P[0].x, b0, __builtin_fmaf(P[1].x, b1, P[2].x * b2)),
-                     __builtin_fmaf(P[0].y, b0, __builtin_fmaf(P[1].y, b1, P[2].y * b2)),
-                     __builtin_fmaf(P[0].z, b0, __builtin_fmaf(P[1].z, b1, P[2].z * b2)));
+    const v3 p = bary_point(P, b0, b1, b2);
     float t = t_in;
-    if (flags & 0x80u) { // FollowShape: t re-derived from the glued point (mesh.cpp:748-752)
-        const v3 po = p - o;
-        t = __builtin_sqrtf(dot3(po, po) / dot3(d, d));
-    }
+    if (flags & HF_RAY_FOLLOWSHAPE) t = follow_t(p, o, d).tt;
     out.t(t);
     out.p(p);
-    if (flags & 0x40u)
-        // 0x10000 (HF_RAY_BOUNDARY_ALL_EDGES, a libhf extension bit): the reference Mesh's per-triangle SDF over all
+    if (flags & HF_RAY_BOUNDARYTEST)
+        // HF_RAY_BOUNDARY_ALL_EDGES (a libhf extension bit): the reference Mesh's per-triangle SDF over all
         // three edges (mesh.cpp:845-890, values in [0, 1]) instead of the silhouette edges only
-        out.boundary_test(boundary_test_flat(p, P[0], dp0, dp1, (flags & 0x10000u) ? 7u : silhouette_edges(f, prim, xform_vec(f.to_object, d))));
+        out.boundary_test(boundary_test_flat(p, P[0], dp0, dp1, (flags & HF_RAY_BOUNDARY_ALL_EDGES) ? 7u : silhouette_edges(f, prim, xform_vec(f.to_object, d))));
     else
         out.boundary_test(0.f);
-    v3 n = normalize3(cross3(dp0, dp1));
+    v3 n = unit_normal(dp0, dp1).n;
     float uv0 = b1, uv1 = b2;
     v3 dp_du, dp_dv;
     coordinate_system(n, dp_du, dp_dv);
-    if (flags & (0x2u | 0x4u)) {
+    if (flags & (HF_RAY_UV | HF_RAY_DPDUV)) {
         uv0 = __builtin_fmaf(U[2], b2, __builtin_fmaf(U[1], b1, U[0] * b0));
         uv1 = __builtin_fmaf(V[2], b2, __builtin_fmaf(V[1], b1, V[0] * b0));
-        if (flags & 0x4u) {
-            const float du0 = U[1] - U[0], dv0 = V[1] - V[0], du1 = U[2] - U[0], dv1 = V[2] - V[0];
-            const float det = __builtin_fmaf(du0, dv1, -(dv0 * du1));
-            const float inv_det = rcp_ieee(det);
-            if (det != 0.f) {
-                dp_du = mk3(__builtin_fmaf(dv1, dp0.x, -(dv0 * dp1.x)) * inv_det,
-                            __builtin_fmaf(dv1, dp0.y, -(dv0 * dp1.y)) * inv_det,
-                            __builtin_fmaf(dv1, dp0.z, -(dv0 * dp1.z)) * inv_det);
-                dp_dv = mk3(__builtin_fmaf(-du1, dp0.x, du0 * dp1.x) * inv_det,
-                            __builtin_fmaf(-du1, dp0.y, du0 * dp1.y) * inv_det,
-                            __builtin_fmaf(-du1, dp0.z, du0 * dp1.z) * inv_det);
+        if (flags & HF_RAY_DPDUV) {
+            const hf_uv_diff g = uv_diff(U, V);
+            if (g.det != 0.f) {
+                dp_du = mk3(__builtin_fmaf(g.dv1, dp0.x, -(g.dv0 * dp1.x)) * g.inv_det,
+                            __builtin_fmaf(g.dv1, dp0.y, -(g.dv0 * dp1.y)) * g.inv_det,
+                            __builtin_fmaf(g.dv1, dp0.z, -(g.dv0 * dp1.z)) * g.inv_det);
+                dp_dv = mk3(__builtin_fmaf(-g.du1, dp0.x, g.du0 * dp1.x) * g.inv_det,
+                            __builtin_fmaf(-g.du1, dp0.y, g.du0 * dp1.y) * g.inv_det,
+                            __builtin_fmaf(-g.du1, dp0.z, g.du0 * dp1.z) * g.inv_det);
             }
         }
     }
@@ -316,7 +377,7 @@ __device__ __forceinline__ void compute_si_to(const hf_dev_field &f, v3 o, v3 d,
     if (f.flip) n = neg3(n);
     out.n(n); // n and sh_n
     v3 sh_s = mk3(0.f, 0.f, 0.f), sh_t = mk3(0.f, 0.f, 0.f);
-    if (flags & 0x8u) { // initialize_sh_frame: Gram-Schmidt on dp_du
+    if (flags & HF_RAY_SHADINGFRAME) { // initialize_sh_frame: Gram-Schmidt on dp_du
         const float nd = -dot3(n, dp_du);
         sh_s = normalize3(fma3(n, nd, dp_du));
         if (dp_du.x == 0.f && dp_du.y == 0.f && dp_du.z == 0.f) {
@@ -330,6 +391,16 @@ __device__ __forceinline__ void compute_si_to(const hf_dev_field &f, v3 o, v3 d,
     out.sh_t(sh_t);
     const v3 md = neg3(d);
     out.wi(mk3(dot3(md, sh_s), dot3(md, sh_t), dot3(md, n)));
+}
+
+// The zero-initialised record of a missed or inactive lane (interaction.h:479-499, 667-673), in compute_si_to's field
+// order, up to wi: a caller that stores wi (= -d) does so itself, after this (passed in here, the negation moved within
+// the fused traversal kernel's schedule).
+template <typename Out>
+__device__ __forceinline__ void si_miss_to(Out &out, uint32_t flags) {
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    out.t(__builtin_inff()); out.p(z); out.boundary_test((flags & HF_RAY_BOUNDARYTEST) ? 1e8f : 0.f);
+    out.uv(0.f, 0.f); out.dp_dv(z); out.n(z); out.dp_du(z); out.sh_s(z); out.sh_t(z);
 }
 
 struct hf_si_rec_sink {

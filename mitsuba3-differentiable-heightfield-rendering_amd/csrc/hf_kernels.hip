@@ -1367,7 +1367,7 @@ struct hf_si_store_sink {
     __device__ __forceinline__ void s3(float *p0, float *p1, float *p2, v3 v) { st(p0, ub, lo, v.x); st(p1, ub, lo, v.y); st(p2, ub, lo, v.z); }
     __device__ __forceinline__ void t(float v) { s1(ka->sio.t, v); }
     __device__ __forceinline__ void p(v3 v) { s3(ka->sio.p[0], ka->sio.p[1], ka->sio.p[2], v); }
-    __device__ __forceinline__ void boundary_test(float v) { if (flags & 0x40u) s1(ka->sio.bt, v); }
+    __device__ __forceinline__ void boundary_test(float v) { if (flags & HF_RAY_BOUNDARYTEST) s1(ka->sio.bt, v); }
     __device__ __forceinline__ void uv(float a, float b) { s1(ka->sio.uv[0], a); s1(ka->sio.uv[1], b); }
     __device__ __forceinline__ void dp_du(v3 v) { s3(ka->sio.dp_du[0], ka->sio.dp_du[1], ka->sio.dp_du[2], v); }
     __device__ __forceinline__ void dp_dv(v3 v) { s3(ka->sio.dp_dv[0], ka->sio.dp_dv[1], ka->sio.dp_dv[2], v); }
@@ -1531,7 +1531,7 @@ void hf_trace_kernel(hf_trace_args a) {
                                     st4(sd.sh_s[c], ubw, l4, zero); st4(sd.sh_t[c], ubw, l4, zero);
                                 }
                                 st4(sd.uv[0], ubw, l4, zero); st4(sd.uv[1], ubw, l4, zero);
-                                if (flags & 0x40u) { const float b0 = z0 + 1e8f; const f4 big = { b0, b0, b0, b0 }; st4(sd.bt, ubw, l4, big); }
+                                if (flags & HF_RAY_BOUNDARYTEST) { const float b0 = z0 + 1e8f; const f4 big = { b0, b0, b0, b0 }; st4(sd.bt, ubw, l4, big); }
                                 st4(sd.wi[0], ubw, l4, -dx); st4(sd.wi[1], ubw, l4, -dy); st4(sd.wi[2], ubw, l4, -dz);
                             }
                         }
@@ -1594,9 +1594,7 @@ void hf_trace_kernel(hf_trace_args a) {
                                     if (pi.v) (pi.v + ubo)[lo] = 0.f;
                                     if (pi.prim) (pi.prim + ubo)[lo] = 0u;
                                     hf_si_store_sink out = { ka, ubo, lo, flags };
-                                    const v3 z = mk3(0.f, 0.f, 0.f); // (the launcher culls only when si.wi -- minus the sample's direction -- is not asked for)
-                                    out.t(__builtin_inff()); out.p(z); out.boundary_test((flags & 0x40u) ? 1e8f : 0.f);
-                                    out.uv(0.f, 0.f); out.dp_dv(z); out.n(z); out.dp_du(z); out.sh_s(z); out.sh_t(z);
+                                    si_miss_to(out, flags); // (the launcher culls only when si.wi -- minus the sample's direction -- is not asked for)
                                 }
                             }
                         }
@@ -1714,10 +1712,8 @@ void hf_trace_kernel(hf_trace_args a) {
                         const hf_dev_field fl = load_field(&ka->f); // to_world etc.: not held across the walk
                         // every field is stored as soon as it is final: the record is never whole in registers
                         compute_si_to(fl, ow, dw, best.t, best.u, best.v, best.prim, flags, out);
-                    } else { // zero-initialised record (interaction.h:479-499, 667-673)
-                        const v3 z = mk3(0.f, 0.f, 0.f);
-                        out.t(__builtin_inff()); out.p(z); out.boundary_test((flags & 0x40u) ? 1e8f : 0.f);
-                        out.uv(0.f, 0.f); out.dp_dv(z); out.n(z); out.dp_du(z); out.sh_s(z); out.sh_t(z);
+                    } else {
+                        si_miss_to(out, flags);
                         out.wi(neg3(dw));
                     }
                 }
@@ -1874,18 +1870,13 @@ void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t 
 // ---------------------------------------------------------------------------------
 // surface interaction from (ray, pi)
 // ---------------------------------------------------------------------------------
-struct hf_pi_cdev {
-    const float *t, *u, *v;
-    const uint32_t *prim;
-};
-
 // The one kernel argument, read from the kernarg segment where it is used (as in the traversal kernel: ~45 pointers and
 // the field by value held across the loop body were spilled into vector-register lanes: 134 SGPR spills).
 struct hf_si_args {
     hf_dev_field f;
     size_t n;
     hf_rays_dev rays;
-    hf_pi_cdev pi;
+    hf_pi_const_t pi;
     const uint8_t *active;
     hf_si_dev sio;
     uint32_t flags;
@@ -1899,7 +1890,7 @@ struct hf_si_kernel_sink {
     __device__ __forceinline__ void s3(float *p0, float *p1, float *p2, v3 v) { st(p0, ub, lo, v.x); st(p1, ub, lo, v.y); st(p2, ub, lo, v.z); }
     __device__ __forceinline__ void t(float v) { s1(ka->sio.t, v); }
     __device__ __forceinline__ void p(v3 v) { s3(ka->sio.p[0], ka->sio.p[1], ka->sio.p[2], v); }
-    __device__ __forceinline__ void boundary_test(float v) { if (flags & 0x40u) s1(ka->sio.bt, v); }
+    __device__ __forceinline__ void boundary_test(float v) { if (flags & HF_RAY_BOUNDARYTEST) s1(ka->sio.bt, v); }
     __device__ __forceinline__ void uv(float a, float b) { s1(ka->sio.uv[0], a); s1(ka->sio.uv[1], b); }
     __device__ __forceinline__ void dp_du(v3 v) { s3(ka->sio.dp_du[0], ka->sio.dp_du[1], ka->sio.dp_du[2], v); }
     __device__ __forceinline__ void dp_dv(v3 v) { s3(ka->sio.dp_dv[0], ka->sio.dp_dv[1], ka->sio.dp_dv[2], v); }
@@ -1932,14 +1923,12 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_si_kernel(hf_si_args a_) {
         const uint32_t flags = ka->flags;
         hf_si_kernel_sink out = { ka, ub, lo, flags };
         if (act) {
-            const float b1 = (ka->pi.u + ub)[lo], b2 = (ka->pi.v + ub)[lo];
-            const uint32_t prim = (ka->pi.prim + ub)[lo];
+            const float b1 = (ka->pi.prim_uv[0] + ub)[lo], b2 = (ka->pi.prim_uv[1] + ub)[lo];
+            const uint32_t prim = (ka->pi.prim_index + ub)[lo];
             const hf_dev_field f = load_field(&ka->f);
             compute_si_to(f, o, d, t, b1, b2, prim, flags, out);
-        } else { // zero-initialised record (interaction.h:479-499, 667-673)
-            const v3 z = mk3(0.f, 0.f, 0.f);
-            out.t(__builtin_inff()); out.p(z); out.boundary_test((flags & 0x40u) ? 1e8f : 0.f);
-            out.uv(0.f, 0.f); out.dp_dv(z); out.n(z); out.dp_du(z); out.sh_s(z); out.sh_t(z);
+        } else {
+            si_miss_to(out, flags);
             out.wi(neg3(d));
         }
     }
@@ -1949,14 +1938,13 @@ void hf_launch_si(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const 
                   const uint8_t *active, const hf_si_t *si, uint32_t flags, hipStream_t stream) {
     if (n == 0) return;
     hf_si_args a;
-    a.f = f; a.n = n; a.rays = to_dev(rays);
-    a.pi.t = pi->t; a.pi.u = pi->prim_uv[0]; a.pi.v = pi->prim_uv[1]; a.pi.prim = pi->prim_index;
-    a.active = active; a.sio = to_dev(si); a.flags = flags;
+    a.f = f; a.n = n; a.rays = to_dev(rays); a.pi = *pi; a.active = active; a.sio = to_dev(si); a.flags = flags;
     hipLaunchKernelGGL(hf_si_kernel, dim3(grid_for(n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------
-// adjoint: reverse mode of compute_si, atomic scatter of dL/dheight
+// adjoint: reverse mode of compute_si, atomic scatter of dL/dheight.  The reverse sweep over compute_si_to's hit-geometry
+// quantities (hf_device.h: prim_world, bary_point, uv_diff, unit_normal, follow_t, mt_terms)
 // ---------------------------------------------------------------------------------
 #define HF_ADJ_TILE 32 // texels per side of the per-wave LDS accumulation tile
 
@@ -2000,12 +1988,6 @@ __device__ __forceinline__ v3 reparam_grad_vdirect(const hf_reparam_args &a, siz
                __builtin_fmaf(w, gV.z, gdivV * dw.z));
 }
 
-struct hf_grad_dev {
-    const float *t, *p[3], *n[3], *uv[2], *sh_n[3], *dp_du[3], *dp_dv[3];
-};
-__device__ __forceinline__ float ld(const float *p, size_t i) { return p ? p[i] : 0.f; }
-__device__ __forceinline__ v3 ld3(const float *const p[3], size_t i) { return mk3(ld(p[0], i), ld(p[1], i), ld(p[2], i)); }
-
 // The one kernel argument.  ~45 pointers and the field by value do not fit the scalar register file: held across the
 // loop body they were spilled into vector-register lanes (108 SGPR spills, 342 v_readlane / v_writelane).  As in the
 // traversal kernel, everything is read from the kernarg segment where it is used (scalar loads that hit the constant
@@ -2014,9 +1996,9 @@ struct hf_adjoint_args {
     hf_dev_field f;
     size_t n;
     hf_rays_dev rays;
-    hf_pi_cdev pi;
+    hf_pi_const_t pi;
     const uint8_t *active;
-    hf_grad_dev g;
+    hf_si_grad_t g;
     uint32_t flags;
     float *grad_h;
     float *go[3], *gd[3];
@@ -2057,8 +2039,8 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
         const uint8_t *active = ka->active;
         const bool act = valid && (active ? ((active + ub)[lo] != 0) : true) && (t_in != __builtin_inff());
         const uint32_t flags = ka->flags;
-        const bool follow = (flags & 0x80u) != 0, detach = (flags & 0x100u) != 0;
-        const bool tex = (flags & (0x2u | 0x4u)) != 0;
+        const bool follow = (flags & HF_RAY_FOLLOWSHAPE) != 0, detach = (flags & HF_RAY_DETACHSHAPE) != 0;
+        const bool tex = (flags & (HF_RAY_UV | HF_RAY_DPDUV)) != 0;
         v3 go = mk3(0.f, 0.f, 0.f), gd = mk3(0.f, 0.f, 0.f);
         float gh[3] = { 0.f, 0.f, 0.f };
         int vr[3] = { 0, 0, 0 }, vc[3] = { 0, 0, 0 };
@@ -2069,15 +2051,15 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
             // trips per iteration (pi.t, this batch, the heights) where the loads used to trail the arithmetic (six).
             const v3 o = mk3((ka->rays.o[0] + ub)[lo], (ka->rays.o[1] + ub)[lo], (ka->rays.o[2] + ub)[lo]);
             const v3 d = mk3((ka->rays.d[0] + ub)[lo], (ka->rays.d[1] + ub)[lo], (ka->rays.d[2] + ub)[lo]);
-            const float b1 = (ka->pi.u + ub)[lo], b2 = (ka->pi.v + ub)[lo], b0 = 1.f - b1 - b2;
-            const uint32_t prim = (ka->pi.prim + ub)[lo];
+            const float b1 = (ka->pi.prim_uv[0] + ub)[lo], b2 = (ka->pi.prim_uv[1] + ub)[lo], b0 = 1.f - b1 - b2;
+            const uint32_t prim = (ka->pi.prim_index + ub)[lo];
             const float gt = ldu(ka->g.t, ub, lo);
             v3 gp = mk3(ldu(ka->g.p[0], ub, lo), ldu(ka->g.p[1], ub, lo), ldu(ka->g.p[2], ub, lo));
             const v3 gn_a = mk3(ldu(ka->g.n[0], ub, lo), ldu(ka->g.n[1], ub, lo), ldu(ka->g.n[2], ub, lo));
             const v3 gn_b = mk3(ldu(ka->g.sh_n[0], ub, lo), ldu(ka->g.sh_n[1], ub, lo), ldu(ka->g.sh_n[2], ub, lo));
             const float guv0 = ldu(ka->g.uv[0], ub, lo), guv1 = ldu(ka->g.uv[1], ub, lo);
             v3 gu_ = mk3(0.f, 0.f, 0.f), gv_ = gu_;
-            if (flags & 0x4u) {
+            if (flags & HF_RAY_DPDUV) {
                 gu_ = mk3(ldu(ka->g.dp_du[0], ub, lo), ldu(ka->g.dp_du[1], ub, lo), ldu(ka->g.dp_du[2], ub, lo));
                 gv_ = mk3(ldu(ka->g.dp_dv[0], ub, lo), ldu(ka->g.dp_dv[1], ub, lo), ldu(ka->g.dp_dv[2], ub, lo));
             }
@@ -2087,17 +2069,13 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
             int vi[3], vj[3];
             prim_world(f, prim, P, U, V, vi, vj);
             const v3 dp0 = P[1] - P[0], dp1 = P[2] - P[0];
-            const v3 p = mk3(__builtin_fmaf(P[0].x, b0, __builtin_fmaf(P[1].x, b1, P[2].x * b2)),
-                             __builtin_fmaf(P[0].y, b0, __builtin_fmaf(P[1].y, b1, P[2].y * b2)),
-                             __builtin_fmaf(P[0].z, b0, __builtin_fmaf(P[1].z, b1, P[2].z * b2)));
+            const v3 p = bary_point(P, b0, b1, b2);
             const v3 z3 = mk3(0.f, 0.f, 0.f);
             v3 gP0 = z3, gP1 = z3, gP2 = z3, gdp0 = z3, gdp1 = z3;
 
             // dp_du / dp_dv from the (constant) texcoord differences
-            if (flags & 0x4u) {
-                const float du0 = U[1] - U[0], dv0 = V[1] - V[0], du1 = U[2] - U[0], dv1 = V[2] - V[0];
-                const float det = __builtin_fmaf(du0, dv1, -(dv0 * du1));
-                const float inv_det = rcp_ieee(det);
+            if (flags & HF_RAY_DPDUV) {
+                const auto [du0, dv0, du1, dv1, det, inv_det] = uv_diff(U, V);
                 if (det != 0.f) {
                     axpy3(dv1 * inv_det, gu_, gdp0);
                     axpy3(-dv0 * inv_det, gu_, gdp1);
@@ -2107,9 +2085,7 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
             }
             // n = sh_n = +-normalize(cross(dp0, dp1))
             {
-                const v3 N = cross3(dp0, dp1);
-                const float r = rsqrt_ieee(dot3(N, N));
-                const v3 nn = N * r;
+                const auto [nn, r] = unit_normal(dp0, dp1);
                 const float sgn = f.flip ? -1.f : 1.f;
                 const v3 gn = mk3(sgn * (gn_a.x + gn_b.x), sgn * (gn_a.y + gn_b.y), sgn * (gn_a.z + gn_b.z));
                 const float proj = dot3(nn, gn);
@@ -2119,8 +2095,7 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
             }
             // FollowShape: t = sqrt(|p-o|^2/|d|^2) feeds p, o, d
             if (follow) {
-                const v3 po = p - o;
-                const float dd = dot3(d, d), tt = __builtin_sqrtf(dot3(po, po) / dd);
+                const auto [po, dd, tt] = follow_t(p, o, d);
                 const float c = gt / (tt * dd);
                 axpy3(c, po, gp);
                 axpy3(-c, po, go);
@@ -2139,11 +2114,7 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
 
             if (!follow) { // reverse of the differentiable Moeller-Trumbore (t_d, prim_uv_d)
                 const v3 e1 = dp0, e2 = dp1;
-                const v3 pvec = cross3(d, e2);
-                const float det = dot3(e1, pvec), inv = rcp_ieee(det);
-                const v3 tvec = o - P[0];
-                const v3 qvec = cross3(tvec, e1);
-                const float a_u = dot3(tvec, pvec), a_v = dot3(d, qvec), a_t = dot3(e2, qvec);
+                const auto [pvec, tvec, qvec, inv, a_u, a_v, a_t] = mt_terms(o, d, P[0], e1, e2);
                 const float g_au = gu * inv, g_av = gv * inv, g_at = gt * inv;
                 const float g_inv = gu * a_u + gv * a_v + gt * a_t;
                 const float g_det = -g_inv * inv * inv;
@@ -2231,16 +2202,8 @@ void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
                        const uint8_t *active, const hf_si_grad_t *gs, uint32_t flags, float *grad_h,
                        float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream) {
     if (n == 0) return;
-    const hf_pi_cdev p = { pi->t, pi->prim_uv[0], pi->prim_uv[1], pi->prim_index };
-    hf_grad_dev g;
-    g.t = gs->t;
-    for (int k = 0; k < 3; ++k) {
-        g.p[k] = gs->p[k]; g.n[k] = gs->n[k]; g.sh_n[k] = gs->sh_n[k];
-        g.dp_du[k] = gs->dp_du[k]; g.dp_dv[k] = gs->dp_dv[k];
-    }
-    g.uv[0] = gs->uv[0]; g.uv[1] = gs->uv[1];
     hf_adjoint_args a;
-    a.f = f; a.n = n; a.rays = to_dev(rays); a.pi = p; a.active = active; a.g = g; a.flags = flags; a.grad_h = grad_h;
+    a.f = f; a.n = n; a.rays = to_dev(rays); a.pi = *pi; a.active = active; a.g = *gs; a.flags = flags; a.grad_h = grad_h;
     a.row_band = row_band;
     for (int k = 0; k < 3; ++k) { a.go[k] = grad_o ? grad_o[k] : nullptr; a.gd[k] = grad_d ? grad_d[k] : nullptr; }
     if (grad_o || grad_d) hipLaunchKernelGGL(hf_adjoint_kernel<true>, dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a);
@@ -2248,24 +2211,22 @@ void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
 }
 
 // ---------------------------------------------------------------------------------
-// tangent: forward mode of compute_si (the transpose of hf_adjoint_kernel, term for term), no scatter
+// tangent: forward mode of compute_si (the transpose of hf_adjoint_kernel, term for term), no scatter.  The forward
+// sweep over the same hit-geometry quantities; prim_world also yields the vertex tangents dP_k
 // ---------------------------------------------------------------------------------
 // Shaped like hf_si_kernel (one block per 256 rays, arguments from the kernarg segment where they are used, every row
 // stored as soon as it is final): a hit lane issues one batch of independent loads (the rest of pi, o, d and the ray
 // tangents), then one round trip for the three heights and three height tangents of its triangle.  A missed lane reads
 // pi.t (and active) and stores zeros.
-struct hf_tan_dev {
-    float *t, *p[3], *n[3], *uv[2], *sh_n[3], *dp_du[3], *dp_dv[3];
-};
 struct hf_tangent_args {
     hf_dev_field f;
     size_t n;
     hf_rays_dev rays;
-    hf_pi_cdev pi;
+    hf_pi_const_t pi;
     const uint8_t *active;
     const float *dh;            // [H*W] height tangent, NULL = zero
     const float *d_o[3], *d_d[3]; // per-ray tangents, NULL rows = zero
-    hf_tan_dev out;             // NULL rows are not written
+    hf_si_tangent_t out;        // NULL rows are not written
     uint32_t flags;
 };
 typedef const __attribute__((address_space(4))) hf_tangent_args *hf_tan_kargs;
@@ -2294,10 +2255,10 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
             continue;
         }
         const uint32_t flags = ka->flags;
-        const bool follow = (flags & 0x80u) != 0, detach = (flags & 0x100u) != 0;
+        const bool follow = (flags & HF_RAY_FOLLOWSHAPE) != 0, detach = (flags & HF_RAY_DETACHSHAPE) != 0;
         // ONE batch of independent loads: pi, the ray, the ray tangents
-        const float b1 = (ka->pi.u + ub)[lo], b2 = (ka->pi.v + ub)[lo], b0 = 1.f - b1 - b2;
-        const uint32_t prim = (ka->pi.prim + ub)[lo];
+        const float b1 = (ka->pi.prim_uv[0] + ub)[lo], b2 = (ka->pi.prim_uv[1] + ub)[lo], b0 = 1.f - b1 - b2;
+        const uint32_t prim = (ka->pi.prim_index + ub)[lo];
         const v3 o = mk3((ka->rays.o[0] + ub)[lo], (ka->rays.o[1] + ub)[lo], (ka->rays.o[2] + ub)[lo]);
         const v3 d = mk3((ka->rays.d[0] + ub)[lo], (ka->rays.d[1] + ub)[lo], (ka->rays.d[2] + ub)[lo]);
         v3 dO = z3, dD = z3;
@@ -2305,37 +2266,17 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
             dO = mk3(ldu(ka->d_o[0], ub, lo), ldu(ka->d_o[1], ub, lo), ldu(ka->d_o[2], ub, lo));
             dD = mk3(ldu(ka->d_d[0], ub, lo), ldu(ka->d_d[1], ub, lo), ldu(ka->d_d[2], ub, lo));
         }
-        // then the three heights and their three tangents: one round trip
+        // then the three heights and their three tangents: one round trip (DetachShape: the heights carry no tangent)
         const hf_dev_field f = load_field(&ka->f);
-        int vi[3], vj[3];
-        prim_vertex_ids(f, prim, vi, vj);
-        const float *dh = detach ? nullptr : ka->dh; // DetachShape: the heights carry no tangent
-        float hz[3], dz[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const size_t idx = (size_t) vi[k] * f.W + vj[k];
-            hz[k] = f.h[idx];
-            dz[k] = dh ? dh[idx] : 0.f;
-        }
-        v3 P[3];
+        v3 P[3], dP[3];
         float U[3], V[3];
-        const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s); // dP_k/dh_k
-        v3 dP[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const v3 q = mk3(__builtin_fmaf((float) vj[k], f.sx, -1.0f), __builtin_fmaf((float) vi[k], f.sy, -1.0f), hz[k] * f.s);
-            P[k] = xform_point(f.to_world, q);
-            U[k] = (float) vj[k] * f.iu;
-            V[k] = (float) vi[k] * f.iv;
-            dP[k] = ez * dz[k];
-        }
+        int vi[3], vj[3];
+        prim_world(f, prim, P, U, V, vi, vj, dP, detach ? nullptr : ka->dh);
         const v3 e1 = P[1] - P[0], e2 = P[2] - P[0];
         const v3 de1 = dP[1] - dP[0], de2 = dP[2] - dP[0];
         // n = sh_n = +-normalize(cross(e1, e2))
         {
-            const v3 N = cross3(e1, e2);
-            const float r = rsqrt_ieee(dot3(N, N));
-            const v3 nn = N * r;
+            const auto [nn, r] = unit_normal(e1, e2);
             const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);
             const v3 dN = mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
             const float proj = dot3(nn, dN);
@@ -2347,10 +2288,8 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
         // dp_du / dp_dv: linear in the edges (the texcoord differences are constant); zero without dPdUV
         {
             v3 ddu = z3, ddv = z3;
-            if (flags & 0x4u) {
-                const float du0 = U[1] - U[0], dv0 = V[1] - V[0], du1 = U[2] - U[0], dv1 = V[2] - V[0];
-                const float det = __builtin_fmaf(du0, dv1, -(dv0 * du1));
-                const float inv_det = rcp_ieee(det);
+            if (flags & HF_RAY_DPDUV) {
+                const auto [du0, dv0, du1, dv1, det, inv_det] = uv_diff(U, V);
                 if (det != 0.f) {
                     const float a0 = dv1 * inv_det, a1 = -dv0 * inv_det, c0 = -du1 * inv_det, c1 = du0 * inv_det;
                     ddu = mk3(a0 * de1.x + a1 * de2.x, a0 * de1.y + a1 * de2.y, a0 * de1.z + a1 * de2.z);
@@ -2363,11 +2302,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
         // barycentric tangents: the differentiable Moeller-Trumbore (default) or frozen (FollowShape)
         float du = 0.f, dv = 0.f, dt = 0.f;
         if (!follow) {
-            const v3 pvec = cross3(d, e2);
-            const float inv = rcp_ieee(dot3(e1, pvec));
-            const v3 tvec = o - P[0];
-            const v3 qvec = cross3(tvec, e1);
-            const float a_u = dot3(tvec, pvec), a_v = dot3(d, qvec), a_t = dot3(e2, qvec);
+            const auto [pvec, tvec, qvec, inv, a_u, a_v, a_t] = mt_terms(o, d, P[0], e1, e2);
             const v3 p1 = cross3(dD, e2), p2 = cross3(d, de2);
             const v3 dpvec = mk3(p1.x + p2.x, p1.y + p2.y, p1.z + p2.z);
             const v3 dtv = dO - dP[0];
@@ -2383,17 +2318,13 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
                           du * e1.y + dv * e2.y + (b0 * dP[0].y + b1 * dP[1].y + b2 * dP[2].y),
                           du * e1.z + dv * e2.z + (b0 * dP[0].z + b1 * dP[1].z + b2 * dP[2].z));
         if (follow) { // t = sqrt(|p - o|^2 / |d|^2)
-            const v3 p = mk3(__builtin_fmaf(P[0].x, b0, __builtin_fmaf(P[1].x, b1, P[2].x * b2)),
-                             __builtin_fmaf(P[0].y, b0, __builtin_fmaf(P[1].y, b1, P[2].y * b2)),
-                             __builtin_fmaf(P[0].z, b0, __builtin_fmaf(P[1].z, b1, P[2].z * b2)));
-            const v3 po = p - o;
-            const float dd = dot3(d, d), tt = __builtin_sqrtf(dot3(po, po) / dd);
+            const auto [po, dd, tt] = follow_t(bary_point(P, b0, b1, b2), o, d);
             dt = dot3(po, dp - dO) / (tt * dd) - (tt / dd) * dot3(d, dD);
         }
         st(ka->out.t, ub, lo, dt);
         st3(ka->out.p, ub, lo, dp);
         float duv0 = du, duv1 = dv;
-        if (flags & (0x2u | 0x4u)) {
+        if (flags & (HF_RAY_UV | HF_RAY_DPDUV)) {
             duv0 = du * (U[1] - U[0]) + dv * (U[2] - U[0]);
             duv1 = du * (V[1] - V[0]) + dv * (V[2] - V[0]);
         }
@@ -2407,18 +2338,11 @@ void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
                        const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream) {
     if (n == 0) return;
     hf_tangent_args a;
-    a.f = f; a.n = n; a.rays = to_dev(rays);
-    a.pi.t = pi->t; a.pi.u = pi->prim_uv[0]; a.pi.v = pi->prim_uv[1]; a.pi.prim = pi->prim_index;
-    a.active = active; a.dh = dh; a.flags = flags;
+    a.f = f; a.n = n; a.rays = to_dev(rays); a.pi = *pi; a.active = active; a.dh = dh; a.out = *out; a.flags = flags;
     bool raytan = false;
     for (int k = 0; k < 3; ++k) {
         a.d_o[k] = d_o ? d_o[k] : nullptr; a.d_d[k] = d_d ? d_d[k] : nullptr;
         raytan = raytan || a.d_o[k] || a.d_d[k];
-    }
-    a.out.t = out->t; a.out.uv[0] = out->uv[0]; a.out.uv[1] = out->uv[1];
-    for (int k = 0; k < 3; ++k) {
-        a.out.p[k] = out->p[k]; a.out.n[k] = out->n[k]; a.out.sh_n[k] = out->sh_n[k];
-        a.out.dp_du[k] = out->dp_du[k]; a.out.dp_dv[k] = out->dp_dv[k];
     }
     const dim3 grid(grid_for(n, HF_SI_GRID_CAP)), block(HF_BLOCK);
     if (raytan) hipLaunchKernelGGL(hf_tangent_kernel<true>, grid, block, 0, stream, a);
@@ -2431,8 +2355,8 @@ void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
 // :236-256), then for every auxiliary HIT the gradient of its V_direct = (si.p - o) / si.t through the FollowShape
 // surface interaction to the three heights of the hit triangle (third loop, :296-325).  Nothing but the auxiliary
 // hits (pi + si.boundary_test per sample) is read: the auxiliary direction is regenerated from (d, k, seed), si.p and
-// the FollowShape si.t are re-derived from pi with compute_si's expressions.  A ray none of whose samples hit does
-// not reach the heights and is skipped after its num_rays reads of pi.t.
+// the FollowShape si.t are re-derived from pi with compute_si's helpers (bary_point, follow_t).  A ray none of whose
+// samples hit does not reach the heights and is skipped after its num_rays reads of pi.t.
 // Sample k of ray i sits at [k * stride + i] of every per-sample array.
 // ---------------------------------------------------------------------------------
 struct hf_reparam_bwd_args {
@@ -2443,8 +2367,8 @@ struct hf_reparam_bwd_args {
     float kappa, exponent;
     int antithetic;
     const uint32_t *ray_id;
-    const float *pi_t, *pi_u, *pi_v, *si_bt;
-    const uint32_t *pi_prim;
+    hf_pi_const_t pi;
+    const float *si_bt;
     const float *g_dir[3], *g_div;
     float *grad_h;
 };
@@ -2487,7 +2411,7 @@ __global__ __launch_bounds__(HF_BLOCK, (HF_RB_TILE > 32 ? 2 : 5)) void hf_repara
         const bool act = valid && (ka->a.active ? (ka->a.active[i] != 0) : true);
         uint32_t hm = 0u; // samples that hit
         for (uint32_t k = 0; k < ka->a.num_rays; ++k)
-            hm |= (act && ka->a.pi_t[k * ka->a.stride + i] != __builtin_inff()) ? (1u << k) : 0u;
+            hm |= (act && ka->a.pi.t[k * ka->a.stride + i] != __builtin_inff()) ? (1u << k) : 0u;
         if (__ballot(hm != 0u) == 0ull) continue; // wave-uniform
         v3 o = mk3(0.f, 0.f, 0.f), d = o, gV = o;
         float gdivV = 0.f;
@@ -2558,17 +2482,15 @@ __global__ __launch_bounds__(HF_BLOCK, (HF_RB_TILE > 32 ? 2 : 5)) void hf_repara
                 const v3 gVd = mk3(__builtin_fmaf(w, gV.x, gdivV * dw.x), __builtin_fmaf(w, gV.y, gdivV * dw.y),
                                    __builtin_fmaf(w, gV.z, gdivV * dw.z));
                 const v3 da = frame_to_world(q, d, q.omega); // the auxiliary direction (= hf_reparam_aux_kernel's)
-                const float b1 = ka->a.pi_u[k * ka->a.stride + i], b2 = ka->a.pi_v[k * ka->a.stride + i], b0 = 1.f - b1 - b2;
+                const float b1 = ka->a.pi.prim_uv[0][k * ka->a.stride + i], b2 = ka->a.pi.prim_uv[1][k * ka->a.stride + i];
+                const float b0 = 1.f - b1 - b2;
                 v3 P[3];
                 float U[3], V[3];
                 int vi[3], vj[3];
-                prim_world(load_field(&ka->f), ka->a.pi_prim[k * ka->a.stride + i], P, U, V, vi, vj);
-                const v3 p = mk3(__builtin_fmaf(P[0].x, b0, __builtin_fmaf(P[1].x, b1, P[2].x * b2)),
-                                 __builtin_fmaf(P[0].y, b0, __builtin_fmaf(P[1].y, b1, P[2].y * b2)),
-                                 __builtin_fmaf(P[0].z, b0, __builtin_fmaf(P[1].z, b1, P[2].z * b2)));
+                prim_world(load_field(&ka->f), ka->a.pi.prim_index[k * ka->a.stride + i], P, U, V, vi, vj);
                 // V_direct = (p - o) / t with the FollowShape t = sqrt(|p - o|^2 / |d_aux|^2) of compute_si
-                const v3 po = p - o;
-                const float dda = dot3(da, da), tt = __builtin_sqrtf(dot3(po, po) / dda), it = 1.0f / tt;
+                const auto [po, dda, tt] = follow_t(bary_point(P, b0, b1, b2), o, da);
+                const float it = 1.0f / tt;
                 v3 gp = mk3(gVd.x * it, gVd.y * it, gVd.z * it);
                 const float gt = -dot3(gVd, po) * it * it;
                 axpy3(gt / (tt * dda), po, gp); // t's dependence on p (hf_adjoint_kernel, FollowShape branch)
@@ -2626,9 +2548,7 @@ void hf_launch_reparam_backward(const hf_dev_field &f, const hf_reparam_args &ra
     a.n = ra.n; a.stride = stride; a.active = ra.active; a.num_rays = num_rays; a.seed = ra.seed; a.kappa = ra.kappa;
     a.exponent = ra.exponent; a.antithetic = ra.antithetic; a.ray_id = ra.ray_id;
     for (int c = 0; c < 3; ++c) { a.o[c] = ra.o[c]; a.d[c] = ra.d[c]; a.g_dir[c] = ra.g_dir[c]; }
-    a.g_div = ra.g_div; a.si_bt = ra.si_bt;
-    a.pi_t = pi->t; a.pi_u = pi->prim_uv[0]; a.pi_v = pi->prim_uv[1]; a.pi_prim = pi->prim_index;
-    a.grad_h = grad_h;
+    a.g_div = ra.g_div; a.si_bt = ra.si_bt; a.pi = *pi; a.grad_h = grad_h;
     hf_reparam_bwd_kargs k;
     k.f = f; k.a = a;
     hipLaunchKernelGGL(hf_reparam_backward_kernel, dim3(grid_for(ra.n)), dim3(HF_BLOCK), 0, stream, k);

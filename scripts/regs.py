@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: scripts/regs.py lib.so [name filter]: VGPRs / spills / LDS of the gfx950 kernels in a built library
+"""usage: scripts/regs.py lib.so [name filter]: VGPRs / SGPRs / spills / LDS / private segment of the gfx950 kernels in a built library
 (reads the offload bundle inside the .so and the code object's metadata notes; compiles nothing)"""
 import re, struct, subprocess, sys, tempfile
 data = open(sys.argv[1], "rb").read()
@@ -28,4 +28,6 @@ for _ in range(n):
         cur[k] = v
         if k == "vgpr_spill_count":
             if pat.search(cur.get("name", "")):
-                print(f"{cur.get('name'):70s} vgpr {cur.get('vgpr_count'):>4s} spill {v:>3s} sgpr_spill {cur.get('sgpr_spill_count'):>3s} lds {cur.get('group_segment_fixed_size')}")
+                print(f"{cur.get('name'):70s} vgpr {cur.get('vgpr_count'):>4s} spill {v:>3s} sgpr {cur.get('sgpr_count'):>3s} "
+                      f"sgpr_spill {cur.get('sgpr_spill_count'):>3s} lds {cur.get('group_segment_fixed_size')} "
+                      f"private {cur.get('private_segment_fixed_size')}")
