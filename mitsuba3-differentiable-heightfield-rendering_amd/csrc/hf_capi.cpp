@@ -130,6 +130,9 @@ static int fail(int code, const char *fmt, ...) {
                         hipGetErrorString(e_));                                                   \
     } while (0)
 
+// three row pointers, none of them NULL
+static bool all3(const float *const p[3]) { return p && p[0] && p[1] && p[2]; }
+
 extern "C" const char *hf_last_error_string(void) { return g_err; }
 extern "C" int hf_version(void) { return HF_VERSION; }
 
@@ -412,18 +415,21 @@ extern "C" int hf_bbox(hf_field_t *hf, float out[6]) {
     return HF_OK;
 }
 
-static int check_rays(const char *fn, const hf_field_t *hf, size_t n, const hf_rays_t *rays) {
-    if (!hf || !rays) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (n == 0) return HF_OK;
-    for (int k = 0; k < 3; ++k)
-        if (!rays->o[k] || !rays->d[k]) return fail(HF_EINVAL, "%s: NULL ray component array", fn);
-    if (!rays->maxt) return fail(HF_EINVAL, "%s: NULL ray maxt array", fn);
-    // the launch goes to the calling thread's current device: it must be the handle's (the query functions do
-    // not switch devices behind the caller's back)
+// the launch goes to the calling thread's current device: it must be the handle's (the query functions do
+// not switch devices behind the caller's back)
+static int check_device(const char *fn, const hf_field_t *hf) {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != hf->device)
         return fail(HF_EDEVICE, "%s: current HIP device is %d, the heightfield lives on device %d", fn, cur, hf->device);
     return HF_OK;
+}
+
+static int check_rays(const char *fn, const hf_field_t *hf, size_t n, const hf_rays_t *rays) {
+    if (!hf || !rays) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (n == 0) return HF_OK;
+    if (!all3(rays->o) || !all3(rays->d)) return fail(HF_EINVAL, "%s: NULL ray component array", fn);
+    if (!rays->maxt) return fail(HF_EINVAL, "%s: NULL ray maxt array", fn);
+    return check_device(fn, hf);
 }
 
 static int check_flags(const char *fn, uint32_t flags) {
@@ -439,19 +445,26 @@ static int check_pi(const char *fn, size_t n, const hf_pi_const_t *pi) {
     return HF_OK;
 }
 
+// one trace launch on a leased scratch block; a lease that fails reports as "<who>: <why>"
+static int trace(const char *who, int mode, const hf_field_t *hf, size_t n, const hf_rays_t *rays, const uint8_t *active,
+                 const hf_pi_t *pi, uint8_t *hit, const hf_si_t *si, uint32_t flags, hipStream_t stream,
+                 const hf_reparam_args *aux, bool lean) {
+    {
+        slot_lease lease(hf, stream, hf_trace_scratch_bytes(n));
+        if (!lease.buf) return fail(lease.code, "%s: %s", who, lease.why);
+        hf_launch_trace(mode, hf->dev, n, rays, active, pi, hit, si, flags, lease.buf, stream, aux, lean);
+    }
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 extern "C" int hf_ray_intersect_preliminary(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
                                             const uint8_t *active, const hf_pi_t *out, hf_stream_t stream) {
     int rc = check_rays("hf_ray_intersect_preliminary", hf, n, rays);
     if (rc) return rc;
     if (!out || (n && !out->t)) return fail(HF_EINVAL, "hf_ray_intersect_preliminary: NULL output");
-    {
-        slot_lease lease(hf, (hipStream_t) stream, hf_trace_scratch_bytes(n));
-        if (!lease.buf) return fail(lease.code, "trace launch: %s", lease.why);
-        hf_launch_trace(0, hf->dev, n, rays, active, out, nullptr, nullptr, 0, lease.buf, (hipStream_t) stream, nullptr,
-                        hf->coherence == HF_COHERENCE_INCOHERENT);
-    }
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return trace("trace launch", 0, hf, n, rays, active, out, nullptr, nullptr, 0, (hipStream_t) stream, nullptr,
+                 hf->coherence == HF_COHERENCE_INCOHERENT);
 }
 
 extern "C" int hf_ray_test(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const uint8_t *active,
@@ -459,14 +472,8 @@ extern "C" int hf_ray_test(const hf_field_t *hf, size_t n, const hf_rays_t *rays
     int rc = check_rays("hf_ray_test", hf, n, rays);
     if (rc) return rc;
     if (n && !out_hit) return fail(HF_EINVAL, "hf_ray_test: NULL output");
-    {
-        slot_lease lease(hf, (hipStream_t) stream, hf_trace_scratch_bytes(n));
-        if (!lease.buf) return fail(lease.code, "trace launch: %s", lease.why);
-        hf_launch_trace(1, hf->dev, n, rays, active, nullptr, out_hit, nullptr, 0, lease.buf, (hipStream_t) stream, nullptr,
-                        hf->coherence == HF_COHERENCE_INCOHERENT);
-    }
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return trace("trace launch", 1, hf, n, rays, active, nullptr, out_hit, nullptr, 0, (hipStream_t) stream, nullptr,
+                 hf->coherence == HF_COHERENCE_INCOHERENT);
 }
 
 extern "C" int hf_compute_surface_interaction(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
@@ -489,14 +496,8 @@ extern "C" int hf_ray_intersect(const hf_field_t *hf, size_t n, const hf_rays_t 
     if (rc) return rc;
     if ((rc = check_flags("hf_ray_intersect", ray_flags))) return rc;
     if (!out_si) return fail(HF_EINVAL, "hf_ray_intersect: NULL output");
-    {
-        slot_lease lease(hf, (hipStream_t) stream, hf_trace_scratch_bytes(n));
-        if (!lease.buf) return fail(lease.code, "trace launch: %s", lease.why);
-        hf_launch_trace(2, hf->dev, n, rays, active, out_pi, nullptr, out_si, ray_flags, lease.buf, (hipStream_t) stream, nullptr,
-                        hf->coherence == HF_COHERENCE_INCOHERENT);
-    }
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return trace("trace launch", 2, hf, n, rays, active, out_pi, nullptr, out_si, ray_flags, (hipStream_t) stream, nullptr,
+                 hf->coherence == HF_COHERENCE_INCOHERENT);
 }
 
 extern "C" int hf_adjoint_rows(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
@@ -508,8 +509,8 @@ extern "C" int hf_adjoint_rows(const hf_field_t *hf, size_t n, const hf_rays_t *
     if ((rc = check_flags("hf_adjoint", ray_flags))) return rc;
     if ((rc = check_pi("hf_adjoint", n, pi))) return rc;
     if (!grad_si) return fail(HF_EINVAL, "hf_adjoint: NULL grad_si");
-    if (grad_o && (!grad_o[0] || !grad_o[1] || !grad_o[2])) return fail(HF_EINVAL, "hf_adjoint: NULL grad_o array");
-    if (grad_d && (!grad_d[0] || !grad_d[1] || !grad_d[2])) return fail(HF_EINVAL, "hf_adjoint: NULL grad_d array");
+    if (grad_o && !all3(grad_o)) return fail(HF_EINVAL, "hf_adjoint: NULL grad_o array");
+    if (grad_d && !all3(grad_d)) return fail(HF_EINVAL, "hf_adjoint: NULL grad_d array");
     hf_launch_adjoint(hf->dev, n, rays, pi, active, grad_si, ray_flags, grad_heights, grad_o, grad_d, row_band,
                       (hipStream_t) stream);
     HF_HIP(hipGetLastError());
@@ -558,18 +559,64 @@ static int pack_lights(const char *who, size_t n, uint32_t spp, const float *con
     return HF_OK;
 }
 
+// One body per direction of the lighting family.  point: point lights at p (hf_point_light_t has hf_dir_light_t's
+// layout: three floats + one), else directional lights and p == NULL.
+static int lighting(const char *who, bool point, size_t n, uint32_t spp, const float *const sh_n[3],
+                    const float *const d[3], const float *t, const float *weight, const float *const p[3],
+                    uint32_t n_lights, const hf_dir_light_t *lights, float albedo, const uint8_t *const *vis,
+                    float *image, hipStream_t stream) {
+    hf_lights_dev L;
+    const int rc = pack_lights(who, n, spp, sh_n, d, t, n_lights, lights, albedo, vis, L);
+    if (rc != HF_OK) return rc;
+    if (point && !all3(p)) return fail(HF_EINVAL, "%s: NULL position array", who);
+    if (!image) return fail(HF_EINVAL, "%s: NULL image", who);
+    L.weight = weight;
+    hf_launch_direct(n, spp, sh_n, d, t, p, L, image, stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+static int lighting_adjoint(const char *who, bool point, size_t n, uint32_t spp, const float *const sh_n[3],
+                            const float *const d[3], const float *t, const float *weight, const float *const p[3],
+                            uint32_t n_lights, const hf_dir_light_t *lights, float albedo, const uint8_t *const *vis,
+                            const float *grad_image, float *const grad_sh_n[3], float *grad_weight,
+                            float *const grad_p[3], hipStream_t stream) {
+    hf_lights_dev L;
+    const int rc = pack_lights(who, n, spp, sh_n, d, t, n_lights, lights, albedo, vis, L);
+    if (rc != HF_OK) return rc;
+    if (point && !all3(p)) return fail(HF_EINVAL, "%s: NULL position array", who);
+    if (!grad_image || !all3(grad_sh_n) || (point && !all3(grad_p))) return fail(HF_EINVAL, "%s: NULL gradient array", who);
+    L.weight = weight; L.grad_weight = grad_weight;
+    hf_launch_direct_adjoint(n, spp, sh_n, d, t, p, L, grad_image, grad_sh_n, grad_p, stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+static int lighting_tangent(const char *who, bool point, size_t n, uint32_t spp, const float *const sh_n[3],
+                            const float *const d[3], const float *t, const float *weight, const float *const p[3],
+                            uint32_t n_lights, const hf_dir_light_t *lights, float albedo, const uint8_t *const *vis,
+                            const float *const dsh_n[3], const float *const dp[3], const float *dweight, float *dimage,
+                            hipStream_t stream) {
+    hf_lights_dev L;
+    const int rc = pack_lights(who, n, spp, sh_n, d, t, n_lights, lights, albedo, vis, L);
+    if (rc != HF_OK) return rc;
+    if (point && !all3(p)) return fail(HF_EINVAL, "%s: NULL position array", who);
+    if (!dimage) return fail(HF_EINVAL, "%s: NULL image", who);
+    if ((dsh_n && !all3(dsh_n)) || (dp && !all3(dp)))
+        return fail(HF_EINVAL, "%s: NULL %s component array", who, point ? "tangent" : "dsh_n");
+    L.weight = weight;
+    hf_launch_direct_tangent(n, spp, sh_n, d, t, p, L, dsh_n, dp, dweight, dimage, stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+static_assert(sizeof(hf_point_light_t) == sizeof(hf_dir_light_t), "light structs share one packing");
+
 extern "C" int hf_direct_lighting_weighted(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                                            const float *t, const float *weight, uint32_t n_lights,
                                            const hf_dir_light_t *lights, float albedo, const uint8_t *const *vis,
                                            float *image, hf_stream_t stream) {
-    hf_lights_dev L;
-    const int rc = pack_lights("hf_direct_lighting", n, spp, sh_n, d, t, n_lights, lights, albedo, vis, L);
-    if (rc != HF_OK) return rc;
-    if (!image) return fail(HF_EINVAL, "hf_direct_lighting: NULL image");
-    L.weight = weight;
-    hf_launch_direct(n, spp, sh_n, d, t, nullptr, L, image, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return lighting("hf_direct_lighting", false, n, spp, sh_n, d, t, weight, nullptr, n_lights, lights, albedo, vis, image,
+                    (hipStream_t) stream);
 }
 extern "C" int hf_direct_lighting(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                                   const float *t, uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
@@ -581,15 +628,8 @@ extern "C" int hf_direct_lighting_weighted_adjoint(size_t n, uint32_t spp, const
                                                    uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
                                                    const uint8_t *const *vis, const float *grad_image,
                                                    float *const grad_sh_n[3], float *grad_weight, hf_stream_t stream) {
-    hf_lights_dev L;
-    const int rc = pack_lights("hf_direct_lighting_adjoint", n, spp, sh_n, d, t, n_lights, lights, albedo, vis, L);
-    if (rc != HF_OK) return rc;
-    if (!grad_image || !grad_sh_n || !grad_sh_n[0] || !grad_sh_n[1] || !grad_sh_n[2])
-        return fail(HF_EINVAL, "hf_direct_lighting_adjoint: NULL gradient array");
-    L.weight = weight; L.grad_weight = grad_weight;
-    hf_launch_direct_adjoint(n, spp, sh_n, d, t, nullptr, L, grad_image, grad_sh_n, nullptr, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return lighting_adjoint("hf_direct_lighting_adjoint", false, n, spp, sh_n, d, t, weight, nullptr, n_lights, lights,
+                            albedo, vis, grad_image, grad_sh_n, grad_weight, nullptr, (hipStream_t) stream);
 }
 extern "C" int hf_direct_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                                           const float *t, uint32_t n_lights, const hf_dir_light_t *lights,
@@ -598,76 +638,38 @@ extern "C" int hf_direct_lighting_adjoint(size_t n, uint32_t spp, const float *c
     return hf_direct_lighting_weighted_adjoint(n, spp, sh_n, d, t, nullptr, n_lights, lights, albedo, vis, grad_image,
                                                grad_sh_n, nullptr, stream);
 }
-
 extern "C" int hf_direct_lighting_weighted_tangent(size_t n, uint32_t spp, const float *const sh_n[3],
                                                    const float *const d[3], const float *t, const float *weight,
                                                    uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
                                                    const uint8_t *const *vis, const float *const dsh_n[3],
                                                    const float *dweight, float *dimage, hf_stream_t stream) {
-    hf_lights_dev L;
-    const int rc = pack_lights("hf_direct_lighting_weighted_tangent", n, spp, sh_n, d, t, n_lights, lights, albedo, vis, L);
-    if (rc != HF_OK) return rc;
-    if (!dimage) return fail(HF_EINVAL, "hf_direct_lighting_weighted_tangent: NULL image");
-    if (dsh_n && (!dsh_n[0] || !dsh_n[1] || !dsh_n[2]))
-        return fail(HF_EINVAL, "hf_direct_lighting_weighted_tangent: NULL dsh_n component array");
-    L.weight = weight;
-    hf_launch_direct_tangent(n, spp, sh_n, d, t, nullptr, L, dsh_n, nullptr, dweight, dimage, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return lighting_tangent("hf_direct_lighting_weighted_tangent", false, n, spp, sh_n, d, t, weight, nullptr, n_lights,
+                            lights, albedo, vis, dsh_n, nullptr, dweight, dimage, (hipStream_t) stream);
 }
 
-static bool all3(const float *const p[3]) { return p && p[0] && p[1] && p[2]; }
-
-// point lights: same packing (hf_point_light_t has hf_dir_light_t's layout: three floats + one)
 extern "C" int hf_point_lighting(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                                  const float *t, const float *const p[3], uint32_t n_lights,
                                  const hf_point_light_t *lights, float albedo, const uint8_t *const *vis, float *image,
                                  hf_stream_t stream) {
-    static_assert(sizeof(hf_point_light_t) == sizeof(hf_dir_light_t), "light structs share one packing");
-    hf_lights_dev L;
-    const int rc = pack_lights("hf_point_lighting", n, spp, sh_n, d, t, n_lights, (const hf_dir_light_t *) lights, albedo, vis, L);
-    if (rc != HF_OK) return rc;
-    if (!all3(p)) return fail(HF_EINVAL, "hf_point_lighting: NULL position array");
-    if (!image) return fail(HF_EINVAL, "hf_point_lighting: NULL image");
-    hf_launch_direct(n, spp, sh_n, d, t, p, L, image, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return lighting("hf_point_lighting", true, n, spp, sh_n, d, t, nullptr, p, n_lights, (const hf_dir_light_t *) lights,
+                    albedo, vis, image, (hipStream_t) stream);
 }
-
 extern "C" int hf_point_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                                          const float *t, const float *const p[3], uint32_t n_lights,
                                          const hf_point_light_t *lights, float albedo, const uint8_t *const *vis,
                                          const float *grad_image, float *const grad_sh_n[3], float *const grad_p[3],
                                          hf_stream_t stream) {
-    hf_lights_dev L;
-    const int rc = pack_lights("hf_point_lighting_adjoint", n, spp, sh_n, d, t, n_lights, (const hf_dir_light_t *) lights,
-                               albedo, vis, L);
-    if (rc != HF_OK) return rc;
-    if (!all3(p)) return fail(HF_EINVAL, "hf_point_lighting_adjoint: NULL position array");
-    if (!grad_image || !grad_sh_n || !grad_sh_n[0] || !grad_sh_n[1] || !grad_sh_n[2] || !grad_p || !grad_p[0] ||
-        !grad_p[1] || !grad_p[2])
-        return fail(HF_EINVAL, "hf_point_lighting_adjoint: NULL gradient array");
-    hf_launch_direct_adjoint(n, spp, sh_n, d, t, p, L, grad_image, grad_sh_n, grad_p, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return lighting_adjoint("hf_point_lighting_adjoint", true, n, spp, sh_n, d, t, nullptr, p, n_lights,
+                            (const hf_dir_light_t *) lights, albedo, vis, grad_image, grad_sh_n, nullptr, grad_p,
+                            (hipStream_t) stream);
 }
-
 extern "C" int hf_point_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                                          const float *t, const float *const p[3], uint32_t n_lights,
                                          const hf_point_light_t *lights, float albedo, const uint8_t *const *vis,
                                          const float *const dsh_n[3], const float *const dp[3], float *dimage,
                                          hf_stream_t stream) {
-    hf_lights_dev L;
-    const int rc = pack_lights("hf_point_lighting_tangent", n, spp, sh_n, d, t, n_lights, (const hf_dir_light_t *) lights,
-                               albedo, vis, L);
-    if (rc != HF_OK) return rc;
-    if (!all3(p)) return fail(HF_EINVAL, "hf_point_lighting_tangent: NULL position array");
-    if (!dimage) return fail(HF_EINVAL, "hf_point_lighting_tangent: NULL image");
-    if ((dsh_n && !all3(dsh_n)) || (dp && !all3(dp)))
-        return fail(HF_EINVAL, "hf_point_lighting_tangent: NULL tangent component array");
-    hf_launch_direct_tangent(n, spp, sh_n, d, t, p, L, dsh_n, dp, nullptr, dimage, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return lighting_tangent("hf_point_lighting_tangent", true, n, spp, sh_n, d, t, nullptr, p, n_lights,
+                            (const hf_dir_light_t *) lights, albedo, vis, dsh_n, dp, nullptr, dimage, (hipStream_t) stream);
 }
 
 // ---- Gaussian reconstruction filter (film) ------------------------------------------------------
@@ -725,7 +727,7 @@ extern "C" int hf_film_splat_adjoint(size_t n, uint32_t channels, const float *p
 extern "C" int hf_reparam_aux_rays(size_t n, const float *const o[3], const float *const d[3], const uint8_t *active,
                                    uint32_t k, float kappa, int antithetic, uint32_t seed, const uint32_t *ray_id,
                                    float *const aux_d[3], float *aux_maxt, hf_stream_t stream) {
-    if (!all3(o) || !all3(d) || !aux_d || !aux_d[0] || !aux_d[1] || !aux_d[2] || !aux_maxt)
+    if (!all3(o) || !all3(d) || !all3(aux_d) || !aux_maxt)
         return fail(HF_EINVAL, "hf_reparam_aux_rays: NULL argument");
     if (!(kappa > 0.f)) return fail(HF_EINVAL, "hf_reparam_aux_rays: kappa must be > 0");
     if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "hf_reparam_aux_rays: more than 2^32 rays");
@@ -745,11 +747,10 @@ extern "C" int hf_reparam_weights(int mode, size_t n, const float *const o[3], c
                                   const float *const grad_direction[3], const float *grad_divergence,
                                   float *const grad_p[3], float *grad_t, float *const grad_vd[3],
                                   hf_stream_t stream) {
-    if (!all3(o) || !all3(d) || !si_t || !si_boundary_test || !Z || !dZ || !dZ[0] || !dZ[1] || !dZ[2])
+    if (!all3(o) || !all3(d) || !si_t || !si_boundary_test || !Z || !all3(dZ))
         return fail(HF_EINVAL, "hf_reparam_weights: NULL argument");
     if (mode != 0 && mode != 1) return fail(HF_EINVAL, "hf_reparam_weights: mode must be 0 or 1");
-    if (mode == 1 && (!all3(si_p) || !all3(grad_direction) || !grad_divergence || !grad_p || !grad_p[0] || !grad_p[1] ||
-                      !grad_p[2] || !grad_t))
+    if (mode == 1 && (!all3(si_p) || !all3(grad_direction) || !grad_divergence || !all3(grad_p) || !grad_t))
         return fail(HF_EINVAL, "hf_reparam_weights: mode 1 needs si_p, grad_direction, grad_divergence, grad_p, grad_t");
     if (!(kappa > 0.f)) return fail(HF_EINVAL, "hf_reparam_weights: kappa must be > 0");
     if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "hf_reparam_weights: more than 2^32 rays");
@@ -762,7 +763,7 @@ extern "C" int hf_reparam_weights(int mode, size_t n, const float *const o[3], c
         a.si_p[c] = si_p ? si_p[c] : nullptr;
         a.g_dir[c] = grad_direction ? grad_direction[c] : nullptr;
         a.g_p[c] = grad_p ? grad_p[c] : nullptr;
-        a.g_vd[c] = (grad_vd && grad_vd[0] && grad_vd[1] && grad_vd[2]) ? grad_vd[c] : nullptr;
+        a.g_vd[c] = all3(grad_vd) ? grad_vd[c] : nullptr;
     }
     hf_launch_reparam_weights(a, (hipStream_t) stream);
     HF_HIP(hipGetLastError());
@@ -792,55 +793,41 @@ extern "C" int hf_set_ray_coherence(hf_field_t *hf, int coherence) {
 }
 extern "C" int hf_get_ray_coherence(const hf_field_t *hf) { return hf ? hf->coherence : HF_COHERENCE_AUTO; }
 
-extern "C" int hf_reparam_trace(const hf_field_t *hf, size_t n, const float *const o[3], const float *const d[3],
-                                const uint8_t *active, uint32_t k, float kappa, int antithetic, uint32_t seed,
-                                const uint32_t *ray_id, const hf_pi_t *out_pi, const hf_si_t *out_si, hf_stream_t stream) {
-    if (!all3(o) || !all3(d)) return fail(HF_EINVAL, "hf_reparam_trace: NULL argument");
+// hf_reparam_trace (all = false: sample k) and hf_reparam_trace_all (all: samples 0 .. num - 1, stride apart)
+static int reparam_trace(const char *fn, bool all, const hf_field_t *hf, size_t n, const float *const o[3],
+                         const float *const d[3], const uint8_t *active, uint32_t k, uint32_t num, size_t stride,
+                         float kappa, int antithetic, uint32_t seed, const uint32_t *ray_id, const hf_pi_t *out_pi,
+                         const hf_si_t *out_si, hipStream_t stream) {
+    if (!all3(o) || !all3(d)) return fail(HF_EINVAL, "%s: NULL argument", fn);
     hf_rays_t rays; // maxt is not read for auxiliary rays (infinity); any readable array of n floats will do
     for (int c = 0; c < 3; ++c) { rays.o[c] = o[c]; rays.d[c] = d[c]; }
     rays.maxt = o[0];
-    int rc = check_rays("hf_reparam_trace", hf, n, &rays);
+    int rc = check_rays(fn, hf, n, &rays);
     if (rc) return rc;
-    if (!out_si) return fail(HF_EINVAL, "hf_reparam_trace: NULL output");
-    if (!(kappa > 0.f)) return fail(HF_EINVAL, "hf_reparam_trace: kappa must be > 0");
-    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "hf_reparam_trace: more than 2^32 rays");
+    if (!out_si) return fail(HF_EINVAL, "%s: NULL output", fn);
+    if (!(kappa > 0.f)) return fail(HF_EINVAL, "%s: kappa must be > 0", fn);
+    if (all && (num == 0 || num > 32)) return fail(HF_EINVAL, "%s: 1..32 auxiliary rays per ray (got %u)", fn, num);
+    if (all && num > 1 && stride < n) return fail(HF_EINVAL, "%s: sample_stride < n", fn);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 rays", fn);
     hf_reparam_args a = {};
-    a.k = k; a.seed = seed; a.kappa = kappa; a.antithetic = antithetic; a.ray_id = ray_id;
-    {
-        slot_lease lease(hf, (hipStream_t) stream, hf_trace_scratch_bytes(n));
-        if (!lease.buf) return fail(lease.code, "trace launch: %s", lease.why);
-        hf_launch_trace(2, hf->dev, n, &rays, active, out_pi, nullptr, out_si,
-                        HF_RAY_ALL | HF_RAY_FOLLOWSHAPE | HF_RAY_BOUNDARYTEST, lease.buf, (hipStream_t) stream, &a, aux_lean(hf, kappa));
-    }
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    a.k = k; a.num = num; a.stride = stride; a.seed = seed; a.kappa = kappa; a.antithetic = antithetic; a.ray_id = ray_id;
+    return trace("trace launch", 2, hf, n, &rays, active, out_pi, nullptr, out_si,
+                 HF_RAY_ALL | HF_RAY_FOLLOWSHAPE | HF_RAY_BOUNDARYTEST, stream, &a, aux_lean(hf, kappa));
+}
+
+extern "C" int hf_reparam_trace(const hf_field_t *hf, size_t n, const float *const o[3], const float *const d[3],
+                                const uint8_t *active, uint32_t k, float kappa, int antithetic, uint32_t seed,
+                                const uint32_t *ray_id, const hf_pi_t *out_pi, const hf_si_t *out_si, hf_stream_t stream) {
+    return reparam_trace("hf_reparam_trace", false, hf, n, o, d, active, k, 0, 0, kappa, antithetic, seed, ray_id, out_pi,
+                         out_si, (hipStream_t) stream);
 }
 
 extern "C" int hf_reparam_trace_all(const hf_field_t *hf, size_t n, const float *const o[3], const float *const d[3],
                                     const uint8_t *active, uint32_t num_rays, float kappa, int antithetic, uint32_t seed,
                                     const uint32_t *ray_id, const hf_pi_t *out_pi, const hf_si_t *out_si, size_t sample_stride,
                                     hf_stream_t stream) {
-    if (!all3(o) || !all3(d)) return fail(HF_EINVAL, "hf_reparam_trace_all: NULL argument");
-    hf_rays_t rays; // maxt is not read for auxiliary rays (infinity); any readable array of n floats will do
-    for (int c = 0; c < 3; ++c) { rays.o[c] = o[c]; rays.d[c] = d[c]; }
-    rays.maxt = o[0];
-    int rc = check_rays("hf_reparam_trace_all", hf, n, &rays);
-    if (rc) return rc;
-    if (!out_si) return fail(HF_EINVAL, "hf_reparam_trace_all: NULL output");
-    if (!(kappa > 0.f)) return fail(HF_EINVAL, "hf_reparam_trace_all: kappa must be > 0");
-    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "hf_reparam_trace_all: 1..32 auxiliary rays per ray (got %u)", num_rays);
-    if (num_rays > 1 && sample_stride < n) return fail(HF_EINVAL, "hf_reparam_trace_all: sample_stride < n");
-    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "hf_reparam_trace_all: more than 2^32 rays");
-    hf_reparam_args a = {};
-    a.k = 0; a.num = num_rays; a.stride = sample_stride; a.seed = seed; a.kappa = kappa; a.antithetic = antithetic; a.ray_id = ray_id;
-    {
-        slot_lease lease(hf, (hipStream_t) stream, hf_trace_scratch_bytes(n));
-        if (!lease.buf) return fail(lease.code, "trace launch: %s", lease.why);
-        hf_launch_trace(2, hf->dev, n, &rays, active, out_pi, nullptr, out_si,
-                        HF_RAY_ALL | HF_RAY_FOLLOWSHAPE | HF_RAY_BOUNDARYTEST, lease.buf, (hipStream_t) stream, &a, aux_lean(hf, kappa));
-    }
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return reparam_trace("hf_reparam_trace_all", true, hf, n, o, d, active, 0, num_rays, sample_stride, kappa, antithetic,
+                         seed, ray_id, out_pi, out_si, (hipStream_t) stream);
 }
 
 extern "C" int hf_reparam_backward(const hf_field_t *hf, size_t n, const float *const o[3], const float *const d[3],
@@ -858,10 +845,7 @@ extern "C" int hf_reparam_backward(const hf_field_t *hf, size_t n, const float *
     if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "hf_reparam_backward: 1..32 auxiliary rays per ray (got %u)", num_rays);
     if (num_rays > 1 && sample_stride < n) return fail(HF_EINVAL, "hf_reparam_backward: sample_stride < n");
     if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "hf_reparam_backward: more than 2^32 rays");
-    int cur = -1; // like the other query functions: the launch goes to the caller's current device
-    if (hipGetDevice(&cur) != hipSuccess || cur != hf->device)
-        return fail(HF_EDEVICE, "hf_reparam_backward: current HIP device is %d, the heightfield lives on device %d", cur,
-                    hf->device);
+    if ((rc = check_device("hf_reparam_backward", hf))) return rc;
     hf_reparam_args a = {};
     a.n = n; a.active = active; a.seed = seed; a.kappa = kappa; a.exponent = exponent; a.antithetic = antithetic;
     a.ray_id = ray_id;
@@ -942,13 +926,9 @@ int packet_trace(const char *fn, int mode, const hf_field_t *hf, uint32_t n, con
     hf_pi_t pi;
     pi.t = d32 + 7 * HF_PACKET_MAX; pi.prim_uv[0] = d32 + 8 * HF_PACKET_MAX; pi.prim_uv[1] = d32 + 9 * HF_PACKET_MAX;
     pi.prim_index = (uint32_t *) (d32 + 10 * HF_PACKET_MAX);
-    {
-        slot_lease lease(hf, st->stream, hf_trace_scratch_bytes(n));
-        if (!lease.buf) return fail(lease.code, "%s: %s", fn, lease.why);
-        hf_launch_trace(mode, hf->dev, n, &rays, dmask, mode == 0 ? &pi : nullptr, mode == 1 ? dhit : nullptr, nullptr, 0,
-                        lease.buf, st->stream);
-    }
-    HF_HIP(hipGetLastError());
+    rc = trace(fn, mode, hf, n, &rays, dmask, mode == 0 ? &pi : nullptr, mode == 1 ? dhit : nullptr, nullptr, 0, st->stream,
+               nullptr, false);
+    if (rc) return rc;
     HF_HIP(hipMemcpyAsync(st->h, st->d, PK_BYTES, hipMemcpyDeviceToHost, st->stream));
     HF_HIP(hipStreamSynchronize(st->stream));
     if (mode == 0) {

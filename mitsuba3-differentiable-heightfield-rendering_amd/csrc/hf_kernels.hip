@@ -1247,19 +1247,6 @@ __device__ __forceinline__ v3 frame_to_world(const hf_aux_sample &q, v3 n, v3 v)
                __builtin_fmaf(n.z, v.z, __builtin_fmaf(q.ft.z, v.y, q.fs.z * v.x)));
 }
 
-struct hf_rays_dev {
-    const float *o[3];
-    const float *d[3];
-    const float *maxt;
-};
-struct hf_pi_dev {
-    float *t, *u, *v;
-    uint32_t *prim;
-};
-struct hf_si_dev {
-    float *t, *p[3], *n[3], *uv[2], *sh_n[3], *dp_du[3], *dp_dv[3], *bt, *sh_s[3], *sh_t[3], *wi[3];
-};
-
 // record stores are write-once streams (72 B/ray): non-temporal, so that they do not push the mip
 // and height lines of concurrently traversing waves out of L2.  Address = (row + ub) + lo: uniform base, lane offset.
 __device__ __forceinline__ void st(float *p, size_t ub, uint32_t lo, float v) { if (p) __builtin_nontemporal_store(v, &(p + ub)[lo]); }
@@ -1298,11 +1285,11 @@ __device__ __forceinline__ void st4(float *p, size_t ub, uint32_t l4, f4 v) { if
 struct hf_trace_args {
     hf_dev_field f;
     size_t n;
-    hf_rays_dev rays;
+    hf_rays_t rays;
     const uint8_t *active;
-    hf_pi_dev pi;
+    hf_pi_t pi;
     uint8_t *hit_out;
-    hf_si_dev sio;
+    hf_si_t sio;
     uint32_t flags;
     uint32_t grab; // rays per fetch, a multiple of 64
     uint32_t wide; // every ray / record row is 16-byte aligned and there is no `active` mask: fetches that miss the bound as a whole take the wide path
@@ -1333,21 +1320,22 @@ __device__ __forceinline__ hf_dev_field load_field(const __attribute__((address_
 }
 
 typedef const __attribute__((address_space(4))) hf_trace_args *hf_kargs_ptr;
-__device__ __forceinline__ hf_rays_dev load_rays(hf_kargs_ptr ka) {
-    hf_rays_dev r;
+// (member-wise: an implicit copy cannot bind an object of the constant address space)
+__device__ __forceinline__ hf_rays_t load_rays(hf_kargs_ptr ka) {
+    hf_rays_t r;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { r.o[k] = ka->rays.o[k]; r.d[k] = ka->rays.d[k]; }
     r.maxt = ka->rays.maxt;
     return r;
 }
-__device__ __forceinline__ hf_pi_dev load_pi(hf_kargs_ptr ka) {
-    hf_pi_dev p;
-    p.t = ka->pi.t; p.u = ka->pi.u; p.v = ka->pi.v; p.prim = ka->pi.prim;
+__device__ __forceinline__ hf_pi_t load_pi(hf_kargs_ptr ka) {
+    hf_pi_t p;
+    p.t = ka->pi.t; p.prim_uv[0] = ka->pi.prim_uv[0]; p.prim_uv[1] = ka->pi.prim_uv[1]; p.prim_index = ka->pi.prim_index;
     return p;
 }
-__device__ __forceinline__ hf_si_dev load_si(hf_kargs_ptr ka) {
-    hf_si_dev d;
-    d.t = ka->sio.t; d.bt = ka->sio.bt;
+__device__ __forceinline__ hf_si_t load_si(hf_kargs_ptr ka) {
+    hf_si_t d;
+    d.t = ka->sio.t; d.boundary_test = ka->sio.boundary_test;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         d.p[k] = ka->sio.p[k]; d.n[k] = ka->sio.n[k]; d.sh_n[k] = ka->sio.sh_n[k]; d.dp_du[k] = ka->sio.dp_du[k];
@@ -1357,17 +1345,18 @@ __device__ __forceinline__ hf_si_dev load_si(hf_kargs_ptr ka) {
     return d;
 }
 
-// compute_si_to sink of the fused mode: a field goes to memory when it is final; the row pointers are read from the
-// kernarg segment at the store
-struct hf_si_store_sink {
-    hf_kargs_ptr ka;
+// compute_si_to sink of the fused trace kernel and hf_si_kernel (KA: their kernarg pointer type): a field goes to memory
+// when it is final; the row pointers are read from the kernarg segment at the store
+template <typename KA>
+struct hf_si_sink {
+    KA ka;
     size_t ub;
     uint32_t lo, flags;
     __device__ __forceinline__ void s1(float *p, float v) { st(p, ub, lo, v); }
     __device__ __forceinline__ void s3(float *p0, float *p1, float *p2, v3 v) { st(p0, ub, lo, v.x); st(p1, ub, lo, v.y); st(p2, ub, lo, v.z); }
     __device__ __forceinline__ void t(float v) { s1(ka->sio.t, v); }
     __device__ __forceinline__ void p(v3 v) { s3(ka->sio.p[0], ka->sio.p[1], ka->sio.p[2], v); }
-    __device__ __forceinline__ void boundary_test(float v) { if (flags & HF_RAY_BOUNDARYTEST) s1(ka->sio.bt, v); }
+    __device__ __forceinline__ void boundary_test(float v) { if (flags & HF_RAY_BOUNDARYTEST) s1(ka->sio.boundary_test, v); }
     __device__ __forceinline__ void uv(float a, float b) { s1(ka->sio.uv[0], a); s1(ka->sio.uv[1], b); }
     __device__ __forceinline__ void dp_du(v3 v) { s3(ka->sio.dp_du[0], ka->sio.dp_du[1], ka->sio.dp_du[2], v); }
     __device__ __forceinline__ void dp_dv(v3 v) { s3(ka->sio.dp_dv[0], ka->sio.dp_dv[1], ka->sio.dp_dv[2], v); }
@@ -1490,7 +1479,7 @@ void hf_trace_kernel(hf_trace_args a) {
                     __builtin_amdgcn_s_setprio(0);
 #endif
                     const uint32_t l4 = lane; // lane l: rays ubw + 4 l .. 4 l + 3
-                    const hf_rays_dev rp = load_rays(kw);
+                    const hf_rays_t rp = load_rays(kw);
                     const f4 ox = ((const f4 *) (rp.o[0] + ubw))[l4], oy = ((const f4 *) (rp.o[1] + ubw))[l4], oz = ((const f4 *) (rp.o[2] + ubw))[l4];
                     const f4 dx = ((const f4 *) (rp.d[0] + ubw))[l4], dy = ((const f4 *) (rp.d[1] + ubw))[l4], dz = ((const f4 *) (rp.d[2] + ubw))[l4];
                     const f4 mt = ((const f4 *) (rp.maxt + ubw))[l4];
@@ -1515,14 +1504,14 @@ void hf_trace_kernel(hf_trace_args a) {
                             ((uint32_t *) (kw->hit_out + ubw))[l4] = 0u;
                         } else {
                             const f4 inf4 = { i0, i0, i0, i0 };
-                            const hf_pi_dev pi = load_pi(kw);
+                            const hf_pi_t pi = load_pi(kw);
                             if (pi.t) st4(pi.t, ubw, l4, inf4);
-                            if (pi.u) st4(pi.u, ubw, l4, zero);
-                            if (pi.v) st4(pi.v, ubw, l4, zero);
-                            if (pi.prim) st4((float *) pi.prim, ubw, l4, zero);
+                            if (pi.prim_uv[0]) st4(pi.prim_uv[0], ubw, l4, zero);
+                            if (pi.prim_uv[1]) st4(pi.prim_uv[1], ubw, l4, zero);
+                            if (pi.prim_index) st4((float *) pi.prim_index, ubw, l4, zero);
                             if (MODE == 2) { // zero-initialised record (interaction.h:479-499, 667-673), wi = -d
                                 const uint32_t flags = kw->flags;
-                                const hf_si_dev sd = load_si(kw);
+                                const hf_si_t sd = load_si(kw);
                                 st4(sd.t, ubw, l4, inf4);
 #pragma unroll
                                 for (int c = 0; c < 3; ++c) {
@@ -1531,15 +1520,15 @@ void hf_trace_kernel(hf_trace_args a) {
                                     st4(sd.sh_s[c], ubw, l4, zero); st4(sd.sh_t[c], ubw, l4, zero);
                                 }
                                 st4(sd.uv[0], ubw, l4, zero); st4(sd.uv[1], ubw, l4, zero);
-                                if (flags & HF_RAY_BOUNDARYTEST) { const float b0 = z0 + 1e8f; const f4 big = { b0, b0, b0, b0 }; st4(sd.bt, ubw, l4, big); }
+                                if (flags & HF_RAY_BOUNDARYTEST) { const float b0 = z0 + 1e8f; const f4 big = { b0, b0, b0, b0 }; st4(sd.boundary_test, ubw, l4, big); }
                                 st4(sd.wi[0], ubw, l4, -dx); st4(sd.wi[1], ubw, l4, -dy); st4(sd.wi[2], ubw, l4, -dz);
                             }
                         }
 #ifdef HF_TSTATS
                         if (MODE != 1 && sub == 0u) { // lane 0's four prim_uv[0] entries: cycles waiting for the grab number, for the rays + test, issuing the stores
                             const long long tw3 = clock64();
-                            const hf_pi_dev pq = load_pi(kw);
-                            if (lane == 0u && pq.u) { (pq.u + ubw)[0] = (float) (tw1 - tw0); (pq.u + ubw)[1] = (float) (tw2 - tw1); (pq.u + ubw)[2] = (float) (tw3 - tw2); (pq.u + ubw)[3] = 1.f; }
+                            const hf_pi_t pq = load_pi(kw);
+                            if (lane == 0u && pq.prim_uv[0]) { (pq.prim_uv[0] + ubw)[0] = (float) (tw1 - tw0); (pq.prim_uv[0] + ubw)[1] = (float) (tw2 - tw1); (pq.prim_uv[0] + ubw)[2] = (float) (tw3 - tw2); (pq.prim_uv[0] + ubw)[3] = 1.f; }
                         }
 #endif
                         sub += 192u; // (+ 64 by the loop: the next fetch of the grab)
@@ -1564,7 +1553,7 @@ void hf_trace_kernel(hf_trace_args a) {
             const bool valid = lane < left;
             const uint32_t lo = valid ? lane : (uint32_t) (left - 1);
             if ((MODE == 2 && AUX) || (sub & 255u) == 0u) { // first batch of a fetch: nothing was requested ahead (see the end of the body; AUX never requests ahead)
-                const hf_rays_dev rp = load_rays(ka);
+                const hf_rays_t rp = load_rays(ka);
                 o = mk3((rp.o[0] + ub)[lo], (rp.o[1] + ub)[lo], (rp.o[2] + ub)[lo]);
                 d = mk3((rp.d[0] + ub)[lo], (rp.d[1] + ub)[lo], (rp.d[2] + ub)[lo]);
                 maxt = (rp.maxt + ub)[lo];
@@ -1588,12 +1577,12 @@ void hf_trace_kernel(hf_trace_args a) {
                                 if (valid) {
                                     const uint32_t flags = ka->flags;
                                     const size_t ubo = ub + (size_t) ak * ka->aux_stride;
-                                    const hf_pi_dev pi = load_pi(ka);
+                                    const hf_pi_t pi = load_pi(ka);
                                     if (pi.t) (pi.t + ubo)[lo] = __builtin_inff();
-                                    if (pi.u) (pi.u + ubo)[lo] = 0.f;
-                                    if (pi.v) (pi.v + ubo)[lo] = 0.f;
-                                    if (pi.prim) (pi.prim + ubo)[lo] = 0u;
-                                    hf_si_store_sink out = { ka, ubo, lo, flags };
+                                    if (pi.prim_uv[0]) (pi.prim_uv[0] + ubo)[lo] = 0.f;
+                                    if (pi.prim_uv[1]) (pi.prim_uv[1] + ubo)[lo] = 0.f;
+                                    if (pi.prim_index) (pi.prim_index + ubo)[lo] = 0u;
+                                    hf_si_sink<hf_kargs_ptr> out = { ka, ubo, lo, flags };
                                     si_miss_to(out, flags); // (the launcher culls only when si.wi -- minus the sample's direction -- is not asked for)
                                 }
                             }
@@ -1607,7 +1596,7 @@ void hf_trace_kernel(hf_trace_args a) {
             if (MODE == 2 && AUX) {
                 asm volatile("" : "+s"(ka)); // opaque per sample: kernarg loads stay inside the loop instead of being hoisted (and spilled)
                 // the ray again (an L1 / L2 hit from the second sample on): nothing of it is held across the walk
-                const hf_rays_dev rp = load_rays(ka);
+                const hf_rays_t rp = load_rays(ka);
                 o = mk3((rp.o[0] + ub)[lo], (rp.o[1] + ub)[lo], (rp.o[2] + ub)[lo]);
                 const v3 dr = mk3((rp.d[0] + ub)[lo], (rp.d[1] + ub)[lo], (rp.d[2] + ub)[lo]);
                 hf_reparam_args sa = {};
@@ -1685,7 +1674,7 @@ void hf_trace_kernel(hf_trace_args a) {
             } else if (((sub + 64u) & 255u) != 0u && sub + 64 < grab && ub + 64 < n) { // (the next fetch decides about its own rays)
                 const size_t ub2 = ub + 64, left2 = n - ub2;
                 const uint32_t lo2 = lane < left2 ? lane : (uint32_t) (left2 - 1);
-                const hf_rays_dev rp = load_rays(ka);
+                const hf_rays_t rp = load_rays(ka);
                 o = mk3((rp.o[0] + ub2)[lo2], (rp.o[1] + ub2)[lo2], (rp.o[2] + ub2)[lo2]);
                 d = mk3((rp.d[0] + ub2)[lo2], (rp.d[1] + ub2)[lo2], (rp.d[2] + ub2)[lo2]);
                 maxt = (rp.maxt + ub2)[lo2];
@@ -1697,17 +1686,17 @@ void hf_trace_kernel(hf_trace_args a) {
                 uint8_t *hit_out = ka->hit_out;
                 (hit_out + ub)[lo] = best.hit ? 1 : 0;
             } else {
-                const hf_pi_dev pi = load_pi(ka);
+                const hf_pi_t pi = load_pi(ka);
                 if (pi.t) (pi.t + ubo)[lo] = best.hit ? best.t : __builtin_inff();
-                if (pi.u) (pi.u + ubo)[lo] = best.hit ? best.u : 0.f;
-                if (pi.v) (pi.v + ubo)[lo] = best.hit ? best.v : 0.f;
-                if (pi.prim) (pi.prim + ubo)[lo] = best.hit ? best.prim : 0u;
+                if (pi.prim_uv[0]) (pi.prim_uv[0] + ubo)[lo] = best.hit ? best.u : 0.f;
+                if (pi.prim_uv[1]) (pi.prim_uv[1] + ubo)[lo] = best.hit ? best.v : 0.f;
+                if (pi.prim_index) (pi.prim_index + ubo)[lo] = best.hit ? best.prim : 0u;
                 if (MODE == 2) {
                     const uint32_t flags = ka->flags;
-                    hf_si_store_sink out = { ka, ubo, lo, flags };
+                    hf_si_sink<hf_kargs_ptr> out = { ka, ubo, lo, flags };
                     if (best.hit) {
                         // the origin is only needed by a hit: read again (an L2 hit) rather than held across the walk
-                        const hf_rays_dev rp = load_rays(ka);
+                        const hf_rays_t rp = load_rays(ka);
                         const v3 ow = mk3((rp.o[0] + ub)[lo], (rp.o[1] + ub)[lo], (rp.o[2] + ub)[lo]);
                         const hf_dev_field fl = load_field(&ka->f); // to_world etc.: not held across the walk
                         // every field is stored as soon as it is final: the record is never whole in registers
@@ -1741,23 +1730,6 @@ static int grid_for(size_t n, size_t cap = HF_FLAT_GRID_CAP) {
 #ifndef HF_SI_GRID_CAP
 #define HF_SI_GRID_CAP (256 * 1024)
 #endif
-
-static hf_rays_dev to_dev(const hf_rays_t *r) {
-    hf_rays_dev d;
-    for (int k = 0; k < 3; ++k) { d.o[k] = r->o[k]; d.d[k] = r->d[k]; }
-    d.maxt = r->maxt;
-    return d;
-}
-static hf_si_dev to_dev(const hf_si_t *s) {
-    hf_si_dev d;
-    d.t = s->t; d.bt = s->boundary_test;
-    for (int k = 0; k < 3; ++k) {
-        d.p[k] = s->p[k]; d.n[k] = s->n[k]; d.sh_n[k] = s->sh_n[k]; d.dp_du[k] = s->dp_du[k];
-        d.dp_dv[k] = s->dp_dv[k]; d.sh_s[k] = s->sh_s[k]; d.sh_t[k] = s->sh_t[k]; d.wi[k] = s->wi[k];
-    }
-    d.uv[0] = s->uv[0]; d.uv[1] = s->uv[1];
-    return d;
-}
 
 // Rays per fetch: HF_GRAB for big wavefronts (a single counter serves ~80 fetches/us, which caps the rate of rays
 // that only stream), fewer for smaller ones so that every resident wave gets about HF_FETCHES_PER_WAVE fetches: the
@@ -1798,25 +1770,22 @@ void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t 
                      hipStream_t stream, const hf_reparam_args *aux, bool lean) {
     if (n == 0) return;
     (void) hipMemsetAsync(scratch, 0, HF_SCR_BYTES, stream);
-    hf_pi_dev p = { nullptr, nullptr, nullptr, nullptr };
-    if (pi) { p.t = pi->t; p.u = pi->prim_uv[0]; p.v = pi->prim_uv[1]; p.prim = pi->prim_index; }
-    hf_si_dev sd;
-    memset(&sd, 0, sizeof(sd));
-    if (si) sd = to_dev(si);
-    const hf_rays_dev r = to_dev(rays);
+    const hf_pi_t p = pi ? *pi : hf_pi_t{};
+    const hf_si_t sd = si ? *si : hf_si_t{};
     const uint32_t grab = hf_grab_for(n, mode);
     size_t waves = (n + grab - 1) / grab, blocks = (waves + 3) / 4;
     const size_t per_cu = lean ? ((aux && mode == 2) ? HF_LEAN_WAVES_AUX : HF_LEAN_WAVES) : mode == 2 ? HF_TRACE_WAVES_FUSED : HF_TRACE_WAVES;
     if (blocks > 256 * per_cu) blocks = 256 * per_cu; // the resident set: that many workgroups per CU
     const dim3 grid((unsigned) blocks), block(HF_BLOCK);
     hf_trace_args a;
-    a.f = f; a.n = n; a.rays = r; a.active = active; a.pi = p; a.hit_out = hit; a.sio = sd; a.flags = flags;
+    a.f = f; a.n = n; a.rays = *rays; a.active = active; a.pi = p; a.hit_out = hit; a.sio = sd; a.flags = flags;
     a.counter = (unsigned long long *) scratch; a.grab = grab;
     {   // the wide path reads and writes 16 bytes per lane: every row it touches must be 16-byte aligned
         uintptr_t bits = 0;
-        for (int k = 0; k < 3; ++k) bits |= (uintptr_t) r.o[k] | (uintptr_t) r.d[k];
-        bits |= (uintptr_t) r.maxt | (uintptr_t) p.t | (uintptr_t) p.u | (uintptr_t) p.v | (uintptr_t) p.prim;
+        for (int k = 0; k < 3; ++k) bits |= (uintptr_t) rays->o[k] | (uintptr_t) rays->d[k];
+        bits |= (uintptr_t) rays->maxt | (uintptr_t) p.t | (uintptr_t) p.prim_uv[0] | (uintptr_t) p.prim_uv[1] | (uintptr_t) p.prim_index;
         if (mode == 1) bits |= (uintptr_t) hit << 2; // (4 bytes per lane)
+        static_assert(sizeof(hf_si_t) == 28 * sizeof(float *), "hf_si_t: nothing but its 28 float * rows");
         const float *const *rows = (const float *const *) &sd;
         for (size_t k = 0; k < sizeof(sd) / sizeof(float *); ++k) bits |= (uintptr_t) rows[k];
         a.wide = (active == nullptr && (bits & 15u) == 0u && grab % 256u == 0u) ? 1u : 0u;
@@ -1848,23 +1817,12 @@ void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t 
         a.aux_cull = 0.f;
 #endif
     }
-    if (lean) {
-        if (mode == 0)
-            hipLaunchKernelGGL((hf_trace_kernel<0, false, true>), grid, block, 0, stream, a);
-        else if (mode == 1)
-            hipLaunchKernelGGL((hf_trace_kernel<1, false, true>), grid, block, 0, stream, a);
-        else if (a.aux_on)
-            hipLaunchKernelGGL((hf_trace_kernel<2, true, true>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((hf_trace_kernel<2, false, true>), grid, block, 0, stream, a);
-    } else if (mode == 0)
-        hipLaunchKernelGGL(hf_trace_kernel<0>, grid, block, 0, stream, a);
-    else if (mode == 1)
-        hipLaunchKernelGGL(hf_trace_kernel<1>, grid, block, 0, stream, a);
-    else if (a.aux_on)
-        hipLaunchKernelGGL((hf_trace_kernel<2, true>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL(hf_trace_kernel<2>, grid, block, 0, stream, a);
+    // [lean][mode + aux]: the auxiliary-ray sampling exists in the fused mode only
+    static void (*const kernel[2][4])(hf_trace_args) = {
+        { hf_trace_kernel<0>, hf_trace_kernel<1>, hf_trace_kernel<2>, hf_trace_kernel<2, true> },
+        { hf_trace_kernel<0, false, true>, hf_trace_kernel<1, false, true>, hf_trace_kernel<2, false, true>, hf_trace_kernel<2, true, true> },
+    };
+    hipLaunchKernelGGL(kernel[lean][mode + a.aux_on], grid, block, 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1875,41 +1833,20 @@ void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t 
 struct hf_si_args {
     hf_dev_field f;
     size_t n;
-    hf_rays_dev rays;
+    hf_rays_t rays;
     hf_pi_const_t pi;
     const uint8_t *active;
-    hf_si_dev sio;
+    hf_si_t sio;
     uint32_t flags;
 };
-// compute_si_to sink of hf_si_kernel: a field goes to memory when it is final, row pointers from the kernarg segment
-struct hf_si_kernel_sink {
-    const __attribute__((address_space(4))) hf_si_args *ka;
-    size_t ub;
-    uint32_t lo, flags;
-    __device__ __forceinline__ void s1(float *p, float v) { st(p, ub, lo, v); }
-    __device__ __forceinline__ void s3(float *p0, float *p1, float *p2, v3 v) { st(p0, ub, lo, v.x); st(p1, ub, lo, v.y); st(p2, ub, lo, v.z); }
-    __device__ __forceinline__ void t(float v) { s1(ka->sio.t, v); }
-    __device__ __forceinline__ void p(v3 v) { s3(ka->sio.p[0], ka->sio.p[1], ka->sio.p[2], v); }
-    __device__ __forceinline__ void boundary_test(float v) { if (flags & HF_RAY_BOUNDARYTEST) s1(ka->sio.bt, v); }
-    __device__ __forceinline__ void uv(float a, float b) { s1(ka->sio.uv[0], a); s1(ka->sio.uv[1], b); }
-    __device__ __forceinline__ void dp_du(v3 v) { s3(ka->sio.dp_du[0], ka->sio.dp_du[1], ka->sio.dp_du[2], v); }
-    __device__ __forceinline__ void dp_dv(v3 v) { s3(ka->sio.dp_dv[0], ka->sio.dp_dv[1], ka->sio.dp_dv[2], v); }
-    __device__ __forceinline__ void n(v3 v) {
-        s3(ka->sio.n[0], ka->sio.n[1], ka->sio.n[2], v);
-        s3(ka->sio.sh_n[0], ka->sio.sh_n[1], ka->sio.sh_n[2], v);
-    }
-    __device__ __forceinline__ void sh_s(v3 v) { s3(ka->sio.sh_s[0], ka->sio.sh_s[1], ka->sio.sh_s[2], v); }
-    __device__ __forceinline__ void sh_t(v3 v) { s3(ka->sio.sh_t[0], ka->sio.sh_t[1], ka->sio.sh_t[2], v); }
-    __device__ __forceinline__ void wi(v3 v) { s3(ka->sio.wi[0], ka->sio.wi[1], ka->sio.wi[2], v); }
-};
+typedef const __attribute__((address_space(4))) hf_si_args *hf_si_kargs;
 
 __global__ __launch_bounds__(HF_BLOCK) void hf_si_kernel(hf_si_args a_) {
     (void) a_;
     const uint32_t lane = threadIdx.x & 63u;
     const size_t stride = (size_t) gridDim.x * HF_BLOCK;
     for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u);; ub += stride) {
-        const __attribute__((address_space(4))) hf_si_args *ka =
-            (const __attribute__((address_space(4))) hf_si_args *) __builtin_amdgcn_kernarg_segment_ptr();
+        hf_si_kargs ka = (hf_si_kargs) __builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(ka)); // opaque: keeps the loads that follow where they are written
         const size_t n = ka->n;
         if (ub >= n) break; // wave-uniform
@@ -1921,7 +1858,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_si_kernel(hf_si_args a_) {
         const uint8_t *active = ka->active;
         const bool act = (active ? ((active + ub)[lo] != 0) : true) && (t != __builtin_inff());
         const uint32_t flags = ka->flags;
-        hf_si_kernel_sink out = { ka, ub, lo, flags };
+        hf_si_sink<hf_si_kargs> out = { ka, ub, lo, flags };
         if (act) {
             const float b1 = (ka->pi.prim_uv[0] + ub)[lo], b2 = (ka->pi.prim_uv[1] + ub)[lo];
             const uint32_t prim = (ka->pi.prim_index + ub)[lo];
@@ -1938,7 +1875,7 @@ void hf_launch_si(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const 
                   const uint8_t *active, const hf_si_t *si, uint32_t flags, hipStream_t stream) {
     if (n == 0) return;
     hf_si_args a;
-    a.f = f; a.n = n; a.rays = to_dev(rays); a.pi = *pi; a.active = active; a.sio = to_dev(si); a.flags = flags;
+    a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.sio = *si; a.flags = flags;
     hipLaunchKernelGGL(hf_si_kernel, dim3(grid_for(n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, a);
 }
 
@@ -1995,7 +1932,7 @@ __device__ __forceinline__ v3 reparam_grad_vdirect(const hf_reparam_args &a, siz
 struct hf_adjoint_args {
     hf_dev_field f;
     size_t n;
-    hf_rays_dev rays;
+    hf_rays_t rays;
     hf_pi_const_t pi;
     const uint8_t *active;
     hf_si_grad_t g;
@@ -2203,7 +2140,7 @@ void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
                        float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream) {
     if (n == 0) return;
     hf_adjoint_args a;
-    a.f = f; a.n = n; a.rays = to_dev(rays); a.pi = *pi; a.active = active; a.g = *gs; a.flags = flags; a.grad_h = grad_h;
+    a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.g = *gs; a.flags = flags; a.grad_h = grad_h;
     a.row_band = row_band;
     for (int k = 0; k < 3; ++k) { a.go[k] = grad_o ? grad_o[k] : nullptr; a.gd[k] = grad_d ? grad_d[k] : nullptr; }
     if (grad_o || grad_d) hipLaunchKernelGGL(hf_adjoint_kernel<true>, dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a);
@@ -2221,7 +2158,7 @@ void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
 struct hf_tangent_args {
     hf_dev_field f;
     size_t n;
-    hf_rays_dev rays;
+    hf_rays_t rays;
     hf_pi_const_t pi;
     const uint8_t *active;
     const float *dh;            // [H*W] height tangent, NULL = zero
@@ -2338,7 +2275,7 @@ void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
                        const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream) {
     if (n == 0) return;
     hf_tangent_args a;
-    a.f = f; a.n = n; a.rays = to_dev(rays); a.pi = *pi; a.active = active; a.dh = dh; a.out = *out; a.flags = flags;
+    a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.dh = dh; a.out = *out; a.flags = flags;
     bool raytan = false;
     for (int k = 0; k < 3; ++k) {
         a.d_o[k] = d_o ? d_o[k] : nullptr; a.d_d[k] = d_d ? d_d[k] : nullptr;
@@ -2640,8 +2577,44 @@ hipError_t hf_launch_adam(size_t n, float *h, const float *g, float *m, float *v
 struct hf_f3ptr { const float *p[3]; };
 struct hf_f3out { float *p[3]; };
 
-// POINT: L.l[k] is the light's position and L.w[k] = albedo/pi * intensity; the direction towards the light and the
-// inverse-square falloff are per sample (src/emitters/point.cpp: d = pos - it.p, spec = intensity / |d|^2)
+// light k seen from p: the unit direction towards it (returned) and ir = 1/|v|.  POINT: L.l[k] is the light's position and
+// L.w[k] = albedo/pi * intensity; the direction towards the light and the inverse-square falloff L.w[k] ir^2 are per
+// sample (src/emitters/point.cpp: d = pos - it.p, spec = intensity / |d|^2).  (The weight is left to the callers: read
+// here, the adjoint's load of it would leave the branch that uses it.)
+template <bool POINT>
+__device__ __forceinline__ v3 light_dir(const hf_lights_dev &L, uint32_t k, v3 p, float &ir) {
+    v3 l = mk3(L.l[k][0], L.l[k][1], L.l[k][2]);
+    ir = 1.f;
+    if (POINT) {
+        const v3 v = l - p;
+        ir = 1.0f / __builtin_sqrtf(dot3(v, v));
+        l = v * ir;
+    }
+    return l;
+}
+
+// the box-filter film: sample i's value c of light k, averaged over the spp samples of its pixel into image[k * npix + pixel].
+// spp a power of two: a butterfly over the g = min(spp, 64) lanes of a pixel (DPP within rows of 16, cross-lane beyond),
+// then one store (the wave holds whole pixels) or atomic (several waves per pixel); otherwise one atomic per sample
+__device__ __forceinline__ void film_pixel(float *image, float c, uint32_t k, size_t npix, size_t i, uint32_t spp, bool in,
+                                           bool pow2, uint32_t g, float inv_spp) {
+    if (pow2) {
+        if (g > 1u) c += HF_DPP_ADD(c, 0xB1);   // quad_perm [1,0,3,2]
+        if (g > 2u) c += HF_DPP_ADD(c, 0x4E);   // quad_perm [2,3,0,1]
+        if (g > 4u) c += HF_DPP_ADD(c, 0x141);  // row_half_mirror: the other quad pair
+        if (g > 8u) c += HF_DPP_ADD(c, 0x140);  // row_mirror: the other half row
+        if (g > 16u) c += __shfl_xor(c, 16);
+        if (g > 32u) c += __shfl_xor(c, 32);
+        if (in && (threadIdx.x & (g - 1u)) == 0u) {
+            if (spp <= 64u) image[k * npix + i / spp] = c * inv_spp;
+            else            atomicAdd(&image[k * npix + i / spp], c * inv_spp);
+        }
+    } else if (in) {
+        atomicAdd(&image[k * npix + i / spp], c * inv_spp);
+    }
+}
+
+// POINT: point lights (light_dir)
 template <bool POINT>
 __global__ __launch_bounds__(HF_BLOCK) void hf_direct_kernel(size_t n, uint32_t spp, hf_f3ptr sn, hf_f3ptr dd,
                                                             const float *__restrict__ t, hf_f3ptr pp, hf_lights_dev L,
@@ -2659,32 +2632,13 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_direct_kernel(size_t n, uint32_t 
     v3 p = mk3(0.f, 0.f, 0.f);
     if (POINT) p = mk3(pp.p[0][ii], pp.p[1][ii], pp.p[2][ii]);
     for (uint32_t k = 0; k < L.n; ++k) {
-        v3 l = mk3(L.l[k][0], L.l[k][1], L.l[k][2]);
-        float wk = L.w[k];
-        if (POINT) {
-            const v3 v = l - p;
-            const float ir = 1.0f / __builtin_sqrtf(dot3(v, v));
-            l = v * ir;
-            wk = wk * (ir * ir);
-        }
+        float ir;
+        const v3 l = light_dir<POINT>(L, k, p, ir);
+        const float wk = POINT ? L.w[k] * (ir * ir) : L.w[k];
         const float co = dot3(nn, l);
         float c = (lit && co > 0.f && (L.vis[k] ? L.vis[k][ii] != 0 : true)) ? wk * co : 0.f;
         if (L.weight) c *= L.weight[ii];
-        if (pow2) {
-            // butterfly over the g = min(spp, 64) lanes of a pixel: DPP within rows of 16, cross-lane beyond
-            if (g > 1u) c += HF_DPP_ADD(c, 0xB1);   // quad_perm [1,0,3,2]
-            if (g > 2u) c += HF_DPP_ADD(c, 0x4E);   // quad_perm [2,3,0,1]
-            if (g > 4u) c += HF_DPP_ADD(c, 0x141);  // row_half_mirror: the other quad pair
-            if (g > 8u) c += HF_DPP_ADD(c, 0x140);  // row_mirror: the other half row
-            if (g > 16u) c += __shfl_xor(c, 16);
-            if (g > 32u) c += __shfl_xor(c, 32);
-            if (in && (threadIdx.x & (g - 1u)) == 0u) {
-                if (spp <= 64u) image[k * npix + i / spp] = c * inv_spp;          // the wave holds whole pixels
-                else            atomicAdd(&image[k * npix + i / spp], c * inv_spp); // several waves per pixel
-            }
-        } else if (in) {
-            atomicAdd(&image[k * npix + i / spp], c * inv_spp);
-        }
+        film_pixel(image, c, k, npix, i, spp, in, pow2, g, inv_spp);
     }
 }
 
@@ -2706,13 +2660,8 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_direct_adjoint_kernel(size_t n, u
     const float wgt = L.weight ? L.weight[i] : 1.f;
     float gw = 0.f; // dL/dweight: the unweighted sample values against the image gradient
     for (uint32_t k = 0; k < L.n; ++k) {
-        v3 l = mk3(L.l[k][0], L.l[k][1], L.l[k][2]);
-        float ir = 1.f;
-        if (POINT) {
-            const v3 v = l - p;
-            ir = 1.0f / __builtin_sqrtf(dot3(v, v));
-            l = v * ir;
-        }
+        float ir;
+        const v3 l = light_dir<POINT>(L, k, p, ir);
         const float co = dot3(nn, l);
         if (lit && co > 0.f && (L.vis[k] ? L.vis[k][i] != 0 : true)) {
             float w = (L.w[k] * inv_spp) * gimg[k * npix + pix];
@@ -2762,14 +2711,9 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_direct_tangent_kernel(size_t n, u
         if (dpp.p[0]) dq = mk3(dpp.p[0][ii], dpp.p[1][ii], dpp.p[2][ii]);
     }
     for (uint32_t k = 0; k < L.n; ++k) {
-        v3 l = mk3(L.l[k][0], L.l[k][1], L.l[k][2]);
-        float wk = L.w[k], ir = 1.f;
-        if (POINT) {
-            const v3 v = l - p;
-            ir = 1.0f / __builtin_sqrtf(dot3(v, v));
-            l = v * ir;
-            wk = wk * (ir * ir);
-        }
+        float ir;
+        const v3 l = light_dir<POINT>(L, k, p, ir);
+        const float wk = POINT ? L.w[k] * (ir * ir) : L.w[k];
         const float co = dot3(nn, l);
         float c = 0.f;
         if (lit && co > 0.f && (L.vis[k] ? L.vis[k][ii] != 0 : true)) {
@@ -2777,20 +2721,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_direct_tangent_kernel(size_t n, u
             if (POINT) s = __builtin_fmaf(ir, __builtin_fmaf(3.f * co, dot3(l, dq), -dot3(nn, dq)), s);
             c = wk * __builtin_fmaf(wgt, s, co * dwgt);
         }
-        if (pow2) { // the primal's butterfly over the lanes of a pixel (hf_direct_kernel)
-            if (g > 1u) c += HF_DPP_ADD(c, 0xB1);
-            if (g > 2u) c += HF_DPP_ADD(c, 0x4E);
-            if (g > 4u) c += HF_DPP_ADD(c, 0x141);
-            if (g > 8u) c += HF_DPP_ADD(c, 0x140);
-            if (g > 16u) c += __shfl_xor(c, 16);
-            if (g > 32u) c += __shfl_xor(c, 32);
-            if (in && (threadIdx.x & (g - 1u)) == 0u) {
-                if (spp <= 64u) dimage[k * npix + i / spp] = c * inv_spp;
-                else            atomicAdd(&dimage[k * npix + i / spp], c * inv_spp);
-            }
-        } else if (in) {
-            atomicAdd(&dimage[k * npix + i / spp], c * inv_spp);
-        }
+        film_pixel(dimage, c, k, npix, i, spp, in, pow2, g, inv_spp); // (the primal's film)
     }
 }
 
@@ -2851,19 +2782,18 @@ void hf_launch_film_splat(const hf_splat_args &a, bool adjoint, hipStream_t stre
     else         hipLaunchKernelGGL(hf_film_splat_kernel<false>, grid, block, 0, stream, a);
 }
 
+// the rows of a [3, n] argument; NULL: three NULL rows
+static hf_f3ptr f3ptr(const float *const r[3]) { return r ? hf_f3ptr{ { r[0], r[1], r[2] } } : hf_f3ptr{}; }
+static hf_f3out f3out(float *const r[3]) { return r ? hf_f3out{ { r[0], r[1], r[2] } } : hf_f3out{}; }
+
 void hf_launch_direct(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
                       const float *const p[3], const hf_lights_dev &lights, float *image, hipStream_t stream) {
     if (n == 0) return;
     const bool pow2 = (spp & (spp - 1u)) == 0u;
     if (!pow2 || spp > 64u) (void) hipMemsetAsync(image, 0, sizeof(float) * lights.n * (n / spp), stream); // atomic paths
-    hf_f3ptr sn = { { sh_n[0], sh_n[1], sh_n[2] } }, dd = { { d[0], d[1], d[2] } }, pp = { { nullptr, nullptr, nullptr } };
-    const size_t blocks = (n + HF_BLOCK - 1) / HF_BLOCK;
-    if (p) { // point lights
-        pp = { { p[0], p[1], p[2] } };
-        hipLaunchKernelGGL(hf_direct_kernel<true>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t, pp, lights, image);
-    } else {
-        hipLaunchKernelGGL(hf_direct_kernel<false>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t, pp, lights, image);
-    }
+    const dim3 grid((unsigned) ((n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    hipLaunchKernelGGL(p ? hf_direct_kernel<true> : hf_direct_kernel<false>, grid, block, 0, stream, n, spp, f3ptr(sh_n),
+                       f3ptr(d), t, f3ptr(p), lights, image);
 }
 
 void hf_launch_direct_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
@@ -2871,18 +2801,9 @@ void hf_launch_direct_adjoint(size_t n, uint32_t spp, const float *const sh_n[3]
                               const float *grad_image, float *const grad_sh_n[3], float *const grad_p[3],
                               hipStream_t stream) {
     if (n == 0) return;
-    hf_f3ptr sn = { { sh_n[0], sh_n[1], sh_n[2] } }, dd = { { d[0], d[1], d[2] } }, pp = { { nullptr, nullptr, nullptr } };
-    hf_f3out gn = { { grad_sh_n[0], grad_sh_n[1], grad_sh_n[2] } }, gp = { { nullptr, nullptr, nullptr } };
-    const size_t blocks = (n + HF_BLOCK - 1) / HF_BLOCK;
-    if (p) {
-        pp = { { p[0], p[1], p[2] } };
-        gp = { { grad_p[0], grad_p[1], grad_p[2] } };
-        hipLaunchKernelGGL(hf_direct_adjoint_kernel<true>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t,
-                           pp, lights, grad_image, gn, gp);
-    } else {
-        hipLaunchKernelGGL(hf_direct_adjoint_kernel<false>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t,
-                           pp, lights, grad_image, gn, gp);
-    }
+    const dim3 grid((unsigned) ((n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    hipLaunchKernelGGL(p ? hf_direct_adjoint_kernel<true> : hf_direct_adjoint_kernel<false>, grid, block, 0, stream, n, spp,
+                       f3ptr(sh_n), f3ptr(d), t, f3ptr(p), lights, grad_image, f3out(grad_sh_n), f3out(p ? grad_p : nullptr));
 }
 
 void hf_launch_direct_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
@@ -2892,19 +2813,9 @@ void hf_launch_direct_tangent(size_t n, uint32_t spp, const float *const sh_n[3]
     if (n == 0) return;
     const bool pow2 = (spp & (spp - 1u)) == 0u;
     if (!pow2 || spp > 64u) (void) hipMemsetAsync(dimage, 0, sizeof(float) * lights.n * (n / spp), stream); // atomic paths
-    hf_f3ptr sn = { { sh_n[0], sh_n[1], sh_n[2] } }, dd = { { d[0], d[1], d[2] } }, pp = { { nullptr, nullptr, nullptr } };
-    hf_f3ptr dsn = { { nullptr, nullptr, nullptr } }, dpp = { { nullptr, nullptr, nullptr } };
-    if (dsh_n) dsn = { { dsh_n[0], dsh_n[1], dsh_n[2] } };
-    if (dp) dpp = { { dp[0], dp[1], dp[2] } };
-    const size_t blocks = (n + HF_BLOCK - 1) / HF_BLOCK;
-    if (p) {
-        pp = { { p[0], p[1], p[2] } };
-        hipLaunchKernelGGL(hf_direct_tangent_kernel<true>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t,
-                           pp, lights, dsn, dpp, dweight, dimage);
-    } else {
-        hipLaunchKernelGGL(hf_direct_tangent_kernel<false>, dim3((unsigned) blocks), dim3(HF_BLOCK), 0, stream, n, spp, sn, dd, t,
-                           pp, lights, dsn, dpp, dweight, dimage);
-    }
+    const dim3 grid((unsigned) ((n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    hipLaunchKernelGGL(p ? hf_direct_tangent_kernel<true> : hf_direct_tangent_kernel<false>, grid, block, 0, stream, n, spp,
+                       f3ptr(sh_n), f3ptr(d), t, f3ptr(p), lights, f3ptr(dsh_n), f3ptr(dp), dweight, dimage);
 }
 
 // ---- warped-area reparameterisation: per-sample kernels (helpers: above hf_adjoint_kernel) ----

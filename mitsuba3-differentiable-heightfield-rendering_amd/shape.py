@@ -697,32 +697,42 @@ class Adam:
         self.shape.mark_dirty()
 
 
+def _p3(x):
+    """ctypes array of the 3 row pointers of a [3, n] tensor"""
+    return (C.c_void_p * 3)(x[0].data_ptr(), x[1].data_ptr(), x[2].data_ptr())
+
+
 def _f3(x):
     """[3, n] float32 device tensor -> (keepalive, ctypes array of 3 row pointers)"""
     x = x.to(dtype=torch.float32).contiguous()
-    return x, (C.c_void_p * 3)(x[0].data_ptr(), x[1].data_ptr(), x[2].data_ptr())
+    return x, _p3(x)
+
+
+def _lighting_inputs(sh_n, d, t, lights, vis):
+    """what both lighting Functions pass to libhf: the sh_n, d and t rows as float32, the [K, 4] lights as the
+    hf_dir_light_t array (hf_point_light_t has its packing: position, intensity) and the vis row pointers"""
+    K = lights.shape[0]
+    L = (_capi.hf_dir_light_t * K)()
+    lh = lights.detach().cpu().tolist()
+    for k in range(K):
+        L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = lh[k]
+    vis_p = None
+    if vis is not None:
+        vis = vis.to(dtype=torch.uint8).contiguous()
+        vis_p = (C.c_void_p * K)(*[vis[k].data_ptr() for k in range(K)])
+    f32 = [x.to(dtype=torch.float32).contiguous() for x in (sh_n, d, t)]
+    return (*f32, L, K, vis, vis_p)
 
 
 class _DirectLightingOp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sh_n, d, t, lights, albedo, spp, vis, weight):
-        n = sh_n.shape[1]
-        K = lights.shape[0]
-        sn, sn_p = _f3(sh_n)
-        dd, dd_p = _f3(d)
-        tt = t.to(dtype=torch.float32).contiguous()
+        sn, dd, tt, L, K, vis, vis_p = _lighting_inputs(sh_n, d, t, lights, vis)
+        n = sn.shape[1]
         ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
-        L = (_capi.hf_dir_light_t * K)()
-        lh = lights.detach().cpu().tolist()
-        for k in range(K):
-            L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = lh[k]
-        vis_p = None
-        if vis is not None:
-            vis = vis.to(dtype=torch.uint8).contiguous()
-            vis_p = (C.c_void_p * K)(*[vis[k].data_ptr() for k in range(K)])
         image = torch.empty((K, n // spp), dtype=torch.float32, device=sh_n.device)
         stream = torch.cuda.current_stream(sh_n.device).cuda_stream
-        check(_capi.lib().hf_direct_lighting_weighted(n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(),
+        check(_capi.lib().hf_direct_lighting_weighted(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(),
                                                       ww.data_ptr() if ww is not None else None, K, L, albedo,
                                                       vis_p, image.data_ptr(), stream))
         ctx.save_for_backward(sn, dd, tt, *([ww] if ww is not None else []))
@@ -736,14 +746,12 @@ class _DirectLightingOp(torch.autograd.Function):
         sn, dd, tt = ctx.saved_tensors[:3]
         ww = ctx.saved_tensors[3] if weighted else None
         n = sn.shape[1]
-        _, sn_p = _f3(sn)
-        _, dd_p = _f3(dd)
         dn, dn_p = _f3(dsh_n) if dsh_n is not None else (None, None)
         dw = dweight.to(dtype=torch.float32).contiguous() if (weighted and dweight is not None) else None
         dimage = torch.empty((K, n // spp), dtype=torch.float32, device=sn.device)
         stream = torch.cuda.current_stream(sn.device).cuda_stream
         check(_capi.lib().hf_direct_lighting_weighted_tangent(
-            n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), ww.data_ptr() if weighted else None, K, L, albedo,
+            n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), ww.data_ptr() if weighted else None, K, L, albedo,
             vis_p, C.byref(dn_p) if dn is not None else None, dw.data_ptr() if dw is not None else None,
             dimage.data_ptr(), stream))
         return dimage
@@ -754,16 +762,13 @@ class _DirectLightingOp(torch.autograd.Function):
         sn, dd, tt = ctx.saved_tensors[:3]
         ww = ctx.saved_tensors[3] if weighted else None
         n = sn.shape[1]
-        _, sn_p = _f3(sn)
-        _, dd_p = _f3(dd)
         gi = grad_image.to(dtype=torch.float32).contiguous()
         gn = torch.empty_like(sn)
         gw = torch.empty(n, dtype=torch.float32, device=sn.device) if weighted else None
-        gn_p = (C.c_void_p * 3)(gn[0].data_ptr(), gn[1].data_ptr(), gn[2].data_ptr())
         stream = torch.cuda.current_stream(sn.device).cuda_stream
         check(_capi.lib().hf_direct_lighting_weighted_adjoint(
-            n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), ww.data_ptr() if weighted else None, K, L, albedo,
-            vis_p, gi.data_ptr(), C.byref(gn_p), gw.data_ptr() if weighted else None, stream))
+            n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), ww.data_ptr() if weighted else None, K, L, albedo,
+            vis_p, gi.data_ptr(), C.byref(_p3(gn)), gw.data_ptr() if weighted else None, stream))
         return gn, None, None, None, None, None, None, gw
 
 
@@ -782,24 +787,13 @@ def direct_lighting(si, ray, lights, albedo=1.0, spp=1, vis=None, weight=None):
 class _PointLightingOp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sh_n, p, d, t, lights, albedo, spp, vis):
-        n = sh_n.shape[1]
-        K = lights.shape[0]
-        sn, sn_p = _f3(sh_n)
-        pp, pp_p = _f3(p)
-        dd, dd_p = _f3(d)
-        tt = t.to(dtype=torch.float32).contiguous()
-        L = (_capi.hf_dir_light_t * K)()   # hf_point_light_t: the same packing (position, intensity)
-        lh = lights.detach().cpu().tolist()
-        for k in range(K):
-            L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = lh[k]
-        vis_p = None
-        if vis is not None:
-            vis = vis.to(dtype=torch.uint8).contiguous()
-            vis_p = (C.c_void_p * K)(*[vis[k].data_ptr() for k in range(K)])
+        sn, dd, tt, L, K, vis, vis_p = _lighting_inputs(sh_n, d, t, lights, vis)
+        n = sn.shape[1]
+        pp = p.to(dtype=torch.float32).contiguous()
         image = torch.empty((K, n // spp), dtype=torch.float32, device=sh_n.device)
         stream = torch.cuda.current_stream(sh_n.device).cuda_stream
-        check(_capi.lib().hf_point_lighting(n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), C.byref(pp_p), K, L,
-                                            albedo, vis_p, image.data_ptr(), stream))
+        check(_capi.lib().hf_point_lighting(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), C.byref(_p3(pp)),
+                                            K, L, albedo, vis_p, image.data_ptr(), stream))
         ctx.save_for_backward(sn, pp, dd, tt)
         ctx.save_for_forward(sn, pp, dd, tt)
         ctx.misc = (L, K, albedo, spp, vis, vis_p)
@@ -810,15 +804,13 @@ class _PointLightingOp(torch.autograd.Function):
         sn, pp, dd, tt = ctx.saved_tensors
         L, K, albedo, spp, vis, vis_p = ctx.misc
         n = sn.shape[1]
-        _, sn_p = _f3(sn)
-        _, pp_p = _f3(pp)
-        _, dd_p = _f3(dd)
         dn, dn_p = _f3(dsh_n) if dsh_n is not None else (None, None)
         dq, dq_p = _f3(dp) if dp is not None else (None, None)
         dimage = torch.empty((K, n // spp), dtype=torch.float32, device=sn.device)
         stream = torch.cuda.current_stream(sn.device).cuda_stream
-        check(_capi.lib().hf_point_lighting_tangent(n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), C.byref(pp_p), K,
-                                                    L, albedo, vis_p, C.byref(dn_p) if dn is not None else None,
+        check(_capi.lib().hf_point_lighting_tangent(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(),
+                                                    C.byref(_p3(pp)), K, L, albedo, vis_p,
+                                                    C.byref(dn_p) if dn is not None else None,
                                                     C.byref(dq_p) if dq is not None else None, dimage.data_ptr(), stream))
         return dimage
 
@@ -827,16 +819,12 @@ class _PointLightingOp(torch.autograd.Function):
         sn, pp, dd, tt = ctx.saved_tensors
         L, K, albedo, spp, vis, vis_p = ctx.misc
         n = sn.shape[1]
-        _, sn_p = _f3(sn)
-        _, pp_p = _f3(pp)
-        _, dd_p = _f3(dd)
         gi = grad_image.to(dtype=torch.float32).contiguous()
         gn = torch.empty_like(sn); gp = torch.empty_like(pp)
-        gn_p = (C.c_void_p * 3)(gn[0].data_ptr(), gn[1].data_ptr(), gn[2].data_ptr())
-        gp_p = (C.c_void_p * 3)(gp[0].data_ptr(), gp[1].data_ptr(), gp[2].data_ptr())
         stream = torch.cuda.current_stream(sn.device).cuda_stream
-        check(_capi.lib().hf_point_lighting_adjoint(n, spp, C.byref(sn_p), C.byref(dd_p), tt.data_ptr(), C.byref(pp_p), K,
-                                                    L, albedo, vis_p, gi.data_ptr(), C.byref(gn_p), C.byref(gp_p), stream))
+        check(_capi.lib().hf_point_lighting_adjoint(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(),
+                                                    C.byref(_p3(pp)), K, L, albedo, vis_p, gi.data_ptr(),
+                                                    C.byref(_p3(gn)), C.byref(_p3(gp)), stream))
         return gn, gp, None, None, None, None, None, None
 
 
@@ -903,10 +891,6 @@ def film_gaussian(values, pos, width, height, stddev=0.5):
     ``direct_lighting(..., spp=1)``), ``pos`` [2, n] film positions in pixels (``workload.film_positions``).  Returns the
     normalised film [K, height * width] (accumulated value / accumulated weight); differentiable w.r.t. ``values``."""
     return _FilmGaussianOp.apply(values, pos, int(width), int(height), float(stddev))
-
-
-def _p3(x):
-    return (C.c_void_p * 3)(x[0].data_ptr(), x[1].data_ptr(), x[2].data_ptr())
 
 
 def _coordinate_system(n):
