@@ -30,6 +30,7 @@
 // set is a conservative superset of the cells the ray can hit; the per-triangle test and the tie rule are order
 // independent, so the result equals the brute force's.
 #include <stdlib.h>
+#include <type_traits>
 #include "hf_device.h"
 #include "hf_launch.h"
 
@@ -1896,6 +1897,53 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
                        __builtin_amdgcn_readlane(x, 32) | __builtin_amdgcn_readlane(x, 48));
 }
 
+__device__ __forceinline__ uint64_t wave_or(uint64_t v) {
+    return (uint64_t) wave_or((uint32_t) v) | ((uint64_t) wave_or((uint32_t) (v >> 32)) << 32);
+}
+
+// Per-wave LDS scatter tile of dL/dheight (hf_adjoint_kernel, hf_reparam_backward_kernel): TILE x TILE texels whose
+// origin (ar, ac) is wave-uniform.  A lane adds its triangle's three contributions into the tile (ds_add_f32) or, outside
+// it, straight to global memory, and records the tile rows it touched in a TILE-bit mask; the flush then adds the
+// touched rows to global memory, 64 consecutive tile entries (64 / TILE rows) per wave-instruction.  The kernels zero
+// their tile themselves (one loop): inlined from a helper, that loop reordered hf_adjoint_kernel's entry block
+template <int TILE> using hf_tile_rows = std::conditional_t<(TILE > 32), uint64_t, uint32_t>;
+// origin `off` texels before the first vertex of the first lane of `m` (a ballot), rows and columns
+__device__ __forceinline__ void tile_anchor(uint64_t m, const int (&vr)[3], const int (&vc)[3], int off, int &ar, int &ac) {
+    const int src = __builtin_ctzll(m);
+    ar = __shfl(vr[0], src) - off; ac = __shfl(vc[0], src) - off;
+}
+// one vertex's contribution g at texel (r, c).  (Per vertex, with the loop over the three at the call site: the
+// lane's vr / vc / gh arrays passed by reference are promoted to registers later and that reorders the adjoint's code)
+template <int TILE>
+__device__ __forceinline__ void tile_add(float *acc, int ar, int ac, int r, int c, float g, float *grad_h, int W,
+                                         hf_tile_rows<TILE> &rows) {
+    const int rr = r - ar, cc = c - ac;
+    if ((unsigned) rr < (unsigned) TILE && (unsigned) cc < (unsigned) TILE) {
+        atomicAdd(acc + rr * TILE + cc, g);
+        rows |= (hf_tile_rows<TILE>) 1 << rr;
+    } else {
+        atomicAdd(grad_h + (size_t) r * W + c, g);
+    }
+}
+// (rows: this lane's mask; ORed over the wave here)
+template <int TILE>
+__device__ __forceinline__ void tile_flush(float *acc, int ar, int ac, hf_tile_rows<TILE> rows, float *grad_h, int W, int lane) {
+    constexpr int R = 64 / TILE; // tile rows per wave-instruction
+    rows = wave_or(rows);
+#pragma unroll 1
+    while (rows != 0u) { // wave-uniform
+        const int k2 = stk_ctz(rows) / R;
+        rows &= R == 1 ? rows - 1u : ~((((hf_tile_rows<TILE>) 1 << R) - 1u) << (R * k2));
+        const int k = k2 * 64 + lane;
+        const float v = acc[k];
+        if (v != 0.f) {
+            const int rr = ar + k / TILE, cc = ac + k % TILE;
+            atomicAdd(grad_h + (size_t) rr * W + cc, v);
+            acc[k] = 0.f;
+        }
+    }
+}
+
 // harmonic weight of one auxiliary sample and its gradient w.r.t. the sampled direction (reparam.py:103-121)
 __device__ __forceinline__ void reparam_weight(const hf_reparam_args &a, const hf_aux_sample &q, v3 d, float B,
                                                float &w, v3 &dw) {
@@ -1908,21 +1956,38 @@ __device__ __forceinline__ void reparam_weight(const hf_reparam_args &a, const h
     const v3 tmp2 = frame_to_world(q, d, mk3(q.omega.x, q.omega.y, 0.f));
     dw = mk3(tmp1 * tmp2.x, tmp1 * tmp2.y, tmp1 * tmp2.z);
 }
-// gradient w.r.t. this sample's V_direct: backward of direction = normalize(d + V/Z),
-// divergence = (div - <V/Z, dZ>) / Z at V = 0 (reparam.py:262-281); V_i = w V_direct, div_i = <d_w_omega, V_direct>
-__device__ __forceinline__ v3 reparam_grad_vdirect(const hf_reparam_args &a, size_t i, v3 d, float w, v3 dw) {
-    const float Z = fmaxf(a.Z[i], 1e-8f), iZ = 1.0f / Z;
-    const v3 gd = mk3(a.g_dir[0][i], a.g_dir[1][i], a.g_dir[2][i]);
-    const float gdiv = a.g_div[i];
+// Adjoint of V_direct.  The upstream gradient of direction = normalize(d + V/Z), divergence = (div - <V/Z, dZ>) / Z
+// at V = 0 (reparam.py:262-281) reaches V = sum_i w_i V_direct_i and div = sum_i <d_w_omega_i, V_direct_i> of the samples
+// of a ray.  vdirect_grad_ray: the part common to the samples, from (d, g_dir, g_div) and the sums Z, dZ.  dZ_of()
+// yields dZ; it is called where hf_reparam_weight_kernel has always loaded dZ (loaded earlier, that kernel's code moves)
+struct hf_vd_grad {
+    v3 gV;       // dL/dV
+    float gdivV; // dL/ddiv
+};
+template <typename DZ>
+__device__ __forceinline__ hf_vd_grad vdirect_grad_ray(v3 d, v3 gd, float gdiv, float Zs, DZ dZ_of) {
+    const float Z = fmaxf(Zs, 1e-8f), iZ = 1.0f / Z;
     const float dd = dot3(d, d), idn = 1.0f / __builtin_sqrtf(dd);
     const float pr = dot3(d, gd) / dd;
-    const v3 dZ = mk3(a.dZ[0][i], a.dZ[1][i], a.dZ[2][i]);
+    const v3 dZ = dZ_of();
     const float c = gdiv * iZ * iZ;
-    const v3 gV = mk3((gd.x - d.x * pr) * idn * iZ - c * dZ.x, (gd.y - d.y * pr) * idn * iZ - c * dZ.y,
-                      (gd.z - d.z * pr) * idn * iZ - c * dZ.z);
-    const float gdivV = gdiv * iZ;
-    return mk3(__builtin_fmaf(w, gV.x, gdivV * dw.x), __builtin_fmaf(w, gV.y, gdivV * dw.y),
-               __builtin_fmaf(w, gV.z, gdivV * dw.z));
+    return hf_vd_grad{ mk3((gd.x - d.x * pr) * idn * iZ - c * dZ.x, (gd.y - d.y * pr) * idn * iZ - c * dZ.y,
+                           (gd.z - d.z * pr) * idn * iZ - c * dZ.z),
+                       gdiv * iZ };
+}
+// gradient w.r.t. one sample's V_direct (V_i = w V_direct, div_i = <d_w_omega, V_direct>)
+__device__ __forceinline__ v3 vdirect_grad_sample(const hf_vd_grad &g, float w, v3 dw) {
+    return mk3(__builtin_fmaf(w, g.gV.x, g.gdivV * dw.x), __builtin_fmaf(w, g.gV.y, g.gdivV * dw.y),
+               __builtin_fmaf(w, g.gV.z, g.gdivV * dw.z));
+}
+// a hit's V_direct = (p - o) / t: gradients w.r.t. p and t from gVd, po = p - o
+struct hf_vd_hit {
+    v3 gp;
+    float gt;
+};
+__device__ __forceinline__ hf_vd_hit vdirect_grad_hit(v3 gVd, v3 po, float t) {
+    const float it = 1.0f / t;
+    return hf_vd_hit{ mk3(gVd.x * it, gVd.y * it, gVd.z * it), -dot3(gVd, po) * it * it };
 }
 
 // The one kernel argument.  ~45 pointers and the field by value do not fit the scalar register file: held across the
@@ -2085,36 +2150,13 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
         if (sm != 0ull) {
             float *grad_h = adj_kargs()->grad_h;
             const int W = adj_kargs()->f.W;
-            // tile anchor from the first scattering lane (wave-uniform)
-            const int src = __builtin_ctzll(sm);
-            const int ar = __shfl(vr[0], src) - HF_ADJ_TILE / 4, ac = __shfl(vc[0], src) - HF_ADJ_TILE / 4;
-            uint32_t rows = 0u; // tile rows this lane added to
-            if (scatter) {
+            int ar, ac;
+            tile_anchor(sm, vr, vc, HF_ADJ_TILE / 4, ar, ac); // from the first scattering lane
+            hf_tile_rows<HF_ADJ_TILE> rows = 0u;
+            if (scatter)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const int rr = vr[k] - ar, cc = vc[k] - ac;
-                    if ((unsigned) rr < (unsigned) HF_ADJ_TILE && (unsigned) cc < (unsigned) HF_ADJ_TILE) {
-                        atomicAdd(acc + rr * HF_ADJ_TILE + cc, gh[k]);
-                        rows |= 1u << rr;
-                    } else {
-                        atomicAdd(grad_h + (size_t) vr[k] * W + vc[k], gh[k]);
-                    }
-                }
-            }
-            rows = wave_or(rows);
-            // flush the touched rows: 64 consecutive tile entries (two 32-texel row segments) per wave-instruction
-#pragma unroll 1
-            while (rows != 0u) { // wave-uniform
-                const int k2 = __builtin_ctz(rows) >> 1;
-                rows &= ~(3u << (2 * k2));
-                const int k = k2 * 64 + (int) lane;
-                const float v = acc[k];
-                if (v != 0.f) {
-                    const int rr = ar + k / HF_ADJ_TILE, cc = ac + k % HF_ADJ_TILE;
-                    atomicAdd(grad_h + (size_t) rr * W + cc, v);
-                    acc[k] = 0.f;
-                }
-            }
+                for (int k = 0; k < 3; ++k) tile_add<HF_ADJ_TILE>(acc, ar, ac, vr[k], vc[k], gh[k], grad_h, W, rows);
+            tile_flush<HF_ADJ_TILE>(acc, ar, ac, rows, grad_h, W, (int) lane);
         }
         if (RAYGRAD && valid) {
             hf_adj_kargs kb = adj_kargs();
@@ -2350,8 +2392,8 @@ __global__ __launch_bounds__(HF_BLOCK, (HF_RB_TILE > 32 ? 2 : 5)) void hf_repara
         for (uint32_t k = 0; k < ka->a.num_rays; ++k)
             hm |= (act && ka->a.pi.t[k * ka->a.stride + i] != __builtin_inff()) ? (1u << k) : 0u;
         if (__ballot(hm != 0u) == 0ull) continue; // wave-uniform
-        v3 o = mk3(0.f, 0.f, 0.f), d = o, gV = o;
-        float gdivV = 0.f;
+        v3 o = mk3(0.f, 0.f, 0.f), d = o;
+        hf_vd_grad g = { o, 0.f };
         v3 kept_om[HF_RB_KEEP], kept_dw[HF_RB_KEEP];
         float kept_w[HF_RB_KEEP];
 #pragma unroll
@@ -2378,22 +2420,13 @@ __global__ __launch_bounds__(HF_BLOCK, (HF_RB_TILE > 32 ? 2 : 5)) void hf_repara
                 for (uint32_t c = 0; c < HF_RB_KEEP; ++c)
                     if (k == c) { kept_om[c] = q.omega; kept_w[c] = w; kept_dw[c] = dw; } // (k is wave-uniform)
             }
-            // the part of reparam_grad_vdirect that is common to the samples of a ray
-            const float Z = fmaxf(Zs, 1e-8f), iZ = 1.0f / Z;
-            const v3 gd = mk3(ka->a.g_dir[0][i], ka->a.g_dir[1][i], ka->a.g_dir[2][i]);
-            const float gdiv = ka->a.g_div[i];
-            const float dd = dot3(d, d), idn = 1.0f / __builtin_sqrtf(dd);
-            const float pr = dot3(d, gd) / dd;
-            const float c = gdiv * iZ * iZ;
-            gV = mk3((gd.x - d.x * pr) * idn * iZ - c * dZ.x, (gd.y - d.y * pr) * idn * iZ - c * dZ.y,
-                     (gd.z - d.z * pr) * idn * iZ - c * dZ.z);
-            gdivV = gdiv * iZ;
+            g = vdirect_grad_ray(d, mk3(ka->a.g_dir[0][i], ka->a.g_dir[1][i], ka->a.g_dir[2][i]), ka->a.g_div[i], Zs, [&] { return dZ; });
         }
         // third loop: the auxiliary hits, sample by sample (wave-uniform loop, lanes with a hit take part); all
         // samples of the batch go into the tile before it is flushed
         int ar = 0, ac = 0;   // tile anchor (wave-uniform), set at the first sample with a hit
         bool anchored = false;
-        uint64_t rows = 0ull;
+        hf_tile_rows<HF_RB_TILE> rows = 0u;
         const uint32_t hm_any = wave_or(hm);
         for (uint32_t k = 0; k < ka->a.num_rays; ++k) {
             if (((hm_any >> k) & 1u) == 0u) continue; // wave-uniform
@@ -2416,8 +2449,7 @@ __global__ __launch_bounds__(HF_BLOCK, (HF_RB_TILE > 32 ? 2 : 5)) void hf_repara
                     aux_sample(sa, i, d, q);
                     reparam_weight(sa, q, d, ka->a.si_bt[k * ka->a.stride + i], w, dw);
                 }
-                const v3 gVd = mk3(__builtin_fmaf(w, gV.x, gdivV * dw.x), __builtin_fmaf(w, gV.y, gdivV * dw.y),
-                                   __builtin_fmaf(w, gV.z, gdivV * dw.z));
+                const v3 gVd = vdirect_grad_sample(g, w, dw);
                 const v3 da = frame_to_world(q, d, q.omega); // the auxiliary direction (= hf_reparam_aux_kernel's)
                 const float b1 = ka->a.pi.prim_uv[0][k * ka->a.stride + i], b2 = ka->a.pi.prim_uv[1][k * ka->a.stride + i];
                 const float b0 = 1.f - b1 - b2;
@@ -2427,9 +2459,7 @@ __global__ __launch_bounds__(HF_BLOCK, (HF_RB_TILE > 32 ? 2 : 5)) void hf_repara
                 prim_world(load_field(&ka->f), ka->a.pi.prim_index[k * ka->a.stride + i], P, U, V, vi, vj);
                 // V_direct = (p - o) / t with the FollowShape t = sqrt(|p - o|^2 / |d_aux|^2) of compute_si
                 const auto [po, dda, tt] = follow_t(bary_point(P, b0, b1, b2), o, da);
-                const float it = 1.0f / tt;
-                v3 gp = mk3(gVd.x * it, gVd.y * it, gVd.z * it);
-                const float gt = -dot3(gVd, po) * it * it;
+                auto [gp, gt] = vdirect_grad_hit(gVd, po, tt);
                 axpy3(gt / (tt * dda), po, gp); // t's dependence on p (hf_adjoint_kernel, FollowShape branch)
                 // p = sum b_k P_k with detached barycentrics; dP_k/dh_k = s * (third column of to_world)
                 const v3 ez = mk3(ka->f.to_world[2], ka->f.to_world[6], ka->f.to_world[10]);
@@ -2442,39 +2472,14 @@ __global__ __launch_bounds__(HF_BLOCK, (HF_RB_TILE > 32 ? 2 : 5)) void hf_repara
                 vc[0] = vj[0]; vc[1] = vj[1]; vc[2] = vj[2];
             }
             if (!anchored) { // wave-uniform: the first sample with a hit anchors the tile
-                const int src = __builtin_ctzll(__ballot(hit));
-                ar = __shfl(vr[0], src) - HF_RB_ANCHOR; ac = __shfl(vc[0], src) - HF_RB_ANCHOR;
+                tile_anchor(__ballot(hit), vr, vc, HF_RB_ANCHOR, ar, ac);
                 anchored = true;
             }
-            if (hit) {
+            if (hit)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int rr = vr[c] - ar, cc = vc[c] - ac;
-                    if ((unsigned) rr < (unsigned) HF_RB_TILE && (unsigned) cc < (unsigned) HF_RB_TILE) {
-                        atomicAdd(acc + rr * HF_RB_TILE + cc, gh[c]);
-                        rows |= 1ull << rr;
-                    } else {
-                        atomicAdd(ka->a.grad_h + (size_t) vr[c] * ka->f.W + vc[c], gh[c]);
-                    }
-                }
-            }
+                for (int c = 0; c < 3; ++c) tile_add<HF_RB_TILE>(acc, ar, ac, vr[c], vc[c], gh[c], ka->a.grad_h, ka->f.W, rows);
         }
-        rows = (uint64_t) wave_or((uint32_t) rows) | ((uint64_t) wave_or((uint32_t) (rows >> 32)) << 32);
-#pragma unroll 1
-        while (rows != 0ull) { // flush the touched rows: 64 consecutive tile entries per wave-instruction
-            const int rr = __builtin_ctzll(rows);
-            rows &= rows - 1ull;
-            for (int c0 = 0; c0 < HF_RB_TILE; c0 += 64) {
-                const int cc = c0 + lane;
-                if (cc < HF_RB_TILE) {
-                    const float v = acc[rr * HF_RB_TILE + cc];
-                    if (v != 0.f) {
-                        atomicAdd(ka->a.grad_h + (size_t) (ar + rr) * ka->f.W + (ac + cc), v);
-                        acc[rr * HF_RB_TILE + cc] = 0.f;
-                    }
-                }
-            }
-        }
+        tile_flush<HF_RB_TILE>(acc, ar, ac, rows, ka->a.grad_h, ka->f.W, lane);
     }
 }
 
@@ -2852,13 +2857,16 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_reparam_weight_kernel(hf_reparam_
     v3 gp = mk3(0.f, 0.f, 0.f), gvd = mk3(0.f, 0.f, 0.f);
     float gt = 0.f;
     if (act) {
-        const v3 gVd = reparam_grad_vdirect(a, i, d, w, dw);
+        const float Zs = a.Z[i];
+        const v3 gd = mk3(a.g_dir[0][i], a.g_dir[1][i], a.g_dir[2][i]);
+        const float gdiv = a.g_div[i];
+        const hf_vd_grad g = vdirect_grad_ray(d, gd, gdiv, Zs, [&] { return mk3(a.dZ[0][i], a.dZ[1][i], a.dZ[2][i]); });
+        const v3 gVd = vdirect_grad_sample(g, w, dw);
         gvd = gVd;
         if (hit) { // V_direct = (p - o) / t
-            const v3 po = mk3(a.si_p[0][i] - o.x, a.si_p[1][i] - o.y, a.si_p[2][i] - o.z);
-            const float it = 1.0f / t;
-            gp = mk3(gVd.x * it, gVd.y * it, gVd.z * it);
-            gt = -dot3(gVd, po) * it * it;
+            const hf_vd_hit h = vdirect_grad_hit(gVd, mk3(a.si_p[0][i] - o.x, a.si_p[1][i] - o.y, a.si_p[2][i] - o.z), t);
+            gp = h.gp;
+            gt = h.gt;
         }
     }
     a.g_p[0][i] = gp.x; a.g_p[1][i] = gp.y; a.g_p[2][i] = gp.z;

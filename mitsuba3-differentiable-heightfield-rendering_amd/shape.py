@@ -906,7 +906,120 @@ def _coordinate_system(n):
 
 
 REPARAM_FUSED = True   # tests switch this off to compare with the per-sample kernels
-REPARAM_ONE_LAUNCH = True   # ... and this one to compare hf_reparam_trace_all with num_rays x hf_reparam_trace
+# The auxiliary hits of the first loop (36 B per ray and sample: pi + si.t, si.p, si.boundary_test) are kept for the
+# second one when they fit; the reference re-traces (reparam.py:296-325), which is the fallback.
+REPARAM_KEEP_BYTES = 64 << 30   # (288 GB of HBM per GPU: 16 samples of a 67 M-ray wavefront are 39 GB)
+
+
+def _sample_structs(buf, n, si_hit=True):
+    """hf_si_t / hf_pi_t over one [9, n] sample buffer: si.t, si.p[3], si.boundary_test | pi.t, u, v, prim_index.
+    Without ``si_hit`` only boundary_test of the SI record is written."""
+    rows = _rows(buf, n)
+    si_s = _capi.hf_si_t()
+    if si_hit:
+        si_s.t = rows[0]
+        for c in range(3):
+            si_s.p[c] = rows[1 + c]
+    si_s.boundary_test = rows[4]
+    pi_s = _capi.hf_pi_t()
+    pi_s.t, pi_s.prim_uv[0], pi_s.prim_uv[1], pi_s.prim_index = rows[5], rows[6], rows[7], rows[8]
+    return rows, si_s, pi_s
+
+
+def _reparam_backward_fused(shape, o, d, gd, gdiv, act_p, rid_p, cfg, stream):
+    """Heights only, hits kept: hf_reparam_trace_all traces every sample (pi and si.boundary_test; a ray is fetched
+    once, batches whose cones miss are culled), then hf_reparam_backward does the weights, their sums and the adjoint
+    of every auxiliary hit.  No per-sample intermediates (their zero fills: 1.3 GB, 0.2 ms for 67 M rays)."""
+    L = _capi.lib()
+    num_rays, kappa, exponent, antithetic, seed = cfg
+    n = o.shape[1]
+    o_p, d_p, gd_p = _p3(o), _p3(d), _p3(gd)
+    store = torch.empty((num_rays, 9, n), dtype=torch.float32, device=o.device)   # sample k: 9 n floats further on
+    grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=o.device)
+    rows, si_s, pi_s = _sample_structs(store[0], n, si_hit=False)
+    check(L.hf_reparam_trace_all(shape._h, n, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, int(antithetic), seed,
+                                 rid_p, C.byref(pi_s), C.byref(si_s), 9 * n, stream))
+    check(L.hf_reparam_backward(shape._h, n, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, exponent,
+                                int(antithetic), seed, rid_p, C.byref(pi_s), rows[4], 9 * n, C.byref(gd_p),
+                                gdiv.data_ptr(), grad_h.data_ptr(), stream))
+    return grad_h
+
+
+def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, need_h, need_o, need_d, stream):
+    """Per sample: hf_reparam_aux_rays + hf_ray_intersect + hf_reparam_weights for the weight sums, then
+    hf_reparam_weights + hf_adjoint on the kept hits (re-traced without ``keep``); the ray gradients too."""
+    L = _capi.lib()
+    num_rays, kappa, exponent, antithetic, seed = cfg
+    dev = o.device
+    n = o.shape[1]
+    ray_grads = need_o or need_d
+    act_p = None if act is None else act.data_ptr()
+    flags = int(RayFlags.All | RayFlags.FollowShape | RayFlags.BoundaryTest)
+    aux_d = torch.empty((3, n), dtype=torch.float32, device=dev); aux_maxt = torch.empty(n, dtype=torch.float32, device=dev)
+    Z = torch.zeros(n, dtype=torch.float32, device=dev); dZ = torch.zeros((3, n), dtype=torch.float32, device=dev)
+    g_p = torch.empty((3, n), dtype=torch.float32, device=dev); g_t = torch.empty(n, dtype=torch.float32, device=dev)
+    grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=dev) if need_h else None
+    o_p, d_p, ad_p, dZ_p, gd_p, gp_p = _p3(o), _p3(d), _p3(aux_d), _p3(dZ), _p3(gd), _p3(g_p)
+    r_s = shape._rays_struct(o, aux_d, aux_maxt)
+    g_s = _capi.hf_si_grad_t()
+    g_s.t = g_t.data_ptr()
+    for c in range(3):
+        g_s.p[c] = g_p[c].data_ptr()
+    gvd_p = go_adj_p = gd_adj_p = grad_o = grad_d = None
+    if ray_grads:   # per-sample ray gradients of the auxiliary hit + the gradient w.r.t. V_direct itself
+        g_vd, go_adj, gd_adj = (torch.empty((3, n), dtype=torch.float32, device=dev) for _ in range(3))
+        grad_o, grad_d = torch.zeros((3, n), dtype=torch.float32, device=dev), torch.zeros((3, n), dtype=torch.float32, device=dev)
+        gvd_p, go_adj_p, gd_adj_p = C.byref(_p3(g_vd)), C.byref(_p3(go_adj)), C.byref(_p3(gd_adj))
+    store = torch.empty((num_rays if keep else 1, 9, n), dtype=torch.float32, device=dev)
+
+    def aux(k):
+        check(L.hf_reparam_aux_rays(n, C.byref(o_p), C.byref(d_p), act_p, k, kappa, int(antithetic), seed, rid_p,
+                                    C.byref(ad_p), aux_maxt.data_ptr(), stream))
+
+    def trace(k, buf):
+        aux(k)
+        _, si_s, pi_s = _sample_structs(buf, n)
+        check(L.hf_ray_intersect(shape._h, n, C.byref(r_s), flags, None, C.byref(pi_s), C.byref(si_s), stream))
+
+    def weights(mode, k, buf):
+        rows = _rows(buf, n)
+        sp_p = (C.c_void_p * 3)(*rows[1:4])
+        check(L.hf_reparam_weights(mode, n, C.byref(o_p), C.byref(d_p), act_p, k, kappa, exponent, int(antithetic),
+                                   seed, rid_p, rows[0], C.byref(sp_p), rows[4], Z.data_ptr(), C.byref(dZ_p), C.byref(gd_p),
+                                   gdiv.data_ptr(), C.byref(gp_p), g_t.data_ptr(), gvd_p if mode == 1 else None, stream))
+
+    for k in range(num_rays):   # weight normalisation (reparam.py:236-256)
+        buf = store[k if keep else 0]
+        trace(k, buf)
+        weights(0, k, buf)
+    for k in range(num_rays):
+        buf = store[k if keep else 0]
+        if keep:
+            aux(k)                      # hf_adjoint needs the auxiliary ray again, not its trace
+        else:
+            trace(k, buf)
+        weights(1, k, buf)
+        _, si_s, pi_s = _sample_structs(buf, n)
+        check(L.hf_adjoint(shape._h, n, C.byref(r_s), C.byref(pi_s), flags, act_p, C.byref(g_s),
+                           grad_h.data_ptr() if need_h else None, go_adj_p, gd_adj_p, stream))
+        if ray_grads:
+            hit = torch.isfinite(buf[0])
+            if act is not None:
+                hit = hit & (act != 0)
+            # hit: V_direct = (p - o) / t  ->  dL/do = [t's dependence on o: hf_adjoint] - gVd / t  (= g_p);
+            #      t's dependence on the auxiliary direction d_aux = Frame3f(d).to_world(omega) goes on to d
+            # miss: V_direct = ray.d (reparam.py:93-95)  ->  dL/dd = gVd
+            grad_o += torch.where(hit, go_adj - g_p, torch.zeros_like(g_p))
+            if need_d:
+                with torch.enable_grad():
+                    dq = d.detach().clone().requires_grad_(True)
+                    s_, t_ = _coordinate_system(dq)
+                    sd, td = s_.detach(), t_.detach()
+                    om = torch.stack([(sd * aux_d).sum(0), (td * aux_d).sum(0), (d * aux_d).sum(0)])  # omega_local
+                    d_aux = s_ * om[0] + t_ * om[1] + dq * om[2]
+                    (gd_through,) = torch.autograd.grad(d_aux, dq, torch.where(hit, gd_adj, torch.zeros_like(gd_adj)))
+                grad_d += gd_through + torch.where(hit, torch.zeros_like(g_vd), g_vd)
+    return grad_h, grad_o, grad_d
 
 
 class _ReparameterizeOp(torch.autograd.Function):
@@ -928,123 +1041,23 @@ class _ReparameterizeOp(torch.autograd.Function):
         shape = ctx.shape
         ray_o, ray_d = ctx.saved_tensors
         num_rays, kappa, exponent, antithetic, seed, active, ray_index = ctx.cfg
+        cfg = (num_rays, kappa, exponent, antithetic, seed)
         rid_p = ray_index.data_ptr() if ray_index is not None else None
         need_h, need_o, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        ray_grads = need_o or need_d
-        L = _capi.lib()
-        dev = ray_o.device
         n = ray_o.shape[1]
         o = ray_o.detach().to(torch.float32).contiguous(); d = ray_d.detach().to(torch.float32).contiguous()
         gd = grad_direction.to(torch.float32).contiguous(); gdiv = grad_divergence.to(torch.float32).contiguous()
         act = None if active is None else active.to(torch.uint8).contiguous()
         act_p = None if act is None else act.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        flags = int(RayFlags.All | RayFlags.FollowShape | RayFlags.BoundaryTest)
-        # The auxiliary hits of the first loop (36 B per ray and sample: pi + si.t, si.p, si.boundary_test) are kept
-        # for the second one when they fit; the reference re-traces (reparam.py:296-325), which is the fallback.
-        keep = 36 * n * num_rays <= (64 << 30)   # (288 GB of HBM per GPU: 16 samples of a 67 M-ray wavefront are 39 GB)
-        # heights only and the hits kept: after the traces ONE kernel does the rest (hf_reparam_backward: the weights of
-        # all samples, their sums, and the adjoint of every auxiliary hit); the traces then only write pi and
-        # si.boundary_test
-        fused = REPARAM_FUSED and keep and not ray_grads and num_rays <= 32
-        # (the per-sample kernels' intermediates: auxiliary rays, weight sums, upstream gradients of the auxiliary hits --
-        # none of them exists on the fused path, where 1.3 GB of zero fills for a 67 M-ray wavefront would be 0.2 ms)
-        m = 0 if fused else n
-        aux_d = torch.empty((3, m), dtype=torch.float32, device=dev); aux_maxt = torch.empty(m, dtype=torch.float32, device=dev)
-        Z = torch.zeros(m, dtype=torch.float32, device=dev); dZ = torch.zeros((3, m), dtype=torch.float32, device=dev)
-        g_p = torch.empty((3, m), dtype=torch.float32, device=dev); g_t = torch.empty(m, dtype=torch.float32, device=dev)
-        grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=dev)
-        o_p, d_p, ad_p, dZ_p, gd_p, gp_p = _p3(o), _p3(d), _p3(aux_d), _p3(dZ), _p3(gd), _p3(g_p)
-        r_s = shape._rays_struct(o, aux_d, aux_maxt)
-        g_s = _capi.hf_si_grad_t()
-        g_s.t = g_t.data_ptr()
-        for c in range(3):
-            g_s.p[c] = g_p[c].data_ptr()
-        if ray_grads:   # per-sample ray gradients of the auxiliary hit + the gradient w.r.t. V_direct itself
-            g_vd = torch.empty((3, n), dtype=torch.float32, device=dev); gvd_p = _p3(g_vd)
-            go_adj = torch.empty((3, n), dtype=torch.float32, device=dev); gd_adj = torch.empty((3, n), dtype=torch.float32, device=dev)
-            go_adj_p, gd_adj_p = _p3(go_adj), _p3(gd_adj)
-            grad_o = torch.zeros((3, n), dtype=torch.float32, device=dev); grad_d = torch.zeros((3, n), dtype=torch.float32, device=dev)
-        store = torch.empty((num_rays if keep else 1, 9, n), dtype=torch.float32, device=dev)
-        bufs = [store[k] for k in range(store.shape[0])]
-
-        def structs(buf):
-            rows = _rows(buf, n)   # si.t, si.p[3], boundary_test | pi.t, u, v, prim_index
-            si_s = _capi.hf_si_t()
-            if not fused:
-                si_s.t = rows[0]
-                for c in range(3):
-                    si_s.p[c] = rows[1 + c]
-            si_s.boundary_test = rows[4]
-            pi_s = _capi.hf_pi_t()
-            pi_s.t, pi_s.prim_uv[0], pi_s.prim_uv[1], pi_s.prim_index = rows[5], rows[6], rows[7], rows[8]
-            return rows, si_s, pi_s
-
-        def aux(k):
-            check(L.hf_reparam_aux_rays(n, C.byref(o_p), C.byref(d_p), act_p, k, kappa, int(antithetic), seed, rid_p,
-                                        C.byref(ad_p), aux_maxt.data_ptr(), stream))
-
-        def trace(k, buf):
-            rows, si_s, pi_s = structs(buf)
-            if fused:   # auxiliary ray generated inside the trace kernel
-                check(L.hf_reparam_trace(shape._h, n, C.byref(o_p), C.byref(d_p), act_p, k, kappa, int(antithetic), seed, rid_p,
-                                         C.byref(pi_s), C.byref(si_s), stream))
-                return
-            aux(k)
-            check(L.hf_ray_intersect(shape._h, n, C.byref(r_s), flags, None, C.byref(pi_s), C.byref(si_s), stream))
-
-        def weights(mode, k, buf):
-            rows = _rows(buf, n)
-            sp_p = (C.c_void_p * 3)(*rows[1:4])
-            check(L.hf_reparam_weights(mode, n, C.byref(o_p), C.byref(d_p), act_p, k, kappa, exponent, int(antithetic),
-                                       seed, rid_p, rows[0], C.byref(sp_p), rows[4], Z.data_ptr(), C.byref(dZ_p), C.byref(gd_p),
-                                       gdiv.data_ptr(), C.byref(gp_p), g_t.data_ptr(),
-                                       C.byref(gvd_p) if (ray_grads and mode == 1) else None, stream))
-
-        if fused and REPARAM_ONE_LAUNCH:    # all samples in one launch (a ray is fetched once; batches whose cones miss are culled)
-            rows, si_s, pi_s = structs(bufs[0])
-            check(L.hf_reparam_trace_all(shape._h, n, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, int(antithetic), seed,
-                                         rid_p, C.byref(pi_s), C.byref(si_s), 9 * n, stream))
-        for k in range(0 if (fused and REPARAM_ONE_LAUNCH) else num_rays):   # weight normalisation (reparam.py:236-256)
-            buf = bufs[k if keep else 0]
-            trace(k, buf)
-            if not fused:
-                weights(0, k, buf)
-        if fused and need_h:
-            rows, si_s, pi_s = structs(bufs[0])   # sample k: the same rows of store[k], 9 n floats further on
-            check(L.hf_reparam_backward(shape._h, n, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, exponent,
-                                        int(antithetic), seed, rid_p, C.byref(pi_s), rows[4], 9 * n, C.byref(gd_p),
-                                        gdiv.data_ptr(), grad_h.data_ptr(), stream))
-        for k in range(0 if fused else num_rays):   # the same, per-sample kernels (ray gradients wanted / hits not kept)
-            buf = bufs[k if keep else 0]
-            if keep:
-                aux(k)                      # hf_adjoint needs the auxiliary ray again, not its trace
-            else:
-                trace(k, buf)
-            weights(1, k, buf)
-            rows, si_s, pi_s = structs(buf)
-            check(L.hf_adjoint(shape._h, n, C.byref(r_s), C.byref(pi_s), flags, act_p, C.byref(g_s),
-                               grad_h.data_ptr() if need_h else None,
-                               C.byref(go_adj_p) if ray_grads else None, C.byref(gd_adj_p) if ray_grads else None, stream))
-            if ray_grads:
-                hit = torch.isfinite(buf[0])
-                if act is not None:
-                    hit = hit & (act != 0)
-                # hit: V_direct = (p - o) / t  ->  dL/do = [t's dependence on o: hf_adjoint] - gVd / t  (= g_p);
-                #      t's dependence on the auxiliary direction d_aux = Frame3f(d).to_world(omega) goes on to d
-                # miss: V_direct = ray.d (reparam.py:93-95)  ->  dL/dd = gVd
-                grad_o += torch.where(hit, go_adj - g_p, torch.zeros_like(g_p))
-                if need_d:
-                    with torch.enable_grad():
-                        dq = d.detach().clone().requires_grad_(True)
-                        s_, t_ = _coordinate_system(dq)
-                        sd, td = s_.detach(), t_.detach()
-                        om = torch.stack([(sd * aux_d).sum(0), (td * aux_d).sum(0), (d * aux_d).sum(0)])  # omega_local
-                        d_aux = s_ * om[0] + t_ * om[1] + dq * om[2]
-                        (gd_through,) = torch.autograd.grad(d_aux, dq, torch.where(hit, gd_adj, torch.zeros_like(gd_adj)))
-                    grad_d += gd_through + torch.where(hit, torch.zeros_like(g_vd), g_vd)
-        gh = grad_h
-        if gh.shape != shape.heightfield.shape:
+        stream = torch.cuda.current_stream(ray_o.device).cuda_stream
+        keep = 36 * n * num_rays <= REPARAM_KEEP_BYTES
+        # (backward runs only when some input needs a gradient: without the ray's, that is the heights')
+        if REPARAM_FUSED and keep and not (need_o or need_d) and num_rays <= 32:
+            gh, grad_o, grad_d = _reparam_backward_fused(shape, o, d, gd, gdiv, act_p, rid_p, cfg, stream), None, None
+        else:
+            gh, grad_o, grad_d = _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep,
+                                                              need_h, need_o, need_d, stream)
+        if gh is not None and gh.shape != shape.heightfield.shape:
             gh = gh.reshape(shape.heightfield.shape)
         return ((gh if need_h else None), (grad_o if need_o else None), (grad_d if need_d else None),
                 None, None, None, None, None, None, None, None)

@@ -99,8 +99,10 @@ def test_gpu_fused_loops_equal_the_per_sample_kernels(hf, kappa, antithetic, num
     gd = torch.from_numpy(rng.normal(size=(3, n)).astype(np.float32)).cuda()
     gdiv = torch.from_numpy(rng.normal(size=n).astype(np.float32)).cuda()
     grads = []
-    for fused in (True, False):
-        shape_mod.REPARAM_FUSED = fused
+    keep_bytes = shape_mod.REPARAM_KEEP_BYTES
+    # fused; per-sample on the kept hits; per-sample re-tracing every sample (no room to keep the hits)
+    for fused, keep in ((True, keep_bytes), (False, keep_bytes), (False, 0)):
+        shape_mod.REPARAM_FUSED, shape_mod.REPARAM_KEEP_BYTES = fused, keep
         try:
             shape = hf.Heightfield(heightfield=torch.from_numpy(h).cuda(), max_height=0.5)
             shape.heightfield.requires_grad_(True)
@@ -110,10 +112,11 @@ def test_gpu_fused_loops_equal_the_per_sample_kernels(hf, kappa, antithetic, num
             ((dirn * gd).sum() + (det * gdiv).sum()).backward()
             grads.append(shape.heightfield.grad.double().cpu().numpy())
         finally:
-            shape_mod.REPARAM_FUSED = True
-    assert np.linalg.norm(grads[1]) > 0
-    rel = np.linalg.norm(grads[0] - grads[1]) / np.linalg.norm(grads[1])
-    assert rel <= 2e-6, rel
+            shape_mod.REPARAM_FUSED, shape_mod.REPARAM_KEEP_BYTES = True, keep_bytes
+    for g in grads[1:]:
+        assert np.linalg.norm(g) > 0
+        rel = np.linalg.norm(grads[0] - g) / np.linalg.norm(g)
+        assert rel <= 2e-6, rel
 
 
 @pytest.mark.gpu
