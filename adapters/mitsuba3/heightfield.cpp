@@ -93,7 +93,8 @@ enum : size_t {
     SI_T = 0, SI_P = 1, SI_N = 4, SI_UV = 7, SI_SHN = 9, SI_DPDU = 12, SI_DPDV = 15,
     SI_BT = 18, SI_SHS = 19, SI_SHT = 22, SI_WI = 25, SI_ROWS = 28,
     ROW_GRAD = ROW_SI + SI_ROWS,                                        // 18 rows of dL/dsi, then 6 rows dL/do, dL/dd
-    ROWS_TOTAL = ROW_GRAD + 18 + 6
+    ROW_DN = ROW_GRAD + 18 + 6,                                         // 6 rows dn_du, dn_dv (RayFlags::dNSdUV)
+    ROWS_TOTAL = ROW_DN + 6
 };
 
 template <typename Float, typename Spectrum> class Heightfield;
@@ -191,6 +192,8 @@ public:
     Heightfield(const Properties &props) : Base(props) {
         m_max_height   = props.get<ScalarFloat>("max_height", 1.f);
         m_flip_normals = props.get<bool>("flip_normals", false);
+        // Mesh's property (mesh.cpp:30), but flat by default: smooth shading is opt-in for a heightfield
+        m_face_normals = props.get<bool>("face_normals", true);
         m_device       = (int) props.get<int64_t>("device", 0);
 
         // height data: a nested bitmap object or a file name, like the bitmap texture (src/textures/bitmap.cpp:122-141)
@@ -233,9 +236,11 @@ public:
         desc.flip_normals  = m_flip_normals ? 1 : 0;
         desc.device        = m_device;
         HfStaging::hip_check(hipSetDevice(m_device));
-        if (!m_hf)
+        if (!m_hf) {
             hf_check(hf_create(&desc, &m_hf));
-        else
+            // smooth: the vertex normals follow every later hf_set_heights* / hf_set_transform (mesh.cpp:115-119)
+            hf_check(hf_set_face_normals(m_hf, m_face_normals ? 1 : 0, nullptr));
+        } else
             hf_check(hf_set_transform(m_hf, desc.to_world, desc.to_object));
 
         // heights: evaluate, then one host -> device copy + rebuild of the min/max pyramid (hf_set_heights_host)
@@ -414,7 +419,13 @@ public:
         si.sh_frame.n = Normal3f(row(SI_SHN), row(SI_SHN + 1), row(SI_SHN + 2));
         si.dp_du      = Vector3f(row(SI_DPDU), row(SI_DPDU + 1), row(SI_DPDU + 2));
         si.dp_dv      = Vector3f(row(SI_DPDV), row(SI_DPDV + 1), row(SI_DPDV + 2));
-        si.dn_du = si.dn_dv = dr::zeros<Vector3f>(n); // flat shading
+        if (has_flag(ray_flags, RayFlags::dNSdUV)) { // hf_shading_derivatives (zero with flat shading), detached
+            const float *dn = m_last_dn.data();
+            si.dn_du = Vector3f(dr::load<Float>(dn, n), dr::load<Float>(dn + n, n), dr::load<Float>(dn + 2 * n, n));
+            si.dn_dv = Vector3f(dr::load<Float>(dn + 3 * n, n), dr::load<Float>(dn + 4 * n, n), dr::load<Float>(dn + 5 * n, n));
+        } else {
+            si.dn_du = si.dn_dv = dr::zeros<Vector3f>(n);
+        }
         if (has_flag(ray_flags, RayFlags::BoundaryTest))
             si.boundary_test = dr::load<Float>(m_last_boundary_test.data(), n); // detached (interaction.h:497-498)
         si.shape    = this;
@@ -437,6 +448,13 @@ public:
                                                 &out, m_stage.stream()));
         std::vector<float> host(SI_ROWS * n);
         m_stage.download(host.data(), dev + ROW_SI * n, SI_ROWS * n);
+        if (has_flag(op.ray_flags, RayFlags::dNSdUV)) { // into the staging block's own rows
+            float *dn_dev = dev + ROW_DN * n;
+            float *du[3] = { dn_dev, dn_dev + n, dn_dev + 2 * n }, *dv[3] = { dn_dev + 3 * n, dn_dev + 4 * n, dn_dev + 5 * n };
+            hf_check(hf_shading_derivatives(m_hf, n, &pic, (const uint8_t *) (dev + ROW_ACTIVE * n), du, dv, m_stage.stream()));
+            m_last_dn.resize(6 * n);
+            m_stage.download(m_last_dn.data(), dn_dev, 6 * n);
+        }
         m_stage.sync();
         m_last_boundary_test.assign(host.begin() + SI_BT * n, host.begin() + (SI_BT + 1) * n);
         return dr::load<Float>(host.data(), 18 * n);
@@ -623,12 +641,14 @@ private:
     TensorXf m_heights;
     ScalarFloat m_max_height = 1.f;
     bool m_flip_normals = false;
+    bool m_face_normals = true; // flat shading (hf_set_face_normals)
     int m_device = 0;
     uint32_t m_width = 0, m_height = 0;
     // the handle's query functions are re-entrant, the staging buffers of this adapter are not
     mutable std::mutex m_mutex;
     mutable HfStaging m_stage;
     mutable std::vector<float> m_last_boundary_test; // detached (interaction.h:497-498), of the last primal call
+    mutable std::vector<float> m_last_dn;            // dn_du, dn_dv rows of the last primal call with RayFlags::dNSdUV
 };
 
 MI_IMPLEMENT_CLASS_VARIANT(Heightfield, Shape)

@@ -42,7 +42,8 @@
  *     The forward-mode entry points (hf_tangent, hf_direct_lighting_weighted_tangent, hf_point_lighting_tangent) are
  *     capturable as well: they reserve no scratch block, allocate nothing and never synchronise the host.
  *     Not capturable: hf_create / hf_destroy, hf_set_heights_host, hf_bbox, hf_get_mip and the host-pointer packet
- *     entry (they synchronise).
+ *     entry (they synchronise); hf_set_face_normals (refused with HF_EINVAL) and, with smooth shading, hf_set_transform
+ *     (it synchronises).
  */
 #ifndef HF_H
 #define HF_H
@@ -138,8 +139,11 @@ typedef struct hf_pi_const {
 
 /* SurfaceInteraction3f fields filled by Shape::compute_surface_interaction +
  * finalize_surface_interaction (interaction.h:175-507).  Any pointer may be NULL
- * (field not wanted).  dn_du/dn_dv are identically zero (flat shading) and
- * duv_dx/duv_dy are zeroed by finalize; neither is stored. */
+ * (field not wanted).  dn_du/dn_dv are not stored: zero with flat shading (the default), and
+ * hf_shading_derivatives computes them with smooth shading (hf_set_face_normals); duv_dx/duv_dy are
+ * zeroed by finalize.  sh_n is the face normal n with flat shading and the interpolated vertex normal
+ * with smooth shading (with HF_RAY_SHADINGFRAME or HF_RAY_DNSDUV, as mesh.cpp:813-840); sh_s, sh_t
+ * and wi are built on sh_n. */
 typedef struct hf_si {
     float *t;
     float *p[3];
@@ -228,8 +232,29 @@ int hf_adam_step_scheduled(hf_field_t *hf, float *d_heights, const float *d_grad
                            const float *d_lr_t, uint32_t *d_step, double beta1, double beta2, double eps,
                            int mask_updates, hf_stream_t stream);
 
-/* Replaces: m_to_world update + update() (rectangle.cpp:101-112, 131-142). */
+/* Replaces: m_to_world update + update() (rectangle.cpp:101-112, 131-142).  With smooth shading the vertex
+ * normals are rebuilt as well: after the last hf_set_heights* (whatever its stream), and the call returns when the
+ * rebuild is complete, so nothing the caller issues afterwards, on any stream, can overlap it.  In that mode the rule
+ * of hf_set_heights holds: no query on this handle may be in flight on another stream. */
 int hf_set_transform(hf_field_t *hf, const float to_world[12], const float *to_object_or_null);
+
+/* Replaces: the Mesh property `face_normals` (src/render/mesh.cpp:30) and the vertex normals it switches on.
+ * face_normals = 1 (the default of a new handle, unlike Mesh's): flat shading, sh_frame.n = the face normal.
+ * face_normals = 0: smooth shading.  The handle then owns one vertex normal per texel (16 bytes each), angle-weighted
+ * as the JIT path of Mesh::recompute_vertex_normals computes them (mesh.cpp:350-384) from the world-space vertices,
+ * and rebuilt wherever they can go stale, as parameters_changed does (mesh.cpp:115-119): by this call on `stream`
+ * (ordered after the last hf_set_heights*; later queries on other streams must be ordered after `stream` by the
+ * caller, as for hf_set_heights), by every hf_set_heights* on its stream (graph-capturable, as before) and by
+ * hf_set_transform (synchronous).  This call itself is not capturable: HF_EINVAL while `stream` is being captured.  A hit's shading normal
+ * is the normalised barycentric blend of its three vertex normals, flipped after the blend by flip_normals
+ * (mesh.cpp:792-840); hf_adjoint / hf_tangent differentiate it through the barycentrics and through the vertex
+ * normals (which stay attached to the heights, as in test_mesh.py:540-600; detached with HF_RAY_DETACHSHAPE,
+ * mesh.cpp:803-811).  boundary_test keeps its geometric (silhouette) definition in both modes, so
+ * hf_reparam_backward does not depend on the mode.  Same rule as hf_set_heights: no query on this handle may be in
+ * flight on another stream.  HF_ENOMEM when the normals cannot be allocated.  Flat mode runs the kernels it always
+ * ran, and frees the normals. */
+int hf_set_face_normals(hf_field_t *hf, int face_normals, hf_stream_t stream);
+int hf_get_face_normals(const hf_field_t *hf);
 
 /* Replaces: Shape::bbox() (include/mitsuba/render/shape.h:253; analog rectangle.cpp:114-124).
  * World-space {min xyz, max xyz}.  Synchronises `stream`-ordered height updates. */
@@ -329,6 +354,13 @@ int hf_adjoint_rows(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
 int hf_tangent(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi, uint32_t ray_flags,
                const uint8_t *active, const float *dheights, const float *const d_o[3], const float *const d_d[3],
                const hf_si_tangent_t *tangent_si, hf_stream_t stream);
+
+/* Replaces: SurfaceInteraction3f::dn_du / dn_dv of the smooth-shaded mesh under RayFlags::dNSdUV (mesh.cpp:818-829):
+ * the derivatives of the shading normal with respect to the barycentrics (b1, b2) of every hit of pi, before
+ * flip_normals (as the reference).  dn_du / dn_dv: 3 device arrays of n floats each (either may be NULL), overwritten.
+ * Zero for misses, inactive lanes and with flat shading.  Forward only. */
+int hf_shading_derivatives(const hf_field_t *hf, size_t n, const hf_pi_const_t *pi, const uint8_t *active,
+                           float *const dn_du[3], float *const dn_dv[3], hf_stream_t stream);
 
 /* ---- next row: minimal direct lighting on the wavefront ------- */
 

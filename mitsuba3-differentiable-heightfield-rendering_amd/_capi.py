@@ -62,6 +62,10 @@ SYMBOLS = {
     "hf_adam_step_scheduled": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _fp, _fp, C.c_double, C.c_double, C.c_double, C.c_int,
                                          C.c_void_p]),
     "hf_set_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "hf_set_face_normals": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hf_get_face_normals": (C.c_int, [C.c_void_p]),
+    "hf_shading_derivatives": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(hf_pi_t), _fp, C.POINTER(_fp * 3),
+                                         C.POINTER(_fp * 3), C.c_void_p]),
     "hf_bbox": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "hf_heights_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "hf_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -36,6 +36,8 @@ struct hf_field {
     uint32_t next_slot, next_capture_slot;
     std::mutex *slot_mutex;
     int coherence;      // hf_set_ray_coherence: HF_COHERENCE_AUTO / _INCOHERENT (which instantiation the trace launches take)
+    float4 *d_vn;       // smooth shading (hf_set_face_normals(hf, 0)): one vertex normal per texel, rebuilt with the
+                        // heights and the transform; NULL = flat shading (the default), and the flat kernels run
 };
 
 static bool stream_capturing(hipStream_t s) {
@@ -185,6 +187,7 @@ static void release(hf_field *hf) {
     if (hf->d_mip) (void) hipFree(hf->d_mip);
     if (hf->d_shear) (void) hipFree(hf->d_shear);
     if (hf->d_misc) (void) hipFree(hf->d_misc);
+    if (hf->d_vn) (void) hipFree(hf->d_vn);
     delete hf->slot_mutex;
     free(hf);
 }
@@ -290,6 +293,7 @@ extern "C" int hf_set_heights(hf_field_t *hf, const float *d_heights, hf_stream_
     if (d_heights != hf->d_heights)
         HF_HIP(hipMemcpyAsync(hf->d_heights, d_heights, bytes, hipMemcpyDeviceToDevice, st));
     hf_launch_build_mips(hf->dev, hf->d_mip, hf->d_shear, st);
+    if (hf->d_vn) hf_launch_build_normals(hf->dev, hf->d_vn, st);
     HF_HIP(hipGetLastError());
     if (!stream_capturing(st)) HF_HIP(hipEventRecord(hf->built, st)); // (a captured rebuild is ordered by its graph)
     return HF_OK;
@@ -350,8 +354,63 @@ extern "C" int hf_set_heights_host(hf_field_t *hf, const float *h_heights, hf_st
 
 extern "C" int hf_set_transform(hf_field_t *hf, const float to_world[12], const float *to_object_or_null) {
     if (!hf || !to_world) return fail(HF_EINVAL, "hf_set_transform: NULL argument");
-    return set_transform(hf, to_world, to_object_or_null);
+    int rc = set_transform(hf, to_world, to_object_or_null);
+    if (rc != HF_OK || !hf->d_vn) return rc;
+    // Smooth shading: the vertex normals are world-space (angles are not affine-invariant) and are rebuilt here.  The
+    // call takes no stream, so the rebuild is made synchronous: on the null stream after the last height update
+    // (`built`, whatever stream that was on), and waited for before returning -- a query or a height update the caller
+    // issues afterwards, on any stream, cannot overlap it.
+    hf_device_guard guard(hf->device);
+    if (!guard.ok) return fail(HF_EDEVICE, "hf_set_transform: cannot select device %d", hf->device);
+    HF_HIP(hipStreamWaitEvent(nullptr, hf->built, 0));
+    hf_launch_build_normals(hf->dev, hf->d_vn, nullptr);
+    HF_HIP(hipGetLastError());
+    HF_HIP(hipEventRecord(hf->built, nullptr));
+    HF_HIP(hipEventSynchronize(hf->built));
+    return HF_OK;
 }
+
+extern "C" int hf_set_face_normals(hf_field_t *hf, int face_normals, hf_stream_t stream) {
+    if (!hf) return fail(HF_EINVAL, "hf_set_face_normals: NULL handle");
+    hf_device_guard guard(hf->device);
+    if (!guard.ok) return fail(HF_EDEVICE, "hf_set_face_normals: cannot select device %d", hf->device);
+    hipStream_t st = (hipStream_t) stream;
+    // Not capturable: a captured switch would publish normals that no build has written before the first replay, and a
+    // captured switch back would free a buffer the graph's kernels still reference.
+    if (stream_capturing(st))
+        return fail(HF_EINVAL, "hf_set_face_normals: not capturable (the stream is being captured into a HIP graph)");
+    if (face_normals) { // flat: the buffer goes (hipFree waits for the work that may still read it)
+        if (hf->d_vn) {
+            float4 *vn = hf->d_vn;
+            hf->d_vn = nullptr;
+            HF_HIP(hipFree(vn));
+        }
+        return HF_OK;
+    }
+    if (hf->d_vn) return HF_OK;
+    const size_t bytes = sizeof(float4) * (size_t) hf->dev.W * hf->dev.H;
+    float4 *vn = nullptr;
+    const hipError_t e = hipMalloc((void **) &vn, bytes);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? HF_ENOMEM : HF_EDEVICE,
+                    "hf_set_face_normals: cannot allocate the vertex normals (%zu bytes): %s", bytes, hipGetErrorString(e));
+    }
+    // the build reads the heights the last hf_set_heights* left, whatever stream that was on
+    HF_HIP(hipStreamWaitEvent(st, hf->built, 0));
+    hf_launch_build_normals(hf->dev, vn, st);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        (void) hipFree(vn);
+        return fail(HF_EDEVICE, "hf_set_face_normals: %s", hipGetErrorString(le));
+    }
+    hf->d_vn = vn;
+    HF_HIP(hipEventRecord(hf->built, st));
+    return HF_OK;
+}
+
+extern "C" int hf_get_face_normals(const hf_field_t *hf) { return hf ? (hf->d_vn ? 0 : 1) : 1; }
+
 
 extern "C" int hf_heights_device(hf_field_t *hf, const float **out) {
     if (!hf || !out) return fail(HF_EINVAL, "hf_heights_device: NULL argument");
@@ -452,7 +511,7 @@ static int trace(const char *who, int mode, const hf_field_t *hf, size_t n, cons
     {
         slot_lease lease(hf, stream, hf_trace_scratch_bytes(n));
         if (!lease.buf) return fail(lease.code, "%s: %s", who, lease.why);
-        hf_launch_trace(mode, hf->dev, n, rays, active, pi, hit, si, flags, lease.buf, stream, aux, lean);
+        hf_launch_trace(mode, hf->dev, n, rays, active, pi, hit, si, flags, lease.buf, stream, aux, lean, hf->d_vn);
     }
     HF_HIP(hipGetLastError());
     return HF_OK;
@@ -484,7 +543,7 @@ extern "C" int hf_compute_surface_interaction(const hf_field_t *hf, size_t n, co
     if ((rc = check_flags("hf_compute_surface_interaction", ray_flags))) return rc;
     if ((rc = check_pi("hf_compute_surface_interaction", n, pi))) return rc;
     if (!out) return fail(HF_EINVAL, "hf_compute_surface_interaction: NULL output");
-    hf_launch_si(hf->dev, n, rays, pi, active, out, ray_flags, (hipStream_t) stream);
+    hf_launch_si(hf->dev, n, rays, pi, active, out, ray_flags, (hipStream_t) stream, hf->d_vn);
     HF_HIP(hipGetLastError());
     return HF_OK;
 }
@@ -512,7 +571,7 @@ extern "C" int hf_adjoint_rows(const hf_field_t *hf, size_t n, const hf_rays_t *
     if (grad_o && !all3(grad_o)) return fail(HF_EINVAL, "hf_adjoint: NULL grad_o array");
     if (grad_d && !all3(grad_d)) return fail(HF_EINVAL, "hf_adjoint: NULL grad_d array");
     hf_launch_adjoint(hf->dev, n, rays, pi, active, grad_si, ray_flags, grad_heights, grad_o, grad_d, row_band,
-                      (hipStream_t) stream);
+                      (hipStream_t) stream, hf->d_vn);
     HF_HIP(hipGetLastError());
     return HF_OK;
 }
@@ -532,7 +591,21 @@ extern "C" int hf_tangent(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
     if ((rc = check_flags("hf_tangent", ray_flags))) return rc;
     if ((rc = check_pi("hf_tangent", n, pi))) return rc;
     if (!tangent_si) return fail(HF_EINVAL, "hf_tangent: NULL output");
-    hf_launch_tangent(hf->dev, n, rays, pi, active, ray_flags, dheights, d_o, d_d, tangent_si, (hipStream_t) stream);
+    hf_launch_tangent(hf->dev, n, rays, pi, active, ray_flags, dheights, d_o, d_d, tangent_si, (hipStream_t) stream, hf->d_vn);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_shading_derivatives(const hf_field_t *hf, size_t n, const hf_pi_const_t *pi, const uint8_t *active,
+                                      float *const dn_du[3], float *const dn_dv[3], hf_stream_t stream) {
+    if (!hf) return fail(HF_EINVAL, "hf_shading_derivatives: NULL handle");
+    int rc;
+    if ((rc = check_pi("hf_shading_derivatives", n, pi))) return rc;
+    if ((dn_du && !all3(dn_du)) || (dn_dv && !all3(dn_dv)))
+        return fail(HF_EINVAL, "hf_shading_derivatives: NULL dn_du / dn_dv array");
+    if (n == 0) return HF_OK;
+    if ((rc = check_device("hf_shading_derivatives", hf))) return rc;
+    hf_launch_shading_derivatives(hf->dev, n, pi, active, dn_du, dn_dv, hf->d_vn, (hipStream_t) stream);
     HF_HIP(hipGetLastError());
     return HF_OK;
 }

@@ -328,18 +328,186 @@ __device__ __forceinline__ hf_mt mt_terms(v3 o, v3 d, v3 p0, v3 e1, v3 e2) {
     return m;
 }
 
+// ---- Smooth shading (hf_set_face_normals(hf, 0)): angle-weighted vertex normals, the JIT path of
+// Mesh::recompute_vertex_normals (mesh.cpp:350-384), and the interpolated shading normal of mesh.cpp:792-840. ----
+
+// The shading normal is interpolated only when the reference fetches the vertex normals for it (mesh.cpp:813-815)
+__device__ __forceinline__ bool smooth_sh(uint32_t flags) { return (flags & (HF_RAY_SHADINGFRAME | HF_RAY_DNSDUV)) != 0u; }
+
+// world-space position of grid vertex (row i, column j) with height h: the expression of prim_world
+__device__ __forceinline__ v3 grid_world(const hf_dev_field &f, int i, int j, float h) {
+    return xform_point(f.to_world, mk3(__builtin_fmaf((float) j, f.sx, -1.0f), __builtin_fmaf((float) i, f.sy, -1.0f), h * f.s));
+}
+
+// The 1-ring of grid vertex (i, j).  With the diagonal split of test_cell, the vertex's neighbours in counter-clockwise
+// order are  E (i, j+1), N (i+1, j), NW (i+1, j-1), W (i, j-1), S (i-1, j), SE (i-1, j+1)  and its incident triangles
+// are exactly (X, R[k], R[k+1 mod 6]) for the consecutive pairs that both exist: tri 0 of cell (j, i) = (X, E, N),
+// tri 1 of cell (j-1, i) = (N, NW, X), tri 0 of cell (j-1, i) = (W, X, NW), tri 1 of cell (j-1, i-1) = (X, W, S),
+// tri 0 of cell (j, i-1) = (S, SE, X), tri 1 of cell (j, i-1) = (E, X, SE), each rotated so that X comes first (a
+// rotation keeps cross(v1 - v0, v2 - v0)).  Up to 6 triangles; border and corner vertices have fewer.  Absent
+// neighbours are loaded at the vertex itself (in bounds) and never used.
+struct hf_ring {
+    v3 X, R[6];
+    int i[7], j[7]; // texel of the vertex (index 6) and of ring vertex k
+    uint32_t in;    // bit k: ring vertex k exists
+};
+__device__ __forceinline__ bool ring_tri(uint32_t in, int k) { return ((in >> k) & (in >> ((k + 1) % 6)) & 1u) != 0u; }
+// dh (optional): per-texel height tangents, returned in dX / dR
+__device__ __forceinline__ void ring_world(const hf_dev_field &f, int i, int j, hf_ring &g, const float *dh = nullptr,
+                                           float *dX = nullptr, float *dR = nullptr) {
+    const int di[6] = { 0, 1, 1, 0, -1, -1 }, dj[6] = { 1, 0, -1, -1, 0, 1 };
+    g.in = 0u;
+    g.i[6] = i; g.j[6] = j;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int ii = i + di[k], jj = j + dj[k];
+        const bool ok = ii >= 0 && ii < f.H && jj >= 0 && jj < f.W;
+        g.i[k] = ok ? ii : i; g.j[k] = ok ? jj : j;
+        g.in |= ok ? (1u << k) : 0u;
+    }
+    const size_t x = (size_t) i * f.W + j;
+    g.X = grid_world(f, i, j, f.h[x]);
+    if (dh) *dX = dh[x];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const size_t r = (size_t) g.i[k] * f.W + g.j[k];
+        g.R[k] = grid_world(f, g.i[k], g.j[k], f.h[r]);
+        if (dh) dR[k] = dh[r];
+    }
+}
+// unit edge directions u_k = (R_k - X) l_k, l_k = 1 / |R_k - X|
+__device__ __forceinline__ void ring_dirs(const hf_ring &g, v3 u[6], float l[6]) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const v3 e = g.R[k] - g.X;
+        l[k] = rsqrt_ieee(dot3(e, e));
+        u[k] = e * l[k];
+    }
+}
+// interior angle of triangle k at X: safe_acos(dot(d0, d1))
+__device__ __forceinline__ float ring_angle(float c) { return acosf(fminf(fmaxf(c, -1.f), 1.f)); }
+// d safe_acos(c) / dc (0 where the clamp is active)
+__device__ __forceinline__ float ring_dangle(float c) { return (c > -1.f && c < 1.f) ? -rsqrt_ieee(1.f - c * c) : 0.f; }
+
+// m = sum_k face_normal_k * angle_k; returns |m|^-1 in rm (the vertex normal is m rm)
+__device__ __forceinline__ v3 ring_sum(const hf_ring &g, const v3 u[6], float &rm) {
+    v3 m = mk3(0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        if (!ring_tri(g.in, k)) continue;
+        const int k1 = (k + 1) % 6;
+        const v3 nt = unit_normal(g.R[k] - g.X, g.R[k1] - g.X).n;
+        m = fma3(nt, ring_angle(dot3(u[k], u[k1])), m);
+    }
+    rm = rsqrt_ieee(dot3(m, m));
+    return m;
+}
+// world-space normal of grid vertex (i, j) (before flip_normals, which the reference applies after interpolation)
+__device__ __forceinline__ v3 vertex_normal(const hf_dev_field &f, int i, int j) {
+    hf_ring g;
+    ring_world(f, i, j, g);
+    v3 u[6];
+    float l[6], rm;
+    ring_dirs(g, u, l);
+    const v3 m = ring_sum(g, u, rm);
+    return m * rm;
+}
+
+// Tangent of vertex_normal: the heights of X and of ring vertex k move by dX, dR[k]; ez = dP/dh (third column of
+// to_world times max_height).  dn = (dm - n <n, dm>) / |m| with dm = sum_k dface_k angle_k + face_k dangle_k.
+__device__ __forceinline__ v3 vertex_normal_jvp(const hf_ring &g, v3 ez, float dX, const float dR[6]) {
+    v3 u[6];
+    float l[6], rm;
+    ring_dirs(g, u, l);
+    const v3 m = ring_sum(g, u, rm);
+    v3 dm = mk3(0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        if (!ring_tri(g.in, k)) continue;
+        const int k1 = (k + 1) % 6;
+        const v3 e1 = g.R[k] - g.X, e2 = g.R[k1] - g.X;
+        const v3 de1 = ez * (dR[k] - dX), de2 = ez * (dR[k1] - dX);
+        const auto [nt, r] = unit_normal(e1, e2);
+        const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);
+        const v3 dN = mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
+        const float pj = dot3(nt, dN);
+        const v3 dnt = mk3((dN.x - nt.x * pj) * r, (dN.y - nt.y * pj) * r, (dN.z - nt.z * pj) * r);
+        const float c = dot3(u[k], u[k1]);
+        const v3 du1 = (de1 - u[k] * dot3(u[k], de1)) * l[k], du2 = (de2 - u[k1] * dot3(u[k1], de2)) * l[k1];
+        const float dth = ring_dangle(c) * (dot3(du1, u[k1]) + dot3(u[k], du2));
+        axpy3(ring_angle(c), dnt, dm);
+        axpy3(dth, nt, dm);
+    }
+    const v3 n = m * rm;
+    const float pj = dot3(n, dm);
+    return mk3((dm.x - n.x * pj) * rm, (dm.y - n.y * pj) * rm, (dm.z - n.z * pj) * rm);
+}
+// Transpose of vertex_normal_jvp: for the upstream gradient gn of the vertex normal, the gradients with respect to the
+// heights of X (gX) and of ring vertex k (gR[k]; zero for absent neighbours).  The position gradients are contracted
+// with ez as they arise (a height moves its vertex along ez only), so no per-edge vector accumulator is live:
+//   d/de_k of face_k:   cross(e_k+1, gN),  d/de_k+1: cross(gN, e_k)
+//   d/de_k of angle_k:  gc l_k (u_k+1 - u_k c)  (and symmetrically), c = <u_k, u_k+1>
+__device__ __forceinline__ void vertex_normal_vjp(const hf_ring &g, v3 ez, v3 gn, float &gX, float gR[6]) {
+    v3 u[6];
+    float l[6], rm;
+    ring_dirs(g, u, l);
+    const v3 m = ring_sum(g, u, rm);
+    const v3 n = m * rm;
+    const float pn = dot3(n, gn);
+    const v3 gm = mk3((gn.x - n.x * pn) * rm, (gn.y - n.y * pn) * rm, (gn.z - n.z * pn) * rm);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) gR[k] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        if (!ring_tri(g.in, k)) continue;
+        const int k1 = (k + 1) % 6;
+        const v3 e1 = g.R[k] - g.X, e2 = g.R[k1] - g.X;
+        const auto [nt, r] = unit_normal(e1, e2);
+        const float c = dot3(u[k], u[k1]), th = ring_angle(c);
+        const v3 gnt = gm * th;
+        const float pj = dot3(nt, gnt);
+        const v3 gN = mk3((gnt.x - nt.x * pj) * r, (gnt.y - nt.y * pj) * r, (gnt.z - nt.z * pj) * r);
+        const float gc = ring_dangle(c) * dot3(nt, gm);
+        const float ez0 = dot3(ez, u[k]), ez1 = dot3(ez, u[k1]);
+        gR[k] += dot3(ez, cross3(e2, gN)) + gc * l[k] * (ez1 - ez0 * c);
+        gR[k1] += dot3(ez, cross3(gN, e1)) + gc * l[k1] * (ez0 - ez1 * c);
+    }
+    gX = 0.f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) gX -= gR[k];
+}
+
+// The three vertex normals of a hit from the handle's buffer (one 16-byte load each)
+__device__ __forceinline__ void load_vn(const hf_dev_field &f, const float4 *vn, const int vi[3], const int vj[3], v3 N[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 q = vn[(size_t) vi[k] * f.W + vj[k]];
+        N[k] = mk3(q.x, q.y, q.z);
+    }
+}
+// fmadd(n2, b2, fmadd(n1, b1, n0 * b0)) (mesh.cpp:818)
+__device__ __forceinline__ v3 bary_normal(const v3 N[3], float b0, float b1, float b2) {
+    return mk3(__builtin_fmaf(N[2].x, b2, __builtin_fmaf(N[1].x, b1, N[0].x * b0)),
+               __builtin_fmaf(N[2].y, b2, __builtin_fmaf(N[1].y, b1, N[0].y * b0)),
+               __builtin_fmaf(N[2].z, b2, __builtin_fmaf(N[1].z, b1, N[0].z * b0)));
+}
+
 // Shape::compute_surface_interaction + finalize_surface_interaction for one valid hit, from the hit-geometry helpers
 // above (hf_adjoint_kernel and hf_tangent_kernel differentiate the same quantities).
+// SMOOTH (vn: the handle's vertex normals): sh_n is the interpolated vertex normal (mesh.cpp:813-840) when smooth_sh(flags),
+// and the shading frame and wi are built on it; the sink then takes n and sh_n separately (n_face / sh_n).
 // The fields are handed to `out` as soon as they are final (out.t(..), out.p(..), ...): the record sink below collects
 // them into an hf_si_rec; the fused traversal kernel stores each one straight away, so that the whole record is
 // never live in registers at once.
-template <typename Out>
+template <bool SMOOTH = false, typename Out>
 __device__ __forceinline__ void compute_si_to(const hf_dev_field &f, v3 o, v3 d, float t_in, float b1, float b2,
-                                              uint32_t prim, uint32_t flags, Out &out) {
+                                              uint32_t prim, uint32_t flags, Out &out, const float4 *vn = nullptr) {
     v3 P[3];
     float U[3], V[3];
     int vi[3], vj[3];
     prim_world(f, prim, P, U, V, vi, vj);
+    v3 NV[3];
+    if (SMOOTH && smooth_sh(flags)) load_vn(f, vn, vi, vj, NV); // (issued with the heights)
     const float b0 = 1.f - b1 - b2;
     const v3 dp0 = P[1] - P[0], dp1 = P[2] - P[0];
     const v3 p = bary_point(P, b0, b1, b2);
@@ -375,7 +543,16 @@ __device__ __forceinline__ void compute_si_to(const hf_dev_field &f, v3 o, v3 d,
     out.uv(uv0, uv1);
     out.dp_dv(dp_dv);
     if (f.flip) n = neg3(n);
-    out.n(n); // n and sh_n
+    if constexpr (SMOOTH) {
+        out.n_face(n);
+        if (smooth_sh(flags)) {
+            n = normalize3(bary_normal(NV, b0, b1, b2));
+            if (f.flip) n = neg3(n); // (after the interpolation, mesh.cpp:837-840)
+        }
+        out.sh_n(n); // n is sh_n from here on
+    } else {
+        out.n(n); // n and sh_n
+    }
     v3 sh_s = mk3(0.f, 0.f, 0.f), sh_t = mk3(0.f, 0.f, 0.f);
     if (flags & HF_RAY_SHADINGFRAME) { // initialize_sh_frame: Gram-Schmidt on dp_du
         const float nd = -dot3(n, dp_du);
@@ -412,6 +589,8 @@ struct hf_si_rec_sink {
     __device__ __forceinline__ void dp_du(v3 v) { si.dp_du = v; }
     __device__ __forceinline__ void dp_dv(v3 v) { si.dp_dv = v; }
     __device__ __forceinline__ void n(v3 v) { si.n = v; si.sh_n = v; }
+    __device__ __forceinline__ void n_face(v3 v) { si.n = v; }
+    __device__ __forceinline__ void sh_n(v3 v) { si.sh_n = v; }
     __device__ __forceinline__ void sh_s(v3 v) { si.sh_s = v; }
     __device__ __forceinline__ void sh_t(v3 v) { si.sh_t = v; }
     __device__ __forceinline__ void wi(v3 v) { si.wi = v; }

@@ -6,8 +6,11 @@
 //        MODE 0 closest hit  -> PreliminaryIntersection   (row a1)
 //        MODE 1 any hit      -> ray_test                   (row a2)
 //        MODE 2 closest hit + fused surface interaction    (rows a1+a4)
-//   hf_si_kernel                                   compute_surface_interaction (row a4)
-//   hf_adjoint_kernel                              reverse mode of a4, atomic scatter (row a5)
+//        MODE 3 MODE 2 with smooth shading (hf_set_face_normals(hf, 0): interpolated vertex normals)
+//   hf_si_kernel / hf_si_smooth_kernel             compute_surface_interaction (row a4), flat / smooth shading
+//   hf_adjoint_kernel / hf_adjoint_smooth_kernel   reverse mode of a4, atomic scatter (row a5)
+//   hf_tangent_kernel / hf_tangent_smooth_kernel   forward mode of a4
+//   hf_vertex_normals_kernel, hf_shading_derivatives_kernel   smooth shading: the vertex normals, dn_du / dn_dv
 //   hf_direct_kernel / hf_direct_adjoint_kernel, hf_adam_kernel     next rows
 //
 // Traversal = a walk of the implicit quadtree over the cells (the grid is mirrored so the ray direction is
@@ -1307,6 +1310,7 @@ struct hf_trace_args {
     uint32_t aux_n;
     size_t aux_stride;
     float aux_cull;
+    const float4 *vn; // MODE 3: the handle's vertex normals (appended: the other modes' arguments keep their offsets)
 };
 
 // member-wise copy out of the kernarg segment (constant address space)
@@ -1365,6 +1369,8 @@ struct hf_si_sink {
         s3(ka->sio.n[0], ka->sio.n[1], ka->sio.n[2], v);
         s3(ka->sio.sh_n[0], ka->sio.sh_n[1], ka->sio.sh_n[2], v);
     }
+    __device__ __forceinline__ void n_face(v3 v) { s3(ka->sio.n[0], ka->sio.n[1], ka->sio.n[2], v); }
+    __device__ __forceinline__ void sh_n(v3 v) { s3(ka->sio.sh_n[0], ka->sio.sh_n[1], ka->sio.sh_n[2], v); }
     __device__ __forceinline__ void sh_s(v3 v) { s3(ka->sio.sh_s[0], ka->sio.sh_s[1], ka->sio.sh_s[2], v); }
     __device__ __forceinline__ void sh_t(v3 v) { s3(ka->sio.sh_t[0], ka->sio.sh_t[1], ka->sio.sh_t[2], v); }
     __device__ __forceinline__ void wi(v3 v) { s3(ka->sio.wi[0], ka->sio.wi[1], ka->sio.wi[2], v); }
@@ -1373,6 +1379,7 @@ struct hf_si_sink {
 // Persistent waves: every wave pulls `grab` consecutive rays at a time from a global
 // counter (zeroed on the stream before the launch), so expensive image regions are
 // spread over all CUs whatever their position in the wavefront.
+// MODE 3: the fused mode with smooth shading, its own instantiations (the flat ones do not read the vertex normals).
 // AUX (fused mode only): auxiliary ray a.aux_k of every ray is traced instead of the ray itself (hf_reparam_trace) -- an
 // instantiation of its own, so that the sampling code costs the ordinary fused launch nothing (inline it was +1.5 %).
 // LEAN (round 4): the instantiations for launches the caller declares INCOHERENT -- the `coherent = false` of
@@ -1389,7 +1396,7 @@ struct hf_si_sink {
 #define HF_LEAN_WAVES_AUX 7
 #endif
 template <int MODE, bool AUX = false, bool LEAN = false>
-__global__ __launch_bounds__(HF_BLOCK, (LEAN ? (AUX ? HF_LEAN_WAVES_AUX : HF_LEAN_WAVES) : MODE == 2 ? HF_TRACE_WAVES_FUSED : HF_TRACE_WAVES))
+__global__ __launch_bounds__(HF_BLOCK, (LEAN ? (AUX ? HF_LEAN_WAVES_AUX : HF_LEAN_WAVES) : MODE >= 2 ? HF_TRACE_WAVES_FUSED : HF_TRACE_WAVES))
 void hf_trace_kernel(hf_trace_args a) {
     const hf_dev_field &f = a.f;
     const unsigned lane = threadIdx.x & 63u;
@@ -1510,7 +1517,7 @@ void hf_trace_kernel(hf_trace_args a) {
                             if (pi.prim_uv[0]) st4(pi.prim_uv[0], ubw, l4, zero);
                             if (pi.prim_uv[1]) st4(pi.prim_uv[1], ubw, l4, zero);
                             if (pi.prim_index) st4((float *) pi.prim_index, ubw, l4, zero);
-                            if (MODE == 2) { // zero-initialised record (interaction.h:479-499, 667-673), wi = -d
+                            if (MODE >= 2) { // zero-initialised record (interaction.h:479-499, 667-673), wi = -d
                                 const uint32_t flags = kw->flags;
                                 const hf_si_t sd = load_si(kw);
                                 st4(sd.t, ubw, l4, inf4);
@@ -1553,13 +1560,13 @@ void hf_trace_kernel(hf_trace_args a) {
             const size_t left = n - ub; // >= 1
             const bool valid = lane < left;
             const uint32_t lo = valid ? lane : (uint32_t) (left - 1);
-            if ((MODE == 2 && AUX) || (sub & 255u) == 0u) { // first batch of a fetch: nothing was requested ahead (see the end of the body; AUX never requests ahead)
+            if ((MODE >= 2 && AUX) || (sub & 255u) == 0u) { // first batch of a fetch: nothing was requested ahead (see the end of the body; AUX never requests ahead)
                 const hf_rays_t rp = load_rays(ka);
                 o = mk3((rp.o[0] + ub)[lo], (rp.o[1] + ub)[lo], (rp.o[2] + ub)[lo]);
                 d = mk3((rp.d[0] + ub)[lo], (rp.d[1] + ub)[lo], (rp.d[2] + ub)[lo]);
                 maxt = (rp.maxt + ub)[lo];
             }
-            if (MODE == 2 && AUX) {
+            if (MODE >= 2 && AUX) {
                 // ---- all samples of all 64 rays at once: when no auxiliary ray of the batch can enter the bound (60 % of
                 // the bench wavefront), the aux_n miss records go out without a single sample being drawn ----
                 const float ct = ka->aux_cull;
@@ -1594,7 +1601,7 @@ void hf_trace_kernel(hf_trace_args a) {
             }
 #pragma unroll 1
             for (uint32_t ak = 0;; ++ak) { // (one trip unless AUX; the trip count is read from the kernarg segment at the end of the body)
-            if (MODE == 2 && AUX) {
+            if (MODE >= 2 && AUX) {
                 asm volatile("" : "+s"(ka)); // opaque per sample: kernarg loads stay inside the loop instead of being hoisted (and spilled)
                 // the ray again (an L1 / L2 hit from the second sample on): nothing of it is held across the walk
                 const hf_rays_t rp = load_rays(ka);
@@ -1668,9 +1675,9 @@ void hf_trace_kernel(hf_trace_args a) {
             // complete in order, so a wave that loads after its stores waits for the store acknowledgements
             // (HBM write latency) on top of its own load latency -- that serial chain, not bandwidth, bounded
             // the rays that only stream.
-            const bool more = (MODE == 2 && AUX) && ak + 1u < ka->aux_n; // further samples of this batch (AUX re-reads its rays: no request ahead)
-            const size_t ubo = (MODE == 2 && AUX) ? ub + (size_t) ak * ka->aux_stride : ub; // where this sample's records go
-            if (MODE == 2 && AUX) {
+            const bool more = (MODE >= 2 && AUX) && ak + 1u < ka->aux_n; // further samples of this batch (AUX re-reads its rays: no request ahead)
+            const size_t ubo = (MODE >= 2 && AUX) ? ub + (size_t) ak * ka->aux_stride : ub; // where this sample's records go
+            if (MODE >= 2 && AUX) {
                 o = mk3(0.f, 0.f, 0.f); d = o; maxt = 0.f;
             } else if (((sub + 64u) & 255u) != 0u && sub + 64 < grab && ub + 64 < n) { // (the next fetch decides about its own rays)
                 const size_t ub2 = ub + 64, left2 = n - ub2;
@@ -1692,7 +1699,7 @@ void hf_trace_kernel(hf_trace_args a) {
                 if (pi.prim_uv[0]) (pi.prim_uv[0] + ubo)[lo] = best.hit ? best.u : 0.f;
                 if (pi.prim_uv[1]) (pi.prim_uv[1] + ubo)[lo] = best.hit ? best.v : 0.f;
                 if (pi.prim_index) (pi.prim_index + ubo)[lo] = best.hit ? best.prim : 0u;
-                if (MODE == 2) {
+                if (MODE >= 2) {
                     const uint32_t flags = ka->flags;
                     hf_si_sink<hf_kargs_ptr> out = { ka, ubo, lo, flags };
                     if (best.hit) {
@@ -1701,7 +1708,8 @@ void hf_trace_kernel(hf_trace_args a) {
                         const v3 ow = mk3((rp.o[0] + ub)[lo], (rp.o[1] + ub)[lo], (rp.o[2] + ub)[lo]);
                         const hf_dev_field fl = load_field(&ka->f); // to_world etc.: not held across the walk
                         // every field is stored as soon as it is final: the record is never whole in registers
-                        compute_si_to(fl, ow, dw, best.t, best.u, best.v, best.prim, flags, out);
+                        if constexpr (MODE == 3) compute_si_to<true>(fl, ow, dw, best.t, best.u, best.v, best.prim, flags, out, ka->vn);
+                        else                     compute_si_to(fl, ow, dw, best.t, best.u, best.v, best.prim, flags, out);
                     } else {
                         si_miss_to(out, flags);
                         out.wi(neg3(dw));
@@ -1768,7 +1776,7 @@ size_t hf_trace_scratch_bytes(size_t n) {
 
 void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t *rays, const uint8_t *active,
                      const hf_pi_t *pi, uint8_t *hit, const hf_si_t *si, uint32_t flags, void *scratch,
-                     hipStream_t stream, const hf_reparam_args *aux, bool lean) {
+                     hipStream_t stream, const hf_reparam_args *aux, bool lean, const float4 *vn) {
     if (n == 0) return;
     (void) hipMemsetAsync(scratch, 0, HF_SCR_BYTES, stream);
     const hf_pi_t p = pi ? *pi : hf_pi_t{};
@@ -1797,6 +1805,7 @@ void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t 
     a.n_grabs = waves;
     a.aux_on = 0u; a.aux_k = 0u; a.aux_seed = 0u; a.aux_kappa = 1.f; a.aux_antithetic = 0; a.aux_ray_id = nullptr;
     a.aux_n = 1u; a.aux_stride = 0; a.aux_cull = 0.f;
+    a.vn = vn;
     if (aux && mode == 2) {
         a.aux_on = 1u; a.aux_k = aux->k; a.aux_seed = aux->seed; a.aux_kappa = aux->kappa; a.aux_antithetic = aux->antithetic;
         a.aux_ray_id = aux->ray_id;
@@ -1818,12 +1827,16 @@ void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t 
         a.aux_cull = 0.f;
 #endif
     }
-    // [lean][mode + aux]: the auxiliary-ray sampling exists in the fused mode only
+    // [lean][mode + aux]: the auxiliary-ray sampling exists in the fused mode only; vn: the smooth-shading instantiations
     static void (*const kernel[2][4])(hf_trace_args) = {
         { hf_trace_kernel<0>, hf_trace_kernel<1>, hf_trace_kernel<2>, hf_trace_kernel<2, true> },
         { hf_trace_kernel<0, false, true>, hf_trace_kernel<1, false, true>, hf_trace_kernel<2, false, true>, hf_trace_kernel<2, true, true> },
     };
-    hipLaunchKernelGGL(kernel[lean][mode + a.aux_on], grid, block, 0, stream, a);
+    static void (*const smooth[2][2])(hf_trace_args) = {
+        { hf_trace_kernel<3>, hf_trace_kernel<3, true> }, { hf_trace_kernel<3, false, true>, hf_trace_kernel<3, true, true> },
+    };
+    if (vn && mode == 2) hipLaunchKernelGGL(smooth[lean][a.aux_on], grid, block, 0, stream, a);
+    else                 hipLaunchKernelGGL(kernel[lean][mode + a.aux_on], grid, block, 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1839,11 +1852,13 @@ struct hf_si_args {
     const uint8_t *active;
     hf_si_t sio;
     uint32_t flags;
+    const float4 *vn; // hf_si_smooth_kernel: the handle's vertex normals
 };
 typedef const __attribute__((address_space(4))) hf_si_args *hf_si_kargs;
 
-__global__ __launch_bounds__(HF_BLOCK) void hf_si_kernel(hf_si_args a_) {
-    (void) a_;
+// the body of hf_si_kernel (flat shading) and hf_si_smooth_kernel
+template <bool SMOOTH>
+__device__ __forceinline__ void si_body() {
     const uint32_t lane = threadIdx.x & 63u;
     const size_t stride = (size_t) gridDim.x * HF_BLOCK;
     for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u);; ub += stride) {
@@ -1864,20 +1879,22 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_si_kernel(hf_si_args a_) {
             const float b1 = (ka->pi.prim_uv[0] + ub)[lo], b2 = (ka->pi.prim_uv[1] + ub)[lo];
             const uint32_t prim = (ka->pi.prim_index + ub)[lo];
             const hf_dev_field f = load_field(&ka->f);
-            compute_si_to(f, o, d, t, b1, b2, prim, flags, out);
+            compute_si_to<SMOOTH>(f, o, d, t, b1, b2, prim, flags, out, SMOOTH ? ka->vn : nullptr);
         } else {
             si_miss_to(out, flags);
             out.wi(neg3(d));
         }
     }
 }
+__global__ __launch_bounds__(HF_BLOCK) void hf_si_kernel(hf_si_args a_) { (void) a_; si_body<false>(); }
+__global__ __launch_bounds__(HF_BLOCK) void hf_si_smooth_kernel(hf_si_args a_) { (void) a_; si_body<true>(); }
 
 void hf_launch_si(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
-                  const uint8_t *active, const hf_si_t *si, uint32_t flags, hipStream_t stream) {
+                  const uint8_t *active, const hf_si_t *si, uint32_t flags, hipStream_t stream, const float4 *vn) {
     if (n == 0) return;
     hf_si_args a;
-    a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.sio = *si; a.flags = flags;
-    hipLaunchKernelGGL(hf_si_kernel, dim3(grid_for(n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, a);
+    a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.sio = *si; a.flags = flags; a.vn = vn;
+    hipLaunchKernelGGL(vn ? hf_si_smooth_kernel : hf_si_kernel, dim3(grid_for(n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2005,6 +2022,7 @@ struct hf_adjoint_args {
     float *grad_h;
     float *go[3], *gd[3];
     uint32_t *row_band; // optional: {lowest texture row that received a contribution, highest + 1}, atomicMin / atomicMax
+    const float4 *vn;   // hf_adjoint_smooth_kernel: the handle's vertex normals
 };
 typedef const __attribute__((address_space(4))) hf_adjoint_args *hf_adj_kargs;
 __device__ __forceinline__ hf_adj_kargs adj_kargs() {
@@ -2015,17 +2033,18 @@ __device__ __forceinline__ hf_adj_kargs adj_kargs() {
 // (row + ub)[lo], 0 for an absent row: scalar base + 32-bit lane offset
 __device__ __forceinline__ float ldu(const float *p, size_t ub, uint32_t lo) { return p ? (p + ub)[lo] : 0.f; }
 
-// RAYGRAD: dL/do and dL/dd are wanted (hf_adjoint's grad_o / grad_d); without them their accumulation is dead code
-template <bool RAYGRAD>
-__global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args a_) {
-    (void) a_;
+// RAYGRAD: dL/do and dL/dd are wanted (hf_adjoint's grad_o / grad_d); without them their accumulation is dead code.
+// SMOOTH (hf_adjoint_smooth_kernel): sh_n is the interpolated vertex normal.  Its gradient reaches the heights through
+// the barycentrics (the Moeller-Trumbore reverse below) and through the three vertex normals: the VJP of vertex_normal
+// is evaluated per hit, on the fly, and its 7 contributions per vertex (the vertex and its 1-ring: up to 12 texels per
+// hit) go through the same LDS tile as the positions' three.  acc: the wave's tile (TILE x TILE floats of LDS).
+template <bool RAYGRAD, bool SMOOTH>
+__device__ __forceinline__ void adjoint_body(float *acc) {
     // Wave-level pre-reduction of the scatter: the hits of one wave (one pixel's samples for
     // primary rays) fall on a few dozen vertices, so their three contributions each are first
     // summed into a 32x32-texel LDS tile anchored near the wave's first hit (ds_add_f32) and the
     // tile is then flushed row by row -- contiguous segments, one global atomic per touched texel
     // instead of three per ray.  Contributions outside the tile go straight to global memory.
-    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
-    float *acc = s_acc[threadIdx.x >> 6];
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t k = lane; k < HF_ADJ_TILE * HF_ADJ_TILE; k += 64) acc[k] = 0.f;
     uint32_t row_lo = 0xFFFFFFFFu, row_hi = 0u; // rows this lane scattered to (hf_adjoint_rows)
@@ -2047,6 +2066,8 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
         float gh[3] = { 0.f, 0.f, 0.f };
         int vr[3] = { 0, 0, 0 }, vc[3] = { 0, 0, 0 };
         bool scatter = false;
+        v3 gnv[3]; // SMOOTH: dL/d(vertex normal k)
+        bool smv = false; // ... to be scattered through vertex_normal_vjp
         if (act) {
             // ONE batch of requests for everything a hit needs that does not depend on other loads -- the ray, the
             // rest of pi, the 18 upstream rows -- then the three heights behind prim_index: three dependent round
@@ -2070,6 +2091,9 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
             float U[3], V[3];
             int vi[3], vj[3];
             prim_world(f, prim, P, U, V, vi, vj);
+            const bool sm = SMOOTH && smooth_sh(flags);
+            v3 NV[3];
+            if (sm) load_vn(f, ka->vn, vi, vj, NV);
             const v3 dp0 = P[1] - P[0], dp1 = P[2] - P[0];
             const v3 p = bary_point(P, b0, b1, b2);
             const v3 z3 = mk3(0.f, 0.f, 0.f);
@@ -2085,11 +2109,12 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
                     axpy3(du0 * inv_det, gv_, gdp1);
                 }
             }
-            // n = sh_n = +-normalize(cross(dp0, dp1))
+            // n = sh_n = +-normalize(cross(dp0, dp1))  (smooth: n only)
             {
                 const auto [nn, r] = unit_normal(dp0, dp1);
                 const float sgn = f.flip ? -1.f : 1.f;
-                const v3 gn = mk3(sgn * (gn_a.x + gn_b.x), sgn * (gn_a.y + gn_b.y), sgn * (gn_a.z + gn_b.z));
+                const v3 gnf = sm ? gn_a : mk3(gn_a.x + gn_b.x, gn_a.y + gn_b.y, gn_a.z + gn_b.z);
+                const v3 gn = mk3(sgn * gnf.x, sgn * gnf.y, sgn * gnf.z);
                 const float proj = dot3(nn, gn);
                 const v3 gN = mk3((gn.x - nn.x * proj) * r, (gn.y - nn.y * proj) * r, (gn.z - nn.z * proj) * r);
                 axpy3(1.f, cross3(dp1, gN), gdp0);
@@ -2105,6 +2130,15 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
             }
             // p = sum b_k P_k, uv = sum b_k uv_k
             float gb0 = dot3(gp, P[0]), gb1 = dot3(gp, P[1]), gb2 = dot3(gp, P[2]);
+            if (sm) { // sh_n = +-normalize(sum b_k N_k): to the barycentrics and to the vertex normals
+                const v3 ns = bary_normal(NV, b0, b1, b2);
+                const float r = rsqrt_ieee(dot3(ns, ns));
+                const v3 sn = ns * r, gs = f.flip ? neg3(gn_b) : gn_b;
+                const float pj = dot3(sn, gs);
+                const v3 gns = mk3((gs.x - sn.x * pj) * r, (gs.y - sn.y * pj) * r, (gs.z - sn.z * pj) * r);
+                gb0 += dot3(gns, NV[0]); gb1 += dot3(gns, NV[1]); gb2 += dot3(gns, NV[2]);
+                gnv[0] = gns * b0; gnv[1] = gns * b1; gnv[2] = gns * b2;
+            }
             if (tex) {
                 gb0 += guv0 * U[0] + guv1 * V[0];
                 gb1 += guv0 * U[1] + guv1 * V[1];
@@ -2142,8 +2176,14 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
                 vr[0] = vi[0]; vr[1] = vi[1]; vr[2] = vi[2];
                 vc[0] = vj[0]; vc[1] = vj[1]; vc[2] = vj[2];
                 scatter = true;
-                row_lo = min(row_lo, (uint32_t) min(vi[0], min(vi[1], vi[2])));
-                row_hi = max(row_hi, (uint32_t) max(vi[0], max(vi[1], vi[2])) + 1u);
+                if (!sm) {
+                    row_lo = min(row_lo, (uint32_t) min(vi[0], min(vi[1], vi[2])));
+                    row_hi = max(row_hi, (uint32_t) max(vi[0], max(vi[1], vi[2])) + 1u);
+                } else { // the vertex normals reach one row further: the band widens by their halo
+                    row_lo = min(row_lo, (uint32_t) max(min(vi[0], min(vi[1], vi[2])) - 1, 0));
+                    row_hi = max(row_hi, (uint32_t) min(max(vi[0], max(vi[1], vi[2])) + 2, f.H));
+                }
+                smv = sm;
             }
         }
         const uint64_t sm = __ballot(scatter);
@@ -2156,6 +2196,21 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
             if (scatter)
 #pragma unroll
                 for (int k = 0; k < 3; ++k) tile_add<HF_ADJ_TILE>(acc, ar, ac, vr[k], vc[k], gh[k], grad_h, W, rows);
+            if (SMOOTH && smv) {
+                const hf_dev_field f = load_field(&adj_kargs()->f);
+                const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
+#pragma unroll 1
+                for (int k = 0; k < 3; ++k) {
+                    hf_ring g;
+                    ring_world(f, vr[k], vc[k], g);
+                    float gX, gR[6];
+                    vertex_normal_vjp(g, ez, gnv[k], gX, gR);
+                    tile_add<HF_ADJ_TILE>(acc, ar, ac, vr[k], vc[k], gX, grad_h, W, rows);
+#pragma unroll
+                    for (int q = 0; q < 6; ++q)
+                        if ((g.in >> q) & 1u) tile_add<HF_ADJ_TILE>(acc, ar, ac, g.i[q], g.j[q], gR[q], grad_h, W, rows);
+                }
+            }
             tile_flush<HF_ADJ_TILE>(acc, ar, ac, rows, grad_h, W, (int) lane);
         }
         if (RAYGRAD && valid) {
@@ -2176,17 +2231,32 @@ __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args
         }
     }
 }
+template <bool RAYGRAD>
+__global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args a_) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<RAYGRAD, false>(s_acc[threadIdx.x >> 6]);
+}
+template <bool RAYGRAD>
+__global__ __launch_bounds__(HF_BLOCK, 4) void hf_adjoint_smooth_kernel(hf_adjoint_args a_) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<RAYGRAD, true>(s_acc[threadIdx.x >> 6]);
+}
 
 void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, const hf_si_grad_t *gs, uint32_t flags, float *grad_h,
-                       float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream) {
+                       float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream,
+                       const float4 *vn) {
     if (n == 0) return;
     hf_adjoint_args a;
     a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.g = *gs; a.flags = flags; a.grad_h = grad_h;
-    a.row_band = row_band;
+    a.row_band = row_band; a.vn = vn;
     for (int k = 0; k < 3; ++k) { a.go[k] = grad_o ? grad_o[k] : nullptr; a.gd[k] = grad_d ? grad_d[k] : nullptr; }
-    if (grad_o || grad_d) hipLaunchKernelGGL(hf_adjoint_kernel<true>, dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a);
-    else                  hipLaunchKernelGGL(hf_adjoint_kernel<false>, dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a);
+    const bool rg = grad_o || grad_d;
+    void (*kernel)(hf_adjoint_args) = vn ? (rg ? hf_adjoint_smooth_kernel<true> : hf_adjoint_smooth_kernel<false>)
+                                         : (rg ? hf_adjoint_kernel<true> : hf_adjoint_kernel<false>);
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2207,13 +2277,15 @@ struct hf_tangent_args {
     const float *d_o[3], *d_d[3]; // per-ray tangents, NULL rows = zero
     hf_si_tangent_t out;        // NULL rows are not written
     uint32_t flags;
+    const float4 *vn;           // hf_tangent_smooth_kernel: the handle's vertex normals
 };
 typedef const __attribute__((address_space(4))) hf_tangent_args *hf_tan_kargs;
 
-// RAYTAN: d_o or d_d is given (without them the ray terms are dead code)
-template <bool RAYTAN>
-__global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_) {
-    (void) a_;
+// RAYTAN: d_o or d_d is given (without them the ray terms are dead code).
+// SMOOTH (hf_tangent_smooth_kernel): sh_n is the interpolated vertex normal; its tangent takes the barycentric tangents
+// and the tangents of the three vertex normals, evaluated on the fly from h and dh (vertex_normal_jvp: no atomics).
+template <bool RAYTAN, bool SMOOTH>
+__device__ __forceinline__ void tangent_body() {
     const uint32_t lane = threadIdx.x & 63u;
     const size_t stride = (size_t) gridDim.x * HF_BLOCK;
     for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u);; ub += stride) {
@@ -2251,9 +2323,12 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
         float U[3], V[3];
         int vi[3], vj[3];
         prim_world(f, prim, P, U, V, vi, vj, dP, detach ? nullptr : ka->dh);
+        const bool sm = SMOOTH && smooth_sh(flags);
+        v3 NV[3];
+        if (sm) load_vn(f, ka->vn, vi, vj, NV);
         const v3 e1 = P[1] - P[0], e2 = P[2] - P[0];
         const v3 de1 = dP[1] - dP[0], de2 = dP[2] - dP[0];
-        // n = sh_n = +-normalize(cross(e1, e2))
+        // n = sh_n = +-normalize(cross(e1, e2))  (smooth: n only; sh_n below)
         {
             const auto [nn, r] = unit_normal(e1, e2);
             const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);
@@ -2262,7 +2337,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
             const float sr = f.flip ? -r : r;
             const v3 dn = mk3((dN.x - nn.x * proj) * sr, (dN.y - nn.y * proj) * sr, (dN.z - nn.z * proj) * sr);
             st3(ka->out.n, ub, lo, dn);
-            st3(ka->out.sh_n, ub, lo, dn);
+            if (!sm) st3(ka->out.sh_n, ub, lo, dn);
         }
         // dp_du / dp_dv: linear in the edges (the texcoord differences are constant); zero without dPdUV
         {
@@ -2292,6 +2367,28 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
             dv = (dot3(dD, qvec) + dot3(d, dqvec)) * inv + a_v * dinv;
             dt = (dot3(de2, qvec) + dot3(e2, dqvec)) * inv + a_t * dinv;
         }
+        if (sm) { // sh_n = +-normalize(sum b_k N_k): d(sum b_k N_k) = du (N_1 - N_0) + dv (N_2 - N_0) + sum b_k dN_k
+            const v3 ns = bary_normal(NV, b0, b1, b2);
+            const float r = rsqrt_ieee(dot3(ns, ns));
+            const v3 sn = ns * r;
+            v3 dns = z3;
+            axpy3(du, NV[1] - NV[0], dns);
+            axpy3(dv, NV[2] - NV[0], dns);
+            const float *dh = detach ? nullptr : ka->dh;
+            if (dh) {
+                const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
+                const float bk[3] = { b0, b1, b2 };
+#pragma unroll 1
+                for (int k = 0; k < 3; ++k) {
+                    hf_ring g;
+                    float dX, dR[6];
+                    ring_world(f, vi[k], vj[k], g, dh, &dX, dR);
+                    axpy3(bk[k], vertex_normal_jvp(g, ez, dX, dR), dns);
+                }
+            }
+            const float pj = dot3(sn, dns), sr = f.flip ? -r : r;
+            st3(ka->out.sh_n, ub, lo, mk3((dns.x - sn.x * pj) * sr, (dns.y - sn.y * pj) * sr, (dns.z - sn.z * pj) * sr));
+        }
         // p = sum b_k P_k:  dp = du e1 + dv e2 + sum b_k dP_k
         const v3 dp = mk3(du * e1.x + dv * e2.x + (b0 * dP[0].x + b1 * dP[1].x + b2 * dP[2].x),
                           du * e1.y + dv * e2.y + (b0 * dP[0].y + b1 * dP[1].y + b2 * dP[2].y),
@@ -2311,21 +2408,92 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_
         st(ka->out.uv[1], ub, lo, duv1);
     }
 }
+template <bool RAYTAN>
+__global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_) { (void) a_; tangent_body<RAYTAN, false>(); }
+template <bool RAYTAN>
+__global__ __launch_bounds__(HF_BLOCK) void hf_tangent_smooth_kernel(hf_tangent_args a_) { (void) a_; tangent_body<RAYTAN, true>(); }
 
 void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, uint32_t flags, const float *dh, const float *const d_o[3],
-                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream) {
+                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream, const float4 *vn) {
     if (n == 0) return;
     hf_tangent_args a;
-    a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.dh = dh; a.out = *out; a.flags = flags;
+    a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.dh = dh; a.out = *out; a.flags = flags; a.vn = vn;
     bool raytan = false;
     for (int k = 0; k < 3; ++k) {
         a.d_o[k] = d_o ? d_o[k] : nullptr; a.d_d[k] = d_d ? d_d[k] : nullptr;
         raytan = raytan || a.d_o[k] || a.d_d[k];
     }
     const dim3 grid(grid_for(n, HF_SI_GRID_CAP)), block(HF_BLOCK);
-    if (raytan) hipLaunchKernelGGL(hf_tangent_kernel<true>, grid, block, 0, stream, a);
-    else        hipLaunchKernelGGL(hf_tangent_kernel<false>, grid, block, 0, stream, a);
+    void (*kernel)(hf_tangent_args) = vn ? (raytan ? hf_tangent_smooth_kernel<true> : hf_tangent_smooth_kernel<false>)
+                                         : (raytan ? hf_tangent_kernel<true> : hf_tangent_kernel<false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
+// Smooth shading: the handle's vertex normals (one float4 per vertex: one 16-byte gather per vertex of a hit) and the
+// forward-only dn_du / dn_dv of hf_shading_derivatives
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(HF_BLOCK) void hf_vertex_normals_kernel(hf_dev_field f, float4 *__restrict__ vn) {
+    const uint32_t x = blockIdx.x * HF_BLOCK + threadIdx.x; // (W H <= 2^30, checked by hf_create)
+    if (x >= (uint32_t) f.W * (uint32_t) f.H) return;
+    const int i = (int) (x / (uint32_t) f.W), j = (int) (x - (uint32_t) i * (uint32_t) f.W);
+    const v3 n = vertex_normal(f, i, j);
+    vn[x] = make_float4(n.x, n.y, n.z, 0.f);
+}
+
+void hf_launch_build_normals(const hf_dev_field &f, float4 *vn, hipStream_t stream) {
+    const uint32_t n = (uint32_t) f.W * (uint32_t) f.H;
+    hipLaunchKernelGGL(hf_vertex_normals_kernel, dim3((n + HF_BLOCK - 1) / HF_BLOCK), dim3(HF_BLOCK), 0, stream, f, vn);
+}
+
+struct hf_shading_deriv_args {
+    int32_t W;
+    size_t n;
+    hf_pi_const_t pi;
+    const uint8_t *active;
+    const float4 *vn; // NULL: flat shading (zeros)
+    float *dn_du[3], *dn_dv[3];
+};
+// mesh.cpp:818-829: with N = sum b_k N_k and il = |N|^-1, n = N il,
+//   dn_du = (N_1 - N_0) il - n <n, (N_1 - N_0) il>,  dn_dv = (N_2 - N_0) il - n <n, (N_2 - N_0) il>
+// (derivatives with respect to the barycentrics b1, b2; not flipped by flip_normals, as in the reference)
+__global__ __launch_bounds__(HF_BLOCK) void hf_shading_derivatives_kernel(hf_shading_deriv_args a) {
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
+        v3 du = mk3(0.f, 0.f, 0.f), dv = du;
+        const bool act = (a.active ? a.active[i] != 0 : true) && a.pi.t[i] != __builtin_inff();
+        if (act && a.vn) {
+            const float b1 = a.pi.prim_uv[0][i], b2 = a.pi.prim_uv[1][i], b0 = 1.f - b1 - b2;
+            hf_dev_field f;
+            f.W = a.W;
+            int vi[3], vj[3];
+            prim_vertex_ids(f, a.pi.prim_index[i], vi, vj);
+            v3 N[3];
+            load_vn(f, a.vn, vi, vj, N);
+            const v3 ns = bary_normal(N, b0, b1, b2);
+            const float il = rsqrt_ieee(dot3(ns, ns));
+            const v3 n = ns * il;
+            du = (N[1] - N[0]) * il;
+            dv = (N[2] - N[0]) * il;
+            du = fma3(n, -dot3(n, du), du);
+            dv = fma3(n, -dot3(n, dv), dv);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (a.dn_du[c]) a.dn_du[c][i] = c == 0 ? du.x : c == 1 ? du.y : du.z;
+            if (a.dn_dv[c]) a.dn_dv[c][i] = c == 0 ? dv.x : c == 1 ? dv.y : dv.z;
+        }
+    }
+}
+
+void hf_launch_shading_derivatives(const hf_dev_field &f, size_t n, const hf_pi_const_t *pi, const uint8_t *active,
+                                   float *const dn_du[3], float *const dn_dv[3], const float4 *vn, hipStream_t stream) {
+    if (n == 0) return;
+    hf_shading_deriv_args a;
+    a.W = f.W; a.n = n; a.pi = *pi; a.active = active; a.vn = vn;
+    for (int c = 0; c < 3; ++c) { a.dn_du[c] = dn_du ? dn_du[c] : nullptr; a.dn_dv[c] = dn_dv ? dn_dv[c] : nullptr; }
+    hipLaunchKernelGGL(hf_shading_derivatives_kernel, dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------

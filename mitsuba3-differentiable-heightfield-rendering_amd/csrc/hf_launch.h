@@ -14,16 +14,24 @@ struct hf_reparam_args;
 // aux (mode 2 only, may be NULL): trace auxiliary ray aux->k of every ray (k, seed, kappa, antithetic are read)
 void hf_launch_trace(int mode, const hf_dev_field &f, size_t n, const hf_rays_t *rays, const uint8_t *active,
                      const hf_pi_t *pi, uint8_t *hit, const hf_si_t *si, uint32_t flags, void *scratch,
-                     hipStream_t stream, const hf_reparam_args *aux = nullptr, bool lean = false); // lean: the launch is declared incoherent (hf_set_ray_coherence)
+                     hipStream_t stream, const hf_reparam_args *aux = nullptr, bool lean = false, // lean: the launch is declared incoherent (hf_set_ray_coherence)
+                     const float4 *vn = nullptr); // vn (mode 2): the handle's vertex normals = smooth shading
+// vn (here and below): the handle's vertex normals when it shades smoothly (hf_set_face_normals), NULL = flat shading
 void hf_launch_si(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
-                  const uint8_t *active, const hf_si_t *si, uint32_t flags, hipStream_t stream);
+                  const uint8_t *active, const hf_si_t *si, uint32_t flags, hipStream_t stream, const float4 *vn = nullptr);
 void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, const hf_si_grad_t *gs, uint32_t flags, float *grad_h,
-                       float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream);
+                       float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream,
+                       const float4 *vn = nullptr);
 // forward mode of compute_si (hf_tangent): dh / d_o / d_d may be NULL (zero tangents)
 void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, uint32_t flags, const float *dh, const float *const d_o[3],
-                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream);
+                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream, const float4 *vn = nullptr);
+// smooth shading: the vertex normals of the current heights and transform into vn (W H float4)
+void hf_launch_build_normals(const hf_dev_field &f, float4 *vn, hipStream_t stream);
+// hf_shading_derivatives: dn_du / dn_dv rows (NULL rows are not written); vn NULL = flat shading = zeros
+void hf_launch_shading_derivatives(const hf_dev_field &f, size_t n, const hf_pi_const_t *pi, const uint8_t *active,
+                                   float *const dn_du[3], float *const dn_dv[3], const float4 *vn, hipStream_t stream);
 // c1 = (float)(1 - beta1), c2 = (float)(1 - beta2): the differences are Python doubles in optimizers.py:279-280,
 // rounded once when they meet the float32 gradient
 hipError_t hf_launch_adam(size_t n, float *h, const float *g, float *m, float *v, float lr_t, float beta1, float beta2,

@@ -221,7 +221,9 @@ class Heightfield:
     Properties (build decision, SURVEY.md section 8a -- the reference snapshot has no
     heightfield plugin): `heightfield` ([H, W] or [H, W, 1] tensor, row 0 at object
     y = -1; cf. TensorXf(data, 3, {H,W,C}) in src/textures/bitmap.cpp:262),
-    `max_height`, `to_world` (3x4 / 4x4 affine), `flip_normals`.
+    `max_height`, `to_world` (3x4 / 4x4 affine), `flip_normals`, `face_normals`.
+    `face_normals` is Mesh's property (src/render/mesh.cpp:30) but defaults to True (flat shading), where Mesh's
+    defaults to False: a heightfield shades flat unless smooth shading is asked for (hf_set_face_normals).
     Object space is Rectangle's: x,y in [-1,1], +Z up (src/shapes/rectangle.cpp:47-48).
     """
 
@@ -232,6 +234,7 @@ class Heightfield:
         self.max_height = float(props.pop("max_height", 1.0))
         to_world = props.pop("to_world", None)
         self.flip_normals = bool(props.pop("flip_normals", False))
+        face_normals = bool(props.pop("face_normals", True))
         device = props.pop("device", None)
         if props:
             raise RuntimeError(f"Unreferenced properties: {sorted(props)}")  # Properties semantics
@@ -265,6 +268,8 @@ class Heightfield:
         # the differentiable parameter (put_parameter("heightfield", ..., Differentiable|Discontinuous))
         self.heightfield = h.to(self.device).contiguous().clone()
         self.parameters_changed(["heightfield"])
+        self.face_normals = True
+        self.set_face_normals(face_normals)
 
     # ---- lifetime ---------------------------------------------------------------------
     def __del__(self):
@@ -300,6 +305,26 @@ class Heightfield:
             tw = (C.c_float * 12)(*self.to_world.reshape(-1).tolist())
             check(_capi.lib().hf_set_transform(self._h, tw, None))
         self.mark_dirty()
+
+    def set_face_normals(self, face_normals):
+        """Flat (True) or smooth (False) shading.  Smooth: angle-weighted vertex normals, rebuilt with every
+        parameters_changed, interpolated into sh_frame.n and differentiated through (hf_set_face_normals)."""
+        check(_capi.lib().hf_set_face_normals(self._h, 1 if face_normals else 0, self._stream()))
+        self.face_normals = bool(face_normals)
+        self.mark_dirty()
+
+    def shading_derivatives(self, pi, active=True):
+        """dn_du, dn_dv ([3, n] each) of the hits of `pi`: the derivatives of the shading normal with respect to the
+        barycentrics (mesh.cpp:818-829, RayFlags.dNSdUV); zero for misses and with flat shading.  Not differentiable."""
+        n = pi.t.shape[0]
+        keep, _ = self._mask(active, n)
+        out = torch.empty((6, n), dtype=torch.float32, device=self.device)
+        _, pu = _f3(out[0:3])
+        _, pv = _f3(out[3:6])
+        pis = self._pi_struct(pi.t.detach().contiguous(), pi.prim_uv.detach().contiguous(), pi.prim_index.contiguous())
+        check(_capi.lib().hf_shading_derivatives(self._h, n, C.byref(pis), keep.data_ptr() if keep is not None else None,
+                                                 C.byref(pu), C.byref(pv), self._stream()))
+        return out[0:3], out[3:6]
 
     def parameters_grad_enabled(self):
         return bool(self.heightfield.requires_grad)
