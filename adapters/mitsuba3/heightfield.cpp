@@ -22,6 +22,8 @@
 //   compute_surface_interaction        include/mitsuba/render/shape.h:179-183 (analog src/render/mesh.cpp:672-903)
 //   reverse mode of the above          Dr.Jit AD over mesh.cpp:672-903 (prb_reparam.py:586-587) -> dr::CustomOp -> hf_adjoint
 //   forward mode of the above          dr.forward / render_forward over mesh.cpp:672-903 -> dr::CustomOp::forward -> hf_tangent
+//   surface_area / sample_position / pdf_position   src/render/mesh.cpp:401-432, 552-642 -> hf_set_area_sampling,
+//                                      hf_surface_area, hf_sample_position (+ dr::CustomOp -> _adjoint / _tangent)
 //   class / plugin registration        include/mitsuba/core/class.h:195-211, src/core/plugin.cpp:93-127
 #include <mitsuba/core/bitmap.h>
 #include <mitsuba/core/fwd.h>
@@ -181,6 +183,59 @@ struct HeightfieldSIOp
     const char *name() const override { return "HeightfieldSI"; }
 };
 
+// Row layout of one staged sample_position call (floats): samples, active (u8), the position sample, gradients
+enum : size_t {
+    SP_SAMPLE = 0, SP_ACTIVE = 2, SP_P = 3, SP_N = 6, SP_UV = 9, SP_PDF = 11, SP_PRIM = 12, SP_B = 13, SP_GRAD = 15,
+    SP_ROWS = 21
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// Differentiable position sample: primal = hf_sample_position, reverse mode = hf_sample_position_adjoint, forward
+// mode = hf_sample_position_tangent.  Input: the height tensor's array; output: p and n packed as 6 n floats.  The
+// sampled triangle and its barycentrics are detached (Mesh::build_pmf's table carries no derivative).
+// ---------------------------------------------------------------------------------------------------------
+template <typename Float, typename Spectrum>
+struct HeightfieldSampleOp : dr::CustomOp<Float, Float /* p, n: 6 n packed rows */, Float /* heights */> {
+    using Base = dr::CustomOp<Float, Float, Float>;
+    using Shape_ = Heightfield<Float, Spectrum>;
+    struct Call {
+        const Shape_ *shape = nullptr;
+        std::vector<float> sample, uv, pdf, b; // host rows (sample: 2 n; uv, b: 2 n, filled by eval)
+        std::vector<uint32_t> prim;
+        std::vector<uint8_t> active;
+        size_t n = 0;
+    };
+    static inline thread_local Call *pending = nullptr;
+    Call call;
+
+    Float eval(const Float &heights) override {
+        (void) heights;
+        if (!pending) Throw("heightfield: HeightfieldSampleOp evaluated outside sample_position");
+        call = std::move(*pending);
+        pending = nullptr;
+        return call.shape->sample_primal(call);
+    }
+    void backward() override {
+        Float g = Base::grad_out(); // [6 n]
+        dr::eval(g); dr::sync_thread();
+        std::vector<float> grad_rows(6 * call.n), grad_h((size_t) call.shape->width() * call.shape->height(), 0.f);
+        dr::store(grad_rows.data(), g);
+        call.shape->sample_adjoint(call, grad_rows.data(), grad_h.data());
+        if (Base::template grad_enabled_in<0>())
+            Base::template set_grad_in<0>(dr::load<Float>(grad_h.data(), grad_h.size()));
+    }
+    void forward() override {
+        const size_t texels = (size_t) call.shape->width() * call.shape->height();
+        std::vector<float> dh(texels, 0.f), rows(6 * call.n, 0.f);
+        Float g = Base::template grad_in<0>();
+        dr::eval(g); dr::sync_thread();
+        if (dr::width(g) == texels) dr::store(dh.data(), g);
+        call.shape->sample_tangent(call, dh.data(), rows.data());
+        Base::set_grad_out(dr::load<Float>(rows.data(), 6 * call.n));
+    }
+    const char *name() const override { return "HeightfieldSample"; }
+};
+
 template <typename Float, typename Spectrum>
 class Heightfield final : public Shape<Float, Spectrum> {
 public:
@@ -188,6 +243,7 @@ public:
     MI_IMPORT_TYPES()
     using FloatStorage = DynamicBuffer<Float>;
     using SIOp = HeightfieldSIOp<Float, Spectrum>;
+    using SampleOp = HeightfieldSampleOp<Float, Spectrum>;
 
     Heightfield(const Properties &props) : Base(props) {
         m_max_height   = props.get<ScalarFloat>("max_height", 1.f);
@@ -260,7 +316,54 @@ public:
         return ScalarBoundingBox3f(ScalarPoint3f(b[0], b[1], b[2]), ScalarPoint3f(b[3], b[4], b[5]));
     }
 
-    Float surface_area() const override { NotImplementedError("surface_area"); }
+    // ---- area sampling (Mesh::build_pmf / surface_area / sample_position / pdf_position, mesh.cpp:401-432, 552-642);
+    // sample_direction / pdf_direction are Shape's (shape.cpp:363-395) on top of these ----
+    // ensure_pmf_built: the table is enabled on first use and then follows every hf_set_heights* / hf_set_transform
+    void ensure_pmf_built() const {
+        std::lock_guard<std::mutex> guard(m_mutex);
+        if (m_area_enabled) return;
+        hf_check(hf_set_area_sampling(m_hf, 1, m_stage.stream()));
+        m_stage.sync();
+        m_area_enabled = true;
+    }
+
+    Float surface_area() const override {
+        ensure_pmf_built();
+        float area = 0.f;
+        hf_check(hf_surface_area(m_hf, &area, nullptr));
+        return Float(area);
+    }
+
+    Float pdf_position(const PositionSample3f & /* ps */, Mask active) const override {
+        ensure_pmf_built();
+        float area = 0.f, norm = 0.f;
+        hf_check(hf_surface_area(m_hf, &area, &norm));
+        return dr::select(active, Float(norm), Float(0.f));
+    }
+
+    PositionSample3f sample_position(Float time, const Point2f &sample, Mask active) const override {
+        ensure_pmf_built();
+        size_t n = dr::width(sample, active);
+        typename SampleOp::Call call;
+        call.shape = this; call.n = n;
+        std::vector<float> sx = to_host(sample.x(), n), sy = to_host(sample.y(), n);
+        call.sample = sx;
+        call.sample.insert(call.sample.end(), sy.begin(), sy.end());
+        call.active = to_host_mask(active, n);
+        SampleOp::pending = &call;
+        // the op moves `call` into itself; its uv / pdf rows are read back from the node's copy through m_last_sample
+        Float rows = dr::custom<SampleOp>(m_heights.array());
+        SampleOp::pending = nullptr;
+        auto row = [&](size_t k) { return dr::gather<Float>(rows, dr::arange<UInt32>((uint32_t) n) + (uint32_t) (k * n)); };
+        PositionSample3f ps = dr::zeros<PositionSample3f>(n);
+        ps.p     = Point3f(row(0), row(1), row(2));
+        ps.n     = Normal3f(row(3), row(4), row(5));
+        ps.uv    = Point2f(dr::load<Float>(m_last_sample.data(), n), dr::load<Float>(m_last_sample.data() + n, n));
+        ps.pdf   = dr::load<Float>(m_last_sample.data() + 2 * n, n);
+        ps.time  = time;
+        ps.delta = false;
+        return ps;
+    }
 
     void traverse(TraversalCallback *callback) override {
         Base::traverse(callback);
@@ -512,6 +615,77 @@ public:
         if (dh_dev) HfStaging::hip_check(hipFree(dh_dev));
     }
 
+    // ---- called by HeightfieldSampleOp ------------------------------------------------------------------------
+    Float sample_primal(typename SampleOp::Call &op) const {
+        size_t n = op.n;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *dev = m_stage.reserve(SP_ROWS, n);
+        m_stage.upload(dev + SP_SAMPLE * n, op.sample.data(), 2 * n);
+        HfStaging::hip_check(hipMemcpyAsync(dev + SP_ACTIVE * n, op.active.data(), n, hipMemcpyHostToDevice, m_stage.stream()));
+        const float *smp[2] = { dev + SP_SAMPLE * n, dev + (SP_SAMPLE + 1) * n };
+        hf_position_sample_t out = { { dev + SP_P * n, dev + (SP_P + 1) * n, dev + (SP_P + 2) * n },
+                                     { dev + SP_N * n, dev + (SP_N + 1) * n, dev + (SP_N + 2) * n },
+                                     { dev + SP_UV * n, dev + (SP_UV + 1) * n }, dev + SP_PDF * n,
+                                     (uint32_t *) (dev + SP_PRIM * n), { dev + SP_B * n, dev + (SP_B + 1) * n } };
+        hf_check(hf_sample_position(m_hf, n, smp, (const uint8_t *) (dev + SP_ACTIVE * n), &out, m_stage.stream()));
+        std::vector<float> host((SP_GRAD - SP_P) * n);
+        m_stage.download(host.data(), dev + SP_P * n, host.size());
+        m_stage.sync();
+        op.uv.assign(host.begin() + (SP_UV - SP_P) * n, host.begin() + (SP_PDF - SP_P) * n);
+        op.pdf.assign(host.begin() + (SP_PDF - SP_P) * n, host.begin() + (SP_PRIM - SP_P) * n);
+        op.prim.resize(n);
+        memcpy(op.prim.data(), host.data() + (SP_PRIM - SP_P) * n, n * sizeof(uint32_t));
+        op.b.assign(host.begin() + (SP_B - SP_P) * n, host.begin() + (SP_GRAD - SP_P) * n);
+        m_last_sample = op.uv;
+        m_last_sample.insert(m_last_sample.end(), op.pdf.begin(), op.pdf.end());
+        return dr::load<Float>(host.data(), 6 * n);
+    }
+
+    // the forward's triangle and barycentrics back into the staging block (the node is self-contained)
+    void upload_sample(float *dev, const typename SampleOp::Call &op) const {
+        size_t n = op.n;
+        m_stage.upload(dev + SP_PRIM * n, (const float *) op.prim.data(), n);
+        m_stage.upload(dev + SP_B * n, op.b.data(), 2 * n);
+        HfStaging::hip_check(hipMemcpyAsync(dev + SP_ACTIVE * n, op.active.data(), n, hipMemcpyHostToDevice, m_stage.stream()));
+    }
+
+    void sample_adjoint(const typename SampleOp::Call &op, const float *grad_rows /* host, 6 n */, float *grad_h) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *dev = m_stage.reserve(SP_ROWS, n);
+        upload_sample(dev, op);
+        float *g = dev + SP_GRAD * n;
+        m_stage.upload(g, grad_rows, 6 * n);
+        float *grad_dev = nullptr;
+        HfStaging::hip_check(hipMalloc((void **) &grad_dev, texels * sizeof(float)));
+        HfStaging::hip_check(hipMemsetAsync(grad_dev, 0, texels * sizeof(float), m_stage.stream()));
+        const float *b[2] = { dev + SP_B * n, dev + (SP_B + 1) * n };
+        const float *gp[3] = { g, g + n, g + 2 * n }, *gn[3] = { g + 3 * n, g + 4 * n, g + 5 * n };
+        hf_check(hf_sample_position_adjoint(m_hf, n, (const uint32_t *) (dev + SP_PRIM * n), b,
+                                            (const uint8_t *) (dev + SP_ACTIVE * n), gp, gn, grad_dev, m_stage.stream()));
+        m_stage.download(grad_h, grad_dev, texels);
+        m_stage.sync();
+        HfStaging::hip_check(hipFree(grad_dev));
+    }
+
+    void sample_tangent(const typename SampleOp::Call &op, const float *dheights /* host, H W */, float *rows /* host, 6 n */) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *dev = m_stage.reserve(SP_ROWS, n);
+        upload_sample(dev, op);
+        float *dh_dev = nullptr;
+        HfStaging::hip_check(hipMalloc((void **) &dh_dev, texels * sizeof(float)));
+        m_stage.upload(dh_dev, dheights, texels);
+        float *t = dev + SP_GRAD * n;
+        const float *b[2] = { dev + SP_B * n, dev + (SP_B + 1) * n };
+        float *dp[3] = { t, t + n, t + 2 * n }, *dn[3] = { t + 3 * n, t + 4 * n, t + 5 * n };
+        hf_check(hf_sample_position_tangent(m_hf, n, (const uint32_t *) (dev + SP_PRIM * n), b,
+                                            (const uint8_t *) (dev + SP_ACTIVE * n), dh_dev, dp, dn, m_stage.stream()));
+        m_stage.download(rows, t, 6 * n);
+        m_stage.sync();
+        HfStaging::hip_check(hipFree(dh_dev));
+    }
+
     std::string to_string() const override {
         std::ostringstream oss;
         oss << "Heightfield[" << std::endl
@@ -649,6 +823,8 @@ private:
     mutable HfStaging m_stage;
     mutable std::vector<float> m_last_boundary_test; // detached (interaction.h:497-498), of the last primal call
     mutable std::vector<float> m_last_dn;            // dn_du, dn_dv rows of the last primal call with RayFlags::dNSdUV
+    mutable std::vector<float> m_last_sample;        // uv (2 n) and pdf (n) rows of the last sample_position
+    mutable bool m_area_enabled = false;             // hf_set_area_sampling (ensure_pmf_built)
 };
 
 MI_IMPLEMENT_CLASS_VARIANT(Heightfield, Shape)

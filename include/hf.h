@@ -42,8 +42,9 @@
  *     The forward-mode entry points (hf_tangent, hf_direct_lighting_weighted_tangent, hf_point_lighting_tangent) are
  *     capturable as well: they reserve no scratch block, allocate nothing and never synchronise the host.
  *     Not capturable: hf_create / hf_destroy, hf_set_heights_host, hf_bbox, hf_get_mip and the host-pointer packet
- *     entry (they synchronise); hf_set_face_normals (refused with HF_EINVAL) and, with smooth shading, hf_set_transform
- *     (it synchronises).
+ *     entry (they synchronise); hf_set_face_normals and hf_set_area_sampling (refused with HF_EINVAL), hf_surface_area
+ *     and, with smooth shading or area sampling, hf_set_transform (they synchronise).  hf_sample_position and its
+ *     adjoint / tangent are capturable like the other wavefront entry points (no scratch block).
  */
 #ifndef HF_H
 #define HF_H
@@ -361,6 +362,71 @@ int hf_tangent(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_p
  * Zero for misses, inactive lanes and with flat shading.  Forward only. */
 int hf_shading_derivatives(const hf_field_t *hf, size_t n, const hf_pi_const_t *pi, const uint8_t *active,
                            float *const dn_du[3], float *const dn_dv[3], hf_stream_t stream);
+
+/* ---- area sampling: the sampling side of Shape (surface_area, sample_position, pdf_position) ------------------ */
+
+/* PositionSample3f (include/mitsuba/render/records.h) as Mesh::sample_position fills it (src/render/mesh.cpp:557-610):
+ * p, n, uv and pdf are required; time stays on the caller's side and delta is always false.  prim_index (the sampled
+ * triangle, prim_index order) and b (the barycentrics b1, b2 of square_to_uniform_triangle, include/mitsuba/core/
+ * warp.h:153-156) may be NULL (not wanted); hf_sample_position_adjoint / _tangent take them back. */
+typedef struct hf_position_sample {
+    float    *p[3];
+    float    *n[3];
+    float    *uv[2];
+    float    *pdf;
+    uint32_t *prim_index;
+    float    *b[2];
+} hf_position_sample_t;
+
+/* Replaces: Mesh::build_pmf / ensure_pmf_built (src/render/mesh.cpp:401-432) and the DiscreteDistribution it builds
+ * (include/mitsuba/core/distr_1d.h:20-240), for the heightfield's triangles in prim_index order.  enable != 0 allocates
+ * the handle's area table (4 bytes per triangle + 1/16 of that for the search) and builds it on `stream` after the last
+ * hf_set_heights*; later queries on other streams must be ordered after `stream` by the caller, as for hf_set_heights.
+ * From then on the table is rebuilt wherever it can go stale: by every hf_set_heights* on its stream (graph-capturable,
+ * like the vertex normals) and by hf_set_transform (synchronous).  The areas do not depend on the shading mode, so
+ * hf_set_face_normals does not rebuild it (hf_sample_position reads the vertex normals of the mode current at launch).
+ * enable = 0 frees the table.  A handle that never enables sampling allocates nothing and runs no extra kernel.
+ * Entry i of the table is the world-space area .5f * norm(cross(p1 - p0, p2 - p0)) of triangle i in fp32; its CDF is
+ * a running fp64 sum, each prefix rounded to fp32, summed in one fixed association order (bitwise the same from build
+ * to build; not the sequential loop's order, so a prefix may differ from compute_cdf's by an fp32 ulp).  The table is
+ * DETACHED: no derivative flows through the pdf or the choice of triangle (as build_pmf).  Not capturable: HF_EINVAL
+ * while `stream` is being captured.  HF_ENOMEM when the table cannot be allocated. */
+int hf_set_area_sampling(hf_field_t *hf, int enable, hf_stream_t stream);
+/* Replaces: Mesh::surface_area (mesh.cpp:552-555) = m_area_pmf.sum(), and pdf_position (mesh.cpp:637-640) =
+ * m_area_pmf.normalization() = (float) (1.0 / sum).  Synchronous: waits for the last rebuild.  normalization may be
+ * NULL.  HF_EINVAL without the table (hf_set_area_sampling). */
+int hf_surface_area(hf_field_t *hf, float *area, float *normalization);
+/* Read-only view of the table for tests and tools: the device pointer to the fp32 CDF (one entry per triangle; the
+ * storage is padded with +inf up to a multiple of 64 entries) and its entry count; NULL / 0 without the table.  Reads
+ * of it are ordered after the last rebuild by the caller. */
+int hf_area_cdf(const hf_field_t *hf, const float **cdf, size_t *count);
+
+/* Replaces: Mesh::sample_position(time, sample, active) (src/render/mesh.cpp:557-610) for n samples (sample: 2 device
+ * arrays of n floats in [0, 1)).  Step by step: the triangle index is DiscreteDistribution::sample_reuse(sample.y)
+ * (distr_1d.h:120-130, 167-176): the first i in [valid.x, valid.y] with !(cdf[i] < sample.y * sum), valid.y when there
+ * is none (dr::binary_search), and sample.y is reused as (sample.y - cdf[i-1] norm) / (pmf[i] norm); then
+ * b = square_to_uniform_triangle, p = fmadd(e0, b.x, fmadd(e1, b.y, p0)), uv the same fmadd chain over the texcoords,
+ * n = normalize(cross(e0, e1)) -- with smooth shading (hf_set_face_normals(hf, 0)) the normalised barycentric blend of
+ * the three vertex normals -- negated by flip_normals, pdf = norm.  Inactive lanes (active: NULL = all) are zeros in
+ * every row.  Capturable (reads the table and its scalars from device memory, so a replay sees later rebuilds).
+ * HF_EINVAL without the table. */
+int hf_sample_position(const hf_field_t *hf, size_t n, const float *const sample[2], const uint8_t *active,
+                       const hf_position_sample_t *out, hf_stream_t stream);
+/* Reverse mode of hf_sample_position with respect to the heights: p and n stay attached to the heights through the
+ * triangle's vertices (vertex_position / vertex_normal in the reference), the index and b do not.  For the samples
+ * (prim_index, b) of a forward call, accumulates dL/dheight into grad_heights (width*height floats, float atomics) from
+ * the upstream gradients grad_p / grad_n (3 device arrays of n floats each; either may be NULL = zero).  Flat shading: 3
+ * heights per sample through p and the face normal; smooth shading: n also reaches the 1-rings of the three vertices
+ * (up to 12 heights) through the vertex-normal VJP.  Capturable; does not need the table. */
+int hf_sample_position_adjoint(const hf_field_t *hf, size_t n, const uint32_t *prim_index, const float *const b[2],
+                               const uint8_t *active, const float *const grad_p[3], const float *const grad_n[3],
+                               float *grad_heights, hf_stream_t stream);
+/* Forward mode of the same: for the height tangent dheights (width*height floats, NULL = zero), the tangents dp / dn (3
+ * device arrays of n floats each, overwritten; either may be NULL = not written) of the samples (prim_index, b).
+ * Inactive lanes get zeros.  No atomics: bitwise the same from launch to launch.  Capturable; does not need the table. */
+int hf_sample_position_tangent(const hf_field_t *hf, size_t n, const uint32_t *prim_index, const float *const b[2],
+                               const uint8_t *active, const float *dheights, float *const dp[3], float *const dn[3],
+                               hf_stream_t stream);
 
 /* ---- next row: minimal direct lighting on the wavefront ------- */
 

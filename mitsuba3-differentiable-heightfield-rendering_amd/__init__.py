@@ -2,5 +2,6 @@
 reference's Shape plugin interface over the C ABI of libhf.so (include/hf.h)."""
 from . import build, workload  # noqa: F401
 from ._capi import HfError  # noqa: F401
-from .shape import (Adam, Frame3f, Heightfield, ParamFlags, PreliminaryIntersection3f, Ray3f, RayFlags,  # noqa: F401
-                    SurfaceInteraction3f, allreduce_gradient, direct_lighting, film_gaussian, point_lighting, reparameterize_ray)
+from .shape import (Adam, DirectionSample3f, Frame3f, Heightfield, ParamFlags, PositionSample3f,  # noqa: F401
+                    PreliminaryIntersection3f, Ray3f, RayFlags, SurfaceInteraction3f, allreduce_gradient,
+                    direct_lighting, film_gaussian, point_lighting, reparameterize_ray)

@@ -40,6 +40,10 @@ class hf_si_tangent_t(C.Structure):
                 ("dp_du", _fp * 3), ("dp_dv", _fp * 3)]
 
 
+class hf_position_sample_t(C.Structure):
+    _fields_ = [("p", _fp * 3), ("n", _fp * 3), ("uv", _fp * 2), ("pdf", _fp), ("prim_index", _fp), ("b", _fp * 2)]
+
+
 # every symbol include/hf.h declares: name -> (restype, argtypes)
 HF_MAX_LIGHTS = 8
 
@@ -66,6 +70,15 @@ SYMBOLS = {
     "hf_get_face_normals": (C.c_int, [C.c_void_p]),
     "hf_shading_derivatives": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(hf_pi_t), _fp, C.POINTER(_fp * 3),
                                          C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_set_area_sampling": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hf_surface_area": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "hf_area_cdf": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "hf_sample_position": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_fp * 2), _fp, C.POINTER(hf_position_sample_t),
+                                     C.c_void_p]),
+    "hf_sample_position_adjoint": (C.c_int, [C.c_void_p, C.c_size_t, _fp, C.POINTER(_fp * 2), _fp, C.POINTER(_fp * 3),
+                                             C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    "hf_sample_position_tangent": (C.c_int, [C.c_void_p, C.c_size_t, _fp, C.POINTER(_fp * 2), _fp, _fp, C.POINTER(_fp * 3),
+                                             C.POINTER(_fp * 3), C.c_void_p]),
     "hf_bbox": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "hf_heights_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "hf_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

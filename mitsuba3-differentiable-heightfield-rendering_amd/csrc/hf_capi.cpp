@@ -38,6 +38,8 @@ struct hf_field {
     int coherence;      // hf_set_ray_coherence: HF_COHERENCE_AUTO / _INCOHERENT (which instantiation the trace launches take)
     float4 *d_vn;       // smooth shading (hf_set_face_normals(hf, 0)): one vertex normal per texel, rebuilt with the
                         // heights and the transform; NULL = flat shading (the default), and the flat kernels run
+    hf_area_table area; // area sampling (hf_set_area_sampling): the triangle-area CDF, rebuilt with the heights and the
+                        // transform; area.cdf NULL = disabled (the default), and nothing of it is allocated or run
 };
 
 static bool stream_capturing(hipStream_t s) {
@@ -176,6 +178,13 @@ static int set_transform(hf_field *hf, const float *to_world, const float *to_ob
     return hf_invert_affine(to_world, hf->dev.to_object);
 }
 
+static void free_area(hf_area_table &t) {
+    void *bufs[5] = { t.cdf, t.coarse, t.tile, t.tile_valid, t.info };
+    for (void *b : bufs)
+        if (b) (void) hipFree(b);
+    t = hf_area_table{};
+}
+
 // frees whatever a (possibly half-constructed) handle owns
 static void release(hf_field *hf) {
     if (hf->built) (void) hipEventDestroy(hf->built);
@@ -188,6 +197,7 @@ static void release(hf_field *hf) {
     if (hf->d_shear) (void) hipFree(hf->d_shear);
     if (hf->d_misc) (void) hipFree(hf->d_misc);
     if (hf->d_vn) (void) hipFree(hf->d_vn);
+    free_area(hf->area);
     delete hf->slot_mutex;
     free(hf);
 }
@@ -294,6 +304,7 @@ extern "C" int hf_set_heights(hf_field_t *hf, const float *d_heights, hf_stream_
         HF_HIP(hipMemcpyAsync(hf->d_heights, d_heights, bytes, hipMemcpyDeviceToDevice, st));
     hf_launch_build_mips(hf->dev, hf->d_mip, hf->d_shear, st);
     if (hf->d_vn) hf_launch_build_normals(hf->dev, hf->d_vn, st);
+    if (hf->area.cdf) hf_launch_build_area(hf->dev, hf->area, st);
     HF_HIP(hipGetLastError());
     if (!stream_capturing(st)) HF_HIP(hipEventRecord(hf->built, st)); // (a captured rebuild is ordered by its graph)
     return HF_OK;
@@ -355,15 +366,16 @@ extern "C" int hf_set_heights_host(hf_field_t *hf, const float *h_heights, hf_st
 extern "C" int hf_set_transform(hf_field_t *hf, const float to_world[12], const float *to_object_or_null) {
     if (!hf || !to_world) return fail(HF_EINVAL, "hf_set_transform: NULL argument");
     int rc = set_transform(hf, to_world, to_object_or_null);
-    if (rc != HF_OK || !hf->d_vn) return rc;
-    // Smooth shading: the vertex normals are world-space (angles are not affine-invariant) and are rebuilt here.  The
-    // call takes no stream, so the rebuild is made synchronous: on the null stream after the last height update
+    if (rc != HF_OK || (!hf->d_vn && !hf->area.cdf)) return rc;
+    // Smooth shading: the vertex normals are world-space (angles are not affine-invariant) and are rebuilt here; so is
+    // the area table (world-space areas).  The call takes no stream, so the rebuild is made synchronous: on the null stream after the last height update
     // (`built`, whatever stream that was on), and waited for before returning -- a query or a height update the caller
     // issues afterwards, on any stream, cannot overlap it.
     hf_device_guard guard(hf->device);
     if (!guard.ok) return fail(HF_EDEVICE, "hf_set_transform: cannot select device %d", hf->device);
     HF_HIP(hipStreamWaitEvent(nullptr, hf->built, 0));
-    hf_launch_build_normals(hf->dev, hf->d_vn, nullptr);
+    if (hf->d_vn) hf_launch_build_normals(hf->dev, hf->d_vn, nullptr);
+    if (hf->area.cdf) hf_launch_build_area(hf->dev, hf->area, nullptr);
     HF_HIP(hipGetLastError());
     HF_HIP(hipEventRecord(hf->built, nullptr));
     HF_HIP(hipEventSynchronize(hf->built));
@@ -410,6 +422,122 @@ extern "C" int hf_set_face_normals(hf_field_t *hf, int face_normals, hf_stream_t
 }
 
 extern "C" int hf_get_face_normals(const hf_field_t *hf) { return hf ? (hf->d_vn ? 0 : 1) : 1; }
+
+static int check_device(const char *fn, const hf_field_t *hf);
+
+extern "C" int hf_set_area_sampling(hf_field_t *hf, int enable, hf_stream_t stream) {
+    if (!hf) return fail(HF_EINVAL, "hf_set_area_sampling: NULL handle");
+    hf_device_guard guard(hf->device);
+    if (!guard.ok) return fail(HF_EDEVICE, "hf_set_area_sampling: cannot select device %d", hf->device);
+    hipStream_t st = (hipStream_t) stream;
+    // Not capturable, for the reasons of hf_set_face_normals: a captured enable would publish a table no build has
+    // written before the first replay, a captured disable would free buffers the graph's kernels still reference.
+    if (stream_capturing(st))
+        return fail(HF_EINVAL, "hf_set_area_sampling: not capturable (the stream is being captured into a HIP graph)");
+    if (!enable) { // hipFree waits for the work that may still read the table
+        free_area(hf->area);
+        return HF_OK;
+    }
+    if (hf->area.cdf) return HF_OK;
+    const uint32_t cw = (uint32_t) hf->dev.W - 1u, ch = (uint32_t) hf->dev.H - 1u;
+    hf_area_table t = {};
+    t.m = 2u * cw * ch;
+    t.nseg = (t.m + HF_AREA_SEG - 1u) / HF_AREA_SEG;
+    t.ncx = (cw + HF_AREA_CHUNK - 1u) / HF_AREA_CHUNK;
+    t.ntiles = t.ncx * ch;
+    const size_t n_cdf = (size_t) t.nseg * HF_AREA_SEG;
+    hipError_t e = hipMalloc((void **) &t.cdf, sizeof(float) * n_cdf);
+    if (e == hipSuccess) e = hipMalloc((void **) &t.coarse, sizeof(float) * t.nseg);
+    if (e == hipSuccess) e = hipMalloc((void **) &t.tile, sizeof(double) * 3 * (size_t) t.ntiles);
+    if (e == hipSuccess) e = hipMalloc((void **) &t.tile_valid, sizeof(uint32_t) * 2 * (size_t) t.ntiles);
+    if (e == hipSuccess) e = hipMalloc((void **) &t.info, sizeof(hf_area_info));
+    // the padding past the last entry is +inf: the segment count of hf_sample_position never counts it
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t) t.cdf, 0x7f800000, n_cdf, st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, hf->built, 0); // the heights of the last hf_set_heights*
+    if (e == hipSuccess) {
+        hf_launch_build_area(hf->dev, t, st);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        (void) hipStreamSynchronize(st);
+        free_area(t);
+        return fail(e == hipErrorOutOfMemory ? HF_ENOMEM : HF_EDEVICE, "hf_set_area_sampling: cannot build the area table "
+                    "(%u triangles): %s", t.m, hipGetErrorString(e));
+    }
+    hf->area = t;
+    HF_HIP(hipEventRecord(hf->built, st));
+    return HF_OK;
+}
+
+extern "C" int hf_surface_area(hf_field_t *hf, float *area, float *normalization) {
+    if (!hf || !area) return fail(HF_EINVAL, "hf_surface_area: NULL argument");
+    if (!hf->area.cdf) return fail(HF_EINVAL, "hf_surface_area: area sampling is not enabled (hf_set_area_sampling)");
+    hf_device_guard guard(hf->device);
+    if (!guard.ok) return fail(HF_EDEVICE, "hf_surface_area: cannot select device %d", hf->device);
+    hf_area_info info;
+    HF_HIP(hipEventSynchronize(hf->built));
+    HF_HIP(hipMemcpy(&info, hf->area.info, sizeof(info), hipMemcpyDeviceToHost));
+    *area = info.sum_f;
+    if (normalization) *normalization = info.norm;
+    return HF_OK;
+}
+
+extern "C" int hf_area_cdf(const hf_field_t *hf, const float **cdf, size_t *count) {
+    if (!hf || !cdf || !count) return fail(HF_EINVAL, "hf_area_cdf: NULL argument");
+    *cdf = hf->area.cdf;
+    *count = hf->area.cdf ? hf->area.m : 0;
+    return HF_OK;
+}
+
+extern "C" int hf_sample_position(const hf_field_t *hf, size_t n, const float *const sample[2], const uint8_t *active,
+                                  const hf_position_sample_t *out, hf_stream_t stream) {
+    if (!hf) return fail(HF_EINVAL, "hf_sample_position: NULL handle");
+    if (!hf->area.cdf) return fail(HF_EINVAL, "hf_sample_position: area sampling is not enabled (hf_set_area_sampling)");
+    if (!sample || !out) return fail(HF_EINVAL, "hf_sample_position: NULL argument");
+    if (n == 0) return HF_OK;
+    if (!sample[0] || !sample[1]) return fail(HF_EINVAL, "hf_sample_position: NULL sample array");
+    if (!all3(out->p) || !all3(out->n) || !out->uv[0] || !out->uv[1] || !out->pdf)
+        return fail(HF_EINVAL, "hf_sample_position: NULL output row (p, n, uv and pdf are required)");
+    int rc;
+    if ((rc = check_device("hf_sample_position", hf))) return rc;
+    hf_launch_sample_position(hf->dev, hf->area, n, sample, active, *out, hf->d_vn, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+// the arguments both derivatives of hf_sample_position share
+static int check_sample_diff(const char *fn, const hf_field_t *hf, size_t n, const uint32_t *prim, const float *const b[2]) {
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    if (n == 0) return HF_OK;
+    if (!prim || !b || !b[0] || !b[1]) return fail(HF_EINVAL, "%s: NULL prim_index / b", fn);
+    return check_device(fn, hf);
+}
+
+extern "C" int hf_sample_position_adjoint(const hf_field_t *hf, size_t n, const uint32_t *prim_index, const float *const b[2],
+                                          const uint8_t *active, const float *const grad_p[3], const float *const grad_n[3],
+                                          float *grad_heights, hf_stream_t stream) {
+    int rc = check_sample_diff("hf_sample_position_adjoint", hf, n, prim_index, b);
+    if (rc || n == 0) return rc;
+    if (!grad_heights) return fail(HF_EINVAL, "hf_sample_position_adjoint: NULL grad_heights");
+    if ((grad_p && !all3(grad_p)) || (grad_n && !all3(grad_n)))
+        return fail(HF_EINVAL, "hf_sample_position_adjoint: NULL grad_p / grad_n array");
+    hf_launch_sample_position_adjoint(hf->dev, n, prim_index, b, active, grad_p, grad_n, grad_heights, hf->d_vn,
+                                      (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_sample_position_tangent(const hf_field_t *hf, size_t n, const uint32_t *prim_index, const float *const b[2],
+                                          const uint8_t *active, const float *dheights, float *const dp[3], float *const dn[3],
+                                          hf_stream_t stream) {
+    int rc = check_sample_diff("hf_sample_position_tangent", hf, n, prim_index, b);
+    if (rc || n == 0) return rc;
+    if ((dp && !all3(dp)) || (dn && !all3(dn))) return fail(HF_EINVAL, "hf_sample_position_tangent: NULL dp / dn array");
+    hf_launch_sample_position_tangent(hf->dev, n, prim_index, b, active, dheights, dp, dn, hf->d_vn, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
 
 
 extern "C" int hf_heights_device(hf_field_t *hf, const float **out) {

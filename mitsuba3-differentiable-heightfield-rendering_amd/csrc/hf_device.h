@@ -600,3 +600,22 @@ __device__ __forceinline__ void compute_si(const hf_dev_field &f, v3 o, v3 d, fl
     hf_si_rec_sink sink = { si };
     compute_si_to(f, o, d, t_in, b1, b2, prim, flags, sink);
 }
+
+// ---- Area sampling (hf_set_area_sampling): the discrete distribution of Mesh::build_pmf (mesh.cpp:401-432) over the
+// triangles in prim_index order, and what Mesh::sample_position (mesh.cpp:557-610) reads of it. ----
+
+// world-space area of the triangle (p0, p1, p2): .5f * norm(cross(p1 - p0, p2 - p0)), norm = sqrt(dot(v, v))
+__device__ __forceinline__ float tri_area(v3 p0, v3 p1, v3 p2) {
+    const v3 c = cross3(p1 - p0, p2 - p0);
+    return 0.5f * __builtin_sqrtf(dot3(c, c));
+}
+
+// The scalars of DiscreteDistribution::compute_cdf (distr_1d.h:212-240), written by the table build on the device so
+// that the sampling kernels (captured ones included) read those of the last rebuild.
+struct hf_area_info {
+    double sum;        // the fp64 total
+    float sum_f;       // m_sum = (float) sum
+    float norm;        // m_normalization = (float) (1.0 / sum)
+    uint32_t valid_lo; // m_valid: first and last entry with a non-zero area
+    uint32_t valid_hi;
+};

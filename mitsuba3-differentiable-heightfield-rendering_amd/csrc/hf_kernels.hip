@@ -12,6 +12,8 @@
 //   hf_tangent_kernel / hf_tangent_smooth_kernel   forward mode of a4
 //   hf_vertex_normals_kernel, hf_shading_derivatives_kernel   smooth shading: the vertex normals, dn_du / dn_dv
 //   hf_direct_kernel / hf_direct_adjoint_kernel, hf_adam_kernel     next rows
+//   hf_area_reduce / _scan_tiles / _cdf_kernel     area sampling: the triangle-area CDF (hf_set_area_sampling)
+//   hf_sample_position / _adjoint / _tangent_kernel  Mesh::sample_position and its two derivatives
 //
 // Traversal = a walk of the implicit quadtree over the cells (the grid is mirrored so the ray direction is
 // non-negative on both axes: "order space").  One visit of an inner node fetches its record -- a plane through
@@ -3049,4 +3051,408 @@ void hf_launch_reparam_aux(const hf_reparam_args &a, hipStream_t stream) {
 void hf_launch_reparam_weights(const hf_reparam_args &a, hipStream_t stream) {
     if (a.n == 0) return;
     hipLaunchKernelGGL(hf_reparam_weight_kernel, dim3((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), dim3(HF_BLOCK), 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
+// Area sampling (hf_set_area_sampling, hf_sample_position): the area distribution of Mesh::build_pmf over the triangles
+// in prim_index order (mesh.cpp:401-432, distr_1d.h:212-240) and Mesh::sample_position (mesh.cpp:557-610).
+//
+// Table build: reduce -> scan of the tile totals -> scan of the tiles, three launches and no inter-workgroup waits.  A
+// tile is one cell row, or a HF_AREA_CHUNK-cell piece of one; both passes over the tiles compute the areas from the
+// heights (coalesced loads, cell c0 + lane + 256 k) into LDS, and every thread then owns 16 consecutive entries.  The
+// fp64 sums follow ONE fixed association, nested four deep:
+//     cdf[i] = (float) (G + (l + (c + r)))
+// r: the running sum over the thread's entries up to i; c: the running sum of the thread totals before it in the tile;
+// l: the running sum of the tile totals before it in its group (the tiles of one thread of the tile-total scan); G: the
+// running sum of the group totals before it.  Each level is a sequential chain whose last partial sum is the total the
+// next level adds, so the fp64 prefixes are non-decreasing across every boundary, the fp32 CDF is sorted, and its last
+// entry is the total bit for bit.  Bitwise the same from build to build.
+// ---------------------------------------------------------------------------------
+#define HF_AREA_PER (2 * HF_AREA_CHUNK / HF_BLOCK) // entries per thread of a tile
+struct hf_area_args {
+    hf_dev_field f;
+    hf_area_table t;
+};
+
+// the tile's areas into s_area[0 .. 2 HF_AREA_CHUNK) (zeros past the end of the row); returns the number of cells
+__device__ __forceinline__ int area_tile_load(const hf_dev_field &f, uint32_t ncx, float *s_area, int &cy, int &c0) {
+    const uint32_t tile = blockIdx.x;
+    cy = (int) (tile / ncx);
+    c0 = (int) (tile - (uint32_t) cy * ncx) * HF_AREA_CHUNK;
+    const int ncell = min(HF_AREA_CHUNK, f.W - 1 - c0);
+    for (int c = (int) threadIdx.x; c < HF_AREA_CHUNK; c += HF_BLOCK) {
+        float a0 = 0.f, a1 = 0.f;
+        if (c < ncell) {
+            const int cx = c0 + c;
+            const size_t r0 = (size_t) cy * f.W + cx, r1 = r0 + f.W;
+            const float h00 = f.h[r0], h10 = f.h[r0 + 1], h01 = f.h[r1], h11 = f.h[r1 + 1];
+            const v3 v00 = grid_world(f, cy, cx, h00), v10 = grid_world(f, cy, cx + 1, h10);
+            const v3 v01 = grid_world(f, cy + 1, cx, h01), v11 = grid_world(f, cy + 1, cx + 1, h11);
+            a0 = tri_area(v00, v10, v01); // tri 0 = (v00, v10, v01)
+            a1 = tri_area(v11, v01, v10); // tri 1 = (v11, v01, v10)
+        }
+        reinterpret_cast<float2 *>(s_area)[c] = make_float2(a0, a1);
+    }
+    return ncell;
+}
+// thread t's entries s_area[16 t .. 16 t + 16): their running fp64 sum
+__device__ __forceinline__ double area_thread_sum(const float *s_area) {
+    double r = 0.0;
+#pragma unroll
+    for (int j = 0; j < HF_AREA_PER; ++j) r += (double) s_area[threadIdx.x * HF_AREA_PER + j];
+    return r;
+}
+// s[u] <- the running sum of s[0 .. u) (one thread, sequential); returns the total
+__device__ __forceinline__ double area_chain(double *s, int count) {
+    double acc = 0.0;
+    for (int u = 0; u < count; ++u) {
+        const double v = s[u];
+        s[u] = acc;
+        acc += v;
+    }
+    return acc;
+}
+
+// pass 1: per tile, the total and the first / last + 1 entry with a non-zero area
+__global__ __launch_bounds__(HF_BLOCK) void hf_area_reduce_kernel(hf_area_args a) {
+    __shared__ float s_area[2 * HF_AREA_CHUNK];
+    __shared__ double s_sum[HF_BLOCK];
+    __shared__ uint32_t s_valid[2];
+    if (threadIdx.x == 0) { s_valid[0] = 0xFFFFFFFFu; s_valid[1] = 0u; }
+    int cy, c0;
+    area_tile_load(a.f, a.t.ncx, s_area, cy, c0);
+    __syncthreads();
+    const uint32_t base = 2u * ((uint32_t) cy * (uint32_t) (a.f.W - 1) + (uint32_t) c0) + threadIdx.x * HF_AREA_PER;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+#pragma unroll
+    for (int j = 0; j < HF_AREA_PER; ++j)
+        if (s_area[threadIdx.x * HF_AREA_PER + j] > 0.f) { lo = min(lo, base + j); hi = base + j + 1u; }
+    s_sum[threadIdx.x] = area_thread_sum(s_area);
+    if (hi != 0u) { atomicMin(&s_valid[0], lo); atomicMax(&s_valid[1], hi); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a.t.tile[blockIdx.x] = area_chain(s_sum, HF_BLOCK);
+        a.t.tile_valid[2 * blockIdx.x] = s_valid[0];
+        a.t.tile_valid[2 * blockIdx.x + 1] = s_valid[1];
+    }
+}
+
+// pass 2 (one workgroup): per tile its group base G and its offset l in the group; the distribution's scalars
+__global__ __launch_bounds__(HF_BLOCK) void hf_area_scan_tiles_kernel(hf_area_args a) {
+    __shared__ double s_sum[HF_BLOCK];
+    __shared__ uint32_t s_valid[2];
+    if (threadIdx.x == 0) { s_valid[0] = 0xFFFFFFFFu; s_valid[1] = 0u; }
+    __syncthreads();
+    const uint32_t nt = a.t.ntiles, per = (nt + HF_BLOCK - 1) / HF_BLOCK;
+    const uint32_t k0 = min(threadIdx.x * per, nt), k1 = min(k0 + per, nt);
+    double *off = a.t.tile + nt; // (G, l) pairs
+    double l = 0.0;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (uint32_t k = k0; k < k1; ++k) {
+        off[2 * k + 1] = l;
+        l += a.t.tile[k];
+        lo = min(lo, a.t.tile_valid[2 * k]);
+        hi = max(hi, a.t.tile_valid[2 * k + 1]);
+    }
+    s_sum[threadIdx.x] = l;
+    if (hi != 0u) { atomicMin(&s_valid[0], lo); atomicMax(&s_valid[1], hi); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double sum = area_chain(s_sum, HF_BLOCK);
+        hf_area_info *info = a.t.info;
+        info->sum = sum;
+        info->sum_f = (float) sum;
+        info->norm = (float) (1.0 / sum);
+        const bool any = s_valid[1] != 0u; // (none: the reference throws; index 0 keeps every read in bounds)
+        info->valid_lo = any ? s_valid[0] : 0u;
+        info->valid_hi = any ? s_valid[1] - 1u : 0u;
+    }
+    __syncthreads();
+    const double G = s_sum[threadIdx.x];
+    for (uint32_t k = k0; k < k1; ++k) off[2 * k] = G;
+}
+
+// pass 3: the CDF of every tile and the coarse table (every 64th entry), stored coalesced through LDS
+__global__ __launch_bounds__(HF_BLOCK) void hf_area_cdf_kernel(hf_area_args a) {
+    __shared__ float s_area[2 * HF_AREA_CHUNK];
+    __shared__ double s_sum[HF_BLOCK];
+    int cy, c0;
+    const int ncell = area_tile_load(a.f, a.t.ncx, s_area, cy, c0);
+    __syncthreads();
+    s_sum[threadIdx.x] = area_thread_sum(s_area);
+    __syncthreads();
+    if (threadIdx.x == 0) area_chain(s_sum, HF_BLOCK);
+    __syncthreads();
+    const double *off = a.t.tile + a.t.ntiles;
+    const double G = off[2 * blockIdx.x], l = off[2 * blockIdx.x + 1], c = s_sum[threadIdx.x];
+    double r = 0.0;
+#pragma unroll
+    for (int j = 0; j < HF_AREA_PER; ++j) { // (each thread rewrites only its own entries)
+        float *e = s_area + threadIdx.x * HF_AREA_PER + j;
+        r += (double) *e;
+        *e = (float) (G + (l + (c + r)));
+    }
+    __syncthreads();
+    const uint32_t base = 2u * ((uint32_t) cy * (uint32_t) (a.f.W - 1) + (uint32_t) c0), cnt = 2u * (uint32_t) ncell;
+    for (uint32_t e = threadIdx.x; e < cnt; e += HF_BLOCK) {
+        const float v = s_area[e];
+        const uint32_t gi = base + e;
+        a.t.cdf[gi] = v;
+        if ((gi & (HF_AREA_SEG - 1u)) == HF_AREA_SEG - 1u || gi == a.t.m - 1u) a.t.coarse[gi / HF_AREA_SEG] = v;
+    }
+}
+
+void hf_launch_build_area(const hf_dev_field &f, const hf_area_table &t, hipStream_t stream) {
+    hf_area_args a;
+    a.f = f; a.t = t;
+    hipLaunchKernelGGL(hf_area_reduce_kernel, dim3(t.ntiles), dim3(HF_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(hf_area_scan_tiles_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, a);
+    hipLaunchKernelGGL(hf_area_cdf_kernel, dim3(t.ntiles), dim3(HF_BLOCK), 0, stream, a);
+}
+
+// Mesh::sample_position for one lane per sample.  The triangle: a binary search over the coarse table (every 64th entry,
+// 2 MB at 4096^2: L2-resident) for the first segment whose last entry is not below sample.y * sum, then the 64 entries
+// of that segment (256 bytes, 16 independent loads) counted against the target: the CDF is sorted, so the count is the
+// first entry that is not below the target -- dr::binary_search's answer once clamped to [valid.x, valid.y].
+struct hf_sample_args {
+    hf_dev_field f;
+    hf_area_table t;
+    size_t n;
+    const float *s[2];
+    const uint8_t *active;
+    hf_position_sample_t out;
+    const float4 *vn; // smooth shading: the handle's vertex normals
+};
+template <bool SMOOTH>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sample_position_kernel(hf_sample_args a) {
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
+        const bool act = a.active ? a.active[i] != 0 : true;
+        v3 p = mk3(0.f, 0.f, 0.f), nn = p;
+        float uv0 = 0.f, uv1 = 0.f, pdf = 0.f, bx = 0.f, by = 0.f;
+        uint32_t idx = 0u;
+        if (act) {
+            const float sx = a.s[0][i], sy = a.s[1][i];
+            const hf_area_info *info = a.t.info;
+            const float target = sy * info->sum_f, norm = info->norm; // sample(): value *= m_sum
+            uint32_t lo = 0u, hi = a.t.nseg - 1u;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (a.t.coarse[mid] < target) lo = mid + 1u; else hi = mid;
+            }
+            const float4 *seg = reinterpret_cast<const float4 *>(a.t.cdf + (size_t) lo * HF_AREA_SEG);
+            uint32_t cnt = 0u;
+#pragma unroll
+            for (int q = 0; q < HF_AREA_SEG / 4; ++q) {
+                const float4 v = seg[q];
+                cnt += (uint32_t) (v.x < target) + (uint32_t) (v.y < target) + (uint32_t) (v.z < target) + (uint32_t) (v.w < target);
+            }
+            idx = min(max(lo * HF_AREA_SEG + cnt, info->valid_lo), info->valid_hi);
+            idx = min(idx, a.t.m - 1u);
+            const float prev = idx > 0u ? a.t.cdf[idx - 1u] : 0.f;
+            v3 P[3], N[3];
+            float U[3], V[3];
+            int vi[3], vj[3];
+            prim_world(a.f, idx, P, U, V, vi, vj);
+            if (SMOOTH) load_vn(a.f, a.vn, vi, vj, N);
+            // sample_reuse: (value - cdf[i-1] norm) / (pmf[i] norm), pmf[i] recomputed from the vertices as build_pmf does
+            const float reused = (sy - prev * norm) / (tri_area(P[0], P[1], P[2]) * norm);
+            const float t = __builtin_sqrtf(fmaxf(1.f - sx, 0.f)); // square_to_uniform_triangle (safe_sqrt)
+            bx = 1.f - t;
+            by = t * reused;
+            const float b0 = 1.f - bx - by;
+            const v3 e0 = P[1] - P[0], e1 = P[2] - P[0];
+            p = mk3(__builtin_fmaf(e0.x, bx, __builtin_fmaf(e1.x, by, P[0].x)),
+                    __builtin_fmaf(e0.y, bx, __builtin_fmaf(e1.y, by, P[0].y)),
+                    __builtin_fmaf(e0.z, bx, __builtin_fmaf(e1.z, by, P[0].z)));
+            uv0 = __builtin_fmaf(U[0], b0, __builtin_fmaf(U[1], bx, U[2] * by));
+            uv1 = __builtin_fmaf(V[0], b0, __builtin_fmaf(V[1], bx, V[2] * by));
+            if (SMOOTH)
+                nn = mk3(__builtin_fmaf(N[0].x, b0, __builtin_fmaf(N[1].x, bx, N[2].x * by)),
+                         __builtin_fmaf(N[0].y, b0, __builtin_fmaf(N[1].y, bx, N[2].y * by)),
+                         __builtin_fmaf(N[0].z, b0, __builtin_fmaf(N[1].z, bx, N[2].z * by)));
+            else
+                nn = cross3(e0, e1);
+            nn = normalize3(nn);
+            if (a.f.flip) nn = neg3(nn);
+            pdf = norm;
+        }
+        a.out.p[0][i] = p.x; a.out.p[1][i] = p.y; a.out.p[2][i] = p.z;
+        a.out.n[0][i] = nn.x; a.out.n[1][i] = nn.y; a.out.n[2][i] = nn.z;
+        a.out.uv[0][i] = uv0; a.out.uv[1][i] = uv1;
+        a.out.pdf[i] = pdf;
+        if (a.out.prim_index) a.out.prim_index[i] = idx;
+        if (a.out.b[0]) a.out.b[0][i] = bx;
+        if (a.out.b[1]) a.out.b[1][i] = by;
+    }
+}
+
+void hf_launch_sample_position(const hf_dev_field &f, const hf_area_table &t, size_t n, const float *const sample[2],
+                               const uint8_t *active, const hf_position_sample_t &out, const float4 *vn, hipStream_t stream) {
+    if (n == 0) return;
+    hf_sample_args a;
+    a.f = f; a.t = t; a.n = n; a.s[0] = sample[0]; a.s[1] = sample[1]; a.active = active; a.out = out; a.vn = vn;
+    hipLaunchKernelGGL(vn ? hf_sample_position_kernel<true> : hf_sample_position_kernel<false>, dim3(grid_for(n)),
+                       dim3(HF_BLOCK), 0, stream, a);
+}
+
+// Reverse and forward mode of sample_position with respect to the heights, for the forward's (prim, b): p = P0 + b1 e0
+// + b2 e1 moves with the three heights along ez (the third column of to_world times max_height); n = N / |N| with
+// N = cross(e0, e1) (flat) or the blend of the three vertex normals (smooth: through vertex_normal_vjp / _jvp).
+struct hf_sample_diff_args {
+    hf_dev_field f;
+    size_t n;
+    const uint32_t *prim;
+    const float *b[2];
+    const uint8_t *active;
+    const float *gp[3], *gn[3]; // adjoint: upstream gradients (NULL rows: zero)
+    float *grad_h;
+    const float *dh;            // tangent: height tangent (NULL: zero)
+    float *dp[3], *dn[3];       // tangent: outputs (NULL rows: not written)
+    const float4 *vn;
+};
+// the sample's triangle and what both modes share; false for inactive lanes and out-of-range indices
+__device__ __forceinline__ bool sample_diff_setup(const hf_sample_diff_args &a, size_t i, uint32_t &prim, float &bx, float &by) {
+    if (a.active && a.active[i] == 0) return false;
+    prim = a.prim[i];
+    if (prim >= 2u * (uint32_t) (a.f.W - 1) * (uint32_t) (a.f.H - 1)) return false;
+    bx = a.b[0][i]; by = a.b[1][i];
+    return true;
+}
+// the normalised blend of the vertex normals N: B, r = |B|^-1
+__device__ __forceinline__ v3 sample_blend(const v3 N[3], float b0, float bx, float by) {
+    return mk3(__builtin_fmaf(N[0].x, b0, __builtin_fmaf(N[1].x, bx, N[2].x * by)),
+               __builtin_fmaf(N[0].y, b0, __builtin_fmaf(N[1].y, bx, N[2].y * by)),
+               __builtin_fmaf(N[0].z, b0, __builtin_fmaf(N[1].z, bx, N[2].z * by)));
+}
+
+template <bool SMOOTH>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_kernel(hf_sample_diff_args a) {
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
+        uint32_t prim;
+        float bx, by;
+        if (!sample_diff_setup(a, i, prim, bx, by)) continue;
+        const hf_dev_field &f = a.f;
+        v3 P[3];
+        float U[3], V[3];
+        int vi[3], vj[3];
+        prim_world(f, prim, P, U, V, vi, vj);
+        const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
+        const v3 gp = a.gp[0] ? mk3(a.gp[0][i], a.gp[1][i], a.gp[2][i]) : mk3(0.f, 0.f, 0.f);
+        v3 gn = a.gn[0] ? mk3(a.gn[0][i], a.gn[1][i], a.gn[2][i]) : mk3(0.f, 0.f, 0.f);
+        if (f.flip) gn = neg3(gn);
+        const float b0 = 1.f - bx - by, gpz = dot3(gp, ez);
+        float gh[3] = { gpz * b0, gpz * bx, gpz * by };
+        v3 gB[3];
+        if (SMOOTH) {
+            v3 N[3];
+            load_vn(f, a.vn, vi, vj, N);
+            const v3 B = sample_blend(N, b0, bx, by);
+            const float r = rsqrt_ieee(dot3(B, B));
+            const v3 n = B * r;
+            const float pj = dot3(n, gn);
+            const v3 g = mk3((gn.x - n.x * pj) * r, (gn.y - n.y * pj) * r, (gn.z - n.z * pj) * r);
+            gB[0] = g * b0; gB[1] = g * bx; gB[2] = g * by;
+        } else {
+            const v3 e0 = P[1] - P[0], e1 = P[2] - P[0];
+            const auto [n, r] = unit_normal(e0, e1);
+            const float pj = dot3(n, gn);
+            const v3 gN = mk3((gn.x - n.x * pj) * r, (gn.y - n.y * pj) * r, (gn.z - n.z * pj) * r);
+            const float g1 = dot3(ez, cross3(e1, gN)), g2 = dot3(ez, cross3(gN, e0)); // d/de0, d/de1
+            gh[1] += g1; gh[2] += g2; gh[0] -= g1 + g2;
+        }
+        float *grad_h = a.grad_h;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) atomicAdd(grad_h + (size_t) vi[k] * f.W + vj[k], gh[k]);
+        if (SMOOTH) {
+#pragma unroll 1
+            for (int k = 0; k < 3; ++k) {
+                hf_ring g;
+                ring_world(f, vi[k], vj[k], g);
+                float gX, gR[6];
+                vertex_normal_vjp(g, ez, gB[k], gX, gR);
+                atomicAdd(grad_h + (size_t) g.i[6] * f.W + g.j[6], gX);
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+                    if ((g.in >> q) & 1u) atomicAdd(grad_h + (size_t) g.i[q] * f.W + g.j[q], gR[q]);
+            }
+        }
+    }
+}
+
+template <bool SMOOTH>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sample_tangent_kernel(hf_sample_diff_args a) {
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
+        uint32_t prim;
+        float bx, by;
+        v3 dp = mk3(0.f, 0.f, 0.f), dn = dp;
+        if (a.dh && sample_diff_setup(a, i, prim, bx, by)) {
+            const hf_dev_field &f = a.f;
+            v3 P[3], dP[3];
+            float U[3], V[3];
+            int vi[3], vj[3];
+            prim_world(f, prim, P, U, V, vi, vj, dP, a.dh);
+            const float b0 = 1.f - bx - by;
+            dp = mk3(dP[0].x * b0 + dP[1].x * bx + dP[2].x * by, dP[0].y * b0 + dP[1].y * bx + dP[2].y * by,
+                     dP[0].z * b0 + dP[1].z * bx + dP[2].z * by);
+            if (SMOOTH) {
+                const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
+                v3 N[3];
+                load_vn(f, a.vn, vi, vj, N);
+                const v3 B = sample_blend(N, b0, bx, by);
+                const float r = rsqrt_ieee(dot3(B, B));
+                const v3 n = B * r;
+                v3 dB = mk3(0.f, 0.f, 0.f);
+                const float w[3] = { b0, bx, by };
+#pragma unroll 1
+                for (int k = 0; k < 3; ++k) {
+                    hf_ring g;
+                    float dX, dR[6];
+                    ring_world(f, vi[k], vj[k], g, a.dh, &dX, dR);
+                    axpy3(w[k], vertex_normal_jvp(g, ez, dX, dR), dB);
+                }
+                const float pj = dot3(n, dB);
+                dn = mk3((dB.x - n.x * pj) * r, (dB.y - n.y * pj) * r, (dB.z - n.z * pj) * r);
+            } else {
+                const v3 e0 = P[1] - P[0], e1 = P[2] - P[0], de0 = dP[1] - dP[0], de1 = dP[2] - dP[0];
+                const auto [n, r] = unit_normal(e0, e1);
+                const v3 c1 = cross3(de0, e1), c2 = cross3(e0, de1);
+                const v3 dN = mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
+                const float pj = dot3(n, dN);
+                dn = mk3((dN.x - n.x * pj) * r, (dN.y - n.y * pj) * r, (dN.z - n.z * pj) * r);
+            }
+            if (f.flip) dn = neg3(dn);
+        }
+        if (a.dp[0]) { a.dp[0][i] = dp.x; a.dp[1][i] = dp.y; a.dp[2][i] = dp.z; }
+        if (a.dn[0]) { a.dn[0][i] = dn.x; a.dn[1][i] = dn.y; a.dn[2][i] = dn.z; }
+    }
+}
+
+static hf_sample_diff_args sample_diff_args(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
+                                            const uint8_t *active, const float4 *vn) {
+    hf_sample_diff_args a = {};
+    a.f = f; a.n = n; a.prim = prim; a.b[0] = b[0]; a.b[1] = b[1]; a.active = active; a.vn = vn;
+    return a;
+}
+void hf_launch_sample_position_adjoint(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
+                                       const uint8_t *active, const float *const gp[3], const float *const gn[3],
+                                       float *grad_h, const float4 *vn, hipStream_t stream) {
+    if (n == 0 || (!gp && !gn)) return;
+    hf_sample_diff_args a = sample_diff_args(f, n, prim, b, active, vn);
+    for (int c = 0; c < 3; ++c) { a.gp[c] = gp ? gp[c] : nullptr; a.gn[c] = gn ? gn[c] : nullptr; }
+    a.grad_h = grad_h;
+    hipLaunchKernelGGL(vn ? hf_sample_adjoint_kernel<true> : hf_sample_adjoint_kernel<false>, dim3(grid_for(n)),
+                       dim3(HF_BLOCK), 0, stream, a);
+}
+void hf_launch_sample_position_tangent(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
+                                       const uint8_t *active, const float *dh, float *const dp[3], float *const dn[3],
+                                       const float4 *vn, hipStream_t stream) {
+    if (n == 0 || (!dp && !dn)) return;
+    hf_sample_diff_args a = sample_diff_args(f, n, prim, b, active, vn);
+    a.dh = dh;
+    for (int c = 0; c < 3; ++c) { a.dp[c] = dp ? dp[c] : nullptr; a.dn[c] = dn ? dn[c] : nullptr; }
+    hipLaunchKernelGGL(vn ? hf_sample_tangent_kernel<true> : hf_sample_tangent_kernel<false>, dim3(grid_for(n)),
+                       dim3(HF_BLOCK), 0, stream, a);
 }

@@ -89,3 +89,25 @@ void hf_launch_reparam_aux(const hf_reparam_args &a, hipStream_t stream);
 void hf_launch_reparam_weights(const hf_reparam_args &a, hipStream_t stream);
 void hf_launch_reparam_backward(const hf_dev_field &f, const hf_reparam_args &a, uint32_t num_rays, size_t stride,
                                 const hf_pi_const_t *pi, float *grad_h, hipStream_t stream);
+// ---- area sampling (hf_set_area_sampling) ----
+#define HF_AREA_CHUNK 2048 // cells per tile of the table build: one cell row, or a 2048-cell piece of one
+#define HF_AREA_SEG 64     // CDF entries per entry of the coarse search table
+// the handle's area table; all device buffers are owned by the handle, NULL cdf = sampling disabled
+struct hf_area_table {
+    float *cdf;          // [nseg * HF_AREA_SEG]: fp32 CDF of the m triangle areas, padded with +inf
+    float *coarse;       // [nseg]: cdf[64 k + 63] (the last entry for the last segment)
+    double *tile;        // [3 ntiles]: tile totals, then per tile (group base, offset within the group)
+    uint32_t *tile_valid;// [2 ntiles]: first nonzero entry, last nonzero entry + 1 of every tile
+    hf_area_info *info;  // the distribution's scalars
+    uint32_t m, nseg, ncx, ntiles;
+};
+// rebuild the table from the current heights and transform: three launches, no inter-workgroup waits
+void hf_launch_build_area(const hf_dev_field &f, const hf_area_table &t, hipStream_t stream);
+void hf_launch_sample_position(const hf_dev_field &f, const hf_area_table &t, size_t n, const float *const sample[2],
+                               const uint8_t *active, const hf_position_sample_t &out, const float4 *vn, hipStream_t stream);
+void hf_launch_sample_position_adjoint(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
+                                       const uint8_t *active, const float *const gp[3], const float *const gn[3],
+                                       float *grad_h, const float4 *vn, hipStream_t stream);
+void hf_launch_sample_position_tangent(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
+                                       const uint8_t *active, const float *dh, float *const dp[3], float *const dn[3],
+                                       const float4 *vn, hipStream_t stream);

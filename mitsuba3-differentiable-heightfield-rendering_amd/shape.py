@@ -15,7 +15,7 @@ import torch
 import torch.autograd.forward_ad as fwAD
 
 from . import _capi
-from ._capi import check, hf_desc_t, hf_pi_t, hf_rays_t, hf_si_grad_t, hf_si_t, hf_si_tangent_t
+from ._capi import check, hf_desc_t, hf_pi_t, hf_position_sample_t, hf_rays_t, hf_si_grad_t, hf_si_t, hf_si_tangent_t
 
 
 class RayFlags(enum.IntFlag):
@@ -148,6 +148,66 @@ class SurfaceInteraction3f:
         o = torch.addcmul(p, mag[None, :], n)
         maxt = torch.full((p.shape[1],), math.inf, dtype=torch.float32, device=p.device)
         return Ray3f(o.contiguous(), d.contiguous(), maxt)
+
+
+def _device_copy(dst, src, nbytes):
+    """synchronous device-to-device copy through the HIP runtime libhf is linked against (test accessors only)"""
+    hip = C.CDLL("libamdhip64.so.7")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    if hip.hipMemcpy(dst, src, nbytes, 3) != 0:   # hipMemcpyDeviceToDevice
+        raise RuntimeError("hipMemcpy failed")
+
+
+class PositionSample3f:
+    """include/mitsuba/render/records.h PositionSample: p, n ([3, n]), uv ([2, n]), time, pdf ([n]), delta.  The
+    heightfield also records the sampled triangle (prim_index) and its barycentrics b ([2, n]: b1, b2)."""
+
+    def __init__(self, p, n, uv, time, pdf, delta=False):
+        self.p, self.n, self.uv, self.time, self.pdf, self.delta = p, n, uv, time, pdf, delta
+        self.prim_index = self.b = None
+
+
+class DirectionSample3f(PositionSample3f):
+    """records.h DirectionSample: a PositionSample plus the unit direction d from the reference point and the
+    distance dist"""
+
+    def __init__(self, ps, d, dist):
+        super().__init__(ps.p, ps.n, ps.uv, ps.time, ps.pdf, ps.delta)
+        self.prim_index, self.b = ps.prim_index, ps.b
+        self.d, self.dist = d, dist
+
+
+class _SamplePositionOp(torch.autograd.Function):
+    """Differentiable [6, n] block (p, n) of sample_position; backward = hf_sample_position_adjoint (atomic scatter of
+    dL/dheight), jvp = hf_sample_position_tangent.  The sampled triangle and b are frozen (detached, as build_pmf)."""
+
+    @staticmethod
+    def forward(ctx, shape, heights, prim, b, active, block):
+        ctx.shape, ctx.active = shape, active
+        ctx.save_for_backward(prim, b)
+        ctx.save_for_forward(prim, b)
+        ctx.h_version = shape._heights_version
+        return block
+
+    @staticmethod
+    def jvp(ctx, _shape, dh, *_):
+        shape = ctx.shape
+        prim, b = ctx.saved_tensors
+        if ctx.h_version != shape._heights_version:
+            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
+        return shape._sample_tangent_raw(prim, b, ctx.active, dh)
+
+    @staticmethod
+    def backward(ctx, g):
+        shape = ctx.shape
+        prim, b = ctx.saved_tensors
+        if ctx.h_version != shape._heights_version:
+            raise RuntimeError("heightfield parameters changed between forward and backward")
+        grad_h = None
+        if ctx.needs_input_grad[1]:
+            grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=prim.device)
+            shape._sample_adjoint_raw(prim, b, ctx.active, g.contiguous().to(torch.float32), grad_h)
+        return None, grad_h, None, None, None, None
 
 
 # order of the differentiable SI block handed to autograd: 18 rows
@@ -324,6 +384,131 @@ class Heightfield:
         pis = self._pi_struct(pi.t.detach().contiguous(), pi.prim_uv.detach().contiguous(), pi.prim_index.contiguous())
         check(_capi.lib().hf_shading_derivatives(self._h, n, C.byref(pis), keep.data_ptr() if keep is not None else None,
                                                  C.byref(pu), C.byref(pv), self._stream()))
+        return out[0:3], out[3:6]
+
+    # ---- area sampling (Mesh::build_pmf / sample_position / pdf_position, mesh.cpp:401-432, 552-642) ----------------
+    def ensure_pmf_built(self):
+        """mesh.cpp ensure_pmf_built: the area table is enabled on first use (hf_set_area_sampling); from then on every
+        parameters_changed / Adam step rebuilds it with the heights"""
+        if not getattr(self, "_area_enabled", False):
+            check(_capi.lib().hf_set_area_sampling(self._h, 1, self._stream()))
+            self._area_enabled = True
+
+    def _area_scalars(self):
+        self.ensure_pmf_built()
+        area, norm = C.c_float(), C.c_float()
+        check(_capi.lib().hf_surface_area(self._h, C.byref(area), C.byref(norm)))
+        return area.value, norm.value
+
+    def surface_area(self):
+        """mesh.cpp:552-555: the sum of the triangle areas (m_area_pmf.sum(), float32)"""
+        return self._area_scalars()[0]
+
+    def area_cdf(self):
+        """the area table's float32 CDF ([2 (W-1) (H-1)] device tensor, a copy; hf_area_cdf)"""
+        self.ensure_pmf_built()
+        ptr, cnt = C.c_void_p(), C.c_size_t()
+        check(_capi.lib().hf_area_cdf(self._h, C.byref(ptr), C.byref(cnt)))
+        out = torch.empty(cnt.value, dtype=torch.float32, device=self.device)
+        if cnt.value:
+            torch.cuda.current_stream(self.device).synchronize()   # the last rebuild, on this stream
+            _device_copy(out.data_ptr(), ptr.value, 4 * cnt.value)
+        return out
+
+    def sample_position(self, time, sample, active=True):
+        """mesh.cpp:557-610 (hf_sample_position): sample [2, n] in [0, 1).  p and n are differentiable in the
+        heightfield (hf_sample_position_adjoint / _tangent); uv, pdf and the choice of triangle are not."""
+        self.ensure_pmf_built()
+        sample = _as_f32(sample, self.device).reshape(2, -1)
+        n = sample.shape[1]
+        keep, ap = self._mask(active, n)
+        block = torch.empty((6, n), dtype=torch.float32, device=self.device)   # p, n
+        rest = torch.empty((5, n), dtype=torch.float32, device=self.device)    # uv, pdf, b
+        prim = torch.empty(n, dtype=torch.int32, device=self.device)
+        out = hf_position_sample_t()
+        rows, more = _rows(block, n), _rows(rest, n)
+        for k in range(3):
+            out.p[k], out.n[k] = rows[k], rows[3 + k]
+        out.uv[0], out.uv[1], out.pdf = more[0], more[1], more[2]
+        out.prim_index = prim.data_ptr()
+        out.b[0], out.b[1] = more[3], more[4]
+        sp = (C.c_void_p * 2)(*_rows(sample, n))
+        check(_capi.lib().hf_sample_position(self._h, n, C.byref(sp), ap, C.byref(out), self._stream()))
+        h = self.heightfield
+        if (torch.is_grad_enabled() and h.requires_grad) or _has_tangent(h):
+            block = _SamplePositionOp.apply(self, h, prim, rest[3:5], keep, block)
+        ps = PositionSample3f(block[0:3], block[3:6], rest[0:2], time, rest[2], False)
+        ps.prim_index, ps.b = prim, rest[3:5]
+        return ps
+
+    def pdf_position(self, ps, active=True):
+        """mesh.cpp:637-640: m_area_pmf.normalization() = (float) (1 / sum) for every active lane"""
+        norm = self._area_scalars()[1]
+        n = ps.p.shape[1]
+        pdf = torch.full((n,), norm, dtype=torch.float32, device=self.device)
+        keep, _ = self._mask(active, n)
+        return pdf if keep is None else torch.where(keep.bool(), pdf, torch.zeros_like(pdf))
+
+    def sample_direction(self, it, sample, active=True):
+        """Shape::sample_direction (shape.cpp:363-382) on sample_position: differentiable in the heightfield and in it.p"""
+        ps = self.sample_position(it.time, sample, active)
+        d = ps.p - it.p
+        dist_squared = (d * d).sum(0)
+        dist = torch.sqrt(dist_squared)
+        d = d / dist
+        dp = (d * ps.n).sum(0).abs()
+        x = dist_squared / dp
+        pdf = ps.pdf * torch.where(torch.isfinite(x), x, torch.zeros_like(x))
+        ps.pdf = pdf
+        return DirectionSample3f(ps, d, dist)
+
+    def pdf_direction(self, it, ds, active=True):
+        """Shape::pdf_direction (shape.cpp:385-395)"""
+        pdf = self.pdf_position(ds, active)
+        dp = (ds.d * ds.n).sum(0).abs()
+        return pdf * torch.where(dp != 0, (ds.dist * ds.dist) / dp, torch.zeros_like(dp))
+
+    def _sample_adjoint_raw(self, prim, b, active_u8, g, grad_h):
+        n = prim.shape[0]
+        rows = _rows(g, n)
+        gp, gn = (C.c_void_p * 3)(*rows[0:3]), (C.c_void_p * 3)(*rows[3:6])
+        bp = (C.c_void_p * 2)(*_rows(b.contiguous(), n))
+        check(_capi.lib().hf_sample_position_adjoint(self._h, n, prim.data_ptr(), C.byref(bp),
+                                                     active_u8.data_ptr() if active_u8 is not None else None,
+                                                     C.byref(gp), C.byref(gn), grad_h.data_ptr(), self._stream()))
+
+    def _sample_tangent_raw(self, prim, b, active_u8, dh):
+        n = prim.shape[0]
+        out = torch.zeros((6, n), dtype=torch.float32, device=self.device)
+        if dh is None:
+            return out
+        dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
+        assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
+        rows = _rows(out, n)
+        dp, dn = (C.c_void_p * 3)(*rows[0:3]), (C.c_void_p * 3)(*rows[3:6])
+        bp = (C.c_void_p * 2)(*_rows(b.contiguous(), n))
+        check(_capi.lib().hf_sample_position_tangent(self._h, n, prim.data_ptr(), C.byref(bp),
+                                                     active_u8.data_ptr() if active_u8 is not None else None,
+                                                     dh.data_ptr(), C.byref(dp), C.byref(dn), self._stream()))
+        return out
+
+    def sample_position_adjoint(self, ps, grad_p=None, grad_n=None, active=True, grad_heightfield=None):
+        """Explicit adjoint of sample_position for the samples of `ps`: accumulates dL/dheight for the upstream
+        gradients grad_p / grad_n ([3, n], None = zero) into grad_heightfield ([H, W])"""
+        n = ps.prim_index.shape[0]
+        if grad_heightfield is None:
+            grad_heightfield = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+        z = torch.zeros((3, n), dtype=torch.float32, device=self.device)
+        g = torch.cat([z if grad_p is None else _as_f32(grad_p, self.device).reshape(3, n),
+                       z if grad_n is None else _as_f32(grad_n, self.device).reshape(3, n)]).contiguous()
+        keep, _ = self._mask(active, n)
+        self._sample_adjoint_raw(ps.prim_index, ps.b, keep, g, grad_heightfield)
+        return grad_heightfield
+
+    def sample_position_tangent(self, ps, dheights, active=True):
+        """Explicit forward mode of sample_position: (dp, dn) ([3, n] each) for the height tangent dheights ([H, W])"""
+        keep, _ = self._mask(active, ps.prim_index.shape[0])
+        out = self._sample_tangent_raw(ps.prim_index, ps.b, keep, dheights)
         return out[0:3], out[3:6]
 
     def parameters_grad_enabled(self):
