@@ -252,13 +252,18 @@ __device__ __forceinline__ float boundary_test_flat(v3 p, v3 p0, v3 dp0, v3 dp1,
 // (hf_tangent_kernel) and hf_reparam_backward_kernel share, each written once.  Every call site gets exactly the
 // operations it had inline (same order, same fmas), so the results are bit for bit those of the inline forms. ----
 
-// World-space vertices + texcoords of a primitive.  With dP: also the vertices' tangents dP_k = dh_k s (third column
-// of to_world) for the height tangent dh (nullptr: zero).  No load depends on another: the three heights and the
-// three height tangents go out as one batch.
+// dP/dh of a grid vertex: the third column of to_world times max_height (a height moves its vertex along it only)
+__device__ __forceinline__ v3 height_axis(const hf_dev_field &f) {
+    return mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
+}
+
+// World-space vertices + texcoords of a primitive.  With dP: also the vertices' tangents dP_k = dh_k height_axis(f)
+// for the height tangent dh (nullptr: zero).  No load depends on another: the three heights and the three height
+// tangents go out as one batch.
 __device__ __forceinline__ void prim_world(const hf_dev_field &f, uint32_t prim, v3 P[3], float U[3], float V[3],
                                            int vi[3], int vj[3], v3 *dP = nullptr, const float *dh = nullptr) {
     prim_vertex_ids(f, prim, vi, vj);
-    const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s); // dP_k/dh_k
+    const v3 ez = height_axis(f); // dP_k/dh_k
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const size_t idx = (size_t) vi[k] * f.W + vj[k];
@@ -326,6 +331,24 @@ __device__ __forceinline__ hf_mt mt_terms(v3 o, v3 d, v3 p0, v3 e1, v3 e2) {
     m.qvec = cross3(m.tvec, e1);
     m.a_u = dot3(m.tvec, m.pvec); m.a_v = dot3(d, m.qvec); m.a_t = dot3(e2, m.qvec);
     return m;
+}
+
+// ---- Derivatives of the normals, written once for every tangent and adjoint kernel and vertex_normal_jvp / _vjp ----
+
+// derivative of normalize at n = N r (r = |N|^-1) applied to x: (x - n <n, x>) r.  The map is symmetric, so the
+// tangent (x = dN) and the adjoint (x = dL/dn) are the same formula.
+__device__ __forceinline__ v3 dnormalize(v3 n, float r, v3 x) {
+    const float pj = dot3(n, x);
+    return mk3((x.x - n.x * pj) * r, (x.y - n.y * pj) * r, (x.z - n.z * pj) * r);
+}
+// tangent of the face normal N = cross(e1, e2): dN = cross(de1, e2) + cross(e1, de2)
+__device__ __forceinline__ v3 face_normal_jvp(v3 e1, v3 e2, v3 de1, v3 de2) {
+    const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);
+    return mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
+}
+// its transpose for the gradient gN of N, contracted with ez = height_axis: g1 = <ez, dL/de1>, g2 = <ez, dL/de2>
+__device__ __forceinline__ void face_normal_vjp(v3 e1, v3 e2, v3 gN, v3 ez, float &g1, float &g2) {
+    g1 = dot3(ez, cross3(e2, gN)); g2 = dot3(ez, cross3(gN, e1));
 }
 
 // ---- Smooth shading (hf_set_face_normals(hf, 0)): angle-weighted vertex normals, the JIT path of
@@ -428,19 +451,14 @@ __device__ __forceinline__ v3 vertex_normal_jvp(const hf_ring &g, v3 ez, float d
         const v3 e1 = g.R[k] - g.X, e2 = g.R[k1] - g.X;
         const v3 de1 = ez * (dR[k] - dX), de2 = ez * (dR[k1] - dX);
         const auto [nt, r] = unit_normal(e1, e2);
-        const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);
-        const v3 dN = mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
-        const float pj = dot3(nt, dN);
-        const v3 dnt = mk3((dN.x - nt.x * pj) * r, (dN.y - nt.y * pj) * r, (dN.z - nt.z * pj) * r);
+        const v3 dnt = dnormalize(nt, r, face_normal_jvp(e1, e2, de1, de2));
         const float c = dot3(u[k], u[k1]);
         const v3 du1 = (de1 - u[k] * dot3(u[k], de1)) * l[k], du2 = (de2 - u[k1] * dot3(u[k1], de2)) * l[k1];
         const float dth = ring_dangle(c) * (dot3(du1, u[k1]) + dot3(u[k], du2));
         axpy3(ring_angle(c), dnt, dm);
         axpy3(dth, nt, dm);
     }
-    const v3 n = m * rm;
-    const float pj = dot3(n, dm);
-    return mk3((dm.x - n.x * pj) * rm, (dm.y - n.y * pj) * rm, (dm.z - n.z * pj) * rm);
+    return dnormalize(m * rm, rm, dm);
 }
 // Transpose of vertex_normal_jvp: for the upstream gradient gn of the vertex normal, the gradients with respect to the
 // heights of X (gX) and of ring vertex k (gR[k]; zero for absent neighbours).  The position gradients are contracted
@@ -452,9 +470,7 @@ __device__ __forceinline__ void vertex_normal_vjp(const hf_ring &g, v3 ez, v3 gn
     float l[6], rm;
     ring_dirs(g, u, l);
     const v3 m = ring_sum(g, u, rm);
-    const v3 n = m * rm;
-    const float pn = dot3(n, gn);
-    const v3 gm = mk3((gn.x - n.x * pn) * rm, (gn.y - n.y * pn) * rm, (gn.z - n.z * pn) * rm);
+    const v3 gm = dnormalize(m * rm, rm, gn);
 #pragma unroll
     for (int k = 0; k < 6; ++k) gR[k] = 0.f;
 #pragma unroll
@@ -464,17 +480,45 @@ __device__ __forceinline__ void vertex_normal_vjp(const hf_ring &g, v3 ez, v3 gn
         const v3 e1 = g.R[k] - g.X, e2 = g.R[k1] - g.X;
         const auto [nt, r] = unit_normal(e1, e2);
         const float c = dot3(u[k], u[k1]), th = ring_angle(c);
-        const v3 gnt = gm * th;
-        const float pj = dot3(nt, gnt);
-        const v3 gN = mk3((gnt.x - nt.x * pj) * r, (gnt.y - nt.y * pj) * r, (gnt.z - nt.z * pj) * r);
+        float g1, g2;
+        face_normal_vjp(e1, e2, dnormalize(nt, r, gm * th), ez, g1, g2);
         const float gc = ring_dangle(c) * dot3(nt, gm);
         const float ez0 = dot3(ez, u[k]), ez1 = dot3(ez, u[k1]);
-        gR[k] += dot3(ez, cross3(e2, gN)) + gc * l[k] * (ez1 - ez0 * c);
-        gR[k1] += dot3(ez, cross3(gN, e1)) + gc * l[k1] * (ez0 - ez1 * c);
+        gR[k] += g1 + gc * l[k] * (ez1 - ez0 * c);
+        gR[k1] += g2 + gc * l[k1] * (ez0 - ez1 * c);
     }
     gX = 0.f;
 #pragma unroll
     for (int k = 0; k < 6; ++k) gX -= gR[k];
+}
+
+// The three vertex normals of a hit (rows vi, columns vj), evaluated on the fly from the heights.  VJP: for their
+// gradients gB[k], the 1 + 6 height gradients of each vertex and its existing ring neighbours go to the sink
+// add(row, column, g); JVP: for the height tangent dh, acc += sum_k w[k] dN_k.
+template <typename Add>
+__device__ __forceinline__ void vertex_normals_vjp(const hf_dev_field &f, const int vi[3], const int vj[3], v3 ez,
+                                                   const v3 gB[3], Add add) {
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        hf_ring g;
+        ring_world(f, vi[k], vj[k], g);
+        float gX, gR[6];
+        vertex_normal_vjp(g, ez, gB[k], gX, gR);
+        add(vi[k], vj[k], gX);
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+            if ((g.in >> q) & 1u) add(g.i[q], g.j[q], gR[q]);
+    }
+}
+__device__ __forceinline__ void vertex_normals_jvp(const hf_dev_field &f, const int vi[3], const int vj[3], v3 ez,
+                                                   const float w[3], const float *dh, v3 &acc) {
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        hf_ring g;
+        float dX, dR[6];
+        ring_world(f, vi[k], vj[k], g, dh, &dX, dR);
+        axpy3(w[k], vertex_normal_jvp(g, ez, dX, dR), acc);
+    }
 }
 
 // The three vertex normals of a hit from the handle's buffer (one 16-byte load each)
@@ -485,11 +529,18 @@ __device__ __forceinline__ void load_vn(const hf_dev_field &f, const float4 *vn,
         N[k] = mk3(q.x, q.y, q.z);
     }
 }
-// fmadd(n2, b2, fmadd(n1, b1, n0 * b0)) (mesh.cpp:818)
+// The blend of the three vertex normals, in the reference's two association orders (they round differently): the
+// surface interaction's fmadd(n2, b2, fmadd(n1, b1, n0 * b0)) (mesh.cpp:818) ...
 __device__ __forceinline__ v3 bary_normal(const v3 N[3], float b0, float b1, float b2) {
     return mk3(__builtin_fmaf(N[2].x, b2, __builtin_fmaf(N[1].x, b1, N[0].x * b0)),
                __builtin_fmaf(N[2].y, b2, __builtin_fmaf(N[1].y, b1, N[0].y * b0)),
                __builtin_fmaf(N[2].z, b2, __builtin_fmaf(N[1].z, b1, N[0].z * b0)));
+}
+// ... and sample_position's fmadd(n0, b0, fmadd(n1, bx, n2 * by)) (mesh.cpp:599-600)
+__device__ __forceinline__ v3 sample_blend(const v3 N[3], float b0, float bx, float by) {
+    return mk3(__builtin_fmaf(N[0].x, b0, __builtin_fmaf(N[1].x, bx, N[2].x * by)),
+               __builtin_fmaf(N[0].y, b0, __builtin_fmaf(N[1].y, bx, N[2].y * by)),
+               __builtin_fmaf(N[0].z, b0, __builtin_fmaf(N[1].z, bx, N[2].z * by)));
 }
 
 // Shape::compute_surface_interaction + finalize_surface_interaction for one valid hit, from the hit-geometry helpers

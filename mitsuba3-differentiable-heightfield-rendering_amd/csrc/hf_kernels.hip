@@ -2117,8 +2117,7 @@ __device__ __forceinline__ void adjoint_body(float *acc) {
                 const float sgn = f.flip ? -1.f : 1.f;
                 const v3 gnf = sm ? gn_a : mk3(gn_a.x + gn_b.x, gn_a.y + gn_b.y, gn_a.z + gn_b.z);
                 const v3 gn = mk3(sgn * gnf.x, sgn * gnf.y, sgn * gnf.z);
-                const float proj = dot3(nn, gn);
-                const v3 gN = mk3((gn.x - nn.x * proj) * r, (gn.y - nn.y * proj) * r, (gn.z - nn.z * proj) * r);
+                const v3 gN = dnormalize(nn, r, gn);
                 axpy3(1.f, cross3(dp1, gN), gdp0);
                 axpy3(1.f, cross3(gN, dp0), gdp1);
             }
@@ -2135,9 +2134,7 @@ __device__ __forceinline__ void adjoint_body(float *acc) {
             if (sm) { // sh_n = +-normalize(sum b_k N_k): to the barycentrics and to the vertex normals
                 const v3 ns = bary_normal(NV, b0, b1, b2);
                 const float r = rsqrt_ieee(dot3(ns, ns));
-                const v3 sn = ns * r, gs = f.flip ? neg3(gn_b) : gn_b;
-                const float pj = dot3(sn, gs);
-                const v3 gns = mk3((gs.x - sn.x * pj) * r, (gs.y - sn.y * pj) * r, (gs.z - sn.z * pj) * r);
+                const v3 gns = dnormalize(ns * r, r, f.flip ? neg3(gn_b) : gn_b);
                 gb0 += dot3(gns, NV[0]); gb1 += dot3(gns, NV[1]); gb2 += dot3(gns, NV[2]);
                 gnv[0] = gns * b0; gnv[1] = gns * b1; gnv[2] = gns * b2;
             }
@@ -2200,18 +2197,9 @@ __device__ __forceinline__ void adjoint_body(float *acc) {
                 for (int k = 0; k < 3; ++k) tile_add<HF_ADJ_TILE>(acc, ar, ac, vr[k], vc[k], gh[k], grad_h, W, rows);
             if (SMOOTH && smv) {
                 const hf_dev_field f = load_field(&adj_kargs()->f);
-                const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
-#pragma unroll 1
-                for (int k = 0; k < 3; ++k) {
-                    hf_ring g;
-                    ring_world(f, vr[k], vc[k], g);
-                    float gX, gR[6];
-                    vertex_normal_vjp(g, ez, gnv[k], gX, gR);
-                    tile_add<HF_ADJ_TILE>(acc, ar, ac, vr[k], vc[k], gX, grad_h, W, rows);
-#pragma unroll
-                    for (int q = 0; q < 6; ++q)
-                        if ((g.in >> q) & 1u) tile_add<HF_ADJ_TILE>(acc, ar, ac, g.i[q], g.j[q], gR[q], grad_h, W, rows);
-                }
+                vertex_normals_vjp(f, vr, vc, height_axis(f), gnv, [&](int r, int c, float g) {
+                    tile_add<HF_ADJ_TILE>(acc, ar, ac, r, c, g, grad_h, W, rows);
+                });
             }
             tile_flush<HF_ADJ_TILE>(acc, ar, ac, rows, grad_h, W, (int) lane);
         }
@@ -2333,11 +2321,8 @@ __device__ __forceinline__ void tangent_body() {
         // n = sh_n = +-normalize(cross(e1, e2))  (smooth: n only; sh_n below)
         {
             const auto [nn, r] = unit_normal(e1, e2);
-            const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);
-            const v3 dN = mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
-            const float proj = dot3(nn, dN);
-            const float sr = f.flip ? -r : r;
-            const v3 dn = mk3((dN.x - nn.x * proj) * sr, (dN.y - nn.y * proj) * sr, (dN.z - nn.z * proj) * sr);
+            const v3 dN = face_normal_jvp(e1, e2, de1, de2);
+            const v3 dn = dnormalize(nn, f.flip ? -r : r, dN);
             st3(ka->out.n, ub, lo, dn);
             if (!sm) st3(ka->out.sh_n, ub, lo, dn);
         }
@@ -2372,24 +2357,15 @@ __device__ __forceinline__ void tangent_body() {
         if (sm) { // sh_n = +-normalize(sum b_k N_k): d(sum b_k N_k) = du (N_1 - N_0) + dv (N_2 - N_0) + sum b_k dN_k
             const v3 ns = bary_normal(NV, b0, b1, b2);
             const float r = rsqrt_ieee(dot3(ns, ns));
-            const v3 sn = ns * r;
             v3 dns = z3;
             axpy3(du, NV[1] - NV[0], dns);
             axpy3(dv, NV[2] - NV[0], dns);
             const float *dh = detach ? nullptr : ka->dh;
             if (dh) {
-                const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
                 const float bk[3] = { b0, b1, b2 };
-#pragma unroll 1
-                for (int k = 0; k < 3; ++k) {
-                    hf_ring g;
-                    float dX, dR[6];
-                    ring_world(f, vi[k], vj[k], g, dh, &dX, dR);
-                    axpy3(bk[k], vertex_normal_jvp(g, ez, dX, dR), dns);
-                }
+                vertex_normals_jvp(f, vi, vj, height_axis(f), bk, dh, dns);
             }
-            const float pj = dot3(sn, dns), sr = f.flip ? -r : r;
-            st3(ka->out.sh_n, ub, lo, mk3((dns.x - sn.x * pj) * sr, (dns.y - sn.y * pj) * sr, (dns.z - sn.z * pj) * sr));
+            st3(ka->out.sh_n, ub, lo, dnormalize(ns * r, f.flip ? -r : r, dns));
         }
         // p = sum b_k P_k:  dp = du e1 + dv e2 + sum b_k dP_k
         const v3 dp = mk3(du * e1.x + dv * e2.x + (b0 * dP[0].x + b1 * dP[1].x + b2 * dP[2].x),
@@ -3267,13 +3243,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sample_position_kernel(hf_sample_
                     __builtin_fmaf(e0.z, bx, __builtin_fmaf(e1.z, by, P[0].z)));
             uv0 = __builtin_fmaf(U[0], b0, __builtin_fmaf(U[1], bx, U[2] * by));
             uv1 = __builtin_fmaf(V[0], b0, __builtin_fmaf(V[1], bx, V[2] * by));
-            if (SMOOTH)
-                nn = mk3(__builtin_fmaf(N[0].x, b0, __builtin_fmaf(N[1].x, bx, N[2].x * by)),
-                         __builtin_fmaf(N[0].y, b0, __builtin_fmaf(N[1].y, bx, N[2].y * by)),
-                         __builtin_fmaf(N[0].z, b0, __builtin_fmaf(N[1].z, bx, N[2].z * by)));
-            else
-                nn = cross3(e0, e1);
-            nn = normalize3(nn);
+            nn = normalize3(SMOOTH ? sample_blend(N, b0, bx, by) : cross3(e0, e1));
             if (a.f.flip) nn = neg3(nn);
             pdf = norm;
         }
@@ -3298,7 +3268,7 @@ void hf_launch_sample_position(const hf_dev_field &f, const hf_area_table &t, si
 
 // Reverse and forward mode of sample_position with respect to the heights, for the forward's (prim, b): p = P0 + b1 e0
 // + b2 e1 moves with the three heights along ez (the third column of to_world times max_height); n = N / |N| with
-// N = cross(e0, e1) (flat) or the blend of the three vertex normals (smooth: through vertex_normal_vjp / _jvp).
+// N = cross(e0, e1) (flat) or the blend of the three vertex normals (smooth: through vertex_normals_vjp / _jvp).
 struct hf_sample_diff_args {
     hf_dev_field f;
     size_t n;
@@ -3319,12 +3289,6 @@ __device__ __forceinline__ bool sample_diff_setup(const hf_sample_diff_args &a, 
     bx = a.b[0][i]; by = a.b[1][i];
     return true;
 }
-// the normalised blend of the vertex normals N: B, r = |B|^-1
-__device__ __forceinline__ v3 sample_blend(const v3 N[3], float b0, float bx, float by) {
-    return mk3(__builtin_fmaf(N[0].x, b0, __builtin_fmaf(N[1].x, bx, N[2].x * by)),
-               __builtin_fmaf(N[0].y, b0, __builtin_fmaf(N[1].y, bx, N[2].y * by)),
-               __builtin_fmaf(N[0].z, b0, __builtin_fmaf(N[1].z, bx, N[2].z * by)));
-}
 
 template <bool SMOOTH>
 __global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_kernel(hf_sample_diff_args a) {
@@ -3338,7 +3302,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_kernel(hf_sample_d
         float U[3], V[3];
         int vi[3], vj[3];
         prim_world(f, prim, P, U, V, vi, vj);
-        const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
+        const v3 ez = height_axis(f);
         const v3 gp = a.gp[0] ? mk3(a.gp[0][i], a.gp[1][i], a.gp[2][i]) : mk3(0.f, 0.f, 0.f);
         v3 gn = a.gn[0] ? mk3(a.gn[0][i], a.gn[1][i], a.gn[2][i]) : mk3(0.f, 0.f, 0.f);
         if (f.flip) gn = neg3(gn);
@@ -3350,34 +3314,20 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_kernel(hf_sample_d
             load_vn(f, a.vn, vi, vj, N);
             const v3 B = sample_blend(N, b0, bx, by);
             const float r = rsqrt_ieee(dot3(B, B));
-            const v3 n = B * r;
-            const float pj = dot3(n, gn);
-            const v3 g = mk3((gn.x - n.x * pj) * r, (gn.y - n.y * pj) * r, (gn.z - n.z * pj) * r);
+            const v3 g = dnormalize(B * r, r, gn);
             gB[0] = g * b0; gB[1] = g * bx; gB[2] = g * by;
         } else {
             const v3 e0 = P[1] - P[0], e1 = P[2] - P[0];
             const auto [n, r] = unit_normal(e0, e1);
-            const float pj = dot3(n, gn);
-            const v3 gN = mk3((gn.x - n.x * pj) * r, (gn.y - n.y * pj) * r, (gn.z - n.z * pj) * r);
-            const float g1 = dot3(ez, cross3(e1, gN)), g2 = dot3(ez, cross3(gN, e0)); // d/de0, d/de1
+            float g1, g2;
+            face_normal_vjp(e0, e1, dnormalize(n, r, gn), ez, g1, g2);
             gh[1] += g1; gh[2] += g2; gh[0] -= g1 + g2;
         }
         float *grad_h = a.grad_h;
+        auto add = [&](int r, int c, float g) { atomicAdd(grad_h + (size_t) r * f.W + c, g); };
 #pragma unroll
-        for (int k = 0; k < 3; ++k) atomicAdd(grad_h + (size_t) vi[k] * f.W + vj[k], gh[k]);
-        if (SMOOTH) {
-#pragma unroll 1
-            for (int k = 0; k < 3; ++k) {
-                hf_ring g;
-                ring_world(f, vi[k], vj[k], g);
-                float gX, gR[6];
-                vertex_normal_vjp(g, ez, gB[k], gX, gR);
-                atomicAdd(grad_h + (size_t) g.i[6] * f.W + g.j[6], gX);
-#pragma unroll
-                for (int q = 0; q < 6; ++q)
-                    if ((g.in >> q) & 1u) atomicAdd(grad_h + (size_t) g.i[q] * f.W + g.j[q], gR[q]);
-            }
-        }
+        for (int k = 0; k < 3; ++k) add(vi[k], vj[k], gh[k]);
+        if (SMOOTH) vertex_normals_vjp(f, vi, vj, ez, gB, add);
     }
 }
 
@@ -3398,30 +3348,18 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sample_tangent_kernel(hf_sample_d
             dp = mk3(dP[0].x * b0 + dP[1].x * bx + dP[2].x * by, dP[0].y * b0 + dP[1].y * bx + dP[2].y * by,
                      dP[0].z * b0 + dP[1].z * bx + dP[2].z * by);
             if (SMOOTH) {
-                const v3 ez = mk3(f.to_world[2] * f.s, f.to_world[6] * f.s, f.to_world[10] * f.s);
                 v3 N[3];
                 load_vn(f, a.vn, vi, vj, N);
                 const v3 B = sample_blend(N, b0, bx, by);
                 const float r = rsqrt_ieee(dot3(B, B));
-                const v3 n = B * r;
                 v3 dB = mk3(0.f, 0.f, 0.f);
                 const float w[3] = { b0, bx, by };
-#pragma unroll 1
-                for (int k = 0; k < 3; ++k) {
-                    hf_ring g;
-                    float dX, dR[6];
-                    ring_world(f, vi[k], vj[k], g, a.dh, &dX, dR);
-                    axpy3(w[k], vertex_normal_jvp(g, ez, dX, dR), dB);
-                }
-                const float pj = dot3(n, dB);
-                dn = mk3((dB.x - n.x * pj) * r, (dB.y - n.y * pj) * r, (dB.z - n.z * pj) * r);
+                vertex_normals_jvp(f, vi, vj, height_axis(f), w, a.dh, dB);
+                dn = dnormalize(B * r, r, dB);
             } else {
                 const v3 e0 = P[1] - P[0], e1 = P[2] - P[0], de0 = dP[1] - dP[0], de1 = dP[2] - dP[0];
                 const auto [n, r] = unit_normal(e0, e1);
-                const v3 c1 = cross3(de0, e1), c2 = cross3(e0, de1);
-                const v3 dN = mk3(c1.x + c2.x, c1.y + c2.y, c1.z + c2.z);
-                const float pj = dot3(n, dN);
-                dn = mk3((dN.x - n.x * pj) * r, (dN.y - n.y * pj) * r, (dN.z - n.z * pj) * r);
+                dn = dnormalize(n, r, face_normal_jvp(e0, e1, de0, de1));
             }
             if (f.flip) dn = neg3(dn);
         }
