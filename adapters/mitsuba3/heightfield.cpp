@@ -24,6 +24,8 @@
 //   forward mode of the above          dr.forward / render_forward over mesh.cpp:672-903 -> dr::CustomOp::forward -> hf_tangent
 //   surface_area / sample_position / pdf_position   src/render/mesh.cpp:401-432, 552-642 -> hf_set_area_sampling,
 //                                      hf_surface_area, hf_sample_position (+ dr::CustomOp -> _adjoint / _tangent)
+//   add_attribute / has_attribute / eval_attribute(_1/_3)   src/render/mesh.cpp:905-1004, include/mitsuba/render/mesh.h:399-440
+//                                      -> hf_eval_attribute (+ dr::CustomOp -> _adjoint / _tangent); unknown names: Shape's
 //   class / plugin registration        include/mitsuba/core/class.h:195-211, src/core/plugin.cpp:93-127
 #include <mitsuba/core/bitmap.h>
 #include <mitsuba/core/fwd.h>
@@ -40,6 +42,8 @@
 #include <hf.h> // include/hf.h of this repository
 
 #include <mutex>
+#include <string>
+#include <unordered_map>
 #include <vector>
 
 NAMESPACE_BEGIN(mitsuba)
@@ -236,6 +240,72 @@ struct HeightfieldSampleOp : dr::CustomOp<Float, Float /* p, n: 6 n packed rows 
     const char *name() const override { return "HeightfieldSample"; }
 };
 
+// Row layout of one staged eval_attribute call (floats): si.p, si.t, prim_index, active (u8), value, tangent of si.p;
+// then the attribute buffer, its gradient / tangent and the height gradient / tangent
+enum : size_t { AT_P = 0, AT_T = 3, AT_PRIM = 4, AT_ACTIVE = 5, AT_OUT = 6, AT_DP = 9, AT_ROWS = 12 };
+
+// ---------------------------------------------------------------------------------------------------------
+// Differentiable attribute value (Mesh::interpolate_attribute): primal = hf_eval_attribute, reverse mode =
+// hf_eval_attribute_adjoint, forward mode = hf_eval_attribute_tangent.  Inputs: the attribute buffer, si.p packed as
+// 3 n floats and the height tensor's array (a vertex attribute is attached to both, mesh.cpp:645-667); output: the
+// `size` rows of the value packed as size n floats.
+// ---------------------------------------------------------------------------------------------------------
+template <typename Float, typename Spectrum>
+struct HeightfieldAttributeOp
+    : dr::CustomOp<Float, Float /* size n rows */, Float /* attribute buffer */, Float /* p: 3 n */, Float /* heights */> {
+    using Base = dr::CustomOp<Float, Float, Float, Float, Float>;
+    using Shape_ = Heightfield<Float, Spectrum>;
+    struct Call {
+        const Shape_ *shape = nullptr;
+        int type = HF_ATTR_VERTEX;
+        uint32_t size = 1;
+        std::vector<float> attr, p, t; // host copies: the buffer (count * size), si.p (3 n), si.t (n)
+        std::vector<uint32_t> prim;
+        std::vector<uint8_t> active;
+        size_t n = 0;
+    };
+    static inline thread_local Call *pending = nullptr;
+    Call call;
+
+    Float eval(const Float &, const Float &, const Float &) override {
+        if (!pending) Throw("heightfield: HeightfieldAttributeOp evaluated outside eval_attribute");
+        call = std::move(*pending);
+        pending = nullptr;
+        return call.shape->attribute_primal(call);
+    }
+    void backward() override {
+        Float g = Base::grad_out(); // [size n]
+        dr::eval(g); dr::sync_thread();
+        std::vector<float> grad_rows(call.size * call.n), grad_attr(call.attr.size(), 0.f), grad_p(3 * call.n, 0.f),
+            grad_h((size_t) call.shape->width() * call.shape->height(), 0.f);
+        dr::store(grad_rows.data(), g);
+        call.shape->attribute_adjoint(call, grad_rows.data(), grad_attr.data(), grad_p.data(), grad_h.data());
+        if (Base::template grad_enabled_in<0>())
+            Base::template set_grad_in<0>(dr::load<Float>(grad_attr.data(), grad_attr.size()));
+        if (Base::template grad_enabled_in<1>())
+            Base::template set_grad_in<1>(dr::load<Float>(grad_p.data(), grad_p.size()));
+        if (Base::template grad_enabled_in<2>())
+            Base::template set_grad_in<2>(dr::load<Float>(grad_h.data(), grad_h.size()));
+    }
+    void forward() override {
+        const size_t texels = (size_t) call.shape->width() * call.shape->height();
+        std::vector<float> da, dp, dh, rows(call.size * call.n, 0.f);
+        auto take = [](const Float &g, size_t count, std::vector<float> &dst) {
+            if (dr::width(g) != count) return;
+            dr::eval(g); dr::sync_thread();
+            dst.resize(count);
+            dr::store(dst.data(), g);
+        };
+        if (Base::template grad_enabled_in<0>()) take(Base::template grad_in<0>(), call.attr.size(), da);
+        if (Base::template grad_enabled_in<1>()) take(Base::template grad_in<1>(), 3 * call.n, dp);
+        if (Base::template grad_enabled_in<2>()) take(Base::template grad_in<2>(), texels, dh);
+        call.shape->attribute_tangent(call, da.empty() ? nullptr : da.data(), dp.empty() ? nullptr : dp.data(),
+                                      dh.empty() ? nullptr : dh.data(), rows.data());
+        Base::set_grad_out(dr::load<Float>(rows.data(), rows.size()));
+    }
+    const char *name() const override { return "HeightfieldAttribute"; }
+};
+
 template <typename Float, typename Spectrum>
 class Heightfield final : public Shape<Float, Spectrum> {
 public:
@@ -244,6 +314,7 @@ public:
     using FloatStorage = DynamicBuffer<Float>;
     using SIOp = HeightfieldSIOp<Float, Spectrum>;
     using SampleOp = HeightfieldSampleOp<Float, Spectrum>;
+    using AttrOp = HeightfieldAttributeOp<Float, Spectrum>;
 
     Heightfield(const Properties &props) : Base(props) {
         m_max_height   = props.get<ScalarFloat>("max_height", 1.f);
@@ -269,6 +340,31 @@ public:
             Throw("heightfield: resolution must be at least 2x2 (got %ux%u)", m_width, m_height);
         size_t shape[3] = { m_height, m_width, 1 };
         m_heights = TensorXf((const float *) bitmap->data(), 3, shape); // TensorXf(data, 3, {H,W,C}): bitmap.cpp:262
+
+        // shape attributes: `vertex_*` ([H, W, C], one value per grid vertex) or `face_*` ([2 (H-1)(W-1), C], one per
+        // triangle) properties, a nested Bitmap (C = its channel count) or a TensorXf (C = its last dimension).  The
+        // Properties of Mitsuba 3.3 have no tensor type: a tensor comes as a Pointer property to a TensorXf.
+        for (const std::string &key : props.property_names()) {
+            if (key.rfind("vertex_", 0) != 0 && key.rfind("face_", 0) != 0) continue;
+            std::vector<InputFloat> data;
+            size_t channels = 1;
+            if (props.type(key) == Properties::Type::Object) {
+                ref<Bitmap> b = dynamic_cast<Bitmap *>(props.object(key).get());
+                if (!b) Throw("Property \"%s\" must be a Bitmap or a tensor.", key);
+                b = b->convert(b->pixel_format(), Struct::Type::Float32, false);
+                channels = b->channel_count();
+                const float *src = (const float *) b->data();
+                data.assign(src, src + b->pixel_count() * channels);
+            } else {
+                if (props.type(key) != Properties::Type::Pointer)
+                    Throw("Property \"%s\" must be a Bitmap or a tensor.", key);
+                const TensorXf &t = *(const TensorXf *) props.pointer(key);
+                channels = t.ndim() > 1 ? t.shape(t.ndim() - 1) : 1;
+                data.resize(dr::width(t.array()));
+                dr::store(data.data(), dr::detach(t.array()));
+            }
+            add_attribute(key, channels, data);
+        }
 
         update();
         initialize();
@@ -371,6 +467,8 @@ public:
         callback->put_parameter("heightfield", m_heights, ParamFlags::Differentiable | ParamFlags::Discontinuous);
         callback->put_parameter("to_world", *m_to_world.ptr(), +ParamFlags::NonDifferentiable);
         callback->put_parameter("max_height", m_max_height, +ParamFlags::NonDifferentiable);
+        for (auto &[name, attribute] : m_attributes) // mesh.cpp:74-76: every attribute is shown as differentiable
+            callback->put_parameter(name, attribute.buf, +ParamFlags::Differentiable);
     }
 
     void parameters_changed(const std::vector<std::string> &keys) override {
@@ -384,7 +482,84 @@ public:
             m_to_world = m_to_world.value();
             update();
         }
+        for (auto &[name, attribute] : m_attributes) { // mesh.cpp:103-110: an attribute of the wrong size is reset
+            size_t expected = attribute.size * attribute_count(attribute.type);
+            if (dr::width(attribute.buf) != expected)
+                attribute.buf = dr::zeros<FloatStorage>(expected);
+        }
         Base::parameters_changed();
+    }
+
+    // =========================================================================================================
+    //  Shape attributes (Mesh::add_attribute / has_attribute / eval_attribute*, mesh.cpp:905-1004)
+    // =========================================================================================================
+    size_t attribute_count(int type) const {
+        return type == HF_ATTR_VERTEX ? (size_t) m_width * m_height : 2 * (size_t) (m_width - 1) * (m_height - 1);
+    }
+
+    void add_attribute(const std::string &name, size_t dim, const std::vector<InputFloat> &data) {
+        if (m_attributes.find(name) != m_attributes.end())
+            Throw("add_attribute(): attribute %s already exists.", name.c_str());
+        bool is_vertex_attr = name.find("vertex_") == 0, is_face_attr = name.find("face_") == 0;
+        if (!is_vertex_attr && !is_face_attr)
+            Throw("add_attribute(): attribute name must start with either \"vertex_\" of \"face_\".");
+        int type = is_vertex_attr ? HF_ATTR_VERTEX : HF_ATTR_FACE;
+        size_t count = attribute_count(type);
+        if (data.size() != count * dim) // (a map of another resolution would be read with the wrong stride)
+            Throw("add_attribute(): attribute %s needs %zu values, got %zu.", name.c_str(), count * dim, data.size());
+        m_attributes.insert({ name, { dim, type, dr::load<FloatStorage>(data.data(), count * dim) } });
+    }
+
+    Mask has_attribute(const std::string &name, Mask active) const override {
+        if (m_attributes.find(name) == m_attributes.end())
+            return Base::has_attribute(name, active);
+        return true;
+    }
+
+    UnpolarizedSpectrum eval_attribute(const std::string &name, const SurfaceInteraction3f &si, Mask active) const override {
+        const auto it = m_attributes.find(name);
+        if (it == m_attributes.end())
+            return Base::eval_attribute(name, si, active);
+        const HfAttribute &attr = it->second;
+        if (attr.size == 1) {
+            Float v = eval_attribute_rows(attr, si, active);
+            return UnpolarizedSpectrum(v); // RGB: the value on every channel
+        } else if (attr.size == 3) {
+            Float rows = eval_attribute_rows(attr, si, active);
+            Color3f c = channels3(rows, dr::width(si.p));
+            if constexpr (is_monochromatic_v<Spectrum>)
+                return luminance(c);
+            else
+                return c;
+        }
+        if constexpr (dr::is_jit_v<Float>)
+            return 0.f;
+        else
+            Throw("eval_attribute(): Attribute \"%s\" requested but had size %u.", name, (uint32_t) attr.size);
+    }
+
+    Float eval_attribute_1(const std::string &name, const SurfaceInteraction3f &si, Mask active) const override {
+        const auto it = m_attributes.find(name);
+        if (it == m_attributes.end())
+            return Base::eval_attribute_1(name, si, active);
+        if (it->second.size == 1)
+            return eval_attribute_rows(it->second, si, active);
+        if constexpr (dr::is_jit_v<Float>)
+            return 0.f;
+        else
+            Throw("eval_attribute_1(): Attribute \"%s\" requested but had size %u.", name, (uint32_t) it->second.size);
+    }
+
+    Color3f eval_attribute_3(const std::string &name, const SurfaceInteraction3f &si, Mask active) const override {
+        const auto it = m_attributes.find(name);
+        if (it == m_attributes.end())
+            return Base::eval_attribute_3(name, si, active);
+        if (it->second.size == 3)
+            return channels3(eval_attribute_rows(it->second, si, active), dr::width(si.p));
+        if constexpr (dr::is_jit_v<Float>)
+            return 0.f;
+        else
+            Throw("eval_attribute_3(): Attribute \"%s\" requested but had size %u.", name, (uint32_t) it->second.size);
     }
 
     bool parameters_grad_enabled() const override { return dr::grad_enabled(m_heights); }
@@ -698,7 +873,103 @@ public:
     }
 
     MI_DECLARE_CLASS()
+
+    // ---- staged calls of the attribute op (HeightfieldAttributeOp): host rows -> device -> hf_eval_attribute* ------
+    // device block: AT_ROWS rows of n floats, then the attribute buffer and a second buffer of its size (gradient or
+    // tangent), then one height texture (gradient or tangent)
+    float *upload_attribute_call(const typename AttrOp::Call &op, float *&attr_dev, float *&attr2_dev, float *&tex_dev) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        float *dev = m_stage.reserve(1, AT_ROWS * n + 2 * op.attr.size() + texels);
+        attr_dev = dev + AT_ROWS * n; attr2_dev = attr_dev + op.attr.size(); tex_dev = attr2_dev + op.attr.size();
+        m_stage.upload(dev + AT_P * n, op.p.data(), 3 * n);
+        m_stage.upload(dev + AT_T * n, op.t.data(), n);
+        m_stage.upload(dev + AT_PRIM * n, (const float *) op.prim.data(), n);
+        HfStaging::hip_check(hipMemcpyAsync(dev + AT_ACTIVE * n, op.active.data(), n, hipMemcpyHostToDevice, m_stage.stream()));
+        m_stage.upload(attr_dev, op.attr.data(), op.attr.size());
+        return dev;
+    }
+    Float attribute_primal(const typename AttrOp::Call &op) const {
+        size_t n = op.n;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *attr_dev, *attr2_dev, *tex_dev;
+        float *dev = upload_attribute_call(op, attr_dev, attr2_dev, tex_dev);
+        const float *p[3] = { dev + AT_P * n, dev + (AT_P + 1) * n, dev + (AT_P + 2) * n };
+        float *out[3] = { dev + AT_OUT * n, dev + (AT_OUT + 1) * n, dev + (AT_OUT + 2) * n };
+        hf_check(hf_eval_attribute(m_hf, n, op.type, op.size, attr_dev, (const uint32_t *) (dev + AT_PRIM * n), p,
+                                   dev + AT_T * n, (const uint8_t *) (dev + AT_ACTIVE * n), out, m_stage.stream()));
+        std::vector<float> host(op.size * n);
+        m_stage.download(host.data(), dev + AT_OUT * n, host.size());
+        m_stage.sync();
+        return dr::load<Float>(host.data(), host.size());
+    }
+    void attribute_adjoint(const typename AttrOp::Call &op, const float *grad_rows /* host, size n */, float *grad_attr,
+                           float *grad_p, float *grad_h) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *attr_dev, *gattr_dev, *gh_dev;
+        float *dev = upload_attribute_call(op, attr_dev, gattr_dev, gh_dev);
+        m_stage.upload(dev + AT_OUT * n, grad_rows, op.size * n);
+        HfStaging::hip_check(hipMemsetAsync(gattr_dev, 0, op.attr.size() * sizeof(float), m_stage.stream()));
+        HfStaging::hip_check(hipMemsetAsync(gh_dev, 0, texels * sizeof(float), m_stage.stream()));
+        const float *p[3] = { dev + AT_P * n, dev + (AT_P + 1) * n, dev + (AT_P + 2) * n };
+        const float *g[3] = { dev + AT_OUT * n, dev + (AT_OUT + 1) * n, dev + (AT_OUT + 2) * n };
+        float *gp[3] = { dev + AT_DP * n, dev + (AT_DP + 1) * n, dev + (AT_DP + 2) * n };
+        hf_check(hf_eval_attribute_adjoint(m_hf, n, op.type, op.size, attr_dev, (const uint32_t *) (dev + AT_PRIM * n), p,
+                                           dev + AT_T * n, (const uint8_t *) (dev + AT_ACTIVE * n), g, gattr_dev, gp,
+                                           gh_dev, m_stage.stream()));
+        m_stage.download(grad_attr, gattr_dev, op.attr.size());
+        if (op.type == HF_ATTR_VERTEX) {
+            m_stage.download(grad_p, dev + AT_DP * n, 3 * n);
+            m_stage.download(grad_h, gh_dev, texels);
+        }
+        m_stage.sync();
+    }
+    void attribute_tangent(const typename AttrOp::Call &op, const float *dattr, const float *dp, const float *dheights,
+                           float *rows /* host, size n */) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *attr_dev, *da_dev, *dh_dev;
+        float *dev = upload_attribute_call(op, attr_dev, da_dev, dh_dev);
+        if (dattr) m_stage.upload(da_dev, dattr, op.attr.size());
+        if (dp) m_stage.upload(dev + AT_DP * n, dp, 3 * n);
+        if (dheights) m_stage.upload(dh_dev, dheights, texels);
+        const float *p[3] = { dev + AT_P * n, dev + (AT_P + 1) * n, dev + (AT_P + 2) * n };
+        const float *dpr[3] = { dev + AT_DP * n, dev + (AT_DP + 1) * n, dev + (AT_DP + 2) * n };
+        float *out[3] = { dev + AT_OUT * n, dev + (AT_OUT + 1) * n, dev + (AT_OUT + 2) * n };
+        hf_check(hf_eval_attribute_tangent(m_hf, n, op.type, op.size, attr_dev, (const uint32_t *) (dev + AT_PRIM * n), p,
+                                           dev + AT_T * n, (const uint8_t *) (dev + AT_ACTIVE * n),
+                                           dattr ? da_dev : nullptr, dp ? dpr : nullptr, dheights ? dh_dev : nullptr,
+                                           out, m_stage.stream()));
+        m_stage.download(rows, dev + AT_OUT * n, op.size * n);
+        m_stage.sync();
+    }
+
 private:
+    struct HfAttribute {
+        size_t size;
+        int type; // HF_ATTR_VERTEX / HF_ATTR_FACE
+        FloatStorage buf;
+    };
+    // the `size` rows of an attribute's value at si (size n floats), attached to the buffer, si.p and the heights
+    Float eval_attribute_rows(const HfAttribute &attr, const SurfaceInteraction3f &si, Mask active) const {
+        size_t n = dr::width(si.p);
+        typename AttrOp::Call call;
+        call.shape = this; call.type = attr.type; call.size = (uint32_t) attr.size; call.n = n;
+        call.attr  = to_host(Float(attr.buf), dr::width(attr.buf));
+        call.p     = to_host(pack3(si.p, n), 3 * n);
+        call.t     = to_host(si.t, n);
+        call.prim  = to_host_u32(si.prim_index, n);
+        call.active = to_host_mask(active, n);
+        AttrOp::pending = &call;
+        Float rows = dr::custom<AttrOp>(Float(attr.buf), pack3(si.p, n), m_heights.array());
+        AttrOp::pending = nullptr;
+        return rows;
+    }
+    static Color3f channels3(const Float &rows, size_t n) {
+        auto row = [&](size_t k) { return dr::gather<Float>(rows, dr::arange<UInt32>((uint32_t) n) + (uint32_t) (k * n)); };
+        return Color3f(row(0), row(1), row(2));
+    }
+
     // ---- marshalling helpers -----------------------------------------------------------------------------------
     static void store_3x4(float out[12], const ScalarMatrix4f &m) {
         for (int r = 0; r < 3; ++r)

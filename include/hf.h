@@ -44,7 +44,8 @@
  *     Not capturable: hf_create / hf_destroy, hf_set_heights_host, hf_bbox, hf_get_mip and the host-pointer packet
  *     entry (they synchronise); hf_set_face_normals and hf_set_area_sampling (refused with HF_EINVAL), hf_surface_area
  *     and, with smooth shading or area sampling, hf_set_transform (they synchronise).  hf_sample_position and its
- *     adjoint / tangent are capturable like the other wavefront entry points (no scratch block).
+ *     adjoint / tangent are capturable like the other wavefront entry points (no scratch block), and so are
+ *     hf_eval_attribute and its adjoint / tangent (the attribute buffer is the caller's).
  */
 #ifndef HF_H
 #define HF_H
@@ -427,6 +428,48 @@ int hf_sample_position_adjoint(const hf_field_t *hf, size_t n, const uint32_t *p
 int hf_sample_position_tangent(const hf_field_t *hf, size_t n, const uint32_t *prim_index, const float *const b[2],
                                const uint8_t *active, const float *dheights, float *const dp[3], float *const dn[3],
                                hf_stream_t stream);
+
+/* ---- shape attributes: the attribute side of Shape (has_attribute, eval_attribute, eval_attribute_1 / _3) -------- */
+
+/* Where an attribute lives (Mesh's MeshAttributeType, include/mitsuba/render/mesh.h): HF_ATTR_VERTEX, one value per grid
+ * vertex, count = width*height in the heights' row-major order (vertex (i, j) = i*width + j); HF_ATTR_FACE, one value per
+ * triangle, count = 2*(width-1)*(height-1) in prim_index order. */
+enum { HF_ATTR_VERTEX = 0, HF_ATTR_FACE = 1 };
+
+/* Replaces: Mesh::eval_attribute / eval_attribute_1 / eval_attribute_3 (src/render/mesh.cpp:944-1004) through
+ * Mesh::interpolate_attribute (include/mitsuba/render/mesh.h:399-440) for n surface interactions, RGB variants (no
+ * spectral upsampling).  attr is the caller's device buffer of count*size floats, interleaved [count][size] like Mesh's
+ * FloatStorage (the attribute is a parameter, not handle state); size is 1 or 3.  Vertex attributes: the weights
+ * (w, u, v) = Mesh::barycentric_coordinates (mesh.cpp:645-667), the least-squares solve from si.p (p: 3 device arrays
+ * of n floats) and the world-space vertices of prim_index in the reference's operation order, then
+ * fmadd(v0, w, fmadd(v1, u, v2 v)); face attributes: the row of prim_index (p is not read and may be NULL).  t (si.t,
+ * may be NULL = every active lane is a hit) and active (NULL = all) select the lanes: misses (t = +inf), inactive lanes
+ * and indices past the last triangle give exactly 0.  out: size device arrays of n floats, overwritten.  HF_EINVAL for a
+ * bad type or size, a NULL attr, prim_index or output row, and p == NULL with HF_ATTR_VERTEX.  Capturable: no scratch
+ * block, no allocation, no synchronisation; re-entrant on a const handle. */
+int hf_eval_attribute(const hf_field_t *hf, size_t n, int type, uint32_t size, const float *attr,
+                      const uint32_t *prim_index, const float *const p[3], const float *t, const uint8_t *active,
+                      float *const out[], hf_stream_t stream);
+/* Reverse mode of hf_eval_attribute (Dr.Jit AD through interpolate_attribute): for the upstream gradients grad_out
+ * (size device arrays of n floats), accumulates dL/dattr into grad_attr (count*size floats, interleaved like attr)
+ * and, for vertex attributes, writes dL/dp into grad_p (3 arrays of n floats, overwritten; zero for face attributes
+ * and for lanes without a hit) and accumulates dL/dheight into grad_heights (width*height floats) through the three
+ * vertices (vertex_position is attached to the heights whatever the ray flags; dP/dh = max_height * to_world[:, 2]).
+ * Float atomics; for vertex attributes pre-summed per wave in an LDS tile first.  Face attributes carry no geometric
+ * derivative.  Any of grad_attr, grad_p and grad_heights may be NULL (not wanted).  Inputs and errors as
+ * hf_eval_attribute; capturable. */
+int hf_eval_attribute_adjoint(const hf_field_t *hf, size_t n, int type, uint32_t size, const float *attr,
+                              const uint32_t *prim_index, const float *const p[3], const float *t, const uint8_t *active,
+                              const float *const grad_out[], float *grad_attr, float *const grad_p[3],
+                              float *grad_heights, hf_stream_t stream);
+/* Forward mode of hf_eval_attribute: for the tangents dattr (count*size floats, interleaved), dp (3 arrays of n floats,
+ * the tangent of si.p) and dheights (width*height floats), each NULL = zero, the tangent of the value in dout (size
+ * arrays of n floats, overwritten; 0 for lanes without a hit).  No atomics: bitwise the same from launch to launch.
+ * Inputs and errors as hf_eval_attribute; capturable. */
+int hf_eval_attribute_tangent(const hf_field_t *hf, size_t n, int type, uint32_t size, const float *attr,
+                              const uint32_t *prim_index, const float *const p[3], const float *t, const uint8_t *active,
+                              const float *dattr, const float *const dp[3], const float *dheights, float *const dout[],
+                              hf_stream_t stream);
 
 /* ---- next row: minimal direct lighting on the wavefront ------- */
 

@@ -6,6 +6,7 @@ import os
 from . import build as _build
 
 HF_OK, HF_EINVAL, HF_EDEVICE, HF_ENOMEM, HF_EFLAGS = 0, 1, 2, 3, 4
+HF_ATTR_VERTEX, HF_ATTR_FACE = 0, 1
 
 _fp = C.c_void_p  # device pointers
 
@@ -79,6 +80,12 @@ SYMBOLS = {
                                              C.POINTER(_fp * 3), _fp, C.c_void_p]),
     "hf_sample_position_tangent": (C.c_int, [C.c_void_p, C.c_size_t, _fp, C.POINTER(_fp * 2), _fp, _fp, C.POINTER(_fp * 3),
                                              C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_eval_attribute": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, _fp, _fp, C.POINTER(_fp * 3), _fp, _fp,
+                                    C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_eval_attribute_adjoint": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, _fp, _fp, C.POINTER(_fp * 3), _fp,
+                                            _fp, C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    "hf_eval_attribute_tangent": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, _fp, _fp, C.POINTER(_fp * 3), _fp,
+                                            _fp, _fp, C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 3), C.c_void_p]),
     "hf_bbox": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "hf_heights_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "hf_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -539,6 +539,79 @@ extern "C" int hf_sample_position_tangent(const hf_field_t *hf, size_t n, const 
     return HF_OK;
 }
 
+// ---- shape attributes: what the three entry points share ----
+static bool all_rows(const float *const *r, uint32_t size) {
+    if (!r) return false;
+    for (uint32_t c = 0; c < size; ++c)
+        if (!r[c]) return false;
+    return true;
+}
+static int attr_args(const char *fn, const hf_field_t *hf, size_t n, int type, uint32_t size, const float *attr,
+                     const uint32_t *prim_index, const float *const p[3], const float *t, const uint8_t *active,
+                     hf_attr_args &a) {
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    if (type != HF_ATTR_VERTEX && type != HF_ATTR_FACE) return fail(HF_EINVAL, "%s: bad attribute type %d", fn, type);
+    if (size != 1 && size != 3) return fail(HF_EINVAL, "%s: attribute size %u (1 or 3)", fn, size);
+    if (!attr || !prim_index) return fail(HF_EINVAL, "%s: NULL attr / prim_index", fn);
+    if (type == HF_ATTR_VERTEX && !all3(p)) return fail(HF_EINVAL, "%s: NULL p (vertex attributes read si.p)", fn);
+    a = hf_attr_args{};
+    a.f = hf->dev; a.n = n; a.attr = attr; a.prim = prim_index; a.t = t; a.active = active;
+    if (type == HF_ATTR_VERTEX)
+        for (int c = 0; c < 3; ++c) a.p[c] = p[c];
+    return n ? check_device(fn, hf) : HF_OK;
+}
+
+extern "C" int hf_eval_attribute(const hf_field_t *hf, size_t n, int type, uint32_t size, const float *attr,
+                                 const uint32_t *prim_index, const float *const p[3], const float *t,
+                                 const uint8_t *active, float *const out[], hf_stream_t stream) {
+    hf_attr_args a;
+    int rc = attr_args("hf_eval_attribute", hf, n, type, size, attr, prim_index, p, t, active, a);
+    if (rc) return rc;
+    if (!all_rows(out, size)) return fail(HF_EINVAL, "hf_eval_attribute: NULL output row");
+    for (uint32_t c = 0; c < size; ++c) a.out[c] = out[c];
+    hf_launch_attribute(0, type, size, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_eval_attribute_adjoint(const hf_field_t *hf, size_t n, int type, uint32_t size, const float *attr,
+                                         const uint32_t *prim_index, const float *const p[3], const float *t,
+                                         const uint8_t *active, const float *const grad_out[], float *grad_attr,
+                                         float *const grad_p[3], float *grad_heights, hf_stream_t stream) {
+    hf_attr_args a;
+    int rc = attr_args("hf_eval_attribute_adjoint", hf, n, type, size, attr, prim_index, p, t, active, a);
+    if (rc) return rc;
+    if (!all_rows(grad_out, size)) return fail(HF_EINVAL, "hf_eval_attribute_adjoint: NULL grad_out row");
+    if (grad_p && !all3(grad_p)) return fail(HF_EINVAL, "hf_eval_attribute_adjoint: NULL grad_p array");
+    for (uint32_t c = 0; c < size; ++c) a.g[c] = grad_out[c];
+    a.grad_attr = grad_attr;
+    if (grad_p)
+        for (int c = 0; c < 3; ++c) a.grad_p[c] = grad_p[c];
+    a.grad_h = type == HF_ATTR_VERTEX ? grad_heights : nullptr; // (face attributes carry no geometric derivative)
+    if (!a.grad_attr && !a.grad_p[0] && !a.grad_h) return HF_OK;
+    hf_launch_attribute(1, type, size, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_eval_attribute_tangent(const hf_field_t *hf, size_t n, int type, uint32_t size, const float *attr,
+                                         const uint32_t *prim_index, const float *const p[3], const float *t,
+                                         const uint8_t *active, const float *dattr, const float *const dp[3],
+                                         const float *dheights, float *const dout[], hf_stream_t stream) {
+    hf_attr_args a;
+    int rc = attr_args("hf_eval_attribute_tangent", hf, n, type, size, attr, prim_index, p, t, active, a);
+    if (rc) return rc;
+    if (!all_rows(dout, size)) return fail(HF_EINVAL, "hf_eval_attribute_tangent: NULL dout row");
+    if (dp && !all3(dp)) return fail(HF_EINVAL, "hf_eval_attribute_tangent: NULL dp array");
+    for (uint32_t c = 0; c < size; ++c) a.dout[c] = dout[c];
+    a.dattr = dattr;
+    if (dp && type == HF_ATTR_VERTEX)
+        for (int c = 0; c < 3; ++c) a.dp[c] = dp[c];
+    a.dh = dheights;
+    hf_launch_attribute(2, type, size, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
 
 extern "C" int hf_heights_device(hf_field_t *hf, const float **out) {
     if (!hf || !out) return fail(HF_EINVAL, "hf_heights_device: NULL argument");

@@ -283,6 +283,58 @@ __device__ __forceinline__ v3 bary_point(const v3 P[3], float b0, float b1, floa
                __builtin_fmaf(P[0].z, b0, __builtin_fmaf(P[1].z, b1, P[2].z * b2)));
 }
 
+// ---- Shape attributes (hf_eval_attribute): Mesh::barycentric_coordinates (mesh.cpp:645-667) and its two derivatives.
+// The weights (w, u, v) of P0, P1, P2 are the least-squares solution of p - P0 = u du + v dv with du = P1 - P0,
+// dv = P2 - P0, in the reference's operation order. ----
+struct hf_bary {
+    v3 rel, du, dv;        // p - P0, P1 - P0, P2 - P0
+    float a11, a12, a22, inv_det;
+    float w, u, v;
+};
+__device__ __forceinline__ hf_bary bary_coords(v3 p, const v3 P[3]) {
+    hf_bary b;
+    b.rel = p - P[0]; b.du = P[1] - P[0]; b.dv = P[2] - P[0];
+    const float b1 = dot3(b.du, b.rel), b2 = dot3(b.dv, b.rel);
+    b.a11 = dot3(b.du, b.du); b.a12 = dot3(b.du, b.dv); b.a22 = dot3(b.dv, b.dv);
+    b.inv_det = rcp_ieee(b.a11 * b.a22 - b.a12 * b.a12);
+    b.u = __builtin_fmaf(b.a22, b1, -(b.a12 * b2)) * b.inv_det;  // fmsub(a22, b1, a12 b2)
+    b.v = __builtin_fmaf(-b.a12, b1, b.a11 * b2) * b.inv_det;    // fnmadd(a12, b1, a11 b2)
+    b.w = 1.f - b.u - b.v;
+    return b;
+}
+// Mesh::interpolate_attribute (mesh.h:409-437): fmadd(v0, w, fmadd(v1, u, v2 v))
+__device__ __forceinline__ float bary_interp(const hf_bary &b, float a0, float a1, float a2) {
+    return __builtin_fmaf(a0, b.w, __builtin_fmaf(a1, b.u, a2 * b.v));
+}
+// With M = [[a11, a12], [a12, a22]] and the residual r = rel - u du - v dv (zero for p in the triangle's plane), the
+// derivatives of (u, v) are d(u, v) = M^-1 (<du, z> + <ddu, r>, <dv, z> + <ddv, r>), z = drel - u ddu - v ddv.
+__device__ __forceinline__ v3 bary_residual(const hf_bary &b) {
+    return mk3(b.rel.x - b.u * b.du.x - b.v * b.dv.x, b.rel.y - b.u * b.du.y - b.v * b.dv.y,
+               b.rel.z - b.u * b.du.z - b.v * b.dv.z);
+}
+// JVP: the tangents (du, dv) of (u, v) for the tangents dp of p and dP[k] of the vertices
+__device__ __forceinline__ void bary_coords_jvp(const hf_bary &b, v3 dp, const v3 dP[3], float &du_, float &dv_) {
+    const v3 r = bary_residual(b);
+    const v3 ddu = dP[1] - dP[0], ddv = dP[2] - dP[0];
+    const v3 drel = dp - dP[0];
+    const v3 z = mk3(drel.x - b.u * ddu.x - b.v * ddv.x, drel.y - b.u * ddu.y - b.v * ddv.y,
+                     drel.z - b.u * ddu.z - b.v * ddv.z);
+    const float r1 = dot3(b.du, z) + dot3(ddu, r), r2 = dot3(b.dv, z) + dot3(ddv, r);
+    du_ = (b.a22 * r1 - b.a12 * r2) * b.inv_det;
+    dv_ = (b.a11 * r2 - b.a12 * r1) * b.inv_det;
+}
+// VJP, its transpose: for the gradients (gu, gv) of (u, v), the gradients of p (gp) and of the vertices (gP[k]).
+// With (g1, g2) = M^-1 (gu, gv) and q = g1 du + g2 dv: gp = q, gP1 = g1 r - u q, gP2 = g2 r - v q, gP0 = -(gp + gP1 + gP2)
+__device__ __forceinline__ void bary_coords_vjp(const hf_bary &b, float gu, float gv, v3 &gp, v3 gP[3]) {
+    const v3 r = bary_residual(b);
+    const float g1 = (b.a22 * gu - b.a12 * gv) * b.inv_det, g2 = (b.a11 * gv - b.a12 * gu) * b.inv_det;
+    const v3 q = mk3(g1 * b.du.x + g2 * b.dv.x, g1 * b.du.y + g2 * b.dv.y, g1 * b.du.z + g2 * b.dv.z);
+    gp = q;
+    gP[1] = mk3(g1 * r.x - b.u * q.x, g1 * r.y - b.u * q.y, g1 * r.z - b.u * q.z);
+    gP[2] = mk3(g2 * r.x - b.v * q.x, g2 * r.y - b.v * q.y, g2 * r.z - b.v * q.z);
+    gP[0] = mk3(-(q.x + gP[1].x + gP[2].x), -(q.y + gP[1].y + gP[2].y), -(q.z + gP[1].z + gP[2].z));
+}
+
 // FollowShape: t re-derived from the glued point p, tt = sqrt(|p - o|^2 / |d|^2) (mesh.cpp:748-752)
 struct hf_follow {
     v3 po;    // p - o

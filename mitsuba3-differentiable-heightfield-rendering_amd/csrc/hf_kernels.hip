@@ -14,6 +14,8 @@
 //   hf_direct_kernel / hf_direct_adjoint_kernel, hf_adam_kernel     next rows
 //   hf_area_reduce / _scan_tiles / _cdf_kernel     area sampling: the triangle-area CDF (hf_set_area_sampling)
 //   hf_sample_position / _adjoint / _tangent_kernel  Mesh::sample_position and its two derivatives
+//   hf_attr / _tangent_kernel<TYPE, SIZE>, hf_attr_adjoint_tile / _face_adjoint_kernel<SIZE>  shape attributes:
+//        Mesh::eval_attribute and its two derivatives
 //
 // Traversal = a walk of the implicit quadtree over the cells (the grid is mirrored so the ray direction is
 // non-negative on both axes: "order space").  One visit of an inner node fetches its record -- a plane through
@@ -1933,7 +1935,8 @@ __device__ __forceinline__ void tile_anchor(uint64_t m, const int (&vr)[3], cons
 }
 // one vertex's contribution g at texel (r, c).  (Per vertex, with the loop over the three at the call site: the
 // lane's vr / vc / gh arrays passed by reference are promoted to registers later and that reorders the adjoint's code)
-template <int TILE>
+// STRIDE: floats per texel of the global buffer (one channel of an interleaved attribute: grad_h = its base + channel)
+template <int TILE, int STRIDE = 1>
 __device__ __forceinline__ void tile_add(float *acc, int ar, int ac, int r, int c, float g, float *grad_h, int W,
                                          hf_tile_rows<TILE> &rows) {
     const int rr = r - ar, cc = c - ac;
@@ -1941,11 +1944,12 @@ __device__ __forceinline__ void tile_add(float *acc, int ar, int ac, int r, int 
         atomicAdd(acc + rr * TILE + cc, g);
         rows |= (hf_tile_rows<TILE>) 1 << rr;
     } else {
-        atomicAdd(grad_h + (size_t) r * W + c, g);
+        if constexpr (STRIDE == 1) atomicAdd(grad_h + (size_t) r * W + c, g);
+        else atomicAdd(grad_h + ((size_t) r * W + c) * STRIDE, g);
     }
 }
 // (rows: this lane's mask; ORed over the wave here)
-template <int TILE>
+template <int TILE, int STRIDE = 1>
 __device__ __forceinline__ void tile_flush(float *acc, int ar, int ac, hf_tile_rows<TILE> rows, float *grad_h, int W, int lane) {
     constexpr int R = 64 / TILE; // tile rows per wave-instruction
     rows = wave_or(rows);
@@ -1957,7 +1961,8 @@ __device__ __forceinline__ void tile_flush(float *acc, int ar, int ac, hf_tile_r
         const float v = acc[k];
         if (v != 0.f) {
             const int rr = ar + k / TILE, cc = ac + k % TILE;
-            atomicAdd(grad_h + (size_t) rr * W + cc, v);
+            if constexpr (STRIDE == 1) atomicAdd(grad_h + (size_t) rr * W + cc, v);
+            else atomicAdd(grad_h + ((size_t) rr * W + cc) * STRIDE, v);
             acc[k] = 0.f;
         }
     }
@@ -3393,4 +3398,215 @@ void hf_launch_sample_position_tangent(const hf_dev_field &f, size_t n, const ui
     for (int c = 0; c < 3; ++c) { a.dp[c] = dp ? dp[c] : nullptr; a.dn[c] = dn ? dn[c] : nullptr; }
     hipLaunchKernelGGL(vn ? hf_sample_tangent_kernel<true> : hf_sample_tangent_kernel<false>, dim3(grid_for(n)),
                        dim3(HF_BLOCK), 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
+// Shape attributes (hf_eval_attribute / _adjoint / _tangent): Mesh::interpolate_attribute (mesh.h:399-440) on the
+// caller's interleaved [count][SIZE] buffer, one lane per ray.  TYPE HF_ATTR_VERTEX: the barycentric blend of the three
+// vertices' values with the weights of bary_coords (hf_device.h) at si.p; HF_ATTR_FACE: the row of si.prim_index.
+// One instantiation per (TYPE, SIZE): no per-lane branch on either.
+// ---------------------------------------------------------------------------------
+// the hit of lane i: false for inactive lanes, t = +inf and out-of-range indices (every lane reads active and t)
+__device__ __forceinline__ bool attr_hit(const hf_attr_args &a, size_t i, uint32_t &prim) {
+    bool ok = !a.active || a.active[i] != 0;
+    if (a.t) ok = ok && a.t[i] != __builtin_inff();
+    if (!ok) return false;
+    prim = a.prim[i];
+    return prim < 2u * (uint32_t) (a.f.W - 1) * (uint32_t) (a.f.H - 1);
+}
+// the SIZE values of the three vertices of a hit (vertex ids from prim_world)
+template <int SIZE>
+__device__ __forceinline__ void attr_vertices(const float *buf, const hf_dev_field &f, const int vi[3], const int vj[3],
+                                              float A[3][SIZE]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const size_t base = ((size_t) vi[k] * f.W + vj[k]) * SIZE;
+#pragma unroll
+        for (int c = 0; c < SIZE; ++c) A[k][c] = buf[base + c];
+    }
+}
+
+template <int TYPE, int SIZE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_attr_kernel(hf_attr_args a) {
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
+        float r[SIZE];
+#pragma unroll
+        for (int c = 0; c < SIZE; ++c) r[c] = 0.f;
+        uint32_t prim;
+        if (attr_hit(a, i, prim)) {
+            if constexpr (TYPE == HF_ATTR_FACE) {
+#pragma unroll
+                for (int c = 0; c < SIZE; ++c) r[c] = a.attr[(size_t) prim * SIZE + c];
+            } else {
+                v3 P[3];
+                float U[3], V[3], A[3][SIZE];
+                int vi[3], vj[3];
+                prim_world(a.f, prim, P, U, V, vi, vj);
+                attr_vertices<SIZE>(a.attr, a.f, vi, vj, A);
+                const hf_bary b = bary_coords(mk3(a.p[0][i], a.p[1][i], a.p[2][i]), P);
+#pragma unroll
+                for (int c = 0; c < SIZE; ++c) r[c] = bary_interp(b, A[0][c], A[1][c], A[2][c]);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < SIZE; ++c) a.out[c][i] = r[c];
+    }
+}
+
+// Reverse mode of one vertex-attribute hit, for its upstream gradient g: the vertices (vi, vj), the weights wk = (w, u, v)
+// (dL/dattr of vertex k, channel c = g[c] wk[k]), dL/dp (gp) and the three height gradients gh (when grad_p or grad_h is
+// wanted; zero otherwise)
+template <int SIZE>
+__device__ __forceinline__ void attr_vertex_vjp(const hf_attr_args &a, size_t i, uint32_t prim, const float g[SIZE],
+                                                int vi[3], int vj[3], float wk[3], float gh[3], v3 &gp) {
+    const hf_dev_field &f = a.f;
+    v3 P[3];
+    float U[3], V[3];
+    prim_world(f, prim, P, U, V, vi, vj);
+    const hf_bary b = bary_coords(mk3(a.p[0][i], a.p[1][i], a.p[2][i]), P);
+    wk[0] = b.w; wk[1] = b.u; wk[2] = b.v;
+    gh[0] = gh[1] = gh[2] = 0.f;
+    if (a.grad_p[0] || a.grad_h) {
+        float A[3][SIZE];
+        attr_vertices<SIZE>(a.attr, f, vi, vj, A);
+        float gw = 0.f, gu = 0.f, gv = 0.f; // dL/dw, dL/du, dL/dv
+#pragma unroll
+        for (int c = 0; c < SIZE; ++c) { gw += g[c] * A[0][c]; gu += g[c] * A[1][c]; gv += g[c] * A[2][c]; }
+        v3 gP[3];
+        bary_coords_vjp(b, gu - gw, gv - gw, gp, gP); // (w = 1 - u - v)
+        const v3 ez = height_axis(f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gh[k] = dot3(ez, gP[k]);
+    }
+}
+
+// Reverse mode of a face attribute: dL/dattr into the row of prim_index, plain float atomics (a face attribute carries no
+// geometric derivative; dL/dp is zero)
+template <int SIZE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_attr_face_adjoint_kernel(hf_attr_args a) {
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
+        uint32_t prim;
+        if (a.grad_attr && attr_hit(a, i, prim)) {
+#pragma unroll
+            for (int c = 0; c < SIZE; ++c) atomicAdd(a.grad_attr + (size_t) prim * SIZE + c, a.g[c][i]);
+        }
+        if (a.grad_p[0]) { a.grad_p[0][i] = 0.f; a.grad_p[1][i] = 0.f; a.grad_p[2][i] = 0.f; }
+    }
+}
+
+// Reverse mode of a vertex attribute: dL/dattr, dL/dheight through the per-wave LDS scatter tile of hf_adjoint_kernel
+// (tile_anchor / tile_add / tile_flush) and dL/dp (rows, overwritten).  One TILE x TILE plane per attribute channel and
+// one for the heights, anchored near the wave's first hit: a hit adds its 3 (SIZE + 1) contributions into the planes
+// (ds_add_f32), or straight to global memory outside the tile; the flush then adds each touched texel of each plane to
+// global memory once.  On the bench wavefront (size 3) this takes 7.53 ms where plain float atomics took 10.06 ms and a
+// 16 x 16 tile 7.83 ms (profiles/attributes/adjoint_ab.txt).
+template <int SIZE, int TILE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_attr_adjoint_tile_kernel(hf_attr_args a) {
+    constexpr int TT = TILE * TILE;
+    __shared__ float s_acc[HF_BLOCK / 64][(SIZE + 1) * TT];
+    float *acc = s_acc[threadIdx.x >> 6];
+    const int lane = (int) (threadIdx.x & 63u);
+    for (int k = lane; k < (SIZE + 1) * TT; k += 64) acc[k] = 0.f;
+    const int W = a.f.W;
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    // whole waves stay in the loop (the ballot below)
+    for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u); ub < a.n; ub += stride) {
+        const size_t i = ub + (size_t) lane;
+        v3 gp = mk3(0.f, 0.f, 0.f);
+        float g[SIZE], wk[3] = { 0.f, 0.f, 0.f }, gh[3] = { 0.f, 0.f, 0.f };
+        int vr[3] = { 0, 0, 0 }, vc[3] = { 0, 0, 0 };
+        uint32_t prim;
+        const bool scatter = i < a.n && attr_hit(a, i, prim);
+        if (scatter) {
+#pragma unroll
+            for (int c = 0; c < SIZE; ++c) g[c] = a.g[c][i];
+            attr_vertex_vjp<SIZE>(a, i, prim, g, vr, vc, wk, gh, gp);
+        }
+        const uint64_t sm = __ballot(scatter);
+        if (sm != 0ull) {
+            int ar, ac;
+            tile_anchor(sm, vr, vc, TILE / 4, ar, ac); // from the first scattering lane
+            hf_tile_rows<TILE> rows = 0u;
+            if (scatter) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    if (a.grad_attr) {
+#pragma unroll
+                        for (int c = 0; c < SIZE; ++c)
+                            tile_add<TILE, SIZE>(acc + c * TT, ar, ac, vr[k], vc[k], g[c] * wk[k], a.grad_attr + c, W, rows);
+                    }
+                    if (a.grad_h) tile_add<TILE>(acc + SIZE * TT, ar, ac, vr[k], vc[k], gh[k], a.grad_h, W, rows);
+                }
+            }
+            if (a.grad_attr) {
+#pragma unroll
+                for (int c = 0; c < SIZE; ++c) tile_flush<TILE, SIZE>(acc + c * TT, ar, ac, rows, a.grad_attr + c, W, lane);
+            }
+            if (a.grad_h) tile_flush<TILE>(acc + SIZE * TT, ar, ac, rows, a.grad_h, W, lane);
+        }
+        if (i < a.n && a.grad_p[0]) { a.grad_p[0][i] = gp.x; a.grad_p[1][i] = gp.y; a.grad_p[2][i] = gp.z; }
+    }
+}
+
+// Forward mode: the tangent of the value for the tangents dattr (interleaved like attr), dp of si.p and dh of the
+// heights (each NULL = zero).  No atomics: bitwise the same from launch to launch.
+template <int TYPE, int SIZE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_attr_tangent_kernel(hf_attr_args a) {
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
+        float r[SIZE];
+#pragma unroll
+        for (int c = 0; c < SIZE; ++c) r[c] = 0.f;
+        uint32_t prim;
+        if (attr_hit(a, i, prim)) {
+            if constexpr (TYPE == HF_ATTR_FACE) {
+                if (a.dattr) {
+#pragma unroll
+                    for (int c = 0; c < SIZE; ++c) r[c] = a.dattr[(size_t) prim * SIZE + c];
+                }
+            } else {
+                v3 P[3], dP[3];
+                float U[3], V[3], A[3][SIZE];
+                int vi[3], vj[3];
+                prim_world(a.f, prim, P, U, V, vi, vj, dP, a.dh);
+                attr_vertices<SIZE>(a.attr, a.f, vi, vj, A);
+                const hf_bary b = bary_coords(mk3(a.p[0][i], a.p[1][i], a.p[2][i]), P);
+                const v3 dp = a.dp[0] ? mk3(a.dp[0][i], a.dp[1][i], a.dp[2][i]) : mk3(0.f, 0.f, 0.f);
+                float du, dv;
+                bary_coords_jvp(b, dp, dP, du, dv);
+                const float dw = -du - dv;
+#pragma unroll
+                for (int c = 0; c < SIZE; ++c) r[c] = A[0][c] * dw + A[1][c] * du + A[2][c] * dv;
+                if (a.dattr) {
+                    float dA[3][SIZE];
+                    attr_vertices<SIZE>(a.dattr, a.f, vi, vj, dA);
+#pragma unroll
+                    for (int c = 0; c < SIZE; ++c) r[c] += dA[0][c] * b.w + dA[1][c] * b.u + dA[2][c] * b.v;
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < SIZE; ++c) a.dout[c][i] = r[c];
+    }
+}
+
+#define HF_ATTR_TILE 32 // texels per side of the vertex adjoint's LDS planes (16: 7.83 ms, 32: 7.53 ms on the bench)
+template <int TYPE, int SIZE>
+static void attr_launch(int mode, const hf_attr_args &a, hipStream_t stream) {
+    if (TYPE == HF_ATTR_VERTEX && mode == 1) { // grid-stride at the default cap, like hf_adjoint_kernel (a tile to clear per wave)
+        void (*k)(hf_attr_args) = hf_attr_adjoint_tile_kernel<SIZE, HF_ATTR_TILE>;
+        hipLaunchKernelGGL(k, dim3(grid_for(a.n)), dim3(HF_BLOCK), 0, stream, a);
+        return;
+    }
+    void (*k)(hf_attr_args) = mode == 0 ? hf_attr_kernel<TYPE, SIZE>
+                            : mode == 1 ? hf_attr_face_adjoint_kernel<SIZE> : hf_attr_tangent_kernel<TYPE, SIZE>;
+    // streaming kernels with no per-block state: one block per 256 rays, as hf_si_kernel
+    hipLaunchKernelGGL(k, dim3(grid_for(a.n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, a);
+}
+void hf_launch_attribute(int mode, int type, uint32_t size, const hf_attr_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    if (type == HF_ATTR_VERTEX) size == 1 ? attr_launch<HF_ATTR_VERTEX, 1>(mode, a, stream) : attr_launch<HF_ATTR_VERTEX, 3>(mode, a, stream);
+    else                        size == 1 ? attr_launch<HF_ATTR_FACE, 1>(mode, a, stream) : attr_launch<HF_ATTR_FACE, 3>(mode, a, stream);
 }

@@ -111,3 +111,21 @@ void hf_launch_sample_position_adjoint(const hf_dev_field &f, size_t n, const ui
 void hf_launch_sample_position_tangent(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
                                        const uint8_t *active, const float *dh, float *const dp[3], float *const dn[3],
                                        const float4 *vn, hipStream_t stream);
+// ---- shape attributes (hf_eval_attribute / _adjoint / _tangent): the buffers are the caller's ----
+struct hf_attr_args {
+    hf_dev_field f;
+    size_t n;
+    const float *attr;          // [count][size] interleaved (count: W H vertices or 2 (W-1)(H-1) faces)
+    const uint32_t *prim;
+    const float *p[3], *t;      // si.p (vertex attributes), si.t (NULL: every active lane is a hit)
+    const uint8_t *active;
+    float *out[3];              // forward: size rows, overwritten
+    const float *g[3];          // adjoint: size rows of dL/dvalue
+    float *grad_attr;           // adjoint, accumulated (NULL: not wanted)
+    float *grad_p[3];           // adjoint, overwritten (NULL rows: not wanted)
+    float *grad_h;              // adjoint, accumulated (NULL: not wanted)
+    const float *dattr, *dp[3], *dh; // tangent inputs (NULL: zero)
+    float *dout[3];             // tangent: size rows, overwritten
+};
+// mode 0: forward, 1: adjoint, 2: tangent; type HF_ATTR_VERTEX / HF_ATTR_FACE, size 1 or 3 (checked by the caller)
+void hf_launch_attribute(int mode, int type, uint32_t size, const hf_attr_args &a, hipStream_t stream);

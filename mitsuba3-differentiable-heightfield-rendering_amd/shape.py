@@ -210,6 +210,40 @@ class _SamplePositionOp(torch.autograd.Function):
         return None, grad_h, None, None, None, None
 
 
+class _AttributeOp(torch.autograd.Function):
+    """Differentiable value [size, n] of eval_attribute*; backward = hf_eval_attribute_adjoint (atomic scatter into the
+    attribute buffer and the heights, dL/dp per lane), jvp = hf_eval_attribute_tangent.  Inputs: the attribute buffer,
+    si.p (vertex attributes; the gradient of p then reaches hf_adjoint through _SurfaceInteractionOp) and the heights."""
+
+    @staticmethod
+    def forward(ctx, shape, name, attr, p, heights, prim, t, active, value):
+        ctx.shape, ctx.name, ctx.active = shape, name, active
+        p = p.detach().contiguous() if p is not None else None
+        ctx.save_for_backward(attr.detach(), p, prim, t)
+        ctx.save_for_forward(attr.detach(), p, prim, t)
+        ctx.h_version = shape._heights_version
+        return value
+
+    @staticmethod
+    def jvp(ctx, _shape, _name, dattr, dp, dh, *_):
+        shape = ctx.shape
+        attr, p, prim, t = ctx.saved_tensors
+        if ctx.h_version != shape._heights_version:
+            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
+        return shape._attr_tangent_raw(ctx.name, attr, p, prim, t, ctx.active, dattr, dp, dh)
+
+    @staticmethod
+    def backward(ctx, g):
+        shape = ctx.shape
+        attr, p, prim, t = ctx.saved_tensors
+        if ctx.h_version != shape._heights_version:
+            raise RuntimeError("heightfield parameters changed between forward and backward")
+        need_a, need_p, need_h = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        ga, gp, gh = shape._attr_adjoint_raw(ctx.name, attr, p, prim, t, ctx.active, g.contiguous().to(torch.float32),
+                                             need_a, need_p, need_h)
+        return None, None, ga, gp, gh, None, None, None, None
+
+
 # order of the differentiable SI block handed to autograd: 18 rows
 _DIFF_ROWS = [("t", 1), ("p", 3), ("n", 3), ("uv", 2), ("sh_n", 3), ("dp_du", 3), ("dp_dv", 3)]
 _AUX_ROWS = [("boundary_test", 1), ("sh_s", 3), ("sh_t", 3), ("wi", 3)]
@@ -285,6 +319,8 @@ class Heightfield:
     `face_normals` is Mesh's property (src/render/mesh.cpp:30) but defaults to True (flat shading), where Mesh's
     defaults to False: a heightfield shades flat unless smooth shading is asked for (hf_set_face_normals).
     Object space is Rectangle's: x,y in [-1,1], +Z up (src/shapes/rectangle.cpp:47-48).
+    Properties named `vertex_*` ([H, W, C] or [H, W] tensor) or `face_*` ([2 (H-1)(W-1), C] tensor) become shape
+    attributes (add_attribute).
     """
 
     def __init__(self, props=None, **kw):
@@ -296,6 +332,7 @@ class Heightfield:
         self.flip_normals = bool(props.pop("flip_normals", False))
         face_normals = bool(props.pop("face_normals", True))
         device = props.pop("device", None)
+        attr_props = [(k, props.pop(k)) for k in sorted(props) if k.startswith(("vertex_", "face_"))]
         if props:
             raise RuntimeError(f"Unreferenced properties: {sorted(props)}")  # Properties semantics
         if not torch.cuda.is_available():
@@ -330,6 +367,18 @@ class Heightfield:
         self.parameters_changed(["heightfield"])
         self.face_normals = True
         self.set_face_normals(face_normals)
+        # shape attributes (Mesh::m_mesh_attributes): name -> flat float32 buffer [count * size] (interleaved), and
+        # name -> (HF_ATTR_VERTEX / HF_ATTR_FACE, size)
+        self.attributes, self._attr_meta = {}, {}
+        for name, data in attr_props:
+            data = torch.as_tensor(data, dtype=torch.float32)
+            if name.startswith("vertex_"):
+                size = 1 if data.dim() == 2 else int(data.shape[-1])
+                if tuple(data.shape[:2]) != (self.height, self.width):
+                    raise RuntimeError(f"{name}: expected a [{self.height}, {self.width}, C] tensor, got {tuple(data.shape)}")
+            else:
+                size = 1 if data.dim() == 1 else int(data.shape[-1])
+            self.add_attribute(name, size, data)
 
     # ---- lifetime ---------------------------------------------------------------------
     def __del__(self):
@@ -346,9 +395,18 @@ class Heightfield:
         callback.put_parameter("heightfield", self.heightfield, ParamFlags.Differentiable | ParamFlags.Discontinuous)
         callback.put_parameter("max_height", self.max_height, ParamFlags.NonDifferentiable)
         callback.put_parameter("to_world", self.to_world, ParamFlags.NonDifferentiable)
+        for name, buf in self.attributes.items():   # mesh.cpp:74-76: every attribute is shown as differentiable
+            callback.put_parameter(name, buf, ParamFlags.Differentiable)
 
     def parameters_changed(self, keys=()):
         keys = list(keys)
+        for name, (type_, size) in getattr(self, "_attr_meta", {}).items():   # every attribute, whatever the keys
+            expected = size * self._attr_count(type_)
+            buf = self.attributes[name]
+            if buf.numel() != expected:   # mesh.cpp:103-110: an attribute of the wrong size is reset to zeros
+                self.attributes[name] = torch.zeros(expected, dtype=torch.float32, device=self.device)
+            elif buf.dtype != torch.float32 or buf.device != self.device or not buf.is_contiguous() or buf.dim() != 1:
+                self.attributes[name] = buf.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
         if not keys or "heightfield" in keys:
             h = self.heightfield
             if h.dim() == 3 and h.shape[2] == 1:
@@ -510,6 +568,166 @@ class Heightfield:
         keep, _ = self._mask(active, ps.prim_index.shape[0])
         out = self._sample_tangent_raw(ps.prim_index, ps.b, keep, dheights)
         return out[0:3], out[3:6]
+
+    # ---- shape attributes (Mesh::add_attribute / has_attribute / eval_attribute*, mesh.cpp:905-1004) -------------------
+    def _attr_count(self, type_):
+        return self.width * self.height if type_ == _capi.HF_ATTR_VERTEX else 2 * (self.width - 1) * (self.height - 1)
+
+    def add_attribute(self, name, size, data):
+        """mesh.cpp:905-936: `vertex_*` holds one value of `size` floats per grid vertex (row-major, vertex (i, j) =
+        i W + j), `face_*` one per triangle (prim_index order); data is read as count * size interleaved floats"""
+        if name in self.attributes:
+            raise RuntimeError(f"add_attribute(): attribute {name} already exists.")
+        if name.startswith("vertex_"):
+            type_ = _capi.HF_ATTR_VERTEX
+        elif name.startswith("face_"):
+            type_ = _capi.HF_ATTR_FACE
+        else:
+            raise RuntimeError('add_attribute(): attribute name must start with either "vertex_" of "face_".')
+        size = int(size)
+        count = self._attr_count(type_)
+        buf = torch.as_tensor(data, dtype=torch.float32).detach().to(self.device).reshape(-1).contiguous().clone()
+        if buf.numel() != count * size:
+            raise RuntimeError(f"add_attribute(): attribute {name}: expected {count} x {size} values, got {buf.numel()}")
+        self.attributes[name] = buf
+        self._attr_meta[name] = (type_, size)
+
+    def has_attribute(self, name, active=True):
+        """mesh.cpp:938-944; Shape::has_attribute (shape.cpp:457-463) is false for any other name"""
+        return name in self.attributes
+
+    def _attr_lookup(self, fn, name, sizes):
+        if name not in self.attributes:   # Shape::eval_attribute* (shape.cpp:465-505)
+            raise RuntimeError(f"Invalid attribute requested {name}.")
+        type_, size = self._attr_meta[name]
+        if size not in sizes:
+            raise RuntimeError(f'{fn}(): Attribute "{name}" requested but had size {size}.')
+        return type_, size
+
+    def eval_attribute(self, name, si, active=True):
+        """mesh.cpp:946-967 in an RGB variant: [3, n]; a size-1 attribute is broadcast to the three channels"""
+        _, size = self._attr_lookup("eval_attribute", name, (1, 3))
+        v = self._eval_attr(name, si, active)
+        return v.expand(3, -1) if size == 1 else v
+
+    def eval_attribute_1(self, name, si, active=True):
+        """mesh.cpp:969-985: [n]"""
+        self._attr_lookup("eval_attribute_1", name, (1,))
+        return self._eval_attr(name, si, active)[0]
+
+    def eval_attribute_3(self, name, si, active=True):
+        """mesh.cpp:987-1004: [3, n]"""
+        self._attr_lookup("eval_attribute_3", name, (3,))
+        return self._eval_attr(name, si, active)
+
+    def _attr_inputs(self, name, attr, p, prim, t, active_u8):
+        """(type, size, attr address, prim address, p rows (byref or None), t address, active address)"""
+        type_, size = self._attr_meta[name]
+        if attr.numel() != size * self._attr_count(type_) or not attr.is_contiguous() or attr.dtype != torch.float32:
+            # the kernels gather count * size floats: a buffer assigned behind parameters_changed's back is refused
+            raise RuntimeError(f"attribute {name}: expected a contiguous float32 buffer of {self._attr_count(type_)} x "
+                               f"{size} values, got {tuple(attr.shape)} {attr.dtype}")
+        pp = None
+        if type_ == _capi.HF_ATTR_VERTEX:
+            assert p.is_contiguous() and p.dtype == torch.float32
+            pp = (C.c_void_p * 3)(*_rows(p, p.shape[1]))
+        return (type_, size, prim.data_ptr(), C.byref(pp) if pp is not None else None,
+                t.data_ptr() if t is not None else None, active_u8.data_ptr() if active_u8 is not None else None)
+
+    def _eval_attr(self, name, si, active):
+        type_ = self._attr_meta[name][0]
+        n = si.prim_index.shape[0]
+        keep, _ = self._mask(active, n)
+        prim = si.prim_index.contiguous()
+        t = si.t.detach().contiguous() if si.t is not None else None
+        p = si.p.detach().to(torch.float32).contiguous() if type_ == _capi.HF_ATTR_VERTEX else None
+        buf = self.attributes[name]
+        value = self._attr_forward_raw(name, buf.detach(), p, prim, t, keep)
+        h = self.heightfield
+        live = [buf] + ([si.p, h] if type_ == _capi.HF_ATTR_VERTEX else [])
+        if any(_has_tangent(x) for x in live) or (torch.is_grad_enabled() and any(x.requires_grad for x in live)):
+            vertex = type_ == _capi.HF_ATTR_VERTEX
+            value = _AttributeOp.apply(self, name, buf, si.p if vertex else None, h if vertex else None, prim, t, keep,
+                                       value)
+        return value
+
+    def _attr_forward_raw(self, name, attr, p, prim, t, active_u8):
+        n = prim.shape[0]
+        type_, size, pr, pp, tp, ap = self._attr_inputs(name, attr, p, prim, t, active_u8)
+        out = torch.empty((size, n), dtype=torch.float32, device=self.device)
+        orow = (C.c_void_p * 3)(*(_rows(out, n) + [None] * (3 - size)))
+        check(_capi.lib().hf_eval_attribute(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap, C.byref(orow),
+                                            self._stream()))
+        return out
+
+    def _attr_adjoint_raw(self, name, attr, p, prim, t, active_u8, g, need_attr=True, need_p=True, need_h=True,
+                          grad_attr=None, grad_h=None):
+        """(dL/dattr [count * size], dL/dp [3, n], dL/dheight [H, W]) for g [size, n]; None where not needed"""
+        n = prim.shape[0]
+        type_, size, pr, pp, tp, ap = self._attr_inputs(name, attr, p, prim, t, active_u8)
+        vertex = type_ == _capi.HF_ATTR_VERTEX
+        need_p, need_h = need_p and vertex, need_h and vertex
+        if need_attr and grad_attr is None:
+            grad_attr = torch.zeros(attr.numel(), dtype=torch.float32, device=self.device)
+        if need_h and grad_h is None:
+            grad_h = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+        gp = torch.empty((3, n), dtype=torch.float32, device=self.device) if need_p else None
+        grow = (C.c_void_p * 3)(*(_rows(g, n) + [None] * (3 - size)))
+        gprow = (C.c_void_p * 3)(*_rows(gp, n)) if need_p else None
+        check(_capi.lib().hf_eval_attribute_adjoint(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap,
+                                                    C.byref(grow), grad_attr.data_ptr() if need_attr else None,
+                                                    C.byref(gprow) if need_p else None,
+                                                    grad_h.data_ptr() if need_h else None, self._stream()))
+        return (grad_attr if need_attr else None), gp, (grad_h if need_h else None)
+
+    def _attr_tangent_raw(self, name, attr, p, prim, t, active_u8, dattr=None, dp=None, dh=None):
+        n = prim.shape[0]
+        type_, size, pr, pp, tp, ap = self._attr_inputs(name, attr, p, prim, t, active_u8)
+        out = torch.empty((size, n), dtype=torch.float32, device=self.device)
+        keep = []
+
+        def flat(x, numel):
+            if x is None:
+                return None
+            x = torch.as_tensor(x, device=self.device).detach().to(torch.float32).reshape(-1).contiguous()
+            assert x.numel() == numel
+            keep.append(x)
+            return x.data_ptr()
+        da = flat(dattr, attr.numel())
+        dhp = flat(dh, self.width * self.height)
+        dpr = None
+        if dp is not None and type_ == _capi.HF_ATTR_VERTEX:
+            dpt = torch.as_tensor(dp, device=self.device).detach().to(torch.float32).reshape(3, n).contiguous()
+            keep.append(dpt)
+            dpr = (C.c_void_p * 3)(*_rows(dpt, n))
+        orow = (C.c_void_p * 3)(*(_rows(out, n) + [None] * (3 - size)))
+        check(_capi.lib().hf_eval_attribute_tangent(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap, da,
+                                                    C.byref(dpr) if dpr is not None else None, dhp, C.byref(orow),
+                                                    self._stream()))
+        return out
+
+    def _attr_si(self, si):
+        prim = si.prim_index.contiguous()
+        t = si.t.detach().contiguous() if si.t is not None else None
+        p = si.p.detach().to(torch.float32).contiguous() if si.p is not None else None
+        return p, prim, t
+
+    def eval_attribute_adjoint(self, name, si, grad, active=True, grad_attr=None, grad_heightfield=None):
+        """Explicit reverse mode of eval_attribute* (no autograd): for dL/dvalue grad ([size, n]) returns
+        (dL/dattr [count * size], accumulated into grad_attr if given; dL/dp [3, n]; dL/dheight [H, W], accumulated into
+        grad_heightfield if given).  Face attributes: dL/dp and dL/dheight are None."""
+        p, prim, t = self._attr_si(si)
+        keep, _ = self._mask(active, prim.shape[0])
+        g = _as_f32(grad, self.device).reshape(self._attr_meta[name][1], -1).contiguous()
+        return self._attr_adjoint_raw(name, self.attributes[name].detach(), p, prim, t, keep, g,
+                                      grad_attr=grad_attr, grad_h=grad_heightfield)
+
+    def eval_attribute_tangent(self, name, si, dattr=None, dp=None, dheights=None, active=True):
+        """Explicit forward mode of eval_attribute*: the tangent [size, n] for the tangents dattr ([count * size]), dp
+        ([3, n], of si.p) and dheights ([H, W]); any of them may be None (zero)"""
+        p, prim, t = self._attr_si(si)
+        keep, _ = self._mask(active, prim.shape[0])
+        return self._attr_tangent_raw(name, self.attributes[name].detach(), p, prim, t, keep, dattr, dp, dheights)
 
     def parameters_grad_enabled(self):
         return bool(self.heightfield.requires_grad)
