@@ -357,6 +357,32 @@ int hf_tangent(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_p
                const uint8_t *active, const float *dheights, const float *const d_o[3], const float *const d_d[3],
                const hf_si_tangent_t *tangent_si, hf_stream_t stream);
 
+/* Replaces: the reverse-mode pass of the reference through Rectangle's attached to_world (src/shapes/rectangle.cpp:128,
+ * 255-310: to_world is Differentiable | Discontinuous there).  hf_adjoint_rows, plus grad_to_world: 12 device floats,
+ * row-major 3x4 [A | t] like hf_desc_t.to_world, ACCUMULATED with dL/d(to_world) = sum_v dL/dP_v (q_v, 1)^T over the
+ * world positions P_v = A q_v + t of the vertices each hit reads, q_v = (x_v, y_v, max_height h_v) in object space: the
+ * hit triangle's three, and with smooth shading also the 1-rings of its three vertex normals.  The modes as in
+ * hf_adjoint: default = Moeller-Trumbore re-intersection (p stays on the ray), HF_RAY_FOLLOWSHAPE = frozen barycentrics
+ * (p is glued to the shape), HF_RAY_DETACHSHAPE = no contribution; the choice of triangle is not differentiated.  No
+ * float atomics on grad_to_world: the blocks' partial sums go to a scratch block of the handle's ring and one more
+ * launch adds them up in a fixed order, so the result is bitwise the same from launch to launch (capturable, like the
+ * trace launches; two streams may launch on one handle concurrently).  grad_heights, grad_o, grad_d and row_band may
+ * each be NULL; grad_heights then equals hf_adjoint's up to the order of its float atomics, and grad_o / grad_d are
+ * bitwise hf_adjoint's.  grad_to_world == NULL: exactly hf_adjoint_rows. */
+int hf_adjoint_transform(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
+                         const hf_pi_const_t *pi, uint32_t ray_flags, const uint8_t *active,
+                         const hf_si_grad_t *grad_si, float *grad_heights,
+                         float *const grad_o[3], float *const grad_d[3], uint32_t *row_band,
+                         float *grad_to_world, hf_stream_t stream);
+/* Replaces: the forward-mode pass of the reference through Rectangle's attached to_world (rectangle.cpp:255-310).
+ * hf_tangent, plus d_to_world: the tangent of to_world, 12 device floats (row-major 3x4), NULL = zero: every vertex the
+ * surface interaction reads moves by dA q_v + dt besides its height tangent.  The transpose of hf_adjoint_transform,
+ * mode for mode.  No atomics: bitwise the same from launch to launch.  d_to_world == NULL: exactly hf_tangent. */
+int hf_tangent_transform(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
+                         uint32_t ray_flags, const uint8_t *active, const float *dheights, const float *const d_o[3],
+                         const float *const d_d[3], const float *d_to_world, const hf_si_tangent_t *tangent_si,
+                         hf_stream_t stream);
+
 /* Replaces: SurfaceInteraction3f::dn_du / dn_dv of the smooth-shaded mesh under RayFlags::dNSdUV (mesh.cpp:818-829):
  * the derivatives of the shading normal with respect to the barycentrics (b1, b2) of every hit of pi, before
  * flip_normals (as the reference).  dn_du / dn_dv: 3 device arrays of n floats each (either may be NULL), overwritten.
@@ -428,6 +454,21 @@ int hf_sample_position_adjoint(const hf_field_t *hf, size_t n, const uint32_t *p
 int hf_sample_position_tangent(const hf_field_t *hf, size_t n, const uint32_t *prim_index, const float *const b[2],
                                const uint8_t *active, const float *dheights, float *const dp[3], float *const dn[3],
                                hf_stream_t stream);
+/* Replaces: the reverse mode of Mesh::sample_position through the attached to_world of the reference's shapes (the
+ * vertex positions that sample_position gathers, mesh.cpp:557-610).  hf_sample_position_adjoint, plus grad_to_world
+ * (12 device floats, accumulated, as in hf_adjoint_transform: p = P0 + b.x e0 + b.y e1 and n, flat or smooth, follow
+ * the vertices; slab reduction, no float atomics on it, bitwise repeatable).  grad_heights may be NULL.
+ * grad_to_world == NULL: exactly hf_sample_position_adjoint. */
+int hf_sample_position_adjoint_transform(const hf_field_t *hf, size_t n, const uint32_t *prim_index,
+                                         const float *const b[2], const uint8_t *active, const float *const grad_p[3],
+                                         const float *const grad_n[3], float *grad_heights, float *grad_to_world,
+                                         hf_stream_t stream);
+/* Replaces: the forward mode of the same.  hf_sample_position_tangent, plus d_to_world (12 device floats, NULL = zero).
+ * No atomics.  d_to_world == NULL: exactly hf_sample_position_tangent. */
+int hf_sample_position_tangent_transform(const hf_field_t *hf, size_t n, const uint32_t *prim_index,
+                                         const float *const b[2], const uint8_t *active, const float *dheights,
+                                         const float *d_to_world, float *const dp[3], float *const dn[3],
+                                         hf_stream_t stream);
 
 /* ---- shape attributes: the attribute side of Shape (has_attribute, eval_attribute, eval_attribute_1 / _3) -------- */
 

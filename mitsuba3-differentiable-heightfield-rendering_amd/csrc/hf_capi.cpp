@@ -26,7 +26,9 @@ struct hf_field {
     // its stream wait for that event (a device-side wait, normally long past), so two pending launches never
     // share a block, and hf_destroy waits for exactly the launches of this handle instead of the whole device.
     // Choice of the slot, launch and event record are ONE critical section (slot_lease below).
-    // Blocks are allocated by hf_create (hf_trace_scratch_bytes is a constant today; a larger request re-allocates).
+    // Blocks are allocated by hf_create (hf_trace_scratch_bytes is a constant today; a larger request re-allocates),
+    // large enough for the slab of any transform-gradient launch too (hf_xform_slab_bytes(0): 240 KB), which also takes
+    // its slab from this ring.
     // HIP-graph capture: a launch issued while its stream is being captured takes its block from the upper half of
     // the ring, touches no event, and keeps the block until hf_capture_reset (slot_lease).
     char *slot_buf[HF_NUM_SLOTS];
@@ -249,7 +251,8 @@ extern "C" int hf_create(const hf_desc_t *desc, hf_field_t **out) {
     if (e == hipSuccess) e = hipEventCreateWithFlags(&hf->built, hipEventDisableTiming);
     for (int k = 0; k < HF_NUM_SLOTS && e == hipSuccess; ++k) {
         e = hipEventCreateWithFlags(&hf->slot_done[k], hipEventDisableTiming);
-        const size_t cap = hf_trace_scratch_bytes(0) < 4096 ? 4096 : hf_trace_scratch_bytes(0);
+        size_t cap = hf_trace_scratch_bytes(0) < 4096 ? 4096 : hf_trace_scratch_bytes(0);
+        if (cap < hf_xform_slab_bytes(0)) cap = hf_xform_slab_bytes(0);
         if (e == hipSuccess) e = hipMalloc((void **) &hf->slot_buf[k], cap);
         if (e == hipSuccess) hf->slot_cap[k] = cap;
     }
@@ -528,6 +531,44 @@ extern "C" int hf_sample_position_adjoint(const hf_field_t *hf, size_t n, const 
     return HF_OK;
 }
 
+// Replaces the reverse mode of sample_position through the reference's attached to_world: see include/hf.h
+extern "C" int hf_sample_position_adjoint_transform(const hf_field_t *hf, size_t n, const uint32_t *prim_index,
+                                                    const float *const b[2], const uint8_t *active,
+                                                    const float *const grad_p[3], const float *const grad_n[3],
+                                                    float *grad_heights, float *grad_to_world, hf_stream_t stream) {
+    const char *fn = "hf_sample_position_adjoint_transform";
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    if (!grad_to_world) return hf_sample_position_adjoint(hf, n, prim_index, b, active, grad_p, grad_n, grad_heights, stream);
+    int rc = check_sample_diff(fn, hf, n, prim_index, b);
+    if (rc || n == 0) return rc;
+    if ((grad_p && !all3(grad_p)) || (grad_n && !all3(grad_n))) return fail(HF_EINVAL, "%s: NULL grad_p / grad_n array", fn);
+    {
+        slot_lease lease(hf, (hipStream_t) stream, hf_xform_slab_bytes(n));
+        if (!lease.buf) return fail(lease.code, "%s: %s", fn, lease.why);
+        hf_launch_sample_position_adjoint(hf->dev, n, prim_index, b, active, grad_p, grad_n, grad_heights, hf->d_vn,
+                                          (hipStream_t) stream, grad_to_world, lease.buf);
+    }
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+// Replaces the forward mode of sample_position through the reference's attached to_world: see include/hf.h
+extern "C" int hf_sample_position_tangent_transform(const hf_field_t *hf, size_t n, const uint32_t *prim_index,
+                                                    const float *const b[2], const uint8_t *active, const float *dheights,
+                                                    const float *d_to_world, float *const dp[3], float *const dn[3],
+                                                    hf_stream_t stream) {
+    const char *fn = "hf_sample_position_tangent_transform";
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    if (!d_to_world) return hf_sample_position_tangent(hf, n, prim_index, b, active, dheights, dp, dn, stream);
+    int rc = check_sample_diff(fn, hf, n, prim_index, b);
+    if (rc || n == 0) return rc;
+    if ((dp && !all3(dp)) || (dn && !all3(dn))) return fail(HF_EINVAL, "%s: NULL dp / dn array", fn);
+    hf_launch_sample_position_tangent(hf->dev, n, prim_index, b, active, dheights, dp, dn, hf->d_vn, (hipStream_t) stream,
+                                      d_to_world);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 extern "C" int hf_sample_position_tangent(const hf_field_t *hf, size_t n, const uint32_t *prim_index, const float *const b[2],
                                           const uint8_t *active, const float *dheights, float *const dp[3], float *const dn[3],
                                           hf_stream_t stream) {
@@ -793,6 +834,52 @@ extern "C" int hf_tangent(const hf_field_t *hf, size_t n, const hf_rays_t *rays,
     if ((rc = check_pi("hf_tangent", n, pi))) return rc;
     if (!tangent_si) return fail(HF_EINVAL, "hf_tangent: NULL output");
     hf_launch_tangent(hf->dev, n, rays, pi, active, ray_flags, dheights, d_o, d_d, tangent_si, (hipStream_t) stream, hf->d_vn);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+// Replaces the reverse-mode pass through the reference's attached to_world (rectangle.cpp:128, 255-310): see include/hf.h
+extern "C" int hf_adjoint_transform(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
+                                    uint32_t ray_flags, const uint8_t *active, const hf_si_grad_t *grad_si,
+                                    float *grad_heights, float *const grad_o[3], float *const grad_d[3],
+                                    uint32_t *row_band, float *grad_to_world, hf_stream_t stream) {
+    const char *fn = "hf_adjoint_transform";
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    if (!grad_to_world)
+        return hf_adjoint_rows(hf, n, rays, pi, ray_flags, active, grad_si, grad_heights, grad_o, grad_d, row_band, stream);
+    int rc = check_rays(fn, hf, n, rays);
+    if (rc) return rc;
+    if ((rc = check_flags(fn, ray_flags))) return rc;
+    if ((rc = check_pi(fn, n, pi))) return rc;
+    if (!grad_si) return fail(HF_EINVAL, "%s: NULL grad_si", fn);
+    if (grad_o && !all3(grad_o)) return fail(HF_EINVAL, "%s: NULL grad_o array", fn);
+    if (grad_d && !all3(grad_d)) return fail(HF_EINVAL, "%s: NULL grad_d array", fn);
+    if (n == 0) return HF_OK;
+    {
+        slot_lease lease(hf, (hipStream_t) stream, hf_xform_slab_bytes(n)); // the slab: this launch's alone
+        if (!lease.buf) return fail(lease.code, "%s: %s", fn, lease.why);
+        hf_launch_adjoint(hf->dev, n, rays, pi, active, grad_si, ray_flags, grad_heights, grad_o, grad_d, row_band,
+                          (hipStream_t) stream, hf->d_vn, grad_to_world, lease.buf);
+    }
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+// Replaces the forward-mode pass through the reference's attached to_world (rectangle.cpp:255-310): see include/hf.h
+extern "C" int hf_tangent_transform(const hf_field_t *hf, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
+                                    uint32_t ray_flags, const uint8_t *active, const float *dheights,
+                                    const float *const d_o[3], const float *const d_d[3], const float *d_to_world,
+                                    const hf_si_tangent_t *tangent_si, hf_stream_t stream) {
+    const char *fn = "hf_tangent_transform";
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    if (!d_to_world) return hf_tangent(hf, n, rays, pi, ray_flags, active, dheights, d_o, d_d, tangent_si, stream);
+    int rc = check_rays(fn, hf, n, rays);
+    if (rc) return rc;
+    if ((rc = check_flags(fn, ray_flags))) return rc;
+    if ((rc = check_pi(fn, n, pi))) return rc;
+    if (!tangent_si) return fail(HF_EINVAL, "%s: NULL output", fn);
+    hf_launch_tangent(hf->dev, n, rays, pi, active, ray_flags, dheights, d_o, d_d, tangent_si, (hipStream_t) stream,
+                      hf->d_vn, d_to_world);
     HF_HIP(hipGetLastError());
     return HF_OK;
 }

@@ -22,6 +22,7 @@ struct v3 {
 
 __device__ __forceinline__ v3 mk3(float x, float y, float z) { return v3{ x, y, z }; }
 __device__ __forceinline__ v3 operator-(v3 a, v3 b) { return v3{ a.x - b.x, a.y - b.y, a.z - b.z }; }
+__device__ __forceinline__ v3 operator+(v3 a, v3 b) { return v3{ a.x + b.x, a.y + b.y, a.z + b.z }; }
 __device__ __forceinline__ v3 operator*(v3 a, float s) { return v3{ a.x * s, a.y * s, a.z * s }; }
 __device__ __forceinline__ v3 neg3(v3 a) { return v3{ -a.x, -a.y, -a.z }; }
 
@@ -409,9 +410,44 @@ __device__ __forceinline__ void face_normal_vjp(v3 e1, v3 e2, v3 gN, v3 ez, floa
 // The shading normal is interpolated only when the reference fetches the vertex normals for it (mesh.cpp:813-815)
 __device__ __forceinline__ bool smooth_sh(uint32_t flags) { return (flags & (HF_RAY_SHADINGFRAME | HF_RAY_DNSDUV)) != 0u; }
 
-// world-space position of grid vertex (row i, column j) with height h: the expression of prim_world
+// object-space position q of grid vertex (row i, column j) with height h, and its world-space position [A | t] q: the
+// expressions of prim_world
+__device__ __forceinline__ v3 grid_local(const hf_dev_field &f, int i, int j, float h) {
+    return mk3(__builtin_fmaf((float) j, f.sx, -1.0f), __builtin_fmaf((float) i, f.sy, -1.0f), h * f.s);
+}
 __device__ __forceinline__ v3 grid_world(const hf_dev_field &f, int i, int j, float h) {
-    return xform_point(f.to_world, mk3(__builtin_fmaf((float) j, f.sx, -1.0f), __builtin_fmaf((float) i, f.sy, -1.0f), h * f.s));
+    return xform_point(f.to_world, grid_local(f, i, j, h));
+}
+
+// ---- Derivatives with respect to to_world = [A | t] (row-major 3x4).  Everything attached depends on to_world only
+// through the world positions P_v = A q_v + t of the vertices it reads, so dL/d(to_world) = sum_v G_v (q_v, 1)^T with
+// G_v = dL/dP_v, and the tangent of P_v for a tangent dM of to_world is dM (q_v, 1) = xform_point(dM, q_v). ----
+
+// M[r][c] += g[r] (q, 1)[c]: one vertex's world-space gradient g times its object-space position q
+__device__ __forceinline__ void xform_grad_point(float M[12], v3 g, v3 q) {
+    const float gr[3] = { g.x, g.y, g.z };
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        M[4 * r + 0] = __builtin_fmaf(gr[r], q.x, M[4 * r + 0]);
+        M[4 * r + 1] = __builtin_fmaf(gr[r], q.y, M[4 * r + 1]);
+        M[4 * r + 2] = __builtin_fmaf(gr[r], q.z, M[4 * r + 2]);
+        M[4 * r + 3] += gr[r];
+    }
+}
+// ... for a gradient g of a difference of two vertices (object-space difference dq): no translation part
+__device__ __forceinline__ void xform_grad_vec(float M[12], v3 g, v3 dq) {
+    const float gr[3] = { g.x, g.y, g.z };
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        M[4 * r + 0] = __builtin_fmaf(gr[r], dq.x, M[4 * r + 0]);
+        M[4 * r + 1] = __builtin_fmaf(gr[r], dq.y, M[4 * r + 1]);
+        M[4 * r + 2] = __builtin_fmaf(gr[r], dq.z, M[4 * r + 2]);
+    }
+}
+// the object-space positions of a primitive's three vertices (prim_vertex_ids' rows vi, columns vj)
+__device__ __forceinline__ void prim_local(const hf_dev_field &f, const int vi[3], const int vj[3], v3 q[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = grid_local(f, vi[k], vj[k], f.h[(size_t) vi[k] * f.W + vj[k]]);
 }
 
 // The 1-ring of grid vertex (i, j).  With the diagonal split of test_cell, the vertex's neighbours in counter-clockwise
@@ -570,6 +606,83 @@ __device__ __forceinline__ void vertex_normals_jvp(const hf_dev_field &f, const 
         float dX, dR[6];
         ring_world(f, vi[k], vj[k], g, dh, &dX, dR);
         axpy3(w[k], vertex_normal_jvp(g, ez, dX, dR), acc);
+    }
+}
+
+// World-space forms of vertex_normal_vjp / _jvp for the transform derivatives, where a vertex moves in every
+// direction: the gradient / the tangent dE[k] of each edge E_k = R_k - X of the ring.  Same ring geometry (ring_dirs,
+// ring_sum) and the same per-triangle terms; the height forms above keep their contraction with ez.  The VJP hands each
+// triangle's two edge gradients to the sink add(k, g) as they arise (no per-edge accumulator is live).
+template <typename Add>
+__device__ __forceinline__ void vertex_normal_vjp_world(const hf_ring &g, v3 gn, Add add) {
+    v3 u[6];
+    float l[6], rm;
+    ring_dirs(g, u, l);
+    const v3 m = ring_sum(g, u, rm);
+    const v3 gm = dnormalize(m * rm, rm, gn);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        if (!ring_tri(g.in, k)) continue;
+        const int k1 = (k + 1) % 6;
+        const v3 e1 = g.R[k] - g.X, e2 = g.R[k1] - g.X;
+        const auto [nt, r] = unit_normal(e1, e2);
+        const float c = dot3(u[k], u[k1]), th = ring_angle(c);
+        const v3 gN = dnormalize(nt, r, gm * th);
+        const float gc = ring_dangle(c) * dot3(nt, gm);
+        add(k, fma3(u[k1] - u[k] * c, gc * l[k], cross3(e2, gN)));
+        add(k1, fma3(u[k] - u[k1] * c, gc * l[k1], cross3(gN, e1)));
+    }
+}
+__device__ __forceinline__ v3 vertex_normal_jvp_world(const hf_ring &g, const v3 dE[6]) {
+    v3 u[6];
+    float l[6], rm;
+    ring_dirs(g, u, l);
+    const v3 m = ring_sum(g, u, rm);
+    v3 dm = mk3(0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        if (!ring_tri(g.in, k)) continue;
+        const int k1 = (k + 1) % 6;
+        const v3 e1 = g.R[k] - g.X, e2 = g.R[k1] - g.X;
+        const v3 de1 = dE[k], de2 = dE[k1];
+        const auto [nt, r] = unit_normal(e1, e2);
+        const v3 dnt = dnormalize(nt, r, face_normal_jvp(e1, e2, de1, de2));
+        const float c = dot3(u[k], u[k1]);
+        const v3 du1 = (de1 - u[k] * dot3(u[k], de1)) * l[k], du2 = (de2 - u[k1] * dot3(u[k1], de2)) * l[k1];
+        const float dth = ring_dangle(c) * (dot3(du1, u[k1]) + dot3(u[k], du2));
+        axpy3(ring_angle(c), dnt, dm);
+        axpy3(dth, nt, dm);
+    }
+    return dnormalize(m * rm, rm, dm);
+}
+// object-space edge E_k of a ring: q(R_k) - q(X) (zero for an absent neighbour, which ring_world puts at X)
+__device__ __forceinline__ v3 ring_local_edge(const hf_dev_field &f, const hf_ring &g, int k) {
+    const float hx = f.h[(size_t) g.i[6] * f.W + g.j[6]], hk = f.h[(size_t) g.i[k] * f.W + g.j[k]];
+    return grid_local(f, g.i[k], g.j[k], hk) - grid_local(f, g.i[6], g.j[6], hx);
+}
+// The three vertex normals of a hit for the transform: VJP: M += sum over the rings of gE[k] (x) E_k (the normals
+// do not depend on the translation); JVP: acc += sum_k w[k] dN_k for the tangent dM of to_world and the height tangent
+// dh (nullptr: zero), each edge moving by dM E_k + ez (dh_k - dh_X).
+__device__ __forceinline__ void vertex_normals_vjp_xform(const hf_dev_field &f, const int vi[3], const int vj[3],
+                                                         const v3 gB[3], float M[12]) {
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        hf_ring g;
+        ring_world(f, vi[k], vj[k], g);
+        vertex_normal_vjp_world(g, gB[k], [&](int q, v3 gE) { xform_grad_vec(M, gE, ring_local_edge(f, g, q)); });
+    }
+}
+__device__ __forceinline__ void vertex_normals_jvp_xform(const hf_dev_field &f, const int vi[3], const int vj[3], v3 ez,
+                                                         const float w[3], const float *dh, const float dM[12], v3 &acc) {
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        hf_ring g;
+        float dX = 0.f, dR[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+        ring_world(f, vi[k], vj[k], g, dh, &dX, dR);
+        v3 dE[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) dE[q] = fma3(ez, dR[q] - dX, xform_vec(dM, ring_local_edge(f, g, q)));
+        axpy3(w[k], vertex_normal_jvp_world(g, dE), acc);
     }
 }
 

@@ -2014,6 +2014,80 @@ __device__ __forceinline__ hf_vd_hit vdirect_grad_hit(v3 gVd, v3 po, float t) {
     return hf_vd_hit{ mk3(gVd.x * it, gVd.y * it, gVd.z * it), -dot3(gVd, po) * it * it };
 }
 
+// ---- dL/d(to_world): the slab reducer (hf_adjoint_transform, hf_sample_position_adjoint_transform).  Every lane keeps
+// its 12 partial sums in registers across its grid-stride loop.  At the end a block sums them (a butterfly over the
+// wave's 64 lanes, then the block's four waves through LDS, in a fixed order) and stores its 12 sums to its row of a
+// slab; hf_xform_sum_kernel then adds the slab's rows, in a fixed order, into the caller's 12 floats.  No float
+// atomics: 16 k blocks x 12 same-address atomics would serialise, and the slab keeps the result bitwise repeatable.
+// The grid of these launches is capped lower than HF_FLAT_GRID_CAP so that the slab (HF_XFORM_GRID_CAP x 48 bytes) fits
+// every scratch block of the handle's ring, the ones reserved for captured launches included (hf_capi.cpp).  Measured
+// on the bench wavefront (hf_adjoint_transform with the heights, median of 20): 2048 blocks 0.784 ms, 5120 0.722 ms,
+// 16384 0.962 ms (profiles/transform_grad/). ----
+#ifndef HF_XFORM_GRID_CAP
+#define HF_XFORM_GRID_CAP 5120
+#endif
+size_t hf_xform_slab_bytes(size_t n) {
+    return (size_t) (n ? grid_for(n, HF_XFORM_GRID_CAP) : HF_XFORM_GRID_CAP) * 12u * sizeof(float);
+}
+// sum over the 64 lanes, the same in every lane (xor butterfly: each step adds two values that commute exactly)
+__device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+// the block's sums of M into slab row blockIdx.x; every thread of the block calls it
+__device__ __forceinline__ void xform_block_store(const float M[12], float *slab) {
+    __shared__ float s_red[HF_BLOCK / 64][12];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        const float v = wave_sum_f32(M[j]);
+        if (lane == 0u) s_red[w][j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12u) {
+        float v = s_red[0][threadIdx.x];
+#pragma unroll
+        for (int k = 1; k < HF_BLOCK / 64; ++k) v += s_red[k][threadIdx.x];
+        slab[(size_t) blockIdx.x * 12u + threadIdx.x] = v;
+    }
+}
+// out[j] += sum over the slab's rows of column j: every thread sums every HF_BLOCK-th row in fp64 (a row is three
+// 16-byte loads; consecutive threads read consecutive rows), then a fixed-order tree over the block through LDS.  (A
+// first form, 16 threads per column striding over the rows one float at a time, took 117 us for 5120 rows.)
+__global__ __launch_bounds__(HF_BLOCK) void hf_xform_sum_kernel(const float *__restrict__ slab, uint32_t rows,
+                                                                 float *__restrict__ out) {
+    __shared__ double s_part[HF_BLOCK][13]; // (13: the rows of 12 spread over the banks)
+    const uint32_t t = threadIdx.x;
+    double acc[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) acc[j] = 0.0;
+    for (uint32_t b = t; b < rows; b += HF_BLOCK) {
+        const float4 *r = reinterpret_cast<const float4 *>(slab + (size_t) b * 12u); // 48-byte rows of a 256-byte-aligned block
+        const float4 v[3] = { r[0], r[1], r[2] };
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc[4 * k + 0] += (double) v[k].x; acc[4 * k + 1] += (double) v[k].y;
+            acc[4 * k + 2] += (double) v[k].z; acc[4 * k + 3] += (double) v[k].w;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 12; ++j) s_part[t][j] = acc[j];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = HF_BLOCK / 2; h > 0; h >>= 1) {
+        if (t < h) {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) s_part[t][j] += s_part[t + h][j];
+        }
+        __syncthreads();
+    }
+    if (t < 12u) out[t] += (float) s_part[0][t];
+}
+static void xform_sum(const float *slab, int rows, float *out, hipStream_t stream) {
+    hipLaunchKernelGGL(hf_xform_sum_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, slab, (uint32_t) rows, out);
+}
+
 // The one kernel argument.  ~45 pointers and the field by value do not fit the scalar register file: held across the
 // loop body they were spilled into vector-register lanes (108 SGPR spills, 342 v_readlane / v_writelane).  As in the
 // traversal kernel, everything is read from the kernarg segment where it is used (scalar loads that hit the constant
@@ -2045,8 +2119,11 @@ __device__ __forceinline__ float ldu(const float *p, size_t ub, uint32_t lo) { r
 // the barycentrics (the Moeller-Trumbore reverse below) and through the three vertex normals: the VJP of vertex_normal
 // is evaluated per hit, on the fly, and its 7 contributions per vertex (the vertex and its 1-ring: up to 12 texels per
 // hit) go through the same LDS tile as the positions' three.  acc: the wave's tile (TILE x TILE floats of LDS).
-template <bool RAYGRAD, bool SMOOTH>
-__device__ __forceinline__ void adjoint_body(float *acc) {
+// XFORM (hf_adjoint_xform_kernel, hf_adjoint_xform_smooth_kernel): also dL/d(to_world) = sum over the hit's vertices of
+// dL/dP_k (q_k, 1)^T, in M across the loop, plus (smooth) the 1-rings of the three vertex normals; the block's sums
+// go to its row of `slab` (xform_block_store).
+template <bool RAYGRAD, bool SMOOTH, bool XFORM = false>
+__device__ __forceinline__ void adjoint_body(float *acc, float *slab = nullptr) {
     // Wave-level pre-reduction of the scatter: the hits of one wave (one pixel's samples for
     // primary rays) fall on a few dozen vertices, so their three contributions each are first
     // summed into a 32x32-texel LDS tile anchored near the wave's first hit (ds_add_f32) and the
@@ -2055,6 +2132,9 @@ __device__ __forceinline__ void adjoint_body(float *acc) {
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t k = lane; k < HF_ADJ_TILE * HF_ADJ_TILE; k += 64) acc[k] = 0.f;
     uint32_t row_lo = 0xFFFFFFFFu, row_hi = 0u; // rows this lane scattered to (hf_adjoint_rows)
+    float M[12]; // XFORM: this lane's dL/d(to_world)
+#pragma unroll
+    for (int j = 0; j < 12; ++j) M[j] = 0.f;
     const size_t stride = (size_t) gridDim.x * HF_BLOCK;
     for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u);; ub += stride) { // whole waves stay in the loop (ballots below)
         hf_adj_kargs ka = adj_kargs();
@@ -2174,6 +2254,14 @@ __device__ __forceinline__ void adjoint_body(float *acc) {
             axpy3(1.f, gdp0, gP1); axpy3(-1.f, gdp0, gP0);
             axpy3(1.f, gdp1, gP2); axpy3(-1.f, gdp1, gP0);
 
+            if constexpr (XFORM) {
+                if (!detach) { // P_k = [A | t] (q_k, 1)
+                    v3 q[3];
+                    prim_local(f, vi, vj, q);
+                    xform_grad_point(M, gP0, q[0]); xform_grad_point(M, gP1, q[1]); xform_grad_point(M, gP2, q[2]);
+                    if (SMOOTH && sm) vertex_normals_vjp_xform(f, vi, vj, gnv, M);
+                }
+            }
             if (!detach && ka->grad_h) { // dP_k/dh_k = s * (third column of to_world)
                 const v3 ez = mk3(f.to_world[2], f.to_world[6], f.to_world[10]);
                 gh[0] = f.s * dot3(ez, gP0); gh[1] = f.s * dot3(ez, gP1); gh[2] = f.s * dot3(ez, gP2);
@@ -2225,6 +2313,7 @@ __device__ __forceinline__ void adjoint_body(float *acc) {
             if (wh > __hip_atomic_load(band + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(band + 1, wh);
         }
     }
+    if constexpr (XFORM) xform_block_store(M, slab);
 }
 template <bool RAYGRAD>
 __global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_kernel(hf_adjoint_args a_) {
@@ -2238,17 +2327,40 @@ __global__ __launch_bounds__(HF_BLOCK, 4) void hf_adjoint_smooth_kernel(hf_adjoi
     __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
     adjoint_body<RAYGRAD, true>(s_acc[threadIdx.x >> 6]);
 }
+// the transform-gradient instantiations.  Flat: the bound of hf_adjoint_kernel (87 / 96 VGPRs).  Smooth: one wave
+// per SIMD less than hf_adjoint_smooth_kernel -- at 128 VGPRs the 12 accumulators and the 1-ring VJP of the vertex
+// normals spilled 27 / 47 registers (144 / 176 bytes of private segment per lane)
+template <bool RAYGRAD>
+__global__ __launch_bounds__(HF_BLOCK, 5) void hf_adjoint_xform_kernel(hf_adjoint_args a_, float *slab) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<RAYGRAD, false, true>(s_acc[threadIdx.x >> 6], slab);
+}
+template <bool RAYGRAD>
+__global__ __launch_bounds__(HF_BLOCK, 3) void hf_adjoint_xform_smooth_kernel(hf_adjoint_args a_, float *slab) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<RAYGRAD, true, true>(s_acc[threadIdx.x >> 6], slab);
+}
 
 void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, const hf_si_grad_t *gs, uint32_t flags, float *grad_h,
                        float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream,
-                       const float4 *vn) {
+                       const float4 *vn, float *grad_to_world, void *slab) {
     if (n == 0) return;
     hf_adjoint_args a;
     a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.g = *gs; a.flags = flags; a.grad_h = grad_h;
     a.row_band = row_band; a.vn = vn;
     for (int k = 0; k < 3; ++k) { a.go[k] = grad_o ? grad_o[k] : nullptr; a.gd[k] = grad_d ? grad_d[k] : nullptr; }
     const bool rg = grad_o || grad_d;
+    if (grad_to_world) { // slab: hf_xform_slab_bytes(n), this launch's alone
+        void (*kx)(hf_adjoint_args, float *) = vn ? (rg ? hf_adjoint_xform_smooth_kernel<true> : hf_adjoint_xform_smooth_kernel<false>)
+                                                  : (rg ? hf_adjoint_xform_kernel<true> : hf_adjoint_xform_kernel<false>);
+        const int grid = grid_for(n, HF_XFORM_GRID_CAP);
+        hipLaunchKernelGGL(kx, dim3(grid), dim3(HF_BLOCK), 0, stream, a, (float *) slab);
+        xform_sum((const float *) slab, grid, grad_to_world, stream);
+        return;
+    }
     void (*kernel)(hf_adjoint_args) = vn ? (rg ? hf_adjoint_smooth_kernel<true> : hf_adjoint_smooth_kernel<false>)
                                          : (rg ? hf_adjoint_kernel<true> : hf_adjoint_kernel<false>);
     hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a);
@@ -2279,8 +2391,15 @@ typedef const __attribute__((address_space(4))) hf_tangent_args *hf_tan_kargs;
 // RAYTAN: d_o or d_d is given (without them the ray terms are dead code).
 // SMOOTH (hf_tangent_smooth_kernel): sh_n is the interpolated vertex normal; its tangent takes the barycentric tangents
 // and the tangents of the three vertex normals, evaluated on the fly from h and dh (vertex_normal_jvp: no atomics).
-template <bool RAYTAN, bool SMOOTH>
-__device__ __forceinline__ void tangent_body() {
+// XFORM (hf_tangent_xform_kernel, hf_tangent_xform_smooth_kernel): the vertices also move by dM (q_k, 1) for the tangent
+// dM (12 device floats) of to_world, and so do the 1-rings of the vertex normals (vertex_normals_jvp_xform).
+template <bool RAYTAN, bool SMOOTH, bool XFORM = false>
+__device__ __forceinline__ void tangent_body(const float *dMp = nullptr) {
+    float dM[12]; // XFORM: wave-uniform
+    if constexpr (XFORM) {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) dM[j] = dMp[j];
+    }
     const uint32_t lane = threadIdx.x & 63u;
     const size_t stride = (size_t) gridDim.x * HF_BLOCK;
     for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u);; ub += stride) {
@@ -2318,6 +2437,14 @@ __device__ __forceinline__ void tangent_body() {
         float U[3], V[3];
         int vi[3], vj[3];
         prim_world(f, prim, P, U, V, vi, vj, dP, detach ? nullptr : ka->dh);
+        if constexpr (XFORM) {
+            if (!detach) {
+                v3 q[3];
+                prim_local(f, vi, vj, q);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dP[k] = dP[k] + xform_point(dM, q[k]);
+            }
+        }
         const bool sm = SMOOTH && smooth_sh(flags);
         v3 NV[3];
         if (sm) load_vn(f, ka->vn, vi, vj, NV);
@@ -2366,7 +2493,12 @@ __device__ __forceinline__ void tangent_body() {
             axpy3(du, NV[1] - NV[0], dns);
             axpy3(dv, NV[2] - NV[0], dns);
             const float *dh = detach ? nullptr : ka->dh;
-            if (dh) {
+            if constexpr (XFORM) {
+                if (!detach) {
+                    const float bk[3] = { b0, b1, b2 };
+                    vertex_normals_jvp_xform(f, vi, vj, height_axis(f), bk, dh, dM, dns);
+                }
+            } else if (dh) {
                 const float bk[3] = { b0, b1, b2 };
                 vertex_normals_jvp(f, vi, vj, height_axis(f), bk, dh, dns);
             }
@@ -2395,10 +2527,21 @@ template <bool RAYTAN>
 __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_kernel(hf_tangent_args a_) { (void) a_; tangent_body<RAYTAN, false>(); }
 template <bool RAYTAN>
 __global__ __launch_bounds__(HF_BLOCK) void hf_tangent_smooth_kernel(hf_tangent_args a_) { (void) a_; tangent_body<RAYTAN, true>(); }
+template <bool RAYTAN>
+__global__ __launch_bounds__(HF_BLOCK) void hf_tangent_xform_kernel(hf_tangent_args a_, const float *dM) {
+    (void) a_;
+    tangent_body<RAYTAN, false, true>(dM);
+}
+template <bool RAYTAN>
+__global__ __launch_bounds__(HF_BLOCK) void hf_tangent_xform_smooth_kernel(hf_tangent_args a_, const float *dM) {
+    (void) a_;
+    tangent_body<RAYTAN, true, true>(dM);
+}
 
 void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, uint32_t flags, const float *dh, const float *const d_o[3],
-                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream, const float4 *vn) {
+                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream, const float4 *vn,
+                       const float *d_to_world) {
     if (n == 0) return;
     hf_tangent_args a;
     a.f = f; a.n = n; a.rays = *rays; a.pi = *pi; a.active = active; a.dh = dh; a.out = *out; a.flags = flags; a.vn = vn;
@@ -2408,6 +2551,12 @@ void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, c
         raytan = raytan || a.d_o[k] || a.d_d[k];
     }
     const dim3 grid(grid_for(n, HF_SI_GRID_CAP)), block(HF_BLOCK);
+    if (d_to_world) {
+        void (*kx)(hf_tangent_args, const float *) = vn ? (raytan ? hf_tangent_xform_smooth_kernel<true> : hf_tangent_xform_smooth_kernel<false>)
+                                                        : (raytan ? hf_tangent_xform_kernel<true> : hf_tangent_xform_kernel<false>);
+        hipLaunchKernelGGL(kx, grid, block, 0, stream, a, d_to_world);
+        return;
+    }
     void (*kernel)(hf_tangent_args) = vn ? (raytan ? hf_tangent_smooth_kernel<true> : hf_tangent_smooth_kernel<false>)
                                          : (raytan ? hf_tangent_kernel<true> : hf_tangent_kernel<false>);
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
@@ -3295,8 +3444,13 @@ __device__ __forceinline__ bool sample_diff_setup(const hf_sample_diff_args &a, 
     return true;
 }
 
-template <bool SMOOTH>
-__global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_kernel(hf_sample_diff_args a) {
+// XFORM (hf_sample_adjoint_xform_kernel): also dL/d(to_world) from the world-space gradients of the three vertices
+// (and, smooth, of the 1-rings), block sums to `slab` (xform_block_store); grad_h may then be NULL
+template <bool SMOOTH, bool XFORM = false>
+__device__ __forceinline__ void sample_adjoint_body(const hf_sample_diff_args &a, float *slab = nullptr) {
+    float M[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) M[j] = 0.f;
     const size_t stride = (size_t) gridDim.x * HF_BLOCK;
     for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
         uint32_t prim;
@@ -3328,27 +3482,63 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_kernel(hf_sample_d
             face_normal_vjp(e0, e1, dnormalize(n, r, gn), ez, g1, g2);
             gh[1] += g1; gh[2] += g2; gh[0] -= g1 + g2;
         }
+        if constexpr (XFORM) { // p = sum b_k P_k; flat n = N / |N|, N = cross(e0, e1)
+            v3 gP[3] = { gp * b0, gp * bx, gp * by };
+            if (!SMOOTH) {
+                const v3 e0 = P[1] - P[0], e1 = P[2] - P[0];
+                const auto [n, r] = unit_normal(e0, e1);
+                const v3 gN = dnormalize(n, r, gn);
+                const v3 ge0 = cross3(e1, gN), ge1 = cross3(gN, e0);
+                gP[1] = gP[1] + ge0; gP[2] = gP[2] + ge1; gP[0] = gP[0] - (ge0 + ge1);
+            }
+            v3 q[3];
+            prim_local(f, vi, vj, q);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) xform_grad_point(M, gP[k], q[k]);
+            if (SMOOTH) vertex_normals_vjp_xform(f, vi, vj, gB, M);
+            if (!a.grad_h) continue;
+        }
         float *grad_h = a.grad_h;
         auto add = [&](int r, int c, float g) { atomicAdd(grad_h + (size_t) r * f.W + c, g); };
 #pragma unroll
         for (int k = 0; k < 3; ++k) add(vi[k], vj[k], gh[k]);
         if (SMOOTH) vertex_normals_vjp(f, vi, vj, ez, gB, add);
     }
+    if constexpr (XFORM) xform_block_store(M, slab);
+}
+template <bool SMOOTH>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_kernel(hf_sample_diff_args a) { sample_adjoint_body<SMOOTH>(a); }
+template <bool SMOOTH>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sample_adjoint_xform_kernel(hf_sample_diff_args a, float *slab) {
+    sample_adjoint_body<SMOOTH, true>(a, slab);
 }
 
-template <bool SMOOTH>
-__global__ __launch_bounds__(HF_BLOCK) void hf_sample_tangent_kernel(hf_sample_diff_args a) {
+// XFORM (hf_sample_tangent_xform_kernel): the vertices also move by dM (q_k, 1) for the tangent dM (12 device floats)
+// of to_world; a.dh may then be NULL
+template <bool SMOOTH, bool XFORM = false>
+__device__ __forceinline__ void sample_tangent_body(const hf_sample_diff_args &a, const float *dMp = nullptr) {
+    float dM[12];
+    if constexpr (XFORM) {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) dM[j] = dMp[j];
+    }
     const size_t stride = (size_t) gridDim.x * HF_BLOCK;
     for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += stride) {
         uint32_t prim;
         float bx, by;
         v3 dp = mk3(0.f, 0.f, 0.f), dn = dp;
-        if (a.dh && sample_diff_setup(a, i, prim, bx, by)) {
+        if ((XFORM || a.dh) && sample_diff_setup(a, i, prim, bx, by)) {
             const hf_dev_field &f = a.f;
             v3 P[3], dP[3];
             float U[3], V[3];
             int vi[3], vj[3];
             prim_world(f, prim, P, U, V, vi, vj, dP, a.dh);
+            if constexpr (XFORM) {
+                v3 q[3];
+                prim_local(f, vi, vj, q);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dP[k] = dP[k] + xform_point(dM, q[k]);
+            }
             const float b0 = 1.f - bx - by;
             dp = mk3(dP[0].x * b0 + dP[1].x * bx + dP[2].x * by, dP[0].y * b0 + dP[1].y * bx + dP[2].y * by,
                      dP[0].z * b0 + dP[1].z * bx + dP[2].z * by);
@@ -3359,7 +3549,8 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sample_tangent_kernel(hf_sample_d
                 const float r = rsqrt_ieee(dot3(B, B));
                 v3 dB = mk3(0.f, 0.f, 0.f);
                 const float w[3] = { b0, bx, by };
-                vertex_normals_jvp(f, vi, vj, height_axis(f), w, a.dh, dB);
+                if constexpr (XFORM) vertex_normals_jvp_xform(f, vi, vj, height_axis(f), w, a.dh, dM, dB);
+                else vertex_normals_jvp(f, vi, vj, height_axis(f), w, a.dh, dB);
                 dn = dnormalize(B * r, r, dB);
             } else {
                 const v3 e0 = P[1] - P[0], e1 = P[2] - P[0], de0 = dP[1] - dP[0], de1 = dP[2] - dP[0];
@@ -3372,6 +3563,12 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sample_tangent_kernel(hf_sample_d
         if (a.dn[0]) { a.dn[0][i] = dn.x; a.dn[1][i] = dn.y; a.dn[2][i] = dn.z; }
     }
 }
+template <bool SMOOTH>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sample_tangent_kernel(hf_sample_diff_args a) { sample_tangent_body<SMOOTH>(a); }
+template <bool SMOOTH>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sample_tangent_xform_kernel(hf_sample_diff_args a, const float *dM) {
+    sample_tangent_body<SMOOTH, true>(a, dM);
+}
 
 static hf_sample_diff_args sample_diff_args(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
                                             const uint8_t *active, const float4 *vn) {
@@ -3381,21 +3578,34 @@ static hf_sample_diff_args sample_diff_args(const hf_dev_field &f, size_t n, con
 }
 void hf_launch_sample_position_adjoint(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
                                        const uint8_t *active, const float *const gp[3], const float *const gn[3],
-                                       float *grad_h, const float4 *vn, hipStream_t stream) {
+                                       float *grad_h, const float4 *vn, hipStream_t stream, float *grad_to_world,
+                                       void *slab) {
     if (n == 0 || (!gp && !gn)) return;
     hf_sample_diff_args a = sample_diff_args(f, n, prim, b, active, vn);
     for (int c = 0; c < 3; ++c) { a.gp[c] = gp ? gp[c] : nullptr; a.gn[c] = gn ? gn[c] : nullptr; }
     a.grad_h = grad_h;
+    if (grad_to_world) { // slab: hf_xform_slab_bytes(n), this launch's alone
+        const int grid = grid_for(n, HF_XFORM_GRID_CAP);
+        hipLaunchKernelGGL(vn ? hf_sample_adjoint_xform_kernel<true> : hf_sample_adjoint_xform_kernel<false>, dim3(grid),
+                           dim3(HF_BLOCK), 0, stream, a, (float *) slab);
+        xform_sum((const float *) slab, grid, grad_to_world, stream);
+        return;
+    }
     hipLaunchKernelGGL(vn ? hf_sample_adjoint_kernel<true> : hf_sample_adjoint_kernel<false>, dim3(grid_for(n)),
                        dim3(HF_BLOCK), 0, stream, a);
 }
 void hf_launch_sample_position_tangent(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
                                        const uint8_t *active, const float *dh, float *const dp[3], float *const dn[3],
-                                       const float4 *vn, hipStream_t stream) {
+                                       const float4 *vn, hipStream_t stream, const float *d_to_world) {
     if (n == 0 || (!dp && !dn)) return;
     hf_sample_diff_args a = sample_diff_args(f, n, prim, b, active, vn);
     a.dh = dh;
     for (int c = 0; c < 3; ++c) { a.dp[c] = dp ? dp[c] : nullptr; a.dn[c] = dn ? dn[c] : nullptr; }
+    if (d_to_world) {
+        hipLaunchKernelGGL(vn ? hf_sample_tangent_xform_kernel<true> : hf_sample_tangent_xform_kernel<false>,
+                           dim3(grid_for(n)), dim3(HF_BLOCK), 0, stream, a, d_to_world);
+        return;
+    }
     hipLaunchKernelGGL(vn ? hf_sample_tangent_kernel<true> : hf_sample_tangent_kernel<false>, dim3(grid_for(n)),
                        dim3(HF_BLOCK), 0, stream, a);
 }

@@ -22,11 +22,17 @@ void hf_launch_si(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const 
 void hf_launch_adjoint(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, const hf_si_grad_t *gs, uint32_t flags, float *grad_h,
                        float *const grad_o[3], float *const grad_d[3], uint32_t *row_band, hipStream_t stream,
-                       const float4 *vn = nullptr);
-// forward mode of compute_si (hf_tangent): dh / d_o / d_d may be NULL (zero tangents)
+                       const float4 *vn = nullptr, float *grad_to_world = nullptr, void *slab = nullptr);
+// grad_to_world (12 device floats, accumulated; hf_adjoint_transform, hf_sample_position_adjoint_transform): the launch
+// also writes its blocks' partial sums to `slab`, hf_xform_slab_bytes(n) bytes that no other pending launch may use,
+// and adds them up.  hf_xform_slab_bytes(0): the most any launch needs.
+size_t hf_xform_slab_bytes(size_t n);
+// forward mode of compute_si (hf_tangent): dh / d_o / d_d may be NULL (zero tangents); d_to_world (12 device floats,
+// hf_tangent_transform): the tangent of to_world, NULL = zero
 void hf_launch_tangent(const hf_dev_field &f, size_t n, const hf_rays_t *rays, const hf_pi_const_t *pi,
                        const uint8_t *active, uint32_t flags, const float *dh, const float *const d_o[3],
-                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream, const float4 *vn = nullptr);
+                       const float *const d_d[3], const hf_si_tangent_t *out, hipStream_t stream, const float4 *vn = nullptr,
+                       const float *d_to_world = nullptr);
 // smooth shading: the vertex normals of the current heights and transform into vn (W H float4)
 void hf_launch_build_normals(const hf_dev_field &f, float4 *vn, hipStream_t stream);
 // hf_shading_derivatives: dn_du / dn_dv rows (NULL rows are not written); vn NULL = flat shading = zeros
@@ -107,10 +113,11 @@ void hf_launch_sample_position(const hf_dev_field &f, const hf_area_table &t, si
                                const uint8_t *active, const hf_position_sample_t &out, const float4 *vn, hipStream_t stream);
 void hf_launch_sample_position_adjoint(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
                                        const uint8_t *active, const float *const gp[3], const float *const gn[3],
-                                       float *grad_h, const float4 *vn, hipStream_t stream);
+                                       float *grad_h, const float4 *vn, hipStream_t stream,
+                                       float *grad_to_world = nullptr, void *slab = nullptr);
 void hf_launch_sample_position_tangent(const hf_dev_field &f, size_t n, const uint32_t *prim, const float *const b[2],
                                        const uint8_t *active, const float *dh, float *const dp[3], float *const dn[3],
-                                       const float4 *vn, hipStream_t stream);
+                                       const float4 *vn, hipStream_t stream, const float *d_to_world = nullptr);
 // ---- shape attributes (hf_eval_attribute / _adjoint / _tangent): the buffers are the caller's ----
 struct hf_attr_args {
     hf_dev_field f;

@@ -179,35 +179,38 @@ class DirectionSample3f(PositionSample3f):
 
 class _SamplePositionOp(torch.autograd.Function):
     """Differentiable [6, n] block (p, n) of sample_position; backward = hf_sample_position_adjoint (atomic scatter of
-    dL/dheight), jvp = hf_sample_position_tangent.  The sampled triangle and b are frozen (detached, as build_pmf)."""
+    dL/dheight), jvp = hf_sample_position_tangent.  The sampled triangle and b are frozen (detached, as build_pmf).
+    to_world (differentiable_to_world shapes, else None): hf_sample_position_adjoint_transform / _tangent_transform."""
 
     @staticmethod
-    def forward(ctx, shape, heights, prim, b, active, block):
+    def forward(ctx, shape, heights, prim, b, active, block, to_world=None):
         ctx.shape, ctx.active = shape, active
         ctx.save_for_backward(prim, b)
         ctx.save_for_forward(prim, b)
-        ctx.h_version = shape._heights_version
+        ctx.h_version = shape._param_version()
+        ctx.tw_like = _tw_like(to_world)
         return block
 
     @staticmethod
-    def jvp(ctx, _shape, dh, *_):
+    def jvp(ctx, _shape, dh, _prim, _b, _active, _block, dtw=None):
         shape = ctx.shape
         prim, b = ctx.saved_tensors
-        if ctx.h_version != shape._heights_version:
+        if ctx.h_version != shape._param_version():
             raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
-        return shape._sample_tangent_raw(prim, b, ctx.active, dh)
+        return shape._sample_tangent_raw(prim, b, ctx.active, dh, _tw_tangent(dtw))
 
     @staticmethod
     def backward(ctx, g):
         shape = ctx.shape
         prim, b = ctx.saved_tensors
-        if ctx.h_version != shape._heights_version:
+        if ctx.h_version != shape._param_version():
             raise RuntimeError("heightfield parameters changed between forward and backward")
-        grad_h = None
-        if ctx.needs_input_grad[1]:
-            grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=prim.device)
-            shape._sample_adjoint_raw(prim, b, ctx.active, g.contiguous().to(torch.float32), grad_h)
-        return None, grad_h, None, None, None, None
+        need_h, need_tw = ctx.needs_input_grad[1], ctx.needs_input_grad[6]
+        grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=prim.device) if need_h else None
+        grad_tw = torch.zeros(12, dtype=torch.float32, device=prim.device) if need_tw else None
+        if need_h or need_tw:
+            shape._sample_adjoint_raw(prim, b, ctx.active, g.contiguous().to(torch.float32), grad_h, grad_tw)
+        return None, grad_h, None, None, None, None, (_tw_grad(grad_tw, ctx.tw_like) if need_tw else None)
 
 
 class _AttributeOp(torch.autograd.Function):
@@ -221,14 +224,14 @@ class _AttributeOp(torch.autograd.Function):
         p = p.detach().contiguous() if p is not None else None
         ctx.save_for_backward(attr.detach(), p, prim, t)
         ctx.save_for_forward(attr.detach(), p, prim, t)
-        ctx.h_version = shape._heights_version
+        ctx.h_version = shape._param_version()
         return value
 
     @staticmethod
     def jvp(ctx, _shape, _name, dattr, dp, dh, *_):
         shape = ctx.shape
         attr, p, prim, t = ctx.saved_tensors
-        if ctx.h_version != shape._heights_version:
+        if ctx.h_version != shape._param_version():
             raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
         return shape._attr_tangent_raw(ctx.name, attr, p, prim, t, ctx.active, dattr, dp, dh)
 
@@ -236,7 +239,7 @@ class _AttributeOp(torch.autograd.Function):
     def backward(ctx, g):
         shape = ctx.shape
         attr, p, prim, t = ctx.saved_tensors
-        if ctx.h_version != shape._heights_version:
+        if ctx.h_version != shape._param_version():
             raise RuntimeError("heightfield parameters changed between forward and backward")
         need_a, need_p, need_h = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         ga, gp, gh = shape._attr_adjoint_raw(ctx.name, attr, p, prim, t, ctx.active, g.contiguous().to(torch.float32),
@@ -274,39 +277,65 @@ def _fill(struct, layout, addrs):
 
 
 class _SurfaceInteractionOp(torch.autograd.Function):
-    """Differentiable SI block [18, n]; backward = hf_adjoint (atomic scatter of dL/dheight), jvp = hf_tangent."""
+    """Differentiable SI block [18, n]; backward = hf_adjoint (atomic scatter of dL/dheight), jvp = hf_tangent.
+    to_world (differentiable_to_world shapes, else None): hf_adjoint_transform / hf_tangent_transform."""
 
     @staticmethod
-    def forward(ctx, shape, heights, o, d, maxt, t, uv, prim, flags, active, diff_block):
+    def forward(ctx, shape, heights, o, d, maxt, t, uv, prim, flags, active, diff_block, to_world=None):
         ctx.shape, ctx.flags, ctx.active = shape, flags, active
         ctx.save_for_backward(o, d, maxt, t, uv, prim)
         ctx.save_for_forward(o, d, maxt, t, uv, prim)
-        ctx.h_version = shape._heights_version
+        ctx.h_version = shape._param_version()
+        ctx.tw_like = _tw_like(to_world)
         return diff_block
 
     @staticmethod
-    def jvp(ctx, _shape, dh, do, dd, *_):
+    def jvp(ctx, _shape, dh, do, dd, _maxt, _t, _uv, _prim, _flags, _active, _diff, dtw=None):
         shape = ctx.shape
         o, d, maxt, t, uv, prim = ctx.saved_tensors
-        if ctx.h_version != shape._heights_version:
+        if ctx.h_version != shape._param_version():
             raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
-        return shape._tangent_raw(o, d, maxt, t, uv, prim, ctx.flags, ctx.active, dh, do, dd)
+        return shape._tangent_raw(o, d, maxt, t, uv, prim, ctx.flags, ctx.active, dh, do, dd, _tw_tangent(dtw))
 
     @staticmethod
     def backward(ctx, g):
         shape = ctx.shape
         o, d, maxt, t, uv, prim = ctx.saved_tensors
-        if ctx.h_version != shape._heights_version:
+        if ctx.h_version != shape._param_version():
             raise RuntimeError("heightfield parameters changed between forward and backward")
         n = o.shape[1]
         g = g.contiguous().to(torch.float32)
         need_h, need_o, need_d = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        need_tw = ctx.needs_input_grad[11]
         grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=o.device) if need_h else None
         grad_od = torch.empty((6, n), dtype=torch.float32, device=o.device) if (need_o or need_d) else None
-        shape._adjoint_raw(o, d, maxt, t, uv, prim, ctx.flags, ctx.active, g, grad_h, grad_od)
+        grad_tw = torch.zeros(12, dtype=torch.float32, device=o.device) if need_tw else None
+        shape._adjoint_raw(o, d, maxt, t, uv, prim, ctx.flags, ctx.active, g, grad_h, grad_od, grad_tw=grad_tw)
         go = grad_od[0:3] if need_o else None
         gd = grad_od[3:6] if need_d else None
-        return None, grad_h, go, gd, None, None, None, None, None, None, None
+        return (None, grad_h, go, gd, None, None, None, None, None, None, None,
+                _tw_grad(grad_tw, ctx.tw_like) if need_tw else None)
+
+
+def _tw_like(to_world):
+    """(shape, dtype, device) of a to_world input, None without one"""
+    return None if to_world is None else (tuple(to_world.shape), to_world.dtype, to_world.device)
+
+
+def _tw_grad(grad12, like):
+    """the 12 floats of dL/d(to_world) as a gradient of the user's 3x4 / 4x4 tensor (a 4x4's last row gets zeros)"""
+    shape, dtype, device = like
+    g = grad12.reshape(3, 4)
+    if shape[0] == 4:
+        g = torch.cat([g, torch.zeros((1, 4), dtype=g.dtype, device=g.device)])
+    return g.reshape(shape).to(device=device, dtype=dtype)
+
+
+def _tw_tangent(dtw):
+    """a 3x4 / 4x4 tangent of to_world as the 12 contiguous float32 device values of the C ABI (None: zero)"""
+    if dtw is None:
+        return None
+    return dtw.detach().reshape(-1)[:12].to(torch.float32).contiguous()
 
 
 class Heightfield:
@@ -331,6 +360,8 @@ class Heightfield:
         to_world = props.pop("to_world", None)
         self.flip_normals = bool(props.pop("flip_normals", False))
         face_normals = bool(props.pop("face_normals", True))
+        # to_world Differentiable | Discontinuous (rectangle.cpp:128) instead of NonDifferentiable; off by default
+        self.differentiable_to_world = bool(props.pop("differentiable_to_world", False))
         device = props.pop("device", None)
         attr_props = [(k, props.pop(k)) for k in sorted(props) if k.startswith(("vertex_", "face_"))]
         if props:
@@ -349,6 +380,7 @@ class Heightfield:
         tw = torch.eye(4, dtype=torch.float64)[:3] if to_world is None else torch.as_tensor(to_world, dtype=torch.float64).cpu()
         tw = tw.reshape(-1)[:12].reshape(3, 4)
         self.to_world = tw.to(torch.float32)
+        self._to_world_in, self._to_world_version = self.to_world, 0
         desc = hf_desc_t()
         desc.width, desc.height = self.width, self.height
         desc.max_height = self.max_height
@@ -394,7 +426,8 @@ class Heightfield:
     def traverse(self, callback):
         callback.put_parameter("heightfield", self.heightfield, ParamFlags.Differentiable | ParamFlags.Discontinuous)
         callback.put_parameter("max_height", self.max_height, ParamFlags.NonDifferentiable)
-        callback.put_parameter("to_world", self.to_world, ParamFlags.NonDifferentiable)
+        callback.put_parameter("to_world", self.to_world, ParamFlags.Differentiable | ParamFlags.Discontinuous
+                               if self.differentiable_to_world else ParamFlags.NonDifferentiable)
         for name, buf in self.attributes.items():   # mesh.cpp:74-76: every attribute is shown as differentiable
             callback.put_parameter(name, buf, ParamFlags.Differentiable)
 
@@ -420,9 +453,28 @@ class Heightfield:
             self._heights_keepalive = hd
             self._heights_version += 1
         if not keys or "to_world" in keys:
-            tw = (C.c_float * 12)(*self.to_world.reshape(-1).tolist())
+            tw = (C.c_float * 12)(*self.to_world.detach().reshape(-1)[:12].tolist())
             check(_capi.lib().hf_set_transform(self._h, tw, None))
+            # the tensor the kernels now use: the autograd input of every differentiable op until the next change
+            self._to_world_in = self.to_world
+            self._to_world_version += 1
         self.mark_dirty()
+
+    def _param_version(self):
+        """what a differentiable op checks between its primal and its derivative pass: the heights' version and, for
+        differentiable_to_world shapes, the transform's"""
+        return (self._heights_version, self._to_world_version if self.differentiable_to_world else 0)
+
+    def _to_world_live(self, detach=False):
+        """the to_world tensor the ops take as an input when a derivative is wanted with respect to it, else None"""
+        if not self.differentiable_to_world or detach:
+            return None
+        tw = self._to_world_in
+        if not isinstance(tw, torch.Tensor):
+            return None
+        if _has_tangent(tw) or (torch.is_grad_enabled() and tw.requires_grad):
+            return tw
+        return None
 
     def set_face_normals(self, face_normals):
         """Flat (True) or smooth (False) shading.  Smooth: angle-weighted vertex normals, rebuilt with every
@@ -493,8 +545,9 @@ class Heightfield:
         sp = (C.c_void_p * 2)(*_rows(sample, n))
         check(_capi.lib().hf_sample_position(self._h, n, C.byref(sp), ap, C.byref(out), self._stream()))
         h = self.heightfield
-        if (torch.is_grad_enabled() and h.requires_grad) or _has_tangent(h):
-            block = _SamplePositionOp.apply(self, h, prim, rest[3:5], keep, block)
+        tw = self._to_world_live()
+        if (torch.is_grad_enabled() and h.requires_grad) or _has_tangent(h) or tw is not None:
+            block = _SamplePositionOp.apply(self, h, prim, rest[3:5], keep, block, tw)
         ps = PositionSample3f(block[0:3], block[3:6], rest[0:2], time, rest[2], False)
         ps.prim_index, ps.b = prim, rest[3:5]
         return ps
@@ -526,33 +579,50 @@ class Heightfield:
         dp = (ds.d * ds.n).sum(0).abs()
         return pdf * torch.where(dp != 0, (ds.dist * ds.dist) / dp, torch.zeros_like(dp))
 
-    def _sample_adjoint_raw(self, prim, b, active_u8, g, grad_h):
+    def _sample_adjoint_raw(self, prim, b, active_u8, g, grad_h, grad_tw=None):
         n = prim.shape[0]
         rows = _rows(g, n)
         gp, gn = (C.c_void_p * 3)(*rows[0:3]), (C.c_void_p * 3)(*rows[3:6])
         bp = (C.c_void_p * 2)(*_rows(b.contiguous(), n))
-        check(_capi.lib().hf_sample_position_adjoint(self._h, n, prim.data_ptr(), C.byref(bp),
-                                                     active_u8.data_ptr() if active_u8 is not None else None,
+        ap = active_u8.data_ptr() if active_u8 is not None else None
+        if grad_tw is not None:
+            assert grad_tw.numel() == 12 and grad_tw.dtype == torch.float32 and grad_tw.is_contiguous()
+            check(_capi.lib().hf_sample_position_adjoint_transform(
+                self._h, n, prim.data_ptr(), C.byref(bp), ap, C.byref(gp), C.byref(gn),
+                grad_h.data_ptr() if grad_h is not None else None, grad_tw.data_ptr(), self._stream()))
+            return
+        check(_capi.lib().hf_sample_position_adjoint(self._h, n, prim.data_ptr(), C.byref(bp), ap,
                                                      C.byref(gp), C.byref(gn), grad_h.data_ptr(), self._stream()))
 
-    def _sample_tangent_raw(self, prim, b, active_u8, dh):
+    def _sample_tangent_raw(self, prim, b, active_u8, dh, dtw=None):
         n = prim.shape[0]
         out = torch.zeros((6, n), dtype=torch.float32, device=self.device)
-        if dh is None:
+        if dh is None and dtw is None:
             return out
-        dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
-        assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
+        if dh is not None:
+            dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
+            assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
         rows = _rows(out, n)
         dp, dn = (C.c_void_p * 3)(*rows[0:3]), (C.c_void_p * 3)(*rows[3:6])
         bp = (C.c_void_p * 2)(*_rows(b.contiguous(), n))
-        check(_capi.lib().hf_sample_position_tangent(self._h, n, prim.data_ptr(), C.byref(bp),
-                                                     active_u8.data_ptr() if active_u8 is not None else None,
-                                                     dh.data_ptr(), C.byref(dp), C.byref(dn), self._stream()))
+        ap = active_u8.data_ptr() if active_u8 is not None else None
+        dhp = dh.data_ptr() if dh is not None else None
+        if dtw is not None:
+            dtw = _tw_tangent(torch.as_tensor(dtw, device=self.device)).to(self.device)
+            check(_capi.lib().hf_sample_position_tangent_transform(self._h, n, prim.data_ptr(), C.byref(bp), ap, dhp,
+                                                                   dtw.data_ptr(), C.byref(dp), C.byref(dn),
+                                                                   self._stream()))
+            return out
+        check(_capi.lib().hf_sample_position_tangent(self._h, n, prim.data_ptr(), C.byref(bp), ap, dhp,
+                                                     C.byref(dp), C.byref(dn), self._stream()))
         return out
 
-    def sample_position_adjoint(self, ps, grad_p=None, grad_n=None, active=True, grad_heightfield=None):
+    def sample_position_adjoint(self, ps, grad_p=None, grad_n=None, active=True, grad_heightfield=None,
+                                grad_to_world=None):
         """Explicit adjoint of sample_position for the samples of `ps`: accumulates dL/dheight for the upstream
-        gradients grad_p / grad_n ([3, n], None = zero) into grad_heightfield ([H, W])"""
+        gradients grad_p / grad_n ([3, n], None = zero) into grad_heightfield ([H, W]).  grad_to_world (12 contiguous
+        float32 device values, row-major 3x4, optional): dL/d(to_world) is accumulated into it as well
+        (hf_sample_position_adjoint_transform)."""
         n = ps.prim_index.shape[0]
         if grad_heightfield is None:
             grad_heightfield = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
@@ -560,13 +630,14 @@ class Heightfield:
         g = torch.cat([z if grad_p is None else _as_f32(grad_p, self.device).reshape(3, n),
                        z if grad_n is None else _as_f32(grad_n, self.device).reshape(3, n)]).contiguous()
         keep, _ = self._mask(active, n)
-        self._sample_adjoint_raw(ps.prim_index, ps.b, keep, g, grad_heightfield)
+        self._sample_adjoint_raw(ps.prim_index, ps.b, keep, g, grad_heightfield, grad_to_world)
         return grad_heightfield
 
-    def sample_position_tangent(self, ps, dheights, active=True):
-        """Explicit forward mode of sample_position: (dp, dn) ([3, n] each) for the height tangent dheights ([H, W])"""
+    def sample_position_tangent(self, ps, dheights, active=True, d_to_world=None):
+        """Explicit forward mode of sample_position: (dp, dn) ([3, n] each) for the height tangent dheights ([H, W])
+        and the tangent d_to_world (3x4 / 4x4 / 12 values) of to_world; either may be None (zero)"""
         keep, _ = self._mask(active, ps.prim_index.shape[0])
-        out = self._sample_tangent_raw(ps.prim_index, ps.b, keep, dheights)
+        out = self._sample_tangent_raw(ps.prim_index, ps.b, keep, dheights, d_to_world)
         return out[0:3], out[3:6]
 
     # ---- shape attributes (Mesh::add_attribute / has_attribute / eval_attribute*, mesh.cpp:905-1004) -------------------
@@ -644,6 +715,10 @@ class Heightfield:
         buf = self.attributes[name]
         value = self._attr_forward_raw(name, buf.detach(), p, prim, t, keep)
         h = self.heightfield
+        if type_ == _capi.HF_ATTR_VERTEX and self._to_world_live() is not None:
+            raise NotImplementedError(
+                f"eval_attribute({name!r}): the derivative of a vertex attribute with respect to to_world is not "
+                "implemented; evaluate it under torch.no_grad() or with a to_world that does not require a gradient")
         live = [buf] + ([si.p, h] if type_ == _capi.HF_ATTR_VERTEX else [])
         if any(_has_tangent(x) for x in live) or (torch.is_grad_enabled() and any(x.requires_grad for x in live)):
             vertex = type_ == _capi.HF_ATTR_VERTEX
@@ -730,7 +805,9 @@ class Heightfield:
         return self._attr_tangent_raw(name, self.attributes[name].detach(), p, prim, t, keep, dattr, dp, dheights)
 
     def parameters_grad_enabled(self):
-        return bool(self.heightfield.requires_grad)
+        tw = self.to_world
+        tw_grad = self.differentiable_to_world and isinstance(tw, torch.Tensor) and tw.requires_grad
+        return bool(self.heightfield.requires_grad or tw_grad)
 
     def mark_dirty(self):
         self._dirty = True
@@ -944,6 +1021,8 @@ class Heightfield:
         # forward mode (torch.autograd.forward_ad): a tangent on the heights or the rays, whatever the grad mode
         if (_has_tangent(self.heightfield) and not detach) or _has_tangent(ray.o) or _has_tangent(ray.d):
             return True
+        if self._to_world_live(detach) is not None:
+            return True
         if not torch.is_grad_enabled():
             return False
         h_live = self.heightfield.requires_grad and not detach
@@ -967,7 +1046,8 @@ class Heightfield:
                                                          C.byref(out), self._stream()))
         if self._wants_grad(ray, ray_flags):
             diff = _SurfaceInteractionOp.apply(self, self.heightfield, ray.o, ray.d, ray.maxt, pi.t, pi.prim_uv,
-                                               pi.prim_index, ray_flags, keep, diff)
+                                               pi.prim_index, ray_flags, keep, diff,
+                                               self._to_world_live(bool(ray_flags & RayFlags.DetachShape)))
         return self._package_si(ray, pi.t, pi.prim_index, diff, aux, ray_flags)
 
     def ray_intersect(self, ray, ray_flags=RayFlags.All, active=True, coherent=None):
@@ -989,13 +1069,14 @@ class Heightfield:
                                                self._stream()))
         if self._wants_grad(ray, ray_flags):
             diff = _SurfaceInteractionOp.apply(self, self.heightfield, ray.o, ray.d, ray.maxt, t, uv, prim,
-                                               ray_flags, keep, diff)
+                                               ray_flags, keep, diff,
+                                               self._to_world_live(bool(ray_flags & RayFlags.DetachShape)))
         si = self._package_si(ray, t, prim, diff, aux, ray_flags)
         si.prim_uv = uv
         return si
 
     # ---- adjoint ------------------------------------------------------------------------------
-    def _adjoint_raw(self, o, d, maxt, t, uv, prim, ray_flags, active_u8, g, grad_h, grad_od, row_band=None):
+    def _adjoint_raw(self, o, d, maxt, t, uv, prim, ray_flags, active_u8, g, grad_h, grad_od, row_band=None, grad_tw=None):
         n = o.shape[1]
         rays = self._rays_struct(o, d, maxt)
         pis = self._pi_struct(t, uv, prim)
@@ -1005,6 +1086,15 @@ class Heightfield:
             rows = _rows(grad_od, n)
             go = (C.c_void_p * 3)(*rows[0:3])
             gd = (C.c_void_p * 3)(*rows[3:6])
+        if grad_tw is not None:
+            assert grad_tw.numel() == 12 and grad_tw.dtype == torch.float32 and grad_tw.is_contiguous()
+            check(_capi.lib().hf_adjoint_transform(
+                self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
+                active_u8.data_ptr() if active_u8 is not None else None, C.byref(gs),
+                grad_h.data_ptr() if grad_h is not None else None, C.byref(go) if go is not None else None,
+                C.byref(gd) if gd is not None else None, row_band.data_ptr() if row_band is not None else None,
+                grad_tw.data_ptr(), self._stream()))
+            return
         check(_capi.lib().hf_adjoint_rows(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
                                           active_u8.data_ptr() if active_u8 is not None else None, C.byref(gs),
                                           grad_h.data_ptr() if grad_h is not None else None,
@@ -1013,7 +1103,7 @@ class Heightfield:
                                           row_band.data_ptr() if row_band is not None else None, self._stream()))
 
     # ---- tangent (forward mode) ------------------------------------------------------------------
-    def _tangent_raw(self, o, d, maxt, t, uv, prim, ray_flags, active_u8, dh, do, dd):
+    def _tangent_raw(self, o, d, maxt, t, uv, prim, ray_flags, active_u8, dh, do, dd, dtw=None):
         n = o.shape[1]
         out = torch.empty((18, n), dtype=torch.float32, device=self.device)
         ts = _fill(hf_si_tangent_t(), _DIFF_ROWS, _rows(out, n))
@@ -1031,6 +1121,15 @@ class Heightfield:
         op, dp = rows3(do), rows3(dd)
         rays = self._rays_struct(o, d, maxt)
         pis = self._pi_struct(t, uv, prim)
+        if dtw is not None:
+            dtw = _tw_tangent(torch.as_tensor(dtw, device=self.device)).to(self.device)
+            check(_capi.lib().hf_tangent_transform(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
+                                                   active_u8.data_ptr() if active_u8 is not None else None,
+                                                   dh.data_ptr() if dh is not None else None,
+                                                   C.byref(op) if op is not None else None,
+                                                   C.byref(dp) if dp is not None else None, dtw.data_ptr(),
+                                                   C.byref(ts), self._stream()))
+            return out
         check(_capi.lib().hf_tangent(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
                                      active_u8.data_ptr() if active_u8 is not None else None,
                                      dh.data_ptr() if dh is not None else None,
@@ -1038,25 +1137,28 @@ class Heightfield:
                                      C.byref(ts), self._stream()))
         return out
 
-    def tangent(self, ray, pi, dheights=None, d_o=None, d_d=None, ray_flags=RayFlags.All, active=True):
+    def tangent(self, ray, pi, dheights=None, d_o=None, d_d=None, ray_flags=RayFlags.All, active=True, d_to_world=None):
         """Explicit forward mode (``hf_tangent``), the mirror of ``adjoint``: the tangent [18, n] (t, p, n, uv,
-        sh_frame.n, dp_du, dp_dv) of the surface interaction for a perturbation ``dheights`` ([H, W]) of the heights
-        and ``d_o`` / ``d_d`` ([3, n]) of the rays; any of them may be None (zero).  Missed and inactive lanes: 0."""
+        sh_frame.n, dp_du, dp_dv) of the surface interaction for a perturbation ``dheights`` ([H, W]) of the heights,
+        ``d_o`` / ``d_d`` ([3, n]) of the rays and ``d_to_world`` (3x4 / 4x4 / 12 values, ``hf_tangent_transform``) of
+        to_world; any of them may be None (zero).  Missed and inactive lanes: 0."""
         self._check_ray(ray)
         keep, _ = self._mask(active, len(ray))
         return self._tangent_raw(ray.o.detach(), ray.d.detach(), ray.maxt, pi.t, pi.prim_uv, pi.prim_index, ray_flags, keep,
-                                 dheights, d_o, d_d)
+                                 dheights, d_o, d_d, d_to_world)
 
     def new_row_band(self):
         """{height, 0} as int32[2] on the device: the initial value of hf_adjoint_rows' row band."""
         return torch.tensor([self.height, 0], dtype=torch.int32, device=self.device)
 
     def adjoint(self, ray, pi, grad_si, ray_flags=RayFlags.All, active=True, grad_heightfield=None,
-                ray_grads=False, row_band=None):
+                ray_grads=False, row_band=None, grad_to_world=None):
         """Explicit adjoint: accumulate dL/dheight for upstream gradients `grad_si`
         ([18, n]: t, p, n, uv, sh_frame.n, dp_du, dp_dv) into `grad_heightfield` ([H, W]).
         row_band (int32[2] device tensor from new_row_band(), optional): updated to {lowest texture row that
-        received a contribution, highest + 1} (hf_adjoint_rows): what a multi-GPU host needs to all-reduce."""
+        received a contribution, highest + 1} (hf_adjoint_rows): what a multi-GPU host needs to all-reduce.
+        grad_to_world (12 contiguous float32 device values, row-major 3x4, optional): dL/d(to_world) is accumulated
+        into it as well (hf_adjoint_transform)."""
         self._check_ray(ray)
         n = len(ray)
         g = _as_f32(grad_si, self.device)
@@ -1066,7 +1168,7 @@ class Heightfield:
         keep, _ = self._mask(active, n)
         grad_od = torch.empty((6, n), dtype=torch.float32, device=self.device) if ray_grads else None
         self._adjoint_raw(ray.o, ray.d, ray.maxt, pi.t, pi.prim_uv, pi.prim_index, ray_flags, keep, g,
-                          grad_heightfield, grad_od, row_band)
+                          grad_heightfield, grad_od, row_band, grad_to_world)
         if ray_grads:
             return grad_heightfield, grad_od[0:3], grad_od[3:6]
         return grad_heightfield
@@ -1373,9 +1475,11 @@ def _reparam_backward_fused(shape, o, d, gd, gdiv, act_p, rid_p, cfg, stream):
     return grad_h
 
 
-def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, need_h, need_o, need_d, stream):
+def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, need_h, need_o, need_d, stream,
+                                 grad_tw=None):
     """Per sample: hf_reparam_aux_rays + hf_ray_intersect + hf_reparam_weights for the weight sums, then
-    hf_reparam_weights + hf_adjoint on the kept hits (re-traced without ``keep``); the ray gradients too."""
+    hf_reparam_weights + hf_adjoint on the kept hits (re-traced without ``keep``); the ray gradients too.
+    grad_tw (12 float32 device values): dL/d(to_world) is accumulated into it (hf_adjoint_transform)."""
     L = _capi.lib()
     num_rays, kappa, exponent, antithetic, seed = cfg
     dev = o.device
@@ -1428,8 +1532,9 @@ def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, n
             trace(k, buf)
         weights(1, k, buf)
         _, si_s, pi_s = _sample_structs(buf, n)
-        check(L.hf_adjoint(shape._h, n, C.byref(r_s), C.byref(pi_s), flags, act_p, C.byref(g_s),
-                           grad_h.data_ptr() if need_h else None, go_adj_p, gd_adj_p, stream))
+        check(L.hf_adjoint_transform(shape._h, n, C.byref(r_s), C.byref(pi_s), flags, act_p, C.byref(g_s),
+                                     grad_h.data_ptr() if need_h else None, go_adj_p, gd_adj_p, None,
+                                     grad_tw.data_ptr() if grad_tw is not None else None, stream))
         if ray_grads:
             hit = torch.isfinite(buf[0])
             if act is not None:
@@ -1456,8 +1561,10 @@ class _ReparameterizeOp(torch.autograd.Function):
     accumulates grad(ray.o), grad(ray.d) over the auxiliary samples)."""
 
     @staticmethod
-    def forward(ctx, heightfield, ray_o, ray_d, shape, num_rays, kappa, exponent, antithetic, seed, active, ray_index=None):
+    def forward(ctx, heightfield, ray_o, ray_d, shape, num_rays, kappa, exponent, antithetic, seed, active, ray_index=None,
+                to_world=None):
         ctx.shape = shape
+        ctx.tw_like = _tw_like(to_world)
         ctx.save_for_backward(ray_o, ray_d)
         ctx.cfg = (int(num_rays), float(kappa), float(exponent), bool(antithetic), int(seed), active, ray_index)
         n = ray_o.shape[1]
@@ -1472,6 +1579,7 @@ class _ReparameterizeOp(torch.autograd.Function):
         cfg = (num_rays, kappa, exponent, antithetic, seed)
         rid_p = ray_index.data_ptr() if ray_index is not None else None
         need_h, need_o, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_tw = ctx.needs_input_grad[11]
         n = ray_o.shape[1]
         o = ray_o.detach().to(torch.float32).contiguous(); d = ray_d.detach().to(torch.float32).contiguous()
         gd = grad_direction.to(torch.float32).contiguous(); gdiv = grad_divergence.to(torch.float32).contiguous()
@@ -1480,15 +1588,17 @@ class _ReparameterizeOp(torch.autograd.Function):
         stream = torch.cuda.current_stream(ray_o.device).cuda_stream
         keep = 36 * n * num_rays <= REPARAM_KEEP_BYTES
         # (backward runs only when some input needs a gradient: without the ray's, that is the heights')
-        if REPARAM_FUSED and keep and not (need_o or need_d) and num_rays <= 32:
+        # (the fused backward is heights-only: a to_world gradient takes the per-sample path)
+        grad_tw = torch.zeros(12, dtype=torch.float32, device=ray_o.device) if need_tw else None
+        if REPARAM_FUSED and keep and not (need_o or need_d or need_tw) and num_rays <= 32:
             gh, grad_o, grad_d = _reparam_backward_fused(shape, o, d, gd, gdiv, act_p, rid_p, cfg, stream), None, None
         else:
             gh, grad_o, grad_d = _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep,
-                                                              need_h, need_o, need_d, stream)
+                                                              need_h, need_o, need_d, stream, grad_tw)
         if gh is not None and gh.shape != shape.heightfield.shape:
             gh = gh.reshape(shape.heightfield.shape)
         return ((gh if need_h else None), (grad_o if need_o else None), (grad_d if need_d else None),
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, (_tw_grad(grad_tw, ctx.tw_like) if need_tw else None))
 
 
 def reparameterize_ray(shape, ray, num_rays=4, kappa=1e5, exponent=3.0, antithetic=False, seed=0, active=None,
@@ -1501,7 +1611,9 @@ def reparameterize_ray(shape, ray, num_rays=4, kappa=1e5, exponent=3.0, antithet
     ``ray.d`` must be unit length.  PCG32 is replaced by sample_tea_32 keyed on (seed, pair, ray id) (include/hf.h);
     ``ray_index`` (int32/uint32 device tensor, one id per ray, e.g. the global pixel index) makes the samples of a
     ray independent of its position in the batch, so a partitioned render draws the same auxiliary rays as the
-    unpartitioned one.  Without it the id is the position in the batch."""
+    unpartitioned one.  Without it the id is the position in the batch.  For a ``differentiable_to_world`` shape whose
+    ``to_world`` needs a gradient, that gradient is accumulated too (the per-sample backward with
+    ``hf_adjoint_transform``; the fused ``hf_reparam_backward`` is heights-only)."""
     if ray_index is not None:
         if ray_index.dtype not in (torch.int32, torch.uint32) or ray_index.numel() != ray.o.shape[1]:
             raise ValueError("ray_index must be an int32/uint32 tensor with one id per ray")
@@ -1509,4 +1621,4 @@ def reparameterize_ray(shape, ray, num_rays=4, kappa=1e5, exponent=3.0, antithet
             raise ValueError("ray_index must live on the rays' device")
         ray_index = ray_index.contiguous()
     return _ReparameterizeOp.apply(shape.heightfield, ray.o, ray.d, shape, num_rays, kappa, exponent, antithetic, seed,
-                                   active, ray_index)
+                                   active, ray_index, shape._to_world_live())
