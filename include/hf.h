@@ -145,7 +145,9 @@ typedef struct hf_pi_const {
  * hf_shading_derivatives computes them with smooth shading (hf_set_face_normals); duv_dx/duv_dy are
  * zeroed by finalize.  sh_n is the face normal n with flat shading and the interpolated vertex normal
  * with smooth shading (with HF_RAY_SHADINGFRAME or HF_RAY_DNSDUV, as mesh.cpp:813-840); sh_s, sh_t
- * and wi are built on sh_n. */
+ * and wi are built on sh_n.  dp_du / dp_dv come from the texcoords with HF_RAY_DPDUV; without it they are
+ * coordinate_system(n) of the face normal before flip_normals (mesh.cpp:762), and hf_adjoint / hf_tangent differentiate
+ * them through n (the sign of n.z held constant).  uv is the texcoord with HF_RAY_UV or HF_RAY_DPDUV, else prim_uv. */
 typedef struct hf_si {
     float *t;
     float *p[3];

@@ -394,6 +394,28 @@ __device__ __forceinline__ v3 dnormalize(v3 n, float r, v3 x) {
     const float pj = dot3(n, x);
     return mk3((x.x - n.x * pj) * r, (x.y - n.y * pj) * r, (x.z - n.z * pj) * r);
 }
+// Derivatives of coordinate_system(n) = (s, t), the dp_du / dp_dv of a record without HF_RAY_DPDUV (mesh.cpp:762).  The
+// sign is that of the forward n.z and is held constant (nothing is differentiated through it); with a = -1/(sign + n.z),
+// b = n.x n.y a: s = (sign n.x^2 a + 1, sign b, -sign n.x), t = (b, n.y^2 a + sign, -n.y), da = a^2 dn.z.
+// JVP: (ds, dt) for the tangent dn.
+__device__ __forceinline__ void coordinate_system_jvp(v3 n, v3 dn, v3 &ds, v3 &dt) {
+    const float sign = signf_(n.z);
+    const float a = -rcp_ieee(sign + n.z);
+    const float da = a * a * dn.z;
+    const float db = (dn.x * n.y + n.x * dn.y) * a + n.x * n.y * da;
+    ds = mk3(sign * (2.f * n.x * dn.x * a + n.x * n.x * da), sign * db, -sign * dn.x);
+    dt = mk3(db, 2.f * n.y * dn.y * a + n.y * n.y * da, -dn.y);
+}
+// VJP: dL/dn for the gradients gs = dL/ds, gt = dL/dt (the transpose of coordinate_system_jvp)
+__device__ __forceinline__ v3 coordinate_system_vjp(v3 n, v3 gs, v3 gt) {
+    const float sign = signf_(n.z);
+    const float a = -rcp_ieee(sign + n.z);
+    const float gb = sign * gs.y + gt.x;
+    const float ga = sign * n.x * n.x * gs.x + n.y * n.y * gt.y + n.x * n.y * gb;
+    return mk3(2.f * sign * n.x * a * gs.x + n.y * a * gb - sign * gs.z,
+               n.x * a * gb + 2.f * n.y * a * gt.y - gt.z,
+               a * a * ga);
+}
 // tangent of the face normal N = cross(e1, e2): dN = cross(de1, e2) + cross(e1, de2)
 __device__ __forceinline__ v3 face_normal_jvp(v3 e1, v3 e2, v3 de1, v3 de2) {
     const v3 c1 = cross3(de1, e2), c2 = cross3(e1, de2);

@@ -2251,6 +2251,16 @@ __device__ __forceinline__ void adjoint_body(float *acc, float *slab = nullptr) 
                 axpy3(1.f, ge1, gP1); axpy3(-1.f, ge1, gP0);
                 axpy3(1.f, ge2, gP2); axpy3(-1.f, ge2, gP0);
             }
+            // without dPdUV, dp_du / dp_dv = coordinate_system of the normal before flip_normals (mesh.cpp:762): their
+            // gradient joins the edges through n here, after the re-intersection's reverse, where fewer values are live
+            if (!(flags & HF_RAY_DPDUV)) {
+                const auto [nn, r] = unit_normal(dp0, dp1);
+                const v3 gN = dnormalize(nn, r, coordinate_system_vjp(nn,
+                    mk3(ldu(ka->g.dp_du[0], ub, lo), ldu(ka->g.dp_du[1], ub, lo), ldu(ka->g.dp_du[2], ub, lo)),
+                    mk3(ldu(ka->g.dp_dv[0], ub, lo), ldu(ka->g.dp_dv[1], ub, lo), ldu(ka->g.dp_dv[2], ub, lo))));
+                axpy3(1.f, cross3(dp1, gN), gdp0);
+                axpy3(1.f, cross3(gN, dp0), gdp1);
+            }
             axpy3(1.f, gdp0, gP1); axpy3(-1.f, gdp0, gP0);
             axpy3(1.f, gdp1, gP2); axpy3(-1.f, gdp1, gP0);
 
@@ -2451,16 +2461,18 @@ __device__ __forceinline__ void tangent_body(const float *dMp = nullptr) {
         const v3 e1 = P[1] - P[0], e2 = P[2] - P[0];
         const v3 de1 = dP[1] - dP[0], de2 = dP[2] - dP[0];
         // n = sh_n = +-normalize(cross(e1, e2))  (smooth: n only; sh_n below)
+        v3 ddu = z3, ddv = z3;
         {
             const auto [nn, r] = unit_normal(e1, e2);
             const v3 dN = face_normal_jvp(e1, e2, de1, de2);
             const v3 dn = dnormalize(nn, f.flip ? -r : r, dN);
             st3(ka->out.n, ub, lo, dn);
             if (!sm) st3(ka->out.sh_n, ub, lo, dn);
+            // without dPdUV, dp_du / dp_dv = coordinate_system of the normal before flip_normals (mesh.cpp:762)
+            if (!(flags & HF_RAY_DPDUV)) coordinate_system_jvp(nn, f.flip ? neg3(dn) : dn, ddu, ddv);
         }
-        // dp_du / dp_dv: linear in the edges (the texcoord differences are constant); zero without dPdUV
+        // dp_du / dp_dv with dPdUV: linear in the edges (the texcoord differences are constant)
         {
-            v3 ddu = z3, ddv = z3;
             if (flags & HF_RAY_DPDUV) {
                 const auto [du0, dv0, du1, dv1, det, inv_det] = uv_diff(U, V);
                 if (det != 0.f) {

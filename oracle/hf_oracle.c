@@ -572,6 +572,17 @@ static void coordinate_system(const float n[3], float s[3], float t[3]) {
     t[1] = fmaf(n[1], n[1] * a, sign);
     t[2] = -n[1];
 }
+/* its reverse: dL/dn += d(s, t)/dn ^T (gs, gt), the sign of n.z held constant.  With a = -1/(sign + n.z) and
+ * b = n.x n.y a: s = (sign n.x^2 a + 1, sign b, -sign n.x), t = (b, n.y^2 a + sign, -n.y), da/dn.z = a^2. */
+static void coordinate_system_vjp(const float n[3], const float gs[3], const float gt[3], float gn[3]) {
+    float sign = signf_(n[2]);
+    float a = -rcpf(sign + n[2]);
+    float gb = sign * gs[1] + gt[0];
+    float ga = sign * n[0] * n[0] * gs[0] + n[1] * n[1] * gt[1] + n[0] * n[1] * gb;
+    gn[0] += 2.f * sign * n[0] * a * gs[0] + n[1] * a * gb - sign * gs[2];
+    gn[1] += n[0] * a * gb + 2.f * n[1] * a * gt[1] - gt[2];
+    gn[2] += a * a * ga;
+}
 
 /* world-space vertices + texcoords of a primitive */
 static void prim_world(const hfo_field *f, uint32_t prim, float P[3][3], float UV[3][2],
@@ -767,7 +778,7 @@ int hfo_adjoint(const hfo_field *f, const float o[3], const float d[3], float t_
     float gp[3] = { g->p[0], g->p[1], g->p[2] };
     float gt = g->t;
 
-    /* dp_du, dp_dv (only when they come from the texcoords; constant duv) */
+    /* dp_du, dp_dv from the texcoords (constant duv); without dPdUV they follow n, below */
     if ((flags & HFO_RAY_DPDUV)) {
         float duv0[2] = { UV[1][0] - UV[0][0], UV[1][1] - UV[0][1] };
         float duv1[2] = { UV[2][0] - UV[0][0], UV[2][1] - UV[0][1] };
@@ -788,6 +799,8 @@ int hfo_adjoint(const hfo_field *f, const float o[3], const float d[3], float t_
         for (int k = 0; k < 3; ++k) n[k] = N[k] * r;
         float sgn = f->flip_normals ? -1.f : 1.f;
         for (int k = 0; k < 3; ++k) gn[k] = sgn * (g->n[k] + g->sh_n[k]);
+        /* without dPdUV: dp_du, dp_dv = coordinate_system(n) of the normal before flip_normals (mesh.cpp:762) */
+        if (!(flags & HFO_RAY_DPDUV)) coordinate_system_vjp(n, g->dp_du, g->dp_dv, gn);
         float proj = dot3(n, gn), gN[3];
         for (int k = 0; k < 3; ++k) gN[k] = (gn[k] - n[k] * proj) * r;
         float c0[3], c1[3];

@@ -7,9 +7,28 @@ test_ad_integrators.py:1001-1012).  Pure test helper.
 """
 import numpy as np
 
-RAY_UV, RAY_DPDUV, RAY_SHADINGFRAME = 0x2, 0x4, 0x8
+RAY_MINIMAL, RAY_UV, RAY_DPDUV, RAY_SHADINGFRAME, RAY_DNSDUV = 0x1, 0x2, 0x4, 0x8, 0x20
 RAY_BOUNDARYTEST, RAY_FOLLOWSHAPE, RAY_DETACHSHAPE = 0x40, 0x80, 0x100
 RAY_ALL = RAY_UV | RAY_DPDUV | RAY_SHADINGFRAME
+
+# the 16 subsets of the flags that choose what the record holds (bit k of the index = k-th flag)
+SI_BITS = (RAY_UV, RAY_DPDUV, RAY_SHADINGFRAME, RAY_DNSDUV)
+FLAG_SUBSETS = [sum(b for k, b in enumerate(SI_BITS) if (i >> k) & 1) for i in range(16)]
+
+
+def coordinate_system(n):
+    """include/mitsuba/core/vector.h:116-136 on [..., 3] numpy or torch arrays: dr::sign(0) = +1, mulsign(a, z) =
+    a * sign(z).  The sign is a constant of the derivative (taken from z without tracking it)."""
+    x, y, z = n[..., 0], n[..., 1], n[..., 2]
+    sgn = (z >= 0) * 2.0 - 1.0
+    if hasattr(sgn, "detach"):
+        sgn = sgn.to(n.dtype)
+    a = -1.0 / (sgn + z)
+    b = x * y * a
+    lib = __import__("torch") if hasattr(n, "detach") else np
+    s = lib.stack([sgn * (x * x * a) + 1.0, sgn * b, -sgn * x], -1)
+    t = lib.stack([b, y * (y * a) + sgn, -y], -1)
+    return s, t
 
 
 def prim_vertex_ids(W, prim):
@@ -69,7 +88,7 @@ def surface_interaction(heights, max_height, to_world, flip_normals, o, d, prim,
     dp0, dp1 = P[1] - P[0], P[2] - P[0]
     N = np.cross(dp0, dp1)
     n = N / np.linalg.norm(N)
-    out = {"t": t, "p": p}
+    out = {"t": t, "p": p, "b": (b0, b1, b2)}
     if flags & (RAY_UV | RAY_DPDUV):
         uv = UV[0] * b0 + UV[1] * b1 + UV[2] * b2
     else:
@@ -80,21 +99,38 @@ def surface_interaction(heights, max_height, to_world, flip_normals, o, d, prim,
         det = duv0[0] * duv1[1] - duv0[1] * duv1[0]
         out["dp_du"] = (duv1[1] * dp0 - duv0[1] * dp1) / det
         out["dp_dv"] = (-duv1[0] * dp0 + duv0[0] * dp1) / det
-    else:
-        out["dp_du"] = np.zeros(3); out["dp_dv"] = np.zeros(3)  # coordinate_system(n): not checked
+    else:  # mesh.cpp:762: coordinate_system of the face normal before flip_normals, attached to the heights
+        out["dp_du"], out["dp_dv"] = coordinate_system(n)
     sgn = -1.0 if flip_normals else 1.0
     out["n"] = sgn * n
     out["sh_n"] = sgn * n
+    out["sh_s"], out["sh_t"], out["wi"] = shading_frame(out["sh_n"], out["dp_du"], d, flags)
     return out
 
 
+def shading_frame(sh_n, dp_du, d, flags):
+    """sh_frame.s, sh_frame.t and wi of finalize_surface_interaction (interaction.h:257-267, 476-499): Gram-Schmidt on
+    dp_du (coordinate_system(sh_n) when dp_du = 0) with ShadingFrame, zero without"""
+    if not (flags & RAY_SHADINGFRAME):
+        sh_s = sh_t = np.zeros(3)
+    else:
+        if np.all(dp_du == 0):
+            sh_s = coordinate_system(sh_n)[0]
+        else:
+            u = dp_du - sh_n * np.dot(sh_n, dp_du)
+            sh_s = u / np.linalg.norm(u)
+        sh_t = np.cross(sh_n, sh_s)
+    return sh_s, sh_t, np.array([-np.dot(d, sh_s), -np.dot(d, sh_t), -np.dot(d, sh_n)])
+
+
 GRAD_FIELDS = [("t", 1), ("p", 3), ("n", 3), ("uv", 2), ("sh_n", 3), ("dp_du", 3), ("dp_dv", 3)]
+FRAME_FIELDS = [("sh_s", 3), ("sh_t", 3), ("wi", 3)]
 
 
 def loss(si, g):
     """scalar L = sum_f <g_f, si_f> for upstream gradient dict g."""
     L = 0.0
-    for name, _ in GRAD_FIELDS:
+    for name, _ in GRAD_FIELDS + FRAME_FIELDS:
         if name in g:
             L += float(np.sum(np.asarray(g[name], np.float64) * si[name]))
     return L

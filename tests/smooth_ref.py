@@ -6,11 +6,14 @@ tests/test_gpu_smooth_shading.py.
     safe_acos(dot(normalize(v[i+1] - v[i]), normalize(v[i+2] - v[i]))), scatter-add of n * angle, normalize;
   * vertex_normals_grid: the heightfield's enumeration of the same sum (the 1-ring of each texel, as vertex_normal in
     hf_device.h);
-  * surface: t, p, n, sh_n of hits in the three AD modes (default: Moeller-Trumbore with attached vertices; follow:
-    frozen barycentrics, t = |p - o| / |d|; detach: no dependence on the heights), differentiable in the heights.
+  * surface: the record of hits in the three AD modes (default: Moeller-Trumbore with attached vertices; follow:
+    frozen barycentrics, t = |p - o| / |d|; detach: no dependence on the heights) under any RayFlags set,
+    differentiable in the heights, the rays and to_world.
 Everything is plain torch, so autograd / torch.func.jvp give the reverse and forward derivatives.
 """
 import torch
+
+from si_numpy import RAY_ALL, RAY_DPDUV, RAY_DNSDUV, RAY_SHADINGFRAME, RAY_UV, coordinate_system
 
 RING = ((0, 1), (1, 0), (1, -1), (0, -1), (-1, 0), (-1, 1))  # E, N, NW, W, S, SE as (row, column) offsets
 
@@ -76,15 +79,23 @@ def vertex_normals_grid(P):
     return _normalize(acc)
 
 
-def surface(h, s, tw, flip, o, d, prim, b_frozen, mode):
-    """t [n], p / n / sh_n / dp_du [n, 3] (float64) of hits (prim [n]; o, d [n, 3]); b_frozen = (b1, b2) [n] each,
-    used by mode 'follow'; 'default' re-intersects with attached vertices; 'detach' detaches the heights"""
+def surface(h, s, tw, flip, o, d, prim, b_frozen, mode, flags=RAY_ALL, smooth=True):
+    """t [n], p / n / sh_n / dp_du / dp_dv / sh_s / sh_t / wi [n, 3], uv [n, 2] (float64) of hits (prim [n]; o, d [n, 3]);
+    b_frozen = (b1, b2) [n] each, used by mode 'follow'; 'default' re-intersects with attached vertices; 'detach'
+    detaches the heights.  `flags` (RayFlags bits) chooses the record as mesh.cpp:672-903 and interaction.h:257-267,
+    475-507 do:
+      * uv: the texcoords with UV or dPdUV, else the barycentrics (b1, b2);
+      * dp_du, dp_dv: from the texcoords with dPdUV, else coordinate_system of the face normal before flip_normals
+        (mesh.cpp:762), attached;
+      * sh_n: the blended vertex normal (smooth) with ShadingFrame or dNSdUV, else the face normal;
+      * sh_s, sh_t: Gram-Schmidt on dp_du with ShadingFrame (coordinate_system(sh_n) where dp_du = 0), else zero;
+        wi = to_local(-d) in that frame.
+    tw may be a float64 tensor that carries a derivative."""
     H, W = h.shape
     P = world_vertices(h, s, tw)
     if mode == "detach":
         P = P.detach()
-    N = vertex_normals_grid(P)
-    V, Nv = P.reshape(-1, 3), N.reshape(-1, 3)
+    V = P.reshape(-1, 3)
     f = grid_faces(W, H).to(P.device)[prim]
     P0, P1, P2 = V[f[:, 0]], V[f[:, 1]], V[f[:, 2]]
     e1, e2 = P1 - P0, P2 - P0
@@ -103,21 +114,46 @@ def surface(h, s, tw, flip, o, d, prim, b_frozen, mode):
     if mode == "follow":
         t = torch.sqrt(((p - o) ** 2).sum(-1) / (d * d).sum(-1))
     sgn = -1.0 if flip else 1.0
-    n = sgn * _normalize(torch.linalg.cross(e1, e2, dim=-1))
-    sh_n = sgn * _normalize(b0[:, None] * Nv[f[:, 0]] + b1[:, None] * Nv[f[:, 1]] + b2[:, None] * Nv[f[:, 2]])
-    # dp_du with the texcoords (j / (W - 1), i / (H - 1)) (mesh.cpp:777-782)
+    n0 = _normalize(torch.linalg.cross(e1, e2, dim=-1))
+    n = sgn * n0
+    out = {"t": t, "p": p, "n": n, "b": (b0, b1, b2)}
+    if smooth:
+        Nv = vertex_normals_grid(P).reshape(-1, 3)
+        out["N"] = Nv[f]
+    if smooth and flags & (RAY_SHADINGFRAME | RAY_DNSDUV):
+        out["sh_n"] = sgn * _normalize(b0[:, None] * Nv[f[:, 0]] + b1[:, None] * Nv[f[:, 1]] + b2[:, None] * Nv[f[:, 2]])
+    else:
+        out["sh_n"] = n
+    # the texcoords (j / (W - 1), i / (H - 1)) (mesh.cpp:764-789)
     U = (f % W).to(P.dtype) / (W - 1)
     Vt = (f // W).to(P.dtype) / (H - 1)
-    du0, dv0 = U[:, 1] - U[:, 0], Vt[:, 1] - Vt[:, 0]
-    du1, dv1 = U[:, 2] - U[:, 0], Vt[:, 2] - Vt[:, 0]
-    det = du0 * dv1 - dv0 * du1
-    dp_du = (dv1[:, None] * e1 - dv0[:, None] * e2) / det[:, None]
-    return {"t": t, "p": p, "n": n, "sh_n": sh_n, "dp_du": dp_du, "b": (b0, b1, b2), "N": Nv[f]}
+    if flags & (RAY_UV | RAY_DPDUV):
+        out["uv"] = torch.stack([b0 * U[:, 0] + b1 * U[:, 1] + b2 * U[:, 2], b0 * Vt[:, 0] + b1 * Vt[:, 1] + b2 * Vt[:, 2]], -1)
+    else:
+        out["uv"] = torch.stack([b1, b2], -1)
+    if flags & RAY_DPDUV:
+        du0, dv0 = U[:, 1] - U[:, 0], Vt[:, 1] - Vt[:, 0]
+        du1, dv1 = U[:, 2] - U[:, 0], Vt[:, 2] - Vt[:, 0]
+        det = du0 * dv1 - dv0 * du1
+        out["dp_du"] = (dv1[:, None] * e1 - dv0[:, None] * e2) / det[:, None]
+        out["dp_dv"] = (-du1[:, None] * e1 + du0[:, None] * e2) / det[:, None]
+    else:
+        out["dp_du"], out["dp_dv"] = coordinate_system(n0)
+    if flags & RAY_SHADINGFRAME:
+        out["sh_s"], out["sh_t"], out["wi"] = shading_frame(out["sh_n"], out["dp_du"], d)
+    else:
+        z = torch.zeros_like(p)
+        out["sh_s"], out["sh_t"] = z, z
+        out["wi"] = torch.stack([z[:, 0], z[:, 0], -(d * out["sh_n"]).sum(-1)], -1)
+    return out
 
 
 def shading_frame(sh_n, dp_du, d):
     """sh_s, sh_t, wi of finalize_surface_interaction (interaction.h:257-267, 476-499) on the shading normal"""
     s = _normalize(dp_du - sh_n * (sh_n * dp_du).sum(-1, keepdim=True))
+    zero = (dp_du == 0).all(-1, keepdim=True)     # dp_du = 0: coordinate_system(sh_n).s
+    if bool(zero.any()):
+        s = torch.where(zero, coordinate_system(sh_n)[0], s)
     t = torch.linalg.cross(sh_n, s, dim=-1)
     md = -d
     wi = torch.stack([(md * s).sum(-1), (md * t).sum(-1), (md * sh_n).sum(-1)], -1)

@@ -2,7 +2,7 @@
 yardstick of tests/test_transform_grad_abi.py and tests/test_gpu_transform_grad.py.
 
 Built on tests/smooth_ref.py (world vertices, the grid's vertex normals, prim_index order) and laid out as the kernels'
-18-row differentiable block (t, p, n, uv, sh_n, dp_du, dp_dv) with RayFlags.All (texcoord uv):
+18-row differentiable block (t, p, n, uv, sh_n, dp_du, dp_dv) under any RayFlags set (smooth_ref.surface):
   * default: Moeller-Trumbore re-intersection with attached vertices (p stays on the ray);
   * follow : frozen barycentrics, t = |p - o| / |d| (p glued to the shape);
   * detach : the vertices carry no derivative.
@@ -17,50 +17,16 @@ import smooth_ref as S
 ROWS = {"t": (0, 1), "p": (1, 4), "n": (4, 7), "uv": (7, 9), "sh_n": (9, 12), "dp_du": (12, 15), "dp_dv": (15, 18)}
 
 
-def si_block(h, s, tw, flip, o, d, prim, b_frozen, mode, smooth, tw_frozen=None):
+def si_block(h, s, tw, flip, o, d, prim, b_frozen, mode, smooth, tw_frozen=None, flags=S.RAY_ALL, frame=False):
     """[18, n] float64 block of the hits (prim [n] int64; o, d [n, 3]; b_frozen = (b1, b2) [n] each, for 'follow').
-    'detach' evaluates the geometry on tw_frozen (when given) and detaches it: nothing depends on tw"""
-    H, W = h.shape
+    'detach' evaluates the geometry on tw_frozen (when given) and detaches it: nothing depends on tw.  `flags`: the
+    RayFlags set of smooth_ref.surface; frame: the 9 rows sh_s, sh_t, wi follow (a [27, n] block)"""
     if mode == "detach" and tw_frozen is not None:
         tw = tw_frozen
     tw = torch.as_tensor(tw, dtype=torch.float64).reshape(3, 4)
-    P = S.world_vertices(h, s, tw)
-    if mode == "detach":
-        P = P.detach()
-    V = P.reshape(-1, 3)
-    f = S.grid_faces(W, H).to(P.device)[prim]
-    P0, P1, P2 = V[f[:, 0]], V[f[:, 1]], V[f[:, 2]]
-    e1, e2 = P1 - P0, P2 - P0
-    if mode == "follow":
-        b1, b2 = b_frozen
-    else:  # mesh.h:357-380
-        pvec = torch.linalg.cross(d, e2, dim=-1)
-        inv = 1.0 / (e1 * pvec).sum(-1)
-        tvec = o - P0
-        qvec = torch.linalg.cross(tvec, e1, dim=-1)
-        b1 = (tvec * pvec).sum(-1) * inv
-        b2 = (d * qvec).sum(-1) * inv
-        t = (e2 * qvec).sum(-1) * inv
-    b0 = 1.0 - b1 - b2
-    p = b0[:, None] * P0 + b1[:, None] * P1 + b2[:, None] * P2
-    if mode == "follow":
-        t = torch.sqrt(((p - o) ** 2).sum(-1) / (d * d).sum(-1))
-    sgn = -1.0 if flip else 1.0
-    n = sgn * S._normalize(torch.linalg.cross(e1, e2, dim=-1))
-    if smooth:
-        Nv = S.vertex_normals_grid(P).reshape(-1, 3)
-        sh_n = sgn * S._normalize(b0[:, None] * Nv[f[:, 0]] + b1[:, None] * Nv[f[:, 1]] + b2[:, None] * Nv[f[:, 2]])
-    else:
-        sh_n = n
-    U = (f % W).to(P.dtype) / (W - 1)
-    Vt = (f // W).to(P.dtype) / (H - 1)
-    uv = torch.stack([b0 * U[:, 0] + b1 * U[:, 1] + b2 * U[:, 2], b0 * Vt[:, 0] + b1 * Vt[:, 1] + b2 * Vt[:, 2]], -1)
-    du0, dv0 = U[:, 1] - U[:, 0], Vt[:, 1] - Vt[:, 0]
-    du1, dv1 = U[:, 2] - U[:, 0], Vt[:, 2] - Vt[:, 0]
-    det = du0 * dv1 - dv0 * du1
-    dp_du = (dv1[:, None] * e1 - dv0[:, None] * e2) / det[:, None]
-    dp_dv = (-du1[:, None] * e1 + du0[:, None] * e2) / det[:, None]
-    return torch.cat([t[None], p.T, n.T, uv.T, sh_n.T, dp_du.T, dp_dv.T])
+    r = S.surface(h, s, tw, flip, o, d, prim, b_frozen, mode, flags, smooth)
+    names = ("t", "p", "n", "uv", "sh_n", "dp_du", "dp_dv") + (("sh_s", "sh_t", "wi") if frame else ())
+    return torch.cat([r[k][None] if k == "t" else r[k].T for k in names])
 
 
 def sample_block(h, s, tw, flip, prim, bx, by, smooth):
