@@ -26,6 +26,8 @@
 //                                      hf_surface_area, hf_sample_position (+ dr::CustomOp -> _adjoint / _tangent)
 //   add_attribute / has_attribute / eval_attribute(_1/_3)   src/render/mesh.cpp:905-1004, include/mitsuba/render/mesh.h:399-440
 //                                      -> hf_eval_attribute (+ dr::CustomOp -> _adjoint / _tangent); unknown names: Shape's
+//   eval_parameterization              include/mitsuba/render/shape.h:361, src/render/mesh.cpp:503-545, 614-635
+//                                      -> hf_eval_parameterization (+ dr::CustomOp -> _adjoint / _tangent)
 //   class / plugin registration        include/mitsuba/core/class.h:195-211, src/core/plugin.cpp:93-127
 #include <mitsuba/core/bitmap.h>
 #include <mitsuba/core/fwd.h>
@@ -240,6 +242,57 @@ struct HeightfieldSampleOp : dr::CustomOp<Float, Float /* p, n: 6 n packed rows 
     const char *name() const override { return "HeightfieldSample"; }
 };
 
+// ---------------------------------------------------------------------------------------------------------
+// Differentiable surface interaction at texture coordinates (Shape::eval_parameterization): primal =
+// hf_eval_parameterization, reverse mode = hf_eval_parameterization_adjoint, forward mode = _tangent.  Input: the height
+// tensor's array; output: the 18 differentiable rows packed as in HeightfieldSIOp.  uv, the triangle and its
+// barycentrics are detached (the FollowShape derivative with t held constant: DESIGN 2).  Staged in the rows of the SI
+// layout above: uv in ROW_U / ROW_V, the mask in ROW_ACTIVE, prim_index in ROW_PRIM, the record from ROW_SI.
+// ---------------------------------------------------------------------------------------------------------
+template <typename Float, typename Spectrum>
+struct HeightfieldParamOp : dr::CustomOp<Float, Float /* 18 n packed rows */, Float /* heights */> {
+    using Base = dr::CustomOp<Float, Float, Float>;
+    using Shape_ = Heightfield<Float, Spectrum>;
+    struct Call {
+        const Shape_ *shape = nullptr;
+        std::vector<float> uv;          // host rows: u then v (2 n)
+        std::vector<uint8_t> active;
+        std::vector<uint32_t> prim;     // filled by eval
+        std::vector<float> aux;         // boundary_test, sh_s, sh_t, wi (10 n), filled by eval
+        uint32_t ray_flags = 0;
+        size_t n = 0;
+    };
+    static inline thread_local Call *pending = nullptr;
+    Call call;
+
+    Float eval(const Float &heights) override {
+        (void) heights;
+        if (!pending) Throw("heightfield: HeightfieldParamOp evaluated outside eval_parameterization");
+        call = std::move(*pending);
+        pending = nullptr;
+        return call.shape->param_primal(call);
+    }
+    void backward() override {
+        Float g = Base::grad_out(); // [18 n]
+        dr::eval(g); dr::sync_thread();
+        std::vector<float> grad_rows(18 * call.n), grad_h((size_t) call.shape->width() * call.shape->height(), 0.f);
+        dr::store(grad_rows.data(), g);
+        call.shape->param_adjoint(call, grad_rows.data(), grad_h.data());
+        if (Base::template grad_enabled_in<0>())
+            Base::template set_grad_in<0>(dr::load<Float>(grad_h.data(), grad_h.size()));
+    }
+    void forward() override {
+        const size_t texels = (size_t) call.shape->width() * call.shape->height();
+        std::vector<float> dh(texels, 0.f), rows(18 * call.n, 0.f);
+        Float g = Base::template grad_in<0>();
+        dr::eval(g); dr::sync_thread();
+        if (dr::width(g) == texels) dr::store(dh.data(), g);
+        call.shape->param_tangent(call, dh.data(), rows.data());
+        Base::set_grad_out(dr::load<Float>(rows.data(), 18 * call.n));
+    }
+    const char *name() const override { return "HeightfieldParam"; }
+};
+
 // Row layout of one staged eval_attribute call (floats): si.p, si.t, prim_index, active (u8), value, tangent of si.p;
 // then the attribute buffer, its gradient / tangent and the height gradient / tangent
 enum : size_t { AT_P = 0, AT_T = 3, AT_PRIM = 4, AT_ACTIVE = 5, AT_OUT = 6, AT_DP = 9, AT_ROWS = 12 };
@@ -314,6 +367,7 @@ public:
     using FloatStorage = DynamicBuffer<Float>;
     using SIOp = HeightfieldSIOp<Float, Spectrum>;
     using SampleOp = HeightfieldSampleOp<Float, Spectrum>;
+    using ParamOp = HeightfieldParamOp<Float, Spectrum>;
     using AttrOp = HeightfieldAttributeOp<Float, Spectrum>;
 
     Heightfield(const Properties &props) : Base(props) {
@@ -459,6 +513,47 @@ public:
         ps.time  = time;
         ps.delta = false;
         return ps;
+    }
+
+    // ---- eval_parameterization (Mesh: mesh.cpp:503-545, 614-635): the record at texture coordinates, the uv -> triangle
+    // lookup in closed form on the device (hf_eval_parameterization); finalized here as Mesh does (mesh.cpp:633) ----
+    SurfaceInteraction3f eval_parameterization(const Point2f &uv, uint32_t ray_flags, Mask active) const override {
+        if (has_flag(ray_flags, RayFlags::DetachShape) && has_flag(ray_flags, RayFlags::FollowShape))
+            Throw("Invalid combination of RayFlags: DetachShape | FollowShape"); // mesh.cpp:709-711
+        size_t n = dr::width(uv, active);
+        typename ParamOp::Call call;
+        call.shape = this; call.ray_flags = ray_flags; call.n = n;
+        std::vector<float> u = to_host(uv.x(), n), v = to_host(uv.y(), n);
+        call.uv = u;
+        call.uv.insert(call.uv.end(), v.begin(), v.end());
+        call.active = to_host_mask(active, n);
+        ParamOp::pending = &call;
+        // the op moves `call` into itself; prim_index and the auxiliary rows come back through m_last_param
+        Float rows = dr::custom<ParamOp>(
+            has_flag(ray_flags, RayFlags::DetachShape) ? dr::detach(m_heights.array()) : m_heights.array());
+        ParamOp::pending = nullptr;
+        auto row = [&](size_t k) { return dr::gather<Float>(rows, dr::arange<UInt32>((uint32_t) n) + (uint32_t) (k * n)); };
+        SurfaceInteraction3f si = dr::zeros<SurfaceInteraction3f>(n);
+        si.t          = row(SI_T);
+        si.p          = Point3f(row(SI_P), row(SI_P + 1), row(SI_P + 2));
+        si.n          = Normal3f(row(SI_N), row(SI_N + 1), row(SI_N + 2));
+        si.uv         = Point2f(row(SI_UV), row(SI_UV + 1));
+        si.sh_frame.n = Normal3f(row(SI_SHN), row(SI_SHN + 1), row(SI_SHN + 2));
+        si.dp_du      = Vector3f(row(SI_DPDU), row(SI_DPDU + 1), row(SI_DPDU + 2));
+        si.dp_dv      = Vector3f(row(SI_DPDV), row(SI_DPDV + 1), row(SI_DPDV + 2));
+        si.dn_du = si.dn_dv = dr::zeros<Vector3f>(n);
+        if (has_flag(ray_flags, RayFlags::BoundaryTest))
+            si.boundary_test = dr::load<Float>(m_last_param.data(), n); // detached
+        si.shape    = this;
+        si.instance = nullptr;
+        PreliminaryIntersection3f pi = dr::zeros<PreliminaryIntersection3f>(n);
+        Mask valid  = dr::neq(si.t, dr::Infinity<Float>);
+        pi.t          = dr::select(valid, Float(1.f), dr::Infinity<Float>);
+        pi.prim_index = dr::load<UInt32>((const uint32_t *) (m_last_param.data() + 10 * n), n);
+        pi.shape      = this;
+        Ray3f ray(Point3f(uv.x(), uv.y(), -1), Vector3f(0, 0, 1), 0, Wavelength(0));
+        si.finalize_surface_interaction(pi, ray, ray_flags, valid);
+        return si;
     }
 
     void traverse(TraversalCallback *callback) override {
@@ -861,6 +956,79 @@ public:
         HfStaging::hip_check(hipFree(dh_dev));
     }
 
+    // ---- called by HeightfieldParamOp ----------------------------------------------------------------------------
+    // the query rows back into the staging block (the node is self-contained: other calls may have used it since)
+    void upload_param(float *dev, const typename ParamOp::Call &op) const {
+        size_t n = op.n;
+        m_stage.upload(dev + ROW_U * n, op.uv.data(), 2 * n); // ROW_U, ROW_V are adjacent
+        HfStaging::hip_check(hipMemcpyAsync(dev + ROW_ACTIVE * n, op.active.data(), n, hipMemcpyHostToDevice, m_stage.stream()));
+    }
+    static void param_uv(float *dev, size_t n, const float *uv[2]) { uv[0] = dev + ROW_U * n; uv[1] = dev + ROW_V * n; }
+
+    Float param_primal(typename ParamOp::Call &op) const {
+        size_t n = op.n;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *dev = m_stage.reserve(ROWS_TOTAL, n);
+        upload_param(dev, op);
+        const float *uv[2];
+        param_uv(dev, n, uv);
+        hf_si_t out = si_at(dev, n);
+        hf_check(hf_eval_parameterization(m_hf, n, uv, op.ray_flags, (const uint8_t *) (dev + ROW_ACTIVE * n), &out,
+                                          (uint32_t *) (dev + ROW_PRIM * n), m_stage.stream()));
+        std::vector<float> host(SI_ROWS * n);
+        m_stage.download(host.data(), dev + ROW_SI * n, SI_ROWS * n);
+        op.prim.resize(n);
+        m_stage.download((float *) op.prim.data(), dev + ROW_PRIM * n, n);
+        m_stage.sync();
+        op.aux.assign(host.begin() + SI_BT * n, host.end());
+        m_last_param = op.aux;
+        m_last_param.insert(m_last_param.end(), (const float *) op.prim.data(), (const float *) op.prim.data() + n);
+        return dr::load<Float>(host.data(), 18 * n);
+    }
+
+    void param_adjoint(const typename ParamOp::Call &op, const float *grad_rows /* host, 18 n */, float *grad_h) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *dev = m_stage.reserve(ROWS_TOTAL, n);
+        upload_param(dev, op);
+        float *g = dev + ROW_GRAD * n;
+        m_stage.upload(g, grad_rows, 18 * n);
+        float *grad_dev = nullptr;
+        HfStaging::hip_check(hipMalloc((void **) &grad_dev, texels * sizeof(float)));
+        HfStaging::hip_check(hipMemsetAsync(grad_dev, 0, texels * sizeof(float), m_stage.stream()));
+        const float *uv[2];
+        param_uv(dev, n, uv);
+        hf_si_grad_t gs = { nullptr, { g + n, g + 2 * n, g + 3 * n }, { g + 4 * n, g + 5 * n, g + 6 * n }, { nullptr, nullptr },
+                            { g + 9 * n, g + 10 * n, g + 11 * n }, { g + 12 * n, g + 13 * n, g + 14 * n },
+                            { g + 15 * n, g + 16 * n, g + 17 * n } };
+        hf_check(hf_eval_parameterization_adjoint(m_hf, n, uv, op.ray_flags, (const uint8_t *) (dev + ROW_ACTIVE * n), &gs,
+                                                  grad_dev, nullptr, m_stage.stream()));
+        m_stage.download(grad_h, grad_dev, texels);
+        m_stage.sync();
+        HfStaging::hip_check(hipFree(grad_dev));
+    }
+
+    void param_tangent(const typename ParamOp::Call &op, const float *dheights /* host, H W */, float *rows /* host, 18 n */) const {
+        size_t n = op.n, texels = (size_t) m_width * m_height;
+        std::lock_guard<std::mutex> guard(m_mutex);
+        float *dev = m_stage.reserve(ROWS_TOTAL, n);
+        upload_param(dev, op);
+        float *dh_dev = nullptr;
+        HfStaging::hip_check(hipMalloc((void **) &dh_dev, texels * sizeof(float)));
+        m_stage.upload(dh_dev, dheights, texels);
+        const float *uv[2];
+        param_uv(dev, n, uv);
+        float *tg = dev + ROW_GRAD * n;
+        hf_si_tangent_t ts = { tg, { tg + n, tg + 2 * n, tg + 3 * n }, { tg + 4 * n, tg + 5 * n, tg + 6 * n }, { tg + 7 * n, tg + 8 * n },
+                               { tg + 9 * n, tg + 10 * n, tg + 11 * n }, { tg + 12 * n, tg + 13 * n, tg + 14 * n },
+                               { tg + 15 * n, tg + 16 * n, tg + 17 * n } };
+        hf_check(hf_eval_parameterization_tangent(m_hf, n, uv, op.ray_flags, (const uint8_t *) (dev + ROW_ACTIVE * n), dh_dev,
+                                                  nullptr, &ts, m_stage.stream()));
+        m_stage.download(rows, tg, 18 * n);
+        m_stage.sync();
+        HfStaging::hip_check(hipFree(dh_dev));
+    }
+
     std::string to_string() const override {
         std::ostringstream oss;
         oss << "Heightfield[" << std::endl
@@ -1095,6 +1263,8 @@ private:
     mutable std::vector<float> m_last_boundary_test; // detached (interaction.h:497-498), of the last primal call
     mutable std::vector<float> m_last_dn;            // dn_du, dn_dv rows of the last primal call with RayFlags::dNSdUV
     mutable std::vector<float> m_last_sample;        // uv (2 n) and pdf (n) rows of the last sample_position
+    mutable std::vector<float> m_last_param;         // boundary_test, sh_s, sh_t, wi (10 n), prim_index (n) of the last
+                                                     // eval_parameterization
     mutable bool m_area_enabled = false;             // hf_set_area_sampling (ensure_pmf_built)
 };
 

@@ -514,6 +514,43 @@ int hf_eval_attribute_tangent(const hf_field_t *hf, size_t n, int type, uint32_t
                               const float *dattr, const float *const dp[3], const float *dheights, float *const dout[],
                               hf_stream_t stream);
 
+/* ---- eval_parameterization: the surface interaction at texture coordinates ---------------------------------------- */
+
+/* Replaces: Shape::eval_parameterization(uv, ray_flags, active) (include/mitsuba/render/shape.h:361) as Mesh implements
+ * it (src/render/mesh.cpp:503-545 build_parameterization, 614-635; Rectangle: src/shapes/rectangle.cpp:173-192), what
+ * the area emitter calls when its radiance varies over the surface (src/emitters/area.cpp:136, 173, 211).  For n queries
+ * uv (2 device arrays of n floats), the surface interaction of the point whose texcoords are uv.  Mesh traces the ray
+ * o = (u, v, -1), d = (0, 0, 1) against its texcoord mesh; the heightfield's regular texcoords give the triangle in
+ * closed form: cell (cx, cy) = (min(floor(u (W-1)), W-2), likewise v), fx = fma(u, W-1, -cx) clamped to [0, 1] (fy
+ * likewise), tri 1 when fx + fy >= 1 (exactly), b = (fx, fy) on tri 0 and (1 - fx, 1 - fy) on tri 1 -- the highest
+ * prim_index among the triangles that contain the point, as for a hit.  A lane is valid when active and 0 <= u, v <= 1
+ * (NaN is not); an invalid lane gets the record of a miss (t = +inf, zeros, boundary_test 1e8 with HF_RAY_BOUNDARYTEST)
+ * with wi = 0.  A valid lane's record is what hf_compute_surface_interaction gives for the UV-space ray and
+ * pi = {1, b, prim_index}: ray_flags as there, t = 1, wi = sh_frame.to_local((0, 0, -1)); HF_RAY_FOLLOWSHAPE does not
+ * replace t, and HF_RAY_BOUNDARYTEST is the all-edge SDF of HF_RAY_BOUNDARY_ALL_EDGES (no viewing ray).  out as in
+ * hf_compute_surface_interaction (any row may be NULL); out_prim_index (n uint32, may be NULL): the triangle, 0 for
+ * invalid lanes.  HF_EFLAGS for DetachShape | FollowShape.  Capturable: no scratch block, no allocation, no
+ * synchronisation.  (HF_VERSION is unchanged: a caller detects the feature by the symbol.) */
+int hf_eval_parameterization(const hf_field_t *hf, size_t n, const float *const uv[2], uint32_t ray_flags,
+                             const uint8_t *active, const hf_si_t *out, uint32_t *out_prim_index, hf_stream_t stream);
+/* Reverse mode of hf_eval_parameterization.  uv, the choice of triangle and b are detached; p, n, sh_n, dp_du and dp_dv
+ * stay attached through the triangle's vertices -- to the heights, with smooth shading to the 1-rings of the vertex
+ * normals, and to to_world: the FollowShape derivative of hf_adjoint with t held constant (the reference's default
+ * mode re-intersects its UV-space ray with the world-space triangle, a derivative without geometric meaning: DESIGN 2).
+ * grad_si.t and grad_si.uv are ignored.  Accumulates dL/dheight into grad_heights (width*height floats, float atomics;
+ * may be NULL) and dL/d(to_world) into grad_to_world (12 floats, may be NULL) through the slab reduction of
+ * hf_adjoint_transform (no float atomics on it: bitwise repeatable).  (prim, b) are recomputed from uv with the forward's
+ * own lookup.  HF_RAY_DETACHSHAPE: no contribution.  Capturable (the slab is a scratch block, as hf_adjoint_transform). */
+int hf_eval_parameterization_adjoint(const hf_field_t *hf, size_t n, const float *const uv[2], uint32_t ray_flags,
+                                     const uint8_t *active, const hf_si_grad_t *grad_si, float *grad_heights,
+                                     float *grad_to_world, hf_stream_t stream);
+/* Forward mode of the same: for the height tangent dheights (width*height floats) and the tangent d_to_world of to_world
+ * (12 floats), either NULL = zero, the tangent rows of tangent_si (overwritten; NULL rows are not written).  The t and uv
+ * rows get 0; invalid lanes get 0 in every row.  No atomics: bitwise the same from launch to launch.  Capturable. */
+int hf_eval_parameterization_tangent(const hf_field_t *hf, size_t n, const float *const uv[2], uint32_t ray_flags,
+                                     const uint8_t *active, const float *dheights, const float *d_to_world,
+                                     const hf_si_tangent_t *tangent_si, hf_stream_t stream);
+
 /* ---- next row: minimal direct lighting on the wavefront ------- */
 
 /* A directional emitter (src/emitters/directional.cpp:82,174): unit direction TOWARDS the light, scalar irradiance. */

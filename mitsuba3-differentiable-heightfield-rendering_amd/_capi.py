@@ -90,6 +90,12 @@ SYMBOLS = {
                                             _fp, C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 3), _fp, C.c_void_p]),
     "hf_eval_attribute_tangent": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, _fp, _fp, C.POINTER(_fp * 3), _fp,
                                             _fp, _fp, C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_eval_parameterization": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, _fp, C.POINTER(hf_si_t),
+                                           _fp, C.c_void_p]),
+    "hf_eval_parameterization_adjoint": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, _fp,
+                                                   C.POINTER(hf_si_grad_t), _fp, _fp, C.c_void_p]),
+    "hf_eval_parameterization_tangent": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, _fp, _fp, _fp,
+                                                   C.POINTER(hf_si_tangent_t), C.c_void_p]),
     "hf_bbox": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "hf_heights_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "hf_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -898,6 +898,78 @@ extern "C" int hf_shading_derivatives(const hf_field_t *hf, size_t n, const hf_p
     return HF_OK;
 }
 
+// ---- eval_parameterization: the surface interaction at texture coordinates ----------------------------------------
+// what the three entry points share: the handle, the flags (as hf_compute_surface_interaction), the uv rows, the device
+static int check_param(const char *fn, const hf_field_t *hf, size_t n, const float *const uv[2], uint32_t ray_flags) {
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc;
+    if ((rc = check_flags(fn, ray_flags))) return rc;
+    if (n == 0) return HF_OK;
+    if (!uv || !uv[0] || !uv[1]) return fail(HF_EINVAL, "%s: NULL uv array", fn);
+    return check_device(fn, hf);
+}
+
+// Replaces: Shape::eval_parameterization (include/mitsuba/render/shape.h:361) as Mesh implements it (src/render/mesh.cpp
+// 503-545 build_parameterization, 614-635) and Rectangle (src/shapes/rectangle.cpp:173-192); called by the area emitter
+// (src/emitters/area.cpp:136, 173, 211).  See include/hf.h.
+extern "C" int hf_eval_parameterization(const hf_field_t *hf, size_t n, const float *const uv[2], uint32_t ray_flags,
+                                        const uint8_t *active, const hf_si_t *out, uint32_t *out_prim_index,
+                                        hf_stream_t stream) {
+    const char *fn = "hf_eval_parameterization";
+    int rc = check_param(fn, hf, n, uv, ray_flags);
+    if (rc) return rc;
+    if (!out) return fail(HF_EINVAL, "%s: NULL output", fn);
+    if (n == 0) return HF_OK;
+    // t stays the UV-space ray's 1 (FollowShape's |p - o| would measure from a UV-space point); boundary_test is the
+    // ray-independent all-edge SDF (there is no viewing ray for the silhouette form)
+    uint32_t flags = ray_flags & ~(uint32_t) HF_RAY_FOLLOWSHAPE;
+    if (flags & HF_RAY_BOUNDARYTEST) flags |= HF_RAY_BOUNDARY_ALL_EDGES;
+    hf_launch_param(hf->dev, n, uv, active, out, out_prim_index, flags, (hipStream_t) stream, hf->d_vn);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+// Replaces: the reverse mode of Mesh::eval_parameterization (mesh.cpp:614-635) with the barycentrics frozen (the
+// FollowShape derivative with t held constant).  See include/hf.h.
+extern "C" int hf_eval_parameterization_adjoint(const hf_field_t *hf, size_t n, const float *const uv[2],
+                                                uint32_t ray_flags, const uint8_t *active, const hf_si_grad_t *grad_si,
+                                                float *grad_heights, float *grad_to_world, hf_stream_t stream) {
+    const char *fn = "hf_eval_parameterization_adjoint";
+    int rc = check_param(fn, hf, n, uv, ray_flags);
+    if (rc) return rc;
+    if (!grad_si) return fail(HF_EINVAL, "%s: NULL grad_si", fn);
+    if (n == 0) return HF_OK;
+    hf_si_grad_t g = *grad_si;
+    g.t = nullptr; g.uv[0] = g.uv[1] = nullptr; // t and uv are not differentiated
+    const uint32_t flags = ray_flags | HF_RAY_FOLLOWSHAPE;
+    if (!grad_to_world) {
+        hf_launch_param_adjoint(hf->dev, n, uv, active, &g, flags, grad_heights, (hipStream_t) stream, hf->d_vn);
+    } else {
+        slot_lease lease(hf, (hipStream_t) stream, hf_xform_slab_bytes(n)); // the slab: this launch's alone
+        if (!lease.buf) return fail(lease.code, "%s: %s", fn, lease.why);
+        hf_launch_param_adjoint(hf->dev, n, uv, active, &g, flags, grad_heights, (hipStream_t) stream, hf->d_vn,
+                                grad_to_world, lease.buf);
+    }
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+// Replaces: the forward mode of the same (mesh.cpp:614-635, frozen barycentrics).  See include/hf.h.
+extern "C" int hf_eval_parameterization_tangent(const hf_field_t *hf, size_t n, const float *const uv[2],
+                                                uint32_t ray_flags, const uint8_t *active, const float *dheights,
+                                                const float *d_to_world, const hf_si_tangent_t *tangent_si,
+                                                hf_stream_t stream) {
+    const char *fn = "hf_eval_parameterization_tangent";
+    int rc = check_param(fn, hf, n, uv, ray_flags);
+    if (rc) return rc;
+    if (!tangent_si) return fail(HF_EINVAL, "%s: NULL output", fn);
+    if (n == 0) return HF_OK;
+    hf_launch_param_tangent(hf->dev, n, uv, active, ray_flags | HF_RAY_FOLLOWSHAPE, dheights, d_to_world, tangent_si,
+                            (hipStream_t) stream, hf->d_vn);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- minimal direct lighting --------------------------------------------------
 static int pack_lights(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                        const float *t, uint32_t n_lights, const hf_dir_light_t *lights, float albedo,

@@ -839,6 +839,27 @@ __device__ __forceinline__ void compute_si(const hf_dev_field &f, v3 o, v3 d, fl
     compute_si_to(f, o, d, t_in, b1, b2, prim, flags, sink);
 }
 
+// ---- eval_parameterization (hf_eval_parameterization and its adjoint / tangent): the triangle of the grid whose texcoords
+// contain the query (u, v), in closed form.  Mesh traces the ray o = (u, v, -1), d = (0, 0, 1) against a copy of itself
+// whose vertices are the texcoords (mesh.cpp:503-545, 614-635); the heightfield's texcoords are the regular grid
+// (j / (W-1), i / (H-1)), so the cell is a floor and the triangle one comparison.  The domain is Moeller-Trumbore's
+// inclusive one, 0 <= u, v <= 1 (NaN fails every test); ties go to the highest prim_index, as for a hit: a point on a cell
+// border to the higher cell (the floor), u = 1 / v = 1 to the last cell (the min), the diagonal to tri 1 (fx + fy >= 1,
+// decided exactly: 1 - fy is exact for fy >= 1/2 and 1 - fx for fx > 1/2, Sterbenz).  fx = fma(u, W-1, -cx) is rounded
+// once, so float64 arithmetic on the host reproduces every value bit for bit (tests/param_ref.py).  b = (b1, b2) in the
+// vertex order of prim_vertex_ids: tri 0 = (v00, v10, v01): (fx, fy); tri 1 = (v11, v01, v10): (1 - fx, 1 - fy). ----
+__device__ __forceinline__ bool param_lookup(int W, int H, float u, float v, uint32_t &prim, float &b1, float &b2) {
+    if (!((u >= 0.f) & (u <= 1.f) & (v >= 0.f) & (v <= 1.f))) return false;
+    const float cw = (float) (W - 1), ch = (float) (H - 1);
+    const float cxf = fminf(floorf(u * cw), (float) (W - 2)), cyf = fminf(floorf(v * ch), (float) (H - 2));
+    const float fx = clamp01(__builtin_fmaf(u, cw, -cxf)), fy = clamp01(__builtin_fmaf(v, ch, -cyf));
+    const bool tri1 = fy >= 0.5f ? fx >= 1.f - fy : fy >= 1.f - fx;
+    prim = 2u * ((uint32_t) cyf * (uint32_t) (W - 1) + (uint32_t) cxf) + (tri1 ? 1u : 0u);
+    b1 = tri1 ? 1.f - fx : fx;
+    b2 = tri1 ? 1.f - fy : fy;
+    return true;
+}
+
 // ---- Area sampling (hf_set_area_sampling): the discrete distribution of Mesh::build_pmf (mesh.cpp:401-432) over the
 // triangles in prim_index order, and what Mesh::sample_position (mesh.cpp:557-610) reads of it. ----
 

@@ -2106,6 +2106,12 @@ struct hf_adjoint_args {
     const float4 *vn;   // hf_adjoint_smooth_kernel: the handle's vertex normals
 };
 typedef const __attribute__((address_space(4))) hf_adjoint_args *hf_adj_kargs;
+// hf_eval_parameterization_adjoint (adjoint_body<..., PARAM>): the query uv rows follow the common arguments, whose
+// rays and pi are not read
+struct hf_param_adjoint_args {
+    hf_adjoint_args a;
+    const float *uv[2];
+};
 __device__ __forceinline__ hf_adj_kargs adj_kargs() {
     hf_adj_kargs ka = (hf_adj_kargs) __builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka)); // opaque: keeps the loads that follow where they are written
@@ -2122,7 +2128,11 @@ __device__ __forceinline__ float ldu(const float *p, size_t ub, uint32_t lo) { r
 // XFORM (hf_adjoint_xform_kernel, hf_adjoint_xform_smooth_kernel): also dL/d(to_world) = sum over the hit's vertices of
 // dL/dP_k (q_k, 1)^T, in M across the loop, plus (smooth) the 1-rings of the three vertex normals; the block's sums
 // go to its row of `slab` (xform_block_store).
-template <bool RAYGRAD, bool SMOOTH, bool XFORM = false>
+// PARAM (hf_param_adjoint*_kernel, hf_eval_parameterization_adjoint): the kernel argument is an hf_param_adjoint_args; a
+// lane's (prim, b) is param_lookup of its query uv instead of pi, and a lane outside the texture square does nothing.
+// The flags carry HF_RAY_FOLLOWSHAPE (frozen barycentrics, never the re-intersection) and t has no gradient, so the
+// FollowShape term of t is not evaluated (its ray is the UV-space one); ray gradients are not offered.
+template <bool RAYGRAD, bool SMOOTH, bool XFORM = false, bool PARAM = false>
 __device__ __forceinline__ void adjoint_body(float *acc, float *slab = nullptr) {
     // Wave-level pre-reduction of the scatter: the hits of one wave (one pixel's samples for
     // primary rays) fall on a few dozen vertices, so their three contributions each are first
@@ -2143,9 +2153,19 @@ __device__ __forceinline__ void adjoint_body(float *acc, float *slab = nullptr) 
         const size_t left = n - ub;
         const bool valid = lane < left;
         const uint32_t lo = valid ? lane : (uint32_t) (left - 1);
-        const float t_in = (ka->pi.t + ub)[lo];
-        const uint8_t *active = ka->active;
-        const bool act = valid && (active ? ((active + ub)[lo] != 0) : true) && (t_in != __builtin_inff());
+        uint32_t qprim = 0u; // PARAM: the lane's triangle and barycentrics
+        float qb1 = 0.f, qb2 = 0.f;
+        bool act;
+        if constexpr (PARAM) {
+            const auto *kp = (const __attribute__((address_space(4))) hf_param_adjoint_args *) ka;
+            const float u = (kp->uv[0] + ub)[lo], v = (kp->uv[1] + ub)[lo];
+            const uint8_t *active = ka->active;
+            act = valid && (active ? ((active + ub)[lo] != 0) : true) && param_lookup(ka->f.W, ka->f.H, u, v, qprim, qb1, qb2);
+        } else {
+            const float t_in = (ka->pi.t + ub)[lo];
+            const uint8_t *active = ka->active;
+            act = valid && (active ? ((active + ub)[lo] != 0) : true) && (t_in != __builtin_inff());
+        }
         const uint32_t flags = ka->flags;
         const bool follow = (flags & HF_RAY_FOLLOWSHAPE) != 0, detach = (flags & HF_RAY_DETACHSHAPE) != 0;
         const bool tex = (flags & (HF_RAY_UV | HF_RAY_DPDUV)) != 0;
@@ -2159,10 +2179,16 @@ __device__ __forceinline__ void adjoint_body(float *acc, float *slab = nullptr) 
             // ONE batch of requests for everything a hit needs that does not depend on other loads -- the ray, the
             // rest of pi, the 18 upstream rows -- then the three heights behind prim_index: three dependent round
             // trips per iteration (pi.t, this batch, the heights) where the loads used to trail the arithmetic (six).
-            const v3 o = mk3((ka->rays.o[0] + ub)[lo], (ka->rays.o[1] + ub)[lo], (ka->rays.o[2] + ub)[lo]);
-            const v3 d = mk3((ka->rays.d[0] + ub)[lo], (ka->rays.d[1] + ub)[lo], (ka->rays.d[2] + ub)[lo]);
-            const float b1 = (ka->pi.prim_uv[0] + ub)[lo], b2 = (ka->pi.prim_uv[1] + ub)[lo], b0 = 1.f - b1 - b2;
-            const uint32_t prim = (ka->pi.prim_index + ub)[lo];
+            v3 o = mk3(0.f, 0.f, 0.f), d = o;
+            float b1 = qb1, b2 = qb2;
+            uint32_t prim = qprim;
+            if constexpr (!PARAM) {
+                o = mk3((ka->rays.o[0] + ub)[lo], (ka->rays.o[1] + ub)[lo], (ka->rays.o[2] + ub)[lo]);
+                d = mk3((ka->rays.d[0] + ub)[lo], (ka->rays.d[1] + ub)[lo], (ka->rays.d[2] + ub)[lo]);
+                b1 = (ka->pi.prim_uv[0] + ub)[lo]; b2 = (ka->pi.prim_uv[1] + ub)[lo];
+                prim = (ka->pi.prim_index + ub)[lo];
+            }
+            const float b0 = 1.f - b1 - b2;
             const float gt = ldu(ka->g.t, ub, lo);
             v3 gp = mk3(ldu(ka->g.p[0], ub, lo), ldu(ka->g.p[1], ub, lo), ldu(ka->g.p[2], ub, lo));
             const v3 gn_a = mk3(ldu(ka->g.n[0], ub, lo), ldu(ka->g.n[1], ub, lo), ldu(ka->g.n[2], ub, lo));
@@ -2207,7 +2233,7 @@ __device__ __forceinline__ void adjoint_body(float *acc, float *slab = nullptr) 
                 axpy3(1.f, cross3(gN, dp0), gdp1);
             }
             // FollowShape: t = sqrt(|p-o|^2/|d|^2) feeds p, o, d
-            if (follow) {
+            if (!PARAM && follow) {
                 const auto [po, dd, tt] = follow_t(p, o, d);
                 const float c = gt / (tt * dd);
                 axpy3(c, po, gp);
@@ -2397,13 +2423,22 @@ struct hf_tangent_args {
     const float4 *vn;           // hf_tangent_smooth_kernel: the handle's vertex normals
 };
 typedef const __attribute__((address_space(4))) hf_tangent_args *hf_tan_kargs;
+// hf_eval_parameterization_tangent (tangent_body<..., PARAM>): the query uv rows follow the common arguments, whose rays
+// and pi are not read
+struct hf_param_tangent_args {
+    hf_tangent_args a;
+    const float *uv[2];
+};
 
 // RAYTAN: d_o or d_d is given (without them the ray terms are dead code).
 // SMOOTH (hf_tangent_smooth_kernel): sh_n is the interpolated vertex normal; its tangent takes the barycentric tangents
 // and the tangents of the three vertex normals, evaluated on the fly from h and dh (vertex_normal_jvp: no atomics).
 // XFORM (hf_tangent_xform_kernel, hf_tangent_xform_smooth_kernel): the vertices also move by dM (q_k, 1) for the tangent
 // dM (12 device floats) of to_world, and so do the 1-rings of the vertex normals (vertex_normals_jvp_xform).
-template <bool RAYTAN, bool SMOOTH, bool XFORM = false>
+// PARAM (hf_param_tangent*_kernel, hf_eval_parameterization_tangent): the kernel argument is an hf_param_tangent_args; a
+// lane's (prim, b) is param_lookup of its query uv instead of pi (outside the texture square: zero tangents).  The flags
+// carry HF_RAY_FOLLOWSHAPE and t gets no tangent (0): the FollowShape t of the UV-space ray is not evaluated.
+template <bool RAYTAN, bool SMOOTH, bool XFORM = false, bool PARAM = false>
 __device__ __forceinline__ void tangent_body(const float *dMp = nullptr) {
     float dM[12]; // XFORM: wave-uniform
     if constexpr (XFORM) {
@@ -2419,9 +2454,19 @@ __device__ __forceinline__ void tangent_body(const float *dMp = nullptr) {
         if (ub >= n) break; // wave-uniform
         if (lane >= n - ub) continue;
         const uint32_t lo = lane;
-        const float t_in = (ka->pi.t + ub)[lo];
-        const uint8_t *active = ka->active;
-        const bool act = (active ? ((active + ub)[lo] != 0) : true) && (t_in != __builtin_inff());
+        uint32_t qprim = 0u; // PARAM: the lane's triangle and barycentrics
+        float qb1 = 0.f, qb2 = 0.f;
+        bool act;
+        if constexpr (PARAM) {
+            const auto *kp = (const __attribute__((address_space(4))) hf_param_tangent_args *) ka;
+            const float u = (kp->uv[0] + ub)[lo], v = (kp->uv[1] + ub)[lo];
+            const uint8_t *active = ka->active;
+            act = (active ? ((active + ub)[lo] != 0) : true) && param_lookup(ka->f.W, ka->f.H, u, v, qprim, qb1, qb2);
+        } else {
+            const float t_in = (ka->pi.t + ub)[lo];
+            const uint8_t *active = ka->active;
+            act = (active ? ((active + ub)[lo] != 0) : true) && (t_in != __builtin_inff());
+        }
         const v3 z3 = mk3(0.f, 0.f, 0.f);
         if (!act) { // missed / inactive: exactly zero tangents
             st(ka->out.t, ub, lo, 0.f); st3(ka->out.p, ub, lo, z3); st3(ka->out.n, ub, lo, z3);
@@ -2432,10 +2477,16 @@ __device__ __forceinline__ void tangent_body(const float *dMp = nullptr) {
         const uint32_t flags = ka->flags;
         const bool follow = (flags & HF_RAY_FOLLOWSHAPE) != 0, detach = (flags & HF_RAY_DETACHSHAPE) != 0;
         // ONE batch of independent loads: pi, the ray, the ray tangents
-        const float b1 = (ka->pi.prim_uv[0] + ub)[lo], b2 = (ka->pi.prim_uv[1] + ub)[lo], b0 = 1.f - b1 - b2;
-        const uint32_t prim = (ka->pi.prim_index + ub)[lo];
-        const v3 o = mk3((ka->rays.o[0] + ub)[lo], (ka->rays.o[1] + ub)[lo], (ka->rays.o[2] + ub)[lo]);
-        const v3 d = mk3((ka->rays.d[0] + ub)[lo], (ka->rays.d[1] + ub)[lo], (ka->rays.d[2] + ub)[lo]);
+        float b1 = qb1, b2 = qb2;
+        uint32_t prim = qprim;
+        v3 o = z3, d = z3;
+        if constexpr (!PARAM) {
+            b1 = (ka->pi.prim_uv[0] + ub)[lo]; b2 = (ka->pi.prim_uv[1] + ub)[lo];
+            prim = (ka->pi.prim_index + ub)[lo];
+            o = mk3((ka->rays.o[0] + ub)[lo], (ka->rays.o[1] + ub)[lo], (ka->rays.o[2] + ub)[lo]);
+            d = mk3((ka->rays.d[0] + ub)[lo], (ka->rays.d[1] + ub)[lo], (ka->rays.d[2] + ub)[lo]);
+        }
+        const float b0 = 1.f - b1 - b2;
         v3 dO = z3, dD = z3;
         if (RAYTAN) {
             dO = mk3(ldu(ka->d_o[0], ub, lo), ldu(ka->d_o[1], ub, lo), ldu(ka->d_o[2], ub, lo));
@@ -2520,7 +2571,7 @@ __device__ __forceinline__ void tangent_body(const float *dMp = nullptr) {
         const v3 dp = mk3(du * e1.x + dv * e2.x + (b0 * dP[0].x + b1 * dP[1].x + b2 * dP[2].x),
                           du * e1.y + dv * e2.y + (b0 * dP[0].y + b1 * dP[1].y + b2 * dP[2].y),
                           du * e1.z + dv * e2.z + (b0 * dP[0].z + b1 * dP[1].z + b2 * dP[2].z));
-        if (follow) { // t = sqrt(|p - o|^2 / |d|^2)
+        if (!PARAM && follow) { // t = sqrt(|p - o|^2 / |d|^2)
             const auto [po, dd, tt] = follow_t(bary_point(P, b0, b1, b2), o, d);
             dt = dot3(po, dp - dO) / (tt * dd) - (tt / dd) * dot3(d, dD);
         }
@@ -3831,4 +3882,143 @@ void hf_launch_attribute(int mode, int type, uint32_t size, const hf_attr_args &
     if (a.n == 0) return;
     if (type == HF_ATTR_VERTEX) size == 1 ? attr_launch<HF_ATTR_VERTEX, 1>(mode, a, stream) : attr_launch<HF_ATTR_VERTEX, 3>(mode, a, stream);
     else                        size == 1 ? attr_launch<HF_ATTR_FACE, 1>(mode, a, stream) : attr_launch<HF_ATTR_FACE, 3>(mode, a, stream);
+}
+
+// ---------------------------------------------------------------------------------
+// eval_parameterization (hf_eval_parameterization / _adjoint / _tangent): the surface interaction at texture coordinates
+// (Shape::eval_parameterization, mesh.cpp:614-635).  One lane per query: the two uv rows (coalesced), the closed-form
+// lookup in registers (param_lookup, hf_device.h), then the hit-geometry helpers on (prim, b) -- compute_si_to for the
+// record with Mesh's UV-space ray o = (u, v, -1), d = (0, 0, 1) and t = 1, the FollowShape branches of adjoint_body /
+// tangent_body for the derivatives.  Nothing is materialised between the lookup and the helpers.
+// ---------------------------------------------------------------------------------
+struct hf_param_args {
+    hf_dev_field f;
+    size_t n;
+    const float *uv[2];
+    const uint8_t *active;
+    hf_si_t sio;
+    uint32_t *prim_out; // may be NULL
+    uint32_t flags;     // the caller's, without HF_RAY_FOLLOWSHAPE; with HF_RAY_BOUNDARY_ALL_EDGES under BoundaryTest
+    const float4 *vn;   // hf_param_smooth_kernel: the handle's vertex normals
+};
+typedef const __attribute__((address_space(4))) hf_param_args *hf_param_kargs;
+
+// Shaped like si_body (one block per 256 queries, arguments from the kernarg segment where they are used, every field
+// stored as soon as it is final): two coalesced loads and the optional mask, then one round trip for the three heights
+// (and three vertex normals) -- no load waits on another beyond that.  Invalid lanes get si_miss_to with wi = 0 and
+// prim_index 0.
+template <bool SMOOTH>
+__device__ __forceinline__ void param_body() {
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t ub = (size_t) blockIdx.x * HF_BLOCK + (threadIdx.x & ~63u);; ub += stride) {
+        hf_param_kargs ka = (hf_param_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka)); // opaque: keeps the loads that follow where they are written
+        const size_t n = ka->n;
+        if (ub >= n) break; // wave-uniform
+        if (lane >= n - ub) continue;
+        const uint32_t lo = lane;
+        const float u = (ka->uv[0] + ub)[lo], v = (ka->uv[1] + ub)[lo];
+        const uint8_t *active = ka->active;
+        uint32_t prim = 0u;
+        float b1 = 0.f, b2 = 0.f;
+        const bool act = (active ? ((active + ub)[lo] != 0) : true) && param_lookup(ka->f.W, ka->f.H, u, v, prim, b1, b2);
+        const uint32_t flags = ka->flags;
+        hf_si_sink<hf_param_kargs> out = { ka, ub, lo, flags };
+        if (act) {
+            const hf_dev_field f = load_field(&ka->f);
+            compute_si_to<SMOOTH>(f, mk3(u, v, -1.f), mk3(0.f, 0.f, 1.f), 1.f, b1, b2, prim, flags, out, SMOOTH ? ka->vn : nullptr);
+        } else {
+            prim = 0u;
+            si_miss_to(out, flags);
+            out.wi(mk3(0.f, 0.f, 0.f));
+        }
+        if (uint32_t *po = ka->prim_out) __builtin_nontemporal_store(prim, &(po + ub)[lo]);
+    }
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_param_kernel(hf_param_args a_) { (void) a_; param_body<false>(); }
+__global__ __launch_bounds__(HF_BLOCK) void hf_param_smooth_kernel(hf_param_args a_) { (void) a_; param_body<true>(); }
+
+// the adjoint (float atomics into grad_h through the per-wave LDS tile) and the transform slab: adjoint_body's launch bounds
+__global__ __launch_bounds__(HF_BLOCK, 5) void hf_param_adjoint_kernel(hf_param_adjoint_args a_) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<false, false, false, true>(s_acc[threadIdx.x >> 6]);
+}
+__global__ __launch_bounds__(HF_BLOCK, 4) void hf_param_adjoint_smooth_kernel(hf_param_adjoint_args a_) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<false, true, false, true>(s_acc[threadIdx.x >> 6]);
+}
+__global__ __launch_bounds__(HF_BLOCK, 5) void hf_param_adjoint_xform_kernel(hf_param_adjoint_args a_, float *slab) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<false, false, true, true>(s_acc[threadIdx.x >> 6], slab);
+}
+__global__ __launch_bounds__(HF_BLOCK, 3) void hf_param_adjoint_xform_smooth_kernel(hf_param_adjoint_args a_, float *slab) {
+    (void) a_;
+    __shared__ float s_acc[HF_BLOCK / 64][HF_ADJ_TILE * HF_ADJ_TILE];
+    adjoint_body<false, true, true, true>(s_acc[threadIdx.x >> 6], slab);
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_param_tangent_kernel(hf_param_tangent_args a_) {
+    (void) a_;
+    tangent_body<false, false, false, true>();
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_param_tangent_smooth_kernel(hf_param_tangent_args a_) {
+    (void) a_;
+    tangent_body<false, true, false, true>();
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_param_tangent_xform_kernel(hf_param_tangent_args a_, const float *dM) {
+    (void) a_;
+    tangent_body<false, false, true, true>(dM);
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_param_tangent_xform_smooth_kernel(hf_param_tangent_args a_, const float *dM) {
+    (void) a_;
+    tangent_body<false, true, true, true>(dM);
+}
+
+void hf_launch_param(const hf_dev_field &f, size_t n, const float *const uv[2], const uint8_t *active, const hf_si_t *si,
+                     uint32_t *prim_out, uint32_t flags, hipStream_t stream, const float4 *vn) {
+    if (n == 0) return;
+    hf_param_args a;
+    a.f = f; a.n = n; a.uv[0] = uv[0]; a.uv[1] = uv[1]; a.active = active; a.sio = *si; a.prim_out = prim_out;
+    a.flags = flags; a.vn = vn;
+    hipLaunchKernelGGL(vn ? hf_param_smooth_kernel : hf_param_kernel, dim3(grid_for(n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0,
+                       stream, a);
+}
+
+void hf_launch_param_adjoint(const hf_dev_field &f, size_t n, const float *const uv[2], const uint8_t *active,
+                             const hf_si_grad_t *gs, uint32_t flags, float *grad_h, hipStream_t stream, const float4 *vn,
+                             float *grad_to_world, void *slab) {
+    if (n == 0) return;
+    hf_param_adjoint_args p = {};
+    hf_adjoint_args &a = p.a;
+    a.f = f; a.n = n; a.active = active; a.g = *gs; a.flags = flags; a.grad_h = grad_h; a.vn = vn;
+    p.uv[0] = uv[0]; p.uv[1] = uv[1];
+    if (grad_to_world) { // slab: hf_xform_slab_bytes(n), this launch's alone
+        const int grid = grid_for(n, HF_XFORM_GRID_CAP);
+        hipLaunchKernelGGL(vn ? hf_param_adjoint_xform_smooth_kernel : hf_param_adjoint_xform_kernel, dim3(grid),
+                           dim3(HF_BLOCK), 0, stream, p, (float *) slab);
+        xform_sum((const float *) slab, grid, grad_to_world, stream);
+        return;
+    }
+    hipLaunchKernelGGL(vn ? hf_param_adjoint_smooth_kernel : hf_param_adjoint_kernel, dim3(grid_for(n)), dim3(HF_BLOCK), 0,
+                       stream, p);
+}
+
+void hf_launch_param_tangent(const hf_dev_field &f, size_t n, const float *const uv[2], const uint8_t *active,
+                             uint32_t flags, const float *dh, const float *d_to_world, const hf_si_tangent_t *out,
+                             hipStream_t stream, const float4 *vn) {
+    if (n == 0) return;
+    hf_param_tangent_args p = {};
+    hf_tangent_args &a = p.a;
+    a.f = f; a.n = n; a.active = active; a.dh = dh; a.out = *out; a.flags = flags; a.vn = vn;
+    p.uv[0] = uv[0]; p.uv[1] = uv[1];
+    const dim3 grid(grid_for(n, HF_SI_GRID_CAP)), block(HF_BLOCK);
+    if (d_to_world) {
+        hipLaunchKernelGGL(vn ? hf_param_tangent_xform_smooth_kernel : hf_param_tangent_xform_kernel, grid, block, 0, stream,
+                           p, d_to_world);
+        return;
+    }
+    hipLaunchKernelGGL(vn ? hf_param_tangent_smooth_kernel : hf_param_tangent_kernel, grid, block, 0, stream, p);
 }

@@ -136,3 +136,15 @@ struct hf_attr_args {
 };
 // mode 0: forward, 1: adjoint, 2: tangent; type HF_ATTR_VERTEX / HF_ATTR_FACE, size 1 or 3 (checked by the caller)
 void hf_launch_attribute(int mode, int type, uint32_t size, const hf_attr_args &a, hipStream_t stream);
+// ---- eval_parameterization (hf_eval_parameterization / _adjoint / _tangent): uv = 2 device rows of n floats ----
+// forward: flags without HF_RAY_FOLLOWSHAPE (the caller's translation); prim_out may be NULL
+void hf_launch_param(const hf_dev_field &f, size_t n, const float *const uv[2], const uint8_t *active, const hf_si_t *si,
+                     uint32_t *prim_out, uint32_t flags, hipStream_t stream, const float4 *vn);
+// adjoint / tangent: flags WITH HF_RAY_FOLLOWSHAPE; grad_to_world / slab as for hf_launch_adjoint, d_to_world as for
+// hf_launch_tangent (NULL: none)
+void hf_launch_param_adjoint(const hf_dev_field &f, size_t n, const float *const uv[2], const uint8_t *active,
+                             const hf_si_grad_t *gs, uint32_t flags, float *grad_h, hipStream_t stream, const float4 *vn,
+                             float *grad_to_world = nullptr, void *slab = nullptr);
+void hf_launch_param_tangent(const hf_dev_field &f, size_t n, const float *const uv[2], const uint8_t *active,
+                             uint32_t flags, const float *dh, const float *d_to_world, const hf_si_tangent_t *out,
+                             hipStream_t stream, const float4 *vn);

@@ -317,6 +317,43 @@ class _SurfaceInteractionOp(torch.autograd.Function):
                 _tw_grad(grad_tw, ctx.tw_like) if need_tw else None)
 
 
+class _ParameterizationOp(torch.autograd.Function):
+    """Differentiable SI block [18, n] of eval_parameterization; backward = hf_eval_parameterization_adjoint (atomic
+    scatter of dL/dheight), jvp = hf_eval_parameterization_tangent.  The triangle and its barycentrics are recomputed
+    from uv by the derivative entries and frozen; the t and uv rows carry no derivative.  to_world
+    (differentiable_to_world shapes, else None): dL/d(to_world) through the same entries."""
+
+    @staticmethod
+    def forward(ctx, shape, heights, uv, flags, active, diff_block, to_world=None):
+        ctx.shape, ctx.flags, ctx.active = shape, flags, active
+        ctx.save_for_backward(uv)
+        ctx.save_for_forward(uv)
+        ctx.h_version = shape._param_version()
+        ctx.tw_like = _tw_like(to_world)
+        return diff_block
+
+    @staticmethod
+    def jvp(ctx, _shape, dh, _uv, _flags, _active, _diff, dtw=None):
+        shape = ctx.shape
+        uv, = ctx.saved_tensors
+        if ctx.h_version != shape._param_version():
+            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
+        return shape._param_tangent_raw(uv, ctx.flags, ctx.active, dh, _tw_tangent(dtw))
+
+    @staticmethod
+    def backward(ctx, g):
+        shape = ctx.shape
+        uv, = ctx.saved_tensors
+        if ctx.h_version != shape._param_version():
+            raise RuntimeError("heightfield parameters changed between forward and backward")
+        need_h, need_tw = ctx.needs_input_grad[1], ctx.needs_input_grad[6]
+        grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=uv.device) if need_h else None
+        grad_tw = torch.zeros(12, dtype=torch.float32, device=uv.device) if need_tw else None
+        if need_h or need_tw:
+            shape._param_adjoint_raw(uv, ctx.flags, ctx.active, g.contiguous().to(torch.float32), grad_h, grad_tw)
+        return None, grad_h, None, None, None, None, (_tw_grad(grad_tw, ctx.tw_like) if need_tw else None)
+
+
 def _tw_like(to_world):
     """(shape, dtype, device) of a to_world input, None without one"""
     return None if to_world is None else (tuple(to_world.shape), to_world.dtype, to_world.device)
@@ -639,6 +676,89 @@ class Heightfield:
         keep, _ = self._mask(active, ps.prim_index.shape[0])
         out = self._sample_tangent_raw(ps.prim_index, ps.b, keep, dheights, d_to_world)
         return out[0:3], out[3:6]
+
+    # ---- eval_parameterization (Shape::eval_parameterization, shape.h:361; Mesh: mesh.cpp:503-545, 614-635) ----------
+    def eval_parameterization(self, uv, ray_flags=RayFlags.All, active=True):
+        """The surface interaction at texture coordinates uv ([2, n]; hf_eval_parameterization): the record of Mesh's
+        UV-space ray o = (u, v, -1), d = (0, 0, 1) (t = 1, wi = sh_frame.to_local((0, 0, -1))).  Lanes outside
+        [0, 1]^2, NaN and inactive lanes are misses (is_valid() False, wi = 0).  si.prim_index is the triangle.
+        p, n, sh_frame (and wi), dp_du, dp_dv are differentiable in the heightfield -- and in to_world for
+        differentiable_to_world shapes -- with the triangle and its barycentrics frozen; uv and t are not."""
+        ray_flags = int(ray_flags)
+        if (ray_flags & RayFlags.DetachShape) and (ray_flags & RayFlags.FollowShape):
+            raise _capi.HfError(_capi.HF_EFLAGS, "Invalid combination of RayFlags: DetachShape | FollowShape")
+        uv = _as_f32(uv.detach() if isinstance(uv, torch.Tensor) else uv, self.device).reshape(2, -1)
+        n = uv.shape[1]
+        diff = torch.empty((18, n), dtype=torch.float32, device=self.device)
+        aux = torch.empty((10, n), dtype=torch.float32, device=self.device)
+        prim = torch.empty(n, dtype=torch.int32, device=self.device)
+        keep, ap = self._mask(active, n)
+        out = _fill(_fill(hf_si_t(), _DIFF_ROWS, _rows(diff, n)), _AUX_ROWS, _rows(aux, n))
+        uvp = (C.c_void_p * 2)(*_rows(uv, n))
+        check(_capi.lib().hf_eval_parameterization(self._h, n, C.byref(uvp), ray_flags, ap, C.byref(out), prim.data_ptr(),
+                                                   self._stream()))
+        detach = bool(ray_flags & RayFlags.DetachShape)
+        h = self.heightfield
+        tw = self._to_world_live(detach)
+        h_live = not detach and ((torch.is_grad_enabled() and h.requires_grad) or _has_tangent(h))
+        if h_live or tw is not None:
+            diff = _ParameterizationOp.apply(self, h, uv, ray_flags, keep, diff, tw)
+        o = torch.stack([uv[0], uv[1], torch.full_like(uv[0], -1.0)])
+        d = torch.zeros((3, n), dtype=torch.float32, device=self.device)
+        d[2] = 1.0
+        ray = Ray3f(o, d, torch.ones(n, dtype=torch.float32, device=self.device))
+        return self._package_si(ray, diff[0], prim, diff, aux, ray_flags)
+
+    def _param_adjoint_raw(self, uv, ray_flags, active_u8, g, grad_h, grad_tw=None):
+        n = uv.shape[1]
+        gs = _fill(hf_si_grad_t(), _DIFF_ROWS, _rows(g, n))
+        uvp = (C.c_void_p * 2)(*_rows(uv, n))
+        if grad_tw is not None:
+            assert grad_tw.numel() == 12 and grad_tw.dtype == torch.float32 and grad_tw.is_contiguous()
+        check(_capi.lib().hf_eval_parameterization_adjoint(
+            self._h, n, C.byref(uvp), int(ray_flags), active_u8.data_ptr() if active_u8 is not None else None, C.byref(gs),
+            grad_h.data_ptr() if grad_h is not None else None, grad_tw.data_ptr() if grad_tw is not None else None,
+            self._stream()))
+
+    def _param_tangent_raw(self, uv, ray_flags, active_u8, dh, dtw=None):
+        n = uv.shape[1]
+        out = torch.zeros((18, n), dtype=torch.float32, device=self.device)
+        if dh is None and dtw is None:
+            return out
+        if dh is not None:
+            dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
+            assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
+        if dtw is not None:
+            dtw = _tw_tangent(torch.as_tensor(dtw, device=self.device)).to(self.device)
+        ts = _fill(hf_si_tangent_t(), _DIFF_ROWS, _rows(out, n))
+        uvp = (C.c_void_p * 2)(*_rows(uv, n))
+        check(_capi.lib().hf_eval_parameterization_tangent(
+            self._h, n, C.byref(uvp), int(ray_flags), active_u8.data_ptr() if active_u8 is not None else None,
+            dh.data_ptr() if dh is not None else None, dtw.data_ptr() if dtw is not None else None, C.byref(ts),
+            self._stream()))
+        return out
+
+    def eval_parameterization_adjoint(self, uv, grad_si, ray_flags=RayFlags.All, active=True, grad_heightfield=None,
+                                      grad_to_world=None):
+        """Explicit adjoint of eval_parameterization: accumulates dL/dheight for the upstream gradients grad_si ([18, n]:
+        t, p, n, uv, sh_frame.n, dp_du, dp_dv; the t and uv rows are ignored) into grad_heightfield ([H, W]) and, when
+        given (12 contiguous float32 device values), dL/d(to_world) into grad_to_world"""
+        uv = _as_f32(uv.detach() if isinstance(uv, torch.Tensor) else uv, self.device).reshape(2, -1)
+        n = uv.shape[1]
+        g = _as_f32(grad_si, self.device)
+        assert g.shape == (18, n)
+        if grad_heightfield is None:
+            grad_heightfield = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+        keep, _ = self._mask(active, n)
+        self._param_adjoint_raw(uv, ray_flags, keep, g, grad_heightfield, grad_to_world)
+        return grad_heightfield
+
+    def eval_parameterization_tangent(self, uv, dheights=None, ray_flags=RayFlags.All, active=True, d_to_world=None):
+        """Explicit forward mode of eval_parameterization: the tangent [18, n] for dheights ([H, W]) and d_to_world
+        (3x4 / 4x4 / 12 values), either None (zero); the t and uv rows are 0"""
+        uv = _as_f32(uv.detach() if isinstance(uv, torch.Tensor) else uv, self.device).reshape(2, -1)
+        keep, _ = self._mask(active, uv.shape[1])
+        return self._param_tangent_raw(uv, ray_flags, keep, dheights, d_to_world)
 
     # ---- shape attributes (Mesh::add_attribute / has_attribute / eval_attribute*, mesh.cpp:905-1004) -------------------
     def _attr_count(self, type_):
