@@ -10,15 +10,19 @@ reparameterised, the pixel value is multiplied by the determinant) on top of the
 Scene: a flat field with a box ridge across it, seen obliquely, so that the ridge's top edge occludes the field
 behind it.  theta lifts the ridge.  dL/dtheta has an interior part (the visible ridge top moves with theta) and a
 SILHOUETTE part (pixels switch from the field to the ridge), which only the reparameterisation sees.  The script
-prints the finite-difference derivative of the rendered sum, the attached-only gradient and the reparameterised one.
+prints the finite-difference derivative of the rendered sum, the attached-only gradient and the reparameterised one;
+with --forward also the forward-mode derivative along the ridge lift (torch.autograd.forward_ad: the tangent of the
+heights goes through reparameterize_ray's jvp, hf_reparam_tangent, then through the surface interaction's), which
+is the same quantity as the reverse-mode one for the same auxiliary samples.
 
-    python examples/silhouette_gradient.py [--film 192 --spp 64 --aux 16]
+    python examples/silhouette_gradient.py [--film 192 --spp 64 --aux 16 --forward]
 """
 import argparse
 import os
 import sys
 
 import torch
+import torch.autograd.forward_ad as fwAD
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hf_amd  # noqa: E402
@@ -65,6 +69,21 @@ def gradients(h, ridge, rays, spp, aux=16, kappa=2e4, exponent=3.0, reparam=True
     return float(L.detach()), float(shape.heightfield.grad[ridge].double().sum())
 
 
+def forward_derivative(h, ridge, rays, spp, aux=16, kappa=2e4, exponent=3.0, seed=0):
+    """dL/dtheta for the same theta in forward mode: one pass with the tangent 'lift every ridge texel' on the heights"""
+    shape = hf_amd.Heightfield(heightfield=h.clone(), max_height=0.5)
+    h0 = shape.heightfield
+    ray = hf_amd.Ray3f(rays[0:3].contiguous(), rays[3:6].contiguous(), rays[6].contiguous())
+    with fwAD.dual_level():
+        shape.heightfield = fwAD.make_dual(h0, ridge.to(h0.dtype))
+        d, det = hf_amd.reparameterize_ray(shape, ray, num_rays=aux, kappa=kappa, exponent=exponent, seed=seed)
+        si = shape.ray_intersect(hf_amd.Ray3f(ray.o, d, ray.maxt), hf_amd.RayFlags.All)
+        L = (f_of(si) * det).sum() / spp
+        tangent = fwAD.unpack_dual(L).tangent
+    shape.heightfield = h0
+    return float(L.detach()), 0.0 if tangent is None else float(tangent)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--film", type=int, default=192)
@@ -72,6 +91,7 @@ def main():
     ap.add_argument("--aux", type=int, default=16)
     ap.add_argument("--kappa", type=float, default=2e4)
     ap.add_argument("--eps", type=float, default=0.02)
+    ap.add_argument("--forward", action="store_true", help="also the forward-mode derivative")
     a = ap.parse_args()
     dev = torch.device("cuda")
     h, ridge = scene(device=dev)
@@ -84,6 +104,10 @@ def main():
     print(f"finite differences (eps {a.eps}):      dL/dtheta = {fd:.3f}")
     print(f"attached geometry only:               dL/dtheta = {g_att:.3f}   (misses the silhouette: {g_att / fd:.2f} of FD)")
     print(f"with reparameterize_ray ({a.aux} aux rays): dL/dtheta = {g_rep:.3f}   ({g_rep / fd:.2f} of FD)")
+    if a.forward:
+        _, g_fwd = forward_derivative(h, ridge, rays, a.spp, aux=a.aux, kappa=a.kappa)
+        print(f"forward mode, reparameterised:        dL/dtheta = {g_fwd:.3f}   ({g_fwd / fd:.2f} of FD, "
+              f"{abs(g_fwd - g_rep) / abs(g_rep):.1e} from reverse mode)")
     return fd, g_att, g_rep
 
 

@@ -722,6 +722,23 @@ int hf_reparam_backward(const hf_field_t *hf, size_t n, const float *const o[3],
                         size_t sample_stride,
                         const float *const grad_direction[3], const float *grad_divergence, float *grad_heights,
                         hf_stream_t stream);
+/* Forward mode of the same reparameterisation (_ReparameterizeOp.forward(), src/python/python/ad/reparam.py:155-221;
+ * src/render/tests/test_reparameterization.py:29-98 checks it), in ONE kernel from the same kept auxiliary hits as
+ * hf_reparam_backward (pi and si_boundary_test at [k * sample_stride + i], as hf_reparam_trace_all writes them) and the
+ * same samples (seed, ray_id, antithetic).  Tangents, any subset, NULL = zero: dheights (device H*W floats), d_o[3] /
+ * d_d[3] (device rows of n floats; the arrays or single rows may be NULL), d_to_world (12 device floats, row-major 3x4).
+ * The weights w_k, d_w_omega_k are detached (B = si.boundary_test for a hit, 1 for a miss); Z = sum w_k and
+ * dZ = sum d_w_omega_k in sample order.  dV_k is the tangent of V_direct_k = (p - o) / t for a hit (FollowShape p with
+ * detached barycentrics, t = sqrt(|p - o|^2 / |d_aux|^2), d_aux = Frame3f(d).to_world(omega_k), omega_k detached) and
+ * d_d for a miss.  Writes out_direction[3][n] = V_theta = sum_k w_k dV_k / max(Z, 1e-8) and out_divergence[n] =
+ * (sum_k <d_w_omega_k, dV_k> - <V_theta, dZ>) / max(Z, 1e-8), overwritten; inactive lanes get 0.  The primal outputs
+ * are (d, 1).  No atomics (bitwise repeatable), no allocation, capturable.  1 <= num_rays <= 32. */
+int hf_reparam_tangent(const hf_field_t *hf, size_t n, const float *const o[3], const float *const d[3],
+                       const uint8_t *active, uint32_t num_rays, float kappa, float exponent, int antithetic,
+                       uint32_t seed, const uint32_t *ray_id, const hf_pi_const_t *pi, const float *si_boundary_test,
+                       size_t sample_stride, const float *dheights, const float *const d_o[3],
+                       const float *const d_d[3], const float *d_to_world, float *const out_direction[3],
+                       float *out_divergence, hf_stream_t stream);
 
 /* ---- scalar / packet entry -----------------------------------------------------
  * Shape::ray_intersect_preliminary_scalar / _packet and ray_test_scalar / _packet

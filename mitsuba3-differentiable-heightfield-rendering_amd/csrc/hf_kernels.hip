@@ -2860,6 +2860,173 @@ void hf_launch_reparam_backward(const hf_dev_field &f, const hf_reparam_args &ra
 }
 
 // ---------------------------------------------------------------------------------
+// Forward mode of the warped-area reparameterisation (reparam.py:155-221): for every ray, from its num_rays kept
+// auxiliary hits, V_theta = sum_k w_k dV_k / Z and div = (sum_k <d_w_omega_k, dV_k> - <V_theta, dZ>) / Z, where dV_k is
+// the tangent of V_direct_k = (p - o) / t (FollowShape p and t, detached barycentrics) for a hit and ray.d's tangent
+// for a miss.  The weights are detached, so ONE pass over the samples yields Z, dZ and both numerators: every sample is
+// drawn once and nothing is kept across samples.  A gather per hit and one store per output row: no atomics (bitwise
+// repeatable).  Instantiated on the tangents present: DH heights, RAY ray.o / ray.d, XF to_world.
+// ---------------------------------------------------------------------------------
+struct hf_reparam_tan_args {
+    size_t n, stride;
+    const float *o[3], *d[3];
+    const uint8_t *active;
+    uint32_t num_rays, seed;
+    float kappa, exponent;
+    int antithetic;
+    const uint32_t *ray_id;
+    hf_pi_const_t pi;
+    const float *si_bt;
+    const float *dh, *d_o[3], *d_d[3], *dM; // tangents (DH, RAY, XF); rows of d_o / d_d may be NULL (zero)
+    float *out_dir[3], *out_div;
+};
+struct hf_reparam_tan_kargs {
+    hf_dev_field f;
+    hf_reparam_tan_args a;
+};
+template <bool DH, bool RAY, bool XF>
+__global__ __launch_bounds__(HF_BLOCK) void hf_reparam_tangent_kernel(hf_reparam_tan_kargs k_) {
+    (void) k_;
+    typedef const __attribute__((address_space(4))) hf_reparam_tan_kargs *kargs_t;
+    kargs_t kc = (kargs_t) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kc));
+    const size_t a_n = kc->a.n;
+    float dM[12]; // XF: wave-uniform
+    if constexpr (XF) {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) dM[j] = kc->a.dM[j];
+    }
+    hf_reparam_args sa = {}; // what the sampling helpers read
+    sa.seed = kc->a.seed; sa.kappa = kc->a.kappa; sa.exponent = kc->a.exponent; sa.antithetic = kc->a.antithetic;
+    sa.ray_id = kc->a.ray_id;
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a_n; i += stride) {
+        kargs_t ka = (kargs_t) __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka)); // opaque: keeps the loads that follow inside the loop body
+        const v3 z3 = mk3(0.f, 0.f, 0.f);
+        const bool act = ka->a.active ? (ka->a.active[i] != 0) : true;
+        v3 Vt = z3;
+        float div = 0.f;
+        const size_t sst = ka->a.stride;
+        const uint32_t K = ka->a.num_rays;
+        uint32_t hm = 0u; // samples that hit
+        if (act)
+            for (uint32_t k = 0; k < K; ++k) hm |= (ka->a.pi.t[k * sst + i] != __builtin_inff()) ? (1u << k) : 0u;
+        // Without a ray tangent a miss contributes dV = 0, so a ray none of whose samples hit gets exactly 0 (what the
+        // sums would give: +0 * iZ) without drawing its samples; a wave of such rays skips to the stores, as
+        // hf_reparam_backward_kernel skips the waves that do not reach the heights
+        const bool work = act && (RAY || hm != 0u);
+        if (__ballot(work) != 0ull && work) {
+            const v3 d = mk3(ka->a.d[0][i], ka->a.d[1][i], ka->a.d[2][i]);
+            v3 o = z3, dO = z3, dD = z3, dfs = z3, dft = z3;
+            if (hm != 0u) o = mk3(ka->a.o[0][i], ka->a.o[1][i], ka->a.o[2][i]);
+            if constexpr (RAY) {
+                dO = mk3(ldu(ka->a.d_o[0], 0, i), ldu(ka->a.d_o[1], 0, i), ldu(ka->a.d_o[2], 0, i));
+                dD = mk3(ldu(ka->a.d_d[0], 0, i), ldu(ka->a.d_d[1], 0, i), ldu(ka->a.d_d[2], 0, i));
+                coordinate_system_jvp(d, dD, dfs, dft); // Frame3f(d)'s tangent: the auxiliary directions follow d
+            }
+            // Z = sum_k w_k, dZ = sum_k d_w_omega_k and the numerators, in sample order from zero.  The loop is written
+            // for latency: the records of sample k + 1 are requested before sample k is worked on, and a hit's heights
+            // (and height tangents) before its sample is drawn, so that neither load round trip waits idle
+            const hf_dev_field f = load_field(&ka->f);
+            const v3 ez = height_axis(f); // dP_k/dh_k
+            float Zs = 0.f, gdiv = 0.f;
+            v3 dZ = z3, gV = z3;
+            float nbt = 1.f, nb1 = 0.f, nb2 = 0.f; // the next sample's record (a hit's)
+            uint32_t nprim = 0u;
+            if (hm & 1u) { nbt = ka->a.si_bt[i]; nb1 = ka->a.pi.prim_uv[0][i]; nb2 = ka->a.pi.prim_uv[1][i]; nprim = ka->a.pi.prim_index[i]; }
+            for (uint32_t k = 0; k < K; ++k) {
+                const bool hit = ((hm >> k) & 1u) != 0u;
+                const float B = hit ? nbt : 1.0f, b1 = nb1, b2 = nb2;
+                const uint32_t prim = nprim;
+                if (k + 1 < K && ((hm >> (k + 1)) & 1u)) { // (k + 1 < K first: a shift by 32 is not defined)
+                    const size_t ik1 = (k + 1) * sst + i;
+                    nbt = ka->a.si_bt[ik1]; nb1 = ka->a.pi.prim_uv[0][ik1]; nb2 = ka->a.pi.prim_uv[1][ik1];
+                    nprim = ka->a.pi.prim_index[ik1];
+                }
+                int vi[3], vj[3];
+                float hz[3] = { 0.f, 0.f, 0.f }, dz[3] = { 0.f, 0.f, 0.f };
+                if (hit) { // the three heights and their tangents: prim_world's loads, used below
+                    prim_vertex_ids(f, prim, vi, vj);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const size_t idx = (size_t) vi[c] * f.W + vj[c];
+                        hz[c] = f.h[idx];
+                        if constexpr (DH) dz[c] = ka->a.dh[idx];
+                    }
+                }
+                sa.k = k;
+                hf_aux_sample q;
+                aux_sample(sa, i, d, q);
+                float w;
+                v3 dw;
+                reparam_weight(sa, q, d, B, w, dw);
+                Zs += w;
+                dZ.x += dw.x; dZ.y += dw.y; dZ.z += dw.z;
+                v3 dV = dD; // miss: V_direct = ray.d (reparam.py:93-95)
+                if (hit) {
+                    const float b0 = 1.f - b1 - b2;
+                    v3 P[3], dP[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) { // prim_world's expressions; dP_k = dh_k ez (+ dM (q_k, 1))
+                        const v3 ql = grid_local(f, vi[c], vj[c], hz[c]);
+                        P[c] = xform_point(f.to_world, ql);
+                        dP[c] = ez * dz[c];
+                        if constexpr (XF) dP[c] = dP[c] + xform_point(dM, ql);
+                    }
+                    const v3 da = frame_to_world(q, d, q.omega); // the auxiliary direction (= hf_reparam_aux_kernel's)
+                    // V_direct = (p - o) / t with the FollowShape t = sqrt(|p - o|^2 / |d_aux|^2) of compute_si
+                    const auto [po, dda, tt] = follow_t(bary_point(P, b0, b1, b2), o, da);
+                    const v3 rel = ((DH || XF) ? bary_point(dP, b0, b1, b2) : z3) - dO; // (p - o)'s tangent
+                    float dt = dot3(po, rel) / (tt * dda);
+                    if constexpr (RAY) { // d_aux = s(d) omega.x + t(d) omega.y + d omega.z, omega detached
+                        const v3 dda_v = mk3(__builtin_fmaf(dD.x, q.omega.z, __builtin_fmaf(dft.x, q.omega.y, dfs.x * q.omega.x)),
+                                             __builtin_fmaf(dD.y, q.omega.z, __builtin_fmaf(dft.y, q.omega.y, dfs.y * q.omega.x)),
+                                             __builtin_fmaf(dD.z, q.omega.z, __builtin_fmaf(dft.z, q.omega.y, dfs.z * q.omega.x)));
+                        dt -= tt * dot3(da, dda_v) / dda;
+                    }
+                    const float it = 1.0f / tt, c = dt * it * it;
+                    dV = mk3(rel.x * it - po.x * c, rel.y * it - po.y * c, rel.z * it - po.z * c);
+                }
+                gV.x += w * dV.x; gV.y += w * dV.y; gV.z += w * dV.z;
+                gdiv += dot3(dw, dV);
+            }
+            const float iZ = 1.0f / fmaxf(Zs, 1e-8f);
+            Vt = gV * iZ;
+            div = (gdiv - dot3(Vt, dZ)) * iZ;
+        }
+        ka->a.out_dir[0][i] = Vt.x; ka->a.out_dir[1][i] = Vt.y; ka->a.out_dir[2][i] = Vt.z;
+        ka->a.out_div[i] = div;
+    }
+}
+
+void hf_launch_reparam_tangent(const hf_dev_field &f, const hf_reparam_args &ra, uint32_t num_rays, size_t stride,
+                               const hf_pi_const_t *pi, const float *dh, const float *const d_o[3],
+                               const float *const d_d[3], const float *d_to_world, float *const out_dir[3],
+                               float *out_div, hipStream_t stream) {
+    if (ra.n == 0) return;
+    hf_reparam_tan_kargs k = {};
+    hf_reparam_tan_args &a = k.a;
+    k.f = f;
+    a.n = ra.n; a.stride = stride; a.active = ra.active; a.num_rays = num_rays; a.seed = ra.seed; a.kappa = ra.kappa;
+    a.exponent = ra.exponent; a.antithetic = ra.antithetic; a.ray_id = ra.ray_id; a.pi = *pi; a.si_bt = ra.si_bt;
+    a.dh = dh; a.dM = d_to_world; a.out_div = out_div;
+    bool ray = false;
+    for (int c = 0; c < 3; ++c) {
+        a.o[c] = ra.o[c]; a.d[c] = ra.d[c]; a.out_dir[c] = out_dir[c];
+        a.d_o[c] = d_o ? d_o[c] : nullptr; a.d_d[c] = d_d ? d_d[c] : nullptr;
+        ray = ray || a.d_o[c] || a.d_d[c];
+    }
+    void (*const table[8])(hf_reparam_tan_kargs) = {
+        hf_reparam_tangent_kernel<false, false, false>, hf_reparam_tangent_kernel<true, false, false>,
+        hf_reparam_tangent_kernel<false, true, false>, hf_reparam_tangent_kernel<true, true, false>,
+        hf_reparam_tangent_kernel<false, false, true>, hf_reparam_tangent_kernel<true, false, true>,
+        hf_reparam_tangent_kernel<false, true, true>, hf_reparam_tangent_kernel<true, true, true> };
+    const int sel = (dh ? 1 : 0) | (ray ? 2 : 0) | (d_to_world ? 4 : 0);
+    hipLaunchKernelGGL(table[sel], dim3(grid_for(ra.n)), dim3(HF_BLOCK), 0, stream, k);
+}
+
+// ---------------------------------------------------------------------------------
 // Adam step on the height texture (optimizers.py:263-300), explicit operation order (no contraction)
 // ---------------------------------------------------------------------------------
 // (sched, ctr): hf_adam_step_scheduled -- the step size is sched[*ctr] (a host-filled table of the bias-corrected step

@@ -95,6 +95,12 @@ void hf_launch_reparam_aux(const hf_reparam_args &a, hipStream_t stream);
 void hf_launch_reparam_weights(const hf_reparam_args &a, hipStream_t stream);
 void hf_launch_reparam_backward(const hf_dev_field &f, const hf_reparam_args &a, uint32_t num_rays, size_t stride,
                                 const hf_pi_const_t *pi, float *grad_h, hipStream_t stream);
+// hf_reparam_tangent: a.active / seed / kappa / exponent / antithetic / ray_id / o / d / si_bt are read; dh, d_o, d_d
+// (or single rows of them), d_to_world (12 device floats) may be NULL (zero tangents); out_dir / out_div overwritten
+void hf_launch_reparam_tangent(const hf_dev_field &f, const hf_reparam_args &a, uint32_t num_rays, size_t stride,
+                               const hf_pi_const_t *pi, const float *dh, const float *const d_o[3],
+                               const float *const d_d[3], const float *d_to_world, float *const out_dir[3],
+                               float *out_div, hipStream_t stream);
 // ---- area sampling (hf_set_area_sampling) ----
 #define HF_AREA_CHUNK 2048 // cells per tile of the table build: one cell row, or a 2048-cell piece of one
 #define HF_AREA_SEG 64     // CDF entries per entry of the coarse search table

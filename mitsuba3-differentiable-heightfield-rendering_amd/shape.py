@@ -1675,6 +1675,80 @@ def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, n
     return grad_h, grad_o, grad_d
 
 
+def _reparam_tangent(shape, o, d, act, ray_index, cfg, dh, do, dd, dtw, stream):
+    """Forward mode (reparam.py:155-221): hf_reparam_trace_all keeps every auxiliary hit (pi + si.boundary_test,
+    20 B per ray and sample), then hf_reparam_tangent.  When the records of all rays exceed REPARAM_KEEP_BYTES the rays
+    go in chunks, each with its global ids as ray_id (or its slice of ray_index): the samples, and so the result, do
+    not depend on the chunking.  Returns (V_theta [3, n], div [n])."""
+    L = _capi.lib()
+    num_rays, kappa, exponent, antithetic, seed = cfg
+    dev = o.device
+    n = o.shape[1]
+    out_dir = torch.empty((3, n), dtype=torch.float32, device=dev)
+    out_div = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out_dir, out_div
+    chunk = max(1, min(n, REPARAM_KEEP_BYTES // (20 * num_rays)))
+    store = torch.empty((num_rays, 5, chunk), dtype=torch.float32, device=dev)   # bt, t, u, v, prim per sample
+    rows = [store[0, r].data_ptr() for r in range(5)]
+    si_s = _capi.hf_si_t()
+    si_s.boundary_test = rows[0]
+    pi_s = _capi.hf_pi_t()
+    pi_s.t, pi_s.prim_uv[0], pi_s.prim_uv[1], pi_s.prim_index = rows[1], rows[2], rows[3], rows[4]
+    dh_p = dh.data_ptr() if dh is not None else None
+    dtw_p = dtw.data_ptr() if dtw is not None else None
+    for s in range(0, n, chunk):   # (row slices of [3, n] tensors are rows of m floats: no copies)
+        m = min(chunk, n - s)
+        sl = slice(s, s + m)
+        if ray_index is not None:
+            rid = ray_index[sl]
+        elif m < n:
+            rid = torch.arange(s, s + m, dtype=torch.int32, device=dev)
+        else:
+            rid = None
+        o_p, d_p = _p3(o[:, sl]), _p3(d[:, sl])
+        act_p = act[sl].data_ptr() if act is not None else None
+        rid_p = rid.data_ptr() if rid is not None else None
+        check(L.hf_reparam_trace_all(shape._h, m, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, int(antithetic),
+                                     seed, rid_p, C.byref(pi_s), C.byref(si_s), 5 * chunk, stream))
+        check(L.hf_reparam_tangent(shape._h, m, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, exponent,
+                                   int(antithetic), seed, rid_p, C.byref(pi_s), rows[0], 5 * chunk, dh_p,
+                                   C.byref(_p3(do[:, sl])) if do is not None else None,
+                                   C.byref(_p3(dd[:, sl])) if dd is not None else None, dtw_p,
+                                   C.byref(_p3(out_dir[:, sl])), out_div[sl].data_ptr(), stream))
+    return out_dir, out_div
+
+
+def _tangent_f32(x, numel, dev, what):
+    """a tangent as a contiguous float32 device tensor (None: zero)"""
+    if x is None:
+        return None
+    x = torch.as_tensor(x, device=dev).detach().to(torch.float32).contiguous()
+    if x.numel() != numel:
+        raise ValueError(f"{what}: expected {numel} values, got {x.numel()}")
+    return x
+
+
+def _reparam_tangent_entry(shape, ray_o, ray_d, dh, do, dd, dtw, num_rays, kappa, exponent, antithetic, seed, active,
+                           ray_index):
+    o = ray_o.detach().to(torch.float32).contiguous()
+    d = ray_d.detach().to(torch.float32).contiguous()
+    n, dev = o.shape[1], o.device
+    act = None if active is None else torch.as_tensor(active, device=dev).to(torch.uint8).reshape(-1).contiguous()
+    if act is not None and act.numel() != n:
+        raise ValueError("active: one flag per ray")
+    dh = _tangent_f32(dh, shape.width * shape.height, dev, "dheights")
+    do = _tangent_f32(do, 3 * n, dev, "d_o")
+    dd = _tangent_f32(dd, 3 * n, dev, "d_d")
+    dtw = _tangent_f32(dtw, 12, dev, "d_to_world")
+    if num_rays < 1 or num_rays > 32:
+        raise ValueError("num_rays: 1..32 auxiliary rays per ray")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    cfg = (int(num_rays), float(kappa), float(exponent), bool(antithetic), int(seed))
+    return _reparam_tangent(shape, o, d, act, ray_index, cfg, dh, None if do is None else do.view(3, n),
+                            None if dd is None else dd.view(3, n), dtw, stream)
+
+
 class _ReparameterizeOp(torch.autograd.Function):
     """reparam.py:126-333 for a scene that is one heightfield: identity in primal mode; in backward mode the
     warped-area gradient of (direction, determinant) with respect to the heights AND the ray (reparam.py:296-325
@@ -1686,10 +1760,20 @@ class _ReparameterizeOp(torch.autograd.Function):
         ctx.shape = shape
         ctx.tw_like = _tw_like(to_world)
         ctx.save_for_backward(ray_o, ray_d)
+        ctx.save_for_forward(ray_o, ray_d)
+        ctx.set_materialize_grads(False)   # jvp: an input without a tangent arrives as None, not as zeros
         ctx.cfg = (int(num_rays), float(kappa), float(exponent), bool(antithetic), int(seed), active, ray_index)
         n = ray_o.shape[1]
         # (an alias of ray.d, not a copy -- 0.8 GB and 0.27 ms for the bench wavefront: the values are ray.d's, reparam.py:139-155)
         return ray_d.detach(), torch.ones(n, dtype=torch.float32, device=ray_o.device)
+
+    @staticmethod
+    def jvp(ctx, dh, do, dd, _shape, _num_rays, _kappa, _exponent, _antithetic, _seed, _active, _ray_index, dtw=None):
+        """reparam.py:155-221: the tangents (V_theta, div V_theta) of (direction, det), hf_reparam_tangent"""
+        ray_o, ray_d = ctx.saved_tensors
+        num_rays, kappa, exponent, antithetic, seed, active, ray_index = ctx.cfg
+        return _reparam_tangent_entry(ctx.shape, ray_o, ray_d, dh, do, dd, _tw_tangent(dtw), num_rays, kappa, exponent,
+                                      antithetic, seed, active, ray_index)
 
     @staticmethod
     def backward(ctx, grad_direction, grad_divergence):
@@ -1702,6 +1786,10 @@ class _ReparameterizeOp(torch.autograd.Function):
         need_tw = ctx.needs_input_grad[11]
         n = ray_o.shape[1]
         o = ray_o.detach().to(torch.float32).contiguous(); d = ray_d.detach().to(torch.float32).contiguous()
+        if grad_direction is None:
+            grad_direction = torch.zeros_like(d)
+        if grad_divergence is None:
+            grad_divergence = torch.zeros(n, dtype=torch.float32, device=d.device)
         gd = grad_direction.to(torch.float32).contiguous(); gdiv = grad_divergence.to(torch.float32).contiguous()
         act = None if active is None else active.to(torch.uint8).contiguous()
         act_p = None if act is None else act.data_ptr()
@@ -1742,3 +1830,21 @@ def reparameterize_ray(shape, ray, num_rays=4, kappa=1e5, exponent=3.0, antithet
         ray_index = ray_index.contiguous()
     return _ReparameterizeOp.apply(shape.heightfield, ray.o, ray.d, shape, num_rays, kappa, exponent, antithetic, seed,
                                    active, ray_index, shape._to_world_live())
+
+
+def reparameterize_ray_tangent(shape, ray, dheights=None, d_o=None, d_d=None, d_to_world=None, num_rays=4, kappa=1e5,
+                               exponent=3.0, antithetic=False, seed=0, active=None, ray_index=None):
+    """Explicit forward mode of ``reparameterize_ray`` (reparam.py:155-221): ``(V_theta [3, n], div [n])``, the
+    tangents of ``(direction, det)`` for tangents of the heights (``dheights`` [H, W]), of the ray (``d_o``, ``d_d``
+    [3, n]) and of ``to_world`` (``d_to_world``: 3x4 / 4x4 / 12 values), any of them None (zero).  The same samples as
+    ``reparameterize_ray`` for the same ``seed`` and ``ray_index``; ``hf_reparam_trace_all`` + ``hf_reparam_tangent``."""
+    if ray_index is not None:
+        if ray_index.dtype not in (torch.int32, torch.uint32) or ray_index.numel() != ray.o.shape[1]:
+            raise ValueError("ray_index must be an int32/uint32 tensor with one id per ray")
+        if ray_index.device != ray.o.device:
+            raise ValueError("ray_index must live on the rays' device")
+        ray_index = ray_index.contiguous()
+    if d_to_world is not None:
+        d_to_world = _tw_tangent(torch.as_tensor(d_to_world, device=ray.o.device))
+    return _reparam_tangent_entry(shape, ray.o, ray.d, dheights, d_o, d_d, d_to_world, num_rays, kappa, exponent,
+                                  antithetic, seed, active, ray_index)
