@@ -49,6 +49,151 @@ def _as_f32(x, device):
     return t.contiguous()
 
 
+# ---- marshalling: what every call into libhf builds its arguments with -------------------------------------------------
+def _ptr(x):
+    """address of a device tensor or a host (numpy) array; None stays None (a NULL argument)"""
+    if x is None:
+        return None
+    return x.data_ptr() if isinstance(x, torch.Tensor) else x.ctypes.data
+
+
+def _ref(c):
+    """C.byref of a ctypes array or struct; None stays None"""
+    return None if c is None else C.byref(c)
+
+
+def _row_addrs(x):
+    """addresses of the rows of a [k, n] array: a device tensor, a row or column slice of one (row slices of
+    [3, n] tensors are rows of m floats: no copies), or a host (numpy) array"""
+    if isinstance(x, torch.Tensor):
+        # (an empty tensor has the address 0, and so have its rows)
+        base, step = x.data_ptr(), x.stride(0) * x.element_size() if x.numel() else 0
+    else:
+        base, step = x.ctypes.data, x.strides[0]
+    return [base + step * k for k in range(x.shape[0])]
+
+
+def _row_ptrs(x, k=None):
+    """ctypes array of the row pointers of a [k, n] array (see _row_addrs), NULL-padded to k entries; None stays None"""
+    if x is None:
+        return None
+    addrs = _row_addrs(x)
+    return (C.c_void_p * (k or len(addrs)))(*addrs)
+
+
+def _rows(buf, n):
+    """device addresses of the rows of a contiguous [k, n] float32 tensor"""
+    return _row_addrs(buf)
+
+
+def _p3(x):
+    """ctypes array of the 3 row pointers of a [3, n] tensor"""
+    return _row_ptrs(x)
+
+
+def _f3(x):
+    """[3, n] float32 device tensor -> (keepalive, ctypes array of 3 row pointers)"""
+    x = x.to(dtype=torch.float32).contiguous()
+    return x, _p3(x)
+
+
+def _fill(struct, layout, addrs):
+    """set the pointer fields of a ctypes struct, named by layout = [(field, rows), ...], to consecutive addresses"""
+    k = 0
+    for name, c in layout:
+        if c == 1:
+            setattr(struct, name, addrs[k])
+        else:
+            arr = getattr(struct, name)
+            for j in range(c):
+                arr[j] = addrs[k + j]
+        k += c
+    return struct
+
+
+def _stream_of(device):
+    """the current stream of `device` as the hf_stream_t of the C ABI"""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _tangent(x, shape, device, what, exc=AssertionError):
+    """a tangent or an upstream gradient as a contiguous float32 device tensor of `shape`; None (zero) stays None.
+    A wrong number of values raises `exc`: AssertionError from the Heightfield methods, ValueError from the
+    reparameterisation entries."""
+    if x is None:
+        return None
+    x = torch.as_tensor(x, device=device).detach().to(torch.float32).contiguous()
+    if x.numel() != math.prod(shape):
+        raise exc(f"{what}: expected {math.prod(shape)} values, got {x.numel()}")
+    return x.reshape(shape)
+
+
+def _tw_tangent(dtw, device=None, exc=AssertionError):
+    """a 3x4 / 4x4 (last row dropped) / 12-value tangent of to_world as the 12 contiguous float32 device values of the
+    C ABI (None: zero)"""
+    if dtw is None:
+        return None
+    dtw = torch.as_tensor(dtw, device=device).detach().reshape(-1)
+    return _tangent(dtw[:12] if dtw.numel() == 16 else dtw, (12,), dtw.device, "d_to_world", exc)
+
+
+def _tw_like(to_world):
+    """(shape, dtype, device) of a to_world input, None without one"""
+    return None if to_world is None else (tuple(to_world.shape), to_world.dtype, to_world.device)
+
+
+def _tw_grad(grad12, like):
+    """the 12 floats of dL/d(to_world) as a gradient of the user's 3x4 / 4x4 tensor (a 4x4's last row gets zeros);
+    None (not wanted) stays None"""
+    if grad12 is None:
+        return None
+    shape, dtype, device = like
+    g = grad12.reshape(3, 4)
+    if shape[0] == 4:
+        g = torch.cat([g, torch.zeros((1, 4), dtype=g.dtype, device=g.device)])
+    return g.reshape(shape).to(device=device, dtype=dtype)
+
+
+def _grad12(grad_tw):
+    """a caller's dL/d(to_world) accumulator as the C ABI takes it: 12 contiguous float32 device values (or None)"""
+    assert grad_tw is None or (grad_tw.numel() == 12 and grad_tw.dtype == torch.float32 and grad_tw.is_contiguous())
+    return grad_tw
+
+
+def _has_tangent(x):
+    """a forward-mode AD tangent is attached to x (torch.autograd.forward_ad; False outside a dual level)"""
+    return isinstance(x, torch.Tensor) and fwAD.unpack_dual(x).tangent is not None
+
+
+# ---- what the height / to_world differentiable ops share: each op below states its inputs, C calls and return tuple ----
+_STALE = {"jvp": "heightfield parameters changed between the primal and the tangent pass",
+          "backward": "heightfield parameters changed between forward and backward"}
+
+
+def _op_save(ctx, shape, tensors, to_world=None):
+    """forward: keep `tensors` for both derivative passes, stamp the parameter version, remember to_world's layout"""
+    ctx.shape = shape
+    ctx.save_for_backward(*tensors)
+    ctx.save_for_forward(*tensors)
+    ctx.h_version = shape._param_version()
+    ctx.tw_like = _tw_like(to_world)
+
+
+def _op_saved(ctx, which):
+    """jvp / backward: (shape, saved tensors), refused when the parameters changed since the primal pass"""
+    if ctx.h_version != ctx.shape._param_version():
+        raise RuntimeError(_STALE[which])
+    return ctx.shape, ctx.saved_tensors
+
+
+def _op_grads(ctx, i_heights, i_to_world):
+    """backward: zeroed accumulators (dL/dheight [H, W], dL/d(to_world) [12]) for the inputs that need a gradient"""
+    shape = ctx.shape
+    grad_h = shape._zero_heights() if ctx.needs_input_grad[i_heights] else None
+    grad_tw = torch.zeros(12, dtype=torch.float32, device=shape.device) if ctx.needs_input_grad[i_to_world] else None
+    return grad_h, grad_tw
+
+
 class Ray3f:
     """SoA ray wavefront: o, d as [3, n] float32 tensors, maxt [n] (default +inf,
     i.e. dr::Largest, ray.h:37).  time / wavelengths are carried but unused."""
@@ -184,33 +329,22 @@ class _SamplePositionOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, shape, heights, prim, b, active, block, to_world=None):
-        ctx.shape, ctx.active = shape, active
-        ctx.save_for_backward(prim, b)
-        ctx.save_for_forward(prim, b)
-        ctx.h_version = shape._param_version()
-        ctx.tw_like = _tw_like(to_world)
+        _op_save(ctx, shape, (prim, b), to_world)
+        ctx.active = active
         return block
 
     @staticmethod
     def jvp(ctx, _shape, dh, _prim, _b, _active, _block, dtw=None):
-        shape = ctx.shape
-        prim, b = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
-        return shape._sample_tangent_raw(prim, b, ctx.active, dh, _tw_tangent(dtw))
+        shape, (prim, b) = _op_saved(ctx, "jvp")
+        return shape._sample_tangent_raw(prim, b, ctx.active, dh, dtw)
 
     @staticmethod
     def backward(ctx, g):
-        shape = ctx.shape
-        prim, b = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between forward and backward")
-        need_h, need_tw = ctx.needs_input_grad[1], ctx.needs_input_grad[6]
-        grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=prim.device) if need_h else None
-        grad_tw = torch.zeros(12, dtype=torch.float32, device=prim.device) if need_tw else None
-        if need_h or need_tw:
+        shape, (prim, b) = _op_saved(ctx, "backward")
+        grad_h, grad_tw = _op_grads(ctx, 1, 6)
+        if grad_h is not None or grad_tw is not None:
             shape._sample_adjoint_raw(prim, b, ctx.active, g.contiguous().to(torch.float32), grad_h, grad_tw)
-        return None, grad_h, None, None, None, None, (_tw_grad(grad_tw, ctx.tw_like) if need_tw else None)
+        return None, grad_h, None, None, None, None, _tw_grad(grad_tw, ctx.tw_like)
 
 
 class _AttributeOp(torch.autograd.Function):
@@ -220,27 +354,19 @@ class _AttributeOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, shape, name, attr, p, heights, prim, t, active, value):
-        ctx.shape, ctx.name, ctx.active = shape, name, active
         p = p.detach().contiguous() if p is not None else None
-        ctx.save_for_backward(attr.detach(), p, prim, t)
-        ctx.save_for_forward(attr.detach(), p, prim, t)
-        ctx.h_version = shape._param_version()
+        _op_save(ctx, shape, (attr.detach(), p, prim, t))
+        ctx.name, ctx.active = name, active
         return value
 
     @staticmethod
     def jvp(ctx, _shape, _name, dattr, dp, dh, *_):
-        shape = ctx.shape
-        attr, p, prim, t = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
+        shape, (attr, p, prim, t) = _op_saved(ctx, "jvp")
         return shape._attr_tangent_raw(ctx.name, attr, p, prim, t, ctx.active, dattr, dp, dh)
 
     @staticmethod
     def backward(ctx, g):
-        shape = ctx.shape
-        attr, p, prim, t = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between forward and backward")
+        shape, (attr, p, prim, t) = _op_saved(ctx, "backward")
         need_a, need_p, need_h = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         ga, gp, gh = shape._attr_adjoint_raw(ctx.name, attr, p, prim, t, ctx.active, g.contiguous().to(torch.float32),
                                              need_a, need_p, need_h)
@@ -250,30 +376,10 @@ class _AttributeOp(torch.autograd.Function):
 # order of the differentiable SI block handed to autograd: 18 rows
 _DIFF_ROWS = [("t", 1), ("p", 3), ("n", 3), ("uv", 2), ("sh_n", 3), ("dp_du", 3), ("dp_dv", 3)]
 _AUX_ROWS = [("boundary_test", 1), ("sh_s", 3), ("sh_t", 3), ("wi", 3)]
-
-
-def _rows(buf, n):
-    """device addresses of the rows of a contiguous [k, n] float32 tensor"""
-    base = buf.data_ptr()
-    return [base + 4 * n * k for k in range(buf.shape[0])]
-
-
-def _has_tangent(x):
-    """a forward-mode AD tangent is attached to x (torch.autograd.forward_ad; False outside a dual level)"""
-    return isinstance(x, torch.Tensor) and fwAD.unpack_dual(x).tangent is not None
-
-
-def _fill(struct, layout, addrs):
-    k = 0
-    for name, c in layout:
-        if c == 1:
-            setattr(struct, name, addrs[k])
-        else:
-            arr = getattr(struct, name)
-            for j in range(c):
-                arr[j] = addrs[k + j]
-        k += c
-    return struct
+# the pointer fields of hf_rays_t, hf_pi_t and hf_position_sample_t, in the order _fill takes their addresses
+_RAY_ROWS = [("o", 3), ("d", 3), ("maxt", 1)]
+_PI_ROWS = [("t", 1), ("prim_uv", 2), ("prim_index", 1)]
+_SAMPLE_ROWS = [("p", 3), ("n", 3), ("uv", 2), ("pdf", 1), ("prim_index", 1), ("b", 2)]
 
 
 class _SurfaceInteractionOp(torch.autograd.Function):
@@ -282,39 +388,27 @@ class _SurfaceInteractionOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, shape, heights, o, d, maxt, t, uv, prim, flags, active, diff_block, to_world=None):
-        ctx.shape, ctx.flags, ctx.active = shape, flags, active
-        ctx.save_for_backward(o, d, maxt, t, uv, prim)
-        ctx.save_for_forward(o, d, maxt, t, uv, prim)
-        ctx.h_version = shape._param_version()
-        ctx.tw_like = _tw_like(to_world)
+        _op_save(ctx, shape, (o, d, maxt, t, uv, prim), to_world)
+        ctx.flags, ctx.active = flags, active
         return diff_block
 
     @staticmethod
     def jvp(ctx, _shape, dh, do, dd, _maxt, _t, _uv, _prim, _flags, _active, _diff, dtw=None):
-        shape = ctx.shape
-        o, d, maxt, t, uv, prim = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
-        return shape._tangent_raw(o, d, maxt, t, uv, prim, ctx.flags, ctx.active, dh, do, dd, _tw_tangent(dtw))
+        shape, saved = _op_saved(ctx, "jvp")
+        return shape._tangent_raw(*saved, ctx.flags, ctx.active, dh, do, dd, dtw)
 
     @staticmethod
     def backward(ctx, g):
-        shape = ctx.shape
-        o, d, maxt, t, uv, prim = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between forward and backward")
-        n = o.shape[1]
-        g = g.contiguous().to(torch.float32)
-        need_h, need_o, need_d = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        need_tw = ctx.needs_input_grad[11]
-        grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=o.device) if need_h else None
-        grad_od = torch.empty((6, n), dtype=torch.float32, device=o.device) if (need_o or need_d) else None
-        grad_tw = torch.zeros(12, dtype=torch.float32, device=o.device) if need_tw else None
-        shape._adjoint_raw(o, d, maxt, t, uv, prim, ctx.flags, ctx.active, g, grad_h, grad_od, grad_tw=grad_tw)
+        shape, saved = _op_saved(ctx, "backward")
+        n = saved[0].shape[1]
+        need_o, need_d = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        grad_h, grad_tw = _op_grads(ctx, 1, 11)
+        grad_od = torch.empty((6, n), dtype=torch.float32, device=shape.device) if (need_o or need_d) else None
+        shape._adjoint_raw(*saved, ctx.flags, ctx.active, g.contiguous().to(torch.float32), grad_h, grad_od,
+                           grad_tw=grad_tw)
         go = grad_od[0:3] if need_o else None
         gd = grad_od[3:6] if need_d else None
-        return (None, grad_h, go, gd, None, None, None, None, None, None, None,
-                _tw_grad(grad_tw, ctx.tw_like) if need_tw else None)
+        return None, grad_h, go, gd, None, None, None, None, None, None, None, _tw_grad(grad_tw, ctx.tw_like)
 
 
 class _ParameterizationOp(torch.autograd.Function):
@@ -325,54 +419,22 @@ class _ParameterizationOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, shape, heights, uv, flags, active, diff_block, to_world=None):
-        ctx.shape, ctx.flags, ctx.active = shape, flags, active
-        ctx.save_for_backward(uv)
-        ctx.save_for_forward(uv)
-        ctx.h_version = shape._param_version()
-        ctx.tw_like = _tw_like(to_world)
+        _op_save(ctx, shape, (uv,), to_world)
+        ctx.flags, ctx.active = flags, active
         return diff_block
 
     @staticmethod
     def jvp(ctx, _shape, dh, _uv, _flags, _active, _diff, dtw=None):
-        shape = ctx.shape
-        uv, = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between the primal and the tangent pass")
-        return shape._param_tangent_raw(uv, ctx.flags, ctx.active, dh, _tw_tangent(dtw))
+        shape, (uv,) = _op_saved(ctx, "jvp")
+        return shape._param_tangent_raw(uv, ctx.flags, ctx.active, dh, dtw)
 
     @staticmethod
     def backward(ctx, g):
-        shape = ctx.shape
-        uv, = ctx.saved_tensors
-        if ctx.h_version != shape._param_version():
-            raise RuntimeError("heightfield parameters changed between forward and backward")
-        need_h, need_tw = ctx.needs_input_grad[1], ctx.needs_input_grad[6]
-        grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=uv.device) if need_h else None
-        grad_tw = torch.zeros(12, dtype=torch.float32, device=uv.device) if need_tw else None
-        if need_h or need_tw:
+        shape, (uv,) = _op_saved(ctx, "backward")
+        grad_h, grad_tw = _op_grads(ctx, 1, 6)
+        if grad_h is not None or grad_tw is not None:
             shape._param_adjoint_raw(uv, ctx.flags, ctx.active, g.contiguous().to(torch.float32), grad_h, grad_tw)
-        return None, grad_h, None, None, None, None, (_tw_grad(grad_tw, ctx.tw_like) if need_tw else None)
-
-
-def _tw_like(to_world):
-    """(shape, dtype, device) of a to_world input, None without one"""
-    return None if to_world is None else (tuple(to_world.shape), to_world.dtype, to_world.device)
-
-
-def _tw_grad(grad12, like):
-    """the 12 floats of dL/d(to_world) as a gradient of the user's 3x4 / 4x4 tensor (a 4x4's last row gets zeros)"""
-    shape, dtype, device = like
-    g = grad12.reshape(3, 4)
-    if shape[0] == 4:
-        g = torch.cat([g, torch.zeros((1, 4), dtype=g.dtype, device=g.device)])
-    return g.reshape(shape).to(device=device, dtype=dtype)
-
-
-def _tw_tangent(dtw):
-    """a 3x4 / 4x4 tangent of to_world as the 12 contiguous float32 device values of the C ABI (None: zero)"""
-    if dtw is None:
-        return None
-    return dtw.detach().reshape(-1)[:12].to(torch.float32).contiguous()
+        return None, grad_h, None, None, None, None, _tw_grad(grad_tw, ctx.tw_like)
 
 
 class Heightfield:
@@ -485,8 +547,7 @@ class Heightfield:
                 # bitmap.cpp:272-286: resolution may not change / must stay >= 2
                 raise RuntimeError(f"heightfield: tensor shape {tuple(h.shape)} != ({self.height}, {self.width})")
             hd = h.detach().to(device=self.device, dtype=torch.float32).contiguous()
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            check(_capi.lib().hf_set_heights(self._h, hd.data_ptr(), stream))
+            check(_capi.lib().hf_set_heights(self._h, hd.data_ptr(), self._stream()))
             self._heights_keepalive = hd
             self._heights_version += 1
         if not keys or "to_world" in keys:
@@ -513,6 +574,23 @@ class Heightfield:
             return tw
         return None
 
+    def _wants_derivative(self, *tensors, detach=False):
+        """a derivative is wanted with respect to one of `tensors`, the heights or to_world: a forward-mode tangent
+        (torch.autograd.forward_ad, whatever the grad mode) or requires_grad with grad mode on.  detach
+        (RayFlags.DetachShape): the heights and to_world do not count, `tensors` (the rays) still do."""
+        live = tensors if detach else (*tensors, self.heightfield)
+        if any(_has_tangent(x) or (torch.is_grad_enabled() and x.requires_grad) for x in live):
+            return True
+        return self._to_world_live(detach) is not None
+
+    def _zero_heights(self):
+        """a zeroed dL/dheight accumulator [H, W]"""
+        return torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+
+    def _dheights(self, dh, exc=AssertionError):
+        """a tangent of the heights for the C ABI: one float32 per height (None: zero)"""
+        return _tangent(dh, (self.height, self.width), self.device, "dheights", exc)
+
     def set_face_normals(self, face_normals):
         """Flat (True) or smooth (False) shading.  Smooth: angle-weighted vertex normals, rebuilt with every
         parameters_changed, interpolated into sh_frame.n and differentiated through (hf_set_face_normals)."""
@@ -526,11 +604,9 @@ class Heightfield:
         n = pi.t.shape[0]
         keep, _ = self._mask(active, n)
         out = torch.empty((6, n), dtype=torch.float32, device=self.device)
-        _, pu = _f3(out[0:3])
-        _, pv = _f3(out[3:6])
         pis = self._pi_struct(pi.t.detach().contiguous(), pi.prim_uv.detach().contiguous(), pi.prim_index.contiguous())
-        check(_capi.lib().hf_shading_derivatives(self._h, n, C.byref(pis), keep.data_ptr() if keep is not None else None,
-                                                 C.byref(pu), C.byref(pv), self._stream()))
+        check(_capi.lib().hf_shading_derivatives(self._h, n, C.byref(pis), _ptr(keep), C.byref(_p3(out[0:3])),
+                                                 C.byref(_p3(out[3:6])), self._stream()))
         return out[0:3], out[3:6]
 
     # ---- area sampling (Mesh::build_pmf / sample_position / pdf_position, mesh.cpp:401-432, 552-642) ----------------
@@ -572,19 +648,11 @@ class Heightfield:
         block = torch.empty((6, n), dtype=torch.float32, device=self.device)   # p, n
         rest = torch.empty((5, n), dtype=torch.float32, device=self.device)    # uv, pdf, b
         prim = torch.empty(n, dtype=torch.int32, device=self.device)
-        out = hf_position_sample_t()
-        rows, more = _rows(block, n), _rows(rest, n)
-        for k in range(3):
-            out.p[k], out.n[k] = rows[k], rows[3 + k]
-        out.uv[0], out.uv[1], out.pdf = more[0], more[1], more[2]
-        out.prim_index = prim.data_ptr()
-        out.b[0], out.b[1] = more[3], more[4]
-        sp = (C.c_void_p * 2)(*_rows(sample, n))
-        check(_capi.lib().hf_sample_position(self._h, n, C.byref(sp), ap, C.byref(out), self._stream()))
-        h = self.heightfield
-        tw = self._to_world_live()
-        if (torch.is_grad_enabled() and h.requires_grad) or _has_tangent(h) or tw is not None:
-            block = _SamplePositionOp.apply(self, h, prim, rest[3:5], keep, block, tw)
+        more = _row_addrs(rest)
+        out = _fill(hf_position_sample_t(), _SAMPLE_ROWS, _row_addrs(block) + more[0:3] + [prim.data_ptr()] + more[3:5])
+        check(_capi.lib().hf_sample_position(self._h, n, C.byref(_row_ptrs(sample)), ap, C.byref(out), self._stream()))
+        if self._wants_derivative():
+            block = _SamplePositionOp.apply(self, self.heightfield, prim, rest[3:5], keep, block, self._to_world_live())
         ps = PositionSample3f(block[0:3], block[3:6], rest[0:2], time, rest[2], False)
         ps.prim_index, ps.b = prim, rest[3:5]
         return ps
@@ -617,41 +685,20 @@ class Heightfield:
         return pdf * torch.where(dp != 0, (ds.dist * ds.dist) / dp, torch.zeros_like(dp))
 
     def _sample_adjoint_raw(self, prim, b, active_u8, g, grad_h, grad_tw=None):
-        n = prim.shape[0]
-        rows = _rows(g, n)
-        gp, gn = (C.c_void_p * 3)(*rows[0:3]), (C.c_void_p * 3)(*rows[3:6])
-        bp = (C.c_void_p * 2)(*_rows(b.contiguous(), n))
-        ap = active_u8.data_ptr() if active_u8 is not None else None
-        if grad_tw is not None:
-            assert grad_tw.numel() == 12 and grad_tw.dtype == torch.float32 and grad_tw.is_contiguous()
-            check(_capi.lib().hf_sample_position_adjoint_transform(
-                self._h, n, prim.data_ptr(), C.byref(bp), ap, C.byref(gp), C.byref(gn),
-                grad_h.data_ptr() if grad_h is not None else None, grad_tw.data_ptr(), self._stream()))
-            return
-        check(_capi.lib().hf_sample_position_adjoint(self._h, n, prim.data_ptr(), C.byref(bp), ap,
-                                                     C.byref(gp), C.byref(gn), grad_h.data_ptr(), self._stream()))
+        b = b.contiguous()
+        check(_capi.lib().hf_sample_position_adjoint_transform(
+            self._h, prim.shape[0], prim.data_ptr(), C.byref(_row_ptrs(b)), _ptr(active_u8), C.byref(_p3(g[0:3])),
+            C.byref(_p3(g[3:6])), _ptr(grad_h), _ptr(_grad12(grad_tw)), self._stream()))
 
     def _sample_tangent_raw(self, prim, b, active_u8, dh, dtw=None):
         n = prim.shape[0]
         out = torch.zeros((6, n), dtype=torch.float32, device=self.device)
         if dh is None and dtw is None:
             return out
-        if dh is not None:
-            dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
-            assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
-        rows = _rows(out, n)
-        dp, dn = (C.c_void_p * 3)(*rows[0:3]), (C.c_void_p * 3)(*rows[3:6])
-        bp = (C.c_void_p * 2)(*_rows(b.contiguous(), n))
-        ap = active_u8.data_ptr() if active_u8 is not None else None
-        dhp = dh.data_ptr() if dh is not None else None
-        if dtw is not None:
-            dtw = _tw_tangent(torch.as_tensor(dtw, device=self.device)).to(self.device)
-            check(_capi.lib().hf_sample_position_tangent_transform(self._h, n, prim.data_ptr(), C.byref(bp), ap, dhp,
-                                                                   dtw.data_ptr(), C.byref(dp), C.byref(dn),
-                                                                   self._stream()))
-            return out
-        check(_capi.lib().hf_sample_position_tangent(self._h, n, prim.data_ptr(), C.byref(bp), ap, dhp,
-                                                     C.byref(dp), C.byref(dn), self._stream()))
+        dh, dtw, b = self._dheights(dh), _tw_tangent(dtw, self.device), b.contiguous()
+        check(_capi.lib().hf_sample_position_tangent_transform(
+            self._h, n, prim.data_ptr(), C.byref(_row_ptrs(b)), _ptr(active_u8), _ptr(dh), _ptr(dtw),
+            C.byref(_p3(out[0:3])), C.byref(_p3(out[3:6])), self._stream()))
         return out
 
     def sample_position_adjoint(self, ps, grad_p=None, grad_n=None, active=True, grad_heightfield=None,
@@ -662,7 +709,7 @@ class Heightfield:
         (hf_sample_position_adjoint_transform)."""
         n = ps.prim_index.shape[0]
         if grad_heightfield is None:
-            grad_heightfield = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+            grad_heightfield = self._zero_heights()
         z = torch.zeros((3, n), dtype=torch.float32, device=self.device)
         g = torch.cat([z if grad_p is None else _as_f32(grad_p, self.device).reshape(3, n),
                        z if grad_n is None else _as_f32(grad_n, self.device).reshape(3, n)]).contiguous()
@@ -689,52 +736,35 @@ class Heightfield:
             raise _capi.HfError(_capi.HF_EFLAGS, "Invalid combination of RayFlags: DetachShape | FollowShape")
         uv = _as_f32(uv.detach() if isinstance(uv, torch.Tensor) else uv, self.device).reshape(2, -1)
         n = uv.shape[1]
-        diff = torch.empty((18, n), dtype=torch.float32, device=self.device)
-        aux = torch.empty((10, n), dtype=torch.float32, device=self.device)
+        diff, aux, out = self._si_blocks(n)
         prim = torch.empty(n, dtype=torch.int32, device=self.device)
         keep, ap = self._mask(active, n)
-        out = _fill(_fill(hf_si_t(), _DIFF_ROWS, _rows(diff, n)), _AUX_ROWS, _rows(aux, n))
-        uvp = (C.c_void_p * 2)(*_rows(uv, n))
-        check(_capi.lib().hf_eval_parameterization(self._h, n, C.byref(uvp), ray_flags, ap, C.byref(out), prim.data_ptr(),
-                                                   self._stream()))
+        check(_capi.lib().hf_eval_parameterization(self._h, n, C.byref(_row_ptrs(uv)), ray_flags, ap, C.byref(out),
+                                                   prim.data_ptr(), self._stream()))
         detach = bool(ray_flags & RayFlags.DetachShape)
-        h = self.heightfield
-        tw = self._to_world_live(detach)
-        h_live = not detach and ((torch.is_grad_enabled() and h.requires_grad) or _has_tangent(h))
-        if h_live or tw is not None:
-            diff = _ParameterizationOp.apply(self, h, uv, ray_flags, keep, diff, tw)
+        if self._wants_derivative(detach=detach):
+            diff = _ParameterizationOp.apply(self, self.heightfield, uv, ray_flags, keep, diff, self._to_world_live(detach))
         o = torch.stack([uv[0], uv[1], torch.full_like(uv[0], -1.0)])
         d = torch.zeros((3, n), dtype=torch.float32, device=self.device)
         d[2] = 1.0
         ray = Ray3f(o, d, torch.ones(n, dtype=torch.float32, device=self.device))
-        return self._package_si(ray, diff[0], prim, diff, aux, ray_flags)
+        return self._package_si(ray, prim, diff, aux, ray_flags)
 
     def _param_adjoint_raw(self, uv, ray_flags, active_u8, g, grad_h, grad_tw=None):
-        n = uv.shape[1]
-        gs = _fill(hf_si_grad_t(), _DIFF_ROWS, _rows(g, n))
-        uvp = (C.c_void_p * 2)(*_rows(uv, n))
-        if grad_tw is not None:
-            assert grad_tw.numel() == 12 and grad_tw.dtype == torch.float32 and grad_tw.is_contiguous()
+        gs = _fill(hf_si_grad_t(), _DIFF_ROWS, _row_addrs(g))
         check(_capi.lib().hf_eval_parameterization_adjoint(
-            self._h, n, C.byref(uvp), int(ray_flags), active_u8.data_ptr() if active_u8 is not None else None, C.byref(gs),
-            grad_h.data_ptr() if grad_h is not None else None, grad_tw.data_ptr() if grad_tw is not None else None,
-            self._stream()))
+            self._h, uv.shape[1], C.byref(_row_ptrs(uv)), int(ray_flags), _ptr(active_u8), C.byref(gs), _ptr(grad_h),
+            _ptr(_grad12(grad_tw)), self._stream()))
 
     def _param_tangent_raw(self, uv, ray_flags, active_u8, dh, dtw=None):
         n = uv.shape[1]
         out = torch.zeros((18, n), dtype=torch.float32, device=self.device)
         if dh is None and dtw is None:
             return out
-        if dh is not None:
-            dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
-            assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
-        if dtw is not None:
-            dtw = _tw_tangent(torch.as_tensor(dtw, device=self.device)).to(self.device)
-        ts = _fill(hf_si_tangent_t(), _DIFF_ROWS, _rows(out, n))
-        uvp = (C.c_void_p * 2)(*_rows(uv, n))
+        dh, dtw = self._dheights(dh), _tw_tangent(dtw, self.device)
+        ts = _fill(hf_si_tangent_t(), _DIFF_ROWS, _row_addrs(out))
         check(_capi.lib().hf_eval_parameterization_tangent(
-            self._h, n, C.byref(uvp), int(ray_flags), active_u8.data_ptr() if active_u8 is not None else None,
-            dh.data_ptr() if dh is not None else None, dtw.data_ptr() if dtw is not None else None, C.byref(ts),
+            self._h, n, C.byref(_row_ptrs(uv)), int(ray_flags), _ptr(active_u8), _ptr(dh), _ptr(dtw), C.byref(ts),
             self._stream()))
         return out
 
@@ -748,7 +778,7 @@ class Heightfield:
         g = _as_f32(grad_si, self.device)
         assert g.shape == (18, n)
         if grad_heightfield is None:
-            grad_heightfield = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+            grad_heightfield = self._zero_heights()
         keep, _ = self._mask(active, n)
         self._param_adjoint_raw(uv, ray_flags, keep, g, grad_heightfield, grad_to_world)
         return grad_heightfield
@@ -818,41 +848,35 @@ class Heightfield:
             # the kernels gather count * size floats: a buffer assigned behind parameters_changed's back is refused
             raise RuntimeError(f"attribute {name}: expected a contiguous float32 buffer of {self._attr_count(type_)} x "
                                f"{size} values, got {tuple(attr.shape)} {attr.dtype}")
-        pp = None
-        if type_ == _capi.HF_ATTR_VERTEX:
-            assert p.is_contiguous() and p.dtype == torch.float32
-            pp = (C.c_void_p * 3)(*_rows(p, p.shape[1]))
-        return (type_, size, prim.data_ptr(), C.byref(pp) if pp is not None else None,
-                t.data_ptr() if t is not None else None, active_u8.data_ptr() if active_u8 is not None else None)
+        vertex = type_ == _capi.HF_ATTR_VERTEX
+        assert not vertex or (p.is_contiguous() and p.dtype == torch.float32)
+        return type_, size, prim.data_ptr(), _ref(_p3(p) if vertex else None), _ptr(t), _ptr(active_u8)
 
     def _eval_attr(self, name, si, active):
-        type_ = self._attr_meta[name][0]
+        vertex = self._attr_meta[name][0] == _capi.HF_ATTR_VERTEX
         n = si.prim_index.shape[0]
         keep, _ = self._mask(active, n)
         prim = si.prim_index.contiguous()
         t = si.t.detach().contiguous() if si.t is not None else None
-        p = si.p.detach().to(torch.float32).contiguous() if type_ == _capi.HF_ATTR_VERTEX else None
+        p = si.p.detach().to(torch.float32).contiguous() if vertex else None
         buf = self.attributes[name]
         value = self._attr_forward_raw(name, buf.detach(), p, prim, t, keep)
-        h = self.heightfield
-        if type_ == _capi.HF_ATTR_VERTEX and self._to_world_live() is not None:
+        if vertex and self._to_world_live() is not None:
             raise NotImplementedError(
                 f"eval_attribute({name!r}): the derivative of a vertex attribute with respect to to_world is not "
                 "implemented; evaluate it under torch.no_grad() or with a to_world that does not require a gradient")
-        live = [buf] + ([si.p, h] if type_ == _capi.HF_ATTR_VERTEX else [])
-        if any(_has_tangent(x) for x in live) or (torch.is_grad_enabled() and any(x.requires_grad for x in live)):
-            vertex = type_ == _capi.HF_ATTR_VERTEX
-            value = _AttributeOp.apply(self, name, buf, si.p if vertex else None, h if vertex else None, prim, t, keep,
-                                       value)
+        # a face attribute depends on its buffer alone; a vertex attribute on si.p and the heights as well
+        if self._wants_derivative(buf, si.p) if vertex else self._wants_derivative(buf, detach=True):
+            value = _AttributeOp.apply(self, name, buf, si.p if vertex else None, self.heightfield if vertex else None,
+                                       prim, t, keep, value)
         return value
 
     def _attr_forward_raw(self, name, attr, p, prim, t, active_u8):
         n = prim.shape[0]
         type_, size, pr, pp, tp, ap = self._attr_inputs(name, attr, p, prim, t, active_u8)
         out = torch.empty((size, n), dtype=torch.float32, device=self.device)
-        orow = (C.c_void_p * 3)(*(_rows(out, n) + [None] * (3 - size)))
-        check(_capi.lib().hf_eval_attribute(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap, C.byref(orow),
-                                            self._stream()))
+        check(_capi.lib().hf_eval_attribute(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap,
+                                            C.byref(_row_ptrs(out, 3)), self._stream()))
         return out
 
     def _attr_adjoint_raw(self, name, attr, p, prim, t, active_u8, g, need_attr=True, need_p=True, need_h=True,
@@ -865,39 +889,22 @@ class Heightfield:
         if need_attr and grad_attr is None:
             grad_attr = torch.zeros(attr.numel(), dtype=torch.float32, device=self.device)
         if need_h and grad_h is None:
-            grad_h = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+            grad_h = self._zero_heights()
         gp = torch.empty((3, n), dtype=torch.float32, device=self.device) if need_p else None
-        grow = (C.c_void_p * 3)(*(_rows(g, n) + [None] * (3 - size)))
-        gprow = (C.c_void_p * 3)(*_rows(gp, n)) if need_p else None
         check(_capi.lib().hf_eval_attribute_adjoint(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap,
-                                                    C.byref(grow), grad_attr.data_ptr() if need_attr else None,
-                                                    C.byref(gprow) if need_p else None,
-                                                    grad_h.data_ptr() if need_h else None, self._stream()))
+                                                    C.byref(_row_ptrs(g, 3)), _ptr(grad_attr if need_attr else None),
+                                                    _ref(_row_ptrs(gp)), _ptr(grad_h if need_h else None),
+                                                    self._stream()))
         return (grad_attr if need_attr else None), gp, (grad_h if need_h else None)
 
     def _attr_tangent_raw(self, name, attr, p, prim, t, active_u8, dattr=None, dp=None, dh=None):
         n = prim.shape[0]
         type_, size, pr, pp, tp, ap = self._attr_inputs(name, attr, p, prim, t, active_u8)
         out = torch.empty((size, n), dtype=torch.float32, device=self.device)
-        keep = []
-
-        def flat(x, numel):
-            if x is None:
-                return None
-            x = torch.as_tensor(x, device=self.device).detach().to(torch.float32).reshape(-1).contiguous()
-            assert x.numel() == numel
-            keep.append(x)
-            return x.data_ptr()
-        da = flat(dattr, attr.numel())
-        dhp = flat(dh, self.width * self.height)
-        dpr = None
-        if dp is not None and type_ == _capi.HF_ATTR_VERTEX:
-            dpt = torch.as_tensor(dp, device=self.device).detach().to(torch.float32).reshape(3, n).contiguous()
-            keep.append(dpt)
-            dpr = (C.c_void_p * 3)(*_rows(dpt, n))
-        orow = (C.c_void_p * 3)(*(_rows(out, n) + [None] * (3 - size)))
-        check(_capi.lib().hf_eval_attribute_tangent(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap, da,
-                                                    C.byref(dpr) if dpr is not None else None, dhp, C.byref(orow),
+        dattr, dh = _tangent(dattr, (attr.numel(),), self.device, "dattr"), self._dheights(dh)
+        dp = _tangent(dp, (3, n), self.device, "dp") if type_ == _capi.HF_ATTR_VERTEX else None
+        check(_capi.lib().hf_eval_attribute_tangent(self._h, n, type_, size, attr.data_ptr(), pr, pp, tp, ap, _ptr(dattr),
+                                                    _ref(_row_ptrs(dp)), _ptr(dh), C.byref(_row_ptrs(out, 3)),
                                                     self._stream()))
         return out
 
@@ -962,7 +969,7 @@ class Heightfield:
 
     # ---- helpers -------------------------------------------------------------------------
     def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return _stream_of(self.device)
 
     def _check_ray(self, ray):
         if not isinstance(ray, Ray3f):
@@ -972,13 +979,7 @@ class Heightfield:
 
     @staticmethod
     def _rays_struct(o, d, maxt):
-        n = o.shape[1]
-        r = hf_rays_t()
-        for k in range(3):
-            r.o[k] = o.data_ptr() + 4 * n * k
-            r.d[k] = d.data_ptr() + 4 * n * k
-        r.maxt = maxt.data_ptr()
-        return r
+        return _fill(hf_rays_t(), _RAY_ROWS, _row_addrs(o)[:3] + _row_addrs(d)[:3] + [maxt.data_ptr()])
 
     def _mask(self, active, n):
         if active is True or active is None:
@@ -993,13 +994,7 @@ class Heightfield:
 
     @staticmethod
     def _pi_struct(t, uv, prim):
-        n = t.shape[0]
-        p = hf_pi_t()
-        p.t = t.data_ptr()
-        p.prim_uv[0] = uv.data_ptr()
-        p.prim_uv[1] = uv.data_ptr() + 4 * n
-        p.prim_index = prim.data_ptr()
-        return p
+        return _fill(hf_pi_t(), _PI_ROWS, [t.data_ptr()] + _row_addrs(uv)[:2] + [prim.data_ptr()])
 
     # ---- the hot path ---------------------------------------------------------------------
     # ---- the `coherent` hint of Scene::ray_intersect / ray_test / ray_intersect_preliminary (scene.h:117-146) ----------
@@ -1064,11 +1059,9 @@ class Heightfield:
         import numpy as np
         o, d, maxt, act, n = self._host_packet(o, d, maxt, active)
         t = np.empty(n, np.float32); uv = np.empty((2, n), np.float32); prim = np.empty(n, np.uint32)
-        op, dp = self._host_rows(o), self._host_rows(d)
-        uvp = (C.c_void_p * 2)(uv[0].ctypes.data, uv[1].ctypes.data)
-        check(_capi.lib().hf_ray_intersect_preliminary_packet(self._h, n, C.byref(op), C.byref(dp), maxt.ctypes.data,
-                                                              act.ctypes.data if act is not None else None,
-                                                              t.ctypes.data, C.byref(uvp), prim.ctypes.data))
+        check(_capi.lib().hf_ray_intersect_preliminary_packet(self._h, n, C.byref(_row_ptrs(o)), C.byref(_row_ptrs(d)),
+                                                              _ptr(maxt), _ptr(act), _ptr(t), C.byref(_row_ptrs(uv)),
+                                                              _ptr(prim)))
         return t, uv, prim
 
     def ray_intersect_preliminary_scalar(self, o, d, maxt=math.inf):
@@ -1079,17 +1072,12 @@ class Heightfield:
         import numpy as np
         o, d, maxt, act, n = self._host_packet(o, d, maxt, active)
         hit = np.empty(n, np.uint8)
-        op, dp = self._host_rows(o), self._host_rows(d)
-        check(_capi.lib().hf_ray_test_packet(self._h, n, C.byref(op), C.byref(dp), maxt.ctypes.data,
-                                             act.ctypes.data if act is not None else None, hit.ctypes.data))
+        check(_capi.lib().hf_ray_test_packet(self._h, n, C.byref(_row_ptrs(o)), C.byref(_row_ptrs(d)), _ptr(maxt),
+                                             _ptr(act), _ptr(hit)))
         return hit.astype(bool)
 
     def ray_test_scalar(self, o, d, maxt=math.inf):
         return bool(self.ray_test_packet(o, d, maxt)[0])
-
-    @staticmethod
-    def _host_rows(a):
-        return (C.c_void_p * 3)(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data)
 
     @staticmethod
     def _host_packet(o, d, maxt, active):
@@ -1103,7 +1091,23 @@ class Heightfield:
         act = None if active is None else np.ascontiguousarray(np.broadcast_to(np.asarray(active).astype(np.uint8).reshape(-1), (n,)))
         return o, d, maxt, act, n
 
-    def _package_si(self, ray, pi_t, pi_prim, diff, aux, ray_flags):
+    def _si_blocks(self, n):
+        """the two blocks of an SI record, [18, n] (_DIFF_ROWS: what autograd sees) and [10, n] (_AUX_ROWS), and the
+        hf_si_t over their rows"""
+        diff = torch.empty((18, n), dtype=torch.float32, device=self.device)
+        aux = torch.empty((10, n), dtype=torch.float32, device=self.device)
+        return diff, aux, _fill(hf_si_t(), _DIFF_ROWS + _AUX_ROWS, _row_addrs(diff) + _row_addrs(aux))
+
+    def _attach_si(self, ray, t, uv, prim, ray_flags, keep, diff):
+        """the differentiable block as the output of _SurfaceInteractionOp when a derivative is wanted.  DetachShape:
+        the heights and to_world are detached, the rays are not."""
+        detach = bool(ray_flags & RayFlags.DetachShape)
+        if self._wants_derivative(ray.o, ray.d, detach=detach):
+            diff = _SurfaceInteractionOp.apply(self, self.heightfield, ray.o, ray.d, ray.maxt, t, uv, prim, ray_flags, keep,
+                                               diff, self._to_world_live(detach))
+        return diff
+
+    def _package_si(self, ray, pi_prim, diff, aux, ray_flags):
         n = len(ray)
         si = SurfaceInteraction3f()
         si.t = diff[0]
@@ -1136,39 +1140,22 @@ class Heightfield:
         si.time, si.wavelengths = ray.time, ray.wavelengths
         return si
 
-    def _wants_grad(self, ray, ray_flags):
-        detach = bool(ray_flags & RayFlags.DetachShape)
-        # forward mode (torch.autograd.forward_ad): a tangent on the heights or the rays, whatever the grad mode
-        if (_has_tangent(self.heightfield) and not detach) or _has_tangent(ray.o) or _has_tangent(ray.d):
-            return True
-        if self._to_world_live(detach) is not None:
-            return True
-        if not torch.is_grad_enabled():
-            return False
-        h_live = self.heightfield.requires_grad and not detach
-        return bool(h_live or ray.o.requires_grad or ray.d.requires_grad)
-
     def compute_surface_interaction(self, ray, pi, ray_flags=RayFlags.All, recursion_depth=0, active=True):
         """shape.h:179-183 + finalize_surface_interaction (interaction.h:476-499)"""
         self._check_ray(ray)
         ray_flags = int(ray_flags)
         n = len(ray)
-        diff = torch.empty((18, n), dtype=torch.float32, device=self.device)
-        aux = torch.empty((10, n), dtype=torch.float32, device=self.device)
+        diff, aux, out = self._si_blocks(n)
         if recursion_depth > 0:   # mesh.cpp:680-682: early exit, zero-initialised record
             diff.zero_(); aux.zero_()
-            return self._package_si(ray, pi.t, pi.prim_index, diff, aux, ray_flags)
+            return self._package_si(ray, pi.prim_index, diff, aux, ray_flags)
         keep, ap = self._mask(active, n)
-        out = _fill(_fill(hf_si_t(), _DIFF_ROWS, _rows(diff, n)), _AUX_ROWS, _rows(aux, n))
         rays = self._rays_struct(ray.o, ray.d, ray.maxt)
         pis = self._pi_struct(pi.t, pi.prim_uv, pi.prim_index)
         check(_capi.lib().hf_compute_surface_interaction(self._h, n, C.byref(rays), C.byref(pis), ray_flags, ap,
                                                          C.byref(out), self._stream()))
-        if self._wants_grad(ray, ray_flags):
-            diff = _SurfaceInteractionOp.apply(self, self.heightfield, ray.o, ray.d, ray.maxt, pi.t, pi.prim_uv,
-                                               pi.prim_index, ray_flags, keep, diff,
-                                               self._to_world_live(bool(ray_flags & RayFlags.DetachShape)))
-        return self._package_si(ray, pi.t, pi.prim_index, diff, aux, ray_flags)
+        diff = self._attach_si(ray, pi.t, pi.prim_uv, pi.prim_index, ray_flags, keep, diff)
+        return self._package_si(ray, pi.prim_index, diff, aux, ray_flags)
 
     def ray_intersect(self, ray, ray_flags=RayFlags.All, active=True, coherent=None):
         """shape.cpp:436-446: preliminary intersection + surface interaction, one fused kernel; ``coherent``: scene.h:117-146"""
@@ -1178,83 +1165,41 @@ class Heightfield:
         t = torch.empty(n, dtype=torch.float32, device=self.device)
         uv = torch.empty((2, n), dtype=torch.float32, device=self.device)
         prim = torch.empty(n, dtype=torch.int32, device=self.device)
-        diff = torch.empty((18, n), dtype=torch.float32, device=self.device)
-        aux = torch.empty((10, n), dtype=torch.float32, device=self.device)
+        diff, aux, out = self._si_blocks(n)
         keep, ap = self._mask(active, n)
-        out = _fill(_fill(hf_si_t(), _DIFF_ROWS, _rows(diff, n)), _AUX_ROWS, _rows(aux, n))
         rays = self._rays_struct(ray.o, ray.d, ray.maxt)
         pis = self._pi_struct(t, uv, prim)
         with self._coherent(coherent):
             check(_capi.lib().hf_ray_intersect(self._h, n, C.byref(rays), ray_flags, ap, C.byref(pis), C.byref(out),
                                                self._stream()))
-        if self._wants_grad(ray, ray_flags):
-            diff = _SurfaceInteractionOp.apply(self, self.heightfield, ray.o, ray.d, ray.maxt, t, uv, prim,
-                                               ray_flags, keep, diff,
-                                               self._to_world_live(bool(ray_flags & RayFlags.DetachShape)))
-        si = self._package_si(ray, t, prim, diff, aux, ray_flags)
+        diff = self._attach_si(ray, t, uv, prim, ray_flags, keep, diff)
+        si = self._package_si(ray, prim, diff, aux, ray_flags)
         si.prim_uv = uv
         return si
 
     # ---- adjoint ------------------------------------------------------------------------------
     def _adjoint_raw(self, o, d, maxt, t, uv, prim, ray_flags, active_u8, g, grad_h, grad_od, row_band=None, grad_tw=None):
-        n = o.shape[1]
         rays = self._rays_struct(o, d, maxt)
         pis = self._pi_struct(t, uv, prim)
-        gs = _fill(hf_si_grad_t(), _DIFF_ROWS, _rows(g, n))
-        go = gd = None
-        if grad_od is not None:
-            rows = _rows(grad_od, n)
-            go = (C.c_void_p * 3)(*rows[0:3])
-            gd = (C.c_void_p * 3)(*rows[3:6])
-        if grad_tw is not None:
-            assert grad_tw.numel() == 12 and grad_tw.dtype == torch.float32 and grad_tw.is_contiguous()
-            check(_capi.lib().hf_adjoint_transform(
-                self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
-                active_u8.data_ptr() if active_u8 is not None else None, C.byref(gs),
-                grad_h.data_ptr() if grad_h is not None else None, C.byref(go) if go is not None else None,
-                C.byref(gd) if gd is not None else None, row_band.data_ptr() if row_band is not None else None,
-                grad_tw.data_ptr(), self._stream()))
-            return
-        check(_capi.lib().hf_adjoint_rows(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
-                                          active_u8.data_ptr() if active_u8 is not None else None, C.byref(gs),
-                                          grad_h.data_ptr() if grad_h is not None else None,
-                                          C.byref(go) if go is not None else None,
-                                          C.byref(gd) if gd is not None else None,
-                                          row_band.data_ptr() if row_band is not None else None, self._stream()))
+        gs = _fill(hf_si_grad_t(), _DIFF_ROWS, _row_addrs(g))
+        go, gd = (None, None) if grad_od is None else (_p3(grad_od[0:3]), _p3(grad_od[3:6]))
+        # (without grad_tw this is hf_adjoint_rows: the entry forwards to it)
+        check(_capi.lib().hf_adjoint_transform(self._h, o.shape[1], C.byref(rays), C.byref(pis), int(ray_flags),
+                                               _ptr(active_u8), C.byref(gs), _ptr(grad_h), _ref(go), _ref(gd),
+                                               _ptr(row_band), _ptr(_grad12(grad_tw)), self._stream()))
 
     # ---- tangent (forward mode) ------------------------------------------------------------------
     def _tangent_raw(self, o, d, maxt, t, uv, prim, ray_flags, active_u8, dh, do, dd, dtw=None):
         n = o.shape[1]
         out = torch.empty((18, n), dtype=torch.float32, device=self.device)
-        ts = _fill(hf_si_tangent_t(), _DIFF_ROWS, _rows(out, n))
-        keep = []
-
-        def rows3(x):
-            if x is None:
-                return None
-            x, p = _f3(torch.as_tensor(x, device=self.device).detach().reshape(3, n))
-            keep.append(x)
-            return p
-        if dh is not None:
-            dh = torch.as_tensor(dh, device=self.device).detach().to(torch.float32).contiguous()
-            assert dh.numel() == self.width * self.height, "dheights: one tangent per height"
-        op, dp = rows3(do), rows3(dd)
+        ts = _fill(hf_si_tangent_t(), _DIFF_ROWS, _row_addrs(out))
+        dh, dtw = self._dheights(dh), _tw_tangent(dtw, self.device)
+        do, dd = _tangent(do, (3, n), self.device, "d_o"), _tangent(dd, (3, n), self.device, "d_d")
         rays = self._rays_struct(o, d, maxt)
         pis = self._pi_struct(t, uv, prim)
-        if dtw is not None:
-            dtw = _tw_tangent(torch.as_tensor(dtw, device=self.device)).to(self.device)
-            check(_capi.lib().hf_tangent_transform(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
-                                                   active_u8.data_ptr() if active_u8 is not None else None,
-                                                   dh.data_ptr() if dh is not None else None,
-                                                   C.byref(op) if op is not None else None,
-                                                   C.byref(dp) if dp is not None else None, dtw.data_ptr(),
-                                                   C.byref(ts), self._stream()))
-            return out
-        check(_capi.lib().hf_tangent(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags),
-                                     active_u8.data_ptr() if active_u8 is not None else None,
-                                     dh.data_ptr() if dh is not None else None,
-                                     C.byref(op) if op is not None else None, C.byref(dp) if dp is not None else None,
-                                     C.byref(ts), self._stream()))
+        check(_capi.lib().hf_tangent_transform(self._h, n, C.byref(rays), C.byref(pis), int(ray_flags), _ptr(active_u8),
+                                               _ptr(dh), _ref(_row_ptrs(do)), _ref(_row_ptrs(dd)), _ptr(dtw), C.byref(ts),
+                                               self._stream()))
         return out
 
     def tangent(self, ray, pi, dheights=None, d_o=None, d_d=None, ray_flags=RayFlags.All, active=True, d_to_world=None):
@@ -1284,7 +1229,7 @@ class Heightfield:
         g = _as_f32(grad_si, self.device)
         assert g.shape == (18, n)
         if grad_heightfield is None:
-            grad_heightfield = torch.zeros((self.height, self.width), dtype=torch.float32, device=self.device)
+            grad_heightfield = self._zero_heights()
         keep, _ = self._mask(active, n)
         grad_od = torch.empty((6, n), dtype=torch.float32, device=self.device) if ray_grads else None
         self._adjoint_raw(ray.o, ray.d, ray.maxt, pi.t, pi.prim_uv, pi.prim_index, ray_flags, keep, g,
@@ -1338,24 +1283,13 @@ class Adam:
         g = g.to(dtype=torch.float32).contiguous()
         self.t += 1
         m, v = self.state
-        stream = torch.cuda.current_stream(h.device).cuda_stream
         check(_capi.lib().hf_adam_step(self.shape._h, h.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
                                        self.lr, self.beta_1, self.beta_2, self.epsilon, self.t,
-                                       (1 if self.mask_updates else 0) | (2 if self.uniform else 0), stream))
+                                       (1 if self.mask_updates else 0) | (2 if self.uniform else 0),
+                                       self.shape._stream()))
         self.shape._heights_keepalive = h
         self.shape._heights_version += 1
         self.shape.mark_dirty()
-
-
-def _p3(x):
-    """ctypes array of the 3 row pointers of a [3, n] tensor"""
-    return (C.c_void_p * 3)(x[0].data_ptr(), x[1].data_ptr(), x[2].data_ptr())
-
-
-def _f3(x):
-    """[3, n] float32 device tensor -> (keepalive, ctypes array of 3 row pointers)"""
-    x = x.to(dtype=torch.float32).contiguous()
-    return x, _p3(x)
 
 
 def _lighting_inputs(sh_n, d, t, lights, vis):
@@ -1366,59 +1300,51 @@ def _lighting_inputs(sh_n, d, t, lights, vis):
     lh = lights.detach().cpu().tolist()
     for k in range(K):
         L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = lh[k]
-    vis_p = None
-    if vis is not None:
-        vis = vis.to(dtype=torch.uint8).contiguous()
-        vis_p = (C.c_void_p * K)(*[vis[k].data_ptr() for k in range(K)])
+    vis = vis.to(dtype=torch.uint8).contiguous() if vis is not None else None
     f32 = [x.to(dtype=torch.float32).contiguous() for x in (sh_n, d, t)]
-    return (*f32, L, K, vis, vis_p)
+    return (*f32, L, K, vis, _row_ptrs(vis))
 
 
 class _DirectLightingOp(torch.autograd.Function):
     @staticmethod
+    def _prefix(ctx, sn, dd, tt, ww=None):
+        """what every hf_direct_lighting_weighted* entry starts with"""
+        K, spp, L, albedo, vis, vis_p = ctx.misc
+        return sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), K, L, albedo, vis_p
+
+    @staticmethod
     def forward(ctx, sh_n, d, t, lights, albedo, spp, vis, weight):
         sn, dd, tt, L, K, vis, vis_p = _lighting_inputs(sh_n, d, t, lights, vis)
-        n = sn.shape[1]
         ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
-        image = torch.empty((K, n // spp), dtype=torch.float32, device=sh_n.device)
-        stream = torch.cuda.current_stream(sh_n.device).cuda_stream
-        check(_capi.lib().hf_direct_lighting_weighted(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(),
-                                                      ww.data_ptr() if ww is not None else None, K, L, albedo,
-                                                      vis_p, image.data_ptr(), stream))
-        ctx.save_for_backward(sn, dd, tt, *([ww] if ww is not None else []))
-        ctx.save_for_forward(sn, dd, tt, *([ww] if ww is not None else []))
-        ctx.misc = (L, K, albedo, spp, vis, vis_p, ww is not None)
+        saved = (sn, dd, tt) if ww is None else (sn, dd, tt, ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.misc = (K, spp, L, albedo, vis, vis_p)
+        image = torch.empty((K, sn.shape[1] // spp), dtype=torch.float32, device=sh_n.device)
+        check(_capi.lib().hf_direct_lighting_weighted(*_DirectLightingOp._prefix(ctx, *saved), image.data_ptr(),
+                                                      _stream_of(sh_n.device)))
         return image
 
     @staticmethod
     def jvp(ctx, dsh_n, _dd, _dt, _dl, _da, _ds, _dv, dweight):
-        L, K, albedo, spp, vis, vis_p, weighted = ctx.misc
-        sn, dd, tt = ctx.saved_tensors[:3]
-        ww = ctx.saved_tensors[3] if weighted else None
-        n = sn.shape[1]
-        dn, dn_p = _f3(dsh_n) if dsh_n is not None else (None, None)
-        dw = dweight.to(dtype=torch.float32).contiguous() if (weighted and dweight is not None) else None
-        dimage = torch.empty((K, n // spp), dtype=torch.float32, device=sn.device)
-        stream = torch.cuda.current_stream(sn.device).cuda_stream
-        check(_capi.lib().hf_direct_lighting_weighted_tangent(
-            n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), ww.data_ptr() if weighted else None, K, L, albedo,
-            vis_p, C.byref(dn_p) if dn is not None else None, dw.data_ptr() if dw is not None else None,
-            dimage.data_ptr(), stream))
+        saved = ctx.saved_tensors
+        dn = _f3(dsh_n)[0] if dsh_n is not None else None
+        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 4 and dweight is not None) else None
+        K, spp, sn = ctx.misc[0], ctx.misc[1], saved[0]
+        dimage = torch.empty((K, sn.shape[1] // spp), dtype=torch.float32, device=sn.device)
+        check(_capi.lib().hf_direct_lighting_weighted_tangent(*_DirectLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
+                                                              _ptr(dw), dimage.data_ptr(), _stream_of(sn.device)))
         return dimage
 
     @staticmethod
     def backward(ctx, grad_image):
-        L, K, albedo, spp, vis, vis_p, weighted = ctx.misc
-        sn, dd, tt = ctx.saved_tensors[:3]
-        ww = ctx.saved_tensors[3] if weighted else None
-        n = sn.shape[1]
+        saved = ctx.saved_tensors
+        sn = saved[0]
         gi = grad_image.to(dtype=torch.float32).contiguous()
         gn = torch.empty_like(sn)
-        gw = torch.empty(n, dtype=torch.float32, device=sn.device) if weighted else None
-        stream = torch.cuda.current_stream(sn.device).cuda_stream
-        check(_capi.lib().hf_direct_lighting_weighted_adjoint(
-            n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), ww.data_ptr() if weighted else None, K, L, albedo,
-            vis_p, gi.data_ptr(), C.byref(_p3(gn)), gw.data_ptr() if weighted else None, stream))
+        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 4 else None
+        check(_capi.lib().hf_direct_lighting_weighted_adjoint(*_DirectLightingOp._prefix(ctx, *saved), gi.data_ptr(),
+                                                              C.byref(_p3(gn)), _ptr(gw), _stream_of(sn.device)))
         return gn, None, None, None, None, None, None, gw
 
 
@@ -1436,45 +1362,41 @@ def direct_lighting(si, ray, lights, albedo=1.0, spp=1, vis=None, weight=None):
 
 class _PointLightingOp(torch.autograd.Function):
     @staticmethod
+    def _prefix(ctx, sn, pp, dd, tt):
+        """what every hf_point_lighting* entry starts with"""
+        K, spp, L, albedo, vis, vis_p = ctx.misc
+        return (sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), C.byref(_p3(pp)), K, L, albedo,
+                vis_p)
+
+    @staticmethod
     def forward(ctx, sh_n, p, d, t, lights, albedo, spp, vis):
         sn, dd, tt, L, K, vis, vis_p = _lighting_inputs(sh_n, d, t, lights, vis)
-        n = sn.shape[1]
-        pp = p.to(dtype=torch.float32).contiguous()
-        image = torch.empty((K, n // spp), dtype=torch.float32, device=sh_n.device)
-        stream = torch.cuda.current_stream(sh_n.device).cuda_stream
-        check(_capi.lib().hf_point_lighting(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), C.byref(_p3(pp)),
-                                            K, L, albedo, vis_p, image.data_ptr(), stream))
-        ctx.save_for_backward(sn, pp, dd, tt)
-        ctx.save_for_forward(sn, pp, dd, tt)
-        ctx.misc = (L, K, albedo, spp, vis, vis_p)
+        saved = (sn, p.to(dtype=torch.float32).contiguous(), dd, tt)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.misc = (K, spp, L, albedo, vis, vis_p)
+        image = torch.empty((K, sn.shape[1] // spp), dtype=torch.float32, device=sh_n.device)
+        check(_capi.lib().hf_point_lighting(*_PointLightingOp._prefix(ctx, *saved), image.data_ptr(),
+                                            _stream_of(sh_n.device)))
         return image
 
     @staticmethod
     def jvp(ctx, dsh_n, dp, *_):
-        sn, pp, dd, tt = ctx.saved_tensors
-        L, K, albedo, spp, vis, vis_p = ctx.misc
-        n = sn.shape[1]
-        dn, dn_p = _f3(dsh_n) if dsh_n is not None else (None, None)
-        dq, dq_p = _f3(dp) if dp is not None else (None, None)
-        dimage = torch.empty((K, n // spp), dtype=torch.float32, device=sn.device)
-        stream = torch.cuda.current_stream(sn.device).cuda_stream
-        check(_capi.lib().hf_point_lighting_tangent(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(),
-                                                    C.byref(_p3(pp)), K, L, albedo, vis_p,
-                                                    C.byref(dn_p) if dn is not None else None,
-                                                    C.byref(dq_p) if dq is not None else None, dimage.data_ptr(), stream))
+        sn = ctx.saved_tensors[0]
+        dn = _f3(dsh_n)[0] if dsh_n is not None else None
+        dq = _f3(dp)[0] if dp is not None else None
+        dimage = torch.empty((ctx.misc[0], sn.shape[1] // ctx.misc[1]), dtype=torch.float32, device=sn.device)
+        check(_capi.lib().hf_point_lighting_tangent(*_PointLightingOp._prefix(ctx, *ctx.saved_tensors), _ref(_row_ptrs(dn)),
+                                                    _ref(_row_ptrs(dq)), dimage.data_ptr(), _stream_of(sn.device)))
         return dimage
 
     @staticmethod
     def backward(ctx, grad_image):
-        sn, pp, dd, tt = ctx.saved_tensors
-        L, K, albedo, spp, vis, vis_p = ctx.misc
-        n = sn.shape[1]
+        sn, pp = ctx.saved_tensors[:2]
         gi = grad_image.to(dtype=torch.float32).contiguous()
         gn = torch.empty_like(sn); gp = torch.empty_like(pp)
-        stream = torch.cuda.current_stream(sn.device).cuda_stream
-        check(_capi.lib().hf_point_lighting_adjoint(n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(),
-                                                    C.byref(_p3(pp)), K, L, albedo, vis_p, gi.data_ptr(),
-                                                    C.byref(_p3(gn)), C.byref(_p3(gp)), stream))
+        check(_capi.lib().hf_point_lighting_adjoint(*_PointLightingOp._prefix(ctx, *ctx.saved_tensors), gi.data_ptr(),
+                                                    C.byref(_p3(gn)), C.byref(_p3(gp)), _stream_of(sn.device)))
         return gn, gp, None, None, None, None, None, None
 
 
@@ -1485,53 +1407,51 @@ def point_lighting(si, ray, lights, albedo=1.0, spp=1, vis=None):
     return _PointLightingOp.apply(si.sh_frame.n, si.p, ray.d, si.t, lights, float(albedo), int(spp), vis)
 
 
+def _film_splat(values, ps, weight, K, n, width, height, stddev):
+    """hf_film_splat of the [K, n] float32 values at ps into a zeroed [K, height * width] image and into weight"""
+    image = torch.zeros((K, height * width), dtype=torch.float32, device=ps.device)
+    px, py = _row_addrs(ps)
+    check(_capi.lib().hf_film_splat(n, K, _row_ptrs(values), px, py, width, height, stddev, image.data_ptr(),
+                                    weight.data_ptr(), _stream_of(ps.device)))
+    return image
+
+
+def _film_normalise(image, weight):
+    """accumulated value / accumulated weight where the weight is positive, else 0"""
+    covered = weight > 0
+    return torch.where(covered[None], image / torch.where(covered, weight, torch.ones_like(weight))[None],
+                       torch.zeros_like(image))
+
+
 class _FilmGaussianOp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, values, pos, width, height, stddev):
         K, n = values.shape
         v = values.detach().to(dtype=torch.float32).contiguous()
         ps = pos.detach().to(dtype=torch.float32).contiguous()
-        image = torch.zeros((K, height * width), dtype=torch.float32, device=v.device)
         weight = torch.zeros(height * width, dtype=torch.float32, device=v.device)
-        vp = (C.c_void_p * K)(*[v[k].data_ptr() for k in range(K)])
-        stream = torch.cuda.current_stream(v.device).cuda_stream
-        check(_capi.lib().hf_film_splat(n, K, vp, ps[0].data_ptr(), ps[1].data_ptr(), width, height, stddev,
-                                        image.data_ptr(), weight.data_ptr(), stream))
+        ctx.misc = (K, n, width, height, stddev)
+        image = _film_splat(v, ps, weight, *ctx.misc)
         ctx.save_for_backward(ps, weight)
         ctx.save_for_forward(ps, weight)
-        ctx.misc = (K, n, width, height, stddev)
-        covered = weight > 0
-        return torch.where(covered[None], image / torch.where(covered, weight, torch.ones_like(weight))[None],
-                           torch.zeros_like(image))
+        return _film_normalise(image, weight)
 
     @staticmethod
     def jvp(ctx, dvalues, *_):
         # the film is linear in the values: its tangent is the splat of the tangent values over the primal weights
         ps, weight = ctx.saved_tensors
-        K, n, width, height, stddev = ctx.misc
-        dv = dvalues.to(dtype=torch.float32).contiguous()
-        image = torch.zeros((K, height * width), dtype=torch.float32, device=ps.device)
-        wscratch = torch.zeros(height * width, dtype=torch.float32, device=ps.device)
-        vp = (C.c_void_p * K)(*[dv[k].data_ptr() for k in range(K)])
-        stream = torch.cuda.current_stream(ps.device).cuda_stream
-        check(_capi.lib().hf_film_splat(n, K, vp, ps[0].data_ptr(), ps[1].data_ptr(), width, height, stddev,
-                                        image.data_ptr(), wscratch.data_ptr(), stream))
-        covered = weight > 0
-        return torch.where(covered[None], image / torch.where(covered, weight, torch.ones_like(weight))[None],
-                           torch.zeros_like(image))
+        image = _film_splat(dvalues.to(dtype=torch.float32).contiguous(), ps, torch.zeros_like(weight), *ctx.misc)
+        return _film_normalise(image, weight)
 
     @staticmethod
     def backward(ctx, grad_film):
         ps, weight = ctx.saved_tensors
         K, n, width, height, stddev = ctx.misc
-        covered = weight > 0
-        ga = torch.where(covered[None], grad_film.to(torch.float32) / torch.where(covered, weight, torch.ones_like(weight))[None],
-                         torch.zeros_like(grad_film, dtype=torch.float32)).contiguous()
+        ga = _film_normalise(grad_film.to(torch.float32), weight).contiguous()
         gv = torch.empty((K, n), dtype=torch.float32, device=ps.device)
-        gp = (C.c_void_p * K)(*[gv[k].data_ptr() for k in range(K)])
-        stream = torch.cuda.current_stream(ps.device).cuda_stream
-        check(_capi.lib().hf_film_splat_adjoint(n, K, ps[0].data_ptr(), ps[1].data_ptr(), width, height, stddev,
-                                                ga.data_ptr(), gp, stream))
+        px, py = _row_addrs(ps)
+        check(_capi.lib().hf_film_splat_adjoint(n, K, px, py, width, height, stddev, ga.data_ptr(), _row_ptrs(gv),
+                                                _stream_of(ps.device)))
         return gv, None, None, None, None
 
 
@@ -1561,19 +1481,38 @@ REPARAM_FUSED = True   # tests switch this off to compare with the per-sample ke
 REPARAM_KEEP_BYTES = 64 << 30   # (288 GB of HBM per GPU: 16 samples of a 67 M-ray wavefront are 39 GB)
 
 
-def _sample_structs(buf, n, si_hit=True):
-    """hf_si_t / hf_pi_t over one [9, n] sample buffer: si.t, si.p[3], si.boundary_test | pi.t, u, v, prim_index.
-    Without ``si_hit`` only boundary_test of the SI record is written."""
-    rows = _rows(buf, n)
-    si_s = _capi.hf_si_t()
-    if si_hit:
-        si_s.t = rows[0]
-        for c in range(3):
-            si_s.p[c] = rows[1 + c]
-    si_s.boundary_test = rows[4]
-    pi_s = _capi.hf_pi_t()
-    pi_s.t, pi_s.prim_uv[0], pi_s.prim_uv[1], pi_s.prim_index = rows[5], rows[6], rows[7], rows[8]
-    return rows, si_s, pi_s
+def _sample_structs(buf, si_hit=True):
+    """hf_si_t / hf_pi_t over one sample buffer.  The backward's [9, n]: si.t, si.p[3], si.boundary_test | pi.t, u, v,
+    prim_index; without ``si_hit`` only boundary_test of the SI record is written.  The tangent's [5, n]: the last
+    five of those rows.  Returns (row addresses, si, pi)."""
+    rows = _row_addrs(buf)
+    si_s = hf_si_t()
+    if si_hit and len(rows) == 9:
+        _fill(si_s, [("t", 1), ("p", 3)], rows)
+    si_s.boundary_test = rows[-5]
+    return rows, si_s, _fill(hf_pi_t(), _PI_ROWS, rows[-4:])
+
+
+def _reparam_inputs(ray_o, ray_d, active):
+    """what the backward and the tangent of reparameterize_ray take: o, d as contiguous float32 [3, n] and active as
+    uint8 [n] (None: every ray)"""
+    o = ray_o.detach().to(torch.float32).contiguous()
+    d = ray_d.detach().to(torch.float32).contiguous()
+    act = None if active is None else torch.as_tensor(active, device=o.device).to(torch.uint8).reshape(-1).contiguous()
+    if act is not None and act.numel() != o.shape[1]:
+        raise ValueError("active: one flag per ray")
+    return o, d, act
+
+
+def _check_ray_index(ray_index, ray):
+    """ray_index of reparameterize_ray / _tangent: contiguous, one int32/uint32 id per ray on the rays' device"""
+    if ray_index is None:
+        return None
+    if ray_index.dtype not in (torch.int32, torch.uint32) or ray_index.numel() != ray.o.shape[1]:
+        raise ValueError("ray_index must be an int32/uint32 tensor with one id per ray")
+    if ray_index.device != ray.o.device:
+        raise ValueError("ray_index must live on the rays' device")
+    return ray_index.contiguous()
 
 
 def _reparam_backward_fused(shape, o, d, gd, gdiv, act_p, rid_p, cfg, stream):
@@ -1585,8 +1524,8 @@ def _reparam_backward_fused(shape, o, d, gd, gdiv, act_p, rid_p, cfg, stream):
     n = o.shape[1]
     o_p, d_p, gd_p = _p3(o), _p3(d), _p3(gd)
     store = torch.empty((num_rays, 9, n), dtype=torch.float32, device=o.device)   # sample k: 9 n floats further on
-    grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=o.device)
-    rows, si_s, pi_s = _sample_structs(store[0], n, si_hit=False)
+    grad_h = shape._zero_heights()
+    rows, si_s, pi_s = _sample_structs(store[0], si_hit=False)
     check(L.hf_reparam_trace_all(shape._h, n, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, int(antithetic), seed,
                                  rid_p, C.byref(pi_s), C.byref(si_s), 9 * n, stream))
     check(L.hf_reparam_backward(shape._h, n, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, exponent,
@@ -1605,18 +1544,15 @@ def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, n
     dev = o.device
     n = o.shape[1]
     ray_grads = need_o or need_d
-    act_p = None if act is None else act.data_ptr()
+    act_p = _ptr(act)
     flags = int(RayFlags.All | RayFlags.FollowShape | RayFlags.BoundaryTest)
     aux_d = torch.empty((3, n), dtype=torch.float32, device=dev); aux_maxt = torch.empty(n, dtype=torch.float32, device=dev)
     Z = torch.zeros(n, dtype=torch.float32, device=dev); dZ = torch.zeros((3, n), dtype=torch.float32, device=dev)
     g_p = torch.empty((3, n), dtype=torch.float32, device=dev); g_t = torch.empty(n, dtype=torch.float32, device=dev)
-    grad_h = torch.zeros((shape.height, shape.width), dtype=torch.float32, device=dev) if need_h else None
+    grad_h = shape._zero_heights() if need_h else None
     o_p, d_p, ad_p, dZ_p, gd_p, gp_p = _p3(o), _p3(d), _p3(aux_d), _p3(dZ), _p3(gd), _p3(g_p)
     r_s = shape._rays_struct(o, aux_d, aux_maxt)
-    g_s = _capi.hf_si_grad_t()
-    g_s.t = g_t.data_ptr()
-    for c in range(3):
-        g_s.p[c] = g_p[c].data_ptr()
+    g_s = _fill(hf_si_grad_t(), [("t", 1), ("p", 3)], [g_t.data_ptr()] + _row_addrs(g_p))
     gvd_p = go_adj_p = gd_adj_p = grad_o = grad_d = None
     if ray_grads:   # per-sample ray gradients of the auxiliary hit + the gradient w.r.t. V_direct itself
         g_vd, go_adj, gd_adj = (torch.empty((3, n), dtype=torch.float32, device=dev) for _ in range(3))
@@ -1630,12 +1566,11 @@ def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, n
 
     def trace(k, buf):
         aux(k)
-        _, si_s, pi_s = _sample_structs(buf, n)
+        _, si_s, pi_s = _sample_structs(buf)
         check(L.hf_ray_intersect(shape._h, n, C.byref(r_s), flags, None, C.byref(pi_s), C.byref(si_s), stream))
 
     def weights(mode, k, buf):
-        rows = _rows(buf, n)
-        sp_p = (C.c_void_p * 3)(*rows[1:4])
+        rows, sp_p = _row_addrs(buf), _p3(buf[1:4])
         check(L.hf_reparam_weights(mode, n, C.byref(o_p), C.byref(d_p), act_p, k, kappa, exponent, int(antithetic),
                                    seed, rid_p, rows[0], C.byref(sp_p), rows[4], Z.data_ptr(), C.byref(dZ_p), C.byref(gd_p),
                                    gdiv.data_ptr(), C.byref(gp_p), g_t.data_ptr(), gvd_p if mode == 1 else None, stream))
@@ -1651,10 +1586,9 @@ def _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep, n
         else:
             trace(k, buf)
         weights(1, k, buf)
-        _, si_s, pi_s = _sample_structs(buf, n)
+        _, si_s, pi_s = _sample_structs(buf)
         check(L.hf_adjoint_transform(shape._h, n, C.byref(r_s), C.byref(pi_s), flags, act_p, C.byref(g_s),
-                                     grad_h.data_ptr() if need_h else None, go_adj_p, gd_adj_p, None,
-                                     grad_tw.data_ptr() if grad_tw is not None else None, stream))
+                                     _ptr(grad_h), go_adj_p, gd_adj_p, None, _ptr(grad_tw), stream))
         if ray_grads:
             hit = torch.isfinite(buf[0])
             if act is not None:
@@ -1690,14 +1624,8 @@ def _reparam_tangent(shape, o, d, act, ray_index, cfg, dh, do, dd, dtw, stream):
         return out_dir, out_div
     chunk = max(1, min(n, REPARAM_KEEP_BYTES // (20 * num_rays)))
     store = torch.empty((num_rays, 5, chunk), dtype=torch.float32, device=dev)   # bt, t, u, v, prim per sample
-    rows = [store[0, r].data_ptr() for r in range(5)]
-    si_s = _capi.hf_si_t()
-    si_s.boundary_test = rows[0]
-    pi_s = _capi.hf_pi_t()
-    pi_s.t, pi_s.prim_uv[0], pi_s.prim_uv[1], pi_s.prim_index = rows[1], rows[2], rows[3], rows[4]
-    dh_p = dh.data_ptr() if dh is not None else None
-    dtw_p = dtw.data_ptr() if dtw is not None else None
-    for s in range(0, n, chunk):   # (row slices of [3, n] tensors are rows of m floats: no copies)
+    rows, si_s, pi_s = _sample_structs(store[0])
+    for s in range(0, n, chunk):   # (column slices of the [3, n] tensors: no copies, see _row_addrs)
         m = min(chunk, n - s)
         sl = slice(s, s + m)
         if ray_index is not None:
@@ -1707,46 +1635,29 @@ def _reparam_tangent(shape, o, d, act, ray_index, cfg, dh, do, dd, dtw, stream):
         else:
             rid = None
         o_p, d_p = _p3(o[:, sl]), _p3(d[:, sl])
-        act_p = act[sl].data_ptr() if act is not None else None
-        rid_p = rid.data_ptr() if rid is not None else None
+        act_p, rid_p = _ptr(act[sl] if act is not None else None), _ptr(rid)
         check(L.hf_reparam_trace_all(shape._h, m, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, int(antithetic),
                                      seed, rid_p, C.byref(pi_s), C.byref(si_s), 5 * chunk, stream))
         check(L.hf_reparam_tangent(shape._h, m, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, exponent,
-                                   int(antithetic), seed, rid_p, C.byref(pi_s), rows[0], 5 * chunk, dh_p,
-                                   C.byref(_p3(do[:, sl])) if do is not None else None,
-                                   C.byref(_p3(dd[:, sl])) if dd is not None else None, dtw_p,
+                                   int(antithetic), seed, rid_p, C.byref(pi_s), rows[0], 5 * chunk, _ptr(dh),
+                                   _ref(_p3(do[:, sl]) if do is not None else None),
+                                   _ref(_p3(dd[:, sl]) if dd is not None else None), _ptr(dtw),
                                    C.byref(_p3(out_dir[:, sl])), out_div[sl].data_ptr(), stream))
     return out_dir, out_div
 
 
-def _tangent_f32(x, numel, dev, what):
-    """a tangent as a contiguous float32 device tensor (None: zero)"""
-    if x is None:
-        return None
-    x = torch.as_tensor(x, device=dev).detach().to(torch.float32).contiguous()
-    if x.numel() != numel:
-        raise ValueError(f"{what}: expected {numel} values, got {x.numel()}")
-    return x
-
-
 def _reparam_tangent_entry(shape, ray_o, ray_d, dh, do, dd, dtw, num_rays, kappa, exponent, antithetic, seed, active,
                            ray_index):
-    o = ray_o.detach().to(torch.float32).contiguous()
-    d = ray_d.detach().to(torch.float32).contiguous()
+    o, d, act = _reparam_inputs(ray_o, ray_d, active)
     n, dev = o.shape[1], o.device
-    act = None if active is None else torch.as_tensor(active, device=dev).to(torch.uint8).reshape(-1).contiguous()
-    if act is not None and act.numel() != n:
-        raise ValueError("active: one flag per ray")
-    dh = _tangent_f32(dh, shape.width * shape.height, dev, "dheights")
-    do = _tangent_f32(do, 3 * n, dev, "d_o")
-    dd = _tangent_f32(dd, 3 * n, dev, "d_d")
-    dtw = _tangent_f32(dtw, 12, dev, "d_to_world")
+    dh = shape._dheights(dh, ValueError)
+    do = _tangent(do, (3, n), dev, "d_o", ValueError)
+    dd = _tangent(dd, (3, n), dev, "d_d", ValueError)
+    dtw = _tw_tangent(dtw, dev, ValueError)
     if num_rays < 1 or num_rays > 32:
         raise ValueError("num_rays: 1..32 auxiliary rays per ray")
-    stream = torch.cuda.current_stream(dev).cuda_stream
     cfg = (int(num_rays), float(kappa), float(exponent), bool(antithetic), int(seed))
-    return _reparam_tangent(shape, o, d, act, ray_index, cfg, dh, None if do is None else do.view(3, n),
-                            None if dd is None else dd.view(3, n), dtw, stream)
+    return _reparam_tangent(shape, o, d, act, ray_index, cfg, dh, do, dd, dtw, shape._stream())
 
 
 class _ReparameterizeOp(torch.autograd.Function):
@@ -1772,8 +1683,8 @@ class _ReparameterizeOp(torch.autograd.Function):
         """reparam.py:155-221: the tangents (V_theta, div V_theta) of (direction, det), hf_reparam_tangent"""
         ray_o, ray_d = ctx.saved_tensors
         num_rays, kappa, exponent, antithetic, seed, active, ray_index = ctx.cfg
-        return _reparam_tangent_entry(ctx.shape, ray_o, ray_d, dh, do, dd, _tw_tangent(dtw), num_rays, kappa, exponent,
-                                      antithetic, seed, active, ray_index)
+        return _reparam_tangent_entry(ctx.shape, ray_o, ray_d, dh, do, dd, dtw, num_rays, kappa, exponent, antithetic,
+                                      seed, active, ray_index)
 
     @staticmethod
     def backward(ctx, grad_direction, grad_divergence):
@@ -1781,32 +1692,31 @@ class _ReparameterizeOp(torch.autograd.Function):
         ray_o, ray_d = ctx.saved_tensors
         num_rays, kappa, exponent, antithetic, seed, active, ray_index = ctx.cfg
         cfg = (num_rays, kappa, exponent, antithetic, seed)
-        rid_p = ray_index.data_ptr() if ray_index is not None else None
+        rid_p = _ptr(ray_index)
         need_h, need_o, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         need_tw = ctx.needs_input_grad[11]
-        n = ray_o.shape[1]
-        o = ray_o.detach().to(torch.float32).contiguous(); d = ray_d.detach().to(torch.float32).contiguous()
-        if grad_direction is None:
-            grad_direction = torch.zeros_like(d)
-        if grad_divergence is None:
-            grad_divergence = torch.zeros(n, dtype=torch.float32, device=d.device)
-        gd = grad_direction.to(torch.float32).contiguous(); gdiv = grad_divergence.to(torch.float32).contiguous()
-        act = None if active is None else active.to(torch.uint8).contiguous()
-        act_p = None if act is None else act.data_ptr()
-        stream = torch.cuda.current_stream(ray_o.device).cuda_stream
+        o, d, act = _reparam_inputs(ray_o, ray_d, active)
+        n = o.shape[1]
+        gd = _tangent(grad_direction, (3, n), o.device, "grad_direction", ValueError)
+        gdiv = _tangent(grad_divergence, (n,), o.device, "grad_divergence", ValueError)
+        if gd is None:
+            gd = torch.zeros_like(d)
+        if gdiv is None:
+            gdiv = torch.zeros(n, dtype=torch.float32, device=d.device)
+        stream = shape._stream()
         keep = 36 * n * num_rays <= REPARAM_KEEP_BYTES
         # (backward runs only when some input needs a gradient: without the ray's, that is the heights')
         # (the fused backward is heights-only: a to_world gradient takes the per-sample path)
         grad_tw = torch.zeros(12, dtype=torch.float32, device=ray_o.device) if need_tw else None
         if REPARAM_FUSED and keep and not (need_o or need_d or need_tw) and num_rays <= 32:
-            gh, grad_o, grad_d = _reparam_backward_fused(shape, o, d, gd, gdiv, act_p, rid_p, cfg, stream), None, None
+            gh, grad_o, grad_d = _reparam_backward_fused(shape, o, d, gd, gdiv, _ptr(act), rid_p, cfg, stream), None, None
         else:
             gh, grad_o, grad_d = _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep,
                                                               need_h, need_o, need_d, stream, grad_tw)
         if gh is not None and gh.shape != shape.heightfield.shape:
             gh = gh.reshape(shape.heightfield.shape)
         return ((gh if need_h else None), (grad_o if need_o else None), (grad_d if need_d else None),
-                None, None, None, None, None, None, None, None, (_tw_grad(grad_tw, ctx.tw_like) if need_tw else None))
+                None, None, None, None, None, None, None, None, _tw_grad(grad_tw, ctx.tw_like))
 
 
 def reparameterize_ray(shape, ray, num_rays=4, kappa=1e5, exponent=3.0, antithetic=False, seed=0, active=None,
@@ -1822,14 +1732,8 @@ def reparameterize_ray(shape, ray, num_rays=4, kappa=1e5, exponent=3.0, antithet
     unpartitioned one.  Without it the id is the position in the batch.  For a ``differentiable_to_world`` shape whose
     ``to_world`` needs a gradient, that gradient is accumulated too (the per-sample backward with
     ``hf_adjoint_transform``; the fused ``hf_reparam_backward`` is heights-only)."""
-    if ray_index is not None:
-        if ray_index.dtype not in (torch.int32, torch.uint32) or ray_index.numel() != ray.o.shape[1]:
-            raise ValueError("ray_index must be an int32/uint32 tensor with one id per ray")
-        if ray_index.device != ray.o.device:
-            raise ValueError("ray_index must live on the rays' device")
-        ray_index = ray_index.contiguous()
     return _ReparameterizeOp.apply(shape.heightfield, ray.o, ray.d, shape, num_rays, kappa, exponent, antithetic, seed,
-                                   active, ray_index, shape._to_world_live())
+                                   active, _check_ray_index(ray_index, ray), shape._to_world_live())
 
 
 def reparameterize_ray_tangent(shape, ray, dheights=None, d_o=None, d_d=None, d_to_world=None, num_rays=4, kappa=1e5,
@@ -1838,13 +1742,5 @@ def reparameterize_ray_tangent(shape, ray, dheights=None, d_o=None, d_d=None, d_
     tangents of ``(direction, det)`` for tangents of the heights (``dheights`` [H, W]), of the ray (``d_o``, ``d_d``
     [3, n]) and of ``to_world`` (``d_to_world``: 3x4 / 4x4 / 12 values), any of them None (zero).  The same samples as
     ``reparameterize_ray`` for the same ``seed`` and ``ray_index``; ``hf_reparam_trace_all`` + ``hf_reparam_tangent``."""
-    if ray_index is not None:
-        if ray_index.dtype not in (torch.int32, torch.uint32) or ray_index.numel() != ray.o.shape[1]:
-            raise ValueError("ray_index must be an int32/uint32 tensor with one id per ray")
-        if ray_index.device != ray.o.device:
-            raise ValueError("ray_index must live on the rays' device")
-        ray_index = ray_index.contiguous()
-    if d_to_world is not None:
-        d_to_world = _tw_tangent(torch.as_tensor(d_to_world, device=ray.o.device))
     return _reparam_tangent_entry(shape, ray.o, ray.d, dheights, d_o, d_d, d_to_world, num_rays, kappa, exponent,
-                                  antithetic, seed, active, ray_index)
+                                  antithetic, seed, active, _check_ray_index(ray_index, ray))
