@@ -11,7 +11,19 @@ parameters, is set as shape.to_world and takes effect at parameters_changed(["to
 parameters through hf_adjoint_transform.  The camera sees the interior of the field only, so every ray hits and the
 image has no silhouette (the attached gradient is the whole derivative).
 
-    python examples/inverse_pose.py [--steps 150 --film 64 --spp 4]
+--silhouette looks at the whole field on a background of height 0 through a pinhole, so the image has a silhouette that
+moves with the pose, and adds the discontinuity term the way prb_reparam.py:317-366 does for the camera ray: the
+primary rays go through hf_amd.reparameterize_ray (identity in primal mode; --aux auxiliary rays per ray), the
+intersection is differentiated with respect to the reparameterised direction as well, every sample is multiplied by the
+determinant, AND the sample is splatted at the film position of the reparameterised ray with a smooth reconstruction
+filter (splat(): the Gaussian of film_gaussian, here in torch so that it is differentiable in the positions too).  The
+loss is then on the PIXELS.  Both are needed: the reparameterisation is a change of variables of the pixel integral,
+so it holds for a loss on integrals, not on single samples, and only when the filter follows the warped ray -- with
+samples kept in fixed pixels (a box film) the term div(f V) integrates to the flux of f V through the pixel edges,
+which for a translating shape is as large as the interior gradient.  The backward reaches to_world
+through hf_reparam_backward_full.
+
+    python examples/inverse_pose.py [--steps 150 --film 64 --spp 4 --silhouette --aux 8]
 """
 import argparse
 import math
@@ -56,6 +68,87 @@ def render(shape, ray):
     return torch.where(si.is_valid(), si.p[2], torch.zeros_like(si.t))
 
 
+EYE = 3.0   # height of the pinhole of the silhouette view above the plane z = 0
+
+
+def film_position(d, film, half):
+    """film position (pixel units) of the direction d [3, n] through the pinhole (0, 0, EYE) that looks down on the
+    square |x|, |y| <= half of the plane z = 0: differentiable in d"""
+    s = -EYE / d[2]
+    return torch.stack([(d[0] * s / half + 1.0) * (0.5 * film), (1.0 - d[1] * s / half) * (0.5 * film)])
+
+
+def pinhole(film, spp, device, half):
+    """(rays, film positions) of a perspective sensor: the warp of reparameterize_ray is one of the ray DIRECTION at a
+    fixed origin, which is a change of variables of the pixel integral for a pinhole (for an orthographic sensor the
+    integral is over the origins, and a direction does not name a film position)"""
+    pos = hf_amd.workload.film_positions(film, film, spp, device)
+    x = (pos[0] / (0.5 * film) - 1.0) * half
+    y = (1.0 - pos[1] / (0.5 * film)) * half
+    d = torch.stack([x, y, torch.full_like(x, -EYE)])
+    d = d / d.norm(dim=0)
+    o = torch.zeros_like(d); o[2] = EYE
+    return hf_amd.Ray3f(o.contiguous(), d.contiguous()), pos
+
+
+def splat(values, weights, pos, film, stddev=0.5, radius=2):
+    """Gaussian reconstruction filter (src/rfilters/gaussian.cpp: exp(-r^2 / 2 stddev^2) minus its value at the radius)
+    of per-sample values at film positions pos [2, n] (pixel units, pixel i covers [i, i + 1)), normalised by the
+    splatted weights: [film * film], differentiable in values, weights and pos"""
+    base = torch.floor(pos.detach()).long()
+    alpha, bias = -0.5 / (stddev * stddev), math.exp(-0.5 * radius * radius / (stddev * stddev))
+    img = torch.zeros(film * film, dtype=values.dtype, device=values.device)
+    wsum = torch.zeros_like(img)
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            px, py = base[0] + dx, base[1] + dy
+            inside = (px >= 0) & (px < film) & (py >= 0) & (py < film)
+            r2 = (pos[0] - (px + 0.5)) ** 2 + (pos[1] - (py + 0.5)) ** 2
+            w = torch.clamp(torch.exp(alpha * r2) - bias, min=0.0) * inside
+            idx = py.clamp(0, film - 1) * film + px.clamp(0, film - 1)
+            img = img.index_add(0, idx, w * values)
+            wsum = wsum.index_add(0, idx, w * weights)
+    return img / wsum.clamp_min(1e-12)
+
+
+def render_silhouette(shape, ray, pos, film, half, aux=8, kappa=2e4, reparam=True):
+    """the film [film * film] of the silhouette view.  reparam: primary rays through reparameterize_ray, values times the
+    determinant, splatted at the film position of the reparameterised ray (prb_reparam.py:317-366, common.py:229-262:
+    the sensor's film position of o + d').  In primal mode d' = d: pos keeps the value, the position's derivative moves"""
+    if not reparam:
+        return splat(render(shape, ray), torch.ones_like(ray.o[0]), pos, film)
+    d, det = hf_amd.reparameterize_ray(shape, ray, num_rays=aux, kappa=kappa, exponent=3.0)
+    vals = render(shape, hf_amd.Ray3f(ray.o, d, ray.maxt))
+    return splat(vals * det, det, pos + (film_position(d, film, half) - film_position(d.detach(), film, half)), film)
+
+
+def recover_silhouette(steps=150, film=64, spp=4, lr=0.01, device="cuda", log=None, aux=8, reparam=True, half=1.3):
+    """recover() on the view that contains the whole field: a loss on the pixels of the Gaussian film.  reparam=False
+    leaves the discontinuity term out (the attached gradient alone), for comparison"""
+    h = field(device=device)
+    shape = hf_amd.Heightfield(heightfield=h, max_height=0.5, differentiable_to_world=True)
+    ray, pos = pinhole(film, spp, device, half)
+    with torch.no_grad():
+        shape.to_world = pose_matrix(torch.tensor(TARGET, dtype=torch.float64))
+        shape.parameters_changed(["to_world"])
+        target = render_silhouette(shape, ray, pos, film, half, reparam=False)
+    p = torch.tensor(START, dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.Adam([p], lr=lr)
+    losses = []
+    for k in range(steps):
+        opt.zero_grad()
+        shape.to_world = pose_matrix(p)
+        shape.parameters_changed(["to_world"])
+        loss = ((render_silhouette(shape, ray, pos, film, half, aux, reparam=reparam) - target) ** 2).mean()
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+        if log and (k % 10 == 0 or k == steps - 1):
+            log(f"step {k:4d}  loss {losses[-1]:.3e}  tx {float(p[0]):+.5f}  ty {float(p[1]):+.5f}  "
+                f"yaw {math.degrees(float(p[2])):+.4f} deg")
+    return TARGET, START, tuple(float(v) for v in p.detach()), losses
+
+
 def recover(steps=150, film=64, spp=4, lr=0.01, device="cuda", log=None):
     """returns (target pose, start pose, final pose, losses)"""
     h = field(device=device)
@@ -91,8 +184,13 @@ def main():
     ap.add_argument("--film", type=int, default=64)
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--silhouette", action="store_true", help="the whole field in view, reparameterised primary rays")
+    ap.add_argument("--aux", type=int, default=8, help="auxiliary rays per primary ray of --silhouette")
     a = ap.parse_args()
-    target, start, final, losses = recover(a.steps, a.film, a.spp, a.lr, log=print)
+    if a.silhouette:
+        target, start, final, losses = recover_silhouette(a.steps, a.film, a.spp, a.lr, log=print, aux=a.aux)
+    else:
+        target, start, final, losses = recover(a.steps, a.film, a.spp, a.lr, log=print)
     print(f"target {target}, start {start}, recovered {final}")
 
 

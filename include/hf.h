@@ -739,6 +739,28 @@ int hf_reparam_tangent(const hf_field_t *hf, size_t n, const float *const o[3], 
                        size_t sample_stride, const float *dheights, const float *const d_o[3],
                        const float *const d_d[3], const float *d_to_world, float *const out_direction[3],
                        float *out_divergence, hf_stream_t stream);
+/* Reverse mode of the same reparameterisation with respect to EVERYTHING attached -- the heights, ray.o, ray.d and
+ * to_world -- in ONE kernel: the transpose of hf_reparam_tangent, from the same inputs (the kept auxiliary hits at
+ * [k * sample_stride + i], the samples regenerated from (d, k, seed, ray_id, antithetic), si.p and the FollowShape
+ * si.t re-derived from pi; weights detached).  Outputs, any subset, NULL = not wanted, at least one:
+ *   grad_heights  H*W device floats, accumulated (+=) with float atomics, as hf_reparam_backward;
+ *   grad_o[3], grad_d[3]  device rows of n floats, OVERWRITTEN; inactive lanes get exact zeros;
+ *   grad_to_world  12 device floats (row-major 3x4), accumulated (+=) through the slab reduction of
+ *                  hf_adjoint_transform: partial sums added in a fixed order, no float atomics.
+ * With gVd the gradient of a sample's V_direct: a hit gives (gp, gt) of V_direct = (p - o) / t,
+ * gp_tot = gp + gt (p - o) / (t |d_aux|^2); the vertices k of the hit triangle receive b_k gp_tot (heights: its
+ * component along max_height to_world[:, 2]; to_world: b_k gp_tot (q_k, 1)^T), grad_o -= gp_tot, and d_aux receives
+ * -gt t d_aux / |d_aux|^2, which goes on to ray.d through d_aux = s(d) omega.x + t(d) omega.y + d omega.z.  A miss on
+ * an active lane has V_direct = ray.d: grad_d += gVd.  grad_o / grad_d / grad_to_world are bitwise repeatable.
+ * Capturable, never synchronises; allocates nothing (grad_to_world leases one scratch block of the handle's ring).
+ * Callers detect the entry point by its symbol (HF_VERSION is unchanged).  1 <= num_rays <= 32. */
+int hf_reparam_backward_full(const hf_field_t *hf, size_t n, const float *const o[3], const float *const d[3],
+                             const uint8_t *active, uint32_t num_rays, float kappa, float exponent, int antithetic,
+                             uint32_t seed, const uint32_t *ray_id, const hf_pi_const_t *pi,
+                             const float *si_boundary_test, size_t sample_stride,
+                             const float *const grad_direction[3], const float *grad_divergence,
+                             float *grad_heights, float *const grad_o[3], float *const grad_d[3],
+                             float *grad_to_world, hf_stream_t stream);
 
 /* ---- scalar / packet entry -----------------------------------------------------
  * Shape::ray_intersect_preliminary_scalar / _packet and ray_test_scalar / _packet

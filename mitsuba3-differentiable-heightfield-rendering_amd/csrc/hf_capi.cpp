@@ -1316,6 +1316,45 @@ extern "C" int hf_reparam_tangent(const hf_field_t *hf, size_t n, const float *c
     return HF_OK;
 }
 
+extern "C" int hf_reparam_backward_full(const hf_field_t *hf, size_t n, const float *const o[3], const float *const d[3],
+                                        const uint8_t *active, uint32_t num_rays, float kappa, float exponent,
+                                        int antithetic, uint32_t seed, const uint32_t *ray_id, const hf_pi_const_t *pi,
+                                        const float *si_boundary_test, size_t sample_stride,
+                                        const float *const grad_direction[3], const float *grad_divergence,
+                                        float *grad_heights, float *const grad_o[3], float *const grad_d[3],
+                                        float *grad_to_world, hf_stream_t stream) {
+    const char *fn = "hf_reparam_backward_full";
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    if (!all3(o) || !all3(d) || !si_boundary_test || !all3(grad_direction) || !grad_divergence)
+        return fail(HF_EINVAL, "%s: NULL argument", fn);
+    int rc = check_pi(fn, n, pi);
+    if (rc) return rc;
+    if (grad_o && !all3(grad_o)) return fail(HF_EINVAL, "%s: NULL grad_o array", fn);
+    if (grad_d && !all3(grad_d)) return fail(HF_EINVAL, "%s: NULL grad_d array", fn);
+    if (!grad_heights && !grad_o && !grad_d && !grad_to_world) return fail(HF_EINVAL, "%s: NULL output (every gradient)", fn);
+    if (!(kappa > 0.f)) return fail(HF_EINVAL, "%s: kappa must be > 0", fn);
+    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 auxiliary rays per ray (got %u)", fn, num_rays);
+    if (num_rays > 1 && sample_stride < n) return fail(HF_EINVAL, "%s: sample_stride < n", fn);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 rays", fn);
+    if ((rc = check_device(fn, hf))) return rc;
+    if (n == 0) return HF_OK;
+    hf_reparam_args a = {};
+    a.n = n; a.active = active; a.seed = seed; a.kappa = kappa; a.exponent = exponent; a.antithetic = antithetic;
+    a.ray_id = ray_id; a.si_bt = si_boundary_test; a.g_div = grad_divergence;
+    for (int c = 0; c < 3; ++c) { a.o[c] = o[c]; a.d[c] = d[c]; a.g_dir[c] = grad_direction[c]; }
+    if (grad_to_world) {
+        slot_lease lease(hf, (hipStream_t) stream, hf_xform_slab_bytes(n)); // the slab: this launch's alone
+        if (!lease.buf) return fail(lease.code, "%s: %s", fn, lease.why);
+        hf_launch_reparam_backward_full(hf->dev, a, num_rays, sample_stride, pi, grad_heights, grad_o, grad_d,
+                                        grad_to_world, lease.buf, (hipStream_t) stream);
+    } else {
+        hf_launch_reparam_backward_full(hf->dev, a, num_rays, sample_stride, pi, grad_heights, grad_o, grad_d, nullptr,
+                                        nullptr, (hipStream_t) stream);
+    }
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- scalar / packet entry: host pointers, per-thread staging ------------------------
 namespace {
 // layout of the staging block, in floats: 7 ray rows, t, u, v, prim (u32), then HF_PACKET_MAX bytes of mask / hit

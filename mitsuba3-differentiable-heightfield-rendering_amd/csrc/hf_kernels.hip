@@ -3027,6 +3027,216 @@ void hf_launch_reparam_tangent(const hf_dev_field &f, const hf_reparam_args &ra,
 }
 
 // ---------------------------------------------------------------------------------
+// Reverse mode of the warped-area reparameterisation with respect to everything attached (hf_reparam_backward_full):
+// the transpose of hf_reparam_tangent_kernel, term for term, instantiated on the outputs wanted -- DH grad_heights,
+// RAY grad_o / grad_d, XF grad_to_world.  Two passes over a ray's samples, as in hf_reparam_backward_kernel (the
+// gradient of a sample's V_direct needs Z and dZ of all of them): the weights and their sums, then per sample
+//   hit:  (gp, gt) of V_direct = (p - o) / t, gp_tot = gp + gt po / (t |d_aux|^2); vertex c receives b_c gp_tot (DH: its
+//         component along height_axis into the scatter tile; XF: times (q_c, 1)^T into the lane's 12 sums); RAY:
+//         grad_o -= gp_tot and d_aux receives -gt t d_aux / |d_aux|^2, accumulated against omega into the gradients of
+//         Frame3f(d)'s s, t and d (coordinate_system_vjp is linear: applied once, after the samples);
+//   miss: V_direct = ray.d, RAY: grad_d += gVd.
+// Every sample is drawn in both passes and nothing is kept in between: the registers go to the sums (XF: 12, RAY: 12).
+// DH: the per-wave 64 x 64 LDS tile of hf_reparam_backward_kernel, two waves per SIMD.  Without DH there is no tile
+// and the launch bound asks for four.  Without RAY a wave whose rays all miss has nothing to add and skips, and so does
+// a sample no lane of the wave hit; with RAY the misses carry grad_d and every lane stores its rows (inactive: zeros).
+// Whole waves stay in the loop (ballots, the tile's shuffles) and no thread leaves before xform_block_store.
+// ---------------------------------------------------------------------------------
+struct hf_reparam_bwdf_kargs {
+    hf_dev_field f;
+    hf_reparam_bwd_args a; // grad_h: NULL without DH
+    float *go[3], *gd[3];  // RAY: either array may be absent (NULL rows)
+    float *slab;           // XF
+};
+template <bool DH, bool RAY, bool XF>
+__global__ __launch_bounds__(HF_BLOCK, (DH ? 2 : 4)) void hf_reparam_backward_full_kernel(hf_reparam_bwdf_kargs k_) {
+    (void) k_;
+    typedef const __attribute__((address_space(4))) hf_reparam_bwdf_kargs *kargs_t;
+    kargs_t kc = (kargs_t) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kc));
+    const size_t a_n = kc->a.n;
+    constexpr int TILE = HF_RB_TILE;
+    __shared__ float s_acc[DH ? HF_BLOCK / 64 : 1][DH ? TILE * TILE : 1]; // per-wave accumulation tile
+    float *acc = s_acc[DH ? (threadIdx.x >> 6) : 0];
+    const int lane = (int) (threadIdx.x & 63u);
+    if constexpr (DH)
+        for (int k = lane; k < TILE * TILE; k += 64) acc[k] = 0.f;
+    float M[12]; // XF: this lane's sums of dL/d(to_world)
+#pragma unroll
+    for (int j = 0; j < 12; ++j) M[j] = 0.f;
+    hf_reparam_args sa = {}; // what the sampling helpers read
+    sa.seed = kc->a.seed; sa.kappa = kc->a.kappa; sa.exponent = kc->a.exponent; sa.antithetic = kc->a.antithetic;
+    sa.ray_id = kc->a.ray_id;
+    const size_t stride = (size_t) gridDim.x * HF_BLOCK;
+    const size_t n_round = (a_n + HF_BLOCK - 1) / HF_BLOCK * HF_BLOCK; // whole waves stay in the loop
+    for (size_t i_raw = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i_raw < n_round; i_raw += stride) {
+        kargs_t ka = (kargs_t) __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka)); // opaque: keeps the loads that follow inside the loop body
+        const v3 z3 = mk3(0.f, 0.f, 0.f);
+        const bool valid = i_raw < a_n;
+        const size_t i = valid ? i_raw : a_n - 1;
+        const bool act = valid && (ka->a.active ? (ka->a.active[i] != 0) : true);
+        const size_t sst = ka->a.stride;
+        const uint32_t K = ka->a.num_rays;
+        uint32_t hm = 0u; // samples that hit
+        for (uint32_t k = 0; k < K; ++k) hm |= (act && ka->a.pi.t[k * sst + i] != __builtin_inff()) ? (1u << k) : 0u;
+        const bool work = act && (RAY || hm != 0u);
+        const bool wave_work = __ballot(work) != 0ull;
+        if constexpr (!RAY) {
+            if (!wave_work) continue; // wave-uniform: nothing reaches the heights or to_world
+        }
+        v3 gO = z3, gD = z3, gFs = z3, gFt = z3; // RAY: dL/do, dL/dd (direct), dL/ds, dL/dt of Frame3f(d)
+        if (wave_work) {
+            v3 o = z3, d = z3;
+            hf_vd_grad g = { z3, 0.f };
+            const hf_dev_field f = load_field(&ka->f);
+            if (work) {
+                d = mk3(ka->a.d[0][i], ka->a.d[1][i], ka->a.d[2][i]);
+                if (hm != 0u) o = mk3(ka->a.o[0][i], ka->a.o[1][i], ka->a.o[2][i]);
+                const v3 gdir = mk3(ka->a.g_dir[0][i], ka->a.g_dir[1][i], ka->a.g_dir[2][i]);
+                const float gdiv = ka->a.g_div[i];
+                // first pass: Z = sum_k w_k, dZ = sum_k d_w_omega_k, in sample order from zero; the boundary test of
+                // sample k + 1 is requested before sample k is drawn
+                float Zs = 0.f;
+                v3 dZ = z3;
+                float nbt = (hm & 1u) ? ka->a.si_bt[i] : 1.0f;
+                for (uint32_t k = 0; k < K; ++k) {
+                    const float B = nbt;
+                    if (k + 1 < K) nbt = ((hm >> (k + 1)) & 1u) ? ka->a.si_bt[(k + 1) * sst + i] : 1.0f;
+                    sa.k = k;
+                    hf_aux_sample q;
+                    aux_sample(sa, i, d, q);
+                    float w;
+                    v3 dw;
+                    reparam_weight(sa, q, d, B, w, dw);
+                    Zs += w;
+                    dZ.x += dw.x; dZ.y += dw.y; dZ.z += dw.z;
+                }
+                g = vdirect_grad_ray(d, gdir, gdiv, Zs, [&] { return dZ; });
+            }
+            // second pass (wave-uniform loop): the samples' V_direct.  The records of sample k + 1 are requested before
+            // sample k is worked on, and a hit's heights before its sample is drawn, as in hf_reparam_tangent_kernel
+            int ar = 0, ac = 0; // tile anchor (wave-uniform), set at the first sample with a hit
+            bool anchored = false;
+            hf_tile_rows<TILE> rows = 0u;
+            const uint32_t hm_any = RAY ? 0u : wave_or(hm);
+            const v3 ez = height_axis(f); // dP_k/dh_k
+            float nbt = 1.f, nb1 = 0.f, nb2 = 0.f; // the next sample's record (a hit's)
+            uint32_t nprim = 0u;
+            if (hm & 1u) { nbt = ka->a.si_bt[i]; nb1 = ka->a.pi.prim_uv[0][i]; nb2 = ka->a.pi.prim_uv[1][i]; nprim = ka->a.pi.prim_index[i]; }
+            for (uint32_t k = 0; k < K; ++k) {
+                const bool hit = ((hm >> k) & 1u) != 0u;
+                const float B = hit ? nbt : 1.0f, b1 = nb1, b2 = nb2;
+                const uint32_t prim = nprim;
+                if (k + 1 < K && ((hm >> (k + 1)) & 1u)) { // (k + 1 < K first: a shift by 32 is not defined)
+                    const size_t ik1 = (k + 1) * sst + i;
+                    nbt = ka->a.si_bt[ik1]; nb1 = ka->a.pi.prim_uv[0][ik1]; nb2 = ka->a.pi.prim_uv[1][ik1];
+                    nprim = ka->a.pi.prim_index[ik1];
+                }
+                if constexpr (!RAY) {
+                    if (((hm_any >> k) & 1u) == 0u) continue; // wave-uniform: a miss adds nothing
+                }
+                float gh[3] = { 0.f, 0.f, 0.f };
+                int vr[3] = { 0, 0, 0 }, vc[3] = { 0, 0, 0 };
+                if (RAY ? work : hit) {
+                    float hz[3] = { 0.f, 0.f, 0.f };
+                    if (hit) { // the three heights: prim_world's loads, used below
+                        prim_vertex_ids(f, prim, vr, vc);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) hz[c] = f.h[(size_t) vr[c] * f.W + vc[c]];
+                    }
+                    sa.k = k;
+                    hf_aux_sample q;
+                    aux_sample(sa, i, d, q);
+                    float w;
+                    v3 dw;
+                    reparam_weight(sa, q, d, B, w, dw);
+                    const v3 gVd = vdirect_grad_sample(g, w, dw);
+                    if (hit) {
+                        const float b0 = 1.f - b1 - b2;
+                        v3 P[3], ql[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { // prim_world's expressions
+                            ql[c] = grid_local(f, vr[c], vc[c], hz[c]);
+                            P[c] = xform_point(f.to_world, ql[c]);
+                        }
+                        const v3 da = frame_to_world(q, d, q.omega); // the auxiliary direction (= hf_reparam_aux_kernel's)
+                        // V_direct = (p - o) / t with the FollowShape t = sqrt(|p - o|^2 / |d_aux|^2) of compute_si
+                        const auto [po, dda, tt] = follow_t(bary_point(P, b0, b1, b2), o, da);
+                        auto [gp, gt] = vdirect_grad_hit(gVd, po, tt);
+                        axpy3(gt / (tt * dda), po, gp); // t's dependence on p - o: gp is now the gradient of p - o
+                        if constexpr (RAY) {
+                            gO = gO - gp;
+                            // t's dependence on d_aux = s(d) omega.x + t(d) omega.y + d omega.z, omega detached
+                            const v3 gda = da * (-gt * tt / dda);
+                            axpy3(q.omega.x, gda, gFs); axpy3(q.omega.y, gda, gFt); axpy3(q.omega.z, gda, gD);
+                        }
+                        // p = sum b_c P_c with detached barycentrics; P_c = to_world (q_c, 1), dP_c/dh_c = ez
+                        const float bc[3] = { b0, b1, b2 };
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const v3 gP = gp * bc[c];
+                            if constexpr (DH) gh[c] = dot3(ez, gP);
+                            if constexpr (XF) xform_grad_point(M, gP, ql[c]);
+                        }
+                    } else if constexpr (RAY) {
+                        gD = gD + gVd; // miss: V_direct = ray.d (reparam.py:93-95)
+                    }
+                }
+                if constexpr (DH) {
+                    const uint64_t hb = __ballot(hit);
+                    if (!anchored && hb != 0ull) { // wave-uniform: the first sample with a hit anchors the tile
+                        tile_anchor(hb, vr, vc, HF_RB_ANCHOR, ar, ac);
+                        anchored = true;
+                    }
+                    if (hit)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) tile_add<TILE>(acc, ar, ac, vr[c], vc[c], gh[c], ka->a.grad_h, f.W, rows);
+                }
+            }
+            if constexpr (DH) tile_flush<TILE>(acc, ar, ac, rows, ka->a.grad_h, f.W, lane);
+            if constexpr (RAY) {
+                if (work) gD = gD + coordinate_system_vjp(d, gFs, gFt);
+            }
+        }
+        if constexpr (RAY) {
+            if (valid) { // inactive lanes: exact zeros
+                if (ka->go[0]) { ka->go[0][i] = gO.x; ka->go[1][i] = gO.y; ka->go[2][i] = gO.z; }
+                if (ka->gd[0]) { ka->gd[0][i] = gD.x; ka->gd[1][i] = gD.y; ka->gd[2][i] = gD.z; }
+            }
+        }
+    }
+    if constexpr (XF) xform_block_store(M, kc->slab); // every thread of the block
+}
+
+void hf_launch_reparam_backward_full(const hf_dev_field &f, const hf_reparam_args &ra, uint32_t num_rays, size_t stride,
+                                     const hf_pi_const_t *pi, float *grad_h, float *const grad_o[3],
+                                     float *const grad_d[3], float *grad_to_world, void *slab, hipStream_t stream) {
+    if (ra.n == 0) return;
+    hf_reparam_bwdf_kargs k = {};
+    hf_reparam_bwd_args &a = k.a;
+    k.f = f;
+    a.n = ra.n; a.stride = stride; a.active = ra.active; a.num_rays = num_rays; a.seed = ra.seed; a.kappa = ra.kappa;
+    a.exponent = ra.exponent; a.antithetic = ra.antithetic; a.ray_id = ra.ray_id; a.pi = *pi; a.si_bt = ra.si_bt;
+    a.g_div = ra.g_div; a.grad_h = grad_h;
+    for (int c = 0; c < 3; ++c) {
+        a.o[c] = ra.o[c]; a.d[c] = ra.d[c]; a.g_dir[c] = ra.g_dir[c];
+        k.go[c] = grad_o ? grad_o[c] : nullptr; k.gd[c] = grad_d ? grad_d[c] : nullptr;
+    }
+    k.slab = (float *) slab;
+    void (*const table[8])(hf_reparam_bwdf_kargs) = {
+        nullptr, hf_reparam_backward_full_kernel<true, false, false>,
+        hf_reparam_backward_full_kernel<false, true, false>, hf_reparam_backward_full_kernel<true, true, false>,
+        hf_reparam_backward_full_kernel<false, false, true>, hf_reparam_backward_full_kernel<true, false, true>,
+        hf_reparam_backward_full_kernel<false, true, true>, hf_reparam_backward_full_kernel<true, true, true> };
+    const int sel = (grad_h ? 1 : 0) | ((grad_o || grad_d) ? 2 : 0) | (grad_to_world ? 4 : 0);
+    if (sel == 0) return; // (refused by the caller)
+    const int grid = grad_to_world ? grid_for(ra.n, HF_XFORM_GRID_CAP) : grid_for(ra.n);
+    hipLaunchKernelGGL(table[sel], dim3(grid), dim3(HF_BLOCK), 0, stream, k);
+    if (grad_to_world) xform_sum((const float *) slab, grid, grad_to_world, stream); // slab: hf_xform_slab_bytes(n), this launch's alone
+}
+
+// ---------------------------------------------------------------------------------
 // Adam step on the height texture (optimizers.py:263-300), explicit operation order (no contraction)
 // ---------------------------------------------------------------------------------
 // (sched, ctr): hf_adam_step_scheduled -- the step size is sched[*ctr] (a host-filled table of the bias-corrected step

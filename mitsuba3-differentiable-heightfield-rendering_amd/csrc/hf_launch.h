@@ -101,6 +101,12 @@ void hf_launch_reparam_tangent(const hf_dev_field &f, const hf_reparam_args &a, 
                                const hf_pi_const_t *pi, const float *dh, const float *const d_o[3],
                                const float *const d_d[3], const float *d_to_world, float *const out_dir[3],
                                float *out_div, hipStream_t stream);
+// hf_reparam_backward_full: a.g_dir / g_div and what hf_launch_reparam_tangent reads; grad_h, grad_o, grad_d,
+// grad_to_world may each be NULL (not wanted).  grad_h, grad_to_world accumulated, grad_o / grad_d overwritten;
+// slab (with grad_to_world): as for hf_launch_adjoint
+void hf_launch_reparam_backward_full(const hf_dev_field &f, const hf_reparam_args &a, uint32_t num_rays, size_t stride,
+                                     const hf_pi_const_t *pi, float *grad_h, float *const grad_o[3],
+                                     float *const grad_d[3], float *grad_to_world, void *slab, hipStream_t stream);
 // ---- area sampling (hf_set_area_sampling) ----
 #define HF_AREA_CHUNK 2048 // cells per tile of the table build: one cell row, or a 2048-cell piece of one
 #define HF_AREA_SEG 64     // CDF entries per entry of the coarse search table

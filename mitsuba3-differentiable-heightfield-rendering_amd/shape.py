@@ -1646,6 +1646,45 @@ def _reparam_tangent(shape, o, d, act, ray_index, cfg, dh, do, dd, dtw, stream):
     return out_dir, out_div
 
 
+def _reparam_backward_full(shape, o, d, gd, gdiv, act, ray_index, cfg, grad_h, need_o, need_d, grad_tw, stream):
+    """Reverse mode with respect to any of the heights, ray.o, ray.d and to_world: hf_reparam_trace_all keeps every
+    auxiliary hit (pi + si.boundary_test, 20 B per ray and sample, the layout of _reparam_tangent), then ONE
+    hf_reparam_backward_full.  grad_h ([H, W]) and grad_tw (12 values) are the caller's accumulators (None: not
+    wanted); returns (grad_o, grad_d) ([3, n], None when not wanted).  Chunked like _reparam_tangent when the records
+    exceed REPARAM_KEEP_BYTES: the chunks' rays keep their global ids, grad_h / grad_tw accumulate across the chunks and
+    grad_o / grad_d are written by column slice."""
+    L = _capi.lib()
+    num_rays, kappa, exponent, antithetic, seed = cfg
+    dev = o.device
+    n = o.shape[1]
+    grad_o = torch.empty((3, n), dtype=torch.float32, device=dev) if need_o else None
+    grad_d = torch.empty((3, n), dtype=torch.float32, device=dev) if need_d else None
+    if n == 0:
+        return grad_o, grad_d
+    chunk = max(1, min(n, REPARAM_KEEP_BYTES // (20 * num_rays)))
+    store = torch.empty((num_rays, 5, chunk), dtype=torch.float32, device=dev)   # bt, t, u, v, prim per sample
+    rows, si_s, pi_s = _sample_structs(store[0])
+    for s in range(0, n, chunk):   # (column slices of the [3, n] tensors: no copies, see _row_addrs)
+        m = min(chunk, n - s)
+        sl = slice(s, s + m)
+        if ray_index is not None:
+            rid = ray_index[sl]
+        elif m < n:
+            rid = torch.arange(s, s + m, dtype=torch.int32, device=dev)
+        else:
+            rid = None
+        o_p, d_p, gd_p = _p3(o[:, sl]), _p3(d[:, sl]), _p3(gd[:, sl])
+        act_p, rid_p = _ptr(act[sl] if act is not None else None), _ptr(rid)
+        check(L.hf_reparam_trace_all(shape._h, m, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, int(antithetic),
+                                     seed, rid_p, C.byref(pi_s), C.byref(si_s), 5 * chunk, stream))
+        check(L.hf_reparam_backward_full(shape._h, m, C.byref(o_p), C.byref(d_p), act_p, num_rays, kappa, exponent,
+                                         int(antithetic), seed, rid_p, C.byref(pi_s), rows[0], 5 * chunk, C.byref(gd_p),
+                                         gdiv[sl].data_ptr(), _ptr(grad_h),
+                                         _ref(_p3(grad_o[:, sl]) if need_o else None),
+                                         _ref(_p3(grad_d[:, sl]) if need_d else None), _ptr(_grad12(grad_tw)), stream))
+    return grad_o, grad_d
+
+
 def _reparam_tangent_entry(shape, ray_o, ray_d, dh, do, dd, dtw, num_rays, kappa, exponent, antithetic, seed, active,
                            ray_index):
     o, d, act = _reparam_inputs(ray_o, ray_d, active)
@@ -1706,9 +1745,14 @@ class _ReparameterizeOp(torch.autograd.Function):
         stream = shape._stream()
         keep = 36 * n * num_rays <= REPARAM_KEEP_BYTES
         # (backward runs only when some input needs a gradient: without the ray's, that is the heights')
-        # (the fused backward is heights-only: a to_world gradient takes the per-sample path)
+        # heights only: hf_reparam_backward; with the ray or to_world: hf_reparam_backward_full (chunked when the hits
+        # do not fit).  The per-sample kernels are what REPARAM_FUSED = False selects
         grad_tw = torch.zeros(12, dtype=torch.float32, device=ray_o.device) if need_tw else None
-        if REPARAM_FUSED and keep and not (need_o or need_d or need_tw) and num_rays <= 32:
+        if REPARAM_FUSED and (need_o or need_d or need_tw) and num_rays <= 32:
+            gh = shape._zero_heights() if need_h else None
+            grad_o, grad_d = _reparam_backward_full(shape, o, d, gd, gdiv, act, ray_index, cfg, gh, need_o, need_d,
+                                                    grad_tw, stream)
+        elif REPARAM_FUSED and keep and num_rays <= 32:
             gh, grad_o, grad_d = _reparam_backward_fused(shape, o, d, gd, gdiv, _ptr(act), rid_p, cfg, stream), None, None
         else:
             gh, grad_o, grad_d = _reparam_backward_per_sample(shape, o, d, gd, gdiv, act, rid_p, cfg, keep,
@@ -1730,8 +1774,9 @@ def reparameterize_ray(shape, ray, num_rays=4, kappa=1e5, exponent=3.0, antithet
     ``ray_index`` (int32/uint32 device tensor, one id per ray, e.g. the global pixel index) makes the samples of a
     ray independent of its position in the batch, so a partitioned render draws the same auxiliary rays as the
     unpartitioned one.  Without it the id is the position in the batch.  For a ``differentiable_to_world`` shape whose
-    ``to_world`` needs a gradient, that gradient is accumulated too (the per-sample backward with
-    ``hf_adjoint_transform``; the fused ``hf_reparam_backward`` is heights-only)."""
+    ``to_world`` needs a gradient, that gradient is accumulated too.  The backward is one trace of all auxiliary rays
+    and one kernel: ``hf_reparam_backward`` when only the heights are differentiated, ``hf_reparam_backward_full``
+    when ``ray.o``, ``ray.d`` or ``to_world`` is."""
     return _ReparameterizeOp.apply(shape.heightfield, ray.o, ray.d, shape, num_rays, kappa, exponent, antithetic, seed,
                                    active, _check_ray_index(ray_index, ray), shape._to_world_live())
 
@@ -1744,3 +1789,49 @@ def reparameterize_ray_tangent(shape, ray, dheights=None, d_o=None, d_d=None, d_
     ``reparameterize_ray`` for the same ``seed`` and ``ray_index``; ``hf_reparam_trace_all`` + ``hf_reparam_tangent``."""
     return _reparam_tangent_entry(shape, ray.o, ray.d, dheights, d_o, d_d, d_to_world, num_rays, kappa, exponent,
                                   antithetic, seed, active, _check_ray_index(ray_index, ray))
+
+
+def _check_accumulator(x, numel, device, what):
+    """a caller's gradient accumulator is handed to the kernel as a device pointer: float32, contiguous, `numel` values,
+    on the rays' device"""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != numel:
+        raise ValueError(f"{what}: a contiguous float32 tensor of {numel} values")
+    if x.device != device:
+        raise ValueError(f"{what} lives on {x.device}, the rays on {device}")
+
+
+def reparameterize_ray_adjoint(shape, ray, grad_direction, grad_divergence, num_rays=4, kappa=1e5, exponent=3.0,
+                               antithetic=False, seed=0, active=None, ray_index=None, heights=True, o=False, d=False,
+                               to_world=False, grad_heightfield=None, grad_to_world=None):
+    """Explicit reverse mode of ``reparameterize_ray`` (reparam.py:224-333), the sibling of
+    ``reparameterize_ray_tangent``: for upstream gradients ``grad_direction`` ([3, n]) and ``grad_divergence`` ([n]) of
+    ``(direction, det)`` (None: zero) returns ``(grad_heights, grad_o, grad_d, grad_to_world)``, None for the outputs not
+    asked for with ``heights`` / ``o`` / ``d`` / ``to_world``.  ``grad_heightfield`` ([H, W] float32) and
+    ``grad_to_world`` (12 contiguous float32 device values, row-major 3x4) are accumulators of the caller's, as in
+    ``Heightfield.adjoint``: the gradients are ADDED to them and they are returned; without them zeroed ones are made.
+    ``grad_o`` / ``grad_d`` ([3, n]) are new tensors.  The same samples as ``reparameterize_ray`` for the same ``seed`` and
+    ``ray_index``; ``hf_reparam_trace_all`` + ``hf_reparam_backward_full``."""
+    ray_index = _check_ray_index(ray_index, ray)
+    ro, rd, act = _reparam_inputs(ray.o, ray.d, active)
+    n, dev = ro.shape[1], ro.device
+    if num_rays < 1 or num_rays > 32:
+        raise ValueError("num_rays: 1..32 auxiliary rays per ray")
+    if not (heights or o or d or to_world):
+        raise ValueError("reparameterize_ray_adjoint: no gradient asked for")
+    gd = _tangent(grad_direction, (3, n), dev, "grad_direction", ValueError)
+    gdiv = _tangent(grad_divergence, (n,), dev, "grad_divergence", ValueError)
+    if gd is None:
+        gd = torch.zeros_like(rd)
+    if gdiv is None:
+        gdiv = torch.zeros(n, dtype=torch.float32, device=dev)
+    grad_h = grad_tw = None
+    if heights:
+        grad_h = shape._zero_heights() if grad_heightfield is None else grad_heightfield
+        _check_accumulator(grad_h, shape.height * shape.width, dev, "grad_heightfield")
+    if to_world:
+        grad_tw = torch.zeros(12, dtype=torch.float32, device=dev) if grad_to_world is None else grad_to_world
+        _check_accumulator(grad_tw, 12, dev, "grad_to_world")
+    cfg = (int(num_rays), float(kappa), float(exponent), bool(antithetic), int(seed))
+    grad_o, grad_d = _reparam_backward_full(shape, ro, rd, gd, gdiv, act, ray_index, cfg, grad_h, bool(o), bool(d), grad_tw,
+                                            shape._stream())
+    return grad_h, grad_o, grad_d, grad_tw
