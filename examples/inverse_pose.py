@@ -16,14 +16,15 @@ moves with the pose, and adds the discontinuity term the way prb_reparam.py:317-
 primary rays go through hf_amd.reparameterize_ray (identity in primal mode; --aux auxiliary rays per ray), the
 intersection is differentiated with respect to the reparameterised direction as well, every sample is multiplied by the
 determinant, AND the sample is splatted at the film position of the reparameterised ray with a smooth reconstruction
-filter (splat(): the Gaussian of film_gaussian, here in torch so that it is differentiable in the positions too).  The
-loss is then on the PIXELS.  Both are needed: the reparameterisation is a change of variables of the pixel integral,
+filter (splat(): a radial Gaussian in torch, differentiable in the positions; --native-film: the library's film,
+hf_amd.film_gaussian(vals * det, pos', film, film, weight=det), the separable filter of ImageBlock with its own adjoint
+and tangent kernels).  The loss is then on the PIXELS.  Both are needed: the reparameterisation is a change of variables of the pixel integral,
 so it holds for a loss on integrals, not on single samples, and only when the filter follows the warped ray -- with
 samples kept in fixed pixels (a box film) the term div(f V) integrates to the flux of f V through the pixel edges,
 which for a translating shape is as large as the interior gradient.  The backward reaches to_world
 through hf_reparam_backward_full.
 
-    python examples/inverse_pose.py [--steps 150 --film 64 --spp 4 --silhouette --aux 8]
+    python examples/inverse_pose.py [--steps 150 --film 64 --spp 4 --silhouette --aux 8 --native-film]
 """
 import argparse
 import math
@@ -111,27 +112,37 @@ def splat(values, weights, pos, film, stddev=0.5, radius=2):
     return img / wsum.clamp_min(1e-12)
 
 
-def render_silhouette(shape, ray, pos, film, half, aux=8, kappa=2e4, reparam=True):
+def film_of(values, weights, pos, film, native_film=False):
+    """the film [film * film] of weighted samples: splat(), or the library's film (ImageBlock::put(pos, value, weight))"""
+    if native_film:
+        return hf_amd.film_gaussian(values[None], pos, film, film, weight=weights)[0]
+    return splat(values, weights, pos, film)
+
+
+def render_silhouette(shape, ray, pos, film, half, aux=8, kappa=2e4, reparam=True, native_film=False):
     """the film [film * film] of the silhouette view.  reparam: primary rays through reparameterize_ray, values times the
     determinant, splatted at the film position of the reparameterised ray (prb_reparam.py:317-366, common.py:229-262:
     the sensor's film position of o + d').  In primal mode d' = d: pos keeps the value, the position's derivative moves"""
     if not reparam:
-        return splat(render(shape, ray), torch.ones_like(ray.o[0]), pos, film)
+        return film_of(render(shape, ray), torch.ones_like(ray.o[0]), pos, film, native_film)
     d, det = hf_amd.reparameterize_ray(shape, ray, num_rays=aux, kappa=kappa, exponent=3.0)
     vals = render(shape, hf_amd.Ray3f(ray.o, d, ray.maxt))
-    return splat(vals * det, det, pos + (film_position(d, film, half) - film_position(d.detach(), film, half)), film)
+    return film_of(vals * det, det, pos + (film_position(d, film, half) - film_position(d.detach(), film, half)), film,
+                   native_film)
 
 
-def recover_silhouette(steps=150, film=64, spp=4, lr=0.01, device="cuda", log=None, aux=8, reparam=True, half=1.3):
+def recover_silhouette(steps=150, film=64, spp=4, lr=0.01, device="cuda", log=None, aux=8, reparam=True, half=1.3,
+                       native_film=False):
     """recover() on the view that contains the whole field: a loss on the pixels of the Gaussian film.  reparam=False
-    leaves the discontinuity term out (the attached gradient alone), for comparison"""
+    leaves the discontinuity term out (the attached gradient alone), for comparison; native_film: the library's film
+    instead of splat(), for the target as well"""
     h = field(device=device)
     shape = hf_amd.Heightfield(heightfield=h, max_height=0.5, differentiable_to_world=True)
     ray, pos = pinhole(film, spp, device, half)
     with torch.no_grad():
         shape.to_world = pose_matrix(torch.tensor(TARGET, dtype=torch.float64))
         shape.parameters_changed(["to_world"])
-        target = render_silhouette(shape, ray, pos, film, half, reparam=False)
+        target = render_silhouette(shape, ray, pos, film, half, reparam=False, native_film=native_film)
     p = torch.tensor(START, dtype=torch.float64, requires_grad=True)
     opt = torch.optim.Adam([p], lr=lr)
     losses = []
@@ -139,7 +150,8 @@ def recover_silhouette(steps=150, film=64, spp=4, lr=0.01, device="cuda", log=No
         opt.zero_grad()
         shape.to_world = pose_matrix(p)
         shape.parameters_changed(["to_world"])
-        loss = ((render_silhouette(shape, ray, pos, film, half, aux, reparam=reparam) - target) ** 2).mean()
+        loss = ((render_silhouette(shape, ray, pos, film, half, aux, reparam=reparam, native_film=native_film)
+                 - target) ** 2).mean()
         loss.backward()
         opt.step()
         losses.append(float(loss.detach()))
@@ -186,9 +198,12 @@ def main():
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--silhouette", action="store_true", help="the whole field in view, reparameterised primary rays")
     ap.add_argument("--aux", type=int, default=8, help="auxiliary rays per primary ray of --silhouette")
+    ap.add_argument("--native-film", action="store_true",
+                    help="--silhouette: hf_amd.film_gaussian(..., weight=det) instead of the example's torch splat()")
     a = ap.parse_args()
     if a.silhouette:
-        target, start, final, losses = recover_silhouette(a.steps, a.film, a.spp, a.lr, log=print, aux=a.aux)
+        target, start, final, losses = recover_silhouette(a.steps, a.film, a.spp, a.lr, log=print, aux=a.aux,
+                                                          native_film=a.native_film)
     else:
         target, start, final, losses = recover(a.steps, a.film, a.spp, a.lr, log=print)
     print(f"target {target}, start {start}, recovered {final}")

@@ -648,6 +648,44 @@ int hf_film_splat_adjoint(size_t n, uint32_t channels, const float *pos_x, const
                           uint32_t height, float stddev, const float *grad_image, float *const *grad_values,
                           hf_stream_t stream);
 
+/* The same film for samples that move and carry a weight: ImageBlock::put(pos, value, weight) with the position
+ * attached (src/render/imageblock.cpp:264-400 evaluates the filter of src/rfilters/gaussian.cpp:48-101 analytically on
+ * it), which is what a reparameterised integrator needs -- value = L det and weight = det splatted at the film position
+ * of the warped ray (src/python/python/ad/integrators/common.py:383-405).  Filter and footprint are exactly
+ * hf_film_splat's: x = px - (pos_x - 0.5), pixels ceil(pos - 0.5 - r) .. floor(pos - 0.5 + r) clamped to the film,
+ * w(x) = max(0, e^(alpha x^2) - e^(alpha r^2)), alpha = -1 / (2 stddev^2), r = 4 stddev, f = w(x) w(y).  Its derivative:
+ * w'(x) = 2 alpha x e^(alpha x^2) where w(x) > 0, else 0, and df/dpos_x = -w'(x) w(y); w is continuous at the radius,
+ * so the clamped footprint has no boundary term.  All three take device pointers, launch on `stream`, allocate nothing,
+ * never synchronise and can be captured; arguments are checked as for hf_film_splat.
+ *
+ * hf_film_splat_weighted accumulates  image[c][pix] += f values[c][i]  and  weight[pix] += f sample_weight[i]
+ * (sample_weight: n floats, NULL = 1: the sums of hf_film_splat up to the order of the float atomics). */
+int hf_film_splat_weighted(size_t n, uint32_t channels, const float *const *values, const float *sample_weight,
+                           const float *pos_x, const float *pos_y, uint32_t width, uint32_t height, float stddev,
+                           float *image, float *weight, hf_stream_t stream);
+/* Reverse mode (common.py:868-970): grad_image [channels][H W] = dL/d(accumulated image), grad_weight [H W] =
+ * dL/d(accumulated weight) (NULL = zero).  With G_i(pix) = sum_c values[c][i] grad_image[c][pix] + sample_weight[i]
+ * grad_weight[pix]:
+ *   grad_values[c][i]     = sum_pix f grad_image[c][pix]
+ *   grad_sample_weight[i] = sum_pix f grad_weight[pix]
+ *   grad_pos_x[i]         = sum_pix -w'(x) w(y) G_i(pix),   grad_pos_y[i] = sum_pix -w(x) w'(y) G_i(pix)
+ * Every output is overwritten; any of them may be NULL (not wanted), not all.  values may be NULL unless a position
+ * gradient is asked for.  A gather without atomics: bitwise the same from launch to launch. */
+int hf_film_splat_weighted_adjoint(size_t n, uint32_t channels, const float *const *values, const float *sample_weight,
+                                   const float *pos_x, const float *pos_y, uint32_t width, uint32_t height, float stddev,
+                                   const float *grad_image, const float *grad_weight,
+                                   float *const *grad_values, float *grad_sample_weight,
+                                   float *grad_pos_x, float *grad_pos_y, hf_stream_t stream);
+/* Forward mode (common.py:705-780, sample_pos_deriv), the exact transpose of the adjoint: tangents dvalues, dsample_weight,
+ * dpos_x, dpos_y (each may be NULL = zero) give, with df = -w'(x) w(y) dpos_x[i] - w(x) w'(y) dpos_y[i],
+ *   dimage[c][pix] += f dvalues[c][i] + df values[c][i],   dweight[pix] += f dsample_weight[i] + df sample_weight[i]
+ * ACCUMULATED with float atomics like the primal (zero them first); a contribution that is exactly zero adds nothing. */
+int hf_film_splat_weighted_tangent(size_t n, uint32_t channels, const float *const *values, const float *sample_weight,
+                                   const float *pos_x, const float *pos_y, uint32_t width, uint32_t height, float stddev,
+                                   const float *const *dvalues, const float *dsample_weight,
+                                   const float *dpos_x, const float *dpos_y,
+                                   float *dimage, float *dweight, hf_stream_t stream);
+
 /* ---- next row: warped-area reparameterisation of rays ---------- */
 
 /* The auxiliary-ray machinery of mitsuba.ad.reparameterize_ray (src/python/python/ad/reparam.py:10-123,

@@ -1155,6 +1155,73 @@ extern "C" int hf_film_splat_adjoint(size_t n, uint32_t channels, const float *p
     return HF_OK;
 }
 
+// ---- the same film, differentiable in the sample positions, with a per-sample weight ----------------
+// rows[0 .. channels) of an optional array of channel rows into out; a NULL row of a given array is refused
+template <class T>
+static int channel_rows(const char *who, uint32_t channels, T *const *rows, T **out) {
+    for (uint32_t k = 0; rows && k < channels; ++k) {
+        if (!rows[k]) return fail(HF_EINVAL, "%s: NULL channel array", who);
+        out[k] = rows[k];
+    }
+    return HF_OK;
+}
+
+extern "C" int hf_film_splat_weighted(size_t n, uint32_t channels, const float *const *values, const float *sample_weight,
+                                      const float *pos_x, const float *pos_y, uint32_t width, uint32_t height,
+                                      float stddev, float *image, float *weight, hf_stream_t stream) {
+    static const char *who = "hf_film_splat_weighted";
+    hf_film_motion_args a = {};
+    int rc = splat_args(who, n, channels, pos_x, pos_y, width, height, stddev, a.s);
+    if (rc != HF_OK) return rc;
+    if (!values || !image || !weight) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if ((rc = channel_rows(who, channels, values, a.s.values)) != HF_OK) return rc;
+    a.sample_weight = sample_weight; a.s.image = image; a.s.weight = weight;
+    hf_launch_film_motion(0, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_film_splat_weighted_adjoint(size_t n, uint32_t channels, const float *const *values,
+                                              const float *sample_weight, const float *pos_x, const float *pos_y,
+                                              uint32_t width, uint32_t height, float stddev, const float *grad_image,
+                                              const float *grad_weight, float *const *grad_values,
+                                              float *grad_sample_weight, float *grad_pos_x, float *grad_pos_y,
+                                              hf_stream_t stream) {
+    static const char *who = "hf_film_splat_weighted_adjoint";
+    hf_film_motion_args a = {};
+    int rc = splat_args(who, n, channels, pos_x, pos_y, width, height, stddev, a.s);
+    if (rc != HF_OK) return rc;
+    if (!grad_image) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (!grad_values && !grad_sample_weight && !grad_pos_x && !grad_pos_y) return fail(HF_EINVAL, "%s: no output", who);
+    if ((grad_pos_x || grad_pos_y) && !values) return fail(HF_EINVAL, "%s: a position gradient needs the values", who);
+    if ((rc = channel_rows(who, channels, values, a.s.values)) != HF_OK) return rc;
+    if ((rc = channel_rows(who, channels, grad_values, a.s.grad_values)) != HF_OK) return rc;
+    a.sample_weight = sample_weight; a.s.grad_image = grad_image; a.grad_weight = grad_weight;
+    a.grad_sample_weight = grad_sample_weight; a.grad_pos_x = grad_pos_x; a.grad_pos_y = grad_pos_y;
+    hf_launch_film_motion(1, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_film_splat_weighted_tangent(size_t n, uint32_t channels, const float *const *values,
+                                              const float *sample_weight, const float *pos_x, const float *pos_y,
+                                              uint32_t width, uint32_t height, float stddev, const float *const *dvalues,
+                                              const float *dsample_weight, const float *dpos_x, const float *dpos_y,
+                                              float *dimage, float *dweight, hf_stream_t stream) {
+    static const char *who = "hf_film_splat_weighted_tangent";
+    hf_film_motion_args a = {};
+    int rc = splat_args(who, n, channels, pos_x, pos_y, width, height, stddev, a.s);
+    if (rc != HF_OK) return rc;
+    if (!values || !dimage || !dweight) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if ((rc = channel_rows(who, channels, values, a.s.values)) != HF_OK) return rc;
+    if ((rc = channel_rows(who, channels, dvalues, a.dvalues)) != HF_OK) return rc;
+    a.sample_weight = sample_weight; a.dsample_weight = dsample_weight; a.dpos_x = dpos_x; a.dpos_y = dpos_y;
+    a.s.image = dimage; a.s.weight = dweight;
+    hf_launch_film_motion(2, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- warped-area reparameterisation --------------------------------------------
 
 extern "C" int hf_reparam_aux_rays(size_t n, const float *const o[3], const float *const d[3], const uint8_t *active,

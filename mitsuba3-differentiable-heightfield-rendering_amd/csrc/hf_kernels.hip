@@ -3527,6 +3527,110 @@ void hf_launch_film_splat(const hf_splat_args &a, bool adjoint, hipStream_t stre
     else         hipLaunchKernelGGL(hf_film_splat_kernel<false>, grid, block, 0, stream, a);
 }
 
+// ---------------------------------------------------------------------------------
+// The same film for samples that MOVE and carry a weight (hf_film_splat_weighted and its two derivatives): what
+// ImageBlock::put(pos, value, weight) does with the position attached (src/render/imageblock.cpp:264-400 evaluates
+// the filter analytically on it), in forward mode (src/python/python/ad/integrators/common.py:705-780) and in reverse
+// (common.py:868-970).  f = w(x) w(y), x = px - (pos_x - 0.5):  df/dpos_x = -w'(x) w(y), w'(x) = 2 alpha x e^(alpha x^2)
+// where w(x) > 0, else 0; w is continuous at the radius, so the clamped footprint has no boundary term.
+// One thread per sample; w(y), w'(y) once per row; one exponential gives w and w' of a coordinate.
+// ---------------------------------------------------------------------------------
+
+__device__ __forceinline__ void film_weight(float alpha, float bias, float x, float &w, float &dw) {
+    const float e = expf(alpha * (x * x));
+    w = fmaxf(e - bias, 0.f);
+    dw = w > 0.f ? 2.f * alpha * x * e : 0.f;
+}
+
+// MODE 0: image += f value, weight += f sample_weight (float atomics)
+// MODE 1: the gather of hf.h -- no atomics, every wanted output overwritten
+// MODE 2: the transpose of MODE 1, scattered like MODE 0; a contribution that is exactly zero issues no atomic
+template <int MODE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_film_motion_kernel(hf_film_motion_args m) {
+    const hf_splat_args &a = m.s;
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const float fx = a.pos_x[i] - 0.5f, fy = a.pos_y[i] - 0.5f;
+    const int x0 = max((int) ceilf(fx - a.radius), 0), x1 = min((int) floorf(fx + a.radius), (int) a.width - 1);
+    const int y0 = max((int) ceilf(fy - a.radius), 0), y1 = min((int) floorf(fy + a.radius), (int) a.height - 1);
+    const float sw = m.sample_weight ? m.sample_weight[i] : 1.f;
+    float val[HF_MAX_LIGHTS];
+    float aux[HF_MAX_LIGHTS]; // MODE 1: the sums of grad_values, MODE 2: the tangent values
+#pragma unroll
+    for (uint32_t k = 0; k < HF_MAX_LIGHTS; ++k) {
+        val[k] = (k < a.channels && a.values[k]) ? a.values[k][i] : 0.f;
+        aux[k] = (MODE == 2 && k < a.channels && m.dvalues[k]) ? m.dvalues[k][i] : 0.f;
+    }
+    float dsw = 0.f, dpx = 0.f, dpy = 0.f; // MODE 1: the sums of the three per-sample outputs, MODE 2: the tangents
+    if (MODE == 2) {
+        if (m.dsample_weight) dsw = m.dsample_weight[i];
+        if (m.dpos_x) dpx = m.dpos_x[i];
+        if (m.dpos_y) dpy = m.dpos_y[i];
+    }
+    const size_t plane = (size_t) a.width * a.height;
+    for (int y = y0; y <= y1; ++y) {
+        float wy, dwy;
+        film_weight(a.alpha, a.bias, (float) y - fy, wy, dwy);
+        if (wy == 0.f) continue; // (then w'(y) = 0 as well)
+        for (int x = x0; x <= x1; ++x) {
+            float wx, dwx;
+            film_weight(a.alpha, a.bias, (float) x - fx, wx, dwx);
+            const float f = wx * wy;
+            const size_t pix = (size_t) y * a.width + x;
+            if (MODE == 0) {
+                if (f == 0.f) continue;
+                atomicAdd(a.weight + pix, f * sw);
+#pragma unroll
+                for (uint32_t k = 0; k < HF_MAX_LIGHTS; ++k)
+                    if (k < a.channels) atomicAdd(a.image + k * plane + pix, f * val[k]);
+                continue;
+            }
+            if (wx == 0.f) continue;
+            const float fpx = -dwx * wy, fpy = -wx * dwy; // df/dpos_x, df/dpos_y
+            if (MODE == 1) {
+                const float gw = m.grad_weight ? m.grad_weight[pix] : 0.f;
+                float G = sw * gw;
+#pragma unroll
+                for (uint32_t k = 0; k < HF_MAX_LIGHTS; ++k)
+                    if (k < a.channels) {
+                        const float g = a.grad_image[k * plane + pix];
+                        aux[k] = __builtin_fmaf(f, g, aux[k]);
+                        G = __builtin_fmaf(val[k], g, G);
+                    }
+                dsw = __builtin_fmaf(f, gw, dsw);
+                dpx = __builtin_fmaf(fpx, G, dpx);
+                dpy = __builtin_fmaf(fpy, G, dpy);
+            } else {
+                const float df = __builtin_fmaf(fpx, dpx, fpy * dpy);
+                const float cw = __builtin_fmaf(f, dsw, df * sw);
+                if (cw != 0.f) atomicAdd(a.weight + pix, cw);
+#pragma unroll
+                for (uint32_t k = 0; k < HF_MAX_LIGHTS; ++k)
+                    if (k < a.channels) {
+                        const float c = __builtin_fmaf(f, aux[k], df * val[k]);
+                        if (c != 0.f) atomicAdd(a.image + k * plane + pix, c);
+                    }
+            }
+        }
+    }
+    if (MODE == 1) {
+#pragma unroll
+        for (uint32_t k = 0; k < HF_MAX_LIGHTS; ++k)
+            if (k < a.channels && a.grad_values[k]) a.grad_values[k][i] = aux[k];
+        if (m.grad_sample_weight) m.grad_sample_weight[i] = dsw;
+        if (m.grad_pos_x) m.grad_pos_x[i] = dpx;
+        if (m.grad_pos_y) m.grad_pos_y[i] = dpy;
+    }
+}
+
+void hf_launch_film_motion(int mode, const hf_film_motion_args &a, hipStream_t stream) {
+    if (a.s.n == 0) return;
+    const dim3 grid((unsigned) ((a.s.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    if (mode == 0)      hipLaunchKernelGGL(hf_film_motion_kernel<0>, grid, block, 0, stream, a);
+    else if (mode == 1) hipLaunchKernelGGL(hf_film_motion_kernel<1>, grid, block, 0, stream, a);
+    else                hipLaunchKernelGGL(hf_film_motion_kernel<2>, grid, block, 0, stream, a);
+}
+
 // the rows of a [3, n] argument; NULL: three NULL rows
 static hf_f3ptr f3ptr(const float *const r[3]) { return r ? hf_f3ptr{ { r[0], r[1], r[2] } } : hf_f3ptr{}; }
 static hf_f3out f3out(float *const r[3]) { return r ? hf_f3out{ { r[0], r[1], r[2] } } : hf_f3out{}; }

@@ -75,6 +75,18 @@ struct hf_splat_args {
     float *grad_values[HF_MAX_LIGHTS];    // adjoint: per-channel, overwritten
 };
 void hf_launch_film_splat(const hf_splat_args &a, bool adjoint, hipStream_t stream);
+// hf_film_splat_weighted / _adjoint / _tangent: the film of samples that move and carry a weight.  s.image / s.weight
+// are the planes the forward AND the tangent accumulate into (the tangent's dimage, dweight)
+struct hf_film_motion_args {
+    hf_splat_args s;                      // s.values: NULL rows where the caller gave none (adjoint, tangent)
+    const float *sample_weight;           // NULL: 1
+    const float *grad_weight;             // adjoint: dL/d(accumulated weight) [H*W], NULL: zero
+    float *grad_sample_weight, *grad_pos_x, *grad_pos_y; // adjoint: overwritten, NULL: not wanted (as s.grad_values rows)
+    const float *dvalues[HF_MAX_LIGHTS];  // tangent inputs, NULL: zero
+    const float *dsample_weight, *dpos_x, *dpos_y;
+};
+// mode 0: forward, 1: adjoint, 2: tangent
+void hf_launch_film_motion(int mode, const hf_film_motion_args &a, hipStream_t stream);
 struct hf_reparam_args {
     size_t n;
     const float *o[3], *d[3];

@@ -1455,12 +1455,83 @@ class _FilmGaussianOp(torch.autograd.Function):
         return gv, None, None, None, None
 
 
-def film_gaussian(values, pos, width, height, stddev=0.5):
+class _FilmMotionOp(torch.autograd.Function):
+    """The two accumulated planes (image [K, H W], weight [H W]) of samples that move and carry a weight:
+    hf_film_splat_weighted; backward = hf_film_splat_weighted_adjoint (gradients of values, pos and weight),
+    jvp = hf_film_splat_weighted_tangent.  ``weight`` None: every sample weighs 1."""
+
+    @staticmethod
+    def forward(ctx, values, pos, weight, width, height, stddev):
+        K, n = values.shape
+        v = values.detach().to(dtype=torch.float32).contiguous()
+        ps = pos.detach().to(dtype=torch.float32, device=v.device).contiguous()
+        sw = None if weight is None else weight.detach().to(dtype=torch.float32, device=v.device).contiguous().reshape(n)
+        assert ps.shape == (2, n), f"pos: expected [2, {n}], got {tuple(ps.shape)}"
+        ctx.misc = (n, K, width, height, stddev)
+        ctx.like = [(x.dtype, x.device) if isinstance(x, torch.Tensor) else None for x in (values, pos, weight)]
+        image = torch.zeros((K, height * width), dtype=torch.float32, device=v.device)
+        plane = torch.zeros(height * width, dtype=torch.float32, device=v.device)
+        px, py = _row_addrs(ps)
+        check(_capi.lib().hf_film_splat_weighted(n, K, _row_ptrs(v), _ptr(sw), px, py, width, height, stddev,
+                                                 image.data_ptr(), plane.data_ptr(), _stream_of(v.device)))
+        saved = (v, ps) if sw is None else (v, ps, sw)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        return image, plane
+
+    @staticmethod
+    def jvp(ctx, dvalues, dpos, dweight, *_):
+        v, ps, sw = (*ctx.saved_tensors, None)[:3]
+        n, K, width, height, stddev = ctx.misc
+        dv = _tangent(dvalues, (K, n), v.device, "dvalues")
+        dps = _tangent(dpos, (2, n), v.device, "dpos")
+        dsw = _tangent(dweight, (n,), v.device, "dweight")
+        dimage = torch.zeros((K, height * width), dtype=torch.float32, device=v.device)
+        dplane = torch.zeros(height * width, dtype=torch.float32, device=v.device)
+        px, py = _row_addrs(ps)
+        dpx, dpy = (None, None) if dps is None else _row_addrs(dps)
+        check(_capi.lib().hf_film_splat_weighted_tangent(n, K, _row_ptrs(v), _ptr(sw), px, py, width, height, stddev,
+                                                         _row_ptrs(dv), _ptr(dsw), dpx, dpy, dimage.data_ptr(),
+                                                         dplane.data_ptr(), _stream_of(v.device)))
+        return dimage, dplane
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_plane):
+        v, ps, sw = (*ctx.saved_tensors, None)[:3]
+        n, K, width, height, stddev = ctx.misc
+        need_v, need_p, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and sw is not None
+        if not (need_v or need_p or need_w):
+            return None, None, None, None, None, None
+        gi = grad_image.to(dtype=torch.float32).contiguous()
+        gw = grad_plane.to(dtype=torch.float32).contiguous()
+        gv = torch.empty((K, n), dtype=torch.float32, device=v.device) if need_v else None
+        gp = torch.empty((2, n), dtype=torch.float32, device=v.device) if need_p else None
+        gsw = torch.empty(n, dtype=torch.float32, device=v.device) if need_w else None
+        px, py = _row_addrs(ps)
+        gpx, gpy = (None, None) if gp is None else _row_addrs(gp)
+        check(_capi.lib().hf_film_splat_weighted_adjoint(n, K, _row_ptrs(v), _ptr(sw), px, py, width, height, stddev,
+                                                         gi.data_ptr(), gw.data_ptr(), _row_ptrs(gv), _ptr(gsw), gpx, gpy,
+                                                         _stream_of(v.device)))
+        back = lambda g, like: None if g is None else g.to(dtype=like[0], device=like[1])
+        return back(gv, ctx.like[0]), back(gp, ctx.like[1]), back(gsw, ctx.like[2]), None, None, None
+
+
+def film_gaussian(values, pos, width, height, stddev=0.5, weight=None):
     """Film with the reference's default reconstruction filter (Gaussian, stddev 0.5 pixel; ``hf_film_splat``;
     src/rfilters/gaussian.cpp, src/render/imageblock.cpp:258-330): ``values`` [K, n] per-sample values (e.g.
     ``direct_lighting(..., spp=1)``), ``pos`` [2, n] film positions in pixels (``workload.film_positions``).  Returns the
-    normalised film [K, height * width] (accumulated value / accumulated weight); differentiable w.r.t. ``values``."""
-    return _FilmGaussianOp.apply(values, pos, int(width), int(height), float(stddev))
+    normalised film [K, height * width] (accumulated value / accumulated weight); differentiable w.r.t. ``values``.
+
+    ``weight`` [n]: what each sample adds to the weight plane per unit of filter weight (``ImageBlock::put(pos, value,
+    weight)``; None = 1) -- the determinant of a reparameterised ray, with ``values`` = L det (common.py:868-970).  With a
+    ``weight``, or a ``pos`` that requires a gradient or carries a forward-mode tangent, the film is differentiable
+    w.r.t. ``values``, ``pos`` and ``weight`` (``hf_film_splat_weighted`` and its adjoint / tangent; the division by the
+    weight plane is differentiated by torch, so the gradient reaches both planes as after ``film.develop()``)."""
+    moving = isinstance(pos, torch.Tensor) and (pos.requires_grad or _has_tangent(pos))
+    if weight is None and not moving:
+        return _FilmGaussianOp.apply(values, pos, int(width), int(height), float(stddev))
+    image, plane = _FilmMotionOp.apply(values, pos, weight, int(width), int(height), float(stddev))
+    return _film_normalise(image, plane)
 
 
 def _coordinate_system(n):
