@@ -33,10 +33,21 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hf_amd  # noqa: E402
 
+SKY_RAYS = 8  # sky directions per sample of --sky
 LIGHTS = torch.tensor([[0.5, 0.2, 0.84], [-0.5, 0.3, 0.81], [0.1, -0.6, 0.79], [0.0, 0.0, 1.0]])
 
 
-def render_reparameterized(shape, ray, lights, spp, aux=8, kappa=2e4, seed=0, ray_index=None):
+def add_sky(images, shape, si, ray, spp, sky, weight=None, ray_index=None):
+    """one more image row: the surface under a constant environment of radiance `sky`, its SKY_RAYS shadow rays per
+    sample traced inside the lighting kernel (hf_sky_lighting); sky = 0: the images as they are"""
+    if not sky:
+        return images
+    row = hf_amd.sky_lighting(shape, si, ray, radiance=sky, albedo=1.0, spp=spp, num_rays=SKY_RAYS, weight=weight,
+                              ray_index=ray_index)
+    return torch.cat([images, row[None]])
+
+
+def render_reparameterized(shape, ray, lights, spp, aux=8, kappa=2e4, seed=0, ray_index=None, sky=0.0):
     """primary rays through reparameterize_ray; per-sample diffuse shading x determinant and the box film in
     hf_direct_lighting (weight row = the determinant); the gradient reaches the heights through hf_adjoint (shading
     normal), the auxiliary rays (reparameterised direction) and the determinant (weight gradient)"""
@@ -46,18 +57,22 @@ def render_reparameterized(shape, ray, lights, spp, aux=8, kappa=2e4, seed=0, ra
     si = shape.ray_intersect(ray2, hf_amd.RayFlags.All)
     valid = si.is_valid()
     images = hf_amd.direct_lighting(si, ray2, lights, albedo=1.0, spp=spp, weight=det)
+    images = add_sky(images, shape, si, ray2, spp, sky, det, ray_index)
     depth = torch.where(valid, si.t, torch.zeros_like(si.t))
     return images, depth, valid
 
 
-def render(shape, ray, lights, spp, shadows=False, silhouette=False, aux=8, kappa=2e4, film=None, ray_index=None):
+def render(shape, ray, lights, spp, shadows=False, silhouette=False, aux=8, kappa=2e4, film=None, ray_index=None,
+           sky=0.0):
     """film: None = box filter (pixel = mean of its samples, inside hf_direct_lighting); (positions [2, n], width,
-    height) = the reference's default Gaussian reconstruction filter (hf_film_splat) on the per-sample values"""
+    height) = the reference's default Gaussian reconstruction filter (hf_film_splat) on the per-sample values;
+    sky: radiance of a constant environment, rendered as one more image row (box film only)"""
     if silhouette:
-        return render_reparameterized(shape, ray, lights, spp, aux, kappa, ray_index=ray_index)
+        return render_reparameterized(shape, ray, lights, spp, aux, kappa, ray_index=ray_index, sky=sky)
     si = shape.ray_intersect(ray, hf_amd.RayFlags.All)
     valid = si.is_valid()
     if film is not None:
+        assert not sky, "the sky row goes through the box film"
         samples = hf_amd.direct_lighting(si, ray, lights, albedo=1.0, spp=1)          # [K, n]
         images = hf_amd.film_gaussian(samples, film[0], film[1], film[2])
         return images, torch.where(valid, si.t, torch.zeros_like(si.t)), valid
@@ -67,6 +82,7 @@ def render(shape, ray, lights, spp, shadows=False, silhouette=False, aux=8, kapp
             vis = torch.stack([~shape.ray_test(si.spawn_ray(l[:3])) for l in lights]).to(torch.uint8)
     # diffuse direct lighting + box-filter film on the wavefront (hf_direct_lighting): [K, pixels]
     images = hf_amd.direct_lighting(si, ray, lights, albedo=1.0, spp=spp, vis=vis)
+    images = add_sky(images, shape, si, ray, spp, sky, ray_index=ray_index)
     depth = torch.where(valid, si.t, torch.zeros_like(si.t))
     return images, depth, valid
 
@@ -79,8 +95,9 @@ def centred_error(h, target):
 
 
 def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=True, seed=0, shadows=False,
-        depth_weight=0.0, silhouette=False, aux=8, kappa=2e4, gaussian_film=False, virtual_ranks=0, record=None):
-    """record (optional list): receives the height texture after every step (trajectory comparisons in the tests)"""
+        depth_weight=0.0, silhouette=False, aux=8, kappa=2e4, gaussian_film=False, virtual_ranks=0, record=None, sky=0.0):
+    """record (optional list): receives the height texture after every step (trajectory comparisons in the tests);
+    sky: radiance of a constant environment added to the rendered and the target images (0: none)"""
     import torch.distributed as dist
     dev = torch.device(device)
     lights = torch.cat([LIGHTS / LIGHTS.norm(dim=1, keepdim=True), torch.full((len(LIGHTS), 1), math.pi)], 1)  # E = pi
@@ -106,8 +123,10 @@ def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=Tr
         ray = hf_amd.Ray3f(rays[0:3], rays[3:6], rays[6])
         flm = (hf_amd.workload.film_positions(film, film, spp, dev, seed=seed), film, film) if gaussian_film else None
         with torch.no_grad():
-            tgt_img, tgt_depth, tgt_valid = render(target, ray, lights, spp, shadows, film=flm)
-        rid = hf_amd.workload.ray_indices(film, film, spp, dev, pixels) if silhouette else None
+            # (the sky samples of a shard are those of the whole film: keyed by the global sample index)
+            sky_id = hf_amd.workload.ray_indices(film, film, spp, dev, pixels) if (sky and pixels is not None) else None
+            tgt_img, tgt_depth, tgt_valid = render(target, ray, lights, spp, shadows, film=flm, ray_index=sky_id, sky=sky)
+        rid = hf_amd.workload.ray_indices(film, film, spp, dev, pixels) if silhouette else sky_id
         shards.append((ray, flm, tgt_img, tgt_depth, tgt_valid, rid))
     shape = hf_amd.Heightfield(heightfield=torch.full_like(target_h, 0.5), max_height=0.5)
     shape.heightfield.requires_grad_(True)
@@ -120,7 +139,7 @@ def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=Tr
         total = 0.0
         for ray, flm, tgt_img, tgt_depth, tgt_valid, rid in shards:    # (backward accumulates into heightfield.grad)
             images, depth, valid = render(shape, ray, lights, spp, shadows, silhouette, aux, kappa, film=flm,
-                                          ray_index=rid)
+                                          ray_index=rid, sky=sky)
             both = valid & tgt_valid
             # the multi-light renders only (configs[4]); mean over the pixels of the WHOLE film: shard losses add up
             loss = ((images - tgt_img) ** 2).sum() / npix_total
@@ -264,6 +283,7 @@ if __name__ == "__main__":
     ap.add_argument("--aux", type=int, default=8, help="auxiliary rays per primary ray of --silhouette")
     ap.add_argument("--gaussian-film", action="store_true", help="Gaussian reconstruction filter instead of the box film")
     ap.add_argument("--virtual-ranks", type=int, default=0, help="render the tile partition of V ranks on this one device")
+    ap.add_argument("--sky", type=float, default=0.0, help="radiance of a constant environment (0: none; hf_sky_lighting)")
     ap.add_argument("--captured", action="store_true", help="one step captured into a HIP graph and replayed (run_captured)")
     a = ap.parse_args()
     if a.captured:
@@ -280,7 +300,7 @@ if __name__ == "__main__":
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend, rank=int(os.environ["RANK"]), world_size=world)
     run(a.grid, a.film, a.spp, a.steps, a.lr, shadows=a.shadows, depth_weight=a.depth_weight, silhouette=a.silhouette,
-        aux=a.aux, gaussian_film=a.gaussian_film, virtual_ranks=a.virtual_ranks,
+        aux=a.aux, gaussian_film=a.gaussian_film, virtual_ranks=a.virtual_ranks, sky=a.sky,
         verbose=int(os.environ.get("RANK", "0")) == 0)
     if world > 1:
         dist.destroy_process_group()

@@ -45,7 +45,9 @@
  *     entry (they synchronise); hf_set_face_normals and hf_set_area_sampling (refused with HF_EINVAL), hf_surface_area
  *     and, with smooth shading or area sampling, hf_set_transform (they synchronise).  hf_sample_position and its
  *     adjoint / tangent are capturable like the other wavefront entry points (no scratch block), and so are
- *     hf_eval_attribute and its adjoint / tangent (the attribute buffer is the caller's).
+ *     hf_eval_attribute and its adjoint / tangent (the attribute buffer is the caller's).  The four hf_sky_* entries
+ *     are capturable too: hf_sky_lighting traces without a work counter (one workgroup per 256 samples), so unlike the
+ *     other trace launches it reserves no scratch block and does not count towards the 32.
  */
 #ifndef HF_H
 #define HF_H
@@ -632,6 +634,68 @@ int hf_point_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3]
                               const float *const p[3], uint32_t n_lights, const hf_point_light_t *lights, float albedo,
                               const uint8_t *const *vis, const float *const dsh_n[3], const float *const dp[3],
                               float *dimage, hf_stream_t stream);
+
+/* ---- next row (emitter sampling): sky lighting, the hemisphere visibility traced in the kernel ----
+ *
+ * Replaces, for diffuse surfaces under a CONSTANT environment of scalar radiance L (src/emitters/constant.cpp:117-145:
+ * direction = square_to_uniform_sphere(sample), pdf 1 / (4 pi), radiance L), the emitter-sampling term of the direct
+ * integrator (direct_reparam.py:150-180: detached emitter sample, MIS weight 1 here, attached BSDF value;
+ * diffuse.cpp:135-140) averaged over K = num_rays emitter samples per wavefront sample, and the shadow rays it traces.
+ *   samples     (r0, r1) = sample_tea_32(sample_tea_32(seed, k)[0], id_i), sample = (r0 >> 9, r1 >> 9) * 2^-23: the
+ *               stream of hf_reparam_* with pair = k; id_i = i or ray_id[i] (device, n uint32, may be NULL);
+ *   direction   w_k = (r cos 2 pi s.x, r sin 2 pi s.x, z), z = 1 - 2 s.y, r = sqrt(max(0, 1 - z^2)) (warp.h:250-255):
+ *               world space, the same for every surface;
+ *   eligible    sample i when t_i is finite and <sh_n_i, -d_i> > 0 (the masks of hf_direct_lighting); direction k of
+ *               an eligible sample is TRACED when <sh_n_i, w_k> > 0;
+ *   shadow ray  SurfaceInteraction::spawn_ray(w_k) (interaction.h:134-136, 161-165): origin p + n s (1 + max|p_c|)
+ *               RayEpsilon with n the geometric normal, s = -1 where <n, w_k> < 0, else 1, RayEpsilon = 1500 * 2^-24
+ *               (math.h:18-22); maxt = +inf -- the environment lies outside the scene, which is this one shape;
+ *   visibility  vis_bits[i], one uint32: bit k is set iff direction k was traced and the any-hit walk found nothing;
+ *               samples that are not eligible get 0;
+ *   value_i     = weight_i * (4 albedo L / K) * sum_k bit_ik <sh_n_i, w_k>       (albedo/pi * cos * L / pdf, averaged)
+ *   image[i / spp] = 1/spp * sum value_i: the box film of hf_direct_lighting, overwritten; n a multiple of spp.
+ * The ray takes the float32 direction (what hf_sky_rays writes); the sums of cosines and of directions are formed from
+ * the same sample's direction in double and rounded once, here and in the adjoint and the tangent.
+ * An unoccluded horizontal plane has expectation albedo * L.  Visibility and the masks are piecewise constant, as in
+ * the rows above: the silhouette part of the shadow gradient is hf_reparam_*'s.
+ * All four entries: 1 <= num_rays <= 32 (hf_sky_rays: k < 32), n < 2^32; NULL pointers (other than those marked
+ * optional), n % spp != 0, num_rays out of range and non-finite radiance / albedo are refused with HF_EINVAL before
+ * anything touches a device.  p, nrm, sh_n, d: 3 device rows of n floats (hf_si_t.p / .n / .sh_n, hf_rays_t.d); t: n.
+ * Callers detect the entries by their symbols (HF_VERSION is unchanged).
+ *
+ * hf_sky_rays materialises shadow ray k of every sample (out_o, out_d: 3 rows of n floats; out_maxt: n floats, +inf
+ * for a traced lane and -1 -- a miss -- for every other, as hf_reparam_aux_rays marks inactive lanes): the two-call
+ * sequence hf_sky_rays + hf_ray_test that hf_sky_lighting equals bit for bit.  Takes no field handle. */
+int hf_sky_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                const float *const d[3], const float *t, uint32_t k, uint32_t seed, const uint32_t *ray_id,
+                float *const out_o[3], float *const out_d[3], float *out_maxt, hf_stream_t stream);
+/* The fused launch: reads a sample's record once, draws its K directions, runs the per-lane any-hit walk for each
+ * traced one and writes vis_bits[i] (n uint32, may be NULL = not wanted) and the film; no ray and no per-ray hit
+ * byte goes to memory.  A batch of 64 samples without an eligible one (the part of an image beside the terrain) draws
+ * nothing.  Every wave walks per lane, whatever hf_set_ray_coherence says: that state is neither read nor changed.
+ * weight: n floats or NULL (1).  Allocates nothing, never synchronises the host. */
+int hf_sky_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                    const float *const sh_n[3], const float *const d[3], const float *t, const float *weight,
+                    uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, float radiance, float albedo,
+                    float *image, uint32_t *vis_bits, hf_stream_t stream);
+/* Reverse mode with respect to sh_n and weight.  Traces nothing: the directions are drawn again and vis_bits (as
+ * hf_sky_lighting wrote it) is read.  With g = grad_image[i / spp] / spp:
+ *   grad_sh_n[i] = g weight_i (4 albedo L / K) sum_k bit_ik w_k,   grad_weight[i] = g (4 albedo L / K) sum_k bit_ik <sh_n_i, w_k>
+ * both overwritten (grad_weight may be NULL), exact zeros for samples that are not eligible; sums in k order, no
+ * atomics: bitwise the same from launch to launch.  Takes no field handle. */
+int hf_sky_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                            const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
+                            float radiance, float albedo, const uint32_t *vis_bits, const float *grad_image,
+                            float *const grad_sh_n[3], float *grad_weight, hf_stream_t stream);
+/* Forward mode, the transpose of the adjoint: for tangents dsh_n (3 rows of n floats) and dweight (n floats), either
+ * may be NULL (zero),
+ *   dimage[i / spp] = 1/spp sum (4 albedo L / K) (weight_i sum_k bit_ik <dsh_n_i, w_k> + dweight_i sum_k bit_ik <sh_n_i, w_k>)
+ * overwritten.  No atomics for any spp (a power of two <= 64: the film's shuffle tree; otherwise one lane adds the
+ * samples of a pixel in order): bitwise the same from launch to launch.  Takes no field handle. */
+int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                            const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
+                            float radiance, float albedo, const uint32_t *vis_bits, const float *const dsh_n[3],
+                            const float *dweight, float *dimage, hf_stream_t stream);
 
 /* Film with a Gaussian reconstruction filter (the reference's default rfilter, src/rfilters/gaussian.cpp:48-101:
  * w(x) = max(0, exp(-x^2 / (2 stddev^2)) - exp(-r^2 / (2 stddev^2))), r = 4 stddev), splatted as ImageBlock::put does

@@ -1105,6 +1105,96 @@ extern "C" int hf_point_lighting_tangent(size_t n, uint32_t spp, const float *co
                             (const hf_dir_light_t *) lights, albedo, vis, dsh_n, dp, nullptr, dimage, (hipStream_t) stream);
 }
 
+// ---- sky lighting: constant environment, the shadow rays traced inside the lighting kernel ----
+// What the four hf_sky_* entries share: the checks (all of them before anything touches a device) and the argument
+// block.  spp / num_rays / radiance / albedo: the film and the emitter of the three lighting entries (hf_sky_rays
+// passes 1, k + 1, 1, 1: its k must name one of 32 directions).
+static int sky_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                    const float *t, const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
+                    float radiance, float albedo, hf_sky_args &a) {
+    if (!all3(sh_n) || !all3(d) || !t) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 sky directions per sample (got %u)", who, num_rays);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (!isfinite(radiance) || !isfinite(albedo)) return fail(HF_EINVAL, "%s: radiance and albedo must be finite", who);
+    a = {};
+    a.n = n; a.spp = spp; a.num_rays = num_rays; a.seed = seed; a.ray_id = ray_id; a.t = t; a.weight = weight;
+    a.scale = (4.f * albedo * radiance) / (float) num_rays; // albedo/pi * L / pdf, pdf = 1 / (4 pi), averaged over num_rays
+    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
+    return HF_OK;
+}
+
+extern "C" int hf_sky_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                           const float *const d[3], const float *t, uint32_t k, uint32_t seed, const uint32_t *ray_id,
+                           float *const out_o[3], float *const out_d[3], float *out_maxt, hf_stream_t stream) {
+    const char *fn = "hf_sky_rays";
+    hf_sky_args a;
+    if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
+    const int rc = sky_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, 1.f, 1.f, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.k = k; a.out_maxt = out_maxt;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
+    hf_launch_sky(3, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_sky_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                               const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                               const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                               const uint32_t *ray_id, float radiance, float albedo, float *image, uint32_t *vis_bits,
+                               hf_stream_t stream) {
+    const char *fn = "hf_sky_lighting";
+    hf_sky_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = sky_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, radiance, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = image; a.vis_bits = vis_bits;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    hf_launch_sky(0, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_sky_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                       const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                                       const uint32_t *ray_id, float radiance, float albedo, const uint32_t *vis_bits,
+                                       const float *grad_image, float *const grad_sh_n[3], float *grad_weight,
+                                       hf_stream_t stream) {
+    const char *fn = "hf_sky_lighting_adjoint";
+    hf_sky_args a;
+    const int rc = sky_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, radiance, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits || !grad_image || !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.gimg = grad_image; a.gw = grad_weight;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n[c];
+    hf_launch_sky(1, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                       const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                                       const uint32_t *ray_id, float radiance, float albedo, const uint32_t *vis_bits,
+                                       const float *const dsh_n[3], const float *dweight, float *dimage,
+                                       hf_stream_t stream) {
+    const char *fn = "hf_sky_lighting_tangent";
+    hf_sky_args a;
+    const int rc = sky_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, radiance, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits || !dimage) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.image = dimage; a.dw = dweight;
+    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    hf_launch_sky(2, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- Gaussian reconstruction filter (film) ------------------------------------------------------
 static int splat_args(const char *who, size_t n, uint32_t channels, const float *pos_x, const float *pos_y,
                       uint32_t width, uint32_t height, float stddev, hf_splat_args &a) {

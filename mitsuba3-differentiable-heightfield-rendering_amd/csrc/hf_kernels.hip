@@ -3341,8 +3341,9 @@ __device__ __forceinline__ v3 light_dir(const hf_lights_dev &L, uint32_t k, v3 p
 // the box-filter film: sample i's value c of light k, averaged over the spp samples of its pixel into image[k * npix + pixel].
 // spp a power of two: a butterfly over the g = min(spp, 64) lanes of a pixel (DPP within rows of 16, cross-lane beyond),
 // then one store (the wave holds whole pixels) or atomic (several waves per pixel); otherwise one atomic per sample
+// (tid: the thread's index in its workgroup, or anything equal to it modulo 64)
 __device__ __forceinline__ void film_pixel(float *image, float c, uint32_t k, size_t npix, size_t i, uint32_t spp, bool in,
-                                           bool pow2, uint32_t g, float inv_spp) {
+                                           bool pow2, uint32_t g, float inv_spp, uint32_t tid = threadIdx.x) {
     if (pow2) {
         if (g > 1u) c += HF_DPP_ADD(c, 0xB1);   // quad_perm [1,0,3,2]
         if (g > 2u) c += HF_DPP_ADD(c, 0x4E);   // quad_perm [2,3,0,1]
@@ -3350,7 +3351,7 @@ __device__ __forceinline__ void film_pixel(float *image, float c, uint32_t k, si
         if (g > 8u) c += HF_DPP_ADD(c, 0x140);  // row_mirror: the other half row
         if (g > 16u) c += __shfl_xor(c, 16);
         if (g > 32u) c += __shfl_xor(c, 32);
-        if (in && (threadIdx.x & (g - 1u)) == 0u) {
+        if (in && (tid & (g - 1u)) == 0u) {
             if (spp <= 64u) image[k * npix + i / spp] = c * inv_spp;
             else            atomicAdd(&image[k * npix + i / spp], c * inv_spp);
         }
@@ -3665,6 +3666,233 @@ void hf_launch_direct_tangent(size_t n, uint32_t spp, const float *const sh_n[3]
     const dim3 grid((unsigned) ((n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
     hipLaunchKernelGGL(p ? hf_direct_tangent_kernel<true> : hf_direct_tangent_kernel<false>, grid, block, 0, stream, n, spp,
                        f3ptr(sh_n), f3ptr(d), t, f3ptr(p), lights, f3ptr(dsh_n), f3ptr(dp), dweight, dimage);
+}
+
+// ---------------------------------------------------------------------------------
+// Sky lighting (include/hf.h hf_sky_*): diffuse surface under a constant environment, the K = num_rays emitter
+// samples of every wavefront sample drawn, traced (any hit, per lane) and reduced in ONE launch.  One lane per sample,
+// `k` a scalar loop with the lanes predicated; nothing of a shadow ray goes to memory: per sample 56 B in (p, n, sh_n,
+// d, t, + weight, ray_id) and one visibility word + the film contribution out.
+// ---------------------------------------------------------------------------------
+// direction k of the sample with stream id `id`: square_to_uniform_sphere (warp.h:250-255) of the TEA sample
+// (the stream of aux_sample with pair = k)
+__device__ __forceinline__ void sky_sample(uint32_t seed, uint32_t k, uint32_t id, float &sx, float &sy) {
+    uint32_t key, unused, r0, r1;
+    tea32(seed, k, key, unused);
+    tea32(key, id, r0, r1);
+    sx = (float) (r0 >> 9) * (1.0f / 8388608.0f); sy = (float) (r1 >> 9) * (1.0f / 8388608.0f);
+}
+__device__ __forceinline__ v3 sky_dir(uint32_t seed, uint32_t k, uint32_t id) {
+    float sx, sy;
+    sky_sample(seed, k, id, sx, sy);
+    const float z = __builtin_fmaf(-2.f, sy, 1.f);
+    const float r = __builtin_sqrtf(fmaxf(__builtin_fmaf(-z, z, 1.f), 0.f));
+    float sn, cs;
+    sincospif(2.f * sx, &sn, &cs);
+    return mk3(r * cs, r * sn, z);
+}
+// Interaction::offset_p (interaction.h:161-165) without the direction: (1 + max|p|) RayEpsilon, RayEpsilon = 1500 * 2^-24
+__device__ __forceinline__ float sky_offset(v3 p) {
+    return (1.f + fmaxf(fmaxf(__builtin_fabsf(p.x), __builtin_fabsf(p.y)), __builtin_fabsf(p.z))) * 8.940696716308594e-05f;
+}
+// origin of spawn_ray(w) (interaction.h:134-136): p moved along the geometric normal to the side w points to
+__device__ __forceinline__ v3 sky_origin(v3 p, v3 gn, float mag, v3 w) {
+    return fma3(gn, dot3(gn, w) < 0.f ? -mag : mag, p);
+}
+// the masks of hf_direct_kernel: a hit seen from the front (diffuse.cpp:137)
+__device__ __forceinline__ bool sky_eligible(float t, v3 sn, v3 d) { return (t != __builtin_inff()) && (-dot3(sn, d) > 0.f); }
+
+// The same direction in double, for the SHADING sums (the cosines of the forward, the sums of directions of the
+// derivative kernels): a float direction is 1e-7 off, which is the whole error of a grazing cosine and of a gradient
+// component that is small because the horizontal components of a hemisphere of unit vectors cancel; drawn and added
+// in double and rounded once, what is left is the rounding of the result.  The RAYS use the float direction.
+struct hf_d3 { double x, y, z; };
+__device__ __forceinline__ hf_d3 sky_dir_f64(uint32_t seed, uint32_t k, uint32_t id) {
+    float sx, sy;
+    sky_sample(seed, k, id, sx, sy);
+    const double z = 1.0 - 2.0 * (double) sy;
+    const double r = sqrt(fmax(1.0 - z * z, 0.0));
+    // sin / cos of pi x, x = 2 sx in [0, 2): the quadrant q = round(2 x) is taken off exactly, |pi t| <= pi / 4 is left
+    // to two Taylor sums whose first dropped terms are 7e-12 and 4e-13 (a dozen fmas and few registers: the library's
+    // sincospi, correct to the last bit of a double, costs the forward kernel 25 spilled registers)
+    const double x = 2.0 * (double) sx, q = rint(2.0 * x), t = x - 0.5 * q;
+    const double a = 3.141592653589793 * t, a2 = a * a;
+    double ps = -1.0 / 39916800.0, pc = 1.0 / 479001600.0;
+    ps = fma(ps, a2, 1.0 / 362880.0); ps = fma(ps, a2, -1.0 / 5040.0); ps = fma(ps, a2, 1.0 / 120.0);
+    ps = fma(ps, a2, -1.0 / 6.0); ps = fma(ps, a2, 1.0); ps *= a;
+    pc = fma(pc, a2, -1.0 / 3628800.0); pc = fma(pc, a2, 1.0 / 40320.0); pc = fma(pc, a2, -1.0 / 720.0);
+    pc = fma(pc, a2, 1.0 / 24.0); pc = fma(pc, a2, -0.5); pc = fma(pc, a2, 1.0);
+    const int qi = (int) q & 3;
+    const double sn = qi == 0 ? ps : qi == 1 ? pc : qi == 2 ? -ps : -pc;
+    const double cs = qi == 0 ? pc : qi == 1 ? -ps : qi == 2 ? -pc : ps;
+    return hf_d3{ r * cs, r * sn, z };
+}
+__device__ __forceinline__ double sky_dot_f64(v3 a, hf_d3 w) { return (double) a.x * w.x + (double) a.y * w.y + (double) a.z * w.z; }
+
+typedef const __attribute__((address_space(4))) hf_sky_args *hf_sky_kargs;
+
+#ifndef HF_SKY_WAVES
+#define HF_SKY_WAVES 6 // resident waves per SIMD (the lean any-hit instantiation's)
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_SKY_WAVES) void hf_sky_kernel(hf_sky_args a) {
+    const hf_dev_field &f = a.f;
+    // n < 2^32 (hf_sky_lighting): the sample index is ONE register across the walk, and everything else about the
+    // sample's place (the clamped index, its lane) is derived from it again where it is needed
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    const v3 sn = mk3(a.sh_n[0][ii], a.sh_n[1][ii], a.sh_n[2][ii]);
+    bool elig;
+    {
+        const v3 d = mk3(a.d[0][ii], a.d[1][ii], a.d[2][ii]);
+        elig = in && sky_eligible(a.t[ii], sn, d);
+    }
+    float acc = 0.f;    // sum over the visible directions of <sh_n, w_k> (sky_dir_f64), in k order
+    uint32_t bits = 0u; // bit k: direction k was traced and is unoccluded
+    if (__ballot(elig) != 0ull) { // wave-uniform: a batch without an eligible sample (the part of an image beside the terrain) draws nothing
+        const v3 p = mk3(a.p[0][ii], a.p[1][ii], a.p[2][ii]);
+        const v3 gn = mk3(a.nrm[0][ii], a.nrm[1][ii], a.nrm[2][ii]);
+        const uint32_t id = a.ray_id ? a.ray_id[ii] : ii;
+        const float mag = sky_offset(p);
+        // (launch constants of the loop are read from the kernarg segment where they are used, as in hf_trace_kernel)
+        hf_sky_kargs ka = (hf_sky_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll 1
+        for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+            asm volatile("" : "+s"(ka)); // opaque per direction: the kernarg loads stay inside the loop
+            // the cosine that is added (sky_dir_f64) first, and finished before the ray is begun (the id goes through
+            // the same opaque statement): its doubles are dead when setup_ray's registers fill, one float is held across the walk
+            v3 snd = sn; // (opaque: the conversions of sh_n to double are otherwise hoisted out of the loop, six registers held across the walk)
+            asm volatile("" : "+v"(snd.x), "+v"(snd.y), "+v"(snd.z));
+            float co = (float) sky_dot_f64(snd, sky_dir_f64(ka->seed, k, id));
+            uint32_t idr = id;
+            asm volatile("" : "+v"(co), "+v"(idr));
+            const v3 w = sky_dir(ka->seed, k, idr);
+            const bool traced = elig && dot3(sn, w) > 0.f;
+            hf_hit best;
+            best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
+            hf_ray_state rs = {}; // fully defined on every path
+            bool alive;
+            {
+                const hf_dev_field f0 = load_field(&ka->f);
+                alive = traced && setup_ray(f0, f0.mip[1], sky_origin(p, gn, mag, w), w, __builtin_inff(), rs);
+            }
+            if (alive) { // the per-lane walk from the root, as an incoherent wave of hf_trace_kernel takes it
+                float thi = rs.thi;
+                hf_src_global src;
+                src.mip = f.mip; src.shear = f.shear; src.h = f.h; src.top = f.top; src.W = f.W;
+                const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
+                (void) walk_subtree<true>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
+            }
+            if (traced && !best.hit) { bits |= 1u << k; acc += co; }
+            if (k + 1u >= ka->num_rays) break;
+        }
+    }
+    // (the output pointers: loaded here, not before the walk)
+    hf_sky_kargs ko = (hf_sky_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    float c = 0.f;
+    if (elig) { // (eligible: in range)
+        const float *weight = ko->weight;
+        c = ko->scale * acc;
+        if (weight) c *= weight[i];
+    }
+    uint32_t *vis_bits = ko->vis_bits;
+    if (in && vis_bits) vis_bits[i] = bits;
+    const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+    film_pixel(ko->image, c, 0u, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+}
+
+// shadow ray a.k of every sample, materialised: what hf_sky_kernel traces for that direction, bit for bit
+__global__ __launch_bounds__(HF_BLOCK) void hf_sky_rays_kernel(hf_sky_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    const v3 w = sky_dir(a.seed, a.k, a.ray_id ? a.ray_id[i] : (uint32_t) i);
+    const bool traced = sky_eligible(a.t[i], sn, d) && dot3(sn, w) > 0.f;
+    const v3 o = sky_origin(p, gn, sky_offset(p), w);
+    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
+    a.out_d[0][i] = w.x; a.out_d[1][i] = w.y; a.out_d[2][i] = w.z;
+    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+}
+
+// Reverse mode of hf_sky_kernel with respect to sh_n and weight: nothing is traced, the directions are drawn again and
+// the visibility word read.  Sums in k order, no atomics.
+__global__ __launch_bounds__(HF_BLOCK) void hf_sky_adjoint_kernel(hf_sky_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    v3 g = mk3(0.f, 0.f, 0.f);
+    float gw = 0.f;
+    if (sky_eligible(a.t[i], sn, d)) {
+        const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+        double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0;
+        for (uint32_t k = 0; k < a.num_rays; ++k) {
+            if ((bits >> k) & 1u) {
+                const hf_d3 w = sky_dir_f64(a.seed, k, id);
+                sx += w.x; sy += w.y; sz += w.z;
+                sc += sky_dot_f64(sn, w);
+            }
+        }
+        const float c = (a.gimg[i / a.spp] * (1.0f / (float) a.spp)) * a.scale;
+        g = mk3((float) sx, (float) sy, (float) sz) * (a.weight ? c * a.weight[i] : c);
+        gw = c * (float) sc;
+    }
+    a.gn[0][i] = g.x; a.gn[1][i] = g.y; a.gn[2][i] = g.z;
+    if (a.gw) a.gw[i] = gw;
+}
+
+// forward mode: the tangent of sample i's value for tangents dn of sh_n and dw of weight (NULL: zero)
+__device__ __forceinline__ float sky_tangent_value(const hf_sky_args &a, size_t i) {
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    if (!sky_eligible(a.t[i], sn, d)) return 0.f;
+    const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    double sd = 0.0, sc = 0.0;
+    for (uint32_t k = 0; k < a.num_rays; ++k) {
+        if ((bits >> k) & 1u) {
+            const hf_d3 w = sky_dir_f64(a.seed, k, id);
+            sd += sky_dot_f64(dn, w);
+            sc += sky_dot_f64(sn, w);
+        }
+    }
+    return (float) ((double) a.scale * ((double) (a.weight ? a.weight[i] : 1.f) * sd + (double) (a.dw ? a.dw[i] : 0.f) * sc));
+}
+// PIXEL = false: one lane per sample and the primal's film (spp a power of two <= 64: its shuffle tree, one store per
+// pixel); PIXEL = true (any other spp): one lane per pixel adds its samples in order -- no atomics either way
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sky_tangent_kernel(hf_sky_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    if (PIXEL) {
+        if (i >= a.n / spp) return;
+        float c = 0.f;
+        for (uint32_t s = 0; s < spp; ++s) c += sky_tangent_value(a, i * spp + s);
+        a.image[i] = c * (1.0f / (float) spp);
+    } else {
+        const bool in = i < a.n;
+        const float c = sky_tangent_value(a, in ? i : a.n - 1);
+        film_pixel(a.image, in ? c : 0.f, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
+    }
+}
+
+static bool sky_tree_film(uint32_t spp) { return (spp & (spp - 1u)) == 0u && spp <= 64u; }
+
+void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    if (mode == 0) {
+        if (!sky_tree_film(a.spp)) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths of film_pixel
+        hipLaunchKernelGGL(hf_sky_kernel, grid, block, 0, stream, a);
+    } else if (mode == 1) {
+        hipLaunchKernelGGL(hf_sky_adjoint_kernel, grid, block, 0, stream, a);
+    } else if (mode == 2) {
+        if (sky_tree_film(a.spp)) hipLaunchKernelGGL(hf_sky_tangent_kernel<false>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(hf_sky_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
+    } else {
+        hipLaunchKernelGGL(hf_sky_rays_kernel, grid, block, 0, stream, a);
+    }
 }
 
 // ---- warped-area reparameterisation: per-sample kernels (helpers: above hf_adjoint_kernel) ----

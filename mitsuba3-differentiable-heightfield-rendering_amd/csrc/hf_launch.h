@@ -64,6 +64,24 @@ void hf_launch_direct_tangent(size_t n, uint32_t spp, const float *const sh_n[3]
                               const float *t, const float *const p[3], const hf_lights_dev &lights,
                               const float *const dsh_n[3], const float *const dp[3], const float *dweight, float *dimage,
                               hipStream_t stream);
+// ---- sky lighting (hf_sky_rays, hf_sky_lighting / _adjoint / _tangent): the one argument of its four kernels ----
+struct hf_sky_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, num_rays, seed, k;         // k: hf_sky_rays' direction
+    float scale;                             // 4 albedo radiance / num_rays
+    const float *p[3], *nrm[3];              // si.p, si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight;
+    const uint32_t *ray_id;                  // optional: the id of sample i in the sample streams (NULL: i)
+    float *image;                            // forward: image; tangent: dimage
+    uint32_t *vis_bits;                      // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    const float *gimg; float *gn[3], *gw;    // adjoint
+    const float *dn[3], *dw;                 // tangent inputs (NULL: zero)
+};
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is the per-lane any-hit walk with the samples
+// drawn in the kernel: no work counter, no scratch block
+void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream);
 struct hf_splat_args {
     size_t n;
     uint32_t channels, width, height;

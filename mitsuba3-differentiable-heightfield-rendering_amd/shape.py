@@ -1407,6 +1407,91 @@ def point_lighting(si, ray, lights, albedo=1.0, spp=1, vis=None):
     return _PointLightingOp.apply(si.sh_frame.n, si.p, ray.d, si.t, lights, float(albedo), int(spp), vis)
 
 
+class _SkyLightingOp(torch.autograd.Function):
+    """(image, visibility words) of hf_sky_lighting; backward = hf_sky_lighting_adjoint (gradients of sh_n and weight),
+    jvp = hf_sky_lighting_tangent.  Both read the visibility word the forward saved and trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, sn, dd, tt, vis, ww=None):
+        """what hf_sky_lighting_adjoint / _tangent start with"""
+        spp, num_rays, seed, rid, radiance, albedo = ctx.misc
+        return (sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(rid),
+                radiance, albedo, vis.data_ptr())
+
+    @staticmethod
+    def forward(ctx, sh_n, weight, shape, p, nrm, d, t, radiance, albedo, spp, num_rays, seed, ray_index):
+        sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (sh_n, p, nrm, d, t))
+        ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
+        n = sn.shape[1]
+        ctx.misc = (spp, num_rays, seed, ray_index, radiance, albedo)
+        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
+        vis = torch.empty(n, dtype=torch.int32, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_sky_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                              C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(ray_index),
+                                              radiance, albedo, image.data_ptr(), vis.data_ptr(), _stream_of(sn.device)))
+        saved = (sn, dd, tt, vis) if ww is None else (sn, dd, tt, vis, ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(vis)
+        return image, vis
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dweight, *_):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        dn = _f3(dsh_n)[0] if dsh_n is not None else None
+        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 5 and dweight is not None) else None
+        dimage = torch.empty(sn.shape[1] // ctx.misc[0], dtype=torch.float32, device=sn.device)
+        if sn.shape[1]:
+            check(_capi.lib().hf_sky_lighting_tangent(*_SkyLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)), _ptr(dw),
+                                                      dimage.data_ptr(), _stream_of(sn.device)))
+        return dimage, None
+
+    @staticmethod
+    def backward(ctx, grad_image, _grad_vis):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        gi = grad_image.to(dtype=torch.float32).contiguous()
+        gn = torch.empty_like(sn)
+        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 5 else None
+        if sn.shape[1]:
+            check(_capi.lib().hf_sky_lighting_adjoint(*_SkyLightingOp._prefix(ctx, *saved), gi.data_ptr(), C.byref(_p3(gn)),
+                                                      _ptr(gw), _stream_of(sn.device)))
+        return (gn, gw) + (None,) * 11
+
+
+def sky_lighting(shape, si, ray, radiance=1.0, albedo=1.0, spp=1, num_rays=8, seed=0, weight=None, ray_index=None,
+                 return_visibility=False):
+    """Diffuse lighting under a constant environment of scalar ``radiance`` (the reference's ``constant`` emitter) +
+    box-filter film, the shadow rays traced inside the lighting kernel (``hf_sky_lighting``): every sample draws
+    ``num_rays`` (1..32) uniform sphere directions from the TEA stream of ``reparameterize_ray`` (``seed``,
+    ``ray_index``), traces ``si.spawn_ray(direction)`` for those above its shading hemisphere and averages
+    ``albedo/pi * cos * radiance / pdf`` over the unoccluded ones.  Returns the [n // spp] image; with
+    ``return_visibility`` also the [n] int32 visibility words (bit k: direction k was traced and reached the sky).
+    Differentiable with respect to ``si.sh_frame.n`` and ``weight`` ([n], optional); visibility is piecewise constant."""
+    shape._check_ray(ray)
+    image, vis = _SkyLightingOp.apply(si.sh_frame.n, weight, shape, si.p, si.n, ray.d, si.t, float(radiance), float(albedo),
+                                      int(spp), int(num_rays), int(seed), _check_ray_index(ray_index, ray))
+    return (image, vis) if return_visibility else image
+
+
+def sky_rays(si, ray, k, seed=0, ray_index=None):
+    """Shadow ray ``k`` of every sample of ``sky_lighting`` as a Ray3f (``hf_sky_rays``): what the fused kernel traces
+    for that direction, bit for bit.  Lanes it does not trace (no hit, seen from behind, direction below the shading
+    hemisphere) get ``maxt = -1``, a miss."""
+    rid = _check_ray_index(ray_index, ray)
+    sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n = sn.shape[1]
+    o, d = torch.empty_like(pp), torch.empty_like(pp)
+    maxt = torch.empty(n, dtype=torch.float32, device=pp.device)
+    if n:
+        check(_capi.lib().hf_sky_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
+                                      tt.data_ptr(), int(k), int(seed), _ptr(rid), C.byref(_p3(o)), C.byref(_p3(d)),
+                                      maxt.data_ptr(), _stream_of(pp.device)))
+    return Ray3f(o, d, maxt)
+
+
 def _film_splat(values, ps, weight, K, n, width, height, stddev):
     """hf_film_splat of the [K, n] float32 values at ps into a zeroed [K, height * width] image and into weight"""
     image = torch.zeros((K, height * width), dtype=torch.float32, device=ps.device)
