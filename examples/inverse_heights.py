@@ -34,6 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hf_amd  # noqa: E402
 
 SKY_RAYS = 8  # sky directions per sample of --sky
+BOUNCE_SEED = 0x626F  # the bounce directions' sample stream: not the sky's nor the reparameterisation's (both seed 0)
 LIGHTS = torch.tensor([[0.5, 0.2, 0.84], [-0.5, 0.3, 0.81], [0.1, -0.6, 0.79], [0.0, 0.0, 1.0]])
 
 
@@ -47,7 +48,18 @@ def add_sky(images, shape, si, ray, spp, sky, weight=None, ray_index=None):
     return torch.cat([images, row[None]])
 
 
-def render_reparameterized(shape, ray, lights, spp, aux=8, kappa=2e4, seed=0, ray_index=None, sky=0.0):
+def add_bounce(images, shape, si, ray, lights, spp, bounce, weight=None, ray_index=None):
+    """one bounce of diffuse interreflection (hf_bounce_lighting: `bounce` cosine-weighted directions per sample, their
+    closest hits and the shadow rays at those hits traced inside the lighting kernel) added onto the directional rows;
+    bounce = 0: the images as they are"""
+    if not bounce:
+        return images
+    rows = hf_amd.bounce_lighting(shape, si, ray, lights, albedo=1.0, spp=spp, num_rays=bounce, seed=BOUNCE_SEED,
+                                  weight=weight, ray_index=ray_index)
+    return torch.cat([images[:len(lights)] + rows, images[len(lights):]])
+
+
+def render_reparameterized(shape, ray, lights, spp, aux=8, kappa=2e4, seed=0, ray_index=None, sky=0.0, bounce=0):
     """primary rays through reparameterize_ray; per-sample diffuse shading x determinant and the box film in
     hf_direct_lighting (weight row = the determinant); the gradient reaches the heights through hf_adjoint (shading
     normal), the auxiliary rays (reparameterised direction) and the determinant (weight gradient)"""
@@ -58,21 +70,23 @@ def render_reparameterized(shape, ray, lights, spp, aux=8, kappa=2e4, seed=0, ra
     valid = si.is_valid()
     images = hf_amd.direct_lighting(si, ray2, lights, albedo=1.0, spp=spp, weight=det)
     images = add_sky(images, shape, si, ray2, spp, sky, det, ray_index)
+    images = add_bounce(images, shape, si, ray2, lights, spp, bounce, det, ray_index)
     depth = torch.where(valid, si.t, torch.zeros_like(si.t))
     return images, depth, valid
 
 
 def render(shape, ray, lights, spp, shadows=False, silhouette=False, aux=8, kappa=2e4, film=None, ray_index=None,
-           sky=0.0):
+           sky=0.0, bounce=0):
     """film: None = box filter (pixel = mean of its samples, inside hf_direct_lighting); (positions [2, n], width,
     height) = the reference's default Gaussian reconstruction filter (hf_film_splat) on the per-sample values;
-    sky: radiance of a constant environment, rendered as one more image row (box film only)"""
+    sky: radiance of a constant environment, rendered as one more image row (box film only); bounce: directions per
+    sample of one diffuse interreflection, added onto the directional rows (box film only)"""
     if silhouette:
-        return render_reparameterized(shape, ray, lights, spp, aux, kappa, ray_index=ray_index, sky=sky)
+        return render_reparameterized(shape, ray, lights, spp, aux, kappa, ray_index=ray_index, sky=sky, bounce=bounce)
     si = shape.ray_intersect(ray, hf_amd.RayFlags.All)
     valid = si.is_valid()
     if film is not None:
-        assert not sky, "the sky row goes through the box film"
+        assert not sky and not bounce, "the sky and bounce rows go through the box film"
         samples = hf_amd.direct_lighting(si, ray, lights, albedo=1.0, spp=1)          # [K, n]
         images = hf_amd.film_gaussian(samples, film[0], film[1], film[2])
         return images, torch.where(valid, si.t, torch.zeros_like(si.t)), valid
@@ -83,6 +97,7 @@ def render(shape, ray, lights, spp, shadows=False, silhouette=False, aux=8, kapp
     # diffuse direct lighting + box-filter film on the wavefront (hf_direct_lighting): [K, pixels]
     images = hf_amd.direct_lighting(si, ray, lights, albedo=1.0, spp=spp, vis=vis)
     images = add_sky(images, shape, si, ray, spp, sky, ray_index=ray_index)
+    images = add_bounce(images, shape, si, ray, lights, spp, bounce, ray_index=ray_index)
     depth = torch.where(valid, si.t, torch.zeros_like(si.t))
     return images, depth, valid
 
@@ -95,9 +110,11 @@ def centred_error(h, target):
 
 
 def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=True, seed=0, shadows=False,
-        depth_weight=0.0, silhouette=False, aux=8, kappa=2e4, gaussian_film=False, virtual_ranks=0, record=None, sky=0.0):
+        depth_weight=0.0, silhouette=False, aux=8, kappa=2e4, gaussian_film=False, virtual_ranks=0, record=None, sky=0.0,
+        bounce=0):
     """record (optional list): receives the height texture after every step (trajectory comparisons in the tests);
-    sky: radiance of a constant environment added to the rendered and the target images (0: none)"""
+    sky: radiance of a constant environment added to the rendered and the target images (0: none); bounce: directions
+    per sample of one diffuse interreflection added to both (0: none)"""
     import torch.distributed as dist
     dev = torch.device(device)
     lights = torch.cat([LIGHTS / LIGHTS.norm(dim=1, keepdim=True), torch.full((len(LIGHTS), 1), math.pi)], 1)  # E = pi
@@ -123,9 +140,11 @@ def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=Tr
         ray = hf_amd.Ray3f(rays[0:3], rays[3:6], rays[6])
         flm = (hf_amd.workload.film_positions(film, film, spp, dev, seed=seed), film, film) if gaussian_film else None
         with torch.no_grad():
-            # (the sky samples of a shard are those of the whole film: keyed by the global sample index)
-            sky_id = hf_amd.workload.ray_indices(film, film, spp, dev, pixels) if (sky and pixels is not None) else None
-            tgt_img, tgt_depth, tgt_valid = render(target, ray, lights, spp, shadows, film=flm, ray_index=sky_id, sky=sky)
+            # (the sky and bounce samples of a shard are those of the whole film: keyed by the global sample index)
+            keyed = (sky or bounce) and pixels is not None
+            sky_id = hf_amd.workload.ray_indices(film, film, spp, dev, pixels) if keyed else None
+            tgt_img, tgt_depth, tgt_valid = render(target, ray, lights, spp, shadows, film=flm, ray_index=sky_id, sky=sky,
+                                                   bounce=bounce)
         rid = hf_amd.workload.ray_indices(film, film, spp, dev, pixels) if silhouette else sky_id
         shards.append((ray, flm, tgt_img, tgt_depth, tgt_valid, rid))
     shape = hf_amd.Heightfield(heightfield=torch.full_like(target_h, 0.5), max_height=0.5)
@@ -139,7 +158,7 @@ def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=Tr
         total = 0.0
         for ray, flm, tgt_img, tgt_depth, tgt_valid, rid in shards:    # (backward accumulates into heightfield.grad)
             images, depth, valid = render(shape, ray, lights, spp, shadows, silhouette, aux, kappa, film=flm,
-                                          ray_index=rid, sky=sky)
+                                          ray_index=rid, sky=sky, bounce=bounce)
             both = valid & tgt_valid
             # the multi-light renders only (configs[4]); mean over the pixels of the WHOLE film: shard losses add up
             loss = ((images - tgt_img) ** 2).sum() / npix_total
@@ -284,6 +303,8 @@ if __name__ == "__main__":
     ap.add_argument("--gaussian-film", action="store_true", help="Gaussian reconstruction filter instead of the box film")
     ap.add_argument("--virtual-ranks", type=int, default=0, help="render the tile partition of V ranks on this one device")
     ap.add_argument("--sky", type=float, default=0.0, help="radiance of a constant environment (0: none; hf_sky_lighting)")
+    ap.add_argument("--bounce", type=int, default=0, metavar="K",
+                    help="one diffuse interreflection with K directions per sample (0: none; hf_bounce_lighting)")
     ap.add_argument("--captured", action="store_true", help="one step captured into a HIP graph and replayed (run_captured)")
     a = ap.parse_args()
     if a.captured:
@@ -300,7 +321,7 @@ if __name__ == "__main__":
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend, rank=int(os.environ["RANK"]), world_size=world)
     run(a.grid, a.film, a.spp, a.steps, a.lr, shadows=a.shadows, depth_weight=a.depth_weight, silhouette=a.silhouette,
-        aux=a.aux, gaussian_film=a.gaussian_film, virtual_ranks=a.virtual_ranks, sky=a.sky,
+        aux=a.aux, gaussian_film=a.gaussian_film, virtual_ranks=a.virtual_ranks, sky=a.sky, bounce=a.bounce,
         verbose=int(os.environ.get("RANK", "0")) == 0)
     if world > 1:
         dist.destroy_process_group()

@@ -48,6 +48,7 @@
  *     hf_eval_attribute and its adjoint / tangent (the attribute buffer is the caller's).  The four hf_sky_* entries
  *     are capturable too: hf_sky_lighting traces without a work counter (one workgroup per 256 samples), so unlike the
  *     other trace launches it reserves no scratch block and does not count towards the 32.
+ *     The four hf_bounce_* entries are capturable in the same way.
  */
 #ifndef HF_H
 #define HF_H
@@ -696,6 +697,92 @@ int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], 
                             const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
                             float radiance, float albedo, const uint32_t *vis_bits, const float *const dsh_n[3],
                             const float *dweight, float *dimage, hf_stream_t stream);
+
+/* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
+ *
+ * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional
+ * lights (src/emitters/directional.cpp), cut after the second vertex: a DETACHED BSDF sample at the first vertex
+ * (diffuse.cpp:101-143: cosine-weighted direction, weight = albedo), the closest hit q of the spawned ray, and the
+ * emitter-sampling term at q with its own shadow rays; Lr_ind = L * replace_grad(1, bsdf_val / bsdf_val_det)
+ * (prb.py:213-223) makes the cosine at the first vertex differentiable.  Averaged over K = num_rays directions.
+ *   samples     (r0, r1) = sample_tea_32(sample_tea_32(seed, k)[0], id_i), sample = (r0 >> 9, r1 >> 9) * 2^-23: the
+ *               stream of hf_sky_* and hf_reparam_* with pair = k; id_i = i or ray_id[i].  A caller that uses several
+ *               of these rows gives them different seeds;
+ *   direction   wo = square_to_cosine_hemisphere(sample) (warp.h:54-90, 320-328: the concentric disk map, then
+ *               z = safe_sqrt(1 - x^2 - y^2), evaluated as sqrt((1 - |r|) (1 + |r|)) with r the map's radius, the same
+ *               number without the cancellation); w_k = s wo.x + t wo.y + sh_n wo.z with (s, t) = coordinate_system(sh_n)
+ *               (vector.h:116-136).  DEVIATION: the reference rotates with the Gram-Schmidt sh_frame.s / .t of the
+ *               interaction; a cosine lobe does not depend on the rotation about sh_n, so the frame is rebuilt from
+ *               sh_n alone and six input rows are saved.  The sampled directions differ, their distribution does not;
+ *   eligible    sample i when t_i is finite and <sh_n_i, -d_i> > 0 (the masks of hf_direct_lighting); direction k of
+ *               an eligible sample is TRACED when wo.z > 0;
+ *   bounce ray  SurfaceInteraction::spawn_ray(w_k) exactly as hf_sky_rays builds it (interaction.h:134-136, 161-165),
+ *               maxt = +inf; its closest hit (t_q, prim_q) is hf_ray_intersect_preliminary's for that ray, bit for bit;
+ *   2nd vertex  q and n_q: the p and n of hf_compute_surface_interaction for that ray and hit; n_q is the FACE normal
+ *               (after flip_normals) under both shading modes of the handle: the first vertex takes the caller's sh_n,
+ *               flat or smooth, but smoothing the normal of an indirect vertex is a second-order effect and would put
+ *               1-rings of vertices into the fused adjoint.  front_ik = hit and <n_q, -w_k> > 0;
+ *   light l     shadow ray traced when front_ik and <n_q, l_l> > 0: spawn_ray(l_l) from (q, n_q), the same offset
+ *               rule, maxt = +inf; lit_ikl = traced and the any-hit walk finds nothing;
+ *   value       R_ikl = albedo/pi E_l lit_ikl <n_q, l_l>,  value_il = weight_i (albedo / K) sum_k R_ikl
+ *   image[l][i / spp] = 1/spp * sum value_il: the box film and per-light rows of hf_direct_lighting, overwritten, so
+ *               the rows add onto that function's; n a multiple of spp;
+ *   record      of direction k of sample i at [k * sample_stride + i], sample_stride >= n: hit_prim (uint32) = prim_q
+ *               where the bounce ray hit, 0xFFFFFFFF where it missed or was not traced; lit_bits (uint8): bit l set
+ *               iff lit_ikl.  Either pointer may be NULL in the forward (not wanted).
+ * A bounce ray that misses contributes nothing: light from the environment is hf_sky_lighting's term.  The rays take
+ * the float32 direction; the derivative kernels form w_k / z_k and their sums from the same sample in double and round
+ * once (1 - |p|^2 cancels near the rim of the disk).  Not differentiated: visibility and the masks (piecewise
+ * constant; silhouettes are hf_reparam_*'s) and to_world (no grad_to_world / d_to_world here).
+ * All four entries: 1 <= num_rays <= 32 (hf_bounce_rays: k < 32), n < 2^32, 1 <= n_lights <= HF_MAX_LIGHTS (lights in
+ * HOST memory); NULL pointers other than those marked optional, a NULL row of a row triple, n % spp != 0, spp == 0,
+ * sample_stride < n with a record pointer given, non-finite albedo, irradiance or light direction are refused with
+ * HF_EINVAL before anything touches a device; n == 0 is legal.  They allocate nothing, never synchronise the host and
+ * are capturable (no work counter, no scratch block).  Callers detect the entries by their symbols (HF_VERSION is
+ * unchanged).
+ *
+ * hf_bounce_rays materialises ray k of every sample (out_o, out_d: 3 rows of n floats; out_maxt: n floats, +inf for a
+ * lane the fused kernel traces and -1 -- a miss -- for every other).  to_light == NULL: the bounce ray.  to_light = 3
+ * HOST floats: the shadow ray from that bounce ray's hit towards to_light; this form traces the bounce ray. */
+int hf_bounce_rays(const hf_field_t *hf, size_t n, const float *const p[3], const float *const nrm[3],
+                   const float *const sh_n[3], const float *const d[3], const float *t, uint32_t k, uint32_t seed,
+                   const uint32_t *ray_id, const float *to_light, float *const out_o[3], float *const out_d[3],
+                   float *out_maxt, hf_stream_t stream);
+/* The fused launch: reads a sample's record once, draws its K directions, walks each traced one to its closest hit per
+ * lane, shades the hit under every light with a per-lane any-hit walk, and writes the two record words and the film.
+ * A batch of 64 samples without an eligible one traces nothing.  Every wave walks per lane, whatever
+ * hf_set_ray_coherence says.  weight: n floats or NULL (1).  image: n_lights * (n / spp) floats. */
+int hf_bounce_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                       const float *const sh_n[3], const float *const d[3], const float *t, const float *weight,
+                       uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t n_lights,
+                       const hf_dir_light_t *lights, float albedo, float *image, uint32_t *hit_prim, uint8_t *lit_bits,
+                       size_t sample_stride, hf_stream_t stream);
+/* Reverse mode.  Traces nothing: the directions are drawn again, the record is read and n_q recomputed from hit_prim
+ * and the heights.  With g_l = grad_image[l][i / spp] / spp, c = albedo / K, G_ik = sum_l g_l R_ikl:
+ *   grad_sh_n[i]   = weight_i c sum_k G_ik w_k / z_k        (z_k = the sampled wo.z)
+ *   grad_weight[i] = c sum_k G_ik
+ * both overwritten, exact zeros for samples that are not eligible, sums in k order without atomics; and for every
+ * record with lit_bits != 0 the gradient gN = weight_i c albedo/pi sum_l g_l E_l lit_ikl l_l of n_q goes through the
+ * flip, the normalisation and the cross product to the three heights of prim_q, ACCUMULATED into grad_heights[H W]
+ * with float atomics.  grad_sh_n, grad_weight, grad_heights may each be NULL, not all of them. */
+int hf_bounce_lighting_adjoint(const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
+                               const float *const d[3], const float *t, const float *weight, uint32_t num_rays,
+                               uint32_t seed, const uint32_t *ray_id, uint32_t n_lights, const hf_dir_light_t *lights,
+                               float albedo, const uint32_t *hit_prim, const uint8_t *lit_bits, size_t sample_stride,
+                               const float *grad_image, float *const grad_sh_n[3], float *grad_weight,
+                               float *grad_heights, hf_stream_t stream);
+/* Forward mode, the transpose of the adjoint: for tangents dsh_n (3 rows of n floats), dweight (n floats) and dheights
+ * (H W floats), each NULL = zero,
+ *   dimage[l][i / spp] = 1/spp sum c (weight_i <dsh_n_i, sum_k R_ikl w_k / z_k> + dweight_i sum_k R_ikl
+ *                                      + weight_i sum_k albedo/pi E_l lit_ikl <dn_q, l_l>)
+ * overwritten.  No atomics for any spp (a power of two <= 64: the film's shuffle tree; otherwise one lane adds the
+ * samples of a pixel in order): bitwise the same from launch to launch. */
+int hf_bounce_lighting_tangent(const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
+                               const float *const d[3], const float *t, const float *weight, uint32_t num_rays,
+                               uint32_t seed, const uint32_t *ray_id, uint32_t n_lights, const hf_dir_light_t *lights,
+                               float albedo, const uint32_t *hit_prim, const uint8_t *lit_bits, size_t sample_stride,
+                               const float *const dsh_n[3], const float *dweight, const float *dheights, float *dimage,
+                               hf_stream_t stream);
 
 /* Film with a Gaussian reconstruction filter (the reference's default rfilter, src/rfilters/gaussian.cpp:48-101:
  * w(x) = max(0, exp(-x^2 / (2 stddev^2)) - exp(-r^2 / (2 stddev^2))), r = 4 stddev), splatted as ImageBlock::put does

@@ -4,5 +4,5 @@ from . import build, workload  # noqa: F401
 from ._capi import HfError  # noqa: F401
 from .shape import (Adam, DirectionSample3f, Frame3f, Heightfield, ParamFlags, PositionSample3f,  # noqa: F401
                     PreliminaryIntersection3f, Ray3f, RayFlags, SurfaceInteraction3f, allreduce_gradient,
-                    direct_lighting, film_gaussian, point_lighting, reparameterize_ray,
+                    bounce_lighting, bounce_rays, direct_lighting, film_gaussian, point_lighting, reparameterize_ray,
                     reparameterize_ray_adjoint, reparameterize_ray_tangent, sky_lighting, sky_rays)

@@ -1195,6 +1195,134 @@ extern "C" int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *cons
     return HF_OK;
 }
 
+// ---- bounce lighting: one diffuse interreflection, both rays traced inside the lighting kernel ----
+// What the four hf_bounce_* entries share: the checks (all of them before anything touches a device) and the argument
+// block.  hf_bounce_rays passes spp 1, num_rays k + 1, albedo 1 and either no light or its one direction.
+static int bounce_args(const char *who, const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
+                       const float *const d[3], const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                       const uint32_t *ray_id, uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
+                       hf_bounce_args &a) {
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", who);
+    if (!all3(sh_n) || !all3(d) || !t || !lights) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 bounce directions per sample (got %u)", who, num_rays);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (n_lights == 0 || n_lights > HF_MAX_LIGHTS)
+        return fail(HF_EINVAL, "%s: 1..%d lights supported (got %u)", who, HF_MAX_LIGHTS, n_lights);
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    a = {};
+    for (uint32_t l = 0; l < n_lights; ++l) {
+        if (!isfinite(lights[l].irradiance) || !isfinite(lights[l].to_light[0]) || !isfinite(lights[l].to_light[1]) ||
+            !isfinite(lights[l].to_light[2]))
+            return fail(HF_EINVAL, "%s: light %u is not finite", who, l);
+        for (int c = 0; c < 3; ++c) a.l[l][c] = lights[l].to_light[c];
+        a.w[l] = (albedo * 0.31830988618379067154f) * lights[l].irradiance; // dr::InvPi
+    }
+    a.n = n; a.spp = spp; a.num_rays = num_rays; a.seed = seed; a.ray_id = ray_id; a.t = t; a.weight = weight;
+    a.n_lights = n_lights;
+    a.scale = albedo / (float) num_rays; // the BSDF weight (cosine and pdf cancel), averaged over num_rays
+    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
+    return HF_OK;
+}
+// the record of the three lighting entries (need: the adjoint and the tangent read it)
+static int bounce_record(const char *who, size_t n, const uint32_t *hit_prim, const uint8_t *lit_bits, size_t sample_stride,
+                         bool need, hf_bounce_args &a) {
+    if (need && (!hit_prim || !lit_bits)) return fail(HF_EINVAL, "%s: NULL record", who);
+    if ((hit_prim || lit_bits) && sample_stride < n)
+        return fail(HF_EINVAL, "%s: sample_stride (%zu) below n (%zu)", who, sample_stride, n);
+    a.hit_prim = const_cast<uint32_t *>(hit_prim); a.lit_bits = const_cast<uint8_t *>(lit_bits); a.sample_stride = sample_stride;
+    return HF_OK;
+}
+
+extern "C" int hf_bounce_rays(const hf_field_t *hf, size_t n, const float *const p[3], const float *const nrm[3],
+                              const float *const sh_n[3], const float *const d[3], const float *t, uint32_t k,
+                              uint32_t seed, const uint32_t *ray_id, const float *to_light, float *const out_o[3],
+                              float *const out_d[3], float *out_maxt, hf_stream_t stream) {
+    const char *fn = "hf_bounce_rays";
+    hf_bounce_args a;
+    if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
+    hf_dir_light_t one = { { 0.f, 0.f, 1.f }, 1.f };
+    if (to_light) for (int c = 0; c < 3; ++c) one.to_light[c] = to_light[c];
+    int rc = bounce_args(fn, hf, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, 1, &one, 1.f, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.k = k; a.shadow = to_light ? 1 : 0; a.out_maxt = out_maxt;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
+    hf_launch_bounce(3, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_bounce_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                  const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                  const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                                  const uint32_t *ray_id, uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
+                                  float *image, uint32_t *hit_prim, uint8_t *lit_bits, size_t sample_stride,
+                                  hf_stream_t stream) {
+    const char *fn = "hf_bounce_lighting";
+    hf_bounce_args a;
+    int rc = bounce_args(fn, hf, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, n_lights, lights, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if ((rc = bounce_record(fn, n, hit_prim, lit_bits, sample_stride, false, a))) return rc;
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = image;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    hf_launch_bounce(0, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_bounce_lighting_adjoint(const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
+                                          const float *const d[3], const float *t, const float *weight,
+                                          uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t n_lights,
+                                          const hf_dir_light_t *lights, float albedo, const uint32_t *hit_prim,
+                                          const uint8_t *lit_bits, size_t sample_stride, const float *grad_image,
+                                          float *const grad_sh_n[3], float *grad_weight, float *grad_heights,
+                                          hf_stream_t stream) {
+    const char *fn = "hf_bounce_lighting_adjoint";
+    hf_bounce_args a;
+    int rc = bounce_args(fn, hf, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, n_lights, lights, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!grad_image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
+    if (!grad_sh_n && !grad_weight && !grad_heights) return fail(HF_EINVAL, "%s: no output", fn);
+    if ((rc = bounce_record(fn, n, hit_prim, lit_bits, sample_stride, true, a))) return rc;
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.gimg = grad_image; a.gw = grad_weight; a.gh = grad_heights;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    hf_launch_bounce(1, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_bounce_lighting_tangent(const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
+                                          const float *const d[3], const float *t, const float *weight,
+                                          uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t n_lights,
+                                          const hf_dir_light_t *lights, float albedo, const uint32_t *hit_prim,
+                                          const uint8_t *lit_bits, size_t sample_stride, const float *const dsh_n[3],
+                                          const float *dweight, const float *dheights, float *dimage,
+                                          hf_stream_t stream) {
+    const char *fn = "hf_bounce_lighting_tangent";
+    hf_bounce_args a;
+    int rc = bounce_args(fn, hf, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, n_lights, lights, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!dimage) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
+    if ((rc = bounce_record(fn, n, hit_prim, lit_bits, sample_stride, true, a))) return rc;
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = dimage; a.dw = dweight; a.dh = dheights;
+    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    hf_launch_bounce(2, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- Gaussian reconstruction filter (film) ------------------------------------------------------
 static int splat_args(const char *who, size_t n, uint32_t channels, const float *pos_x, const float *pos_y,
                       uint32_t width, uint32_t height, float stddev, hf_splat_args &a) {

@@ -3895,6 +3895,359 @@ void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream) {
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Bounce lighting (include/hf.h hf_bounce_*): one diffuse interreflection.  Every wavefront sample draws K = num_rays
+// cosine-weighted directions (detached BSDF sample, prb.py:162-226; diffuse.cpp:101-143), traces each to its closest
+// hit, shades that second vertex under the directional lights with shadow rays of its own and reduces into the film:
+// ONE launch, one lane per sample, `k` and the light index scalar loops with the lanes predicated.  Per direction one
+// primitive index and one byte of visibility go to memory and nothing else of the rays, hits or interactions.
+// ---------------------------------------------------------------------------------
+// square_to_cosine_hemisphere (warp.h:54-90, 320-328) of direction k's sample, local frame.  phi / pi = rp / (4 r) is at
+// most 1/4 in magnitude; the other quadrant pair (phi -> pi/2 - phi) swaps sine and cosine.  z = safe_sqrt(1 - |p|^2)
+// is taken as sqrt((1 - |r|) (1 + |r|)): |p| = |r| for the concentric map, r = 2 s - 1 is exact, and the difference
+// 1 - px^2 - py^2 of rounded products would lose z to cancellation near the rim of the disk (2.7e-6 at z = 0.01).
+__device__ __forceinline__ v3 bounce_local(uint32_t seed, uint32_t k, uint32_t id) {
+    float sx, sy;
+    sky_sample(seed, k, id, sx, sy);
+    const float x = __builtin_fmaf(2.f, sx, -1.f), y = __builtin_fmaf(2.f, sy, -1.f);
+    const bool q13 = __builtin_fabsf(x) < __builtin_fabsf(y);
+    const float r = q13 ? y : x, rp = q13 ? x : y;
+    const float a = (x == 0.f && y == 0.f) ? 0.f : 0.25f * rp / r;
+    float sn, cs;
+    sincospif(a, &sn, &cs);
+    const float px = r * (q13 ? sn : cs), py = r * (q13 ? cs : sn);
+    const float ar = __builtin_fabsf(r);
+    return mk3(px, py, __builtin_sqrtf((1.f - ar) * (1.f + ar)));
+}
+// Frame3f(sh_n).to_world with (s, t) = coordinate_system(sh_n)
+__device__ __forceinline__ v3 bounce_world(v3 sn, v3 wo) {
+    v3 s, t;
+    coordinate_system(sn, s, t);
+    return fma3(sn, wo.z, fma3(t, wo.y, s * wo.x));
+}
+// The same direction in double for the SHADING sums of the derivative kernels (w_k / z_k: 1 - |p|^2 cancels near the rim
+// of the disk; see sky_dir_f64).  Returns the world direction, z = the local wo.z.  The RAYS use the float direction.
+__device__ __forceinline__ hf_d3 bounce_dir_f64(v3 sn, uint32_t seed, uint32_t k, uint32_t id, double &z) {
+    float sx, sy;
+    sky_sample(seed, k, id, sx, sy);
+    const double x = 2.0 * (double) sx - 1.0, y = 2.0 * (double) sy - 1.0;
+    const bool q13 = fabs(x) < fabs(y);
+    const double r = q13 ? y : x, rp = q13 ? x : y;
+    const double a = (x == 0.0 && y == 0.0) ? 0.0 : 0.7853981633974483 * rp / r, a2 = a * a; // |a| <= pi / 4: sky_dir_f64's sums
+    double ps = -1.0 / 39916800.0, pc = 1.0 / 479001600.0;
+    ps = fma(ps, a2, 1.0 / 362880.0); ps = fma(ps, a2, -1.0 / 5040.0); ps = fma(ps, a2, 1.0 / 120.0);
+    ps = fma(ps, a2, -1.0 / 6.0); ps = fma(ps, a2, 1.0); ps *= a;
+    pc = fma(pc, a2, -1.0 / 3628800.0); pc = fma(pc, a2, 1.0 / 40320.0); pc = fma(pc, a2, -1.0 / 720.0);
+    pc = fma(pc, a2, 1.0 / 24.0); pc = fma(pc, a2, -0.5); pc = fma(pc, a2, 1.0);
+    const double px = r * (q13 ? ps : pc), py = r * (q13 ? pc : ps);
+    z = sqrt((1.0 - fabs(r)) * (1.0 + fabs(r))); // (as bounce_local)
+    // coordinate_system (vector.h:116-136) in double
+    const double nx = sn.x, ny = sn.y, nz = sn.z, sg = nz >= 0.0 ? 1.0 : -1.0;
+    const double ca = -1.0 / (sg + nz), cb = nx * ny * ca;
+    const hf_d3 s = { sg * (nx * nx * ca) + 1.0, sg * cb, -sg * nx }, t = { cb, ny * ny * ca + sg, -ny };
+    return hf_d3{ s.x * px + t.x * py + nx * z, s.y * px + t.y * py + ny * z, s.z * px + t.z * py + nz * z };
+}
+
+typedef const __attribute__((address_space(4))) hf_bounce_args *hf_bounce_kargs;
+
+// one lane's walk from the root (closest hit, or ANY hit), as an incoherent wave of hf_trace_kernel takes it.  `f`: the
+// kernel's by-value argument; what setup_ray needs of it is read from the kernarg segment again
+template <bool ANY>
+__device__ __forceinline__ void bounce_walk(hf_bounce_kargs ka, const hf_dev_field &f, v3 o, v3 w, bool traced, hf_hit &best) {
+    best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
+    hf_ray_state rs = {}; // fully defined on every path
+    bool alive;
+    {
+        const hf_dev_field f0 = load_field(&ka->f);
+        alive = traced && setup_ray(f0, f0.mip[1], o, w, __builtin_inff(), rs);
+    }
+    if (alive) {
+        float thi = rs.thi;
+        hf_src_global src;
+        src.mip = f.mip; src.shear = f.shear; src.h = f.h; src.top = f.top; src.W = f.W;
+        const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
+        (void) walk_subtree<ANY>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
+    }
+}
+// the second vertex: p and the face normal of compute_si_to for the hit (prim, b1, b2), its arithmetic
+__device__ __forceinline__ void bounce_vertex(const hf_dev_field &f, uint32_t prim, float b1, float b2, v3 &q, v3 &nq) {
+    v3 P[3];
+    float U[3], V[3];
+    int vi[3], vj[3];
+    prim_world(f, prim, P, U, V, vi, vj);
+    q = bary_point(P, 1.f - b1 - b2, b1, b2);
+    nq = unit_normal(P[1] - P[0], P[2] - P[0]).n;
+    if (f.flip) nq = neg3(nq);
+}
+
+#ifndef HF_BOUNCE_WAVES
+#define HF_BOUNCE_WAVES 6 // resident waves per SIMD: chosen by an A/B against 4 and 5 (profiles/bounce_lighting/)
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_BOUNCE_WAVES) void hf_bounce_kernel(hf_bounce_args a) {
+    // the per-light sums of a sample, in k order: a lane reads and writes its own column only (no barrier)
+    __shared__ float s_acc[HF_MAX_LIGHTS][HF_BLOCK];
+    const hf_dev_field &f = a.f;
+    // n < 2^32 (hf_bounce_lighting): the sample index is ONE register across the walks
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    const v3 sn = mk3(a.sh_n[0][ii], a.sh_n[1][ii], a.sh_n[2][ii]);
+    bool elig;
+    {
+        const v3 d = mk3(a.d[0][ii], a.d[1][ii], a.d[2][ii]);
+        elig = in && sky_eligible(a.t[ii], sn, d);
+    }
+    for (uint32_t l = 0; l < a.n_lights; ++l) s_acc[l][threadIdx.x] = 0.f;
+    const bool any = __ballot(elig) != 0ull; // wave-uniform: a batch without an eligible sample draws and traces nothing
+    v3 p = mk3(0.f, 0.f, 0.f), gn = p;
+    uint32_t id = 0u;
+    if (any) {
+        p = mk3(a.p[0][ii], a.p[1][ii], a.p[2][ii]);
+        gn = mk3(a.nrm[0][ii], a.nrm[1][ii], a.nrm[2][ii]);
+        id = a.ray_id ? a.ray_id[ii] : ii;
+    }
+    // (launch constants of the loops are read from the kernarg segment where they are used, as in hf_sky_kernel)
+    hf_bounce_kargs ka = (hf_bounce_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll 1
+    for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+        asm volatile("" : "+s"(ka)); // opaque per direction: the kernarg loads stay inside the loop
+        uint32_t prim_out = 0xFFFFFFFFu, bits = 0u;
+        if (any) {
+            const v3 wo = bounce_local(ka->seed, k, id);
+            const v3 w = bounce_world(sn, wo);
+            bool hit;
+            hf_hit best;
+            {
+                const bool traced = elig && wo.z > 0.f;
+                bounce_walk<false>(ka, f, sky_origin(p, gn, sky_offset(p), w), w, traced, best);
+                hit = traced && best.hit;
+            }
+            if (__ballot(hit) != 0ull) { // (wave-uniform)
+                v3 q, nq;
+                {
+                    const hf_dev_field fl = load_field(&ka->f); // to_world etc.: not held across the walk
+                    bounce_vertex(fl, hit ? best.prim : 0u, hit ? best.u : 0.f, hit ? best.v : 0.f, q, nq);
+                }
+                if (hit) prim_out = best.prim;
+                const bool front = hit && (-dot3(nq, w) > 0.f);
+                if (__ballot(front) != 0ull) {
+#pragma unroll 1
+                    for (uint32_t l = 0;; ++l) { // the directional lights at q: kernarg scalars, never held in vector registers
+                        asm volatile("" : "+s"(ka));
+                        const v3 ll = mk3(ka->l[l][0], ka->l[l][1], ka->l[l][2]);
+                        const bool ts = front && dot3(nq, ll) > 0.f;
+                        hf_hit sh;
+                        bounce_walk<true>(ka, f, sky_origin(q, nq, sky_offset(q), ll), ll, ts, sh);
+                        if (ts && !sh.hit) {
+                            bits |= 1u << l;
+                            // the cosine from the float normal in double, rounded once (the float dot3 decides the mask only)
+                            const float co = (float) ((double) nq.x * (double) ll.x + (double) nq.y * (double) ll.y + (double) nq.z * (double) ll.z);
+                            s_acc[l][threadIdx.x] += ka->w[l] * co;
+                        }
+                        if (l + 1u >= ka->n_lights) break;
+                    }
+                }
+            }
+        }
+        {
+            uint32_t *hit_prim = ka->hit_prim;
+            uint8_t *lit_bits = ka->lit_bits;
+            const size_t at = (size_t) k * ka->sample_stride + i;
+            if (in && hit_prim) hit_prim[at] = prim_out;
+            if (in && lit_bits) lit_bits[at] = (uint8_t) bits;
+        }
+        if (k + 1u >= ka->num_rays) break;
+    }
+    // (the output pointers: loaded here, not before the walks)
+    hf_bounce_kargs ko = (hf_bounce_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    float cw = 0.f;
+    if (elig) { // (eligible: in range)
+        const float *weight = ko->weight;
+        cw = ko->scale;
+        if (weight) cw *= weight[i];
+    }
+    const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u, nl = ko->n_lights;
+    const size_t npix = ko->n / spp;
+    const bool pow2 = (spp & (spp - 1u)) == 0u;
+    for (uint32_t l = 0; l < nl; ++l)
+        film_pixel(ko->image, cw * s_acc[l][threadIdx.x], l, npix, i, spp, in, pow2, g, 1.0f / (float) spp, i);
+}
+
+// Ray a.k of every sample, materialised: the bounce ray (a.shadow == 0), or the shadow ray from that bounce ray's hit
+// towards a.l[0] (the bounce ray is then traced here, per lane): what hf_bounce_kernel traces, bit for bit
+__global__ __launch_bounds__(HF_BLOCK) void hf_bounce_rays_kernel(hf_bounce_args a) {
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const size_t i = in ? i64 : a.n - 1;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    const v3 wo = bounce_local(a.seed, a.k, a.ray_id ? a.ray_id[i] : (uint32_t) i);
+    const v3 w = bounce_world(sn, wo);
+    bool traced = in && sky_eligible(a.t[i], sn, d) && wo.z > 0.f;
+    v3 o = sky_origin(p, gn, sky_offset(p), w), dir = w;
+    if (a.shadow) {
+        hf_bounce_kargs ka = (hf_bounce_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+        hf_hit best;
+        bounce_walk<false>(ka, a.f, o, w, traced, best);
+        const bool hit = traced && best.hit;
+        v3 q, nq;
+        bounce_vertex(a.f, hit ? best.prim : 0u, hit ? best.u : 0.f, hit ? best.v : 0.f, q, nq);
+        dir = mk3(a.l[0][0], a.l[0][1], a.l[0][2]);
+        traced = hit && (-dot3(nq, w) > 0.f) && dot3(nq, dir) > 0.f;
+        o = hit ? sky_origin(q, nq, sky_offset(q), dir) : mk3(0.f, 0.f, 0.f);
+    }
+    if (!in) return;
+    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
+    a.out_d[0][i] = dir.x; a.out_d[1][i] = dir.y; a.out_d[2][i] = dir.z;
+    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+}
+
+// What the derivative kernels read of one record: the triangle of hit_prim (edges, unit normal before flip_normals and
+// 1 / |N|, vertex texels), from the heights as they are now.  false: a miss, or an index that names no triangle
+struct hf_bounce_tri { v3 e0, e1, n; float r; int vi[3], vj[3]; };
+__device__ __forceinline__ bool bounce_record(const hf_bounce_args &a, size_t at, hf_bounce_tri &tr, uint32_t &bits,
+                                              v3 *dP = nullptr, const float *dh = nullptr) {
+    const uint32_t prim = a.hit_prim[at];
+    bits = a.lit_bits[at];
+    if (bits == 0u || prim >= 2u * (uint32_t) (a.f.W - 1) * (uint32_t) (a.f.H - 1)) return false;
+    v3 P[3];
+    float U[3], V[3];
+    prim_world(a.f, prim, P, U, V, tr.vi, tr.vj, dP, dh);
+    tr.e0 = P[1] - P[0]; tr.e1 = P[2] - P[0];
+    const auto [n, r] = unit_normal(tr.e0, tr.e1);
+    tr.n = n; tr.r = r;
+    return true;
+}
+
+// Reverse mode of hf_bounce_kernel with respect to sh_n, weight and the heights: nothing is traced, the directions are
+// drawn again and the record read.  Sums in k order; float atomics on grad_heights only.
+__global__ __launch_bounds__(HF_BLOCK) void hf_bounce_adjoint_kernel(hf_bounce_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    double sx = 0.0, sy = 0.0, sz = 0.0, sg = 0.0;
+    const float wgt = a.weight ? a.weight[i] : 1.f;
+    if (sky_eligible(a.t[i], sn, d)) {
+        const uint32_t id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+        const size_t npix = a.n / a.spp, pix = i / a.spp;
+        const float inv_spp = 1.0f / (float) a.spp;
+        const v3 ez = height_axis(a.f);
+        for (uint32_t k = 0; k < a.num_rays; ++k) {
+            hf_bounce_tri tr;
+            uint32_t bits;
+            if (!bounce_record(a, (size_t) k * a.sample_stride + i, tr, bits)) continue;
+            const v3 nq = a.f.flip ? neg3(tr.n) : tr.n;
+            double G = 0.0, nx = 0.0, ny = 0.0, nz = 0.0; // G_ik and the gradient of n_q (before weight_i c)
+#pragma unroll 1
+            for (uint32_t l = 0; l < a.n_lights; ++l) { // (scalar loop: the lights are kernarg scalars, the image gradient an L1 hit)
+                if (!((bits >> l) & 1u)) continue;
+                const double lx = a.l[l][0], ly = a.l[l][1], lz = a.l[l][2];
+                const double g = (a.gimg[l * npix + pix] * inv_spp) * a.w[l]; // g_l albedo/pi E_l
+                G += g * ((double) nq.x * lx + (double) nq.y * ly + (double) nq.z * lz);
+                nx += g * lx; ny += g * ly; nz += g * lz;
+            }
+            double z;
+            const hf_d3 w = bounce_dir_f64(sn, a.seed, k, id, z);
+            const double s = z > 0.0 ? G / z : 0.0; // the attached cosine over the detached one (prb.py:213-223)
+            sx += s * w.x; sy += s * w.y; sz += s * w.z; sg += G;
+            if (a.gh) {
+                const float c = wgt * a.scale;
+                v3 gN = mk3(c * (float) nx, c * (float) ny, c * (float) nz);
+                if (a.f.flip) gN = neg3(gN);
+                float g1, g2;
+                face_normal_vjp(tr.e0, tr.e1, dnormalize(tr.n, tr.r, gN), ez, g1, g2);
+                atomicAdd(a.gh + (size_t) tr.vi[0] * a.f.W + tr.vj[0], -(g1 + g2));
+                atomicAdd(a.gh + (size_t) tr.vi[1] * a.f.W + tr.vj[1], g1);
+                atomicAdd(a.gh + (size_t) tr.vi[2] * a.f.W + tr.vj[2], g2);
+            }
+        }
+    }
+    if (a.gn[0]) {
+        const double c = (double) wgt * (double) a.scale;
+        a.gn[0][i] = (float) (c * sx); a.gn[1][i] = (float) (c * sy); a.gn[2][i] = (float) (c * sz);
+    }
+    if (a.gw) a.gw[i] = (float) ((double) a.scale * sg);
+}
+
+// forward mode: the tangents of sample i's values under every light, for tangents dn of sh_n, dw of weight and dh of
+// the heights (NULL: zero), ADDED to the lane's column acc[l * HF_BLOCK] (LDS: the light index stays a scalar loop)
+__device__ __forceinline__ void bounce_tangent_values(const hf_bounce_args &a, size_t i, double *acc) {
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    if (!sky_eligible(a.t[i], sn, d)) return;
+    const uint32_t id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const double wgt = a.weight ? a.weight[i] : 1.f, dw = a.dw ? a.dw[i] : 0.f;
+    for (uint32_t k = 0; k < a.num_rays; ++k) {
+        hf_bounce_tri tr;
+        uint32_t bits;
+        v3 dP[3];
+        if (!bounce_record(a, (size_t) k * a.sample_stride + i, tr, bits, dP, a.dh)) continue;
+        const v3 nq = a.f.flip ? neg3(tr.n) : tr.n;
+        v3 dnq = mk3(0.f, 0.f, 0.f);
+        if (a.dh) {
+            dnq = dnormalize(tr.n, tr.r, face_normal_jvp(tr.e0, tr.e1, dP[1] - dP[0], dP[2] - dP[0]));
+            if (a.f.flip) dnq = neg3(dnq);
+        }
+        double z;
+        const hf_d3 w = bounce_dir_f64(sn, a.seed, k, id, z);
+        const double s = z > 0.0 ? sky_dot_f64(dn, w) / z : 0.0;
+        const double f1 = wgt * s + dw; // what multiplies R_ikl
+#pragma unroll 1
+        for (uint32_t l = 0; l < a.n_lights; ++l) {
+            if (!((bits >> l) & 1u)) continue;
+            const double lx = a.l[l][0], ly = a.l[l][1], lz = a.l[l][2];
+            const double co = (double) nq.x * lx + (double) nq.y * ly + (double) nq.z * lz;
+            const double dco = (double) dnq.x * lx + (double) dnq.y * ly + (double) dnq.z * lz;
+            acc[l * HF_BLOCK] += (double) a.w[l] * (co * f1 + wgt * dco);
+        }
+    }
+}
+// PIXEL = false: one lane per sample and the primal's film (spp a power of two <= 64: its shuffle tree, one store per
+// pixel and light); PIXEL = true (any other spp): one lane per pixel adds its samples in order -- no atomics either way
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_bounce_tangent_kernel(hf_bounce_args a) {
+    __shared__ double s_acc[HF_MAX_LIGHTS][HF_BLOCK]; // a lane reads and writes its own column only (no barrier)
+    __shared__ float s_pix[PIXEL ? HF_MAX_LIGHTS : 1][HF_BLOCK];
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    const size_t npix = a.n / spp;
+    double *acc = &s_acc[0][threadIdx.x];
+    if (PIXEL) {
+        if (i >= npix) return;
+        for (uint32_t l = 0; l < a.n_lights; ++l) s_pix[l][threadIdx.x] = 0.f;
+        for (uint32_t s = 0; s < spp; ++s) {
+            for (uint32_t l = 0; l < a.n_lights; ++l) acc[l * HF_BLOCK] = 0.0;
+            bounce_tangent_values(a, i * spp + s, acc);
+            for (uint32_t l = 0; l < a.n_lights; ++l) s_pix[l][threadIdx.x] += (float) ((double) a.scale * acc[l * HF_BLOCK]);
+        }
+        for (uint32_t l = 0; l < a.n_lights; ++l) a.image[l * npix + i] = s_pix[l][threadIdx.x] * (1.0f / (float) spp);
+    } else {
+        const bool in = i < a.n;
+        for (uint32_t l = 0; l < a.n_lights; ++l) acc[l * HF_BLOCK] = 0.0;
+        if (in) bounce_tangent_values(a, i, acc);
+        for (uint32_t l = 0; l < a.n_lights; ++l)
+            film_pixel(a.image, (float) ((double) a.scale * acc[l * HF_BLOCK]), l, npix, i, spp, in, true, spp, 1.0f / (float) spp);
+    }
+}
+
+void hf_launch_bounce(int mode, const hf_bounce_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    if (mode == 0) {
+        if (!sky_tree_film(a.spp)) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp) * a.n_lights, stream); // atomic paths of film_pixel
+        hipLaunchKernelGGL(hf_bounce_kernel, grid, block, 0, stream, a);
+    } else if (mode == 1) {
+        hipLaunchKernelGGL(hf_bounce_adjoint_kernel, grid, block, 0, stream, a);
+    } else if (mode == 2) {
+        if (sky_tree_film(a.spp)) hipLaunchKernelGGL(hf_bounce_tangent_kernel<false>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(hf_bounce_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
+    } else {
+        hipLaunchKernelGGL(hf_bounce_rays_kernel, grid, block, 0, stream, a);
+    }
+}
+
 // ---- warped-area reparameterisation: per-sample kernels (helpers: above hf_adjoint_kernel) ----
 __global__ __launch_bounds__(HF_BLOCK) void hf_reparam_aux_kernel(hf_reparam_args a) {
     const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;

@@ -82,6 +82,29 @@ struct hf_sky_args {
 // mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is the per-lane any-hit walk with the samples
 // drawn in the kernel: no work counter, no scratch block
 void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream);
+// ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
+struct hf_bounce_args {
+    hf_dev_field f;                          // the walks (forward, rays) and the triangles of the record (adjoint, tangent)
+    size_t n, sample_stride;                 // record of direction k of sample i at [k * sample_stride + i]
+    uint32_t spp, num_rays, seed, k;         // k: hf_bounce_rays' direction
+    uint32_t n_lights;
+    int32_t shadow;                          // hf_bounce_rays: 0 = the bounce ray, 1 = the shadow ray towards l[0]
+    float scale;                             // albedo / num_rays
+    float l[HF_MAX_LIGHTS][3];               // unit directions towards the lights
+    float w[HF_MAX_LIGHTS];                  // albedo/pi * irradiance
+    const float *p[3], *nrm[3];              // si.p, si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight;
+    const uint32_t *ray_id;                  // optional: the id of sample i in the sample streams (NULL: i)
+    float *image;                            // forward: image; tangent: dimage
+    uint32_t *hit_prim;                      // forward: written (NULL: not wanted); adjoint, tangent: read
+    uint8_t *lit_bits;                       // the same
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    const float *gimg; float *gn[3], *gw, *gh; // adjoint (gn rows, gw, gh: NULL = not wanted; gh accumulated)
+    const float *dn[3], *dw, *dh;            // tangent inputs (NULL: zero)
+};
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is the per-lane closest-hit and any-hit walks
+// with the samples drawn in the kernel: no work counter, no scratch block
+void hf_launch_bounce(int mode, const hf_bounce_args &a, hipStream_t stream);
 struct hf_splat_args {
     size_t n;
     uint32_t channels, width, height;

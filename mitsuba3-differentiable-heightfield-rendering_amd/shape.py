@@ -1492,6 +1492,111 @@ def sky_rays(si, ray, k, seed=0, ray_index=None):
     return Ray3f(o, d, maxt)
 
 
+class _BounceLightingOp(torch.autograd.Function):
+    """(image, hit_prim, lit_bits) of hf_bounce_lighting; backward = hf_bounce_lighting_adjoint (gradients of sh_n, weight
+    and the heights), jvp = hf_bounce_lighting_tangent.  Both read the record the forward saved and trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, shape, sn, dd, tt, prim, lit, ww=None):
+        """what hf_bounce_lighting_adjoint / _tangent start with"""
+        spp, num_rays, seed, rid, L, K, albedo = ctx.misc
+        n = sn.shape[1]
+        return (shape._h, n, spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(rid),
+                K, L, albedo, prim.data_ptr(), lit.data_ptr(), n)
+
+    @staticmethod
+    def forward(ctx, sh_n, weight, heights, shape, p, nrm, d, t, lights, albedo, spp, num_rays, seed, ray_index):
+        sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (sh_n, p, nrm, d, t))
+        ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
+        n, K = sn.shape[1], lights.shape[0]
+        L = (_capi.hf_dir_light_t * max(K, 1))()
+        for k, row in enumerate(lights.detach().cpu().tolist()):
+            L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = row
+        ctx.misc = (spp, num_rays, seed, ray_index, L, K, albedo)
+        image = torch.empty((K, n // max(spp, 1)), dtype=torch.float32, device=sn.device)
+        prim = torch.empty((num_rays, n), dtype=torch.int32, device=sn.device)
+        lit = torch.empty((num_rays, n), dtype=torch.uint8, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_bounce_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                                 C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(ray_index),
+                                                 K, L, albedo, image.data_ptr(), prim.data_ptr(), lit.data_ptr(), n,
+                                                 _stream_of(sn.device)))
+        saved = (sn, dd, tt, prim, lit) if ww is None else (sn, dd, tt, prim, lit, ww)
+        _op_save(ctx, shape, saved)
+        ctx.mark_non_differentiable(prim, lit)
+        return image, prim, lit
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dweight, dheights, *_):
+        shape, saved = _op_saved(ctx, "jvp")
+        sn = saved[0]
+        dn = _f3(dsh_n)[0] if dsh_n is not None else None
+        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 6 and dweight is not None) else None
+        dh = shape._dheights(dheights)
+        dimage = torch.empty((ctx.misc[5], sn.shape[1] // ctx.misc[0]), dtype=torch.float32, device=sn.device)
+        if sn.shape[1]:
+            check(_capi.lib().hf_bounce_lighting_tangent(*_BounceLightingOp._prefix(ctx, shape, *saved), _ref(_row_ptrs(dn)),
+                                                         _ptr(dw), _ptr(dh), dimage.data_ptr(), _stream_of(sn.device)))
+        return dimage, None, None
+
+    @staticmethod
+    def backward(ctx, grad_image, _grad_prim, _grad_lit):
+        shape, saved = _op_saved(ctx, "backward")
+        sn = saved[0]
+        gi = grad_image.to(dtype=torch.float32).contiguous()
+        gn = torch.empty_like(sn)
+        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 6 else None
+        gh = shape._zero_heights() if ctx.needs_input_grad[2] else None
+        if sn.shape[1]:
+            check(_capi.lib().hf_bounce_lighting_adjoint(*_BounceLightingOp._prefix(ctx, shape, *saved), gi.data_ptr(),
+                                                         C.byref(_p3(gn)), _ptr(gw), _ptr(gh), _stream_of(sn.device)))
+        return (gn, gw, gh) + (None,) * 11
+
+
+def _check_static_to_world(shape, what):
+    """rows that do not differentiate to_world refuse a transform that asks for a derivative"""
+    if shape._to_world_live() is not None:
+        raise _capi.HfError(_capi.HF_EINVAL, f"{what}: to_world is not differentiated by this row (it requires "
+                                             "grad or carries a tangent); detach it")
+
+
+def bounce_lighting(shape, si, ray, lights, albedo=1.0, spp=1, num_rays=4, seed=0, weight=None, ray_index=None,
+                    return_records=False):
+    """One bounce of diffuse interreflection under directional lights + box-filter film, both rays of every path
+    traced inside the lighting kernel (``hf_bounce_lighting``): every sample draws ``num_rays`` (1..32) cosine-weighted
+    directions about ``si.sh_frame.n`` from the TEA stream of ``sky_lighting`` (``seed``, ``ray_index``; give the rows
+    different seeds), traces ``si.spawn_ray(direction)`` to its closest hit and shades that hit, with its face normal
+    and shadow rays of its own, under ``lights`` ([K, 4]: unit direction towards the light, irradiance).  Returns the
+    [K, n // spp] image, whose rows add onto ``direct_lighting``'s; with ``return_records`` also ``hit_prim``
+    ([num_rays, n] int32, -1 = no hit) and ``lit_bits`` ([num_rays, n] uint8, bit l: light l reaches the hit).
+    Differentiable with respect to ``si.sh_frame.n``, ``weight`` ([n], optional) and ``shape.heightfield`` (through the
+    normals of the hit triangles); visibility is piecewise constant and ``to_world`` is not differentiated."""
+    shape._check_ray(ray)
+    _check_static_to_world(shape, "bounce_lighting")
+    lights = torch.as_tensor(lights, dtype=torch.float32).reshape(-1, 4)
+    image, prim, lit = _BounceLightingOp.apply(si.sh_frame.n, weight, shape.heightfield, shape, si.p, si.n, ray.d, si.t,
+                                               lights, float(albedo), int(spp), int(num_rays), int(seed),
+                                               _check_ray_index(ray_index, ray))
+    return (image, prim, lit) if return_records else image
+
+
+def bounce_rays(shape, si, ray, k, seed=0, ray_index=None, to_light=None):
+    """Ray ``k`` of every sample of ``bounce_lighting`` as a Ray3f (``hf_bounce_rays``), bit for bit what the fused
+    kernel traces: the bounce ray, or with ``to_light`` (3 floats) the shadow ray from that bounce ray's hit towards
+    the light.  Lanes the fused kernel does not trace get ``maxt = -1``, a miss."""
+    rid = _check_ray_index(ray_index, ray)
+    sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n = sn.shape[1]
+    o, d = torch.empty_like(pp), torch.empty_like(pp)
+    maxt = torch.empty(n, dtype=torch.float32, device=pp.device)
+    tl = (C.c_float * 3)(*[float(x) for x in to_light]) if to_light is not None else None
+    if n:
+        check(_capi.lib().hf_bounce_rays(shape._h, n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
+                                         tt.data_ptr(), int(k), int(seed), _ptr(rid), _ref(tl), C.byref(_p3(o)),
+                                         C.byref(_p3(d)), maxt.data_ptr(), _stream_of(pp.device)))
+    return Ray3f(o, d, maxt)
+
+
 def _film_splat(values, ps, weight, K, n, width, height, stddev):
     """hf_film_splat of the [K, n] float32 values at ps into a zeroed [K, height * width] image and into weight"""
     image = torch.zeros((K, height * width), dtype=torch.float32, device=ps.device)
