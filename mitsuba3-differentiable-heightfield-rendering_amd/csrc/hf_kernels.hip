@@ -4107,18 +4107,45 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_bounce_rays_kernel(hf_bounce_args
 // What the derivative kernels read of one record: the triangle of hit_prim (edges, unit normal before flip_normals and
 // 1 / |N|, vertex texels), from the heights as they are now.  false: a miss, or an index that names no triangle
 struct hf_bounce_tri { v3 e0, e1, n; float r; int vi[3], vj[3]; };
-__device__ __forceinline__ bool bounce_record(const hf_bounce_args &a, size_t at, hf_bounce_tri &tr, uint32_t &bits,
-                                              v3 *dP = nullptr, const float *dh = nullptr) {
+__device__ __forceinline__ bool bounce_record(const hf_bounce_args &a, size_t at, hf_bounce_tri &tr, uint32_t &bits) {
     const uint32_t prim = a.hit_prim[at];
     bits = a.lit_bits[at];
     if (bits == 0u || prim >= 2u * (uint32_t) (a.f.W - 1) * (uint32_t) (a.f.H - 1)) return false;
     v3 P[3];
     float U[3], V[3];
-    prim_world(a.f, prim, P, U, V, tr.vi, tr.vj, dP, dh);
+    prim_world(a.f, prim, P, U, V, tr.vi, tr.vj);
     tr.e0 = P[1] - P[0]; tr.e1 = P[2] - P[0];
     const auto [n, r] = unit_normal(tr.e0, tr.e1);
     tr.n = n; tr.r = r;
     return true;
+}
+// The tangent of the unit normal of triangle `tr` (before flip_normals) for the height tangent dh, in double from the
+// OBJECT-space edges.  The world vertices are float32: an edge P_k - P_0 is off by an ulp of |P|, 3e-6 of a cell at 40
+// cells per unit, and dnormalize amplifies that by |dN| r / |dn| -- in float the tangent image misses the bound the
+// dsh_n and dweight tangents keep (1.2 to 1.6 times it under a general to_world).  In object space the edges of a grid
+// triangle are differences of (j gx, i gy, h s), exact in double, and to_world's linear part maps them to world once.
+__device__ __forceinline__ hf_d3 bounce_dnq_f64(const hf_dev_field &f, const hf_bounce_tri &tr, const float *dh) {
+    const double gx = 2.0 / (double) (f.W - 1), gy = 2.0 / (double) (f.H - 1), s = f.s;
+    const double ez[3] = { f.to_world[2], f.to_world[6], f.to_world[10] }; // the height axis (height_axis / s)
+    const size_t i0 = (size_t) tr.vi[0] * f.W + tr.vj[0];
+    const double h0 = f.h[i0], d0 = dh[i0];
+    double e[2][3], de[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const size_t idx = (size_t) tr.vi[k + 1] * f.W + tr.vj[k + 1];
+        const double qx = (double) (tr.vj[k + 1] - tr.vj[0]) * gx, qy = (double) (tr.vi[k + 1] - tr.vi[0]) * gy;
+        const double qz = ((double) f.h[idx] - h0) * s;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[k][c] = (double) f.to_world[4 * c] * qx + (double) f.to_world[4 * c + 1] * qy + ez[c] * qz;
+        de[k] = ((double) dh[idx] - d0) * s; // the edge's tangent is de[k] ez
+    }
+    const double N[3] = { e[0][1] * e[1][2] - e[0][2] * e[1][1], e[0][2] * e[1][0] - e[0][0] * e[1][2], e[0][0] * e[1][1] - e[0][1] * e[1][0] };
+    // dN = cross(de1 ez, e2) + cross(e1, de2 ez) = cross(ez, de1 e2 - de2 e1)
+    const double m[3] = { de[0] * e[1][0] - de[1] * e[0][0], de[0] * e[1][1] - de[1] * e[0][1], de[0] * e[1][2] - de[1] * e[0][2] };
+    const double dN[3] = { ez[1] * m[2] - ez[2] * m[1], ez[2] * m[0] - ez[0] * m[2], ez[0] * m[1] - ez[1] * m[0] };
+    const double r2 = 1.0 / (N[0] * N[0] + N[1] * N[1] + N[2] * N[2]), r = sqrt(r2);
+    const double pj = (N[0] * dN[0] + N[1] * dN[1] + N[2] * dN[2]) * r2; // <n, dN> / |N|
+    return hf_d3{ (dN[0] - N[0] * pj) * r, (dN[1] - N[1] * pj) * r, (dN[2] - N[2] * pj) * r };
 }
 
 // Reverse mode of hf_bounce_kernel with respect to sh_n, weight and the heights: nothing is traced, the directions are
@@ -4182,13 +4209,12 @@ __device__ __forceinline__ void bounce_tangent_values(const hf_bounce_args &a, s
     for (uint32_t k = 0; k < a.num_rays; ++k) {
         hf_bounce_tri tr;
         uint32_t bits;
-        v3 dP[3];
-        if (!bounce_record(a, (size_t) k * a.sample_stride + i, tr, bits, dP, a.dh)) continue;
+        if (!bounce_record(a, (size_t) k * a.sample_stride + i, tr, bits)) continue;
         const v3 nq = a.f.flip ? neg3(tr.n) : tr.n;
-        v3 dnq = mk3(0.f, 0.f, 0.f);
+        hf_d3 dnq = { 0.0, 0.0, 0.0 };
         if (a.dh) {
-            dnq = dnormalize(tr.n, tr.r, face_normal_jvp(tr.e0, tr.e1, dP[1] - dP[0], dP[2] - dP[0]));
-            if (a.f.flip) dnq = neg3(dnq);
+            dnq = bounce_dnq_f64(a.f, tr, a.dh);
+            if (a.f.flip) dnq = hf_d3{ -dnq.x, -dnq.y, -dnq.z };
         }
         double z;
         const hf_d3 w = bounce_dir_f64(sn, a.seed, k, id, z);
@@ -4199,7 +4225,7 @@ __device__ __forceinline__ void bounce_tangent_values(const hf_bounce_args &a, s
             if (!((bits >> l) & 1u)) continue;
             const double lx = a.l[l][0], ly = a.l[l][1], lz = a.l[l][2];
             const double co = (double) nq.x * lx + (double) nq.y * ly + (double) nq.z * lz;
-            const double dco = (double) dnq.x * lx + (double) dnq.y * ly + (double) dnq.z * lz;
+            const double dco = dnq.x * lx + dnq.y * ly + dnq.z * lz;
             acc[l * HF_BLOCK] += (double) a.w[l] * (co * f1 + wgt * dco);
         }
     }

@@ -1,6 +1,7 @@
 """Float64 restatement of the bounce-lighting row of include/hf.h (hf_bounce_rays, hf_bounce_lighting, _adjoint,
 _tangent): the sample stream, the cosine-weighted directions and their frame, the masks, the spawned origins, the
-value, its adjoint and its tangent, and the face normal of a grid triangle with its VJP and JVP.  The record (which
+value, its adjoint and its tangent, and the face normal of a grid triangle (rectangular grids, any constant affine
+to_world) with its VJP and JVP.  The record (which
 bounce rays hit, which lights reach the hit) and the normals n_q of the hits are inputs: nothing here traces.  Uses the
 oracle's sample_tea_32 (through tests/sky_ref.py, which restates the shared stream) and nothing of the product.
 
@@ -71,7 +72,7 @@ def unpack(hit_prim, lit_bits, L):
     return prim != MISS, lit
 
 
-# ---- the face normal of a grid triangle (identity to_world: x = j sx - 1, y = i sy - 1, z = h max_height) ------------
+# ---- the face normal of a grid triangle: P = A (j sx - 1, i sy - 1, h max_height) + T for to_world = [A | T] ----------
 def prim_vertices(prim, W):
     """rows vi [3, m] and columns vj [3, m] of the three vertices: tri 0 = (v00, v10, v01), tri 1 = (v11, v01, v10)"""
     prim = np.asarray(prim, np.int64)
@@ -82,27 +83,36 @@ def prim_vertices(prim, W):
     return vi, vj
 
 
-def _edges(heights, prim, max_height):
+def _affine(to_world):
+    """(A [3, 3], T [3]) of a row-major 3x4 to_world (None: the identity)"""
+    M = np.eye(4)[:3] if to_world is None else np.asarray(to_world, np.float64).reshape(3, 4)
+    return M[:, :3], M[:, 3]
+
+
+def _edges(heights, prim, max_height, to_world=None):
+    """the WORLD edges P1 - P0, P2 - P0 [3, m], the vertex ids and dP/dh = max_height A[:, 2] (the same for every vertex)"""
     H, W = heights.shape
+    A, T = _affine(to_world)
     vi, vj = prim_vertices(prim, W)
-    P = np.stack([vj * (2.0 / (W - 1)) - 1.0, vi * (2.0 / (H - 1)) - 1.0, np.asarray(heights, np.float64)[vi, vj] * max_height], 1)
-    return P[1] - P[0], P[2] - P[0], vi, vj                               # [3, m] each
+    Q = np.stack([vj * (2.0 / (W - 1)) - 1.0, vi * (2.0 / (H - 1)) - 1.0, np.asarray(heights, np.float64)[vi, vj] * max_height], 1)
+    P = np.einsum("cd,kdm->kcm", A, Q) + T[None, :, None]                 # [3 vertices, 3, m]
+    return P[1] - P[0], P[2] - P[0], vi, vj, max_height * A[:, 2]
 
 
-def face_normal(heights, prim, max_height, flip=False):
-    """[3, m]: normalize(cross(P1 - P0, P2 - P0)), negated with flip_normals"""
-    e1, e2, _, _ = _edges(heights, prim, max_height)
+def face_normal(heights, prim, max_height, flip=False, to_world=None):
+    """[3, m]: normalize(cross(P1 - P0, P2 - P0)) of the world vertices (not a transformed object normal: a mirror turns
+    it over), negated with flip_normals"""
+    e1, e2, _, _, _ = _edges(heights, prim, max_height, to_world)
     N = np.cross(e1, e2, axis=0)
     n = N / np.linalg.norm(N, axis=0)
     return -n if flip else n
 
 
-def face_normal_jvp(heights, prim, max_height, dheights, flip=False):
+def face_normal_jvp(heights, prim, max_height, dheights, flip=False, to_world=None):
     """[3, m]: the tangent of face_normal for the height tangent dheights [H, W]"""
-    e1, e2, vi, vj = _edges(heights, prim, max_height)
-    dz = np.asarray(dheights, np.float64)[vi, vj] * max_height
-    z = np.zeros_like(dz[0])
-    de1, de2 = np.stack([z, z, dz[1] - dz[0]]), np.stack([z, z, dz[2] - dz[0]])
+    e1, e2, vi, vj, ez = _edges(heights, prim, max_height, to_world)
+    dz = np.asarray(dheights, np.float64)[vi, vj]
+    de1, de2 = ez[:, None] * (dz[1] - dz[0])[None], ez[:, None] * (dz[2] - dz[0])[None]
     N = np.cross(e1, e2, axis=0)
     r = 1.0 / np.linalg.norm(N, axis=0)
     n = N * r
@@ -111,16 +121,16 @@ def face_normal_jvp(heights, prim, max_height, dheights, flip=False):
     return -dn if flip else dn
 
 
-def face_normal_vjp(heights, prim, max_height, gn, flip=False):
+def face_normal_vjp(heights, prim, max_height, gn, flip=False, to_world=None):
     """[H, W]: the gradients gn [3, m] of the normals of `prim`, carried to the heights and added up"""
-    e1, e2, vi, vj = _edges(heights, prim, max_height)
+    e1, e2, vi, vj, ez = _edges(heights, prim, max_height, to_world)
     gn = -np.asarray(gn, np.float64) if flip else np.asarray(gn, np.float64)
     N = np.cross(e1, e2, axis=0)
     r = 1.0 / np.linalg.norm(N, axis=0)
     n = N * r
     gN = (gn - n * (n * gn).sum(0)) * r
-    g1 = np.cross(e2, gN, axis=0)[2] * max_height
-    g2 = np.cross(gN, e1, axis=0)[2] * max_height
+    g1 = (np.cross(e2, gN, axis=0) * ez[:, None]).sum(0)                 # <dP/dh, dL/de1>
+    g2 = (np.cross(gN, e1, axis=0) * ez[:, None]).sum(0)
     out = np.zeros(heights.shape)
     np.add.at(out, (vi[0], vj[0]), -(g1 + g2))
     np.add.at(out, (vi[1], vj[1]), g1)

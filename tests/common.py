@@ -18,7 +18,14 @@ def affine(seed=0):
     return np.concatenate([A, T[:, None]], 1).astype(np.float32)
 
 
-def heights(kind, W, H, rng):
+def mirror_shear():
+    """a mirror (x -> -x) of a shear + translation, row-major 3x4 float32: negative determinant, so world-space face
+    normals are turned over"""
+    S_ = np.array([[1.0, 0.35, 0.0], [0.0, 1.0, 0.25], [0.2, 0.0, 1.0]])
+    return np.concatenate([np.diag([-1.0, 1.0, 1.0]) @ S_, np.array([[-0.1], [0.2], [0.1]])], 1).astype(np.float32)
+
+
+def heights(kind, W, H, rng=None):
     if kind == "flat":
         return np.full((H, W), 0.5, np.float32)
     if kind == "rand":

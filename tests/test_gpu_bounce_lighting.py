@@ -20,6 +20,7 @@ import torch
 import torch.autograd.forward_ad as fwAD
 
 import bounce_ref as B
+from lighting_scenes import _close, _records, _rows7
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -36,10 +37,6 @@ MISS = 0xFFFFFFFF
 
 def _np(x):
     return x.detach().cpu().numpy()
-
-
-def _rows7(r):
-    return _np(torch.cat([r.o, r.d, r.maxt[None]]))
 
 
 @pytest.fixture(scope="module")
@@ -180,14 +177,6 @@ def test_record_equals_the_oracles_exactly(hf, scene):
     assert np.all((0.05 < n_lit / n_shadow) & (n_lit / n_shadow < 0.95))
 
 
-def _close(got, ref, absum, num_rays):
-    """the derived bound: 1e-5 |ref| + 1e-7 + K 2^-24 sum |terms| (a float32 accumulation of K terms errs by no more)"""
-    err = np.abs(got - ref)
-    bound = 1e-5 * np.abs(ref) + 1e-7 + num_rays * 2.0 ** -24 * absum
-    print("   max |ref|", np.abs(ref).max(), "max err", err.max(), "max err / bound", (err / bound).max())
-    return bool(np.all(err <= bound))
-
-
 @pytest.mark.parametrize("num_rays", [1, 4, 32])
 @pytest.mark.parametrize("with_weight", [False, True])
 @pytest.mark.parametrize("spp", [1, 4, 3])
@@ -238,10 +227,6 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp, with_
     assert np.abs(tref).max() > 0 and _close(tan, tref, tabs, num_rays)
 
 
-def _records(prim, lit):
-    return B.unpack(_np(prim), _np(lit), NL)
-
-
 def _nq_route(shape_flat, prim, lit, gnq):
     """the composition of existing pieces: per direction, hf_sample_position_adjoint at the centroid of the hit
     triangle with grad_n = gN_k, into one accumulator"""
@@ -272,7 +257,7 @@ def test_grad_heights_against_the_composition(hf, scene, face_normals):
     got = _np(shape.heightfield.grad).astype(np.float64)
     # the restatement at this handle's own sh_n and record; n_q: the face normals of the recorded triangles
     sh_n, t = _np(si.sh_frame.n), _np(si.t)
-    hit, lt = _records(prim, lit)
+    hit, lt = _records(prim, lit, NL)
     hnp = _np(sc.h).astype(np.float64)
     nq = np.stack([B.face_normal(hnp, np.where(hit[k], _np(prim[k]).view(np.uint32), 0), MAXH) for k in range(K)])
     w, z = B.directions(sh_n, np.arange(sc.n), K, SEED)

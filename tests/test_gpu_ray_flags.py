@@ -32,12 +32,7 @@ REC = {"t": [0], "boundary_test": [1], "uv": [2, 3], "p": [4, 5, 6], "n": [7, 8,
 SENTINEL = 7.0
 
 
-def _mirror_shear():
-    S_ = np.array([[1.0, 0.35, 0.0], [0.0, 1.0, 0.25], [0.2, 0.0, 1.0]])
-    return np.concatenate([np.diag([-1.0, 1.0, 1.0]) @ S_, np.array([[-0.1], [0.2], [0.1]])], 1).astype(np.float32)
-
-
-TRANSFORMS = {"identity": np.eye(4)[:3].astype(np.float32), "affine": common.affine(4), "mirror_shear": _mirror_shear()}
+TRANSFORMS = {"identity": np.eye(4)[:3].astype(np.float32), "affine": common.affine(4), "mirror_shear": common.mirror_shear()}
 # (W, H, transform, flip, smooth, blocks of 256 rays that hit / that pass beside the field)
 SCENES = [(2, 2, "identity", False, False, 4, 2), (9, 7, "affine", True, True, 6, 2), (9, 7, "mirror_shear", False, False, 6, 2),
           (33, 17, "mirror_shear", True, True, 8, 4), (33, 17, "affine", False, False, 8, 4),
