@@ -120,7 +120,13 @@ typedef struct hf_desc {
  * (DESIGN 4.1 "wide path": -4 % on the BASELINE wavefront); results do not depend on it.
  * TEST HOOK: the environment variable HF_FORCE_GRAB=<64 .. 4096, a multiple of 64>, read at every trace launch, fixes
  * the number of rays a wave fetches at a time (otherwise chosen from the size of the launch); 256 lets launches of any
- * size take the wide path (tests/test_gpu_parity.py, tests/tools/fuzz_parity.py).  Results do not depend on it. */
+ * size take the wide path (tests/test_gpu_parity.py, tests/tools/fuzz_parity.py).  Results do not depend on it.
+ * TEST HOOK: the environment variable HF_FORCE_GRID=<blocks, an integer >= 1>, read at every launch of a grid-stride
+ * kernel (every entry point but the traversal: SI, adjoints, tangents, reparameterisation, Adam, area sampling, attributes,
+ * parameterisation), makes the grid min(usual grid, blocks): launches of test size then go round their loops several
+ * times (tests/test_gpu_grid_stride.py).  It only ever lowers the grid, so scratch and captured launches stay within
+ * what they reserve; any other value is ignored.  Results do not depend on it except through the order of float
+ * additions (atomic scatters, the per-block sums of dL/d(to_world)); per-lane outputs keep their bytes. */
 typedef struct hf_rays {
     const float *o[3];
     const float *d[3];
@@ -987,6 +993,11 @@ int hf_num_levels(const hf_field_t *hf);
 int hf_get_mip(const hf_field_t *hf, int level, float *h_out, uint32_t *w, uint32_t *h);
 /* inverse of a row-major 3x4 affine matrix (double precision, rounded to float) */
 int hf_invert_affine(const float in[12], float out[12]);
+/* blocks (of 256 threads) that a grid-stride launch of n items gets, HF_FORCE_GRID included.  family: 0 the flat cap
+ * (adjoints, reparameterisation, Adam, area sampling, ...), 1 the cap of the streaming kernels (SI, hf_tangent, the
+ * forward and tangent of attributes and of eval_parameterization), 2 the cap of the launches that sum dL/d(to_world).
+ * 0 for an unknown family.  Needs no device. */
+int hf_grid_blocks(size_t n, int family);
 const char *hf_last_error_string(void);
 int hf_version(void);
 

@@ -1734,6 +1734,13 @@ static int grid_for(size_t n, size_t cap = HF_FLAT_GRID_CAP) {
     size_t blocks = (n + HF_BLOCK - 1) / HF_BLOCK;
     // grid-stride kernels: many short blocks balance better than one resident set
     if (blocks > cap) blocks = cap;
+    // TEST HOOK (include/hf.h): HF_FORCE_GRID=<blocks >= 1> lowers the grid (never raises it: the transform slab, the scratch
+    // ring and captured launches stay within what they reserve), so that launches of test size go round their loops
+    if (const char *e = getenv("HF_FORCE_GRID")) {
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end != e && *end == '\0' && v >= 1 && (size_t) v < blocks) blocks = (size_t) v;
+    }
     if (blocks < 1) blocks = 1;
     return (int) blocks;
 }
@@ -2028,6 +2035,15 @@ __device__ __forceinline__ hf_vd_hit vdirect_grad_hit(v3 gVd, v3 po, float t) {
 #endif
 size_t hf_xform_slab_bytes(size_t n) {
     return (size_t) (n ? grid_for(n, HF_XFORM_GRID_CAP) : HF_XFORM_GRID_CAP) * 12u * sizeof(float);
+}
+// introspection (include/hf.h): the grid a grid-stride launch of n items gets, HF_FORCE_GRID included
+extern "C" int hf_grid_blocks(size_t n, int family) {
+    switch (family) {
+    case 0: return grid_for(n, HF_FLAT_GRID_CAP);
+    case 1: return grid_for(n, HF_SI_GRID_CAP);
+    case 2: return grid_for(n, HF_XFORM_GRID_CAP);
+    default: return 0;
+    }
 }
 // sum over the 64 lanes, the same in every lane (xor butterfly: each step adds two values that commute exactly)
 __device__ __forceinline__ float wave_sum_f32(float v) {

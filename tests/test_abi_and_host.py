@@ -59,6 +59,31 @@ def test_invert_affine_host_function():
     assert b"singular" in _capi.lib().hf_last_error_string()
 
 
+def test_grid_blocks_and_the_force_grid_hook():
+    """hf_grid_blocks (needs no device) reports the grid of a grid-stride launch: one block per 256 items up to the
+    family's cap.  The TEST HOOK HF_FORCE_GRID only ever lowers it, and every value but an integer >= 1 is ignored."""
+    from hf_amd import _capi
+    blocks = _capi.lib().hf_grid_blocks
+    caps = {0: 16384, 1: 262144, 2: 5120}          # HF_FLAT_GRID_CAP, HF_SI_GRID_CAP, HF_XFORM_GRID_CAP
+    old = os.environ.pop("HF_FORCE_GRID", None)
+    try:
+        for fam, cap in caps.items():
+            assert [blocks(n, fam) for n in (1, 256, 257, 2597)] == [1, 1, 2, 11]
+            assert blocks(cap * 256, fam) == cap and blocks(cap * 256 + 1, fam) == cap and blocks(1 << 33, fam) == cap
+            assert blocks((cap - 1) * 256 + 1, fam) == cap
+        assert blocks(2597, 3) == 0 and blocks(2597, -1) == 0        # an unknown family
+        for value, want in (("3", 3), ("1", 1), ("11", 11), ("12", 11), ("100000000", 11), ("0", 11), ("-2", 11),
+                            ("", 11), ("x", 11), ("3x", 11), ("2.5", 11)):
+            os.environ["HF_FORCE_GRID"] = value
+            assert [blocks(2597, fam) for fam in caps] == [want] * 3, value
+        os.environ["HF_FORCE_GRID"] = "5000"
+        assert [blocks(1 << 30, fam) for fam in caps] == [5000] * 3 and blocks(300, 0) == 2
+    finally:
+        os.environ.pop("HF_FORCE_GRID", None)
+        if old is not None:
+            os.environ["HF_FORCE_GRID"] = old
+
+
 def test_ray_container_semantics():
     import hf_amd
     r = hf_amd.Ray3f(torch.zeros(3, 5), torch.ones(3, 5))

@@ -7,6 +7,10 @@ configs[2] 2048^2 grid, adjoint dL/dheight   : L = sum t, against float64 centra
 configs[3] 4096^2 grid, 1024^2 @64spp        : size-independent properties on all 67.1 M rays (fused ==
                                                unfused, ray_test == is_valid, run-to-run identical,
                                                linearity of the adjoint) + the oracle on a 1 M-ray sample
+
+The 4 194 304-ray launches of configs[2], and the stride-16 subset of configs[3] that the adjoint's linearity is
+checked on, are exactly one grid of the flat cap (16 384 blocks of 256): every wave of their grid-stride kernels does
+one iteration.  The loops beyond their first iteration are covered by tests/test_gpu_grid_stride.py.
 """
 import numpy as np
 import pytest
