@@ -14,7 +14,7 @@
  *     component, cf. the RayHitT offsets in src/render/scene_native.inl:106-113).
  *   - Every call is asynchronous and ordered on the caller's `stream`
  *     (a hipStream_t passed as void*; NULL = default stream).  No hidden
- *     synchronisation except where stated (hf_bbox, hf_get_mip).
+ *     synchronisation except where stated (hf_bbox, hf_get_mip, hf_get_node_level).
  *   - `active` (uint8 per lane, NULL = all lanes active) mirrors the `Mask active`
  *     argument of the reference methods; inactive lanes produce a miss /
  *     zero-initialised record (include/mitsuba/render/interaction.h:479-499, 667-673).
@@ -36,13 +36,14 @@
  *         without a reset in between (distinct blocks); replays that run concurrently with other work of the same
  *         handle on other streams are ordered by the caller, as for any buffer the graph writes;
  *       * a replayed hf_set_heights / hf_adam_step does not record the handle's "built" event: after such a replay
- *         synchronise the replay's stream before hf_bbox, hf_get_mip, the packet entry points or hf_destroy;
+ *         synchronise the replay's stream before hf_bbox, hf_get_mip, hf_get_node_level, the packet entry points or
+ *         hf_destroy;
  *       * a captured launch snapshots the transform (to_world / to_object) by value: hf_set_transform after the
  *         capture does not reach the replays -- re-capture.
  *     The forward-mode entry points (hf_tangent, hf_direct_lighting_weighted_tangent, hf_point_lighting_tangent) are
  *     capturable as well: they reserve no scratch block, allocate nothing and never synchronise the host.
- *     Not capturable: hf_create / hf_destroy, hf_set_heights_host, hf_bbox, hf_get_mip and the host-pointer packet
- *     entry (they synchronise); hf_set_face_normals and hf_set_area_sampling (refused with HF_EINVAL), hf_surface_area
+ *     Not capturable: hf_create / hf_destroy, hf_set_heights_host, hf_bbox, hf_get_mip, hf_get_node_level and the
+ *     host-pointer packet entry (they synchronise); hf_set_face_normals and hf_set_area_sampling (refused with HF_EINVAL), hf_surface_area
  *     and, with smooth shading or area sampling, hf_set_transform (they synchronise).  hf_sample_position and its
  *     adjoint / tangent are capturable like the other wavefront entry points (no scratch block), and so are
  *     hf_eval_attribute and its adjoint / tangent (the attribute buffer is the caller's).  The four hf_sky_* entries
@@ -991,6 +992,12 @@ int hf_num_levels(const hf_field_t *hf);
 /* copies mip level `level` (1..num_levels) to HOST memory as (min,max) pairs,
  * row-major w x h; out may be NULL to query w,h.  Synchronises. */
 int hf_get_mip(const hf_field_t *hf, int level, float *h_out, uint32_t *w, uint32_t *h);
+/* copies the acceleration data of the nodes of level `level` (1..num_levels) to HOST memory exactly as stored: the
+ * whole padded level, *side x *side slots with *side = 2^(num_levels - level), row-major by (iy, ix), nodes beyond
+ * the grid included.  h_records: 12 floats per slot, the node record the traversal reads,
+ * { a, b, c, f, lo0, hi0, lo1, hi1, lo2, hi2, lo3, hi3 }; h_minmax: 2 floats per slot, the (min, max) of the pyramid
+ * at the same depth.  Either output may be NULL (both: queries *side).  Synchronises; not capturable. */
+int hf_get_node_level(const hf_field_t *hf, int level, float *h_records, float *h_minmax, uint32_t *side);
 /* inverse of a row-major 3x4 affine matrix (double precision, rounded to float) */
 int hf_invert_affine(const float in[12], float out[12]);
 /* blocks (of 256 threads) that a grid-stride launch of n items gets, HF_FORCE_GRID included.  family: 0 the flat cap

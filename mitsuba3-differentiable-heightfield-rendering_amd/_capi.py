@@ -209,6 +209,7 @@ SYMBOLS = {
     "hf_num_levels": (C.c_int, [C.c_void_p]),
     "hf_get_mip": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint32),
                              C.POINTER(C.c_uint32)]),
+    "hf_get_node_level": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "hf_invert_affine": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "hf_grid_blocks": (C.c_int, [C.c_size_t, C.c_int]),
     "hf_last_error_string": (C.c_char_p, []),

@@ -690,6 +690,23 @@ extern "C" int hf_get_mip(const hf_field_t *hf, int level, float *h_out, uint32_
     return HF_OK;
 }
 
+extern "C" int hf_get_node_level(const hf_field_t *hf, int level, float *h_records, float *h_minmax, uint32_t *side) {
+    if (!hf || level < 1 || level > hf->dev.top) return fail(HF_EINVAL, "hf_get_node_level: bad level %d", level);
+    const int k = hf->dev.top - level;
+    const size_t slots = (size_t) 1 << (2 * k); // the whole padded level, as stored
+    if (side) *side = 1u << k;
+    if (h_records || h_minmax) {
+        hf_device_guard guard(hf->device);
+        HF_HIP(hipEventSynchronize(hf->built));
+        if (h_records)
+            HF_HIP(hipMemcpy(h_records, hf->d_shear + (size_t) (hf_depth_off(k) - 1u) * 3, sizeof(float4) * 3 * slots,
+                             hipMemcpyDeviceToHost));
+        if (h_minmax)
+            HF_HIP(hipMemcpy(h_minmax, hf->d_mip + hf_depth_off(k), sizeof(float2) * slots, hipMemcpyDeviceToHost));
+    }
+    return HF_OK;
+}
+
 // world-space box of the 8 corners of the object-space bound (analog: rectangle.cpp:114-124)
 extern "C" int hf_bbox(hf_field_t *hf, float out[6]) {
     if (!hf || !out) return fail(HF_EINVAL, "hf_bbox: NULL argument");

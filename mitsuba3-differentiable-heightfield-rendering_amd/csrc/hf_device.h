@@ -98,8 +98,10 @@ __host__ __device__ __forceinline__ uint32_t hf_depth_off(int k) { return (0x555
 // units, (xc,yc) the node centre) and, per child, the exact range of  z - plane  over the child's
 // vertices: the box test of the walk then runs in the sheared coordinate  w = z - plane, in which
 // the ray is still a straight line.  Any plane is valid (the ranges are exact for the plane that is
-// stored); record = { (a, b, c, |a|+|b|), (lo0, hi0, lo1, hi1), (lo2, hi2, lo3, hi3) }, children in
-// actual order j = 2 jy + jx, absent children (+inf, -inf).  Same coarse-first indexing as the
+// stored); record = { (a, b, c, f), (lo0, hi0, lo1, hi1), (lo2, hi2, lo3, hi3) }, children in
+// actual order j = 2 jy + jx, absent children (+inf, -inf).  The slope factor f = |a|+|b| + 2 max_j(hi_j - lo_j)
+// over the existing children (the needle term, see hf_shear_kernel in hf_kernels.hip).  Levels above HF_SHEAR_TOP
+// store the zero plane and the children's min/max boxes in the same form.  Same coarse-first indexing as the
 // pyramid: node (ix,iy) of level L = depth k = top - L is record  hf_depth_off(k) - 1 + (iy << k) + ix.
 #ifndef HF_SHEAR_TOP
 #define HF_SHEAR_TOP 5

@@ -967,6 +967,16 @@ class Heightfield:
         check(_capi.lib().hf_get_mip(self._h, level, out.data_ptr(), C.byref(w), C.byref(h)))
         return out
 
+    def node_level(self, level):
+        """the acceleration data of level `level` as stored, padded slots included: (records [side, side, 12] =
+        (a, b, c, f, lo0, hi0, .., lo3, hi3) per node, minmax [side, side, 2]), side = 2^(num_levels - level)"""
+        side = C.c_uint32()
+        check(_capi.lib().hf_get_node_level(self._h, level, None, None, C.byref(side)))
+        rec = torch.empty((side.value, side.value, 12), dtype=torch.float32)
+        mm = torch.empty((side.value, side.value, 2), dtype=torch.float32)
+        check(_capi.lib().hf_get_node_level(self._h, level, rec.data_ptr(), mm.data_ptr(), C.byref(side)))
+        return rec, mm
+
     # ---- helpers -------------------------------------------------------------------------
     def _stream(self):
         return _stream_of(self.device)
