@@ -49,7 +49,8 @@
  *     hf_eval_attribute and its adjoint / tangent (the attribute buffer is the caller's).  The four hf_sky_* entries
  *     are capturable too: hf_sky_lighting traces without a work counter (one workgroup per 256 samples), so unlike the
  *     other trace launches it reserves no scratch block and does not count towards the 32.
- *     The four hf_bounce_* entries are capturable in the same way.
+ *     The four hf_bounce_* entries are capturable in the same way, and so are the hf_envmap_* entries, the table
+ *     build included (the map and its table are the caller's buffers).
  */
 #ifndef HF_H
 #define HF_H
@@ -704,6 +705,105 @@ int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], 
                             const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
                             float radiance, float albedo, const uint32_t *vis_bits, const float *const dsh_n[3],
                             const float *dweight, float *dimage, hf_stream_t stream);
+
+/* ---- next row: environment-map lighting, importance-sampled, the shadow rays traced in the kernel ----
+ *
+ * hf_sky_lighting with a direction-dependent environment: the reference's `envmap` emitter (src/emitters/envmap.cpp), one
+ * channel, sampled by importance and differentiable in its texels.
+ *   data        data[H][W] float32, row-major, scalar radiance, the CALLER's device buffer (W >= 2, H >= 2).  Row 0 is the
+ *               map's north pole (theta = 0, local +Y); column W - 1 is the seam column, a copy of column 0
+ *               (envmap.cpp:147, 249-258) -- the entries do not check it.
+ *   radiance    in cell (cx, cy) at fractions (fx, fy): eval_spectrum's non-spectral branch (envmap.cpp:498-555),
+ *               v0 = fma(1 - fx, v00, fx v10), v1 = fma(1 - fx, v01, fx v11), L = fma(1 - fy, v0, fy v1).
+ *   direction   of uv = ((cx + fx + 1/2) / (W - 1), (cy + fy) / (H - 1)): theta = pi uv.y, phi = 2 pi uv.x, local
+ *               d = (sin theta sin phi, cos theta, -sin theta cos phi) (envmap.cpp:393-397, 406), world w = R d.
+ *               rot: 9 HOST floats, a row-major rotation, NULL = identity, detached.
+ *   distribution piecewise constant over the (W - 1)(H - 1) bilinear cells (NOT the reference's Hierarchical2D; the sample
+ *               streams differ from its PCG32 anyway):  weight_c = sin(pi (cy + 1/2) / (H - 1)) ((1 - u) m_c + u mbar),
+ *               m_c = the mean of max(texel, 0) over the cell's corners, mbar = the mean of m_c, u in [0, 1] a DEFENSIVE
+ *               fraction given at build time (0: proportional to luminance; > 0 keeps dark texels reachable while the
+ *               texels are optimised).  Detached (direct_reparam.py:152-160).  In float32:
+ *               m_c = 0.25 ((p00 + p10) + (p01 + p11)), weight_c = s ((1 - u) m_c + u mbar), s the sine evaluated in
+ *               double and rounded once; one rounding per operation, nothing fused.
+ *   table       hf_envmap_table_floats(W, H) = 4 + (H - 1) + (H - 1)(W - 1) floats, the caller's: header {Sigma, mbar, u,
+ *               0}; the marginal M, H - 1 inclusive prefix sums of the row sums (the last is Sigma); the conditional
+ *               C[cy], W - 1 inclusive prefix sums of weight_c per cell row.  A conditional entry is the fp64 running sum
+ *               of the row's float32 weights in cell order, rounded once; rowsum_cy = C[cy][W - 2]; a marginal entry is
+ *               the fp64 running sum of the float32 rowsums in row order, rounded once; mbar = the fp64 sum in row order of
+ *               the rows' float32-rounded fp64 sums of m_c, divided by the cell count, rounded once.  Bitwise the same
+ *               from build to build.
+ *   draw        direction k of sample i from (s.x, s.y), the TEA stream of hf_sky_* (pair = k, id_i = i or ray_id[i]);
+ *               float32, one rounding per step:  y = s.y Sigma, cy = the first row with !(M[cy] < y) (H - 2 if none),
+ *               fy = clamp((y - M[cy - 1]) / rowsum_cy, 0, 1 - 2^-24) (M[-1] = 0);  x = s.x rowsum_cy, cx = the first cell
+ *               with !(C[cy][cx] < x) (W - 2 if none), fx = clamp((x - C[cy][cx - 1]) / weight_c, 0, 1 - 2^-24) with
+ *               weight_c RECOMPUTED from the four texels and the header.  Sigma = 0 or weight_c <= 0: the draw is INVALID,
+ *               it is not traced and contributes exactly 0 (its fractions are reported as 0: a finite direction).
+ *   value       pdf_uv = weight_c (W - 1)(H - 1) / Sigma, pdf_w = pdf_uv / (2 pi^2 sin theta) (envmap.cpp:403-415);
+ *               E_k = L_k 2 pi^2 sin theta_k / pdf_uv;
+ *               value_i = weight_i (albedo / (pi K)) sum_k bit_ik <sh_n_i, w_k> E_k;  image[i / spp] = 1/spp sum value_i.
+ *   masks       hf_sky_lighting's: eligible when t is finite and <sh_n, -d> > 0; direction k is TRACED when the sample is
+ *               eligible, the draw valid and <sh_n, w_k> > 0; shadow ray spawn_ray(w_k), maxt = +inf; bit k of vis_bits[i]
+ *               is set iff direction k was traced and is unoccluded; the box film and spp as there.
+ * The ray takes the float32 direction; the shading sums take the same draw's direction and E_k in double, rounded once.
+ * Attached: sh_n, weight and data (through L_k only).  Not differentiated: visibility, the masks, the table, rot.
+ * All entries: device pointers and a stream, no allocation, no host synchronisation, capturable without a scratch block.
+ * NULL pointers (other than those marked optional), W < 2 or H < 2, u outside [0, 1] or not finite, num_rays outside
+ * 1..32 (hf_envmap_rays: k >= 32), n % spp != 0, spp == 0, n >= 2^32 and a non-finite albedo or rot are refused with
+ * HF_EINVAL before anything touches a device.  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+/* the table's size in floats; 0 for W < 2 or H < 2 */
+size_t hf_envmap_table_floats(uint32_t W, uint32_t H);
+/* builds the table of `data` (three launches: the rows' sums of m_c, the conditional rows, the marginal and the header) */
+int hf_envmap_build_table(uint32_t W, uint32_t H, const float *data, float u, float *table, hf_stream_t stream);
+/* Emitter::sample_direction for caller-supplied samples (sample: 2 device rows of n floats in [0, 1)): out_d the float32
+ * direction the rays take, out_weight = E, out_pdf = pdf_w (both 0 for an invalid draw), out_cell = cy (W - 1) + cx
+ * (n uint32, may be NULL), out_frac = (fx, fy), the position in the cell (2 rows of n floats, may be NULL).
+ * NOTE the parameter list: out_frac is an output that Emitter::sample_direction does not have (the fractions of the draw,
+ * which no other output determines bit for bit), and it stands BETWEEN out_cell and stream -- a caller that passes the
+ * stream right after out_cell is passing it as out_frac.  Pass NULL there when the fractions are not wanted. */
+int hf_envmap_sample_direction(size_t n, const float *const sample[2], uint32_t W, uint32_t H, const float *data,
+                               const float *table, const float rot[9], float *const out_d[3], float *out_weight,
+                               float *out_pdf, uint32_t *out_cell, float *const out_frac[2], hf_stream_t stream);
+/* Emitter::eval for world directions d (envmap.cpp:323-333, 498-509), evaluated in double and rounded once: v = R^T d, uv = (atan2(v.x, -v.z) / 2 pi,
+ * acos(clamp(v.y, -1, 1)) / pi), uv.x -= 1/2 / (W - 1), uv -= floor(uv), the cell min(uint(uv (res - 1)), res - 2) and the
+ * bilinear value; lanes with active[i] == 0 get 0 (active may be NULL: every lane).  The map is linear in data: called
+ * with a tangent of the texels in place of data it is the tangent. */
+int hf_envmap_eval(size_t n, const float *const d[3], const uint8_t *active, uint32_t W, uint32_t H, const float *data,
+                   const float rot[9], float *out, hf_stream_t stream);
+/* its transpose: grad_data[H][W] += grad_out[i] * (bilinear weight) on the four texels of every active lane (each product
+ * formed in double and rounded once), float atomics; ACCUMULATED into, like grad_heightfield. */
+int hf_envmap_eval_adjoint(size_t n, const float *const d[3], const uint8_t *active, uint32_t W, uint32_t H,
+                           const float rot[9], const float *grad_out, float *grad_data, hf_stream_t stream);
+/* shadow ray k of every sample, as hf_sky_rays: maxt = +inf where direction k is traced, -1 elsewhere; out_weight (n floats,
+ * may be NULL) = E_k, 0 for an invalid draw.  Takes no field handle. */
+int hf_envmap_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                   const float *const d[3], const float *t, uint32_t k, uint32_t seed, const uint32_t *ray_id, uint32_t W,
+                   uint32_t H, const float *data, const float *table, const float rot[9], float *const out_o[3],
+                   float *const out_d[3], float *out_maxt, float *out_weight, hf_stream_t stream);
+/* The fused launch (hf_sky_lighting's mapping: one lane per sample, one workgroup per 256 samples, no work counter): equals
+ * hf_envmap_rays + hf_ray_test bit for bit in the visibility word.  weight: n floats or NULL (1); vis_bits may be NULL. */
+int hf_envmap_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                       const float *const sh_n[3], const float *const d[3], const float *t, const float *weight,
+                       uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data,
+                       const float *table, const float rot[9], float albedo, float *image, uint32_t *vis_bits,
+                       hf_stream_t stream);
+/* Reverse mode.  Traces nothing: the directions are drawn again and vis_bits read.  With g = grad_image[i / spp] / spp,
+ * c = albedo / (pi K) and G_k = E_k / L_k:
+ *   grad_sh_n[i] = g weight_i c sum_k bit_ik E_k w_k,   grad_weight[i] = g c sum_k bit_ik <sh_n_i, w_k> E_k
+ * overwritten (grad_weight may be NULL), sums in k order, no atomics: bitwise the same from launch to launch;
+ *   grad_data[texel j of the cell of direction k] += g weight_i c bit_ik <sh_n_i, w_k> G_k b_j   (b: the bilinear weights)
+ * accumulated with float atomics; grad_data ([H][W]) may be NULL.  Takes no field handle. */
+int hf_envmap_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                               const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t W,
+                               uint32_t H, const float *data, const float *table, const float rot[9], float albedo,
+                               const uint32_t *vis_bits, const float *grad_image, float *const grad_sh_n[3],
+                               float *grad_weight, float *grad_data, hf_stream_t stream);
+/* Forward mode, the transpose of the adjoint, for tangents dsh_n (3 rows), dweight (n) and ddata ([H][W]; it enters through
+ * L_k with the PRIMAL table), each may be NULL (zero); dimage overwritten.  No atomics for any spp. */
+int hf_envmap_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                               const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t W,
+                               uint32_t H, const float *data, const float *table, const float rot[9], float albedo,
+                               const uint32_t *vis_bits, const float *const dsh_n[3], const float *dweight,
+                               const float *ddata, float *dimage, hf_stream_t stream);
 
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *

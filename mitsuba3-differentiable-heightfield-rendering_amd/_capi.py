@@ -154,6 +154,30 @@ SYMBOLS = {
     "hf_sky_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp,
                                           C.c_uint32, C.c_uint32, _fp, C.c_float, C.c_float, _fp, C.POINTER(_fp * 3), _fp,
                                           _fp, C.c_void_p]),
+    "hf_envmap_table_floats": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "hf_envmap_build_table": (C.c_int, [C.c_uint32, C.c_uint32, _fp, C.c_float, _fp, C.c_void_p]),
+    "hf_envmap_sample_direction": (C.c_int, [C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, C.c_uint32, _fp, _fp,
+                                             C.POINTER(C.c_float * 9), C.POINTER(_fp * 3), _fp, _fp, _fp, C.POINTER(_fp * 2),
+                                             C.c_void_p]),
+    "hf_envmap_eval": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), _fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_float * 9),
+                                 _fp, C.c_void_p]),
+    "hf_envmap_eval_adjoint": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), _fp, C.c_uint32, C.c_uint32,
+                                         C.POINTER(C.c_float * 9), _fp, _fp, C.c_void_p]),
+    "hf_envmap_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                 _fp, C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _fp, _fp,
+                                 C.POINTER(C.c_float * 9), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_void_p]),
+    "hf_envmap_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                     C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32, C.c_uint32, _fp,
+                                     C.c_uint32, C.c_uint32, _fp, _fp, C.POINTER(C.c_float * 9), C.c_float, _fp, _fp,
+                                     C.c_void_p]),
+    "hf_envmap_lighting_adjoint": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp,
+                                             C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _fp, _fp,
+                                             C.POINTER(C.c_float * 9), C.c_float, _fp, _fp, C.POINTER(_fp * 3), _fp, _fp,
+                                             C.c_void_p]),
+    "hf_envmap_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp,
+                                             C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _fp, _fp,
+                                             C.POINTER(C.c_float * 9), C.c_float, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp,
+                                             C.c_void_p]),
     "hf_bounce_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
                                  C.POINTER(_fp * 3), _fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_float * 3),
                                  C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_void_p]),

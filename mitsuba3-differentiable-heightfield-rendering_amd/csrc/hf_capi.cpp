@@ -1212,6 +1212,176 @@ extern "C" int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *cons
     return HF_OK;
 }
 
+// ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----
+// What the hf_envmap_* entries share: the checks of the map (all of them before anything touches a device) ...
+static int envmap_map(const char *who, uint32_t W, uint32_t H, const float *data, bool need_data, const float *table,
+                      bool need_table, const float rot[9], hf_envmap_args &a) {
+    if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the map must have at least 2 x 2 texels (got %u x %u)", who, W, H);
+    if ((need_data && !data) || (need_table && !table)) return fail(HF_EINVAL, "%s: NULL argument", who);
+    a = {};
+    a.W = W; a.H = H; a.data = data; a.table = table;
+    for (int j = 0; j < 9; ++j) {
+        a.rot[j] = rot ? rot[j] : (j % 4 == 0 ? 1.f : 0.f);
+        if (!isfinite(a.rot[j])) return fail(HF_EINVAL, "%s: rot must be finite", who);
+    }
+    return HF_OK;
+}
+// ... and of the wavefront, for the four entries that light one (hf_envmap_rays passes spp 1, num_rays k + 1, albedo 1)
+static int envmap_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                       const float *t, const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
+                       uint32_t W, uint32_t H, const float *data, const float *table, const float rot[9], float albedo,
+                       hf_envmap_args &a) {
+    if (!all3(sh_n) || !all3(d) || !t) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 directions per sample (got %u)", who, num_rays);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    const int rc = envmap_map(who, W, H, data, true, table, true, rot, a);
+    if (rc != HF_OK) return rc;
+    a.n = n; a.spp = spp; a.num_rays = num_rays; a.seed = seed; a.ray_id = ray_id; a.t = t; a.weight = weight;
+    a.scale = (float) ((double) albedo / (3.141592653589793 * (double) num_rays));
+    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
+    return HF_OK;
+}
+
+extern "C" size_t hf_envmap_table_floats(uint32_t W, uint32_t H) {
+    if (W < 2 || H < 2) return 0;
+    return 4 + (size_t) (H - 1) + (size_t) (H - 1) * (size_t) (W - 1);
+}
+
+extern "C" int hf_envmap_build_table(uint32_t W, uint32_t H, const float *data, float u, float *table, hf_stream_t stream) {
+    const char *fn = "hf_envmap_build_table";
+    hf_envmap_args a;
+    const int rc = envmap_map(fn, W, H, data, true, table, true, nullptr, a);
+    if (rc != HF_OK) return rc;
+    if (!(u >= 0.f && u <= 1.f)) return fail(HF_EINVAL, "%s: the defensive fraction must lie in [0, 1] (got %g)", fn, (double) u);
+    hf_launch_envmap_build(W, H, data, u, table, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_envmap_sample_direction(size_t n, const float *const sample[2], uint32_t W, uint32_t H, const float *data,
+                                          const float *table, const float rot[9], float *const out_d[3], float *out_weight,
+                                          float *out_pdf, uint32_t *out_cell, float *const out_frac[2],
+                                          hf_stream_t stream) {
+    const char *fn = "hf_envmap_sample_direction";
+    hf_envmap_args a;
+    const int rc = envmap_map(fn, W, H, data, true, table, true, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!sample || !sample[0] || !sample[1] || !all3(out_d) || !out_weight || !out_pdf) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (out_frac && (!out_frac[0] || !out_frac[1])) return fail(HF_EINVAL, "%s: NULL out_frac component array", fn);
+    if (out_frac) { a.out_frac[0] = out_frac[0]; a.out_frac[1] = out_frac[1]; }
+    a.n = n; a.sample[0] = sample[0]; a.sample[1] = sample[1]; a.out_weight = out_weight; a.out_pdf = out_pdf; a.out_cell = out_cell;
+    for (int c = 0; c < 3; ++c) a.out_d[c] = out_d[c];
+    hf_launch_envmap(4, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_envmap_eval(size_t n, const float *const d[3], const uint8_t *active, uint32_t W, uint32_t H,
+                              const float *data, const float rot[9], float *out, hf_stream_t stream) {
+    const char *fn = "hf_envmap_eval";
+    hf_envmap_args a;
+    const int rc = envmap_map(fn, W, H, data, true, nullptr, false, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(d) || !out) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.n = n; a.active = active; a.out = out;
+    for (int c = 0; c < 3; ++c) a.d[c] = d[c];
+    hf_launch_envmap(5, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_envmap_eval_adjoint(size_t n, const float *const d[3], const uint8_t *active, uint32_t W, uint32_t H,
+                                      const float rot[9], const float *grad_out, float *grad_data, hf_stream_t stream) {
+    const char *fn = "hf_envmap_eval_adjoint";
+    hf_envmap_args a;
+    const int rc = envmap_map(fn, W, H, nullptr, false, nullptr, false, rot, a); // (the map is linear: its values are not read)
+    if (rc != HF_OK) return rc;
+    if (!grad_data) return fail(HF_EINVAL, "%s: grad_data is NULL", fn);
+    if (!all3(d) || !grad_out) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.n = n; a.active = active; a.gout = grad_out; a.gdata = grad_data;
+    for (int c = 0; c < 3; ++c) a.d[c] = d[c];
+    hf_launch_envmap(6, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_envmap_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                              const float *const d[3], const float *t, uint32_t k, uint32_t seed, const uint32_t *ray_id,
+                              uint32_t W, uint32_t H, const float *data, const float *table, const float rot[9],
+                              float *const out_o[3], float *const out_d[3], float *out_maxt, float *out_weight,
+                              hf_stream_t stream) {
+    const char *fn = "hf_envmap_rays";
+    hf_envmap_args a;
+    if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
+    const int rc = envmap_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, W, H, data, table, rot, 1.f, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.k = k; a.out_maxt = out_maxt; a.out_weight = out_weight;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
+    hf_launch_envmap(3, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_envmap_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                  const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                  const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                                  const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data, const float *table,
+                                  const float rot[9], float albedo, float *image, uint32_t *vis_bits, hf_stream_t stream) {
+    const char *fn = "hf_envmap_lighting";
+    hf_envmap_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = envmap_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, W, H, data, table, rot, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = image; a.vis_bits = vis_bits;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    hf_launch_envmap(0, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_envmap_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                          const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                                          const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data,
+                                          const float *table, const float rot[9], float albedo, const uint32_t *vis_bits,
+                                          const float *grad_image, float *const grad_sh_n[3], float *grad_weight,
+                                          float *grad_data, hf_stream_t stream) {
+    const char *fn = "hf_envmap_lighting_adjoint";
+    hf_envmap_args a;
+    const int rc = envmap_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, W, H, data, table, rot, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits || !grad_image || !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.gimg = grad_image; a.gw = grad_weight; a.gdata = grad_data;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n[c];
+    hf_launch_envmap(1, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_envmap_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                          const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                                          const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data,
+                                          const float *table, const float rot[9], float albedo, const uint32_t *vis_bits,
+                                          const float *const dsh_n[3], const float *dweight, const float *ddata,
+                                          float *dimage, hf_stream_t stream) {
+    const char *fn = "hf_envmap_lighting_tangent";
+    hf_envmap_args a;
+    const int rc = envmap_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, W, H, data, table, rot, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits || !dimage) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.image = dimage; a.dw = dweight; a.ddata = ddata;
+    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    hf_launch_envmap(2, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- bounce lighting: one diffuse interreflection, both rays traced inside the lighting kernel ----
 // What the four hf_bounce_* entries share: the checks (all of them before anything touches a device) and the argument
 // block.  hf_bounce_rays passes spp 1, num_rays k + 1, albedo 1 and either no light or its one direction.

@@ -5126,3 +5126,465 @@ void hf_launch_param_tangent(const hf_dev_field &f, size_t n, const float *const
     }
     hipLaunchKernelGGL(vn ? hf_param_tangent_smooth_kernel : hf_param_tangent_kernel, grid, block, 0, stream, p);
 }
+
+// ---------------------------------------------------------------------------------
+// Environment-map lighting (include/hf.h hf_envmap_*): diffuse surface under a latitude-longitude radiance map
+// (src/emitters/envmap.cpp), the K = num_rays emitter samples of every wavefront sample drawn by importance sampling of
+// the map, traced (any hit, per lane) and reduced in ONE launch: hf_sky_kernel's mapping, with the draw (two binary
+// searches of the caller's table, four texels, the angles and the rotation) in place of the uniform sphere.
+// ---------------------------------------------------------------------------------
+// sin(pi x), cos(pi x) in double for x in [0, 4): sky_dir_f64's quadrant reduction and Taylor sums (first dropped terms
+// 7e-12 and 4e-13), a dozen fmas and no call
+__device__ __forceinline__ void env_sincospi_f64(double x, double &sn, double &cs) {
+    const double q = rint(2.0 * x), t = x - 0.5 * q;
+    const double a = 3.141592653589793 * t, a2 = a * a;
+    double ps = -1.0 / 39916800.0, pc = 1.0 / 479001600.0;
+    ps = fma(ps, a2, 1.0 / 362880.0); ps = fma(ps, a2, -1.0 / 5040.0); ps = fma(ps, a2, 1.0 / 120.0);
+    ps = fma(ps, a2, -1.0 / 6.0); ps = fma(ps, a2, 1.0); ps *= a;
+    pc = fma(pc, a2, -1.0 / 3628800.0); pc = fma(pc, a2, 1.0 / 40320.0); pc = fma(pc, a2, -1.0 / 720.0);
+    pc = fma(pc, a2, 1.0 / 24.0); pc = fma(pc, a2, -0.5); pc = fma(pc, a2, 1.0);
+    const int qi = (int) q & 3;
+    sn = qi == 0 ? ps : qi == 1 ? pc : qi == 2 ? -ps : -pc;
+    cs = qi == 0 ? pc : qi == 1 ? -ps : qi == 2 ? -pc : ps;
+}
+// the solid-angle factor of cell row cy: sin(pi (cy + 1/2) / (H - 1)), evaluated in double and rounded once
+__device__ __forceinline__ float env_row_sin(uint32_t cy, uint32_t H) {
+    double sn, cs;
+    env_sincospi_f64(((double) cy + 0.5) / (double) (H - 1u), sn, cs);
+    return (float) sn;
+}
+// m_c: the mean of max(texel, 0) over the four corners of cell (cx, cy); float32, this association
+__device__ __forceinline__ float env_cell_mean(float v00, float v10, float v01, float v11) {
+    return 0.25f * ((fmaxf(v00, 0.f) + fmaxf(v10, 0.f)) + (fmaxf(v01, 0.f) + fmaxf(v11, 0.f)));
+}
+// weight_c = sin_cy ((1 - u) m_c + u mbar): float32, one rounding per step, no fused step
+__device__ __forceinline__ float env_cell_weight(float mc, float rs, float u, float mbar) {
+    return rs * ((1.f - u) * mc + u * mbar);
+}
+#define HF_ENV_HEADER 4u // {Sigma, mbar, u, 0}, then the marginal (H - 1), then the conditional rows ((H - 1)(W - 1))
+
+// thread 0 adds s[0 .. cnt) to acc in order (fp64) and, with `out`, writes every running sum rounded once
+__device__ __forceinline__ double env_chain(const double *s, uint32_t cnt, double acc, float *out) {
+    for (uint32_t j = 0; j < cnt; ++j) {
+        acc += s[j];
+        if (out) out[j] = (float) acc;
+    }
+    return acc;
+}
+// mbar from the rows' sums of m_c that pass 1 left in the marginal's slots: their fp64 sum in row order / the cell count
+__device__ __forceinline__ float env_mbar(const float *table, uint32_t W, uint32_t H) {
+    double s = 0.0;
+    for (uint32_t r = 0; r + 1u < H; ++r) s += (double) table[HF_ENV_HEADER + r];
+    return (float) (s / ((double) (W - 1u) * (double) (H - 1u)));
+}
+// PASS 0: the sum of m_c of every cell row -> the row's slot of the marginal (float32; read back by the next two passes)
+// PASS 1: the conditional prefix sums of every cell row
+template <int PASS>
+__global__ __launch_bounds__(HF_BLOCK) void hf_envmap_rows_kernel(uint32_t W, uint32_t H, const float *__restrict__ data, float u,
+                                                                 float *__restrict__ table) {
+    __shared__ double s_val[HF_BLOCK];
+    __shared__ float s_mbar;
+    const uint32_t cy = blockIdx.x, ncx = W - 1u;
+    if (PASS == 1 && threadIdx.x == 0) s_mbar = env_mbar(table, W, H);
+    __syncthreads();
+    const float mbar = PASS == 1 ? s_mbar : 0.f, rs = env_row_sin(cy, H);
+    float *crow = table + HF_ENV_HEADER + (H - 1u) + (size_t) cy * ncx;
+    double acc = 0.0;
+    for (uint32_t c0 = 0; c0 < ncx; c0 += HF_BLOCK) {
+        const uint32_t cx = c0 + threadIdx.x;
+        double v = 0.0;
+        if (cx < ncx) {
+            const size_t r0 = (size_t) cy * W + cx, r1 = r0 + W;
+            const float mc = env_cell_mean(data[r0], data[r0 + 1], data[r1], data[r1 + 1]);
+            v = (double) (PASS == 0 ? mc : env_cell_weight(mc, rs, u, mbar));
+        }
+        s_val[threadIdx.x] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) acc = env_chain(s_val, min(ncx - c0, (uint32_t) HF_BLOCK), acc, PASS == 1 ? crow + c0 : nullptr);
+        __syncthreads();
+    }
+    if (PASS == 0 && threadIdx.x == 0) table[HF_ENV_HEADER + cy] = (float) acc;
+}
+// the marginal: the fp64 running sum, in row order, of the float32 row sums (the last conditional entry of a row), and the header
+__global__ void hf_envmap_marginal_kernel(uint32_t W, uint32_t H, float u, float *__restrict__ table) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const float mbar = env_mbar(table, W, H); // (before the slots are overwritten)
+    const uint32_t ncx = W - 1u;
+    const float *cond = table + HF_ENV_HEADER + (H - 1u);
+    double acc = 0.0;
+    float last = 0.f;
+    for (uint32_t r = 0; r + 1u < H; ++r) {
+        acc += (double) cond[(size_t) r * ncx + (ncx - 1u)];
+        table[HF_ENV_HEADER + r] = last = (float) acc;
+    }
+    table[0] = last; table[1] = mbar; table[2] = u; table[3] = 0.f;
+}
+
+void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream) {
+    hipLaunchKernelGGL(hf_envmap_rows_kernel<0>, dim3(H - 1u), dim3(HF_BLOCK), 0, stream, W, H, data, u, table);
+    hipLaunchKernelGGL(hf_envmap_rows_kernel<1>, dim3(H - 1u), dim3(HF_BLOCK), 0, stream, W, H, data, u, table);
+    hipLaunchKernelGGL(hf_envmap_marginal_kernel, dim3(1), dim3(64), 0, stream, W, H, u, table);
+}
+
+// ---- the draw ----
+// first index in [0, n) whose entry is not below x (n - 1 if there is none): a branch-free lower bound, the trip count
+// depends on n alone (wave-uniform)
+__device__ __forceinline__ uint32_t env_lower_bound(const float *__restrict__ T, uint32_t n, float x) {
+    uint32_t base = 0u;
+    for (uint32_t len = n; len > 1u;) {
+        const uint32_t half = len >> 1;
+        base += (T[base + half - 1u] < x) ? half : 0u;
+        len -= half;
+    }
+    base += (T[base] < x) ? 1u : 0u;
+    return base < n ? base : n - 1u;
+}
+// one draw: the cell, the position in it, the cell's four texels, its weight (recomputed from the texels and the header)
+struct hf_env_draw {
+    uint32_t cx, cy;
+    float fx, fy, wc, sigma;
+    float v00, v10, v01, v11;
+    bool valid;
+};
+#define HF_ENV_ONE_BELOW 0.99999994f // 1 - 2^-24
+__device__ __forceinline__ hf_env_draw env_draw(const float *__restrict__ data, const float *__restrict__ table, uint32_t W,
+                                                uint32_t H, float sx, float sy) {
+    hf_env_draw r;
+    const uint32_t ncx = W - 1u, ncy = H - 1u;
+    const float *M = table + HF_ENV_HEADER, *C = M + ncy;
+    r.sigma = table[0];
+    const float mbar = table[1], u = table[2];
+    const float y = sy * r.sigma;
+    r.cy = env_lower_bound(M, ncy, y);
+    const float *row = C + (size_t) r.cy * ncx;
+    const float rowsum = row[ncx - 1u];
+    r.fy = fminf(fmaxf((y - (r.cy ? M[r.cy - 1u] : 0.f)) / rowsum, 0.f), HF_ENV_ONE_BELOW);
+    const float x = sx * rowsum;
+    r.cx = env_lower_bound(row, ncx, x);
+    const size_t r0 = (size_t) r.cy * W + r.cx, r1 = r0 + W;
+    r.v00 = data[r0]; r.v10 = data[r0 + 1]; r.v01 = data[r1]; r.v11 = data[r1 + 1];
+    r.wc = env_cell_weight(env_cell_mean(r.v00, r.v10, r.v01, r.v11), env_row_sin(r.cy, H), u, mbar);
+    r.fx = fminf(fmaxf((x - (r.cx ? row[r.cx - 1u] : 0.f)) / r.wc, 0.f), HF_ENV_ONE_BELOW);
+    r.valid = r.sigma > 0.f && r.wc > 0.f;
+    if (!r.valid) { r.fx = 0.f; r.fy = 0.f; } // (a corner of the cell: an invalid draw still has a finite direction)
+    return r;
+}
+// the rotation (row-major) of a local direction
+__device__ __forceinline__ v3 env_rotate(const float *R, v3 d) {
+    return mk3(__builtin_fmaf(R[2], d.z, __builtin_fmaf(R[1], d.y, R[0] * d.x)),
+               __builtin_fmaf(R[5], d.z, __builtin_fmaf(R[4], d.y, R[3] * d.x)),
+               __builtin_fmaf(R[8], d.z, __builtin_fmaf(R[7], d.y, R[6] * d.x)));
+}
+// the float32 direction of a draw (what the ray takes): uv = ((cx + fx + 1/2) / (W - 1), (cy + fy) / (H - 1)), theta = pi
+// uv.y, phi = 2 pi uv.x, local (sin theta sin phi, cos theta, -sin theta cos phi) (envmap.cpp:393-397), world R d
+template <typename RT>
+__device__ __forceinline__ v3 env_dir(uint32_t cx, uint32_t cy, float fx, float fy, uint32_t W, uint32_t H, RT R) {
+    const float ux = ((float) cx + (fx + 0.5f)) / (float) (W - 1u);
+    // theta from the nearer pole: in the lower half uv.y = 1 - ((H - 1 - cy) - fy) / (H - 1), and the difference in the
+    // bracket is exact where it is small, so sin theta keeps its relative precision at the south pole as at the north
+    const bool south = 2u * cy + 1u >= H - 1u;
+    const float uy = (south ? (float) (H - 1u - cy) - fy : (float) cy + fy) / (float) (H - 1u);
+    float st, ct, sp, cp;
+    sincospif(uy, &st, &ct);
+    ct = south ? -ct : ct;
+    sincospif(2.f * ux, &sp, &cp);
+    const float rr[9] = { R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8] };
+    return env_rotate(rr, mk3(st * sp, ct, -(st * cp)));
+}
+// the same direction in double for the shading sums, and what the emitter weight is made of: L (the bilinear radiance,
+// envmap.cpp:498-555) and G = 2 pi^2 sin theta Sigma / (weight_c (W - 1)(H - 1)) = 1 / pdf_omega: E = L G.  bw: the four
+// bilinear weights (v00, v10, v01, v11)
+struct hf_env_shade { hf_d3 w; double L, G, bw[4]; };
+template <typename RT>
+__device__ __forceinline__ hf_d3 env_dir_f64(uint32_t cx, uint32_t cy, float fx, float fy, uint32_t W, uint32_t H, RT R, double &st) {
+    const double ux = ((double) cx + ((double) fx + 0.5)) / (double) (W - 1u), uy = ((double) cy + (double) fy) / (double) (H - 1u);
+    double ct, sp, cp;
+    env_sincospi_f64(uy, st, ct);
+    env_sincospi_f64(2.0 * ux, sp, cp);
+    const double x = st * sp, y = ct, z = -(st * cp);
+    return hf_d3{ (double) R[0] * x + (double) R[1] * y + (double) R[2] * z, (double) R[3] * x + (double) R[4] * y + (double) R[5] * z,
+                  (double) R[6] * x + (double) R[7] * y + (double) R[8] * z };
+}
+__device__ __forceinline__ double env_inv_pdf(float wc, float sigma, double st, uint32_t W, uint32_t H) {
+    return (19.739208802178716 * st * (double) sigma) / ((double) wc * ((double) (W - 1u) * (double) (H - 1u)));
+}
+__device__ __forceinline__ double env_bilinear(float fx, float fy, double v00, double v10, double v01, double v11) {
+    const double x1 = (double) fx, x0 = 1.0 - x1, y1 = (double) fy, y0 = 1.0 - y1;
+    return y0 * (x0 * v00 + x1 * v10) + y1 * (x0 * v01 + x1 * v11);
+}
+// E_k <sh_n, w_k> of a valid draw, in double
+template <typename RT>
+__device__ __forceinline__ double env_term(const hf_env_draw &r, v3 sn, uint32_t W, uint32_t H, RT R) {
+    double st;
+    const hf_d3 w = env_dir_f64(r.cx, r.cy, r.fx, r.fy, W, H, R, st);
+    return sky_dot_f64(sn, w) * (env_bilinear(r.fx, r.fy, r.v00, r.v10, r.v01, r.v11) * env_inv_pdf(r.wc, r.sigma, st, W, H));
+}
+
+typedef const __attribute__((address_space(4))) hf_envmap_args *hf_envmap_kargs;
+
+#ifndef HF_ENVMAP_WAVES
+#define HF_ENVMAP_WAVES 6 // resident waves per SIMD
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_ENVMAP_WAVES) void hf_envmap_kernel(hf_envmap_args a) {
+    const hf_dev_field &f = a.f;
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; // n < 2^32 (hf_envmap_lighting)
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    const v3 sn = mk3(a.sh_n[0][ii], a.sh_n[1][ii], a.sh_n[2][ii]);
+    bool elig;
+    {
+        const v3 d = mk3(a.d[0][ii], a.d[1][ii], a.d[2][ii]);
+        elig = in && sky_eligible(a.t[ii], sn, d);
+    }
+    double acc = 0.0;   // sum over the visible directions of <sh_n, w_k> E_k, in k order
+    uint32_t bits = 0u; // bit k: direction k was traced and is unoccluded
+    if (__ballot(elig) != 0ull) { // wave-uniform: a batch without an eligible sample draws nothing
+        const v3 p = mk3(a.p[0][ii], a.p[1][ii], a.p[2][ii]);
+        const v3 gn = mk3(a.nrm[0][ii], a.nrm[1][ii], a.nrm[2][ii]);
+        const uint32_t id = a.ray_id ? a.ray_id[ii] : ii;
+        const float mag = sky_offset(p);
+        hf_envmap_kargs ka = (hf_envmap_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll 1
+        for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+            asm volatile("" : "+s"(ka)); // opaque per direction: the kernarg loads stay inside the loop
+            // the draw and the term that is added first, finished before the ray is begun: the texels and the doubles are
+            // dead when setup_ray's registers fill; the cell, the position in it and the term are held across the walk
+            uint32_t cx, cy;
+            float fx, fy;
+            double co;
+            bool valid;
+            {
+                float sx, sy;
+                sky_sample(ka->seed, k, id, sx, sy);
+                const hf_env_draw r = env_draw(ka->data, ka->table, ka->W, ka->H, sx, sy);
+                v3 snd = sn; // (opaque: the conversions of sh_n to double are otherwise hoisted out of the loop)
+                asm volatile("" : "+v"(snd.x), "+v"(snd.y), "+v"(snd.z));
+                co = r.valid ? env_term(r, snd, ka->W, ka->H, ka->rot) : 0.0;
+                cx = r.cx; cy = r.cy; fx = r.fx; fy = r.fy; valid = r.valid;
+            }
+            asm volatile("" : "+v"(cx), "+v"(cy), "+v"(fx), "+v"(fy));
+            const v3 w = env_dir(cx, cy, fx, fy, ka->W, ka->H, ka->rot);
+            const bool traced = elig && valid && dot3(sn, w) > 0.f;
+            hf_hit best;
+            best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
+            hf_ray_state rs = {}; // fully defined on every path
+            bool alive;
+            {
+                const hf_dev_field f0 = load_field(&ka->f);
+                alive = traced && setup_ray(f0, f0.mip[1], sky_origin(p, gn, mag, w), w, __builtin_inff(), rs);
+            }
+            if (alive) { // the per-lane walk from the root, as in hf_sky_kernel
+                float thi = rs.thi;
+                hf_src_global src;
+                src.mip = f.mip; src.shear = f.shear; src.h = f.h; src.top = f.top; src.W = f.W;
+                const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
+                (void) walk_subtree<true>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
+            }
+            if (traced && !best.hit) { bits |= 1u << k; acc += co; }
+            if (k + 1u >= ka->num_rays) break;
+        }
+    }
+    hf_envmap_kargs ko = (hf_envmap_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    float c = 0.f;
+    if (elig) { // (eligible: in range)
+        const float *weight = ko->weight;
+        c = (float) ((double) ko->scale * acc);
+        if (weight) c *= weight[i];
+    }
+    uint32_t *vis_bits = ko->vis_bits;
+    if (in && vis_bits) vis_bits[i] = bits;
+    const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+    film_pixel(ko->image, c, 0u, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+}
+
+// shadow ray a.k of every sample, materialised: what hf_envmap_kernel traces for that direction, bit for bit
+__global__ __launch_bounds__(HF_BLOCK) void hf_envmap_rays_kernel(hf_envmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    float sx, sy;
+    sky_sample(a.seed, a.k, a.ray_id ? a.ray_id[i] : (uint32_t) i, sx, sy);
+    const hf_env_draw r = env_draw(a.data, a.table, a.W, a.H, sx, sy);
+    const v3 w = env_dir(r.cx, r.cy, r.fx, r.fy, a.W, a.H, a.rot);
+    const bool traced = sky_eligible(a.t[i], sn, d) && r.valid && dot3(sn, w) > 0.f;
+    const v3 o = sky_origin(p, gn, sky_offset(p), w);
+    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
+    a.out_d[0][i] = w.x; a.out_d[1][i] = w.y; a.out_d[2][i] = w.z;
+    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+    if (a.out_weight) {
+        double st;
+        (void) env_dir_f64(r.cx, r.cy, r.fx, r.fy, a.W, a.H, a.rot, st);
+        a.out_weight[i] = r.valid ? (float) (env_bilinear(r.fx, r.fy, r.v00, r.v10, r.v01, r.v11) * env_inv_pdf(r.wc, r.sigma, st, a.W, a.H)) : 0.f;
+    }
+}
+
+// Emitter::sample_direction for caller-supplied samples: direction (float32, as the rays take it), E, pdf_omega, cell
+__global__ __launch_bounds__(HF_BLOCK) void hf_envmap_sample_kernel(hf_envmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const hf_env_draw r = env_draw(a.data, a.table, a.W, a.H, a.sample[0][i], a.sample[1][i]);
+    const v3 w = env_dir(r.cx, r.cy, r.fx, r.fy, a.W, a.H, a.rot);
+    double st;
+    (void) env_dir_f64(r.cx, r.cy, r.fx, r.fy, a.W, a.H, a.rot, st);
+    const double G = env_inv_pdf(r.wc, r.sigma, st, a.W, a.H);
+    a.out_d[0][i] = w.x; a.out_d[1][i] = w.y; a.out_d[2][i] = w.z;
+    a.out_weight[i] = r.valid ? (float) (env_bilinear(r.fx, r.fy, r.v00, r.v10, r.v01, r.v11) * G) : 0.f;
+    a.out_pdf[i] = r.valid ? (float) (1.0 / G) : 0.f;
+    if (a.out_cell) a.out_cell[i] = r.cy * (a.W - 1u) + r.cx;
+    if (a.out_frac[0]) { a.out_frac[0][i] = r.fx; a.out_frac[1][i] = r.fy; }
+}
+
+// Emitter::eval (envmap.cpp:323-333, 498-509): the cell of a world direction and the position in it.  In double: a bilinear
+// weight is then exact to its last float32 bit, which is what the summation bound of the adjoint's atomics rests on
+__device__ __forceinline__ void env_lookup(const hf_envmap_args &a, v3 d, uint32_t &cx, uint32_t &cy, double &fx, double &fy) {
+    const float *R = a.rot; // v = R^T d
+    const double vx = (double) R[0] * d.x + (double) R[3] * d.y + (double) R[6] * d.z;
+    const double vy = (double) R[1] * d.x + (double) R[4] * d.y + (double) R[7] * d.z;
+    const double vz = (double) R[2] * d.x + (double) R[5] * d.y + (double) R[8] * d.z;
+    double ux = atan2(vx, -vz) / 6.283185307179586 - 0.5 / (double) (a.W - 1u);
+    double uy = acos(fmin(fmax(vy, -1.0), 1.0)) / 3.141592653589793;
+    ux -= floor(ux); uy -= floor(uy);
+    ux *= (double) (a.W - 1u); uy *= (double) (a.H - 1u);
+    // (a NaN direction converts to 0: every index stays in the map)
+    cx = min((uint32_t) fmax(ux, 0.0), a.W - 2u); cy = min((uint32_t) fmax(uy, 0.0), a.H - 2u);
+    fx = ux - (double) cx; fy = uy - (double) cy;
+}
+// ADJ = false: out[i] = the bilinear value, rounded once, 0 for an inactive lane;
+// ADJ = true: grad_data += grad_out[i] * the bilinear weights (each product rounded once; float atomics)
+template <bool ADJ>
+__global__ __launch_bounds__(HF_BLOCK) void hf_envmap_eval_kernel(hf_envmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const bool act = a.active ? a.active[i] != 0 : true;
+    if (!act) {
+        if (!ADJ) a.out[i] = 0.f;
+        return;
+    }
+    uint32_t cx, cy;
+    double fx, fy;
+    env_lookup(a, mk3(a.d[0][i], a.d[1][i], a.d[2][i]), cx, cy, fx, fy);
+    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
+    const double gx = 1.0 - fx, gy = 1.0 - fy;
+    if (!ADJ) {
+        a.out[i] = (float) (gy * (gx * (double) a.data[r0] + fx * (double) a.data[r0 + 1]) +
+                            fy * (gx * (double) a.data[r1] + fx * (double) a.data[r1 + 1]));
+    } else {
+        const double g = (double) a.gout[i];
+        atomicAdd(a.gdata + r0, (float) (g * (gy * gx))); atomicAdd(a.gdata + r0 + 1, (float) (g * (gy * fx)));
+        atomicAdd(a.gdata + r1, (float) (g * (fy * gx))); atomicAdd(a.gdata + r1 + 1, (float) (g * (fy * fx)));
+    }
+}
+
+// what the derivative kernels need of direction k of sample i: drawn again, nothing traced
+__device__ __forceinline__ hf_env_shade env_shade(const hf_envmap_args &a, uint32_t k, uint32_t id, size_t &r0) {
+    float sx, sy;
+    sky_sample(a.seed, k, id, sx, sy);
+    const hf_env_draw r = env_draw(a.data, a.table, a.W, a.H, sx, sy);
+    hf_env_shade s;
+    double st;
+    s.w = env_dir_f64(r.cx, r.cy, r.fx, r.fy, a.W, a.H, a.rot, st);
+    s.G = env_inv_pdf(r.wc, r.sigma, st, a.W, a.H);
+    s.L = env_bilinear(r.fx, r.fy, r.v00, r.v10, r.v01, r.v11);
+    const double x1 = (double) r.fx, x0 = 1.0 - x1, y1 = (double) r.fy, y0 = 1.0 - y1;
+    s.bw[0] = y0 * x0; s.bw[1] = y0 * x1; s.bw[2] = y1 * x0; s.bw[3] = y1 * x1;
+    r0 = (size_t) r.cy * a.W + r.cx;
+    return s;
+}
+
+// Reverse mode of hf_envmap_kernel with respect to sh_n, weight and the texels.  grad_sh_n / grad_weight: sums in k order,
+// no atomics; grad_data: one float atomic per texel of every visible direction
+__global__ __launch_bounds__(HF_BLOCK) void hf_envmap_adjoint_kernel(hf_envmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    v3 g = mk3(0.f, 0.f, 0.f);
+    float gw = 0.f;
+    if (sky_eligible(a.t[i], sn, d)) {
+        const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+        const float c = (a.gimg[i / a.spp] * (1.0f / (float) a.spp)) * a.scale;
+        const float cw = a.weight ? c * a.weight[i] : c;
+        double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0;
+        for (uint32_t k = 0; k < a.num_rays; ++k) {
+            if ((bits >> k) & 1u) {
+                size_t r0;
+                const hf_env_shade s = env_shade(a, k, id, r0);
+                const double E = s.L * s.G, co = sky_dot_f64(sn, s.w);
+                sx += s.w.x * E; sy += s.w.y * E; sz += s.w.z * E;
+                sc += co * E;
+                if (a.gdata) {
+                    const double q = (double) cw * (co * s.G);
+                    atomicAdd(a.gdata + r0, (float) (q * s.bw[0])); atomicAdd(a.gdata + r0 + 1, (float) (q * s.bw[1]));
+                    atomicAdd(a.gdata + r0 + a.W, (float) (q * s.bw[2])); atomicAdd(a.gdata + r0 + a.W + 1, (float) (q * s.bw[3]));
+                }
+            }
+        }
+        g = mk3((float) sx, (float) sy, (float) sz) * cw;
+        gw = c * (float) sc;
+    }
+    a.gn[0][i] = g.x; a.gn[1][i] = g.y; a.gn[2][i] = g.z;
+    if (a.gw) a.gw[i] = gw;
+}
+
+// forward mode: the tangent of sample i's value for tangents dn of sh_n, dw of weight and ddata of the texels (NULL: zero)
+__device__ __forceinline__ float envmap_tangent_value(const hf_envmap_args &a, size_t i) {
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    if (!sky_eligible(a.t[i], sn, d)) return 0.f;
+    const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    double sd = 0.0, sc = 0.0;
+    for (uint32_t k = 0; k < a.num_rays; ++k) {
+        if ((bits >> k) & 1u) {
+            size_t r0;
+            const hf_env_shade s = env_shade(a, k, id, r0);
+            const double co = sky_dot_f64(sn, s.w);
+            double dL = 0.0;
+            if (a.ddata)
+                dL = s.bw[0] * (double) a.ddata[r0] + s.bw[1] * (double) a.ddata[r0 + 1] + s.bw[2] * (double) a.ddata[r0 + a.W] +
+                     s.bw[3] * (double) a.ddata[r0 + a.W + 1];
+            sd += (sky_dot_f64(dn, s.w) * s.L + co * dL) * s.G;
+            sc += co * (s.L * s.G);
+        }
+    }
+    return (float) ((double) a.scale * ((double) (a.weight ? a.weight[i] : 1.f) * sd + (double) (a.dw ? a.dw[i] : 0.f) * sc));
+}
+// PIXEL as in hf_sky_tangent_kernel: no atomics for any spp
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_envmap_tangent_kernel(hf_envmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    if (PIXEL) {
+        if (i >= a.n / spp) return;
+        float c = 0.f;
+        for (uint32_t s = 0; s < spp; ++s) c += envmap_tangent_value(a, i * spp + s);
+        a.image[i] = c * (1.0f / (float) spp);
+    } else {
+        const bool in = i < a.n;
+        const float c = envmap_tangent_value(a, in ? i : a.n - 1);
+        film_pixel(a.image, in ? c : 0.f, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
+    }
+}
+
+void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    if (mode == 0) {
+        if (!sky_tree_film(a.spp)) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths of film_pixel
+        hipLaunchKernelGGL(hf_envmap_kernel, grid, block, 0, stream, a);
+    } else if (mode == 1) {
+        hipLaunchKernelGGL(hf_envmap_adjoint_kernel, grid, block, 0, stream, a);
+    } else if (mode == 2) {
+        if (sky_tree_film(a.spp)) hipLaunchKernelGGL(hf_envmap_tangent_kernel<false>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(hf_envmap_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
+    } else if (mode == 3) {
+        hipLaunchKernelGGL(hf_envmap_rays_kernel, grid, block, 0, stream, a);
+    } else if (mode == 4) {
+        hipLaunchKernelGGL(hf_envmap_sample_kernel, grid, block, 0, stream, a);
+    } else if (mode == 5) {
+        hipLaunchKernelGGL(hf_envmap_eval_kernel<false>, grid, block, 0, stream, a);
+    } else {
+        hipLaunchKernelGGL(hf_envmap_eval_kernel<true>, grid, block, 0, stream, a);
+    }
+}

@@ -82,6 +82,36 @@ struct hf_sky_args {
 // mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is the per-lane any-hit walk with the samples
 // drawn in the kernel: no work counter, no scratch block
 void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream);
+// ---- environment-map lighting (hf_envmap_*): the one argument of its kernels; data and table are the caller's ----
+struct hf_envmap_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, num_rays, seed, k;         // k: hf_envmap_rays' direction
+    uint32_t W, H;                           // texels per row (the seam column included), rows
+    float scale;                             // albedo / (pi num_rays)
+    float rot[9];                            // row-major rotation, map space -> world (identity for NULL)
+    const float *data, *table;               // [H][W] radiance; hf_envmap_table_floats(W, H) floats
+    const float *p[3], *nrm[3];              // si.p, si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight; // d: the camera ray's direction; hf_envmap_eval: the directions to look up
+    const uint32_t *ray_id;                  // optional: the id of sample i in the sample streams (NULL: i)
+    float *image;                            // forward: image; tangent: dimage
+    uint32_t *vis_bits;                      // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *out_o[3], *out_d[3], *out_maxt;   // rays; out_d: sample_direction too
+    float *out_weight, *out_pdf;             // rays (optional), sample_direction
+    uint32_t *out_cell;                      // sample_direction (optional)
+    float *out_frac[2];                      // sample_direction (optional): the position (fx, fy) in the cell
+    const float *gimg; float *gn[3], *gw;    // adjoint
+    float *gdata;                            // adjoint, eval_adjoint: accumulated (lighting adjoint: NULL = not wanted)
+    const float *dn[3], *dw, *ddata;         // tangent inputs (NULL: zero)
+    const float *sample[2];                  // sample_direction
+    const uint8_t *active;                   // eval, eval_adjoint (NULL: every lane)
+    float *out; const float *gout;           // eval: values; eval_adjoint: dL/dvalue
+};
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays, 4: sample_direction, 5: eval, 6: eval_adjoint.  The forward launch
+// is hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
+void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream);
+// the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
+void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
 struct hf_bounce_args {
     hf_dev_field f;                          // the walks (forward, rays) and the triangles of the record (adjoint, tangent)

@@ -1502,6 +1502,243 @@ def sky_rays(si, ray, k, seed=0, ray_index=None):
     return Ray3f(o, d, maxt)
 
 
+class _EnvmapEvalOp(torch.autograd.Function):
+    """hf_envmap_eval of the map `full` ([H, W], the seam column included) for world directions; linear in the texels:
+    backward = hf_envmap_eval_adjoint, jvp = hf_envmap_eval of the texels' tangent."""
+
+    @staticmethod
+    def _eval(dat, dd, act, rot):
+        out = torch.empty(dd.shape[1], dtype=torch.float32, device=dd.device)
+        if dd.shape[1]:
+            check(_capi.lib().hf_envmap_eval(dd.shape[1], C.byref(_p3(dd)), _ptr(act), dat.shape[1], dat.shape[0],
+                                             dat.data_ptr(), C.byref(rot), out.data_ptr(), _stream_of(dd.device)))
+        return out
+
+    @staticmethod
+    def forward(ctx, full, d, active, rot):
+        dat = full.detach().to(dtype=torch.float32).contiguous()
+        dd = d.detach().to(dtype=torch.float32).contiguous()
+        act = active.to(dtype=torch.uint8).contiguous() if active is not None else None
+        ctx.misc = (act, rot, tuple(dat.shape))
+        ctx.save_for_backward(dd)
+        ctx.save_for_forward(dd)
+        return _EnvmapEvalOp._eval(dat, dd, act, rot)
+
+    @staticmethod
+    def jvp(ctx, dfull, *_):
+        act, rot, shape = ctx.misc
+        dd, = ctx.saved_tensors
+        if dfull is None:
+            return torch.zeros(dd.shape[1], dtype=torch.float32, device=dd.device)
+        return _EnvmapEvalOp._eval(dfull.to(dtype=torch.float32).contiguous(), dd, act, rot)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        act, rot, (H, W) = ctx.misc
+        dd, = ctx.saved_tensors
+        gd = torch.zeros((H, W), dtype=torch.float32, device=dd.device)
+        if dd.shape[1]:
+            go = grad_out.to(dtype=torch.float32).contiguous()
+            check(_capi.lib().hf_envmap_eval_adjoint(dd.shape[1], C.byref(_p3(dd)), _ptr(act), W, H, C.byref(rot),
+                                                     go.data_ptr(), gd.data_ptr(), _stream_of(dd.device)))
+        return gd, None, None, None
+
+
+class Envmap:
+    """The reference's ``envmap`` emitter (src/emitters/envmap.cpp) for one channel: a latitude-longitude map of scalar
+    radiance, row 0 the north pole (the map's +Y).  ``data``: [H, W0] float32 device tensor (W0 >= 1, H >= 2), kept by
+    reference -- it may require grad; the seam column (a copy of column 0, envmap.cpp:147, 249-258) is appended with
+    ``torch.cat`` at every use, so autograd folds its gradient back onto column 0.  ``to_world``: 3 x 3 rotation from the
+    map's space to world, default the one that takes the map's +Y to world +Z (Rectangle's object space is Z-up);
+    detached.  ``defensive``: the fraction u in [0, 1] of the sampling distribution that is spread evenly over the cells
+    (include/hf.h); 0 samples in proportion to luminance, a positive value keeps dark texels reachable while the texels
+    are optimised.  The object owns the sampling table (``hf_envmap_build_table``) and rebuilds it when ``data`` has been
+    written to (its version counter) and in ``parameters_changed()``."""
+
+    def __init__(self, data, to_world=None, defensive=0.0):
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.float32:
+            data = torch.as_tensor(data, dtype=torch.float32)
+        if data.dim() != 2 or data.shape[0] < 2 or data.shape[1] < 1:
+            raise ValueError("Envmap: data must be [H >= 2, W0 >= 1]")
+        if not 0.0 <= float(defensive) <= 1.0:
+            raise ValueError("Envmap: defensive must lie in [0, 1]")
+        self.data = data
+        self.defensive = float(defensive)
+        tw = torch.tensor([[1.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]]) if to_world is None else \
+            torch.as_tensor(to_world, dtype=torch.float32).detach().cpu().reshape(3, 3)
+        self.to_world = tw
+        self._rot = (C.c_float * 9)(*[float(v) for v in tw.reshape(-1)])
+        self._table = None
+        self._key = None
+
+    @property
+    def resolution(self):
+        """(W, H) of the map the kernels read: the seam column included"""
+        return self.data.shape[1] + 1, self.data.shape[0]
+
+    def parameters_changed(self, keys=()):
+        self._key = None
+
+    def full(self):
+        """[H, W0 + 1]: data with its seam column, attached to ``data``"""
+        return torch.cat([self.data, self.data[:, :1]], 1)
+
+    def table(self):
+        """the sampling table of the current texels (a new tensor whenever it is rebuilt: an earlier one stays valid for
+        the backward pass of the call that used it)"""
+        key = (self.data._version, self.data.data_ptr(), tuple(self.data.shape), self.defensive)
+        if self._table is None or key != self._key:
+            W, H = self.resolution
+            dat = self.full().detach().contiguous()
+            table = torch.empty(_capi.lib().hf_envmap_table_floats(W, H), dtype=torch.float32, device=dat.device)
+            check(_capi.lib().hf_envmap_build_table(W, H, dat.data_ptr(), self.defensive, table.data_ptr(),
+                                                    _stream_of(dat.device)))
+            self._table, self._key = table, key
+        return self._table
+
+    def eval(self, d, active=True):
+        """radiance seen along the world directions ``d`` [3, n] (Emitter::eval); differentiable in ``data``"""
+        act = None if active is True else torch.as_tensor(active, device=d.device).expand(d.shape[1])
+        return _EnvmapEvalOp.apply(self.full(), d, act, self._rot)
+
+    def sample_direction(self, sample):
+        """Emitter::sample_direction for ``sample`` [2, n] in [0, 1): (ds, weight) with ds.d the world direction, ds.pdf
+        the density per solid angle (0 for an invalid draw), ds.cell the index cy (W - 1) + cx of the drawn cell, ds.frac
+        ([2, n]) the position in it and weight = radiance / pdf.  The distribution is detached; so are the returned values."""
+        W, H = self.resolution
+        s = sample.detach().to(dtype=torch.float32).contiguous()
+        n = s.shape[1]
+        dat, table = self.full().detach().contiguous(), self.table()
+        d = torch.empty((3, n), dtype=torch.float32, device=s.device)
+        weight, pdf = torch.empty_like(s[0]), torch.empty_like(s[0])
+        cell = torch.empty(n, dtype=torch.int32, device=s.device)
+        frac = torch.empty_like(s)
+        if n:
+            check(_capi.lib().hf_envmap_sample_direction(n, C.byref(_row_ptrs(s)), W, H, dat.data_ptr(), table.data_ptr(),
+                                                         C.byref(self._rot), C.byref(_p3(d)), weight.data_ptr(),
+                                                         pdf.data_ptr(), cell.data_ptr(), C.byref(_row_ptrs(frac)),
+                                                         _stream_of(s.device)))
+        ds = DirectionSample3f(PositionSample3f(None, -d, None, None, pdf, False), d, math.inf)
+        ds.cell, ds.frac = cell, frac
+        return ds, weight
+
+    def pdf_direction(self, d):
+        """density per solid angle with which ``sample_direction`` draws the world directions ``d`` [3, n]: plain torch
+        over the table's header and the texels (not a hot path)"""
+        W, H = self.resolution
+        dat, table = self.full().detach(), self.table()
+        sigma, mbar, u = table[0], table[1], table[2]
+        # (the lookup in double, as hf_envmap_eval does it: near a pole it amplifies an input error by 1 / theta)
+        v = torch.nan_to_num(self.to_world.to(device=d.device, dtype=torch.float64).T @ d.detach().to(dtype=torch.float64))
+        ux = torch.atan2(v[0], -v[2]) / (2.0 * math.pi) - 0.5 / (W - 1)
+        uy = torch.acos(v[1].clamp(-1.0, 1.0)) / math.pi
+        ux = (ux - torch.floor(ux)) * (W - 1); uy = (uy - torch.floor(uy)) * (H - 1)
+        cx = ux.long().clamp(0, W - 2); cy = uy.long().clamp(0, H - 2)
+        p = dat.clamp(min=0.0)
+        mc = 0.25 * ((p[cy, cx] + p[cy, cx + 1]) + (p[cy + 1, cx] + p[cy + 1, cx + 1]))
+        wc = torch.sin(math.pi * (cy + 0.5) / (H - 1)) * ((1.0 - u) * mc + u * mbar)
+        st = torch.sqrt(v[0] * v[0] + v[2] * v[2]).clamp(min=1e-12)   # sin theta as envmap.cpp:403-415 takes it: well conditioned at the poles
+        pdf = (wc * ((W - 1) * (H - 1)) / sigma / (2.0 * math.pi ** 2 * st)).to(torch.float32)
+        return torch.where((sigma > 0) & (wc > 0), pdf, torch.zeros_like(pdf))
+
+
+class _EnvmapLightingOp(torch.autograd.Function):
+    """(image, visibility words) of hf_envmap_lighting; backward = hf_envmap_lighting_adjoint (gradients of sh_n, weight and
+    the texels), jvp = hf_envmap_lighting_tangent.  Both read the visibility word and the table the forward saved and
+    trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, sn, dd, tt, vis, dat, table, ww=None):
+        """what hf_envmap_lighting_adjoint / _tangent start with"""
+        spp, num_rays, seed, rid, rot, albedo = ctx.misc
+        return (sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(rid),
+                dat.shape[1], dat.shape[0], dat.data_ptr(), table.data_ptr(), C.byref(rot), albedo, vis.data_ptr())
+
+    @staticmethod
+    def forward(ctx, sh_n, weight, full, shape, p, nrm, d, t, table, rot, albedo, spp, num_rays, seed, ray_index):
+        sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (sh_n, p, nrm, d, t))
+        ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
+        dat = full.detach().to(dtype=torch.float32).contiguous()
+        n = sn.shape[1]
+        ctx.misc = (spp, num_rays, seed, ray_index, rot, albedo)
+        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
+        vis = torch.empty(n, dtype=torch.int32, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_envmap_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                                 C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(ray_index),
+                                                 dat.shape[1], dat.shape[0], dat.data_ptr(), table.data_ptr(), C.byref(rot),
+                                                 albedo, image.data_ptr(), vis.data_ptr(), _stream_of(sn.device)))
+        saved = (sn, dd, tt, vis, dat, table) if ww is None else (sn, dd, tt, vis, dat, table, ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(vis)
+        return image, vis
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dweight, dfull, *_):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        dn = _f3(dsh_n)[0] if dsh_n is not None else None
+        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 7 and dweight is not None) else None
+        df = dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
+        dimage = torch.empty(sn.shape[1] // ctx.misc[0], dtype=torch.float32, device=sn.device)
+        if sn.shape[1]:
+            check(_capi.lib().hf_envmap_lighting_tangent(*_EnvmapLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
+                                                         _ptr(dw), _ptr(df), dimage.data_ptr(), _stream_of(sn.device)))
+        return dimage, None
+
+    @staticmethod
+    def backward(ctx, grad_image, _grad_vis):
+        saved = ctx.saved_tensors
+        sn, dat = saved[0], saved[4]
+        gi = grad_image.to(dtype=torch.float32).contiguous()
+        gn = torch.empty_like(sn)
+        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 7 else None
+        gd = torch.zeros_like(dat) if ctx.needs_input_grad[2] else None
+        if sn.shape[1]:
+            check(_capi.lib().hf_envmap_lighting_adjoint(*_EnvmapLightingOp._prefix(ctx, *saved), gi.data_ptr(),
+                                                         C.byref(_p3(gn)), _ptr(gw), _ptr(gd), _stream_of(sn.device)))
+        return (gn, gw, gd) + (None,) * 12
+
+
+def envmap_lighting(shape, si, ray, envmap, albedo=1.0, spp=1, num_rays=8, seed=0, weight=None, ray_index=None,
+                    return_visibility=False):
+    """Diffuse lighting under an environment map (``Envmap``; the reference's ``envmap`` emitter) + box-filter film, the
+    shadow rays traced inside the lighting kernel (``hf_envmap_lighting``): every sample draws ``num_rays`` (1..32)
+    directions by importance sampling of the map from the TEA stream of ``sky_lighting`` (``seed``, ``ray_index``), traces
+    ``si.spawn_ray(direction)`` for those above its shading hemisphere and averages ``albedo/pi * cos * radiance / pdf``
+    over the unoccluded ones.  Returns the [n // spp] image; with ``return_visibility`` also the [n] int32 visibility
+    words.  Differentiable with respect to ``si.sh_frame.n``, ``weight`` ([n], optional) and ``envmap.data``; visibility
+    and the sampling distribution are detached."""
+    shape._check_ray(ray)
+    image, vis = _EnvmapLightingOp.apply(si.sh_frame.n, weight, envmap.full(), shape, si.p, si.n, ray.d, si.t, envmap.table(),
+                                         envmap._rot, float(albedo), int(spp), int(num_rays), int(seed),
+                                         _check_ray_index(ray_index, ray))
+    return (image, vis) if return_visibility else image
+
+
+def envmap_rays(si, ray, envmap, k, seed=0, ray_index=None, return_weight=False):
+    """Shadow ray ``k`` of every sample of ``envmap_lighting`` as a Ray3f (``hf_envmap_rays``): what the fused kernel
+    traces for that direction, bit for bit.  Lanes it does not trace (no hit, seen from behind, an invalid draw,
+    direction below the shading hemisphere) get ``maxt = -1``, a miss.  ``return_weight``: also the emitter weights
+    ``radiance / pdf`` of the draws ([n])."""
+    rid = _check_ray_index(ray_index, ray)
+    sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n = sn.shape[1]
+    W, H = envmap.resolution
+    dat, table = envmap.full().detach().contiguous(), envmap.table()
+    o, d = torch.empty_like(pp), torch.empty_like(pp)
+    maxt = torch.empty(n, dtype=torch.float32, device=pp.device)
+    wgt = torch.empty(n, dtype=torch.float32, device=pp.device) if return_weight else None
+    if n:
+        check(_capi.lib().hf_envmap_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
+                                         tt.data_ptr(), int(k), int(seed), _ptr(rid), W, H, dat.data_ptr(), table.data_ptr(),
+                                         C.byref(envmap._rot), C.byref(_p3(o)), C.byref(_p3(d)), maxt.data_ptr(), _ptr(wgt),
+                                         _stream_of(pp.device)))
+    r = Ray3f(o, d, maxt)
+    return (r, wgt) if return_weight else r
+
+
 class _BounceLightingOp(torch.autograd.Function):
     """(image, hit_prim, lit_bits) of hf_bounce_lighting; backward = hf_bounce_lighting_adjoint (gradients of sh_n, weight
     and the heights), jvp = hf_bounce_lighting_tangent.  Both read the record the forward saved and trace nothing."""
