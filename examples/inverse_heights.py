@@ -21,6 +21,10 @@ way, the image loss normalised by the pixel count of the whole film so that the 
 single-rank loss -- and the gradient texture is summed with one all-reduce per step; the Adam step is replicated.
 --virtual-ranks V runs the same partition on one device, shard after shard (what tests/test_gpu_inverse_loop.py
 compares with the unsharded loop).
+--large-steps LAMBDA preconditions the loop (Nicolet et al. 2021; hf_amd.LargeSteps, the reference's
+mitsuba.ad.largesteps.LargeSteps): the optimised tensor is the latent u = (I + LAMBDA L) h, every step sets the heights
+to from_differential(u) -- a conjugate-gradient solve warm-started from the previous heights -- and takes the gradient
+back through the same solve; the latent is stepped by uniform Adam (optimizers.py:259, 290-291) in a few torch lines.
 """
 import argparse
 import math
@@ -111,10 +115,11 @@ def centred_error(h, target):
 
 def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=True, seed=0, shadows=False,
         depth_weight=0.0, silhouette=False, aux=8, kappa=2e4, gaussian_film=False, virtual_ranks=0, record=None, sky=0.0,
-        bounce=0):
+        bounce=0, large_steps=0.0):
     """record (optional list): receives the height texture after every step (trajectory comparisons in the tests);
     sky: radiance of a constant environment added to the rendered and the target images (0: none); bounce: directions
-    per sample of one diffuse interreflection added to both (0: none)"""
+    per sample of one diffuse interreflection added to both (0: none); large_steps: lambda of the large-steps
+    preconditioner (0: off, the heights themselves are optimised by hf_amd.Adam)"""
     import torch.distributed as dist
     dev = torch.device(device)
     lights = torch.cat([LIGHTS / LIGHTS.norm(dim=1, keepdim=True), torch.full((len(LIGHTS), 1), math.pi)], 1)  # E = pi
@@ -150,11 +155,25 @@ def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=Tr
     shape = hf_amd.Heightfield(heightfield=torch.full_like(target_h, 0.5), max_height=0.5)
     shape.heightfield.requires_grad_(True)
     opt = hf_amd.Adam(shape, lr=lr)                       # hf_adam_step: optimizers.py:263-300 + params.update
+    if large_steps:
+        # the latent and its uniform-Adam state; the heights are from_differential(latent), a leaf copy of which the
+        # shape renders, so that the shards' gradients add up in one place and go through ONE solve per step
+        ls = hf_amd.LargeSteps(grid, grid, lambda_=large_steps)
+        latent = ls.to_differential(shape.heightfield.detach()).requires_grad_(True)
+        adam_m, adam_v = torch.zeros_like(latent), torch.zeros_like(latent)
+        b1, b2, eps = 0.9, 0.999, 1e-8
+
+        def set_heights(guess):
+            v = ls.from_differential(latent, guess=guess)      # attached to the latent
+            shape.heightfield = v.detach().requires_grad_(True)
+            shape.parameters_changed(["heightfield"])
+            return v
+        heights_of_latent = set_heights(shape.heightfield.detach())
     hist = []
     t0 = time.perf_counter()
     n_rays = sum(len(sh[0]) for sh in shards)
     for it in range(steps):
-        opt.zero_grad()
+        opt.zero_grad()             # (large steps: the heights are a fresh leaf every step)
         total = 0.0
         for ray, flm, tgt_img, tgt_depth, tgt_valid, rid in shards:    # (backward accumulates into heightfield.grad)
             images, depth, valid = render(shape, ray, lights, spp, shadows, silhouette, aux, kappa, film=flm,
@@ -171,7 +190,20 @@ def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=Tr
         if distributed:                                             # image loss and gradient texture: sums over ranks
             dist.all_reduce(total)
         hf_amd.allreduce_gradient(shape.heightfield.grad)
-        opt.step()                                            # Adam update + rebuild of the acceleration data (replicated)
+        if large_steps:
+            # dL/dlatent = A^-1 dL/dheights (the solve's backward is the solve), then UniformAdam on the latent
+            # (hf_adam_step steps the parameter of a shape and rebuilds it: not a free buffer)
+            latent.grad = None
+            heights_of_latent.backward(shape.heightfield.grad)
+            with torch.no_grad():
+                g = latent.grad
+                adam_m.mul_(b1).add_(g, alpha=1 - b1)
+                adam_v.mul_(b2).addcmul_(g, g, value=1 - b2)
+                lr_t = lr * math.sqrt(1 - b2 ** (it + 1)) / (1 - b1 ** (it + 1))
+                latent.sub_(lr_t * adam_m / (adam_v.max().sqrt() + eps))
+            heights_of_latent = set_heights(shape.heightfield.detach())
+        else:
+            opt.step()                                        # Adam update + rebuild of the acceleration data (replicated)
         hist.append(float(total))
         if record is not None:
             record.append(shape.heightfield.detach().clone())
@@ -190,6 +222,7 @@ def run(grid=128, film=256, spp=1, steps=100, lr=0.02, device="cuda", verbose=Tr
               f"(first step {1e3 * t_first:.0f} ms, then {1e3 * (wall - t_first) / max(1, steps - 1):.2f} ms/step)")
     run.last_centred_error = centred_error(shape.heightfield.detach(), target_h)
     run.start_centred_error = centred_error(torch.full_like(target_h, 0.5), target_h)
+    run.last_large_steps = (ls, latent, shape) if large_steps else None
     return hist, err, wall
 
 
@@ -305,6 +338,8 @@ if __name__ == "__main__":
     ap.add_argument("--sky", type=float, default=0.0, help="radiance of a constant environment (0: none; hf_sky_lighting)")
     ap.add_argument("--bounce", type=int, default=0, metavar="K",
                     help="one diffuse interreflection with K directions per sample (0: none; hf_bounce_lighting)")
+    ap.add_argument("--large-steps", type=float, default=0.0, metavar="LAMBDA",
+                    help="optimise the latent (I + LAMBDA L) h with uniform Adam (0: off; hf_amd.LargeSteps)")
     ap.add_argument("--captured", action="store_true", help="one step captured into a HIP graph and replayed (run_captured)")
     a = ap.parse_args()
     if a.captured:
@@ -322,6 +357,6 @@ if __name__ == "__main__":
         dist.init_process_group(backend, rank=int(os.environ["RANK"]), world_size=world)
     run(a.grid, a.film, a.spp, a.steps, a.lr, shadows=a.shadows, depth_weight=a.depth_weight, silhouette=a.silhouette,
         aux=a.aux, gaussian_film=a.gaussian_film, virtual_ranks=a.virtual_ranks, sky=a.sky, bounce=a.bounce,
-        verbose=int(os.environ.get("RANK", "0")) == 0)
+        large_steps=a.large_steps, verbose=int(os.environ.get("RANK", "0")) == 0)
     if world > 1:
         dist.destroy_process_group()

@@ -1076,6 +1076,46 @@ int hf_ray_intersect_preliminary_packet(const hf_field_t *hf, uint32_t n, const 
 int hf_ray_test_packet(const hf_field_t *hf, uint32_t n, const float *const h_o[3], const float *const h_d[3],
                        const float *h_maxt, const uint8_t *h_active, uint8_t *h_hit);
 
+/* ---- next row: large-steps preconditioning of the height grid (Nicolet et al. 2021) ----
+ *
+ * The reference's mitsuba.ad.largesteps.LargeSteps (src/python/python/ad/largesteps.py) for a heightfield: the optimiser
+ * steps the latent u = (I + lambda L) v instead of the heights v, and every step solves (I + lambda L) v = u.
+ *   L           the combinatorial Laplacian of the tessellation (every cell split along v10-v01), as mesh_laplacian
+ *               (largesteps.py:6-28) builds it from the faces.  Vertex (i, j) -- row i, column j, index i W + j -- is
+ *               adjacent to (i, j-1), (i, j+1), (i-1, j), (i+1, j), (i+1, j-1), (i-1, j+1), where they exist:
+ *               (A v)_ij = v_ij + lambda (deg_ij v_ij - sum of the neighbours),  A = I + lambda L,
+ *               deg the number of neighbours that exist (6 inside, 4 on an edge, 2 or 3 at the corners).  Nothing wraps
+ *               or mirrors.  A is symmetric, its spectrum lies in [1, 1 + 12 lambda], 1^T A = 1^T.
+ *   arithmetic  float32, one rounding per operation, nothing fused: the neighbours summed in the order listed above,
+ *               then v + lambda (deg v - sum).  lambda is rounded to float32 once.
+ *   solve       conjugate gradients, float32 vectors, the dot products accumulated in double (one double per block, the
+ *               blocks' partials added in one fixed order: no float atomics; bitwise the same from call to call for a
+ *               given grid and HF_FORCE_GRID), alpha and beta computed in double and rounded once.  Starts from v
+ *               (warm != 0) or from 0 (v is write-only); ends when the recursive residual satisfies
+ *               |r| <= rel_tol |u| (tested before every iteration, the first included) or after max_iter iterations.
+ *               u = 0 gives v = 0 exactly, whatever the guess.  A NaN or an infinity in the input spreads; the call
+ *               still ends.
+ *   sum         A 1 = 1: the constant field is an eigenvector of A, and sum(u - A v) = sum(u) - sum(v).  After the last
+ *               iteration (sum(u) - sum(v)) / (W H), both sums in double, is added to every v: the exact solve in that
+ *               eigenspace.  It takes the mean out of the true residual (whose norm cannot grow), so that the solve
+ *               keeps the sum of its right-hand side to float32 rounding, which the recursion alone does not.
+ *   launches    1 + 2 max_iter + 2, the same whatever the data: the solve never synchronises with the host and can be
+ *               captured in a HIP graph.  The launches after convergence return after one load of a device word.
+ *   workspace   hf_large_steps_workspace_floats(W, H) floats of device memory, 16-byte aligned, the caller's; exclusively
+ *               this solve's until it has completed.  (r, q, two p buffers, the blocks' partial sums, the scalars.)
+ *   info        2 device floats, may be NULL: { iterations performed, the final |r| / |u| (0 for u = 0) }.
+ * Free functions on caller buffers; no field handle.  Refused with HF_EINVAL before anything touches a device: NULL u, v
+ * or workspace, W or H below 2 or above hf_create's limits (32768 cells per side, 2^30 vertices), lambda negative or not
+ * finite, rel_tol negative or NaN, max_iter == 0, u == v, a workspace that is not 16-byte aligned.  Callers detect the
+ * entries by their symbols (HF_VERSION is unchanged). */
+/* the workspace of a solve in floats; 0 for W < 2 or H < 2 */
+size_t hf_large_steps_workspace_floats(uint32_t W, uint32_t H);
+/* u = A v (LargeSteps.to_differential); also its own adjoint and tangent */
+int hf_large_steps_apply(uint32_t W, uint32_t H, double lambda, const float *v, float *u, hf_stream_t stream);
+/* v ~= A^-1 u (LargeSteps.from_differential); its adjoint and tangent are the solve of the incoming gradient / tangent */
+int hf_large_steps_solve(uint32_t W, uint32_t H, double lambda, const float *u, float *v, int warm, uint32_t max_iter,
+                         float rel_tol, float *workspace, float *info, hf_stream_t stream);
+
 /* ---- multi-GPU -------------------------------------------------------------------
  * Rays shard over image tiles, heights and acceleration data are replicated, every GPU accumulates a private
  * dL/dheight texture; this is the ONE collective of the path: an in-place sum all-reduce (float32) of that

@@ -178,6 +178,10 @@ SYMBOLS = {
                                              C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _fp, _fp,
                                              C.POINTER(C.c_float * 9), C.c_float, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp,
                                              C.c_void_p]),
+    "hf_large_steps_workspace_floats": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "hf_large_steps_apply": (C.c_int, [C.c_uint32, C.c_uint32, C.c_double, _fp, _fp, C.c_void_p]),
+    "hf_large_steps_solve": (C.c_int, [C.c_uint32, C.c_uint32, C.c_double, _fp, _fp, C.c_int, C.c_uint32, C.c_float, _fp, _fp,
+                                       C.c_void_p]),
     "hf_bounce_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
                                  C.POINTER(_fp * 3), _fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_float * 3),
                                  C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_void_p]),

@@ -1930,6 +1930,47 @@ extern "C" int hf_ray_test_packet(const hf_field_t *hf, uint32_t n, const float 
     return packet_trace("hf_ray_test_packet", 1, hf, n, h_o, h_d, h_maxt, h_active, nullptr, nullptr, nullptr, h_hit);
 }
 
+// ---- large-steps preconditioning: u = (I + lambda L) v and its conjugate-gradient solve on the vertex grid ----
+// the grid limits are hf_create's: at most 32768 cells per side and 2^30 vertices
+static int large_steps_grid(const char *who, uint32_t W, uint32_t H, double lambda) {
+    if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the grid must have at least 2 x 2 vertices (got %u x %u)", who, W, H);
+    if (W > 32769u || H > 32769u || (size_t) W * (size_t) H > ((size_t) 1 << 30))
+        return fail(HF_EINVAL, "%s: grid too large (more than 32768 cells per side or 2^30 vertices)", who);
+    if (!(lambda >= 0.0) || !isfinite(lambda)) return fail(HF_EINVAL, "%s: lambda must be finite and >= 0 (got %g)", who, lambda);
+    return HF_OK;
+}
+
+extern "C" size_t hf_large_steps_workspace_floats(uint32_t W, uint32_t H) {
+    if (W < 2 || H < 2) return 0;
+    return hf_large_steps_scratch_floats(W, H);
+}
+
+extern "C" int hf_large_steps_apply(uint32_t W, uint32_t H, double lambda, const float *v, float *u, hf_stream_t stream) {
+    const char *fn = "hf_large_steps_apply";
+    if (!v || !u) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    const int rc = large_steps_grid(fn, W, H, lambda);
+    if (rc != HF_OK) return rc;
+    if (v == u) return fail(HF_EINVAL, "%s: v and u must be different buffers (a block reads its neighbours' vertices)", fn);
+    hf_launch_large_steps_apply(W, H, lambda, v, u, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_large_steps_solve(uint32_t W, uint32_t H, double lambda, const float *u, float *v, int warm, uint32_t max_iter,
+                                    float rel_tol, float *workspace, float *info, hf_stream_t stream) {
+    const char *fn = "hf_large_steps_solve";
+    if (!u || !v || !workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    const int rc = large_steps_grid(fn, W, H, lambda);
+    if (rc != HF_OK) return rc;
+    if (!(rel_tol >= 0.f)) return fail(HF_EINVAL, "%s: rel_tol must be >= 0 (got %g)", fn, (double) rel_tol);
+    if (max_iter == 0) return fail(HF_EINVAL, "%s: max_iter must be at least 1", fn);
+    if (u == v) return fail(HF_EINVAL, "%s: u and v must be different buffers", fn);
+    if ((uintptr_t) workspace % 16u) return fail(HF_EINVAL, "%s: the workspace must be 16-byte aligned", fn);
+    hf_launch_large_steps_solve(W, H, lambda, u, v, warm, max_iter, rel_tol, workspace, info, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- multi-GPU: the one collective of the path --------------------------------------------
 namespace {
 typedef int (*nccl_allreduce_fn)(const void *, void *, size_t, int, int, void *, hipStream_t);

@@ -16,6 +16,8 @@
 //   hf_sample_position / _adjoint / _tangent_kernel  Mesh::sample_position and its two derivatives
 //   hf_attr / _tangent_kernel<TYPE, SIZE>, hf_attr_adjoint_tile / _face_adjoint_kernel<SIZE>  shape attributes:
 //        Mesh::eval_attribute and its two derivatives
+//   hf_large_steps_stencil / _update / _cold / _sum / _finish_kernel  large-steps preconditioning: (I + lambda L) v and
+//        its conjugate-gradient solve on the vertex grid (end of the file)
 //
 // Traversal = a walk of the implicit quadtree over the cells (the grid is mirrored so the ray direction is
 // non-negative on both axes: "order space").  One visit of an inner node fetches its record -- a plane through
@@ -5587,4 +5589,391 @@ void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream) {
     } else {
         hipLaunchKernelGGL(hf_envmap_eval_kernel<true>, grid, block, 0, stream, a);
     }
+}
+
+// ---------------------------------------------------------------------------------
+// Large-steps preconditioning (include/hf.h): A = I + lambda L on the W x H vertex grid, L the combinatorial
+// Laplacian of the tessellation (every cell split along v10-v01), and conjugate gradients for A v = u.
+//
+// Bandwidth-bound 7-point stencil.  An ITEM is 4 consecutive columns of HF_LS_ROWS consecutive rows; consecutive lanes
+// own consecutive column groups, so a wave's row accesses are 16 bytes per lane, contiguous (rows of a grid whose W is
+// no multiple of 4 are only 4-byte aligned: the same wide instruction, which takes dword alignment).  The rows above
+// and below and the two columns beside a lane's own come as further loads of lines its neighbours fetch anyway (L1 /
+// L2 hits; no LDS tile).  A group that hangs over the right edge takes the scalar path, rows below the grid are skipped,
+// and a vertex's degree comes from index tests.
+// Per CG iteration two launches: (a) p = r + beta p_old into the OTHER p buffer (so no block reads a halo value that
+// another has replaced), q = A p, the blocks' partials of <p, q>;  (b) x += alpha p, r -= alpha q, the partials of
+// <r, r>.  A partial is one double per block, from a shuffle tree and 4 LDS slots; the next launch's prologue has
+// every block add them up in one order, so alpha and beta are the same in every block and a solve is bitwise
+// repeatable for a fixed grid.  No float atomics.  About 11 passes over the grid per iteration:
+// (a) r and p_old 1.5 times each (6 rows for 4) + p + q, (b) x, p, r, q in, x, r out.
+// Around the iterations: one start launch (r = u, x = 0, or r = u - A x0 for a warm start) and two end launches (the
+// exact solve in the eigenspace of the constant field, and info).  The launch count does not depend on the data: a
+// device word per launch parity says that the solve has ended, and the launches that follow return after reading it.
+// ---------------------------------------------------------------------------------
+#define HF_LS_ROWS 4
+typedef float hf_ls_f4 __attribute__((ext_vector_type(4), aligned(4)));
+
+struct hf_ls_args {
+    uint32_t W, H, G, k;                 // G: column groups per row; k: the iteration of this launch
+    uint32_t nparts, max_iter;           // partials per sum = the grid of every launch of the solve
+    uint64_t items;                      // G * ceil(H / HF_LS_ROWS)
+    float lambda;
+    double tol2;                         // rel_tol^2
+    const float *in0, *in1;              // apply: v, -; residual: x0, u; (a): r, p_old
+    float *out0, *out1;                  // apply: u, -; residual: r, -;  (a): p, q
+    float *x, *r;                        // (b), cold start
+    const float *p, *q;                  // (b)
+    double *part_pq, *part_rr, *part_uu, *part_su; // nparts doubles each; su: the sum of u
+    double *S;                           // { uu, rr[2], rr at convergence }
+    uint32_t *flag;                      // { done[2], iterations at convergence }
+    float *info;
+};
+
+// the sum of a double over the block, the same in every thread (xor butterfly, then the 4 waves' sums in order); every
+// thread of the block calls it
+__device__ __forceinline__ double ls_block_sum(double v) {
+    __shared__ double s_ls[HF_BLOCK / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    if ((threadIdx.x & 63u) == 0u) s_ls[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = s_ls[0];
+#pragma unroll
+    for (int j = 1; j < HF_BLOCK / 64; ++j) s += s_ls[j];
+    __syncthreads(); // (the next call writes the slots again)
+    return s;
+}
+// the sum of n partials in one fixed order, the same in every thread of every block
+__device__ __forceinline__ double ls_sum_partials(const double *part, uint32_t n) {
+    double s = 0.0;
+    for (uint32_t i = threadIdx.x; i < n; i += HF_BLOCK) s += part[i];
+    return ls_block_sum(s);
+}
+
+struct ls_row6 { float v[6]; }; // columns j0 - 1 .. j0 + 4 of a row, 0 outside the grid
+__device__ __forceinline__ ls_row6 ls_load_row(const float *__restrict__ a, bool row_in, size_t off, uint32_t j0, uint32_t W) {
+    ls_row6 o;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) o.v[c] = 0.f;
+    if (!row_in) return o;
+    if (j0 + 4u <= W) {
+        const hf_ls_f4 t = *(const hf_ls_f4 *) (a + off);
+        o.v[1] = t.x; o.v[2] = t.y; o.v[3] = t.z; o.v[4] = t.w;
+    } else {
+#pragma unroll
+        for (uint32_t c = 0; c < 3; ++c)
+            if (j0 + c < W) o.v[1 + c] = a[off + c];
+    }
+    if (j0 > 0u) o.v[0] = a[off - 1];
+    if (j0 + 4u < W) o.v[5] = a[off + 4];
+    return o;
+}
+__device__ __forceinline__ void ls_store4(float *a, size_t off, uint32_t j0, uint32_t W, const float v[4]) {
+    if (j0 + 4u <= W) {
+        hf_ls_f4 t; t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
+        *(hf_ls_f4 *) (a + off) = t;
+    } else {
+#pragma unroll
+        for (uint32_t c = 0; c < 3; ++c)
+            if (j0 + c < W) a[off + c] = v[c];
+    }
+}
+__device__ __forceinline__ void ls_load4(const float *a, size_t off, uint32_t j0, uint32_t W, float v[4]) {
+    if (j0 + 4u <= W) {
+        const hf_ls_f4 t = *(const hf_ls_f4 *) (a + off);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) v[c] = (c < 3u && j0 + c < W) ? a[off + c] : 0.f;
+    }
+}
+// (A v) at column c (1..4 of the rows' six) of row i: up / mid / dn are rows i - 1, i, i + 1.  The neighbours in one
+// order -- left, right, up, down, (i+1, j-1), (i-1, j+1) --, one rounding per operation; a neighbour outside the grid
+// was loaded as 0 and is not counted in the degree
+__device__ __forceinline__ float ls_stencil(const ls_row6 &up, const ls_row6 &mid, const ls_row6 &dn, int c, uint32_t i,
+                                            uint32_t j, uint32_t W, uint32_t H, float lambda) {
+    const bool l = j > 0u, r = j + 1u < W, u = i > 0u, d = i + 1u < H;
+    const float deg = (float) ((int) l + (int) r + (int) u + (int) d + (int) (d && l) + (int) (u && r));
+    float s = mid.v[c - 1] + mid.v[c + 1];
+    s = s + up.v[c];
+    s = s + dn.v[c];
+    s = s + dn.v[c - 1];
+    s = s + up.v[c + 1];
+    return mid.v[c] + lambda * (deg * mid.v[c] - s);
+}
+
+// the prologue of launch (a) of iteration k: LS_ENDED when the solve has ended (the block returns), LS_ZERO when u = 0
+// (iteration 0 only: the answer is 0 exactly, whatever the guess; the block clears its part of x), else LS_GO with beta.
+// Block 0 keeps the scalars that later launches read; no launch reads a word that the same launch writes.
+enum { LS_ENDED = 0, LS_GO = 1, LS_ZERO = 2 };
+__device__ __forceinline__ int ls_begin_iteration(const hf_ls_args &a, float &beta) {
+    const uint32_t k = a.k;
+    if (k > 0u && a.flag[(k - 1u) & 1u] != 0u) { // one uniform load
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.flag[k & 1u] = 1u;
+        return LS_ENDED;
+    }
+    const double rr = ls_sum_partials(a.part_rr, a.nparts);
+    const double uu = k == 0u ? ls_sum_partials(a.part_uu, a.nparts) : a.S[0];
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    const bool zero = k == 0u && uu == 0.0;
+    // (false for a NaN or an infinite <r, r>: such a solve runs its max_iter launches and reports the NaN)
+    if (zero || (rr <= a.tol2 * uu && rr < (double) __builtin_inff())) {
+        if (first) { a.flag[k & 1u] = 1u; a.flag[2] = k; a.S[3] = zero ? 0.0 : rr; if (k == 0u) a.S[0] = uu; }
+        return zero ? LS_ZERO : LS_ENDED;
+    }
+    double b = 0.0;
+    if (k > 0u) { const double old = a.S[1 + ((k - 1u) & 1u)]; b = old != 0.0 ? rr / old : 0.0; }
+    beta = (float) b;
+    if (first) { a.S[1 + (k & 1u)] = rr; if (k == 0u) a.S[0] = uu; }
+    return LS_GO;
+}
+
+enum { LS_APPLY = 0, LS_RESIDUAL = 1, LS_FIRST = 2, LS_ITER = 3 };
+// LS_APPLY: out0 = A in0.  LS_RESIDUAL (warm start): out0 = in1 - A in0, partials of <r, r> and <u, u>, the flags
+// cleared.  LS_FIRST / LS_ITER: launch (a), p = r (iteration 0: p_old holds nothing) / p = r + beta p_old.
+template <int MODE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_large_steps_stencil_kernel(hf_ls_args a) {
+    float beta = 0.f;
+    const uint32_t W = a.W, H = a.H, G = a.G;
+    if (MODE >= LS_FIRST) {
+        const int go = ls_begin_iteration(a, beta);
+        if (go == LS_ENDED) return;
+        if (MODE == LS_FIRST && go == LS_ZERO) {
+            const float z[4] = { 0.f, 0.f, 0.f, 0.f };
+            for (uint64_t it = (uint64_t) blockIdx.x * HF_BLOCK + threadIdx.x; it < a.items; it += (uint64_t) gridDim.x * HF_BLOCK) {
+                const uint32_t strip = (uint32_t) (it / G), j0 = 4u * (uint32_t) (it - (uint64_t) strip * G);
+                for (uint32_t i = strip * HF_LS_ROWS; i < H && i < (strip + 1u) * HF_LS_ROWS; ++i)
+                    ls_store4(a.x, (size_t) i * W + j0, j0, W, z);
+            }
+            return;
+        }
+    }
+    if (MODE == LS_RESIDUAL && blockIdx.x == 0 && threadIdx.x < 3u) a.flag[threadIdx.x] = 0u;
+    const float lambda = a.lambda;
+    double acc = 0.0, acc2 = 0.0, acc3 = 0.0;
+    const uint64_t stride = (uint64_t) gridDim.x * HF_BLOCK;
+    for (uint64_t it = (uint64_t) blockIdx.x * HF_BLOCK + threadIdx.x; it < a.items; it += stride) {
+        const uint32_t strip = (uint32_t) (it / G), j0 = 4u * (uint32_t) (it - (uint64_t) strip * G), i0 = strip * HF_LS_ROWS;
+        ls_row6 P[HF_LS_ROWS + 2]; // rows i0 - 1 .. i0 + HF_LS_ROWS of what the stencil applies to
+#pragma unroll
+        for (int rr = 0; rr < HF_LS_ROWS + 2; ++rr) {
+            const uint32_t i = i0 + (uint32_t) rr - 1u; // (wraps for the row above row 0: not < H)
+            const bool in = i < H;
+            const size_t off = (size_t) (in ? i : 0u) * W + j0;
+            P[rr] = ls_load_row(a.in0, in, off, j0, W);
+            if (MODE == LS_ITER) {
+                const ls_row6 o = ls_load_row(a.in1, in, off, j0, W);
+#pragma unroll
+                for (int c = 0; c < 6; ++c) P[rr].v[c] = P[rr].v[c] + beta * o.v[c];
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < HF_LS_ROWS; ++rr) {
+            const uint32_t i = i0 + (uint32_t) rr;
+            if (i >= H) break;
+            const size_t off = (size_t) i * W + j0;
+            float q[4], p[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                p[c] = P[rr + 1].v[c + 1];
+                q[c] = ls_stencil(P[rr], P[rr + 1], P[rr + 2], c + 1, i, j0 + (uint32_t) c, W, H, lambda);
+            }
+            if (MODE == LS_APPLY) {
+                ls_store4(a.out0, off, j0, W, q);
+            } else if (MODE == LS_RESIDUAL) {
+                float u[4];
+                ls_load4(a.in1, off, j0, W, u);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const bool in = j0 + (uint32_t) c < W;
+                    q[c] = u[c] - q[c];
+                    acc += in ? (double) q[c] * (double) q[c] : 0.0;
+                    acc2 += in ? (double) u[c] * (double) u[c] : 0.0;
+                    acc3 += in ? (double) u[c] : 0.0;
+                }
+                ls_store4(a.out0, off, j0, W, q);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc += j0 + (uint32_t) c < W ? (double) p[c] * (double) q[c] : 0.0;
+                ls_store4(a.out0, off, j0, W, p);
+                ls_store4(a.out1, off, j0, W, q);
+            }
+        }
+    }
+    if (MODE == LS_APPLY) return;
+    const double s = ls_block_sum(acc);
+    if (MODE == LS_RESIDUAL) {
+        const double s2 = ls_block_sum(acc2), s3 = ls_block_sum(acc3);
+        if (threadIdx.x == 0) { a.part_rr[blockIdx.x] = s; a.part_uu[blockIdx.x] = s2; a.part_su[blockIdx.x] = s3; }
+    } else if (threadIdx.x == 0) {
+        a.part_pq[blockIdx.x] = s;
+    }
+}
+
+// cold start: r = u, x = 0, the partials of <u, u> (= <r, r>), the flags cleared
+__global__ __launch_bounds__(HF_BLOCK) void hf_large_steps_cold_kernel(hf_ls_args a) {
+    if (blockIdx.x == 0 && threadIdx.x < 3u) a.flag[threadIdx.x] = 0u;
+    const uint32_t W = a.W, H = a.H, G = a.G;
+    double acc = 0.0, acc3 = 0.0;
+    const uint64_t stride = (uint64_t) gridDim.x * HF_BLOCK;
+    for (uint64_t it = (uint64_t) blockIdx.x * HF_BLOCK + threadIdx.x; it < a.items; it += stride) {
+        const uint32_t strip = (uint32_t) (it / G), j0 = 4u * (uint32_t) (it - (uint64_t) strip * G), i0 = strip * HF_LS_ROWS;
+#pragma unroll
+        for (int rr = 0; rr < HF_LS_ROWS; ++rr) {
+            const uint32_t i = i0 + (uint32_t) rr;
+            if (i >= H) break;
+            const size_t off = (size_t) i * W + j0;
+            float u[4];
+            const float z[4] = { 0.f, 0.f, 0.f, 0.f };
+            ls_load4(a.in1, off, j0, W, u);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { acc += (double) u[c] * (double) u[c]; acc3 += (double) u[c]; } // (0 beyond the row's end)
+            ls_store4(a.r, off, j0, W, u);
+            ls_store4(a.x, off, j0, W, z);
+        }
+    }
+    const double s = ls_block_sum(acc), s3 = ls_block_sum(acc3);
+    if (threadIdx.x == 0) { a.part_rr[blockIdx.x] = s; a.part_uu[blockIdx.x] = s; a.part_su[blockIdx.x] = s3; }
+}
+
+// launch (b) of iteration k: alpha = <r, r> / <p, q>, x += alpha p, r -= alpha q, the partials of the new <r, r>
+__global__ __launch_bounds__(HF_BLOCK) void hf_large_steps_update_kernel(hf_ls_args a) {
+    const uint32_t k = a.k;
+    if (a.flag[k & 1u] != 0u) return; // one uniform load
+    const uint32_t W = a.W, H = a.H, G = a.G;
+    const double pq = ls_sum_partials(a.part_pq, a.nparts);
+    const double rr = a.S[1 + (k & 1u)];
+    const float alpha = (float) (pq != 0.0 ? rr / pq : 0.0);
+    double acc = 0.0;
+    const uint64_t stride = (uint64_t) gridDim.x * HF_BLOCK;
+    for (uint64_t it = (uint64_t) blockIdx.x * HF_BLOCK + threadIdx.x; it < a.items; it += stride) {
+        const uint32_t strip = (uint32_t) (it / G), j0 = 4u * (uint32_t) (it - (uint64_t) strip * G), i0 = strip * HF_LS_ROWS;
+#pragma unroll
+        for (int rr_ = 0; rr_ < HF_LS_ROWS; ++rr_) {
+            const uint32_t i = i0 + (uint32_t) rr_;
+            if (i >= H) break;
+            const size_t off = (size_t) i * W + j0;
+            float x[4], p[4], r[4], q[4];
+            ls_load4(a.x, off, j0, W, x);
+            ls_load4(a.p, off, j0, W, p);
+            ls_load4(a.r, off, j0, W, r);
+            ls_load4(a.q, off, j0, W, q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                x[c] = x[c] + alpha * p[c];
+                r[c] = r[c] - alpha * q[c];
+                acc += (double) r[c] * (double) r[c]; // (0 beyond the row's end)
+            }
+            ls_store4(a.x, off, j0, W, x);
+            ls_store4(a.r, off, j0, W, r);
+        }
+    }
+    const double s = ls_block_sum(acc);
+    if (threadIdx.x == 0) a.part_rr[blockIdx.x] = s;
+}
+
+// After the last iteration.  A 1 = 1 and 1^T A = 1^T: the constant field is an eigenvector of A (eigenvalue 1), and the
+// sum of the true residual u - A x is sum(u) - sum(x).  Adding c = (sum(u) - sum(x)) / (W H) to every x is the exact
+// solve in that eigenspace: it takes the true residual's mean out (its norm cannot grow) and makes the solve keep the
+// sum of its right-hand side, which rounding in the recursion does not.  Launch 1: the partials of sum(x).
+__global__ __launch_bounds__(HF_BLOCK) void hf_large_steps_sum_kernel(hf_ls_args a) {
+    const uint32_t W = a.W, H = a.H, G = a.G;
+    double acc = 0.0;
+    for (uint64_t it = (uint64_t) blockIdx.x * HF_BLOCK + threadIdx.x; it < a.items; it += (uint64_t) gridDim.x * HF_BLOCK) {
+        const uint32_t strip = (uint32_t) (it / G), j0 = 4u * (uint32_t) (it - (uint64_t) strip * G);
+        for (uint32_t i = strip * HF_LS_ROWS; i < H && i < (strip + 1u) * HF_LS_ROWS; ++i) {
+            float x[4];
+            ls_load4(a.x, (size_t) i * W + j0, j0, W, x);
+            acc += ((double) x[0] + (double) x[1]) + ((double) x[2] + (double) x[3]);
+        }
+    }
+    const double s = ls_block_sum(acc);
+    if (threadIdx.x == 0) a.part_pq[blockIdx.x] = s;
+}
+// Launch 2: x += c (not for u = 0: the zeros stay zeros), and info = { iterations performed, |r| / |u| } (the recursive
+// residual; 0 for u = 0: the answer is exact)
+__global__ __launch_bounds__(HF_BLOCK) void hf_large_steps_finish_kernel(hf_ls_args a) {
+    const uint32_t W = a.W, H = a.H, G = a.G;
+    const double su = ls_sum_partials(a.part_su, a.nparts), sx = ls_sum_partials(a.part_pq, a.nparts);
+    const double uu = a.S[0];
+    if (a.info && blockIdx.x == 0) {
+        const double last = ls_sum_partials(a.part_rr, a.nparts);
+        if (threadIdx.x == 0) {
+            const bool done = a.flag[(a.max_iter - 1u) & 1u] != 0u;
+            const double rr = done ? a.S[3] : last;
+            a.info[0] = (float) (done ? a.flag[2] : a.max_iter);
+            a.info[1] = uu != 0.0 ? (float) __builtin_sqrt(rr / uu) : 0.f;
+        }
+    }
+    if (uu == 0.0) return;
+    const float c = (float) ((su - sx) / ((double) W * (double) H));
+    for (uint64_t it = (uint64_t) blockIdx.x * HF_BLOCK + threadIdx.x; it < a.items; it += (uint64_t) gridDim.x * HF_BLOCK) {
+        const uint32_t strip = (uint32_t) (it / G), j0 = 4u * (uint32_t) (it - (uint64_t) strip * G);
+        for (uint32_t i = strip * HF_LS_ROWS; i < H && i < (strip + 1u) * HF_LS_ROWS; ++i) {
+            const size_t off = (size_t) i * W + j0;
+            float x[4];
+            ls_load4(a.x, off, j0, W, x);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] = x[k] + c;
+            ls_store4(a.x, off, j0, W, x);
+        }
+    }
+}
+
+static void ls_shape(hf_ls_args &a, uint32_t W, uint32_t H, double lambda) {
+    a.W = W; a.H = H; a.G = (W + 3u) / 4u;
+    a.items = (uint64_t) a.G * ((H + HF_LS_ROWS - 1u) / HF_LS_ROWS);
+    a.lambda = (float) lambda;
+}
+// the floats of a solve's workspace (the layout: hf_launch_large_steps_solve)
+size_t hf_large_steps_scratch_floats(uint32_t W, uint32_t H) {
+    const size_t n4 = ((size_t) W * H + 3u) & ~(size_t) 3u;
+    return 4 * n4 + 2 * (4 * (size_t) HF_FLAT_GRID_CAP + 4) + 4;
+}
+
+void hf_launch_large_steps_apply(uint32_t W, uint32_t H, double lambda, const float *v, float *u, hipStream_t stream) {
+    hf_ls_args a = {};
+    ls_shape(a, W, H, lambda);
+    a.in0 = v; a.out0 = u;
+    hipLaunchKernelGGL(hf_large_steps_stencil_kernel<LS_APPLY>, dim3(grid_for(a.items)), dim3(HF_BLOCK), 0, stream, a);
+}
+
+// workspace (include/hf.h): r, q, p[2] of n4 = W H rounded up to 4 floats each, then as doubles the three rows of
+// partials and the scalars, then the flag words.  1 + 2 max_iter + 2 launches, the same whatever the data.
+void hf_launch_large_steps_solve(uint32_t W, uint32_t H, double lambda, const float *u, float *v, int warm, uint32_t max_iter,
+                                 float rel_tol, float *workspace, float *info, hipStream_t stream) {
+    hf_ls_args a = {};
+    ls_shape(a, W, H, lambda);
+    const size_t n4 = ((size_t) W * H + 3u) & ~(size_t) 3u;
+    float *r = workspace, *q = r + n4, *p[2] = { q + n4, q + 2 * n4 };
+    a.part_pq = (double *) (workspace + 4 * n4);
+    a.part_rr = a.part_pq + HF_FLAT_GRID_CAP;
+    a.part_uu = a.part_rr + HF_FLAT_GRID_CAP;
+    a.part_su = a.part_uu + HF_FLAT_GRID_CAP;
+    a.S = a.part_su + HF_FLAT_GRID_CAP;
+    a.flag = (uint32_t *) (a.S + 4);
+    a.info = info;
+    a.max_iter = max_iter;
+    a.tol2 = (double) rel_tol * (double) rel_tol;
+    a.x = v; a.r = r;
+    const dim3 grid(grid_for(a.items)), block(HF_BLOCK);
+    a.nparts = grid.x;
+    if (warm) {
+        a.in0 = v; a.in1 = u; a.out0 = r;
+        hipLaunchKernelGGL(hf_large_steps_stencil_kernel<LS_RESIDUAL>, grid, block, 0, stream, a);
+    } else {
+        a.in1 = u;
+        hipLaunchKernelGGL(hf_large_steps_cold_kernel, grid, block, 0, stream, a);
+    }
+    for (uint32_t k = 0; k < max_iter; ++k) {
+        a.k = k;
+        a.in0 = r; a.in1 = p[(k + 1u) & 1u]; a.out0 = p[k & 1u]; a.out1 = q;
+        if (k == 0) hipLaunchKernelGGL(hf_large_steps_stencil_kernel<LS_FIRST>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(hf_large_steps_stencil_kernel<LS_ITER>, grid, block, 0, stream, a);
+        a.p = p[k & 1u]; a.q = q;
+        hipLaunchKernelGGL(hf_large_steps_update_kernel, grid, block, 0, stream, a);
+    }
+    hipLaunchKernelGGL(hf_large_steps_sum_kernel, grid, block, 0, stream, a);
+    hipLaunchKernelGGL(hf_large_steps_finish_kernel, grid, block, 0, stream, a);
 }

@@ -243,3 +243,9 @@ void hf_launch_param_adjoint(const hf_dev_field &f, size_t n, const float *const
 void hf_launch_param_tangent(const hf_dev_field &f, size_t n, const float *const uv[2], const uint8_t *active,
                              uint32_t flags, const float *dh, const float *d_to_world, const hf_si_tangent_t *out,
                              hipStream_t stream, const float4 *vn);
+// ---- large-steps preconditioning (hf_large_steps_*): A = I + lambda L on the vertex grid; the buffers are the caller's ----
+size_t hf_large_steps_scratch_floats(uint32_t W, uint32_t H);
+void hf_launch_large_steps_apply(uint32_t W, uint32_t H, double lambda, const float *v, float *u, hipStream_t stream);
+// conjugate gradients, 2 max_iter + 3 launches whatever the data; no host synchronisation
+void hf_launch_large_steps_solve(uint32_t W, uint32_t H, double lambda, const float *u, float *v, int warm, uint32_t max_iter,
+                                 float rel_tol, float *workspace, float *info, hipStream_t stream);

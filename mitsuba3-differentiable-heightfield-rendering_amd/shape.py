@@ -2343,3 +2343,112 @@ def reparameterize_ray_adjoint(shape, ray, grad_direction, grad_divergence, num_
     grad_o, grad_d = _reparam_backward_full(shape, ro, rd, gd, gdiv, act, ray_index, cfg, grad_h, bool(o), bool(d), grad_tw,
                                             shape._stream())
     return grad_h, grad_o, grad_d, grad_tw
+
+
+class _LargeStepsApplyOp(torch.autograd.Function):
+    """u = (I + lambda L) v (hf_large_steps_apply).  The matrix is symmetric: backward and jvp are the apply."""
+
+    @staticmethod
+    def forward(ctx, ls, v):
+        ctx.misc = ls
+        return ls._apply(v)
+
+    @staticmethod
+    def jvp(ctx, _ls, dv):
+        return ctx.misc._apply(dv)
+
+    @staticmethod
+    def backward(ctx, grad_u):
+        return None, ctx.misc._apply(grad_u)
+
+
+class _LargeStepsSolveOp(torch.autograd.Function):
+    """v = (I + lambda L)^-1 u (hf_large_steps_solve); backward and jvp are the solve of the incoming gradient / tangent
+    (SolveCholesky.forward / backward, largesteps.py:41-49), always from a cold start."""
+
+    @staticmethod
+    def forward(ctx, ls, u, guess, info):
+        ctx.misc = ls
+        return ls._solve(u, guess, info)
+
+    @staticmethod
+    def jvp(ctx, _ls, du, _guess, _info):
+        return ctx.misc._solve(du, None, None)
+
+    @staticmethod
+    def backward(ctx, grad_v):
+        return None, ctx.misc._solve(grad_v, None, None), None, None
+
+
+class LargeSteps:
+    """The reference's ``mitsuba.ad.largesteps.LargeSteps`` (src/python/python/ad/largesteps.py:55-161; Nicolet et al.
+    2021) for a ``width`` x ``height`` height grid: optimise the latent ``u = (I + lambda_ L) v`` instead of the heights
+    ``v``, with L the combinatorial Laplacian of the tessellation (include/hf.h).  ``to_differential`` is one stencil
+    launch, ``from_differential`` a conjugate-gradient solve (at most ``max_iter`` iterations, to the relative residual
+    ``tol``) in place of the reference's sparse Cholesky factorisation; both take and return [H, W] float32 device
+    tensors, are differentiable in both modes, never synchronise (unless asked to check) and can be captured.  The object
+    owns the solver's workspace: its calls belong on one stream at a time."""
+
+    def __init__(self, width, height, lambda_=19.0, max_iter=256, tol=1e-6):
+        if int(width) < 2 or int(height) < 2:
+            raise ValueError("LargeSteps: the grid must have at least 2 x 2 vertices")
+        if not (float(lambda_) >= 0.0 and math.isfinite(float(lambda_))):
+            raise ValueError("LargeSteps: lambda_ must be finite and >= 0")
+        if int(max_iter) < 1:
+            raise ValueError("LargeSteps: max_iter must be at least 1")
+        if not float(tol) >= 0.0:
+            raise ValueError("LargeSteps: tol must be >= 0")
+        self.width, self.height = int(width), int(height)
+        self.lambda_, self.max_iter, self.tol = float(lambda_), int(max_iter), float(tol)
+        self._workspace = None
+        self._info = None
+
+    def _field(self, x, what):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError(f"LargeSteps: {what} must be a device tensor")
+        if tuple(x.shape) != (self.height, self.width):
+            raise ValueError(f"LargeSteps: {what} must be [{self.height}, {self.width}], got {tuple(x.shape)}")
+        return x.detach().to(dtype=torch.float32).contiguous()
+
+    def _apply(self, v):
+        v = self._field(v, "v")
+        u = torch.empty_like(v)
+        check(_capi.lib().hf_large_steps_apply(self.width, self.height, self.lambda_, v.data_ptr(), u.data_ptr(),
+                                               _stream_of(v.device)))
+        return u
+
+    def _solve(self, u, guess, info):
+        u = self._field(u, "u")
+        if self._workspace is None or self._workspace.device != u.device:
+            n = _capi.lib().hf_large_steps_workspace_floats(self.width, self.height)
+            self._workspace = torch.empty(n, dtype=torch.float32, device=u.device)
+        v = torch.empty_like(u) if guess is None else self._field(guess, "guess").to(u.device).clone()
+        check(_capi.lib().hf_large_steps_solve(self.width, self.height, self.lambda_, u.data_ptr(), v.data_ptr(),
+                                               0 if guess is None else 1, self.max_iter, self.tol,
+                                               self._workspace.data_ptr(), _ptr(info), _stream_of(u.device)))
+        return v
+
+    def to_differential(self, v):
+        """the latent u = (I + lambda_ L) v of the heights v (largesteps.py:122-141)"""
+        return _LargeStepsApplyOp.apply(self, v)
+
+    def from_differential(self, u, guess=None, check=False):
+        """the heights v = (I + lambda_ L)^-1 u of the latent u (largesteps.py:143-161).  ``guess``: a tensor the solve
+        starts from (detached; the previous step's heights).  ``check``: synchronise and raise RuntimeError when the
+        solve ended at ``max_iter`` above ``tol``."""
+        info = torch.zeros(2, dtype=torch.float32, device=u.device) if isinstance(u, torch.Tensor) and u.is_cuda else None
+        v = _LargeStepsSolveOp.apply(self, u, None if guess is None else guess.detach(), info)
+        self._info = info
+        if check:
+            it, res = self.last_info()
+            if not res <= self.tol:
+                raise RuntimeError(f"LargeSteps.from_differential: relative residual {res:.3e} after {it} iterations "
+                                   f"(tol {self.tol:.3e}, max_iter {self.max_iter})")
+        return v
+
+    def last_info(self):
+        """(iterations, relative residual) of the last ``from_differential``; synchronises"""
+        if self._info is None:
+            raise RuntimeError("LargeSteps.last_info: no solve yet")
+        it, res = self._info.tolist()
+        return int(it), float(res)
