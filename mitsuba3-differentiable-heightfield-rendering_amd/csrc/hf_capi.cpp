@@ -1122,22 +1122,68 @@ extern "C" int hf_point_lighting_tangent(size_t n, uint32_t spp, const float *co
                             (const hf_dir_light_t *) lights, albedo, vis, dsh_n, dp, nullptr, dimage, (hipStream_t) stream);
 }
 
+// ---- lighting rows, shared: what the sky, envmap and bounce entries below check and fill alike (A: the row's argument
+// block, zeroed by the caller).  All checks come before anything touches a device. ----
+// the wavefront and the sample count; `dirs`: the row's word for its directions, other_null: a row's further pointers
+template <class A>
+static int light_args(const char *who, const char *dirs, size_t n, uint32_t spp, const float *const sh_n[3],
+                      const float *const d[3], const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                      const uint32_t *ray_id, bool other_null, A &a) {
+    if (!all3(sh_n) || !all3(d) || !t || other_null) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 %s per sample (got %u)", who, dirs, num_rays);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    a.n = n; a.spp = spp; a.num_rays = num_rays; a.seed = seed; a.ray_id = ray_id; a.t = t; a.weight = weight;
+    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
+    return HF_OK;
+}
+// the outputs of a *_rays entry (and the two rows only it and the forward read)
+template <class A>
+static int light_rays_out(const char *who, const float *const p[3], const float *const nrm[3], uint32_t k,
+                          float *const out_o[3], float *const out_d[3], float *out_maxt, A &a) {
+    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", who);
+    a.k = k; a.out_maxt = out_maxt;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
+    return HF_OK;
+}
+// of a forward entry
+template <class A>
+static int light_forward_out(const char *who, const float *const p[3], const float *const nrm[3], float *image, A &a) {
+    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", who);
+    a.image = image;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    return HF_OK;
+}
+// the tangents of sh_n and weight (NULL: zero) and the image of a tangent entry
+template <class A>
+static int light_tangent_io(const char *who, bool other_null, const float *const dsh_n[3], const float *dweight,
+                            float *dimage, A &a) {
+    if (other_null || !dimage) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", who);
+    a.image = dimage; a.dw = dweight;
+    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    return HF_OK;
+}
+
+// the launch of mode `mode` of a row, and what it reports
+template <class A>
+static int light_launch(void (*launch)(int, const A &, hipStream_t), int mode, const A &a, hf_stream_t stream) {
+    launch(mode, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
 // ---- sky lighting: constant environment, the shadow rays traced inside the lighting kernel ----
-// What the four hf_sky_* entries share: the checks (all of them before anything touches a device) and the argument
-// block.  spp / num_rays / radiance / albedo: the film and the emitter of the three lighting entries (hf_sky_rays
-// passes 1, k + 1, 1, 1: its k must name one of 32 directions).
+// What the four hf_sky_* entries share.  spp / num_rays / radiance / albedo: the film and the emitter of the three
+// lighting entries (hf_sky_rays passes 1, k + 1, 1, 1: its k must name one of 32 directions).
 static int sky_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                     const float *t, const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
                     float radiance, float albedo, hf_sky_args &a) {
-    if (!all3(sh_n) || !all3(d) || !t) return fail(HF_EINVAL, "%s: NULL argument", who);
-    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
-    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 sky directions per sample (got %u)", who, num_rays);
-    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
-    if (!isfinite(radiance) || !isfinite(albedo)) return fail(HF_EINVAL, "%s: radiance and albedo must be finite", who);
     a = {};
-    a.n = n; a.spp = spp; a.num_rays = num_rays; a.seed = seed; a.ray_id = ray_id; a.t = t; a.weight = weight;
+    const int rc = light_args(who, "sky directions", n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, false, a);
+    if (rc != HF_OK) return rc;
+    if (!isfinite(radiance) || !isfinite(albedo)) return fail(HF_EINVAL, "%s: radiance and albedo must be finite", who);
     a.scale = (4.f * albedo * radiance) / (float) num_rays; // albedo/pi * L / pdf, pdf = 1 / (4 pi), averaged over num_rays
-    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
     return HF_OK;
 }
 
@@ -1147,14 +1193,9 @@ extern "C" int hf_sky_rays(size_t n, const float *const p[3], const float *const
     const char *fn = "hf_sky_rays";
     hf_sky_args a;
     if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
-    const int rc = sky_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, 1.f, 1.f, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    a.k = k; a.out_maxt = out_maxt;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
-    hf_launch_sky(3, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    int rc = sky_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, 1.f, 1.f, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
+    return light_launch(hf_launch_sky, 3, a, stream);
 }
 
 extern "C" int hf_sky_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
@@ -1166,15 +1207,11 @@ extern "C" int hf_sky_lighting(const hf_field_t *hf, size_t n, uint32_t spp, con
     hf_sky_args a;
     if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
     int rc = sky_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, radiance, albedo, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (rc != HF_OK || (rc = light_forward_out(fn, p, nrm, image, a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.image = image; a.vis_bits = vis_bits;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
-    hf_launch_sky(0, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    a.f = hf->dev; a.vis_bits = vis_bits;
+    return light_launch(hf_launch_sky, 0, a, stream);
 }
 
 extern "C" int hf_sky_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
@@ -1189,9 +1226,7 @@ extern "C" int hf_sky_lighting_adjoint(size_t n, uint32_t spp, const float *cons
     if (!vis_bits || !grad_image || !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL argument", fn);
     a.vis_bits = const_cast<uint32_t *>(vis_bits); a.gimg = grad_image; a.gw = grad_weight;
     for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n[c];
-    hf_launch_sky(1, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return light_launch(hf_launch_sky, 1, a, stream);
 }
 
 extern "C" int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
@@ -1201,24 +1236,18 @@ extern "C" int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *cons
                                        hf_stream_t stream) {
     const char *fn = "hf_sky_lighting_tangent";
     hf_sky_args a;
-    const int rc = sky_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, radiance, albedo, a);
-    if (rc != HF_OK) return rc;
-    if (!vis_bits || !dimage) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
-    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.image = dimage; a.dw = dweight;
-    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
-    hf_launch_sky(2, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    int rc = sky_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, radiance, albedo, a);
+    if (rc != HF_OK || (rc = light_tangent_io(fn, !vis_bits, dsh_n, dweight, dimage, a))) return rc;
+    a.vis_bits = const_cast<uint32_t *>(vis_bits);
+    return light_launch(hf_launch_sky, 2, a, stream);
 }
 
 // ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----
-// What the hf_envmap_* entries share: the checks of the map (all of them before anything touches a device) ...
+// What the hf_envmap_* entries share: the checks of the map (`a`: zeroed by the caller) ...
 static int envmap_map(const char *who, uint32_t W, uint32_t H, const float *data, bool need_data, const float *table,
                       bool need_table, const float rot[9], hf_envmap_args &a) {
     if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the map must have at least 2 x 2 texels (got %u x %u)", who, W, H);
     if ((need_data && !data) || (need_table && !table)) return fail(HF_EINVAL, "%s: NULL argument", who);
-    a = {};
     a.W = W; a.H = H; a.data = data; a.table = table;
     for (int j = 0; j < 9; ++j) {
         a.rot[j] = rot ? rot[j] : (j % 4 == 0 ? 1.f : 0.f);
@@ -1231,16 +1260,12 @@ static int envmap_args(const char *who, size_t n, uint32_t spp, const float *con
                        const float *t, const float *weight, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id,
                        uint32_t W, uint32_t H, const float *data, const float *table, const float rot[9], float albedo,
                        hf_envmap_args &a) {
-    if (!all3(sh_n) || !all3(d) || !t) return fail(HF_EINVAL, "%s: NULL argument", who);
-    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
-    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 directions per sample (got %u)", who, num_rays);
-    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
-    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
-    const int rc = envmap_map(who, W, H, data, true, table, true, rot, a);
+    a = {};
+    int rc = light_args(who, "directions", n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, false, a);
     if (rc != HF_OK) return rc;
-    a.n = n; a.spp = spp; a.num_rays = num_rays; a.seed = seed; a.ray_id = ray_id; a.t = t; a.weight = weight;
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    if ((rc = envmap_map(who, W, H, data, true, table, true, rot, a))) return rc;
     a.scale = (float) ((double) albedo / (3.141592653589793 * (double) num_rays));
-    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
     return HF_OK;
 }
 
@@ -1251,7 +1276,7 @@ extern "C" size_t hf_envmap_table_floats(uint32_t W, uint32_t H) {
 
 extern "C" int hf_envmap_build_table(uint32_t W, uint32_t H, const float *data, float u, float *table, hf_stream_t stream) {
     const char *fn = "hf_envmap_build_table";
-    hf_envmap_args a;
+    hf_envmap_args a = {};
     const int rc = envmap_map(fn, W, H, data, true, table, true, nullptr, a);
     if (rc != HF_OK) return rc;
     if (!(u >= 0.f && u <= 1.f)) return fail(HF_EINVAL, "%s: the defensive fraction must lie in [0, 1] (got %g)", fn, (double) u);
@@ -1265,7 +1290,7 @@ extern "C" int hf_envmap_sample_direction(size_t n, const float *const sample[2]
                                           float *out_pdf, uint32_t *out_cell, float *const out_frac[2],
                                           hf_stream_t stream) {
     const char *fn = "hf_envmap_sample_direction";
-    hf_envmap_args a;
+    hf_envmap_args a = {};
     const int rc = envmap_map(fn, W, H, data, true, table, true, rot, a);
     if (rc != HF_OK) return rc;
     if (!sample || !sample[0] || !sample[1] || !all3(out_d) || !out_weight || !out_pdf) return fail(HF_EINVAL, "%s: NULL argument", fn);
@@ -1273,38 +1298,32 @@ extern "C" int hf_envmap_sample_direction(size_t n, const float *const sample[2]
     if (out_frac) { a.out_frac[0] = out_frac[0]; a.out_frac[1] = out_frac[1]; }
     a.n = n; a.sample[0] = sample[0]; a.sample[1] = sample[1]; a.out_weight = out_weight; a.out_pdf = out_pdf; a.out_cell = out_cell;
     for (int c = 0; c < 3; ++c) a.out_d[c] = out_d[c];
-    hf_launch_envmap(4, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return light_launch(hf_launch_envmap, 4, a, stream);
 }
 
 extern "C" int hf_envmap_eval(size_t n, const float *const d[3], const uint8_t *active, uint32_t W, uint32_t H,
                               const float *data, const float rot[9], float *out, hf_stream_t stream) {
     const char *fn = "hf_envmap_eval";
-    hf_envmap_args a;
+    hf_envmap_args a = {};
     const int rc = envmap_map(fn, W, H, data, true, nullptr, false, rot, a);
     if (rc != HF_OK) return rc;
     if (!all3(d) || !out) return fail(HF_EINVAL, "%s: NULL argument", fn);
     a.n = n; a.active = active; a.out = out;
     for (int c = 0; c < 3; ++c) a.d[c] = d[c];
-    hf_launch_envmap(5, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return light_launch(hf_launch_envmap, 5, a, stream);
 }
 
 extern "C" int hf_envmap_eval_adjoint(size_t n, const float *const d[3], const uint8_t *active, uint32_t W, uint32_t H,
                                       const float rot[9], const float *grad_out, float *grad_data, hf_stream_t stream) {
     const char *fn = "hf_envmap_eval_adjoint";
-    hf_envmap_args a;
+    hf_envmap_args a = {};
     const int rc = envmap_map(fn, W, H, nullptr, false, nullptr, false, rot, a); // (the map is linear: its values are not read)
     if (rc != HF_OK) return rc;
     if (!grad_data) return fail(HF_EINVAL, "%s: grad_data is NULL", fn);
     if (!all3(d) || !grad_out) return fail(HF_EINVAL, "%s: NULL argument", fn);
     a.n = n; a.active = active; a.gout = grad_out; a.gdata = grad_data;
     for (int c = 0; c < 3; ++c) a.d[c] = d[c];
-    hf_launch_envmap(6, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return light_launch(hf_launch_envmap, 6, a, stream);
 }
 
 extern "C" int hf_envmap_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
@@ -1315,14 +1334,10 @@ extern "C" int hf_envmap_rays(size_t n, const float *const p[3], const float *co
     const char *fn = "hf_envmap_rays";
     hf_envmap_args a;
     if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
-    const int rc = envmap_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, W, H, data, table, rot, 1.f, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    a.k = k; a.out_maxt = out_maxt; a.out_weight = out_weight;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
-    hf_launch_envmap(3, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    int rc = envmap_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, W, H, data, table, rot, 1.f, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
+    a.out_weight = out_weight;
+    return light_launch(hf_launch_envmap, 3, a, stream);
 }
 
 extern "C" int hf_envmap_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
@@ -1334,15 +1349,11 @@ extern "C" int hf_envmap_lighting(const hf_field_t *hf, size_t n, uint32_t spp, 
     hf_envmap_args a;
     if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
     int rc = envmap_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, W, H, data, table, rot, albedo, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (rc != HF_OK || (rc = light_forward_out(fn, p, nrm, image, a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.image = image; a.vis_bits = vis_bits;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
-    hf_launch_envmap(0, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    a.f = hf->dev; a.vis_bits = vis_bits;
+    return light_launch(hf_launch_envmap, 0, a, stream);
 }
 
 extern "C" int hf_envmap_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
@@ -1358,9 +1369,7 @@ extern "C" int hf_envmap_lighting_adjoint(size_t n, uint32_t spp, const float *c
     if (!vis_bits || !grad_image || !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL argument", fn);
     a.vis_bits = const_cast<uint32_t *>(vis_bits); a.gimg = grad_image; a.gw = grad_weight; a.gdata = grad_data;
     for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n[c];
-    hf_launch_envmap(1, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return light_launch(hf_launch_envmap, 1, a, stream);
 }
 
 extern "C" int hf_envmap_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
@@ -1371,33 +1380,25 @@ extern "C" int hf_envmap_lighting_tangent(size_t n, uint32_t spp, const float *c
                                           float *dimage, hf_stream_t stream) {
     const char *fn = "hf_envmap_lighting_tangent";
     hf_envmap_args a;
-    const int rc = envmap_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, W, H, data, table, rot, albedo, a);
-    if (rc != HF_OK) return rc;
-    if (!vis_bits || !dimage) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
-    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.image = dimage; a.dw = dweight; a.ddata = ddata;
-    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
-    hf_launch_envmap(2, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    int rc = envmap_args(fn, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, W, H, data, table, rot, albedo, a);
+    if (rc != HF_OK || (rc = light_tangent_io(fn, !vis_bits, dsh_n, dweight, dimage, a))) return rc;
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.ddata = ddata;
+    return light_launch(hf_launch_envmap, 2, a, stream);
 }
 
 // ---- bounce lighting: one diffuse interreflection, both rays traced inside the lighting kernel ----
-// What the four hf_bounce_* entries share: the checks (all of them before anything touches a device) and the argument
-// block.  hf_bounce_rays passes spp 1, num_rays k + 1, albedo 1 and either no light or its one direction.
+// What the four hf_bounce_* entries share.  hf_bounce_rays passes spp 1, num_rays k + 1, albedo 1 and either no light or its one direction.
 static int bounce_args(const char *who, const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
                        const float *const d[3], const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
                        const uint32_t *ray_id, uint32_t n_lights, const hf_dir_light_t *lights, float albedo,
                        hf_bounce_args &a) {
     if (!hf) return fail(HF_EINVAL, "%s: NULL handle", who);
-    if (!all3(sh_n) || !all3(d) || !t || !lights) return fail(HF_EINVAL, "%s: NULL argument", who);
-    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
-    if (num_rays == 0 || num_rays > 32) return fail(HF_EINVAL, "%s: 1..32 bounce directions per sample (got %u)", who, num_rays);
-    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    a = {};
+    const int rc = light_args(who, "bounce directions", n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, !lights, a);
+    if (rc != HF_OK) return rc;
     if (n_lights == 0 || n_lights > HF_MAX_LIGHTS)
         return fail(HF_EINVAL, "%s: 1..%d lights supported (got %u)", who, HF_MAX_LIGHTS, n_lights);
     if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
-    a = {};
     for (uint32_t l = 0; l < n_lights; ++l) {
         if (!isfinite(lights[l].irradiance) || !isfinite(lights[l].to_light[0]) || !isfinite(lights[l].to_light[1]) ||
             !isfinite(lights[l].to_light[2]))
@@ -1405,10 +1406,8 @@ static int bounce_args(const char *who, const hf_field_t *hf, size_t n, uint32_t
         for (int c = 0; c < 3; ++c) a.l[l][c] = lights[l].to_light[c];
         a.w[l] = (albedo * 0.31830988618379067154f) * lights[l].irradiance; // dr::InvPi
     }
-    a.n = n; a.spp = spp; a.num_rays = num_rays; a.seed = seed; a.ray_id = ray_id; a.t = t; a.weight = weight;
     a.n_lights = n_lights;
     a.scale = albedo / (float) num_rays; // the BSDF weight (cosine and pdf cancel), averaged over num_rays
-    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
     return HF_OK;
 }
 // the record of the three lighting entries (need: the adjoint and the tangent read it)
@@ -1431,15 +1430,11 @@ extern "C" int hf_bounce_rays(const hf_field_t *hf, size_t n, const float *const
     hf_dir_light_t one = { { 0.f, 0.f, 1.f }, 1.f };
     if (to_light) for (int c = 0; c < 3; ++c) one.to_light[c] = to_light[c];
     int rc = bounce_args(fn, hf, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, 1, &one, 1.f, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.k = k; a.shadow = to_light ? 1 : 0; a.out_maxt = out_maxt;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
-    hf_launch_bounce(3, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    a.f = hf->dev; a.shadow = to_light ? 1 : 0;
+    return light_launch(hf_launch_bounce, 3, a, stream);
 }
 
 extern "C" int hf_bounce_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
@@ -1451,16 +1446,12 @@ extern "C" int hf_bounce_lighting(const hf_field_t *hf, size_t n, uint32_t spp, 
     const char *fn = "hf_bounce_lighting";
     hf_bounce_args a;
     int rc = bounce_args(fn, hf, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, n_lights, lights, albedo, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (rc != HF_OK || (rc = light_forward_out(fn, p, nrm, image, a))) return rc;
     if ((rc = bounce_record(fn, n, hit_prim, lit_bits, sample_stride, false, a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.image = image;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
-    hf_launch_bounce(0, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    a.f = hf->dev;
+    return light_launch(hf_launch_bounce, 0, a, stream);
 }
 
 extern "C" int hf_bounce_lighting_adjoint(const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
@@ -1482,9 +1473,7 @@ extern "C" int hf_bounce_lighting_adjoint(const hf_field_t *hf, size_t n, uint32
     if ((rc = check_device(fn, hf))) return rc;
     a.f = hf->dev; a.gimg = grad_image; a.gw = grad_weight; a.gh = grad_heights;
     for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
-    hf_launch_bounce(1, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    return light_launch(hf_launch_bounce, 1, a, stream);
 }
 
 extern "C" int hf_bounce_lighting_tangent(const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],
@@ -1497,17 +1486,12 @@ extern "C" int hf_bounce_lighting_tangent(const hf_field_t *hf, size_t n, uint32
     const char *fn = "hf_bounce_lighting_tangent";
     hf_bounce_args a;
     int rc = bounce_args(fn, hf, n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, n_lights, lights, albedo, a);
-    if (rc != HF_OK) return rc;
-    if (!dimage) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
+    if (rc != HF_OK || (rc = light_tangent_io(fn, false, dsh_n, dweight, dimage, a))) return rc;
     if ((rc = bounce_record(fn, n, hit_prim, lit_bits, sample_stride, true, a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.image = dimage; a.dw = dweight; a.dh = dheights;
-    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
-    hf_launch_bounce(2, a, (hipStream_t) stream);
-    HF_HIP(hipGetLastError());
-    return HF_OK;
+    a.f = hf->dev; a.dh = dheights;
+    return light_launch(hf_launch_bounce, 2, a, stream);
 }
 
 // ---- Gaussian reconstruction filter (film) ------------------------------------------------------

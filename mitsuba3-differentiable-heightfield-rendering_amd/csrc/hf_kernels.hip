@@ -3650,6 +3650,114 @@ void hf_launch_film_motion(int mode, const hf_film_motion_args &a, hipStream_t s
     else                hipLaunchKernelGGL(hf_film_motion_kernel<2>, grid, block, 0, stream, a);
 }
 
+// ---------------------------------------------------------------------------------
+// Lighting rows, shared: what the sky, bounce and envmap sections below have in common -- the per-lane walk of a shadow
+// or bounce ray, the f64 sine / cosine of their shading sums, the first reads of a derivative or rays kernel, the ray
+// store, the tangent shell and the launch.  Only text that is the same for every row belongs here; nothing in this block
+// asks which row calls it (A: the row's argument struct, its common fields under their common names).
+// ---------------------------------------------------------------------------------
+// the masks of hf_direct_kernel: a hit seen from the front (diffuse.cpp:137)
+__device__ __forceinline__ bool sky_eligible(float t, v3 sn, v3 d) { return (t != __builtin_inff()) && (-dot3(sn, d) > 0.f); }
+
+// one lane's walk from the root (closest hit, or ANY hit), as an incoherent wave of hf_trace_kernel takes it.  `f`: the
+// kernel's by-value argument; what setup_ray needs of it is read from the kernarg segment (`kf`) again
+template <bool ANY>
+__device__ __forceinline__ void light_walk(const __attribute__((address_space(4))) hf_dev_field *kf, const hf_dev_field &f, v3 o,
+                                           v3 w, bool traced, hf_hit &best) {
+    best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
+    hf_ray_state rs = {}; // fully defined on every path
+    bool alive;
+    {
+        const hf_dev_field f0 = load_field(kf);
+        alive = traced && setup_ray(f0, f0.mip[1], o, w, __builtin_inff(), rs);
+    }
+    if (alive) {
+        float thi = rs.thi;
+        hf_src_global src;
+        src.mip = f.mip; src.shear = f.shear; src.h = f.h; src.top = f.top; src.W = f.W;
+        const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
+        (void) walk_subtree<ANY>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
+    }
+}
+
+// sin a, cos a in double for |a| <= pi / 4: two Taylor sums whose first dropped terms are 7e-12 and 4e-13 (a dozen fmas
+// and few registers: the library's sincospi, correct to the last bit of a double, costs the forward kernel 25 spilled
+// registers)
+struct hf_sincos { double s, c; };
+__device__ __forceinline__ hf_sincos light_sincos_f64(double a) {
+    const double a2 = a * a;
+    double ps = -1.0 / 39916800.0, pc = 1.0 / 479001600.0;
+    ps = fma(ps, a2, 1.0 / 362880.0); ps = fma(ps, a2, -1.0 / 5040.0); ps = fma(ps, a2, 1.0 / 120.0);
+    ps = fma(ps, a2, -1.0 / 6.0); ps = fma(ps, a2, 1.0); ps *= a;
+    pc = fma(pc, a2, -1.0 / 3628800.0); pc = fma(pc, a2, 1.0 / 40320.0); pc = fma(pc, a2, -1.0 / 720.0);
+    pc = fma(pc, a2, 1.0 / 24.0); pc = fma(pc, a2, -0.5); pc = fma(pc, a2, 1.0);
+    return hf_sincos{ ps, pc };
+}
+// sin(pi x), cos(pi x) in double for x in [0, 4): the quadrant q = round(2 x) is taken off exactly, |pi t| <= pi / 4 is
+// left to light_sincos_f64; no call
+__device__ __forceinline__ void env_sincospi_f64(double x, double &sn, double &cs) {
+    const double q = rint(2.0 * x), t = x - 0.5 * q;
+    const auto [ps, pc] = light_sincos_f64(3.141592653589793 * t);
+    const int qi = (int) q & 3;
+    sn = qi == 0 ? ps : qi == 1 ? pc : qi == 2 ? -ps : -pc;
+    cs = qi == 0 ? pc : qi == 1 ? -ps : qi == 2 ? -pc : ps;
+}
+
+// what a derivative or rays kernel reads of sample i first: the shading normal, and whether the sample is shaded at all
+// (false: a miss, or seen from behind); light_id: its id in the sample streams
+template <class A>
+__device__ __forceinline__ bool light_sample(const A &a, size_t i, v3 &sn) {
+    sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]);
+    const v3 d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    return sky_eligible(a.t[i], sn, d);
+}
+template <class A>
+__device__ __forceinline__ uint32_t light_id(const A &a, size_t i) { return a.ray_id ? a.ray_id[i] : (uint32_t) i; }
+// a materialised ray; maxt = -1: the fused kernel does not trace it
+template <class A>
+__device__ __forceinline__ void light_store_ray(const A &a, size_t i, v3 o, v3 d, bool traced) {
+    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
+    a.out_d[0][i] = d.x; a.out_d[1][i] = d.y; a.out_d[2][i] = d.z;
+    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+}
+
+// The tangent image of a row with one channel, VALUE(a, i) the tangent of sample i's value.  PIXEL = false: one lane per
+// sample and the primal's film (spp a power of two <= 64: its shuffle tree, one store per pixel); PIXEL = true (any
+// other spp): one lane per pixel adds its samples in order -- no atomics either way
+template <bool PIXEL, class A, float (*VALUE)(const A &, size_t)>
+__device__ __forceinline__ void light_tangent_image(const A &a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    if (PIXEL) {
+        if (i >= a.n / spp) return;
+        float c = 0.f;
+        for (uint32_t s = 0; s < spp; ++s) c += VALUE(a, i * spp + s);
+        a.image[i] = c * (1.0f / (float) spp);
+    } else {
+        const bool in = i < a.n;
+        const float c = VALUE(a, in ? i : a.n - 1);
+        film_pixel(a.image, in ? c : 0.f, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
+    }
+}
+
+// film_pixel reduces the samples of a pixel in a shuffle tree and stores once; any other spp takes its atomic paths,
+// which want a zeroed image
+static bool sky_tree_film(uint32_t spp) { return (spp & (spp - 1u)) == 0u && spp <= 64u; }
+
+// modes 0 to 3 of a row: forward (`channels` film planes), adjoint, tangent, rays
+template <class A>
+static void launch_light(int mode, const A &a, uint32_t channels, hipStream_t stream, void (*forward)(A), void (*adjoint)(A),
+                         void (*tangent)(A), void (*tangent_pixel)(A), void (*rays)(A)) {
+    if (a.n == 0) return;
+    const bool tree = sky_tree_film(a.spp);
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    if (mode == 0 && !tree) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp) * channels, stream);
+    if (mode == 2 && !tree)
+        hipLaunchKernelGGL(tangent_pixel, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(mode == 0 ? forward : mode == 1 ? adjoint : mode == 2 ? tangent : rays, grid, block, 0, stream, a);
+}
+
 // the rows of a [3, n] argument; NULL: three NULL rows
 static hf_f3ptr f3ptr(const float *const r[3]) { return r ? hf_f3ptr{ { r[0], r[1], r[2] } } : hf_f3ptr{}; }
 static hf_f3out f3out(float *const r[3]) { return r ? hf_f3out{ { r[0], r[1], r[2] } } : hf_f3out{}; }
@@ -3657,8 +3765,7 @@ static hf_f3out f3out(float *const r[3]) { return r ? hf_f3out{ { r[0], r[1], r[
 void hf_launch_direct(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
                       const float *const p[3], const hf_lights_dev &lights, float *image, hipStream_t stream) {
     if (n == 0) return;
-    const bool pow2 = (spp & (spp - 1u)) == 0u;
-    if (!pow2 || spp > 64u) (void) hipMemsetAsync(image, 0, sizeof(float) * lights.n * (n / spp), stream); // atomic paths
+    if (!sky_tree_film(spp)) (void) hipMemsetAsync(image, 0, sizeof(float) * lights.n * (n / spp), stream); // atomic paths
     const dim3 grid((unsigned) ((n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
     hipLaunchKernelGGL(p ? hf_direct_kernel<true> : hf_direct_kernel<false>, grid, block, 0, stream, n, spp, f3ptr(sh_n),
                        f3ptr(d), t, f3ptr(p), lights, image);
@@ -3679,8 +3786,7 @@ void hf_launch_direct_tangent(size_t n, uint32_t spp, const float *const sh_n[3]
                               const float *const dsh_n[3], const float *const dp[3], const float *dweight, float *dimage,
                               hipStream_t stream) {
     if (n == 0) return;
-    const bool pow2 = (spp & (spp - 1u)) == 0u;
-    if (!pow2 || spp > 64u) (void) hipMemsetAsync(dimage, 0, sizeof(float) * lights.n * (n / spp), stream); // atomic paths
+    if (!sky_tree_film(spp)) (void) hipMemsetAsync(dimage, 0, sizeof(float) * lights.n * (n / spp), stream); // atomic paths
     const dim3 grid((unsigned) ((n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
     hipLaunchKernelGGL(p ? hf_direct_tangent_kernel<true> : hf_direct_tangent_kernel<false>, grid, block, 0, stream, n, spp,
                        f3ptr(sh_n), f3ptr(d), t, f3ptr(p), lights, f3ptr(dsh_n), f3ptr(dp), dweight, dimage);
@@ -3717,8 +3823,6 @@ __device__ __forceinline__ float sky_offset(v3 p) {
 __device__ __forceinline__ v3 sky_origin(v3 p, v3 gn, float mag, v3 w) {
     return fma3(gn, dot3(gn, w) < 0.f ? -mag : mag, p);
 }
-// the masks of hf_direct_kernel: a hit seen from the front (diffuse.cpp:137)
-__device__ __forceinline__ bool sky_eligible(float t, v3 sn, v3 d) { return (t != __builtin_inff()) && (-dot3(sn, d) > 0.f); }
 
 // The same direction in double, for the SHADING sums (the cosines of the forward, the sums of directions of the
 // derivative kernels): a float direction is 1e-7 off, which is the whole error of a grazing cosine and of a gradient
@@ -3730,16 +3834,10 @@ __device__ __forceinline__ hf_d3 sky_dir_f64(uint32_t seed, uint32_t k, uint32_t
     sky_sample(seed, k, id, sx, sy);
     const double z = 1.0 - 2.0 * (double) sy;
     const double r = sqrt(fmax(1.0 - z * z, 0.0));
-    // sin / cos of pi x, x = 2 sx in [0, 2): the quadrant q = round(2 x) is taken off exactly, |pi t| <= pi / 4 is left
-    // to two Taylor sums whose first dropped terms are 7e-12 and 4e-13 (a dozen fmas and few registers: the library's
-    // sincospi, correct to the last bit of a double, costs the forward kernel 25 spilled registers)
+    // env_sincospi_f64(2 sx), with the quadrant selected by value here: called through its references the selects are
+    // compiled differently, and hf_sky_kernel grows by five instructions (by value there, hf_envmap_kernel changes)
     const double x = 2.0 * (double) sx, q = rint(2.0 * x), t = x - 0.5 * q;
-    const double a = 3.141592653589793 * t, a2 = a * a;
-    double ps = -1.0 / 39916800.0, pc = 1.0 / 479001600.0;
-    ps = fma(ps, a2, 1.0 / 362880.0); ps = fma(ps, a2, -1.0 / 5040.0); ps = fma(ps, a2, 1.0 / 120.0);
-    ps = fma(ps, a2, -1.0 / 6.0); ps = fma(ps, a2, 1.0); ps *= a;
-    pc = fma(pc, a2, -1.0 / 3628800.0); pc = fma(pc, a2, 1.0 / 40320.0); pc = fma(pc, a2, -1.0 / 720.0);
-    pc = fma(pc, a2, 1.0 / 24.0); pc = fma(pc, a2, -0.5); pc = fma(pc, a2, 1.0);
+    const auto [ps, pc] = light_sincos_f64(3.141592653589793 * t);
     const int qi = (int) q & 3;
     const double sn = qi == 0 ? ps : qi == 1 ? pc : qi == 2 ? -ps : -pc;
     const double cs = qi == 0 ? pc : qi == 1 ? -ps : qi == 2 ? -pc : ps;
@@ -3788,20 +3886,7 @@ __global__ __launch_bounds__(HF_BLOCK, HF_SKY_WAVES) void hf_sky_kernel(hf_sky_a
             const v3 w = sky_dir(ka->seed, k, idr);
             const bool traced = elig && dot3(sn, w) > 0.f;
             hf_hit best;
-            best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
-            hf_ray_state rs = {}; // fully defined on every path
-            bool alive;
-            {
-                const hf_dev_field f0 = load_field(&ka->f);
-                alive = traced && setup_ray(f0, f0.mip[1], sky_origin(p, gn, mag, w), w, __builtin_inff(), rs);
-            }
-            if (alive) { // the per-lane walk from the root, as an incoherent wave of hf_trace_kernel takes it
-                float thi = rs.thi;
-                hf_src_global src;
-                src.mip = f.mip; src.shear = f.shear; src.h = f.h; src.top = f.top; src.W = f.W;
-                const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
-                (void) walk_subtree<true>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
-            }
+            light_walk<true>(&ka->f, f, sky_origin(p, gn, mag, w), w, traced, best);
             if (traced && !best.hit) { bits |= 1u << k; acc += co; }
             if (k + 1u >= ka->num_rays) break;
         }
@@ -3825,14 +3910,11 @@ __global__ __launch_bounds__(HF_BLOCK, HF_SKY_WAVES) void hf_sky_kernel(hf_sky_a
 __global__ __launch_bounds__(HF_BLOCK) void hf_sky_rays_kernel(hf_sky_args a) {
     const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
     if (i >= a.n) return;
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    v3 sn;
+    const bool elig = light_sample(a, i, sn);
     const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
-    const v3 w = sky_dir(a.seed, a.k, a.ray_id ? a.ray_id[i] : (uint32_t) i);
-    const bool traced = sky_eligible(a.t[i], sn, d) && dot3(sn, w) > 0.f;
-    const v3 o = sky_origin(p, gn, sky_offset(p), w);
-    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
-    a.out_d[0][i] = w.x; a.out_d[1][i] = w.y; a.out_d[2][i] = w.z;
-    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+    const v3 w = sky_dir(a.seed, a.k, light_id(a, i));
+    light_store_ray(a, i, sky_origin(p, gn, sky_offset(p), w), w, elig && dot3(sn, w) > 0.f);
 }
 
 // Reverse mode of hf_sky_kernel with respect to sh_n and weight: nothing is traced, the directions are drawn again and
@@ -3840,11 +3922,10 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sky_rays_kernel(hf_sky_args a) {
 __global__ __launch_bounds__(HF_BLOCK) void hf_sky_adjoint_kernel(hf_sky_args a) {
     const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
     if (i >= a.n) return;
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
-    v3 g = mk3(0.f, 0.f, 0.f);
+    v3 sn, g = mk3(0.f, 0.f, 0.f);
     float gw = 0.f;
-    if (sky_eligible(a.t[i], sn, d)) {
-        const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    if (light_sample(a, i, sn)) {
+        const uint32_t bits = a.vis_bits[i], id = light_id(a, i);
         double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0;
         for (uint32_t k = 0; k < a.num_rays; ++k) {
             if ((bits >> k) & 1u) {
@@ -3863,9 +3944,9 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sky_adjoint_kernel(hf_sky_args a)
 
 // forward mode: the tangent of sample i's value for tangents dn of sh_n and dw of weight (NULL: zero)
 __device__ __forceinline__ float sky_tangent_value(const hf_sky_args &a, size_t i) {
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
-    if (!sky_eligible(a.t[i], sn, d)) return 0.f;
-    const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    v3 sn;
+    if (!light_sample(a, i, sn)) return 0.f;
+    const uint32_t bits = a.vis_bits[i], id = light_id(a, i);
     const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
     double sd = 0.0, sc = 0.0;
     for (uint32_t k = 0; k < a.num_rays; ++k) {
@@ -3877,40 +3958,14 @@ __device__ __forceinline__ float sky_tangent_value(const hf_sky_args &a, size_t 
     }
     return (float) ((double) a.scale * ((double) (a.weight ? a.weight[i] : 1.f) * sd + (double) (a.dw ? a.dw[i] : 0.f) * sc));
 }
-// PIXEL = false: one lane per sample and the primal's film (spp a power of two <= 64: its shuffle tree, one store per
-// pixel); PIXEL = true (any other spp): one lane per pixel adds its samples in order -- no atomics either way
 template <bool PIXEL>
 __global__ __launch_bounds__(HF_BLOCK) void hf_sky_tangent_kernel(hf_sky_args a) {
-    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
-    const uint32_t spp = a.spp;
-    if (PIXEL) {
-        if (i >= a.n / spp) return;
-        float c = 0.f;
-        for (uint32_t s = 0; s < spp; ++s) c += sky_tangent_value(a, i * spp + s);
-        a.image[i] = c * (1.0f / (float) spp);
-    } else {
-        const bool in = i < a.n;
-        const float c = sky_tangent_value(a, in ? i : a.n - 1);
-        film_pixel(a.image, in ? c : 0.f, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
-    }
+    light_tangent_image<PIXEL, hf_sky_args, sky_tangent_value>(a);
 }
 
-static bool sky_tree_film(uint32_t spp) { return (spp & (spp - 1u)) == 0u && spp <= 64u; }
-
 void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream) {
-    if (a.n == 0) return;
-    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
-    if (mode == 0) {
-        if (!sky_tree_film(a.spp)) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths of film_pixel
-        hipLaunchKernelGGL(hf_sky_kernel, grid, block, 0, stream, a);
-    } else if (mode == 1) {
-        hipLaunchKernelGGL(hf_sky_adjoint_kernel, grid, block, 0, stream, a);
-    } else if (mode == 2) {
-        if (sky_tree_film(a.spp)) hipLaunchKernelGGL(hf_sky_tangent_kernel<false>, grid, block, 0, stream, a);
-        else hipLaunchKernelGGL(hf_sky_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
-    } else {
-        hipLaunchKernelGGL(hf_sky_rays_kernel, grid, block, 0, stream, a);
-    }
+    launch_light(mode, a, 1u, stream, hf_sky_kernel, hf_sky_adjoint_kernel, hf_sky_tangent_kernel<false>,
+                 hf_sky_tangent_kernel<true>, hf_sky_rays_kernel);
 }
 
 // ---------------------------------------------------------------------------------
@@ -3951,12 +4006,7 @@ __device__ __forceinline__ hf_d3 bounce_dir_f64(v3 sn, uint32_t seed, uint32_t k
     const double x = 2.0 * (double) sx - 1.0, y = 2.0 * (double) sy - 1.0;
     const bool q13 = fabs(x) < fabs(y);
     const double r = q13 ? y : x, rp = q13 ? x : y;
-    const double a = (x == 0.0 && y == 0.0) ? 0.0 : 0.7853981633974483 * rp / r, a2 = a * a; // |a| <= pi / 4: sky_dir_f64's sums
-    double ps = -1.0 / 39916800.0, pc = 1.0 / 479001600.0;
-    ps = fma(ps, a2, 1.0 / 362880.0); ps = fma(ps, a2, -1.0 / 5040.0); ps = fma(ps, a2, 1.0 / 120.0);
-    ps = fma(ps, a2, -1.0 / 6.0); ps = fma(ps, a2, 1.0); ps *= a;
-    pc = fma(pc, a2, -1.0 / 3628800.0); pc = fma(pc, a2, 1.0 / 40320.0); pc = fma(pc, a2, -1.0 / 720.0);
-    pc = fma(pc, a2, 1.0 / 24.0); pc = fma(pc, a2, -0.5); pc = fma(pc, a2, 1.0);
+    const auto [ps, pc] = light_sincos_f64((x == 0.0 && y == 0.0) ? 0.0 : 0.7853981633974483 * rp / r); // (|a| <= pi / 4)
     const double px = r * (q13 ? ps : pc), py = r * (q13 ? pc : ps);
     z = sqrt((1.0 - fabs(r)) * (1.0 + fabs(r))); // (as bounce_local)
     // coordinate_system (vector.h:116-136) in double
@@ -3968,25 +4018,6 @@ __device__ __forceinline__ hf_d3 bounce_dir_f64(v3 sn, uint32_t seed, uint32_t k
 
 typedef const __attribute__((address_space(4))) hf_bounce_args *hf_bounce_kargs;
 
-// one lane's walk from the root (closest hit, or ANY hit), as an incoherent wave of hf_trace_kernel takes it.  `f`: the
-// kernel's by-value argument; what setup_ray needs of it is read from the kernarg segment again
-template <bool ANY>
-__device__ __forceinline__ void bounce_walk(hf_bounce_kargs ka, const hf_dev_field &f, v3 o, v3 w, bool traced, hf_hit &best) {
-    best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
-    hf_ray_state rs = {}; // fully defined on every path
-    bool alive;
-    {
-        const hf_dev_field f0 = load_field(&ka->f);
-        alive = traced && setup_ray(f0, f0.mip[1], o, w, __builtin_inff(), rs);
-    }
-    if (alive) {
-        float thi = rs.thi;
-        hf_src_global src;
-        src.mip = f.mip; src.shear = f.shear; src.h = f.h; src.top = f.top; src.W = f.W;
-        const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
-        (void) walk_subtree<ANY>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
-    }
-}
 // the second vertex: p and the face normal of compute_si_to for the hit (prim, b1, b2), its arithmetic
 __device__ __forceinline__ void bounce_vertex(const hf_dev_field &f, uint32_t prim, float b1, float b2, v3 &q, v3 &nq) {
     v3 P[3];
@@ -4038,7 +4069,7 @@ __global__ __launch_bounds__(HF_BLOCK, HF_BOUNCE_WAVES) void hf_bounce_kernel(hf
             hf_hit best;
             {
                 const bool traced = elig && wo.z > 0.f;
-                bounce_walk<false>(ka, f, sky_origin(p, gn, sky_offset(p), w), w, traced, best);
+                light_walk<false>(&ka->f, f, sky_origin(p, gn, sky_offset(p), w), w, traced, best);
                 hit = traced && best.hit;
             }
             if (__ballot(hit) != 0ull) { // (wave-uniform)
@@ -4056,7 +4087,7 @@ __global__ __launch_bounds__(HF_BLOCK, HF_BOUNCE_WAVES) void hf_bounce_kernel(hf
                         const v3 ll = mk3(ka->l[l][0], ka->l[l][1], ka->l[l][2]);
                         const bool ts = front && dot3(nq, ll) > 0.f;
                         hf_hit sh;
-                        bounce_walk<true>(ka, f, sky_origin(q, nq, sky_offset(q), ll), ll, ts, sh);
+                        light_walk<true>(&ka->f, f, sky_origin(q, nq, sky_offset(q), ll), ll, ts, sh);
                         if (ts && !sh.hit) {
                             bits |= 1u << l;
                             // the cosine from the float normal in double, rounded once (the float dot3 decides the mask only)
@@ -4099,16 +4130,17 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_bounce_rays_kernel(hf_bounce_args
     const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
     const bool in = i64 < a.n;
     const size_t i = in ? i64 : a.n - 1;
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    v3 sn;
+    const bool elig = light_sample(a, i, sn);
     const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
-    const v3 wo = bounce_local(a.seed, a.k, a.ray_id ? a.ray_id[i] : (uint32_t) i);
+    const v3 wo = bounce_local(a.seed, a.k, light_id(a, i));
     const v3 w = bounce_world(sn, wo);
-    bool traced = in && sky_eligible(a.t[i], sn, d) && wo.z > 0.f;
+    bool traced = in && elig && wo.z > 0.f;
     v3 o = sky_origin(p, gn, sky_offset(p), w), dir = w;
     if (a.shadow) {
         hf_bounce_kargs ka = (hf_bounce_kargs) __builtin_amdgcn_kernarg_segment_ptr();
         hf_hit best;
-        bounce_walk<false>(ka, a.f, o, w, traced, best);
+        light_walk<false>(&ka->f, a.f, o, w, traced, best);
         const bool hit = traced && best.hit;
         v3 q, nq;
         bounce_vertex(a.f, hit ? best.prim : 0u, hit ? best.u : 0.f, hit ? best.v : 0.f, q, nq);
@@ -4116,10 +4148,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_bounce_rays_kernel(hf_bounce_args
         traced = hit && (-dot3(nq, w) > 0.f) && dot3(nq, dir) > 0.f;
         o = hit ? sky_origin(q, nq, sky_offset(q), dir) : mk3(0.f, 0.f, 0.f);
     }
-    if (!in) return;
-    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
-    a.out_d[0][i] = dir.x; a.out_d[1][i] = dir.y; a.out_d[2][i] = dir.z;
-    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+    if (in) light_store_ray(a, i, o, dir, traced);
 }
 
 // What the derivative kernels read of one record: the triangle of hit_prim (edges, unit normal before flip_normals and
@@ -4171,11 +4200,11 @@ __device__ __forceinline__ hf_d3 bounce_dnq_f64(const hf_dev_field &f, const hf_
 __global__ __launch_bounds__(HF_BLOCK) void hf_bounce_adjoint_kernel(hf_bounce_args a) {
     const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
     if (i >= a.n) return;
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    v3 sn;
     double sx = 0.0, sy = 0.0, sz = 0.0, sg = 0.0;
     const float wgt = a.weight ? a.weight[i] : 1.f;
-    if (sky_eligible(a.t[i], sn, d)) {
-        const uint32_t id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    if (light_sample(a, i, sn)) {
+        const uint32_t id = light_id(a, i);
         const size_t npix = a.n / a.spp, pix = i / a.spp;
         const float inv_spp = 1.0f / (float) a.spp;
         const v3 ez = height_axis(a.f);
@@ -4219,9 +4248,9 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_bounce_adjoint_kernel(hf_bounce_a
 // forward mode: the tangents of sample i's values under every light, for tangents dn of sh_n, dw of weight and dh of
 // the heights (NULL: zero), ADDED to the lane's column acc[l * HF_BLOCK] (LDS: the light index stays a scalar loop)
 __device__ __forceinline__ void bounce_tangent_values(const hf_bounce_args &a, size_t i, double *acc) {
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
-    if (!sky_eligible(a.t[i], sn, d)) return;
-    const uint32_t id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    v3 sn;
+    if (!light_sample(a, i, sn)) return;
+    const uint32_t id = light_id(a, i);
     const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
     const double wgt = a.weight ? a.weight[i] : 1.f, dw = a.dw ? a.dw[i] : 0.f;
     for (uint32_t k = 0; k < a.num_rays; ++k) {
@@ -4277,19 +4306,8 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_bounce_tangent_kernel(hf_bounce_a
 }
 
 void hf_launch_bounce(int mode, const hf_bounce_args &a, hipStream_t stream) {
-    if (a.n == 0) return;
-    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
-    if (mode == 0) {
-        if (!sky_tree_film(a.spp)) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp) * a.n_lights, stream); // atomic paths of film_pixel
-        hipLaunchKernelGGL(hf_bounce_kernel, grid, block, 0, stream, a);
-    } else if (mode == 1) {
-        hipLaunchKernelGGL(hf_bounce_adjoint_kernel, grid, block, 0, stream, a);
-    } else if (mode == 2) {
-        if (sky_tree_film(a.spp)) hipLaunchKernelGGL(hf_bounce_tangent_kernel<false>, grid, block, 0, stream, a);
-        else hipLaunchKernelGGL(hf_bounce_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
-    } else {
-        hipLaunchKernelGGL(hf_bounce_rays_kernel, grid, block, 0, stream, a);
-    }
+    launch_light(mode, a, a.n_lights, stream, hf_bounce_kernel, hf_bounce_adjoint_kernel, hf_bounce_tangent_kernel<false>,
+                 hf_bounce_tangent_kernel<true>, hf_bounce_rays_kernel);
 }
 
 // ---- warped-area reparameterisation: per-sample kernels (helpers: above hf_adjoint_kernel) ----
@@ -5135,20 +5153,6 @@ void hf_launch_param_tangent(const hf_dev_field &f, size_t n, const float *const
 // the map, traced (any hit, per lane) and reduced in ONE launch: hf_sky_kernel's mapping, with the draw (two binary
 // searches of the caller's table, four texels, the angles and the rotation) in place of the uniform sphere.
 // ---------------------------------------------------------------------------------
-// sin(pi x), cos(pi x) in double for x in [0, 4): sky_dir_f64's quadrant reduction and Taylor sums (first dropped terms
-// 7e-12 and 4e-13), a dozen fmas and no call
-__device__ __forceinline__ void env_sincospi_f64(double x, double &sn, double &cs) {
-    const double q = rint(2.0 * x), t = x - 0.5 * q;
-    const double a = 3.141592653589793 * t, a2 = a * a;
-    double ps = -1.0 / 39916800.0, pc = 1.0 / 479001600.0;
-    ps = fma(ps, a2, 1.0 / 362880.0); ps = fma(ps, a2, -1.0 / 5040.0); ps = fma(ps, a2, 1.0 / 120.0);
-    ps = fma(ps, a2, -1.0 / 6.0); ps = fma(ps, a2, 1.0); ps *= a;
-    pc = fma(pc, a2, -1.0 / 3628800.0); pc = fma(pc, a2, 1.0 / 40320.0); pc = fma(pc, a2, -1.0 / 720.0);
-    pc = fma(pc, a2, 1.0 / 24.0); pc = fma(pc, a2, -0.5); pc = fma(pc, a2, 1.0);
-    const int qi = (int) q & 3;
-    sn = qi == 0 ? ps : qi == 1 ? pc : qi == 2 ? -ps : -pc;
-    cs = qi == 0 ? pc : qi == 1 ? -ps : qi == 2 ? -pc : ps;
-}
 // the solid-angle factor of cell row cy: sin(pi (cy + 1/2) / (H - 1)), evaluated in double and rounded once
 __device__ __forceinline__ float env_row_sin(uint32_t cy, uint32_t H) {
     double sn, cs;
@@ -5369,20 +5373,7 @@ __global__ __launch_bounds__(HF_BLOCK, HF_ENVMAP_WAVES) void hf_envmap_kernel(hf
             const v3 w = env_dir(cx, cy, fx, fy, ka->W, ka->H, ka->rot);
             const bool traced = elig && valid && dot3(sn, w) > 0.f;
             hf_hit best;
-            best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
-            hf_ray_state rs = {}; // fully defined on every path
-            bool alive;
-            {
-                const hf_dev_field f0 = load_field(&ka->f);
-                alive = traced && setup_ray(f0, f0.mip[1], sky_origin(p, gn, mag, w), w, __builtin_inff(), rs);
-            }
-            if (alive) { // the per-lane walk from the root, as in hf_sky_kernel
-                float thi = rs.thi;
-                hf_src_global src;
-                src.mip = f.mip; src.shear = f.shear; src.h = f.h; src.top = f.top; src.W = f.W;
-                const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
-                (void) walk_subtree<true>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
-            }
+            light_walk<true>(&ka->f, f, sky_origin(p, gn, mag, w), w, traced, best);
             if (traced && !best.hit) { bits |= 1u << k; acc += co; }
             if (k + 1u >= ka->num_rays) break;
         }
@@ -5405,17 +5396,14 @@ __global__ __launch_bounds__(HF_BLOCK, HF_ENVMAP_WAVES) void hf_envmap_kernel(hf
 __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_rays_kernel(hf_envmap_args a) {
     const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
     if (i >= a.n) return;
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    v3 sn;
+    const bool elig = light_sample(a, i, sn);
     const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
     float sx, sy;
-    sky_sample(a.seed, a.k, a.ray_id ? a.ray_id[i] : (uint32_t) i, sx, sy);
+    sky_sample(a.seed, a.k, light_id(a, i), sx, sy);
     const hf_env_draw r = env_draw(a.data, a.table, a.W, a.H, sx, sy);
     const v3 w = env_dir(r.cx, r.cy, r.fx, r.fy, a.W, a.H, a.rot);
-    const bool traced = sky_eligible(a.t[i], sn, d) && r.valid && dot3(sn, w) > 0.f;
-    const v3 o = sky_origin(p, gn, sky_offset(p), w);
-    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
-    a.out_d[0][i] = w.x; a.out_d[1][i] = w.y; a.out_d[2][i] = w.z;
-    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+    light_store_ray(a, i, sky_origin(p, gn, sky_offset(p), w), w, elig && r.valid && dot3(sn, w) > 0.f);
     if (a.out_weight) {
         double st;
         (void) env_dir_f64(r.cx, r.cy, r.fx, r.fy, a.W, a.H, a.rot, st);
@@ -5501,11 +5489,10 @@ __device__ __forceinline__ hf_env_shade env_shade(const hf_envmap_args &a, uint3
 __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_adjoint_kernel(hf_envmap_args a) {
     const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
     if (i >= a.n) return;
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
-    v3 g = mk3(0.f, 0.f, 0.f);
+    v3 sn, g = mk3(0.f, 0.f, 0.f);
     float gw = 0.f;
-    if (sky_eligible(a.t[i], sn, d)) {
-        const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    if (light_sample(a, i, sn)) {
+        const uint32_t bits = a.vis_bits[i], id = light_id(a, i);
         const float c = (a.gimg[i / a.spp] * (1.0f / (float) a.spp)) * a.scale;
         const float cw = a.weight ? c * a.weight[i] : c;
         double sx = 0.0, sy = 0.0, sz = 0.0, sc = 0.0;
@@ -5532,9 +5519,9 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_adjoint_kernel(hf_envmap_a
 
 // forward mode: the tangent of sample i's value for tangents dn of sh_n, dw of weight and ddata of the texels (NULL: zero)
 __device__ __forceinline__ float envmap_tangent_value(const hf_envmap_args &a, size_t i) {
-    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
-    if (!sky_eligible(a.t[i], sn, d)) return 0.f;
-    const uint32_t bits = a.vis_bits[i], id = a.ray_id ? a.ray_id[i] : (uint32_t) i;
+    v3 sn;
+    if (!light_sample(a, i, sn)) return 0.f;
+    const uint32_t bits = a.vis_bits[i], id = light_id(a, i);
     const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
     double sd = 0.0, sc = 0.0;
     for (uint32_t k = 0; k < a.num_rays; ++k) {
@@ -5552,42 +5539,19 @@ __device__ __forceinline__ float envmap_tangent_value(const hf_envmap_args &a, s
     }
     return (float) ((double) a.scale * ((double) (a.weight ? a.weight[i] : 1.f) * sd + (double) (a.dw ? a.dw[i] : 0.f) * sc));
 }
-// PIXEL as in hf_sky_tangent_kernel: no atomics for any spp
 template <bool PIXEL>
 __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_tangent_kernel(hf_envmap_args a) {
-    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
-    const uint32_t spp = a.spp;
-    if (PIXEL) {
-        if (i >= a.n / spp) return;
-        float c = 0.f;
-        for (uint32_t s = 0; s < spp; ++s) c += envmap_tangent_value(a, i * spp + s);
-        a.image[i] = c * (1.0f / (float) spp);
-    } else {
-        const bool in = i < a.n;
-        const float c = envmap_tangent_value(a, in ? i : a.n - 1);
-        film_pixel(a.image, in ? c : 0.f, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
-    }
+    light_tangent_image<PIXEL, hf_envmap_args, envmap_tangent_value>(a);
 }
 
 void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream) {
-    if (a.n == 0) return;
-    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
-    if (mode == 0) {
-        if (!sky_tree_film(a.spp)) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths of film_pixel
-        hipLaunchKernelGGL(hf_envmap_kernel, grid, block, 0, stream, a);
-    } else if (mode == 1) {
-        hipLaunchKernelGGL(hf_envmap_adjoint_kernel, grid, block, 0, stream, a);
-    } else if (mode == 2) {
-        if (sky_tree_film(a.spp)) hipLaunchKernelGGL(hf_envmap_tangent_kernel<false>, grid, block, 0, stream, a);
-        else hipLaunchKernelGGL(hf_envmap_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
-    } else if (mode == 3) {
-        hipLaunchKernelGGL(hf_envmap_rays_kernel, grid, block, 0, stream, a);
-    } else if (mode == 4) {
-        hipLaunchKernelGGL(hf_envmap_sample_kernel, grid, block, 0, stream, a);
-    } else if (mode == 5) {
-        hipLaunchKernelGGL(hf_envmap_eval_kernel<false>, grid, block, 0, stream, a);
-    } else {
-        hipLaunchKernelGGL(hf_envmap_eval_kernel<true>, grid, block, 0, stream, a);
+    if (mode <= 3) {
+        launch_light(mode, a, 1u, stream, hf_envmap_kernel, hf_envmap_adjoint_kernel, hf_envmap_tangent_kernel<false>,
+                     hf_envmap_tangent_kernel<true>, hf_envmap_rays_kernel);
+    } else if (a.n != 0) {
+        const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+        hipLaunchKernelGGL(mode == 4 ? hf_envmap_sample_kernel : mode == 5 ? hf_envmap_eval_kernel<false> : hf_envmap_eval_kernel<true>,
+                           grid, block, 0, stream, a);
     }
 }
 

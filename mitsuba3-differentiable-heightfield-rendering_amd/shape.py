@@ -1302,17 +1302,45 @@ class Adam:
         self.shape.mark_dirty()
 
 
+# ---- what the lighting Functions (direct, sky, envmap, bounce) marshal alike -------------------------------------------
+def _detached_f32(x):
+    """a wavefront row (sh_n, p, n, d, t, weight of a lighting row) as a detached contiguous float32 tensor; None stays None"""
+    return x.detach().to(dtype=torch.float32).contiguous() if x is not None else None
+
+
+def _dir_lights(lights):
+    """the [K, 4] lights as (hf_dir_light_t array of at least one entry, K); hf_point_light_t has its packing: position, intensity"""
+    L = (_capi.hf_dir_light_t * max(lights.shape[0], 1))()
+    for k, row in enumerate(lights.detach().cpu().tolist()):
+        L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = row
+    return L, lights.shape[0]
+
+
+def _with_weight(ctx, saved, ww):
+    """forward: the tensors to save, the optional per-sample weight last; ctx.weighted tells jvp and backward that it is there"""
+    ctx.weighted = ww is not None
+    return saved + (ww,) if ctx.weighted else saved
+
+
+def _weighted_tangents(ctx, dsh_n, dweight):
+    """jvp: the tangents of sh_n and weight as float32 (None: zero, or no weight was given)"""
+    return _detached_f32(dsh_n), _detached_f32(dweight if ctx.weighted else None)
+
+
+def _weighted_grads(ctx, sn, grad_image):
+    """backward: grad_image as float32, the gradient outputs of sh_n and of weight (None: no weight was given)"""
+    return _detached_f32(grad_image), torch.empty_like(sn), torch.empty_like(sn[0]) if ctx.weighted else None
+
+
+def _empty_rays(pp):
+    """the outputs of a *_rays entry: a Ray3f of the wavefront's size"""
+    return Ray3f(torch.empty_like(pp), torch.empty_like(pp), torch.empty(pp.shape[1], dtype=torch.float32, device=pp.device))
+
+
 def _lighting_inputs(sh_n, d, t, lights, vis):
-    """what both lighting Functions pass to libhf: the sh_n, d and t rows as float32, the [K, 4] lights as the
-    hf_dir_light_t array (hf_point_light_t has its packing: position, intensity) and the vis row pointers"""
-    K = lights.shape[0]
-    L = (_capi.hf_dir_light_t * K)()
-    lh = lights.detach().cpu().tolist()
-    for k in range(K):
-        L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = lh[k]
+    """what both direct lighting Functions pass to libhf: the sh_n, d and t rows as float32, the lights and the vis row pointers"""
     vis = vis.to(dtype=torch.uint8).contiguous() if vis is not None else None
-    f32 = [x.to(dtype=torch.float32).contiguous() for x in (sh_n, d, t)]
-    return (*f32, L, K, vis, _row_ptrs(vis))
+    return (*(x.to(dtype=torch.float32).contiguous() for x in (sh_n, d, t)), *_dir_lights(lights), vis, _row_ptrs(vis))
 
 
 class _DirectLightingOp(torch.autograd.Function):
@@ -1325,8 +1353,7 @@ class _DirectLightingOp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sh_n, d, t, lights, albedo, spp, vis, weight):
         sn, dd, tt, L, K, vis, vis_p = _lighting_inputs(sh_n, d, t, lights, vis)
-        ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
-        saved = (sn, dd, tt) if ww is None else (sn, dd, tt, ww)
+        saved = _with_weight(ctx, (sn, dd, tt), _detached_f32(weight))
         ctx.save_for_backward(*saved)
         ctx.save_for_forward(*saved)
         ctx.misc = (K, spp, L, albedo, vis, vis_p)
@@ -1338,8 +1365,7 @@ class _DirectLightingOp(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, dsh_n, _dd, _dt, _dl, _da, _ds, _dv, dweight):
         saved = ctx.saved_tensors
-        dn = _f3(dsh_n)[0] if dsh_n is not None else None
-        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 4 and dweight is not None) else None
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
         K, spp, sn = ctx.misc[0], ctx.misc[1], saved[0]
         dimage = torch.empty((K, sn.shape[1] // spp), dtype=torch.float32, device=sn.device)
         check(_capi.lib().hf_direct_lighting_weighted_tangent(*_DirectLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
@@ -1350,9 +1376,7 @@ class _DirectLightingOp(torch.autograd.Function):
     def backward(ctx, grad_image):
         saved = ctx.saved_tensors
         sn = saved[0]
-        gi = grad_image.to(dtype=torch.float32).contiguous()
-        gn = torch.empty_like(sn)
-        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 4 else None
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
         check(_capi.lib().hf_direct_lighting_weighted_adjoint(*_DirectLightingOp._prefix(ctx, *saved), gi.data_ptr(),
                                                               C.byref(_p3(gn)), _ptr(gw), _stream_of(sn.device)))
         return gn, None, None, None, None, None, None, gw
@@ -1393,8 +1417,7 @@ class _PointLightingOp(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, dsh_n, dp, *_):
         sn = ctx.saved_tensors[0]
-        dn = _f3(dsh_n)[0] if dsh_n is not None else None
-        dq = _f3(dp)[0] if dp is not None else None
+        dn, dq = _detached_f32(dsh_n), _detached_f32(dp)
         dimage = torch.empty((ctx.misc[0], sn.shape[1] // ctx.misc[1]), dtype=torch.float32, device=sn.device)
         check(_capi.lib().hf_point_lighting_tangent(*_PointLightingOp._prefix(ctx, *ctx.saved_tensors), _ref(_row_ptrs(dn)),
                                                     _ref(_row_ptrs(dq)), dimage.data_ptr(), _stream_of(sn.device)))
@@ -1430,8 +1453,7 @@ class _SkyLightingOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sh_n, weight, shape, p, nrm, d, t, radiance, albedo, spp, num_rays, seed, ray_index):
-        sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (sh_n, p, nrm, d, t))
-        ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
+        sn, pp, gn, dd, tt, ww = map(_detached_f32, (sh_n, p, nrm, d, t, weight))
         n = sn.shape[1]
         ctx.misc = (spp, num_rays, seed, ray_index, radiance, albedo)
         image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
@@ -1440,7 +1462,7 @@ class _SkyLightingOp(torch.autograd.Function):
             check(_capi.lib().hf_sky_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
                                               C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(ray_index),
                                               radiance, albedo, image.data_ptr(), vis.data_ptr(), _stream_of(sn.device)))
-        saved = (sn, dd, tt, vis) if ww is None else (sn, dd, tt, vis, ww)
+        saved = _with_weight(ctx, (sn, dd, tt, vis), ww)
         ctx.save_for_backward(*saved)
         ctx.save_for_forward(*saved)
         ctx.mark_non_differentiable(vis)
@@ -1450,8 +1472,7 @@ class _SkyLightingOp(torch.autograd.Function):
     def jvp(ctx, dsh_n, dweight, *_):
         saved = ctx.saved_tensors
         sn = saved[0]
-        dn = _f3(dsh_n)[0] if dsh_n is not None else None
-        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 5 and dweight is not None) else None
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
         dimage = torch.empty(sn.shape[1] // ctx.misc[0], dtype=torch.float32, device=sn.device)
         if sn.shape[1]:
             check(_capi.lib().hf_sky_lighting_tangent(*_SkyLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)), _ptr(dw),
@@ -1462,9 +1483,7 @@ class _SkyLightingOp(torch.autograd.Function):
     def backward(ctx, grad_image, _grad_vis):
         saved = ctx.saved_tensors
         sn = saved[0]
-        gi = grad_image.to(dtype=torch.float32).contiguous()
-        gn = torch.empty_like(sn)
-        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 5 else None
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
         if sn.shape[1]:
             check(_capi.lib().hf_sky_lighting_adjoint(*_SkyLightingOp._prefix(ctx, *saved), gi.data_ptr(), C.byref(_p3(gn)),
                                                       _ptr(gw), _stream_of(sn.device)))
@@ -1491,15 +1510,13 @@ def sky_rays(si, ray, k, seed=0, ray_index=None):
     for that direction, bit for bit.  Lanes it does not trace (no hit, seen from behind, direction below the shading
     hemisphere) get ``maxt = -1``, a miss."""
     rid = _check_ray_index(ray_index, ray)
-    sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (si.sh_frame.n, si.p, si.n, ray.d, si.t))
-    n = sn.shape[1]
-    o, d = torch.empty_like(pp), torch.empty_like(pp)
-    maxt = torch.empty(n, dtype=torch.float32, device=pp.device)
+    sn, pp, gn, dd, tt = map(_detached_f32, (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n, r = sn.shape[1], _empty_rays(pp)
     if n:
         check(_capi.lib().hf_sky_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
-                                      tt.data_ptr(), int(k), int(seed), _ptr(rid), C.byref(_p3(o)), C.byref(_p3(d)),
-                                      maxt.data_ptr(), _stream_of(pp.device)))
-    return Ray3f(o, d, maxt)
+                                      tt.data_ptr(), int(k), int(seed), _ptr(rid), C.byref(_p3(r.o)), C.byref(_p3(r.d)),
+                                      r.maxt.data_ptr(), _stream_of(pp.device)))
+    return r
 
 
 class _EnvmapEvalOp(torch.autograd.Function):
@@ -1656,9 +1673,7 @@ class _EnvmapLightingOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sh_n, weight, full, shape, p, nrm, d, t, table, rot, albedo, spp, num_rays, seed, ray_index):
-        sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (sh_n, p, nrm, d, t))
-        ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
-        dat = full.detach().to(dtype=torch.float32).contiguous()
+        sn, pp, gn, dd, tt, ww, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, full))
         n = sn.shape[1]
         ctx.misc = (spp, num_rays, seed, ray_index, rot, albedo)
         image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
@@ -1668,7 +1683,7 @@ class _EnvmapLightingOp(torch.autograd.Function):
                                                  C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(ray_index),
                                                  dat.shape[1], dat.shape[0], dat.data_ptr(), table.data_ptr(), C.byref(rot),
                                                  albedo, image.data_ptr(), vis.data_ptr(), _stream_of(sn.device)))
-        saved = (sn, dd, tt, vis, dat, table) if ww is None else (sn, dd, tt, vis, dat, table, ww)
+        saved = _with_weight(ctx, (sn, dd, tt, vis, dat, table), ww)
         ctx.save_for_backward(*saved)
         ctx.save_for_forward(*saved)
         ctx.mark_non_differentiable(vis)
@@ -1678,8 +1693,7 @@ class _EnvmapLightingOp(torch.autograd.Function):
     def jvp(ctx, dsh_n, dweight, dfull, *_):
         saved = ctx.saved_tensors
         sn = saved[0]
-        dn = _f3(dsh_n)[0] if dsh_n is not None else None
-        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 7 and dweight is not None) else None
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
         df = dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
         dimage = torch.empty(sn.shape[1] // ctx.misc[0], dtype=torch.float32, device=sn.device)
         if sn.shape[1]:
@@ -1691,9 +1705,7 @@ class _EnvmapLightingOp(torch.autograd.Function):
     def backward(ctx, grad_image, _grad_vis):
         saved = ctx.saved_tensors
         sn, dat = saved[0], saved[4]
-        gi = grad_image.to(dtype=torch.float32).contiguous()
-        gn = torch.empty_like(sn)
-        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 7 else None
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
         gd = torch.zeros_like(dat) if ctx.needs_input_grad[2] else None
         if sn.shape[1]:
             check(_capi.lib().hf_envmap_lighting_adjoint(*_EnvmapLightingOp._prefix(ctx, *saved), gi.data_ptr(),
@@ -1723,19 +1735,16 @@ def envmap_rays(si, ray, envmap, k, seed=0, ray_index=None, return_weight=False)
     direction below the shading hemisphere) get ``maxt = -1``, a miss.  ``return_weight``: also the emitter weights
     ``radiance / pdf`` of the draws ([n])."""
     rid = _check_ray_index(ray_index, ray)
-    sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (si.sh_frame.n, si.p, si.n, ray.d, si.t))
-    n = sn.shape[1]
+    sn, pp, gn, dd, tt = map(_detached_f32, (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n, r = sn.shape[1], _empty_rays(pp)
     W, H = envmap.resolution
     dat, table = envmap.full().detach().contiguous(), envmap.table()
-    o, d = torch.empty_like(pp), torch.empty_like(pp)
-    maxt = torch.empty(n, dtype=torch.float32, device=pp.device)
     wgt = torch.empty(n, dtype=torch.float32, device=pp.device) if return_weight else None
     if n:
         check(_capi.lib().hf_envmap_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
                                          tt.data_ptr(), int(k), int(seed), _ptr(rid), W, H, dat.data_ptr(), table.data_ptr(),
-                                         C.byref(envmap._rot), C.byref(_p3(o)), C.byref(_p3(d)), maxt.data_ptr(), _ptr(wgt),
-                                         _stream_of(pp.device)))
-    r = Ray3f(o, d, maxt)
+                                         C.byref(envmap._rot), C.byref(_p3(r.o)), C.byref(_p3(r.d)), r.maxt.data_ptr(),
+                                         _ptr(wgt), _stream_of(pp.device)))
     return (r, wgt) if return_weight else r
 
 
@@ -1753,12 +1762,8 @@ class _BounceLightingOp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sh_n, weight, heights, shape, p, nrm, d, t, lights, albedo, spp, num_rays, seed, ray_index):
-        sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (sh_n, p, nrm, d, t))
-        ww = weight.detach().to(dtype=torch.float32).contiguous() if weight is not None else None
-        n, K = sn.shape[1], lights.shape[0]
-        L = (_capi.hf_dir_light_t * max(K, 1))()
-        for k, row in enumerate(lights.detach().cpu().tolist()):
-            L[k].to_light[0], L[k].to_light[1], L[k].to_light[2], L[k].irradiance = row
+        sn, pp, gn, dd, tt, ww = map(_detached_f32, (sh_n, p, nrm, d, t, weight))
+        n, (L, K) = sn.shape[1], _dir_lights(lights)
         ctx.misc = (spp, num_rays, seed, ray_index, L, K, albedo)
         image = torch.empty((K, n // max(spp, 1)), dtype=torch.float32, device=sn.device)
         prim = torch.empty((num_rays, n), dtype=torch.int32, device=sn.device)
@@ -1768,8 +1773,7 @@ class _BounceLightingOp(torch.autograd.Function):
                                                  C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(ray_index),
                                                  K, L, albedo, image.data_ptr(), prim.data_ptr(), lit.data_ptr(), n,
                                                  _stream_of(sn.device)))
-        saved = (sn, dd, tt, prim, lit) if ww is None else (sn, dd, tt, prim, lit, ww)
-        _op_save(ctx, shape, saved)
+        _op_save(ctx, shape, _with_weight(ctx, (sn, dd, tt, prim, lit), ww))
         ctx.mark_non_differentiable(prim, lit)
         return image, prim, lit
 
@@ -1777,8 +1781,7 @@ class _BounceLightingOp(torch.autograd.Function):
     def jvp(ctx, dsh_n, dweight, dheights, *_):
         shape, saved = _op_saved(ctx, "jvp")
         sn = saved[0]
-        dn = _f3(dsh_n)[0] if dsh_n is not None else None
-        dw = dweight.to(dtype=torch.float32).contiguous() if (len(saved) == 6 and dweight is not None) else None
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
         dh = shape._dheights(dheights)
         dimage = torch.empty((ctx.misc[5], sn.shape[1] // ctx.misc[0]), dtype=torch.float32, device=sn.device)
         if sn.shape[1]:
@@ -1790,9 +1793,7 @@ class _BounceLightingOp(torch.autograd.Function):
     def backward(ctx, grad_image, _grad_prim, _grad_lit):
         shape, saved = _op_saved(ctx, "backward")
         sn = saved[0]
-        gi = grad_image.to(dtype=torch.float32).contiguous()
-        gn = torch.empty_like(sn)
-        gw = torch.empty(sn.shape[1], dtype=torch.float32, device=sn.device) if len(saved) == 6 else None
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
         gh = shape._zero_heights() if ctx.needs_input_grad[2] else None
         if sn.shape[1]:
             check(_capi.lib().hf_bounce_lighting_adjoint(*_BounceLightingOp._prefix(ctx, shape, *saved), gi.data_ptr(),
@@ -1832,16 +1833,14 @@ def bounce_rays(shape, si, ray, k, seed=0, ray_index=None, to_light=None):
     kernel traces: the bounce ray, or with ``to_light`` (3 floats) the shadow ray from that bounce ray's hit towards
     the light.  Lanes the fused kernel does not trace get ``maxt = -1``, a miss."""
     rid = _check_ray_index(ray_index, ray)
-    sn, pp, gn, dd, tt = (x.detach().to(dtype=torch.float32).contiguous() for x in (si.sh_frame.n, si.p, si.n, ray.d, si.t))
-    n = sn.shape[1]
-    o, d = torch.empty_like(pp), torch.empty_like(pp)
-    maxt = torch.empty(n, dtype=torch.float32, device=pp.device)
+    sn, pp, gn, dd, tt = map(_detached_f32, (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n, r = sn.shape[1], _empty_rays(pp)
     tl = (C.c_float * 3)(*[float(x) for x in to_light]) if to_light is not None else None
     if n:
         check(_capi.lib().hf_bounce_rays(shape._h, n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
-                                         tt.data_ptr(), int(k), int(seed), _ptr(rid), _ref(tl), C.byref(_p3(o)),
-                                         C.byref(_p3(d)), maxt.data_ptr(), _stream_of(pp.device)))
-    return Ray3f(o, d, maxt)
+                                         tt.data_ptr(), int(k), int(seed), _ptr(rid), _ref(tl), C.byref(_p3(r.o)),
+                                         C.byref(_p3(r.d)), r.maxt.data_ptr(), _stream_of(pp.device)))
+    return r
 
 
 def _film_splat(values, ps, weight, K, n, width, height, stddev):

@@ -11,7 +11,8 @@ fails or runs out of time ends the script.  One JSON line per measurement (mean 
 composition's image is compared with the fused one first, and the fused forward is timed before and after the
 composition).  --stats: registers, LDS, private segment and occupancy of the hf_bounce_* kernels, read from the
 metadata of the library that ran (HF_LIB or the in-tree build; compiles nothing; --stats-only needs no device)."""
-import argparse, json, math, os, re, struct, subprocess, sys, tempfile
+import argparse, json, math, os, subprocess, sys
+from regs import kernel_stats, occupancy_line
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -31,45 +32,12 @@ SEED, ALBEDO = 3, 0.8
 LIGHTS = [[0.3, 0.2, 0.9, 1.0], [-0.5, 0.4, 0.6, 0.7]]
 
 
-def kernel_stats(lib_path):
-    """one line per hf_bounce_* kernel of the gfx950 code object inside lib_path"""
-    data = open(lib_path, "rb").read()
-    at = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert at >= 0, "no uncompressed offload bundle in " + lib_path
-    n, = struct.unpack_from("<Q", data, at + 24)
-    p, lines = at + 32, []
-    for _ in range(n):
-        off, size, tl = struct.unpack_from("<QQQ", data, p); p += 24
-        triple = data[p:p + tl].decode(); p += tl
-        if "gfx950" not in triple:
-            continue
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(data[at + off:at + off + size]); f.flush()
-            notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
-        cur = {}
-        for line in notes.splitlines():
-            m = re.match(r"\s+-?\s*\.(\w+):\s+(\S+)", line)
-            if not m:
-                continue
-            k, v = m.groups()
-            if k == "group_segment_fixed_size" and "name" in cur:   # a new kernel record starts (fields come sorted by key)
-                cur = {}
-            cur[k] = v
-            if k == "vgpr_spill_count" and "hf_bounce" in cur.get("name", ""):
-                vg = int(cur["vgpr_count"])
-                occ = min(8, 512 // max(8, (vg + 7) // 8 * 8))     # waves per SIMD the 512-register file admits
-                lines.append(f"{cur['name']:60s} vgpr {vg:4d} spill {v:>3s} sgpr {cur.get('sgpr_count'):>3s} sgpr_spill "
-                             f"{cur.get('sgpr_spill_count'):>3s} lds {cur.get('group_segment_fixed_size')} private "
-                             f"{cur.get('private_segment_fixed_size')} occupancy {occ} waves/SIMD")
-    return lines
-
-
 if a.child is None:
     # ---- the parent: touches no device; one child per scene, each under its own time limit ----
     import hf_amd  # noqa: E402
     lib_path = os.environ.get("HF_LIB") or hf_amd.build.LIB_PATH
     if a.stats or a.stats_only:
-        text = "\n".join(kernel_stats(lib_path))
+        text = "\n".join(map(occupancy_line, kernel_stats(lib_path, "hf_bounce")))
         print(text)
         if a.stats:
             os.makedirs(os.path.dirname(os.path.abspath(a.stats)), exist_ok=True)

@@ -13,7 +13,8 @@ One JSON line per measurement (mean / min ms over the timed calls).  `model_gbps
 its own count -- 11 passes of 4 W H bytes per iteration, 2 per apply -- over the measured time of the WHOLE
 call: an end-to-end figure, not a kernel's share of peak.  --stats: registers, LDS, private segment and occupancy of the
 hf_large_steps_* kernels, read from the metadata of the library that ran (compiles nothing; --stats-only needs no device)."""
-import argparse, json, os, re, struct, subprocess, sys, tempfile
+import argparse, json, os, sys
+from regs import kernel_stats, occupancy_line
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 ap = argparse.ArgumentParser()
@@ -28,42 +29,9 @@ LAMBDA, MAX_ITER, TOL, STEP = 19.0, 256, 1e-6, 1e-3
 PASSES_PER_ITERATION, PASSES_PER_APPLY = 11, 2
 
 
-def kernel_stats(lib_path):
-    """one line per hf_large_steps_* kernel of the gfx950 code object inside lib_path"""
-    data = open(lib_path, "rb").read()
-    at = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    assert at >= 0, "no uncompressed offload bundle in " + lib_path
-    n, = struct.unpack_from("<Q", data, at + 24)
-    p, lines = at + 32, []
-    for _ in range(n):
-        off, size, tl = struct.unpack_from("<QQQ", data, p); p += 24
-        triple = data[p:p + tl].decode(); p += tl
-        if "gfx950" not in triple:
-            continue
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(data[at + off:at + off + size]); f.flush()
-            notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
-        cur = {}
-        for line in notes.splitlines():
-            m = re.match(r"\s+-?\s*\.(\w+):\s+(\S+)", line)
-            if not m:
-                continue
-            k, v = m.groups()
-            if k == "group_segment_fixed_size" and "name" in cur:   # a new kernel record starts (fields come sorted by key)
-                cur = {}
-            cur[k] = v
-            if k == "vgpr_spill_count" and "hf_large_steps" in cur.get("name", ""):
-                vg = int(cur["vgpr_count"])
-                occ = min(8, 512 // max(8, (vg + 7) // 8 * 8))     # waves per SIMD the 512-register file admits
-                lines.append(f"{cur['name']:60s} vgpr {vg:4d} spill {v:>3s} sgpr {cur.get('sgpr_count'):>3s} sgpr_spill "
-                             f"{cur.get('sgpr_spill_count'):>3s} lds {cur.get('group_segment_fixed_size')} private "
-                             f"{cur.get('private_segment_fixed_size')} occupancy {occ} waves/SIMD")
-    return lines
-
-
 import hf_amd  # noqa: E402
 if a.stats or a.stats_only:
-    text = "\n".join(kernel_stats(hf_amd.build.LIB_PATH))
+    text = "\n".join(map(occupancy_line, kernel_stats(hf_amd.build.LIB_PATH, "hf_large_steps")))
     print(text)
     if a.stats:
         os.makedirs(os.path.dirname(os.path.abspath(a.stats)), exist_ok=True)

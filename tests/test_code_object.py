@@ -95,13 +95,16 @@ def test_private_segment_and_stack_of_every_kernel(code_object):
 
 def test_spills_of_the_hot_kernels(code_object):
     """register allocation is the fragile part of the traversal kernels: a source change that pushes the
-    hot kernels into spilling shows up here before it shows up in a profile"""
+    hot kernels into spilling shows up here before it shows up in a profile.  The lighting forward kernels walk per lane at
+    six waves per SIMD: 80 VGPRs, and no more spilled registers than they had when that was measured"""
     ks = {k["name"]: k for k in _kernels(code_object)}
-    bounds = {"hf_trace_kernelILi0ELb0": 8, "hf_trace_kernelILi1ELb0": 8, "hf_trace_kernelILi2ELb0": 8, "hf_trace_kernelILi2ELb1": 16,
-              "hf_adjoint_kernelILb0": 0, "hf_si_kernel": 0}
-    for frag, cap in bounds.items():
+    # fragment of the name -> (spilled VGPRs, VGPRs) at most
+    bounds = {"hf_trace_kernelILi0ELb0": (8, 128), "hf_trace_kernelILi1ELb0": (8, 128), "hf_trace_kernelILi2ELb0": (8, 128),
+              "hf_trace_kernelILi2ELb1": (16, 128), "hf_adjoint_kernelILb0": (0, 128), "hf_si_kernel": (0, 128),
+              "hf_sky_kernel": (15, 80), "hf_envmap_kernel": (15, 80), "hf_bounce_kernel": (10, 80)}
+    for frag, (cap, vgprs) in bounds.items():
         hit = [k for n, k in ks.items() if frag in n]
         assert hit, f"kernel {frag} not found in {sorted(ks)}"
         for k in hit:
             assert int(k["vgpr_spill_count"]) <= cap, f"{k['name']}: {k['vgpr_spill_count']} spilled VGPRs (cap {cap})"
-            assert int(k["vgpr_count"]) <= 128, k["name"]
+            assert int(k["vgpr_count"]) <= vgprs, f"{k['name']}: {k['vgpr_count']} VGPRs (cap {vgprs})"
