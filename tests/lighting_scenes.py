@@ -10,7 +10,11 @@ normalised; irradiance linspace(1.0, 0.4, L).
 
 cpu_model() runs a scene with the oracle and the float64 restatements alone (tests/sky_ref.py, tests/bounce_ref.py) and
 returns the shares that make the scene a test: how many samples are eligible, how many bounce rays hit, how many lights
-reach a hit, how many lanes a rounding decides."""
+reach a hit, how many lanes a rounding decides.
+
+smooth_normals() and bent_normals() give a scene shading normals that are not its geometric normals, and normals_model()
+counts, again with the oracle and the restatements alone, the decisions that then separate the two (tests/
+test_lighting_normals.py on the CPU, tests/test_gpu_lighting_normals.py on the GPU)."""
 import types
 
 import numpy as np
@@ -144,6 +148,115 @@ def cpu_model(sc, oracle):
                 "lit": m.lit.sum((0, 2)) / np.maximum(m.shadow.sum((0, 2)), 1), "lit_records": m.lit.sum((0, 2)),
                 "undecided": undecided / total, "max_coordinate": float(max(coords))}
     return m
+
+
+# ---- shading normals that are not the geometric normal (tests/test_lighting_normals.py, test_gpu_lighting_normals.py) -----
+KINDS = ("smooth", "bent")
+ENV_SCENES = ("affine", "mirror_flip", "rand8")            # the scenes and maps of the envmap row's draws
+ENV_MAPS = (("sun", 0.25), ("gradient", 0.0))
+BEND = 0.5                                                 # tan of the angle between `bent` and n: 26.6 degrees
+
+
+def smooth_normals(sc, rays, prim, hit):
+    """[3, n] float64: sh_n of smooth_ref.surface(mode="default") (the blended vertex normals, face_normals = false) at
+    the triangles `prim` of the hits; zero on misses, as the record is"""
+    import torch
+    import smooth_ref
+    at = np.flatnonzero(hit)
+    r64 = torch.from_numpy(np.asarray(rays, np.float64)[:, at])
+    ref = smooth_ref.surface(torch.from_numpy(sc.h64), sc.max_height, torch.from_numpy(np.asarray(sc.to_world, np.float64)),
+                             sc.flip, r64[0:3].T.contiguous(), r64[3:6].T.contiguous(),
+                             torch.from_numpy(np.asarray(prim).view(np.uint32)[at].astype(np.int64)), None, "default")
+    out = np.zeros((3, len(hit)))
+    out[:, at] = ref["sh_n"].numpy().T
+    return out
+
+
+def bent_normals(n, hit):
+    """[3, n] float32: normalize(n + BEND tau), tau the default_rng(3) normal draw projected off n and normalised: BEND
+    is the tangent of the angle to n on every hit; misses keep n"""
+    n64 = np.asarray(n, np.float64)
+    tau = np.random.default_rng(3).normal(size=n64.shape)
+    tau -= n64 * (n64 * tau).sum(0)
+    tau /= np.linalg.norm(tau, axis=0)
+    b = n64 + BEND * tau
+    b /= np.linalg.norm(b, axis=0)
+    return np.where(np.asarray(hit, bool)[None], b.astype(np.float32), np.asarray(n, np.float32))
+
+
+def below_counts(sh_n, gn, d, t, w, valid=None):
+    """what separates the two normals among the decisions of a sky-like row (directions w [K, 3, n], `valid` [K, n] draws):
+    (traced [K, n] by sh_n, <gn, w> [K, n], lanes traced with <gn, w> < -MARGIN, lanes of eligible samples with a valid draw
+    that are NOT traced although <gn, w> > MARGIN)"""
+    el, _ = S.eligible(sh_n, d, t)
+    ok = el[None] if valid is None else el[None] & valid
+    co = np.einsum("cn,kcn->kn", np.asarray(sh_n, np.float64), w)
+    cg = np.einsum("cn,kcn->kn", np.asarray(gn, np.float64), w)
+    traced = ok & (co > 0)
+    return traced, cg, traced & (cg < -MARGIN), ok & ~traced & (cg > MARGIN)
+
+
+def normals_model(sc, oracle, kind, maps=()):
+    """the scene with the shading normals `kind` through the oracle and the restatements only (sky_ref, bounce_ref,
+    envmap_ref, smooth_ref): the populations that make (scene, kind) a test of WHICH normal a kernel uses.  Returns
+    (counts of the sky and bounce rows, {(map, u): counts of the envmap row})"""
+    import envmap_ref as E
+    f = oracle_field(sc, oracle)
+    r = sc.rays
+    t, u, v, prim = f.ray_intersect_preliminary(r)
+    rec = f.compute_surface_interaction(r, t, u, v, prim, oracle.RAY_ALL)
+    hit = np.isfinite(t)
+    p, gn, d = (x.astype(np.float64) for x in (rec["p"], rec["n"], r[3:6]))
+    sh_n = smooth_normals(sc, r, prim, hit) if kind == "smooth" else bent_normals(rec["n"], hit).astype(np.float64)
+    ids = np.arange(sc.n)
+    el, elm = S.eligible(sh_n, d, t)
+    el_n, _ = S.eligible(gn, d, t)
+    angle = np.degrees(np.arccos(np.clip((sh_n * gn).sum(0)[hit], -1, 1)))
+    common_ = {"hits": int(hit.sum()), "eligible": int(el.sum()), "eligibility_differs": int((el != el_n).sum()),
+               "angle_deg": (float(angle.min()), float(np.median(angle)), float(angle.max())), "max_p": float(np.abs(p).max())}
+
+    def shadow_row(w, valid, margin):
+        """the counts of a row whose rays are shadow rays: sky, envmap"""
+        traced, cg, below, above = below_counts(sh_n, gn, d, t, w, valid)
+        seen = np.zeros(traced.shape, bool)
+        for k in range(K):
+            tr = np.flatnonzero(traced[k])
+            seen[k, tr] = ~f.ray_test(_rays7(S.spawn_origin(p, gn, w[k])[:, tr], w[k][:, tr])).astype(bool)
+        ok = hit[None] if valid is None else hit[None] & valid
+        undecided = (ok & (elm[None] <= MARGIN)) | (el[None] & ok & ((margin <= MARGIN) | (np.abs(cg) <= MARGIN)))
+        return {"traced": int(traced.sum()), "traced_below": int(below.sum()), "below_unoccluded": int((below & seen).sum()),
+                "below_occluded": int((below & ~seen).sum()), "above_untraced": int(above.sum()),
+                "undecided": float(undecided.mean())}
+
+    # ---- the sky row
+    ws = S.directions(ids, K, SEED)
+    sky = shadow_row(ws, None, S.traced(sh_n, d, t, ws)[1])
+    # ---- the bounce row
+    w, z = B.directions(sh_n, ids, K, SEED)
+    traced = B.traced(sh_n, d, t, z)
+    cg = np.einsum("cn,kcn->kn", gn, w)
+    below = traced & (cg < -MARGIN)
+    bhit = np.zeros(traced.shape, bool); back = np.zeros(traced.shape, bool)
+    for k in range(K):
+        tr = np.flatnonzero(traced[k])
+        t2, _, _, prim2 = f.ray_intersect_preliminary(_rays7(B.spawn_origin(p, gn, w[k])[:, tr], w[k][:, tr]))
+        bhit[k, tr] = np.isfinite(t2)
+        hp = np.full(sc.n, MISS, np.uint32); hp[tr[np.isfinite(t2)]] = prim2[np.isfinite(t2)]
+        back[k] = bhit[k] & ((normals_of(sc, hp, bhit[k]) * w[k]).sum(0) > MARGIN)
+    undecided = (hit[None] & (elm[None] <= MARGIN)) | (el[None] & ((z <= MARGIN) | (np.abs(cg) <= MARGIN)))
+    bounce = {"traced": int(traced.sum()), "traced_below": int(below.sum()), "below_hit": int((below & bhit).sum()),
+              "hit_from_behind": int(back.sum()), "undecided": float(undecided.mean())}
+    # ---- the envmap row
+    env = {}
+    for name, u_ in maps:
+        data = E.MAPS[name]()
+        dr = E.draws(data, E.build_table(data, u_), ids, K, SEED, E.DEFAULT_ROT)
+        env[(name, u_)] = shadow_row(dr["w"], dr["valid"], E.traced(sh_n, d, t, dr)[1])
+    return types.SimpleNamespace(sh_n=sh_n, n=gn, common=common_, sky=sky, bounce=bounce, env=env)
+
+
+# the floors of tests/test_lighting_normals.py, which the GPU tests hold their own populations to
+FLOOR_BELOW, FLOOR_ABOVE, FLOOR_OUTCOME, FLOOR_BOUNCE_HIT, FLOOR_ELIGIBILITY, FLOOR_BEHIND = 200, 100, 10, 100, 40, 100
 
 
 # ---- what the GPU lighting tests share ---------------------------------------------------------------------------------
