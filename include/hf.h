@@ -706,6 +706,79 @@ int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], 
                             float radiance, float albedo, const uint32_t *vis_bits, const float *const dsh_n[3],
                             const float *dweight, float *dimage, hf_stream_t stream);
 
+/* ---- next row: refractive caustics, light tracing through the surface ----
+ *
+ * The rows above end at a diffuse surface seen from a camera.  Here every wavefront sample is a LIGHT sample that arrives
+ * along d, is refracted at the surface (the `dielectric` BSDF's transmission lobe in importance mode, dielectric.cpp:361)
+ * and lands on a receiver plane: sunlight through a water surface onto a pool floor, a caustic lens.  World space.
+ *   inputs      p, nrm (the geometric normal g), sh_n (the shading normal m), d: 3 device rows of n floats; t: n floats;
+ *               weight: n floats or NULL (1); active: n bytes or NULL (every lane); wi = -d.
+ *   constants   eta: the relative index as fresnel() defines it (> 1: the normal points into the less dense side);
+ *               power: the flux one sample carries; receiver (HOST memory): the plane through `origin` spanned by ex and
+ *               ey, N = normalize(ex x ey); film x = <X - origin, ex>, y = <X - origin, ey>, in pixels.
+ *   eligible    t_i is finite, the sample is active, c_i = <m, wi> != 0 and <g, wi> c_i > 0 (both normals agree on the
+ *               side; both signs of c_i are served, as fresnel() serves them);
+ *   Fresnel     (F, c_t, eta_it, eta_ti) = fresnel(c_i, eta), include/mitsuba/render/fresnel.h:35-71, operation for
+ *               operation in float32; cos_theta_t_sqr <= 0 is total internal reflection: nothing is transmitted;
+ *   direction   wo = refract(wi, m, c_t, eta_ti) = m (<wi, m> eta_ti + c_t) - wi eta_ti (fresnel.h:311-314);
+ *   consistent  <g, wo> <g, wi> < 0: the transmitted ray leaves on the other side of the true surface;
+ *   receiver    s = <origin - p, N> / <wo, N>; it is REACHED when s is finite and s > 0;
+ *   traced      = eligible, transmitted, consistent and reached;
+ *   ray         SurfaceInteraction::spawn_ray(wo) exactly as hf_sky_rays builds it, direction wo, maxt = s: a receiver
+ *               that cuts through the terrain's bound clips the walk;
+ *   deposited   vis[i] = 1 iff the sample is traced and the any-hit walk of that ray finds nothing;
+ *   landing     X = p + s wo, pos = (<X - origin, ex>, <X - origin, ey>);
+ *   value       weight_i power (1 - F): no eta^2 factor (importance mode);
+ *   every other sample: value = 0, vis = 0, pos = (-16, -16) -- outside every film by more than the filter radius of
+ *               hf_film_splat_weighted (4 stddev), whose clamped footprint is then empty.
+ * One square root and three divisions per sample (two in fresnel(), one for s); no transcendental, no double precision.
+ * The masks and the occlusion are piecewise constant, as in the rows above: the silhouette term is out of scope.
+ * pos and value are differentiated with respect to sh_n, p and weight -- through c_i, F, c_t, wo and s, with the sign
+ * choices and the masks held; d and the receiver are constants.  With c = c_i, e = eta_ti, q = c e + c_t, b = <wo, N>:
+ *   d c_t / d c = -|c| e^2 / |c_t|,   q' = e + d c_t / d c,   F' = a_s a_s' + a_p a_p' (0 for eta = 1),
+ *   d wo = d m q + m q' <d m, wi>,   d s = -(<d p, N> + s <d wo, N>) / b,   d X = d p + wo d s + s d wo,
+ *   d pos = (<d X, ex>, <d X, ey>),   d value = d weight power (1 - F) - weight power F' <d m, wi>.
+ * All four entries refuse with HF_EINVAL, before anything touches a device: NULL pointers (other than those marked
+ * optional), n >= 2^32, a non-finite or non-positive eta, a non-finite power, a receiver that is not finite, whose
+ * ex x ey is zero or whose ex, ey are not orthogonal to within 1e-5 |ex| |ey|.  Callers detect the entries by their
+ * symbols (HF_VERSION is unchanged). */
+typedef struct hf_receiver {      /* HOST memory */
+    float origin[3];              /* world point at film position (0, 0) */
+    float ex[3], ey[3];           /* film x = <X - origin, ex>, y = <X - origin, ey>, in pixels */
+} hf_receiver_t;
+/* hf_caustic_rays materialises the refracted ray of every sample (out_o, out_d: 3 rows of n floats; out_maxt: n floats,
+ * s for a traced lane; every other lane gets -1 -- a miss -- and a zero origin and direction): the two-call sequence
+ * hf_caustic_rays + hf_ray_test that hf_caustic_lighting equals bit for bit.  Takes no field handle. */
+int hf_caustic_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                    const float *const d[3], const float *t, const uint8_t *active, float eta,
+                    const hf_receiver_t *receiver, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                    hf_stream_t stream);
+/* The fused launch (hf_sky_lighting's mapping: one lane per sample, one workgroup per 256 samples, no work counter):
+ * reads a sample's record once, refracts, runs the per-lane any-hit walk with the ray's maxt and writes pos (2 rows of n
+ * floats), value (n floats) and vis (n bytes, may be NULL = not wanted); no ray goes to memory.  A batch of 64 samples
+ * without a traced lane skips the walk.  Every wave walks per lane, whatever hf_set_ray_coherence says: that state is
+ * neither read nor changed.  Allocates nothing, never synchronises the host, capturable. */
+int hf_caustic_lighting(const hf_field_t *hf, size_t n, const float *const p[3], const float *const nrm[3],
+                        const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                        const float *weight, float eta, float power, const hf_receiver_t *receiver, float *const pos[2],
+                        float *value, uint8_t *vis, hf_stream_t stream);
+/* Reverse mode with respect to sh_n, p and weight.  Traces nothing: the vertex is formed again and vis (as
+ * hf_caustic_lighting wrote it) is read.  grad_pos (2 rows) and grad_value may be NULL (zero); grad_sh_n, grad_p (3 rows
+ * each) and grad_weight may be NULL (not wanted).  Outputs are overwritten, exact zeros where vis = 0; one lane per
+ * sample, no atomics: bitwise the same from launch to launch.  Takes no field handle. */
+int hf_caustic_adjoint(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                       const float *const d[3], const float *t, const uint8_t *active, const float *weight, float eta,
+                       float power, const hf_receiver_t *receiver, const uint8_t *vis, const float *const grad_pos[2],
+                       const float *grad_value, float *const grad_sh_n[3], float *const grad_p[3], float *grad_weight,
+                       hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint: tangents dsh_n, dp (3 rows each) and dweight, each may be NULL (zero);
+ * dpos (2 rows) and dvalue are overwritten (either may be NULL = not wanted), exact zeros where vis = 0. */
+int hf_caustic_tangent(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                       const float *const d[3], const float *t, const uint8_t *active, const float *weight, float eta,
+                       float power, const hf_receiver_t *receiver, const uint8_t *vis, const float *const dsh_n[3],
+                       const float *const dp[3], const float *dweight, float *const dpos[2], float *dvalue,
+                       hf_stream_t stream);
+
 /* ---- next row: environment-map lighting, importance-sampled, the shadow rays traced in the kernel ----
  *
  * hf_sky_lighting with a direction-dependent environment: the reference's `envmap` emitter (src/emitters/envmap.cpp), one

@@ -53,6 +53,12 @@ class hf_dir_light_t(C.Structure):
     _fields_ = [("to_light", C.c_float * 3), ("irradiance", C.c_float)]
 
 
+class hf_receiver_t(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("ex", C.c_float * 3), ("ey", C.c_float * 3)]
+
+
+_caustic_in = [C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp]  # p, nrm, sh_n, d, t, active
+
 SYMBOLS = {
     "hf_create": (C.c_int, [C.POINTER(hf_desc_t), C.POINTER(C.c_void_p)]),
     "hf_destroy": (C.c_int, [C.c_void_p]),
@@ -154,6 +160,14 @@ SYMBOLS = {
     "hf_sky_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp,
                                           C.c_uint32, C.c_uint32, _fp, C.c_float, C.c_float, _fp, C.POINTER(_fp * 3), _fp,
                                           _fp, C.c_void_p]),
+    "hf_caustic_rays": (C.c_int, [C.c_size_t, *_caustic_in, C.c_float, C.POINTER(hf_receiver_t), C.POINTER(_fp * 3),
+                                  C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    "hf_caustic_lighting": (C.c_int, [C.c_void_p, C.c_size_t, *_caustic_in, _fp, C.c_float, C.c_float,
+                                      C.POINTER(hf_receiver_t), C.POINTER(_fp * 2), _fp, _fp, C.c_void_p]),
+    "hf_caustic_adjoint": (C.c_int, [C.c_size_t, *_caustic_in, _fp, C.c_float, C.c_float, C.POINTER(hf_receiver_t), _fp,
+                                     C.POINTER(_fp * 2), _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    "hf_caustic_tangent": (C.c_int, [C.c_size_t, *_caustic_in, _fp, C.c_float, C.c_float, C.POINTER(hf_receiver_t), _fp,
+                                     C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 2), _fp, C.c_void_p]),
     "hf_envmap_table_floats": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "hf_envmap_build_table": (C.c_int, [C.c_uint32, C.c_uint32, _fp, C.c_float, _fp, C.c_void_p]),
     "hf_envmap_sample_direction": (C.c_int, [C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, C.c_uint32, _fp, _fp,

@@ -1242,6 +1242,102 @@ extern "C" int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *cons
     return light_launch(hf_launch_sky, 2, a, stream);
 }
 
+// ---- refractive caustics: light tracing through the surface, the refracted rays walked in the kernel ----
+// What the four hf_caustic_* entries share: the wavefront rows, the interface and the receiver
+static int caustic_args(const char *who, size_t n, const float *const p[3], const float *const nrm[3],
+                        const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                        const float *weight, float eta, float power, const hf_receiver_t *rcv, hf_caustic_args &a) {
+    a = {};
+    if (!all3(p) || !all3(nrm) || !all3(sh_n) || !all3(d) || !t || !rcv) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (!isfinite(eta) || !(eta > 0.f)) return fail(HF_EINVAL, "%s: eta must be finite and positive (got %g)", who, (double) eta);
+    if (!isfinite(power)) return fail(HF_EINVAL, "%s: power must be finite", who);
+    double ex[3], ey[3], N[3], lx = 0.0, ly = 0.0, xy = 0.0, ln = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        if (!isfinite(rcv->origin[c]) || !isfinite(rcv->ex[c]) || !isfinite(rcv->ey[c]))
+            return fail(HF_EINVAL, "%s: the receiver must be finite", who);
+        ex[c] = rcv->ex[c]; ey[c] = rcv->ey[c];
+        lx += ex[c] * ex[c]; ly += ey[c] * ey[c]; xy += ex[c] * ey[c];
+    }
+    N[0] = ex[1] * ey[2] - ex[2] * ey[1]; N[1] = ex[2] * ey[0] - ex[0] * ey[2]; N[2] = ex[0] * ey[1] - ex[1] * ey[0];
+    for (int c = 0; c < 3; ++c) ln += N[c] * N[c];
+    if (!(ln > 0.0)) return fail(HF_EINVAL, "%s: the receiver's ex x ey is zero", who);
+    if (fabs(xy) > 1e-5 * sqrt(lx * ly)) return fail(HF_EINVAL, "%s: the receiver's ex and ey are not orthogonal", who);
+    a.n = n; a.eta = eta; a.rcp_eta = 1.f / eta; a.power = power; a.t = t; a.active = active; a.weight = weight;
+    for (int c = 0; c < 3; ++c) {
+        a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.sh_n[c] = sh_n[c]; a.d[c] = d[c];
+        a.origin[c] = rcv->origin[c]; a.ex[c] = rcv->ex[c]; a.ey[c] = rcv->ey[c]; a.N[c] = (float) (N[c] / sqrt(ln));
+    }
+    return HF_OK;
+}
+
+extern "C" int hf_caustic_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                               const float *const d[3], const float *t, const uint8_t *active, float eta,
+                               const hf_receiver_t *receiver, float *const out_o[3], float *const out_d[3],
+                               float *out_maxt, hf_stream_t stream) {
+    const char *fn = "hf_caustic_rays";
+    hf_caustic_args a;
+    const int rc = caustic_args(fn, n, p, nrm, sh_n, d, t, active, nullptr, eta, 1.f, receiver, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.out_maxt = out_maxt;
+    for (int c = 0; c < 3; ++c) { a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
+    return light_launch(hf_launch_caustic, 3, a, stream);
+}
+
+extern "C" int hf_caustic_lighting(const hf_field_t *hf, size_t n, const float *const p[3], const float *const nrm[3],
+                                   const float *const sh_n[3], const float *const d[3], const float *t,
+                                   const uint8_t *active, const float *weight, float eta, float power,
+                                   const hf_receiver_t *receiver, float *const pos[2], float *value, uint8_t *vis,
+                                   hf_stream_t stream) {
+    const char *fn = "hf_caustic_lighting";
+    hf_caustic_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = caustic_args(fn, n, p, nrm, sh_n, d, t, active, weight, eta, power, receiver, a);
+    if (rc != HF_OK) return rc;
+    if (!pos || !pos[0] || !pos[1] || !value) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.pos[0] = pos[0]; a.pos[1] = pos[1]; a.value = value; a.vis = vis;
+    return light_launch(hf_launch_caustic, 0, a, stream);
+}
+
+extern "C" int hf_caustic_adjoint(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                                  const float *const d[3], const float *t, const uint8_t *active, const float *weight,
+                                  float eta, float power, const hf_receiver_t *receiver, const uint8_t *vis,
+                                  const float *const grad_pos[2], const float *grad_value, float *const grad_sh_n[3],
+                                  float *const grad_p[3], float *grad_weight, hf_stream_t stream) {
+    const char *fn = "hf_caustic_adjoint";
+    hf_caustic_args a;
+    const int rc = caustic_args(fn, n, p, nrm, sh_n, d, t, active, weight, eta, power, receiver, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if ((grad_pos && (!grad_pos[0] || !grad_pos[1])) || (grad_sh_n && !all3(grad_sh_n)) || (grad_p && !all3(grad_p)))
+        return fail(HF_EINVAL, "%s: NULL component array", fn);
+    a.vis = const_cast<uint8_t *>(vis); a.gvalue = grad_value; a.gw = grad_weight;
+    for (int c = 0; c < 2; ++c) a.gpos[c] = grad_pos ? grad_pos[c] : nullptr;
+    for (int c = 0; c < 3; ++c) { a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr; a.gp[c] = grad_p ? grad_p[c] : nullptr; }
+    return light_launch(hf_launch_caustic, 1, a, stream);
+}
+
+extern "C" int hf_caustic_tangent(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                                  const float *const d[3], const float *t, const uint8_t *active, const float *weight,
+                                  float eta, float power, const hf_receiver_t *receiver, const uint8_t *vis,
+                                  const float *const dsh_n[3], const float *const dp[3], const float *dweight,
+                                  float *const dpos[2], float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_caustic_tangent";
+    hf_caustic_args a;
+    const int rc = caustic_args(fn, n, p, nrm, sh_n, d, t, active, weight, eta, power, receiver, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if ((dsh_n && !all3(dsh_n)) || (dp && !all3(dp)) || (dpos && (!dpos[0] || !dpos[1])))
+        return fail(HF_EINVAL, "%s: NULL component array", fn);
+    a.vis = const_cast<uint8_t *>(vis); a.dw = dweight; a.value = dvalue;
+    for (int c = 0; c < 2; ++c) a.pos[c] = dpos ? dpos[c] : nullptr;
+    for (int c = 0; c < 3; ++c) { a.dn[c] = dsh_n ? dsh_n[c] : nullptr; a.dp[c] = dp ? dp[c] : nullptr; }
+    return light_launch(hf_launch_caustic, 2, a, stream);
+}
+
 // ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----
 // What the hf_envmap_* entries share: the checks of the map (`a`: zeroed by the caller) ...
 static int envmap_map(const char *who, uint32_t W, uint32_t H, const float *data, bool need_data, const float *table,

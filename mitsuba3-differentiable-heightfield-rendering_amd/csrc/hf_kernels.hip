@@ -3660,16 +3660,17 @@ void hf_launch_film_motion(int mode, const hf_film_motion_args &a, hipStream_t s
 __device__ __forceinline__ bool sky_eligible(float t, v3 sn, v3 d) { return (t != __builtin_inff()) && (-dot3(sn, d) > 0.f); }
 
 // one lane's walk from the root (closest hit, or ANY hit), as an incoherent wave of hf_trace_kernel takes it.  `f`: the
-// kernel's by-value argument; what setup_ray needs of it is read from the kernarg segment (`kf`) again
+// kernel's by-value argument; what setup_ray needs of it is read from the kernarg segment (`kf`) again.  `maxt`: where
+// the ray ends (the overload below: a ray towards the environment, which lies outside the scene)
 template <bool ANY>
 __device__ __forceinline__ void light_walk(const __attribute__((address_space(4))) hf_dev_field *kf, const hf_dev_field &f, v3 o,
-                                           v3 w, bool traced, hf_hit &best) {
+                                           v3 w, float maxt, bool traced, hf_hit &best) {
     best.hit = false; best.t = __builtin_inff(); best.u = 0.f; best.v = 0.f; best.prim = 0u;
     hf_ray_state rs = {}; // fully defined on every path
     bool alive;
     {
         const hf_dev_field f0 = load_field(kf);
-        alive = traced && setup_ray(f0, f0.mip[1], o, w, __builtin_inff(), rs);
+        alive = traced && setup_ray(f0, f0.mip[1], o, w, maxt, rs);
     }
     if (alive) {
         float thi = rs.thi;
@@ -3678,6 +3679,11 @@ __device__ __forceinline__ void light_walk(const __attribute__((address_space(4)
         const uint32_t lfxm = rs.fx ? ((1u << f.top) - 1u) : 0u, lfym = rs.fy ? ((1u << f.top) - 1u) : 0u;
         (void) walk_subtree<ANY>(f, src, rs, rs.r, rs.fx, rs.fy, lfxm, lfym, 0u, 0u, f.top, thi, best);
     }
+}
+template <bool ANY>
+__device__ __forceinline__ void light_walk(const __attribute__((address_space(4))) hf_dev_field *kf, const hf_dev_field &f, v3 o,
+                                           v3 w, bool traced, hf_hit &best) {
+    light_walk<ANY>(kf, f, o, w, __builtin_inff(), traced, best);
 }
 
 // sin a, cos a in double for |a| <= pi / 4: two Taylor sums whose first dropped terms are 7e-12 and 4e-13 (a dozen fmas
@@ -3966,6 +3972,201 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sky_tangent_kernel(hf_sky_args a)
 void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream) {
     launch_light(mode, a, 1u, stream, hf_sky_kernel, hf_sky_adjoint_kernel, hf_sky_tangent_kernel<false>,
                  hf_sky_tangent_kernel<true>, hf_sky_rays_kernel);
+}
+
+// ---------------------------------------------------------------------------------
+// Refractive caustics (include/hf.h hf_caustic_*): light tracing through the surface.  Every wavefront sample is a
+// light sample that arrives along d; it is refracted at the shading normal (the `dielectric` BSDF's transmission lobe
+// in importance mode, dielectric.cpp:361: no eta^2), the refracted ray is walked (any hit, per lane, maxt = the
+// distance to the receiver plane) and what gets through lands on the receiver.  ONE launch, one lane per sample;
+// nothing of the ray goes to memory: per sample 56 B in (+ weight, active) and pos, value, one visibility byte out.
+// ---------------------------------------------------------------------------------
+// The specular vertex of one sample, the same text for the fused kernel, the rays kernel and the two derivatives.
+// fresnel() (fresnel.h:35-71) and refract() (fresnel.h:311-314) operation for operation: the fmas below are the
+// reference's fnmadd / fmadd / fmsub and nothing else fuses (the build contracts nothing).
+//   dF, dq: d F / d c_i and d (c_i eta_ti + c_t) / d c_i with the side (the sign of c_i) held; only the derivative
+//   kernels use them (one more division there)
+struct hf_caustic_vertex {
+    bool traced;                  // eligible, transmitted, consistent and on its way to the receiver
+    v3 wi, wo;
+    float s, b, F, q, dF, dq;     // s: distance to the receiver, b = <wo, N>, q = c_i eta_ti + c_t
+};
+template <class P>
+__device__ __forceinline__ hf_caustic_vertex caustic_vertex(P a, v3 m, v3 g, v3 d, v3 p, float t, bool act) {
+    hf_caustic_vertex v;
+    v.wi = mk3(-d.x, -d.y, -d.z);
+    const float ci = dot3(m, v.wi), gi = dot3(g, v.wi);
+    bool ok = act && (__builtin_fabsf(t) < __builtin_inff()) && (ci != 0.f) && (gi * ci > 0.f);
+    const float eta = a->eta, rcp_eta = a->rcp_eta;
+    const bool outside = ci >= 0.f;
+    const float eta_it = outside ? eta : rcp_eta, eta_ti = outside ? rcp_eta : eta;
+    const float e2 = eta_ti * eta_ti;
+    const float ct2 = __builtin_fmaf(-__builtin_fmaf(-ci, ci, 1.f), e2, 1.f);
+    ok = ok && (ct2 > 0.f); // total internal reflection: nothing is transmitted
+    const float cia = __builtin_fabsf(ci), cta = __builtin_sqrtf(fmaxf(ct2, 0.f));
+    const float ns = __builtin_fmaf(-eta_it, cta, cia), ds = __builtin_fmaf(eta_it, cta, cia);
+    const float np = __builtin_fmaf(-eta_it, cia, cta), dp = __builtin_fmaf(eta_it, cia, cta);
+    const float a_s = ns / ds, a_p = np / dp;
+    const bool matched = eta == 1.f; // (the other special case, c_i = 0, is not eligible)
+    v.F = matched ? 0.f : 0.5f * (a_s * a_s + a_p * a_p);
+    const float ct = outside ? -cta : cta; // mulsign_neg(cos_theta_t_abs, cos_theta_i)
+    v.q = __builtin_fmaf(ci, eta_ti, ct);
+    v.wo = mk3(__builtin_fmaf(m.x, v.q, -(v.wi.x * eta_ti)), __builtin_fmaf(m.y, v.q, -(v.wi.y * eta_ti)),
+               __builtin_fmaf(m.z, v.q, -(v.wi.z * eta_ti)));
+    ok = ok && (dot3(g, v.wo) * gi < 0.f); // leaves on the other side of the true surface
+    const v3 N = mk3(a->N[0], a->N[1], a->N[2]), org = mk3(a->origin[0], a->origin[1], a->origin[2]);
+    v.b = dot3(v.wo, N);
+    v.s = dot3(org - p, N) / v.b;
+    v.traced = ok && (__builtin_fabsf(v.s) < __builtin_inff()) && (v.s > 0.f);
+    // the derivatives with respect to c_i, the side held: d cta = c_i eta_ti^2 / cta
+    const float sg = outside ? 1.f : -1.f, dcta = ci * e2 / cta;
+    const float das = 2.f * ((eta_it * cta) * sg - cia * (eta_it * dcta)) / (ds * ds);
+    const float dap = 2.f * ((eta_it * cia) * dcta - cta * (eta_it * sg)) / (dp * dp);
+    v.dF = matched ? 0.f : a_s * das + a_p * dap;
+    v.dq = eta_ti - sg * dcta;
+    return v;
+}
+// where a deposited sample lands: film coordinates of p + s wo
+template <class P>
+__device__ __forceinline__ void caustic_landing(P a, v3 p, const hf_caustic_vertex &v, float &x, float &y) {
+    const v3 r = fma3(v.wo, v.s, p) - mk3(a->origin[0], a->origin[1], a->origin[2]);
+    x = dot3(r, mk3(a->ex[0], a->ex[1], a->ex[2]));
+    y = dot3(r, mk3(a->ey[0], a->ey[1], a->ey[2]));
+}
+// the vertex of sample i from the rows
+template <class P>
+__device__ __forceinline__ hf_caustic_vertex caustic_sample(P a, size_t i, bool in, v3 &m, v3 &p) {
+    m = mk3(a->sh_n[0][i], a->sh_n[1][i], a->sh_n[2][i]);
+    p = mk3(a->p[0][i], a->p[1][i], a->p[2][i]);
+    const v3 g = mk3(a->nrm[0][i], a->nrm[1][i], a->nrm[2][i]), d = mk3(a->d[0][i], a->d[1][i], a->d[2][i]);
+    const uint8_t *active = a->active;
+    return caustic_vertex(a, m, g, d, p, a->t[i], in && (active ? active[i] != 0 : true));
+}
+
+typedef const __attribute__((address_space(4))) hf_caustic_args *hf_caustic_kargs;
+
+__global__ __launch_bounds__(HF_BLOCK, HF_SKY_WAVES) void hf_caustic_kernel(hf_caustic_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    // (launch constants are read from the kernarg segment where they are used, as in hf_sky_kernel)
+    hf_caustic_kargs ka = (hf_caustic_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    float x = -16.f, y = -16.f, val = 0.f; // what a sample that deposits nothing writes
+    bool traced;
+    hf_hit best;
+    best.hit = false;
+    {
+        v3 m, p;
+        const hf_caustic_vertex v = caustic_sample(ka, ii, in, m, p);
+        traced = v.traced;
+        if (__ballot(traced) != 0ull) { // wave-uniform: a batch without a traced sample walks nothing
+            const v3 gn = mk3(ka->nrm[0][ii], ka->nrm[1][ii], ka->nrm[2][ii]);
+            if (traced) {
+                caustic_landing(ka, p, v, x, y);
+                val = ka->power * (1.f - v.F);
+            }
+            // three floats and the index are held across the walk; the ray ends at the receiver
+            light_walk<true>(&ka->f, f, sky_origin(p, gn, sky_offset(p), v.wo), v.wo, v.s, traced, best);
+        }
+    }
+    // (the output pointers: loaded here, not before the walk)
+    hf_caustic_kargs ko = (hf_caustic_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    if (!in) return;
+    const bool lit = traced && !best.hit;
+    const float *weight = ko->weight;
+    if (lit && weight) val *= weight[i];
+    ko->pos[0][i] = lit ? x : -16.f;
+    ko->pos[1][i] = lit ? y : -16.f;
+    ko->value[i] = lit ? val : 0.f;
+    uint8_t *vis = ko->vis;
+    if (vis) vis[i] = lit ? 1 : 0;
+}
+
+// the refracted ray of every sample, materialised: what hf_caustic_kernel walks, bit for bit (maxt = -1 and a zero
+// origin and direction: the fused kernel does not trace the lane)
+__global__ __launch_bounds__(HF_BLOCK) void hf_caustic_rays_kernel(hf_caustic_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 m, p;
+    const hf_caustic_vertex v = caustic_sample(&a, i, true, m, p);
+    const v3 gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    const v3 o = v.traced ? sky_origin(p, gn, sky_offset(p), v.wo) : z, w = v.traced ? v.wo : z;
+    a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
+    a.out_d[0][i] = w.x; a.out_d[1][i] = w.y; a.out_d[2][i] = w.z;
+    a.out_maxt[i] = v.traced ? v.s : -1.f;
+}
+
+// Reverse mode of hf_caustic_kernel with respect to sh_n, p and weight: nothing is traced, the vertex is formed again
+// and the visibility byte read.  One lane per sample, every wanted output overwritten, no atomics.
+__global__ __launch_bounds__(HF_BLOCK) void hf_caustic_adjoint_kernel(hf_caustic_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 gm = mk3(0.f, 0.f, 0.f), gp = gm;
+    float gw = 0.f;
+    if (a.vis[i]) {
+        v3 m, p;
+        const hf_caustic_vertex v = caustic_sample(&a, i, true, m, p);
+        if (v.traced) {
+            const float gx = a.gpos[0] ? a.gpos[0][i] : 0.f, gy = a.gpos[1] ? a.gpos[1][i] : 0.f;
+            const float gv = a.gvalue ? a.gvalue[i] : 0.f;
+            const v3 N = mk3(a.N[0], a.N[1], a.N[2]);
+            const v3 gX = fma3(mk3(a.ex[0], a.ex[1], a.ex[2]), gx, mk3(a.ey[0], a.ey[1], a.ey[2]) * gy);
+            const float c = -dot3(gX, v.wo) / v.b;     // dL/ds over -b
+            gp = fma3(N, c, gX);
+            const v3 gwo = fma3(N, c * v.s, gX * v.s);
+            const float pw = a.power * (a.weight ? a.weight[i] : 1.f);
+            const float gci = __builtin_fmaf(v.dq, dot3(m, gwo), -(pw * v.dF) * gv);
+            gm = fma3(v.wi, gci, gwo * v.q);
+            gw = a.power * (1.f - v.F) * gv;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (a.gn[c]) a.gn[c][i] = c == 0 ? gm.x : c == 1 ? gm.y : gm.z;
+        if (a.gp[c]) a.gp[c][i] = c == 0 ? gp.x : c == 1 ? gp.y : gp.z;
+    }
+    if (a.gw) a.gw[i] = gw;
+}
+
+// forward mode, the transpose of the above: tangents dn of sh_n, dp of p, dw of weight (NULL: zero)
+__global__ __launch_bounds__(HF_BLOCK) void hf_caustic_tangent_kernel(hf_caustic_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    float dx = 0.f, dy = 0.f, dv = 0.f;
+    if (a.vis[i]) {
+        v3 m, p;
+        const hf_caustic_vertex v = caustic_sample(&a, i, true, m, p);
+        if (v.traced) {
+            const v3 dm = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+            const v3 dp = a.dp[0] ? mk3(a.dp[0][i], a.dp[1][i], a.dp[2][i]) : mk3(0.f, 0.f, 0.f);
+            const float dw = a.dw ? a.dw[i] : 0.f;
+            const v3 N = mk3(a.N[0], a.N[1], a.N[2]);
+            const float dci = dot3(dm, v.wi);
+            const v3 dwo = fma3(m, v.dq * dci, dm * v.q);
+            const float ds = -(dot3(dp, N) + v.s * dot3(dwo, N)) / v.b;
+            const v3 dX = fma3(v.wo, ds, fma3(dwo, v.s, dp));
+            dx = dot3(dX, mk3(a.ex[0], a.ex[1], a.ex[2]));
+            dy = dot3(dX, mk3(a.ey[0], a.ey[1], a.ey[2]));
+            const float pw = a.power * (a.weight ? a.weight[i] : 1.f);
+            dv = __builtin_fmaf(dw, a.power * (1.f - v.F), -(pw * v.dF) * dci);
+        }
+    }
+    if (a.pos[0]) a.pos[0][i] = dx;
+    if (a.pos[1]) a.pos[1][i] = dy;
+    if (a.value) a.value[i] = dv;
+}
+
+void hf_launch_caustic(int mode, const hf_caustic_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    hipLaunchKernelGGL(mode == 0 ? hf_caustic_kernel : mode == 1 ? hf_caustic_adjoint_kernel : mode == 2 ? hf_caustic_tangent_kernel
+                                                                                                          : hf_caustic_rays_kernel,
+                       grid, block, 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------

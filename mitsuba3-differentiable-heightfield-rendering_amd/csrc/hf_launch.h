@@ -82,6 +82,24 @@ struct hf_sky_args {
 // mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is the per-lane any-hit walk with the samples
 // drawn in the kernel: no work counter, no scratch block
 void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream);
+// ---- refractive caustics (hf_caustic_rays, hf_caustic_lighting / _adjoint / _tangent): the one argument of its four kernels ----
+struct hf_caustic_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    float eta, rcp_eta, power;               // rcp_eta = 1 / eta, rounded once on the host
+    float origin[3], ex[3], ey[3], N[3];     // the receiver; N = normalize(ex x ey)
+    const float *p[3], *nrm[3], *sh_n[3], *d[3], *t, *weight;
+    const uint8_t *active;                   // optional (NULL: every lane)
+    float *pos[2], *value;                   // forward: written; tangent: dpos, dvalue
+    uint8_t *vis;                            // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    const float *gpos[2], *gvalue;           // adjoint inputs (NULL: zero)
+    float *gn[3], *gp[3], *gw;               // adjoint outputs (NULL: not wanted)
+    const float *dn[3], *dp[3], *dw;         // tangent inputs (NULL: zero)
+};
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is hf_launch_sky's: the per-lane any-hit walk,
+// no work counter, no scratch block
+void hf_launch_caustic(int mode, const hf_caustic_args &a, hipStream_t stream);
 // ---- environment-map lighting (hf_envmap_*): the one argument of its kernels; data and table are the caller's ----
 struct hf_envmap_args {
     hf_dev_field f;                          // forward only (the walk)

@@ -1519,6 +1519,138 @@ def sky_rays(si, ray, k, seed=0, ray_index=None):
     return r
 
 
+class Receiver:
+    """The plane a caustic lands on (``hf_receiver_t``): the world point ``origin`` at film position (0, 0) and the two
+    orthogonal vectors ``ex``, ``ey`` with film x = <X - origin, ex>, y = <X - origin, ey> in pixels."""
+
+    def __init__(self, origin, ex, ey):
+        self.origin, self.ex, self.ey = (tuple(float(c) for c in v) for v in (origin, ex, ey))
+        assert all(len(v) == 3 for v in (self.origin, self.ex, self.ey)), "origin, ex, ey: three components each"
+
+    @staticmethod
+    def plane_z(z, x_range, y_range, width, height):
+        """the horizontal plane at height ``z`` whose rectangle x_range x y_range is a film of width x height pixels
+        (pixel (0, 0) at the corner (x_range[0], y_range[0]))"""
+        sx, sy = width / (x_range[1] - x_range[0]), height / (y_range[1] - y_range[0])
+        return Receiver((x_range[0], y_range[0], z), (sx, 0.0, 0.0), (0.0, sy, 0.0))
+
+    def _struct(self):
+        return _capi.hf_receiver_t((C.c_float * 3)(*self.origin), (C.c_float * 3)(*self.ex), (C.c_float * 3)(*self.ey))
+
+
+class _CausticLightingOp(torch.autograd.Function):
+    """(pos, value, visibility bytes) of hf_caustic_lighting; backward = hf_caustic_adjoint (gradients of sh_n, p and
+    weight), jvp = hf_caustic_tangent.  Both read the visibility byte the forward saved and trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, sn, pp, gn, dd, tt, vis, ww=None):
+        """what hf_caustic_adjoint / _tangent start with"""
+        eta, power, rcv, act = ctx.misc
+        return (sn.shape[1], C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(act),
+                _ptr(ww), eta, power, C.byref(rcv), vis.data_ptr())
+
+    @staticmethod
+    def forward(ctx, sh_n, p, weight, shape, nrm, d, t, active, eta, power, receiver):
+        sn, pp, gn, dd, tt, ww = map(_detached_f32, (sh_n, p, nrm, d, t, weight))
+        n = sn.shape[1]
+        ctx.misc = (eta, power, receiver._struct(), active)
+        pos = torch.empty((2, n), dtype=torch.float32, device=sn.device)
+        value = torch.empty(n, dtype=torch.float32, device=sn.device)
+        vis = torch.empty(n, dtype=torch.uint8, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_caustic_lighting(shape._h, n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                                  C.byref(_p3(dd)), tt.data_ptr(), _ptr(active), _ptr(ww), eta, power,
+                                                  C.byref(ctx.misc[2]), _ref(_row_ptrs(pos)), value.data_ptr(),
+                                                  vis.data_ptr(), _stream_of(sn.device)))
+        saved = _with_weight(ctx, (sn, pp, gn, dd, tt, vis), ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(vis)
+        return pos, value, vis
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dp, dweight, *_):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
+        dq = _detached_f32(dp)
+        dpos, dvalue = torch.empty((2, sn.shape[1]), dtype=torch.float32, device=sn.device), torch.empty_like(sn[0])
+        if sn.shape[1]:
+            check(_capi.lib().hf_caustic_tangent(*_CausticLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
+                                                 _ref(_row_ptrs(dq)), _ptr(dw), _ref(_row_ptrs(dpos)), dvalue.data_ptr(),
+                                                 _stream_of(sn.device)))
+        return dpos, dvalue, None
+
+    @staticmethod
+    def backward(ctx, grad_pos, grad_value, _grad_vis):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        gq, gv = _detached_f32(grad_pos), _detached_f32(grad_value)
+        gn, gp = torch.empty_like(sn), torch.empty_like(sn)
+        gw = torch.empty_like(sn[0]) if ctx.weighted else None
+        if sn.shape[1]:
+            check(_capi.lib().hf_caustic_adjoint(*_CausticLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(gq)), _ptr(gv),
+                                                 C.byref(_p3(gn)), C.byref(_p3(gp)), _ptr(gw), _stream_of(sn.device)))
+        return (gn, gp, gw) + (None,) * 8
+
+
+def _caustic_active(active, n, device):
+    """``active`` as the [n] uint8 row of the hf_caustic_* entries; True = None: every lane"""
+    if active is True or active is None:
+        return None
+    a = torch.as_tensor(active, device=device)
+    return a.to(dtype=torch.uint8).expand(n).contiguous()
+
+
+def caustic_lighting(shape, si, ray, receiver, eta=1.33, power=1.0, weight=None, active=True, return_visibility=False):
+    """Light tracing through the surface (``hf_caustic_lighting``): every sample of the wavefront is a light sample
+    that arrives along ``ray.d`` at ``si``, is refracted at ``si.sh_frame.n`` with the relative index ``eta`` (as the
+    reference's ``fresnel()`` defines it; the ``dielectric`` BSDF's transmission lobe in importance mode), walked
+    against the same terrain up to the ``receiver`` (a ``Receiver``) and, where nothing is in the way, lands there.
+    Returns ``(pos [2, n], value [n])``: the landing position in the receiver's film coordinates and the flux
+    ``weight * power * (1 - F)``; a sample that deposits nothing has value 0 and pos (-16, -16), outside every film.  With
+    ``return_visibility`` also the [n] uint8 row (1: deposited).  Differentiable with respect to ``si.sh_frame.n``,
+    ``si.p`` and ``weight`` ([n], optional), in reverse and forward mode; the masks and the occlusion are piecewise
+    constant.  Splat the result with ``caustic_film``."""
+    shape._check_ray(ray)
+    n = len(ray)
+    pos, value, vis = _CausticLightingOp.apply(si.sh_frame.n, si.p, weight, shape, si.n, ray.d, si.t,
+                                               _caustic_active(active, n, ray.d.device), float(eta), float(power), receiver)
+    return (pos, value, vis) if return_visibility else (pos, value)
+
+
+def caustic_rays(si, ray, receiver, eta=1.33, active=True):
+    """The refracted ray of every sample of ``caustic_lighting`` as a Ray3f (``hf_caustic_rays``): what the fused kernel
+    walks, bit for bit; ``maxt`` is the distance to the receiver.  Lanes it does not trace (no hit, the normals disagree
+    on the side, total internal reflection, a receiver behind the ray) get ``maxt = -1``, a miss, and a zero ray."""
+    sn, pp, gn, dd, tt = map(_detached_f32, (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n, r = sn.shape[1], _empty_rays(pp)
+    if n:
+        rcv = receiver._struct()
+        check(_capi.lib().hf_caustic_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
+                                          tt.data_ptr(), _ptr(_caustic_active(active, n, pp.device)), float(eta),
+                                          C.byref(rcv), C.byref(_p3(r.o)), C.byref(_p3(r.d)), r.maxt.data_ptr(),
+                                          _stream_of(pp.device)))
+    return r
+
+
+def caustic_filter_mass(stddev=0.5):
+    """The integral of the film's filter over its window, squared: w(x) = exp(-x^2 / (2 stddev^2)) - exp(-8) on
+    |x| <= 4 stddev (src/rfilters/gaussian.cpp), so int w = stddev (sqrt(2 pi) erf(2 sqrt(2)) - 8 exp(-8))."""
+    return (stddev * (math.sqrt(2.0 * math.pi) * math.erf(2.0 * math.sqrt(2.0)) - 8.0 * math.exp(-8.0))) ** 2
+
+
+def caustic_film(pos, value, width, height, stddev=0.5):
+    """The film of a light tracer: the ACCUMULATED image plane of ``hf_film_splat_weighted`` for the samples of
+    ``caustic_lighting``, [height * width] -- a sum, not an average, so it is not divided by the weight plane.  It is
+    divided by the filter's mass ``caustic_filter_mass(stddev)``, a closed-form constant (0.6248 pixel^2 for stddev 0.5),
+    which makes a pixel hold the flux that lands on it: sum(film) = sum(value) for samples well inside the film, to
+    within the lattice ripple of the filter (2 exp(-2 pi^2 stddev^2) per axis and sample: 1.4 % for stddev 0.5).
+    Differentiable with respect to ``pos`` and ``value``."""
+    image, _ = _FilmMotionOp.apply(value[None], pos, None, int(width), int(height), float(stddev))
+    return image[0] / caustic_filter_mass(float(stddev))
+
+
 class _EnvmapEvalOp(torch.autograd.Function):
     """hf_envmap_eval of the map `full` ([H, W], the seam column included) for world directions; linear in the texels:
     backward = hf_envmap_eval_adjoint, jvp = hf_envmap_eval of the texels' tangent."""
