@@ -878,6 +878,73 @@ int hf_envmap_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3
                                const uint32_t *vis_bits, const float *const dsh_n[3], const float *dweight,
                                const float *ddata, float *dimage, hf_stream_t stream);
 
+/* ---- next row: specular reflection of the environment map, the mirror ray traced in the kernel ----
+ *
+ * The rows above end at a Lambertian surface or refract through it.  Here every wavefront sample is MIRRORED at the surface
+ * and sees the environment map: reflect(wi, m) (include/mitsuba/render/fresnel.h:282-284), the reflection lobe of the
+ * `dielectric` BSDF (or of a `conductor` idealised to F = 1: eta = 0) and Emitter::eval of src/emitters/envmap.cpp.  World
+ * space; the map conventions (W, H, data, rot) are hf_envmap_eval's, and nothing is sampled: no table, no seed.
+ *   inputs      p, nrm (the geometric normal g), sh_n (the shading normal m), d: 3 device rows of n floats; t: n floats;
+ *               weight: n floats or NULL (1), the specular reflectance; active: n bytes or NULL (every lane); wi = -d.
+ *   eligible    the sample is active, t_i is finite, c = <m, wi> > 0 and <g, wi> > 0;
+ *   Fresnel     F = fresnel(c, eta)[0] (fresnel.h:35-71) operation for operation in float32, as hf_caustic_lighting has
+ *               it; eta == 0 is the ideal mirror: F = 1, F' = 0;
+ *   direction   wr = fmsub(m, 2 c, wi) in float32;
+ *   consistent  <g, wr> > 0: a reflected ray that would start below the true surface is not traced and contributes 0;
+ *   traced      = eligible and consistent;
+ *   ray         SurfaceInteraction::spawn_ray(wr) exactly as hf_sky_rays builds it, maxt = +inf, any-hit walk;
+ *   visible     vis[i] = 1 iff the sample is traced and the walk finds nothing;
+ *   radiance    L = hf_envmap_eval's value for the direction wr (the same lookup, in double, rounded once);
+ *   value       value_i = (weight_i F) L in float32 where vis = 1, exactly 0 for every other sample;
+ *   image       image[i / spp] = 1/spp sum value_i: the box film of the rows above, overwritten; n a multiple of spp.
+ * A reflected ray that hits the terrain contributes 0: a second specular or diffuse vertex is OUT OF SCOPE.
+ * Differentiated with respect to sh_n, weight and data; the masks, the visibility, the cell of the lookup and rot are held
+ * (the silhouette term belongs to hf_reparam_*).  With v = R^T wr, the cell's fractions (fx, fy), texels v00 .. v11 and
+ * bilinear weights b_j:
+ *   Lx = (1 - fy)(v10 - v00) + fy (v11 - v01),   Ly = (1 - fx)(v01 - v00) + fx (v11 - v10),
+ *   s2 = vx^2 + vz^2,   q = 1 - vy^2,
+ *   dL/dv = Lx (W - 1) / (2 pi) (-vz, 0, vx) / s2 + Ly (H - 1) / pi (0, -1 / sqrt(q), 0),   G = R dL/dv,
+ *   d wr = 2 (d m c + m <d m, wi>),   F' = a_s a_s' + a_p a_p' (hf_caustic_lighting's; 0 where F = 1 by total reflection),
+ *   d value     = d weight F L + weight (F' <d m, wi> L + F <G, d wr>) + weight F sum_j b_j d data_j,
+ *   grad_sh_n   = g weight (F' L wi + 2 F (c G + <m, G> wi)),   grad_weight = g F L,   grad_data[j] += g weight F b_j.
+ * At the poles of the map (s2 < 1e-12 or q < 1e-12) G is EXACTLY ZERO.  G is formed in double from the same lookup and
+ * rounded once.
+ * All four entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional,
+ * n >= 2^32, spp == 0 or n % spp != 0, W < 2 or H < 2, a negative or non-finite eta, a non-finite rot (rot NULL: the
+ * identity).  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+/* materialises the reflected ray of every sample (out_o, out_d: 3 rows of n floats; out_maxt: n floats, +inf for a traced
+ * lane; every other lane gets -1 -- a miss -- and a zero origin and direction, as hf_caustic_rays does): the two-call
+ * sequence hf_reflect_rays + hf_ray_test that hf_reflect_lighting equals bit for bit.  Takes no field handle. */
+int hf_reflect_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                    const float *const d[3], const float *t, const uint8_t *active, float *const out_o[3],
+                    float *const out_d[3], float *out_maxt, hf_stream_t stream);
+/* The fused launch (hf_sky_lighting's mapping: one lane per sample, one workgroup per 256 samples, no work counter):
+ * reads a sample's record once, reflects, runs the per-lane any-hit walk, looks the map up and writes image (n / spp
+ * floats), value (n floats) and vis (n bytes); each may be NULL (not wanted), but not all three.  No ray goes to memory.
+ * A batch of 64 samples without a traced lane skips the walk.  hf_set_ray_coherence is neither read nor changed.
+ * Allocates nothing, never synchronises the host, capturable. */
+int hf_reflect_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                        const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                        const float *weight, float eta, uint32_t W, uint32_t H, const float *data, const float rot[9],
+                        float *image, float *value, uint8_t *vis, hf_stream_t stream);
+/* Reverse mode.  Traces nothing: the vertex is formed again and vis (as hf_reflect_lighting wrote it) is read.  The
+ * upstream of sample i is g = grad_image[i / spp] / spp + grad_value[i]; either may be NULL (zero).  grad_sh_n (3 rows)
+ * and grad_weight are overwritten, exact zeros where vis = 0, one lane per sample, no atomics: bitwise the same from
+ * launch to launch; grad_data ([H][W]) is ACCUMULATED with float atomics.  Any of the three may be NULL (not wanted).
+ * Takes no field handle. */
+int hf_reflect_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                                const uint8_t *active, const float *weight, float eta, uint32_t W, uint32_t H,
+                                const float *data, const float rot[9], const uint8_t *vis, const float *grad_image,
+                                const float *grad_value, float *const grad_sh_n[3], float *grad_weight, float *grad_data,
+                                hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dsh_n (3 rows), dweight (n) and ddata ([H][W]), each may
+ * be NULL (zero); dimage (n / spp) and dvalue (n) are overwritten, either may be NULL (not wanted), not both.  No atomics
+ * for any spp (the film tree of the rows above, or one lane per pixel). */
+int hf_reflect_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                                const uint8_t *active, const float *weight, float eta, uint32_t W, uint32_t H,
+                                const float *data, const float rot[9], const uint8_t *vis, const float *const dsh_n[3],
+                                const float *dweight, const float *ddata, float *dimage, float *dvalue, hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional

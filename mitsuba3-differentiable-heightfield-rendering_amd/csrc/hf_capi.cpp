@@ -1482,6 +1482,102 @@ extern "C" int hf_envmap_lighting_tangent(size_t n, uint32_t spp, const float *c
     return light_launch(hf_launch_envmap, 2, a, stream);
 }
 
+// ---- specular reflection of the environment map: the mirror ray walked in the kernel, the map looked up ----
+// What the hf_reflect_* entries share: the wavefront rows (`a` is zeroed here) ...
+static int reflect_rows(const char *who, size_t n, const float *const sh_n[3], const float *const d[3], const float *t,
+                        const uint8_t *active, hf_reflect_args &a) {
+    a = {};
+    if (!all3(sh_n) || !all3(d) || !t) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    a.n = n; a.spp = 1; a.t = t; a.active = active;
+    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
+    return HF_OK;
+}
+// ... and the film, the interface and the map of the three lighting entries
+static int reflect_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                        const float *t, const uint8_t *active, const float *weight, float eta, uint32_t W, uint32_t H,
+                        const float *data, const float rot[9], hf_reflect_args &a) {
+    const int rc = reflect_rows(who, n, sh_n, d, t, active, a);
+    if (rc != HF_OK) return rc;
+    if (!data) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the map must have at least 2 x 2 texels (got %u x %u)", who, W, H);
+    if (!isfinite(eta) || eta < 0.f) return fail(HF_EINVAL, "%s: eta must be finite and not negative (got %g)", who, (double) eta);
+    a.spp = spp; a.weight = weight; a.W = W; a.H = H; a.data = data;
+    a.eta = eta; a.rcp_eta = eta > 0.f ? 1.f / eta : 0.f;
+    for (int j = 0; j < 9; ++j) {
+        a.rot[j] = rot ? rot[j] : (j % 4 == 0 ? 1.f : 0.f);
+        if (!isfinite(a.rot[j])) return fail(HF_EINVAL, "%s: rot must be finite", who);
+    }
+    return HF_OK;
+}
+
+extern "C" int hf_reflect_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                               const float *const d[3], const float *t, const uint8_t *active, float *const out_o[3],
+                               float *const out_d[3], float *out_maxt, hf_stream_t stream) {
+    const char *fn = "hf_reflect_rays";
+    hf_reflect_args a;
+    const int rc = reflect_rows(fn, n, sh_n, d, t, active, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.eta = 1.f; a.rcp_eta = 1.f; // (the direction does not depend on the interface)
+    a.out_maxt = out_maxt;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
+    return light_launch(hf_launch_reflect, 3, a, stream);
+}
+
+extern "C" int hf_reflect_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                   const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                   const float *t, const uint8_t *active, const float *weight, float eta, uint32_t W,
+                                   uint32_t H, const float *data, const float rot[9], float *image, float *value,
+                                   uint8_t *vis, hf_stream_t stream) {
+    const char *fn = "hf_reflect_lighting";
+    hf_reflect_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm)) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!image && !value && !vis) return fail(HF_EINVAL, "%s: image, value and vis are all NULL", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = image; a.value = value; a.vis = vis;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    return light_launch(hf_launch_reflect, 0, a, stream);
+}
+
+extern "C" int hf_reflect_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                           const float *t, const uint8_t *active, const float *weight, float eta,
+                                           uint32_t W, uint32_t H, const float *data, const float rot[9], const uint8_t *vis,
+                                           const float *grad_image, const float *grad_value, float *const grad_sh_n[3],
+                                           float *grad_weight, float *grad_data, hf_stream_t stream) {
+    const char *fn = "hf_reflect_lighting_adjoint";
+    hf_reflect_args a;
+    const int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
+    a.vis = const_cast<uint8_t *>(vis); a.gimg = grad_image; a.gvalue = grad_value; a.gw = grad_weight; a.gdata = grad_data;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    return light_launch(hf_launch_reflect, 1, a, stream);
+}
+
+extern "C" int hf_reflect_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                           const float *t, const uint8_t *active, const float *weight, float eta,
+                                           uint32_t W, uint32_t H, const float *data, const float rot[9], const uint8_t *vis,
+                                           const float *const dsh_n[3], const float *dweight, const float *ddata,
+                                           float *dimage, float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_reflect_lighting_tangent";
+    hf_reflect_args a;
+    const int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
+    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
+    a.vis = const_cast<uint8_t *>(vis); a.dw = dweight; a.ddata = ddata; a.image = dimage; a.value = dvalue;
+    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    return light_launch(hf_launch_reflect, 2, a, stream);
+}
+
 // ---- bounce lighting: one diffuse interreflection, both rays traced inside the lighting kernel ----
 // What the four hf_bounce_* entries share.  hf_bounce_rays passes spp 1, num_rays k + 1, albedo 1 and either no light or its one direction.
 static int bounce_args(const char *who, const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],

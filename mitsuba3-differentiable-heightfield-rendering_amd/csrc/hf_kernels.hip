@@ -5630,8 +5630,10 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_sample_kernel(hf_envmap_ar
 
 // Emitter::eval (envmap.cpp:323-333, 498-509): the cell of a world direction and the position in it.  In double: a bilinear
 // weight is then exact to its last float32 bit, which is what the summation bound of the adjoint's atomics rests on
-__device__ __forceinline__ void env_lookup(const hf_envmap_args &a, v3 d, uint32_t &cx, uint32_t &cy, double &fx, double &fy) {
-    const float *R = a.rot; // v = R^T d
+// (A: hf_envmap_args, or the reflection row's block, which has the same W, H and rot)
+template <class A>
+__device__ __forceinline__ void env_lookup(const A &a, v3 d, uint32_t &cx, uint32_t &cy, double &fx, double &fy) {
+    const auto *R = a.rot; // v = R^T d
     const double vx = (double) R[0] * d.x + (double) R[3] * d.y + (double) R[6] * d.z;
     const double vy = (double) R[1] * d.x + (double) R[4] * d.y + (double) R[7] * d.z;
     const double vz = (double) R[2] * d.x + (double) R[5] * d.y + (double) R[8] * d.z;
@@ -5754,6 +5756,249 @@ void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream) {
         hipLaunchKernelGGL(mode == 4 ? hf_envmap_sample_kernel : mode == 5 ? hf_envmap_eval_kernel<false> : hf_envmap_eval_kernel<true>,
                            grid, block, 0, stream, a);
     }
+}
+
+// ---------------------------------------------------------------------------------
+// Specular reflection of the environment map (include/hf.h hf_reflect_*): every wavefront sample is mirrored at its
+// shading normal (reflect(wi, m), fresnel.h:282-284; the `dielectric` reflection lobe, or an ideal mirror for eta = 0),
+// the reflected ray is walked (any hit, per lane, maxt = +inf) and what escapes looks the map up (Emitter::eval of
+// envmap.cpp, env_lookup above, in double).  ONE launch, one lane per sample; nothing of the ray goes to memory.  A
+// reflected ray that hits the terrain contributes 0: no second vertex.
+// ---------------------------------------------------------------------------------
+// The specular vertex of one sample, the same text for the fused kernel, the rays kernel and the two derivatives:
+// fresnel() as caustic_vertex has it (c > 0 on every lane that is used: the outside branch) and reflect().
+//   dF = d F / d c (a_s a_s' + a_p a_p'; 0 for eta = 0, eta = 1 and under total internal reflection, where F = 1)
+struct hf_reflect_vertex {
+    v3 wi, wr;
+    float c, F, dF;
+};
+template <class P>
+__device__ __forceinline__ hf_reflect_vertex reflect_vertex(P a, v3 m, v3 d) {
+    hf_reflect_vertex v;
+    v.wi = mk3(-d.x, -d.y, -d.z);
+    const float ci = dot3(m, v.wi);
+    v.c = ci;
+    const float eta = a->eta, rcp_eta = a->rcp_eta;
+    const bool outside = ci >= 0.f;
+    const float eta_it = outside ? eta : rcp_eta, eta_ti = outside ? rcp_eta : eta;
+    const float e2 = eta_ti * eta_ti;
+    const float ct2 = __builtin_fmaf(-__builtin_fmaf(-ci, ci, 1.f), e2, 1.f);
+    const float cia = __builtin_fabsf(ci), cta = __builtin_sqrtf(fmaxf(ct2, 0.f));
+    const float ns = __builtin_fmaf(-eta_it, cta, cia), ds = __builtin_fmaf(eta_it, cta, cia);
+    const float np = __builtin_fmaf(-eta_it, cia, cta), dp = __builtin_fmaf(eta_it, cia, cta);
+    const float a_s = ns / ds, a_p = np / dp;
+    const bool mirror = eta == 0.f, matched = eta == 1.f;
+    v.F = mirror ? 1.f : matched ? 0.f : 0.5f * (a_s * a_s + a_p * a_p);
+    const float sg = outside ? 1.f : -1.f, dcta = ci * e2 / cta;
+    const float das = 2.f * ((eta_it * cta) * sg - cia * (eta_it * dcta)) / (ds * ds);
+    const float dap = 2.f * ((eta_it * cia) * dcta - cta * (eta_it * sg)) / (dp * dp);
+    v.dF = (mirror || matched || !(ct2 > 0.f)) ? 0.f : a_s * das + a_p * dap;
+    const float c2 = 2.f * ci; // reflect(wi, m) = fmsub(m, 2 <wi, m>, wi)
+    v.wr = mk3(__builtin_fmaf(m.x, c2, -v.wi.x), __builtin_fmaf(m.y, c2, -v.wi.y), __builtin_fmaf(m.z, c2, -v.wi.z));
+    return v;
+}
+// eligible (active, a finite t, both normals face the viewer) and consistent (the mirror ray leaves the true surface)
+__device__ __forceinline__ bool reflect_traced(const hf_reflect_vertex &v, v3 g, float t, bool act) {
+    return act && (__builtin_fabsf(t) < __builtin_inff()) && (v.c > 0.f) && (dot3(g, v.wi) > 0.f) && (dot3(g, v.wr) > 0.f);
+}
+// the vertex of sample i from the rows
+template <class P>
+__device__ __forceinline__ hf_reflect_vertex reflect_sample(P a, size_t i, v3 &m) {
+    m = mk3(a->sh_n[0][i], a->sh_n[1][i], a->sh_n[2][i]);
+    return reflect_vertex(a, m, mk3(a->d[0][i], a->d[1][i], a->d[2][i]));
+}
+// Emitter::eval for the direction w: hf_envmap_eval_kernel's expression, rounded once
+template <class A>
+__device__ __forceinline__ float reflect_radiance(const A &a, const float *data, v3 w) {
+    uint32_t cx, cy;
+    double fx, fy;
+    env_lookup(a, w, cx, cy, fx, fy);
+    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
+    const double gx = 1.0 - fx, gy = 1.0 - fy;
+    return (float) (gy * (gx * (double) data[r0] + fx * (double) data[r0 + 1]) + fy * (gx * (double) data[r1] + fx * (double) data[r1 + 1]));
+}
+// what the derivative kernels need of the lookup: the radiance, the bilinear weights, the first texel's index and
+// G = R dL/dv, the derivative of the radiance with respect to the world direction with the cell held (exactly 0 at
+// the poles of the map); formed in double from the same lookup, each rounded once
+struct hf_reflect_shade { float L; v3 G; double bw[4]; size_t r0; };
+__device__ __forceinline__ hf_reflect_shade reflect_shade(const hf_reflect_args &a, v3 w) {
+    hf_reflect_shade s;
+    uint32_t cx, cy;
+    double fx, fy;
+    env_lookup(a, w, cx, cy, fx, fy);
+    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
+    const double gx = 1.0 - fx, gy = 1.0 - fy;
+    const double v00 = (double) a.data[r0], v10 = (double) a.data[r0 + 1], v01 = (double) a.data[r1], v11 = (double) a.data[r1 + 1];
+    s.L = (float) (gy * (gx * v00 + fx * v10) + fy * (gx * v01 + fx * v11));
+    s.bw[0] = gy * gx; s.bw[1] = gy * fx; s.bw[2] = fy * gx; s.bw[3] = fy * fx;
+    s.r0 = r0;
+    const float *R = a.rot;
+    const double vx = (double) R[0] * w.x + (double) R[3] * w.y + (double) R[6] * w.z;
+    const double vy = (double) R[1] * w.x + (double) R[4] * w.y + (double) R[7] * w.z;
+    const double vz = (double) R[2] * w.x + (double) R[5] * w.y + (double) R[8] * w.z;
+    const double s2 = vx * vx + vz * vz, q = 1.0 - vy * vy;
+    double lx = 0.0, ly = 0.0, lz = 0.0;
+    if (!(s2 < 1e-12) && !(q < 1e-12)) {
+        const double Lx = gy * (v10 - v00) + fy * (v11 - v01), Ly = gx * (v01 - v00) + fx * (v11 - v10);
+        const double kx = Lx * (double) (a.W - 1u) / 6.283185307179586 / s2;
+        lx = -(kx * vz); lz = kx * vx;
+        ly = -(Ly * (double) (a.H - 1u) / 3.141592653589793 / sqrt(q));
+    }
+    s.G = mk3((float) ((double) R[0] * lx + (double) R[1] * ly + (double) R[2] * lz),
+              (float) ((double) R[3] * lx + (double) R[4] * ly + (double) R[5] * lz),
+              (float) ((double) R[6] * lx + (double) R[7] * ly + (double) R[8] * lz));
+    return s;
+}
+
+typedef const __attribute__((address_space(4))) hf_reflect_args *hf_reflect_kargs;
+
+#ifndef HF_REFLECT_WAVES
+#define HF_REFLECT_WAVES 6 // resident waves per SIMD (the siblings')
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_REFLECT_WAVES) void hf_reflect_kernel(hf_reflect_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    hf_reflect_kargs ka = (hf_reflect_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    v3 wr;
+    float F;
+    bool traced;
+    hf_hit best;
+    best.hit = false;
+    {
+        v3 m;
+        const hf_reflect_vertex v = reflect_sample(ka, ii, m);
+        const v3 gn = mk3(ka->nrm[0][ii], ka->nrm[1][ii], ka->nrm[2][ii]);
+        const uint8_t *active = ka->active;
+        traced = reflect_traced(v, gn, ka->t[ii], in && (active ? active[ii] != 0 : true));
+        wr = v.wr; F = v.F;
+        if (__ballot(traced) != 0ull) { // wave-uniform: a batch without a traced sample walks nothing
+            const v3 p = mk3(ka->p[0][ii], ka->p[1][ii], ka->p[2][ii]);
+            // the direction, F and the index are held across the walk
+            light_walk<true>(&ka->f, f, sky_origin(p, gn, sky_offset(p), wr), wr, traced, best);
+        }
+    }
+    // (the map and the output pointers: loaded here, not before the walk; the lookup in double runs when the walk's
+    // state is dead)
+    hf_reflect_kargs ko = (hf_reflect_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    const bool lit = traced && !best.hit; // (traced: in range)
+    float val = 0.f;
+    if (lit) {
+        const float *weight = ko->weight;
+        const float L = reflect_radiance(*ko, ko->data, wr);
+        val = (weight ? weight[i] * F : F) * L;
+    }
+    if (in) {
+        float *value = ko->value;
+        uint8_t *vis = ko->vis;
+        if (value) value[i] = val;
+        if (vis) vis[i] = lit ? 1 : 0;
+    }
+    float *image = ko->image;
+    if (image) {
+        const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+        film_pixel(image, val, 0u, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+    }
+}
+
+// the reflected ray of every sample, materialised: what hf_reflect_kernel walks, bit for bit (maxt = -1 and a zero
+// origin and direction: the fused kernel does not trace the lane)
+__global__ __launch_bounds__(HF_BLOCK) void hf_reflect_rays_kernel(hf_reflect_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 m;
+    const hf_reflect_vertex v = reflect_sample(&a, i, m);
+    const v3 gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+    const bool traced = reflect_traced(v, gn, a.t[i], a.active ? a.active[i] != 0 : true);
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    light_store_ray(a, i, traced ? sky_origin(p, gn, sky_offset(p), v.wr) : z, traced ? v.wr : z, traced);
+}
+
+// Reverse mode of hf_reflect_kernel with respect to sh_n, weight and the texels: nothing is traced, the vertex is
+// formed again and the visibility byte read.  grad_sh_n, grad_weight: one lane per sample, overwritten, no atomics;
+// grad_data: one float atomic per texel of every visible sample
+__global__ __launch_bounds__(HF_BLOCK) void hf_reflect_adjoint_kernel(hf_reflect_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 gm = mk3(0.f, 0.f, 0.f);
+    float gw = 0.f;
+    if (a.vis[i]) {
+        v3 m;
+        const hf_reflect_vertex v = reflect_sample(&a, i, m);
+        const hf_reflect_shade s = reflect_shade(a, v.wr);
+        const float g = (a.gimg ? a.gimg[i / a.spp] * (1.0f / (float) a.spp) : 0.f) + (a.gvalue ? a.gvalue[i] : 0.f);
+        const float gwt = a.weight ? g * a.weight[i] : g;
+        gw = g * (v.F * s.L);
+        const float k = __builtin_fmaf(v.dF, s.L, (2.f * v.F) * dot3(m, s.G));
+        gm = fma3(v.wi, k, s.G * ((2.f * v.F) * v.c)) * gwt;
+        if (a.gdata) {
+            const double q = (double) (gwt * v.F);
+            atomicAdd(a.gdata + s.r0, (float) (q * s.bw[0])); atomicAdd(a.gdata + s.r0 + 1, (float) (q * s.bw[1]));
+            atomicAdd(a.gdata + s.r0 + a.W, (float) (q * s.bw[2])); atomicAdd(a.gdata + s.r0 + a.W + 1, (float) (q * s.bw[3]));
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        if (a.gn[c]) a.gn[c][i] = c == 0 ? gm.x : c == 1 ? gm.y : gm.z;
+    if (a.gw) a.gw[i] = gw;
+}
+
+// forward mode, the transpose of the above: the tangent of sample i's value for tangents dn of sh_n, dw of weight and
+// ddata of the texels (NULL: zero)
+__device__ __forceinline__ float reflect_tangent_value(const hf_reflect_args &a, size_t i) {
+    if (!a.vis[i]) return 0.f;
+    v3 m;
+    const hf_reflect_vertex v = reflect_sample(&a, i, m);
+    const hf_reflect_shade s = reflect_shade(a, v.wr);
+    const v3 dm = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const float w = a.weight ? a.weight[i] : 1.f, dw = a.dw ? a.dw[i] : 0.f;
+    const float dci = dot3(dm, v.wi);
+    const float k = __builtin_fmaf(v.dF, s.L, (2.f * v.F) * dot3(m, s.G));
+    float dv = __builtin_fmaf(k, dci, ((2.f * v.F) * v.c) * dot3(s.G, dm));
+    if (a.ddata)
+        dv += v.F * (float) (s.bw[0] * (double) a.ddata[s.r0] + s.bw[1] * (double) a.ddata[s.r0 + 1] +
+                             s.bw[2] * (double) a.ddata[s.r0 + a.W] + s.bw[3] * (double) a.ddata[s.r0 + a.W + 1]);
+    return __builtin_fmaf(dw, v.F * s.L, w * dv);
+}
+// PIXEL = false: one lane per sample and the primal's film (spp a power of two <= 64, or no image wanted); PIXEL = true
+// (any other spp): one lane per pixel adds its samples in order -- no atomics either way (light_tangent_image, with
+// the per-sample tangent written too)
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_reflect_tangent_kernel(hf_reflect_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    if (PIXEL) {
+        if (i >= a.n / spp) return;
+        float c = 0.f;
+        for (uint32_t s = 0; s < spp; ++s) {
+            const float dv = reflect_tangent_value(a, i * spp + s);
+            if (a.value) a.value[i * spp + s] = dv;
+            c += dv;
+        }
+        a.image[i] = c * (1.0f / (float) spp);
+    } else {
+        const bool in = i < a.n;
+        const float c = in ? reflect_tangent_value(a, i) : 0.f;
+        if (in && a.value) a.value[i] = c;
+        if (a.image) film_pixel(a.image, c, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
+    }
+}
+
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays (launch_light, with an image that may be NULL)
+void hf_launch_reflect(int mode, const hf_reflect_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const bool tree = sky_tree_film(a.spp) || !a.image;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    if (mode == 0 && !tree) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths
+    if (mode == 2 && !tree)
+        hipLaunchKernelGGL(hf_reflect_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(mode == 0 ? hf_reflect_kernel : mode == 1 ? hf_reflect_adjoint_kernel
+                           : mode == 2 ? hf_reflect_tangent_kernel<false> : hf_reflect_rays_kernel, grid, block, 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------

@@ -128,6 +128,28 @@ struct hf_envmap_args {
 // mode 0: forward, 1: adjoint, 2: tangent, 3: rays, 4: sample_direction, 5: eval, 6: eval_adjoint.  The forward launch
 // is hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
 void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream);
+// ---- specular reflection of the environment map (hf_reflect_rays, hf_reflect_lighting / _adjoint / _tangent): the one
+// argument of its four kernels; W, H, rot as in hf_envmap_args (env_lookup reads either) ----
+struct hf_reflect_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, W, H;
+    float eta, rcp_eta;                      // rcp_eta = 1 / eta, rounded once on the host (0 for the mirror, eta = 0)
+    float rot[9];                            // row-major rotation, map space -> world (identity for NULL)
+    const float *data;                       // [H][W] radiance
+    const float *p[3], *nrm[3];              // si.p, si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight;
+    const uint8_t *active;                   // optional (NULL: every lane)
+    float *image, *value;                    // forward: written (NULL: not wanted); tangent: dimage, dvalue
+    uint8_t *vis;                            // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    const float *gimg, *gvalue;              // adjoint inputs (NULL: zero)
+    float *gn[3], *gw, *gdata;               // adjoint outputs (NULL: not wanted); gdata is accumulated
+    const float *dn[3], *dw, *ddata;         // tangent inputs (NULL: zero)
+};
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is hf_launch_sky's: the per-lane any-hit walk,
+// no work counter, no scratch block
+void hf_launch_reflect(int mode, const hf_reflect_args &a, hipStream_t stream);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----

@@ -1880,6 +1880,96 @@ def envmap_rays(si, ray, envmap, k, seed=0, ray_index=None, return_weight=False)
     return (r, wgt) if return_weight else r
 
 
+class _ReflectionLightingOp(torch.autograd.Function):
+    """(image, per-sample value, visibility bytes) of hf_reflect_lighting; backward = hf_reflect_lighting_adjoint (gradients
+    of sh_n, weight and the texels), jvp = hf_reflect_lighting_tangent.  Both read the visibility byte the forward saved
+    and trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, sn, dd, tt, vis, dat, ww=None):
+        """what hf_reflect_lighting_adjoint / _tangent start with"""
+        spp, eta, rot, act = ctx.misc
+        return (sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(act), _ptr(ww), eta, dat.shape[1],
+                dat.shape[0], dat.data_ptr(), C.byref(rot), vis.data_ptr())
+
+    @staticmethod
+    def forward(ctx, sh_n, weight, full, shape, p, nrm, d, t, active, rot, eta, spp):
+        sn, pp, gn, dd, tt, ww, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, full))
+        n = sn.shape[1]
+        ctx.misc = (spp, eta, rot, active)
+        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
+        value = torch.empty(n, dtype=torch.float32, device=sn.device)
+        vis = torch.empty(n, dtype=torch.uint8, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_reflect_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                                  C.byref(_p3(dd)), tt.data_ptr(), _ptr(active), _ptr(ww), eta, dat.shape[1],
+                                                  dat.shape[0], dat.data_ptr(), C.byref(rot), image.data_ptr(),
+                                                  value.data_ptr(), vis.data_ptr(), _stream_of(sn.device)))
+        saved = _with_weight(ctx, (sn, dd, tt, vis, dat), ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(vis)
+        return image, value, vis
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dweight, dfull, *_):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
+        df = dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
+        dimage = torch.empty(sn.shape[1] // max(ctx.misc[0], 1), dtype=torch.float32, device=sn.device)
+        dvalue = torch.empty_like(sn[0])
+        if sn.shape[1]:
+            check(_capi.lib().hf_reflect_lighting_tangent(*_ReflectionLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
+                                                          _ptr(dw), _ptr(df), dimage.data_ptr(), dvalue.data_ptr(),
+                                                          _stream_of(sn.device)))
+        return dimage, dvalue, None
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_value, _grad_vis):
+        saved = ctx.saved_tensors
+        sn, dat = saved[0], saved[4]
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
+        gv = _detached_f32(grad_value)
+        gd = torch.zeros_like(dat) if ctx.needs_input_grad[2] else None
+        if sn.shape[1]:
+            check(_capi.lib().hf_reflect_lighting_adjoint(*_ReflectionLightingOp._prefix(ctx, *saved), _ptr(gi), _ptr(gv),
+                                                          C.byref(_p3(gn)), _ptr(gw), _ptr(gd), _stream_of(sn.device)))
+        return (gn, gw, gd) + (None,) * 9
+
+
+def reflection_lighting(shape, si, ray, envmap, eta=0.0, spp=1, weight=None, active=True, return_value=False,
+                        return_visibility=False):
+    """Specular reflection of an environment map (``Envmap``) + box-filter film, the mirror ray traced inside the lighting
+    kernel (``hf_reflect_lighting``): every sample is reflected at ``si.sh_frame.n`` (``reflect(wi, m)``), the ray
+    ``si.spawn_ray(wr)`` is walked against the terrain and, where it escapes, the sample's value is ``weight * F *
+    envmap.eval(wr)`` with ``F`` the Fresnel reflectance of the relative index ``eta`` (``fresnel()``; ``eta = 0``: an ideal
+    mirror, F = 1).  A reflected ray that hits the terrain contributes 0 (no second vertex).  Returns the [n // spp] image;
+    with ``return_value`` also the [n] per-sample values (what ``film_gaussian(..., weight=)`` consumes) and with
+    ``return_visibility`` the [n] uint8 row (1: the mirror ray escapes).  Differentiable with respect to
+    ``si.sh_frame.n``, ``weight`` ([n], optional: the specular reflectance) and ``envmap.data``, in reverse and forward
+    mode; the masks, the visibility and the cell of the lookup are piecewise constant."""
+    shape._check_ray(ray)
+    image, value, vis = _ReflectionLightingOp.apply(si.sh_frame.n, weight, envmap.full(), shape, si.p, si.n, ray.d, si.t,
+                                                    _caustic_active(active, len(ray), ray.d.device), envmap._rot, float(eta),
+                                                    int(spp))
+    out = (image,) + ((value,) if return_value else ()) + ((vis,) if return_visibility else ())
+    return out if len(out) > 1 else image
+
+
+def reflection_rays(si, ray, active=True):
+    """The reflected ray of every sample of ``reflection_lighting`` as a Ray3f (``hf_reflect_rays``): what the fused
+    kernel walks, bit for bit.  Lanes it does not trace (no hit, seen from behind, a mirror direction below the true
+    surface) get ``maxt = -1``, a miss, and a zero ray."""
+    sn, pp, gn, dd, tt = map(_detached_f32, (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n, r = sn.shape[1], _empty_rays(pp)
+    if n:
+        check(_capi.lib().hf_reflect_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
+                                          tt.data_ptr(), _ptr(_caustic_active(active, n, pp.device)), C.byref(_p3(r.o)),
+                                          C.byref(_p3(r.d)), r.maxt.data_ptr(), _stream_of(pp.device)))
+    return r
+
+
 class _BounceLightingOp(torch.autograd.Function):
     """(image, hit_prim, lit_bits) of hf_bounce_lighting; backward = hf_bounce_lighting_adjoint (gradients of sh_n, weight
     and the heights), jvp = hf_bounce_lighting_tangent.  Both read the record the forward saved and trace nothing."""
