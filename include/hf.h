@@ -945,6 +945,104 @@ int hf_reflect_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[
                                 const float *data, const float rot[9], const uint8_t *vis, const float *const dsh_n[3],
                                 const float *dweight, const float *ddata, float *dimage, float *dvalue, hf_stream_t stream);
 
+/* ---- next row: glossy reflection of the environment map, a GGX lobe with a learnable roughness ----
+ *
+ * Between the Lambertian rows and the perfectly smooth interface of hf_reflect_*: the reflection lobe of `roughconductor`
+ * / `roughdielectric` (roughconductor.cpp:242-268) with an isotropic GGX MicrofacetDistribution sampled by its visible
+ * normals (include/mitsuba/render/microfacet.h).  Every wavefront sample draws K = num_rays microfacet normals, mirrors
+ * wi at each, walks the K mirror rays inside one kernel and looks the map up where they escape.  World space; the map
+ * conventions (W, H, data, rot) are hf_envmap_eval's; the sample stream is hf_sky_*'s TEA stream with pair = k and
+ * id = i or ray_id[i]; no table is used.
+ *   inputs      p, nrm (the geometric normal g), sh_n (the shading normal n), d: 3 device rows of n floats; t: n floats;
+ *               weight: n floats or NULL (1), the specular reflectance; active: n bytes or NULL (every lane);
+ *               alpha: n floats, the isotropic GGX roughness of every sample; wi = -d.
+ *   roughness   a = max(alpha_i, 1e-4) (configure(), microfacet.h:426); a non-finite alpha_i makes the sample ineligible;
+ *   eligible    the sample is active, t_i is finite, alpha_i is finite, c_i = <n, wi> > 0 and <g, wi> > 0;
+ *   draw k      in float32, one rounding per operation, the same device function in every kernel of the row:
+ *               (s, t) = coordinate_system(n);  wi_l = (<wi, s>, <wi, t>, <wi, n>);
+ *               the visible-normal branch of MicrofacetDistribution::sample (microfacet.h:297-319):
+ *                 wi_p = normalize(a wi_l.x, a wi_l.y, wi_l.z)  (v * (1 / sqrt(<v, v>)));
+ *                 (sin_phi, cos_phi) = Frame3f::sincos_phi(wi_p) (frame.h:111-122): (0, 1) where fma(x, x, y y) <= 2^-22;
+ *                 the GGX branch of sample_visible_11(wi_p.z, .) (microfacet.h:405-420) on the concentric disk point
+ *                 (px, py) of hf_bounce_*'s draw for the TEA sample: s = (1 + wi_p.z) / 2,
+ *                 y = lerp(safe_sqrt(1 - px^2), py, s), x = px, z = safe_sqrt(1 - (x^2 + y^2)),
+ *                 sin_i = safe_sqrt(1 - wi_p.z^2), norm = 1 / fma(sin_i, y, wi_p.z z),
+ *                 slope = (fmsub(wi_p.z, y, sin_i z), x) norm;
+ *                 slope = (fmsub(cos_phi, slope.x, sin_phi slope.y) a, fmadd(sin_phi, slope.x, cos_phi slope.y) a);
+ *                 h_l = normalize(-slope.x, -slope.y, 1);
+ *               h = Frame(n).to_world(h_l) = fma(n, h_l.z, fma(t, h_l.y, s h_l.x));
+ *   valid       every component of h is finite and <wi, h> > 0;
+ *   direction   wo = fmsub(h, 2 <wi, h>, wi) in float32 (hf_reflect_lighting's expression with h for the normal);
+ *   traced      direction k is traced iff the sample is eligible, the draw is valid, c_o = <n, wo> > 0 and <g, wo> > 0;
+ *   ray         SurfaceInteraction::spawn_ray(wo) exactly as hf_sky_rays builds it, maxt = +inf, any-hit walk;
+ *   visible     bit k of vis_bits[i] is set iff direction k is traced and the walk finds nothing;
+ *   Fresnel     F_k = fresnel(<wi, h>, eta)[0] in hf_reflect_lighting's arithmetic; eta == 0: F = 1;
+ *   Smith term  frame-free; smith_g1 (microfacet.h:341-365) for unit vectors and an isotropic lobe:
+ *               T(c) = a^2 max(fnmadd(c, c, 1), 0) / (c c),   G1(c) = 2 / (1 + sqrt(1 + T));
+ *   radiance    L_k = hf_envmap_eval's value for the direction wo_k (in double, rounded once);
+ *   value       value_i = weight_i / K sum_k bit_ik (F_k G1(c_o,k)) L_k, summed in k order in float32: the weight of a
+ *               visible-normal sample (roughconductor.cpp:262) times the radiance; exactly 0 for a sample without a bit;
+ *   image       image[i / spp] = 1/spp sum value_i: the box film of the rows above, overwritten; n a multiple of spp.
+ * OUT OF SCOPE: a reflected ray that hits the terrain contributes 0 (no second vertex, as DESIGN 4.19); anisotropy;
+ * the Beckmann distribution; a complex index of refraction (weight carries the reflectance); the transmission lobe; the
+ * silhouette term (it belongs to hf_reparam_*).  The per-sample deviation of the estimator grows as alpha falls (about
+ * 10 at alpha = 0.1 against 1 at 0.6 under a smooth map): near-mirrors belong to hf_reflect_*.
+ * Differentiated with respect to sh_n, weight, alpha and data.  Held, in world space: the drawn h_k and wo_k, hence
+ * F_k, the lookup's cell and fractions, the masks and the visibility -- the detached sample with attached evaluation
+ * of prb.py:213-223, as hf_bounce_*: of the ratio f cos / pdf_det the numerator D(c_h) G1(c_i) G1(c_o) F / (4 c_i) is
+ * attached.  With c_h = <n, h>, q = c_h^2 (a^2 - 1) + 1, r = sqrt(1 + T), v = wi for c_i and wo for c_o:
+ *   d ln D / d c_h = -4 c_h (a^2 - 1) / q,   d ln D / d a = 2 / a - 4 c_h^2 a / q,
+ *   d G1 / d T = -1 / ((1 + r)^2 r),   d T / d c = -2 a^2 / c^3,   d T / d a = 2 a max(1 - c^2, 0) / c^2,
+ *   dG1(c) = d G1 / d T (d T / d c <dn, v> + d T / d a da),   da = dalpha_i where alpha_i > 1e-4, else 0,
+ *   dlnA_k = d ln D / d c_h <dn, h> + d ln D / d a da + dG1(c_i) / G1(c_i) - <dn, wi> / c_i,
+ *   dvalue_i = dweight_i (value_i / weight_i)
+ *              + weight_i / K sum_k bit_ik F_k [ L_k (G1(c_o) dlnA_k + dG1(c_o)) + G1(c_o) sum_j b_j ddata_j ].
+ * The formulas take n as it comes, through the three cosines only: they are the derivative for unit n and tangential
+ * dn, which the normalisation of the surface interaction supplies.
+ * All four entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional (alpha
+ * included), n >= 2^32, spp == 0 or n % spp != 0, num_rays outside 1..32 (hf_glossy_rays: k >= 32), W < 2 or H < 2, a
+ * negative or non-finite eta, a non-finite rot (rot NULL: the identity).  They take device pointers and a stream,
+ * allocate nothing, never synchronise the host and are capturable.  Callers detect the entries by their symbols
+ * (HF_VERSION is unchanged). */
+/* materialises mirror ray k of every sample (out_o, out_d: 3 rows of n floats; out_maxt: n floats, +inf for a traced
+ * lane; every other lane gets -1 -- a miss -- and a zero origin and direction, as hf_reflect_rays): the two-call
+ * sequence hf_glossy_rays + hf_ray_test that bit k of hf_glossy_lighting's vis_bits equals.  out_h (3 rows, may be NULL):
+ * the microfacet normal h of an eligible sample, zero for an invalid draw.  Takes no field handle. */
+int hf_glossy_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                   const float *const d[3], const float *t, const uint8_t *active, const float *alpha, uint32_t k,
+                   uint32_t seed, const uint32_t *ray_id, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                   float *const out_h[3], hf_stream_t stream);
+/* The fused launch (hf_sky_lighting's mapping: one lane per sample, one workgroup per 256 samples, no work counter, a
+ * wave-uniform loop over the K directions): writes image (n / spp floats), value (n floats) and vis_bits (n words);
+ * each may be NULL (not wanted), but not all three.  No ray goes to memory.  A batch of 64 samples without an eligible
+ * lane draws nothing.  hf_set_ray_coherence is neither read nor changed. */
+int hf_glossy_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                       const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                       const float *weight, const float *alpha, float eta, uint32_t num_rays, uint32_t seed,
+                       const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data, const float rot[9], float *image,
+                       float *value, uint32_t *vis_bits, hf_stream_t stream);
+/* Reverse mode, the exact transpose of the tangent.  Traces nothing: the draws are formed again and vis_bits (as
+ * hf_glossy_lighting wrote it) is read; it takes no field handle and no p / nrm: a set bit implies the masks.  The
+ * upstream of sample i is g = grad_image[i / spp] / spp + grad_value[i]; either may be NULL (zero).  grad_sh_n (3 rows),
+ * grad_weight and grad_alpha are overwritten, exact zeros where no bit is set, one lane per sample, sums in k order, no
+ * atomics: bitwise the same from launch to launch; grad_data ([H][W]) is ACCUMULATED with float atomics, as
+ * hf_reflect_lighting_adjoint does.  Any of the four may be NULL (not wanted). */
+int hf_glossy_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                               const uint8_t *active, const float *weight, const float *alpha, float eta, uint32_t num_rays,
+                               uint32_t seed, const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data,
+                               const float rot[9], const uint32_t *vis_bits, const float *grad_image,
+                               const float *grad_value, float *const grad_sh_n[3], float *grad_weight, float *grad_alpha,
+                               float *grad_data, hf_stream_t stream);
+/* Forward mode for tangents dsh_n (3 rows), dweight (n), dalpha (n) and ddata ([H][W]), each may be NULL (zero); dimage
+ * (n / spp) and dvalue (n) are overwritten, either may be NULL (not wanted), not both.  No atomics for any spp (the film
+ * tree of the rows above, or one lane per pixel). */
+int hf_glossy_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *t,
+                               const uint8_t *active, const float *weight, const float *alpha, float eta, uint32_t num_rays,
+                               uint32_t seed, const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data,
+                               const float rot[9], const uint32_t *vis_bits, const float *const dsh_n[3],
+                               const float *dweight, const float *dalpha, const float *ddata, float *dimage, float *dvalue,
+                               hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional

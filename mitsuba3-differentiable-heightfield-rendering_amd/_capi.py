@@ -60,6 +60,9 @@ class hf_receiver_t(C.Structure):
 _caustic_in = [C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp]  # p, nrm, sh_n, d, t, active
 # sh_n, d, t, active, weight, eta, W, H, data, rot
 _reflect_in = [C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, C.c_float, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_float * 9)]
+# alpha, eta, num_rays, seed, ray_id, W, H, data, rot
+_glossy_mid = [_fp, C.c_float, C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_float * 9)]
+_glossy_in = [C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, *_glossy_mid]  # sh_n, d, t, active, weight, ...
 
 SYMBOLS = {
     "hf_create": (C.c_int, [C.POINTER(hf_desc_t), C.POINTER(C.c_void_p)]),
@@ -177,6 +180,14 @@ SYMBOLS = {
                                               C.c_void_p]),
     "hf_reflect_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, *_reflect_in, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp,
                                               C.c_void_p]),
+    "hf_glossy_rays": (C.c_int, [C.c_size_t, *_caustic_in, _fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(_fp * 3),
+                                 C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_glossy_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, *_caustic_in, _fp, *_glossy_mid, _fp, _fp, _fp,
+                                     C.c_void_p]),
+    "hf_glossy_lighting_adjoint": (C.c_int, [C.c_size_t, C.c_uint32, *_glossy_in, _fp, _fp, _fp, C.POINTER(_fp * 3), _fp, _fp,
+                                             _fp, C.c_void_p]),
+    "hf_glossy_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, *_glossy_in, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp,
+                                             _fp, C.c_void_p]),
     "hf_envmap_table_floats":(C.c_size_t, [C.c_uint32, C.c_uint32]),
     "hf_envmap_build_table": (C.c_int, [C.c_uint32, C.c_uint32, _fp, C.c_float, _fp, C.c_void_p]),
     "hf_envmap_sample_direction": (C.c_int, [C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, C.c_uint32, _fp, _fp,

@@ -1578,6 +1578,108 @@ extern "C" int hf_reflect_lighting_tangent(size_t n, uint32_t spp, const float *
     return light_launch(hf_launch_reflect, 2, a, stream);
 }
 
+// ---- glossy reflection of the environment map: a GGX lobe, K mirror rays per sample walked in the kernel ----
+// What the hf_glossy_* entries share: the wavefront rows and the sample stream (`a` is zeroed here; hf_glossy_rays passes
+// spp 1 and num_rays k + 1) ...
+static int glossy_rows(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                       const float *t, const uint8_t *active, const float *alpha, uint32_t num_rays, uint32_t seed,
+                       const uint32_t *ray_id, hf_glossy_args &a) {
+    a = {};
+    const int rc = light_args(who, "mirror rays", n, spp, sh_n, d, t, nullptr, num_rays, seed, ray_id, !alpha, a);
+    if (rc != HF_OK) return rc;
+    a.active = active; a.alpha = alpha; a.inv_k = 1.f / (float) num_rays;
+    return HF_OK;
+}
+// ... and the interface and the map of the three lighting entries
+static int glossy_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                       const float *t, const uint8_t *active, const float *weight, const float *alpha, float eta,
+                       uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t W, uint32_t H, const float *data,
+                       const float rot[9], hf_glossy_args &a) {
+    const int rc = glossy_rows(who, n, spp, sh_n, d, t, active, alpha, num_rays, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!data) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the map must have at least 2 x 2 texels (got %u x %u)", who, W, H);
+    if (!isfinite(eta) || eta < 0.f) return fail(HF_EINVAL, "%s: eta must be finite and not negative (got %g)", who, (double) eta);
+    a.weight = weight; a.W = W; a.H = H; a.data = data;
+    a.eta = eta; a.rcp_eta = eta > 0.f ? 1.f / eta : 0.f;
+    for (int j = 0; j < 9; ++j) {
+        a.rot[j] = rot ? rot[j] : (j % 4 == 0 ? 1.f : 0.f);
+        if (!isfinite(a.rot[j])) return fail(HF_EINVAL, "%s: rot must be finite", who);
+    }
+    return HF_OK;
+}
+
+extern "C" int hf_glossy_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                              const float *const d[3], const float *t, const uint8_t *active, const float *alpha, uint32_t k,
+                              uint32_t seed, const uint32_t *ray_id, float *const out_o[3], float *const out_d[3],
+                              float *out_maxt, float *const out_h[3], hf_stream_t stream) {
+    const char *fn = "hf_glossy_rays";
+    hf_glossy_args a;
+    if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
+    int rc = glossy_rows(fn, n, 1, sh_n, d, t, active, alpha, k + 1, seed, ray_id, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
+    if (out_h && !all3(out_h)) return fail(HF_EINVAL, "%s: NULL out_h component array", fn);
+    a.eta = 1.f; a.rcp_eta = 1.f; // (the direction does not depend on the interface)
+    for (int c = 0; c < 3; ++c) a.out_h[c] = out_h ? out_h[c] : nullptr;
+    return light_launch(hf_launch_glossy, 3, a, stream);
+}
+
+extern "C" int hf_glossy_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                  const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                  const float *t, const uint8_t *active, const float *weight, const float *alpha, float eta,
+                                  uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t W, uint32_t H,
+                                  const float *data, const float rot[9], float *image, float *value, uint32_t *vis_bits,
+                                  hf_stream_t stream) {
+    const char *fn = "hf_glossy_lighting";
+    hf_glossy_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(p) || !all3(nrm)) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!image && !value && !vis_bits) return fail(HF_EINVAL, "%s: image, value and vis_bits are all NULL", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = image; a.value = value; a.vis_bits = vis_bits;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    return light_launch(hf_launch_glossy, 0, a, stream);
+}
+
+extern "C" int hf_glossy_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                          const float *t, const uint8_t *active, const float *weight, const float *alpha,
+                                          float eta, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t W,
+                                          uint32_t H, const float *data, const float rot[9], const uint32_t *vis_bits,
+                                          const float *grad_image, const float *grad_value, float *const grad_sh_n[3],
+                                          float *grad_weight, float *grad_alpha, float *grad_data, hf_stream_t stream) {
+    const char *fn = "hf_glossy_lighting_adjoint";
+    hf_glossy_args a;
+    const int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.gimg = grad_image; a.gvalue = grad_value;
+    a.gw = grad_weight; a.ga = grad_alpha; a.gdata = grad_data;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    return light_launch(hf_launch_glossy, 1, a, stream);
+}
+
+extern "C" int hf_glossy_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                          const float *t, const uint8_t *active, const float *weight, const float *alpha,
+                                          float eta, uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, uint32_t W,
+                                          uint32_t H, const float *data, const float rot[9], const uint32_t *vis_bits,
+                                          const float *const dsh_n[3], const float *dweight, const float *dalpha,
+                                          const float *ddata, float *dimage, float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_glossy_lighting_tangent";
+    hf_glossy_args a;
+    const int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
+    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.dw = dweight; a.da = dalpha; a.ddata = ddata; a.image = dimage; a.value = dvalue;
+    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    return light_launch(hf_launch_glossy, 2, a, stream);
+}
+
 // ---- bounce lighting: one diffuse interreflection, both rays traced inside the lighting kernel ----
 // What the four hf_bounce_* entries share.  hf_bounce_rays passes spp 1, num_rays k + 1, albedo 1 and either no light or its one direction.
 static int bounce_args(const char *who, const hf_field_t *hf, size_t n, uint32_t spp, const float *const sh_n[3],

@@ -4180,7 +4180,8 @@ void hf_launch_caustic(int mode, const hf_caustic_args &a, hipStream_t stream) {
 // most 1/4 in magnitude; the other quadrant pair (phi -> pi/2 - phi) swaps sine and cosine.  z = safe_sqrt(1 - |p|^2)
 // is taken as sqrt((1 - |r|) (1 + |r|)): |p| = |r| for the concentric map, r = 2 s - 1 is exact, and the difference
 // 1 - px^2 - py^2 of rounded products would lose z to cancellation near the rim of the disk (2.7e-6 at z = 0.01).
-__device__ __forceinline__ v3 bounce_local(uint32_t seed, uint32_t k, uint32_t id) {
+// (bounce_disk: square_to_uniform_disk_concentric of that sample as (px, py, |r|); the glossy row draws on the same disk)
+__device__ __forceinline__ v3 bounce_disk(uint32_t seed, uint32_t k, uint32_t id) {
     float sx, sy;
     sky_sample(seed, k, id, sx, sy);
     const float x = __builtin_fmaf(2.f, sx, -1.f), y = __builtin_fmaf(2.f, sy, -1.f);
@@ -4190,8 +4191,12 @@ __device__ __forceinline__ v3 bounce_local(uint32_t seed, uint32_t k, uint32_t i
     float sn, cs;
     sincospif(a, &sn, &cs);
     const float px = r * (q13 ? sn : cs), py = r * (q13 ? cs : sn);
-    const float ar = __builtin_fabsf(r);
-    return mk3(px, py, __builtin_sqrtf((1.f - ar) * (1.f + ar)));
+    return mk3(px, py, __builtin_fabsf(r));
+}
+__device__ __forceinline__ v3 bounce_local(uint32_t seed, uint32_t k, uint32_t id) {
+    const v3 q = bounce_disk(seed, k, id);
+    const float ar = q.z;
+    return mk3(q.x, q.y, __builtin_sqrtf((1.f - ar) * (1.f + ar)));
 }
 // Frame3f(sh_n).to_world with (s, t) = coordinate_system(sh_n)
 __device__ __forceinline__ v3 bounce_world(v3 sn, v3 wo) {
@@ -5999,6 +6004,320 @@ void hf_launch_reflect(int mode, const hf_reflect_args &a, hipStream_t stream) {
     else
         hipLaunchKernelGGL(mode == 0 ? hf_reflect_kernel : mode == 1 ? hf_reflect_adjoint_kernel
                            : mode == 2 ? hf_reflect_tangent_kernel<false> : hf_reflect_rays_kernel, grid, block, 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
+// Glossy reflection of the environment map (include/hf.h hf_glossy_*): the reflection lobe of a rough conductor or
+// dielectric (roughconductor.cpp:242-268) with an isotropic GGX distribution sampled by its visible normals
+// (microfacet.h:297-319, 405-420).  Every wavefront sample draws K = num_rays microfacet normals from the TEA stream,
+// mirrors wi at each (reflect_vertex with the microfacet normal in the place of the shading normal), walks the mirror
+// ray (any hit, per lane, maxt = +inf) and, where it escapes, looks the map up in double.  ONE launch, one lane per
+// sample, `k` a scalar loop with the lanes predicated; nothing of a ray goes to memory.
+// ---------------------------------------------------------------------------------
+// Draw k of one sample, the same text for the fused kernel, the rays kernel and the two derivatives: the microfacet
+// normal h (world), the mirror direction wo, the cosines <wi, h>, <n, h>, <n, wo>, F and whether the draw is valid
+struct hf_glossy_draw {
+    v3 h, wo;
+    float cwh, ch, co, F;
+    bool valid;
+};
+template <class P>
+__device__ __forceinline__ hf_glossy_draw glossy_draw(P a, v3 n, v3 d, float al, uint32_t k, uint32_t id) {
+    hf_glossy_draw g;
+    v3 s, t;
+    coordinate_system(n, s, t);
+    const v3 wi = mk3(-d.x, -d.y, -d.z);
+    const v3 wl = mk3(dot3(wi, s), dot3(wi, t), dot3(wi, n));
+    // step 1: stretch wi (microfacet.h:301-305)
+    const v3 wp = normalize3(mk3(al * wl.x, al * wl.y, wl.z));
+    // Frame3f::sincos_phi (frame.h:111-122); Epsilon = 2^-24
+    const float st2 = __builtin_fmaf(wp.x, wp.x, wp.y * wp.y), ist = rsqrt_ieee(st2); // Frame3f::sin_theta_2
+    const bool pole = __builtin_fabsf(st2) <= 2.384185791015625e-07f;
+    const float cphi = pole ? 1.f : fminf(fmaxf(wp.x * ist, -1.f), 1.f), sphi = pole ? 0.f : fminf(fmaxf(wp.y * ist, -1.f), 1.f);
+    const float ct = wp.z;
+    // step 2: sample_visible_11, the GGX branch (microfacet.h:405-420), on the disk of bounce_local
+    const v3 q = bounce_disk(a->seed, k, id);
+    const float sh = 0.5f * (1.f + ct);
+    const float e = __builtin_sqrtf(fmaxf(__builtin_fmaf(-q.x, q.x, 1.f), 0.f));
+    const float x = q.x, y = __builtin_fmaf(q.y, sh, __builtin_fmaf(-e, sh, e)); // lerp(e, p.y, s)
+    const float z = __builtin_sqrtf(fmaxf(1.f - __builtin_fmaf(y, y, x * x), 0.f));
+    const float si = __builtin_sqrtf(fmaxf(__builtin_fmaf(-ct, ct, 1.f), 0.f));
+    const float nr = rcp_ieee(__builtin_fmaf(si, y, ct * z));
+    const float slx = __builtin_fmaf(ct, y, -(si * z)) * nr, sly = x * nr;
+    // step 3: rotate and unstretch; step 4: the normal
+    const float rx = __builtin_fmaf(cphi, slx, -(sphi * sly)) * al, ry = __builtin_fmaf(sphi, slx, cphi * sly) * al;
+    const v3 hl = normalize3(mk3(-rx, -ry, 1.f));
+    g.h = fma3(n, hl.z, fma3(t, hl.y, s * hl.x)); // Frame3f(n).to_world, as bounce_world
+    const hf_reflect_vertex v = reflect_vertex(a, g.h, d); // fresnel(<wi, h>, eta) and reflect(wi, h)
+    g.cwh = v.c; g.wo = v.wr; g.F = v.F;
+    const float inf = __builtin_inff();
+    g.valid = (__builtin_fabsf(g.h.x) < inf) && (__builtin_fabsf(g.h.y) < inf) && (__builtin_fabsf(g.h.z) < inf) && (v.c > 0.f);
+    g.ch = dot3(n, g.h); g.co = dot3(n, g.wo);
+    return g;
+}
+// smith_g1 (microfacet.h:341-365) of a unit vector with cosine c to the normal, frame-free, and its derivatives:
+//   T = a^2 max(1 - c^2, 0) / c^2,  G1 = 2 / (1 + sqrt(1 + T)),  dG1/dT = -1 / ((1 + r)^2 r),  dT/dc = -2 a^2 / c^3
+struct hf_glossy_smith { float G, dc, da; }; // G1, dG1 / dc, dG1 / da
+__device__ __forceinline__ hf_glossy_smith glossy_smith(float al, float c) {
+    hf_glossy_smith s;
+    const float a2 = al * al, m = fmaxf(__builtin_fmaf(-c, c, 1.f), 0.f), c2 = c * c;
+    const float T = a2 * m / c2, r = __builtin_sqrtf(1.f + T), q = 1.f + r;
+    s.G = 2.f / q;
+    const float dT = -1.f / ((q * q) * r);
+    s.dc = dT * (-2.f * a2 / (c2 * c));
+    s.da = dT * (2.f * al * m / c2);
+    return s;
+}
+// the rows of sample i that every kernel of the row reads: n, d and the roughness a = max(alpha, 1e-4)
+template <class P>
+__device__ __forceinline__ float glossy_sample(P a, size_t i, v3 &n, v3 &d) {
+    n = mk3(a->sh_n[0][i], a->sh_n[1][i], a->sh_n[2][i]);
+    d = mk3(a->d[0][i], a->d[1][i], a->d[2][i]);
+    return a->alpha[i];
+}
+// eligible: active, a finite t, a finite roughness, both normals face the viewer
+__device__ __forceinline__ bool glossy_eligible(v3 n, v3 g, v3 d, float t, float alpha, bool act) {
+    const float inf = __builtin_inff();
+    return act && (__builtin_fabsf(t) < inf) && (__builtin_fabsf(alpha) < inf) && (-dot3(n, d) > 0.f) && (-dot3(g, d) > 0.f);
+}
+// what the derivative kernels need of the lookup: the radiance, the bilinear weights and the first texel's index
+struct hf_glossy_shade { float L; double bw[4]; size_t r0; };
+__device__ __forceinline__ hf_glossy_shade glossy_shade(const hf_glossy_args &a, v3 w) {
+    hf_glossy_shade s;
+    uint32_t cx, cy;
+    double fx, fy;
+    env_lookup(a, w, cx, cy, fx, fy);
+    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
+    const double gx = 1.0 - fx, gy = 1.0 - fy;
+    s.L = (float) (gy * (gx * (double) a.data[r0] + fx * (double) a.data[r0 + 1]) + fy * (gx * (double) a.data[r1] + fx * (double) a.data[r1 + 1]));
+    s.bw[0] = gy * gx; s.bw[1] = gy * fx; s.bw[2] = fy * gx; s.bw[3] = fy * fx;
+    s.r0 = r0;
+    return s;
+}
+
+typedef const __attribute__((address_space(4))) hf_glossy_args *hf_glossy_kargs;
+
+#ifndef HF_GLOSSY_WAVES
+#define HF_GLOSSY_WAVES 5 // resident waves per SIMD (96 VGPRs; why not six: profiles/glossy/registers.txt)
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_GLOSSY_WAVES) void hf_glossy_kernel(hf_glossy_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    bool elig;
+    {
+        v3 sn, d;
+        const float al = glossy_sample(&a, ii, sn, d);
+        const v3 gn = mk3(a.nrm[0][ii], a.nrm[1][ii], a.nrm[2][ii]);
+        elig = glossy_eligible(sn, gn, d, a.t[ii], al, in && (a.active ? a.active[ii] != 0 : true));
+    }
+    // Two loops over the directions.  The first draws and walks and keeps only the bit; the second, when every walk is
+    // over, forms the draws of the set bits again (the same device function: the same bits) and looks the map up in
+    // double.  With the lookup inside the walk's loop its atan2 / acos polynomials' constants, sixty registers, are
+    // hoisted in front of the loop and held across every walk (profiles/glossy/registers.txt).
+    // In both loops the sample's record is read again per direction (the index goes through an opaque statement, so the
+    // loads stay in the loop; they hit the cache): thirteen registers that are then not held across the walk.
+    uint32_t bits = 0u; // bit k: direction k was traced and is unoccluded
+    if (__ballot(elig) != 0ull) { // wave-uniform: a batch without an eligible sample draws nothing
+        hf_glossy_kargs ka = (hf_glossy_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll 1
+        for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+            asm volatile("" : "+s"(ka)); // opaque per direction: the kernarg loads stay inside the loop
+            v3 wo, o;
+            bool traced;
+            {
+                uint32_t ix = ii;
+                asm volatile("" : "+v"(ix));
+                v3 sn, d;
+                const float al = fmaxf(glossy_sample(ka, ix, sn, d), 1e-4f);
+                const v3 gn = mk3(ka->nrm[0][ix], ka->nrm[1][ix], ka->nrm[2][ix]);
+                const uint32_t *ray_id = ka->ray_id;
+                const hf_glossy_draw g = glossy_draw(ka, sn, d, al, k, ray_id ? ray_id[ix] : ix);
+                traced = elig && g.valid && (g.co > 0.f) && (dot3(gn, g.wo) > 0.f);
+                wo = g.wo;
+                const v3 p = mk3(ka->p[0][ix], ka->p[1][ix], ka->p[2][ix]);
+                o = sky_origin(p, gn, sky_offset(p), wo);
+            }
+            hf_hit best;
+            light_walk<true>(&ka->f, f, o, wo, traced, best);
+            if (traced && !best.hit) bits |= 1u << k;
+            if (k + 1u >= ka->num_rays) break;
+        }
+    }
+    // (the map and the output pointers: loaded here, not before the walks)
+    hf_glossy_kargs ko = (hf_glossy_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    float acc = 0.f; // sum over the visible directions of F G1(c_o) L, in k order
+    if (__ballot(bits != 0u) != 0ull) { // wave-uniform: on lit lanes only
+#pragma unroll 1
+        for (uint32_t k = 0; k < ko->num_rays; ++k) {
+            asm volatile("" : "+s"(ko));
+            if ((bits >> k) & 1u) {
+                uint32_t ix = ii;
+                asm volatile("" : "+v"(ix));
+                v3 sn, d;
+                const float al = fmaxf(glossy_sample(ko, ix, sn, d), 1e-4f);
+                const uint32_t *ray_id = ko->ray_id;
+                const hf_glossy_draw g = glossy_draw(ko, sn, d, al, k, ray_id ? ray_id[ix] : ix);
+                acc += (g.F * glossy_smith(al, g.co).G) * reflect_radiance(*ko, ko->data, g.wo);
+            }
+        }
+    }
+    float val = 0.f;
+    if (bits != 0u) { // (a set bit: eligible, in range)
+        const float *weight = ko->weight;
+        val = ko->inv_k * acc;
+        if (weight) val *= weight[i];
+    }
+    if (in) {
+        float *value = ko->value;
+        uint32_t *vis_bits = ko->vis_bits;
+        if (value) value[i] = val;
+        if (vis_bits) vis_bits[i] = bits;
+    }
+    float *image = ko->image;
+    if (image) {
+        const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+        film_pixel(image, val, 0u, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+    }
+}
+
+// mirror ray a.k of every sample, materialised: what hf_glossy_kernel walks for that direction, bit for bit (maxt = -1
+// and a zero origin and direction: the fused kernel does not trace the lane); out_h: the microfacet normal, zero for an
+// invalid draw or a sample that is not eligible
+__global__ __launch_bounds__(HF_BLOCK) void hf_glossy_rays_kernel(hf_glossy_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 sn, d;
+    const float al = glossy_sample(&a, i, sn, d);
+    const v3 gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+    const bool elig = glossy_eligible(sn, gn, d, a.t[i], al, a.active ? a.active[i] != 0 : true);
+    const hf_glossy_draw g = glossy_draw(&a, sn, d, fmaxf(al, 1e-4f), a.k, light_id(a, i));
+    const bool traced = elig && g.valid && (g.co > 0.f) && (dot3(gn, g.wo) > 0.f);
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    light_store_ray(a, i, traced ? sky_origin(p, gn, sky_offset(p), g.wo) : z, traced ? g.wo : z, traced);
+    if (a.out_h[0]) {
+        const v3 h = (elig && g.valid) ? g.h : z;
+        a.out_h[0][i] = h.x; a.out_h[1][i] = h.y; a.out_h[2][i] = h.z;
+    }
+}
+
+// The derivative of one sample with the draws held (include/hf.h): with S = sum_k F G1(c_o) L over the set bits,
+//   value = weight / K S,   d value = d weight S / K + weight / K (<N, dn> + A da + sum_k F G1(c_o) sum_j b_j ddata_j).
+// VISIT(k, F G1(c_o), shade) is called per set bit (the texel terms of the adjoint and the tangent)
+struct hf_glossy_sums { v3 N; float A, S; };
+template <class V>
+__device__ __forceinline__ hf_glossy_sums glossy_sums(const hf_glossy_args &a, size_t i, uint32_t bits, V visit) {
+    hf_glossy_sums r;
+    r.N = mk3(0.f, 0.f, 0.f); r.A = 0.f; r.S = 0.f;
+    v3 sn, d;
+    const float al = fmaxf(glossy_sample(&a, i, sn, d), 1e-4f);
+    const uint32_t id = light_id(a, i);
+    const v3 wi = mk3(-d.x, -d.y, -d.z);
+    const float ci = dot3(sn, wi);
+    const hf_glossy_smith gi = glossy_smith(al, ci);
+    const float a2m1 = __builtin_fmaf(al, al, -1.f);
+    const float ki = gi.dc / gi.G - 1.f / ci, kia = gi.da / gi.G; // d ln (G1(c_i) / c_i)
+    for (uint32_t k = 0; k < a.num_rays; ++k) {
+        if (!((bits >> k) & 1u)) continue;
+        const hf_glossy_draw g = glossy_draw(&a, sn, d, al, k, id);
+        const hf_glossy_smith go = glossy_smith(al, g.co);
+        const hf_glossy_shade s = glossy_shade(a, g.wo);
+        const float q = __builtin_fmaf(g.ch * g.ch, a2m1, 1.f);
+        const float dDc = -4.f * g.ch * a2m1 / q, dDa = 2.f / al - 4.f * (g.ch * g.ch) * al / q; // d ln D
+        const float FL = g.F * s.L;
+        // L (G1(c_o) d ln A + d G1(c_o))
+        r.N = fma3(g.wo, FL * go.dc, fma3(wi, (FL * go.G) * ki, fma3(g.h, (FL * go.G) * dDc, r.N)));
+        r.A += FL * __builtin_fmaf(go.G, dDa + kia, go.da);
+        r.S += g.F * go.G * s.L;
+        visit(g.F * go.G, s);
+    }
+    return r;
+}
+
+// Reverse mode of hf_glossy_kernel with respect to sh_n, weight, alpha and the texels: nothing is traced, the draws
+// are formed again and the visibility word read.  grad_sh_n, grad_weight, grad_alpha: one lane per sample, sums in k
+// order, overwritten, no atomics; grad_data: one float atomic per texel of every set bit
+__global__ __launch_bounds__(HF_BLOCK) void hf_glossy_adjoint_kernel(hf_glossy_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 gm = mk3(0.f, 0.f, 0.f);
+    float gw = 0.f, ga = 0.f;
+    const uint32_t bits = a.vis_bits[i];
+    if (bits != 0u) {
+        const float g = (a.gimg ? a.gimg[i / a.spp] * (1.0f / (float) a.spp) : 0.f) + (a.gvalue ? a.gvalue[i] : 0.f);
+        const float gk = (a.weight ? g * a.weight[i] : g) * a.inv_k;
+        const hf_glossy_sums r = glossy_sums(a, i, bits, [&](float fg, const hf_glossy_shade &s) {
+            if (a.gdata) {
+                const double q = (double) (gk * fg);
+                atomicAdd(a.gdata + s.r0, (float) (q * s.bw[0])); atomicAdd(a.gdata + s.r0 + 1, (float) (q * s.bw[1]));
+                atomicAdd(a.gdata + s.r0 + a.W, (float) (q * s.bw[2])); atomicAdd(a.gdata + s.r0 + a.W + 1, (float) (q * s.bw[3]));
+            }
+        });
+        gm = r.N * gk;
+        ga = a.alpha[i] > 1e-4f ? r.A * gk : 0.f;
+        gw = (g * a.inv_k) * r.S;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        if (a.gn[c]) a.gn[c][i] = c == 0 ? gm.x : c == 1 ? gm.y : gm.z;
+    if (a.gw) a.gw[i] = gw;
+    if (a.ga) a.ga[i] = ga;
+}
+
+// forward mode, the transpose of the above: the tangent of sample i's value for tangents dn of sh_n, dw of weight, da of
+// alpha and ddata of the texels (NULL: zero)
+__device__ __forceinline__ float glossy_tangent_value(const hf_glossy_args &a, size_t i) {
+    const uint32_t bits = a.vis_bits[i];
+    if (bits == 0u) return 0.f;
+    float dt = 0.f; // sum_k F G1(c_o) sum_j b_j ddata_j
+    const hf_glossy_sums r = glossy_sums(a, i, bits, [&](float fg, const hf_glossy_shade &s) {
+        if (a.ddata)
+            dt += fg * (float) (s.bw[0] * (double) a.ddata[s.r0] + s.bw[1] * (double) a.ddata[s.r0 + 1] +
+                                s.bw[2] * (double) a.ddata[s.r0 + a.W] + s.bw[3] * (double) a.ddata[s.r0 + a.W + 1]);
+    });
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const float w = a.weight ? a.weight[i] : 1.f, dw = a.dw ? a.dw[i] : 0.f;
+    const float da = (a.da && a.alpha[i] > 1e-4f) ? a.da[i] : 0.f;
+    const float dv = __builtin_fmaf(r.A, da, dot3(r.N, dn)) + dt;
+    return __builtin_fmaf(dw * a.inv_k, r.S, (w * a.inv_k) * dv);
+}
+// PIXEL as in hf_reflect_tangent_kernel: no atomics either way, the per-sample tangent written too
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_glossy_tangent_kernel(hf_glossy_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    if (PIXEL) {
+        if (i >= a.n / spp) return;
+        float c = 0.f;
+        for (uint32_t s = 0; s < spp; ++s) {
+            const float dv = glossy_tangent_value(a, i * spp + s);
+            if (a.value) a.value[i * spp + s] = dv;
+            c += dv;
+        }
+        a.image[i] = c * (1.0f / (float) spp);
+    } else {
+        const bool in = i < a.n;
+        const float c = in ? glossy_tangent_value(a, i) : 0.f;
+        if (in && a.value) a.value[i] = c;
+        if (a.image) film_pixel(a.image, c, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
+    }
+}
+
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays (hf_launch_reflect's shape)
+void hf_launch_glossy(int mode, const hf_glossy_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const bool tree = sky_tree_film(a.spp) || !a.image;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    if (mode == 0 && !tree) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths
+    if (mode == 2 && !tree)
+        hipLaunchKernelGGL(hf_glossy_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(mode == 0 ? hf_glossy_kernel : mode == 1 ? hf_glossy_adjoint_kernel
+                           : mode == 2 ? hf_glossy_tangent_kernel<false> : hf_glossy_rays_kernel, grid, block, 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------

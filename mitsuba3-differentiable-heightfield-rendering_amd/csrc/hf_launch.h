@@ -150,6 +150,33 @@ struct hf_reflect_args {
 // mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is hf_launch_sky's: the per-lane any-hit walk,
 // no work counter, no scratch block
 void hf_launch_reflect(int mode, const hf_reflect_args &a, hipStream_t stream);
+// ---- glossy reflection of the environment map (hf_glossy_rays, hf_glossy_lighting / _adjoint / _tangent): the one
+// argument of its four kernels; eta, rcp_eta as in hf_reflect_args (reflect_vertex reads either), W, H, rot as in
+// hf_envmap_args ----
+struct hf_glossy_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, num_rays, seed, k;         // k: hf_glossy_rays' direction
+    uint32_t W, H;
+    float eta, rcp_eta;                      // rcp_eta = 1 / eta, rounded once on the host (0 for eta = 0: F = 1)
+    float inv_k;                             // 1 / num_rays, rounded once on the host
+    float rot[9];                            // row-major rotation, map space -> world (identity for NULL)
+    const float *data;                       // [H][W] radiance
+    const float *p[3], *nrm[3];              // si.p, si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight, *alpha;
+    const uint8_t *active;                   // optional (NULL: every lane)
+    const uint32_t *ray_id;                  // optional: the id of sample i in the sample streams (NULL: i)
+    float *image, *value;                    // forward: written (NULL: not wanted); tangent: dimage, dvalue
+    uint32_t *vis_bits;                      // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    float *out_h[3];                         // rays (optional): the microfacet normal
+    const float *gimg, *gvalue;              // adjoint inputs (NULL: zero)
+    float *gn[3], *gw, *ga, *gdata;          // adjoint outputs (NULL: not wanted); gdata is accumulated
+    const float *dn[3], *dw, *da, *ddata;    // tangent inputs (NULL: zero)
+};
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is hf_launch_sky's: the per-lane any-hit walk,
+// no work counter, no scratch block
+void hf_launch_glossy(int mode, const hf_glossy_args &a, hipStream_t stream);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----

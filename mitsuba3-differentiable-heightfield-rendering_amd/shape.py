@@ -1970,6 +1970,117 @@ def reflection_rays(si, ray, active=True):
     return r
 
 
+class _GlossyLightingOp(torch.autograd.Function):
+    """(image, per-sample value, visibility words) of hf_glossy_lighting; backward = hf_glossy_lighting_adjoint (gradients
+    of sh_n, weight, alpha and the texels), jvp = hf_glossy_lighting_tangent.  Both read the visibility word the forward
+    saved, draw the microfacet normals again and trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, sn, dd, tt, al, vis, dat, ww=None):
+        """what hf_glossy_lighting_adjoint / _tangent start with"""
+        spp, eta, num_rays, seed, rid, rot, act = ctx.misc
+        return (sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(act), _ptr(ww), al.data_ptr(), eta,
+                num_rays, seed, _ptr(rid), dat.shape[1], dat.shape[0], dat.data_ptr(), C.byref(rot), vis.data_ptr())
+
+    @staticmethod
+    def forward(ctx, sh_n, weight, alpha, full, shape, p, nrm, d, t, active, rot, eta, spp, num_rays, seed, ray_index):
+        sn, pp, gn, dd, tt, ww, al, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, alpha, full))
+        n = sn.shape[1]
+        ctx.misc = (spp, eta, num_rays, seed, ray_index, rot, active)
+        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
+        value = torch.empty(n, dtype=torch.float32, device=sn.device)
+        vis = torch.empty(n, dtype=torch.int32, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_glossy_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                                 C.byref(_p3(dd)), tt.data_ptr(), _ptr(active), _ptr(ww), al.data_ptr(), eta,
+                                                 num_rays, seed, _ptr(ray_index), dat.shape[1], dat.shape[0], dat.data_ptr(),
+                                                 C.byref(rot), image.data_ptr(), value.data_ptr(), vis.data_ptr(),
+                                                 _stream_of(sn.device)))
+        saved = _with_weight(ctx, (sn, dd, tt, al, vis, dat), ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(vis)
+        return image, value, vis
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dweight, dalpha, dfull, *_):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
+        da = _detached_f32(dalpha)
+        df = dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
+        dimage = torch.empty(sn.shape[1] // max(ctx.misc[0], 1), dtype=torch.float32, device=sn.device)
+        dvalue = torch.empty_like(sn[0])
+        if sn.shape[1]:
+            check(_capi.lib().hf_glossy_lighting_tangent(*_GlossyLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
+                                                         _ptr(dw), _ptr(da), _ptr(df), dimage.data_ptr(), dvalue.data_ptr(),
+                                                         _stream_of(sn.device)))
+        return dimage, dvalue, None
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_value, _grad_vis):
+        saved = ctx.saved_tensors
+        sn, dat = saved[0], saved[5]
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
+        gv = _detached_f32(grad_value)
+        ga = torch.empty_like(sn[0]) if ctx.needs_input_grad[2] else None
+        gd = torch.zeros_like(dat) if ctx.needs_input_grad[3] else None
+        if sn.shape[1]:
+            check(_capi.lib().hf_glossy_lighting_adjoint(*_GlossyLightingOp._prefix(ctx, *saved), _ptr(gi), _ptr(gv),
+                                                         C.byref(_p3(gn)), _ptr(gw), _ptr(ga), _ptr(gd), _stream_of(sn.device)))
+        return (gn, gw, ga, gd) + (None,) * 12
+
+
+def _glossy_alpha(alpha, n, device):
+    """``alpha`` (a float, or a tensor of 1 or n elements) as the [n] float32 row of the hf_glossy_* entries; a scalar is
+    broadcast here, so its gradient is the sum torch forms"""
+    a = torch.as_tensor(alpha, dtype=torch.float32, device=device).reshape(-1)
+    if a.numel() not in (1, n):
+        raise ValueError("alpha must be a float or a tensor of 1 or %d elements (got %d)" % (n, a.numel()))
+    return a.expand(n)
+
+
+def glossy_lighting(shape, si, ray, envmap, alpha, eta=0.0, spp=1, num_rays=4, seed=0, weight=None, ray_index=None,
+                    active=True, return_value=False, return_visibility=False):
+    """Glossy reflection of an environment map (``Envmap``) + box-filter film (``hf_glossy_lighting``): the reflection
+    lobe of a rough conductor or dielectric with an isotropic GGX distribution of roughness ``alpha`` (a float, or a
+    tensor of 1 or n elements, e.g. a roughness texture read through ``eval_attribute``).  Every sample draws
+    ``num_rays`` (1..32) microfacet normals about ``si.sh_frame.n`` by visible-normal sampling from the TEA stream of
+    ``sky_lighting`` (``seed``, ``ray_index``), mirrors ``wi`` at each, walks ``si.spawn_ray(wo)`` against the terrain
+    inside the kernel and averages ``weight * F * G1(wo) * envmap.eval(wo)`` over the rays that escape (``F``: the
+    Fresnel reflectance of the relative index ``eta``; ``eta = 0``: F = 1).  A reflected ray that hits the terrain
+    contributes 0.  Returns the [n // spp] image; with ``return_value`` also the [n] per-sample values and with
+    ``return_visibility`` the [n] int32 words (bit k: mirror ray k escapes).  Differentiable with respect to
+    ``si.sh_frame.n``, ``weight`` ([n], optional: the specular reflectance), ``alpha`` and ``envmap.data``, in reverse and
+    forward mode, with the drawn directions held (detached sampling, attached evaluation).  The variance of the estimator
+    grows as ``alpha`` falls: a near-mirror belongs to ``reflection_lighting``."""
+    shape._check_ray(ray)
+    n = len(ray)
+    image, value, vis = _GlossyLightingOp.apply(si.sh_frame.n, weight, _glossy_alpha(alpha, n, ray.d.device), envmap.full(),
+                                                shape, si.p, si.n, ray.d, si.t, _caustic_active(active, n, ray.d.device),
+                                                envmap._rot, float(eta), int(spp), int(num_rays), int(seed),
+                                                _check_ray_index(ray_index, ray))
+    out = (image,) + ((value,) if return_value else ()) + ((vis,) if return_visibility else ())
+    return out if len(out) > 1 else image
+
+
+def glossy_rays(si, ray, alpha, k, seed=0, ray_index=None, active=True, return_normal=False):
+    """Mirror ray ``k`` of every sample of ``glossy_lighting`` as a Ray3f (``hf_glossy_rays``): what the fused kernel walks
+    for that direction, bit for bit.  Lanes it does not trace get ``maxt = -1``, a miss, and a zero ray.  With
+    ``return_normal`` also the [3, n] microfacet normals (zero for an invalid draw)."""
+    sn, pp, gn, dd, tt = map(_detached_f32, (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n, r = sn.shape[1], _empty_rays(pp)
+    h = torch.empty_like(pp) if return_normal else None
+    al = _glossy_alpha(alpha, n, pp.device).detach().contiguous()
+    rid = _check_ray_index(ray_index, ray)
+    if n:
+        check(_capi.lib().hf_glossy_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
+                                         tt.data_ptr(), _ptr(_caustic_active(active, n, pp.device)), al.data_ptr(), int(k),
+                                         int(seed), _ptr(rid), C.byref(_p3(r.o)), C.byref(_p3(r.d)), r.maxt.data_ptr(),
+                                         _ref(_row_ptrs(h)), _stream_of(pp.device)))
+    return (r, h) if return_normal else r
+
+
 class _BounceLightingOp(torch.autograd.Function):
     """(image, hit_prim, lit_bits) of hf_bounce_lighting; backward = hf_bounce_lighting_adjoint (gradients of sh_n, weight
     and the heights), jvp = hf_bounce_lighting_tangent.  Both read the record the forward saved and trace nothing."""

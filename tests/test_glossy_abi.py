@@ -1,0 +1,97 @@
+"""Glossy reflection of the environment map (hf_glossy_rays, hf_glossy_lighting, _adjoint, _tangent) on the CPU: the
+four entry points are declared, exported and bound, HF_VERSION is unchanged, and every bad argument is refused with
+HF_EINVAL and a message before anything touches a device (host addresses stand in for device pointers)."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FNS = ("hf_glossy_rays", "hf_glossy_lighting", "hf_glossy_lighting_adjoint", "hf_glossy_lighting_tangent")
+NAN, INF = float("nan"), float("inf")
+IDENTITY = (1, 0, 0, 0, 1, 0, 0, 0, 1)
+
+
+def test_symbols_declared_exported_and_bound():
+    import hf_amd
+    from hf_amd import _capi
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
+    lib = C.CDLL(hf_amd.build.LIB_PATH)
+    for fn in FNS:
+        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
+        assert hasattr(lib, fn)
+        assert fn in _capi.SYMBOLS
+    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
+    for name in ("glossy_lighting", "glossy_rays"):
+        assert callable(getattr(hf_amd, name)), name
+
+
+def _call(lib, fn, n=8, spp=1, eta=1.5, num_rays=4, k=0, W=5, H=3, rot=IDENTITY, null=(), null_row=None):
+    from hf_amd import _capi
+    keep = (C.c_float * 16384)()            # (also the stand-in for the handle: no case gets as far as reading it)
+    a = C.addressof(keep)
+
+    def rows(name, k_=3):
+        if name in null:
+            return None
+        r = (_capi._fp * k_)(*([a] * k_))
+        if null_row == name:
+            r[k_ - 1] = None
+        return r
+    arg = lambda name: None if name in null else a
+    R = None if rot is None else (C.c_float * 9)(*rot)
+    if fn == "hf_glossy_rays":
+        return lib.hf_glossy_rays(n, rows("p"), rows("nrm"), rows("sh_n"), rows("d"), arg("t"), arg("active"), arg("alpha"), k, 0,
+                                  arg("ray_id"), rows("out_o"), rows("out_d"), arg("out_maxt"), rows("out_h"), None)
+    mid = (arg("active"), arg("weight"), arg("alpha"), eta, num_rays, 0, arg("ray_id"), W, H, arg("data"), R)
+    if fn == "hf_glossy_lighting":
+        return lib.hf_glossy_lighting(arg("hf"), n, spp, rows("p"), rows("nrm"), rows("sh_n"), rows("d"), arg("t"), *mid,
+                                      arg("image"), arg("value"), arg("vis_bits"), None)
+    head = (n, spp, rows("sh_n"), rows("d"), arg("t"), *mid, arg("vis_bits"))
+    if fn == "hf_glossy_lighting_adjoint":
+        return lib.hf_glossy_lighting_adjoint(*head, arg("grad_image"), arg("grad_value"), rows("grad_sh_n"), arg("grad_weight"),
+                                              arg("grad_alpha"), arg("grad_data"), None)
+    return lib.hf_glossy_lighting_tangent(*head, rows("dsh_n"), arg("dweight"), arg("dalpha"), arg("ddata"), arg("dimage"),
+                                          arg("dvalue"), None)
+
+
+ROWS = [{"n": 1 << 32}] + [{"null": (x,)} for x in ("sh_n", "d", "t", "alpha")] + [{"null_row": x} for x in ("sh_n", "d")]
+LIGHT = ROWS + [{"spp": 0}, {"n": 9, "spp": 2}, {"num_rays": 0}, {"num_rays": 33}, {"W": 1}, {"H": 1}, {"W": 0, "H": 0},
+                {"eta": -1.5}, {"eta": -0.0 - 1e-30}, {"eta": NAN}, {"eta": INF}, {"eta": -INF},
+                {"rot": (1, 0, 0, 0, NAN, 0, 0, 0, 1)}, {"rot": (1, 0, 0, 0, 1, 0, 0, 0, INF)}, {"null": ("data",)}]
+CASES = {
+    "hf_glossy_rays": ROWS + [{"k": 32}, {"k": 0xFFFFFFFF}] + [{"null": (x,)} for x in ("p", "nrm", "out_o", "out_d", "out_maxt")] +
+                      [{"null_row": x} for x in ("p", "nrm", "out_o", "out_d", "out_h")],
+    "hf_glossy_lighting": LIGHT + [{"null": (x,)} for x in ("hf", "p", "nrm")] + [{"null_row": x} for x in ("p", "nrm")] +
+                          [{"null": ("image", "value", "vis_bits")}],
+    "hf_glossy_lighting_adjoint": LIGHT + [{"null": ("vis_bits",)}, {"null_row": "grad_sh_n"}],
+    "hf_glossy_lighting_tangent": LIGHT + [{"null": ("vis_bits",)}, {"null_row": "dsh_n"}, {"null": ("dimage", "dvalue")}],
+}
+MESSAGE = {"n": "2^32", "spp": "multiple of spp", "num_rays": "1..32", "k": "below 32", "W": "2 x 2", "H": "2 x 2",
+           "eta": "eta must be", "rot": "rot must be finite", "null": "NULL", "null_row": "NULL"}
+
+
+@pytest.mark.parametrize("fn", FNS)
+def test_bad_arguments_are_refused(fn):
+    from hf_amd import _capi
+    lib = _capi.lib()
+    for kw in CASES[fn]:
+        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
+        msg = lib.hf_last_error_string().decode()
+        assert msg.startswith(fn + ":"), (kw, msg)
+        first = "spp" if "spp" in kw else next(iter(kw))
+        assert MESSAGE[first] in msg, (kw, msg)
+
+
+def test_optional_pointers_are_not_refused_for_being_null():
+    """weight, active, ray_id, rot (the identity), out_h and two of the three forward outputs may be NULL: the call then
+    fails on the LAST check made on the host (a NULL vis_bits for the derivatives, an all-NULL output set for the forward,
+    a NULL out_maxt for the rays), not before"""
+    from hf_amd import _capi
+    lib = _capi.lib()
+    for fn, last in (("hf_glossy_lighting_adjoint", ("vis_bits",)), ("hf_glossy_lighting_tangent", ("vis_bits",)),
+                     ("hf_glossy_lighting", ("image", "value", "vis_bits")), ("hf_glossy_rays", ("out_h", "out_maxt"))):
+        assert _call(lib, fn, eta=0.0, rot=None, null=("weight", "active", "ray_id") + last) == _capi.HF_EINVAL
+        msg = lib.hf_last_error_string().decode()
+        assert "NULL" in msg and "eta" not in msg and "rot" not in msg, msg
