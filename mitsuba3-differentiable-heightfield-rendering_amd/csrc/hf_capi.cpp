@@ -1122,8 +1122,8 @@ extern "C" int hf_point_lighting_tangent(size_t n, uint32_t spp, const float *co
                             (const hf_dir_light_t *) lights, albedo, vis, dsh_n, dp, nullptr, dimage, (hipStream_t) stream);
 }
 
-// ---- lighting rows, shared: what the sky, envmap and bounce entries below check and fill alike (A: the row's argument
-// block, zeroed by the caller).  All checks come before anything touches a device. ----
+// ---- lighting rows, shared: what the sky, envmap, reflect, glossy and bounce entries below check and fill alike (A: the
+// row's argument block, zeroed by the caller).  All checks come before anything touches a device. ----
 // the wavefront and the sample count; `dirs`: the row's word for its directions, other_null: a row's further pointers
 template <class A>
 static int light_args(const char *who, const char *dirs, size_t n, uint32_t spp, const float *const sh_n[3],
@@ -1139,17 +1139,18 @@ static int light_args(const char *who, const char *dirs, size_t n, uint32_t spp,
 }
 // the outputs of a *_rays entry (and the two rows only it and the forward read)
 template <class A>
-static int light_rays_out(const char *who, const float *const p[3], const float *const nrm[3], uint32_t k,
-                          float *const out_o[3], float *const out_d[3], float *out_maxt, A &a) {
+static int light_rays_out(const char *who, const float *const p[3], const float *const nrm[3], float *const out_o[3],
+                          float *const out_d[3], float *out_maxt, A &a) {
     if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", who);
-    a.k = k; a.out_maxt = out_maxt;
+    a.out_maxt = out_maxt;
     for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
     return HF_OK;
 }
-// of a forward entry
+// of a forward entry (image_optional: a row that has other outputs)
 template <class A>
-static int light_forward_out(const char *who, const float *const p[3], const float *const nrm[3], float *image, A &a) {
-    if (!all3(p) || !all3(nrm) || !image) return fail(HF_EINVAL, "%s: NULL argument", who);
+static int light_forward_out(const char *who, const float *const p[3], const float *const nrm[3], float *image, A &a,
+                             bool image_optional = false) {
+    if (!all3(p) || !all3(nrm) || (!image && !image_optional)) return fail(HF_EINVAL, "%s: NULL argument", who);
     a.image = image;
     for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
     return HF_OK;
@@ -1157,11 +1158,48 @@ static int light_forward_out(const char *who, const float *const p[3], const flo
 // the tangents of sh_n and weight (NULL: zero) and the image of a tangent entry
 template <class A>
 static int light_tangent_io(const char *who, bool other_null, const float *const dsh_n[3], const float *dweight,
-                            float *dimage, A &a) {
-    if (other_null || !dimage) return fail(HF_EINVAL, "%s: NULL argument", who);
+                            float *dimage, A &a, bool image_optional = false) {
+    if (other_null || (!dimage && !image_optional)) return fail(HF_EINVAL, "%s: NULL argument", who);
     if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", who);
     a.image = dimage; a.dw = dweight;
     for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    return HF_OK;
+}
+// The same for a row with a per-sample value beside its image (reflect, glossy).  The caller sets its visibility row
+// (vis_null: it is missing; vis_name: what the row calls it).  Forward: image, value, visibility -- at least one
+template <class A>
+static int light_value_forward_out(const char *who, const float *const p[3], const float *const nrm[3], float *image,
+                                   float *value, bool vis_null, const char *vis_name, A &a) {
+    const int rc = light_forward_out(who, p, nrm, image, a, true);
+    if (rc != HF_OK) return rc;
+    if (!image && !value && vis_null) return fail(HF_EINVAL, "%s: image, value and %s are all NULL", who, vis_name);
+    a.value = value;
+    return HF_OK;
+}
+// adjoint: dL/dimage, dL/dvalue (NULL: zero); grad_sh_n (NULL, or rows of which any may be), weight, texels (NULL: not wanted)
+template <class A>
+static int light_value_adjoint_io(const char *who, bool vis_null, const float *grad_image, const float *grad_value,
+                                  float *const grad_sh_n[3], float *grad_weight, float *grad_data, A &a) {
+    if (vis_null) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", who);
+    a.gimg = grad_image; a.gvalue = grad_value; a.gw = grad_weight; a.gdata = grad_data;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    return HF_OK;
+}
+// tangent: the tangents of sh_n, weight and the texels (NULL: zero); dimage, dvalue -- at least one
+template <class A>
+static int light_value_tangent_io(const char *who, bool vis_null, const float *const dsh_n[3], const float *dweight,
+                                  const float *ddata, float *dimage, float *dvalue, A &a) {
+    if (vis_null) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", who);
+    a.ddata = ddata; a.value = dvalue;
+    return light_tangent_io(who, false, dsh_n, dweight, dimage, a, true);
+}
+// the interface of a reflection lobe: the relative index eta (0: F = 1, an ideal mirror), rcp_eta rounded once here
+template <class A>
+static int light_interface(const char *who, float eta, A &a) {
+    if (!isfinite(eta) || eta < 0.f) return fail(HF_EINVAL, "%s: eta must be finite and not negative (got %g)", who, (double) eta);
+    a.eta = eta; a.rcp_eta = eta > 0.f ? 1.f / eta : 0.f;
     return HF_OK;
 }
 
@@ -1194,7 +1232,8 @@ extern "C" int hf_sky_rays(size_t n, const float *const p[3], const float *const
     hf_sky_args a;
     if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
     int rc = sky_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, 1.f, 1.f, a);
-    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
+    a.k = k;
     return light_launch(hf_launch_sky, 3, a, stream);
 }
 
@@ -1339,17 +1378,32 @@ extern "C" int hf_caustic_tangent(size_t n, const float *const p[3], const float
 }
 
 // ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----
-// What the hf_envmap_* entries share: the checks of the map (`a`: zeroed by the caller) ...
-static int envmap_map(const char *who, uint32_t W, uint32_t H, const float *data, bool need_data, const float *table,
-                      bool need_table, const float rot[9], hf_envmap_args &a) {
+// What every entry that reads a map shares, the reflection rows' too: the checks of the map (A: a block with W, H, data
+// and rot, zeroed by the caller), in two pieces because the entries check other things between them: the texels ...
+template <class A>
+static int envmap_texels(const char *who, uint32_t W, uint32_t H, const float *data, bool need_data, A &a) {
     if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the map must have at least 2 x 2 texels (got %u x %u)", who, W, H);
-    if ((need_data && !data) || (need_table && !table)) return fail(HF_EINVAL, "%s: NULL argument", who);
-    a.W = W; a.H = H; a.data = data; a.table = table;
+    if (need_data && !data) return fail(HF_EINVAL, "%s: NULL argument", who);
+    a.W = W; a.H = H; a.data = data;
+    return HF_OK;
+}
+// ... and the rotation (NULL: the identity)
+template <class A>
+static int envmap_rot(const char *who, const float rot[9], A &a) {
     for (int j = 0; j < 9; ++j) {
         a.rot[j] = rot ? rot[j] : (j % 4 == 0 ? 1.f : 0.f);
         if (!isfinite(a.rot[j])) return fail(HF_EINVAL, "%s: rot must be finite", who);
     }
     return HF_OK;
+}
+// the two for the hf_envmap_* entries; table: the sampling table of those that draw from it or build it (else need_table = false)
+static int envmap_map(const char *who, uint32_t W, uint32_t H, const float *data, bool need_data, const float *table,
+                      bool need_table, const float rot[9], hf_envmap_args &a) {
+    const int rc = envmap_texels(who, W, H, data, need_data, a);
+    if (rc != HF_OK) return rc;
+    if (need_table && !table) return fail(HF_EINVAL, "%s: NULL argument", who);
+    a.table = table;
+    return envmap_rot(who, rot, a);
 }
 // ... and of the wavefront, for the four entries that light one (hf_envmap_rays passes spp 1, num_rays k + 1, albedo 1)
 static int envmap_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
@@ -1431,8 +1485,8 @@ extern "C" int hf_envmap_rays(size_t n, const float *const p[3], const float *co
     hf_envmap_args a;
     if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
     int rc = envmap_args(fn, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, W, H, data, table, rot, 1.f, a);
-    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
-    a.out_weight = out_weight;
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
+    a.k = k; a.out_weight = out_weight;
     return light_launch(hf_launch_envmap, 3, a, stream);
 }
 
@@ -1493,6 +1547,13 @@ static int reflect_rows(const char *who, size_t n, const float *const sh_n[3], c
     for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
     return HF_OK;
 }
+// the map and the interface of a reflection row (glossy too), checked in the order 2 x 2, eta, rot (a NULL data: the caller's check)
+template <class A>
+static int reflect_map(const char *who, float eta, uint32_t W, uint32_t H, const float *data, const float rot[9], A &a) {
+    int rc = envmap_texels(who, W, H, data, true, a);
+    if (rc != HF_OK || (rc = light_interface(who, eta, a))) return rc;
+    return envmap_rot(who, rot, a);
+}
 // ... and the film, the interface and the map of the three lighting entries
 static int reflect_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
                         const float *t, const uint8_t *active, const float *weight, float eta, uint32_t W, uint32_t H,
@@ -1501,15 +1562,8 @@ static int reflect_args(const char *who, size_t n, uint32_t spp, const float *co
     if (rc != HF_OK) return rc;
     if (!data) return fail(HF_EINVAL, "%s: NULL argument", who);
     if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
-    if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the map must have at least 2 x 2 texels (got %u x %u)", who, W, H);
-    if (!isfinite(eta) || eta < 0.f) return fail(HF_EINVAL, "%s: eta must be finite and not negative (got %g)", who, (double) eta);
-    a.spp = spp; a.weight = weight; a.W = W; a.H = H; a.data = data;
-    a.eta = eta; a.rcp_eta = eta > 0.f ? 1.f / eta : 0.f;
-    for (int j = 0; j < 9; ++j) {
-        a.rot[j] = rot ? rot[j] : (j % 4 == 0 ? 1.f : 0.f);
-        if (!isfinite(a.rot[j])) return fail(HF_EINVAL, "%s: rot must be finite", who);
-    }
-    return HF_OK;
+    a.spp = spp; a.weight = weight;
+    return reflect_map(who, eta, W, H, data, rot, a);
 }
 
 extern "C" int hf_reflect_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
@@ -1517,12 +1571,9 @@ extern "C" int hf_reflect_rays(size_t n, const float *const p[3], const float *c
                                float *const out_d[3], float *out_maxt, hf_stream_t stream) {
     const char *fn = "hf_reflect_rays";
     hf_reflect_args a;
-    const int rc = reflect_rows(fn, n, sh_n, d, t, active, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm) || !all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    int rc = reflect_rows(fn, n, sh_n, d, t, active, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
     a.eta = 1.f; a.rcp_eta = 1.f; // (the direction does not depend on the interface)
-    a.out_maxt = out_maxt;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
     return light_launch(hf_launch_reflect, 3, a, stream);
 }
 
@@ -1535,13 +1586,10 @@ extern "C" int hf_reflect_lighting(const hf_field_t *hf, size_t n, uint32_t spp,
     hf_reflect_args a;
     if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
     int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm)) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (!image && !value && !vis) return fail(HF_EINVAL, "%s: image, value and vis are all NULL", fn);
+    if (rc != HF_OK || (rc = light_value_forward_out(fn, p, nrm, image, value, !vis, "vis", a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.image = image; a.value = value; a.vis = vis;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    a.f = hf->dev; a.vis = vis;
     return light_launch(hf_launch_reflect, 0, a, stream);
 }
 
@@ -1552,12 +1600,9 @@ extern "C" int hf_reflect_lighting_adjoint(size_t n, uint32_t spp, const float *
                                            float *grad_weight, float *grad_data, hf_stream_t stream) {
     const char *fn = "hf_reflect_lighting_adjoint";
     hf_reflect_args a;
-    const int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
-    if (rc != HF_OK) return rc;
-    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
-    a.vis = const_cast<uint8_t *>(vis); a.gimg = grad_image; a.gvalue = grad_value; a.gw = grad_weight; a.gdata = grad_data;
-    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
+    if (rc != HF_OK || (rc = light_value_adjoint_io(fn, !vis, grad_image, grad_value, grad_sh_n, grad_weight, grad_data, a))) return rc;
+    a.vis = const_cast<uint8_t *>(vis);
     return light_launch(hf_launch_reflect, 1, a, stream);
 }
 
@@ -1568,13 +1613,9 @@ extern "C" int hf_reflect_lighting_tangent(size_t n, uint32_t spp, const float *
                                            float *dimage, float *dvalue, hf_stream_t stream) {
     const char *fn = "hf_reflect_lighting_tangent";
     hf_reflect_args a;
-    const int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
-    if (rc != HF_OK) return rc;
-    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
-    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
-    a.vis = const_cast<uint8_t *>(vis); a.dw = dweight; a.ddata = ddata; a.image = dimage; a.value = dvalue;
-    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    int rc = reflect_args(fn, n, spp, sh_n, d, t, active, weight, eta, W, H, data, rot, a);
+    if (rc != HF_OK || (rc = light_value_tangent_io(fn, !vis, dsh_n, dweight, ddata, dimage, dvalue, a))) return rc;
+    a.vis = const_cast<uint8_t *>(vis);
     return light_launch(hf_launch_reflect, 2, a, stream);
 }
 
@@ -1598,15 +1639,8 @@ static int glossy_args(const char *who, size_t n, uint32_t spp, const float *con
     const int rc = glossy_rows(who, n, spp, sh_n, d, t, active, alpha, num_rays, seed, ray_id, a);
     if (rc != HF_OK) return rc;
     if (!data) return fail(HF_EINVAL, "%s: NULL argument", who);
-    if (W < 2 || H < 2) return fail(HF_EINVAL, "%s: the map must have at least 2 x 2 texels (got %u x %u)", who, W, H);
-    if (!isfinite(eta) || eta < 0.f) return fail(HF_EINVAL, "%s: eta must be finite and not negative (got %g)", who, (double) eta);
-    a.weight = weight; a.W = W; a.H = H; a.data = data;
-    a.eta = eta; a.rcp_eta = eta > 0.f ? 1.f / eta : 0.f;
-    for (int j = 0; j < 9; ++j) {
-        a.rot[j] = rot ? rot[j] : (j % 4 == 0 ? 1.f : 0.f);
-        if (!isfinite(a.rot[j])) return fail(HF_EINVAL, "%s: rot must be finite", who);
-    }
-    return HF_OK;
+    a.weight = weight;
+    return reflect_map(who, eta, W, H, data, rot, a);
 }
 
 extern "C" int hf_glossy_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
@@ -1617,9 +1651,9 @@ extern "C" int hf_glossy_rays(size_t n, const float *const p[3], const float *co
     hf_glossy_args a;
     if (k >= 32) return fail(HF_EINVAL, "%s: direction k must be below 32 (got %u)", fn, k);
     int rc = glossy_rows(fn, n, 1, sh_n, d, t, active, alpha, k + 1, seed, ray_id, a);
-    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
     if (out_h && !all3(out_h)) return fail(HF_EINVAL, "%s: NULL out_h component array", fn);
-    a.eta = 1.f; a.rcp_eta = 1.f; // (the direction does not depend on the interface)
+    a.k = k; a.eta = 1.f; a.rcp_eta = 1.f; // (the direction does not depend on the interface)
     for (int c = 0; c < 3; ++c) a.out_h[c] = out_h ? out_h[c] : nullptr;
     return light_launch(hf_launch_glossy, 3, a, stream);
 }
@@ -1634,13 +1668,10 @@ extern "C" int hf_glossy_lighting(const hf_field_t *hf, size_t n, uint32_t spp, 
     hf_glossy_args a;
     if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
     int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
-    if (rc != HF_OK) return rc;
-    if (!all3(p) || !all3(nrm)) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (!image && !value && !vis_bits) return fail(HF_EINVAL, "%s: image, value and vis_bits are all NULL", fn);
+    if (rc != HF_OK || (rc = light_value_forward_out(fn, p, nrm, image, value, !vis_bits, "vis_bits", a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.image = image; a.value = value; a.vis_bits = vis_bits;
-    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; }
+    a.f = hf->dev; a.vis_bits = vis_bits;
     return light_launch(hf_launch_glossy, 0, a, stream);
 }
 
@@ -1652,13 +1683,9 @@ extern "C" int hf_glossy_lighting_adjoint(size_t n, uint32_t spp, const float *c
                                           float *grad_weight, float *grad_alpha, float *grad_data, hf_stream_t stream) {
     const char *fn = "hf_glossy_lighting_adjoint";
     hf_glossy_args a;
-    const int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
-    if (rc != HF_OK) return rc;
-    if (!vis_bits) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
-    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.gimg = grad_image; a.gvalue = grad_value;
-    a.gw = grad_weight; a.ga = grad_alpha; a.gdata = grad_data;
-    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
+    if (rc != HF_OK || (rc = light_value_adjoint_io(fn, !vis_bits, grad_image, grad_value, grad_sh_n, grad_weight, grad_data, a))) return rc;
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.ga = grad_alpha;
     return light_launch(hf_launch_glossy, 1, a, stream);
 }
 
@@ -1670,13 +1697,9 @@ extern "C" int hf_glossy_lighting_tangent(size_t n, uint32_t spp, const float *c
                                           const float *ddata, float *dimage, float *dvalue, hf_stream_t stream) {
     const char *fn = "hf_glossy_lighting_tangent";
     hf_glossy_args a;
-    const int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
-    if (rc != HF_OK) return rc;
-    if (!vis_bits) return fail(HF_EINVAL, "%s: NULL argument", fn);
-    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
-    if (dsh_n && !all3(dsh_n)) return fail(HF_EINVAL, "%s: NULL dsh_n component array", fn);
-    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.dw = dweight; a.da = dalpha; a.ddata = ddata; a.image = dimage; a.value = dvalue;
-    for (int c = 0; c < 3; ++c) a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+    int rc = glossy_args(fn, n, spp, sh_n, d, t, active, weight, alpha, eta, num_rays, seed, ray_id, W, H, data, rot, a);
+    if (rc != HF_OK || (rc = light_value_tangent_io(fn, !vis_bits, dsh_n, dweight, ddata, dimage, dvalue, a))) return rc;
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.da = dalpha;
     return light_launch(hf_launch_glossy, 2, a, stream);
 }
 
@@ -1724,10 +1747,10 @@ extern "C" int hf_bounce_rays(const hf_field_t *hf, size_t n, const float *const
     hf_dir_light_t one = { { 0.f, 0.f, 1.f }, 1.f };
     if (to_light) for (int c = 0; c < 3; ++c) one.to_light[c] = to_light[c];
     int rc = bounce_args(fn, hf, n, 1, sh_n, d, t, nullptr, k + 1, seed, ray_id, 1, &one, 1.f, a);
-    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, k, out_o, out_d, out_maxt, a))) return rc;
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
     if (n == 0) return HF_OK;
     if ((rc = check_device(fn, hf))) return rc;
-    a.f = hf->dev; a.shadow = to_light ? 1 : 0;
+    a.f = hf->dev; a.k = k; a.shadow = to_light ? 1 : 0;
     return light_launch(hf_launch_bounce, 3, a, stream);
 }
 

@@ -3651,10 +3651,12 @@ void hf_launch_film_motion(int mode, const hf_film_motion_args &a, hipStream_t s
 }
 
 // ---------------------------------------------------------------------------------
-// Lighting rows, shared: what the sky, bounce and envmap sections below have in common -- the per-lane walk of a shadow
-// or bounce ray, the f64 sine / cosine of their shading sums, the first reads of a derivative or rays kernel, the ray
-// store, the tangent shell and the launch.  Only text that is the same for every row belongs here; nothing in this block
-// asks which row calls it (A: the row's argument struct, its common fields under their common names).
+// Lighting rows, shared: what the sky, bounce, envmap, reflect and glossy sections below have in common -- the per-lane
+// walk of a shadow or bounce ray, the f64 sine / cosine of their shading sums, the first reads of a derivative or rays
+// kernel, the ray stores, the seed and the optional outputs of an adjoint, the tangent shell and the launch.  (The map
+// lookup of the last three, env_texels / env_scatter4 / env_gather4, stands beside env_lookup in the envmap section.)
+// Only text that is the same for every row belongs here; nothing in this block asks which row calls it (A: the row's
+// argument struct, its common fields under their common names).
 // ---------------------------------------------------------------------------------
 // the masks of hf_direct_kernel: a hit seen from the front (diffuse.cpp:137)
 __device__ __forceinline__ bool sky_eligible(float t, v3 sn, v3 d) { return (t != __builtin_inff()) && (-dot3(sn, d) > 0.f); }
@@ -3719,6 +3721,14 @@ __device__ __forceinline__ bool light_sample(const A &a, size_t i, v3 &sn) {
 }
 template <class A>
 __device__ __forceinline__ uint32_t light_id(const A &a, size_t i) { return a.ray_id ? a.ray_id[i] : (uint32_t) i; }
+// Interaction::offset_p (interaction.h:161-165) without the direction: (1 + max|p|) RayEpsilon, RayEpsilon = 1500 * 2^-24
+__device__ __forceinline__ float sky_offset(v3 p) {
+    return (1.f + fmaxf(fmaxf(__builtin_fabsf(p.x), __builtin_fabsf(p.y)), __builtin_fabsf(p.z))) * 8.940696716308594e-05f;
+}
+// origin of spawn_ray(w) (interaction.h:134-136): p moved along the geometric normal to the side w points to
+__device__ __forceinline__ v3 sky_origin(v3 p, v3 gn, float mag, v3 w) {
+    return fma3(gn, dot3(gn, w) < 0.f ? -mag : mag, p);
+}
 // a materialised ray; maxt = -1: the fused kernel does not trace it
 template <class A>
 __device__ __forceinline__ void light_store_ray(const A &a, size_t i, v3 o, v3 d, bool traced) {
@@ -3726,23 +3736,52 @@ __device__ __forceinline__ void light_store_ray(const A &a, size_t i, v3 o, v3 d
     a.out_d[0][i] = d.x; a.out_d[1][i] = d.y; a.out_d[2][i] = d.z;
     a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
 }
+// the same for a row whose untraced lanes get a zero origin and direction: spawn_ray(w) where the fused kernel walks it
+template <class A>
+__device__ __forceinline__ void light_store_spawned(const A &a, size_t i, v3 p, v3 gn, v3 w, bool traced) {
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    light_store_ray(a, i, traced ? sky_origin(p, gn, sky_offset(p), w) : z, traced ? w : z, traced);
+}
+// what the adjoint of a row with an image and a per-sample value starts from: dL/dvalue of sample i (NULL: zero)
+template <class A>
+__device__ __forceinline__ float light_value_seed(const A &a, size_t i) {
+    return (a.gimg ? a.gimg[i / a.spp] * (1.0f / (float) a.spp) : 0.f) + (a.gvalue ? a.gvalue[i] : 0.f);
+}
+// an adjoint's output of three optional rows, and the gradients of sh_n and weight of such a row (NULL: not wanted)
+__device__ __forceinline__ void light_store3(float *const r[3], size_t i, v3 g) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        if (r[c]) r[c][i] = c == 0 ? g.x : c == 1 ? g.y : g.z;
+}
+template <class A>
+__device__ __forceinline__ void light_store_grads(const A &a, size_t i, v3 gn, float gw) {
+    light_store3(a.gn, i, gn);
+    if (a.gw) a.gw[i] = gw;
+}
 
 // The tangent image of a row with one channel, VALUE(a, i) the tangent of sample i's value.  PIXEL = false: one lane per
-// sample and the primal's film (spp a power of two <= 64: its shuffle tree, one store per pixel); PIXEL = true (any
-// other spp): one lane per pixel adds its samples in order -- no atomics either way
+// sample and the primal's film (spp a power of two <= 64: its shuffle tree, one store per pixel; or no image wanted);
+// PIXEL = true (any other spp): one lane per pixel adds its samples in order -- no atomics either way.  `value`: the
+// per-sample tangents, for the rows that have them (NULL: not wanted; the literal nullptr of the rows that have none
+// compiles the stores away); such a row's `image` may be NULL too
 template <bool PIXEL, class A, float (*VALUE)(const A &, size_t)>
-__device__ __forceinline__ void light_tangent_image(const A &a) {
+__device__ __forceinline__ void light_tangent_image(const A &a, float *value) {
     const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
     const uint32_t spp = a.spp;
     if (PIXEL) {
         if (i >= a.n / spp) return;
         float c = 0.f;
-        for (uint32_t s = 0; s < spp; ++s) c += VALUE(a, i * spp + s);
+        for (uint32_t s = 0; s < spp; ++s) {
+            const float dv = VALUE(a, i * spp + s);
+            if (value) value[i * spp + s] = dv;
+            c += dv;
+        }
         a.image[i] = c * (1.0f / (float) spp);
     } else {
         const bool in = i < a.n;
         const float c = VALUE(a, in ? i : a.n - 1);
-        film_pixel(a.image, in ? c : 0.f, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
+        if (in && value) value[i] = c;
+        if (a.image) film_pixel(a.image, in ? c : 0.f, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
     }
 }
 
@@ -3750,12 +3789,13 @@ __device__ __forceinline__ void light_tangent_image(const A &a) {
 // which want a zeroed image
 static bool sky_tree_film(uint32_t spp) { return (spp & (spp - 1u)) == 0u && spp <= 64u; }
 
-// modes 0 to 3 of a row: forward (`channels` film planes), adjoint, tangent, rays
+// modes 0 to 3 of a row: forward (`channels` film planes), adjoint, tangent, rays.  A NULL image (the rows with a
+// per-sample value): no film to clear, and the tangent with one lane per sample
 template <class A>
 static void launch_light(int mode, const A &a, uint32_t channels, hipStream_t stream, void (*forward)(A), void (*adjoint)(A),
                          void (*tangent)(A), void (*tangent_pixel)(A), void (*rays)(A)) {
     if (a.n == 0) return;
-    const bool tree = sky_tree_film(a.spp);
+    const bool tree = sky_tree_film(a.spp) || !a.image;
     const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
     if (mode == 0 && !tree) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp) * channels, stream);
     if (mode == 2 && !tree)
@@ -3820,14 +3860,6 @@ __device__ __forceinline__ v3 sky_dir(uint32_t seed, uint32_t k, uint32_t id) {
     float sn, cs;
     sincospif(2.f * sx, &sn, &cs);
     return mk3(r * cs, r * sn, z);
-}
-// Interaction::offset_p (interaction.h:161-165) without the direction: (1 + max|p|) RayEpsilon, RayEpsilon = 1500 * 2^-24
-__device__ __forceinline__ float sky_offset(v3 p) {
-    return (1.f + fmaxf(fmaxf(__builtin_fabsf(p.x), __builtin_fabsf(p.y)), __builtin_fabsf(p.z))) * 8.940696716308594e-05f;
-}
-// origin of spawn_ray(w) (interaction.h:134-136): p moved along the geometric normal to the side w points to
-__device__ __forceinline__ v3 sky_origin(v3 p, v3 gn, float mag, v3 w) {
-    return fma3(gn, dot3(gn, w) < 0.f ? -mag : mag, p);
 }
 
 // The same direction in double, for the SHADING sums (the cosines of the forward, the sums of directions of the
@@ -3966,7 +3998,7 @@ __device__ __forceinline__ float sky_tangent_value(const hf_sky_args &a, size_t 
 }
 template <bool PIXEL>
 __global__ __launch_bounds__(HF_BLOCK) void hf_sky_tangent_kernel(hf_sky_args a) {
-    light_tangent_image<PIXEL, hf_sky_args, sky_tangent_value>(a);
+    light_tangent_image<PIXEL, hf_sky_args, sky_tangent_value>(a, nullptr);
 }
 
 void hf_launch_sky(int mode, const hf_sky_args &a, hipStream_t stream) {
@@ -4125,12 +4157,8 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_caustic_adjoint_kernel(hf_caustic
             gw = a.power * (1.f - v.F) * gv;
         }
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (a.gn[c]) a.gn[c][i] = c == 0 ? gm.x : c == 1 ? gm.y : gm.z;
-        if (a.gp[c]) a.gp[c][i] = c == 0 ? gp.x : c == 1 ? gp.y : gp.z;
-    }
-    if (a.gw) a.gw[i] = gw;
+    light_store_grads(a, i, gm, gw);
+    light_store3(a.gp, i, gp);
 }
 
 // forward mode, the transpose of the above: tangents dn of sh_n, dp of p, dw of weight (NULL: zero)
@@ -5650,6 +5678,38 @@ __device__ __forceinline__ void env_lookup(const A &a, v3 d, uint32_t &cx, uint3
     cx = min((uint32_t) fmax(ux, 0.0), a.W - 2u); cy = min((uint32_t) fmax(uy, 0.0), a.H - 2u);
     fx = ux - (double) cx; fy = uy - (double) cy;
 }
+// THE lookup of a world direction, for every kernel that evaluates the map or differentiates the evaluation: the first
+// texel's index, the position in the cell and its complements, the four bilinear weights and the four texels (v00, v10,
+// v01, v11; TEXELS = false: not read -- the map is linear, its adjoint needs no values), all in double
+struct hf_env_texels {
+    size_t r0;
+    double fx, fy, gx, gy, bw[4], v[4];
+    // Emitter::eval, rounded once.  Every radiance a kernel reports is THIS expression: hf_envmap_eval and the
+    // reflection rows agree bit for bit because there is no second one
+    __device__ __forceinline__ float value() const { return (float) (gy * (gx * v[0] + fx * v[1]) + fy * (gx * v[2] + fx * v[3])); }
+};
+template <bool TEXELS = true, class A>
+__device__ __forceinline__ hf_env_texels env_texels(const A &a, const float *data, v3 d) {
+    hf_env_texels e;
+    uint32_t cx, cy;
+    env_lookup(a, d, cx, cy, e.fx, e.fy);
+    e.r0 = (size_t) cy * a.W + cx;
+    const size_t r1 = e.r0 + a.W;
+    e.gx = 1.0 - e.fx; e.gy = 1.0 - e.fy;
+    e.bw[0] = e.gy * e.gx; e.bw[1] = e.gy * e.fx; e.bw[2] = e.fy * e.gx; e.bw[3] = e.fy * e.fx;
+    e.v[0] = TEXELS ? (double) data[e.r0] : 0.0; e.v[1] = TEXELS ? (double) data[e.r0 + 1] : 0.0;
+    e.v[2] = TEXELS ? (double) data[r1] : 0.0;   e.v[3] = TEXELS ? (double) data[r1 + 1] : 0.0;
+    return e;
+}
+// the texel terms of a derivative, for bilinear weights bw about the texel r0 of a map with W texels per row:
+// gdata += q bw (each product rounded once; four float atomics), and sum_j bw_j ddata_j in double
+__device__ __forceinline__ void env_scatter4(float *gdata, uint32_t W, size_t r0, const double bw[4], double q) {
+    atomicAdd(gdata + r0, (float) (q * bw[0])); atomicAdd(gdata + r0 + 1, (float) (q * bw[1]));
+    atomicAdd(gdata + r0 + W, (float) (q * bw[2])); atomicAdd(gdata + r0 + W + 1, (float) (q * bw[3]));
+}
+__device__ __forceinline__ double env_gather4(const float *ddata, uint32_t W, size_t r0, const double bw[4]) {
+    return bw[0] * (double) ddata[r0] + bw[1] * (double) ddata[r0 + 1] + bw[2] * (double) ddata[r0 + W] + bw[3] * (double) ddata[r0 + W + 1];
+}
 // ADJ = false: out[i] = the bilinear value, rounded once, 0 for an inactive lane;
 // ADJ = true: grad_data += grad_out[i] * the bilinear weights (each product rounded once; float atomics)
 template <bool ADJ>
@@ -5661,19 +5721,9 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_eval_kernel(hf_envmap_args
         if (!ADJ) a.out[i] = 0.f;
         return;
     }
-    uint32_t cx, cy;
-    double fx, fy;
-    env_lookup(a, mk3(a.d[0][i], a.d[1][i], a.d[2][i]), cx, cy, fx, fy);
-    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
-    const double gx = 1.0 - fx, gy = 1.0 - fy;
-    if (!ADJ) {
-        a.out[i] = (float) (gy * (gx * (double) a.data[r0] + fx * (double) a.data[r0 + 1]) +
-                            fy * (gx * (double) a.data[r1] + fx * (double) a.data[r1 + 1]));
-    } else {
-        const double g = (double) a.gout[i];
-        atomicAdd(a.gdata + r0, (float) (g * (gy * gx))); atomicAdd(a.gdata + r0 + 1, (float) (g * (gy * fx)));
-        atomicAdd(a.gdata + r1, (float) (g * (fy * gx))); atomicAdd(a.gdata + r1 + 1, (float) (g * (fy * fx)));
-    }
+    const hf_env_texels e = env_texels<!ADJ>(a, a.data, mk3(a.d[0][i], a.d[1][i], a.d[2][i]));
+    if (!ADJ) a.out[i] = e.value();
+    else env_scatter4(a.gdata, a.W, e.r0, e.bw, (double) a.gout[i]);
 }
 
 // what the derivative kernels need of direction k of sample i: drawn again, nothing traced
@@ -5711,11 +5761,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_adjoint_kernel(hf_envmap_a
                 const double E = s.L * s.G, co = sky_dot_f64(sn, s.w);
                 sx += s.w.x * E; sy += s.w.y * E; sz += s.w.z * E;
                 sc += co * E;
-                if (a.gdata) {
-                    const double q = (double) cw * (co * s.G);
-                    atomicAdd(a.gdata + r0, (float) (q * s.bw[0])); atomicAdd(a.gdata + r0 + 1, (float) (q * s.bw[1]));
-                    atomicAdd(a.gdata + r0 + a.W, (float) (q * s.bw[2])); atomicAdd(a.gdata + r0 + a.W + 1, (float) (q * s.bw[3]));
-                }
+                if (a.gdata) env_scatter4(a.gdata, a.W, r0, s.bw, (double) cw * (co * s.G));
             }
         }
         g = mk3((float) sx, (float) sy, (float) sz) * cw;
@@ -5737,10 +5783,7 @@ __device__ __forceinline__ float envmap_tangent_value(const hf_envmap_args &a, s
             size_t r0;
             const hf_env_shade s = env_shade(a, k, id, r0);
             const double co = sky_dot_f64(sn, s.w);
-            double dL = 0.0;
-            if (a.ddata)
-                dL = s.bw[0] * (double) a.ddata[r0] + s.bw[1] * (double) a.ddata[r0 + 1] + s.bw[2] * (double) a.ddata[r0 + a.W] +
-                     s.bw[3] * (double) a.ddata[r0 + a.W + 1];
+            const double dL = a.ddata ? env_gather4(a.ddata, a.W, r0, s.bw) : 0.0;
             sd += (sky_dot_f64(dn, s.w) * s.L + co * dL) * s.G;
             sc += co * (s.L * s.G);
         }
@@ -5749,7 +5792,7 @@ __device__ __forceinline__ float envmap_tangent_value(const hf_envmap_args &a, s
 }
 template <bool PIXEL>
 __global__ __launch_bounds__(HF_BLOCK) void hf_envmap_tangent_kernel(hf_envmap_args a) {
-    light_tangent_image<PIXEL, hf_envmap_args, envmap_tangent_value>(a);
+    light_tangent_image<PIXEL, hf_envmap_args, envmap_tangent_value>(a, nullptr);
 }
 
 void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream) {
@@ -5767,8 +5810,10 @@ void hf_launch_envmap(int mode, const hf_envmap_args &a, hipStream_t stream) {
 // Specular reflection of the environment map (include/hf.h hf_reflect_*): every wavefront sample is mirrored at its
 // shading normal (reflect(wi, m), fresnel.h:282-284; the `dielectric` reflection lobe, or an ideal mirror for eta = 0),
 // the reflected ray is walked (any hit, per lane, maxt = +inf) and what escapes looks the map up (Emitter::eval of
-// envmap.cpp, env_lookup above, in double).  ONE launch, one lane per sample; nothing of the ray goes to memory.  A
-// reflected ray that hits the terrain contributes 0: no second vertex.
+// envmap.cpp: env_texels above, in double, the expression hf_envmap_eval_kernel rounds).  ONE launch, one lane per
+// sample; nothing of the ray goes to memory.  A reflected ray that hits the terrain contributes 0: no second vertex.
+// The row's own text is its vertex and the direction derivative of the lookup; the ray store, the adjoint's seed and
+// outputs, the texel terms, the tangent film and the launch are the lighting rows' shared functions.
 // ---------------------------------------------------------------------------------
 // The specular vertex of one sample, the same text for the fused kernel, the rays kernel and the two derivatives:
 // fresnel() as caustic_vertex has it (c > 0 on every lane that is used: the outside branch) and reflect().
@@ -5812,31 +5857,11 @@ __device__ __forceinline__ hf_reflect_vertex reflect_sample(P a, size_t i, v3 &m
     m = mk3(a->sh_n[0][i], a->sh_n[1][i], a->sh_n[2][i]);
     return reflect_vertex(a, m, mk3(a->d[0][i], a->d[1][i], a->d[2][i]));
 }
-// Emitter::eval for the direction w: hf_envmap_eval_kernel's expression, rounded once
-template <class A>
-__device__ __forceinline__ float reflect_radiance(const A &a, const float *data, v3 w) {
-    uint32_t cx, cy;
-    double fx, fy;
-    env_lookup(a, w, cx, cy, fx, fy);
-    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
-    const double gx = 1.0 - fx, gy = 1.0 - fy;
-    return (float) (gy * (gx * (double) data[r0] + fx * (double) data[r0 + 1]) + fy * (gx * (double) data[r1] + fx * (double) data[r1 + 1]));
-}
-// what the derivative kernels need of the lookup: the radiance, the bilinear weights, the first texel's index and
-// G = R dL/dv, the derivative of the radiance with respect to the world direction with the cell held (exactly 0 at
-// the poles of the map); formed in double from the same lookup, each rounded once
-struct hf_reflect_shade { float L; v3 G; double bw[4]; size_t r0; };
-__device__ __forceinline__ hf_reflect_shade reflect_shade(const hf_reflect_args &a, v3 w) {
-    hf_reflect_shade s;
-    uint32_t cx, cy;
-    double fx, fy;
-    env_lookup(a, w, cx, cy, fx, fy);
-    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
-    const double gx = 1.0 - fx, gy = 1.0 - fy;
-    const double v00 = (double) a.data[r0], v10 = (double) a.data[r0 + 1], v01 = (double) a.data[r1], v11 = (double) a.data[r1 + 1];
-    s.L = (float) (gy * (gx * v00 + fx * v10) + fy * (gx * v01 + fx * v11));
-    s.bw[0] = gy * gx; s.bw[1] = gy * fx; s.bw[2] = fy * gx; s.bw[3] = fy * fx;
-    s.r0 = r0;
+// what the derivative kernels need of the lookup beyond env_texels (the radiance e.value(), the bilinear weights, the
+// first texel's index): G = R dL/dv, the derivative of the radiance with respect to the world direction with the cell
+// held (exactly 0 at the poles of the map); formed in double from the same lookup `e` of w, each component rounded once
+__device__ __forceinline__ v3 reflect_shade(const hf_reflect_args &a, const hf_env_texels &e, v3 w) {
+    const double fx = e.fx, fy = e.fy, gx = e.gx, gy = e.gy, v00 = e.v[0], v10 = e.v[1], v01 = e.v[2], v11 = e.v[3];
     const float *R = a.rot;
     const double vx = (double) R[0] * w.x + (double) R[3] * w.y + (double) R[6] * w.z;
     const double vy = (double) R[1] * w.x + (double) R[4] * w.y + (double) R[7] * w.z;
@@ -5849,10 +5874,9 @@ __device__ __forceinline__ hf_reflect_shade reflect_shade(const hf_reflect_args 
         lx = -(kx * vz); lz = kx * vx;
         ly = -(Ly * (double) (a.H - 1u) / 3.141592653589793 / sqrt(q));
     }
-    s.G = mk3((float) ((double) R[0] * lx + (double) R[1] * ly + (double) R[2] * lz),
-              (float) ((double) R[3] * lx + (double) R[4] * ly + (double) R[5] * lz),
-              (float) ((double) R[6] * lx + (double) R[7] * ly + (double) R[8] * lz));
-    return s;
+    return mk3((float) ((double) R[0] * lx + (double) R[1] * ly + (double) R[2] * lz),
+               (float) ((double) R[3] * lx + (double) R[4] * ly + (double) R[5] * lz),
+               (float) ((double) R[6] * lx + (double) R[7] * ly + (double) R[8] * lz));
 }
 
 typedef const __attribute__((address_space(4))) hf_reflect_args *hf_reflect_kargs;
@@ -5894,7 +5918,7 @@ __global__ __launch_bounds__(HF_BLOCK, HF_REFLECT_WAVES) void hf_reflect_kernel(
     float val = 0.f;
     if (lit) {
         const float *weight = ko->weight;
-        const float L = reflect_radiance(*ko, ko->data, wr);
+        const float L = env_texels(*ko, ko->data, wr).value();
         val = (weight ? weight[i] * F : F) * L;
     }
     if (in) {
@@ -5918,9 +5942,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_reflect_rays_kernel(hf_reflect_ar
     v3 m;
     const hf_reflect_vertex v = reflect_sample(&a, i, m);
     const v3 gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
-    const bool traced = reflect_traced(v, gn, a.t[i], a.active ? a.active[i] != 0 : true);
-    const v3 z = mk3(0.f, 0.f, 0.f);
-    light_store_ray(a, i, traced ? sky_origin(p, gn, sky_offset(p), v.wr) : z, traced ? v.wr : z, traced);
+    light_store_spawned(a, i, p, gn, v.wr, reflect_traced(v, gn, a.t[i], a.active ? a.active[i] != 0 : true));
 }
 
 // Reverse mode of hf_reflect_kernel with respect to sh_n, weight and the texels: nothing is traced, the vertex is
@@ -5934,22 +5956,17 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_reflect_adjoint_kernel(hf_reflect
     if (a.vis[i]) {
         v3 m;
         const hf_reflect_vertex v = reflect_sample(&a, i, m);
-        const hf_reflect_shade s = reflect_shade(a, v.wr);
-        const float g = (a.gimg ? a.gimg[i / a.spp] * (1.0f / (float) a.spp) : 0.f) + (a.gvalue ? a.gvalue[i] : 0.f);
+        const hf_env_texels e = env_texels(a, a.data, v.wr);
+        const float L = e.value();
+        const v3 G = reflect_shade(a, e, v.wr);
+        const float g = light_value_seed(a, i);
         const float gwt = a.weight ? g * a.weight[i] : g;
-        gw = g * (v.F * s.L);
-        const float k = __builtin_fmaf(v.dF, s.L, (2.f * v.F) * dot3(m, s.G));
-        gm = fma3(v.wi, k, s.G * ((2.f * v.F) * v.c)) * gwt;
-        if (a.gdata) {
-            const double q = (double) (gwt * v.F);
-            atomicAdd(a.gdata + s.r0, (float) (q * s.bw[0])); atomicAdd(a.gdata + s.r0 + 1, (float) (q * s.bw[1]));
-            atomicAdd(a.gdata + s.r0 + a.W, (float) (q * s.bw[2])); atomicAdd(a.gdata + s.r0 + a.W + 1, (float) (q * s.bw[3]));
-        }
+        gw = g * (v.F * L);
+        const float k = __builtin_fmaf(v.dF, L, (2.f * v.F) * dot3(m, G));
+        gm = fma3(v.wi, k, G * ((2.f * v.F) * v.c)) * gwt;
+        if (a.gdata) env_scatter4(a.gdata, a.W, e.r0, e.bw, (double) (gwt * v.F));
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        if (a.gn[c]) a.gn[c][i] = c == 0 ? gm.x : c == 1 ? gm.y : gm.z;
-    if (a.gw) a.gw[i] = gw;
+    light_store_grads(a, i, gm, gw);
 }
 
 // forward mode, the transpose of the above: the tangent of sample i's value for tangents dn of sh_n, dw of weight and
@@ -5958,52 +5975,27 @@ __device__ __forceinline__ float reflect_tangent_value(const hf_reflect_args &a,
     if (!a.vis[i]) return 0.f;
     v3 m;
     const hf_reflect_vertex v = reflect_sample(&a, i, m);
-    const hf_reflect_shade s = reflect_shade(a, v.wr);
+    const hf_env_texels e = env_texels(a, a.data, v.wr);
+    const float L = e.value();
+    const v3 G = reflect_shade(a, e, v.wr);
     const v3 dm = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
     const float w = a.weight ? a.weight[i] : 1.f, dw = a.dw ? a.dw[i] : 0.f;
     const float dci = dot3(dm, v.wi);
-    const float k = __builtin_fmaf(v.dF, s.L, (2.f * v.F) * dot3(m, s.G));
-    float dv = __builtin_fmaf(k, dci, ((2.f * v.F) * v.c) * dot3(s.G, dm));
-    if (a.ddata)
-        dv += v.F * (float) (s.bw[0] * (double) a.ddata[s.r0] + s.bw[1] * (double) a.ddata[s.r0 + 1] +
-                             s.bw[2] * (double) a.ddata[s.r0 + a.W] + s.bw[3] * (double) a.ddata[s.r0 + a.W + 1]);
-    return __builtin_fmaf(dw, v.F * s.L, w * dv);
+    const float k = __builtin_fmaf(v.dF, L, (2.f * v.F) * dot3(m, G));
+    float dv = __builtin_fmaf(k, dci, ((2.f * v.F) * v.c) * dot3(G, dm));
+    if (a.ddata) dv += v.F * (float) env_gather4(a.ddata, a.W, e.r0, e.bw);
+    return __builtin_fmaf(dw, v.F * L, w * dv);
 }
-// PIXEL = false: one lane per sample and the primal's film (spp a power of two <= 64, or no image wanted); PIXEL = true
-// (any other spp): one lane per pixel adds its samples in order -- no atomics either way (light_tangent_image, with
-// the per-sample tangent written too)
+// (the per-sample tangent is written too, and the image may be NULL)
 template <bool PIXEL>
 __global__ __launch_bounds__(HF_BLOCK) void hf_reflect_tangent_kernel(hf_reflect_args a) {
-    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
-    const uint32_t spp = a.spp;
-    if (PIXEL) {
-        if (i >= a.n / spp) return;
-        float c = 0.f;
-        for (uint32_t s = 0; s < spp; ++s) {
-            const float dv = reflect_tangent_value(a, i * spp + s);
-            if (a.value) a.value[i * spp + s] = dv;
-            c += dv;
-        }
-        a.image[i] = c * (1.0f / (float) spp);
-    } else {
-        const bool in = i < a.n;
-        const float c = in ? reflect_tangent_value(a, i) : 0.f;
-        if (in && a.value) a.value[i] = c;
-        if (a.image) film_pixel(a.image, c, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
-    }
+    light_tangent_image<PIXEL, hf_reflect_args, reflect_tangent_value>(a, a.value);
 }
 
-// mode 0: forward, 1: adjoint, 2: tangent, 3: rays (launch_light, with an image that may be NULL)
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays
 void hf_launch_reflect(int mode, const hf_reflect_args &a, hipStream_t stream) {
-    if (a.n == 0) return;
-    const bool tree = sky_tree_film(a.spp) || !a.image;
-    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
-    if (mode == 0 && !tree) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths
-    if (mode == 2 && !tree)
-        hipLaunchKernelGGL(hf_reflect_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
-    else
-        hipLaunchKernelGGL(mode == 0 ? hf_reflect_kernel : mode == 1 ? hf_reflect_adjoint_kernel
-                           : mode == 2 ? hf_reflect_tangent_kernel<false> : hf_reflect_rays_kernel, grid, block, 0, stream, a);
+    launch_light(mode, a, 1u, stream, hf_reflect_kernel, hf_reflect_adjoint_kernel, hf_reflect_tangent_kernel<false>,
+                 hf_reflect_tangent_kernel<true>, hf_reflect_rays_kernel);
 }
 
 // ---------------------------------------------------------------------------------
@@ -6012,7 +6004,9 @@ void hf_launch_reflect(int mode, const hf_reflect_args &a, hipStream_t stream) {
 // (microfacet.h:297-319, 405-420).  Every wavefront sample draws K = num_rays microfacet normals from the TEA stream,
 // mirrors wi at each (reflect_vertex with the microfacet normal in the place of the shading normal), walks the mirror
 // ray (any hit, per lane, maxt = +inf) and, where it escapes, looks the map up in double.  ONE launch, one lane per
-// sample, `k` a scalar loop with the lanes predicated; nothing of a ray goes to memory.
+// sample, `k` a scalar loop with the lanes predicated; nothing of a ray goes to memory.  The row's own text is its draw
+// (glossy_draw, glossy_smith) and the derivative of its sums (glossy_sums); the lookup and everything around the
+// kernels are the shared functions the reflect row uses.
 // ---------------------------------------------------------------------------------
 // Draw k of one sample, the same text for the fused kernel, the rays kernel and the two derivatives: the microfacet
 // normal h (world), the mirror direction wo, the cosines <wi, h>, <n, h>, <n, wo>, F and whether the draw is valid
@@ -6079,20 +6073,6 @@ __device__ __forceinline__ float glossy_sample(P a, size_t i, v3 &n, v3 &d) {
 __device__ __forceinline__ bool glossy_eligible(v3 n, v3 g, v3 d, float t, float alpha, bool act) {
     const float inf = __builtin_inff();
     return act && (__builtin_fabsf(t) < inf) && (__builtin_fabsf(alpha) < inf) && (-dot3(n, d) > 0.f) && (-dot3(g, d) > 0.f);
-}
-// what the derivative kernels need of the lookup: the radiance, the bilinear weights and the first texel's index
-struct hf_glossy_shade { float L; double bw[4]; size_t r0; };
-__device__ __forceinline__ hf_glossy_shade glossy_shade(const hf_glossy_args &a, v3 w) {
-    hf_glossy_shade s;
-    uint32_t cx, cy;
-    double fx, fy;
-    env_lookup(a, w, cx, cy, fx, fy);
-    const size_t r0 = (size_t) cy * a.W + cx, r1 = r0 + a.W;
-    const double gx = 1.0 - fx, gy = 1.0 - fy;
-    s.L = (float) (gy * (gx * (double) a.data[r0] + fx * (double) a.data[r0 + 1]) + fy * (gx * (double) a.data[r1] + fx * (double) a.data[r1 + 1]));
-    s.bw[0] = gy * gx; s.bw[1] = gy * fx; s.bw[2] = fy * gx; s.bw[3] = fy * fx;
-    s.r0 = r0;
-    return s;
 }
 
 typedef const __attribute__((address_space(4))) hf_glossy_args *hf_glossy_kargs;
@@ -6162,7 +6142,7 @@ __global__ __launch_bounds__(HF_BLOCK, HF_GLOSSY_WAVES) void hf_glossy_kernel(hf
                 const float al = fmaxf(glossy_sample(ko, ix, sn, d), 1e-4f);
                 const uint32_t *ray_id = ko->ray_id;
                 const hf_glossy_draw g = glossy_draw(ko, sn, d, al, k, ray_id ? ray_id[ix] : ix);
-                acc += (g.F * glossy_smith(al, g.co).G) * reflect_radiance(*ko, ko->data, g.wo);
+                acc += (g.F * glossy_smith(al, g.co).G) * env_texels(*ko, ko->data, g.wo).value();
             }
         }
     }
@@ -6196,18 +6176,16 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_glossy_rays_kernel(hf_glossy_args
     const v3 gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
     const bool elig = glossy_eligible(sn, gn, d, a.t[i], al, a.active ? a.active[i] != 0 : true);
     const hf_glossy_draw g = glossy_draw(&a, sn, d, fmaxf(al, 1e-4f), a.k, light_id(a, i));
-    const bool traced = elig && g.valid && (g.co > 0.f) && (dot3(gn, g.wo) > 0.f);
-    const v3 z = mk3(0.f, 0.f, 0.f);
-    light_store_ray(a, i, traced ? sky_origin(p, gn, sky_offset(p), g.wo) : z, traced ? g.wo : z, traced);
+    light_store_spawned(a, i, p, gn, g.wo, elig && g.valid && (g.co > 0.f) && (dot3(gn, g.wo) > 0.f));
     if (a.out_h[0]) {
-        const v3 h = (elig && g.valid) ? g.h : z;
+        const v3 h = (elig && g.valid) ? g.h : mk3(0.f, 0.f, 0.f);
         a.out_h[0][i] = h.x; a.out_h[1][i] = h.y; a.out_h[2][i] = h.z;
     }
 }
 
 // The derivative of one sample with the draws held (include/hf.h): with S = sum_k F G1(c_o) L over the set bits,
 //   value = weight / K S,   d value = d weight S / K + weight / K (<N, dn> + A da + sum_k F G1(c_o) sum_j b_j ddata_j).
-// VISIT(k, F G1(c_o), shade) is called per set bit (the texel terms of the adjoint and the tangent)
+// VISIT(F G1(c_o), lookup) is called per set bit (the texel terms of the adjoint and the tangent)
 struct hf_glossy_sums { v3 N; float A, S; };
 template <class V>
 __device__ __forceinline__ hf_glossy_sums glossy_sums(const hf_glossy_args &a, size_t i, uint32_t bits, V visit) {
@@ -6225,15 +6203,16 @@ __device__ __forceinline__ hf_glossy_sums glossy_sums(const hf_glossy_args &a, s
         if (!((bits >> k) & 1u)) continue;
         const hf_glossy_draw g = glossy_draw(&a, sn, d, al, k, id);
         const hf_glossy_smith go = glossy_smith(al, g.co);
-        const hf_glossy_shade s = glossy_shade(a, g.wo);
+        const hf_env_texels e = env_texels(a, a.data, g.wo);
+        const float L = e.value();
         const float q = __builtin_fmaf(g.ch * g.ch, a2m1, 1.f);
         const float dDc = -4.f * g.ch * a2m1 / q, dDa = 2.f / al - 4.f * (g.ch * g.ch) * al / q; // d ln D
-        const float FL = g.F * s.L;
+        const float FL = g.F * L;
         // L (G1(c_o) d ln A + d G1(c_o))
         r.N = fma3(g.wo, FL * go.dc, fma3(wi, (FL * go.G) * ki, fma3(g.h, (FL * go.G) * dDc, r.N)));
         r.A += FL * __builtin_fmaf(go.G, dDa + kia, go.da);
-        r.S += g.F * go.G * s.L;
-        visit(g.F * go.G, s);
+        r.S += g.F * go.G * L;
+        visit(g.F * go.G, e);
     }
     return r;
 }
@@ -6248,23 +6227,16 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_glossy_adjoint_kernel(hf_glossy_a
     float gw = 0.f, ga = 0.f;
     const uint32_t bits = a.vis_bits[i];
     if (bits != 0u) {
-        const float g = (a.gimg ? a.gimg[i / a.spp] * (1.0f / (float) a.spp) : 0.f) + (a.gvalue ? a.gvalue[i] : 0.f);
+        const float g = light_value_seed(a, i);
         const float gk = (a.weight ? g * a.weight[i] : g) * a.inv_k;
-        const hf_glossy_sums r = glossy_sums(a, i, bits, [&](float fg, const hf_glossy_shade &s) {
-            if (a.gdata) {
-                const double q = (double) (gk * fg);
-                atomicAdd(a.gdata + s.r0, (float) (q * s.bw[0])); atomicAdd(a.gdata + s.r0 + 1, (float) (q * s.bw[1]));
-                atomicAdd(a.gdata + s.r0 + a.W, (float) (q * s.bw[2])); atomicAdd(a.gdata + s.r0 + a.W + 1, (float) (q * s.bw[3]));
-            }
+        const hf_glossy_sums r = glossy_sums(a, i, bits, [&](float fg, const hf_env_texels &e) {
+            if (a.gdata) env_scatter4(a.gdata, a.W, e.r0, e.bw, (double) (gk * fg));
         });
         gm = r.N * gk;
         ga = a.alpha[i] > 1e-4f ? r.A * gk : 0.f;
         gw = (g * a.inv_k) * r.S;
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        if (a.gn[c]) a.gn[c][i] = c == 0 ? gm.x : c == 1 ? gm.y : gm.z;
-    if (a.gw) a.gw[i] = gw;
+    light_store_grads(a, i, gm, gw);
     if (a.ga) a.ga[i] = ga;
 }
 
@@ -6274,10 +6246,8 @@ __device__ __forceinline__ float glossy_tangent_value(const hf_glossy_args &a, s
     const uint32_t bits = a.vis_bits[i];
     if (bits == 0u) return 0.f;
     float dt = 0.f; // sum_k F G1(c_o) sum_j b_j ddata_j
-    const hf_glossy_sums r = glossy_sums(a, i, bits, [&](float fg, const hf_glossy_shade &s) {
-        if (a.ddata)
-            dt += fg * (float) (s.bw[0] * (double) a.ddata[s.r0] + s.bw[1] * (double) a.ddata[s.r0 + 1] +
-                                s.bw[2] * (double) a.ddata[s.r0 + a.W] + s.bw[3] * (double) a.ddata[s.r0 + a.W + 1]);
+    const hf_glossy_sums r = glossy_sums(a, i, bits, [&](float fg, const hf_env_texels &e) {
+        if (a.ddata) dt += fg * (float) env_gather4(a.ddata, a.W, e.r0, e.bw);
     });
     const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
     const float w = a.weight ? a.weight[i] : 1.f, dw = a.dw ? a.dw[i] : 0.f;
@@ -6285,39 +6255,16 @@ __device__ __forceinline__ float glossy_tangent_value(const hf_glossy_args &a, s
     const float dv = __builtin_fmaf(r.A, da, dot3(r.N, dn)) + dt;
     return __builtin_fmaf(dw * a.inv_k, r.S, (w * a.inv_k) * dv);
 }
-// PIXEL as in hf_reflect_tangent_kernel: no atomics either way, the per-sample tangent written too
+// (the per-sample tangent is written too, and the image may be NULL)
 template <bool PIXEL>
 __global__ __launch_bounds__(HF_BLOCK) void hf_glossy_tangent_kernel(hf_glossy_args a) {
-    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
-    const uint32_t spp = a.spp;
-    if (PIXEL) {
-        if (i >= a.n / spp) return;
-        float c = 0.f;
-        for (uint32_t s = 0; s < spp; ++s) {
-            const float dv = glossy_tangent_value(a, i * spp + s);
-            if (a.value) a.value[i * spp + s] = dv;
-            c += dv;
-        }
-        a.image[i] = c * (1.0f / (float) spp);
-    } else {
-        const bool in = i < a.n;
-        const float c = in ? glossy_tangent_value(a, i) : 0.f;
-        if (in && a.value) a.value[i] = c;
-        if (a.image) film_pixel(a.image, c, 0u, a.n / spp, i, spp, in, true, spp, 1.0f / (float) spp);
-    }
+    light_tangent_image<PIXEL, hf_glossy_args, glossy_tangent_value>(a, a.value);
 }
 
-// mode 0: forward, 1: adjoint, 2: tangent, 3: rays (hf_launch_reflect's shape)
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays
 void hf_launch_glossy(int mode, const hf_glossy_args &a, hipStream_t stream) {
-    if (a.n == 0) return;
-    const bool tree = sky_tree_film(a.spp) || !a.image;
-    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
-    if (mode == 0 && !tree) (void) hipMemsetAsync(a.image, 0, sizeof(float) * (a.n / a.spp), stream); // atomic paths
-    if (mode == 2 && !tree)
-        hipLaunchKernelGGL(hf_glossy_tangent_kernel<true>, dim3((unsigned) ((a.n / a.spp + HF_BLOCK - 1) / HF_BLOCK)), block, 0, stream, a);
-    else
-        hipLaunchKernelGGL(mode == 0 ? hf_glossy_kernel : mode == 1 ? hf_glossy_adjoint_kernel
-                           : mode == 2 ? hf_glossy_tangent_kernel<false> : hf_glossy_rays_kernel, grid, block, 0, stream, a);
+    launch_light(mode, a, 1u, stream, hf_glossy_kernel, hf_glossy_adjoint_kernel, hf_glossy_tangent_kernel<false>,
+                 hf_glossy_tangent_kernel<true>, hf_glossy_rays_kernel);
 }
 
 // ---------------------------------------------------------------------------------

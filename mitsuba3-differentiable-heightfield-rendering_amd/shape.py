@@ -1332,6 +1332,16 @@ def _weighted_grads(ctx, sn, grad_image):
     return _detached_f32(grad_image), torch.empty_like(sn), torch.empty_like(sn[0]) if ctx.weighted else None
 
 
+def _texel_tangent(dfull):
+    """jvp: the tangent of a map's texels as contiguous float32 (None: zero)"""
+    return dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
+
+
+def _texel_grad(ctx, i, dat):
+    """backward: the zeroed grad_data an adjoint accumulates into, or None if input ``i`` (the texels) wants no gradient"""
+    return torch.zeros_like(dat) if ctx.needs_input_grad[i] else None
+
+
 def _empty_rays(pp):
     """the outputs of a *_rays entry: a Ray3f of the wavefront's size"""
     return Ray3f(torch.empty_like(pp), torch.empty_like(pp), torch.empty(pp.shape[1], dtype=torch.float32, device=pp.device))
@@ -1679,7 +1689,7 @@ class _EnvmapEvalOp(torch.autograd.Function):
         dd, = ctx.saved_tensors
         if dfull is None:
             return torch.zeros(dd.shape[1], dtype=torch.float32, device=dd.device)
-        return _EnvmapEvalOp._eval(dfull.to(dtype=torch.float32).contiguous(), dd, act, rot)
+        return _EnvmapEvalOp._eval(_texel_tangent(dfull), dd, act, rot)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -1826,7 +1836,7 @@ class _EnvmapLightingOp(torch.autograd.Function):
         saved = ctx.saved_tensors
         sn = saved[0]
         dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
-        df = dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
+        df = _texel_tangent(dfull)
         dimage = torch.empty(sn.shape[1] // ctx.misc[0], dtype=torch.float32, device=sn.device)
         if sn.shape[1]:
             check(_capi.lib().hf_envmap_lighting_tangent(*_EnvmapLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
@@ -1838,7 +1848,7 @@ class _EnvmapLightingOp(torch.autograd.Function):
         saved = ctx.saved_tensors
         sn, dat = saved[0], saved[4]
         gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
-        gd = torch.zeros_like(dat) if ctx.needs_input_grad[2] else None
+        gd = _texel_grad(ctx, 2, dat)
         if sn.shape[1]:
             check(_capi.lib().hf_envmap_lighting_adjoint(*_EnvmapLightingOp._prefix(ctx, *saved), gi.data_ptr(),
                                                          C.byref(_p3(gn)), _ptr(gw), _ptr(gd), _stream_of(sn.device)))
@@ -1880,62 +1890,91 @@ def envmap_rays(si, ray, envmap, k, seed=0, ray_index=None, return_weight=False)
     return (r, wgt) if return_weight else r
 
 
+# ---- what the two reflection Functions (reflect, glossy) are made of.  `entry`: the C entry's name; `mid(ctx, dat, ww,
+# *extra)`: the row's C arguments between t and its outputs (derivatives: its visibility row); `extra`: the row's further
+# differentiable rows (glossy: alpha), which follow sh_n and weight among the inputs, the tangents and the gradients ----
+def _reflection_forward(ctx, entry, mid, vis_dtype, shape, sh_n, p, nrm, d, t, weight, full, *extra):
+    """(image, value, vis) of a forward entry; saves (sn, dd, tt, vis, dat, *extra[, weight]).  ctx.misc[0] is spp"""
+    sn, pp, gn, dd, tt, ww, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, full))
+    extra = tuple(map(_detached_f32, extra))
+    n, spp = sn.shape[1], ctx.misc[0]
+    image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
+    value = torch.empty(n, dtype=torch.float32, device=sn.device)
+    vis = torch.empty(n, dtype=vis_dtype, device=sn.device)
+    if n:  # (an empty wavefront has no rows to point to)
+        check(getattr(_capi.lib(), entry)(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                          C.byref(_p3(dd)), tt.data_ptr(), *mid(ctx, dat, ww, *extra), image.data_ptr(),
+                                          value.data_ptr(), vis.data_ptr(), _stream_of(sn.device)))
+    saved = _with_weight(ctx, (sn, dd, tt, vis, dat) + extra, ww)
+    ctx.save_for_backward(*saved)
+    ctx.save_for_forward(*saved)
+    ctx.mark_non_differentiable(vis)
+    return image, value, vis
+
+
+def _reflection_prefix(ctx, mid):
+    """what a row's _adjoint / _tangent entries start with"""
+    sn, dd, tt, vis, dat, *extra = ctx.saved_tensors
+    ww = extra.pop() if ctx.weighted else None
+    return (sn.shape[1], ctx.misc[0], C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), *mid(ctx, dat, ww, *extra),
+            vis.data_ptr())
+
+
+def _reflection_jvp(ctx, entry, mid, dsh_n, dweight, dfull, *dextra):
+    sn = ctx.saved_tensors[0]
+    dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
+    dx, df = tuple(map(_detached_f32, dextra)), _texel_tangent(dfull)   # (held until the call has been enqueued)
+    dimage = torch.empty(sn.shape[1] // max(ctx.misc[0], 1), dtype=torch.float32, device=sn.device)
+    dvalue = torch.empty_like(sn[0])
+    if sn.shape[1]:
+        check(getattr(_capi.lib(), entry)(*_reflection_prefix(ctx, mid), _ref(_row_ptrs(dn)), _ptr(dw), *map(_ptr, dx),
+                                          _ptr(df), dimage.data_ptr(), dvalue.data_ptr(), _stream_of(sn.device)))
+    return dimage, dvalue, None
+
+
+def _reflection_backward(ctx, entry, mid, grad_image, grad_value, n_extra=0):
+    """the gradients of sh_n, weight, the `n_extra` further rows and the texels (inputs 0, 1, 2 .. and 2 + n_extra)"""
+    sn, dat = ctx.saved_tensors[0], ctx.saved_tensors[4]
+    gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
+    gv = _detached_f32(grad_value)
+    gx = tuple(torch.empty_like(sn[0]) if ctx.needs_input_grad[2 + j] else None for j in range(n_extra))
+    gd = _texel_grad(ctx, 2 + n_extra, dat)
+    if sn.shape[1]:
+        check(getattr(_capi.lib(), entry)(*_reflection_prefix(ctx, mid), _ptr(gi), _ptr(gv), C.byref(_p3(gn)), _ptr(gw),
+                                          *map(_ptr, gx), _ptr(gd), _stream_of(sn.device)))
+    return (gn, gw) + gx + (gd,)
+
+
+def _value_outputs(image, value, vis, return_value, return_visibility):
+    """what reflection_lighting and glossy_lighting return: the image, then what was asked for of value and visibility"""
+    out = (image,) + ((value,) if return_value else ()) + ((vis,) if return_visibility else ())
+    return out if len(out) > 1 else image
+
+
 class _ReflectionLightingOp(torch.autograd.Function):
     """(image, per-sample value, visibility bytes) of hf_reflect_lighting; backward = hf_reflect_lighting_adjoint (gradients
     of sh_n, weight and the texels), jvp = hf_reflect_lighting_tangent.  Both read the visibility byte the forward saved
     and trace nothing."""
 
     @staticmethod
-    def _prefix(ctx, sn, dd, tt, vis, dat, ww=None):
-        """what hf_reflect_lighting_adjoint / _tangent start with"""
+    def _mid(ctx, dat, ww):
         spp, eta, rot, act = ctx.misc
-        return (sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(act), _ptr(ww), eta, dat.shape[1],
-                dat.shape[0], dat.data_ptr(), C.byref(rot), vis.data_ptr())
+        return (_ptr(act), _ptr(ww), eta, dat.shape[1], dat.shape[0], dat.data_ptr(), C.byref(rot))
 
     @staticmethod
     def forward(ctx, sh_n, weight, full, shape, p, nrm, d, t, active, rot, eta, spp):
-        sn, pp, gn, dd, tt, ww, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, full))
-        n = sn.shape[1]
         ctx.misc = (spp, eta, rot, active)
-        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
-        value = torch.empty(n, dtype=torch.float32, device=sn.device)
-        vis = torch.empty(n, dtype=torch.uint8, device=sn.device)
-        if n:  # (an empty wavefront has no rows to point to)
-            check(_capi.lib().hf_reflect_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
-                                                  C.byref(_p3(dd)), tt.data_ptr(), _ptr(active), _ptr(ww), eta, dat.shape[1],
-                                                  dat.shape[0], dat.data_ptr(), C.byref(rot), image.data_ptr(),
-                                                  value.data_ptr(), vis.data_ptr(), _stream_of(sn.device)))
-        saved = _with_weight(ctx, (sn, dd, tt, vis, dat), ww)
-        ctx.save_for_backward(*saved)
-        ctx.save_for_forward(*saved)
-        ctx.mark_non_differentiable(vis)
-        return image, value, vis
+        return _reflection_forward(ctx, "hf_reflect_lighting", _ReflectionLightingOp._mid, torch.uint8, shape, sh_n, p, nrm,
+                                   d, t, weight, full)
 
     @staticmethod
     def jvp(ctx, dsh_n, dweight, dfull, *_):
-        saved = ctx.saved_tensors
-        sn = saved[0]
-        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
-        df = dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
-        dimage = torch.empty(sn.shape[1] // max(ctx.misc[0], 1), dtype=torch.float32, device=sn.device)
-        dvalue = torch.empty_like(sn[0])
-        if sn.shape[1]:
-            check(_capi.lib().hf_reflect_lighting_tangent(*_ReflectionLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
-                                                          _ptr(dw), _ptr(df), dimage.data_ptr(), dvalue.data_ptr(),
-                                                          _stream_of(sn.device)))
-        return dimage, dvalue, None
+        return _reflection_jvp(ctx, "hf_reflect_lighting_tangent", _ReflectionLightingOp._mid, dsh_n, dweight, dfull)
 
     @staticmethod
     def backward(ctx, grad_image, grad_value, _grad_vis):
-        saved = ctx.saved_tensors
-        sn, dat = saved[0], saved[4]
-        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
-        gv = _detached_f32(grad_value)
-        gd = torch.zeros_like(dat) if ctx.needs_input_grad[2] else None
-        if sn.shape[1]:
-            check(_capi.lib().hf_reflect_lighting_adjoint(*_ReflectionLightingOp._prefix(ctx, *saved), _ptr(gi), _ptr(gv),
-                                                          C.byref(_p3(gn)), _ptr(gw), _ptr(gd), _stream_of(sn.device)))
-        return (gn, gw, gd) + (None,) * 9
+        return _reflection_backward(ctx, "hf_reflect_lighting_adjoint", _ReflectionLightingOp._mid, grad_image,
+                                    grad_value) + (None,) * 9
 
 
 def reflection_lighting(shape, si, ray, envmap, eta=0.0, spp=1, weight=None, active=True, return_value=False,
@@ -1953,8 +1992,7 @@ def reflection_lighting(shape, si, ray, envmap, eta=0.0, spp=1, weight=None, act
     image, value, vis = _ReflectionLightingOp.apply(si.sh_frame.n, weight, envmap.full(), shape, si.p, si.n, ray.d, si.t,
                                                     _caustic_active(active, len(ray), ray.d.device), envmap._rot, float(eta),
                                                     int(spp))
-    out = (image,) + ((value,) if return_value else ()) + ((vis,) if return_visibility else ())
-    return out if len(out) > 1 else image
+    return _value_outputs(image, value, vis, return_value, return_visibility)
 
 
 def reflection_rays(si, ray, active=True):
@@ -1976,59 +2014,25 @@ class _GlossyLightingOp(torch.autograd.Function):
     saved, draw the microfacet normals again and trace nothing."""
 
     @staticmethod
-    def _prefix(ctx, sn, dd, tt, al, vis, dat, ww=None):
-        """what hf_glossy_lighting_adjoint / _tangent start with"""
+    def _mid(ctx, dat, ww, al):
         spp, eta, num_rays, seed, rid, rot, act = ctx.misc
-        return (sn.shape[1], spp, C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(act), _ptr(ww), al.data_ptr(), eta,
-                num_rays, seed, _ptr(rid), dat.shape[1], dat.shape[0], dat.data_ptr(), C.byref(rot), vis.data_ptr())
+        return (_ptr(act), _ptr(ww), al.data_ptr(), eta, num_rays, seed, _ptr(rid), dat.shape[1], dat.shape[0], dat.data_ptr(),
+                C.byref(rot))
 
     @staticmethod
     def forward(ctx, sh_n, weight, alpha, full, shape, p, nrm, d, t, active, rot, eta, spp, num_rays, seed, ray_index):
-        sn, pp, gn, dd, tt, ww, al, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, alpha, full))
-        n = sn.shape[1]
         ctx.misc = (spp, eta, num_rays, seed, ray_index, rot, active)
-        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
-        value = torch.empty(n, dtype=torch.float32, device=sn.device)
-        vis = torch.empty(n, dtype=torch.int32, device=sn.device)
-        if n:  # (an empty wavefront has no rows to point to)
-            check(_capi.lib().hf_glossy_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
-                                                 C.byref(_p3(dd)), tt.data_ptr(), _ptr(active), _ptr(ww), al.data_ptr(), eta,
-                                                 num_rays, seed, _ptr(ray_index), dat.shape[1], dat.shape[0], dat.data_ptr(),
-                                                 C.byref(rot), image.data_ptr(), value.data_ptr(), vis.data_ptr(),
-                                                 _stream_of(sn.device)))
-        saved = _with_weight(ctx, (sn, dd, tt, al, vis, dat), ww)
-        ctx.save_for_backward(*saved)
-        ctx.save_for_forward(*saved)
-        ctx.mark_non_differentiable(vis)
-        return image, value, vis
+        return _reflection_forward(ctx, "hf_glossy_lighting", _GlossyLightingOp._mid, torch.int32, shape, sh_n, p, nrm, d, t,
+                                   weight, full, alpha)
 
     @staticmethod
     def jvp(ctx, dsh_n, dweight, dalpha, dfull, *_):
-        saved = ctx.saved_tensors
-        sn = saved[0]
-        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
-        da = _detached_f32(dalpha)
-        df = dfull.to(dtype=torch.float32).contiguous() if dfull is not None else None
-        dimage = torch.empty(sn.shape[1] // max(ctx.misc[0], 1), dtype=torch.float32, device=sn.device)
-        dvalue = torch.empty_like(sn[0])
-        if sn.shape[1]:
-            check(_capi.lib().hf_glossy_lighting_tangent(*_GlossyLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
-                                                         _ptr(dw), _ptr(da), _ptr(df), dimage.data_ptr(), dvalue.data_ptr(),
-                                                         _stream_of(sn.device)))
-        return dimage, dvalue, None
+        return _reflection_jvp(ctx, "hf_glossy_lighting_tangent", _GlossyLightingOp._mid, dsh_n, dweight, dfull, dalpha)
 
     @staticmethod
     def backward(ctx, grad_image, grad_value, _grad_vis):
-        saved = ctx.saved_tensors
-        sn, dat = saved[0], saved[5]
-        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
-        gv = _detached_f32(grad_value)
-        ga = torch.empty_like(sn[0]) if ctx.needs_input_grad[2] else None
-        gd = torch.zeros_like(dat) if ctx.needs_input_grad[3] else None
-        if sn.shape[1]:
-            check(_capi.lib().hf_glossy_lighting_adjoint(*_GlossyLightingOp._prefix(ctx, *saved), _ptr(gi), _ptr(gv),
-                                                         C.byref(_p3(gn)), _ptr(gw), _ptr(ga), _ptr(gd), _stream_of(sn.device)))
-        return (gn, gw, ga, gd) + (None,) * 12
+        return _reflection_backward(ctx, "hf_glossy_lighting_adjoint", _GlossyLightingOp._mid, grad_image, grad_value,
+                                    n_extra=1) + (None,) * 12
 
 
 def _glossy_alpha(alpha, n, device):
@@ -2060,8 +2064,7 @@ def glossy_lighting(shape, si, ray, envmap, alpha, eta=0.0, spp=1, num_rays=4, s
                                                 shape, si.p, si.n, ray.d, si.t, _caustic_active(active, n, ray.d.device),
                                                 envmap._rot, float(eta), int(spp), int(num_rays), int(seed),
                                                 _check_ray_index(ray_index, ray))
-    out = (image,) + ((value,) if return_value else ()) + ((vis,) if return_visibility else ())
-    return out if len(out) > 1 else image
+    return _value_outputs(image, value, vis, return_value, return_visibility)
 
 
 def glossy_rays(si, ray, alpha, k, seed=0, ray_index=None, active=True, return_normal=False):
