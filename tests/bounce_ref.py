@@ -9,6 +9,7 @@ Shapes: n samples, K directions, L lights.  hit [K, n] bool, lit [K, L, n] bool,
 direction towards the light, irradiance)."""
 import numpy as np
 
+from reparam_tangent_ref import coordinate_system  # noqa: F401  ((s, t) of vector.h:116-136 for [3, n] float64 normals)
 from sky_ref import RAY_EPSILON, eligible, samples, spawn_origin, tea32  # noqa: F401  (the stream and the masks are the sky row's)
 
 MISS = 0xFFFFFFFF
@@ -29,17 +30,6 @@ def local_directions(ids, K, seed):
         px, py = r * np.cos(phi), r * np.sin(phi)
         out[k] = np.stack([px, py, np.sqrt(np.maximum(0.0, 1.0 - px * px - py * py))])
     return out
-
-
-def coordinate_system(n):
-    """(s, t) of vector.h:116-136 for the [3, n] normals"""
-    n = np.asarray(n, np.float64)
-    sign = np.where(n[2] >= 0, 1.0, -1.0)
-    a = -1.0 / (sign + n[2])
-    b = n[0] * n[1] * a
-    s = np.stack([sign * (n[0] * n[0] * a) + 1.0, sign * b, -sign * n[0]])
-    t = np.stack([b, n[1] * n[1] * a + sign, -n[1]])
-    return s, t
 
 
 def directions(sh_n, ids, K, seed):

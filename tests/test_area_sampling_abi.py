@@ -8,6 +8,7 @@ import re
 import numpy as np
 import torch
 
+from abi_helpers import assert_symbols
 import area_ref as A
 import common
 import smooth_ref as S
@@ -18,15 +19,7 @@ NEW = ("hf_set_area_sampling", "hf_surface_area", "hf_area_cdf", "hf_sample_posi
 
 
 def test_new_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", hdr), f"{name} not declared in include/hf.h"
-        assert hasattr(lib, name), f"{name} not exported by libhf.so"
-        assert name in _capi.SYMBOLS, f"{name} missing from the binding table"
-    assert _capi.lib().hf_version() == 4
+    assert_symbols(NEW)
 
 
 def test_null_handle_is_refused():

@@ -4,46 +4,25 @@ declared, exported and bound; every bad argument is refused before anything touc
 facet that faces its light, its adjoint agrees with central differences of its own forward and its tangent is the
 transpose of its adjoint."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import bounce_ref as B
+from abi_helpers import assert_refused, assert_symbols, stand_ins
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FNS = ("hf_bounce_rays", "hf_bounce_lighting", "hf_bounce_lighting_adjoint", "hf_bounce_lighting_tangent")
 
 
 def test_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for fn in FNS:
-        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
-        assert hasattr(lib, fn)
-        assert fn in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
-    assert callable(hf_amd.bounce_lighting) and callable(hf_amd.bounce_rays)
+    assert_symbols(FNS, ("bounce_lighting", "bounce_rays"))
 
 
 # ---- argument checks: host addresses stand in for device pointers, every case fails before a launch ------------------
 def _call(lib, fn, n=8, spp=2, num_rays=4, k=3, albedo=0.5, n_lights=2, stride=8, light=(0.0, 0.6, 0.8, 1.0), null=(),
           null_row=None):
     from hf_amd import _capi
-    keep = (C.c_float * 16384)()            # (also the stand-in for the handle: no case gets as far as reading it)
-    a = C.addressof(keep)
-
-    def rows(name):
-        if name in null:
-            return None
-        r = (_capi._fp * 3)(a, a, a)
-        if null_row == name:
-            r[2] = None
-        return r
-    arg = lambda name: None if name in null else a
+    rows, arg = stand_ins(null, null_row)
     L = (_capi.hf_dir_light_t * 9)()
     for j in range(9):
         L[j].to_light[0], L[j].to_light[1], L[j].to_light[2], L[j].irradiance = (0.0, 0.0, 1.0, 1.0)
@@ -86,11 +65,7 @@ CASES = {
 
 @pytest.mark.parametrize("fn", FNS)
 def test_bad_arguments_are_refused(fn):
-    from hf_amd import _capi
-    lib = _capi.lib()
-    for kw in CASES[fn]:
-        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith(fn + ":"), (kw, lib.hf_last_error_string())
+    assert_refused(_call, fn, CASES[fn])
 
 
 def test_an_empty_wavefront_is_legal_before_any_device():

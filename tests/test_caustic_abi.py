@@ -2,45 +2,25 @@
 declared, exported and bound, HF_VERSION is unchanged, and every bad argument is refused with HF_EINVAL and a message
 before anything touches a device (host addresses stand in for device pointers)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_helpers import assert_refused, assert_symbols, stand_ins
+
 FNS = ("hf_caustic_rays", "hf_caustic_lighting", "hf_caustic_adjoint", "hf_caustic_tangent")
 
 
 def test_symbols_declared_exported_and_bound():
     import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for fn in FNS:
-        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
-        assert hasattr(lib, fn)
-        assert fn in _capi.SYMBOLS
+    hdr = assert_symbols(FNS, ("Receiver", "caustic_lighting", "caustic_rays", "caustic_film"))
     assert "hf_receiver_t" in hdr
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
-    for name in ("Receiver", "caustic_lighting", "caustic_rays", "caustic_film"):
-        assert callable(getattr(hf_amd, name)), name
     r = hf_amd.Receiver.plane_z(-0.5, (-1.0, 1.0), (-2.0, 2.0), 64, 32)
     assert r.origin == (-1.0, -2.0, -0.5) and r.ex == (32.0, 0.0, 0.0) and r.ey == (0.0, 8.0, 0.0)
 
 
 def _call(lib, fn, n=8, eta=1.33, power=1.0, rcv=((0, 0, -1), (4, 0, 0), (0, 4, 0)), null=(), null_row=None):
     from hf_amd import _capi
-    keep = (C.c_float * 16384)()            # (also the stand-in for the handle: no case gets as far as reading it)
-    a = C.addressof(keep)
-
-    def rows(name, k=3):
-        if name in null:
-            return None
-        r = (_capi._fp * k)(*([a] * k))
-        if null_row == name:
-            r[k - 1] = None
-        return r
-    arg = lambda name: None if name in null else a
+    rows, arg = stand_ins(null, null_row)
     receiver = None if "receiver" in null else _capi.hf_receiver_t(*[(C.c_float * 3)(*v) for v in rcv])
     head = (n, rows("p"), rows("nrm"), rows("sh_n"), rows("d"), arg("t"), arg("active"))
     if fn == "hf_caustic_rays":
@@ -74,11 +54,7 @@ CASES = {
 
 @pytest.mark.parametrize("fn", FNS)
 def test_bad_arguments_are_refused(fn):
-    from hf_amd import _capi
-    lib = _capi.lib()
-    for kw in CASES[fn]:
-        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith(fn + ":"), (kw, lib.hf_last_error_string())
+    assert_refused(_call, fn, CASES[fn])
 
 
 def test_orthogonality_bound_is_relative():

@@ -2,28 +2,18 @@
 argument is refused with HF_EINVAL before anything touches a device (host addresses stand in for device pointers, so a
 call that got as far as a launch would not return HF_EINVAL); HF_VERSION is unchanged."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_helpers import assert_refused, assert_symbols, stand_ins
+
 FNS = ("hf_envmap_table_floats", "hf_envmap_build_table", "hf_envmap_sample_direction", "hf_envmap_eval",
        "hf_envmap_eval_adjoint", "hf_envmap_rays", "hf_envmap_lighting", "hf_envmap_lighting_adjoint",
        "hf_envmap_lighting_tangent")
 
 
 def test_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for fn in FNS:
-        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
-        assert hasattr(lib, fn)
-        assert fn in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
-    assert callable(hf_amd.envmap_lighting) and callable(hf_amd.envmap_rays) and callable(hf_amd.Envmap)
+    assert_symbols(FNS, ("envmap_lighting", "envmap_rays", "Envmap"))
 
 
 def test_table_size():
@@ -39,18 +29,7 @@ NAN, INF = float("nan"), float("inf")
 
 
 def _call(lib, fn, n=8, spp=2, num_rays=8, k=3, W=17, H=9, u=0.25, albedo=0.5, rot=None, null=(), null_row=None):
-    from hf_amd import _capi
-    keep = (C.c_float * 16384)()            # (also the stand-in for the handle: no case gets as far as reading it)
-    a = C.addressof(keep)
-
-    def rows(name, k=3):
-        if name in null:
-            return None
-        r = (_capi._fp * k)(*([a] * k))
-        if null_row == name:
-            r[k - 1] = None
-        return r
-    arg = lambda name: None if name in null else a
+    rows, arg = stand_ins(null, null_row)
     R = None if rot is None else C.byref((C.c_float * 9)(*rot))
     env = (W, H, arg("data"), arg("table"), R)
     if fn == "hf_envmap_build_table":
@@ -102,11 +81,7 @@ CASES = {
 
 @pytest.mark.parametrize("fn", sorted(CASES))
 def test_bad_arguments_are_refused(fn):
-    from hf_amd import _capi
-    lib = _capi.lib()
-    for kw in CASES[fn]:
-        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith(fn + ":"), (kw, lib.hf_last_error_string())
+    assert_refused(_call, fn, CASES[fn])
 
 
 def test_python_argument_checks():

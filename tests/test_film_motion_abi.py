@@ -4,28 +4,18 @@ before anything touches a device; the float64 restatement (tests/film_ref.py) ag
 two overlap, its position / weight derivatives with central differences of its own forward, and its tangent is the
 transpose of its adjoint."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+from abi_helpers import assert_refused, assert_symbols
 import film_ref as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FNS = ("hf_film_splat_weighted", "hf_film_splat_weighted_adjoint", "hf_film_splat_weighted_tangent")
 
 
 def test_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for fn in FNS:
-        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
-        assert hasattr(lib, fn)
-        assert fn in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
+    assert_symbols(FNS)
 
 
 # ---- argument checks: host addresses stand in for device pointers, every case fails before a launch ------------------
@@ -66,11 +56,7 @@ CASES = {
 
 @pytest.mark.parametrize("fn", FNS)
 def test_bad_arguments_are_refused(fn):
-    from hf_amd import _capi
-    lib = _capi.lib()
-    for kw in CASES[fn]:
-        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith(fn + ":"), (kw, lib.hf_last_error_string())
+    assert_refused(_call, fn, CASES[fn])
 
 
 # ---- the float64 restatement ---------------------------------------------------------------------------------------

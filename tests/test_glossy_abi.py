@@ -2,44 +2,22 @@
 four entry points are declared, exported and bound, HF_VERSION is unchanged, and every bad argument is refused with
 HF_EINVAL and a message before anything touches a device (host addresses stand in for device pointers)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_helpers import assert_refused, assert_symbols, stand_ins
+
 FNS = ("hf_glossy_rays", "hf_glossy_lighting", "hf_glossy_lighting_adjoint", "hf_glossy_lighting_tangent")
 NAN, INF = float("nan"), float("inf")
 IDENTITY = (1, 0, 0, 0, 1, 0, 0, 0, 1)
 
 
 def test_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for fn in FNS:
-        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
-        assert hasattr(lib, fn)
-        assert fn in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
-    for name in ("glossy_lighting", "glossy_rays"):
-        assert callable(getattr(hf_amd, name)), name
+    assert_symbols(FNS, ("glossy_lighting", "glossy_rays"))
 
 
 def _call(lib, fn, n=8, spp=1, eta=1.5, num_rays=4, k=0, W=5, H=3, rot=IDENTITY, null=(), null_row=None):
-    from hf_amd import _capi
-    keep = (C.c_float * 16384)()            # (also the stand-in for the handle: no case gets as far as reading it)
-    a = C.addressof(keep)
-
-    def rows(name, k_=3):
-        if name in null:
-            return None
-        r = (_capi._fp * k_)(*([a] * k_))
-        if null_row == name:
-            r[k_ - 1] = None
-        return r
-    arg = lambda name: None if name in null else a
+    rows, arg = stand_ins(null, null_row)
     R = None if rot is None else (C.c_float * 9)(*rot)
     if fn == "hf_glossy_rays":
         return lib.hf_glossy_rays(n, rows("p"), rows("nrm"), rows("sh_n"), rows("d"), arg("t"), arg("active"), arg("alpha"), k, 0,
@@ -74,14 +52,7 @@ MESSAGE = {"n": "2^32", "spp": "multiple of spp", "num_rays": "1..32", "k": "bel
 
 @pytest.mark.parametrize("fn", FNS)
 def test_bad_arguments_are_refused(fn):
-    from hf_amd import _capi
-    lib = _capi.lib()
-    for kw in CASES[fn]:
-        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
-        msg = lib.hf_last_error_string().decode()
-        assert msg.startswith(fn + ":"), (kw, msg)
-        first = "spp" if "spp" in kw else next(iter(kw))
-        assert MESSAGE[first] in msg, (kw, msg)
+    assert_refused(_call, fn, CASES[fn], MESSAGE)
 
 
 def test_optional_pointers_are_not_refused_for_being_null():

@@ -21,6 +21,7 @@ import torch.autograd.forward_ad as fwAD
 
 import bounce_ref as B
 from lighting_scenes import _close, _records, _rows7
+from row_helpers import GUARD, _np, base_scene, guarded, intact, rows, sub
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -35,20 +36,11 @@ MARGIN = 4e-6
 MISS = 0xFFFFFFFF
 
 
-def _np(x):
-    return x.detach().cpu().numpy()
-
-
 @pytest.fixture(scope="module")
 def scene(hf, oracle):
-    h = hf.workload.sine_heights(96, 96, device="cuda")
-    shape = hf.Heightfield(heightfield=h, max_height=MAXH)
-    rays = hf.workload.ortho_rays(64, 64, 4, "cuda", seed=1, origin=(0.6, 0.35, 2.0), target=(0.0, 0.0, 0.25), scale=(0.9, 0.9, 1.0))
-    ray = hf.Ray3f(rays[0:3], rays[3:6], rays[6])
-    si = shape.ray_intersect(ray, hf.RayFlags.All)
-    n = len(ray)
-    sc = types.SimpleNamespace(h=h, shape=shape, rays=rays, ray=ray, si=si, n=n, lights=torch.from_numpy(LIGHTS))
-    sc.np = {k: _np(v) for k, v in (("p", si.p), ("n", si.n), ("sh_n", si.sh_frame.n), ("d", ray.d), ("t", si.t))}
+    sc = base_scene(hf, oracle, (64, 64, 4), (0.6, 0.35, 2.0))                 # (max_height 0.5 = MAXH)
+    shape, ray, si, n = sc.shape, sc.ray, sc.si, sc.n
+    sc.lights = torch.from_numpy(LIGHTS)
     sc.w, sc.z = B.directions(sc.np["sh_n"], np.arange(n), 32, SEED)     # [32, 3, n], [32, n]: every num_rays is a prefix
     sc.eligible, _ = B.eligible(sc.np["sh_n"], sc.np["d"], sc.np["t"])
     sc.traced = B.traced(sc.np["sh_n"], sc.np["d"], sc.np["t"], sc.z)
@@ -69,17 +61,7 @@ def scene(hf, oracle):
     sc.shit = [[shape.ray_test(sc.srays[k][l]) for l in range(NL)] for k in range(K)]
     _, prim, lit = hf.bounce_lighting(shape, si, ray, sc.lights, spp=4, num_rays=K, seed=SEED, return_records=True)
     sc.prim, sc.lit = _np(prim).view(np.uint32), _np(lit)
-    sc.field = oracle.OracleField(_np(h), max_height=MAXH)
     return sc
-
-
-def _sub(hf, sc, m, requires_grad=False):
-    """(si, ray) of the first m samples as records of their own"""
-    si = hf.SurfaceInteraction3f()
-    cut = lambda x: x.detach()[..., :m].contiguous()
-    si.p, si.n, si.t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.t)
-    si.sh_frame = hf.Frame3f(None, None, cut(sc.si.sh_frame.n).requires_grad_(requires_grad))
-    return si, hf.Ray3f(cut(sc.ray.o), cut(sc.ray.d))
 
 
 def test_materialised_rays_against_the_restatement(hf, scene):
@@ -187,7 +169,7 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp, with_
     m = sc.n - sc.n % spp
     albedo, wmax = 0.7, 1.5
     rng = np.random.default_rng(100 * spp + num_rays)
-    si, ray = _sub(hf, sc, m, requires_grad=True)
+    si, ray = sub(hf, sc, 0, m, requires_grad=True)
     wgt = rng.uniform(0.5, wmax, m).astype(np.float32) if with_weight else None
     wt = torch.from_numpy(wgt).cuda().requires_grad_(True) if with_weight else None
     img, prim, lit = hf.bounce_lighting(sc.shape, si, ray, sc.lights, albedo=albedo, spp=spp, num_rays=num_rays, seed=SEED,
@@ -269,7 +251,6 @@ def test_grad_heights_against_the_composition(hf, scene, face_normals):
     L = (hf._capi.hf_dir_light_t * NL)()
     for l in range(NL):
         L[l].to_light[0], L[l].to_light[1], L[l].to_light[2], L[l].irradiance = LIGHTS[l].tolist()
-    rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (j * x.shape[1]) for j in range(3)])
     sn, dd, tt = si.sh_frame.n.detach().contiguous(), sc.ray.d.contiguous(), si.t.detach().contiguous()
     gh = shape._zero_heights()
     git = torch.from_numpy(gi).cuda()
@@ -293,7 +274,7 @@ def test_tangent_of_the_heights_is_the_transpose(hf, scene):
     """forward mode through shape.heightfield: <tangent(dh), gi> = <dh, adjoint(gi)> (n_q route; float32 sums)"""
     sc = scene
     shape = hf.Heightfield(heightfield=sc.h.clone(), max_height=MAXH)
-    si, ray = _sub(hf, sc, sc.n)
+    si, ray = sub(hf, sc, 0, sc.n)
     gi = torch.from_numpy(np.random.default_rng(5).normal(size=(NL, sc.n // 4)).astype(np.float32)).cuda()
     dh = torch.from_numpy(np.random.default_rng(6).normal(size=(96, 96)).astype(np.float32)).cuda()
     shape.heightfield.requires_grad_(True)
@@ -316,19 +297,19 @@ def test_repeatable_and_edge_cases(hf, scene):
     wt0 = torch.from_numpy(np.random.default_rng(3).uniform(0.5, 1.5, m).astype(np.float32)).cuda()
     runs = []
     for _ in range(2):
-        si, ray = _sub(hf, sc, m, requires_grad=True)
+        si, ray = sub(hf, sc, 0, m, requires_grad=True)
         wt = wt0.clone().requires_grad_(True)
         img, prim, lit = hf.bounce_lighting(sc.shape, si, ray, sc.lights, spp=4, num_rays=K, seed=SEED, weight=wt, return_records=True)
         (img * gi).sum().backward()
         with fwAD.dual_level():
-            si2, _ = _sub(hf, sc, m)
+            si2, _ = sub(hf, sc, 0, m)
             si2.sh_frame.n = fwAD.make_dual(si2.sh_frame.n, dn)
             tan = fwAD.unpack_dual(hf.bounce_lighting(sc.shape, si2, ray, sc.lights, spp=4, num_rays=K, seed=SEED, weight=wt0)).tangent
         runs.append((prim.clone(), lit.clone(), img.detach().clone(), si.sh_frame.n.grad.clone(), wt.grad.clone(), tan.clone()))
     for a, b in zip(*runs):
         assert torch.equal(a, b)
     # n = 0 is legal
-    si0, ray0 = _sub(hf, sc, 0, requires_grad=True)
+    si0, ray0 = sub(hf, sc, 0, 0, requires_grad=True)
     img0, prim0, lit0 = hf.bounce_lighting(sc.shape, si0, ray0, sc.lights, spp=4, num_rays=K, return_records=True)
     assert img0.shape == (NL, 0) and prim0.shape == (K, 0) and lit0.shape == (K, 0)
     img0.sum().backward()
@@ -378,18 +359,9 @@ def test_nothing_is_written_beside_the_rows(hf, scene):
     cut = lambda x: x.detach()[..., start:start + n].contiguous()
     p, nr, sn, d, t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.sh_frame.n), cut(sc.ray.d), cut(sc.si.t)
     assert bool(torch.isfinite(t).any())
-    rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(3)])
-    GUARD = -12345.0
     L = (hf._capi.hf_dir_light_t * NL)()
     for l in range(NL):
         L[l].to_light[0], L[l].to_light[1], L[l].to_light[2], L[l].irradiance = LIGHTS[l].tolist()
-
-    def guarded(k=1):
-        buf = torch.full((k, n + 2 * G), GUARD, device="cuda")
-        return buf, (hf._capi._fp * 3)(*[buf.data_ptr() + 4 * (j * (n + 2 * G) + G) for j in range(k)] + [None] * (3 - k))
-
-    def intact(buf):
-        return bool((buf[:, :G] == GUARD).all()) and bool((buf[:, G + n:] == GUARD).all()) and bool((buf[:, G:G + n] != GUARD).all())
     image = torch.full((G + NL * n + G,), GUARD, device="cuda")          # the per-light rows are contiguous (npix = n)
     prim = torch.full((G + K * stride,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     lit = torch.full((G + K * stride,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -408,21 +380,21 @@ def test_nothing_is_written_beside_the_rows(hf, scene):
     # the slice, with its ids, is the slice of the whole
     assert np.array_equal(_np(pr[:, :n]).view(np.uint32), sc.prim[:, start:start + n]) and np.array_equal(_np(lb[:, :n]), sc.lit[:, start:start + n])
     gi = torch.ones(NL * n, device="cuda")
-    gn, gp = guarded(3)
-    gw, gwp = guarded()
+    gn, gp = guarded(n, G, 3)
+    gw, gwp = guarded(n, G)
     gh = torch.zeros((96, 96), device="cuda")
     head = (sc.shape._h, n, 1, rows(sn), rows(d), t.data_ptr(), None, K, SEED, ids.data_ptr(), NL, L, 1.0, prim.data_ptr() + 4 * G,
             lit.data_ptr() + G, stride)
     hf._capi.check(lib.hf_bounce_lighting_adjoint(*head, gi.data_ptr(), gp, gwp[0], gh.data_ptr(), stream))
-    assert intact(gn) and intact(gw) and bool(gh.any())
+    assert intact(gn, n, G) and intact(gw, n, G) and bool(gh.any())
     dimg = torch.full((G + NL * n + G,), GUARD, device="cuda")
     hf._capi.check(lib.hf_bounce_lighting_tangent(*head, rows(sn), None, None, dimg.data_ptr() + 4 * G, stream))
     assert bool((dimg[:G] == GUARD).all()) and bool((dimg[G + NL * n:] == GUARD).all()) and bool((dimg[G:G + NL * n] != GUARD).all())
     for tl in (None, (C.c_float * 3)(*LIGHTS[0, :3].tolist())):
-        ro, rop = guarded(3); rd, rdp = guarded(3); rm, rmp = guarded()
+        ro, rop = guarded(n, G, 3); rd, rdp = guarded(n, G, 3); rm, rmp = guarded(n, G)
         hf._capi.check(lib.hf_bounce_rays(sc.shape._h, n, rows(p), rows(nr), rows(sn), rows(d), t.data_ptr(), 0, SEED, ids.data_ptr(),
                                           tl, rop, rdp, rmp[0], stream))
-        assert intact(ro) and intact(rd) and intact(rm)
+        assert intact(ro, n, G) and intact(rd, n, G) and intact(rm, n, G)
     torch.cuda.synchronize()
 
 
@@ -435,7 +407,6 @@ def test_forward_and_adjoint_captured_and_replayed_equal_eager(hf, scene):
     L = (hf._capi.hf_dir_light_t * NL)()
     for l in range(NL):
         L[l].to_light[0], L[l].to_light[1], L[l].to_light[2], L[l].irradiance = LIGHTS[l].tolist()
-    rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(3)])
     p, nr, sn, d, t = (x.detach().contiguous() for x in (sc.si.p, sc.si.n, sc.si.sh_frame.n, sc.ray.d, sc.si.t))
     gi = torch.from_numpy(np.random.default_rng(8).normal(size=NL * (n // spp)).astype(np.float32)).cuda()
     out = dict(image=torch.empty(NL * (n // spp), device=dev), prim=torch.empty((K, n), dtype=torch.int32, device=dev),

@@ -30,6 +30,7 @@ import torch.autograd.forward_ad as fwAD
 
 import caustic_ref as R
 import film_ref
+from row_helpers import UNSURE_CAP, _np, _rel, base_scene, guarded, intact, rows, transposition_gap
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -44,11 +45,6 @@ TOL = {k: 4 * v for k, v in F32.items()}
 # a mask is decided by the sign of a float32 quantity (c_i, <g, wi> c_i, cos_theta_t_sqr, <g, wo> <g, wi>, s, <wo, N>): a
 # lane on which one of them is below this in magnitude is decided by rounding and is left out of mask comparisons
 MARGIN = 1e-5
-UNSURE_CAP = 1e-3      # of the samples (the cap of tests/test_gpu_sky_lighting.py)
-
-
-def _np(x):
-    return x.detach().cpu().numpy()
 
 
 def _rcv(hf, z):
@@ -62,15 +58,8 @@ def _scene(hf, oracle, oi, face_normals):
     """the wavefront from origin `oi` on the shape in the given shading mode, its records as numpy, once for all tests"""
     key = (oi, face_normals)
     if key not in _SCENES:
-        h = hf.workload.sine_heights(96, 96, device="cuda")
-        shape = hf.Heightfield(heightfield=h, max_height=0.5, face_normals=face_normals)
-        rays = hf.workload.ortho_rays(64, 64, 4, "cuda", seed=1, origin=ORIGINS[oi], target=(0.0, 0.0, 0.25), scale=(0.9, 0.9, 1.0))
-        ray = hf.Ray3f(rays[0:3], rays[3:6], rays[6])
-        si = shape.ray_intersect(ray, hf.RayFlags.All)
-        sc = types.SimpleNamespace(h=h, shape=shape, rays=rays, ray=ray, si=si, n=len(ray))
-        sc.a = tuple(_np(x) for x in (si.p, si.n, si.sh_frame.n, ray.d, si.t))       # the restatement's first five arguments
-        sc.hit = np.isfinite(sc.a[4])
-        sc.field = oracle.OracleField(_np(h), max_height=0.5)
+        sc = base_scene(hf, oracle, (64, 64, 4), ORIGINS[oi], face_normals)
+        sc.a = tuple(sc.np[k] for k in ("p", "n", "sh_n", "d", "t"))                 # the restatement's first five arguments
         sc.runs = {}
         _SCENES[key] = sc
     return _SCENES[key]
@@ -89,10 +78,6 @@ def _run(hf, sc, eta, z):
         r.sure = (r.v.margin > MARGIN) | ~sc.hit
         sc.runs[key] = r
     return sc.runs[key]
-
-
-def _rel(got, ref):
-    return float(np.linalg.norm(np.asarray(got, np.float64) - ref) / np.linalg.norm(ref))
 
 
 @pytest.mark.parametrize("face_normals", [True, False])
@@ -224,11 +209,11 @@ def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, fac
             err["dpos"], err["dvalue"] = _rel(_np(tpos)[:, keep], dpos[:, keep]), _rel(_np(tval)[keep], dval[keep])
             # transposition on the device: <J u, v> = <u, J^T v>, both sides float32 results added up in float64; each
             # side is within its tolerance of the exact bilinear form, so they agree to the sum of the two
-            lhs = (_np(tpos).astype(np.float64) * gpos).sum() + (_np(tval).astype(np.float64) * gv).sum()
-            rhs = sum((got[k].astype(np.float64) * t).sum() for k, t in (("grad_sh_n", dn), ("grad_p", dp), ("grad_weight", dw)))
+            gap = transposition_gap(((_np(tpos), gpos), (_np(tval), gv)),
+                                    ((got["grad_sh_n"], dn), (got["grad_p"], dp), (got["grad_weight"], dw)))
             size = np.linalg.norm(dpos) * np.linalg.norm(gpos) + np.linalg.norm(dval) * np.linalg.norm(gv)
-            print(ORIGINS[oi], "z %.1f" % z, {k: "%.3g" % v for k, v in err.items()}, "transposition", abs(lhs - rhs) / size)
-            assert abs(lhs - rhs) <= (TOL["dpos"] + TOL["grad_sh_n"]) * size, (lhs, rhs)
+            print(ORIGINS[oi], "z %.1f" % z, {k: "%.3g" % v for k, v in err.items()}, "transposition", gap / size)
+            assert gap <= (TOL["dpos"] + TOL["grad_sh_n"]) * size, gap
             for k in err:
                 worst[k] = max(worst[k], err[k])
     print("worst", {k: "%.3g / %.3g" % (worst[k], TOL[k]) for k in TOL})
@@ -332,37 +317,28 @@ def test_nothing_is_written_beside_the_rows(hf, oracle):
     start = int(torch.nonzero(whole.vis)[0]) // 64 * 64
     cut = lambda x: x.detach()[..., start:start + n].contiguous()
     p, nr, sn, d, t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.sh_frame.n), cut(sc.ray.d), cut(sc.si.t)
-    rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(3)])
-    GUARD = -12345.0
-
-    def guarded(k=1):
-        buf = torch.full((k, n + 2 * G), GUARD, device="cuda")
-        return buf, (hf._capi._fp * k)(*[buf.data_ptr() + 4 * (j * (n + 2 * G) + G) for j in range(k)])
-
-    def intact(buf):
-        return bool((buf[:, :G] == GUARD).all()) and bool((buf[:, G + n:] == GUARD).all()) and bool((buf[:, G:G + n] != GUARD).all())
     stream = torch.cuda.current_stream().cuda_stream
     head = (n, rows(p), rows(nr), rows(sn), rows(d), t.data_ptr(), None)
-    pos, pp = guarded(2); val, vp = guarded()
+    pos, pp = guarded(n, G, 2); val, vp = guarded(n, G)
     vis = torch.full((n + 2 * G,), 0x5A, dtype=torch.uint8, device="cuda")
     hf._capi.check(lib.hf_caustic_lighting(sc.shape._h, *head, None, eta, 1.0, rcv, pp, vp[0], vis.data_ptr() + G, stream))
-    assert intact(pos) and intact(val)
+    assert intact(pos, n, G) and intact(val, n, G)
     assert bool((vis[:G] == 0x5A).all()) and bool((vis[G + n:] == 0x5A).all())
     assert torch.equal(vis[G:G + n], whole.vis[start:start + n]) and torch.equal(pos[:, G:G + n], whole.pos[:, start:start + n])
     assert torch.equal(val[0, G:G + n], whole.value[start:start + n]) and 0 < int(vis[G:G + n].sum()) < n
     bytes_ = vis[G:G + n].contiguous()
     ones = torch.ones((3, n), device="cuda")
-    gn, gnp = guarded(3); gp, gpp = guarded(3); gw, gwp = guarded()
+    gn, gnp = guarded(n, G, 3); gp, gpp = guarded(n, G, 3); gw, gwp = guarded(n, G)
     hf._capi.check(lib.hf_caustic_adjoint(*head, None, eta, 1.0, rcv, bytes_.data_ptr(), (hf._capi._fp * 2)(*rows(ones)[:2]),
                                           ones.data_ptr(), gnp, gpp, gwp[0], stream))
-    assert intact(gn) and intact(gp) and intact(gw)
-    dpos, dpp = guarded(2); dval, dvp = guarded()
+    assert intact(gn, n, G) and intact(gp, n, G) and intact(gw, n, G)
+    dpos, dpp = guarded(n, G, 2); dval, dvp = guarded(n, G)
     hf._capi.check(lib.hf_caustic_tangent(*head, None, eta, 1.0, rcv, bytes_.data_ptr(), rows(ones), rows(ones), ones.data_ptr(),
                                           dpp, dvp[0], stream))
-    assert intact(dpos) and intact(dval)
-    ro, rop = guarded(3); rd, rdp = guarded(3); rm, rmp = guarded()
+    assert intact(dpos, n, G) and intact(dval, n, G)
+    ro, rop = guarded(n, G, 3); rd, rdp = guarded(n, G, 3); rm, rmp = guarded(n, G)
     hf._capi.check(lib.hf_caustic_rays(*head, eta, rcv, rop, rdp, rmp[0], stream))
-    assert intact(ro) and intact(rd) and intact(rm)
+    assert intact(ro, n, G) and intact(rd, n, G) and intact(rm, n, G)
     assert torch.equal(rm[0, G:G + n], whole.rays.maxt[start:start + n])
     torch.cuda.synchronize()
 
@@ -374,7 +350,6 @@ def test_captured_graph_replays_to_the_same_bits(hf, oracle):
     lib = hf._capi.lib()
     rcv = r.rcv._struct()
     p, nr, sn, d, t = (x.detach().contiguous() for x in (sc.si.p, sc.si.n, sc.si.sh_frame.n, sc.ray.d, sc.si.t))
-    rows = lambda x: (hf._capi._fp * x.shape[0])(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(x.shape[0])])
     pos = torch.zeros((2, sc.n), device="cuda"); value = torch.zeros(sc.n, device="cuda")
     vis = torch.zeros(sc.n, dtype=torch.uint8, device="cuda")
     gn = torch.zeros((3, sc.n), device="cuda"); gp = torch.zeros((3, sc.n), device="cuda")

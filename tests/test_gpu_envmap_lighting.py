@@ -23,6 +23,7 @@ import envmap_ref as E
 import lighting_scenes as LS
 import sky_ref as S
 from lighting_scenes import K, MARGIN, SEED, SPLIT, _np, _rows7
+from row_helpers import GUARD, _cu, _fold, guarded, intact, sub
 
 gpu = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -82,21 +83,17 @@ def test_scene_conditions_on_the_cpu(oracle, pair):
 _BUILT = {}
 
 
-def _cuda(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
 def _env(hf, name, u, to_world=None):
     data = E.MAPS[name]()
-    return data, hf.Envmap(_cuda(data[:, :-1]), to_world=to_world, defensive=u)
+    return data, hf.Envmap(_cu(data[:, :-1]), to_world=to_world, defensive=u)
 
 
 def _scene(hf, oracle, name):
     if name not in _BUILT:
         sc = LS.scene(name)
-        sc.shape = hf.Heightfield(heightfield=_cuda(sc.h), max_height=sc.max_height, to_world=np.asarray(sc.to_world, np.float64),
+        sc.shape = hf.Heightfield(heightfield=_cu(sc.h), max_height=sc.max_height, to_world=np.asarray(sc.to_world, np.float64),
                                   flip_normals=sc.flip)
-        rt = _cuda(sc.rays)
+        rt = _cu(sc.rays)
         sc.ray = hf.Ray3f(rt[0:3].contiguous(), rt[3:6].contiguous(), rt[6].contiguous())
         sc.si = si = sc.shape.ray_intersect(sc.ray, hf.RayFlags.All)
         sc.np = {k: _np(v) for k, v in (("p", si.p), ("n", si.n), ("sh_n", si.sh_frame.n), ("d", sc.ray.d), ("t", si.t))}
@@ -126,19 +123,6 @@ def _prefix(dr, k):
     return {key: v[:k] for key, v in dr.items()}
 
 
-def _sub(hf, sc, lo, hi, requires_grad=False):
-    si = hf.SurfaceInteraction3f()
-    cut = lambda x: x.detach()[..., lo:hi].contiguous()
-    si.p, si.n, si.t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.t)
-    si.sh_frame = hf.Frame3f(None, None, cut(sc.si.sh_frame.n).requires_grad_(requires_grad))
-    return si, hf.Ray3f(cut(sc.ray.o), cut(sc.ray.d))
-
-
-def _fold(x):
-    """[H, W] -> [H, W - 1]: the seam column added onto column 0, as autograd folds the gradient of Envmap's torch.cat"""
-    return np.concatenate([x[:, :1] + x[:, -1:], x[:, 1:-1]], 1)
-
-
 def _ulps(a, b):
     return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
 
@@ -155,7 +139,7 @@ def _big_map():
 def test_table_against_the_restatement(hf, which):
     name, u = which
     data = _big_map() if name == "big" else E.MAPS[name]()
-    env = hf.Envmap(_cuda(data[:, :-1]), defensive=u)
+    env = hf.Envmap(_cu(data[:, :-1]), defensive=u)
     got = _np(env.table()).copy()
     ref = E.build_table(data, u)
     H, W = data.shape
@@ -212,14 +196,14 @@ def test_sample_direction_eval_and_pdf(hf, which, rot):
     name, u = which
     data = {"hole": _hole_map, "zero": lambda: np.zeros((5, 9), np.float32)}.get(name, E.MAPS.get(name))()
     R = ROT if rot == "default" else GENERIC_ROT
-    env = hf.Envmap(_cuda(data[:, :-1]), to_world=None if rot == "default" else R, defensive=u)
+    env = hf.Envmap(_cu(data[:, :-1]), to_world=None if rot == "default" else R, defensive=u)
     table = _np(env.table())
     H, W = data.shape
     rng = np.random.default_rng(11)
     fsx, fsy = _forced(data, table)
     sx = np.concatenate([fsx, (rng.integers(0, 1 << 23, 3000) * 2.0 ** -23).astype(np.float32)])
     sy = np.concatenate([fsy, (rng.integers(0, 1 << 23, 3000) * 2.0 ** -23).astype(np.float32)])
-    ds, weight = env.sample_direction(_cuda(np.stack([sx, sy])))
+    ds, weight = env.sample_direction(_cu(np.stack([sx, sy])))
     cx, cy, fx, fy, wc, valid = E.draw(data, table, sx, sy)
     w, L, G, st = E.shade(data, table, cx, cy, fx, fy, wc, valid, R)
     assert np.array_equal(_np(ds.cell), cy * (W - 1) + cx)                    # the cell: bit for bit
@@ -270,13 +254,13 @@ def test_eval_grid_and_eval_adjoint(hf, which):
     d = (GENERIC_ROT @ local).astype(np.float32)
     rng = np.random.default_rng(2)
     act = rng.uniform(size=d.shape[1]) < 0.9
-    got = _np(env.eval(_cuda(d), active=_cuda(act)))
+    got = _np(env.eval(_cu(d), active=_cu(act)))
     ref = E.eval_map(data, d.astype(np.float64), GENERIC_ROT, act)
     print(which, "eval err", np.abs(got - ref).max())
     assert not got[~act].any() and np.allclose(got, ref, rtol=1e-5, atol=1e-7 * np.abs(data).max())
     go = rng.normal(size=d.shape[1]).astype(np.float32)
     acc = rng.uniform(1e-3, 2e-3, data.shape).astype(np.float32)               # a non-zero accumulator: accumulation is proven
-    gd, dd, act_t, go_t = _cuda(acc), _cuda(d), _cuda(act.astype(np.uint8)), _cuda(go)
+    gd, dd, act_t, go_t = _cu(acc), _cu(d), _cu(act.astype(np.uint8)), _cu(go)
     lib = hf._capi.lib()
     hf._capi.check(lib.hf_envmap_eval_adjoint(d.shape[1], C.byref(hf.shape._p3(dd)), act_t.data_ptr(), W, H, C.byref(env._rot),
                                               go_t.data_ptr(), gd.data_ptr(), torch.cuda.current_stream().cuda_stream))
@@ -287,7 +271,7 @@ def test_eval_grid_and_eval_adjoint(hf, which):
     assert np.all(err <= bound) and np.array_equal(_np(gd)[cnt == 0], acc[cnt == 0])
     # through autograd: the seam column's gradient lands on column 0
     env.data.requires_grad_(True)
-    (env.eval(dd, active=_cuda(act)) * _cuda(go)).sum().backward()
+    (env.eval(dd, active=_cu(act)) * _cu(go)).sum().backward()
     assert np.all(np.abs(_np(env.data.grad).astype(np.float64) - _fold(rgd)) <= (_fold(cnt) + 5) * 2.0 ** -24 * _fold(ab))
 
 
@@ -367,7 +351,7 @@ def _adjoint_abi(hf, cfg, sn, dd, tt, ww, num_rays, spp, vis, gi, prior, ids=Non
     lib, p3 = hf._capi.lib(), hf.shape._p3
     n = sn.shape[1]
     W, H = cfg.env.resolution
-    gn = torch.empty_like(sn); gw = torch.empty(n, device="cuda"); gd = _cuda(prior)
+    gn = torch.empty_like(sn); gw = torch.empty(n, device="cuda"); gd = _cu(prior)
     dat = cfg.env.full().detach().contiguous()
     hf._capi.check(lib.hf_envmap_lighting_adjoint(n, spp, C.byref(p3(sn)), C.byref(p3(dd)), tt.data_ptr(), hf.shape._ptr(ww),
                                                   num_rays, SEED, hf.shape._ptr(ids), W, H, dat.data_ptr(),
@@ -390,9 +374,9 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
         for with_weight in (False, True):
             rng = np.random.default_rng(100 * spp + num_rays)
             dr = {key: v[:num_rays, ..., :m] for key, v in cfg.dr.items()}
-            si, ray = _sub(hf, sc, 0, m, requires_grad=True)
+            si, ray = sub(hf, sc, 0, m, requires_grad=True)
             wgt = rng.uniform(0.5, 1.5, m).astype(np.float32) if with_weight else None
-            wt = _cuda(wgt).requires_grad_(True) if with_weight else None
+            wt = _cu(wgt).requires_grad_(True) if with_weight else None
             cfg.env.data.requires_grad_(True); cfg.env.data.grad = None
             img, vis = hf.envmap_lighting(sc.shape, si, ray, cfg.env, albedo=ALBEDO, spp=spp, num_rays=num_rays, seed=SEED,
                                           weight=wt, return_visibility=True)
@@ -404,7 +388,7 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
             print(cfg.pair, "spp", spp, "num_rays", num_rays, "weight", with_weight, "image")
             assert ref.max() > 0 and _close(_np(img), ref, S_)
             gi = rng.normal(size=m // spp).astype(np.float32)
-            (img * _cuda(gi)).sum().backward()
+            (img * _cu(gi)).sum().backward()
             gn, gw, gd, cnt, ab = E.adjoint(*arrs, wgt, bits, dr, ALBEDO, spp, gi, cfg.data.shape)
             Sn, Sw = E.adjoint_scales(*arrs, wgt, bits, dr, ALBEDO, spp, gi)
             print("grad_sh_n"); got_n = _np(si.sh_frame.n.grad)
@@ -416,11 +400,11 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
             assert np.all(np.abs(_np(cfg.env.data.grad).astype(np.float64) - _fold(gd)) <= (_fold(cnt) + 5) * 2.0 ** -24 * _fold(ab))
             # the accumulating entry itself, per texel
             prior = rng.uniform(0.5, 1.0, cfg.data.shape).astype(np.float32) * np.float32(1e-3 * np.abs(gd).max() + 1e-6)
-            sn, dd, tt = (_cuda(a) for a in arrs)
-            an, aw, ad = _adjoint_abi(hf, cfg, sn, dd, tt, wt.detach() if with_weight else None, num_rays, spp, vis, _cuda(gi), prior)
+            sn, dd, tt = (_cu(a) for a in arrs)
+            an, aw, ad = _adjoint_abi(hf, cfg, sn, dd, tt, wt.detach() if with_weight else None, num_rays, spp, vis, _cu(gi), prior)
             assert torch.equal(an, si.sh_frame.n.grad)
             assert _texel_bound(_np(ad), prior, gd, cnt, ab) and np.array_equal(_np(ad)[cnt == 0], prior[cnt == 0])
-            an2, aw2, _ = _adjoint_abi(hf, cfg, sn, dd, tt, wt.detach() if with_weight else None, num_rays, spp, vis, _cuda(gi), prior)
+            an2, aw2, _ = _adjoint_abi(hf, cfg, sn, dd, tt, wt.detach() if with_weight else None, num_rays, spp, vis, _cu(gi), prior)
             assert torch.equal(an, an2) and torch.equal(aw, aw2)                             # bitwise repeatable
             cfg.env.data.requires_grad_(False)
             dn = rng.uniform(-0.25, 0.25, (3, m)).astype(np.float32)
@@ -429,10 +413,10 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
             tans = []
             for _ in range(2):
                 with fwAD.dual_level():
-                    si2, _r = _sub(hf, sc, 0, m)
-                    si2.sh_frame.n = fwAD.make_dual(si2.sh_frame.n, _cuda(dn))
-                    wd = fwAD.make_dual(wt.detach(), _cuda(dw)) if with_weight else None
-                    env2 = hf.Envmap(fwAD.make_dual(cfg.env.data.detach(), _cuda(dda)), defensive=cfg.u)
+                    si2, _r = sub(hf, sc, 0, m)
+                    si2.sh_frame.n = fwAD.make_dual(si2.sh_frame.n, _cu(dn))
+                    wd = fwAD.make_dual(wt.detach(), _cu(dw)) if with_weight else None
+                    env2 = hf.Envmap(fwAD.make_dual(cfg.env.data.detach(), _cu(dda)), defensive=cfg.u)
                     out = hf.envmap_lighting(sc.shape, si2, ray, env2, albedo=ALBEDO, spp=spp, num_rays=num_rays, seed=SEED, weight=wd)
                     tans.append(fwAD.unpack_dual(out).tangent.clone())
             assert torch.equal(tans[0], tans[1])
@@ -451,13 +435,13 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
 @gpu
 def test_a_cut_wavefront_is_the_whole(hf, cfg):
     sc = cfg.sc
-    gi = _cuda(np.random.default_rng(5).normal(size=sc.n // 4).astype(np.float32))
+    gi = _cu(np.random.default_rng(5).normal(size=sc.n // 4).astype(np.float32))
     ids = torch.arange(sc.n, dtype=torch.int32, device="cuda")
-    wt = _cuda(np.random.default_rng(6).uniform(0.5, 1.5, sc.n).astype(np.float32))
-    dn = _cuda(np.random.default_rng(7).normal(size=(3, sc.n)).astype(np.float32))
+    wt = _cu(np.random.default_rng(6).uniform(0.5, 1.5, sc.n).astype(np.float32))
+    dn = _cu(np.random.default_rng(7).normal(size=(3, sc.n)).astype(np.float32))
     out = []
     for lo, hi in ((0, sc.n), (0, SPLIT), (SPLIT, sc.n)):
-        si, ray = _sub(hf, sc, lo, hi, requires_grad=True)
+        si, ray = sub(hf, sc, lo, hi, requires_grad=True)
         w = wt[lo:hi].clone().requires_grad_(True)
         cfg.env.data.requires_grad_(True); cfg.env.data.grad = None
         img, vis = hf.envmap_lighting(sc.shape, si, ray, cfg.env, albedo=ALBEDO, spp=4, num_rays=K, seed=SEED, weight=w,
@@ -465,7 +449,7 @@ def test_a_cut_wavefront_is_the_whole(hf, cfg):
         (img * gi[lo // 4:hi // 4]).sum().backward()
         cfg.env.data.requires_grad_(False)
         with fwAD.dual_level():
-            si2, _r = _sub(hf, sc, lo, hi)
+            si2, _r = sub(hf, sc, lo, hi)
             si2.sh_frame.n = fwAD.make_dual(si2.sh_frame.n, dn[:, lo:hi].contiguous())
             tan = fwAD.unpack_dual(hf.envmap_lighting(sc.shape, si2, ray, cfg.env, albedo=ALBEDO, spp=4, num_rays=K, seed=SEED,
                                                       weight=w.detach(), ray_index=ids[lo:hi].contiguous())).tangent
@@ -486,7 +470,7 @@ def test_edge_cases_and_guards(hf, cfg):
     sc = cfg.sc
     lib, p3 = hf._capi.lib(), hf.shape._p3
     # an empty wavefront, and one that misses everything
-    si0, ray0 = _sub(hf, sc, 0, 0, requires_grad=True)
+    si0, ray0 = sub(hf, sc, 0, 0, requires_grad=True)
     img0, vis0 = hf.envmap_lighting(sc.shape, si0, ray0, cfg.env, spp=4, num_rays=K, return_visibility=True)
     assert img0.shape == (0,) and vis0.shape == (0,)
     img0.sum().backward()
@@ -506,7 +490,7 @@ def test_edge_cases_and_guards(hf, cfg):
     with pytest.raises(hf.HfError):
         hf.envmap_lighting(sc.shape, sc.si, sc.ray, cfg.env, num_rays=33)
     # guard values around every output row at n = 197
-    n, G, GUARD = 197, 96, -12345.0
+    n, G = 197, 96
     start = int(torch.nonzero(sc.si.is_valid())[0]) // 64 * 64
     cut = lambda x: x.detach()[..., start:start + n].contiguous()
     p, nr, sn, d, t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.sh_frame.n), cut(sc.ray.d), cut(sc.si.t)
@@ -514,46 +498,39 @@ def test_edge_cases_and_guards(hf, cfg):
     dat, tab, rot = cfg.env.full().detach().contiguous(), cfg.env.table(), C.byref(cfg.env._rot)
     envargs = (W, H, dat.data_ptr(), tab.data_ptr(), rot)
     stream = torch.cuda.current_stream().cuda_stream
-
-    def guarded(k=1):
-        buf = torch.full((k, n + 2 * G), GUARD, device="cuda")
-        return buf, (hf._capi._fp * 3)(*[buf.data_ptr() + 4 * (j * (n + 2 * G) + G) for j in range(k)] + [None] * (3 - k))
-
-    def intact(buf):
-        return bool((buf[:, :G] == GUARD).all()) and bool((buf[:, G + n:] == GUARD).all()) and bool((buf[:, G:G + n] != GUARD).all())
-    image, ip = guarded()
+    image, ip = guarded(n, G)
     vis = torch.full((n + 2 * G,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     ids = torch.arange(start, start + n, dtype=torch.int32, device="cuda")
     hf._capi.check(lib.hf_envmap_lighting(sc.shape._h, n, 1, p3(p), p3(nr), p3(sn), p3(d), t.data_ptr(), None, K, SEED,
                                           ids.data_ptr(), *envargs, ALBEDO, ip[0], vis.data_ptr() + 4 * G, stream))
-    assert intact(image) and bool((vis[:G] == 0x5A5A5A5A).all()) and bool((vis[G + n:] == 0x5A5A5A5A).all())
+    assert intact(image, n, G) and bool((vis[:G] == 0x5A5A5A5A).all()) and bool((vis[G + n:] == 0x5A5A5A5A).all())
     assert np.array_equal(_np(vis[G:G + n]).view(np.uint32), cfg.words[start:start + n])      # the slice, with its ids
     words = vis[G:G + n].contiguous()
     gi = torch.ones(n, device="cuda")
-    gn, gp = guarded(3); gw, gwp = guarded()
+    gn, gp = guarded(n, G, 3); gw, gwp = guarded(n, G)
     gd = torch.full((H + 2, W), GUARD, device="cuda")
     gd[1:H + 1] = 0.0
     head = (n, 1, p3(sn), p3(d), t.data_ptr(), None, K, SEED, ids.data_ptr(), *envargs, ALBEDO, words.data_ptr())
     hf._capi.check(lib.hf_envmap_lighting_adjoint(*head, gi.data_ptr(), gp, gwp[0], gd.data_ptr() + 4 * W, stream))
-    assert intact(gn) and intact(gw) and bool((gd[0] == GUARD).all()) and bool((gd[H + 1] == GUARD).all())
-    dimg, dp = guarded()
+    assert intact(gn, n, G) and intact(gw, n, G) and bool((gd[0] == GUARD).all()) and bool((gd[H + 1] == GUARD).all())
+    dimg, dp = guarded(n, G)
     hf._capi.check(lib.hf_envmap_lighting_tangent(*head, p3(sn), None, dat.data_ptr(), dp[0], stream))
-    assert intact(dimg)
-    ro, rop = guarded(3); rd, rdp = guarded(3); rm, rmp = guarded(); rw, rwp = guarded()
+    assert intact(dimg, n, G)
+    ro, rop = guarded(n, G, 3); rd, rdp = guarded(n, G, 3); rm, rmp = guarded(n, G); rw, rwp = guarded(n, G)
     hf._capi.check(lib.hf_envmap_rays(n, p3(p), p3(nr), p3(sn), p3(d), t.data_ptr(), 0, SEED, ids.data_ptr(), *envargs, rop, rdp,
                                       rmp[0], rwp[0], stream))
-    assert intact(ro) and intact(rd) and intact(rm) and intact(rw)
-    sd, sdp = guarded(3); sw, swp = guarded(); sp, spp_ = guarded(); sf, sfp = guarded(2)
+    assert intact(ro, n, G) and intact(rd, n, G) and intact(rm, n, G) and intact(rw, n, G)
+    sd, sdp = guarded(n, G, 3); sw, swp = guarded(n, G); sp, spp_ = guarded(n, G); sf, sfp = guarded(n, G, 2)
     cell = torch.full((n + 2 * G,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     smp = torch.rand((2, n), device="cuda")
     hf._capi.check(lib.hf_envmap_sample_direction(n, (hf._capi._fp * 2)(smp[0].data_ptr(), smp[1].data_ptr()), *envargs, sdp,
                                                   swp[0], spp_[0], cell.data_ptr() + 4 * G,
                                                   (hf._capi._fp * 2)(sfp[0], sfp[1]), stream))
-    assert intact(sd) and intact(sw) and intact(sp) and intact(sf)
+    assert intact(sd, n, G) and intact(sw, n, G) and intact(sp, n, G) and intact(sf, n, G)
     assert bool((cell[:G] == 0x5A5A5A5A).all()) and bool((cell[G + n:] == 0x5A5A5A5A).all()) and bool((cell[G:G + n] < (W - 1) * (H - 1)).all())
-    ev, evp = guarded()
+    ev, evp = guarded(n, G)
     hf._capi.check(lib.hf_envmap_eval(n, p3(d), None, W, H, dat.data_ptr(), rot, evp[0], stream))
-    assert intact(ev)
+    assert intact(ev, n, G)
     gd.fill_(GUARD); gd[1:H + 1] = 0.0                          # grad_data is the one output of hf_envmap_eval_adjoint
     hf._capi.check(lib.hf_envmap_eval_adjoint(n, p3(d), None, W, H, rot, gi.data_ptr(), gd.data_ptr() + 4 * W, stream))
     assert bool((gd[0] == GUARD).all()) and bool((gd[H + 1] == GUARD).all()) and bool((gd[1:H + 1] != GUARD).all())
@@ -571,7 +548,7 @@ def test_graph_capture_of_table_forward_and_adjoint(hf, cfg):
     p, nr, sn, d, t = (x.detach().contiguous() for x in (sc.si.p, sc.si.n, sc.si.sh_frame.n, sc.ray.d, sc.si.t))
     table = torch.zeros_like(cfg.env.table())
     image = torch.zeros(n // 4, device="cuda"); vis = torch.zeros(n, dtype=torch.int32, device="cuda")
-    gi = _cuda(np.random.default_rng(3).normal(size=n // 4).astype(np.float32))
+    gi = _cu(np.random.default_rng(3).normal(size=n // 4).astype(np.float32))
     gn = torch.zeros_like(sn); gw = torch.zeros(n, device="cuda"); gd = torch.zeros_like(dat)
     rot = C.byref(cfg.env._rot)
 
@@ -617,20 +594,20 @@ def test_gradients_through_python(hf, oracle, cfg):
     interaction), envmap.data and weight against the restatement's chain (its grad_sh_n carried to the heights by the
     oracle's adjoint); forward_ad of the texels agrees with the restatement's tangent"""
     sc = cfg.sc
-    shape = hf.Heightfield(heightfield=_cuda(sc.h), max_height=sc.max_height, to_world=np.asarray(sc.to_world, np.float64),
+    shape = hf.Heightfield(heightfield=_cu(sc.h), max_height=sc.max_height, to_world=np.asarray(sc.to_world, np.float64),
                            flip_normals=sc.flip)
     shape.heightfield.requires_grad_(True)
     si = shape.ray_intersect(sc.ray, hf.RayFlags.All)
     rng = np.random.default_rng(11)
     wgt = rng.uniform(0.5, 1.5, sc.n).astype(np.float32)
-    wt = _cuda(wgt).requires_grad_(True)
+    wt = _cu(wgt).requires_grad_(True)
     data = cfg.env.data.detach().clone().requires_grad_(True)
     env = hf.Envmap(data, defensive=cfg.u)
     img, vis = hf.envmap_lighting(shape, si, sc.ray, env, albedo=ALBEDO, spp=4, num_rays=K, seed=SEED, weight=wt,
                                   return_visibility=True)
     assert np.array_equal(_np(vis).view(np.uint32), cfg.words)
     gi = rng.normal(size=tuple(img.shape)).astype(np.float32)
-    gh, gdat, gwt = torch.autograd.grad((img * _cuda(gi)).sum(), (shape.heightfield, data, wt))
+    gh, gdat, gwt = torch.autograd.grad((img * _cu(gi)).sum(), (shape.heightfield, data, wt))
     bits = S.unpack(cfg.words, K)
     r = sc.rays
     t, u, v, prim = sc.field.ray_intersect_preliminary(r)
@@ -648,7 +625,7 @@ def test_gradients_through_python(hf, oracle, cfg):
     assert np.all(errd <= (fcnt + 5) * 2.0 ** -24 * fab) and not _np(gdat)[fcnt == 0].any()
     dda = rng.uniform(-0.5, 0.5, tuple(data.shape)).astype(np.float32)
     with fwAD.dual_level():
-        env2 = hf.Envmap(fwAD.make_dual(data.detach(), _cuda(dda)), defensive=cfg.u)
+        env2 = hf.Envmap(fwAD.make_dual(data.detach(), _cu(dda)), defensive=cfg.u)
         out = hf.envmap_lighting(sc.shape, sc.si, sc.ray, env2, albedo=ALBEDO, spp=4, num_rays=K, seed=SEED)
         tan = _np(fwAD.unpack_dual(out).tangent)
     tref, St = E.tangent(*sc.arrs, None, bits, dr, ALBEDO, 4, None, None, E.with_seam(dda), return_scale=True)

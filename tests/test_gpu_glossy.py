@@ -33,9 +33,10 @@ import pytest
 import torch
 import torch.autograd.forward_ad as fwAD
 
-import envmap_ref as E
 import glossy_ref as G
 import reflect_ref as R
+from row_helpers import (GUARD, UNSURE_CAP, _cu, _fold, _np, _rel, base_scene, envmap, guarded, intact, leaf_si, rows,
+                         transposition_gap)
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -47,24 +48,10 @@ F32 = {"value": 8.7e-4, "image": 2.2e-4, "grad_sh_n": 3.1e-5, "grad_weight": 1.5
        "dimage": 3.1e-5, "dvalue": 3.0e-5, "ray_d": 4.2e-6, "ray_h": 2.1e-6}
 TOL = {k: 4 * v for k, v in F32.items()}
 MARGIN = 1e-5
-UNSURE_CAP = 1e-3      # of the samples (the cap of tests/test_gpu_reflect.py)
-
-
-def _np(x):
-    return x.detach().cpu().numpy()
-
-
-def _cu(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 def _envmap(hf, name, rname, requires_grad=False):
-    """(Envmap, the [H, W] map with its seam column as numpy, the rotation)"""
-    full = E.MAPS[name](*G.MAP_SIZES[name])
-    data = _cu(full[:, :-1].astype(np.float32))
-    if requires_grad:
-        data.requires_grad_(True)
-    return hf.Envmap(data, to_world=G.ROTS[rname]), full, G.ROTS[rname]
+    return envmap(hf, G.MAP_SIZES, G.ROTS, name, rname, requires_grad)
 
 
 _SCENES, _DRAWS = {}, {}
@@ -74,16 +61,10 @@ def _scene(hf, oracle, oi, face_normals):
     """the wavefront from origin `oi` on the shape in the given shading mode and its records as numpy: once for all tests"""
     key = (oi, face_normals)
     if key not in _SCENES:
-        h = hf.workload.sine_heights(96, 96, device="cuda")
-        shape = hf.Heightfield(heightfield=h, max_height=0.5, face_normals=face_normals)
-        rays = hf.workload.ortho_rays(*G.FILM, "cuda", seed=1, origin=G.ORIGINS[oi], target=(0.0, 0.0, 0.25), scale=(0.9, 0.9, 1.0))
-        ray = hf.Ray3f(rays[0:3], rays[3:6], rays[6])
-        si = shape.ray_intersect(ray, hf.RayFlags.All)
-        sc = types.SimpleNamespace(key=key, h=h, shape=shape, rays=rays, ray=ray, si=si, n=len(ray))
-        sc.p = _np(si.p)
-        sc.a = tuple(_np(x) for x in (si.n, si.sh_frame.n, ray.d, si.t))             # the restatement's first four arguments
-        sc.hit = np.isfinite(sc.a[3])
-        sc.field = oracle.OracleField(_np(h), max_height=0.5)
+        sc = base_scene(hf, oracle, G.FILM, G.ORIGINS[oi], face_normals)
+        sc.key = key
+        sc.p = sc.np["p"]
+        sc.a = tuple(sc.np[k] for k in ("n", "sh_n", "d", "t"))                      # the restatement's first four arguments
         _SCENES[key] = sc
     return _SCENES[key]
 
@@ -109,10 +90,6 @@ def _draws(hf, sc, akind):
 def _sure(sc, dw, K):
     """samples none of whose first K directions is within MARGIN of a mask decision"""
     return (dw.margin[:K].min(0) > MARGIN) | ~sc.hit
-
-
-def _rel(got, ref):
-    return float(np.linalg.norm(np.asarray(got, np.float64) - ref) / np.linalg.norm(ref))
 
 
 @pytest.mark.parametrize("face_normals", [True, False])
@@ -183,20 +160,6 @@ def test_fused_equals_the_two_call_sequence_and_the_oracle(hf, oracle, face_norm
             assert torch.equal(w3, dw.words & 7)
 
 
-def _leaf_si(hf, sc, sh_n=None):
-    si = hf.SurfaceInteraction3f()
-    si.p, si.n, si.t = sc.si.p.detach(), sc.si.n.detach(), sc.si.t.detach()
-    si.sh_frame = hf.Frame3f(None, None, sc.si.sh_frame.n.detach().clone().requires_grad_(True) if sh_n is None else sh_n)
-    return si
-
-
-def _fold(gd):
-    """the gradient of the [H, W] map folded onto the [H, W - 1] texels: the seam column is a copy of column 0"""
-    out = gd[:, :-1].copy()
-    out[:, 0] += gd[:, -1]
-    return out
-
-
 @pytest.mark.parametrize("face_normals", [True, False])
 @pytest.mark.parametrize("eta", ETAS)
 def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, face_normals):
@@ -213,7 +176,7 @@ def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, fac
             kp = keep.reshape(-1, SPP).all(1)
             dn, dwt, da, gv, gi = dn * keep, dwt * keep, da * keep, gv * keep, gi * kp
             args = (*sc.a, None, w, dw.alpha, eta, K, SEED, None, full, rot, bits, SPP)
-            si = _leaf_si(hf, sc)
+            si = leaf_si(hf, sc)
             wt, at = _cu(w).requires_grad_(True), dw.alpha_t.clone().requires_grad_(True)
             img, val, words = hf.glossy_lighting(sc.shape, si, sc.ray, env, at, eta=eta, spp=SPP, num_rays=K, seed=SEED, weight=wt,
                                                  return_value=True, return_visibility=True)
@@ -234,7 +197,7 @@ def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, fac
             err["grad_alpha"] = _rel(got["grad_alpha"][keep], ga[keep])
             err["grad_data"] = _rel(got["grad_data"], _fold(gd))
             with fwAD.dual_level():
-                sd = _leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), _cu(dn.astype(np.float32))))
+                sd = leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), _cu(dn.astype(np.float32))))
                 envd = hf.Envmap(fwAD.make_dual(env.data.detach(), _cu(dd[:, :-1])), to_world=rot)
                 ti, tv = hf.glossy_lighting(sc.shape, sd, sc.ray, envd, fwAD.make_dual(dw.alpha_t, _cu(da.astype(np.float32))), eta=eta,
                                             spp=SPP, num_rays=K, seed=SEED, weight=fwAD.make_dual(_cu(w), _cu(dwt.astype(np.float32))),
@@ -246,13 +209,13 @@ def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, fac
             err["dimage"], err["dvalue"] = _rel(_np(timg)[kp], dimg[kp]), _rel(_np(tval)[keep], dval[keep])
             # transposition on the device: <J u, v> = <u, J^T v>, both sides float32 results added up in float64; each side
             # is within its tolerance of the exact bilinear form, so they agree to the sum of the two
-            lhs = (_np(timg).astype(np.float64) * gi).sum() + (_np(tval).astype(np.float64) * gv).sum()
-            rhs = (got["grad_sh_n"].astype(np.float64) * dn).sum() + (got["grad_weight"].astype(np.float64) * dwt).sum() + \
-                (got["grad_alpha"].astype(np.float64) * da).sum() + (got["grad_data"].astype(np.float64) * dd[:, :-1]).sum()
+            gap = transposition_gap(((_np(timg), gi), (_np(tval), gv)),
+                                    ((got["grad_sh_n"], dn), (got["grad_weight"], dwt), (got["grad_alpha"], da),
+                                     (got["grad_data"], dd[:, :-1])))
             size = np.linalg.norm(dimg) * np.linalg.norm(gi) + np.linalg.norm(dval) * np.linalg.norm(gv)
             print(G.ORIGINS[oi], K, akind, name, rname, {k: "%.3g" % v for k, v in err.items()}, "left out", float((~keep).mean()),
-                  "transposition", abs(lhs - rhs) / size)
-            assert abs(lhs - rhs) <= (TOL["dvalue"] + TOL["grad_sh_n"]) * size, (lhs, rhs)
+                  "transposition", gap / size)
+            assert gap <= (TOL["dvalue"] + TOL["grad_sh_n"]) * size, gap
             for k in err:
                 worst[k] = max(worst[k], err[k])
     print("worst", {k: "%.3g / %.3g" % (worst[k], TOL[k]) for k in worst})
@@ -267,7 +230,7 @@ def test_forward_and_reverse_mode_agree(hf, oracle):
     sc = _scene(hf, oracle, 1, False)
     env, full, rot = _envmap(hf, "sun", "identity", requires_grad=True)
     w, gi, gv, dn, dw, da, dd = (_cu(x) for x in G.test_inputs(sc.n, full.shape))
-    si = _leaf_si(hf, sc)
+    si = leaf_si(hf, sc)
     wt = w.clone().requires_grad_(True)
     al = torch.tensor(0.3, device="cuda", requires_grad=True)
     img, val = hf.glossy_lighting(sc.shape, si, sc.ray, env, al, eta=1.5, spp=SPP, num_rays=3, seed=SEED, weight=wt, return_value=True)
@@ -276,7 +239,7 @@ def test_forward_and_reverse_mode_agree(hf, oracle):
     rhs = sum(float((g.double() * t.double()).sum()) for g, t in ((si.sh_frame.n.grad, dn), (wt.grad, dw), (env.data.grad, dd[:, :-1]))) + \
         0.7 * float(al.grad)
     with fwAD.dual_level():
-        sd = _leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), dn))
+        sd = leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), dn))
         envd = hf.Envmap(fwAD.make_dual(env.data.detach(), dd[:, :-1].contiguous()), to_world=rot)
         ald = fwAD.make_dual(torch.tensor(0.3, device="cuda"), torch.tensor(0.7, device="cuda"))
         ti, tv = hf.glossy_lighting(sc.shape, sd, sc.ray, envd, ald, eta=1.5, spp=SPP, num_rays=3, seed=SEED, weight=fwAD.make_dual(w, dw),
@@ -330,7 +293,7 @@ def test_repeatable_and_edge_cases(hf, oracle):
     w, gi, gv, dn, dwt, da, dd = (_cu(x) for x in G.test_inputs(sc.n, full.shape))
     runs = []
     for _ in range(2):
-        si = _leaf_si(hf, sc)
+        si = leaf_si(hf, sc)
         wt, at = w.clone().requires_grad_(True), dw.alpha_t.clone().requires_grad_(True)
         img, val, vis = hf.glossy_lighting(sc.shape, si, sc.ray, env, at, eta=1.5, spp=SPP, num_rays=32, seed=SEED, weight=wt,
                                            return_value=True, return_visibility=True)
@@ -388,33 +351,23 @@ def test_odd_sizes_guard_bands_and_optional_pointers(hf, oracle, spp):
     cut = lambda x: x.detach()[..., start:start + n].contiguous()
     p, nr, sn, d, t, al = cut(sc.si.p), cut(sc.si.n), cut(sc.si.sh_frame.n), cut(sc.ray.d), cut(sc.si.t), cut(dw.alpha_t)
     ids = torch.arange(start, start + n, device="cuda", dtype=torch.int32)
-    rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(3)])
-    GUARD = -12345.0
-
-    def guarded(m, k=1, dtype=torch.float32):
-        buf = torch.full((k, m + 2 * GB), GUARD, device="cuda").to(dtype)
-        return buf, (hf._capi._fp * k)(*[buf.data_ptr() + 4 * (j * (m + 2 * GB) + GB) for j in range(k)])
-
-    def intact(buf, m):
-        g = buf[0, 0]
-        return bool((buf[:, :GB] == g).all()) and bool((buf[:, GB + m:] == g).all()) and bool((buf[:, GB:GB + m] != g).all())
     stream = torch.cuda.current_stream().cuda_stream
     mid = (None, None, al.data_ptr(), eta, K, SEED, ids.data_ptr(), W, H, dat.data_ptr(), C.byref(env._rot))
     fwd = lambda image, value, vis: hf._capi.check(lib.hf_glossy_lighting(sc.shape._h, n, spp, rows(p), rows(nr), rows(sn), rows(d),
                                                                           t.data_ptr(), *mid, image, value, vis, stream))
-    img, ip = guarded(npix); val, vp = guarded(n); vis, vsp = guarded(n, 1, torch.int32)
+    img, ip = guarded(npix, GB); val, vp = guarded(n, GB); vis, vsp = guarded(n, GB, 1, torch.int32)
     fwd(ip[0], vp[0], vsp[0])
-    assert intact(img, npix) and intact(val, n) and intact(vis, n)
+    assert intact(img, npix, GB) and intact(val, n, GB) and intact(vis, n, GB)
     assert torch.equal(vis[0, GB:GB + n], dw.words[start:start + n]) and torch.equal(val[0, GB:GB + n], whole_val[start:start + n])
     assert int((vis[0, GB:GB + n] != 0).sum()) > 0
     want = val[0, GB:GB + n].reshape(npix, spp).double().mean(1)
     assert float((img[0, GB:GB + npix] - want).abs().max()) <= 2.5e-7 * float(want.abs().max())
     # (the film: one product and at most three additions per pixel, each rounded to 2^-24 of the largest value: 2.5e-7)
     for skip in range(3):       # every optional output NULL in turn: the others are unchanged
-        img2, ip2 = guarded(npix); val2, vp2 = guarded(n); vis2, vsp2 = guarded(n, 1, torch.int32)
+        img2, ip2 = guarded(npix, GB); val2, vp2 = guarded(n, GB); vis2, vsp2 = guarded(n, GB, 1, torch.int32)
         fwd(None if skip == 0 else ip2[0], None if skip == 1 else vp2[0], None if skip == 2 else vsp2[0])
         if skip != 0:
-            assert intact(img2, npix) and float((img2 - img).abs().max()) <= 2.5e-7 * float(want.abs().max())
+            assert intact(img2, npix, GB) and float((img2 - img).abs().max()) <= 2.5e-7 * float(want.abs().max())
         else:
             assert bool((img2 == GUARD).all())
         assert torch.equal(val2, val) if skip != 1 else bool((val2 == GUARD).all())
@@ -423,30 +376,30 @@ def test_odd_sizes_guard_bands_and_optional_pointers(hf, oracle, spp):
     ones, onesp = torch.ones((3, n), device="cuda"), torch.ones(npix, device="cuda")
     head = (n, spp, rows(sn), rows(d), t.data_ptr(), *mid, words.data_ptr())
     adj = lambda *tail: hf._capi.check(lib.hf_glossy_lighting_adjoint(*head, *tail, stream))
-    gn, gnp = guarded(n, 3); gw, gwp = guarded(n); ga, gap = guarded(n)
+    gn, gnp = guarded(n, GB, 3); gw, gwp = guarded(n, GB); ga, gap = guarded(n, GB)
     gd = torch.full((H * W + 2 * GB,), 0.0, device="cuda"); gd[:GB] = GUARD; gd[GB + H * W:] = GUARD
     adj(onesp.data_ptr(), ones.data_ptr(), gnp, gwp[0], gap[0], gd.data_ptr() + 4 * GB)
-    assert intact(gn, n) and intact(gw, n) and intact(ga, n) and bool((gd[:GB] == GUARD).all()) and bool((gd[GB + H * W:] == GUARD).all())
+    assert intact(gn, n, GB) and intact(gw, n, GB) and intact(ga, n, GB) and bool((gd[:GB] == GUARD).all()) and bool((gd[GB + H * W:] == GUARD).all())
     assert float(gd[GB:GB + H * W].abs().sum()) > 0 and float(ga[0, GB:GB + n].abs().sum()) > 0
     # each adjoint output NULL in turn, and each upstream NULL
-    gn2, gnp2 = guarded(n, 3); gw2, gwp2 = guarded(n); ga2, gap2 = guarded(n)
+    gn2, gnp2 = guarded(n, GB, 3); gw2, gwp2 = guarded(n, GB); ga2, gap2 = guarded(n, GB)
     adj(onesp.data_ptr(), ones.data_ptr(), None, gwp2[0], None, None)
     adj(onesp.data_ptr(), ones.data_ptr(), gnp2, None, gap2[0], None)
     assert torch.equal(gn2, gn) and torch.equal(gw2, gw) and torch.equal(ga2, ga)
-    g1, g1p = guarded(n, 3); g2, g2p = guarded(n, 3)
+    g1, g1p = guarded(n, GB, 3); g2, g2p = guarded(n, GB, 3)
     adj(onesp.data_ptr(), None, g1p, None, None, None)
     adj(None, ones.data_ptr(), g2p, None, None, None)
     scale = float(gn[:, GB:GB + n].abs().max())
     assert float((g1 + g2 - gn)[:, GB:GB + n].abs().max()) <= 1e-6 * scale
-    dimg, dip = guarded(npix); dval, dvp = guarded(n)
+    dimg, dip = guarded(npix, GB); dval, dvp = guarded(n, GB)
     ddat = torch.ones((H, W), device="cuda")
     tail = (rows(ones), ones.data_ptr(), ones.data_ptr(), ddat.data_ptr())
     tan = lambda *out: hf._capi.check(lib.hf_glossy_lighting_tangent(*head, *tail, *out, stream))
     tan(dip[0], dvp[0])
-    assert intact(dimg, npix) and intact(dval, n)
+    assert intact(dimg, npix, GB) and intact(dval, n, GB)
     wantd = dval[0, GB:GB + n].reshape(npix, spp).double().mean(1)
     assert float((dimg[0, GB:GB + npix] - wantd).abs().max()) <= 2.5e-7 * float(dval[0, GB:GB + n].abs().max())
-    dimg2, dip2 = guarded(npix); dval2, dvp2 = guarded(n)
+    dimg2, dip2 = guarded(npix, GB); dval2, dvp2 = guarded(n, GB)
     tan(dip2[0], None)
     tan(None, dvp2[0])
     assert torch.equal(dimg2, dimg) and torch.equal(dval2, dval)
@@ -454,18 +407,18 @@ def test_odd_sizes_guard_bands_and_optional_pointers(hf, oracle, spp):
     # (each part is a few float32 roundings of its own size off: 1e-6 of the largest part)
     parts, size = torch.zeros(n, device="cuda", dtype=torch.float64), float(dval[0, GB:GB + n].abs().max())
     for j in range(4):
-        dv, dvq = guarded(n)
+        dv, dvq = guarded(n, GB)
         one = [None] * 4; one[j] = tail[j]
         hf._capi.check(lib.hf_glossy_lighting_tangent(*head, *one, None, dvq[0], stream))
         parts += dv[0, GB:GB + n].double()
         size = max(size, float(dv[0, GB:GB + n].abs().max()))
     assert float((parts - dval[0, GB:GB + n].double()).abs().max()) <= 1e-6 * size
-    ro, rop = guarded(n, 3); rd, rdp = guarded(n, 3); rm, rmp = guarded(n); rh, rhp = guarded(n, 3)
+    ro, rop = guarded(n, GB, 3); rd, rdp = guarded(n, GB, 3); rm, rmp = guarded(n, GB); rh, rhp = guarded(n, GB, 3)
     ray_args = (n, rows(p), rows(nr), rows(sn), rows(d), t.data_ptr(), None, al.data_ptr(), 31, SEED, ids.data_ptr())
     hf._capi.check(lib.hf_glossy_rays(*ray_args, rop, rdp, rmp[0], rhp, stream))
-    assert intact(ro, n) and intact(rd, n) and intact(rm, n) and intact(rh, n)
+    assert intact(ro, n, GB) and intact(rd, n, GB) and intact(rm, n, GB) and intact(rh, n, GB)
     assert torch.equal(rm[0, GB:GB + n], dw.rr[31].maxt[start:start + n]) and torch.equal(rh[:, GB:GB + n], dw.hh[31][:, start:start + n])
-    rd2, rdp2 = guarded(n, 3)
+    rd2, rdp2 = guarded(n, GB, 3)
     hf._capi.check(lib.hf_glossy_rays(*ray_args, rop, rdp2, rmp[0], None, stream))        # out_h is optional
     assert torch.equal(rd2, rd)
     torch.cuda.synchronize()
@@ -480,7 +433,6 @@ def test_captured_graph_replays_to_the_same_bits(hf, oracle):
     H, W = full.shape
     K = 3
     p, nr, sn, d, t = (x.detach().contiguous() for x in (sc.si.p, sc.si.n, sc.si.sh_frame.n, sc.ray.d, sc.si.t))
-    rows = lambda x: (hf._capi._fp * x.shape[0])(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(x.shape[0])])
     img = torch.zeros(sc.n // SPP, device="cuda"); value = torch.zeros(sc.n, device="cuda")
     vis = torch.zeros(sc.n, dtype=torch.int32, device="cuda")
     gn = torch.zeros((3, sc.n), device="cuda"); ga = torch.zeros(sc.n, device="cuda"); timg = torch.zeros(sc.n // SPP, device="cuda")

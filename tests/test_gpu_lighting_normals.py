@@ -46,6 +46,7 @@ import envmap_ref as E
 import lighting_scenes as LS
 import sky_ref as S
 from lighting_scenes import K, MARGIN, MISS, SEED, _close, _np, _records, _rows7
+from row_helpers import _cu, sub
 from test_gpu_envmap_lighting import _close as _close_env, _fold
 
 pytestmark = pytest.mark.gpu
@@ -59,10 +60,6 @@ _BUILT, _ENV = {}, {}
 
 def _id(p):
     return "-".join(str(x) for x in p)
-
-
-def _cuda(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 @pytest.fixture(scope="module", params=CONFIGS, ids=_id)
@@ -86,9 +83,9 @@ def _build(hf, oracle, name, kind):
     sc = LS.scene(name)
     sc.kind = kind
     sc.tw64 = np.asarray(sc.to_world, np.float64)
-    mk = lambda fn: hf.Heightfield(heightfield=_cuda(sc.h), max_height=sc.max_height, to_world=sc.tw64, flip_normals=sc.flip,
+    mk = lambda fn: hf.Heightfield(heightfield=_cu(sc.h), max_height=sc.max_height, to_world=sc.tw64, flip_normals=sc.flip,
                                    face_normals=fn)
-    rt = _cuda(sc.rays)
+    rt = _cu(sc.rays)
     sc.ray = hf.Ray3f(rt[0:3].contiguous(), rt[3:6].contiguous(), rt[6].contiguous())
     flat = mk(True)
     fsi = flat.ray_intersect(sc.ray, hf.RayFlags.All)
@@ -111,7 +108,7 @@ def _build(hf, oracle, name, kind):
         sc.shape = flat
         si = hf.SurfaceInteraction3f()
         si.p, si.n, si.t = fsi.p.detach(), fsi.n.detach(), fsi.t.detach()
-        si.sh_frame = hf.Frame3f(None, None, _cuda(LS.bent_normals(_np(fsi.n), sc.hit)))
+        si.sh_frame = hf.Frame3f(None, None, _cu(LS.bent_normals(_np(fsi.n), sc.hit)))
     sc.si = si
     sc.lt = torch.from_numpy(sc.lights)
     sc.np = {k: _np(v) for k, v in (("p", si.p), ("n", si.n), ("sh_n", si.sh_frame.n), ("d", sc.ray.d), ("t", si.t))}
@@ -142,7 +139,7 @@ def _env(hf, oracle, scene, kind, name, u):
         sc = _scene(hf, oracle, scene, kind)
         c = types.SimpleNamespace(sc=sc, name=name, u=u, pair=(scene, kind, name, u))
         c.data = E.MAPS[name]()
-        c.env = hf.Envmap(_cuda(c.data[:, :-1]), defensive=u)
+        c.env = hf.Envmap(_cu(c.data[:, :-1]), defensive=u)
         c.table = _np(c.env.table())                                      # the DEVICE's table: the restatement draws the same cells
         c.dr = E.draws(c.data, c.table, np.arange(sc.n), K, SEED, ROT)
         c.traced, c.margin = E.traced(*sc.arrs, c.dr)
@@ -151,15 +148,6 @@ def _env(hf, oracle, scene, kind, name, u):
         c.words = _np(vis).view(np.uint32)
         _ENV[scene, kind, name, u] = c
     return _ENV[scene, kind, name, u]
-
-
-def _sub(hf, sc, m, requires_grad=False):
-    """(si, ray) of the samples [0, m) as records of their own"""
-    si = hf.SurfaceInteraction3f()
-    cut = lambda x: x.detach()[..., :m].contiguous()
-    si.p, si.n, si.t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.t)
-    si.sh_frame = hf.Frame3f(None, None, cut(sc.si.sh_frame.n).requires_grad_(requires_grad))
-    return si, hf.Ray3f(cut(sc.ray.o), cut(sc.ray.d))
 
 
 # ---- (1) the materialised rays ---------------------------------------------------------------------------------------
@@ -352,9 +340,9 @@ def test_bounce_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
     m = sc.n - sc.n % spp
     albedo, wmax = 0.7, 1.5
     rng = np.random.default_rng(100 * spp + 4)
-    si, ray = _sub(hf, sc, m, requires_grad=True)
+    si, ray = sub(hf, sc, 0, m, requires_grad=True)
     wgt = rng.uniform(0.5, wmax, m).astype(np.float32)
-    wt = _cuda(wgt).requires_grad_(True)
+    wt = _cu(wgt).requires_grad_(True)
     img, prim, lit = hf.bounce_lighting(sc.shape, si, ray, sc.lt, albedo=albedo, spp=spp, num_rays=K, seed=SEED, weight=wt,
                                         return_records=True)
     assert img.shape == (sc.L, m // spp) and prim.shape == (K, m) and lit.shape == (K, m)
@@ -368,7 +356,7 @@ def test_bounce_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
     print(sc.name, sc.kind, "spp", spp, "image")
     assert np.all(ref.max(1) > 0) and 0.002 < ref.max() <= 1.0 and _close(_np(img), ref, absum, K)   # (every light's row is lit)
     gi = rng.normal(size=(sc.L, m // spp)).astype(np.float32)
-    (img * _cuda(gi)).sum().backward()
+    (img * _cu(gi)).sum().backward()
     adj = B.adjoint(*arrs, wgt, hit, lt, nq, sc.lights, albedo, spp, w, z, gi)
     el = _shaded(sc, m)
     got_n, got_w = _np(si.sh_frame.n.grad), _np(wt.grad)
@@ -380,9 +368,9 @@ def test_bounce_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
     dn = rng.uniform(-0.25, 0.25, (3, m)).astype(np.float32)
     dw = rng.uniform(-0.5, 0.5, m).astype(np.float32)
     with fwAD.dual_level():
-        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cuda(dn))
+        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cu(dn))
         out = hf.bounce_lighting(sc.shape, si, ray, sc.lt, albedo=albedo, spp=spp, num_rays=K, seed=SEED,
-                                 weight=fwAD.make_dual(wt.detach(), _cuda(dw)))
+                                 weight=fwAD.make_dual(wt.detach(), _cu(dw)))
         tan = _np(fwAD.unpack_dual(out).tangent)
     tref, tabs = B.tangent(*arrs, wgt, hit, lt, nq, sc.lights, albedo, spp, w, z, dn, dw)
     print("tangent")
@@ -397,9 +385,9 @@ def test_sky_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
     albedo, wmax = 0.7, 1.5
     L = 1.0 / (4.0 * albedo * wmax)
     rng = np.random.default_rng(100 * spp + 8)
-    si, ray = _sub(hf, sc, m, requires_grad=True)
+    si, ray = sub(hf, sc, 0, m, requires_grad=True)
     wgt = rng.uniform(0.5, wmax, m).astype(np.float32)
-    wt = _cuda(wgt).requires_grad_(True)
+    wt = _cu(wgt).requires_grad_(True)
     img, vis = hf.sky_lighting(sc.shape, si, ray, radiance=L, albedo=albedo, spp=spp, num_rays=K, seed=SEED, weight=wt,
                                return_visibility=True)
     assert img.shape == (m // spp,) and vis.shape == (m,)
@@ -412,7 +400,7 @@ def test_sky_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
     print(sc.name, sc.kind, "spp", spp, "image: max", ref.max(), "err", np.abs(got - ref).max())
     assert 0.02 < ref.max() <= 1.0 and np.allclose(got, ref, rtol=1e-5, atol=1e-7), np.abs(got - ref).max()
     gi = rng.normal(size=m // spp).astype(np.float32)
-    (img * _cuda(gi)).sum().backward()
+    (img * _cu(gi)).sum().backward()
     gn, gw = S.adjoint(*arrs, wgt, bits, w, L, albedo, spp, gi)
     got_n, got_w = _np(si.sh_frame.n.grad), _np(wt.grad)
     print("grad_sh_n: max", np.abs(gn).max(), "err", np.abs(got_n - gn).max(), "grad_weight: err", np.abs(got_w - gw).max())
@@ -423,9 +411,9 @@ def test_sky_image_adjoint_and_tangent_against_the_restatement(hf, cfg, spp):
     dn = rng.uniform(-0.25, 0.25, (3, m)).astype(np.float32)
     dw = rng.uniform(-0.5, 0.5, m).astype(np.float32)
     with fwAD.dual_level():
-        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cuda(dn))
+        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cu(dn))
         out = hf.sky_lighting(sc.shape, si, ray, radiance=L, albedo=albedo, spp=spp, num_rays=K, seed=SEED,
-                              weight=fwAD.make_dual(wt.detach(), _cuda(dw)))
+                              weight=fwAD.make_dual(wt.detach(), _cu(dw)))
         tan = _np(fwAD.unpack_dual(out).tangent)
     tref = S.tangent(*arrs, wgt, bits, w, L, albedo, spp, dn, dw)
     print("tangent: max", np.abs(tref).max(), "err", np.abs(tan - tref).max())
@@ -442,9 +430,9 @@ def test_envmap_image_adjoint_and_tangent_against_the_restatement(hf, ecfg, spp)
     arrs = [a[..., :m] for a in sc.arrs]
     dr = {key: v[..., :m] for key, v in c.dr.items()}
     rng = np.random.default_rng(100 * spp + K)
-    si, ray = _sub(hf, sc, m, requires_grad=True)
+    si, ray = sub(hf, sc, 0, m, requires_grad=True)
     wgt = rng.uniform(0.5, 1.5, m).astype(np.float32)
-    wt = _cuda(wgt).requires_grad_(True)
+    wt = _cu(wgt).requires_grad_(True)
     c.env.data.requires_grad_(True); c.env.data.grad = None
     try:
         img, vis = hf.envmap_lighting(sc.shape, si, ray, c.env, albedo=ALBEDO, spp=spp, num_rays=K, seed=SEED, weight=wt,
@@ -456,7 +444,7 @@ def test_envmap_image_adjoint_and_tangent_against_the_restatement(hf, ecfg, spp)
         print(c.pair, "spp", spp, "image")
         assert ref.max() > 0 and _close_env(_np(img), ref, S_)
         gi = rng.normal(size=m // spp).astype(np.float32)
-        (img * _cuda(gi)).sum().backward()
+        (img * _cu(gi)).sum().backward()
         got_d = _np(c.env.data.grad).astype(np.float64)
     finally:
         c.env.data.requires_grad_(False); c.env.data.grad = None
@@ -474,10 +462,10 @@ def test_envmap_image_adjoint_and_tangent_against_the_restatement(hf, ecfg, spp)
     dw = rng.uniform(-0.5, 0.5, m).astype(np.float32)
     dda = rng.uniform(-0.5, 0.5, c.data[:, :-1].shape).astype(np.float32)
     with fwAD.dual_level():
-        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cuda(dn))
-        env2 = hf.Envmap(fwAD.make_dual(c.env.data.detach(), _cuda(dda)), defensive=c.u)
+        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cu(dn))
+        env2 = hf.Envmap(fwAD.make_dual(c.env.data.detach(), _cu(dda)), defensive=c.u)
         out = hf.envmap_lighting(sc.shape, si, ray, env2, albedo=ALBEDO, spp=spp, num_rays=K, seed=SEED,
-                                 weight=fwAD.make_dual(wt.detach(), _cuda(dw)))
+                                 weight=fwAD.make_dual(wt.detach(), _cu(dw)))
         tan = _np(fwAD.unpack_dual(out).tangent)
     tref, St = E.tangent(*arrs, wgt, bits, dr, ALBEDO, spp, dn, dw, E.with_seam(dda), return_scale=True)
     print("tangent")

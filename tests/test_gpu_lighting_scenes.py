@@ -21,6 +21,7 @@ import bounce_ref as B
 import lighting_scenes as LS
 import sky_ref as S
 from lighting_scenes import K, MARGIN, MISS, SEED, SPLIT, _close, _np, _records, _rows7
+from row_helpers import _cu, sub
 
 pytestmark = pytest.mark.gpu
 
@@ -72,22 +73,9 @@ def _build(hf, oracle, name):
     return sc
 
 
-def _sub(hf, sc, lo, hi, requires_grad=False):
-    """(si, ray) of the samples [lo, hi) as records of their own"""
-    si = hf.SurfaceInteraction3f()
-    cut = lambda x: x.detach()[..., lo:hi].contiguous()
-    si.p, si.n, si.t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.t)
-    si.sh_frame = hf.Frame3f(None, None, cut(sc.si.sh_frame.n).requires_grad_(requires_grad))
-    return si, hf.Ray3f(cut(sc.ray.o), cut(sc.ray.d))
-
-
 def _nq(sc, prim, hit):
     """[K, 3, m] float64: the restatement's face normals of the recorded triangles (never a second product call)"""
     return np.stack([LS.normals_of(sc, prim[k], hit[k]) for k in range(len(prim))])
-
-
-def _cuda(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 # ---- (1) the materialised rays ---------------------------------------------------------------------------------------
@@ -208,9 +196,9 @@ def test_bounce_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp
     m = sc.n - sc.n % spp
     albedo, wmax = 0.7, 1.5
     rng = np.random.default_rng(100 * spp + 4)
-    si, ray = _sub(hf, sc, 0, m, requires_grad=True)
+    si, ray = sub(hf, sc, 0, m, requires_grad=True)
     wgt = rng.uniform(0.5, wmax, m).astype(np.float32) if with_weight else None
-    wt = _cuda(wgt).requires_grad_(True) if with_weight else None
+    wt = _cu(wgt).requires_grad_(True) if with_weight else None
     img, prim, lit = hf.bounce_lighting(sc.shape, si, ray, sc.lt, albedo=albedo, spp=spp, num_rays=K, seed=SEED, weight=wt,
                                         return_records=True)
     assert img.shape == (sc.L, m // spp) and prim.shape == (K, m) and lit.shape == (K, m)
@@ -223,7 +211,7 @@ def test_bounce_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp
     print(sc.name, "spp", spp, "image")
     assert np.all(ref.max(1) > 0) and 0.002 < ref.max() <= 1.0 and _close(_np(img), ref, absum, K)   # (every light's row is lit)
     gi = rng.normal(size=(sc.L, m // spp)).astype(np.float32)
-    (img * _cuda(gi)).sum().backward()
+    (img * _cu(gi)).sum().backward()
     adj = B.adjoint(*arrs, wgt, hit, lt, nq, sc.lights, albedo, spp, w, z, gi)
     el = sc.eligible[:m]
     got_n = _np(si.sh_frame.n.grad)
@@ -238,8 +226,8 @@ def test_bounce_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp
     dn = rng.uniform(-0.25, 0.25, (3, m)).astype(np.float32)
     dw = rng.uniform(-0.5, 0.5, m).astype(np.float32) if with_weight else None
     with fwAD.dual_level():
-        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cuda(dn))
-        wd = fwAD.make_dual(wt.detach(), _cuda(dw)) if with_weight else None
+        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cu(dn))
+        wd = fwAD.make_dual(wt.detach(), _cu(dw)) if with_weight else None
         out = hf.bounce_lighting(sc.shape, si, ray, sc.lt, albedo=albedo, spp=spp, num_rays=K, seed=SEED, weight=wd)
         tan = _np(fwAD.unpack_dual(out).tangent)
     tref, tabs = B.tangent(*arrs, wgt, hit, lt, nq, sc.lights, albedo, spp, w, z, dn, dw)
@@ -256,9 +244,9 @@ def test_sky_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp, w
     albedo, wmax = 0.7, 1.5
     L = 1.0 / (4.0 * albedo * wmax)
     rng = np.random.default_rng(100 * spp + 8)
-    si, ray = _sub(hf, sc, 0, m, requires_grad=True)
+    si, ray = sub(hf, sc, 0, m, requires_grad=True)
     wgt = rng.uniform(0.5, wmax, m).astype(np.float32) if with_weight else None
-    wt = _cuda(wgt).requires_grad_(True) if with_weight else None
+    wt = _cu(wgt).requires_grad_(True) if with_weight else None
     img, vis = hf.sky_lighting(sc.shape, si, ray, radiance=L, albedo=albedo, spp=spp, num_rays=K, seed=SEED, weight=wt,
                                return_visibility=True)
     assert img.shape == (m // spp,) and vis.shape == (m,)
@@ -271,7 +259,7 @@ def test_sky_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp, w
     print(sc.name, "spp", spp, "image: max", ref.max(), "err", np.abs(got - ref).max())
     assert 0.02 < ref.max() <= 1.0 and np.allclose(got, ref, rtol=1e-5, atol=1e-7), np.abs(got - ref).max()
     gi = rng.normal(size=m // spp).astype(np.float32)
-    (img * _cuda(gi)).sum().backward()
+    (img * _cu(gi)).sum().backward()
     gn, gw = S.adjoint(*arrs, wgt, bits, w, L, albedo, spp, gi)
     got_n = _np(si.sh_frame.n.grad)
     print("grad_sh_n: max", np.abs(gn).max(), "err", np.abs(got_n - gn).max())
@@ -286,8 +274,8 @@ def test_sky_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp, w
     dn = rng.uniform(-0.25, 0.25, (3, m)).astype(np.float32)
     dw = rng.uniform(-0.5, 0.5, m).astype(np.float32) if with_weight else None
     with fwAD.dual_level():
-        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cuda(dn))
-        wd = fwAD.make_dual(wt.detach(), _cuda(dw)) if with_weight else None
+        si.sh_frame.n = fwAD.make_dual(si.sh_frame.n.detach(), _cu(dn))
+        wd = fwAD.make_dual(wt.detach(), _cu(dw)) if with_weight else None
         out = hf.sky_lighting(sc.shape, si, ray, radiance=L, albedo=albedo, spp=spp, num_rays=K, seed=SEED, weight=wd)
         tan = _np(fwAD.unpack_dual(out).tangent)
     tref = S.tangent(*arrs, wgt, bits, w, L, albedo, spp, dn, dw)
@@ -321,7 +309,7 @@ def test_bounce_grad_heights_of_the_c_entry(hf, scene):
     rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (j * x.shape[1]) for j in range(3)])
     sn, dd, tt = (x.detach().contiguous() for x in (sc.si.sh_frame.n, sc.ray.d, sc.si.t))
     gh = sc.shape._zero_heights()
-    git = _cuda(gi)
+    git = _cu(gi)
     hf._capi.check(hf._capi.lib().hf_bounce_lighting_adjoint(
         sc.shape._h, sc.n, spp, rows(sn), rows(dd), tt.data_ptr(), None, K, SEED, None, sc.L, _lights_struct(hf, sc), albedo,
         sc.prim_t.data_ptr(), sc.lit_t.data_ptr(), sc.n, git.data_ptr(), None, None, gh.data_ptr(),
@@ -342,7 +330,7 @@ def _chain(hf, oracle, sc, face_normals):
     si = shape.ray_intersect(sc.ray, hf.RayFlags.All)
     img, prim, lit = hf.bounce_lighting(shape, si, sc.ray, sc.lt, albedo=albedo, spp=spp, num_rays=K, seed=SEED, return_records=True)
     gi = np.random.default_rng(12).normal(size=tuple(img.shape)).astype(np.float32)
-    (img * _cuda(gi)).sum().backward()
+    (img * _cu(gi)).sum().backward()
     got = _np(shape.heightfield.grad).astype(np.float64)
     sh_n, t = _np(si.sh_frame.n), _np(si.t)
     hit, lt = _records(prim, lit, sc.L)
@@ -356,7 +344,7 @@ def _chain(hf, oracle, sc, face_normals):
         t_, u_, v_, prim_ = sc.field.ray_intersect_preliminary(sc.rays)
         route_sh = sc.field.adjoint(sc.rays, t_, u_, v_, prim_, {"sh_n": gn}, oracle.RAY_ALL).astype(np.float64)
     else:                                                                 # the smooth normal's adjoint (tests/test_gpu_smooth_shading.py)
-        ybar = torch.zeros((18, sc.n), device="cuda"); ybar[9:12] = _cuda(gn)
+        ybar = torch.zeros((18, sc.n), device="cuda"); ybar[9:12] = _cu(gn)
         pi = shape.ray_intersect_preliminary(sc.ray)
         route_sh = _np(shape.adjoint(sc.ray, pi, ybar, ray_flags=int(hf.RayFlags.All))).astype(np.float64)
     return got, route_sh, route_nq
@@ -387,15 +375,15 @@ def test_bounce_height_tangent(hf, scene):
     sc = scene
     spp = 4
     shape = hf.Heightfield(heightfield=sc.ht.clone(), max_height=sc.max_height, to_world=sc.tw64, flip_normals=sc.flip)
-    si, ray = _sub(hf, sc, 0, sc.n)
-    gi = _cuda(np.random.default_rng(5).normal(size=(sc.L, sc.n // spp)).astype(np.float32))
+    si, ray = sub(hf, sc, 0, sc.n)
+    gi = _cu(np.random.default_rng(5).normal(size=(sc.L, sc.n // spp)).astype(np.float32))
     dh = np.random.default_rng(6).normal(size=(sc.H, sc.W)).astype(np.float32)
     shape.heightfield.requires_grad_(True)
     img = hf.bounce_lighting(shape, si, ray, sc.lt, spp=spp, num_rays=K, seed=SEED)
     (img * gi).sum().backward()
-    rhs = float((shape.heightfield.grad.double() * _cuda(dh).double()).sum())
+    rhs = float((shape.heightfield.grad.double() * _cu(dh).double()).sum())
     with fwAD.dual_level():
-        shape.heightfield = fwAD.make_dual(shape.heightfield.detach(), _cuda(dh))
+        shape.heightfield = fwAD.make_dual(shape.heightfield.detach(), _cu(dh))
         tan = fwAD.unpack_dual(hf.bounce_lighting(shape, si, ray, sc.lt, spp=spp, num_rays=K, seed=SEED)).tangent
     hit, lt = B.unpack(sc.prim, sc.lit, sc.L)
     dnq = np.stack([B.face_normal_jvp(sc.h64, np.where(hit[k], sc.prim[k], 0), sc.max_height, dh, sc.flip, sc.to_world) for k in range(K)])
@@ -417,7 +405,7 @@ def test_sky_chain_to_the_heights(hf, oracle, name):
     si = shape.ray_intersect(sc.ray, hf.RayFlags.All)
     img, vis = hf.sky_lighting(shape, si, sc.ray, radiance=1.3, albedo=0.8, spp=4, num_rays=K, seed=SEED, return_visibility=True)
     gi = np.random.default_rng(11).normal(size=tuple(img.shape)).astype(np.float32)
-    (img * _cuda(gi)).sum().backward()
+    (img * _cu(gi)).sum().backward()
     got = _np(shape.heightfield.grad).astype(np.float64)
     assert np.array_equal(_np(vis).view(np.uint32), sc.words)
     t, u, v, prim = sc.field.ray_intersect_preliminary(sc.rays)
@@ -436,7 +424,7 @@ def _run_both(hf, sc, lo, hi, ids, gi_b, gi_s, wgt, dn, dw, shape=None):
     shape = shape or sc.shape
     out = {}
     for row in ("bounce", "sky"):
-        si, ray = _sub(hf, sc, lo, hi, requires_grad=True)
+        si, ray = sub(hf, sc, lo, hi, requires_grad=True)
         wt = wgt[lo:hi].clone().requires_grad_(True)
         if row == "bounce":
             call = lambda s, w_: hf.bounce_lighting(shape, s, ray, sc.lt, albedo=0.7, spp=4, num_rays=K, seed=SEED, weight=w_,
@@ -453,7 +441,7 @@ def _run_both(hf, sc, lo, hi, ids, gi_b, gi_s, wgt, dn, dw, shape=None):
         out[row + "_image"] = img.detach().clone()
         out[row + "_grad_sh_n"], out[row + "_grad_weight"] = si.sh_frame.n.grad.clone(), wt.grad.clone()
         with fwAD.dual_level():
-            si2, _ = _sub(hf, sc, lo, hi)
+            si2, _ = sub(hf, sc, lo, hi)
             si2.sh_frame.n = fwAD.make_dual(si2.sh_frame.n, dn[:, lo:hi].contiguous())
             wd = fwAD.make_dual(wgt[lo:hi].clone(), dw[lo:hi].contiguous())
             out[row + "_tangent"] = fwAD.unpack_dual(call(si2, wd)[0]).tangent.clone()
@@ -462,9 +450,9 @@ def _run_both(hf, sc, lo, hi, ids, gi_b, gi_s, wgt, dn, dw, shape=None):
 
 def _inputs(sc, seed):
     rng = np.random.default_rng(seed)
-    return (_cuda(rng.normal(size=(sc.L, sc.n // 4)).astype(np.float32)), _cuda(rng.normal(size=sc.n // 4).astype(np.float32)),
-            _cuda(rng.uniform(0.5, 1.5, sc.n).astype(np.float32)), _cuda(rng.uniform(-0.25, 0.25, (3, sc.n)).astype(np.float32)),
-            _cuda(rng.uniform(-0.5, 0.5, sc.n).astype(np.float32)))
+    return (_cu(rng.normal(size=(sc.L, sc.n // 4)).astype(np.float32)), _cu(rng.normal(size=sc.n // 4).astype(np.float32)),
+            _cu(rng.uniform(0.5, 1.5, sc.n).astype(np.float32)), _cu(rng.uniform(-0.25, 0.25, (3, sc.n)).astype(np.float32)),
+            _cu(rng.uniform(-0.5, 0.5, sc.n).astype(np.float32)))
 
 
 def test_a_wavefront_cut_in_two_is_the_whole_bit_for_bit(hf, scene):
@@ -491,7 +479,7 @@ def test_a_wavefront_cut_in_two_is_the_whole_bit_for_bit(hf, scene):
         shape = hf.Heightfield(heightfield=sc.ht.clone(), max_height=sc.max_height, to_world=sc.tw64, flip_normals=sc.flip)
         shape.heightfield.requires_grad_(True)
         for lo, hi, rid in chunks:
-            si, ray = _sub(hf, sc, lo, hi)
+            si, ray = sub(hf, sc, lo, hi)
             img = hf.bounce_lighting(shape, si, ray, sc.lt, spp=4, num_rays=K, seed=SEED, ray_index=rid)
             (img * gi[:, lo // 4:hi // 4]).sum().backward()
         grads.append(_np(shape.heightfield.grad).astype(np.float64))

@@ -26,7 +26,6 @@ import ctypes as C
 import math
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -35,6 +34,8 @@ import torch.autograd.forward_ad as fwAD
 
 import envmap_ref as E
 import reflect_ref as R
+from row_helpers import (GUARD, UNSURE_CAP, _cu, _fold, _np, _rel, base_scene, envmap, guarded, intact, leaf_si, rows,
+                         transposition_gap)
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -51,25 +52,11 @@ TOL = {k: 4 * v for k, v in F32.items()}
 # a mask is decided by the sign of a float32 quantity (c, <g, wi>, <g, wr>): a lane on which one of them is below this in
 # magnitude is decided by rounding and is left out of mask comparisons
 MARGIN = 1e-5
-UNSURE_CAP = 1e-3      # of the samples (the cap of tests/test_gpu_sky_lighting.py)
 BORDER, LEFT_OUT_CAP = 1e-4, 2e-3
 
 
-def _np(x):
-    return x.detach().cpu().numpy()
-
-
-def _cu(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
 def _envmap(hf, name, rname, requires_grad=False):
-    """(Envmap, the [H, W] map with its seam column as numpy, the rotation)"""
-    full = E.MAPS[name](*MAPS[name])
-    data = _cu(full[:, :-1].astype(np.float32))
-    if requires_grad:
-        data.requires_grad_(True)
-    return hf.Envmap(data, to_world=ROTS[rname]), full, ROTS[rname]
+    return envmap(hf, MAPS, ROTS, name, rname, requires_grad)
 
 
 _SCENES = {}
@@ -80,29 +67,18 @@ def _scene(hf, oracle, oi, face_normals):
     the two-call answer and the restatement's rays: once for all tests"""
     key = (oi, face_normals)
     if key not in _SCENES:
-        h = hf.workload.sine_heights(96, 96, device="cuda")
-        shape = hf.Heightfield(heightfield=h, max_height=0.5, face_normals=face_normals)
-        rays = hf.workload.ortho_rays(64, 64, SPP, "cuda", seed=1, origin=ORIGINS[oi], target=(0.0, 0.0, 0.25), scale=(0.9, 0.9, 1.0))
-        ray = hf.Ray3f(rays[0:3], rays[3:6], rays[6])
-        si = shape.ray_intersect(ray, hf.RayFlags.All)
-        sc = types.SimpleNamespace(h=h, shape=shape, rays=rays, ray=ray, si=si, n=len(ray))
-        sc.p = _np(si.p)
-        sc.a = tuple(_np(x) for x in (si.n, si.sh_frame.n, ray.d, si.t))             # the restatement's first four arguments
-        sc.hit = np.isfinite(sc.a[3])
-        sc.field = oracle.OracleField(_np(h), max_height=0.5)
-        sc.rr = hf.reflection_rays(si, ray)
-        sc.occluded = shape.ray_test(sc.rr)
+        sc = base_scene(hf, oracle, (64, 64, SPP), ORIGINS[oi], face_normals)
+        sc.p = sc.np["p"]
+        sc.a = tuple(sc.np[k] for k in ("n", "sh_n", "d", "t"))                      # the restatement's first four arguments
+        sc.rr = hf.reflection_rays(sc.si, sc.ray)
+        sc.occluded = sc.shape.ray_test(sc.rr)
         env, _, _ = _envmap(hf, "gradient", "identity")
-        _, sc.vis = hf.reflection_lighting(shape, si, ray, env, spp=SPP, return_visibility=True)
+        _, sc.vis = hf.reflection_lighting(sc.shape, sc.si, sc.ray, env, spp=SPP, return_visibility=True)
         sc.visn = _np(sc.vis).astype(bool)
         sc.traced, sc.o, sc.wr, sc.maxt, sc.v = R.rays(sc.p, *sc.a)
         sc.sure = (sc.v.margin > MARGIN) | ~sc.hit
         _SCENES[key] = sc
     return _SCENES[key]
-
-
-def _rel(got, ref):
-    return float(np.linalg.norm(np.asarray(got, np.float64) - ref) / np.linalg.norm(ref))
 
 
 @pytest.mark.parametrize("face_normals", [True, False])
@@ -178,20 +154,6 @@ def _inputs(n, shape):
     return w, gi, gv, dn, dw, dd
 
 
-def _leaf_si(hf, sc, sh_n=None):
-    si = hf.SurfaceInteraction3f()
-    si.p, si.n, si.t = sc.si.p.detach(), sc.si.n.detach(), sc.si.t.detach()
-    si.sh_frame = hf.Frame3f(None, None, sc.si.sh_frame.n.detach().clone().requires_grad_(True) if sh_n is None else sh_n)
-    return si
-
-
-def _fold(gd):
-    """the gradient of the [H, W] map folded onto the [H, W - 1] texels: the seam column is a copy of column 0"""
-    out = gd[:, :-1].copy()
-    out[:, 0] += gd[:, -1]
-    return out
-
-
 @pytest.mark.parametrize("face_normals", [True, False])
 @pytest.mark.parametrize("eta", ETAS)
 def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, face_normals):
@@ -208,7 +170,7 @@ def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, fac
                 assert left_out <= LEFT_OUT_CAP, left_out
                 dn = dn * keep
                 args = (*sc.a, None, w, eta, full, rot, sc.visn, SPP)
-                si = _leaf_si(hf, sc)
+                si = leaf_si(hf, sc)
                 wt = _cu(w).requires_grad_(True)
                 img, val, vis = hf.reflection_lighting(sc.shape, si, sc.ray, env, eta=eta, spp=SPP, weight=wt, return_value=True,
                                                        return_visibility=True)
@@ -225,7 +187,7 @@ def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, fac
                 err["grad_weight"] = _rel(got["grad_weight"][keep], gw[keep])
                 err["grad_data"] = _rel(got["grad_data"], _fold(gd))
                 with fwAD.dual_level():
-                    sd = _leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), _cu(dn.astype(np.float32))))
+                    sd = leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), _cu(dn.astype(np.float32))))
                     envd = hf.Envmap(fwAD.make_dual(env.data.detach(), _cu(dd[:, :-1])), to_world=rot)
                     # (the seam column's tangent is column 0's, as Envmap.full() copies it)
                     ti, tv = hf.reflection_lighting(sc.shape, sd, sc.ray, envd, eta=eta, spp=SPP, weight=fwAD.make_dual(_cu(w), _cu(dw)),
@@ -236,15 +198,13 @@ def test_values_adjoint_and_tangent_against_the_restatement(hf, oracle, eta, fac
                 assert not _np(tval)[~sc.visn].any()
                 err["dimage"], err["dvalue"] = _rel(_np(timg), dimg), _rel(_np(tval)[keep], dval[keep])
                 # transposition on the device: <J u, v> = <u, J^T v>, both sides float32 results added up in float64; each
-                # side is within its tolerance of the exact bilinear form, so they agree to the sum of the two (the
-                # bound of test (e) of tests/test_gpu_caustic.py, with this row's names)
-                lhs = (_np(timg).astype(np.float64) * gi).sum() + (_np(tval).astype(np.float64) * gv).sum()
-                rhs = (got["grad_sh_n"].astype(np.float64) * dn).sum() + (got["grad_weight"].astype(np.float64) * dw).sum() + \
-                    (got["grad_data"].astype(np.float64) * dd[:, :-1]).sum()
+                # side is within its tolerance of the exact bilinear form, so they agree to the sum of the two
+                gap = transposition_gap(((_np(timg), gi), (_np(tval), gv)),
+                                        ((got["grad_sh_n"], dn), (got["grad_weight"], dw), (got["grad_data"], dd[:, :-1])))
                 size = np.linalg.norm(dimg) * np.linalg.norm(gi) + np.linalg.norm(dval) * np.linalg.norm(gv)
                 print(ORIGINS[oi], name, rname, {k: "%.3g" % v for k, v in err.items()}, "left out", left_out, "transposition",
-                      abs(lhs - rhs) / size)
-                assert abs(lhs - rhs) <= (TOL["dvalue"] + TOL["grad_sh_n"]) * size, (lhs, rhs)
+                      gap / size)
+                assert gap <= (TOL["dvalue"] + TOL["grad_sh_n"]) * size, gap
                 for k in err:
                     worst[k] = max(worst[k], err[k])
     print("worst", {k: "%.3g / %.3g" % (worst[k], TOL[k]) for k in TOL})
@@ -291,7 +251,7 @@ def test_repeatable_and_edge_cases(hf, oracle):
     w, gi, gv, dn, dw, dd = (_cu(x) for x in _inputs(sc.n, full.shape))
     runs = []
     for _ in range(2):
-        si = _leaf_si(hf, sc)
+        si = leaf_si(hf, sc)
         wt = w.clone().requires_grad_(True)
         img, val, vis = hf.reflection_lighting(sc.shape, si, sc.ray, env, eta=1.5, spp=SPP, weight=wt, return_value=True,
                                                return_visibility=True)
@@ -338,23 +298,14 @@ def test_odd_sizes_guard_bands_and_optional_outputs(hf, oracle, spp):
     start = int(torch.nonzero(sc.vis)[0]) // 64 * 64
     cut = lambda x: x.detach()[..., start:start + n].contiguous()
     p, nr, sn, d, t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.sh_frame.n), cut(sc.ray.d), cut(sc.si.t)
-    rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(3)])
-    GUARD = -12345.0
-
-    def guarded(m, k=1):
-        buf = torch.full((k, m + 2 * G), GUARD, device="cuda")
-        return buf, (hf._capi._fp * k)(*[buf.data_ptr() + 4 * (j * (m + 2 * G) + G) for j in range(k)])
-
-    def intact(buf, m):
-        return bool((buf[:, :G] == GUARD).all()) and bool((buf[:, G + m:] == GUARD).all()) and bool((buf[:, G:G + m] != GUARD).all())
     stream = torch.cuda.current_stream().cuda_stream
     mid = (None, None, eta, W, H, dat.data_ptr(), C.byref(rotc))
     fwd = lambda image, value, vis: hf._capi.check(lib.hf_reflect_lighting(sc.shape._h, n, spp, rows(p), rows(nr), rows(sn), rows(d),
                                                                            t.data_ptr(), *mid, image, value, vis, stream))
-    img, ip = guarded(npix); val, vp = guarded(n)
+    img, ip = guarded(npix, G); val, vp = guarded(n, G)
     vis = torch.full((n + 2 * G,), 0x5A, dtype=torch.uint8, device="cuda")
     fwd(ip[0], vp[0], vis.data_ptr() + G)
-    assert intact(img, npix) and intact(val, n)
+    assert intact(img, npix, G) and intact(val, n, G)
     assert bool((vis[:G] == 0x5A).all()) and bool((vis[G + n:] == 0x5A).all())
     assert torch.equal(vis[G:G + n], sc.vis[start:start + n]) and torch.equal(val[0, G:G + n], whole_val[start:start + n])
     assert 0 < int(vis[G:G + n].sum()) < n
@@ -363,11 +314,11 @@ def test_odd_sizes_guard_bands_and_optional_outputs(hf, oracle, spp):
     # (the film: one product and at most three additions per pixel, each rounded to 2^-24 of the largest value: 2.5e-7)
     # every optional output NULL in turn: the others are unchanged
     for skip in range(3):
-        img2, ip2 = guarded(npix); val2, vp2 = guarded(n)
+        img2, ip2 = guarded(npix, G); val2, vp2 = guarded(n, G)
         vis2 = torch.full((n + 2 * G,), 0x5A, dtype=torch.uint8, device="cuda")
         fwd(None if skip == 0 else ip2[0], None if skip == 1 else vp2[0], None if skip == 2 else vis2.data_ptr() + G)
         if skip != 0:
-            assert intact(img2, npix) and float((img2 - img).abs().max()) <= 2.5e-7 * float(want.abs().max())
+            assert intact(img2, npix, G) and float((img2 - img).abs().max()) <= 2.5e-7 * float(want.abs().max())
         else:
             assert bool((img2 == GUARD).all())
         assert torch.equal(val2, val) if skip != 1 else bool((val2 == GUARD).all())
@@ -375,35 +326,35 @@ def test_odd_sizes_guard_bands_and_optional_outputs(hf, oracle, spp):
     bytes_ = vis[G:G + n].contiguous()
     ones, onesp = torch.ones((3, n), device="cuda"), torch.ones(npix, device="cuda")
     head = (n, spp, rows(sn), rows(d), t.data_ptr(), *mid, bytes_.data_ptr())
-    gn, gnp = guarded(n, 3); gw, gwp = guarded(n)
+    gn, gnp = guarded(n, G, 3); gw, gwp = guarded(n, G)
     gd = torch.full((H * W + 2 * G,), 0.0, device="cuda"); gd[:G] = GUARD; gd[G + H * W:] = GUARD
     hf._capi.check(lib.hf_reflect_lighting_adjoint(*head, onesp.data_ptr(), ones.data_ptr(), gnp, gwp[0], gd.data_ptr() + 4 * G, stream))
-    assert intact(gn, n) and intact(gw, n) and bool((gd[:G] == GUARD).all()) and bool((gd[G + H * W:] == GUARD).all())
+    assert intact(gn, n, G) and intact(gw, n, G) and bool((gd[:G] == GUARD).all()) and bool((gd[G + H * W:] == GUARD).all())
     assert float(gd[G:G + H * W].abs().sum()) > 0
     # each adjoint output NULL in turn, and each upstream NULL
-    gn2, gnp2 = guarded(n, 3); gw2, gwp2 = guarded(n)
+    gn2, gnp2 = guarded(n, G, 3); gw2, gwp2 = guarded(n, G)
     hf._capi.check(lib.hf_reflect_lighting_adjoint(*head, onesp.data_ptr(), ones.data_ptr(), None, gwp2[0], None, stream))
     hf._capi.check(lib.hf_reflect_lighting_adjoint(*head, onesp.data_ptr(), ones.data_ptr(), gnp2, None, None, stream))
     assert torch.equal(gn2, gn) and torch.equal(gw2, gw)
-    ga, gap = guarded(n, 3); gb, gbp = guarded(n, 3)
+    ga, gap = guarded(n, G, 3); gb, gbp = guarded(n, G, 3)
     hf._capi.check(lib.hf_reflect_lighting_adjoint(*head, onesp.data_ptr(), None, gap, None, None, stream))
     hf._capi.check(lib.hf_reflect_lighting_adjoint(*head, None, ones.data_ptr(), gbp, None, None, stream))
     scale = float(gn[:, G:G + n].abs().max())
     assert float((ga + gb - gn)[:, G:G + n].abs().max()) <= 1e-6 * scale
-    dimg, dip = guarded(npix); dval, dvp = guarded(n)
+    dimg, dip = guarded(npix, G); dval, dvp = guarded(n, G)
     ddat = torch.ones((H, W), device="cuda")
     tail = (rows(ones), ones.data_ptr(), ddat.data_ptr())
     hf._capi.check(lib.hf_reflect_lighting_tangent(*head, *tail, dip[0], dvp[0], stream))
-    assert intact(dimg, npix) and intact(dval, n)
+    assert intact(dimg, npix, G) and intact(dval, n, G)
     wantd = dval[0, G:G + n].reshape(npix, spp).double().mean(1)
     assert float((dimg[0, G:G + npix] - wantd).abs().max()) <= 2.5e-7 * float(dval[0, G:G + n].abs().max())
-    dimg2, dip2 = guarded(npix); dval2, dvp2 = guarded(n)
+    dimg2, dip2 = guarded(npix, G); dval2, dvp2 = guarded(n, G)
     hf._capi.check(lib.hf_reflect_lighting_tangent(*head, *tail, dip2[0], None, stream))
     hf._capi.check(lib.hf_reflect_lighting_tangent(*head, *tail, None, dvp2[0], stream))
     assert torch.equal(dimg2, dimg) and torch.equal(dval2, dval)
-    ro, rop = guarded(n, 3); rd, rdp = guarded(n, 3); rm, rmp = guarded(n)
+    ro, rop = guarded(n, G, 3); rd, rdp = guarded(n, G, 3); rm, rmp = guarded(n, G)
     hf._capi.check(lib.hf_reflect_rays(n, rows(p), rows(nr), rows(sn), rows(d), t.data_ptr(), None, rop, rdp, rmp[0], stream))
-    assert intact(ro, n) and intact(rd, n) and intact(rm, n)
+    assert intact(ro, n, G) and intact(rd, n, G) and intact(rm, n, G)
     assert torch.equal(rm[0, G:G + n], sc.rr.maxt[start:start + n])
     torch.cuda.synchronize()
 
@@ -415,7 +366,6 @@ def test_captured_graph_replays_to_the_same_bits(hf, oracle):
     dat = _cu(full.astype(np.float32))
     H, W = full.shape
     p, nr, sn, d, t = (x.detach().contiguous() for x in (sc.si.p, sc.si.n, sc.si.sh_frame.n, sc.ray.d, sc.si.t))
-    rows = lambda x: (hf._capi._fp * x.shape[0])(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(x.shape[0])])
     img = torch.zeros(sc.n // SPP, device="cuda"); value = torch.zeros(sc.n, device="cuda")
     vis = torch.zeros(sc.n, dtype=torch.uint8, device="cuda")
     gn = torch.zeros((3, sc.n), device="cuda"); timg = torch.zeros(sc.n // SPP, device="cuda")
@@ -455,13 +405,13 @@ def test_forward_and_reverse_mode_agree(hf, oracle):
     sc = _scene(hf, oracle, 0, False)
     env, full, rot = _envmap(hf, "sun", "identity", requires_grad=True)
     w, gi, gv, dn, dw, dd = (_cu(x) for x in _inputs(sc.n, full.shape))
-    si = _leaf_si(hf, sc)
+    si = leaf_si(hf, sc)
     wt = w.clone().requires_grad_(True)
     img, val = hf.reflection_lighting(sc.shape, si, sc.ray, env, eta=1.5, spp=SPP, weight=wt, return_value=True)
     ((img * gi).sum() + (val * gv).sum()).backward()
     rhs = sum(float((g.double() * t.double()).sum()) for g, t in ((si.sh_frame.n.grad, dn), (wt.grad, dw), (env.data.grad, dd[:, :-1])))
     with fwAD.dual_level():
-        sd = _leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), dn))
+        sd = leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), dn))
         envd = hf.Envmap(fwAD.make_dual(env.data.detach(), dd[:, :-1].contiguous()), to_world=rot)
         ti, tv = hf.reflection_lighting(sc.shape, sd, sc.ray, envd, eta=1.5, spp=SPP, weight=fwAD.make_dual(w, dw), return_value=True)
         timg, tval = fwAD.unpack_dual(ti).tangent, fwAD.unpack_dual(tv).tangent

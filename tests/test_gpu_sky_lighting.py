@@ -8,11 +8,9 @@ wavefront, K = 8 (131 072 shadow rays).
   (e) the chain image -> backward -> dL/dheight against the oracle's chain;
   (f) repeatability, empty and all-miss wavefronts, nothing written beside the rows;
   (g) the inverse loop with a sky term descends."""
-import ctypes as C
 import math
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -20,6 +18,7 @@ import torch
 import torch.autograd.forward_ad as fwAD
 
 import sky_ref as S
+from row_helpers import base_scene, guarded, intact, rows, sub
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
@@ -31,33 +30,17 @@ MARGIN = 4e-6
 
 @pytest.fixture(scope="module")
 def scene(hf, oracle):
-    h = hf.workload.sine_heights(96, 96, device="cuda")
-    shape = hf.Heightfield(heightfield=h, max_height=0.5)
-    rays = hf.workload.ortho_rays(64, 64, 4, "cuda", seed=1, origin=(0.6, 0.35, 2.0), target=(0.0, 0.0, 0.25), scale=(0.9, 0.9, 1.0))
-    ray = hf.Ray3f(rays[0:3], rays[3:6], rays[6])
-    si = shape.ray_intersect(ray, hf.RayFlags.All)
-    n = len(ray)
-    sc = types.SimpleNamespace(h=h, shape=shape, rays=rays, ray=ray, si=si, n=n)
-    sc.np = {k: v.detach().cpu().numpy() for k, v in (("p", si.p), ("n", si.n), ("sh_n", si.sh_frame.n), ("d", ray.d), ("t", si.t))}
+    sc = base_scene(hf, oracle, (64, 64, 4), (0.6, 0.35, 2.0))
+    shape, ray, si, n = sc.shape, sc.ray, sc.si, sc.n
     sc.w = S.directions(np.arange(n), 32, SEED)                          # [32, 3, n]: every num_rays is a prefix
     sc.eligible, _ = S.eligible(sc.np["sh_n"], sc.np["d"], sc.np["t"])
     sc.traced, sc.margin = S.traced(sc.np["sh_n"], sc.np["d"], sc.np["t"], sc.w)
     # the two-call sequence: materialised rays and their any-hit answers, once for all tests
     sc.sky_rays = [hf.sky_rays(si, ray, k, seed=SEED) for k in range(K)]
-    sc.hit = [shape.ray_test(r) for r in sc.sky_rays]
+    sc.occluded = [shape.ray_test(r) for r in sc.sky_rays]
     _, vis = hf.sky_lighting(shape, si, ray, spp=4, num_rays=K, seed=SEED, return_visibility=True)
     sc.words = vis.cpu().numpy().view(np.uint32)
-    sc.field = oracle.OracleField(h.cpu().numpy(), max_height=0.5)
     return sc
-
-
-def _sub(hf, sc, m, requires_grad=False):
-    """(si, ray) of the first m samples as records of their own"""
-    si = hf.SurfaceInteraction3f()
-    cut = lambda x: x.detach()[..., :m].contiguous()
-    si.p, si.n, si.t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.t)
-    si.sh_frame = hf.Frame3f(None, None, cut(sc.si.sh_frame.n).requires_grad_(requires_grad))
-    return si, hf.Ray3f(cut(sc.ray.o), cut(sc.ray.d))
 
 
 def test_materialised_rays_against_the_restatement(hf, scene):
@@ -91,7 +74,7 @@ def test_fused_equals_the_two_call_sequence_bitwise(hf, scene):
     bits = S.unpack(sc.words, 32)
     assert not bits[K:].any()                                          # no bit beyond num_rays
     for k in range(K):
-        two = (sc.sky_rays[k].maxt >= 0) & ~sc.hit[k]
+        two = (sc.sky_rays[k].maxt >= 0) & ~sc.occluded[k]
         assert np.array_equal(bits[k], two.cpu().numpy()), (k, int((bits[k] != two.cpu().numpy()).sum()))
     # a permuted ray_id against the same sequence
     ids = torch.randperm(sc.n, generator=torch.Generator().manual_seed(6)).to(device="cuda", dtype=torch.int32)
@@ -133,7 +116,7 @@ def test_image_adjoint_and_tangent_against_the_restatement(hf, scene, spp, with_
     albedo, wmax = 0.7, 1.5
     L = 1.0 / (4.0 * albedo * wmax)
     rng = np.random.default_rng(100 * spp + num_rays)
-    si, ray = _sub(hf, sc, m, requires_grad=True)
+    si, ray = sub(hf, sc, 0, m, requires_grad=True)
     wgt = rng.uniform(0.5, wmax, m).astype(np.float32) if with_weight else None
     wt = torch.from_numpy(wgt).cuda().requires_grad_(True) if with_weight else None
     img, vis = hf.sky_lighting(sc.shape, si, ray, radiance=L, albedo=albedo, spp=spp, num_rays=num_rays, seed=SEED,
@@ -212,18 +195,18 @@ def test_repeatable_and_edge_cases(hf, scene):
     dn = torch.from_numpy(np.random.default_rng(2).normal(size=(3, m)).astype(np.float32)).cuda()
     runs = []
     for _ in range(2):
-        si, ray = _sub(hf, sc, m, requires_grad=True)
+        si, ray = sub(hf, sc, 0, m, requires_grad=True)
         img, vis = hf.sky_lighting(sc.shape, si, ray, spp=4, num_rays=K, seed=SEED, return_visibility=True)
         (img * gi).sum().backward()
         with fwAD.dual_level():
-            si2, _ = _sub(hf, sc, m)
+            si2, _ = sub(hf, sc, 0, m)
             si2.sh_frame.n = fwAD.make_dual(si2.sh_frame.n, dn)
             tan = fwAD.unpack_dual(hf.sky_lighting(sc.shape, si2, ray, spp=4, num_rays=K, seed=SEED)).tangent
         runs.append((vis.clone(), si.sh_frame.n.grad.clone(), tan.clone(), img.detach().clone()))
     for a, b in zip(*runs):
         assert torch.equal(a, b)
     # n = 0 is legal
-    si0, ray0 = _sub(hf, sc, 0, requires_grad=True)
+    si0, ray0 = sub(hf, sc, 0, 0, requires_grad=True)
     img0, vis0 = hf.sky_lighting(sc.shape, si0, ray0, spp=4, num_rays=K, return_visibility=True)
     assert img0.shape == (0,) and vis0.shape == (0,)
     img0.sum().backward()
@@ -258,42 +241,33 @@ def test_nothing_is_written_beside_the_rows(hf, scene):
     cut = lambda x: x.detach()[..., start:start + n].contiguous()
     p, nr, sn, d, t = cut(sc.si.p), cut(sc.si.n), cut(sc.si.sh_frame.n), cut(sc.ray.d), cut(sc.si.t)
     assert bool(torch.isfinite(t).any())
-    rows = lambda x: (hf._capi._fp * 3)(*[x.data_ptr() + 4 * (k * x.shape[1]) for k in range(3)])
-    GUARD = -12345.0
-
-    def guarded(k=1):
-        buf = torch.full((k, n + 2 * G), GUARD, device="cuda")
-        return buf, (hf._capi._fp * 3)(*[buf.data_ptr() + 4 * (j * (n + 2 * G) + G) for j in range(k)] + [None] * (3 - k))
-
-    def intact(buf):
-        return bool((buf[:, :G] == GUARD).all()) and bool((buf[:, G + n:] == GUARD).all()) and bool((buf[:, G:G + n] != GUARD).all())
-    image, ip = guarded()
+    image, ip = guarded(n, G)
     vis = torch.full((n + 2 * G,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     hf._capi.check(lib.hf_sky_lighting(sc.shape._h, n, 1, rows(p), rows(nr), rows(sn), rows(d), t.data_ptr(), None, K, SEED, None,
                                        1.0, 1.0, ip[0], vis.data_ptr() + 4 * G, stream))
-    assert intact(image)
+    assert intact(image, n, G)
     assert bool((vis[:G] == 0x5A5A5A5A).all()) and bool((vis[G + n:] == 0x5A5A5A5A).all())
     ids = torch.arange(start, start + n, dtype=torch.int32, device="cuda")
-    _, whole = hf.sky_lighting(sc.shape, *_sub(hf, sc, sc.n), spp=1, num_rays=K, seed=SEED, return_visibility=True)
+    _, whole = hf.sky_lighting(sc.shape, *sub(hf, sc, 0, sc.n), spp=1, num_rays=K, seed=SEED, return_visibility=True)
     hf._capi.check(lib.hf_sky_lighting(sc.shape._h, n, 1, rows(p), rows(nr), rows(sn), rows(d), t.data_ptr(), None, K, SEED,
                                        ids.data_ptr(), 1.0, 1.0, ip[0], vis.data_ptr() + 4 * G, stream))
     assert torch.equal(vis[G:G + n], whole[start:start + n])             # the slice, with its ids, is the slice of the whole
     words = vis[G:G + n].contiguous()
     gi = torch.ones(n, device="cuda")
-    gn, gp = guarded(3)
-    gw, gwp = guarded()
+    gn, gp = guarded(n, G, 3)
+    gw, gwp = guarded(n, G)
     hf._capi.check(lib.hf_sky_lighting_adjoint(n, 1, rows(sn), rows(d), t.data_ptr(), None, K, SEED, ids.data_ptr(), 1.0, 1.0,
                                                words.data_ptr(), gi.data_ptr(), gp, gwp[0], stream))
-    assert intact(gn) and intact(gw)
-    dimg, dp = guarded()
+    assert intact(gn, n, G) and intact(gw, n, G)
+    dimg, dp = guarded(n, G)
     hf._capi.check(lib.hf_sky_lighting_tangent(n, 1, rows(sn), rows(d), t.data_ptr(), None, K, SEED, ids.data_ptr(), 1.0, 1.0,
                                                words.data_ptr(), rows(sn), None, dp[0], stream))
-    assert intact(dimg)
-    ro, rop = guarded(3); rd, rdp = guarded(3); rm, rmp = guarded()
+    assert intact(dimg, n, G)
+    ro, rop = guarded(n, G, 3); rd, rdp = guarded(n, G, 3); rm, rmp = guarded(n, G)
     hf._capi.check(lib.hf_sky_rays(n, rows(p), rows(nr), rows(sn), rows(d), t.data_ptr(), 0, SEED, ids.data_ptr(), rop, rdp,
                                    rmp[0], stream))
-    assert intact(ro) and intact(rd) and intact(rm)
+    assert intact(ro, n, G) and intact(rd, n, G) and intact(rm, n, G)
     torch.cuda.synchronize()
 
 

@@ -1,28 +1,16 @@
 """Large-steps preconditioning (hf_large_steps_*) on the CPU: the entry points are declared, exported and bound; every bad
 argument is refused with HF_EINVAL before anything touches a device (host addresses stand in for device pointers, so a
 call that got as far as a launch would not return HF_EINVAL); HF_VERSION is unchanged."""
-import ctypes as C
-import os
-import re
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_helpers import assert_refused, assert_symbols, stand_ins
+
 FNS = ("hf_large_steps_workspace_floats", "hf_large_steps_apply", "hf_large_steps_solve")
 NAN, INF = float("nan"), float("inf")
 
 
 def test_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for fn in FNS:
-        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
-        assert hasattr(lib, fn)
-        assert fn in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
-    assert callable(hf_amd.LargeSteps)
+    assert_symbols(FNS, ("LargeSteps",))
 
 
 def test_workspace_size():
@@ -40,9 +28,7 @@ def test_workspace_size():
 
 
 def _call(lib, fn, W=17, H=9, lam=19.0, warm=0, max_iter=8, tol=1e-6, null=(), alias=False, misalign=False):
-    keep = (C.c_float * 16384)()
-    a = C.addressof(keep)
-    arg = lambda name, off=0: None if name in null else a + off
+    _, arg = stand_ins(null)
     if fn == "hf_large_steps_apply":
         return lib.hf_large_steps_apply(W, H, lam, arg("v"), arg("v") if alias else arg("u", 4096), None)
     return lib.hf_large_steps_solve(W, H, lam, arg("u"), arg("u") if alias else arg("v", 4096), warm, max_iter, tol,
@@ -60,11 +46,7 @@ CASES = {
 
 @pytest.mark.parametrize("fn", sorted(CASES))
 def test_bad_arguments_are_refused(fn):
-    from hf_amd import _capi
-    lib = _capi.lib()
-    for kw in CASES[fn]:
-        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith(fn + ":"), (kw, lib.hf_last_error_string())
+    assert_refused(_call, fn, CASES[fn])
 
 
 def test_python_argument_checks():

@@ -3,13 +3,13 @@ the float64 restatement (tests/param_ref.py) reproduces the reference's known an
 test09, src/shapes/tests/test_rectangle.py test09), its closed-form lookup agrees with Mesh's way -- a float64
 Moeller-Trumbore over the texcoord mesh -- on random points and on every exact border, diagonal and corner, and its
 derivatives agree with central differences; the adapter overrides the method."""
-import ctypes as C
 import os
 import re
 
 import numpy as np
 import torch
 
+from abi_helpers import assert_symbols
 import common
 import param_ref as R
 from si_numpy import RAY_ALL, RAY_DPDUV, RAY_SHADINGFRAME, RAY_UV
@@ -19,15 +19,7 @@ NEW = ("hf_eval_parameterization", "hf_eval_parameterization_adjoint", "hf_eval_
 
 
 def test_new_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", hdr), f"{name} not declared in include/hf.h"
-        assert hasattr(lib, name), f"{name} not exported by libhf.so"
-        assert name in _capi.SYMBOLS, f"{name} missing from the binding table"
-    assert _capi.lib().hf_version() == 4
+    assert_symbols(NEW)
     import hf_amd.shape as sh
     assert callable(getattr(sh.Heightfield, "eval_parameterization", None))
 

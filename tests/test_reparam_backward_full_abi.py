@@ -3,31 +3,21 @@ CPU: the entry point is declared, exported and bound; every bad argument is refu
 the float64 restatement (tests/reparam_backward_ref.py) is the transpose of tests/reparam_tangent_ref.py for every kind
 of tangent, and its heights / ray.o / ray.d parts agree with oracle.reparam_backward."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+from abi_helpers import assert_refused, assert_symbols
 import common
 import reparam_backward_ref as B
 import reparam_tangent_ref as R
 from test_reparam_tangent_abi import _setup
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FN = "hf_reparam_backward_full"
 
 
 def test_symbol_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    assert re.search(rf"\b{FN}\s*\(", hdr), f"{FN} not declared in include/hf.h"
-    assert hasattr(lib, FN)
-    assert FN in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbol
-    assert callable(hf_amd.reparameterize_ray_adjoint)
+    assert_symbols((FN,), ("reparameterize_ray_adjoint",))
 
 
 def _call(lib, hf, n=4, num_rays=4, kappa=1e5, stride=None, null=(), outs=("h", "o", "d", "M")):
@@ -46,17 +36,13 @@ def _call(lib, hf, n=4, num_rays=4, kappa=1e5, stride=None, null=(), outs=("h", 
 
 
 def test_bad_arguments_are_refused():
-    from hf_amd import _capi
-    lib = _capi.lib()
     fake = C.create_string_buffer(4096)   # never dereferenced: every case fails before the handle's device is read
     h = C.cast(fake, C.c_void_p)
-    cases = [(None, {})]
-    cases += [(h, {"null": (name,)}) for name in ("o", "d", "pi", "bt", "g_dir", "g_div")]
-    cases += [(h, {"outs": ()}), (h, {"kappa": 0.0}), (h, {"kappa": -1.0}), (h, {"kappa": float("nan")}),
-              (h, {"num_rays": 0}), (h, {"num_rays": 33}), (h, {"stride": 3}), (h, {"n": 1 << 32})]
-    for hf, kw in cases:
-        assert _call(lib, hf, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith(FN + ":"), (kw, lib.hf_last_error_string())
+    cases = [{"hf": None}]                                                 # (every case but this one has the handle h)
+    cases += [{"null": (name,)} for name in ("o", "d", "pi", "bt", "g_dir", "g_div")]
+    cases += [{"outs": ()}, {"kappa": 0.0}, {"kappa": -1.0}, {"kappa": float("nan")}, {"num_rays": 0}, {"num_rays": 33},
+              {"stride": 3}, {"n": 1 << 32}]
+    assert_refused(lambda lib, fn, hf=h, **kw: _call(lib, hf, **kw), FN, cases)
 
 
 # ---- the float64 restatement ---------------------------------------------------------------------------------------

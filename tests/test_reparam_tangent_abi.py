@@ -4,28 +4,17 @@ NULL handles, bad num_rays and bad kappa are refused before anything touches a d
 V_direct_k> for tangents of the heights, the ray and to_world, reduces to oracle.reparam_forward for heights, and
 reproduces the known answers of the reference's test01 (src/render/tests/test_reparameterization.py:29-98)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+from abi_helpers import assert_refused, assert_symbols
 import common
 import reparam_tangent_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def test_symbol_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    assert re.search(r"\bhf_reparam_tangent\s*\(", hdr), "hf_reparam_tangent not declared in include/hf.h"
-    assert hasattr(lib, "hf_reparam_tangent")
-    assert "hf_reparam_tangent" in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4
-    assert callable(hf_amd.reparameterize_ray_tangent)
+    assert_symbols(("hf_reparam_tangent",), ("reparameterize_ray_tangent",))
     from hf_amd import shape as sh
     import torch
     assert sh._ReparameterizeOp.jvp is not torch.autograd.Function.jvp
@@ -44,15 +33,11 @@ def _call(lib, hf, n=4, num_rays=4, kappa=1e5, pi=True, out=True):
 
 
 def test_bad_arguments_are_refused():
-    from hf_amd import _capi
-    lib = _capi.lib()
     fake = C.create_string_buffer(4096)   # never dereferenced: every case fails before the handle's device is read
     h = C.cast(fake, C.c_void_p)
-    cases = [(None, {}), (h, {"num_rays": 0}), (h, {"num_rays": 33}), (h, {"kappa": 0.0}), (h, {"kappa": float("nan")}),
-             (h, {"kappa": -1.0}), (h, {"pi": False}), (h, {"out": False}), (h, {"n": 1 << 32})]
-    for hf, kw in cases:
-        assert _call(lib, hf, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith("hf_reparam_tangent:"), lib.hf_last_error_string()
+    cases = [{"hf": None}, {"num_rays": 0}, {"num_rays": 33}, {"kappa": 0.0}, {"kappa": float("nan")}, {"kappa": -1.0},
+             {"pi": False}, {"out": False}, {"n": 1 << 32}]                # (every case but the first has the handle h)
+    assert_refused(lambda lib, fn, hf=h, **kw: _call(lib, hf, **kw), "hf_reparam_tangent", cases)
 
 
 # ---- the float64 restatement ---------------------------------------------------------------------------------------

@@ -2,30 +2,17 @@
 exported and bound; every bad argument is refused before anything touches a device; the float64 restatement
 (tests/sky_ref.py) draws unit directions that average to zero, lights an unoccluded plane with albedo * L, its adjoint
 agrees with central differences of its own forward and its tangent is the transpose of its adjoint."""
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
 import sky_ref as S
+from abi_helpers import assert_refused, assert_symbols, stand_ins
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FNS = ("hf_sky_rays", "hf_sky_lighting", "hf_sky_lighting_adjoint", "hf_sky_lighting_tangent")
 
 
 def test_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for fn in FNS:
-        assert re.search(rf"\b{fn}\s*\(", hdr), f"{fn} not declared in include/hf.h"
-        assert hasattr(lib, fn)
-        assert fn in _capi.SYMBOLS
-    assert _capi.lib().hf_version() == 4          # the feature is detected by its symbols
-    assert callable(hf_amd.sky_lighting) and callable(hf_amd.sky_rays)
+    assert_symbols(FNS, ("sky_lighting", "sky_rays"))
 
 
 # ---- argument checks: host addresses stand in for device pointers, every case fails before a launch ------------------
@@ -33,18 +20,7 @@ ROWS = ("p", "nrm", "sh_n", "d", "out_o", "out_d", "grad_sh_n", "dsh_n")
 
 
 def _call(lib, fn, n=8, spp=2, num_rays=8, k=3, radiance=1.0, albedo=0.5, null=(), null_row=None):
-    from hf_amd import _capi
-    keep = (C.c_float * 16384)()            # (also the stand-in for the handle: no case gets as far as reading it)
-    a = C.addressof(keep)
-
-    def rows(name):
-        if name in null:
-            return None
-        r = (_capi._fp * 3)(a, a, a)
-        if null_row == name:
-            r[2] = None
-        return r
-    arg = lambda name: None if name in null else a
+    rows, arg = stand_ins(null, null_row)
     mid = (arg("weight"), num_rays, 7, arg("ray_id"), radiance, albedo)
     if fn == "hf_sky_rays":
         return lib.hf_sky_rays(n, rows("p"), rows("nrm"), rows("sh_n"), rows("d"), arg("t"), k, 7, arg("ray_id"),
@@ -75,11 +51,7 @@ CASES = {
 
 @pytest.mark.parametrize("fn", FNS)
 def test_bad_arguments_are_refused(fn):
-    from hf_amd import _capi
-    lib = _capi.lib()
-    for kw in CASES[fn]:
-        assert _call(lib, fn, **kw) == _capi.HF_EINVAL, kw
-        assert lib.hf_last_error_string().decode().startswith(fn + ":"), (kw, lib.hf_last_error_string())
+    assert_refused(_call, fn, CASES[fn])
 
 
 # ---- the float64 restatement ---------------------------------------------------------------------------------------

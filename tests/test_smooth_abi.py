@@ -1,13 +1,13 @@
 """Smooth shading on the CPU: the new entry points are declared, exported and bound; the float64 restatement
 (tests/smooth_ref.py) reproduces the reference's known answer and agrees with itself between the explicit face list
 and the heightfield's 1-ring enumeration; the adapter wires the property and both entry points."""
-import ctypes as C
 import os
 import re
 
 import numpy as np
 import torch
 
+from abi_helpers import assert_symbols
 import common
 import smooth_ref as R
 
@@ -16,15 +16,8 @@ NEW = ("hf_set_face_normals", "hf_get_face_normals", "hf_shading_derivatives")
 
 
 def test_new_symbols_declared_exported_and_bound():
-    import hf_amd
+    assert_symbols(NEW)
     from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", hdr), f"{name} not declared in include/hf.h"
-        assert hasattr(lib, name), f"{name} not exported by libhf.so"
-        assert name in _capi.SYMBOLS, f"{name} missing from the binding table"
-    assert _capi.lib().hf_version() == 4
     assert _capi.lib().hf_get_face_normals(None) == 1      # no handle: the default mode
 
 

@@ -1,31 +1,21 @@
 """Transform derivatives on the CPU: the four to_world entry points are declared, exported and bound; NULL handles are
 refused; the float64 restatement (tests/xform_ref.py), differentiated by central differences in to_world, reproduces
 the reference's test08 answers (src/shapes/tests/test_rectangle.py:176-272) on flat grids, which are the rectangle."""
-import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_helpers import assert_symbols
 import xform_ref as X
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hf_adjoint_transform", "hf_tangent_transform", "hf_sample_position_adjoint_transform",
        "hf_sample_position_tangent_transform")
 
 
 def test_new_symbols_declared_exported_and_bound():
-    import hf_amd
-    from hf_amd import _capi
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hf.h")).read(), flags=re.S)
-    lib = C.CDLL(hf_amd.build.LIB_PATH)
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", hdr), f"{name} not declared in include/hf.h"
-        assert hasattr(lib, name), f"{name} not exported by libhf.so"
-        assert name in _capi.SYMBOLS, f"{name} missing from the binding table"
-    assert _capi.lib().hf_version() == 4
+    assert_symbols(NEW)
 
 
 def test_null_handle_is_refused():
