@@ -1043,6 +1043,86 @@ int hf_glossy_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3
                                const float *dweight, const float *dalpha, const float *ddata, float *dimage, float *dvalue,
                                hf_stream_t stream);
 
+/* ---- next row: the refraction view, a textured plane seen through the surface ----
+ *
+ * The camera side of transmission, the other half of the `dielectric` BSDF that hf_reflect_* started: every wavefront
+ * sample is a CAMERA sample that looks along d, is refracted at the surface (the transmission lobe in radiance mode,
+ * src/bsdfs/dielectric.cpp:263-288, 358-363: the factor eta_ti^2 that hf_caustic_lighting leaves out), walked against the
+ * terrain up to a receiver plane and sees the bitmap texture the plane carries (src/textures/bitmap.cpp:400, 497-520)
+ * through a homogeneous absorbing medium below the surface.  A pool floor through water, a print through a glass relief.
+ *   vertex      the inputs, eligible, Fresnel (fresnel.h:35-71), direction (fresnel.h:311-314), consistent, receiver,
+ *               traced, ray (maxt = s), landing and pos are EXACTLY hf_caustic_lighting's, both signs of c_i included;
+ *               vis[i] = 1 iff the sample is traced and the any-hit walk of that ray finds nothing.  The materialised ray
+ *               is hf_caustic_rays': hf_caustic_rays + hf_ray_test equals vis bit for bit.
+ *   texture     tex[TH][TW] float32, row-major, scalar, the CALLER's device buffer.  A film position of the receiver is a
+ *               texel coordinate: texel (ix, iy) has its centre at pos = (ix + 0.5, iy + 0.5) -- the bitmap's
+ *               fmadd(uv, res, -0.5) with uv = pos / res.  Per axis, in float32: q = pos - 0.5, i0 = floor(q), f = q - i0;
+ *               the texels are wrap(i0) and wrap(i0 + 1), HF_WRAP_CLAMP: min(max(i, 0), res - 1), HF_WRAP_REPEAT: the
+ *               non-negative remainder of i by res.
+ *   lookup      v0 = fma(1 - fx, v00, fx v10), v1 = fma(1 - fx, v01, fx v11), L = fma(1 - fy, v0, fy v1);
+ *               with the cell held  Lx = (1 - fy)(v10 - v00) + fy (v11 - v01),  Ly = (1 - fx)(v01 - v00) + fx (v11 - v10)
+ *               (under clamp zero outside the texture of its own accord); b_j: the bilinear weights of the four texels.
+ *               A coordinate that is not finite or has |q| >= 2^23: under clamp it reads what a float clamp of q to
+ *               [-1, res] reads (the border texel, f = 0); under repeat L = 0 and every derivative is zero.
+ *   value       a = weight_i (1 - F) (weight NULL: 1 - F),  b = a (eta_ti eta_ti),  T = expf(-sigma_t s) (the accurate
+ *               float32 exponential; sigma_t == 0: no T at all),  value_i = (b T) L(pos) in float32 where vis = 1, exactly
+ *               0 elsewhere; pos = (-16, -16) where vis = 0.
+ *   image       image[i / spp] = 1/spp sum value_i: the box film of the rows above, overwritten; n a multiple of spp.
+ * Differentiated with respect to sh_n, p, weight and tex; the masks, the visibility, the sign choices, the cell, d, the
+ * receiver, eta and sigma_t are held.  With hf_caustic_lighting's d pos and d s and e2 = eta_ti^2:
+ *   d value = d weight (1 - F) e2 T L
+ *           + weight e2 T (-F' <d m, wi> L - (1 - F) sigma_t L d s + (1 - F) (Lx d pos_x + Ly d pos_y))
+ *           + weight (1 - F) e2 T sum_j b_j d tex_j.
+ * OUT OF SCOPE: a gradient for sigma_t, RGB, the mirror wrap, a second vertex (a transmitted ray that hits the terrain
+ * contributes 0).
+ * All five entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional,
+ * n >= 2^32, spp == 0 or n % spp != 0, TW == 0, TH == 0 or TW TH >= 2^31, a wrap that is neither constant, a non-finite or
+ * non-positive eta, a negative or non-finite sigma_t, an invalid receiver (hf_caustic_*'s checks).  Callers detect the
+ * entries by their symbols (HF_VERSION is unchanged). */
+#define HF_WRAP_CLAMP 0
+#define HF_WRAP_REPEAT 1
+/* the lookup alone, for film positions pos (2 device rows of n floats): out (n floats) = L, 0 on lanes with active[i] == 0
+ * (active NULL: every lane); out_grad (2 rows: Lx, Ly; zero on inactive lanes) may be NULL (not wanted).  The map is
+ * linear in tex: called with a tangent of the texels in place of tex it is the tangent, as hf_envmap_eval. */
+int hf_bitmap_eval(size_t n, const float *const pos[2], const uint8_t *active, uint32_t TW, uint32_t TH, const float *tex,
+                   int wrap, float *out, float *const out_grad[2], hf_stream_t stream);
+/* its transpose: grad_pos (2 rows, OVERWRITTEN, zero on inactive lanes) = grad_out (Lx, Ly); grad_tex[TH][TW] +=
+ * grad_out[i] b_j on the four texels of every active lane, float atomics, ACCUMULATED into.  Either may be NULL (not
+ * wanted), not both. */
+int hf_bitmap_eval_adjoint(size_t n, const float *const pos[2], const uint8_t *active, uint32_t TW, uint32_t TH,
+                           const float *tex, int wrap, const float *grad_out, float *const grad_pos[2], float *grad_tex,
+                           hf_stream_t stream);
+/* The fused launch (hf_reflect_lighting's shape: one lane per sample, one workgroup per 256 samples, no work counter):
+ * reads a sample's record once, refracts, runs the per-lane any-hit walk with maxt = s, looks the texture up where the ray
+ * lands and writes image (n / spp floats), value (n floats), vis (n bytes) and pos (2 rows of n floats); each may be NULL
+ * (not wanted), but not all four.  No ray goes to memory.  A batch of 64 samples without a traced lane skips the walk.
+ * hf_set_ray_coherence is neither read nor changed.  Allocates nothing, never synchronises the host, capturable. */
+int hf_refract_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                        const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                        const float *weight, float eta, float sigma_t, const hf_receiver_t *receiver, uint32_t TW,
+                        uint32_t TH, const float *tex, int wrap, float *image, float *value, uint8_t *vis,
+                        float *const pos[2], hf_stream_t stream);
+/* Reverse mode.  Traces nothing: the vertex is formed again and vis (as hf_refract_lighting wrote it) is read.  The
+ * upstream of sample i is g = grad_image[i / spp] / spp + grad_value[i]; either may be NULL (zero).  grad_sh_n, grad_p
+ * (3 rows each) and grad_weight are overwritten, exact zeros where vis = 0, one lane per sample, no atomics: bitwise the
+ * same from launch to launch; grad_tex ([TH][TW]) is ACCUMULATED with float atomics.  Any of the four may be NULL (not
+ * wanted).  Takes no field handle. */
+int hf_refract_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                                const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                                const float *weight, float eta, float sigma_t, const hf_receiver_t *receiver, uint32_t TW,
+                                uint32_t TH, const float *tex, int wrap, const uint8_t *vis, const float *grad_image,
+                                const float *grad_value, float *const grad_sh_n[3], float *const grad_p[3],
+                                float *grad_weight, float *grad_tex, hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dsh_n, dp (3 rows each), dweight (n) and dtex
+ * ([TH][TW]), each may be NULL (zero); dimage (n / spp) and dvalue (n) are overwritten, either may be NULL (not wanted),
+ * not both.  No atomics for any spp (the film tree of the rows above, or one lane per pixel). */
+int hf_refract_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                                const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                                const float *weight, float eta, float sigma_t, const hf_receiver_t *receiver, uint32_t TW,
+                                uint32_t TH, const float *tex, int wrap, const uint8_t *vis, const float *const dsh_n[3],
+                                const float *const dp[3], const float *dweight, const float *dtex, float *dimage,
+                                float *dvalue, hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional

@@ -63,6 +63,9 @@ _reflect_in = [C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, C.c_float,
 # alpha, eta, num_rays, seed, ray_id, W, H, data, rot
 _glossy_mid = [_fp, C.c_float, C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_float * 9)]
 _glossy_in = [C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, *_glossy_mid]  # sh_n, d, t, active, weight, ...
+HF_WRAP_CLAMP, HF_WRAP_REPEAT = 0, 1
+_bitmap_in = [C.c_uint32, C.c_uint32, _fp, C.c_int]  # TW, TH, tex, wrap
+_refract_mid = [_fp, C.c_float, C.c_float, C.POINTER(hf_receiver_t), *_bitmap_in]  # weight, eta, sigma_t, receiver, ...
 
 SYMBOLS = {
     "hf_create": (C.c_int, [C.POINTER(hf_desc_t), C.POINTER(C.c_void_p)]),
@@ -188,6 +191,15 @@ SYMBOLS = {
                                              _fp, C.c_void_p]),
     "hf_glossy_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, *_glossy_in, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp,
                                              _fp, C.c_void_p]),
+    "hf_bitmap_eval": (C.c_int, [C.c_size_t, C.POINTER(_fp * 2), _fp, *_bitmap_in, _fp, C.POINTER(_fp * 2), C.c_void_p]),
+    "hf_bitmap_eval_adjoint": (C.c_int, [C.c_size_t, C.POINTER(_fp * 2), _fp, *_bitmap_in, _fp, C.POINTER(_fp * 2), _fp,
+                                         C.c_void_p]),
+    "hf_refract_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, *_caustic_in, *_refract_mid, _fp, _fp, _fp,
+                                      C.POINTER(_fp * 2), C.c_void_p]),
+    "hf_refract_lighting_adjoint": (C.c_int, [C.c_size_t, C.c_uint32, *_caustic_in, *_refract_mid, _fp, _fp, _fp,
+                                              C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_void_p]),
+    "hf_refract_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, *_caustic_in, *_refract_mid, _fp, C.POINTER(_fp * 3),
+                                              C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, C.c_void_p]),
     "hf_envmap_table_floats":(C.c_size_t, [C.c_uint32, C.c_uint32]),
     "hf_envmap_build_table": (C.c_int, [C.c_uint32, C.c_uint32, _fp, C.c_float, _fp, C.c_void_p]),
     "hf_envmap_sample_direction": (C.c_int, [C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, C.c_uint32, _fp, _fp,

@@ -1282,15 +1282,22 @@ extern "C" int hf_sky_lighting_tangent(size_t n, uint32_t spp, const float *cons
 }
 
 // ---- refractive caustics: light tracing through the surface, the refracted rays walked in the kernel ----
-// What the four hf_caustic_* entries share: the wavefront rows, the interface and the receiver
-static int caustic_args(const char *who, size_t n, const float *const p[3], const float *const nrm[3],
+// What the hf_caustic_* entries and the refraction view (hf_refract_*) share, in the two pieces between which an entry
+// checks what is its own (A: the row's argument block, zeroed by the caller): the wavefront rows and the interface ...
+template <class A>
+static int caustic_rows(const char *who, size_t n, const float *const p[3], const float *const nrm[3],
                         const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
-                        const float *weight, float eta, float power, const hf_receiver_t *rcv, hf_caustic_args &a) {
-    a = {};
+                        const float *weight, float eta, const hf_receiver_t *rcv, A &a) {
     if (!all3(p) || !all3(nrm) || !all3(sh_n) || !all3(d) || !t || !rcv) return fail(HF_EINVAL, "%s: NULL argument", who);
     if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
     if (!isfinite(eta) || !(eta > 0.f)) return fail(HF_EINVAL, "%s: eta must be finite and positive (got %g)", who, (double) eta);
-    if (!isfinite(power)) return fail(HF_EINVAL, "%s: power must be finite", who);
+    a.n = n; a.eta = eta; a.rcp_eta = 1.f / eta; a.t = t; a.active = active; a.weight = weight;
+    for (int c = 0; c < 3; ++c) { a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.sh_n[c] = sh_n[c]; a.d[c] = d[c]; }
+    return HF_OK;
+}
+// ... and the receiver
+template <class A>
+static int caustic_receiver(const char *who, const hf_receiver_t *rcv, A &a) {
     double ex[3], ey[3], N[3], lx = 0.0, ly = 0.0, xy = 0.0, ln = 0.0;
     for (int c = 0; c < 3; ++c) {
         if (!isfinite(rcv->origin[c]) || !isfinite(rcv->ex[c]) || !isfinite(rcv->ey[c]))
@@ -1302,12 +1309,21 @@ static int caustic_args(const char *who, size_t n, const float *const p[3], cons
     for (int c = 0; c < 3; ++c) ln += N[c] * N[c];
     if (!(ln > 0.0)) return fail(HF_EINVAL, "%s: the receiver's ex x ey is zero", who);
     if (fabs(xy) > 1e-5 * sqrt(lx * ly)) return fail(HF_EINVAL, "%s: the receiver's ex and ey are not orthogonal", who);
-    a.n = n; a.eta = eta; a.rcp_eta = 1.f / eta; a.power = power; a.t = t; a.active = active; a.weight = weight;
     for (int c = 0; c < 3; ++c) {
-        a.p[c] = p[c]; a.nrm[c] = nrm[c]; a.sh_n[c] = sh_n[c]; a.d[c] = d[c];
         a.origin[c] = rcv->origin[c]; a.ex[c] = rcv->ex[c]; a.ey[c] = rcv->ey[c]; a.N[c] = (float) (N[c] / sqrt(ln));
     }
     return HF_OK;
+}
+// What the four hf_caustic_* entries share: the wavefront rows, the interface, the power and the receiver
+static int caustic_args(const char *who, size_t n, const float *const p[3], const float *const nrm[3],
+                        const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                        const float *weight, float eta, float power, const hf_receiver_t *rcv, hf_caustic_args &a) {
+    a = {};
+    const int rc = caustic_rows(who, n, p, nrm, sh_n, d, t, active, weight, eta, rcv, a);
+    if (rc != HF_OK) return rc;
+    if (!isfinite(power)) return fail(HF_EINVAL, "%s: power must be finite", who);
+    a.power = power;
+    return caustic_receiver(who, rcv, a);
 }
 
 extern "C" int hf_caustic_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
@@ -1375,6 +1391,131 @@ extern "C" int hf_caustic_tangent(size_t n, const float *const p[3], const float
     for (int c = 0; c < 2; ++c) a.pos[c] = dpos ? dpos[c] : nullptr;
     for (int c = 0; c < 3; ++c) { a.dn[c] = dsh_n ? dsh_n[c] : nullptr; a.dp[c] = dp ? dp[c] : nullptr; }
     return light_launch(hf_launch_caustic, 2, a, stream);
+}
+
+// ---- the refraction view: a textured receiver seen through the surface, the refracted rays walked in the kernel ----
+// the plane texture of the hf_bitmap_* and hf_refract_* entries (A: a block with TW, TH, wrap and tex, zeroed by the caller)
+template <class A>
+static int bitmap_texture(const char *who, uint32_t TW, uint32_t TH, const float *tex, int wrap, A &a) {
+    if (!tex) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (TW == 0 || TH == 0 || (uint64_t) TW * TH >= ((uint64_t) 1 << 31))
+        return fail(HF_EINVAL, "%s: the texture must have 1 .. 2^31 - 1 texels (got %u x %u)", who, TW, TH);
+    if (wrap != HF_WRAP_CLAMP && wrap != HF_WRAP_REPEAT)
+        return fail(HF_EINVAL, "%s: wrap must be HF_WRAP_CLAMP or HF_WRAP_REPEAT (got %d)", who, wrap);
+    a.TW = TW; a.TH = TH; a.tex = tex; a.wrap = wrap;
+    return HF_OK;
+}
+static int bitmap_args(const char *who, size_t n, const float *const pos[2], const uint8_t *active, uint32_t TW, uint32_t TH,
+                       const float *tex, int wrap, hf_bitmap_args &a) {
+    a = {};
+    if (!pos || !pos[0] || !pos[1]) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    a.n = n; a.pos[0] = pos[0]; a.pos[1] = pos[1]; a.active = active;
+    return bitmap_texture(who, TW, TH, tex, wrap, a);
+}
+
+extern "C" int hf_bitmap_eval(size_t n, const float *const pos[2], const uint8_t *active, uint32_t TW, uint32_t TH,
+                              const float *tex, int wrap, float *out, float *const out_grad[2], hf_stream_t stream) {
+    const char *fn = "hf_bitmap_eval";
+    hf_bitmap_args a;
+    const int rc = bitmap_args(fn, n, pos, active, TW, TH, tex, wrap, a);
+    if (rc != HF_OK) return rc;
+    if (!out || (out_grad && (!out_grad[0] || !out_grad[1]))) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.out = out;
+    for (int c = 0; c < 2; ++c) a.out_grad[c] = out_grad ? out_grad[c] : nullptr;
+    if (n == 0) return HF_OK;
+    hf_launch_bitmap(false, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_bitmap_eval_adjoint(size_t n, const float *const pos[2], const uint8_t *active, uint32_t TW, uint32_t TH,
+                                      const float *tex, int wrap, const float *grad_out, float *const grad_pos[2],
+                                      float *grad_tex, hf_stream_t stream) {
+    const char *fn = "hf_bitmap_eval_adjoint";
+    hf_bitmap_args a;
+    const int rc = bitmap_args(fn, n, pos, active, TW, TH, tex, wrap, a);
+    if (rc != HF_OK) return rc;
+    if (!grad_out || (grad_pos && (!grad_pos[0] || !grad_pos[1]))) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!grad_pos && !grad_tex) return fail(HF_EINVAL, "%s: grad_pos and grad_tex are both NULL", fn);
+    a.gout = grad_out; a.gtex = grad_tex;
+    for (int c = 0; c < 2; ++c) a.gpos[c] = grad_pos ? grad_pos[c] : nullptr;
+    if (n == 0) return HF_OK;
+    hf_launch_bitmap(true, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+// What the three hf_refract_* entries share: the caustic row's rows, interface and receiver, the film's sample count,
+// the texture and the medium
+static int refract_args(const char *who, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                        const float *const sh_n[3], const float *const d[3], const float *t, const uint8_t *active,
+                        const float *weight, float eta, float sigma_t, const hf_receiver_t *rcv, uint32_t TW, uint32_t TH,
+                        const float *tex, int wrap, hf_refract_args &a) {
+    a = {};
+    int rc = caustic_rows(who, n, p, nrm, sh_n, d, t, active, weight, eta, rcv, a);
+    if (rc != HF_OK) return rc;
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if ((rc = bitmap_texture(who, TW, TH, tex, wrap, a))) return rc;
+    if (!isfinite(sigma_t) || sigma_t < 0.f)
+        return fail(HF_EINVAL, "%s: sigma_t must be finite and not negative (got %g)", who, (double) sigma_t);
+    a.spp = spp; a.sigma_t = sigma_t;
+    return caustic_receiver(who, rcv, a);
+}
+
+extern "C" int hf_refract_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                   const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                   const float *t, const uint8_t *active, const float *weight, float eta, float sigma_t,
+                                   const hf_receiver_t *receiver, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                                   float *image, float *value, uint8_t *vis, float *const pos[2], hf_stream_t stream) {
+    const char *fn = "hf_refract_lighting";
+    hf_refract_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = refract_args(fn, n, spp, p, nrm, sh_n, d, t, active, weight, eta, sigma_t, receiver, TW, TH, tex, wrap, a);
+    if (rc != HF_OK) return rc;
+    if (pos && (!pos[0] || !pos[1])) return fail(HF_EINVAL, "%s: NULL pos component array", fn);
+    if (!image && !value && !vis && !pos) return fail(HF_EINVAL, "%s: image, value, vis and pos are all NULL", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = image; a.value = value; a.vis = vis;
+    for (int c = 0; c < 2; ++c) a.pos[c] = pos ? pos[c] : nullptr;
+    return light_launch(hf_launch_refract, 0, a, stream);
+}
+
+extern "C" int hf_refract_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                                           const float *const sh_n[3], const float *const d[3], const float *t,
+                                           const uint8_t *active, const float *weight, float eta, float sigma_t,
+                                           const hf_receiver_t *receiver, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                                           const uint8_t *vis, const float *grad_image, const float *grad_value,
+                                           float *const grad_sh_n[3], float *const grad_p[3], float *grad_weight,
+                                           float *grad_tex, hf_stream_t stream) {
+    const char *fn = "hf_refract_lighting_adjoint";
+    hf_refract_args a;
+    int rc = refract_args(fn, n, spp, p, nrm, sh_n, d, t, active, weight, eta, sigma_t, receiver, TW, TH, tex, wrap, a);
+    if (rc != HF_OK) return rc;
+    if (grad_p && !all3(grad_p)) return fail(HF_EINVAL, "%s: NULL grad_p component array", fn);
+    if ((rc = light_value_adjoint_io(fn, !vis, grad_image, grad_value, grad_sh_n, grad_weight, grad_tex, a))) return rc;
+    a.vis = const_cast<uint8_t *>(vis);
+    for (int c = 0; c < 3; ++c) a.gp[c] = grad_p ? grad_p[c] : nullptr;
+    return light_launch(hf_launch_refract, 1, a, stream);
+}
+
+extern "C" int hf_refract_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                                           const float *const sh_n[3], const float *const d[3], const float *t,
+                                           const uint8_t *active, const float *weight, float eta, float sigma_t,
+                                           const hf_receiver_t *receiver, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                                           const uint8_t *vis, const float *const dsh_n[3], const float *const dp[3],
+                                           const float *dweight, const float *dtex, float *dimage, float *dvalue,
+                                           hf_stream_t stream) {
+    const char *fn = "hf_refract_lighting_tangent";
+    hf_refract_args a;
+    int rc = refract_args(fn, n, spp, p, nrm, sh_n, d, t, active, weight, eta, sigma_t, receiver, TW, TH, tex, wrap, a);
+    if (rc != HF_OK) return rc;
+    if (dp && !all3(dp)) return fail(HF_EINVAL, "%s: NULL dp component array", fn);
+    if ((rc = light_value_tangent_io(fn, !vis, dsh_n, dweight, dtex, dimage, dvalue, a))) return rc;
+    a.vis = const_cast<uint8_t *>(vis);
+    for (int c = 0; c < 3; ++c) a.dp[c] = dp ? dp[c] : nullptr;
+    return light_launch(hf_launch_refract, 2, a, stream);
 }
 
 // ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----

@@ -3758,6 +3758,12 @@ __device__ __forceinline__ void light_store_grads(const A &a, size_t i, v3 gn, f
     light_store3(a.gn, i, gn);
     if (a.gw) a.gw[i] = gw;
 }
+// ... and of p, for the rows whose value or landing depends on it
+template <class A>
+__device__ __forceinline__ void light_store_grads(const A &a, size_t i, v3 gn, v3 gp, float gw) {
+    light_store_grads(a, i, gn, gw);
+    light_store3(a.gp, i, gp);
+}
 
 // The tangent image of a row with one channel, VALUE(a, i) the tangent of sample i's value.  PIXEL = false: one lane per
 // sample and the primal's film (spp a power of two <= 64: its shuffle tree, one store per pixel; or no image wanted);
@@ -4022,6 +4028,7 @@ struct hf_caustic_vertex {
     bool traced;                  // eligible, transmitted, consistent and on its way to the receiver
     v3 wi, wo;
     float s, b, F, q, dF, dq;     // s: distance to the receiver, b = <wo, N>, q = c_i eta_ti + c_t
+    float e2;                     // eta_ti^2: the radiance-mode factor of the refraction view (the caustics carry importance)
 };
 template <class P>
 __device__ __forceinline__ hf_caustic_vertex caustic_vertex(P a, v3 m, v3 g, v3 d, v3 p, float t, bool act) {
@@ -4033,6 +4040,7 @@ __device__ __forceinline__ hf_caustic_vertex caustic_vertex(P a, v3 m, v3 g, v3 
     const bool outside = ci >= 0.f;
     const float eta_it = outside ? eta : rcp_eta, eta_ti = outside ? rcp_eta : eta;
     const float e2 = eta_ti * eta_ti;
+    v.e2 = e2;
     const float ct2 = __builtin_fmaf(-__builtin_fmaf(-ci, ci, 1.f), e2, 1.f);
     ok = ok && (ct2 > 0.f); // total internal reflection: nothing is transmitted
     const float cia = __builtin_fabsf(ci), cta = __builtin_sqrtf(fmaxf(ct2, 0.f));
@@ -4064,6 +4072,32 @@ __device__ __forceinline__ void caustic_landing(P a, v3 p, const hf_caustic_vert
     const v3 r = fma3(v.wo, v.s, p) - mk3(a->origin[0], a->origin[1], a->origin[2]);
     x = dot3(r, mk3(a->ex[0], a->ex[1], a->ex[2]));
     y = dot3(r, mk3(a->ey[0], a->ey[1], a->ey[2]));
+}
+// The derivatives of the landing, for the rows that land on the receiver (A: hf_caustic_args or hf_refract_args).
+// Forward mode: tangents dm of sh_n and dp of p, dci = <dm, wi>; d wo, d s (`ds`) and d pos = (dx, dy)
+template <class A>
+__device__ __forceinline__ void caustic_landing_tangent(const A &a, const hf_caustic_vertex &v, v3 m, v3 dm, v3 dp, float dci,
+                                                        float &dx, float &dy, float &ds) {
+    const v3 N = mk3(a.N[0], a.N[1], a.N[2]);
+    const v3 dwo = fma3(m, v.dq * dci, dm * v.q);
+    ds = -(dot3(dp, N) + v.s * dot3(dwo, N)) / v.b;
+    const v3 dX = fma3(v.wo, ds, fma3(dwo, v.s, dp));
+    dx = dot3(dX, mk3(a.ex[0], a.ex[1], a.ex[2]));
+    dy = dot3(dX, mk3(a.ey[0], a.ey[1], a.ey[2]));
+}
+// Reverse mode, its transpose: (gx, gy) = dL/dpos, gs = dL/ds (DS: the row's value depends on s), gc = dL/dc_i through
+// the value; gm, gp: the gradients of sh_n and p
+template <bool DS, class A>
+__device__ __forceinline__ void caustic_landing_adjoint(const A &a, const hf_caustic_vertex &v, v3 m, float gx, float gy, float gs,
+                                                        float gc, v3 &gm, v3 &gp) {
+    const v3 N = mk3(a.N[0], a.N[1], a.N[2]);
+    const v3 gX = fma3(mk3(a.ex[0], a.ex[1], a.ex[2]), gx, mk3(a.ey[0], a.ey[1], a.ey[2]) * gy);
+    const float gl = dot3(gX, v.wo);
+    const float c = -(DS ? gl + gs : gl) / v.b;   // dL/ds over -b
+    gp = fma3(N, c, gX);
+    const v3 gwo = fma3(N, c * v.s, gX * v.s);
+    const float gci = __builtin_fmaf(v.dq, dot3(m, gwo), gc);
+    gm = fma3(v.wi, gci, gwo * v.q);
 }
 // the vertex of sample i from the rows
 template <class P>
@@ -4146,19 +4180,12 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_caustic_adjoint_kernel(hf_caustic
         if (v.traced) {
             const float gx = a.gpos[0] ? a.gpos[0][i] : 0.f, gy = a.gpos[1] ? a.gpos[1][i] : 0.f;
             const float gv = a.gvalue ? a.gvalue[i] : 0.f;
-            const v3 N = mk3(a.N[0], a.N[1], a.N[2]);
-            const v3 gX = fma3(mk3(a.ex[0], a.ex[1], a.ex[2]), gx, mk3(a.ey[0], a.ey[1], a.ey[2]) * gy);
-            const float c = -dot3(gX, v.wo) / v.b;     // dL/ds over -b
-            gp = fma3(N, c, gX);
-            const v3 gwo = fma3(N, c * v.s, gX * v.s);
             const float pw = a.power * (a.weight ? a.weight[i] : 1.f);
-            const float gci = __builtin_fmaf(v.dq, dot3(m, gwo), -(pw * v.dF) * gv);
-            gm = fma3(v.wi, gci, gwo * v.q);
+            caustic_landing_adjoint<false>(a, v, m, gx, gy, 0.f, -(pw * v.dF) * gv, gm, gp);
             gw = a.power * (1.f - v.F) * gv;
         }
     }
-    light_store_grads(a, i, gm, gw);
-    light_store3(a.gp, i, gp);
+    light_store_grads(a, i, gm, gp, gw);
 }
 
 // forward mode, the transpose of the above: tangents dn of sh_n, dp of p, dw of weight (NULL: zero)
@@ -4173,13 +4200,9 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_caustic_tangent_kernel(hf_caustic
             const v3 dm = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
             const v3 dp = a.dp[0] ? mk3(a.dp[0][i], a.dp[1][i], a.dp[2][i]) : mk3(0.f, 0.f, 0.f);
             const float dw = a.dw ? a.dw[i] : 0.f;
-            const v3 N = mk3(a.N[0], a.N[1], a.N[2]);
             const float dci = dot3(dm, v.wi);
-            const v3 dwo = fma3(m, v.dq * dci, dm * v.q);
-            const float ds = -(dot3(dp, N) + v.s * dot3(dwo, N)) / v.b;
-            const v3 dX = fma3(v.wo, ds, fma3(dwo, v.s, dp));
-            dx = dot3(dX, mk3(a.ex[0], a.ex[1], a.ex[2]));
-            dy = dot3(dX, mk3(a.ey[0], a.ey[1], a.ey[2]));
+            float ds;
+            caustic_landing_tangent(a, v, m, dm, dp, dci, dx, dy, ds);
             const float pw = a.power * (a.weight ? a.weight[i] : 1.f);
             dv = __builtin_fmaf(dw, a.power * (1.f - v.F), -(pw * v.dF) * dci);
         }
@@ -6265,6 +6288,239 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_glossy_tangent_kernel(hf_glossy_a
 void hf_launch_glossy(int mode, const hf_glossy_args &a, hipStream_t stream) {
     launch_light(mode, a, 1u, stream, hf_glossy_kernel, hf_glossy_adjoint_kernel, hf_glossy_tangent_kernel<false>,
                  hf_glossy_tangent_kernel<true>, hf_glossy_rays_kernel);
+}
+
+// ---------------------------------------------------------------------------------
+// The refraction view (include/hf.h hf_refract_*, hf_bitmap_*): the camera side of transmission.  Every wavefront
+// sample looks along d, is refracted at its shading normal (caustic_vertex: the vertex, the masks, the ray and the
+// landing are the caustic row's, function for function), walked up to the receiver (any hit, per lane, maxt = s) and
+// sees the receiver's bitmap texture (bitmap.cpp:400, 497-520) through an absorbing medium:
+//   value = ((weight (1 - F)) eta_ti^2) exp(-sigma_t s) L(pos)   (dielectric.cpp:358-363, radiance mode).
+// ONE launch, one lane per sample, hf_reflect_kernel's shape: the lookup runs after the walk.  The row's own text is
+// the texture lookup and the value's derivative; the vertex and the landing's derivatives are the caustic row's, the
+// seed, the outputs, the tangent film and the launch the lighting rows' shared functions.
+// ---------------------------------------------------------------------------------
+// One axis of the lookup in float32: q = pos - 0.5, i0 = floor(q), f = q - i0, the texels wrap(i0) and wrap(i0 + 1).
+// A coordinate that is not finite or beyond 2^23 (its floor is no int32, its fraction no fraction): under clamp the
+// border texel q is nearest to with f = 0 -- what a float clamp of q to [-1, res] reads; under repeat nothing (false)
+__device__ __forceinline__ uint32_t bitmap_wrap(int32_t i, uint32_t res, bool repeat) {
+    if (repeat) {
+        const int32_t r = i % (int32_t) res;
+        return (uint32_t) (r < 0 ? r + (int32_t) res : r);
+    }
+    return (uint32_t) min(max(i, 0), (int32_t) res - 1);
+}
+__device__ __forceinline__ bool bitmap_axis(float pos, uint32_t res, bool repeat, uint32_t &i0, uint32_t &i1, float &f) {
+    const float q = pos - 0.5f;
+    if (!(__builtin_fabsf(q) < 8388608.f)) {
+        i0 = i1 = (!repeat && q > 0.f) ? res - 1u : 0u;
+        f = 0.f;
+        return !repeat;
+    }
+    const float fl = __builtin_floorf(q);
+    f = q - fl;
+    i0 = bitmap_wrap((int32_t) fl, res, repeat);
+    i1 = bitmap_wrap((int32_t) fl + 1, res, repeat);
+    return true;
+}
+// THE lookup of a film position, for every kernel that evaluates the texture or differentiates the evaluation: the
+// offsets of the texels v00, v10, v01, v11, the position in the cell, and whether anything is read at all
+// (P: a pointer to hf_refract_args or hf_bitmap_args)
+struct hf_bitmap_cell {
+    size_t j[4];
+    float fx, fy;
+    bool ok;
+    // Texture::eval_1 (bitmap.cpp:497-520).  Every radiance a kernel reports is THIS expression; linear in the texels
+    __device__ __forceinline__ float value(const float *tex) const {
+        const float gx = 1.f - fx, gy = 1.f - fy;
+        const float v0 = __builtin_fmaf(gx, tex[j[0]], fx * tex[j[1]]), v1 = __builtin_fmaf(gx, tex[j[2]], fx * tex[j[3]]);
+        return ok ? __builtin_fmaf(gy, v0, fy * v1) : 0.f;
+    }
+    // (Lx, Ly) = dL/dpos with the cell held
+    __device__ __forceinline__ void slopes(const float *tex, float &Lx, float &Ly) const {
+        const float v00 = tex[j[0]], v10 = tex[j[1]], v01 = tex[j[2]], v11 = tex[j[3]];
+        Lx = ok ? (1.f - fy) * (v10 - v00) + fy * (v11 - v01) : 0.f;
+        Ly = ok ? (1.f - fx) * (v01 - v00) + fx * (v11 - v10) : 0.f;
+    }
+    // gtex += q b_j: four float atomics
+    __device__ __forceinline__ void scatter(float *gtex, float q) const {
+        if (!ok) return;
+        const float gx = 1.f - fx, gy = 1.f - fy;
+        atomicAdd(gtex + j[0], q * (gy * gx)); atomicAdd(gtex + j[1], q * (gy * fx));
+        atomicAdd(gtex + j[2], q * (fy * gx)); atomicAdd(gtex + j[3], q * (fy * fx));
+    }
+};
+template <class P>
+__device__ __forceinline__ hf_bitmap_cell bitmap_cell(P a, float x, float y) {
+    hf_bitmap_cell e;
+    const uint32_t TW = a->TW, TH = a->TH;
+    const bool repeat = a->wrap == HF_WRAP_REPEAT;
+    uint32_t x0, x1, y0, y1;
+    const bool okx = bitmap_axis(x, TW, repeat, x0, x1, e.fx), oky = bitmap_axis(y, TH, repeat, y0, y1, e.fy);
+    e.ok = okx && oky;
+    e.j[0] = (size_t) y0 * TW + x0; e.j[1] = (size_t) y0 * TW + x1;
+    e.j[2] = (size_t) y1 * TW + x0; e.j[3] = (size_t) y1 * TW + x1;
+    return e;
+}
+// ADJ = false: out[i] = L, out_grad = (Lx, Ly), zeros for an inactive lane;
+// ADJ = true: grad_pos = grad_out[i] (Lx, Ly) overwritten, grad_tex += grad_out[i] b_j (float atomics)
+template <bool ADJ>
+__global__ __launch_bounds__(HF_BLOCK) void hf_bitmap_eval_kernel(hf_bitmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    float *const sx = ADJ ? a.gpos[0] : a.out_grad[0], *const sy = ADJ ? a.gpos[1] : a.out_grad[1];
+    float L = 0.f, Lx = 0.f, Ly = 0.f;
+    if (a.active ? a.active[i] != 0 : true) {
+        const hf_bitmap_cell e = bitmap_cell(&a, a.pos[0][i], a.pos[1][i]);
+        const float g = ADJ ? a.gout[i] : 1.f;
+        if (!ADJ) L = e.value(a.tex);
+        if (sx) {
+            e.slopes(a.tex, Lx, Ly);
+            Lx *= g; Ly *= g;
+        }
+        if (ADJ && a.gtex) e.scatter(a.gtex, g);
+    }
+    if (!ADJ) a.out[i] = L;
+    if (sx) { sx[i] = Lx; sy[i] = Ly; }
+}
+void hf_launch_bitmap(bool adjoint, const hf_bitmap_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    hipLaunchKernelGGL(adjoint ? hf_bitmap_eval_kernel<true> : hf_bitmap_eval_kernel<false>, grid, block, 0, stream, a);
+}
+
+typedef const __attribute__((address_space(4))) hf_refract_args *hf_refract_kargs;
+
+// what a deposited sample carries to the lookup besides its landing: ((weight (1 - F)) eta_ti^2) exp(-sigma_t s), in
+// this order; sigma_t == 0: no exponential at all
+__device__ __forceinline__ float refract_throughput(const hf_caustic_vertex &v, const float *weight, size_t i, float sigma_t) {
+    const float oneF = 1.f - v.F;
+    const float b = (weight ? weight[i] * oneF : oneF) * v.e2;
+    return sigma_t != 0.f ? b * expf(-sigma_t * v.s) : b;
+}
+
+#ifndef HF_REFRACT_WAVES
+#define HF_REFRACT_WAVES 6 // resident waves per SIMD (the siblings')
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_REFRACT_WAVES) void hf_refract_kernel(hf_refract_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    hf_refract_kargs ka = (hf_refract_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    float x = -16.f, y = -16.f, bT = 0.f; // what a sample that sees nothing writes
+    bool traced;
+    hf_hit best;
+    best.hit = false;
+    {
+        v3 m, p;
+        const hf_caustic_vertex v = caustic_sample(ka, ii, in, m, p);
+        traced = v.traced;
+        if (__ballot(traced) != 0ull) { // wave-uniform: a batch without a traced sample walks nothing
+            const v3 gn = mk3(ka->nrm[0][ii], ka->nrm[1][ii], ka->nrm[2][ii]);
+            if (traced) {
+                caustic_landing(ka, p, v, x, y);
+                bT = refract_throughput(v, ka->weight, ii, ka->sigma_t); // (the exponential: before the walk's state is live)
+            }
+            // the landing, the throughput and the index are held across the walk; the ray ends at the receiver
+            light_walk<true>(&ka->f, f, sky_origin(p, gn, sky_offset(p), v.wo), v.wo, v.s, traced, best);
+        }
+    }
+    // (the texture and the output pointers: loaded here, not before the walk; the lookup runs when the walk's state is
+    // dead)
+    hf_refract_kargs ko = (hf_refract_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    const bool lit = traced && !best.hit; // (traced: in range)
+    float val = 0.f;
+    if (lit) val = bT * bitmap_cell(ko, x, y).value(ko->tex);
+    if (in) {
+        float *value = ko->value, *px = ko->pos[0], *py = ko->pos[1];
+        uint8_t *vis = ko->vis;
+        if (value) value[i] = val;
+        if (vis) vis[i] = lit ? 1 : 0;
+        if (px) { px[i] = lit ? x : -16.f; py[i] = lit ? y : -16.f; }
+    }
+    float *image = ko->image;
+    if (image) {
+        const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+        film_pixel(image, val, 0u, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+    }
+}
+
+// What the two derivative kernels form again of a visible sample: the vertex, the landing's lookup and the factors of
+//   d value = dw oneF k L + A (-dF dci L + oneF (-sigma_t L ds + Lx dx + Ly dy)) + A oneF sum_j b_j dtex_j,
+// k = eta_ti^2 T, A = weight k
+struct hf_refract_shade {
+    hf_caustic_vertex v;
+    hf_bitmap_cell e;
+    v3 m;
+    float oneF, k, A, L, Lx, Ly;
+};
+__device__ __forceinline__ hf_refract_shade refract_shade(const hf_refract_args &a, size_t i) {
+    hf_refract_shade s;
+    v3 p;
+    s.v = caustic_sample(&a, i, true, s.m, p);
+    float x, y;
+    caustic_landing(&a, p, s.v, x, y);
+    s.e = bitmap_cell(&a, x, y);
+    s.L = s.e.value(a.tex);
+    s.e.slopes(a.tex, s.Lx, s.Ly);
+    s.oneF = 1.f - s.v.F;
+    s.k = a.sigma_t != 0.f ? s.v.e2 * expf(-a.sigma_t * s.v.s) : s.v.e2;
+    s.A = a.weight ? a.weight[i] * s.k : s.k;
+    return s;
+}
+
+// Reverse mode of hf_refract_kernel with respect to sh_n, p, weight and the texels: nothing is traced, the vertex is
+// formed again and the visibility byte read.  grad_sh_n, grad_p, grad_weight: one lane per sample, overwritten, no
+// atomics; grad_tex: one float atomic per texel of every visible sample
+__global__ __launch_bounds__(HF_BLOCK) void hf_refract_adjoint_kernel(hf_refract_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 gm = mk3(0.f, 0.f, 0.f), gp = gm;
+    float gw = 0.f;
+    if (a.vis[i]) {
+        const hf_refract_shade s = refract_shade(a, i);
+        if (s.v.traced) {
+            const float g = light_value_seed(a, i);
+            const float gA = g * s.A, gAF = gA * s.oneF;
+            gw = g * ((s.oneF * s.k) * s.L);
+            caustic_landing_adjoint<true>(a, s.v, s.m, gAF * s.Lx, gAF * s.Ly, -(gAF * a.sigma_t) * s.L, -(gA * s.v.dF) * s.L, gm, gp);
+            if (a.gdata) s.e.scatter(a.gdata, gAF);
+        }
+    }
+    light_store_grads(a, i, gm, gp, gw);
+}
+
+// forward mode, the transpose of the above: the tangent of sample i's value for tangents dn of sh_n, dp of p, dw of
+// weight and dtex of the texels (NULL: zero)
+__device__ __forceinline__ float refract_tangent_value(const hf_refract_args &a, size_t i) {
+    if (!a.vis[i]) return 0.f;
+    const hf_refract_shade s = refract_shade(a, i);
+    if (!s.v.traced) return 0.f;
+    const v3 dm = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const v3 dp = a.dp[0] ? mk3(a.dp[0][i], a.dp[1][i], a.dp[2][i]) : mk3(0.f, 0.f, 0.f);
+    const float dw = a.dw ? a.dw[i] : 0.f;
+    const float dci = dot3(dm, s.v.wi);
+    float dx, dy, ds;
+    caustic_landing_tangent(a, s.v, s.m, dm, dp, dci, dx, dy, ds);
+    float dL = __builtin_fmaf(s.Lx, dx, s.Ly * dy) - (a.sigma_t * s.L) * ds;
+    if (a.ddata) dL += s.e.value(a.ddata);
+    const float dv = __builtin_fmaf(s.oneF, dL, -(s.v.dF * dci) * s.L);
+    return __builtin_fmaf(dw, (s.oneF * s.k) * s.L, s.A * dv);
+}
+// (the per-sample tangent is written too, and the image may be NULL)
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_refract_tangent_kernel(hf_refract_args a) {
+    light_tangent_image<PIXEL, hf_refract_args, refract_tangent_value>(a, a.value);
+}
+
+// mode 0: forward, 1: adjoint, 2: tangent (the row has no rays kernel: its ray is hf_caustic_rays')
+void hf_launch_refract(int mode, const hf_refract_args &a, hipStream_t stream) {
+    launch_light(mode, a, 1u, stream, hf_refract_kernel, hf_refract_adjoint_kernel, hf_refract_tangent_kernel<false>,
+                 hf_refract_tangent_kernel<true>, (void (*)(hf_refract_args)) nullptr);
 }
 
 // ---------------------------------------------------------------------------------

@@ -177,6 +177,41 @@ struct hf_glossy_args {
 // mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is hf_launch_sky's: the per-lane any-hit walk,
 // no work counter, no scratch block
 void hf_launch_glossy(int mode, const hf_glossy_args &a, hipStream_t stream);
+// ---- the refraction view (hf_refract_lighting / _adjoint / _tangent): the one argument of its three kernels; eta,
+// rcp_eta, the receiver and the rows under hf_caustic_args' names (caustic_vertex reads either), TW, TH, wrap as in
+// hf_bitmap_args (bitmap_cell reads either) ----
+struct hf_refract_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, TW, TH;
+    int32_t wrap;                            // HF_WRAP_CLAMP / HF_WRAP_REPEAT
+    float eta, rcp_eta, sigma_t;             // rcp_eta = 1 / eta, rounded once on the host
+    float origin[3], ex[3], ey[3], N[3];     // the receiver; N = normalize(ex x ey)
+    const float *tex;                        // [TH][TW]
+    const float *p[3], *nrm[3], *sh_n[3], *d[3], *t, *weight;
+    const uint8_t *active;                   // optional (NULL: every lane)
+    float *image, *value;                    // forward: written (NULL: not wanted); tangent: dimage, dvalue
+    uint8_t *vis;                            // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *pos[2];                           // forward: written (NULL: not wanted)
+    const float *gimg, *gvalue;              // adjoint inputs (NULL: zero)
+    float *gn[3], *gp[3], *gw, *gdata;       // adjoint outputs (NULL: not wanted); gdata (the texels') is accumulated
+    const float *dn[3], *dp[3], *dw, *ddata; // tangent inputs (NULL: zero); ddata: the texels'
+};
+// mode 0: forward, 1: adjoint, 2: tangent.  The forward launch is hf_launch_sky's: the per-lane any-hit walk, no work
+// counter, no scratch block
+void hf_launch_refract(int mode, const hf_refract_args &a, hipStream_t stream);
+// ---- the plane texture alone (hf_bitmap_eval / _adjoint) ----
+struct hf_bitmap_args {
+    size_t n;
+    uint32_t TW, TH;
+    int32_t wrap;
+    const float *tex, *pos[2];
+    const uint8_t *active;                   // optional (NULL: every lane)
+    float *out, *out_grad[2];                // eval: L and (optional) Lx, Ly
+    const float *gout;                       // adjoint: dL/dvalue
+    float *gpos[2], *gtex;                   // adjoint outputs (NULL: not wanted); gtex is accumulated
+};
+void hf_launch_bitmap(bool adjoint, const hf_bitmap_args &a, hipStream_t stream);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----

@@ -2084,6 +2084,179 @@ def glossy_rays(si, ray, alpha, k, seed=0, ray_index=None, active=True, return_n
     return (r, h) if return_normal else r
 
 
+_WRAPS = {"clamp": _capi.HF_WRAP_CLAMP, "repeat": _capi.HF_WRAP_REPEAT}
+
+
+def _bitmap_in(dat, wrap):
+    """the texture's C arguments: TW, TH, tex, wrap"""
+    return dat.shape[1], dat.shape[0], dat.data_ptr(), wrap
+
+
+class _BitmapEvalOp(torch.autograd.Function):
+    """hf_bitmap_eval of the texture `data` ([TH, TW]) at film positions; backward = hf_bitmap_eval_adjoint (gradients of
+    the texels and of the positions, the cell held), jvp = hf_bitmap_eval of the texels' tangent + (Lx, Ly) . dpos."""
+
+    @staticmethod
+    def _eval(dat, pp, act, wrap, slopes=False):
+        n = pp.shape[1]
+        out = torch.empty(n, dtype=torch.float32, device=pp.device)
+        grad = torch.empty((2, n), dtype=torch.float32, device=pp.device) if slopes else None
+        if n:
+            check(_capi.lib().hf_bitmap_eval(n, _ref(_row_ptrs(pp)), _ptr(act), *_bitmap_in(dat, wrap), out.data_ptr(),
+                                             _ref(_row_ptrs(grad)), _stream_of(pp.device)))
+        return (out, grad) if slopes else out
+
+    @staticmethod
+    def forward(ctx, data, pos, active, wrap):
+        dat, pp = _detached_f32(data), _detached_f32(pos)
+        ctx.misc = (active, wrap)
+        ctx.save_for_backward(dat, pp)
+        ctx.save_for_forward(dat, pp)
+        return _BitmapEvalOp._eval(dat, pp, active, wrap)
+
+    @staticmethod
+    def jvp(ctx, ddata, dpos, *_):
+        act, wrap = ctx.misc
+        dat, pp = ctx.saved_tensors
+        out = torch.zeros(pp.shape[1], dtype=torch.float32, device=pp.device)
+        if ddata is not None:
+            out = _BitmapEvalOp._eval(_texel_tangent(ddata), pp, act, wrap)
+        if dpos is not None:
+            _, slopes = _BitmapEvalOp._eval(dat, pp, act, wrap, slopes=True)
+            out = out + (slopes * dpos.to(dtype=torch.float32)).sum(0)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        act, wrap = ctx.misc
+        dat, pp = ctx.saved_tensors
+        gd = _texel_grad(ctx, 0, dat)
+        gp = torch.zeros_like(pp) if ctx.needs_input_grad[1] else None
+        if pp.shape[1] and (gd is not None or gp is not None):
+            go = _detached_f32(grad_out)
+            check(_capi.lib().hf_bitmap_eval_adjoint(pp.shape[1], _ref(_row_ptrs(pp)), _ptr(act), *_bitmap_in(dat, wrap),
+                                                     go.data_ptr(), _ref(_row_ptrs(gp)), _ptr(gd), _stream_of(pp.device)))
+        return gd, gp, None, None
+
+
+class Bitmap:
+    """The reference's ``bitmap`` texture (src/textures/bitmap.cpp) for one channel with the bilinear filter, laid on a
+    ``Receiver``: a film position of the receiver is a texel coordinate, texel (ix, iy) has its centre at
+    ``(ix + 0.5, iy + 0.5)``.  ``data``: [TH, TW] float32 device tensor, kept by reference -- it may require grad.
+    ``wrap``: ``"clamp"`` or ``"repeat"``."""
+
+    def __init__(self, data, wrap="clamp"):
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.float32:
+            data = torch.as_tensor(data, dtype=torch.float32)
+        if data.dim() != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+            raise ValueError("Bitmap: data must be [TH >= 1, TW >= 1]")
+        if wrap not in _WRAPS:
+            raise ValueError("Bitmap: wrap must be 'clamp' or 'repeat' (got %r)" % (wrap,))
+        self.data = data
+        self.wrap = wrap
+
+    @property
+    def resolution(self):
+        """(TW, TH)"""
+        return self.data.shape[1], self.data.shape[0]
+
+    def eval(self, pos, active=True):
+        """the texture at the film positions ``pos`` [2, n] (``hf_bitmap_eval``), 0 on inactive lanes; differentiable in
+        ``pos`` (with the cell held) and in ``data``, in reverse and forward mode"""
+        return _BitmapEvalOp.apply(self.data, pos, _caustic_active(active, pos.shape[1], pos.device), _WRAPS[self.wrap])
+
+
+class _RefractionLightingOp(torch.autograd.Function):
+    """(image, per-sample value, visibility bytes, landing positions) of hf_refract_lighting; backward =
+    hf_refract_lighting_adjoint (gradients of sh_n, p, weight and the texels), jvp = hf_refract_lighting_tangent.  Both
+    read the visibility byte the forward saved and trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, sn, pp, gn, dd, tt, vis, dat, ww=None):
+        """what hf_refract_lighting_adjoint / _tangent start with"""
+        spp, eta, sigma_t, rcv, wrap, act = ctx.misc
+        return (sn.shape[1], spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(),
+                _ptr(act), _ptr(ww), eta, sigma_t, C.byref(rcv), *_bitmap_in(dat, wrap), vis.data_ptr())
+
+    @staticmethod
+    def forward(ctx, sh_n, p, weight, data, shape, nrm, d, t, active, eta, sigma_t, receiver, wrap, spp):
+        sn, pp, gn, dd, tt, ww, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, data))
+        n = sn.shape[1]
+        ctx.misc = (spp, eta, sigma_t, receiver._struct(), wrap, active)
+        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
+        value = torch.empty(n, dtype=torch.float32, device=sn.device)
+        vis = torch.empty(n, dtype=torch.uint8, device=sn.device)
+        pos = torch.empty((2, n), dtype=torch.float32, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_refract_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                                  C.byref(_p3(dd)), tt.data_ptr(), _ptr(active), _ptr(ww), eta, sigma_t,
+                                                  C.byref(ctx.misc[3]), *_bitmap_in(dat, wrap), image.data_ptr(),
+                                                  value.data_ptr(), vis.data_ptr(), _ref(_row_ptrs(pos)),
+                                                  _stream_of(sn.device)))
+        saved = _with_weight(ctx, (sn, pp, gn, dd, tt, vis, dat), ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(vis, pos)
+        return image, value, vis, pos
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dp, dweight, ddata, *_):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
+        dq, df = _detached_f32(dp), _texel_tangent(ddata)   # (held until the call has been enqueued)
+        dimage = torch.empty(sn.shape[1] // max(ctx.misc[0], 1), dtype=torch.float32, device=sn.device)
+        dvalue = torch.empty_like(sn[0])
+        if sn.shape[1]:
+            check(_capi.lib().hf_refract_lighting_tangent(*_RefractionLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
+                                                          _ref(_row_ptrs(dq)), _ptr(dw), _ptr(df), dimage.data_ptr(),
+                                                          dvalue.data_ptr(), _stream_of(sn.device)))
+        return dimage, dvalue, None, None
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_value, _grad_vis, _grad_pos):
+        saved = ctx.saved_tensors
+        sn, dat = saved[0], saved[6]
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
+        gv, gp, gd = _detached_f32(grad_value), torch.empty_like(sn), _texel_grad(ctx, 3, dat)
+        if sn.shape[1]:
+            check(_capi.lib().hf_refract_lighting_adjoint(*_RefractionLightingOp._prefix(ctx, *saved), _ptr(gi), _ptr(gv),
+                                                          C.byref(_p3(gn)), C.byref(_p3(gp)), _ptr(gw), _ptr(gd),
+                                                          _stream_of(sn.device)))
+        return (gn, gp, gw, gd) + (None,) * 10
+
+
+def refraction_lighting(shape, si, ray, receiver, bitmap, eta=1.33, sigma_t=0.0, spp=1, weight=None, active=True,
+                        return_value=False, return_visibility=False, return_position=False):
+    """The refraction view + box-filter film (``hf_refract_lighting``): every sample of the wavefront looks along
+    ``ray.d``, is refracted at ``si.sh_frame.n`` with the relative index ``eta`` (the ``dielectric`` BSDF's transmission
+    lobe in radiance mode), walked against the same terrain up to the ``receiver`` (a ``Receiver``) and, where nothing is
+    in the way, sees the ``bitmap`` (a ``Bitmap`` laid on the receiver) where it lands: the sample's value is
+    ``weight * (1 - F) * eta_ti^2 * exp(-sigma_t * s) * bitmap.eval(pos)`` with ``s`` the length of the transmitted
+    segment.  A transmitted ray that hits the terrain contributes 0 (no second vertex).  Returns the [n // spp] image;
+    with ``return_value`` also the [n] per-sample values, with ``return_visibility`` the [n] uint8 row (1: the receiver
+    is seen) and with ``return_position`` the [2, n] landing positions ((-16, -16) where nothing is seen; detached: their
+    derivatives are ``caustic_lighting``'s).  Differentiable with respect to ``si.sh_frame.n``, ``si.p``, ``weight`` ([n],
+    optional) and ``bitmap.data``, in reverse and forward mode; the masks, the visibility and the cell of the lookup are
+    piecewise constant, ``sigma_t`` is a constant."""
+    shape._check_ray(ray)
+    image, value, vis, pos = _RefractionLightingOp.apply(si.sh_frame.n, si.p, weight, bitmap.data, shape, si.n, ray.d, si.t,
+                                                         _caustic_active(active, len(ray), ray.d.device), float(eta),
+                                                         float(sigma_t), receiver, _WRAPS[bitmap.wrap], int(spp))
+    out = _value_outputs(image, value, vis, return_value, return_visibility)
+    if return_position:
+        out = (out if isinstance(out, tuple) else (out,)) + (pos,)
+    return out
+
+
+def dielectric_lighting(shape, si, ray, envmap, receiver, bitmap, eta=1.33, sigma_t=0.0, spp=1, weight=None, active=True):
+    """Both lobes of a smooth dielectric interface seen from the camera, [n // spp]: ``reflection_lighting(eta)`` (the
+    environment map mirrored at the surface, weighted by F) + ``refraction_lighting(eta)`` (the textured receiver seen
+    through it, weighted by (1 - F) eta_ti^2).  A plain sum of the two rows: no kernel of its own."""
+    return reflection_lighting(shape, si, ray, envmap, eta=eta, spp=spp, weight=weight, active=active) + \
+        refraction_lighting(shape, si, ray, receiver, bitmap, eta=eta, sigma_t=sigma_t, spp=spp, weight=weight, active=active)
+
+
 class _BounceLightingOp(torch.autograd.Function):
     """(image, hit_prim, lit_bits) of hf_bounce_lighting; backward = hf_bounce_lighting_adjoint (gradients of sh_n, weight
     and the heights), jvp = hf_bounce_lighting_tangent.  Both read the record the forward saved and trace nothing."""
