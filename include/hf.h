@@ -1123,6 +1123,97 @@ int hf_refract_lighting_tangent(size_t n, uint32_t spp, const float *const p[3],
                                 const float *const dp[3], const float *dweight, const float *dtex, float *dimage,
                                 float *dvalue, hf_stream_t stream);
 
+/* ---- next row: area-light lighting, soft shadows from a rectangle emitter traced in the kernel ----
+ *
+ * Replaces, for diffuse surfaces under ONE one-sided `area` emitter on a `rectangle` (src/emitters/area.cpp,
+ * src/shapes/rectangle.cpp: a lamp, a softbox, a light panel), the emitter-sampling term of the direct integrator
+ * (direct_reparam.py:150-180: detached emitter sample, MIS weight 1 here, attached BSDF value; diffuse.cpp:135-140)
+ * averaged over K = num_rays points of the lamp per wavefront sample, and the shadow rays it traces.  The direction
+ * towards the lamp, the inverse-square falloff and the lamp's own cosine depend on the hit point, and the shadows have a
+ * penumbra; the terrain is the RECEIVER (a heightfield that carries an emitter is the adapter's business).
+ *   lamp        hf_rect_light_t, HOST memory: the rectangle's to_world as the centre and the images ex, ey of (1, 0, 0)
+ *               and (0, 1, 0) (the rectangle spans [-1, 1]^2); n_l = normalize(ex x ey), A = 4 |ex x ey|
+ *               (rectangle.cpp:104-108, 144-146), both formed in double on the host; radiance: the scalar L.  The lamp
+ *               emits on the side of n_l only (area.cpp:128).
+ *   samples     (s.x, s.y) of draw k of sample i: the TEA stream of hf_sky_* (pair = k, id_i = i or ray_id[i]);
+ *   point       q_k = center + (2 s.x - 1) ex + (2 s.y - 1) ey (rectangle.cpp:152-166): uniform in area, detached;
+ *   geometry    u = q_k - p, r = |u|, w = u / r, c_s = <sh_n, w>, c_l = -<n_l, w>;
+ *   eligible    sample i when t_i is finite and <sh_n_i, -d_i> > 0 (the masks of hf_direct_lighting); draw k of an
+ *               eligible sample is TRACED when c_s > 0, c_l > 0 and r is finite and > 0 -- decided in float32 on the
+ *               signs of <sh_n, u> and <n_l, u> and on r^2;
+ *   shadow ray  Interaction::spawn_ray_to(q_k) (interaction.h:141-147, 161-165): origin o = p + n s (1 + max|p_c|)
+ *               RayEpsilon with n the geometric normal, s = -1 where <n, u> < 0, else 1; direction (q_k - o) / |q_k - o|;
+ *               maxt = |q_k - o| (1 - ShadowEpsilon), ShadowEpsilon = 10 RayEpsilon (math.h:18-22);
+ *   visibility  vis_bits[i], one uint32: bit k is set iff draw k was traced and the any-hit walk found nothing before
+ *               maxt; samples that are not eligible get 0;
+ *   radiance    L_k = radiance without a texture (tex == NULL; TW, TH are then not read); else radiance times the
+ *               bilinear lookup of tex[TH][TW] (float32, row-major, the caller's device buffer) at the texel coordinate
+ *               (s.x TW, s.y TH) by hf_bitmap_eval's rules under HF_WRAP_CLAMP (bitmap.cpp:497-520).  The coordinate is a
+ *               function of the detached draw only: there are no Lx, Ly terms;
+ *   value_i     = weight_i (albedo A / (pi K)) sum_k bit_ik L_k c_s c_l / r^2: albedo/pi * c_s * L / pdf with the
+ *               solid-angle pdf r^2 / (A c_l) (shape.cpp:364-380), averaged;
+ *   image[i / spp] = 1/spp * sum value_i: the box film of hf_direct_lighting, overwritten; n a multiple of spp.
+ * The ray takes float32 quantities (what hf_rect_rays writes); every term of the shading sums -- G = c_s c_l / r^2, its
+ * derivatives -- is formed from the same draw in double (the texture's lookup is float32, hf_bitmap_eval's expression),
+ * the terms are added in double in k order and the sum is rounded once, in the forward, the adjoint and the tangent.
+ * Differentiated with respect to sh_n, p, weight and tex.  HELD: the visibility, the masks, the draw, the lamp.  With
+ * G = c_s c_l / r^2:   dG/dsh_n = w c_l / r^2,   dG/dp = (4 c_s c_l w - c_l sh_n + c_s n_l) / r^3
+ * (a lamp that faces the sample, c_l = 1 and n_l = -w, gives hf_point_lighting's (3 c_s w - sh_n) / r^3).  The silhouette
+ * part of the shadow gradient is hf_reparam_*'s, as in the rows above.
+ * OUT OF SCOPE: a gradient for the lamp's pose or its radiance scalar, importance sampling of the texture or of the solid
+ * angle, RGB, two-sided lamps, MIS with BSDF sampling, several lamps per call (call once per lamp and add the images).
+ * All four entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional,
+ * n >= 2^32, spp == 0 or n % spp != 0, num_rays outside 1..32 (hf_rect_rays: k >= 32), a non-finite field of the lamp, a
+ * non-finite albedo, |ex x ey| == 0, and with tex != NULL: TW == 0, TH == 0 or TW TH >= 2^31.  p, nrm, sh_n, d: 3 device
+ * rows of n floats; t: n.  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+typedef struct hf_rect_light {
+    float center[3], ex[3], ey[3];   /* the rectangle's to_world: the centre, the images of (1, 0, 0) and (0, 1, 0) */
+    float radiance;                  /* scalar L; multiplies the texture if there is one */
+} hf_rect_light_t;                   /* HOST memory, as hf_receiver_t */
+/* the lamp alone, no wavefront: area = A and normal = n_l as the entries below form them, rounded to float (either may be
+ * NULL); refuses what they refuse of a lamp.  Host only, touches no device. */
+int hf_rect_light_geometry(const hf_rect_light_t *light, float *area, float normal[3]);
+/* hf_rect_rays materialises shadow ray k of every sample (out_o, out_d: 3 rows of n floats; out_maxt: n floats, the
+ * finite maxt above for a traced lane; a lane that is not traced gets a zero origin and direction and maxt = -1, a miss):
+ * the two-call sequence hf_rect_rays + hf_ray_test that hf_rect_lighting equals bit for bit.  Takes no field handle. */
+int hf_rect_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                 const float *const d[3], const float *t, uint32_t k, uint32_t seed, const uint32_t *ray_id,
+                 const hf_rect_light_t *light, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                 hf_stream_t stream);
+/* The fused launch (hf_sky_lighting's shape): reads a sample's record once, draws its K points, runs the per-lane any-hit
+ * walk up to maxt for each traced one and writes vis_bits[i] (n uint32, may be NULL = not wanted) and the film; no ray
+ * and no per-ray hit byte goes to memory.  A batch of 64 samples without an eligible one draws nothing.
+ * hf_set_ray_coherence is neither read nor changed.  weight: n floats or NULL (1).  Allocates nothing, never
+ * synchronises the host, capturable. */
+int hf_rect_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                     const float *const sh_n[3], const float *const d[3], const float *t, const float *weight,
+                     uint32_t num_rays, uint32_t seed, const uint32_t *ray_id, const hf_rect_light_t *light, uint32_t TW,
+                     uint32_t TH, const float *tex, float albedo, float *image, uint32_t *vis_bits, hf_stream_t stream);
+/* Reverse mode with respect to sh_n, p, weight and tex.  Traces nothing: the points are drawn again and vis_bits (as
+ * hf_rect_lighting wrote it) is read.  With g = grad_image[i / spp] / spp and c = albedo A / (pi K):
+ *   grad_sh_n[i] = g weight_i c sum_k bit_ik L_k dG/dsh_n,   grad_p[i] = g weight_i c sum_k bit_ik L_k dG/dp,
+ *   grad_weight[i] = g c sum_k bit_ik L_k G
+ * overwritten, exact zeros for samples that are not eligible; sums in k order, no atomics: bitwise the same from launch to
+ * launch.  grad_tex[TH][TW] += g weight_i c radiance G b_j on the four texels of every visible draw: float atomics,
+ * ACCUMULATED into (ignored without a texture).  grad_sh_n, grad_p (3 rows each), grad_weight and grad_tex may each be
+ * NULL (not wanted).  Takes no field handle. */
+int hf_rect_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                             const float *const d[3], const float *t, const float *weight, uint32_t num_rays,
+                             uint32_t seed, const uint32_t *ray_id, const hf_rect_light_t *light, uint32_t TW, uint32_t TH,
+                             const float *tex, float albedo, const uint32_t *vis_bits, const float *grad_image,
+                             float *const grad_sh_n[3], float *const grad_p[3], float *grad_weight, float *grad_tex,
+                             hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dsh_n, dp (3 rows of n floats each), dweight (n) and dtex
+ * ([TH][TW]; ignored without a texture), each may be NULL (zero); dimage (n / spp) is overwritten.  No atomics for any
+ * spp (a power of two <= 64: the film's shuffle tree; otherwise one lane adds the samples of a pixel in order): bitwise
+ * the same from launch to launch.  Takes no field handle. */
+int hf_rect_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                             const float *const d[3], const float *t, const float *weight, uint32_t num_rays,
+                             uint32_t seed, const uint32_t *ray_id, const hf_rect_light_t *light, uint32_t TW, uint32_t TH,
+                             const float *tex, float albedo, const uint32_t *vis_bits, const float *const dsh_n[3],
+                             const float *const dp[3], const float *dweight, const float *dtex, float *dimage,
+                             hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional

@@ -3,8 +3,8 @@ reference's Shape plugin interface over the C ABI of libhf.so (include/hf.h)."""
 from . import build, workload  # noqa: F401
 from ._capi import HfError  # noqa: F401
 from .shape import (Adam, Bitmap, DirectionSample3f, Envmap, Frame3f, Heightfield, LargeSteps, ParamFlags,  # noqa: F401
-                    PositionSample3f, PreliminaryIntersection3f, Ray3f, RayFlags, Receiver, SurfaceInteraction3f, allreduce_gradient,
+                    PositionSample3f, PreliminaryIntersection3f, Ray3f, RayFlags, Receiver, RectLight, SurfaceInteraction3f, allreduce_gradient,
                     bounce_lighting, bounce_rays, caustic_film, caustic_filter_mass, caustic_lighting, caustic_rays,
                     dielectric_lighting, direct_lighting, envmap_lighting, envmap_rays, film_gaussian, glossy_lighting, glossy_rays,
-                    point_lighting, reflection_lighting, reflection_rays, refraction_lighting, reparameterize_ray, reparameterize_ray_adjoint, reparameterize_ray_tangent,
+                    point_lighting, rect_lighting, rect_rays, reflection_lighting, reflection_rays, refraction_lighting, reparameterize_ray, reparameterize_ray_adjoint, reparameterize_ray_tangent,
                     sky_lighting, sky_rays)

@@ -67,6 +67,15 @@ HF_WRAP_CLAMP, HF_WRAP_REPEAT = 0, 1
 _bitmap_in = [C.c_uint32, C.c_uint32, _fp, C.c_int]  # TW, TH, tex, wrap
 _refract_mid = [_fp, C.c_float, C.c_float, C.POINTER(hf_receiver_t), *_bitmap_in]  # weight, eta, sigma_t, receiver, ...
 
+
+class hf_rect_light_t(C.Structure):
+    _fields_ = [("center", C.c_float * 3), ("ex", C.c_float * 3), ("ey", C.c_float * 3), ("radiance", C.c_float)]
+
+
+# weight, num_rays, seed, ray_id, light, TW, TH, tex, albedo
+_rect_mid = [_fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(hf_rect_light_t), C.c_uint32, C.c_uint32, _fp, C.c_float]
+_rect_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp]  # n, spp, p, sh_n, d, t
+
 SYMBOLS = {
     "hf_create": (C.c_int, [C.POINTER(hf_desc_t), C.POINTER(C.c_void_p)]),
     "hf_destroy": (C.c_int, [C.c_void_p]),
@@ -200,6 +209,16 @@ SYMBOLS = {
                                               C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_void_p]),
     "hf_refract_lighting_tangent": (C.c_int, [C.c_size_t, C.c_uint32, *_caustic_in, *_refract_mid, _fp, C.POINTER(_fp * 3),
                                               C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, C.c_void_p]),
+    "hf_rect_light_geometry": (C.c_int, [C.POINTER(hf_rect_light_t), C.POINTER(C.c_float), C.POINTER(C.c_float * 3)]),
+    "hf_rect_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
+                               C.c_uint32, C.c_uint32, _fp, C.POINTER(hf_rect_light_t), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                               _fp, C.c_void_p]),
+    "hf_rect_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                   C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, *_rect_mid, _fp, _fp, C.c_void_p]),
+    "hf_rect_lighting_adjoint": (C.c_int, [*_rect_in, *_rect_mid, _fp, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp,
+                                           C.c_void_p]),
+    "hf_rect_lighting_tangent": (C.c_int, [*_rect_in, *_rect_mid, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp,
+                                           C.c_void_p]),
     "hf_envmap_table_floats":(C.c_size_t, [C.c_uint32, C.c_uint32]),
     "hf_envmap_build_table": (C.c_int, [C.c_uint32, C.c_uint32, _fp, C.c_float, _fp, C.c_void_p]),
     "hf_envmap_sample_direction": (C.c_int, [C.c_size_t, C.POINTER(_fp * 2), C.c_uint32, C.c_uint32, _fp, _fp,

@@ -1518,6 +1518,117 @@ extern "C" int hf_refract_lighting_tangent(size_t n, uint32_t spp, const float *
     return light_launch(hf_launch_refract, 2, a, stream);
 }
 
+// ---- area-light lighting: a rectangle emitter, the shadow rays towards it traced in the kernel ----
+// the lamp's checks and what follows from it alone: n_l = normalize(ex x ey) and A = 4 |ex x ey|, in double
+static int rect_lamp(const char *who, const hf_rect_light_t *light, double nl[3], double *area) {
+    if (!light) return fail(HF_EINVAL, "%s: NULL argument", who);
+    for (int c = 0; c < 3; ++c)
+        if (!isfinite(light->center[c]) || !isfinite(light->ex[c]) || !isfinite(light->ey[c]))
+            return fail(HF_EINVAL, "%s: the light's center, ex and ey must be finite", who);
+    if (!isfinite(light->radiance)) return fail(HF_EINVAL, "%s: the light's radiance must be finite", who);
+    const double ex[3] = { light->ex[0], light->ex[1], light->ex[2] }, ey[3] = { light->ey[0], light->ey[1], light->ey[2] };
+    const double cr[3] = { ex[1] * ey[2] - ex[2] * ey[1], ex[2] * ey[0] - ex[0] * ey[2], ex[0] * ey[1] - ex[1] * ey[0] };
+    const double len = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
+    if (!(len > 0.0)) return fail(HF_EINVAL, "%s: the light's ex and ey span no area (|ex x ey| == 0)", who);
+    for (int c = 0; c < 3; ++c) nl[c] = cr[c] / len;
+    *area = 4.0 * len;
+    return HF_OK;
+}
+
+extern "C" int hf_rect_light_geometry(const hf_rect_light_t *light, float *area, float normal[3]) {
+    const char *fn = "hf_rect_light_geometry";
+    double nl[3], A;
+    const int rc = rect_lamp(fn, light, nl, &A);
+    if (rc != HF_OK) return rc;
+    if (area) *area = (float) A;
+    for (int c = 0; c < 3 && normal; ++c) normal[c] = (float) nl[c];
+    return HF_OK;
+}
+
+// What the four hf_rect_* entries share (hf_rect_rays passes spp 1, num_rays k + 1, no texture, albedo 1): the
+// wavefront, the lamp, its texture (tex NULL: none, TW and TH are not read) and the scale of the sum
+static int rect_args(const char *who, size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                     const float *const d[3], const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                     const uint32_t *ray_id, const hf_rect_light_t *light, uint32_t TW, uint32_t TH, const float *tex,
+                     float albedo, hf_rect_args &a) {
+    a = {};
+    int rc = light_args(who, "points of the light", n, spp, sh_n, d, t, weight, num_rays, seed, ray_id, !all3(p) || !light, a);
+    if (rc != HF_OK) return rc;
+    double A;
+    if ((rc = rect_lamp(who, light, a.nld, &A))) return rc;
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    if (tex && (rc = bitmap_texture(who, TW, TH, tex, HF_WRAP_CLAMP, a))) return rc;
+    for (int c = 0; c < 3; ++c) {
+        a.p[c] = p[c]; a.center[c] = light->center[c]; a.ex[c] = light->ex[c]; a.ey[c] = light->ey[c]; a.nl[c] = (float) a.nld[c];
+    }
+    a.scale = (float) ((double) albedo * (double) light->radiance * A / (3.141592653589793 * (double) num_rays));
+    return HF_OK;
+}
+
+extern "C" int hf_rect_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                            const float *const d[3], const float *t, uint32_t k, uint32_t seed, const uint32_t *ray_id,
+                            const hf_rect_light_t *light, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                            hf_stream_t stream) {
+    const char *fn = "hf_rect_rays";
+    hf_rect_args a;
+    if (k >= 32) return fail(HF_EINVAL, "%s: point k must be below 32 (got %u)", fn, k);
+    int rc = rect_args(fn, n, 1, p, sh_n, d, t, nullptr, k + 1, seed, ray_id, light, 0, 0, nullptr, 1.f, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
+    a.k = k;
+    return light_launch(hf_launch_rect, 3, a, stream);
+}
+
+extern "C" int hf_rect_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                const float *t, const float *weight, uint32_t num_rays, uint32_t seed,
+                                const uint32_t *ray_id, const hf_rect_light_t *light, uint32_t TW, uint32_t TH,
+                                const float *tex, float albedo, float *image, uint32_t *vis_bits, hf_stream_t stream) {
+    const char *fn = "hf_rect_lighting";
+    hf_rect_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = rect_args(fn, n, spp, p, sh_n, d, t, weight, num_rays, seed, ray_id, light, TW, TH, tex, albedo, a);
+    if (rc != HF_OK || (rc = light_forward_out(fn, p, nrm, image, a))) return rc;
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.vis_bits = vis_bits;
+    return light_launch(hf_launch_rect, 0, a, stream);
+}
+
+extern "C" int hf_rect_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                        const float *const d[3], const float *t, const float *weight, uint32_t num_rays,
+                                        uint32_t seed, const uint32_t *ray_id, const hf_rect_light_t *light, uint32_t TW,
+                                        uint32_t TH, const float *tex, float albedo, const uint32_t *vis_bits,
+                                        const float *grad_image, float *const grad_sh_n[3], float *const grad_p[3],
+                                        float *grad_weight, float *grad_tex, hf_stream_t stream) {
+    const char *fn = "hf_rect_lighting_adjoint";
+    hf_rect_args a;
+    const int rc = rect_args(fn, n, spp, p, sh_n, d, t, weight, num_rays, seed, ray_id, light, TW, TH, tex, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits || !grad_image) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
+    if (grad_p && !all3(grad_p)) return fail(HF_EINVAL, "%s: NULL grad_p component array", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.gimg = grad_image; a.gw = grad_weight; a.gdata = grad_tex;
+    for (int c = 0; c < 3; ++c) { a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr; a.gp[c] = grad_p ? grad_p[c] : nullptr; }
+    return light_launch(hf_launch_rect, 1, a, stream);
+}
+
+extern "C" int hf_rect_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                        const float *const d[3], const float *t, const float *weight, uint32_t num_rays,
+                                        uint32_t seed, const uint32_t *ray_id, const hf_rect_light_t *light, uint32_t TW,
+                                        uint32_t TH, const float *tex, float albedo, const uint32_t *vis_bits,
+                                        const float *const dsh_n[3], const float *const dp[3], const float *dweight,
+                                        const float *dtex, float *dimage, hf_stream_t stream) {
+    const char *fn = "hf_rect_lighting_tangent";
+    hf_rect_args a;
+    int rc = rect_args(fn, n, spp, p, sh_n, d, t, weight, num_rays, seed, ray_id, light, TW, TH, tex, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (dp && !all3(dp)) return fail(HF_EINVAL, "%s: NULL dp component array", fn);
+    if ((rc = light_tangent_io(fn, !vis_bits, dsh_n, dweight, dimage, a))) return rc;
+    a.vis_bits = const_cast<uint32_t *>(vis_bits); a.ddata = dtex;
+    for (int c = 0; c < 3; ++c) a.dp[c] = dp ? dp[c] : nullptr;
+    return light_launch(hf_launch_rect, 2, a, stream);
+}
+
 // ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----
 // What every entry that reads a map shares, the reflection rows' too: the checks of the map (A: a block with W, H, data
 // and rot, zeroed by the caller), in two pieces because the entries check other things between them: the texels ...

@@ -3729,12 +3729,13 @@ __device__ __forceinline__ float sky_offset(v3 p) {
 __device__ __forceinline__ v3 sky_origin(v3 p, v3 gn, float mag, v3 w) {
     return fma3(gn, dot3(gn, w) < 0.f ? -mag : mag, p);
 }
-// a materialised ray; maxt = -1: the fused kernel does not trace it
+// a materialised ray; maxt = -1: the fused kernel does not trace it (`maxt`: where a traced ray ends, for the row whose
+// rays end inside the scene)
 template <class A>
-__device__ __forceinline__ void light_store_ray(const A &a, size_t i, v3 o, v3 d, bool traced) {
+__device__ __forceinline__ void light_store_ray(const A &a, size_t i, v3 o, v3 d, bool traced, float maxt = __builtin_inff()) {
     a.out_o[0][i] = o.x; a.out_o[1][i] = o.y; a.out_o[2][i] = o.z;
     a.out_d[0][i] = d.x; a.out_d[1][i] = d.y; a.out_d[2][i] = d.z;
-    a.out_maxt[i] = traced ? __builtin_inff() : -1.f;
+    a.out_maxt[i] = traced ? maxt : -1.f;
 }
 // the same for a row whose untraced lanes get a zero origin and direction: spawn_ray(w) where the fused kernel walks it
 template <class A>
@@ -6521,6 +6522,232 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_refract_tangent_kernel(hf_refract
 void hf_launch_refract(int mode, const hf_refract_args &a, hipStream_t stream) {
     launch_light(mode, a, 1u, stream, hf_refract_kernel, hf_refract_adjoint_kernel, hf_refract_tangent_kernel<false>,
                  hf_refract_tangent_kernel<true>, (void (*)(hf_refract_args)) nullptr);
+}
+
+// ---------------------------------------------------------------------------------
+// Area-light lighting (include/hf.h hf_rect_*): diffuse surface under a one-sided `area` emitter on a `rectangle`, the
+// K = num_rays points of the lamp of every wavefront sample drawn (uniform in area, rectangle.cpp:152-166), their
+// shadow rays (Interaction::spawn_ray_to, a FINITE maxt) traced (any hit, per lane) and reduced in ONE launch:
+// hf_sky_kernel's mapping.  The direction, the falloff and the lamp's cosine depend on the hit point:
+//   value = weight (albedo A / (pi K)) sum_k bit_k L_k c_s c_l / r^2.
+// The row's own text is the lamp's point, the ray towards it and G = c_s c_l / r^2 with its derivatives; the sample
+// stream, the origin, the walk, the film, the outputs, the tangent shell and the launch are the lighting rows' shared
+// functions, the texture lookup and its scatter / gather the refraction view's (bitmap_cell).
+// (P below: a pointer to hf_rect_args, in the kernarg segment or not)
+// ---------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) hf_rect_args *hf_rect_kargs;
+
+// The shadow ray of a draw, in float32: q = center + (2 s.x - 1) ex + (2 s.y - 1) ey, u = q - p, the origin
+// offset_p(u), the direction (q - o) / |q - o| and maxt = |q - o| (1 - ShadowEpsilon), ShadowEpsilon = 10 RayEpsilon
+// (math.h:22).  front: <sh_n, u> > 0, <n_l, u> < 0 (the signs of c_s and c_l) and r finite and > 0
+struct hf_rect_ray { v3 o, w; float maxt; bool front; };
+template <class P>
+__device__ __forceinline__ hf_rect_ray rect_ray(P a, v3 p, v3 gn, v3 sn, float mag, float sx, float sy) {
+    hf_rect_ray r;
+    const float su = __builtin_fmaf(2.f, sx, -1.f), sv = __builtin_fmaf(2.f, sy, -1.f);
+    const v3 q = mk3(__builtin_fmaf(sv, a->ey[0], __builtin_fmaf(su, a->ex[0], a->center[0])),
+                     __builtin_fmaf(sv, a->ey[1], __builtin_fmaf(su, a->ex[1], a->center[1])),
+                     __builtin_fmaf(sv, a->ey[2], __builtin_fmaf(su, a->ex[2], a->center[2])));
+    const v3 u = q - p;
+    const float r2 = dot3(u, u);
+    r.front = dot3(sn, u) > 0.f && dot3(mk3(a->nl[0], a->nl[1], a->nl[2]), u) < 0.f && r2 > 0.f && r2 < __builtin_inff();
+    r.o = sky_origin(p, gn, mag, u);
+    const v3 dv = q - r.o;
+    const float dist = __builtin_sqrtf(dot3(dv, dv));
+    r.w = dv * (1.0f / dist);
+    r.maxt = dist * (1.f - 8.940696716308594e-04f);
+    return r;
+}
+
+// The same draw in double, for the SHADING sums (sky_dir_f64's reason: c_s and c_l graze, and u is a difference): u = q - p
+// and the unnormalised cosines cs = <sh_n, u>, cl = -<n_l, u>, so that G = c_s c_l / r^2 = cs cl / r2^2 without a root
+struct hf_rect_geom { hf_d3 u; double r2, cs, cl; };
+template <class P>
+__device__ __forceinline__ hf_rect_geom rect_geom_f64(P a, v3 p, v3 sn, float sx, float sy) {
+    hf_rect_geom g;
+    const double su = 2.0 * (double) sx - 1.0, sv = 2.0 * (double) sy - 1.0;
+    g.u.x = ((double) a->center[0] + su * (double) a->ex[0] + sv * (double) a->ey[0]) - (double) p.x;
+    g.u.y = ((double) a->center[1] + su * (double) a->ex[1] + sv * (double) a->ey[1]) - (double) p.y;
+    g.u.z = ((double) a->center[2] + su * (double) a->ex[2] + sv * (double) a->ey[2]) - (double) p.z;
+    g.r2 = g.u.x * g.u.x + g.u.y * g.u.y + g.u.z * g.u.z;
+    g.cs = sky_dot_f64(sn, g.u);
+    g.cl = -(a->nld[0] * g.u.x + a->nld[1] * g.u.y + a->nld[2] * g.u.z);
+    return g;
+}
+// the texel coordinate of a draw: (s.x TW, s.y TH), a function of the detached draw alone
+template <class P>
+__device__ __forceinline__ hf_bitmap_cell rect_cell(P a, float sx, float sy) {
+    return bitmap_cell(a, sx * (float) a->TW, sy * (float) a->TH);
+}
+
+#ifndef HF_RECT_WAVES
+#define HF_RECT_WAVES 6 // resident waves per SIMD (the siblings')
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_RECT_WAVES) void hf_rect_kernel(hf_rect_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    const v3 sn = mk3(a.sh_n[0][ii], a.sh_n[1][ii], a.sh_n[2][ii]);
+    bool elig;
+    {
+        const v3 d = mk3(a.d[0][ii], a.d[1][ii], a.d[2][ii]);
+        elig = in && sky_eligible(a.t[ii], sn, d);
+    }
+    double acc = 0.0;   // sum over the visible points of L_k c_s c_l / r^2 (rect_geom_f64), in k order, rounded once below
+    uint32_t bits = 0u; // bit k: point k was traced and is unoccluded
+    if (__ballot(elig) != 0ull) { // wave-uniform: a batch without an eligible sample draws nothing
+        const v3 p = mk3(a.p[0][ii], a.p[1][ii], a.p[2][ii]);
+        const v3 gn = mk3(a.nrm[0][ii], a.nrm[1][ii], a.nrm[2][ii]);
+        const uint32_t id = a.ray_id ? a.ray_id[ii] : ii;
+        const float mag = sky_offset(p);
+        // (launch constants of the loop, the lamp among them, are read from the kernarg segment where they are used)
+        hf_rect_kargs ka = (hf_rect_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll 1
+        for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+            asm volatile("" : "+s"(ka)); // opaque per point: the kernarg loads stay inside the loop
+            // the term that is added first, in double, and finished before the ray is begun (hf_sky_kernel's order: its
+            // other doubles and the texels are dead when setup_ray's registers fill, this one is held across the walk)
+            v3 snd = sn, pd = p; // (opaque: their conversions to double are otherwise hoisted out of the loop)
+            asm volatile("" : "+v"(snd.x), "+v"(snd.y), "+v"(snd.z), "+v"(pd.x), "+v"(pd.y), "+v"(pd.z));
+            float sx, sy;
+            sky_sample(ka->seed, k, id, sx, sy);
+            double co;
+            {
+                const hf_rect_geom g = rect_geom_f64(ka, pd, snd, sx, sy);
+                co = (g.cs * g.cl) / (g.r2 * g.r2);
+                const float *tex = ka->tex;
+                if (tex) co *= (double) rect_cell(ka, sx, sy).value(tex); // (wave-uniform)
+            }
+            asm volatile("" : "+v"(co), "+v"(sx), "+v"(sy));
+            const hf_rect_ray r = rect_ray(ka, p, gn, sn, mag, sx, sy);
+            const bool traced = elig && r.front;
+            hf_hit best;
+            light_walk<true>(&ka->f, f, r.o, r.w, r.maxt, traced, best);
+            if (traced && !best.hit) { bits |= 1u << k; acc += co; }
+            if (k + 1u >= ka->num_rays) break;
+        }
+    }
+    // (the output pointers: loaded here, not before the walk)
+    hf_rect_kargs ko = (hf_rect_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    float c = 0.f;
+    if (elig) { // (eligible: in range)
+        const float *weight = ko->weight;
+        c = ko->scale * (float) acc;
+        if (weight) c *= weight[i];
+    }
+    uint32_t *vis_bits = ko->vis_bits;
+    if (in && vis_bits) vis_bits[i] = bits;
+    const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+    film_pixel(ko->image, c, 0u, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+}
+
+// shadow ray a.k of every sample, materialised: what hf_rect_kernel traces for that point, bit for bit (an untraced
+// lane: a zero origin and direction, maxt = -1)
+__global__ __launch_bounds__(HF_BLOCK) void hf_rect_rays_kernel(hf_rect_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 sn;
+    const bool elig = light_sample(a, i, sn);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    float sx, sy;
+    sky_sample(a.seed, a.k, light_id(a, i), sx, sy);
+    const hf_rect_ray r = rect_ray(&a, p, gn, sn, sky_offset(p), sx, sy);
+    const bool traced = elig && r.front;
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    light_store_ray(a, i, traced ? r.o : z, traced ? r.w : z, traced, r.maxt);
+}
+
+// What the two derivative kernels form again of a visible point: the cell of its texel coordinate, L (1 without a
+// texture), G and its derivatives with the draw, the masks and the lamp held:
+//   dG/dsh_n = w c_l / r^2 = u cl / r2^2,   dG/dp = (4 c_s c_l w - c_l sh_n + c_s n_l) / r^3 = 4 cs cl u / r2^3 + (cs n_l - cl sh_n) / r2^2
+struct hf_rect_shade {
+    hf_bitmap_cell e;
+    double L, G;
+    hf_d3 Gn, Gp;
+};
+__device__ __forceinline__ hf_rect_shade rect_shade(const hf_rect_args &a, v3 p, v3 sn, uint32_t k, uint32_t id) {
+    hf_rect_shade s;
+    float sx, sy;
+    sky_sample(a.seed, k, id, sx, sy);
+    const hf_rect_geom g = rect_geom_f64(&a, p, sn, sx, sy);
+    const double i4 = 1.0 / (g.r2 * g.r2), cc = g.cs * g.cl;
+    s.G = cc * i4;
+    const double gu = 4.0 * cc * i4 / g.r2;
+    s.Gn = hf_d3{ g.u.x * (g.cl * i4), g.u.y * (g.cl * i4), g.u.z * (g.cl * i4) };
+    s.Gp = hf_d3{ gu * g.u.x + (g.cs * a.nld[0] - g.cl * (double) sn.x) * i4, gu * g.u.y + (g.cs * a.nld[1] - g.cl * (double) sn.y) * i4,
+                  gu * g.u.z + (g.cs * a.nld[2] - g.cl * (double) sn.z) * i4 };
+    s.L = 1.0;
+    if (a.tex) {
+        s.e = rect_cell(&a, sx, sy);
+        s.L = (double) s.e.value(a.tex);
+    }
+    return s;
+}
+
+// Reverse mode of hf_rect_kernel with respect to sh_n, p, weight and the texels: nothing is traced, the points are drawn
+// again and the visibility word read.  grad_sh_n, grad_p, grad_weight: sums in k order, in double, overwritten, no
+// atomics; grad_tex: four float atomics per visible point
+__global__ __launch_bounds__(HF_BLOCK) void hf_rect_adjoint_kernel(hf_rect_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 sn, gn = mk3(0.f, 0.f, 0.f), gp = gn;
+    float gw = 0.f;
+    if (light_sample(a, i, sn)) {
+        const uint32_t bits = a.vis_bits[i], id = light_id(a, i);
+        const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+        const float c = (a.gimg[i / a.spp] * (1.0f / (float) a.spp)) * a.scale; // dL/d(sum) but for the weight
+        const float cw = a.weight ? c * a.weight[i] : c;
+        hf_d3 sgn = { 0.0, 0.0, 0.0 }, sgp = { 0.0, 0.0, 0.0 };
+        double sc = 0.0;
+        for (uint32_t k = 0; k < a.num_rays; ++k) {
+            if ((bits >> k) & 1u) {
+                const hf_rect_shade s = rect_shade(a, p, sn, k, id);
+                sgn.x += s.L * s.Gn.x; sgn.y += s.L * s.Gn.y; sgn.z += s.L * s.Gn.z;
+                sgp.x += s.L * s.Gp.x; sgp.y += s.L * s.Gp.y; sgp.z += s.L * s.Gp.z;
+                sc += s.L * s.G;
+                if (a.tex && a.gdata) s.e.scatter(a.gdata, (float) ((double) cw * s.G));
+            }
+        }
+        gn = mk3((float) sgn.x, (float) sgn.y, (float) sgn.z) * cw;
+        gp = mk3((float) sgp.x, (float) sgp.y, (float) sgp.z) * cw;
+        gw = c * (float) sc;
+    }
+    light_store_grads(a, i, gn, gp, gw);
+}
+
+// forward mode, the transpose of the above: the tangent of sample i's value for tangents dn of sh_n, dp of p, dw of
+// weight and dtex of the texels (NULL: zero)
+__device__ __forceinline__ float rect_tangent_value(const hf_rect_args &a, size_t i) {
+    v3 sn;
+    if (!light_sample(a, i, sn)) return 0.f;
+    const uint32_t bits = a.vis_bits[i], id = light_id(a, i);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const v3 dp = a.dp[0] ? mk3(a.dp[0][i], a.dp[1][i], a.dp[2][i]) : mk3(0.f, 0.f, 0.f);
+    double sd = 0.0, sc = 0.0;
+    for (uint32_t k = 0; k < a.num_rays; ++k) {
+        if ((bits >> k) & 1u) {
+            const hf_rect_shade s = rect_shade(a, p, sn, k, id);
+            double dG = s.L * (sky_dot_f64(dn, s.Gn) + sky_dot_f64(dp, s.Gp));
+            if (a.tex && a.ddata) dG += (double) s.e.value(a.ddata) * s.G;
+            sd += dG;
+            sc += s.L * s.G;
+        }
+    }
+    return (float) ((double) a.scale * ((double) (a.weight ? a.weight[i] : 1.f) * sd + (double) (a.dw ? a.dw[i] : 0.f) * sc));
+}
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_rect_tangent_kernel(hf_rect_args a) {
+    light_tangent_image<PIXEL, hf_rect_args, rect_tangent_value>(a, nullptr);
+}
+
+void hf_launch_rect(int mode, const hf_rect_args &a, hipStream_t stream) {
+    launch_light(mode, a, 1u, stream, hf_rect_kernel, hf_rect_adjoint_kernel, hf_rect_tangent_kernel<false>,
+                 hf_rect_tangent_kernel<true>, hf_rect_rays_kernel);
 }
 
 // ---------------------------------------------------------------------------------

@@ -212,6 +212,31 @@ struct hf_bitmap_args {
     float *gpos[2], *gtex;                   // adjoint outputs (NULL: not wanted); gtex is accumulated
 };
 void hf_launch_bitmap(bool adjoint, const hf_bitmap_args &a, hipStream_t stream);
+// ---- area-light lighting (hf_rect_rays, hf_rect_lighting / _adjoint / _tangent): the one argument of its four kernels;
+// TW, TH, wrap as in hf_bitmap_args (bitmap_cell reads either) ----
+struct hf_rect_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, num_rays, seed, k;         // k: hf_rect_rays' draw
+    uint32_t TW, TH;                         // 0, 0 without a texture
+    int32_t wrap;                            // HF_WRAP_CLAMP (the lamp's texture has no other)
+    float scale;                             // albedo radiance A / (pi num_rays), A = 4 |ex x ey|, rounded once on the host
+    float center[3], ex[3], ey[3], nl[3];    // the lamp; nl = normalize(ex x ey), for the ray's masks
+    double nld[3];                           // the same normal before its rounding to float, for the shading sums
+    const float *tex;                        // [TH][TW], NULL: the lamp is uniform
+    const float *p[3], *nrm[3];              // si.p (every mode), si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight;
+    const uint32_t *ray_id;                  // optional: the id of sample i in the sample streams (NULL: i)
+    float *image;                            // forward: image; tangent: dimage
+    uint32_t *vis_bits;                      // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    const float *gimg;                       // adjoint input
+    float *gn[3], *gp[3], *gw, *gdata;       // adjoint outputs (NULL: not wanted); gdata (the texels') is accumulated
+    const float *dn[3], *dp[3], *dw, *ddata; // tangent inputs (NULL: zero); ddata: the texels'
+};
+// mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is hf_launch_sky's: the per-lane any-hit walk,
+// no work counter, no scratch block
+void hf_launch_rect(int mode, const hf_rect_args &a, hipStream_t stream);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----

@@ -2257,6 +2257,136 @@ def dielectric_lighting(shape, si, ray, envmap, receiver, bitmap, eta=1.33, sigm
         refraction_lighting(shape, si, ray, receiver, bitmap, eta=eta, sigma_t=sigma_t, spp=spp, weight=weight, active=active)
 
 
+class RectLight:
+    """A one-sided ``area`` emitter on a ``rectangle`` (``hf_rect_light_t``): the rectangle [-1, 1]^2 under a to_world
+    whose translation is ``center`` and whose images of (1, 0, 0) and (0, 1, 0) are ``ex`` and ``ey``; it emits the scalar
+    ``radiance`` on the side of ``normalize(ex x ey)``.  ``texture``: a ``Bitmap`` or a [TH, TW] float32 device tensor
+    that multiplies the radiance (bilinear, clamped; texel (0, 0) at the corner ``center - ex - ey``), kept by reference
+    -- it may require grad."""
+
+    def __init__(self, center, ex, ey, radiance=1.0, texture=None):
+        self.center, self.ex, self.ey = (tuple(float(c) for c in v) for v in (center, ex, ey))
+        assert all(len(v) == 3 for v in (self.center, self.ex, self.ey)), "center, ex, ey: three components each"
+        self.radiance = float(radiance)
+        if isinstance(texture, Bitmap):
+            if texture.wrap != "clamp":
+                raise ValueError("RectLight: the texture of a lamp is clamped")
+            texture = texture.data
+        if texture is not None and (not isinstance(texture, torch.Tensor) or texture.dtype != torch.float32 or
+                                    texture.dim() != 2 or texture.shape[0] < 1 or texture.shape[1] < 1):
+            raise ValueError("RectLight: texture must be a Bitmap or a float32 tensor [TH >= 1, TW >= 1]")
+        self.texture = texture
+
+    @staticmethod
+    def from_to_world(M, radiance=1.0, texture=None):
+        """the lamp of a rectangle with the 3 x 4 (or 4 x 4) to_world ``M``"""
+        M = torch.as_tensor(M, dtype=torch.float64).cpu()
+        return RectLight(M[:3, 3].tolist(), M[:3, 0].tolist(), M[:3, 1].tolist(), radiance, texture)
+
+    def _struct(self):
+        return _capi.hf_rect_light_t((C.c_float * 3)(*self.center), (C.c_float * 3)(*self.ex), (C.c_float * 3)(*self.ey),
+                                     self.radiance)
+
+    def geometry(self):
+        """(area, unit normal) as the entries form them (``hf_rect_light_geometry``)"""
+        area, nl = C.c_float(), (C.c_float * 3)()
+        check(_capi.lib().hf_rect_light_geometry(C.byref(self._struct()), C.byref(area), C.byref(nl)))
+        return area.value, tuple(nl)
+
+
+def _rect_tex(dat):
+    """the texture's C arguments: TW, TH, tex (no texture: 0, 0, NULL)"""
+    return (dat.shape[1], dat.shape[0], dat.data_ptr()) if dat is not None else (0, 0, None)
+
+
+class _RectLightingOp(torch.autograd.Function):
+    """(image, visibility words) of hf_rect_lighting; backward = hf_rect_lighting_adjoint (gradients of sh_n, p, weight
+    and the texels), jvp = hf_rect_lighting_tangent.  Both read the visibility word the forward saved and trace nothing."""
+
+    @staticmethod
+    def _prefix(ctx, sn, pp, dd, tt, vis, *rest):
+        """what hf_rect_lighting_adjoint / _tangent start with (rest: the texels if the lamp has them, then the weight)"""
+        spp, num_rays, seed, rid, lamp, albedo = ctx.misc
+        dat = rest[0] if ctx.textured else None
+        ww = rest[-1] if ctx.weighted else None
+        return (sn.shape[1], spp, C.byref(_p3(pp)), C.byref(_p3(sn)), C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed,
+                _ptr(rid), C.byref(lamp), *_rect_tex(dat), albedo, vis.data_ptr())
+
+    @staticmethod
+    def forward(ctx, sh_n, p, weight, texture, shape, nrm, d, t, lamp, albedo, spp, num_rays, seed, ray_index):
+        sn, pp, gn, dd, tt, ww, dat = map(_detached_f32, (sh_n, p, nrm, d, t, weight, texture))
+        n = sn.shape[1]
+        ctx.misc = (spp, num_rays, seed, ray_index, lamp, albedo)
+        ctx.textured = dat is not None
+        image = torch.empty(n // max(spp, 1), dtype=torch.float32, device=sn.device)
+        vis = torch.empty(n, dtype=torch.int32, device=sn.device)
+        if n:  # (an empty wavefront has no rows to point to)
+            check(_capi.lib().hf_rect_lighting(shape._h, n, spp, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)),
+                                               C.byref(_p3(dd)), tt.data_ptr(), _ptr(ww), num_rays, seed, _ptr(ray_index),
+                                               C.byref(lamp), *_rect_tex(dat), albedo, image.data_ptr(), vis.data_ptr(),
+                                               _stream_of(sn.device)))
+        saved = _with_weight(ctx, (sn, pp, dd, tt, vis) + ((dat,) if ctx.textured else ()), ww)
+        ctx.save_for_backward(*saved)
+        ctx.save_for_forward(*saved)
+        ctx.mark_non_differentiable(vis)
+        return image, vis
+
+    @staticmethod
+    def jvp(ctx, dsh_n, dp, dweight, dtexture, *_):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        dn, dw = _weighted_tangents(ctx, dsh_n, dweight)
+        dq, df = _detached_f32(dp), _texel_tangent(dtexture if ctx.textured else None)  # (held until the call has been enqueued)
+        dimage = torch.empty(sn.shape[1] // max(ctx.misc[0], 1), dtype=torch.float32, device=sn.device)
+        if sn.shape[1]:
+            check(_capi.lib().hf_rect_lighting_tangent(*_RectLightingOp._prefix(ctx, *saved), _ref(_row_ptrs(dn)),
+                                                       _ref(_row_ptrs(dq)), _ptr(dw), _ptr(df), dimage.data_ptr(),
+                                                       _stream_of(sn.device)))
+        return dimage, None
+
+    @staticmethod
+    def backward(ctx, grad_image, _grad_vis):
+        saved = ctx.saved_tensors
+        sn = saved[0]
+        gi, gn, gw = _weighted_grads(ctx, sn, grad_image)
+        gp = torch.empty_like(sn)
+        gd = _texel_grad(ctx, 3, saved[5]) if ctx.textured else None
+        if sn.shape[1]:
+            check(_capi.lib().hf_rect_lighting_adjoint(*_RectLightingOp._prefix(ctx, *saved), gi.data_ptr(), C.byref(_p3(gn)),
+                                                       C.byref(_p3(gp)), _ptr(gw), _ptr(gd), _stream_of(sn.device)))
+        return (gn, gp, gw, gd) + (None,) * 10
+
+
+def rect_lighting(shape, si, ray, light, albedo=1.0, spp=1, num_rays=8, seed=0, weight=None, ray_index=None,
+                  return_visibility=False):
+    """Diffuse lighting under a rectangle lamp (``RectLight``; the reference's ``area`` emitter on a ``rectangle``) +
+    box-filter film, soft shadows traced inside the lighting kernel (``hf_rect_lighting``): every sample draws
+    ``num_rays`` (1..32) points of the lamp, uniform in area, from the TEA stream of ``sky_lighting`` (``seed``,
+    ``ray_index``), traces ``si.spawn_ray_to(point)`` for those in front of both the sample and the lamp and averages
+    ``albedo/pi * radiance * c_s * c_l * A / r^2`` over the unoccluded ones.  Returns the [n // spp] image; with
+    ``return_visibility`` also the [n] int32 visibility words (bit k: point k was traced and is seen).  Differentiable
+    with respect to ``si.sh_frame.n``, ``si.p``, ``weight`` ([n], optional) and the lamp's texture, in reverse and forward
+    mode; the visibility, the masks, the draws and the lamp's pose and radiance are held.  Several lamps: one call each."""
+    shape._check_ray(ray)
+    image, vis = _RectLightingOp.apply(si.sh_frame.n, si.p, weight, light.texture, shape, si.n, ray.d, si.t, light._struct(),
+                                       float(albedo), int(spp), int(num_rays), int(seed), _check_ray_index(ray_index, ray))
+    return (image, vis) if return_visibility else image
+
+
+def rect_rays(si, ray, light, k, seed=0, ray_index=None):
+    """Shadow ray ``k`` of every sample of ``rect_lighting`` as a Ray3f (``hf_rect_rays``): what the fused kernel traces
+    for that point of the lamp, bit for bit, ``maxt`` just short of the lamp.  Lanes it does not trace (no hit, seen from
+    behind, the point behind the sample or the sample behind the lamp) get ``maxt = -1``, a miss."""
+    rid = _check_ray_index(ray_index, ray)
+    sn, pp, gn, dd, tt = map(_detached_f32, (si.sh_frame.n, si.p, si.n, ray.d, si.t))
+    n, r = sn.shape[1], _empty_rays(pp)
+    if n:
+        check(_capi.lib().hf_rect_rays(n, C.byref(_p3(pp)), C.byref(_p3(gn)), C.byref(_p3(sn)), C.byref(_p3(dd)),
+                                       tt.data_ptr(), int(k), int(seed), _ptr(rid), C.byref(light._struct()),
+                                       C.byref(_p3(r.o)), C.byref(_p3(r.d)), r.maxt.data_ptr(), _stream_of(pp.device)))
+    return r
+
+
 class _BounceLightingOp(torch.autograd.Function):
     """(image, hit_prim, lit_bits) of hf_bounce_lighting; backward = hf_bounce_lighting_adjoint (gradients of sh_n, weight
     and the heights), jvp = hf_bounce_lighting_tangent.  Both read the record the forward saved and trace nothing."""
