@@ -128,7 +128,11 @@ typedef struct hf_desc {
  * parameterisation), makes the grid min(usual grid, blocks): launches of test size then go round their loops several
  * times (tests/test_gpu_grid_stride.py).  It only ever lowers the grid, so scratch and captured launches stay within
  * what they reserve; any other value is ignored.  Results do not depend on it except through the order of float
- * additions (atomic scatters, the per-block sums of dL/d(to_world)); per-lane outputs keep their bytes. */
+ * additions (atomic scatters, the per-block sums of dL/d(to_world)); per-lane outputs keep their bytes.
+ * TEST HOOK: the environment variable HF_SENSOR_STORE=dword|wide, read at every hf_sensor_rays, picks the store variant of
+ * its kernel (one sample per lane and 4-byte stores, or four per lane and one 16-byte store per row where the row is
+ * aligned) instead of the one the library was built to use; any other value is ignored.  Results do not
+ * depend on it: the two variants write the same bytes (tests/test_gpu_sensor.py). */
 typedef struct hf_rays {
     const float *o[3];
     const float *d[3];
@@ -1214,6 +1218,105 @@ int hf_rect_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], co
                              const float *const dp[3], const float *dweight, const float *dtex, float *dimage,
                              hf_stream_t stream);
 
+/* ---- the sensor: the primary wavefront of a perspective or an orthographic camera, differentiable ----
+ *
+ * Replaces Sensor::sample_ray of `perspective` (src/sensors/perspective.cpp:198-234) and `orthographic`
+ * (src/sensors/orthographic.cpp:119-142) together with the wavefront's sample positions (src/render/integrator.cpp:
+ * 251-268, src/python/python/ad/integrators/common.py:309-337), in one launch.
+ *   sensor      hf_sensor_t, HOST memory.  to_world: row-major 3x4 [A | c] (the layout of hf_desc_t.to_world; here in
+ *               double, as every real field, because the constants below are formed in double); x_fov: degrees along x
+ *               (perspective only); the film's size and its crop window in pixels (crop_offset = (crop_x, crop_y),
+ *               crop_size = (crop_w, crop_h); no crop: 0, 0, film_w, film_h).
+ *   index       sample i of the call has the wavefront index id_i = start + i, or ray_id[i] when the device row ray_id
+ *               is given (hf_reparam_*'s convention: a rank's tiles draw the samples of the unsharded wavefront);
+ *   pixel       pix = id / spp, py = pix / crop_w, px = pix - py crop_w (integrator.cpp:251-268: the wavefront covers
+ *               the crop window);
+ *   jitter      (jx, jy) = (v0 >> 9, v1 >> 9) 2^-23 with (v0, v1) = sample_tea_32(seed, id) (random.h:76-91);
+ *   pos         = (px + crop_x + jx, py + crop_y + jy): the film position in pixels of the WHOLE film (common.py:331-337),
+ *               written to out_pos (2 rows, may be NULL);
+ *   g           = pos / film_size: the sample s = (pos - crop_offset) / crop_size of sample_ray carried through the crop
+ *               window by camera_to_sample (sensor.h:238-240, 256-259), g = (crop_offset + s crop_size) / film_size;
+ *   w           = (1 - 2 g.x, (1 - 2 g.y) / a),  a = film_w / film_h (sensor.h:242, 260-261).
+ * HF_SENSOR_PERSPECTIVE, with tau = tan(x_fov pi / 360) (transform.h:216-233):
+ *   v = (w.x tau, w.y tau, 1): sample_to_camera's near-plane point over near (perspective.cpp:216-219),
+ *   d_c = v / |v| (:222),   ray.d = A d_c, not renormalised (:225),   ray.o = c + near A v = c + ray.d near / d_c.z
+ *   (:224-230),   maxt = (far - near) |v| (:227-231).
+ * HF_SENSOR_ORTHOGRAPHIC (orthographic.cpp:119-142; sensor.h:266-301):
+ *   o = A (w.x, w.y, near)^T + c,   d = normalize(A e_z),   maxt = far - near.
+ * Everything is formed in double and rounded once to float32.  out_o, out_d: 3 rows of n floats; out_maxt: n floats.
+ * One grid-stride launch; allocates nothing, never synchronises the host, capturable.  The kernel takes four consecutive
+ * samples per lane and stores 16 bytes per row where the row is aligned: its grid is family 1 of
+ * hf_grid_blocks for (n - head) / 4 items, head <= 3 (for n items with HF_SENSOR_STORE=dword, and below 64 samples).
+ *
+ * Differentiated with respect to to_world (all 12 entries, unconstrained, as the shape's) and x_fov, with
+ * d tau = (pi / 360) (1 + tau^2) d fov; maxt, the jitter and the pixel are HELD.  With u = (w.x, w.y, 0):
+ *   perspective   d v = u d tau,   d d_c = (d v - d_c <d_c, d v>) / |v|,   d ray.d = dA d_c + A d d_c,
+ *                 d ray.o = dc + near (dA v + A d v);
+ *   orthographic  d o = dA (w.x, w.y, near)^T + dc,   d d = (dA e_z - d <d, dA e_z>) / |A e_z|;  x_fov is not read.
+ * hf_sensor_rays_tangent: d_to_world (12 device floats) and d_fov (1 device float), either may be NULL (zero); writes
+ * out_do, out_dd (3 rows of n floats each); per lane, no atomics.  hf_sensor_rays_adjoint: the exact transpose; grad_o,
+ * grad_d (3 rows of n floats, either may be NULL = zero) are reduced into grad_to_world (12 device floats) and grad_fov
+ * (1 device float; the orthographic type leaves it untouched), both ACCUMULATED into, either may be NULL.  No float
+ * atomics: every block stores its 13 partial sums in double to `workspace` -- hf_sensor_workspace_floats() floats of
+ * device memory, 8-byte aligned, the caller's, exclusively this call's until it has completed -- and one more launch adds
+ * them in a fixed order (family 2 of hf_grid_blocks): bitwise the same from launch to launch, capturable.
+ * OUT OF SCOPE: the principal point offset, sample_border, the thin lens, the d_x / d_y of sample_ray_differential,
+ * wavelengths and time.
+ *
+ * hf_sensor_project is the way back, the perspective sensor's sample_direction (perspective.cpp:279-318, 334-383), for
+ * points p (3 device rows of n floats) and an optional byte row `active` (NULL: every lane):
+ *   ref       = to_world^-1 p; the affine inverse is formed once on the host in double (:283-284);
+ *   inside_z  = active and near <= ref.z <= far (:289);
+ *   g         = ((1 - ref.x / (ref.z tau)) / 2, (1 - a ref.y / (ref.z tau)) / 2): camera_to_sample in units of the whole
+ *               film; s_crop = (g film_size - crop_offset) / crop_size;   valid = inside_z and s_crop in [0, 1]^2 (:299);
+ *   uv        = s_crop crop_size + crop_offset = g film_size (:304, common.py:383-400): the pos of hf_sensor_rays, so the
+ *               projection of a point of sample i's ray is pos_i;
+ *   weight    = importance(local_d) / dist^2 = |ref| / (A' ref.z^3),   A' = (2 tau)^2 / a (crop_w crop_h) / (film_w film_h)
+ *               (:317, 340-345, 372-382).
+ * Written, a stated deviation from the reference's early returns: uv (2 rows) for every inside_z lane and zeros
+ * elsewhere; valid (n bytes); weight (n floats, may be NULL), zero unless valid.  The derivatives of uv are taken where
+ * inside_z and those of weight where valid, with respect to p (per lane), to_world and x_fov, with
+ * d ref = A^-1 (dp - dA ref - dc); the masks are HELD.  hf_sensor_project_tangent: dp (3 rows), d_to_world (12 device
+ * floats), d_fov (1 device float), each may be NULL (zero); writes duv (2 rows) and dweight (may be NULL).
+ * hf_sensor_project_adjoint: grad_uv (2 rows) and grad_weight, either may be NULL (zero); grad_p (3 rows, may be NULL) is
+ * OVERWRITTEN, grad_to_world and grad_fov are ACCUMULATED into through the workspace, as in hf_sensor_rays_adjoint.
+ * An orthographic sensor is refused with HF_EINVAL: the reference has no sample_direction for it, and a point names no
+ * film position of a sensor whose pixel integral is over the origins.
+ * All entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional, n >= 2^32,
+ * spp == 0, a crop window that is empty or not inside the film, a non-finite field, near_clip <= 0 or far_clip <=
+ * near_clip, a type that is neither; perspective: x_fov outside (0, 180) or a to_world whose linear part has scale
+ * (perspective.cpp:163-164; |A^T A - I| > 1e-4); without ray_id: start + n or crop_w crop_h spp beyond 2^32.  n == 0 is
+ * legal.  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+#define HF_SENSOR_PERSPECTIVE 0
+#define HF_SENSOR_ORTHOGRAPHIC 1
+typedef struct hf_sensor {          /* HOST memory, as hf_receiver_t */
+    int32_t type;                   /* HF_SENSOR_* */
+    uint32_t film_w, film_h;        /* the film in pixels */
+    uint32_t crop_x, crop_y, crop_w, crop_h;
+    double to_world[12];            /* row-major 3x4 [A | c] */
+    double x_fov;                   /* degrees, along x; perspective only */
+    double near_clip, far_clip;
+} hf_sensor_t;
+int hf_sensor_rays(const hf_sensor_t *sensor, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                   const uint32_t *ray_id, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                   float *const out_pos[2], hf_stream_t stream);
+int hf_sensor_rays_tangent(const hf_sensor_t *sensor, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                           const uint32_t *ray_id, const float *d_to_world, const float *d_fov, float *const out_do[3],
+                           float *const out_dd[3], hf_stream_t stream);
+/* the adjoint's workspace in floats (a constant: the most any launch needs) */
+size_t hf_sensor_workspace_floats(void);
+int hf_sensor_rays_adjoint(const hf_sensor_t *sensor, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                           const uint32_t *ray_id, const float *const grad_o[3], const float *const grad_d[3],
+                           float *grad_to_world, float *grad_fov, float *workspace, hf_stream_t stream);
+int hf_sensor_project(const hf_sensor_t *sensor, size_t n, const float *const p[3], const uint8_t *active,
+                      float *const uv[2], uint8_t *valid, float *weight, hf_stream_t stream);
+int hf_sensor_project_tangent(const hf_sensor_t *sensor, size_t n, const float *const p[3], const uint8_t *active,
+                              const float *const dp[3], const float *d_to_world, const float *d_fov, float *const duv[2],
+                              float *dweight, hf_stream_t stream);
+int hf_sensor_project_adjoint(const hf_sensor_t *sensor, size_t n, const float *const p[3], const uint8_t *active,
+                              const float *const grad_uv[2], const float *grad_weight, float *const grad_p[3],
+                              float *grad_to_world, float *grad_fov, float *workspace, hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional
@@ -1551,7 +1654,8 @@ int hf_get_node_level(const hf_field_t *hf, int level, float *h_records, float *
 int hf_invert_affine(const float in[12], float out[12]);
 /* blocks (of 256 threads) that a grid-stride launch of n items gets, HF_FORCE_GRID included.  family: 0 the flat cap
  * (adjoints, reparameterisation, Adam, area sampling, ...), 1 the cap of the streaming kernels (SI, hf_tangent, the
- * forward and tangent of attributes and of eval_parameterization), 2 the cap of the launches that sum dL/d(to_world).
+ * forward and tangent of attributes and of eval_parameterization, the sensor's rays, projection and their tangents), 2
+ * the cap of the launches that sum dL/d(to_world), the sensor's adjoints among them.
  * 0 for an unknown family.  Needs no device. */
 int hf_grid_blocks(size_t n, int family);
 const char *hf_last_error_string(void);

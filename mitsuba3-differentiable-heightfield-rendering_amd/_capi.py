@@ -76,7 +76,26 @@ class hf_rect_light_t(C.Structure):
 _rect_mid = [_fp, C.c_uint32, C.c_uint32, _fp, C.POINTER(hf_rect_light_t), C.c_uint32, C.c_uint32, _fp, C.c_float]
 _rect_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp]  # n, spp, p, sh_n, d, t
 
+HF_SENSOR_PERSPECTIVE, HF_SENSOR_ORTHOGRAPHIC = 0, 1
+
+
+class hf_sensor_t(C.Structure):
+    _fields_ = [("type", C.c_int32), ("film_w", C.c_uint32), ("film_h", C.c_uint32), ("crop_x", C.c_uint32),
+                ("crop_y", C.c_uint32), ("crop_w", C.c_uint32), ("crop_h", C.c_uint32), ("to_world", C.c_double * 12),
+                ("x_fov", C.c_double), ("near_clip", C.c_double), ("far_clip", C.c_double)]
+
+
+_sensor_in = [C.POINTER(hf_sensor_t), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _fp]  # sensor, n, start, spp, seed, ray_id
+_project_in = [C.POINTER(hf_sensor_t), C.c_size_t, C.POINTER(_fp * 3), _fp]  # sensor, n, p, active
+
 SYMBOLS = {
+    "hf_sensor_rays": (C.c_int, [*_sensor_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 2), C.c_void_p]),
+    "hf_sensor_rays_tangent": (C.c_int, [*_sensor_in, _fp, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_sensor_workspace_floats": (C.c_size_t, []),
+    "hf_sensor_rays_adjoint": (C.c_int, [*_sensor_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, C.c_void_p]),
+    "hf_sensor_project": (C.c_int, [*_project_in, C.POINTER(_fp * 2), _fp, _fp, C.c_void_p]),
+    "hf_sensor_project_tangent": (C.c_int, [*_project_in, C.POINTER(_fp * 3), _fp, _fp, C.POINTER(_fp * 2), _fp, C.c_void_p]),
+    "hf_sensor_project_adjoint": (C.c_int, [*_project_in, C.POINTER(_fp * 2), _fp, C.POINTER(_fp * 3), _fp, _fp, _fp, C.c_void_p]),
     "hf_create": (C.c_int, [C.POINTER(hf_desc_t), C.POINTER(C.c_void_p)]),
     "hf_destroy": (C.c_int, [C.c_void_p]),
     "hf_capture_reset": (C.c_int, [C.c_void_p]),

@@ -1629,6 +1629,212 @@ extern "C" int hf_rect_lighting_tangent(size_t n, uint32_t spp, const float *con
     return light_launch(hf_launch_rect, 2, a, stream);
 }
 
+// ---- the sensor: the primary wavefront of a perspective or an orthographic camera ----
+static int log2_or_minus1(uint32_t v) {
+    if (v == 0 || (v & (v - 1u))) return -1;
+    int s = 0;
+    while ((1u << s) != v) ++s;
+    return s;
+}
+// the checks of the sensor alone, what every hf_sensor_* entry starts with
+static int sensor_checks(const char *who, const hf_sensor_t *s, size_t n) {
+    if (!s) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (s->type != HF_SENSOR_PERSPECTIVE && s->type != HF_SENSOR_ORTHOGRAPHIC)
+        return fail(HF_EINVAL, "%s: the sensor's type must be HF_SENSOR_PERSPECTIVE or HF_SENSOR_ORTHOGRAPHIC (got %d)", who, s->type);
+    const bool persp = s->type == HF_SENSOR_PERSPECTIVE;
+    if ((uint64_t) n >= (1ull << 32)) return fail(HF_EINVAL, "%s: n must be below 2^32", who);
+    if (s->crop_w == 0 || s->crop_h == 0 || (uint64_t) s->crop_x + s->crop_w > s->film_w ||
+        (uint64_t) s->crop_y + s->crop_h > s->film_h)
+        return fail(HF_EINVAL, "%s: the crop window (%u, %u, %u, %u) is empty or not inside the %u x %u film", who, s->crop_x,
+                    s->crop_y, s->crop_w, s->crop_h, s->film_w, s->film_h);
+    for (int j = 0; j < 12; ++j)
+        if (!isfinite(s->to_world[j])) return fail(HF_EINVAL, "%s: the sensor's to_world must be finite", who);
+    if (!isfinite(s->near_clip) || !isfinite(s->far_clip) || (persp && !isfinite(s->x_fov)))
+        return fail(HF_EINVAL, "%s: the sensor's near_clip, far_clip and x_fov must be finite", who);
+    if (!(s->near_clip > 0.0) || !(s->far_clip > s->near_clip))
+        return fail(HF_EINVAL, "%s: the sensor needs 0 < near_clip < far_clip (got %g, %g)", who, s->near_clip, s->far_clip);
+    const double *M = s->to_world;
+    if (persp) {
+        if (!(s->x_fov > 0.0) || !(s->x_fov < 180.0))
+            return fail(HF_EINVAL, "%s: the sensor's x_fov must be in (0, 180) degrees (got %g)", who, s->x_fov);
+        for (int i = 0; i < 3; ++i) // perspective.cpp:163-164: has_scale()
+            for (int j = i; j < 3; ++j) {
+                const double g = M[i] * M[j] + M[4 + i] * M[4 + j] + M[8 + i] * M[8 + j];
+                if (fabs(g - (i == j ? 1.0 : 0.0)) > 1e-4)
+                    return fail(HF_EINVAL, "%s: scale factors in the sensor's to_world are not allowed (perspective)", who);
+            }
+    }
+    return HF_OK;
+}
+// What hf_sensor_rays and its two derivatives share: the checks of the sensor and of the wavefront, and every constant
+// of the kernels, formed in double
+static int sensor_args(const char *who, const hf_sensor_t *s, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                       const uint32_t *ray_id, hf_sensor_args &a) {
+    a = {};
+    const int rc = sensor_checks(who, s, n);
+    if (rc != HF_OK) return rc;
+    if (spp == 0) return fail(HF_EINVAL, "%s: spp must be at least 1", who);
+    const bool persp = s->type == HF_SENSOR_PERSPECTIVE;
+    const double *M = s->to_world;
+    if (!ray_id) {
+        const uint64_t window = (uint64_t) s->crop_w * s->crop_h;
+        if ((uint64_t) start + (uint64_t) n > (1ull << 32) || window > (1ull << 32) || window * spp > (1ull << 32))
+            return fail(HF_EINVAL, "%s: start + n and crop_w crop_h spp must not exceed 2^32 without ray_id", who);
+    }
+    a.n = n; a.start = start; a.spp = spp; a.seed = seed; a.ray_id = ray_id;
+    a.crop_w = s->crop_w; a.crop_x = s->crop_x; a.crop_y = s->crop_y;
+    a.spp_shift = log2_or_minus1(spp); a.crop_w_shift = log2_or_minus1(s->crop_w);
+    a.film_w = (double) s->film_w; a.film_h = (double) s->film_h; a.aspect = a.film_w / a.film_h; // sensor.h:242
+    for (int k = 0; k < 3; ++k) {
+        for (int j = 0; j < 3; ++j) a.A[3 * k + j] = M[4 * k + j];
+        a.c[k] = M[4 * k + 3];
+    }
+    a.near = s->near_clip; a.span = s->far_clip - s->near_clip;
+    if (persp) {
+        a.tau = tan(s->x_fov * 3.141592653589793 / 360.0); // transform.h:216-233: 1 / cot(fov / 2)
+        a.dtau = (3.141592653589793 / 360.0) * (1.0 + a.tau * a.tau);
+    } else {
+        a.tau = 1.0; a.dtau = 0.0;
+        const double len = sqrt(M[2] * M[2] + M[6] * M[6] + M[10] * M[10]); // orthographic.cpp:137: normalize(to_world * (0, 0, 1))
+        if (!(len > 0.0) || !isfinite(len)) return fail(HF_EINVAL, "%s: the sensor's to_world has no z axis (orthographic)", who);
+        for (int k = 0; k < 3; ++k) { a.dz[k] = M[4 * k + 2] / len; a.An[k] = M[4 * k + 2] * s->near_clip; }
+        a.inv_len_z = 1.0 / len;
+    }
+    return HF_OK;
+}
+
+static int sensor_launch(int mode, const hf_sensor_t *s, const hf_sensor_args &a, hf_stream_t stream) {
+    if (a.n == 0) return HF_OK;
+    hf_launch_sensor(mode, s->type, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_sensor_rays(const hf_sensor_t *sensor, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                              const uint32_t *ray_id, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                              float *const out_pos[2], hf_stream_t stream) {
+    const char *fn = "hf_sensor_rays";
+    hf_sensor_args a;
+    const int rc = sensor_args(fn, sensor, n, start, spp, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (out_pos && (!out_pos[0] || !out_pos[1])) return fail(HF_EINVAL, "%s: NULL out_pos component array", fn);
+    for (int k = 0; k < 3; ++k) { a.out_o[k] = out_o[k]; a.out_d[k] = out_d[k]; }
+    a.out_maxt = out_maxt;
+    for (int k = 0; k < 2; ++k) a.out_pos[k] = out_pos ? out_pos[k] : nullptr;
+    return sensor_launch(0, sensor, a, stream);
+}
+
+extern "C" int hf_sensor_rays_tangent(const hf_sensor_t *sensor, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                                      const uint32_t *ray_id, const float *d_to_world, const float *d_fov,
+                                      float *const out_do[3], float *const out_dd[3], hf_stream_t stream) {
+    const char *fn = "hf_sensor_rays_tangent";
+    hf_sensor_args a;
+    const int rc = sensor_args(fn, sensor, n, start, spp, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(out_do) || !all3(out_dd)) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    for (int k = 0; k < 3; ++k) { a.out_o[k] = out_do[k]; a.out_d[k] = out_dd[k]; }
+    a.d_tw = d_to_world; a.d_fov = d_fov;
+    return sensor_launch(2, sensor, a, stream);
+}
+
+extern "C" size_t hf_sensor_workspace_floats(void) { return 2u * hf_sensor_slab_doubles(); }
+
+extern "C" int hf_sensor_rays_adjoint(const hf_sensor_t *sensor, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                                      const uint32_t *ray_id, const float *const grad_o[3], const float *const grad_d[3],
+                                      float *grad_to_world, float *grad_fov, float *workspace, hf_stream_t stream) {
+    const char *fn = "hf_sensor_rays_adjoint";
+    hf_sensor_args a;
+    const int rc = sensor_args(fn, sensor, n, start, spp, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (grad_o && !all3(grad_o)) return fail(HF_EINVAL, "%s: NULL grad_o component array", fn);
+    if (grad_d && !all3(grad_d)) return fail(HF_EINVAL, "%s: NULL grad_d component array", fn);
+    if (!workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    for (int k = 0; k < 3; ++k) { a.go[k] = grad_o ? grad_o[k] : nullptr; a.gd[k] = grad_d ? grad_d[k] : nullptr; }
+    a.slab = (double *) workspace; a.g_tw = grad_to_world; a.g_fov = grad_fov;
+    return sensor_launch(1, sensor, a, stream);
+}
+
+// What hf_sensor_project and its two derivatives share.  The affine inverse is formed once, here, in double (adjugate)
+static int sensor_project_args(const char *who, const hf_sensor_t *s, size_t n, const float *const p[3], const uint8_t *active,
+                               hf_sensor_project_args &a) {
+    a = {};
+    const int rc = sensor_checks(who, s, n);
+    if (rc != HF_OK) return rc;
+    if (s->type != HF_SENSOR_PERSPECTIVE)
+        return fail(HF_EINVAL, "%s: an orthographic sensor has no sample_direction (a point names no film position there)", who);
+    if (!all3(p)) return fail(HF_EINVAL, "%s: NULL argument", who);
+    const double *M = s->to_world;
+    const double m[3][3] = { { M[0], M[1], M[2] }, { M[4], M[5], M[6] }, { M[8], M[9], M[10] } };
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) { // Ai[r][c] = cofactor(c, r) / det
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+            a.Ai[3 * r + c] = (m[r1][c1] * m[r2][c2] - m[r1][c2] * m[r2][c1]) / det;
+        }
+    for (int k = 0; k < 3; ++k) a.c[k] = M[4 * k + 3];
+    a.n = n; a.active = active;
+    for (int k = 0; k < 3; ++k) a.p[k] = p[k];
+    a.near = s->near_clip; a.far = s->far_clip;
+    a.tau = tan(s->x_fov * 3.141592653589793 / 360.0);
+    a.dtau = (3.141592653589793 / 360.0) * (1.0 + a.tau * a.tau);
+    a.film_w = (double) s->film_w; a.film_h = (double) s->film_h; a.aspect = a.film_w / a.film_h;
+    a.crop_x = (double) s->crop_x; a.crop_y = (double) s->crop_y; a.crop_w = (double) s->crop_w; a.crop_h = (double) s->crop_h;
+    // importance(): A' = (2 tan(x_fov / 2))^2 / aspect (crop_w / film_w) (crop_h / film_h) (perspective.cpp:340-345)
+    a.inv_area = 1.0 / ((2.0 * a.tau) * (2.0 * a.tau) / a.aspect * (a.crop_w * a.crop_h) / (a.film_w * a.film_h));
+    return HF_OK;
+}
+static int sensor_project_launch(int mode, const hf_sensor_project_args &a, hf_stream_t stream) {
+    if (a.n == 0) return HF_OK;
+    hf_launch_sensor_project(mode, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_sensor_project(const hf_sensor_t *sensor, size_t n, const float *const p[3], const uint8_t *active,
+                                 float *const uv[2], uint8_t *valid, float *weight, hf_stream_t stream) {
+    const char *fn = "hf_sensor_project";
+    hf_sensor_project_args a;
+    const int rc = sensor_project_args(fn, sensor, n, p, active, a);
+    if (rc != HF_OK) return rc;
+    if (!uv || !uv[0] || !uv[1] || !valid) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.uv[0] = uv[0]; a.uv[1] = uv[1]; a.valid = valid; a.weight = weight;
+    return sensor_project_launch(0, a, stream);
+}
+
+extern "C" int hf_sensor_project_tangent(const hf_sensor_t *sensor, size_t n, const float *const p[3], const uint8_t *active,
+                                         const float *const dp[3], const float *d_to_world, const float *d_fov,
+                                         float *const duv[2], float *dweight, hf_stream_t stream) {
+    const char *fn = "hf_sensor_project_tangent";
+    hf_sensor_project_args a;
+    const int rc = sensor_project_args(fn, sensor, n, p, active, a);
+    if (rc != HF_OK) return rc;
+    if (!duv || !duv[0] || !duv[1]) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (dp && !all3(dp)) return fail(HF_EINVAL, "%s: NULL dp component array", fn);
+    for (int k = 0; k < 3; ++k) a.dp[k] = dp ? dp[k] : nullptr;
+    a.d_tw = d_to_world; a.d_fov = d_fov; a.uv[0] = duv[0]; a.uv[1] = duv[1]; a.weight = dweight;
+    return sensor_project_launch(2, a, stream);
+}
+
+extern "C" int hf_sensor_project_adjoint(const hf_sensor_t *sensor, size_t n, const float *const p[3], const uint8_t *active,
+                                         const float *const grad_uv[2], const float *grad_weight, float *const grad_p[3],
+                                         float *grad_to_world, float *grad_fov, float *workspace, hf_stream_t stream) {
+    const char *fn = "hf_sensor_project_adjoint";
+    hf_sensor_project_args a;
+    const int rc = sensor_project_args(fn, sensor, n, p, active, a);
+    if (rc != HF_OK) return rc;
+    if (grad_uv && (!grad_uv[0] || !grad_uv[1])) return fail(HF_EINVAL, "%s: NULL grad_uv component array", fn);
+    if (grad_p && (!grad_p[0] || !grad_p[1] || !grad_p[2])) return fail(HF_EINVAL, "%s: NULL grad_p component array", fn);
+    if (!workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    for (int k = 0; k < 2; ++k) a.guv[k] = grad_uv ? grad_uv[k] : nullptr;
+    for (int k = 0; k < 3; ++k) a.gp[k] = grad_p ? grad_p[k] : nullptr;
+    a.gweight = grad_weight; a.slab = (double *) workspace; a.g_tw = grad_to_world; a.g_fov = grad_fov;
+    return sensor_project_launch(1, a, stream);
+}
+
 // ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----
 // What every entry that reads a map shares, the reflection rows' too: the checks of the map (A: a block with W, H, data
 // and rot, zeroed by the caller), in two pieces because the entries check other things between them: the texels ...

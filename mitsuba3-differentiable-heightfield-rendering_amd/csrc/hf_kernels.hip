@@ -6751,6 +6751,386 @@ void hf_launch_rect(int mode, const hf_rect_args &a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------
+// The sensor (include/hf.h): the primary wavefront of a perspective or an orthographic camera, its tangent
+// and its adjoint.  One sample per lane, consecutive lanes store consecutive floats of every row; no LDS in the rays
+// and tangent kernels.  The sensor's constants come as kernel arguments (formed on the host in double), so they are
+// wave-uniform; the per-sample arithmetic is double and every output is rounded once.
+// ---------------------------------------------------------------------------------
+struct hf_sensor_film {
+    double px, py; // pos: the film position in pixels of the whole film
+    double wx, wy; // w = (1 - 2 g.x, (1 - 2 g.y) / a), g = pos / film_size
+};
+__device__ __forceinline__ hf_sensor_film sensor_sample(const hf_sensor_args &a, size_t i) {
+    const uint32_t id = a.ray_id ? a.ray_id[i] : a.start + (uint32_t) i;
+    uint32_t v0, v1;
+    tea32(a.seed, id, v0, v1);
+    // integrator.cpp:251-268; a shift where the divisor is a power of two (wave-uniform choice)
+    const uint32_t pix = a.spp_shift >= 0 ? id >> a.spp_shift : id / a.spp;
+    const uint32_t row = a.crop_w_shift >= 0 ? pix >> a.crop_w_shift : pix / a.crop_w;
+    const uint32_t col = pix - row * a.crop_w;
+    hf_sensor_film f;
+    f.px = (double) (col + a.crop_x) + (double) (v0 >> 9) * (1.0 / 8388608.0);
+    f.py = (double) (row + a.crop_y) + (double) (v1 >> 9) * (1.0 / 8388608.0);
+    f.wx = 1.0 - 2.0 * (f.px / a.film_w);
+    f.wy = (1.0 - 2.0 * (f.py / a.film_h)) / a.aspect;
+    return f;
+}
+// perspective: v = (w tau, 1), its length and d_c = v / |v|
+struct hf_sensor_dir {
+    double vx, vy, len, il, cx, cy, cz;
+};
+__device__ __forceinline__ hf_sensor_dir sensor_dir(const hf_sensor_args &a, const hf_sensor_film &f) {
+    hf_sensor_dir q;
+    q.vx = f.wx * a.tau; q.vy = f.wy * a.tau;
+    q.len = __builtin_sqrt(q.vx * q.vx + q.vy * q.vy + 1.0);
+    q.il = 1.0 / q.len;
+    q.cx = q.vx * q.il; q.cy = q.vy * q.il; q.cz = q.il;
+    return q;
+}
+
+// one sample's nine outputs, in the order of the rows: o (3), d (3), maxt, pos (2)
+#define HF_SENSOR_ROWS 9
+template <int TYPE>
+__device__ __forceinline__ void sensor_ray(const hf_sensor_args &a, size_t i, float r[HF_SENSOR_ROWS]) {
+    const hf_sensor_film f = sensor_sample(a, i);
+    r[7] = (float) f.px; r[8] = (float) f.py;
+    if (TYPE == HF_SENSOR_PERSPECTIVE) {
+        const hf_sensor_dir q = sensor_dir(a, f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double Av = a.A[3 * k] * q.vx + a.A[3 * k + 1] * q.vy + a.A[3 * k + 2];
+            r[k] = (float) (a.c[k] + a.near * Av);
+            r[3 + k] = (float) (a.A[3 * k] * q.cx + a.A[3 * k + 1] * q.cy + a.A[3 * k + 2] * q.cz);
+        }
+        r[6] = (float) (a.span * q.len);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            r[k] = (float) (a.A[3 * k] * f.wx + a.A[3 * k + 1] * f.wy + a.An[k] + a.c[k]);
+            r[3 + k] = (float) a.dz[k];
+        }
+        r[6] = (float) a.span;
+    }
+}
+// the dword path: sample i to element i of every row that is wanted
+template <int TYPE>
+__device__ __forceinline__ void sensor_ray_store(const hf_sensor_args &a, size_t i) {
+    float r[HF_SENSOR_ROWS];
+    sensor_ray<TYPE>(a, i, r);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { a.out_o[k][i] = r[k]; a.out_d[k][i] = r[3 + k]; }
+    a.out_maxt[i] = r[6];
+    if (a.out_pos[0]) { a.out_pos[0][i] = r[7]; a.out_pos[1][i] = r[8]; }
+}
+// variant A: one sample per lane, a wave stores 256 contiguous bytes of every row
+template <int TYPE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_rays_kernel(hf_sensor_args a) {
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK)
+        sensor_ray_store<TYPE>(a, i);
+}
+// variant B: four consecutive samples per lane, one 16-byte store per row.  a.head samples come before the first group,
+// so that element a.head of out_o[0] is 16-byte aligned; bit k of a.wide_mask says that row k has the same alignment
+// (its groups are stored as one float4), any other row takes four dword stores per group; the head and the tail (fewer
+// than 4 + 4 samples) take the dword path on the first lanes of the grid.
+typedef float hf_sensor_f4 __attribute__((ext_vector_type(4)));
+template <int TYPE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_rays_wide_kernel(hf_sensor_args a) {
+    float *const row[HF_SENSOR_ROWS] = { a.out_o[0], a.out_o[1], a.out_o[2], a.out_d[0], a.out_d[1], a.out_d[2], a.out_maxt,
+                                         a.out_pos[0], a.out_pos[1] };
+    const size_t tid = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const size_t groups = (a.n - a.head) >> 2;
+    for (size_t g = tid; g < groups; g += (size_t) gridDim.x * HF_BLOCK) {
+        const size_t i0 = a.head + 4 * g;
+        float r[4][HF_SENSOR_ROWS];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sensor_ray<TYPE>(a, i0 + j, r[j]);
+#pragma unroll
+        for (int k = 0; k < HF_SENSOR_ROWS; ++k) {
+            if (!row[k]) continue;
+            if ((a.wide_mask >> k) & 1u) {
+                const hf_sensor_f4 v = { r[0][k], r[1][k], r[2][k], r[3][k] };
+                *reinterpret_cast<hf_sensor_f4 *>(row[k] + i0) = v;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) row[k][i0 + j] = r[j][k];
+            }
+        }
+    }
+    const size_t tail0 = a.head + 4 * groups, rest = a.head + (a.n - tail0);
+    if (tid < rest) sensor_ray_store<TYPE>(a, tid < a.head ? tid : tail0 + (tid - a.head));
+}
+
+template <int TYPE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_tangent_kernel(hf_sensor_args a) {
+    double dM[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) dM[j] = a.d_tw ? (double) a.d_tw[j] : 0.0;
+    const double dT = a.d_fov ? (double) a.d_fov[0] * a.dtau : 0.0;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_sensor_film f = sensor_sample(a, i);
+        if (TYPE == HF_SENSOR_PERSPECTIVE) {
+            const hf_sensor_dir q = sensor_dir(a, f);
+            const double dvx = f.wx * dT, dvy = f.wy * dT;
+            const double pr = q.cx * dvx + q.cy * dvy;
+            const double ex = (dvx - q.cx * pr) * q.il, ey = (dvy - q.cy * pr) * q.il, ez = -(q.cz * pr) * q.il;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double *A = a.A + 3 * k, *dA = dM + 4 * k;
+                a.out_o[k][i] = (float) (dA[3] + a.near * (dA[0] * q.vx + dA[1] * q.vy + dA[2] + A[0] * dvx + A[1] * dvy));
+                a.out_d[k][i] = (float) (dA[0] * q.cx + dA[1] * q.cy + dA[2] * q.cz + A[0] * ex + A[1] * ey + A[2] * ez);
+            }
+        } else {
+            const double pr = a.dz[0] * dM[2] + a.dz[1] * dM[6] + a.dz[2] * dM[10];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double *dA = dM + 4 * k;
+                a.out_o[k][i] = (float) (dA[0] * f.wx + dA[1] * f.wy + dA[2] * a.near + dA[3]);
+                a.out_d[k][i] = (float) ((dA[2] - a.dz[k] * pr) * a.inv_len_z);
+            }
+        }
+    }
+}
+
+// The adjoint: every lane keeps its 13 sums (to_world's 12, tau's) in double across its grid-stride loop; a block adds
+// them (a butterfly over the wave, then the four waves through LDS, in a fixed order) into its row of the slab, and
+// hf_sensor_sum_kernel adds the rows in a fixed order: no float atomics, bitwise the same from launch to launch.
+#define HF_SENSOR_SUMS 13
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+// the block's sums of M into slab row blockIdx.x; every thread of the block calls it
+__device__ __forceinline__ void sensor_block_store(const double M[HF_SENSOR_SUMS], double *slab) {
+    __shared__ double s_red[HF_BLOCK / 64][HF_SENSOR_SUMS];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < HF_SENSOR_SUMS; ++j) {
+        const double v = wave_sum_f64(M[j]);
+        if (lane == 0u) s_red[w][j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < HF_SENSOR_SUMS) {
+        double v = s_red[0][threadIdx.x];
+#pragma unroll
+        for (int k = 1; k < HF_BLOCK / 64; ++k) v += s_red[k][threadIdx.x];
+        slab[(size_t) blockIdx.x * HF_SENSOR_SUMS + threadIdx.x] = v;
+    }
+}
+template <int TYPE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_adjoint_kernel(hf_sensor_args a) {
+    double M[HF_SENSOR_SUMS];
+#pragma unroll
+    for (int j = 0; j < HF_SENSOR_SUMS; ++j) M[j] = 0.0;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_sensor_film f = sensor_sample(a, i);
+        double go[3], gd[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            go[k] = a.go[k] ? (double) a.go[k][i] : 0.0;
+            gd[k] = a.gd[k] ? (double) a.gd[k][i] : 0.0;
+        }
+        if (TYPE == HF_SENSOR_PERSPECTIVE) {
+            const hf_sensor_dir q = sensor_dir(a, f);
+            double p[2] = { 0.0, 0.0 }, t[3] = { 0.0, 0.0, 0.0 }; // near A^T go (x, y), A^T gd
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double *A = a.A + 3 * k, no = a.near * go[k];
+                M[4 * k] += no * q.vx + gd[k] * q.cx;
+                M[4 * k + 1] += no * q.vy + gd[k] * q.cy;
+                M[4 * k + 2] += no + gd[k] * q.cz;
+                M[4 * k + 3] += go[k];
+                p[0] += A[0] * no; p[1] += A[1] * no;
+                t[0] += A[0] * gd[k]; t[1] += A[1] * gd[k]; t[2] += A[2] * gd[k];
+            }
+            const double pr = q.cx * t[0] + q.cy * t[1] + q.cz * t[2];
+            M[12] += (p[0] + (t[0] - q.cx * pr) * q.il) * f.wx + (p[1] + (t[1] - q.cy * pr) * q.il) * f.wy;
+        } else {
+            const double pr = a.dz[0] * gd[0] + a.dz[1] * gd[1] + a.dz[2] * gd[2];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                M[4 * k] += go[k] * f.wx;
+                M[4 * k + 1] += go[k] * f.wy;
+                M[4 * k + 2] += go[k] * a.near + (gd[k] - a.dz[k] * pr) * a.inv_len_z;
+                M[4 * k + 3] += go[k];
+            }
+        }
+    }
+    sensor_block_store(M, a.slab);
+}
+// g_tw[j] += column j of the slab's rows, g_fov[0] += dtau * column 12: every thread adds every HF_BLOCK-th row, then a
+// fixed-order tree over the block through LDS.  One block.
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_sum_kernel(const double *__restrict__ slab, uint32_t rows, double dtau,
+                                                                  float *__restrict__ g_tw, float *__restrict__ g_fov) {
+    __shared__ double s_part[HF_BLOCK][HF_SENSOR_SUMS];
+    const uint32_t t = threadIdx.x;
+    double acc[HF_SENSOR_SUMS];
+#pragma unroll
+    for (int j = 0; j < HF_SENSOR_SUMS; ++j) acc[j] = 0.0;
+    for (uint32_t b = t; b < rows; b += HF_BLOCK) {
+#pragma unroll
+        for (int j = 0; j < HF_SENSOR_SUMS; ++j) acc[j] += slab[(size_t) b * HF_SENSOR_SUMS + j];
+    }
+#pragma unroll
+    for (int j = 0; j < HF_SENSOR_SUMS; ++j) s_part[t][j] = acc[j];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = HF_BLOCK / 2; h > 0; h >>= 1) {
+        if (t < h) {
+#pragma unroll
+            for (int j = 0; j < HF_SENSOR_SUMS; ++j) s_part[t][j] += s_part[t + h][j];
+        }
+        __syncthreads();
+    }
+    if (t < 12u) {
+        if (g_tw) g_tw[t] += (float) s_part[0][t];
+    } else if (t == 12u && g_fov) {
+        g_fov[0] += (float) (s_part[0][12] * dtau);
+    }
+}
+size_t hf_sensor_slab_doubles() { return (size_t) HF_XFORM_GRID_CAP * HF_SENSOR_SUMS; }
+
+// ---- the way back: perspective sample_direction (perspective.cpp:279-318, 334-383) ----
+struct hf_sensor_proj {
+    bool inside, valid;  // inside_z; inside_z and s_crop in [0, 1]^2
+    double x, y, z;      // ref = to_world^-1 p
+    double iz, rx, ry;   // 1 / ref.z, ref.x / ref.z, ref.y / ref.z
+    double u, v;         // uv: the film position in pixels of the whole film
+    double r2, W;        // |ref|^2, importance(local_d) / dist^2 = |ref| / (A' ref.z^3)
+};
+__device__ __forceinline__ hf_sensor_proj sensor_project(const hf_sensor_project_args &a, size_t i) {
+    hf_sensor_proj r;
+    const double q0 = (double) a.p[0][i] - a.c[0], q1 = (double) a.p[1][i] - a.c[1], q2 = (double) a.p[2][i] - a.c[2];
+    r.x = a.Ai[0] * q0 + a.Ai[1] * q1 + a.Ai[2] * q2;
+    r.y = a.Ai[3] * q0 + a.Ai[4] * q1 + a.Ai[5] * q2;
+    r.z = a.Ai[6] * q0 + a.Ai[7] * q1 + a.Ai[8] * q2;
+    r.inside = (!a.active || a.active[i] != 0) && r.z >= a.near && r.z <= a.far; // perspective.cpp:289
+    r.iz = 1.0 / r.z; r.rx = r.x * r.iz; r.ry = r.y * r.iz;
+    r.u = 0.5 * (1.0 - r.rx / a.tau) * a.film_w;                                   // camera_to_sample (sensor.h:256-262)
+    r.v = 0.5 * (1.0 - a.aspect * r.ry / a.tau) * a.film_h;
+    const double sx = (r.u - a.crop_x) / a.crop_w, sy = (r.v - a.crop_y) / a.crop_h;
+    r.valid = r.inside && sx >= 0.0 && sx <= 1.0 && sy >= 0.0 && sy <= 1.0;        // perspective.cpp:299-300
+    r.r2 = r.x * r.x + r.y * r.y + r.z * r.z;
+    r.W = __builtin_sqrt(r.r2) * a.inv_area * (r.iz * r.iz * r.iz);                // perspective.cpp:317, 372-382
+    return r;
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_project_kernel(hf_sensor_project_args a) {
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_sensor_proj r = sensor_project(a, i);
+        a.uv[0][i] = r.inside ? (float) r.u : 0.f;
+        a.uv[1][i] = r.inside ? (float) r.v : 0.f;
+        a.valid[i] = r.valid ? 1 : 0;
+        if (a.weight) a.weight[i] = r.valid ? (float) r.W : 0.f;
+    }
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_project_tangent_kernel(hf_sensor_project_args a) {
+    double dM[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) dM[j] = a.d_tw ? (double) a.d_tw[j] : 0.0;
+    const double dT = (a.d_fov ? (double) a.d_fov[0] * a.dtau : 0.0) / a.tau; // d tau / tau
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_sensor_proj r = sensor_project(a, i);
+        double dq[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) // dp - dA ref - dc
+            dq[k] = (a.dp[k] ? (double) a.dp[k][i] : 0.0) - (dM[4 * k] * r.x + dM[4 * k + 1] * r.y + dM[4 * k + 2] * r.z) - dM[4 * k + 3];
+        const double dx = a.Ai[0] * dq[0] + a.Ai[1] * dq[1] + a.Ai[2] * dq[2];
+        const double dy = a.Ai[3] * dq[0] + a.Ai[4] * dq[1] + a.Ai[5] * dq[2];
+        const double dz = a.Ai[6] * dq[0] + a.Ai[7] * dq[1] + a.Ai[8] * dq[2];
+        const double drx = (dx - r.rx * dz) * r.iz, dry = (dy - r.ry * dz) * r.iz;
+        const double cu = -0.5 * a.film_w / a.tau, cv = -0.5 * a.film_h * a.aspect / a.tau;
+        a.uv[0][i] = r.inside ? (float) (cu * (drx - r.rx * dT)) : 0.f;
+        a.uv[1][i] = r.inside ? (float) (cv * (dry - r.ry * dT)) : 0.f;
+        if (a.weight)
+            a.weight[i] = r.valid ? (float) (r.W * ((r.x * dx + r.y * dy + r.z * dz) / r.r2 - 3.0 * dz * r.iz - 2.0 * dT)) : 0.f;
+    }
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_project_adjoint_kernel(hf_sensor_project_args a) {
+    double M[HF_SENSOR_SUMS];
+#pragma unroll
+    for (int j = 0; j < HF_SENSOR_SUMS; ++j) M[j] = 0.0;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_sensor_proj r = sensor_project(a, i);
+        const double cu = -0.5 * a.film_w / a.tau, cv = -0.5 * a.film_h * a.aspect / a.tau;
+        const double grx = r.inside && a.guv[0] ? cu * (double) a.guv[0][i] : 0.0;
+        const double gry = r.inside && a.guv[1] ? cv * (double) a.guv[1][i] : 0.0;
+        const double gW = r.valid && a.gweight ? r.W * (double) a.gweight[i] : 0.0;
+        // dL/dref and dL/d(ln tau)
+        const double gx = grx * r.iz + gW * r.x / r.r2;
+        const double gy = gry * r.iz + gW * r.y / r.r2;
+        const double gz = -(grx * r.rx + gry * r.ry) * r.iz + gW * (r.z / r.r2 - 3.0 * r.iz);
+        const bool any = r.inside; // (valid implies inside: a lane outside the clip range has no derivative)
+        double h[3]; // to_world^-T dL/dref = dL/dp
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            h[k] = any ? a.Ai[k] * gx + a.Ai[3 + k] * gy + a.Ai[6 + k] * gz : 0.0;
+            if (a.gp[k]) a.gp[k][i] = (float) h[k];
+            M[4 * k] -= h[k] * r.x; M[4 * k + 1] -= h[k] * r.y; M[4 * k + 2] -= h[k] * r.z; M[4 * k + 3] -= h[k];
+        }
+        M[12] -= any ? grx * r.rx + gry * r.ry + 2.0 * gW : 0.0;
+    }
+    sensor_block_store(M, a.slab);
+}
+
+void hf_launch_sensor_project(int mode, const hf_sensor_project_args &a, hipStream_t stream) {
+    if (mode == 1) {
+        const int grid = grid_for(a.n, HF_XFORM_GRID_CAP);
+        hipLaunchKernelGGL(hf_sensor_project_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        // column 12 holds dL/d(ln tau): times d tau / tau per degree
+        hipLaunchKernelGGL(hf_sensor_sum_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, a.slab, (uint32_t) grid, a.dtau / a.tau,
+                           a.g_tw, a.g_fov);
+        return;
+    }
+    hipLaunchKernelGGL(mode == 0 ? hf_sensor_project_kernel : hf_sensor_project_tangent_kernel,
+                       dim3(grid_for(a.n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, a);
+}
+
+// Which store variant hf_sensor_rays launches.  HF_SENSOR_WIDE_DEFAULT is the one that measured faster (DESIGN 4.23,
+// profiles/sensor/times.jsonl); TEST HOOK (include/hf.h): HF_SENSOR_STORE=dword|wide picks the other, so that the two can be
+// timed in one process and compared bit for bit.
+#ifndef HF_SENSOR_WIDE_DEFAULT
+#define HF_SENSOR_WIDE_DEFAULT 1
+#endif
+static bool sensor_wide_store() {
+    if (const char *e = getenv("HF_SENSOR_STORE")) {
+        if (!strcmp(e, "wide")) return true;
+        if (!strcmp(e, "dword")) return false;
+    }
+    return HF_SENSOR_WIDE_DEFAULT != 0;
+}
+void hf_launch_sensor(int mode, int type, const hf_sensor_args &a, hipStream_t stream) {
+    const bool persp = type == HF_SENSOR_PERSPECTIVE;
+    if (mode == 1) {
+        const int grid = grid_for(a.n, HF_XFORM_GRID_CAP); // the slab holds HF_XFORM_GRID_CAP rows
+        hipLaunchKernelGGL(persp ? hf_sensor_adjoint_kernel<HF_SENSOR_PERSPECTIVE> : hf_sensor_adjoint_kernel<HF_SENSOR_ORTHOGRAPHIC>,
+                           dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        hipLaunchKernelGGL(hf_sensor_sum_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, a.slab, (uint32_t) grid, a.dtau, a.g_tw,
+                           persp ? a.g_fov : nullptr);
+        return;
+    }
+    if (mode == 0 && sensor_wide_store() && a.n >= 64) {
+        hf_sensor_args w = a;
+        float *const row[HF_SENSOR_ROWS] = { a.out_o[0], a.out_o[1], a.out_o[2], a.out_d[0], a.out_d[1], a.out_d[2], a.out_maxt,
+                                             a.out_pos[0], a.out_pos[1] };
+        const uint32_t r0 = (uint32_t) (((uintptr_t) row[0] >> 2) & 3u);
+        w.head = (4u - r0) & 3u;
+        for (int k = 0; k < HF_SENSOR_ROWS; ++k)
+            if (row[k] && (((uintptr_t) row[k] >> 2) & 3u) == r0) w.wide_mask |= 1u << k;
+        const size_t groups = (a.n - w.head) >> 2;
+        hipLaunchKernelGGL(persp ? hf_sensor_rays_wide_kernel<HF_SENSOR_PERSPECTIVE> : hf_sensor_rays_wide_kernel<HF_SENSOR_ORTHOGRAPHIC>,
+                           dim3(grid_for(groups, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, w);
+        return;
+    }
+    const dim3 grid(grid_for(a.n, HF_SI_GRID_CAP)), block(HF_BLOCK);
+    if (mode == 0)
+        hipLaunchKernelGGL(persp ? hf_sensor_rays_kernel<HF_SENSOR_PERSPECTIVE> : hf_sensor_rays_kernel<HF_SENSOR_ORTHOGRAPHIC>,
+                           grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(persp ? hf_sensor_tangent_kernel<HF_SENSOR_PERSPECTIVE> : hf_sensor_tangent_kernel<HF_SENSOR_ORTHOGRAPHIC>,
+                           grid, block, 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
 // Large-steps preconditioning (include/hf.h): A = I + lambda L on the W x H vertex grid, L the combinatorial
 // Laplacian of the tessellation (every cell split along v10-v01), and conjugate gradients for A v = u.
 //

@@ -237,6 +237,50 @@ struct hf_rect_args {
 // mode 0: forward, 1: adjoint, 2: tangent, 3: rays.  The forward launch is hf_launch_sky's: the per-lane any-hit walk,
 // no work counter, no scratch block
 void hf_launch_rect(int mode, const hf_rect_args &a, hipStream_t stream);
+// ---- the sensor (hf_sensor_rays / _tangent / _adjoint): the one argument of its kernels; every constant is formed on
+// the host in double, so it is wave-uniform ----
+struct hf_sensor_args {
+    size_t n;
+    uint32_t start, spp, seed, crop_w, crop_x, crop_y;
+    int32_t spp_shift, crop_w_shift;         // log2 where spp / crop_w is a power of two, else -1 (a division)
+    uint32_t head, wide_mask;                // the 16-byte store variant only (set by the launcher): samples before the
+                                             // first aligned group; the rows that share out_o[0]'s alignment
+    double film_w, film_h, aspect;           // aspect = film_w / film_h
+    double A[9], c[3];                       // to_world = [A | c]
+    double near, tau, dtau;                  // tau = tan(x_fov pi / 360), dtau = (pi / 360) (1 + tau^2); orthographic: 1, 0
+    double span;                             // far - near
+    double An[3];                            // orthographic: A e_z near
+    double dz[3], inv_len_z;                 // orthographic: d = A e_z / |A e_z| and 1 / |A e_z|
+    const uint32_t *ray_id;                  // optional: the wavefront index of sample i (NULL: start + i)
+    float *out_o[3], *out_d[3], *out_maxt;   // forward; tangent: out_do, out_dd
+    float *out_pos[2];                       // forward, optional
+    const float *d_tw, *d_fov;               // tangent inputs (NULL: zero)
+    const float *go[3], *gd[3];              // adjoint inputs (NULL rows: zero)
+    double *slab;                            // adjoint: 13 doubles per block
+    float *g_tw, *g_fov;                     // adjoint outputs, accumulated (NULL: not wanted)
+};
+// mode 0: rays, 1: adjoint (two launches: the blocks' partial sums, their sum), 2: tangent
+void hf_launch_sensor(int mode, int type, const hf_sensor_args &a, hipStream_t stream);
+size_t hf_sensor_slab_doubles();             // the most any adjoint launch needs
+// ---- the way back (hf_sensor_project / _tangent / _adjoint; perspective only) ----
+struct hf_sensor_project_args {
+    size_t n;
+    double Ai[9], c[3];                      // to_world^-1's linear part (formed on the host in double), to_world's c
+    double near, far, tau, dtau, aspect;
+    double film_w, film_h, crop_x, crop_y, crop_w, crop_h;
+    double inv_area;                         // 1 / A', A' = (2 tau)^2 / a (crop_w crop_h) / (film_w film_h)
+    const float *p[3];
+    const uint8_t *active;                   // optional (NULL: every lane)
+    float *uv[2], *weight;                   // forward: written (weight optional); tangent: duv, dweight
+    uint8_t *valid;                          // forward
+    const float *dp[3], *d_tw, *d_fov;       // tangent inputs (NULL: zero)
+    const float *guv[2], *gweight;           // adjoint inputs (NULL: zero)
+    float *gp[3];                            // adjoint output rows, overwritten (NULL: not wanted)
+    double *slab;                            // adjoint: 13 doubles per block
+    float *g_tw, *g_fov;                     // adjoint outputs, accumulated (NULL: not wanted)
+};
+// mode 0: forward, 1: adjoint (two launches), 2: tangent
+void hf_launch_sensor_project(int mode, const hf_sensor_project_args &a, hipStream_t stream);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
