@@ -129,10 +129,10 @@ typedef struct hf_desc {
  * times (tests/test_gpu_grid_stride.py).  It only ever lowers the grid, so scratch and captured launches stay within
  * what they reserve; any other value is ignored.  Results do not depend on it except through the order of float
  * additions (atomic scatters, the per-block sums of dL/d(to_world)); per-lane outputs keep their bytes.
- * TEST HOOK: the environment variable HF_SENSOR_STORE=dword|wide, read at every hf_sensor_rays, picks the store variant of
- * its kernel (one sample per lane and 4-byte stores, or four per lane and one 16-byte store per row where the row is
- * aligned) instead of the one the library was built to use; any other value is ignored.  Results do not
- * depend on it: the two variants write the same bytes (tests/test_gpu_sensor.py). */
+ * TEST HOOK: the environment variable HF_SENSOR_STORE=dword|wide, read at every hf_sensor_rays and hf_thinlens_rays,
+ * picks the store variant of its kernel (one sample per lane and 4-byte stores, or four per lane and one 16-byte store per
+ * row where the row is aligned) instead of the one the library was built to use; any other value is ignored.
+ * Results do not depend on it: the two variants write the same bytes (tests/test_gpu_sensor.py, test_gpu_thinlens.py). */
 typedef struct hf_rays {
     const float *o[3];
     const float *d[3];
@@ -1260,8 +1260,8 @@ int hf_rect_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], co
  * atomics: every block stores its 13 partial sums in double to `workspace` -- hf_sensor_workspace_floats() floats of
  * device memory, 8-byte aligned, the caller's, exclusively this call's until it has completed -- and one more launch adds
  * them in a fixed order (family 2 of hf_grid_blocks): bitwise the same from launch to launch, capturable.
- * OUT OF SCOPE: the principal point offset, sample_border, the thin lens, the d_x / d_y of sample_ray_differential,
- * wavelengths and time.
+ * OUT OF SCOPE: the principal point offset, sample_border, the d_x / d_y of sample_ray_differential, wavelengths and
+ * time.  (The thin lens is hf_thinlens_*, below.)
  *
  * hf_sensor_project is the way back, the perspective sensor's sample_direction (perspective.cpp:279-318, 334-383), for
  * points p (3 device rows of n floats) and an optional byte row `active` (NULL: every lane):
@@ -1316,6 +1316,82 @@ int hf_sensor_project_tangent(const hf_sensor_t *sensor, size_t n, const float *
 int hf_sensor_project_adjoint(const hf_sensor_t *sensor, size_t n, const float *const p[3], const uint8_t *active,
                               const float *const grad_uv[2], const float *grad_weight, float *const grad_p[3],
                               float *grad_to_world, float *grad_fov, float *workspace, hf_stream_t stream);
+
+/* ---- the thin lens: the perspective sensor with a finite aperture, depth of field, differentiable ----
+ *
+ * Replaces Sensor::sample_ray and sample_direction of `thinlens` (src/sensors/thinlens.cpp:216-254, 305-350).  hf_sensor_t
+ * and every hf_sensor_* entry stay as they are; the lens is a struct of its own around one:
+ *   lens        hf_thinlens_t, HOST memory.  base: the sensor, type HF_SENSOR_PERSPECTIVE; aperture_radius r >= 0 (0 is the
+ *               pinhole: the same rays as hf_sensor_rays up to the rounding of the outputs; the reference replaces 0 by an
+ *               epsilon, thinlens.cpp:158-161); focus_distance f > 0.
+ *   sampling    the index, the pixel, the jitter, pos, g and w are exactly hf_sensor_rays'.  The aperture sample is a second
+ *               draw in the keyed convention of the lighting rows: key = sample_tea_32(seed, HF_THINLENS_PAIR).v0,
+ *               (a0, a1) = sample_tea_32(key, id), s = (a >> 9) 2^-23.  The pair lies outside 0..31, so a lighting row on
+ *               the same seed shares no number with the lens.
+ *   D           = (D.x, D.y, 0) = square_to_uniform_disk_concentric(s) (warp.h; thinlens.cpp:235-236), evaluated in double
+ *               from the exact float s, the sine and cosine taken of an argument of at most pi / 4.
+ * Rays, with tau and v = (w.x tau, w.y tau, 1) as above (near_p = near v, :231-232; focus_p = f v, :239):
+ *   e = f v - r D,   d_c = e / |e| (:242),   ray.d = A d_c (:245),
+ *   ray.o = c + A (r (1 - near / f) D + near v) = to_world aperture_p + ray.d near / d_c.z (:244-250),
+ *   maxt = (far - near) |e| / f (:247-251).
+ * Everything in double, every output rounded once; one grid-stride launch in the store variants of hf_sensor_rays (the
+ * same HF_SENSOR_STORE hook, the same grids); allocates nothing, never synchronises the host, capturable.
+ *
+ * Differentiated with respect to to_world (12), x_fov (through tau), aperture_radius and focus_distance -- an extension:
+ * the reference marks all four NonDifferentiable (:171-177).  maxt, the pixel, the jitter and the disk point are HELD.
+ * With u = (w.x, w.y, 0) and o_c = r (1 - near / f) D + near v:
+ *   de = f u dtau + v df - D dr,   d d_c = (de - d_c <d_c, de>) / |e|,   d ray.d = dA d_c + A d d_c,
+ *   d o_c = (1 - near / f) D dr + (r near / f^2) D df + near u dtau,   d ray.o = dc + dA o_c + A d o_c.
+ * hf_thinlens_rays_tangent: d_to_world (12 device floats), d_fov, d_radius, d_focus (1 device float each), each may be
+ * NULL (zero).  hf_thinlens_rays_adjoint: the exact transpose; grad_to_world (12), grad_fov, grad_radius, grad_focus (1
+ * each) are ACCUMULATED into, each may be NULL.  15 sums per lane in double, per block to `workspace`
+ * (hf_thinlens_workspace_floats() floats, 8-byte aligned, this call's until it has completed), then one fixed-order sum
+ * launch: no float atomics, bitwise repeatable, capturable -- hf_sensor_rays_adjoint's pattern with rows of 15.
+ *
+ * hf_thinlens_project is the way back (:305-350).  Lane i uses ITS OWN aperture draw -- that of the wavefront index
+ * start + i, or ray_id[i] -- so that the projection of a point of sample i's ray is pos_i:
+ *   ref       = A^-1 (p - c) (:309-310);   inside_z = active and near <= ref.z <= far (:315);
+ *   q         = ref - r D (:324);   F = r D + q f / q.z (:333; its z is f);
+ *   g         = ((1 - F.x / (f tau)) / 2, (1 - a F.y / (f tau)) / 2),   uv = g film_size (:340);
+ *   valid     = inside_z and s_crop in [0, 1]^2 (:334; the reference also tests scr.z, which says near <= f <= far);
+ *   weight    = |q| / (A' q.z^3) with hf_sensor_project's A': m_normalization inv_ct^3 / dist^2 (:335, 349).
+ * What is written, and the stated deviation from the reference's early returns, are hf_sensor_project's.  Derivatives
+ * with respect to p (per lane), to_world, x_fov, r and f, the masks and D HELD; the tangent and the adjoint take the same
+ * start, seed and ray_id; grad_p is OVERWRITTEN, the reduced gradients are ACCUMULATED into through the workspace.
+ * OUT OF SCOPE: ds.p, ds.d, ds.dist and the aperture pdf of sample_direction; the d_x / d_y of
+ * sample_ray_differential; wavelengths and time.
+ * All entries refuse with HF_EINVAL, before anything touches a device: everything hf_sensor_rays (hf_sensor_project)
+ * refuses for a perspective sensor, base.type != HF_SENSOR_PERSPECTIVE, a non-finite or negative aperture_radius, a
+ * non-finite or non-positive focus_distance.  n == 0 is legal.  Callers detect the entries by their symbols (HF_VERSION
+ * is unchanged). */
+typedef struct hf_thinlens {        /* HOST memory */
+    hf_sensor_t base;               /* type must be HF_SENSOR_PERSPECTIVE */
+    double aperture_radius;         /* >= 0, finite; 0 is the pinhole */
+    double focus_distance;          /* > 0, finite */
+} hf_thinlens_t;
+#define HF_THINLENS_PAIR 0x4C454E53u
+int hf_thinlens_rays(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                     const uint32_t *ray_id, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                     float *const out_pos[2], hf_stream_t stream);
+int hf_thinlens_rays_tangent(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                             const uint32_t *ray_id, const float *d_to_world, const float *d_fov, const float *d_radius,
+                             const float *d_focus, float *const out_do[3], float *const out_dd[3], hf_stream_t stream);
+size_t hf_thinlens_workspace_floats(void);
+int hf_thinlens_rays_adjoint(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                             const uint32_t *ray_id, const float *const grad_o[3], const float *const grad_d[3],
+                             float *grad_to_world, float *grad_fov, float *grad_radius, float *grad_focus, float *workspace,
+                             hf_stream_t stream);
+int hf_thinlens_project(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t seed, const uint32_t *ray_id,
+                        const float *const p[3], const uint8_t *active, float *const uv[2], uint8_t *valid, float *weight,
+                        hf_stream_t stream);
+int hf_thinlens_project_tangent(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t seed, const uint32_t *ray_id,
+                                const float *const p[3], const uint8_t *active, const float *const dp[3],
+                                const float *d_to_world, const float *d_fov, const float *d_radius, const float *d_focus,
+                                float *const duv[2], float *dweight, hf_stream_t stream);
+int hf_thinlens_project_adjoint(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t seed, const uint32_t *ray_id,
+                                const float *const p[3], const uint8_t *active, const float *const grad_uv[2],
+                                const float *grad_weight, float *const grad_p[3], float *grad_to_world, float *grad_fov,
+                                float *grad_radius, float *grad_focus, float *workspace, hf_stream_t stream);
 
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *

@@ -8,4 +8,4 @@ from .shape import (Adam, Bitmap, DirectionSample3f, Envmap, Frame3f, Heightfiel
                     dielectric_lighting, direct_lighting, envmap_lighting, envmap_rays, film_gaussian, glossy_lighting, glossy_rays,
                     point_lighting, rect_lighting, rect_rays, reflection_lighting, reflection_rays, refraction_lighting, reparameterize_ray, reparameterize_ray_adjoint, reparameterize_ray_tangent,
                     sky_lighting, sky_rays)
-from .sensor import OrthographicCamera, PerspectiveCamera  # noqa: F401
+from .sensor import OrthographicCamera, PerspectiveCamera, ThinLensCamera  # noqa: F401

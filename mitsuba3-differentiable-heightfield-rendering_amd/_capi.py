@@ -88,7 +88,28 @@ class hf_sensor_t(C.Structure):
 _sensor_in = [C.POINTER(hf_sensor_t), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _fp]  # sensor, n, start, spp, seed, ray_id
 _project_in = [C.POINTER(hf_sensor_t), C.c_size_t, C.POINTER(_fp * 3), _fp]  # sensor, n, p, active
 
+HF_THINLENS_PAIR = 0x4C454E53
+
+
+class hf_thinlens_t(C.Structure):
+    _fields_ = [("base", hf_sensor_t), ("aperture_radius", C.c_double), ("focus_distance", C.c_double)]
+
+
+_lens_in = [C.POINTER(hf_thinlens_t), *_sensor_in[1:]]  # lens, n, start, spp, seed, ray_id
+# lens, n, start, seed, ray_id, p, active
+_lens_project_in = [C.POINTER(hf_thinlens_t), C.c_size_t, C.c_uint32, C.c_uint32, _fp, C.POINTER(_fp * 3), _fp]
+
 SYMBOLS = {
+    "hf_thinlens_rays": (C.c_int, [*_lens_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 2), C.c_void_p]),
+    "hf_thinlens_rays_tangent": (C.c_int, [*_lens_in, _fp, _fp, _fp, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p]),
+    "hf_thinlens_workspace_floats": (C.c_size_t, []),
+    "hf_thinlens_rays_adjoint": (C.c_int, [*_lens_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, _fp,
+                                           C.c_void_p]),
+    "hf_thinlens_project": (C.c_int, [*_lens_project_in, C.POINTER(_fp * 2), _fp, _fp, C.c_void_p]),
+    "hf_thinlens_project_tangent": (C.c_int, [*_lens_project_in, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, C.POINTER(_fp * 2),
+                                              _fp, C.c_void_p]),
+    "hf_thinlens_project_adjoint": (C.c_int, [*_lens_project_in, C.POINTER(_fp * 2), _fp, C.POINTER(_fp * 3), _fp, _fp, _fp,
+                                              _fp, _fp, C.c_void_p]),
     "hf_sensor_rays": (C.c_int, [*_sensor_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 2), C.c_void_p]),
     "hf_sensor_rays_tangent": (C.c_int, [*_sensor_in, _fp, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p]),
     "hf_sensor_workspace_floats": (C.c_size_t, []),

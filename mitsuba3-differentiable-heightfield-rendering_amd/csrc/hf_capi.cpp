@@ -1835,6 +1835,155 @@ extern "C" int hf_sensor_project_adjoint(const hf_sensor_t *sensor, size_t n, co
     return sensor_project_launch(1, a, stream);
 }
 
+// ---- the thin lens: the perspective sensor with an aperture ----
+// the checks of the lens alone, what every hf_thinlens_* entry starts with (the base's follow in sensor_args)
+static int thinlens_checks(const char *who, const hf_thinlens_t *l) {
+    if (!l) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (l->base.type != HF_SENSOR_PERSPECTIVE)
+        return fail(HF_EINVAL, "%s: the lens's base.type must be HF_SENSOR_PERSPECTIVE (got %d)", who, l->base.type);
+    if (!isfinite(l->aperture_radius) || l->aperture_radius < 0.0)
+        return fail(HF_EINVAL, "%s: aperture_radius must be finite and not negative (got %g)", who, l->aperture_radius);
+    if (!isfinite(l->focus_distance) || !(l->focus_distance > 0.0))
+        return fail(HF_EINVAL, "%s: focus_distance must be finite and positive (got %g)", who, l->focus_distance);
+    return HF_OK;
+}
+static int thinlens_args(const char *who, const hf_thinlens_t *l, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                         const uint32_t *ray_id, hf_thinlens_args &a) {
+    a = {};
+    int rc = thinlens_checks(who, l);
+    if (rc != HF_OK) return rc;
+    if ((rc = sensor_args(who, &l->base, n, start, spp, seed, ray_id, a.s)) != HF_OK) return rc;
+    a.radius = l->aperture_radius; a.focus = l->focus_distance;
+    a.lens_o = a.radius * (1.0 - a.s.near / a.focus);
+    a.maxt_scale = a.s.span / a.focus;
+    return HF_OK;
+}
+static int thinlens_launch(int mode, const hf_thinlens_args &a, hf_stream_t stream) {
+    if (a.s.n == 0) return HF_OK;
+    hf_launch_thinlens(mode, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_thinlens_rays(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                                const uint32_t *ray_id, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                                float *const out_pos[2], hf_stream_t stream) {
+    const char *fn = "hf_thinlens_rays";
+    hf_thinlens_args a;
+    const int rc = thinlens_args(fn, lens, n, start, spp, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (out_pos && (!out_pos[0] || !out_pos[1])) return fail(HF_EINVAL, "%s: NULL out_pos component array", fn);
+    for (int k = 0; k < 3; ++k) { a.s.out_o[k] = out_o[k]; a.s.out_d[k] = out_d[k]; }
+    a.s.out_maxt = out_maxt;
+    for (int k = 0; k < 2; ++k) a.s.out_pos[k] = out_pos ? out_pos[k] : nullptr;
+    return thinlens_launch(0, a, stream);
+}
+
+extern "C" int hf_thinlens_rays_tangent(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                                        const uint32_t *ray_id, const float *d_to_world, const float *d_fov,
+                                        const float *d_radius, const float *d_focus, float *const out_do[3],
+                                        float *const out_dd[3], hf_stream_t stream) {
+    const char *fn = "hf_thinlens_rays_tangent";
+    hf_thinlens_args a;
+    const int rc = thinlens_args(fn, lens, n, start, spp, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(out_do) || !all3(out_dd)) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    for (int k = 0; k < 3; ++k) { a.s.out_o[k] = out_do[k]; a.s.out_d[k] = out_dd[k]; }
+    a.s.d_tw = d_to_world; a.s.d_fov = d_fov; a.d_radius = d_radius; a.d_focus = d_focus;
+    return thinlens_launch(2, a, stream);
+}
+
+extern "C" size_t hf_thinlens_workspace_floats(void) { return 2u * hf_thinlens_slab_doubles(); }
+
+extern "C" int hf_thinlens_rays_adjoint(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t spp, uint32_t seed,
+                                        const uint32_t *ray_id, const float *const grad_o[3], const float *const grad_d[3],
+                                        float *grad_to_world, float *grad_fov, float *grad_radius, float *grad_focus,
+                                        float *workspace, hf_stream_t stream) {
+    const char *fn = "hf_thinlens_rays_adjoint";
+    hf_thinlens_args a;
+    const int rc = thinlens_args(fn, lens, n, start, spp, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (grad_o && !all3(grad_o)) return fail(HF_EINVAL, "%s: NULL grad_o component array", fn);
+    if (grad_d && !all3(grad_d)) return fail(HF_EINVAL, "%s: NULL grad_d component array", fn);
+    if (!workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    for (int k = 0; k < 3; ++k) { a.s.go[k] = grad_o ? grad_o[k] : nullptr; a.s.gd[k] = grad_d ? grad_d[k] : nullptr; }
+    a.s.slab = (double *) workspace; a.s.g_tw = grad_to_world; a.s.g_fov = grad_fov;
+    a.g_radius = grad_radius; a.g_focus = grad_focus;
+    return thinlens_launch(1, a, stream);
+}
+
+// What hf_thinlens_project and its two derivatives share
+static int thinlens_project_args(const char *who, const hf_thinlens_t *l, size_t n, uint32_t start, uint32_t seed,
+                                 const uint32_t *ray_id, const float *const p[3], const uint8_t *active,
+                                 hf_thinlens_project_args &a) {
+    a = {};
+    int rc = thinlens_checks(who, l);
+    if (rc != HF_OK) return rc;
+    if ((rc = sensor_project_args(who, &l->base, n, p, active, a.s)) != HF_OK) return rc;
+    if (!ray_id && (uint64_t) start + (uint64_t) n > (1ull << 32))
+        return fail(HF_EINVAL, "%s: start + n must not exceed 2^32 without ray_id", who);
+    a.start = start; a.seed = seed; a.ray_id = ray_id;
+    a.radius = l->aperture_radius; a.focus = l->focus_distance;
+    return HF_OK;
+}
+static int thinlens_project_launch(int mode, const hf_thinlens_project_args &a, hf_stream_t stream) {
+    if (a.s.n == 0) return HF_OK;
+    hf_launch_thinlens_project(mode, a, (hipStream_t) stream);
+    HF_HIP(hipGetLastError());
+    return HF_OK;
+}
+
+extern "C" int hf_thinlens_project(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t seed, const uint32_t *ray_id,
+                                   const float *const p[3], const uint8_t *active, float *const uv[2], uint8_t *valid,
+                                   float *weight, hf_stream_t stream) {
+    const char *fn = "hf_thinlens_project";
+    hf_thinlens_project_args a;
+    const int rc = thinlens_project_args(fn, lens, n, start, seed, ray_id, p, active, a);
+    if (rc != HF_OK) return rc;
+    if (!uv || !uv[0] || !uv[1] || !valid) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.s.uv[0] = uv[0]; a.s.uv[1] = uv[1]; a.s.valid = valid; a.s.weight = weight;
+    return thinlens_project_launch(0, a, stream);
+}
+
+extern "C" int hf_thinlens_project_tangent(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t seed,
+                                           const uint32_t *ray_id, const float *const p[3], const uint8_t *active,
+                                           const float *const dp[3], const float *d_to_world, const float *d_fov,
+                                           const float *d_radius, const float *d_focus, float *const duv[2], float *dweight,
+                                           hf_stream_t stream) {
+    const char *fn = "hf_thinlens_project_tangent";
+    hf_thinlens_project_args a;
+    const int rc = thinlens_project_args(fn, lens, n, start, seed, ray_id, p, active, a);
+    if (rc != HF_OK) return rc;
+    if (!duv || !duv[0] || !duv[1]) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (dp && !all3(dp)) return fail(HF_EINVAL, "%s: NULL dp component array", fn);
+    for (int k = 0; k < 3; ++k) a.s.dp[k] = dp ? dp[k] : nullptr;
+    a.s.d_tw = d_to_world; a.s.d_fov = d_fov; a.d_radius = d_radius; a.d_focus = d_focus;
+    a.s.uv[0] = duv[0]; a.s.uv[1] = duv[1]; a.s.weight = dweight;
+    return thinlens_project_launch(2, a, stream);
+}
+
+extern "C" int hf_thinlens_project_adjoint(const hf_thinlens_t *lens, size_t n, uint32_t start, uint32_t seed,
+                                           const uint32_t *ray_id, const float *const p[3], const uint8_t *active,
+                                           const float *const grad_uv[2], const float *grad_weight, float *const grad_p[3],
+                                           float *grad_to_world, float *grad_fov, float *grad_radius, float *grad_focus,
+                                           float *workspace, hf_stream_t stream) {
+    const char *fn = "hf_thinlens_project_adjoint";
+    hf_thinlens_project_args a;
+    const int rc = thinlens_project_args(fn, lens, n, start, seed, ray_id, p, active, a);
+    if (rc != HF_OK) return rc;
+    if (grad_uv && (!grad_uv[0] || !grad_uv[1])) return fail(HF_EINVAL, "%s: NULL grad_uv component array", fn);
+    if (grad_p && (!grad_p[0] || !grad_p[1] || !grad_p[2])) return fail(HF_EINVAL, "%s: NULL grad_p component array", fn);
+    if (!workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    for (int k = 0; k < 2; ++k) a.s.guv[k] = grad_uv ? grad_uv[k] : nullptr;
+    for (int k = 0; k < 3; ++k) a.s.gp[k] = grad_p ? grad_p[k] : nullptr;
+    a.s.gweight = grad_weight; a.s.slab = (double *) workspace; a.s.g_tw = grad_to_world; a.s.g_fov = grad_fov;
+    a.g_radius = grad_radius; a.g_focus = grad_focus;
+    return thinlens_project_launch(1, a, stream);
+}
+
 // ---- environment-map lighting: importance-sampled latitude-longitude map, the shadow rays traced in the kernel ----
 // What every entry that reads a map shares, the reflection rows' too: the checks of the map (A: a block with W, H, data
 // and rot, zeroed by the caller), in two pieces because the entries check other things between them: the texels ...

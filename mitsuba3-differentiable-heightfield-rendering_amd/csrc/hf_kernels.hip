@@ -1213,7 +1213,7 @@ __device__ __forceinline__ bool walk_beam(const hf_dev_field &f, const hf_ray_st
 // ---------------------------------------------------------------------------------
 // Warped-area reparameterisation (include/hf.h; reparam.py:10-123,224-333): per-sample kernels
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ void tea32(uint32_t v0, uint32_t v1, uint32_t &o0, uint32_t &o1) { // random.h:76-91
+__host__ __device__ __forceinline__ void tea32(uint32_t v0, uint32_t v1, uint32_t &o0, uint32_t &o1) { // random.h:76-91
     uint32_t sum = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -6812,29 +6812,37 @@ __device__ __forceinline__ void sensor_ray(const hf_sensor_args &a, size_t i, fl
         r[6] = (float) a.span;
     }
 }
+// (ARGS: hf_sensor_args, or the thin lens's block around one -- sensor_base is the block the store code reads)
+__device__ __forceinline__ const hf_sensor_args &sensor_base(const hf_sensor_args &a) { return a; }
 // the dword path: sample i to element i of every row that is wanted
-template <int TYPE>
-__device__ __forceinline__ void sensor_ray_store(const hf_sensor_args &a, size_t i) {
+template <int TYPE, class ARGS>
+__device__ __forceinline__ void sensor_ray_store(const ARGS &args, size_t i) {
+    const hf_sensor_args &a = sensor_base(args);
     float r[HF_SENSOR_ROWS];
-    sensor_ray<TYPE>(a, i, r);
+    sensor_ray<TYPE>(args, i, r);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { a.out_o[k][i] = r[k]; a.out_d[k][i] = r[3 + k]; }
     a.out_maxt[i] = r[6];
     if (a.out_pos[0]) { a.out_pos[0][i] = r[7]; a.out_pos[1][i] = r[8]; }
 }
+template <int TYPE, class ARGS>
+__device__ __forceinline__ void sensor_rays_dword(const ARGS &args) {
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < sensor_base(args).n; i += (size_t) gridDim.x * HF_BLOCK)
+        sensor_ray_store<TYPE>(args, i);
+}
 // variant A: one sample per lane, a wave stores 256 contiguous bytes of every row
 template <int TYPE>
 __global__ __launch_bounds__(HF_BLOCK) void hf_sensor_rays_kernel(hf_sensor_args a) {
-    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK)
-        sensor_ray_store<TYPE>(a, i);
+    sensor_rays_dword<TYPE>(a);
 }
 // variant B: four consecutive samples per lane, one 16-byte store per row.  a.head samples come before the first group,
 // so that element a.head of out_o[0] is 16-byte aligned; bit k of a.wide_mask says that row k has the same alignment
 // (its groups are stored as one float4), any other row takes four dword stores per group; the head and the tail (fewer
 // than 4 + 4 samples) take the dword path on the first lanes of the grid.
 typedef float hf_sensor_f4 __attribute__((ext_vector_type(4)));
-template <int TYPE>
-__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_rays_wide_kernel(hf_sensor_args a) {
+template <int TYPE, class ARGS>
+__device__ __forceinline__ void sensor_rays_wide(const ARGS &args) {
+    const hf_sensor_args &a = sensor_base(args);
     float *const row[HF_SENSOR_ROWS] = { a.out_o[0], a.out_o[1], a.out_o[2], a.out_d[0], a.out_d[1], a.out_d[2], a.out_maxt,
                                          a.out_pos[0], a.out_pos[1] };
     const size_t tid = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
@@ -6843,7 +6851,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sensor_rays_wide_kernel(hf_sensor
         const size_t i0 = a.head + 4 * g;
         float r[4][HF_SENSOR_ROWS];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sensor_ray<TYPE>(a, i0 + j, r[j]);
+        for (int j = 0; j < 4; ++j) sensor_ray<TYPE>(args, i0 + j, r[j]);
 #pragma unroll
         for (int k = 0; k < HF_SENSOR_ROWS; ++k) {
             if (!row[k]) continue;
@@ -6857,7 +6865,11 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sensor_rays_wide_kernel(hf_sensor
         }
     }
     const size_t tail0 = a.head + 4 * groups, rest = a.head + (a.n - tail0);
-    if (tid < rest) sensor_ray_store<TYPE>(a, tid < a.head ? tid : tail0 + (tid - a.head));
+    if (tid < rest) sensor_ray_store<TYPE>(args, tid < a.head ? tid : tail0 + (tid - a.head));
+}
+template <int TYPE>
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_rays_wide_kernel(hf_sensor_args a) {
+    sensor_rays_wide<TYPE>(a);
 }
 
 template <int TYPE>
@@ -6901,20 +6913,21 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 // the block's sums of M into slab row blockIdx.x; every thread of the block calls it
-__device__ __forceinline__ void sensor_block_store(const double M[HF_SENSOR_SUMS], double *slab) {
-    __shared__ double s_red[HF_BLOCK / 64][HF_SENSOR_SUMS];
+template <int SUMS>
+__device__ __forceinline__ void sensor_block_store(const double M[SUMS], double *slab) {
+    __shared__ double s_red[HF_BLOCK / 64][SUMS];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
 #pragma unroll
-    for (int j = 0; j < HF_SENSOR_SUMS; ++j) {
+    for (int j = 0; j < SUMS; ++j) {
         const double v = wave_sum_f64(M[j]);
         if (lane == 0u) s_red[w][j] = v;
     }
     __syncthreads();
-    if (threadIdx.x < HF_SENSOR_SUMS) {
+    if (threadIdx.x < SUMS) {
         double v = s_red[0][threadIdx.x];
 #pragma unroll
         for (int k = 1; k < HF_BLOCK / 64; ++k) v += s_red[k][threadIdx.x];
-        slab[(size_t) blockIdx.x * HF_SENSOR_SUMS + threadIdx.x] = v;
+        slab[(size_t) blockIdx.x * SUMS + threadIdx.x] = v;
     }
 }
 template <int TYPE>
@@ -6956,36 +6969,43 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sensor_adjoint_kernel(hf_sensor_a
             }
         }
     }
-    sensor_block_store(M, a.slab);
+    sensor_block_store<HF_SENSOR_SUMS>(M, a.slab);
 }
 // g_tw[j] += column j of the slab's rows, g_fov[0] += dtau * column 12: every thread adds every HF_BLOCK-th row, then a
 // fixed-order tree over the block through LDS.  One block.
-__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_sum_kernel(const double *__restrict__ slab, uint32_t rows, double dtau,
-                                                                  float *__restrict__ g_tw, float *__restrict__ g_fov) {
-    __shared__ double s_part[HF_BLOCK][HF_SENSOR_SUMS];
+// (sensor_slab_sums: the columns' sums, readable by every thread of the one block once it returns)
+template <int SUMS>
+__device__ __forceinline__ const double *sensor_slab_sums(const double *__restrict__ slab, uint32_t rows) {
+    __shared__ double s_part[HF_BLOCK][SUMS];
     const uint32_t t = threadIdx.x;
-    double acc[HF_SENSOR_SUMS];
+    double acc[SUMS];
 #pragma unroll
-    for (int j = 0; j < HF_SENSOR_SUMS; ++j) acc[j] = 0.0;
+    for (int j = 0; j < SUMS; ++j) acc[j] = 0.0;
     for (uint32_t b = t; b < rows; b += HF_BLOCK) {
 #pragma unroll
-        for (int j = 0; j < HF_SENSOR_SUMS; ++j) acc[j] += slab[(size_t) b * HF_SENSOR_SUMS + j];
+        for (int j = 0; j < SUMS; ++j) acc[j] += slab[(size_t) b * SUMS + j];
     }
 #pragma unroll
-    for (int j = 0; j < HF_SENSOR_SUMS; ++j) s_part[t][j] = acc[j];
+    for (int j = 0; j < SUMS; ++j) s_part[t][j] = acc[j];
     __syncthreads();
 #pragma unroll
     for (uint32_t h = HF_BLOCK / 2; h > 0; h >>= 1) {
         if (t < h) {
 #pragma unroll
-            for (int j = 0; j < HF_SENSOR_SUMS; ++j) s_part[t][j] += s_part[t + h][j];
+            for (int j = 0; j < SUMS; ++j) s_part[t][j] += s_part[t + h][j];
         }
         __syncthreads();
     }
+    return s_part[0];
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_sensor_sum_kernel(const double *__restrict__ slab, uint32_t rows, double dtau,
+                                                                  float *__restrict__ g_tw, float *__restrict__ g_fov) {
+    const double *const sum = sensor_slab_sums<HF_SENSOR_SUMS>(slab, rows);
+    const uint32_t t = threadIdx.x;
     if (t < 12u) {
-        if (g_tw) g_tw[t] += (float) s_part[0][t];
+        if (g_tw) g_tw[t] += (float) sum[t];
     } else if (t == 12u && g_fov) {
-        g_fov[0] += (float) (s_part[0][12] * dtau);
+        g_fov[0] += (float) (sum[12] * dtau);
     }
 }
 size_t hf_sensor_slab_doubles() { return (size_t) HF_XFORM_GRID_CAP * HF_SENSOR_SUMS; }
@@ -7069,7 +7089,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_sensor_project_adjoint_kernel(hf_
         }
         M[12] -= any ? grx * r.rx + gry * r.ry + 2.0 * gW : 0.0;
     }
-    sensor_block_store(M, a.slab);
+    sensor_block_store<HF_SENSOR_SUMS>(M, a.slab);
 }
 
 void hf_launch_sensor_project(int mode, const hf_sensor_project_args &a, hipStream_t stream) {
@@ -7098,6 +7118,16 @@ static bool sensor_wide_store() {
     }
     return HF_SENSOR_WIDE_DEFAULT != 0;
 }
+// the 16-byte variant's head and wide_mask from the rows' addresses; returns the number of four-sample groups
+static size_t sensor_wide_groups(hf_sensor_args &w) {
+    float *const row[HF_SENSOR_ROWS] = { w.out_o[0], w.out_o[1], w.out_o[2], w.out_d[0], w.out_d[1], w.out_d[2], w.out_maxt,
+                                         w.out_pos[0], w.out_pos[1] };
+    const uint32_t r0 = (uint32_t) (((uintptr_t) row[0] >> 2) & 3u);
+    w.head = (4u - r0) & 3u;
+    for (int k = 0; k < HF_SENSOR_ROWS; ++k)
+        if (row[k] && (((uintptr_t) row[k] >> 2) & 3u) == r0) w.wide_mask |= 1u << k;
+    return (w.n - w.head) >> 2;
+}
 void hf_launch_sensor(int mode, int type, const hf_sensor_args &a, hipStream_t stream) {
     const bool persp = type == HF_SENSOR_PERSPECTIVE;
     if (mode == 1) {
@@ -7110,13 +7140,7 @@ void hf_launch_sensor(int mode, int type, const hf_sensor_args &a, hipStream_t s
     }
     if (mode == 0 && sensor_wide_store() && a.n >= 64) {
         hf_sensor_args w = a;
-        float *const row[HF_SENSOR_ROWS] = { a.out_o[0], a.out_o[1], a.out_o[2], a.out_d[0], a.out_d[1], a.out_d[2], a.out_maxt,
-                                             a.out_pos[0], a.out_pos[1] };
-        const uint32_t r0 = (uint32_t) (((uintptr_t) row[0] >> 2) & 3u);
-        w.head = (4u - r0) & 3u;
-        for (int k = 0; k < HF_SENSOR_ROWS; ++k)
-            if (row[k] && (((uintptr_t) row[k] >> 2) & 3u) == r0) w.wide_mask |= 1u << k;
-        const size_t groups = (a.n - w.head) >> 2;
+        const size_t groups = sensor_wide_groups(w);
         hipLaunchKernelGGL(persp ? hf_sensor_rays_wide_kernel<HF_SENSOR_PERSPECTIVE> : hf_sensor_rays_wide_kernel<HF_SENSOR_ORTHOGRAPHIC>,
                            dim3(grid_for(groups, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, w);
         return;
@@ -7128,6 +7152,282 @@ void hf_launch_sensor(int mode, int type, const hf_sensor_args &a, hipStream_t s
     else
         hipLaunchKernelGGL(persp ? hf_sensor_tangent_kernel<HF_SENSOR_PERSPECTIVE> : hf_sensor_tangent_kernel<HF_SENSOR_ORTHOGRAPHIC>,
                            grid, block, 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
+// The thin lens (include/hf.h): the perspective sensor with an aperture of radius r focused at the distance f
+// (thinlens.cpp:216-254, 305-350).  The film sample, the store code and the reducer are the sensor's; what is new per
+// sample is one more TEA draw, the concentric disk in double and e = f v - r D in place of v.  One sample per lane, the
+// constants wave-uniform kernel arguments, double arithmetic, every output rounded once; 15 sums (to_world's 12, tau's,
+// r's, f's) where the sensor has 13.
+// ---------------------------------------------------------------------------------
+#define HF_THINLENS_TYPE 2 // the TYPE of the shared store templates (no hf_sensor_t carries it)
+#define HF_THINLENS_SUMS 15
+__device__ __forceinline__ const hf_sensor_args &sensor_base(const hf_thinlens_args &a) { return a.s; }
+// the stream of the aperture samples: sky_sample's keyed convention with a pair no lighting row draws; the key is one
+// more constant formed on the host (by the launchers below)
+static uint32_t thinlens_key(uint32_t seed) {
+    uint32_t key, unused;
+    tea32(seed, HF_THINLENS_PAIR, key, unused);
+    return key;
+}
+// D = square_to_uniform_disk_concentric (warp.h, as bounce_disk has it) of the sample (a >> 9) 2^-23 of tea32(key, id), in
+// double from the exact float: phi / pi = rp / (4 r) is at most 1/4, the other quadrant pair swaps sine and cosine
+struct hf_lens_disk { double x, y; };
+__device__ __forceinline__ hf_lens_disk thinlens_disk(uint32_t key, uint32_t id) {
+    uint32_t a0, a1;
+    tea32(key, id, a0, a1);
+    const double x = 2.0 * ((double) (a0 >> 9) * (1.0 / 8388608.0)) - 1.0, y = 2.0 * ((double) (a1 >> 9) * (1.0 / 8388608.0)) - 1.0;
+    const bool q13 = __builtin_fabs(x) < __builtin_fabs(y);
+    const double r = q13 ? y : x, rp = q13 ? x : y;
+    const double a = r == 0.0 ? 0.0 : 0.25 * rp / r; // (|rp| <= |r|: r == 0 is the centre)
+    const auto [sn, cs] = light_sincos_f64(3.141592653589793 * a);
+    return hf_lens_disk{ r * (q13 ? sn : cs), r * (q13 ? cs : sn) };
+}
+__device__ __forceinline__ uint32_t thinlens_id(const hf_sensor_args &s, size_t i) { return s.ray_id ? s.ray_id[i] : s.start + (uint32_t) i; }
+// e = f v - r D (thinlens.cpp:239-242), its length and d_c = e / |e|; v = (vx, vy, 1) as the perspective sensor's
+struct hf_lens_dir {
+    double Dx, Dy, vx, vy, len, il, cx, cy, cz;
+};
+__device__ __forceinline__ hf_lens_dir thinlens_dir(const hf_thinlens_args &a, const hf_sensor_film &f, size_t i) {
+    const hf_lens_disk D = thinlens_disk(a.key, thinlens_id(a.s, i));
+    hf_lens_dir q;
+    q.Dx = D.x; q.Dy = D.y;
+    q.vx = f.wx * a.s.tau; q.vy = f.wy * a.s.tau;
+    const double ex = a.focus * q.vx - a.radius * D.x, ey = a.focus * q.vy - a.radius * D.y;
+    q.len = __builtin_sqrt(ex * ex + ey * ey + a.focus * a.focus);
+    q.il = 1.0 / q.len;
+    q.cx = ex * q.il; q.cy = ey * q.il; q.cz = a.focus * q.il;
+    return q;
+}
+template <int TYPE>
+__device__ __forceinline__ void sensor_ray(const hf_thinlens_args &a, size_t i, float r[HF_SENSOR_ROWS]) {
+    const hf_sensor_film f = sensor_sample(a.s, i);
+    r[7] = (float) f.px; r[8] = (float) f.py;
+    const hf_lens_dir q = thinlens_dir(a, f, i);
+    const double ox = a.lens_o * q.Dx + a.s.near * q.vx, oy = a.lens_o * q.Dy + a.s.near * q.vy; // o_c; its z is near
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double *A = a.s.A + 3 * k;
+        r[k] = (float) (a.s.c[k] + (A[0] * ox + A[1] * oy + A[2] * a.s.near));
+        r[3 + k] = (float) (A[0] * q.cx + A[1] * q.cy + A[2] * q.cz);
+    }
+    r[6] = (float) (a.maxt_scale * q.len);
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_rays_kernel(hf_thinlens_args a) {
+    sensor_rays_dword<HF_THINLENS_TYPE>(a);
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_rays_wide_kernel(hf_thinlens_args a) {
+    sensor_rays_wide<HF_THINLENS_TYPE>(a);
+}
+
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_tangent_kernel(hf_thinlens_args a) {
+    double dM[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) dM[j] = a.s.d_tw ? (double) a.s.d_tw[j] : 0.0;
+    const double dT = a.s.d_fov ? (double) a.s.d_fov[0] * a.s.dtau : 0.0;
+    const double dr = a.d_radius ? (double) a.d_radius[0] : 0.0, df = a.d_focus ? (double) a.d_focus[0] : 0.0;
+    const double near = a.s.near, oD = (1.0 - near / a.focus) * dr + (a.radius * near / (a.focus * a.focus)) * df;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.s.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_sensor_film f = sensor_sample(a.s, i);
+        const hf_lens_dir q = thinlens_dir(a, f, i);
+        // de = f u dtau + v df - D dr,   d d_c = (de - d_c <d_c, de>) / |e|
+        const double dex = a.focus * f.wx * dT + q.vx * df - q.Dx * dr, dey = a.focus * f.wy * dT + q.vy * df - q.Dy * dr;
+        const double pr = q.cx * dex + q.cy * dey + q.cz * df;
+        const double ex = (dex - q.cx * pr) * q.il, ey = (dey - q.cy * pr) * q.il, ez = (df - q.cz * pr) * q.il;
+        // o_c and d o_c = oD D + near u dtau
+        const double ox = a.lens_o * q.Dx + near * q.vx, oy = a.lens_o * q.Dy + near * q.vy;
+        const double dox = oD * q.Dx + near * f.wx * dT, doy = oD * q.Dy + near * f.wy * dT;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double *A = a.s.A + 3 * k, *dA = dM + 4 * k;
+            a.s.out_o[k][i] = (float) (dA[3] + (dA[0] * ox + dA[1] * oy + dA[2] * near) + (A[0] * dox + A[1] * doy));
+            a.s.out_d[k][i] = (float) (dA[0] * q.cx + dA[1] * q.cy + dA[2] * q.cz + A[0] * ex + A[1] * ey + A[2] * ez);
+        }
+    }
+}
+// the exact transpose; sums 0..11: to_world, 12: tau, 13: r, 14: f
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_adjoint_kernel(hf_thinlens_args a) {
+    double M[HF_THINLENS_SUMS];
+#pragma unroll
+    for (int j = 0; j < HF_THINLENS_SUMS; ++j) M[j] = 0.0;
+    const double near = a.s.near, oR = 1.0 - near / a.focus, oF = a.radius * near / (a.focus * a.focus);
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.s.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_sensor_film f = sensor_sample(a.s, i);
+        const hf_lens_dir q = thinlens_dir(a, f, i);
+        const double ox = a.lens_o * q.Dx + near * q.vx, oy = a.lens_o * q.Dy + near * q.vy;
+        double p[2] = { 0.0, 0.0 }, t[3] = { 0.0, 0.0, 0.0 }; // A^T go (x, y), A^T gd
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double *A = a.s.A + 3 * k;
+            const double go = a.s.go[k] ? (double) a.s.go[k][i] : 0.0, gd = a.s.gd[k] ? (double) a.s.gd[k][i] : 0.0;
+            M[4 * k] += go * ox + gd * q.cx;
+            M[4 * k + 1] += go * oy + gd * q.cy;
+            M[4 * k + 2] += go * near + gd * q.cz;
+            M[4 * k + 3] += go;
+            p[0] += A[0] * go; p[1] += A[1] * go;
+            t[0] += A[0] * gd; t[1] += A[1] * gd; t[2] += A[2] * gd;
+        }
+        const double pr = q.cx * t[0] + q.cy * t[1] + q.cz * t[2];
+        const double gx = (t[0] - q.cx * pr) * q.il, gy = (t[1] - q.cy * pr) * q.il, gz = (t[2] - q.cz * pr) * q.il; // dL/de
+        const double pD = p[0] * q.Dx + p[1] * q.Dy;
+        M[12] += (a.focus * gx + near * p[0]) * f.wx + (a.focus * gy + near * p[1]) * f.wy;
+        M[13] += oR * pD - (gx * q.Dx + gy * q.Dy);
+        M[14] += oF * pD + (gx * q.vx + gy * q.vy + gz);
+    }
+    sensor_block_store<HF_THINLENS_SUMS>(M, a.s.slab);
+}
+// g_tw[j] += column j, g_fov[0] += dtau * column 12, g_radius[0] += column 13, g_focus[0] += column 14.  One block.
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_sum_kernel(const double *__restrict__ slab, uint32_t rows, double dtau,
+                                                                    float *__restrict__ g_tw, float *__restrict__ g_fov,
+                                                                    float *__restrict__ g_radius, float *__restrict__ g_focus) {
+    const double *const sum = sensor_slab_sums<HF_THINLENS_SUMS>(slab, rows);
+    const uint32_t t = threadIdx.x;
+    if (t < 12u) {
+        if (g_tw) g_tw[t] += (float) sum[t];
+    } else if (t == 12u) {
+        if (g_fov) g_fov[0] += (float) (sum[12] * dtau);
+    } else if (t == 13u) {
+        if (g_radius) g_radius[0] += (float) sum[13];
+    } else if (t == 14u) {
+        if (g_focus) g_focus[0] += (float) sum[14];
+    }
+}
+size_t hf_thinlens_slab_doubles() { return (size_t) HF_XFORM_GRID_CAP * HF_THINLENS_SUMS; }
+
+void hf_launch_thinlens(int mode, const hf_thinlens_args &args, hipStream_t stream) {
+    hf_thinlens_args a = args;
+    a.key = thinlens_key(a.s.seed);
+    if (mode == 1) {
+        const int grid = grid_for(a.s.n, HF_XFORM_GRID_CAP); // the slab holds HF_XFORM_GRID_CAP rows
+        hipLaunchKernelGGL(hf_thinlens_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        hipLaunchKernelGGL(hf_thinlens_sum_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, a.s.slab, (uint32_t) grid, a.s.dtau,
+                           a.s.g_tw, a.s.g_fov, a.g_radius, a.g_focus);
+        return;
+    }
+    if (mode == 0 && sensor_wide_store() && a.s.n >= 64) {
+        hf_thinlens_args w = a;
+        const size_t groups = sensor_wide_groups(w.s);
+        hipLaunchKernelGGL(hf_thinlens_rays_wide_kernel, dim3(grid_for(groups, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, w);
+        return;
+    }
+    hipLaunchKernelGGL(mode == 0 ? hf_thinlens_rays_kernel : hf_thinlens_tangent_kernel, dim3(grid_for(a.s.n, HF_SI_GRID_CAP)),
+                       dim3(HF_BLOCK), 0, stream, a);
+}
+
+// ---- the way back: thin-lens sample_direction (thinlens.cpp:305-350) with the lane's own aperture draw ----
+struct hf_lens_proj {
+    bool inside, valid;
+    double x, y, z;      // ref = to_world^-1 p
+    double Dx, Dy;
+    double qx, qy;       // q = ref - r D (q.z = ref.z)
+    double iz, mx, my;   // 1 / q.z, q.x / q.z, q.y / q.z
+    double kx, ky;       // F / f = (r / f) D + m
+    double u, v, r2, W;  // uv; |q|^2; |q| / (A' q.z^3)
+};
+__device__ __forceinline__ hf_lens_proj thinlens_project(const hf_thinlens_project_args &b, size_t i) {
+    const hf_sensor_project_args &a = b.s;
+    hf_lens_proj r;
+    const double q0 = (double) a.p[0][i] - a.c[0], q1 = (double) a.p[1][i] - a.c[1], q2 = (double) a.p[2][i] - a.c[2];
+    r.x = a.Ai[0] * q0 + a.Ai[1] * q1 + a.Ai[2] * q2;
+    r.y = a.Ai[3] * q0 + a.Ai[4] * q1 + a.Ai[5] * q2;
+    r.z = a.Ai[6] * q0 + a.Ai[7] * q1 + a.Ai[8] * q2;
+    r.inside = (!a.active || a.active[i] != 0) && r.z >= a.near && r.z <= a.far;   // thinlens.cpp:315
+    const hf_lens_disk D = thinlens_disk(b.key, b.ray_id ? b.ray_id[i] : b.start + (uint32_t) i);
+    r.Dx = D.x; r.Dy = D.y;
+    r.qx = r.x - b.radius * D.x; r.qy = r.y - b.radius * D.y;                      // :324
+    r.iz = 1.0 / r.z; r.mx = r.qx * r.iz; r.my = r.qy * r.iz;
+    r.kx = (b.radius / b.focus) * D.x + r.mx; r.ky = (b.radius / b.focus) * D.y + r.my; // :333 over f
+    r.u = 0.5 * (1.0 - r.kx / a.tau) * a.film_w;
+    r.v = 0.5 * (1.0 - a.aspect * r.ky / a.tau) * a.film_h;
+    const double sx = (r.u - a.crop_x) / a.crop_w, sy = (r.v - a.crop_y) / a.crop_h;
+    r.valid = r.inside && sx >= 0.0 && sx <= 1.0 && sy >= 0.0 && sy <= 1.0;        // :334
+    r.r2 = r.qx * r.qx + r.qy * r.qy + r.z * r.z;
+    r.W = __builtin_sqrt(r.r2) * a.inv_area * (r.iz * r.iz * r.iz);                // :335, 349
+    return r;
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_project_kernel(hf_thinlens_project_args b) {
+    const hf_sensor_project_args &a = b.s;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_lens_proj r = thinlens_project(b, i);
+        a.uv[0][i] = r.inside ? (float) r.u : 0.f;
+        a.uv[1][i] = r.inside ? (float) r.v : 0.f;
+        a.valid[i] = r.valid ? 1 : 0;
+        if (a.weight) a.weight[i] = r.valid ? (float) r.W : 0.f;
+    }
+}
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_project_tangent_kernel(hf_thinlens_project_args b) {
+    const hf_sensor_project_args &a = b.s;
+    double dM[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) dM[j] = a.d_tw ? (double) a.d_tw[j] : 0.0;
+    const double dT = (a.d_fov ? (double) a.d_fov[0] * a.dtau : 0.0) / a.tau; // d tau / tau
+    const double dr = b.d_radius ? (double) b.d_radius[0] : 0.0, df = b.d_focus ? (double) b.d_focus[0] : 0.0;
+    const double dk = dr / b.focus - b.radius * df / (b.focus * b.focus);      // d (r / f)
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_lens_proj r = thinlens_project(b, i);
+        double dq[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) // dp - dA ref - dc
+            dq[k] = (a.dp[k] ? (double) a.dp[k][i] : 0.0) - (dM[4 * k] * r.x + dM[4 * k + 1] * r.y + dM[4 * k + 2] * r.z) - dM[4 * k + 3];
+        // dq = d ref - D dr
+        const double dx = a.Ai[0] * dq[0] + a.Ai[1] * dq[1] + a.Ai[2] * dq[2] - r.Dx * dr;
+        const double dy = a.Ai[3] * dq[0] + a.Ai[4] * dq[1] + a.Ai[5] * dq[2] - r.Dy * dr;
+        const double dz = a.Ai[6] * dq[0] + a.Ai[7] * dq[1] + a.Ai[8] * dq[2];
+        const double dkx = dk * r.Dx + (dx - r.mx * dz) * r.iz, dky = dk * r.Dy + (dy - r.my * dz) * r.iz;
+        const double cu = -0.5 * a.film_w / a.tau, cv = -0.5 * a.film_h * a.aspect / a.tau;
+        a.uv[0][i] = r.inside ? (float) (cu * (dkx - r.kx * dT)) : 0.f;
+        a.uv[1][i] = r.inside ? (float) (cv * (dky - r.ky * dT)) : 0.f;
+        if (a.weight)
+            a.weight[i] = r.valid ? (float) (r.W * ((r.qx * dx + r.qy * dy + r.z * dz) / r.r2 - 3.0 * dz * r.iz - 2.0 * dT)) : 0.f;
+    }
+}
+// sums 0..11: to_world, 12: ln tau, 13: r, 14: f
+__global__ __launch_bounds__(HF_BLOCK) void hf_thinlens_project_adjoint_kernel(hf_thinlens_project_args b) {
+    const hf_sensor_project_args &a = b.s;
+    double M[HF_THINLENS_SUMS];
+#pragma unroll
+    for (int j = 0; j < HF_THINLENS_SUMS; ++j) M[j] = 0.0;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const hf_lens_proj r = thinlens_project(b, i);
+        const double cu = -0.5 * a.film_w / a.tau, cv = -0.5 * a.film_h * a.aspect / a.tau;
+        const double gkx = r.inside && a.guv[0] ? cu * (double) a.guv[0][i] : 0.0;  // dL/d(F / f)
+        const double gky = r.inside && a.guv[1] ? cv * (double) a.guv[1][i] : 0.0;
+        const double gW = r.valid && a.gweight ? r.W * (double) a.gweight[i] : 0.0;
+        // dL/dq (= dL/dref)
+        const double gx = gkx * r.iz + gW * r.qx / r.r2;
+        const double gy = gky * r.iz + gW * r.qy / r.r2;
+        const double gz = -(gkx * r.mx + gky * r.my) * r.iz + gW * (r.z / r.r2 - 3.0 * r.iz);
+        double h[3]; // to_world^-T dL/dref = dL/dp (zero outside the clip range: every term above is)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            h[k] = r.inside ? a.Ai[k] * gx + a.Ai[3 + k] * gy + a.Ai[6 + k] * gz : 0.0;
+            if (a.gp[k]) a.gp[k][i] = (float) h[k];
+            M[4 * k] -= h[k] * r.x; M[4 * k + 1] -= h[k] * r.y; M[4 * k + 2] -= h[k] * r.z; M[4 * k + 3] -= h[k];
+        }
+        if (r.inside) {
+            const double gD = gkx * r.Dx + gky * r.Dy;
+            M[12] -= gkx * r.kx + gky * r.ky + 2.0 * gW;
+            M[13] += gD / b.focus - (gx * r.Dx + gy * r.Dy);
+            M[14] -= gD * b.radius / (b.focus * b.focus);
+        }
+    }
+    sensor_block_store<HF_THINLENS_SUMS>(M, a.slab);
+}
+
+void hf_launch_thinlens_project(int mode, const hf_thinlens_project_args &args, hipStream_t stream) {
+    hf_thinlens_project_args a = args;
+    a.key = thinlens_key(a.seed);
+    if (mode == 1) {
+        const int grid = grid_for(a.s.n, HF_XFORM_GRID_CAP);
+        hipLaunchKernelGGL(hf_thinlens_project_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        // column 12 holds dL/d(ln tau): times d tau / tau per degree
+        hipLaunchKernelGGL(hf_thinlens_sum_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, a.s.slab, (uint32_t) grid,
+                           a.s.dtau / a.s.tau, a.s.g_tw, a.s.g_fov, a.g_radius, a.g_focus);
+        return;
+    }
+    hipLaunchKernelGGL(mode == 0 ? hf_thinlens_project_kernel : hf_thinlens_project_tangent_kernel,
+                       dim3(grid_for(a.s.n, HF_SI_GRID_CAP)), dim3(HF_BLOCK), 0, stream, a);
 }
 
 // ---------------------------------------------------------------------------------

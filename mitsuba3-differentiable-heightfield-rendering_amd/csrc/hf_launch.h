@@ -281,6 +281,31 @@ struct hf_sensor_project_args {
 };
 // mode 0: forward, 1: adjoint (two launches), 2: tangent
 void hf_launch_sensor_project(int mode, const hf_sensor_project_args &a, hipStream_t stream);
+// ---- the thin lens (hf_thinlens_rays / _tangent / _adjoint): the perspective sensor's argument (its kernels'
+// layout stays as it is) and the lens's own constants behind it ----
+struct hf_thinlens_args {
+    hf_sensor_args s;                        // as a perspective sensor's; slab: 15 doubles per block
+    double radius, focus;                    // aperture_radius r, focus_distance f
+    double lens_o;                           // r (1 - near / f): o_c = lens_o D + near v
+    double maxt_scale;                       // (far - near) / f
+    uint32_t key;                            // tea32(seed, HF_THINLENS_PAIR).v0 (set by the launcher)
+    const float *d_radius, *d_focus;         // tangent inputs (NULL: zero)
+    float *g_radius, *g_focus;               // adjoint outputs, accumulated (NULL: not wanted)
+};
+// mode 0: rays, 1: adjoint (two launches), 2: tangent
+void hf_launch_thinlens(int mode, const hf_thinlens_args &a, hipStream_t stream);
+size_t hf_thinlens_slab_doubles();
+// ---- the way back (hf_thinlens_project / _tangent / _adjoint) ----
+struct hf_thinlens_project_args {
+    hf_sensor_project_args s;                // as hf_sensor_project's; slab: 15 doubles per block
+    uint32_t start, seed;                    // the lane's aperture draw: wavefront index start + i, or ray_id[i]
+    uint32_t key;                            // tea32(seed, HF_THINLENS_PAIR).v0 (set by the launcher)
+    const uint32_t *ray_id;
+    double radius, focus;
+    const float *d_radius, *d_focus;
+    float *g_radius, *g_focus;
+};
+void hf_launch_thinlens_project(int mode, const hf_thinlens_project_args &a, hipStream_t stream);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
