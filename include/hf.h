@@ -1393,6 +1393,102 @@ int hf_thinlens_project_adjoint(const hf_thinlens_t *lens, size_t n, uint32_t st
                                 const float *grad_weight, float *const grad_p[3], float *grad_to_world, float *grad_fov,
                                 float *grad_radius, float *grad_focus, float *workspace, hf_stream_t stream);
 
+/* ---- next row: projector lighting, a structured-light emitter whose shadow ray is traced in the kernel ----
+ *
+ * Replaces, for diffuse surfaces under ONE `projector` emitter (src/emitters/projector.cpp, "the reciprocal counterpart
+ * of the perspective camera": a pinhole that throws a bitmap onto the scene), the emitter-sampling term of the direct
+ * integrator (Emitter::sample_direction, projector.cpp:204-246; attached BSDF value, diffuse.cpp:135-140) and the shadow
+ * ray it traces.  The emitter is a point, so there is one draw per sample and no sample stream.
+ *   projector   hf_projector_t, HOST memory.  to_world: row-major 3x4 [A | c], scale-free (hf_sensor_t's check
+ *               |A^T A - I| <= 1e-4); x_fov: degrees along x, in (0, 180); scale: the reference's `scale` (:124).
+ *   texture     the irradiance tex[TH][TW] (float32, row-major, the caller's device buffer) with wrap = HF_WRAP_* (the
+ *               reference's bitmap default is repeat); tex == NULL: uniform irradiance 1.  The aspect a = TW / TH
+ *               (:128-129), so TW and TH are read without a texture too.
+ *   mapping     ref = to_world^-1 p (:210), the affine inverse formed once on the host in double;
+ *               tau = tan(x_fov pi / 360);   uv = ((1 - ref.x / (ref.z tau)) / 2, (1 - a ref.y / (ref.z tau)) / 2) (:213:
+ *               hf_sensor_project's g);   lit = ref.z > 0 and uv in [0, 1]^2 (:214).  The near and far planes of
+ *               :148-150 do not enter sample_direction and are no parameters.
+ *   lookup      I(uv): the texel coordinate (uv.x TW, uv.y TH), rounded once to float32 (hf_sensor_project's uv for a film
+ *               of TW x TH), by hf_bitmap_eval's float32 expression and rules (bitmap.cpp:497-520);
+ *   eligible    sample i when t_i is finite and <sh_n_i, -d_i> > 0 (the masks of hf_direct_lighting); an eligible sample
+ *               is TRACED when it is lit, <sh_n, u> > 0 with u = c - p, and |u|^2 is finite and > 0 -- the last two decided
+ *               in float32 with c rounded to float32, lit in double;
+ *   shadow ray  Interaction::spawn_ray_to(c), hf_rect_rays' ray: origin o = p + n s (1 + max|p_c|) RayEpsilon with n the
+ *               geometric normal, s = -1 where <n, u> < 0, else 1; direction (c - o) / |c - o|; maxt = |c - o| (1 -
+ *               ShadowEpsilon) (interaction.h:141-147, 161-165, math.h:18-22);
+ *   visibility  vis[i], one byte: 1 iff the sample was traced and the any-hit walk found nothing before maxt;
+ *   value_i     = weight_i albedo scale I(uv) G,   G = <sh_n, c - p> / ref.z^3, where vis_i = 1 and exactly 0 elsewhere:
+ *               spec = pi scale I / (ref.z^2 cos) with cos = ref.z / |ref| (:231-245; |ref| = |u| for the scale-free
+ *               to_world) times albedo/pi <sh_n, u> / |u| (diffuse.cpp).  No square root is taken;
+ *   image[i / spp] = 1/spp * sum value_i: the box film of hf_direct_lighting, overwritten; n a multiple of spp;
+ *   uv          2 rows of n floats: uv of every sample with ref.z > 0, zeros elsewhere (eligible or not).
+ * G, uv and every derivative sum are formed in double from the float32 inputs and rounded once (DESIGN 4.22's reasons:
+ * u is a difference, ref.z^3 amplifies); the lookup is float32; the shadow ray takes float32 quantities (what
+ * hf_projector_rays writes).
+ * Differentiated with respect to sh_n, p, weight, tex, to_world (all 12 entries, unconstrained, hf_sensor_project's
+ * convention), x_fov and scale.  HELD: the visibility, every mask, the cell of the lookup.  With z = ref.z, (Lx, Ly) the
+ * lookup's slopes and b_j its four weights:
+ *   d ref = A^-1 (dp - dA ref - dc),   d tau = (pi / 360) (1 + tau^2) d fov,
+ *   dG = <d sh_n, u> / z^3 + <sh_n, dc - dp> / z^3 - 3 <sh_n, u> d ref.z / z^4,
+ *   dI = Lx TW d uv.x + Ly TH d uv.y + sum_j b_j d tex_j,   d uv from the mapping above.
+ * OUT OF SCOPE: the silhouette part of a moving shadow (hf_reparam_*'s, as in the rows above), sample_ray (light tracing
+ * from the projector with importance-sampled pixels), RGB, the other fov_axis values, several projectors per call (call
+ * once each and add the images), spot.cpp.
+ * All entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional, n >= 2^32,
+ * spp == 0 or n % spp != 0, TW == 0, TH == 0 or TW TH >= 2^31, a wrap that is neither, a non-finite field of the
+ * projector, x_fov outside (0, 180), a to_world with scale, a non-finite albedo.  p, nrm, sh_n, d: 3 device rows of n
+ * floats; t: n.  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+typedef struct hf_projector {       /* HOST memory, as hf_sensor_t */
+    double to_world[12];            /* row-major 3x4 [A | c], scale-free */
+    double x_fov;                   /* degrees, along x, in (0, 180) */
+    float scale;                    /* multiplies the irradiance */
+} hf_projector_t;
+/* hf_projector_rays materialises the shadow ray of every sample (out_o, out_d: 3 rows of n floats; out_maxt: n floats, the
+ * finite maxt above for a traced lane; a lane that is not traced gets a zero origin and direction and maxt = -1, a miss):
+ * the two-call sequence hf_projector_rays + hf_ray_test that hf_projector_lighting equals bit for bit.  TW, TH: for the
+ * aspect.  Takes no field handle. */
+int hf_projector_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                      const float *const d[3], const float *t, const hf_projector_t *projector, uint32_t TW, uint32_t TH,
+                      float *const out_o[3], float *const out_d[3], float *out_maxt, hf_stream_t stream);
+/* The fused launch (hf_refract_lighting's shape): reads a sample's record once, maps it, looks the texture up, runs the
+ * per-lane any-hit walk up to maxt where the sample is traced, and writes image (n / spp), value (n), vis (n bytes) and
+ * uv (2 rows) -- each may be NULL (not wanted), not all of them; no ray and no hit byte goes to memory.  A batch of 64
+ * samples without a traced one skips the walk.  hf_set_ray_coherence is neither read nor changed.  weight: n floats or
+ * NULL (1).  Allocates nothing, never synchronises the host, capturable. */
+int hf_projector_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                          const float *const sh_n[3], const float *const d[3], const float *t, const float *weight,
+                          const hf_projector_t *projector, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                          float albedo, float *image, float *value, uint8_t *vis, float *const uv[2], hf_stream_t stream);
+/* the adjoint's workspace in floats (a constant: the most any launch needs) */
+size_t hf_projector_workspace_floats(void);
+/* Reverse mode.  Traces nothing: vis (as hf_projector_lighting wrote it) is read.  With the upstream
+ * g = grad_image[i / spp] / spp + grad_value[i] (either may be NULL = zero): grad_sh_n, grad_p (3 rows each) and
+ * grad_weight are OVERWRITTEN, one lane per sample, exact zeros where vis = 0, no atomics; grad_tex[TH][TW] is ACCUMULATED
+ * into on the four texels of every visible sample (float atomics; ignored without a texture); grad_to_world (12 device
+ * floats), grad_fov and grad_scale (1 device float each) are ACCUMULATED into without atomics: every block stores its 14
+ * partial sums in double to `workspace` -- hf_projector_workspace_floats() floats of device memory, 8-byte aligned, the
+ * caller's, this call's until it has completed; needed only when one of the three is wanted -- and one more launch adds
+ * them in a fixed order (hf_sensor_rays_adjoint's pattern with rows of 14; family 2 of hf_grid_blocks): bitwise the same
+ * from launch to launch.  Every output may be NULL (not wanted).  Takes no field handle. */
+int hf_projector_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                  const float *const d[3], const float *t, const float *weight,
+                                  const hf_projector_t *projector, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                                  float albedo, const uint8_t *vis, const float *grad_image, const float *grad_value,
+                                  float *const grad_sh_n[3], float *const grad_p[3], float *grad_weight, float *grad_tex,
+                                  float *grad_to_world, float *grad_fov, float *grad_scale, float *workspace,
+                                  hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dsh_n, dp (3 rows of n floats each), dweight (n), dtex
+ * ([TH][TW]; ignored without a texture), d_to_world (12 device floats), d_fov and d_scale (1 device float each), each may
+ * be NULL (zero); dimage (n / spp) and / or dvalue (n) are overwritten (at least one).  No atomics for any spp (a power of
+ * two <= 64: the film's shuffle tree; otherwise one lane adds the samples of a pixel in order): bitwise the same from
+ * launch to launch.  Takes no field handle. */
+int hf_projector_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                  const float *const d[3], const float *t, const float *weight,
+                                  const hf_projector_t *projector, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                                  float albedo, const uint8_t *vis, const float *const dsh_n[3], const float *const dp[3],
+                                  const float *dweight, const float *dtex, const float *d_to_world, const float *d_fov,
+                                  const float *d_scale, float *dimage, float *dvalue, hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional
@@ -1731,7 +1827,7 @@ int hf_invert_affine(const float in[12], float out[12]);
 /* blocks (of 256 threads) that a grid-stride launch of n items gets, HF_FORCE_GRID included.  family: 0 the flat cap
  * (adjoints, reparameterisation, Adam, area sampling, ...), 1 the cap of the streaming kernels (SI, hf_tangent, the
  * forward and tangent of attributes and of eval_parameterization, the sensor's rays, projection and their tangents), 2
- * the cap of the launches that sum dL/d(to_world), the sensor's adjoints among them.
+ * the cap of the launches that sum dL/d(to_world), the sensor's adjoints and hf_projector_lighting_adjoint among them.
  * 0 for an unknown family.  Needs no device. */
 int hf_grid_blocks(size_t n, int family);
 const char *hf_last_error_string(void);

@@ -9,3 +9,4 @@ from .shape import (Adam, Bitmap, DirectionSample3f, Envmap, Frame3f, Heightfiel
                     point_lighting, rect_lighting, rect_rays, reflection_lighting, reflection_rays, refraction_lighting, reparameterize_ray, reparameterize_ray_adjoint, reparameterize_ray_tangent,
                     sky_lighting, sky_rays)
 from .sensor import OrthographicCamera, PerspectiveCamera, ThinLensCamera  # noqa: F401
+from .projector import Projector, projector_lighting, projector_rays  # noqa: F401

@@ -99,7 +99,28 @@ _lens_in = [C.POINTER(hf_thinlens_t), *_sensor_in[1:]]  # lens, n, start, spp, s
 # lens, n, start, seed, ray_id, p, active
 _lens_project_in = [C.POINTER(hf_thinlens_t), C.c_size_t, C.c_uint32, C.c_uint32, _fp, C.POINTER(_fp * 3), _fp]
 
+class hf_projector_t(C.Structure):
+    _fields_ = [("to_world", C.c_double * 12), ("x_fov", C.c_double), ("scale", C.c_float)]
+
+
+# n, spp, p, sh_n, d, t, weight, projector, TW, TH, tex, wrap, albedo, vis
+_projector_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp,
+                 C.POINTER(hf_projector_t), *_bitmap_in, C.c_float, _fp]
+
 SYMBOLS = {
+    "hf_projector_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
+                                    C.POINTER(hf_projector_t), C.c_uint32, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                    _fp, C.c_void_p]),
+    "hf_projector_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                        C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.POINTER(hf_projector_t), *_bitmap_in,
+                                        C.c_float, _fp, _fp, _fp, C.POINTER(_fp * 2), C.c_void_p]),
+    "hf_projector_workspace_floats": (C.c_size_t, []),
+    # ..., grad_image, grad_value, grad_sh_n, grad_p, grad_weight, grad_tex, grad_to_world, grad_fov, grad_scale, workspace
+    "hf_projector_lighting_adjoint": (C.c_int, [*_projector_in, _fp, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp,
+                                                _fp, _fp, _fp, C.c_void_p]),
+    # ..., dsh_n, dp, dweight, dtex, d_to_world, d_fov, d_scale, dimage, dvalue
+    "hf_projector_lighting_tangent": (C.c_int, [*_projector_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, _fp,
+                                                _fp, _fp, C.c_void_p]),
     "hf_thinlens_rays": (C.c_int, [*_lens_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 2), C.c_void_p]),
     "hf_thinlens_rays_tangent": (C.c_int, [*_lens_in, _fp, _fp, _fp, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p]),
     "hf_thinlens_workspace_floats": (C.c_size_t, []),

@@ -1629,6 +1629,132 @@ extern "C" int hf_rect_lighting_tangent(size_t n, uint32_t spp, const float *con
     return light_launch(hf_launch_rect, 2, a, stream);
 }
 
+// ---- projector lighting: a pinhole that throws a texture onto the terrain, the shadow ray traced in the kernel ----
+// What the four hf_projector_* entries share (hf_projector_rays passes spp 1, no texture, HF_WRAP_REPEAT, albedo 1): the
+// wavefront, the projector's checks, the affine inverse (formed once, here, in double: adjugate) and the constants of
+// the mapping
+static int projector_args(const char *who, size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                          const float *const d[3], const float *t, const float *weight, const hf_projector_t *pr,
+                          uint32_t TW, uint32_t TH, const float *tex, int wrap, float albedo, hf_projector_args &a) {
+    a = {};
+    if (!all3(p) || !all3(sh_n) || !all3(d) || !t || !pr) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (TW == 0 || TH == 0 || (uint64_t) TW * TH >= ((uint64_t) 1 << 31))
+        return fail(HF_EINVAL, "%s: the texture must have 1 .. 2^31 - 1 texels (got %u x %u)", who, TW, TH);
+    if (wrap != HF_WRAP_CLAMP && wrap != HF_WRAP_REPEAT)
+        return fail(HF_EINVAL, "%s: wrap must be HF_WRAP_CLAMP or HF_WRAP_REPEAT (got %d)", who, wrap);
+    const double *M = pr->to_world;
+    for (int j = 0; j < 12; ++j)
+        if (!isfinite(M[j])) return fail(HF_EINVAL, "%s: the projector's to_world must be finite", who);
+    if (!isfinite(pr->x_fov) || !isfinite(pr->scale)) return fail(HF_EINVAL, "%s: the projector's x_fov and scale must be finite", who);
+    if (!(pr->x_fov > 0.0) || !(pr->x_fov < 180.0))
+        return fail(HF_EINVAL, "%s: the projector's x_fov must be in (0, 180) degrees (got %g)", who, pr->x_fov);
+    for (int i = 0; i < 3; ++i) // projector.cpp: has_scale(), hf_sensor_t's check
+        for (int j = i; j < 3; ++j) {
+            const double g = M[i] * M[j] + M[4 + i] * M[4 + j] + M[8 + i] * M[8 + j];
+            if (fabs(g - (i == j ? 1.0 : 0.0)) > 1e-4)
+                return fail(HF_EINVAL, "%s: scale factors in the projector's to_world are not allowed", who);
+        }
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    const double m[3][3] = { { M[0], M[1], M[2] }, { M[4], M[5], M[6] }, { M[8], M[9], M[10] } };
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) { // Ai[r][c] = cofactor(c, r) / det
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+            a.Ai[3 * r + c] = (m[r1][c1] * m[r2][c2] - m[r1][c2] * m[r2][c1]) / det;
+        }
+    for (int k = 0; k < 3; ++k) {
+        a.c[k] = M[4 * k + 3]; a.cf[k] = (float) M[4 * k + 3];
+        a.p[k] = p[k]; a.sh_n[k] = sh_n[k]; a.d[k] = d[k];
+    }
+    a.n = n; a.spp = spp; a.t = t; a.weight = weight;
+    a.TW = TW; a.TH = TH; a.tex = tex; a.wrap = wrap;
+    a.tau = tan(pr->x_fov * 3.141592653589793 / 360.0);
+    a.dtau = (3.141592653589793 / 360.0) * (1.0 + a.tau * a.tau);
+    a.aspect = (double) TW / (double) TH; // projector.cpp:128-129
+    a.albedo = (double) albedo; a.cs = (double) albedo * (double) pr->scale;
+    return HF_OK;
+}
+
+extern "C" int hf_projector_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                                 const float *const d[3], const float *t, const hf_projector_t *projector, uint32_t TW,
+                                 uint32_t TH, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                                 hf_stream_t stream) {
+    const char *fn = "hf_projector_rays";
+    hf_projector_args a;
+    int rc = projector_args(fn, n, 1, p, sh_n, d, t, nullptr, projector, TW, TH, nullptr, HF_WRAP_REPEAT, 1.f, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_projector, 3, a, stream);
+}
+
+extern "C" int hf_projector_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                     const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                     const float *t, const float *weight, const hf_projector_t *projector, uint32_t TW,
+                                     uint32_t TH, const float *tex, int wrap, float albedo, float *image, float *value,
+                                     uint8_t *vis, float *const uv[2], hf_stream_t stream) {
+    const char *fn = "hf_projector_lighting";
+    hf_projector_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = projector_args(fn, n, spp, p, sh_n, d, t, weight, projector, TW, TH, tex, wrap, albedo, a);
+    if (rc != HF_OK || (rc = light_forward_out(fn, p, nrm, image, a, true))) return rc;
+    if (uv && (!uv[0] || !uv[1])) return fail(HF_EINVAL, "%s: NULL uv component array", fn);
+    if (!image && !value && !vis && !uv) return fail(HF_EINVAL, "%s: image, value, vis and uv are all NULL", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.value = value; a.vis = vis;
+    for (int c = 0; c < 2; ++c) a.uv[c] = uv ? uv[c] : nullptr;
+    return light_launch(hf_launch_projector, 0, a, stream);
+}
+
+extern "C" size_t hf_projector_workspace_floats(void) { return 2u * hf_projector_slab_doubles(); }
+
+extern "C" int hf_projector_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                             const float *const d[3], const float *t, const float *weight,
+                                             const hf_projector_t *projector, uint32_t TW, uint32_t TH, const float *tex,
+                                             int wrap, float albedo, const uint8_t *vis, const float *grad_image,
+                                             const float *grad_value, float *const grad_sh_n[3], float *const grad_p[3],
+                                             float *grad_weight, float *grad_tex, float *grad_to_world, float *grad_fov,
+                                             float *grad_scale, float *workspace, hf_stream_t stream) {
+    const char *fn = "hf_projector_lighting_adjoint";
+    hf_projector_args a;
+    int rc = projector_args(fn, n, spp, p, sh_n, d, t, weight, projector, TW, TH, tex, wrap, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (grad_p && !all3(grad_p)) return fail(HF_EINVAL, "%s: NULL grad_p component array", fn);
+    if ((rc = light_value_adjoint_io(fn, !vis, grad_image, grad_value, grad_sh_n, grad_weight, grad_tex, a))) return rc;
+    const bool reduced = grad_to_world || grad_fov || grad_scale;
+    if (reduced && !workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (reduced && ((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    a.vis = const_cast<uint8_t *>(vis);
+    for (int c = 0; c < 3; ++c) a.gp[c] = grad_p ? grad_p[c] : nullptr;
+    a.slab = reduced ? (double *) workspace : nullptr;
+    a.g_tw = grad_to_world; a.g_fov = grad_fov; a.g_scale = grad_scale;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_projector, 1, a, stream);
+}
+
+extern "C" int hf_projector_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                             const float *const d[3], const float *t, const float *weight,
+                                             const hf_projector_t *projector, uint32_t TW, uint32_t TH, const float *tex,
+                                             int wrap, float albedo, const uint8_t *vis, const float *const dsh_n[3],
+                                             const float *const dp[3], const float *dweight, const float *dtex,
+                                             const float *d_to_world, const float *d_fov, const float *d_scale,
+                                             float *dimage, float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_projector_lighting_tangent";
+    hf_projector_args a;
+    int rc = projector_args(fn, n, spp, p, sh_n, d, t, weight, projector, TW, TH, tex, wrap, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (dp && !all3(dp)) return fail(HF_EINVAL, "%s: NULL dp component array", fn);
+    if ((rc = light_value_tangent_io(fn, !vis, dsh_n, dweight, dtex, dimage, dvalue, a))) return rc;
+    a.vis = const_cast<uint8_t *>(vis);
+    for (int c = 0; c < 3; ++c) a.dp[c] = dp ? dp[c] : nullptr;
+    a.d_tw = d_to_world; a.d_fov = d_fov; a.d_scale = d_scale;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_projector, 2, a, stream);
+}
+
 // ---- the sensor: the primary wavefront of a perspective or an orthographic camera ----
 static int log2_or_minus1(uint32_t v) {
     if (v == 0 || (v & (v - 1u))) return -1;

@@ -7431,6 +7431,293 @@ void hf_launch_thinlens_project(int mode, const hf_thinlens_project_args &args, 
 }
 
 // ---------------------------------------------------------------------------------
+// Projector lighting (include/hf.h hf_projector_*): diffuse surface under a `projector` emitter, the
+// reciprocal of the perspective sensor: a pinhole at to_world's c that throws the texture onto the terrain.  One draw per
+// sample (the pinhole is a point): the frustum mapping p -> uv, the bilinear lookup, the shadow ray towards c
+// (Interaction::spawn_ray_to, a FINITE maxt) traced (any hit, per lane) and the film in ONE launch, hf_refract_kernel's
+// and hf_rect_kernel's shape:
+//   value = weight albedo scale I(uv) G,   G = <sh_n, c - p> / ref.z^3.
+// The row's own text is the mapping, G and their derivatives with the pose, the field of view and the scale; the masks,
+// the origin, the walk, the film, the outputs, the tangent shell and the launch are the lighting rows' shared functions,
+// the lookup with its scatter / gather the refraction view's (bitmap_cell), the reduction of the 14 pose numbers the
+// sensor's (sensor_block_store, sensor_slab_sums).
+// (P below: a pointer to hf_projector_args, in the kernarg segment or not)
+// ---------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) hf_projector_args *hf_projector_kargs;
+
+// The mapping (projector.cpp:209-214) in double from the float32 point: ref = to_world^-1 p, uv = camera_to_sample of
+// ref / ref.z (hf_sensor_project's expressions in units of the whole film), lit = ref.z > 0 and uv in [0, 1]^2
+struct hf_projector_map {
+    double x, y, z;    // ref
+    double iz, rx, ry; // 1 / ref.z, ref.x / ref.z, ref.y / ref.z
+    double u, v;       // uv
+    bool lit;
+};
+template <class P>
+__device__ __forceinline__ hf_projector_map projector_map(P a, v3 p) {
+    hf_projector_map m;
+    const double q0 = (double) p.x - a->c[0], q1 = (double) p.y - a->c[1], q2 = (double) p.z - a->c[2];
+    m.x = a->Ai[0] * q0 + a->Ai[1] * q1 + a->Ai[2] * q2;
+    m.y = a->Ai[3] * q0 + a->Ai[4] * q1 + a->Ai[5] * q2;
+    m.z = a->Ai[6] * q0 + a->Ai[7] * q1 + a->Ai[8] * q2;
+    m.iz = 1.0 / m.z; m.rx = m.x * m.iz; m.ry = m.y * m.iz;
+    m.u = 0.5 * (1.0 - m.rx / a->tau);
+    m.v = 0.5 * (1.0 - a->aspect * m.ry / a->tau);
+    m.lit = m.z > 0.0 && m.u >= 0.0 && m.u <= 1.0 && m.v >= 0.0 && m.v <= 1.0;
+    return m;
+}
+// u = c - p in double, for the shading sums (G's numerator is <sh_n, u>)
+template <class P>
+__device__ __forceinline__ hf_d3 projector_to_c(P a, v3 p) {
+    return hf_d3{ a->c[0] - (double) p.x, a->c[1] - (double) p.y, a->c[2] - (double) p.z };
+}
+// the texel coordinate of a lit point: (uv.x TW, uv.y TH), rounded once to float32 (hf_sensor_project's uv for a film of
+// TW x TH), then hf_bitmap_eval's float32 lookup
+template <class P>
+__device__ __forceinline__ hf_bitmap_cell projector_cell(P a, const hf_projector_map &m) {
+    return bitmap_cell(a, (float) (m.u * (double) a->TW), (float) (m.v * (double) a->TH));
+}
+// The float32 side, what the ray takes: u = c - p with c rounded to float32; front: <sh_n, u> > 0 and |u|^2 finite and > 0
+__device__ __forceinline__ bool projector_front(v3 cf, v3 p, v3 sn) {
+    const v3 u = cf - p;
+    const float r2 = dot3(u, u);
+    return dot3(sn, u) > 0.f && r2 > 0.f && r2 < __builtin_inff();
+}
+// spawn_ray_to(c) (hf_rect_rays' ray with the lamp's point at c): the origin offset_p(u), the direction (c - o) / |c - o|
+// and maxt = |c - o| (1 - ShadowEpsilon)
+struct hf_projector_ray { v3 o, w; float maxt; };
+__device__ __forceinline__ hf_projector_ray projector_ray(v3 cf, v3 p, v3 gn, float mag) {
+    hf_projector_ray r;
+    r.o = sky_origin(p, gn, mag, cf - p);
+    const v3 dv = cf - r.o;
+    const float dist = __builtin_sqrtf(dot3(dv, dv));
+    r.w = dv * (1.0f / dist);
+    r.maxt = dist * (1.f - 8.940696716308594e-04f);
+    return r;
+}
+
+#ifndef HF_PROJECTOR_WAVES
+#define HF_PROJECTOR_WAVES 6 // resident waves per SIMD (the siblings')
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_PROJECTOR_WAVES) void hf_projector_kernel(hf_projector_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    hf_projector_kargs ka = (hf_projector_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    float val = 0.f; // the value of a sample that turns out visible: finished before the ray is begun, held across the walk
+    bool traced;
+    hf_hit best;
+    best.hit = false;
+    {
+        const v3 sn = mk3(ka->sh_n[0][ii], ka->sh_n[1][ii], ka->sh_n[2][ii]);
+        bool elig;
+        {
+            const v3 d = mk3(ka->d[0][ii], ka->d[1][ii], ka->d[2][ii]);
+            elig = in && sky_eligible(ka->t[ii], sn, d);
+        }
+        const v3 p = mk3(ka->p[0][ii], ka->p[1][ii], ka->p[2][ii]);
+        bool lit;
+        { // the doubles and the four texel addresses are dead when setup_ray's registers fill; uv is stored here
+            const hf_projector_map m = projector_map(ka, p);
+            lit = m.lit;
+            float *ux = ka->uv[0], *uy = ka->uv[1];
+            if (in && ux) {
+                const bool facing = m.z > 0.0;
+                ux[i] = facing ? (float) m.u : 0.f; uy[i] = facing ? (float) m.v : 0.f;
+            }
+            if (elig && lit) {
+                const double iz3 = m.iz * m.iz * m.iz;
+                double v = ka->cs * (sky_dot_f64(sn, projector_to_c(ka, p)) * iz3);
+                const float *tex = ka->tex, *weight = ka->weight;
+                if (tex) v *= (double) projector_cell(ka, m).value(tex); // (wave-uniform)
+                if (weight) v *= (double) weight[ii];
+                val = (float) v;
+            }
+        }
+        asm volatile("" : "+v"(val));
+        const v3 cf = mk3(ka->cf[0], ka->cf[1], ka->cf[2]);
+        traced = elig && lit && projector_front(cf, p, sn);
+        if (__ballot(traced) != 0ull) { // wave-uniform: a batch without a traced sample walks nothing
+            const v3 gn = mk3(ka->nrm[0][ii], ka->nrm[1][ii], ka->nrm[2][ii]);
+            const hf_projector_ray r = projector_ray(cf, p, gn, sky_offset(p));
+            light_walk<true>(&ka->f, f, r.o, r.w, r.maxt, traced, best);
+        }
+    }
+    // (the output pointers: loaded here, not before the walk)
+    hf_projector_kargs ko = (hf_projector_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    const bool seen = traced && !best.hit; // (traced: in range)
+    if (!seen) val = 0.f;
+    if (in) {
+        float *value = ko->value;
+        uint8_t *vis = ko->vis;
+        if (value) value[i] = val;
+        if (vis) vis[i] = seen ? 1 : 0;
+    }
+    float *image = ko->image;
+    if (image) {
+        const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+        film_pixel(image, val, 0u, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+    }
+}
+
+// the shadow ray of every sample, materialised: what hf_projector_kernel traces, bit for bit (an untraced lane: a zero
+// origin and direction, maxt = -1)
+__global__ __launch_bounds__(HF_BLOCK) void hf_projector_rays_kernel(hf_projector_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 sn;
+    const bool elig = light_sample(a, i, sn);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    const v3 cf = mk3(a.cf[0], a.cf[1], a.cf[2]);
+    const bool traced = elig && projector_map(&a, p).lit && projector_front(cf, p, sn);
+    const hf_projector_ray r = projector_ray(cf, p, gn, sky_offset(p));
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    light_store_ray(a, i, traced ? r.o : z, traced ? r.w : z, traced, r.maxt);
+}
+
+// What the two derivative kernels form again of a visible sample: the mapping, u = c - p, <sh_n, u>, G, the cell of the
+// lookup, I (1 without a texture) and dI/duv = (Lx TW, Ly TH) with the cell held
+struct hf_projector_shade {
+    hf_projector_map m;
+    hf_bitmap_cell e;
+    hf_d3 u;
+    double iz3, G, I, Iu, Iv;
+};
+__device__ __forceinline__ hf_projector_shade projector_shade(const hf_projector_args &a, v3 p, v3 sn) {
+    hf_projector_shade s;
+    s.m = projector_map(&a, p);
+    s.u = projector_to_c(&a, p);
+    s.iz3 = s.m.iz * s.m.iz * s.m.iz;
+    s.G = sky_dot_f64(sn, s.u) * s.iz3;
+    s.I = 1.0; s.Iu = 0.0; s.Iv = 0.0;
+    if (a.tex) {
+        s.e = projector_cell(&a, s.m);
+        float Lx, Ly;
+        s.e.slopes(a.tex, Lx, Ly);
+        s.I = (double) s.e.value(a.tex);
+        s.Iu = (double) Lx * (double) a.TW; s.Iv = (double) Ly * (double) a.TH;
+    }
+    return s;
+}
+
+// Reverse mode of hf_projector_kernel with respect to sh_n, p, weight, the texels, to_world, x_fov and scale: nothing is
+// traced, the visibility byte is read.  grad_sh_n, grad_p, grad_weight: one lane per sample, overwritten, no atomics;
+// grad_tex: one float atomic per texel of every visible sample; the 14 pose numbers (to_world's 12, ln tau's, scale's)
+// are kept per lane in double across the grid-stride loop and reduced as the sensor's 13
+#define HF_PROJECTOR_SUMS 14
+__global__ __launch_bounds__(HF_BLOCK) void hf_projector_adjoint_kernel(hf_projector_args a) {
+    double M[HF_PROJECTOR_SUMS];
+#pragma unroll
+    for (int j = 0; j < HF_PROJECTOR_SUMS; ++j) M[j] = 0.0;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        v3 gn = mk3(0.f, 0.f, 0.f), gp = gn;
+        float gw = 0.f;
+        if (a.vis[i]) {
+            const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+            const hf_projector_shade s = projector_shade(a, p, sn);
+            if (s.m.lit) { // (a visible sample is lit: the guard of the divisions by ref.z)
+                const double g = (double) light_value_seed(a, i), w = a.weight ? (double) a.weight[i] : 1.0;
+                const double gV = g * s.I * s.G; // dL/d(weight albedo scale)
+                gw = (float) (gV * a.cs);
+                M[13] += gV * w * a.albedo;
+                const double gG = (g * w * a.cs) * s.I, gI = (g * w * a.cs) * s.G; // dL/dG, dL/dI
+                // dL/d(ref.x / ref.z), dL/d(ref.y / ref.z) through uv, then dL/dref
+                const double grx = gI * s.Iu * (-0.5 / a.tau), gry = gI * s.Iv * (-0.5 * a.aspect / a.tau);
+                const double gx = grx * s.m.iz, gy = gry * s.m.iz;
+                const double gz = -(grx * s.m.rx + gry * s.m.ry) * s.m.iz - 3.0 * gG * s.G * s.m.iz;
+                const double gu = gG * s.iz3; // dL/d<sh_n, u>
+                const double n3[3] = { (double) sn.x, (double) sn.y, (double) sn.z }, u3[3] = { s.u.x, s.u.y, s.u.z };
+                float o_n[3], o_p[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double h = a.Ai[k] * gx + a.Ai[3 + k] * gy + a.Ai[6 + k] * gz; // to_world^-T dL/dref
+                    o_n[k] = (float) (gu * u3[k]);
+                    o_p[k] = (float) (h - gu * n3[k]);
+                    M[4 * k] -= h * s.m.x; M[4 * k + 1] -= h * s.m.y; M[4 * k + 2] -= h * s.m.z;
+                    M[4 * k + 3] += gu * n3[k] - h;
+                }
+                M[12] -= grx * s.m.rx + gry * s.m.ry;
+                gn = mk3(o_n[0], o_n[1], o_n[2]); gp = mk3(o_p[0], o_p[1], o_p[2]);
+                if (a.tex && a.gdata) s.e.scatter(a.gdata, (float) gI);
+            }
+        }
+        light_store_grads(a, i, gn, gp, gw);
+    }
+    if (a.slab) sensor_block_store<HF_PROJECTOR_SUMS>(M, a.slab); // (launch-uniform: no reduced gradient is wanted)
+}
+// g_tw[j] += column j, g_fov[0] += column 12 times d tau / tau per degree, g_scale[0] += column 13.  One block.
+__global__ __launch_bounds__(HF_BLOCK) void hf_projector_sum_kernel(const double *__restrict__ slab, uint32_t rows, double dtau,
+                                                                     float *__restrict__ g_tw, float *__restrict__ g_fov,
+                                                                     float *__restrict__ g_scale) {
+    const double *const sum = sensor_slab_sums<HF_PROJECTOR_SUMS>(slab, rows);
+    const uint32_t t = threadIdx.x;
+    if (t < 12u) {
+        if (g_tw) g_tw[t] += (float) sum[t];
+    } else if (t == 12u) {
+        if (g_fov) g_fov[0] += (float) (sum[12] * dtau);
+    } else if (t == 13u) {
+        if (g_scale) g_scale[0] += (float) sum[13];
+    }
+}
+size_t hf_projector_slab_doubles() { return (size_t) HF_XFORM_GRID_CAP * HF_PROJECTOR_SUMS; }
+
+// forward mode, the transpose of the above: the tangent of sample i's value for tangents dn of sh_n, dp of p, dw of
+// weight, dtex of the texels, d_tw of to_world, d_fov and d_scale (NULL: zero)
+__device__ __forceinline__ float projector_tangent_value(const hf_projector_args &a, size_t i) {
+    if (!a.vis[i]) return 0.f;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+    const hf_projector_shade s = projector_shade(a, p, sn);
+    if (!s.m.lit) return 0.f;
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const double dp[3] = { a.dp[0] ? (double) a.dp[0][i] : 0.0, a.dp[1] ? (double) a.dp[1][i] : 0.0, a.dp[2] ? (double) a.dp[2][i] : 0.0 };
+    const double n3[3] = { (double) sn.x, (double) sn.y, (double) sn.z };
+    const double dT = (a.d_fov ? (double) a.d_fov[0] * a.dtau : 0.0) / a.tau; // d tau / tau
+    double dq[3], dnu = sky_dot_f64(dn, s.u); // dp - dA ref - dc; d<sh_n, u>
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        double dA0 = 0.0, dA1 = 0.0, dA2 = 0.0, dc = 0.0;
+        if (a.d_tw) { dA0 = (double) a.d_tw[4 * k]; dA1 = (double) a.d_tw[4 * k + 1]; dA2 = (double) a.d_tw[4 * k + 2]; dc = (double) a.d_tw[4 * k + 3]; }
+        dq[k] = dp[k] - (dA0 * s.m.x + dA1 * s.m.y + dA2 * s.m.z) - dc;
+        dnu += n3[k] * (dc - dp[k]);
+    }
+    const double dx = a.Ai[0] * dq[0] + a.Ai[1] * dq[1] + a.Ai[2] * dq[2];
+    const double dy = a.Ai[3] * dq[0] + a.Ai[4] * dq[1] + a.Ai[5] * dq[2];
+    const double dz = a.Ai[6] * dq[0] + a.Ai[7] * dq[1] + a.Ai[8] * dq[2];
+    const double drx = (dx - s.m.rx * dz) * s.m.iz, dry = (dy - s.m.ry * dz) * s.m.iz;
+    double dI = s.Iu * ((-0.5 / a.tau) * (drx - s.m.rx * dT)) + s.Iv * ((-0.5 * a.aspect / a.tau) * (dry - s.m.ry * dT));
+    if (a.tex && a.ddata) dI += (double) s.e.value(a.ddata);
+    const double dG = dnu * s.iz3 - 3.0 * s.G * dz * s.m.iz;
+    const double w = a.weight ? (double) a.weight[i] : 1.0;
+    const double dwc = (a.dw ? (double) a.dw[i] : 0.0) * a.cs + w * ((a.d_scale ? (double) a.d_scale[0] : 0.0) * a.albedo);
+    return (float) (dwc * (s.I * s.G) + (w * a.cs) * (dI * s.G + s.I * dG));
+}
+// (the per-sample tangent is written too, and the image may be NULL)
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_projector_tangent_kernel(hf_projector_args a) {
+    light_tangent_image<PIXEL, hf_projector_args, projector_tangent_value>(a, a.value);
+}
+
+// mode 0: forward, 1: adjoint (and, where a reduced gradient is wanted, the sum of the blocks' rows), 2: tangent, 3: rays
+void hf_launch_projector(int mode, const hf_projector_args &a, hipStream_t stream) {
+    if (mode == 1) {
+        if (a.n == 0) return;
+        const int grid = grid_for(a.n, HF_XFORM_GRID_CAP); // the slab holds HF_XFORM_GRID_CAP rows
+        hipLaunchKernelGGL(hf_projector_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        // column 12 holds dL/d(ln tau): times d tau / tau per degree
+        if (a.slab)
+            hipLaunchKernelGGL(hf_projector_sum_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, a.slab, (uint32_t) grid, a.dtau / a.tau,
+                               a.g_tw, a.g_fov, a.g_scale);
+        return;
+    }
+    launch_light(mode, a, 1u, stream, hf_projector_kernel, hf_projector_adjoint_kernel, hf_projector_tangent_kernel<false>,
+                 hf_projector_tangent_kernel<true>, hf_projector_rays_kernel);
+}
+
+// ---------------------------------------------------------------------------------
 // Large-steps preconditioning (include/hf.h): A = I + lambda L on the W x H vertex grid, L the combinatorial
 // Laplacian of the tessellation (every cell split along v10-v01), and conjugate gradients for A v = u.
 //

@@ -306,6 +306,36 @@ struct hf_thinlens_project_args {
     float *g_radius, *g_focus;
 };
 void hf_launch_thinlens_project(int mode, const hf_thinlens_project_args &a, hipStream_t stream);
+// ---- projector lighting (hf_projector_rays, hf_projector_lighting / _adjoint / _tangent): the one argument
+// of its kernels; every constant of the mapping is formed on the host in double; TW, TH, wrap as in hf_bitmap_args
+// (bitmap_cell reads either) ----
+struct hf_projector_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, TW, TH;                    // TW, TH: read for the aspect without a texture too
+    int32_t wrap;                            // HF_WRAP_CLAMP / HF_WRAP_REPEAT
+    double Ai[9], c[3];                      // to_world^-1's linear part (adjugate, in double), to_world's c
+    double tau, dtau, aspect;                // tan(x_fov pi / 360), (pi / 360) (1 + tau^2), TW / TH
+    double albedo, cs;                       // cs = albedo scale
+    float cf[3];                             // c rounded to float32: what the shadow ray takes
+    const float *tex;                        // [TH][TW], NULL: uniform irradiance 1
+    const float *p[3], *nrm[3];              // si.p (every mode), si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight;
+    float *image, *value;                    // forward: written (NULL: not wanted); tangent: dimage, dvalue
+    uint8_t *vis;                            // forward: written (NULL: not wanted); adjoint, tangent: read
+    float *uv[2];                            // forward: written (NULL: not wanted)
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    const float *gimg, *gvalue;              // adjoint inputs (NULL: zero)
+    float *gn[3], *gp[3], *gw, *gdata;       // adjoint outputs (NULL: not wanted); gdata (the texels') is accumulated
+    double *slab;                            // adjoint: 14 doubles per block (NULL: no reduced gradient is wanted)
+    float *g_tw, *g_fov, *g_scale;           // adjoint outputs, accumulated (NULL: not wanted)
+    const float *dn[3], *dp[3], *dw, *ddata; // tangent inputs (NULL: zero); ddata: the texels'
+    const float *d_tw, *d_fov, *d_scale;     // tangent inputs: 12, 1, 1 device floats (NULL: zero)
+};
+// mode 0: forward, 1: adjoint (two launches where a reduced gradient is wanted), 2: tangent, 3: rays.  The forward launch
+// is hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
+void hf_launch_projector(int mode, const hf_projector_args &a, hipStream_t stream);
+size_t hf_projector_slab_doubles();
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
