@@ -1433,7 +1433,7 @@ int hf_thinlens_project_adjoint(const hf_thinlens_t *lens, size_t n, uint32_t st
  *   dI = Lx TW d uv.x + Ly TH d uv.y + sum_j b_j d tex_j,   d uv from the mapping above.
  * OUT OF SCOPE: the silhouette part of a moving shadow (hf_reparam_*'s, as in the rows above), sample_ray (light tracing
  * from the projector with importance-sampled pixels), RGB, the other fov_axis values, several projectors per call (call
- * once each and add the images), spot.cpp.
+ * once each and add the images).  spot.cpp is the next row's (hf_spot_lighting).
  * All entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional, n >= 2^32,
  * spp == 0 or n % spp != 0, TW == 0, TH == 0 or TW TH >= 2^31, a wrap that is neither, a non-finite field of the
  * projector, x_fov outside (0, 180), a to_world with scale, a non-finite albedo.  p, nrm, sh_n, d: 3 device rows of n
@@ -1488,6 +1488,95 @@ int hf_projector_lighting_tangent(size_t n, uint32_t spp, const float *const p[3
                                   float albedo, const uint8_t *vis, const float *const dsh_n[3], const float *const dp[3],
                                   const float *dweight, const float *dtex, const float *d_to_world, const float *d_fov,
                                   const float *d_scale, float *dimage, float *dvalue, hf_stream_t stream);
+
+/* ---- next row: spot lighting, a rig of up to HF_MAX_LIGHTS cone emitters whose shadow rays are traced in
+ * the kernel ----
+ *
+ * Replaces, for diffuse surfaces under 1 <= K <= HF_MAX_LIGHTS `spot` emitters (src/emitters/spot.cpp), the
+ * emitter-sampling term of the direct integrator (SpotLight::sample_direction, spot.cpp:177-212; falloff_curve,
+ * :143-151; attached BSDF value, diffuse.cpp:135-140) and the K shadow rays it traces, in ONE launch with one image per
+ * light: near-light photometric stereo.  A light with cutoff_angle = beam_width = 180 is the reference's point light.
+ *   lights      n_lights hf_spot_light_t, HOST memory.  to_world: row-major 3x4 [A | c], scale-free (hf_sensor_t's check);
+ *               intensity: W/sr on the axis; cutoff_angle, beam_width: degrees, 0 < beam_width <= cutoff_angle <= 180.
+ *               The host forms A^-1, the angles in radians and their cosines once, in double.
+ *   mapping     ref = A^-1 (p - c) in double from the float32 point; cos(theta) = ref.z / |ref|; the sample is in the
+ *               cone when cos(theta) > cos(cutoff), in the full beam when cos(theta) >= cos(beam), in the transition zone
+ *               when it is in the cone but not in the full beam;
+ *   falloff     f = 1 in the full beam, (cutoff - theta) / (cutoff - beam) in the zone with theta = atan2(hypot(ref.x,
+ *               ref.y), ref.z) (the acos of the cosine, better conditioned), 0 elsewhere.  cutoff == beam is a hard edge
+ *               without a zone; nothing divides by the zero width;
+ *   eligible    sample i when t_i is finite and <sh_n_i, -d_i> > 0 (the masks of every row); an eligible sample is TRACED
+ *               towards light k when f > 0 (spot.cpp:198), <sh_n, u> > 0 with u = c - p, and |u|^2 is finite and > 0 -- the
+ *               last two decided in float32 with c rounded to float32 (hf_projector_lighting's), f in double;
+ *   shadow ray  Interaction::spawn_ray_to(c), hf_projector_rays' ray unchanged;
+ *   vis[i]      one byte: bit k is set iff sample i was traced towards light k and the any-hit walk found nothing before
+ *               maxt (HF_MAX_LIGHTS = 8 fills the byte);
+ *   value[k][i] = weight_i albedo/pi intensity_k f <sh_n, u> / |u|^3 where bit k is set and exactly 0 elsewhere, formed in
+ *               double and rounded once;
+ *   image[k][i / spp] = 1/spp * sum value[k][i]: hf_point_lighting's layout, K images of n / spp, overwritten; n a
+ *               multiple of spp.
+ * Differentiated with respect to sh_n, p, weight and, per light, to_world (all 12 entries, unconstrained,
+ * hf_projector_lighting's convention), intensity, cutoff_angle and beam_width (per degree): HF_SPOT_PARAMS numbers per
+ * light in this order.  HELD: the visibility bits, every mask and the branch of the falloff.  With rho = hypot(ref.x,
+ * ref.y) (> 0 in the zone), S = <sh_n, u>, r = |u| and du = dc - dp:
+ *   d ref = A^-1 (dp - dA ref - dc),
+ *   in the zone: d theta = (ref.z d rho - rho d ref.z) / |ref|^2,  d rho = (ref.x d ref.x + ref.y d ref.y) / rho,
+ *                df = ((dcut - d theta) - f (dcut - dbeam)) / (cutoff - beam);   outside it df = 0, so a light with
+ *                cutoff == beam has exact zeros for both angle gradients,
+ *   d(S / r^3) = <d sh_n, u> / r^3 + <sh_n, du> / r^3 - 3 S <u, du> / r^5   (for dc = 0: hf_point_lighting's).
+ * OUT OF SCOPE: the `texture` parameter of spot.cpp (a textured cone is hf_projector_lighting's business), sample_ray,
+ * RGB, and the silhouette part of a moving shadow (hf_reparam_*'s, as in every row).
+ * All entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional, n >= 2^32,
+ * spp == 0 or n % spp != 0, n_lights outside 1..HF_MAX_LIGHTS, a non-finite field of a light, angles outside
+ * 0 < beam_width <= cutoff_angle <= 180, a to_world with scale, a non-finite albedo.  p, nrm, sh_n, d: 3 device rows of n
+ * floats; t: n.  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+#define HF_SPOT_PARAMS 15           /* to_world[12], intensity, cutoff_angle, beam_width: the order of every parameter row */
+typedef struct hf_spot_light {      /* HOST memory, as hf_projector_t */
+    double to_world[12];            /* row-major 3x4 [A | c], scale-free */
+    float intensity;                /* W/sr on the axis */
+    float cutoff_angle, beam_width; /* degrees, 0 < beam_width <= cutoff_angle <= 180 */
+} hf_spot_light_t;
+/* hf_spot_rays materialises the shadow ray of every sample towards ONE light (out_o, out_d: 3 rows of n floats; out_maxt: n
+ * floats, the finite maxt for a traced lane; a lane that is not traced gets a zero origin and direction and maxt = -1, a
+ * miss): bit k of hf_spot_lighting's vis equals hf_spot_rays(light k) + hf_ray_test bit for bit.  Takes no field handle. */
+int hf_spot_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                 const float *const d[3], const float *t, const hf_spot_light_t *light, float *const out_o[3],
+                 float *const out_d[3], float *out_maxt, hf_stream_t stream);
+/* The fused launch: reads a sample's record once and holds it across a wave-uniform loop over the lights; for each light
+ * it maps the point, finishes the value, runs the per-lane any-hit walk up to maxt where the sample is traced and reduces
+ * the film; image (K rows of n / spp), value (K rows of n) and vis (n bytes) may each be NULL (not wanted), not all of
+ * them; no ray and no hit byte goes to memory.  A batch of 64 samples with no lane traced towards light k skips that walk.
+ * hf_set_ray_coherence is neither read nor changed.  weight: n floats or NULL (1).  Allocates nothing, never synchronises
+ * the host, capturable. */
+int hf_spot_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],
+                     const float *const sh_n[3], const float *const d[3], const float *t, const float *weight,
+                     uint32_t n_lights, const hf_spot_light_t *lights, float albedo, float *image, float *value,
+                     uint8_t *vis, hf_stream_t stream);
+/* the adjoint's workspace in floats for a rig of n_lights (0 for a count outside 1..HF_MAX_LIGHTS) */
+size_t hf_spot_workspace_floats(uint32_t n_lights);
+/* Reverse mode.  Traces nothing: vis (as hf_spot_lighting wrote it) is read.  With the upstream of light k
+ * g_k = grad_image[k][i / spp] / spp + grad_value[k][i] (either may be NULL = zero): grad_sh_n, grad_p (3 rows each) and
+ * grad_weight are OVERWRITTEN, one lane per sample, the K lights summed in light order in double and rounded once, exact
+ * zeros where vis = 0, no atomics; grad_lights[K][HF_SPOT_PARAMS] (device floats) is ACCUMULATED into without atomics:
+ * every block stores the 15 partial sums of every light in double to `workspace` -- hf_spot_workspace_floats(n_lights)
+ * floats of device memory, 8-byte aligned, the caller's, this call's until it has completed; needed only when grad_lights
+ * is wanted -- and one more launch adds them in a fixed order (hf_sensor_rays_adjoint's pattern with rows of 15; family 2
+ * of hf_grid_blocks): bitwise the same from launch to launch.  Every output may be NULL (not wanted).  Takes no field
+ * handle. */
+int hf_spot_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                             const float *const d[3], const float *t, const float *weight, uint32_t n_lights,
+                             const hf_spot_light_t *lights, float albedo, const uint8_t *vis, const float *grad_image,
+                             const float *grad_value, float *const grad_sh_n[3], float *const grad_p[3], float *grad_weight,
+                             float *grad_lights, float *workspace, hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dsh_n, dp (3 rows of n floats each), dweight (n) and
+ * d_lights ([K][HF_SPOT_PARAMS] device floats), each may be NULL (zero); dimage (K rows of n / spp) and / or dvalue (K rows
+ * of n) are overwritten (at least one).  No atomics for any spp (a power of two <= 64: the film's shuffle tree; otherwise
+ * one lane adds the samples of a pixel in order): bitwise the same from launch to launch.  Takes no field handle. */
+int hf_spot_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                             const float *const d[3], const float *t, const float *weight, uint32_t n_lights,
+                             const hf_spot_light_t *lights, float albedo, const uint8_t *vis, const float *const dsh_n[3],
+                             const float *const dp[3], const float *dweight, const float *d_lights, float *dimage,
+                             float *dvalue, hf_stream_t stream);
 
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
@@ -1827,7 +1916,8 @@ int hf_invert_affine(const float in[12], float out[12]);
 /* blocks (of 256 threads) that a grid-stride launch of n items gets, HF_FORCE_GRID included.  family: 0 the flat cap
  * (adjoints, reparameterisation, Adam, area sampling, ...), 1 the cap of the streaming kernels (SI, hf_tangent, the
  * forward and tangent of attributes and of eval_parameterization, the sensor's rays, projection and their tangents), 2
- * the cap of the launches that sum dL/d(to_world), the sensor's adjoints and hf_projector_lighting_adjoint among them.
+ * the cap of the launches that sum dL/d(to_world), the sensor's adjoints, hf_projector_lighting_adjoint and hf_spot_lighting_adjoint among
+ * them.
  * 0 for an unknown family.  Needs no device. */
 int hf_grid_blocks(size_t n, int family);
 const char *hf_last_error_string(void);

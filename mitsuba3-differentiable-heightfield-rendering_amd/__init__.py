@@ -10,3 +10,4 @@ from .shape import (Adam, Bitmap, DirectionSample3f, Envmap, Frame3f, Heightfiel
                     sky_lighting, sky_rays)
 from .sensor import OrthographicCamera, PerspectiveCamera, ThinLensCamera  # noqa: F401
 from .projector import Projector, projector_lighting, projector_rays  # noqa: F401
+from .spot import SpotLight, spot_lighting, spot_rays  # noqa: F401

@@ -107,7 +107,26 @@ class hf_projector_t(C.Structure):
 _projector_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp,
                  C.POINTER(hf_projector_t), *_bitmap_in, C.c_float, _fp]
 
+class hf_spot_light_t(C.Structure):
+    _fields_ = [("to_world", C.c_double * 12), ("intensity", C.c_float), ("cutoff_angle", C.c_float), ("beam_width", C.c_float)]
+
+
+HF_SPOT_PARAMS = 15
+# n, spp, p, sh_n, d, t, weight, n_lights, lights, albedo, vis
+_spot_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32,
+            C.POINTER(hf_spot_light_t), C.c_float, _fp]
+
 SYMBOLS = {
+    "hf_spot_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
+                               C.POINTER(hf_spot_light_t), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    "hf_spot_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                   C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32, C.POINTER(hf_spot_light_t),
+                                   C.c_float, _fp, _fp, _fp, C.c_void_p]),
+    "hf_spot_workspace_floats": (C.c_size_t, [C.c_uint32]),
+    # ..., grad_image, grad_value, grad_sh_n, grad_p, grad_weight, grad_lights, workspace
+    "hf_spot_lighting_adjoint": (C.c_int, [*_spot_in, _fp, _fp, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, C.c_void_p]),
+    # ..., dsh_n, dp, dweight, d_lights, dimage, dvalue
+    "hf_spot_lighting_tangent": (C.c_int, [*_spot_in, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, C.c_void_p]),
     "hf_projector_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
                                     C.POINTER(hf_projector_t), C.c_uint32, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),
                                     _fp, C.c_void_p]),

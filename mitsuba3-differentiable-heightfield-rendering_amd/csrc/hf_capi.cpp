@@ -1755,6 +1755,140 @@ extern "C" int hf_projector_lighting_tangent(size_t n, uint32_t spp, const float
     return light_launch(hf_launch_projector, 2, a, stream);
 }
 
+// ---- spot lighting: a rig of 1..HF_MAX_LIGHTS cone emitters, the shadow rays traced in the kernel ----
+// What the four hf_spot_* entries share (hf_spot_rays passes spp 1, one light, albedo 1): the wavefront, every light's
+// checks, its affine inverse (formed once, here, in double: adjugate), the angles in radians and their cosines
+static int spot_args(const char *who, size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                     const float *const d[3], const float *t, const float *weight, uint32_t n_lights,
+                     const hf_spot_light_t *lights, float albedo, hf_spot_args &a) {
+    a = {};
+    if (!all3(p) || !all3(sh_n) || !all3(d) || !t || !lights) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (n_lights == 0 || n_lights > HF_MAX_LIGHTS)
+        return fail(HF_EINVAL, "%s: 1..%d lights supported (got %u)", who, HF_MAX_LIGHTS, n_lights);
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    const double rad = 3.141592653589793 / 180.0;
+    for (uint32_t l = 0; l < n_lights; ++l) {
+        const hf_spot_light_t &s = lights[l];
+        hf_spot_light_dev &o = a.L[l];
+        const double *M = s.to_world;
+        for (int j = 0; j < 12; ++j)
+            if (!isfinite(M[j])) return fail(HF_EINVAL, "%s: light %u: to_world must be finite", who, l);
+        if (!isfinite(s.intensity) || !isfinite(s.cutoff_angle) || !isfinite(s.beam_width))
+            return fail(HF_EINVAL, "%s: light %u: intensity, cutoff_angle and beam_width must be finite", who, l);
+        if (!(s.beam_width > 0.f) || !(s.beam_width <= s.cutoff_angle) || !(s.cutoff_angle <= 180.f))
+            return fail(HF_EINVAL, "%s: light %u: 0 < beam_width <= cutoff_angle <= 180 degrees (got %g, %g)", who, l,
+                        (double) s.beam_width, (double) s.cutoff_angle);
+        for (int i = 0; i < 3; ++i) // spot.cpp: has_scale(), hf_sensor_t's check
+            for (int j = i; j < 3; ++j) {
+                const double g = M[i] * M[j] + M[4 + i] * M[4 + j] + M[8 + i] * M[8 + j];
+                if (fabs(g - (i == j ? 1.0 : 0.0)) > 1e-4)
+                    return fail(HF_EINVAL, "%s: light %u: scale factors in to_world are not allowed", who, l);
+            }
+        const double m[3][3] = { { M[0], M[1], M[2] }, { M[4], M[5], M[6] }, { M[8], M[9], M[10] } };
+        const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) { // Ai[r][c] = cofactor(c, r) / det
+                const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+                o.Ai[3 * r + c] = (m[r1][c1] * m[r2][c2] - m[r1][c2] * m[r2][c1]) / det;
+            }
+        for (int k = 0; k < 3; ++k) { o.c[k] = M[4 * k + 3]; o.cf[k] = (float) M[4 * k + 3]; }
+        o.cutoff = (double) s.cutoff_angle * rad; o.beam = (double) s.beam_width * rad;
+        // (180 degrees: cos(pi) rounds to -1 exactly, so cutoff = beam = 180 lights every direction but the one behind)
+        o.cos_cutoff = cos(o.cutoff); o.cos_beam = cos(o.beam);
+        o.inv_width = s.cutoff_angle > s.beam_width ? 1.0 / (o.cutoff - o.beam) : 0.0;
+        o.ci = (double) albedo / 3.141592653589793 * (double) s.intensity;
+    }
+    for (int k = 0; k < 3; ++k) { a.p[k] = p[k]; a.sh_n[k] = sh_n[k]; a.d[k] = d[k]; }
+    a.n = n; a.spp = spp; a.n_lights = n_lights; a.t = t; a.weight = weight;
+    a.albedo_pi = (double) albedo / 3.141592653589793;
+    // atan(t) / t as a polynomial in t^2 on [0, tan(pi / 8)] (Chebyshev interpolation, degree 9: 7e-16 off), then the
+    // constants of the two folds
+    static const double atan_c[14] = { 0.99999999999999922, -0.33333333333215148, 0.19999999977575814, -0.14285712620968255,
+                                       0.11111047794231604, -0.090895137758045072, 0.076733844914957605, -0.065051346366116522,
+                                       0.05022119694104614, -0.025281436432647405, 0.41421356237309503, 0.78539816339744831,
+                                       1.5707963267948966, 3.141592653589793 };
+    for (int j = 0; j < 14; ++j) a.atan_c[j] = atan_c[j];
+    return HF_OK;
+}
+
+extern "C" int hf_spot_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                            const float *const d[3], const float *t, const hf_spot_light_t *light, float *const out_o[3],
+                            float *const out_d[3], float *out_maxt, hf_stream_t stream) {
+    const char *fn = "hf_spot_rays";
+    hf_spot_args a;
+    int rc = spot_args(fn, n, 1, p, sh_n, d, t, nullptr, 1, light, 1.f, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_spot, 3, a, stream);
+}
+
+extern "C" int hf_spot_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                const float *t, const float *weight, uint32_t n_lights, const hf_spot_light_t *lights,
+                                float albedo, float *image, float *value, uint8_t *vis, hf_stream_t stream) {
+    const char *fn = "hf_spot_lighting";
+    hf_spot_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = spot_args(fn, n, spp, p, sh_n, d, t, weight, n_lights, lights, albedo, a);
+    if (rc != HF_OK || (rc = light_forward_out(fn, p, nrm, image, a, true))) return rc;
+    if (!image && !value && !vis) return fail(HF_EINVAL, "%s: image, value and vis are all NULL", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.value = value; a.vis = vis;
+    return light_launch(hf_launch_spot, 0, a, stream);
+}
+
+extern "C" size_t hf_spot_workspace_floats(uint32_t n_lights) {
+    return n_lights >= 1 && n_lights <= HF_MAX_LIGHTS ? 2u * hf_spot_slab_doubles(n_lights) : 0u;
+}
+
+extern "C" int hf_spot_lighting_adjoint(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                        const float *const d[3], const float *t, const float *weight, uint32_t n_lights,
+                                        const hf_spot_light_t *lights, float albedo, const uint8_t *vis,
+                                        const float *grad_image, const float *grad_value, float *const grad_sh_n[3],
+                                        float *const grad_p[3], float *grad_weight, float *grad_lights, float *workspace,
+                                        hf_stream_t stream) {
+    const char *fn = "hf_spot_lighting_adjoint";
+    hf_spot_args a;
+    int rc = spot_args(fn, n, spp, p, sh_n, d, t, weight, n_lights, lights, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
+    if (grad_p && !all3(grad_p)) return fail(HF_EINVAL, "%s: NULL grad_p component array", fn);
+    if (grad_lights && !workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_lights && ((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    a.vis = const_cast<uint8_t *>(vis);
+    a.gimg = grad_image; a.gvalue = grad_value; a.gw = grad_weight;
+    for (int c = 0; c < 3; ++c) { a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr; a.gp[c] = grad_p ? grad_p[c] : nullptr; }
+    a.slab = grad_lights ? (double *) workspace : nullptr;
+    a.g_lights = grad_lights;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_spot, 1, a, stream);
+}
+
+extern "C" int hf_spot_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], const float *const sh_n[3],
+                                        const float *const d[3], const float *t, const float *weight, uint32_t n_lights,
+                                        const hf_spot_light_t *lights, float albedo, const uint8_t *vis,
+                                        const float *const dsh_n[3], const float *const dp[3], const float *dweight,
+                                        const float *d_lights, float *dimage, float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_spot_lighting_tangent";
+    hf_spot_args a;
+    int rc = spot_args(fn, n, spp, p, sh_n, d, t, weight, n_lights, lights, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
+    if (dp && !all3(dp)) return fail(HF_EINVAL, "%s: NULL dp component array", fn);
+    if ((rc = light_tangent_io(fn, false, dsh_n, dweight, dimage, a, true))) return rc;
+    a.vis = const_cast<uint8_t *>(vis); a.value = dvalue;
+    for (int c = 0; c < 3; ++c) a.dp[c] = dp ? dp[c] : nullptr;
+    a.d_lights = d_lights;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_spot, 2, a, stream);
+}
+
 // ---- the sensor: the primary wavefront of a perspective or an orthographic camera ----
 static int log2_or_minus1(uint32_t v) {
     if (v == 0 || (v & (v - 1u))) return -1;

@@ -7718,6 +7718,362 @@ void hf_launch_projector(int mode, const hf_projector_args &a, hipStream_t strea
 }
 
 // ---------------------------------------------------------------------------------
+// Spot lighting (include/hf.h hf_spot_*): diffuse surface under a RIG of 1..HF_MAX_LIGHTS `spot` emitters
+// (src/emitters/spot.cpp), cones with a linear falloff between beam_width and cutoff_angle.  Every light is a point, so
+// there is one draw per sample and light: the cone mapping p -> theta, the falloff, the shadow ray towards c
+// (the projector's, Interaction::spawn_ray_to) traced (any hit, per lane) and the film, for ALL lights in ONE launch:
+// the sample's record is read once and held across a wave-uniform loop over the lights (hf_sky_kernel's k loop),
+//   value_k = weight albedo / pi intensity_k f_k <sh_n, u> / |u|^3,   u = c_k - p.
+// The row's own text is the mapping, the falloff and their derivatives; the masks, the origin, the ray, the walk, the
+// film and the launch are the lighting rows' and the projector's shared functions, the reduction of the 15 numbers of
+// every light the sensor's (sensor_block_store, sensor_slab_sums).
+// (LP below: a pointer to one hf_spot_light_dev, in the kernarg segment or not)
+// ---------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) hf_spot_args *hf_spot_kargs;
+
+// The mapping (spot.cpp:183-198) in double from the float32 point: ref = to_world^-1 p, cos(theta) = ref.z / |ref|, and
+// falloff_curve (:143-151) with theta = atan2(hypot(ref.x, ref.y), ref.z) (spot_theta): the acos of the cosine, better
+// conditioned.
+// The sums are written as fma chains: the forward and the rays kernel must form the same bits
+struct hf_spot_map {
+    double x, y, z; // ref
+    double r2;      // |ref|^2
+    double f;       // the falloff of the branch the point is on: 1 in the full beam, the ramp elsewhere (the cone is `lit`'s)
+    bool full, lit; // cos(theta) >= cos(beam); in the cone with f > 0
+};
+// theta = atan2(rho, z) for rho >= 0, in [0, pi]: t = min / max of (rho, |z|), folded once more about tan(pi / 8) with
+// the same single division ((t - 1) / (t + 1) = (min - max) / (min + max)), then an odd polynomial of degree 19 whose
+// error on [0, tan(pi / 8)] is 7e-16.  C: its ten coefficients, tan(pi / 8), pi / 4, pi / 2 and pi -- fourteen doubles of
+// the kernarg segment, scalar operands: the library's atan2 keeps twenty-one constants in vector registers, which the
+// loop over the lights hoists and then spills (43 registers of hf_spot_kernel)
+template <class CP>
+__device__ __forceinline__ double spot_theta(CP C, double rho, double z) {
+    const double az = fabs(z), lo = fmin(rho, az), hi = fmax(rho, az);
+    const bool fold = lo > C[10] * hi;
+    const double t = (fold ? lo - hi : lo) / (fold ? lo + hi : hi), s = t * t;
+    double q = C[9];
+#pragma unroll
+    for (int j = 8; j >= 0; --j) q = fma(q, s, C[j]);
+    double r = q * t;
+    if (fold) r += C[11];
+    if (rho > az) r = C[12] - r;
+    if (z < 0.0) r = C[13] - r;
+    return r;
+}
+template <class LP, class CP>
+__device__ __forceinline__ hf_spot_map spot_map(LP L, CP C, v3 p) {
+    hf_spot_map m;
+    const double q0 = (double) p.x - L->c[0], q1 = (double) p.y - L->c[1], q2 = (double) p.z - L->c[2];
+    m.x = fma(L->Ai[0], q0, fma(L->Ai[1], q1, L->Ai[2] * q2));
+    m.y = fma(L->Ai[3], q0, fma(L->Ai[4], q1, L->Ai[5] * q2));
+    m.z = fma(L->Ai[6], q0, fma(L->Ai[7], q1, L->Ai[8] * q2));
+    const double rho2 = fma(m.x, m.x, m.y * m.y);
+    m.r2 = fma(m.z, m.z, rho2);
+    const double co = m.z / sqrt(m.r2); // (NaN at the apex: in no cone)
+    m.full = co >= L->cos_beam;
+    m.f = 1.0;
+    if (!m.full) m.f = (L->cutoff - spot_theta(C, sqrt(rho2), m.z)) * L->inv_width; // (a hard edge: inv_width = 0, no division)
+    m.lit = co > L->cos_cutoff && m.f > 0.0;
+    return m;
+}
+
+#ifndef HF_SPOT_WAVES
+#define HF_SPOT_WAVES 6 // resident waves per SIMD (the siblings')
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_SPOT_WAVES) void hf_spot_kernel(hf_spot_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    hf_spot_kargs ka = (hf_spot_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    // the sample's record: read once, held across the loop over the lights
+    const v3 sn = mk3(ka->sh_n[0][ii], ka->sh_n[1][ii], ka->sh_n[2][ii]);
+    bool elig;
+    {
+        const v3 d = mk3(ka->d[0][ii], ka->d[1][ii], ka->d[2][ii]);
+        elig = in && sky_eligible(ka->t[ii], sn, d);
+    }
+    const v3 p = mk3(ka->p[0][ii], ka->p[1][ii], ka->p[2][ii]);
+    const v3 gn = mk3(ka->nrm[0][ii], ka->nrm[1][ii], ka->nrm[2][ii]);
+    float wgt = 1.f;
+    {
+        const float *weight = ka->weight;
+        if (weight) wgt = weight[ii];
+    }
+    uint32_t bits = 0u; // bit k: the sample was traced towards light k and nothing is in the way
+#pragma unroll 1
+    for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+        asm volatile("" : "+s"(ka)); // opaque per light: the kernarg loads stay inside the loop
+        // light k's value of a sample that turns out visible: finished and rounded before the ray is begun (the
+        // projector kernel's discipline), one float held across the walk
+        float val = 0.f;
+        bool lit = false;
+        {
+            v3 pd = p, snd = sn; // (opaque: the conversions to double are otherwise hoisted out of the loop and held across the walk)
+            asm volatile("" : "+v"(pd.x), "+v"(pd.y), "+v"(pd.z), "+v"(snd.x), "+v"(snd.y), "+v"(snd.z));
+            if (elig) {
+                const hf_spot_map m = spot_map(&ka->L[k], &ka->atan_c[0], pd);
+                lit = m.lit;
+                if (lit) {
+                    const hf_d3 u = hf_d3{ ka->L[k].c[0] - (double) pd.x, ka->L[k].c[1] - (double) pd.y, ka->L[k].c[2] - (double) pd.z };
+                    const double r2 = fma(u.x, u.x, fma(u.y, u.y, u.z * u.z));
+                    val = (float) ((double) wgt * (ka->L[k].ci * m.f) * (sky_dot_f64(snd, u) / (r2 * sqrt(r2))));
+                }
+            }
+        }
+        asm volatile("" : "+v"(val));
+        const v3 cf = mk3(ka->L[k].cf[0], ka->L[k].cf[1], ka->L[k].cf[2]);
+        const bool traced = elig && lit && projector_front(cf, p, sn);
+        hf_hit best;
+        best.hit = false;
+        if (__ballot(traced) != 0ull) { // wave-uniform: a batch without a sample traced towards this light skips its walk
+            const hf_projector_ray r = projector_ray(cf, p, gn, sky_offset(p));
+            light_walk<true>(&ka->f, f, r.o, r.w, r.maxt, traced, best);
+        }
+        // (the output pointers: loaded here, not before the walk)
+        hf_spot_kargs ko = (hf_spot_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ko));
+        const bool seen = traced && !best.hit; // (traced: in range)
+        if (!seen) val = 0.f;
+        if (seen) bits |= 1u << k;
+        float *value = ko->value;
+        if (in && value) value[(size_t) k * ko->n + i] = val;
+        float *image = ko->image;
+        if (image) { // the film of light k: hf_point_lighting's layout, K images of n / spp
+            const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+            film_pixel(image, val, k, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+        }
+        if (k + 1u >= ko->n_lights) break;
+    }
+    hf_spot_kargs ko = (hf_spot_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    uint8_t *vis = ko->vis;
+    if (in && vis) vis[i] = (uint8_t) bits;
+}
+
+// the shadow ray of every sample towards ONE light (L[0]), materialised: what hf_spot_kernel traces for it, bit for bit
+// (an untraced lane: a zero origin and direction, maxt = -1)
+__global__ __launch_bounds__(HF_BLOCK) void hf_spot_rays_kernel(hf_spot_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    hf_spot_kargs ka = (hf_spot_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    v3 sn;
+    const bool elig = light_sample(a, i, sn);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    const v3 cf = mk3(ka->L[0].cf[0], ka->L[0].cf[1], ka->L[0].cf[2]);
+    const bool traced = elig && spot_map(&ka->L[0], &ka->atan_c[0], p).lit && projector_front(cf, p, sn);
+    const hf_projector_ray r = projector_ray(cf, p, gn, sky_offset(p));
+    const v3 z = mk3(0.f, 0.f, 0.f);
+    light_store_ray(a, i, traced ? r.o : z, traced ? r.w : z, traced, r.maxt);
+}
+
+// What the two derivative kernels form again of a sample whose bit for light L is set: the mapping (the branch of the
+// falloff is the one the point is on, the cone is the bit's), u = c - p, S = <sh_n, u>, |u|^-2, |u|^-3 and G = S / |u|^3
+struct hf_spot_shade {
+    hf_spot_map m;
+    hf_d3 u;
+    double S, ir2, ir3, G;
+    bool ok; // the guard of the divisions: a sample that hf_spot_kernel found visible passes it
+};
+template <class LP, class CP>
+__device__ __forceinline__ hf_spot_shade spot_shade(LP L, CP C, v3 p, v3 sn) {
+    hf_spot_shade s;
+    s.m = spot_map(L, C, p);
+    s.u = hf_d3{ L->c[0] - (double) p.x, L->c[1] - (double) p.y, L->c[2] - (double) p.z };
+    s.S = sky_dot_f64(sn, s.u);
+    const double r2 = fma(s.u.x, s.u.x, fma(s.u.y, s.u.y, s.u.z * s.u.z));
+    s.ir2 = 1.0 / r2; s.ir3 = s.ir2 / sqrt(r2);
+    s.G = s.S * s.ir3;
+    s.ok = r2 > 0.0 && s.m.r2 > 0.0 && (s.m.full || fma(s.m.x, s.m.x, s.m.y * s.m.y) > 0.0);
+    return s;
+}
+// the upstream of light k's value of sample i: grad_image[k][i / spp] / spp + grad_value[k][i] (NULL: zero)
+__device__ __forceinline__ float spot_value_seed(const hf_spot_args &a, uint32_t k, size_t i) {
+    return (a.gimg ? a.gimg[(size_t) k * (a.n / a.spp) + i / a.spp] * (1.0f / (float) a.spp) : 0.f) +
+           (a.gvalue ? a.gvalue[(size_t) k * a.n + i] : 0.f);
+}
+// Reverse mode of ONE light's value = w ci f G of one sample, for the upstream g:
+//   gn = dL/dsh_n,  h = dL/dq (q = p - c, through ref = A^-1 q),  gu = dL/du (through S and |u|),  gw = dL/dweight,
+//   gi = dL/dintensity, gcut, gbeam = dL/dcutoff, dL/dbeam (per radian)
+struct hf_spot_grads { double gn[3], h[3], gu[3], gw, gi, gcut, gbeam; };
+template <class LP>
+__device__ __forceinline__ hf_spot_grads spot_light_grads(LP L, double albedo_pi, const hf_spot_shade &s, v3 sn, double g, double w) {
+    hf_spot_grads o;
+    const double fG = s.m.f * s.G;
+    o.gw = g * L->ci * fG;
+    o.gi = g * w * albedo_pi * fG;
+    const double gf = (g * w * L->ci) * s.G, gG = (g * w * L->ci) * s.m.f; // dL/df, dL/dG
+    double gx = 0.0, gy = 0.0, gz = 0.0;
+    o.gcut = 0.0; o.gbeam = 0.0;
+    if (!s.m.full) { // the zone: f = (cutoff - theta) / (cutoff - beam), theta = atan2(rho, ref.z)
+        const double t = gf * L->inv_width;
+        o.gcut = t * (1.0 - s.m.f); o.gbeam = t * s.m.f;
+        const double rho = sqrt(fma(s.m.x, s.m.x, s.m.y * s.m.y)), ir2 = 1.0 / s.m.r2;
+        const double grho = -t * s.m.z * ir2; // dL/dtheta = -t; d theta = (z d rho - rho dz) / |ref|^2
+        gz = t * rho * ir2;
+        gx = grho * (s.m.x / rho); gy = grho * (s.m.y / rho);
+    }
+    const double gS = gG * s.ir3, gr = -3.0 * gG * s.G * s.ir2; // dL/dS; dL/du through |u|: gr u
+    const double n3[3] = { (double) sn.x, (double) sn.y, (double) sn.z }, u3[3] = { s.u.x, s.u.y, s.u.z };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        o.h[c] = L->Ai[c] * gx + L->Ai[3 + c] * gy + L->Ai[6 + c] * gz; // to_world^-T dL/dref
+        o.gn[c] = gS * u3[c];
+        o.gu[c] = gS * n3[c] + gr * u3[c];
+    }
+    return o;
+}
+
+// Reverse mode of hf_spot_kernel with respect to sh_n, p, weight and, per light, to_world, intensity and both angles:
+// nothing is traced, the visibility byte is read.  First every sample's own gradients: one lane per sample, the lights
+// of its byte summed in light order in double and rounded once, overwritten, no atomics.  Then, where grad_lights is
+// wanted, light by light (wave-uniform): the 15 numbers of the light kept per lane in double across the grid-stride loop
+// over the samples whose bit is set, and reduced as the sensor's 13 (K x 15 live doubles would not fit a lane)
+#define HF_SPOT_SUMS 15
+__global__ __launch_bounds__(HF_BLOCK) void hf_spot_adjoint_kernel(hf_spot_args a) {
+    hf_spot_kargs ka = (hf_spot_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    if (a.gn[0] || a.gp[0] || a.gw) { // (launch-uniform)
+        for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+            const uint32_t bits = a.vis[i];
+            double gn[3] = { 0.0, 0.0, 0.0 }, gp[3] = { 0.0, 0.0, 0.0 }, gw = 0.0;
+            if (bits) {
+                const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+                const double w = a.weight ? (double) a.weight[i] : 1.0;
+#pragma unroll 1
+                for (uint32_t k = 0; k < a.n_lights; ++k) {
+                    if (!((bits >> k) & 1u)) continue;
+                    const hf_spot_shade s = spot_shade(&ka->L[k], &ka->atan_c[0], p, sn);
+                    if (!s.ok) continue;
+                    const hf_spot_grads o = spot_light_grads(&ka->L[k], a.albedo_pi, s, sn, (double) spot_value_seed(a, k, i), w);
+                    gw += o.gw;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) { gn[c] += o.gn[c]; gp[c] += o.h[c] - o.gu[c]; }
+                }
+            }
+            light_store_grads(a, i, mk3((float) gn[0], (float) gn[1], (float) gn[2]), mk3((float) gp[0], (float) gp[1], (float) gp[2]),
+                              (float) gw);
+        }
+    }
+    if (!a.slab) return; // (launch-uniform: grad_lights is not wanted)
+#pragma unroll 1
+    for (uint32_t k = 0; k < a.n_lights; ++k) { // block-uniform
+        double M[HF_SPOT_SUMS];
+#pragma unroll
+        for (int j = 0; j < HF_SPOT_SUMS; ++j) M[j] = 0.0;
+        for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+            if (!((a.vis[i] >> k) & 1u)) continue;
+            const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+            const hf_spot_shade s = spot_shade(&ka->L[k], &ka->atan_c[0], p, sn);
+            if (!s.ok) continue;
+            const hf_spot_grads o = spot_light_grads(&ka->L[k], a.albedo_pi, s, sn, (double) spot_value_seed(a, k, i),
+                                                     a.weight ? (double) a.weight[i] : 1.0);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { // q = p - c and ref = A^-1 q: d ref = A^-1 (dp - dA ref - dc); u = c - p
+                M[4 * c] -= o.h[c] * s.m.x; M[4 * c + 1] -= o.h[c] * s.m.y; M[4 * c + 2] -= o.h[c] * s.m.z;
+                M[4 * c + 3] += o.gu[c] - o.h[c];
+            }
+            M[12] += o.gi; M[13] += o.gcut; M[14] += o.gbeam;
+        }
+        sensor_block_store<HF_SPOT_SUMS>(M, a.slab + (size_t) k * gridDim.x * HF_SPOT_SUMS);
+        __syncthreads(); // (the next light's sums go through the same LDS rows)
+    }
+}
+// block k: g_lights[k][j] += column j of light k's rows; the angles' columns (per radian) times pi / 180: per degree
+__global__ __launch_bounds__(HF_BLOCK) void hf_spot_sum_kernel(const double *__restrict__ slab, uint32_t rows, float *__restrict__ g_lights) {
+    const double *const sum = sensor_slab_sums<HF_SPOT_SUMS>(slab + (size_t) blockIdx.x * rows * HF_SPOT_SUMS, rows);
+    const uint32_t t = threadIdx.x;
+    if (t < (uint32_t) HF_SPOT_SUMS)
+        g_lights[blockIdx.x * HF_SPOT_SUMS + t] += (float) (t < 13u ? sum[t] : sum[t] * (3.141592653589793 / 180.0));
+}
+size_t hf_spot_slab_doubles(uint32_t n_lights) { return (size_t) HF_XFORM_GRID_CAP * HF_SPOT_SUMS * n_lights; }
+
+// forward mode, the transpose of the above: the tangent of light k's value of sample i for tangents dn of sh_n, dp of p,
+// dw of weight and row k of d_lights (NULL: zero)
+template <class LP, class CP>
+__device__ __forceinline__ float spot_tangent_value(const hf_spot_args &a, LP L, CP C, uint32_t k, size_t i) {
+    if (!((a.vis[i] >> k) & 1u)) return 0.f;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]);
+    const hf_spot_shade s = spot_shade(L, C, p, sn);
+    if (!s.ok) return 0.f;
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const double dp[3] = { a.dp[0] ? (double) a.dp[0][i] : 0.0, a.dp[1] ? (double) a.dp[1][i] : 0.0, a.dp[2] ? (double) a.dp[2][i] : 0.0 };
+    const double n3[3] = { (double) sn.x, (double) sn.y, (double) sn.z }, u3[3] = { s.u.x, s.u.y, s.u.z };
+    const float *dl = a.d_lights ? a.d_lights + k * HF_SPOT_SUMS : nullptr;
+    double dq[3], dS = sky_dot_f64(dn, s.u), udu = 0.0; // dp - dA ref - dc; d<sh_n, u>; <u, du>
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double dA0 = 0.0, dA1 = 0.0, dA2 = 0.0, dc = 0.0;
+        if (dl) { dA0 = (double) dl[4 * c]; dA1 = (double) dl[4 * c + 1]; dA2 = (double) dl[4 * c + 2]; dc = (double) dl[4 * c + 3]; }
+        dq[c] = dp[c] - (dA0 * s.m.x + dA1 * s.m.y + dA2 * s.m.z) - dc;
+        dS += n3[c] * (dc - dp[c]);
+        udu += u3[c] * (dc - dp[c]);
+    }
+    double df = 0.0;
+    if (!s.m.full) {
+        const double dx = L->Ai[0] * dq[0] + L->Ai[1] * dq[1] + L->Ai[2] * dq[2];
+        const double dy = L->Ai[3] * dq[0] + L->Ai[4] * dq[1] + L->Ai[5] * dq[2];
+        const double dz = L->Ai[6] * dq[0] + L->Ai[7] * dq[1] + L->Ai[8] * dq[2];
+        const double rho = sqrt(fma(s.m.x, s.m.x, s.m.y * s.m.y));
+        const double drho = (s.m.x * dx + s.m.y * dy) / rho;
+        const double dth = (s.m.z * drho - rho * dz) / s.m.r2;
+        const double dcut = dl ? (double) dl[13] * (3.141592653589793 / 180.0) : 0.0;
+        const double dbeam = dl ? (double) dl[14] * (3.141592653589793 / 180.0) : 0.0;
+        df = ((dcut - dth) - s.m.f * (dcut - dbeam)) * L->inv_width;
+    }
+    const double dG = dS * s.ir3 - 3.0 * s.G * udu * s.ir2;
+    const double w = a.weight ? (double) a.weight[i] : 1.0;
+    const double dwc = (a.dw ? (double) a.dw[i] : 0.0) * L->ci + w * ((dl ? (double) dl[12] : 0.0) * a.albedo_pi);
+    return (float) (dwc * (s.m.f * s.G) + (w * L->ci) * (df * s.G + s.m.f * dG));
+}
+// light_tangent_image with a loop over the lights: PIXEL = false: one lane per sample and the primal's film (spp a power
+// of two <= 64, or no image wanted); PIXEL = true: one lane per pixel adds its samples in order -- no atomics either way
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_spot_tangent_kernel(hf_spot_args a) {
+    hf_spot_kargs ka = (hf_spot_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    const size_t npix = a.n / spp;
+    if (PIXEL) {
+        if (i >= npix) return;
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.n_lights; ++k) {
+            float c = 0.f;
+            for (uint32_t s = 0; s < spp; ++s) {
+                const float dv = spot_tangent_value(a, &ka->L[k], &ka->atan_c[0], k, i * spp + s);
+                if (a.value) a.value[(size_t) k * a.n + i * spp + s] = dv;
+                c += dv;
+            }
+            a.image[(size_t) k * npix + i] = c * (1.0f / (float) spp);
+        }
+    } else {
+        const bool in = i < a.n;
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.n_lights; ++k) { // wave-uniform
+            const float c = spot_tangent_value(a, &ka->L[k], &ka->atan_c[0], k, in ? i : a.n - 1);
+            if (in && a.value) a.value[(size_t) k * a.n + i] = c;
+            if (a.image) film_pixel(a.image, in ? c : 0.f, k, npix, i, spp, in, true, spp, 1.0f / (float) spp);
+        }
+    }
+}
+
+// mode 0: forward, 1: adjoint (and, where grad_lights is wanted, the sum of the blocks' rows, one block per light),
+// 2: tangent, 3: rays
+void hf_launch_spot(int mode, const hf_spot_args &a, hipStream_t stream) {
+    if (mode == 1) {
+        if (a.n == 0) return;
+        const int grid = grid_for(a.n, HF_XFORM_GRID_CAP); // the slab holds HF_XFORM_GRID_CAP rows per light
+        hipLaunchKernelGGL(hf_spot_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        if (a.slab)
+            hipLaunchKernelGGL(hf_spot_sum_kernel, dim3(a.n_lights), dim3(HF_BLOCK), 0, stream, a.slab, (uint32_t) grid, a.g_lights);
+        return;
+    }
+    launch_light(mode, a, a.n_lights, stream, hf_spot_kernel, hf_spot_adjoint_kernel, hf_spot_tangent_kernel<false>,
+                 hf_spot_tangent_kernel<true>, hf_spot_rays_kernel);
+}
+
+// ---------------------------------------------------------------------------------
 // Large-steps preconditioning (include/hf.h): A = I + lambda L on the W x H vertex grid, L the combinatorial
 // Laplacian of the tessellation (every cell split along v10-v01), and conjugate gradients for A v = u.
 //

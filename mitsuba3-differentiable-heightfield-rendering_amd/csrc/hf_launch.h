@@ -336,6 +336,39 @@ struct hf_projector_args {
 // is hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
 void hf_launch_projector(int mode, const hf_projector_args &a, hipStream_t stream);
 size_t hf_projector_slab_doubles();
+// ---- spot lighting (hf_spot_rays, hf_spot_lighting / _adjoint / _tangent): a rig of up to HF_MAX_LIGHTS
+// cone emitters in one launch.  One light of the rig, every constant formed on the host in double ----
+struct hf_spot_light_dev {
+    double Ai[9], c[3];                      // to_world^-1's linear part (adjugate, in double), to_world's c
+    double cutoff, beam;                     // radians
+    double cos_cutoff, cos_beam;
+    double inv_width;                        // 1 / (cutoff - beam); 0 for a hard edge (cutoff == beam: there is no zone)
+    double ci;                               // albedo / pi * intensity
+    float cf[3], pad;                        // c rounded to float32: what the shadow ray takes
+};
+struct hf_spot_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, n_lights;
+    double albedo_pi;                        // albedo / pi: d value / d intensity
+    double atan_c[14];                       // spot_theta's constants: 10 coefficients, tan(pi / 8), pi / 4, pi / 2, pi
+    hf_spot_light_dev L[HF_MAX_LIGHTS];      // the first n_lights are read
+    const float *p[3], *nrm[3];              // si.p (every mode), si.n (forward, rays)
+    const float *sh_n[3], *d[3], *t, *weight;
+    float *image, *value;                    // forward: written, K rows each (NULL: not wanted); tangent: dimage, dvalue
+    uint8_t *vis;                            // forward: written (NULL: not wanted); adjoint, tangent: read; bit k: light k
+    float *out_o[3], *out_d[3], *out_maxt;   // rays (of light 0)
+    const float *gimg, *gvalue;              // adjoint inputs, K rows each (NULL: zero)
+    float *gn[3], *gp[3], *gw;               // adjoint outputs (NULL: not wanted)
+    double *slab;                            // adjoint: per light, 15 doubles per block (NULL: grad_lights is not wanted)
+    float *g_lights;                         // adjoint output [K][15], accumulated
+    const float *dn[3], *dp[3], *dw;         // tangent inputs (NULL: zero)
+    const float *d_lights;                   // tangent input [K][15] device floats (NULL: zero)
+};
+// mode 0: forward, 1: adjoint (two launches where grad_lights is wanted), 2: tangent, 3: rays.  The forward launch is
+// hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
+void hf_launch_spot(int mode, const hf_spot_args &a, hipStream_t stream);
+size_t hf_spot_slab_doubles(uint32_t n_lights);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
