@@ -1578,6 +1578,91 @@ int hf_spot_lighting_tangent(size_t n, uint32_t spp, const float *const p[3], co
                              const float *const dp[3], const float *dweight, const float *d_lights, float *dimage,
                              float *dvalue, hf_stream_t stream);
 
+/* ---- next row: directional lighting, a rig of up to HF_MAX_LIGHTS distant emitters whose shadow rays are
+ * traced in the kernel ----
+ *
+ * Replaces, for diffuse surfaces under 1 <= K <= HF_MAX_LIGHTS `directional` emitters (src/emitters/directional.cpp), the
+ * emitter-sampling term of the direct integrator (DirectionalEmitter::sample_direction, directional.cpp:150-177;
+ * attached BSDF value, diffuse.cpp:135-140) and the K shadow rays it traces, in ONE launch with one image per light:
+ * photometric stereo with cast shadows.  hf_direct_lighting* takes the visibility from the caller and holds the lights
+ * constant; this row traces it and differentiates them.  hf_direct_lighting* itself is unchanged.
+ *   lights      n_lights hf_directional_light_t, HOST memory.  to_light: towards the light (the reference's `direction`
+ *               is -to_light), any finite length > 0; the host forms l = to_light / |to_light| once, in double.
+ *               irradiance: W/m^2 on a surface facing the light (directional.cpp:82, 174).
+ *   eligible    sample i when t_i is finite and <sh_n_i, -d_i> > 0 (the masks of every row); an eligible sample is TRACED
+ *               towards light k when <sh_n, l_k> > 0, decided in float32 with l rounded to float32 -- that rounded vector
+ *               is the ray's own direction (hf_spot_lighting's convention for its `front` test);
+ *   shadow ray  si.spawn_ray(l_k), hf_sky_rays' ray for the direction l_k: o = p + n s (1 + max|p_c|) 1500 2^-24 with
+ *               s = sign <n, l>, d = float32(l), maxt = inf;
+ *   vis[i]      one byte: bit k is set iff sample i was traced towards light k and the any-hit walk found nothing
+ *               (HF_MAX_LIGHTS = 8 fills the byte);
+ *   value[k][i] = weight_i albedo/pi irradiance_k <sh_n_i, l_k> where bit k is set and exactly 0 elsewhere, formed in
+ *               double and rounded once;
+ *   image[k][i / spp] = 1/spp * sum value[k][i]: hf_point_lighting's layout, K images of n / spp, overwritten; n a
+ *               multiple of spp.
+ * Differentiated with respect to sh_n, weight and, per light, to_light and irradiance: HF_DIRECTIONAL_PARAMS numbers per
+ * light in this order.  (directional.cpp:96 keeps the emitter's to_world non-differentiable; the direction's derivative
+ * goes beyond the reference.)  HELD: the visibility bits and every mask.  The value does not depend on p: p and nrm enter
+ * only the held shadow ray, so there is no grad_p and the derivative entries do not take them.  With L = |to_light|,
+ * S = <sh_n, l>, c = albedo / pi:
+ *   dl = (dv - l <l, dv>) / L,
+ *   d value = c [ dw E S + w dE S + w E (<d sh_n, l> + <sh_n, dl>) ].
+ * The gradient of to_light is orthogonal to l: scaling to_light by s leaves every output unchanged and divides that
+ * gradient by s.
+ * OUT OF SCOPE: sample_ray, RGB, and the silhouette part of a moving shadow (hf_reparam_*'s, as in every row).
+ * All entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional, n >= 2^32,
+ * spp == 0 or n % spp != 0, n_lights outside 1..HF_MAX_LIGHTS, a non-finite field of a light, |to_light| zero or
+ * non-finite, a non-finite albedo.  p, nrm, sh_n, d: 3 device rows of n floats; t: n.  Callers detect the entries by
+ * their symbols (HF_VERSION is unchanged). */
+#define HF_DIRECTIONAL_PARAMS 4          /* to_light[3], irradiance: the order of every parameter row */
+typedef struct hf_directional_light {    /* HOST memory, as hf_spot_light_t */
+    double to_light[3];                  /* towards the light; any finite length > 0; the host normalises it once, in double */
+    float irradiance;                    /* directional.cpp:82, 174 */
+} hf_directional_light_t;
+/* hf_directional_rays materialises the shadow ray of every sample towards ONE light (out_o, out_d: 3 rows of n floats;
+ * out_maxt: n floats, inf for a traced lane; a lane that is not traced gets a zero origin and direction and maxt = -1, a
+ * miss): bit k of hf_directional_lighting's vis equals hf_directional_rays(light k) + hf_ray_test bit for bit.  Takes no
+ * field handle. */
+int hf_directional_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                        const float *const d[3], const float *t, const hf_directional_light_t *light,
+                        float *const out_o[3], float *const out_d[3], float *out_maxt, hf_stream_t stream);
+/* The fused launch: reads a sample's record once and holds it across a wave-uniform loop over the lights; for each light
+ * it finishes the value, runs the per-lane any-hit walk where the sample is traced and reduces the film; image (K rows of
+ * n / spp), value (K rows of n) and vis (n bytes) may each be NULL (not wanted), not all of them; no ray and no hit byte
+ * goes to memory.  A batch of 64 samples with no lane traced towards light k skips that walk.  hf_set_ray_coherence is
+ * neither read nor changed.  weight: n floats or NULL (1).  Allocates nothing, never synchronises the host, capturable. */
+int hf_directional_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                            const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                            const float *t, const float *weight, uint32_t n_lights, const hf_directional_light_t *lights,
+                            float albedo, float *image, float *value, uint8_t *vis, hf_stream_t stream);
+/* the adjoint's workspace in floats for a rig of n_lights (0 for a count outside 1..HF_MAX_LIGHTS) */
+size_t hf_directional_workspace_floats(uint32_t n_lights);
+/* Reverse mode.  Traces nothing: vis (as hf_directional_lighting wrote it) is read.  With the upstream of light k
+ * g_k = grad_image[k][i / spp] / spp + grad_value[k][i] (either may be NULL = zero):
+ *   grad_sh_n = sum_k g_k w c E_k l_k,   grad_weight = sum_k g_k c E_k S_k
+ * (3 rows and 1 row) are OVERWRITTEN, one lane per sample, the K lights summed in light order in double and rounded once,
+ * exact zeros where vis = 0, no atomics;
+ *   grad_lights[k] = ( sum_i g w c E (sh_n - l S) / L ,  sum_i g w c S )
+ * ([K][HF_DIRECTIONAL_PARAMS] device floats) is ACCUMULATED into without atomics: every block stores the 4 partial sums of
+ * every light in double to `workspace` -- hf_directional_workspace_floats(n_lights) floats of device memory, 8-byte
+ * aligned, the caller's, this call's until it has completed; needed only when grad_lights is wanted -- and one more
+ * launch adds them in a fixed order (hf_spot_lighting_adjoint's pattern with rows of 4; family 2 of hf_grid_blocks):
+ * bitwise the same from launch to launch.  Every output may be NULL (not wanted).  Takes no field handle. */
+int hf_directional_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                    const float *t, const float *weight, uint32_t n_lights,
+                                    const hf_directional_light_t *lights, float albedo, const uint8_t *vis,
+                                    const float *grad_image, const float *grad_value, float *const grad_sh_n[3],
+                                    float *grad_weight, float *grad_lights, float *workspace, hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dsh_n (3 rows of n floats), dweight (n) and d_lights
+ * ([K][HF_DIRECTIONAL_PARAMS] device floats), each may be NULL (zero); dimage (K rows of n / spp) and / or dvalue (K rows
+ * of n) are overwritten (at least one).  No atomics for any spp (a power of two <= 64: the film's shuffle tree; otherwise
+ * one lane adds the samples of a pixel in order): bitwise the same from launch to launch.  Takes no field handle. */
+int hf_directional_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                    const float *t, const float *weight, uint32_t n_lights,
+                                    const hf_directional_light_t *lights, float albedo, const uint8_t *vis,
+                                    const float *const dsh_n[3], const float *dweight, const float *d_lights,
+                                    float *dimage, float *dvalue, hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional
@@ -1916,8 +2001,8 @@ int hf_invert_affine(const float in[12], float out[12]);
 /* blocks (of 256 threads) that a grid-stride launch of n items gets, HF_FORCE_GRID included.  family: 0 the flat cap
  * (adjoints, reparameterisation, Adam, area sampling, ...), 1 the cap of the streaming kernels (SI, hf_tangent, the
  * forward and tangent of attributes and of eval_parameterization, the sensor's rays, projection and their tangents), 2
- * the cap of the launches that sum dL/d(to_world), the sensor's adjoints, hf_projector_lighting_adjoint and hf_spot_lighting_adjoint among
- * them.
+ * the cap of the launches that sum dL/d(to_world), the sensor's adjoints, hf_projector_lighting_adjoint, hf_spot_lighting_adjoint and
+ * hf_directional_lighting_adjoint among them.
  * 0 for an unknown family.  Needs no device. */
 int hf_grid_blocks(size_t n, int family);
 const char *hf_last_error_string(void);

@@ -11,3 +11,4 @@ from .shape import (Adam, Bitmap, DirectionSample3f, Envmap, Frame3f, Heightfiel
 from .sensor import OrthographicCamera, PerspectiveCamera, ThinLensCamera  # noqa: F401
 from .projector import Projector, projector_lighting, projector_rays  # noqa: F401
 from .spot import SpotLight, spot_lighting, spot_rays  # noqa: F401
+from .directional import DirectionalLight, directional_lighting, directional_rays  # noqa: F401

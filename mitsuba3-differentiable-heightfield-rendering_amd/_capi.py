@@ -116,7 +116,27 @@ HF_SPOT_PARAMS = 15
 _spot_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32,
             C.POINTER(hf_spot_light_t), C.c_float, _fp]
 
+class hf_directional_light_t(C.Structure):
+    _fields_ = [("to_light", C.c_double * 3), ("irradiance", C.c_float)]
+
+
+HF_DIRECTIONAL_PARAMS = 4
+# n, spp, sh_n, d, t, weight, n_lights, lights, albedo, vis
+_directional_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32,
+                   C.POINTER(hf_directional_light_t), C.c_float, _fp]
+
 SYMBOLS = {
+    "hf_directional_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                      _fp, C.POINTER(hf_directional_light_t), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
+                                      C.c_void_p]),
+    "hf_directional_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                          C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32,
+                                          C.POINTER(hf_directional_light_t), C.c_float, _fp, _fp, _fp, C.c_void_p]),
+    "hf_directional_workspace_floats": (C.c_size_t, [C.c_uint32]),
+    # ..., grad_image, grad_value, grad_sh_n, grad_weight, grad_lights, workspace
+    "hf_directional_lighting_adjoint": (C.c_int, [*_directional_in, _fp, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp, C.c_void_p]),
+    # ..., dsh_n, dweight, d_lights, dimage, dvalue
+    "hf_directional_lighting_tangent": (C.c_int, [*_directional_in, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, C.c_void_p]),
     "hf_spot_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
                                C.POINTER(hf_spot_light_t), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_void_p]),
     "hf_spot_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),

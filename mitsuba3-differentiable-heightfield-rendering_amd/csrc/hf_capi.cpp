@@ -1889,6 +1889,111 @@ extern "C" int hf_spot_lighting_tangent(size_t n, uint32_t spp, const float *con
     return light_launch(hf_launch_spot, 2, a, stream);
 }
 
+// ---- directional lighting: a rig of 1..HF_MAX_LIGHTS distant emitters, the shadow rays traced in the kernel ----
+// What the four hf_directional_* entries share (hf_directional_rays passes spp 1, one light, albedo 1): the wavefront,
+// every light's checks and its unit direction, formed once, here, in double
+static int directional_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                            const float *t, const float *weight, uint32_t n_lights, const hf_directional_light_t *lights,
+                            float albedo, hf_directional_args &a) {
+    a = {};
+    if (!all3(sh_n) || !all3(d) || !t || !lights) return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
+    if (n_lights == 0 || n_lights > HF_MAX_LIGHTS)
+        return fail(HF_EINVAL, "%s: 1..%d lights supported (got %u)", who, HF_MAX_LIGHTS, n_lights);
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    for (uint32_t l = 0; l < n_lights; ++l) {
+        const hf_directional_light_t &s = lights[l];
+        hf_directional_light_dev &o = a.L[l];
+        const double *v = s.to_light;
+        if (!isfinite(v[0]) || !isfinite(v[1]) || !isfinite(v[2]) || !isfinite(s.irradiance))
+            return fail(HF_EINVAL, "%s: light %u: to_light and irradiance must be finite", who, l);
+        const double len = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        if (!(len > 0.0) || !isfinite(len) || !isfinite(1.0 / len))
+            return fail(HF_EINVAL, "%s: light %u: to_light must have a finite length > 0", who, l);
+        o.inv_len = 1.0 / len;
+        for (int k = 0; k < 3; ++k) { o.l[k] = v[k] / len; o.lf[k] = (float) o.l[k]; }
+        o.ce = (double) albedo / 3.141592653589793 * (double) s.irradiance;
+    }
+    for (int k = 0; k < 3; ++k) { a.sh_n[k] = sh_n[k]; a.d[k] = d[k]; }
+    a.n = n; a.spp = spp; a.n_lights = n_lights; a.t = t; a.weight = weight;
+    a.albedo_pi = (double) albedo / 3.141592653589793;
+    return HF_OK;
+}
+
+extern "C" int hf_directional_rays(size_t n, const float *const p[3], const float *const nrm[3], const float *const sh_n[3],
+                                   const float *const d[3], const float *t, const hf_directional_light_t *light,
+                                   float *const out_o[3], float *const out_d[3], float *out_maxt, hf_stream_t stream) {
+    const char *fn = "hf_directional_rays";
+    hf_directional_args a;
+    int rc = directional_args(fn, n, 1, sh_n, d, t, nullptr, 1, light, 1.f, a);
+    if (rc != HF_OK || (rc = light_rays_out(fn, p, nrm, out_o, out_d, out_maxt, a))) return rc;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_directional, 3, a, stream);
+}
+
+extern "C" int hf_directional_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const p[3],
+                                       const float *const nrm[3], const float *const sh_n[3], const float *const d[3],
+                                       const float *t, const float *weight, uint32_t n_lights,
+                                       const hf_directional_light_t *lights, float albedo, float *image, float *value,
+                                       uint8_t *vis, hf_stream_t stream) {
+    const char *fn = "hf_directional_lighting";
+    hf_directional_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = directional_args(fn, n, spp, sh_n, d, t, weight, n_lights, lights, albedo, a);
+    if (rc != HF_OK || (rc = light_forward_out(fn, p, nrm, image, a, true))) return rc;
+    if (!image && !value && !vis) return fail(HF_EINVAL, "%s: image, value and vis are all NULL", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.value = value; a.vis = vis;
+    return light_launch(hf_launch_directional, 0, a, stream);
+}
+
+extern "C" size_t hf_directional_workspace_floats(uint32_t n_lights) {
+    return n_lights >= 1 && n_lights <= HF_MAX_LIGHTS ? 2u * hf_directional_slab_doubles(n_lights) : 0u;
+}
+
+extern "C" int hf_directional_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                               const float *t, const float *weight, uint32_t n_lights,
+                                               const hf_directional_light_t *lights, float albedo, const uint8_t *vis,
+                                               const float *grad_image, const float *grad_value, float *const grad_sh_n[3],
+                                               float *grad_weight, float *grad_lights, float *workspace,
+                                               hf_stream_t stream) {
+    const char *fn = "hf_directional_lighting_adjoint";
+    hf_directional_args a;
+    int rc = directional_args(fn, n, spp, sh_n, d, t, weight, n_lights, lights, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
+    if (grad_lights && !workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_lights && ((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    a.vis = const_cast<uint8_t *>(vis);
+    a.gimg = grad_image; a.gvalue = grad_value; a.gw = grad_weight;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    a.slab = grad_lights ? (double *) workspace : nullptr;
+    a.g_lights = grad_lights;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_directional, 1, a, stream);
+}
+
+extern "C" int hf_directional_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                               const float *t, const float *weight, uint32_t n_lights,
+                                               const hf_directional_light_t *lights, float albedo, const uint8_t *vis,
+                                               const float *const dsh_n[3], const float *dweight, const float *d_lights,
+                                               float *dimage, float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_directional_lighting_tangent";
+    hf_directional_args a;
+    int rc = directional_args(fn, n, spp, sh_n, d, t, weight, n_lights, lights, albedo, a);
+    if (rc != HF_OK) return rc;
+    if (!vis) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
+    if ((rc = light_tangent_io(fn, false, dsh_n, dweight, dimage, a, true))) return rc;
+    a.vis = const_cast<uint8_t *>(vis); a.value = dvalue;
+    a.d_lights = d_lights;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_directional, 2, a, stream);
+}
+
 // ---- the sensor: the primary wavefront of a perspective or an orthographic camera ----
 static int log2_or_minus1(uint32_t v) {
     if (v == 0 || (v & (v - 1u))) return -1;

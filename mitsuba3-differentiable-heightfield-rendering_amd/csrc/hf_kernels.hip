@@ -8074,6 +8074,231 @@ void hf_launch_spot(int mode, const hf_spot_args &a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------
+// Directional lighting (include/hf.h hf_directional_*): diffuse surface under a RIG of 1..HF_MAX_LIGHTS
+// `directional` emitters (src/emitters/directional.cpp), distant lights of irradiance E_k from the unit direction l_k.
+// One draw per sample and light: the shadow ray si.spawn_ray(l_k) (the sky row's ray for that direction) traced (any hit,
+// per lane) and the film, for ALL lights in ONE launch: hf_spot_kernel's skeleton without the cone mapping,
+//   value_k = weight albedo / pi E_k <sh_n, l_k>.
+// The row's own text is that term, its derivatives (the direction's through l = v / |v|) and the reduction of the 4
+// numbers of every light; the masks, the origin, the walk, the film and the launch are the lighting rows' shared
+// functions, the reduction the sensor's (sensor_block_store, sensor_slab_sums).
+// ---------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) hf_directional_args *hf_directional_kargs;
+
+#ifndef HF_DIRECTIONAL_WAVES
+#define HF_DIRECTIONAL_WAVES 6 // resident waves per SIMD (the siblings')
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_DIRECTIONAL_WAVES) void hf_directional_kernel(hf_directional_args a) {
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    hf_directional_kargs ka = (hf_directional_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    // the sample's record: read once, held across the loop over the lights
+    const v3 sn = mk3(ka->sh_n[0][ii], ka->sh_n[1][ii], ka->sh_n[2][ii]);
+    bool elig;
+    {
+        const v3 d = mk3(ka->d[0][ii], ka->d[1][ii], ka->d[2][ii]);
+        elig = in && sky_eligible(ka->t[ii], sn, d);
+    }
+    const v3 p = mk3(ka->p[0][ii], ka->p[1][ii], ka->p[2][ii]);
+    const v3 gn = mk3(ka->nrm[0][ii], ka->nrm[1][ii], ka->nrm[2][ii]);
+    float wgt = 1.f;
+    {
+        const float *weight = ka->weight;
+        if (weight) wgt = weight[ii];
+    }
+    uint32_t bits = 0u; // bit k: the sample was traced towards light k and nothing is in the way
+#pragma unroll 1
+    for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+        asm volatile("" : "+s"(ka)); // opaque per light: the kernarg loads stay inside the loop
+        const v3 lf = mk3(ka->L[k].lf[0], ka->L[k].lf[1], ka->L[k].lf[2]);
+        const bool traced = elig && dot3(sn, lf) > 0.f;
+        // light k's value of a sample that turns out visible: finished and rounded before the ray is begun (the
+        // projector kernel's discipline), one float held across the walk
+        float val = 0.f;
+        {
+            v3 snd = sn; // (opaque: the conversions to double are otherwise hoisted out of the loop and held across the walk)
+            asm volatile("" : "+v"(snd.x), "+v"(snd.y), "+v"(snd.z));
+            if (traced) {
+                const hf_d3 l = hf_d3{ ka->L[k].l[0], ka->L[k].l[1], ka->L[k].l[2] };
+                val = (float) ((double) wgt * ka->L[k].ce * sky_dot_f64(snd, l));
+            }
+        }
+        asm volatile("" : "+v"(val));
+        hf_hit best;
+        best.hit = false;
+        if (__ballot(traced) != 0ull) // wave-uniform: a batch without a sample traced towards this light skips its walk
+            light_walk<true>(&ka->f, f, sky_origin(p, gn, sky_offset(p), lf), lf, traced, best);
+        // (the output pointers: loaded here, not before the walk)
+        hf_directional_kargs ko = (hf_directional_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ko));
+        const bool seen = traced && !best.hit; // (traced: in range)
+        if (!seen) val = 0.f;
+        if (seen) bits |= 1u << k;
+        float *value = ko->value;
+        if (in && value) value[(size_t) k * ko->n + i] = val;
+        float *image = ko->image;
+        if (image) { // the film of light k: hf_point_lighting's layout, K images of n / spp
+            const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+            film_pixel(image, val, k, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+        }
+        if (k + 1u >= ko->n_lights) break;
+    }
+    hf_directional_kargs ko = (hf_directional_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    uint8_t *vis = ko->vis;
+    if (in && vis) vis[i] = (uint8_t) bits;
+}
+
+// the shadow ray of every sample towards ONE light (L[0]), materialised: what hf_directional_kernel traces for it, bit
+// for bit (an untraced lane: a zero origin and direction, maxt = -1)
+__global__ __launch_bounds__(HF_BLOCK) void hf_directional_rays_kernel(hf_directional_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    v3 sn;
+    const bool elig = light_sample(a, i, sn);
+    const v3 p = mk3(a.p[0][i], a.p[1][i], a.p[2][i]), gn = mk3(a.nrm[0][i], a.nrm[1][i], a.nrm[2][i]);
+    const v3 lf = mk3(a.L[0].lf[0], a.L[0].lf[1], a.L[0].lf[2]);
+    light_store_spawned(a, i, p, gn, lf, elig && dot3(sn, lf) > 0.f);
+}
+
+// the upstream of light k's value of sample i: grad_image[k][i / spp] / spp + grad_value[k][i] (NULL: zero)
+__device__ __forceinline__ float directional_value_seed(const hf_directional_args &a, uint32_t k, size_t i) {
+    return (a.gimg ? a.gimg[(size_t) k * (a.n / a.spp) + i / a.spp] * (1.0f / (float) a.spp) : 0.f) +
+           (a.gvalue ? a.gvalue[(size_t) k * a.n + i] : 0.f);
+}
+
+// Reverse mode of hf_directional_kernel with respect to sh_n, weight and, per light, to_light and irradiance: nothing is
+// traced, the visibility byte is read.  First every sample's own gradients: one lane per sample, the lights of its byte
+// summed in light order in double and rounded once, overwritten, no atomics.  Then, where grad_lights is wanted, light by
+// light (block-uniform): the 4 numbers of the light kept per lane in double across the grid-stride loop over the samples
+// whose bit is set, and reduced as the sensor's 13.  With S = <sh_n, l> and L = |to_light|:
+//   d value = c [ dw E S + w dE S + w E (<dsh_n, l> + <sh_n, dl>) ],   dl = (dv - l <l, dv>) / L
+#define HF_DIRECTIONAL_SUMS 4
+__global__ __launch_bounds__(HF_BLOCK) void hf_directional_adjoint_kernel(hf_directional_args a) {
+    hf_directional_kargs ka = (hf_directional_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    if (a.gn[0] || a.gn[1] || a.gn[2] || a.gw) { // (launch-uniform)
+        for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+            const uint32_t bits = a.vis[i];
+            double gn[3] = { 0.0, 0.0, 0.0 }, gw = 0.0;
+            if (bits) {
+                const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]);
+                const double w = a.weight ? (double) a.weight[i] : 1.0;
+#pragma unroll 1
+                for (uint32_t k = 0; k < a.n_lights; ++k) {
+                    if (!((bits >> k) & 1u)) continue;
+                    const hf_d3 l = hf_d3{ ka->L[k].l[0], ka->L[k].l[1], ka->L[k].l[2] };
+                    const double gce = (double) directional_value_seed(a, k, i) * ka->L[k].ce;
+                    gw += gce * sky_dot_f64(sn, l);
+                    gn[0] += gce * w * l.x; gn[1] += gce * w * l.y; gn[2] += gce * w * l.z;
+                }
+            }
+            light_store_grads(a, i, mk3((float) gn[0], (float) gn[1], (float) gn[2]), (float) gw);
+        }
+    }
+    if (!a.slab) return; // (launch-uniform: grad_lights is not wanted)
+#pragma unroll 1
+    for (uint32_t k = 0; k < a.n_lights; ++k) { // block-uniform
+        double M[HF_DIRECTIONAL_SUMS];
+#pragma unroll
+        for (int j = 0; j < HF_DIRECTIONAL_SUMS; ++j) M[j] = 0.0;
+        const hf_d3 l = hf_d3{ ka->L[k].l[0], ka->L[k].l[1], ka->L[k].l[2] };
+        const double ce_l = ka->L[k].ce * ka->L[k].inv_len;
+        for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+            if (!((a.vis[i] >> k) & 1u)) continue;
+            const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]);
+            const double gw = (double) directional_value_seed(a, k, i) * (a.weight ? (double) a.weight[i] : 1.0);
+            const double S = sky_dot_f64(sn, l), gl = gw * ce_l;
+            M[0] += gl * ((double) sn.x - l.x * S); // sh_n's part orthogonal to l, over |to_light|
+            M[1] += gl * ((double) sn.y - l.y * S);
+            M[2] += gl * ((double) sn.z - l.z * S);
+            M[3] += gw * a.albedo_pi * S;
+        }
+        sensor_block_store<HF_DIRECTIONAL_SUMS>(M, a.slab + (size_t) k * gridDim.x * HF_DIRECTIONAL_SUMS);
+        __syncthreads(); // (the next light's sums go through the same LDS rows)
+    }
+}
+// block k: g_lights[k][j] += column j of light k's rows
+__global__ __launch_bounds__(HF_BLOCK) void hf_directional_sum_kernel(const double *__restrict__ slab, uint32_t rows,
+                                                                       float *__restrict__ g_lights) {
+    const double *const sum = sensor_slab_sums<HF_DIRECTIONAL_SUMS>(slab + (size_t) blockIdx.x * rows * HF_DIRECTIONAL_SUMS, rows);
+    const uint32_t t = threadIdx.x;
+    if (t < (uint32_t) HF_DIRECTIONAL_SUMS) g_lights[blockIdx.x * HF_DIRECTIONAL_SUMS + t] += (float) sum[t];
+}
+size_t hf_directional_slab_doubles(uint32_t n_lights) { return (size_t) HF_XFORM_GRID_CAP * HF_DIRECTIONAL_SUMS * n_lights; }
+
+// forward mode, the transpose of the above: the tangent of light k's value of sample i for tangents dn of sh_n, dw of
+// weight and row k of d_lights (NULL: zero)
+template <class LP>
+__device__ __forceinline__ float directional_tangent_value(const hf_directional_args &a, LP L, uint32_t k, size_t i) {
+    if (!((a.vis[i] >> k) & 1u)) return 0.f;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]);
+    const v3 dn = a.dn[0] ? mk3(a.dn[0][i], a.dn[1][i], a.dn[2][i]) : mk3(0.f, 0.f, 0.f);
+    const hf_d3 l = hf_d3{ L->l[0], L->l[1], L->l[2] };
+    const double S = sky_dot_f64(sn, l), w = a.weight ? (double) a.weight[i] : 1.0;
+    double dS = sky_dot_f64(dn, l), dE = 0.0;
+    if (a.d_lights) {
+        const float *dl = a.d_lights + k * HF_DIRECTIONAL_SUMS;
+        const double dv[3] = { (double) dl[0], (double) dl[1], (double) dl[2] };
+        const double ldv = l.x * dv[0] + l.y * dv[1] + l.z * dv[2];
+        const hf_d3 dlk = hf_d3{ (dv[0] - l.x * ldv) * L->inv_len, (dv[1] - l.y * ldv) * L->inv_len, (dv[2] - l.z * ldv) * L->inv_len };
+        dS += sky_dot_f64(sn, dlk);
+        dE = (double) dl[3];
+    }
+    const double dw = a.dw ? (double) a.dw[i] : 0.0;
+    return (float) ((dw * L->ce + w * (dE * a.albedo_pi)) * S + (w * L->ce) * dS);
+}
+// light_tangent_image with a loop over the lights: PIXEL = false: one lane per sample and the primal's film (spp a power
+// of two <= 64, or no image wanted); PIXEL = true: one lane per pixel adds its samples in order -- no atomics either way
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_directional_tangent_kernel(hf_directional_args a) {
+    hf_directional_kargs ka = (hf_directional_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    const size_t npix = a.n / spp;
+    if (PIXEL) {
+        if (i >= npix) return;
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.n_lights; ++k) {
+            float c = 0.f;
+            for (uint32_t s = 0; s < spp; ++s) {
+                const float dv = directional_tangent_value(a, &ka->L[k], k, i * spp + s);
+                if (a.value) a.value[(size_t) k * a.n + i * spp + s] = dv;
+                c += dv;
+            }
+            a.image[(size_t) k * npix + i] = c * (1.0f / (float) spp);
+        }
+    } else {
+        const bool in = i < a.n;
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.n_lights; ++k) { // wave-uniform
+            const float c = directional_tangent_value(a, &ka->L[k], k, in ? i : a.n - 1);
+            if (in && a.value) a.value[(size_t) k * a.n + i] = c;
+            if (a.image) film_pixel(a.image, in ? c : 0.f, k, npix, i, spp, in, true, spp, 1.0f / (float) spp);
+        }
+    }
+}
+
+// mode 0: forward, 1: adjoint (and, where grad_lights is wanted, the sum of the blocks' rows, one block per light),
+// 2: tangent, 3: rays
+void hf_launch_directional(int mode, const hf_directional_args &a, hipStream_t stream) {
+    if (mode == 1) {
+        if (a.n == 0) return;
+        const int grid = grid_for(a.n, HF_XFORM_GRID_CAP); // the slab holds HF_XFORM_GRID_CAP rows per light
+        hipLaunchKernelGGL(hf_directional_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        if (a.slab)
+            hipLaunchKernelGGL(hf_directional_sum_kernel, dim3(a.n_lights), dim3(HF_BLOCK), 0, stream, a.slab, (uint32_t) grid,
+                               a.g_lights);
+        return;
+    }
+    launch_light(mode, a, a.n_lights, stream, hf_directional_kernel, hf_directional_adjoint_kernel,
+                 hf_directional_tangent_kernel<false>, hf_directional_tangent_kernel<true>, hf_directional_rays_kernel);
+}
+
+// ---------------------------------------------------------------------------------
 // Large-steps preconditioning (include/hf.h): A = I + lambda L on the W x H vertex grid, L the combinatorial
 // Laplacian of the tessellation (every cell split along v10-v01), and conjugate gradients for A v = u.
 //

@@ -369,6 +369,36 @@ struct hf_spot_args {
 // hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
 void hf_launch_spot(int mode, const hf_spot_args &a, hipStream_t stream);
 size_t hf_spot_slab_doubles(uint32_t n_lights);
+// ---- directional lighting (hf_directional_rays, hf_directional_lighting / _adjoint / _tangent): a rig of up
+// to HF_MAX_LIGHTS distant emitters in one launch.  One light of the rig, every constant formed on the host in double ----
+struct hf_directional_light_dev {
+    double l[3];                             // to_light / |to_light|
+    double inv_len;                          // 1 / |to_light|
+    double ce;                               // albedo / pi * irradiance
+    float lf[3], pad;                        // l rounded to float32: the shadow ray's direction, and what decides `traced`
+};
+struct hf_directional_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, n_lights;
+    double albedo_pi;                        // albedo / pi: d value / d irradiance
+    hf_directional_light_dev L[HF_MAX_LIGHTS]; // the first n_lights are read
+    const float *p[3], *nrm[3];              // si.p, si.n (forward, rays: the held shadow ray)
+    const float *sh_n[3], *d[3], *t, *weight;
+    float *image, *value;                    // forward: written, K rows each (NULL: not wanted); tangent: dimage, dvalue
+    uint8_t *vis;                            // forward: written (NULL: not wanted); adjoint, tangent: read; bit k: light k
+    float *out_o[3], *out_d[3], *out_maxt;   // rays (of light 0)
+    const float *gimg, *gvalue;              // adjoint inputs, K rows each (NULL: zero)
+    float *gn[3], *gw;                       // adjoint outputs (NULL: not wanted)
+    double *slab;                            // adjoint: per light, 4 doubles per block (NULL: grad_lights is not wanted)
+    float *g_lights;                         // adjoint output [K][4], accumulated
+    const float *dn[3], *dw;                 // tangent inputs (NULL: zero)
+    const float *d_lights;                   // tangent input [K][4] device floats (NULL: zero)
+};
+// mode 0: forward, 1: adjoint (two launches where grad_lights is wanted), 2: tangent, 3: rays.  The forward launch is
+// hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
+void hf_launch_directional(int mode, const hf_directional_args &a, hipStream_t stream);
+size_t hf_directional_slab_doubles(uint32_t n_lights);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
