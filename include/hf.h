@@ -1663,6 +1663,64 @@ int hf_directional_lighting_tangent(size_t n, uint32_t spp, const float *const s
                                     const float *const dsh_n[3], const float *dweight, const float *d_lights,
                                     float *dimage, float *dvalue, hf_stream_t stream);
 
+/* ---- the normal map: the shading normal perturbed by an RGB texture, fused and differentiable ----
+ *
+ * The reference's `normalmap` (src/bsdfs/normalmap.cpp:188-196) as a map of the ONE thing every lighting row consumes
+ * of the surface, the shading normal: a per-texel normal field, finer than the height grid and independent of it -- the
+ * unknown of photometric stereo.  The result is a new sh_n; every lighting row takes it as it takes any other.
+ * Per sample i:
+ *   inputs      uv (2 rows), b = sh_n (3 rows), dp_du (3 rows) of n floats, active (n bytes; NULL: every lane);
+ *   texture     tex[3][TH][TW], float32, PLANAR, the caller's device buffer: plane k is exactly a hf_bitmap_eval texture;
+ *               wrap = HF_WRAP_CLAMP or HF_WRAP_REPEAT;
+ *   lookup      pos = (float32(u TW), float32(v TH)), each product rounded once; c_k = hf_bitmap_eval of plane k at pos,
+ *               bit for bit (bitmap.cpp:497-520), k = 0, 1, 2;
+ *   normal      mt = 2 c - 1, m = mt / |mt| (normalmap.cpp:189-192), in double from the three float32 lookups;
+ *   base frame  a = dp_du - b <b, dp_du>, s0 = a / |a|, t0 = b x s0 (interaction.h:257-267), in double;
+ *   result      N = s0 m_x + t0 m_y + b m_z, formed in double and rounded once per component; NOT renormalised: unit to
+ *               rounding when b is.
+ * A lane is PERTURBED when it is active, uv, b and dp_du are finite, the lookup reads something (under HF_WRAP_REPEAT a
+ * coordinate beyond 2^23 texels reads nothing), |mt|^2 >= 1e-12, |dp_du|^2 > 0 and |a|^2 >= 1e-12 |dp_du|^2.  Every other
+ * lane PASSES THROUGH: N = b bit for bit, its derivative is the identity on sh_n and zero for everything else.  The
+ * reference's fall-back to coordinate_system(n) at dp_du = 0 is deliberately not taken: a lane without a
+ * parameterisation has no tangent space to perturb in.  mask (n bytes, optional): 1 where perturbed, 0 elsewhere.
+ * DEVIATION: the reference rebuilds frame.s from the world-space dp_du and the LOCAL perturbed normal, mixing spaces;
+ * here everything is in world space and only N is returned, the one member of the frame a row reads.  s and t are the
+ * host's business (NormalMap.perturb rebuilds them from dp_du and N) and carry no gradient, as hf_si_grad_t has none
+ * for them.
+ * Differentiated with respect to tex, uv (through the slopes Lx, Ly of each plane), sh_n and dp_du.  HELD: the cell, the
+ * perturbed / pass-through decision, the masks.  With A = |a|, M = |mt|, dpos = (TW du, TH dv) and b_j the four bilinear
+ * weights of the cell:
+ *   dc_k = sum_j b_j dtex_k,j + Lx_k dpos_x + Ly_k dpos_y,
+ *   dmt  = 2 dc,   dm = (dmt - m <m, dmt>) / M,
+ *   da   = ddp_du - db <b, dp_du> - b (<db, dp_du> + <b, ddp_du>),
+ *   ds0  = (da - s0 <s0, da>) / A,   dt0 = db x s0 + b x ds0,
+ *   dN   = ds0 m_x + dt0 m_y + db m_z + s0 dm_x + t0 dm_y + b dm_z.
+ * The adjoint is the exact transpose.
+ * OUT OF SCOPE: `bumpmap`; the BSDF-side test cos_theta(wo) cos_theta(perturbed_wo) > 0 (normalmap.cpp:148: the rows
+ * decide on <sh_n, l> as before); nearest filtering; a gradient for s or t; the mirror wrap.
+ * All three entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional,
+ * n >= 2^32, TW == 0 or TH == 0, TW TH >= 2^31, a wrap that is neither constant.  n == 0 is legal and launches nothing.
+ * They take no field handle, allocate nothing, never synchronise the host and are capturable; one launch each, one lane
+ * per sample.  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+int hf_normalmap_eval(size_t n, const float *const uv[2], const float *const sh_n[3], const float *const dp_du[3],
+                      const uint8_t *active, uint32_t TW, uint32_t TH, const float *tex, int wrap, float *const out_n[3],
+                      uint8_t *mask, hf_stream_t stream);
+/* Forward mode: dtex ([3][TH][TW], planar), duv (2 rows), dsh_n, ddp_du (3 rows each) may each be NULL (zero); dout_n
+ * (3 rows) is overwritten.  Bitwise the same from launch to launch. */
+int hf_normalmap_eval_tangent(size_t n, const float *const uv[2], const float *const sh_n[3], const float *const dp_du[3],
+                              const uint8_t *active, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                              const float *dtex, const float *const duv[2], const float *const dsh_n[3],
+                              const float *const ddp_du[3], float *const dout_n[3], hf_stream_t stream);
+/* Reverse mode: grad_out (3 rows) is dL/dN.  grad_tex ([3][TH][TW]) is ACCUMULATED into with float atomics, the four
+ * products of hf_bitmap_eval_adjoint per plane -- at most twelve per perturbed sample: consecutive lanes of a wave that
+ * share a cell add theirs up first -- in a free order: repeatable to rounding; grad_uv (2 rows), grad_sh_n and
+ * grad_dp_du (3 rows each) are OVERWRITTEN, with exact zeros where nothing flows.  Each output may be NULL (not wanted),
+ * not all of them. */
+int hf_normalmap_eval_adjoint(size_t n, const float *const uv[2], const float *const sh_n[3], const float *const dp_du[3],
+                              const uint8_t *active, uint32_t TW, uint32_t TH, const float *tex, int wrap,
+                              const float *const grad_out[3], float *grad_tex, float *const grad_uv[2],
+                              float *const grad_sh_n[3], float *const grad_dp_du[3], hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional

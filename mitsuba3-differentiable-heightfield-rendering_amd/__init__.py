@@ -12,3 +12,4 @@ from .sensor import OrthographicCamera, PerspectiveCamera, ThinLensCamera  # noq
 from .projector import Projector, projector_lighting, projector_rays  # noqa: F401
 from .spot import SpotLight, spot_lighting, spot_rays  # noqa: F401
 from .directional import DirectionalLight, directional_lighting, directional_rays  # noqa: F401
+from .normalmap import NormalMap  # noqa: F401

@@ -125,7 +125,18 @@ HF_DIRECTIONAL_PARAMS = 4
 _directional_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32,
                    C.POINTER(hf_directional_light_t), C.c_float, _fp]
 
+# n, uv, sh_n, dp_du, active, TW, TH, tex, wrap
+_normalmap_in = [C.c_size_t, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, *_bitmap_in]
+
 SYMBOLS = {
+    # ..., out_n, mask
+    "hf_normalmap_eval": (C.c_int, [*_normalmap_in, C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    # ..., dtex, duv, dsh_n, ddp_du, dout_n
+    "hf_normalmap_eval_tangent": (C.c_int, [*_normalmap_in, _fp, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                            C.POINTER(_fp * 3), C.c_void_p]),
+    # ..., grad_out, grad_tex, grad_uv, grad_sh_n, grad_dp_du
+    "hf_normalmap_eval_adjoint": (C.c_int, [*_normalmap_in, C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 2), C.POINTER(_fp * 3),
+                                            C.POINTER(_fp * 3), C.c_void_p]),
     "hf_directional_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
                                       _fp, C.POINTER(hf_directional_light_t), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
                                       C.c_void_p]),

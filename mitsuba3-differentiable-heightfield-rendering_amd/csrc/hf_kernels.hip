@@ -8684,3 +8684,250 @@ void hf_launch_large_steps_solve(uint32_t W, uint32_t H, double lambda, const fl
     hipLaunchKernelGGL(hf_large_steps_sum_kernel, grid, block, 0, stream, a);
     hipLaunchKernelGGL(hf_large_steps_finish_kernel, grid, block, 0, stream, a);
 }
+
+// ---------------------------------------------------------------------------------
+// The normal map (include/hf.h hf_normalmap_*): the reference's `normalmap` (normalmap.cpp:188-196) as a
+// map of the shading normal alone.  One lane per sample, the record read once: the three planes of the texture are
+// looked up at pos = (u TW, v TH) by the refraction view's bitmap_cell (twelve texel loads, the plane an offset), the
+// tangent-space normal m = (2 c - 1) / |2 c - 1| and the base frame s0 = normalize(dp_du - b <b, dp_du>), t0 = b x s0
+// are formed in double and N = s0 m_x + t0 m_y + b m_z is rounded once per component.  A lane that is not perturbed
+// (inactive, a record that is not finite, no lookup, a degenerate m or frame) passes b through bit for bit.  The
+// tangent and the adjoint rebuild the same lane state (normalmap_lane) and differ only in what they do with it; the
+// adjoint's texel scatter is hf_bitmap_cell::scatter's products, the lanes of a wave that share a cell added up before
+// the atomic (normalmap_scatter): at most twelve float atomics per perturbed sample.
+// ---------------------------------------------------------------------------------
+#ifndef HF_NORMALMAP_WAVES
+#define HF_NORMALMAP_WAVES 8 // resident waves per SIMD of the forward kernel: it streams and walks nothing
+#endif
+#ifndef HF_NORMALMAP_AD_WAVES
+#define HF_NORMALMAP_AD_WAVES 6 // the tangent and the adjoint hold the frame and its derivative in double: 10 VGPRs spilled at 8
+#endif
+// what the three kernels know of a perturbed lane: the cell, the base normal b and dp_du (u), the frame, m and the
+// numbers the derivatives divide by (rA = 1 / |a|, rM = 1 / |2 c - 1|, bu = <b, dp_du>)
+struct hf_normalmap_lane {
+    hf_bitmap_cell e;
+    float bf[3];
+    double b[3], u[3], s0[3], t0[3], m[3];
+    double bu, rA, rM;
+};
+__device__ __forceinline__ bool nm_finite(float x) { return __builtin_fabsf(x) <= 3.402823466e38f; }
+__device__ __forceinline__ double nm_dot(const double *x, const double *y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
+__device__ __forceinline__ void nm_cross(const double *x, const double *y, double *o) {
+    o[0] = x[1] * y[2] - x[2] * y[1];
+    o[1] = x[2] * y[0] - x[0] * y[2];
+    o[2] = x[0] * y[1] - x[1] * y[0];
+}
+// the lane's state; false: a pass-through lane (s.bf alone is then defined)
+__device__ __forceinline__ bool normalmap_lane(const hf_normalmap_args &a, size_t i, hf_normalmap_lane &s) {
+    float uf[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s.bf[c] = a.sh_n[c][i]; uf[c] = a.dp_du[c][i]; }
+    const float u = a.uv[0][i], v = a.uv[1][i];
+    if (!(a.active ? a.active[i] != 0 : true)) return false;
+    if (!(nm_finite(u) && nm_finite(v) && nm_finite(s.bf[0]) && nm_finite(s.bf[1]) && nm_finite(s.bf[2]) && nm_finite(uf[0]) &&
+          nm_finite(uf[1]) && nm_finite(uf[2])))
+        return false;
+    // one rounding each: no contraction into bitmap_axis' pos - 0.5 can move the cell
+    s.e = bitmap_cell(&a, __fmul_rn(u, (float) a.TW), __fmul_rn(v, (float) a.TH));
+    if (!s.e.ok) return false;
+    const size_t plane = (size_t) a.TW * a.TH;
+    double mt[3], av[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        mt[k] = 2.0 * (double) s.e.value(a.tex + (size_t) k * plane) - 1.0;
+        s.b[k] = (double) s.bf[k];
+        s.u[k] = (double) uf[k];
+    }
+    s.bu = nm_dot(s.b, s.u);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) av[c] = s.u[c] - s.b[c] * s.bu;
+    const double M2 = nm_dot(mt, mt), A2 = nm_dot(av, av), U2 = nm_dot(s.u, s.u);
+    if (!(M2 >= 1e-12) || !(U2 > 0.0) || !(A2 >= 1e-12 * U2)) return false;
+    s.rM = 1.0 / sqrt(M2);
+    s.rA = 1.0 / sqrt(A2);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s.m[c] = mt[c] * s.rM; s.s0[c] = av[c] * s.rA; }
+    nm_cross(s.b, s.s0, s.t0);
+    return true;
+}
+
+__global__ __launch_bounds__(HF_BLOCK, HF_NORMALMAP_WAVES) void hf_normalmap_kernel(hf_normalmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    hf_normalmap_lane s;
+    const bool pert = normalmap_lane(a, i, s);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        a.out_n[c][i] = pert ? (float) (s.s0[c] * s.m[0] + s.t0[c] * s.m[1] + s.b[c] * s.m[2]) : s.bf[c];
+    if (a.mask) a.mask[i] = pert ? 1 : 0;
+}
+
+// dN of the tangents dtex, duv, dsh_n, ddp_du (each NULL: zero) with the cell and the decision held; a pass-through
+// lane: dN = dsh_n
+__global__ __launch_bounds__(HF_BLOCK, HF_NORMALMAP_AD_WAVES) void hf_normalmap_tangent_kernel(hf_normalmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    hf_normalmap_lane s;
+    const bool pert = normalmap_lane(a, i, s);
+    float dbf[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dbf[c] = a.dn[c] ? a.dn[c][i] : 0.f;
+    if (!pert) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.out_n[c][i] = dbf[c];
+        return;
+    }
+    const size_t plane = (size_t) a.TW * a.TH;
+    const double dpx = a.duv[0] ? (double) a.TW * (double) a.duv[0][i] : 0.0;
+    const double dpy = a.duv[1] ? (double) a.TH * (double) a.duv[1][i] : 0.0;
+    double db[3], du[3], dmt[3], dm[3], da[3], ds0[3], dt0[3], x0[3], x1[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        double dc = a.dtex ? (double) s.e.value(a.dtex + (size_t) k * plane) : 0.0;
+        if (a.duv[0]) {
+            float Lx, Ly;
+            s.e.slopes(a.tex + (size_t) k * plane, Lx, Ly);
+            dc += (double) Lx * dpx + (double) Ly * dpy;
+        }
+        dmt[k] = 2.0 * dc;
+        db[k] = (double) dbf[k];
+        du[k] = a.dp[k] ? (double) a.dp[k][i] : 0.0;
+    }
+    const double mdm = nm_dot(s.m, dmt), dbu = nm_dot(db, s.u) + nm_dot(s.b, du);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        dm[c] = (dmt[c] - s.m[c] * mdm) * s.rM;
+        da[c] = du[c] - db[c] * s.bu - s.b[c] * dbu;
+    }
+    const double sda = nm_dot(s.s0, da);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ds0[c] = (da[c] - s.s0[c] * sda) * s.rA;
+    nm_cross(db, s.s0, x0);
+    nm_cross(s.b, ds0, x1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        dt0[c] = x0[c] + x1[c];
+        a.out_n[c][i] = (float) (ds0[c] * s.m[0] + dt0[c] * s.m[1] + db[c] * s.m[2] + s.s0[c] * dm[0] + s.t0[c] * dm[1] +
+                                 s.b[c] * dm[2]);
+    }
+}
+
+// The adjoint's texel scatter: gtex[k][j] += q_k b_j for the three planes, hf_bitmap_cell::scatter's products.  On a
+// coherent wavefront neighbouring lanes share a cell (the samples of a pixel, the pixels of a texel), and float atomics
+// are the part of the adjoint that dominates (2.7 of 3.0 ms), so the lanes of a RUN -- consecutive perturbed
+// lanes of the wave with the same cell -- add their products up in a shuffle tree first and the run's first lane issues
+// the twelve atomics.  Lanes that share a cell without standing next to each other stay separate adds: the result is the
+// same sum.  HF_NORMALMAP_MERGE = 0 builds the plain form, hf_bitmap_cell::scatter per lane and plane (profiles/normalmap).
+#ifndef HF_NORMALMAP_MERGE
+#define HF_NORMALMAP_MERGE 1
+#endif
+// every lane of the wave calls this (a lane past the end or a pass-through lane with pert = false: it adds nothing)
+__device__ __forceinline__ void normalmap_scatter(const hf_normalmap_args &a, const hf_bitmap_cell &e, bool pert, const float *q) {
+    const size_t plane = (size_t) a.TW * a.TH;
+#if HF_NORMALMAP_MERGE
+    const unsigned lane = __lane_id();
+    // a cell is named by its first and last texel (both below 2^31)
+    const unsigned long long key = pert ? ((unsigned long long) e.j[0] | ((unsigned long long) e.j[3] << 32)) : ~0ull;
+    const unsigned long long before = __shfl_up(key, 1);
+    const bool head = !pert || lane == 0 || before != key;
+    const unsigned long long heads = __ballot(head);
+    const float gx = 1.f - e.fx, gy = 1.f - e.fy;
+    const float w[4] = { gy * gx, gy * e.fx, e.fy * gx, e.fy * e.fx };
+#pragma unroll 1
+    for (int k = 0; k < 3; ++k) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = pert ? q[k] * w[j] : 0.f;
+        // after the step d a lane holds the sum of its run over [lane, lane + 2 d)
+        for (unsigned d = 1; d < 64u; d <<= 1) {
+            const bool join = lane + d < 64u && (((heads >> 1) >> lane) & ((1ull << d) - 1ull)) == 0ull;
+            if (__ballot(join) == 0ull) break; // wave-uniform: no run is longer than d
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float o = __shfl_down(v[j], d);
+                if (join) v[j] += o;
+            }
+        }
+        if (pert && head) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) atomicAdd(a.gtex + (size_t) k * plane + e.j[j], v[j]);
+        }
+    }
+#else
+    if (pert) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e.scatter(a.gtex + (size_t) k * plane, q[k]);
+    }
+#endif
+}
+
+// the transpose: grad_uv, grad_sh_n, grad_dp_du overwritten (exact zeros where nothing flows; a pass-through lane hands
+// grad_out to grad_sh_n), grad_tex accumulated into with float atomics (normalmap_scatter).  No lane leaves before the
+// scatter: a lane past the end reads the last sample and stores nothing
+__global__ __launch_bounds__(HF_BLOCK, HF_NORMALMAP_AD_WAVES) void hf_normalmap_adjoint_kernel(hf_normalmap_args a) {
+    const size_t i0 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i0 < a.n;
+    const size_t i = in ? i0 : a.n - 1;
+    hf_normalmap_lane s;
+    const bool pert = normalmap_lane(a, i, s) && in;
+    float gf[3], q[3] = { 0.f, 0.f, 0.f };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) gf[c] = a.gout[c][i];
+    if (!pert) {
+        if (in) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (a.gn[0]) a.gn[c][i] = gf[c];
+                if (a.gp[0]) a.gp[c][i] = 0.f;
+            }
+            if (a.guv[0]) { a.guv[0][i] = 0.f; a.guv[1][i] = 0.f; }
+        }
+    } else {
+        const size_t plane = (size_t) a.TW * a.TH;
+        double g[3], gs0[3], gt0[3], gb[3], gm[3], ga[3], x0[3], x1[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            g[c] = (double) gf[c];
+            gs0[c] = g[c] * s.m[0]; gt0[c] = g[c] * s.m[1]; gb[c] = g[c] * s.m[2];
+        }
+        gm[0] = nm_dot(s.s0, g); gm[1] = nm_dot(s.t0, g); gm[2] = nm_dot(s.b, g);
+        // t0 = b x s0
+        nm_cross(s.s0, gt0, x0);
+        nm_cross(gt0, s.b, x1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { gb[c] += x0[c]; gs0[c] += x1[c]; }
+        // s0 = a / |a|, a = u - b <b, u>
+        const double sg = nm_dot(s.s0, gs0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ga[c] = (gs0[c] - s.s0[c] * sg) * s.rA;
+        const double gab = nm_dot(ga, s.b);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (a.gn[0]) a.gn[c][i] = (float) (gb[c] - s.bu * ga[c] - s.u[c] * gab);
+            if (a.gp[0]) a.gp[c][i] = (float) (ga[c] - s.b[c] * gab);
+        }
+        // m = mt / |mt|, mt = 2 c - 1
+        const double mg = nm_dot(s.m, gm);
+        double gx = 0.0, gy = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double gc = 2.0 * (gm[k] - s.m[k] * mg) * s.rM;
+            if (a.guv[0]) {
+                float Lx, Ly;
+                s.e.slopes(a.tex + (size_t) k * plane, Lx, Ly);
+                gx += gc * (double) Lx; gy += gc * (double) Ly;
+            }
+            q[k] = (float) gc;
+        }
+        if (a.guv[0]) { a.guv[0][i] = (float) ((double) a.TW * gx); a.guv[1][i] = (float) ((double) a.TH * gy); }
+    }
+    if (a.gtex) normalmap_scatter(a, s.e, pert, q);
+}
+
+// mode 0: forward, 1: adjoint, 2: tangent
+void hf_launch_normalmap(int mode, const hf_normalmap_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    hipLaunchKernelGGL(mode == 0 ? hf_normalmap_kernel : mode == 1 ? hf_normalmap_adjoint_kernel : hf_normalmap_tangent_kernel,
+                       grid, block, 0, stream, a);
+}

@@ -276,6 +276,7 @@ class SurfaceInteraction3f:
         self.instance = None
         self.time = 0.0
         self.wavelengths = None
+        self.ray_flags = None        # the RayFlags the record was computed with (None: not known)
 
     def is_valid(self):
         return self.t != math.inf
@@ -1148,6 +1149,7 @@ class Heightfield:
         si.prim_index = pi_prim                       # interaction.h:486
         si.shape = self
         si.time, si.wavelengths = ray.time, ray.wavelengths
+        si.ray_flags = int(ray_flags)
         return si
 
     def compute_surface_interaction(self, ray, pi, ray_flags=RayFlags.All, recursion_depth=0, active=True):
