@@ -1721,6 +1721,81 @@ int hf_normalmap_eval_adjoint(size_t n, const float *const uv[2], const float *c
                               const float *const grad_out[3], float *grad_tex, float *const grad_uv[2],
                               float *const grad_sh_n[3], float *const grad_dp_du[3], hf_stream_t stream);
 
+/* ---- next row: specular highlights, a GGX lobe under the directional rig, nothing traced ----
+ *
+ * The reflection lobe of a rough dielectric or conductor surface (roughplastic.cpp:315-350, roughconductor.cpp's eval:
+ * F D G / (4 cos theta_i), MicrofacetDistribution::eval and smith_g1 of microfacet.h:185-207, 341-365) under the rig of
+ * hf_directional_lighting, for ALL K lights in ONE launch that reads a sample's record once.  The row traces nothing:
+ * bit k of hf_directional_lighting's vis ("eligible, <sh_n, l_k> > 0, traced, unoccluded") is the mask of light k, read
+ * as the directional adjoint and tangent read it.  A diffuse + specular image is hf_directional_lighting and this row:
+ * one shadow walk per light, not two.  No other entry changes.
+ *   lights      n_lights hf_directional_light_t, HOST memory, exactly as hf_directional_lighting takes them; the host
+ *               forms l_k = to_light / |to_light| once, in double;
+ *   alpha       n floats, the GGX roughness of every sample, as hf_glossy_lighting's; a = max(alpha, 1e-4);
+ *   eta         the relative index of the interface (HOST float); 0 is the ideal mirror F = 1, as in the reflect and the
+ *               glossy row;
+ *   vis         n bytes as hf_directional_lighting wrote them (a foreign byte is legal: see below);
+ *   wi = -d,  h = (wi + l) / |wi + l|,  c_i = <sh_n, wi>,  c_o = <sh_n, l>,  c_h = <sh_n, h>   (all in double from the
+ *               float32 rows and the double l);
+ *   value[k][i] = weight E_k F(<wi, h>, eta) D(c_h, a) G1(c_i, a) G1(c_o, a) / (4 c_i)
+ *               where bit k of vis[i] is set, c_i > 0, c_o > 0 and alpha is finite, and exactly 0 everywhere else -- a
+ *               lane whose bit was set by a foreign byte but whose cosines are not positive included;
+ *               D = 1 / (pi a^2 (s^2 / a^2 + c_h^2)^2),  s^2 = max(1 - c_h^2, 0)   (microfacet.h:185-207, isotropic GGX);
+ *   arithmetic  D and the product are formed in double and rounded once (D cancels at small a near c_h = 1).  F is the
+ *               float32 Fresnel term of the reflect and glossy rows at the float32 cosine <wi, float32(h)>, G1 the
+ *               float32 smith_g1 of the glossy row at float32(c_i) and float32(c_o): the same device functions;
+ *   no further masks: on every lane that passes, c_h = (c_i + c_o) / |wi + l| > 0 and <wi, h> = |wi + l| / 2 > 0, so
+ *               the conditions of microfacet.h:206 (D only where <n, h> > 0) and :362 (G1 only where <v, h> <v, n> > 0)
+ *               hold identically; they are NOT tested, so that no rounding decides a mask;
+ *   image[k][i / spp] = 1/spp * sum value[k][i]: hf_point_lighting's layout, K images of n / spp, overwritten.
+ * image (K rows of n / spp) and value (K rows of n) may each be NULL (not wanted), not both.  There is no field handle,
+ * no p, no nrm, no t and no visibility output.
+ * Differentiated with respect to sh_n, weight, alpha (per sample; zero where the clamp a = 1e-4 is active) and, per
+ * light, to_light and irradiance: HF_DIRECTIONAL_PARAMS numbers per light in that order.  HELD: vis and every mask.
+ * With v = F R, R = D G1(c_i) G1(c_o) / (4 c_i), u = <wi, h>, M = |wi + l|, L = |to_light|:
+ *   dv/dsh_n = v [ (dlnD/dc_h) h + (dlnG1(c_i)/dc - 1/c_i) wi + (dlnG1(c_o)/dc) l ],
+ *   dv/da    = v [ dlnD/da + dlnG1(c_i)/da + dlnG1(c_o)/da ],
+ *   dv/dl    = v (dlnG1(c_o)/dc) sh_n + [ v (dlnD/dc_h) (sh_n - h c_h) + R (dF/du) (wi - h u) ] / M   (dh/dl included),
+ *   dl       = (dv - l <l, dv>) / L,
+ *   d value  = dw E v + w dE v + w E ( <dv/dsh_n, dsh_n> + dv/da da + <dv/dl, dl> ).
+ * The gradient of to_light is orthogonal to l: scaling to_light by s leaves every output unchanged and divides that
+ * gradient by s.  G1 and its derivatives are float32: for a positive cosine so small (below about 1e-13) that G1 or one of
+ * its derivatives leaves float32's range, that lane's dlnG1 terms count as 0 -- every derivative stays finite (the value
+ * itself is finite and tends to 0 there).
+ * OUT OF SCOPE: a gradient for d or eta, anisotropy, the Beckmann distribution, a complex index of refraction,
+ * roughplastic's coupled diffuse term (its t_i t_o transmittance tables), RGB, a spot or projector rig.
+ * All entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional (vis among
+ * them), n >= 2^32, spp == 0 or n % spp != 0, n_lights outside 1..HF_MAX_LIGHTS, a non-finite field of a light,
+ * |to_light| zero or non-finite, a negative or non-finite eta.  n == 0 is legal and launches nothing.  The entries
+ * allocate nothing, never synchronise the host and are capturable.  Callers detect them by their symbols (HF_VERSION is
+ * unchanged). */
+int hf_specular_lighting(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3], const float *weight,
+                         const float *alpha, float eta, uint32_t n_lights, const hf_directional_light_t *lights,
+                         const uint8_t *vis, float *image, float *value, hf_stream_t stream);
+/* the adjoint's workspace in floats for a rig of n_lights (0 for a count outside 1..HF_MAX_LIGHTS) */
+size_t hf_specular_workspace_floats(uint32_t n_lights);
+/* Reverse mode.  With the upstream of light k g_k = grad_image[k][i / spp] / spp + grad_value[k][i] (either may be NULL
+ * = zero): grad_sh_n (3 rows), grad_weight and grad_alpha (1 row each) are OVERWRITTEN, one lane per sample, the K lights
+ * summed in light order in double and rounded once, exact zeros where vis = 0, no atomics; grad_lights
+ * ([K][HF_DIRECTIONAL_PARAMS] device floats) is ACCUMULATED into without atomics through `workspace` --
+ * hf_specular_workspace_floats(n_lights) floats of device memory, 8-byte aligned, the caller's, this call's until it has
+ * completed; needed only when grad_lights is wanted -- and one more launch that adds the blocks' rows in a fixed order
+ * (hf_directional_lighting_adjoint's pattern; family 2 of hf_grid_blocks): bitwise the same from launch to launch.  Every
+ * output may be NULL (not wanted). */
+int hf_specular_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                 const float *weight, const float *alpha, float eta, uint32_t n_lights,
+                                 const hf_directional_light_t *lights, const uint8_t *vis, const float *grad_image,
+                                 const float *grad_value, float *const grad_sh_n[3], float *grad_weight, float *grad_alpha,
+                                 float *grad_lights, float *workspace, hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dsh_n (3 rows of n floats), dweight (n), dalpha (n) and
+ * d_lights ([K][HF_DIRECTIONAL_PARAMS] device floats), each may be NULL (zero); dimage (K rows of n / spp) and / or
+ * dvalue (K rows of n) are overwritten (at least one).  No atomics for any spp: bitwise the same from launch to launch. */
+int hf_specular_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                 const float *weight, const float *alpha, float eta, uint32_t n_lights,
+                                 const hf_directional_light_t *lights, const uint8_t *vis, const float *const dsh_n[3],
+                                 const float *dweight, const float *dalpha, const float *d_lights, float *dimage,
+                                 float *dvalue, hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional
@@ -2059,8 +2134,8 @@ int hf_invert_affine(const float in[12], float out[12]);
 /* blocks (of 256 threads) that a grid-stride launch of n items gets, HF_FORCE_GRID included.  family: 0 the flat cap
  * (adjoints, reparameterisation, Adam, area sampling, ...), 1 the cap of the streaming kernels (SI, hf_tangent, the
  * forward and tangent of attributes and of eval_parameterization, the sensor's rays, projection and their tangents), 2
- * the cap of the launches that sum dL/d(to_world), the sensor's adjoints, hf_projector_lighting_adjoint, hf_spot_lighting_adjoint and
- * hf_directional_lighting_adjoint among them.
+ * the cap of the launches that sum dL/d(to_world), the sensor's adjoints, hf_projector_lighting_adjoint,
+ * hf_spot_lighting_adjoint, hf_directional_lighting_adjoint and hf_specular_lighting_adjoint among them.
  * 0 for an unknown family.  Needs no device. */
 int hf_grid_blocks(size_t n, int family);
 const char *hf_last_error_string(void);

@@ -13,3 +13,4 @@ from .projector import Projector, projector_lighting, projector_rays  # noqa: F4
 from .spot import SpotLight, spot_lighting, spot_rays  # noqa: F401
 from .directional import DirectionalLight, directional_lighting, directional_rays  # noqa: F401
 from .normalmap import NormalMap  # noqa: F401
+from .specular import specular_lighting  # noqa: F401

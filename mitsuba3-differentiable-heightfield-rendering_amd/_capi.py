@@ -125,6 +125,10 @@ HF_DIRECTIONAL_PARAMS = 4
 _directional_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_uint32,
                    C.POINTER(hf_directional_light_t), C.c_float, _fp]
 
+# n, spp, sh_n, d, weight, alpha, eta, n_lights, lights, vis
+_specular_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_float, C.c_uint32,
+                C.POINTER(hf_directional_light_t), _fp]
+
 # n, uv, sh_n, dp_du, active, TW, TH, tex, wrap
 _normalmap_in = [C.c_size_t, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, *_bitmap_in]
 
@@ -148,6 +152,13 @@ SYMBOLS = {
     "hf_directional_lighting_adjoint": (C.c_int, [*_directional_in, _fp, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp, C.c_void_p]),
     # ..., dsh_n, dweight, d_lights, dimage, dvalue
     "hf_directional_lighting_tangent": (C.c_int, [*_directional_in, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, C.c_void_p]),
+    # ..., image, value
+    "hf_specular_lighting": (C.c_int, [*_specular_in, _fp, _fp, C.c_void_p]),
+    "hf_specular_workspace_floats": (C.c_size_t, [C.c_uint32]),
+    # ..., grad_image, grad_value, grad_sh_n, grad_weight, grad_alpha, grad_lights, workspace
+    "hf_specular_lighting_adjoint": (C.c_int, [*_specular_in, _fp, _fp, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, C.c_void_p]),
+    # ..., dsh_n, dweight, dalpha, d_lights, dimage, dvalue
+    "hf_specular_lighting_tangent": (C.c_int, [*_specular_in, C.POINTER(_fp * 3), _fp, _fp, _fp, _fp, _fp, C.c_void_p]),
     "hf_spot_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
                                C.POINTER(hf_spot_light_t), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.c_void_p]),
     "hf_spot_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3),

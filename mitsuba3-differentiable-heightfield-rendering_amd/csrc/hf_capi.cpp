@@ -1966,21 +1966,20 @@ extern "C" int hf_spot_lighting_tangent(size_t n, uint32_t spp, const float *con
 }
 
 // ---- directional lighting: a rig of 1..HF_MAX_LIGHTS distant emitters, the shadow rays traced in the kernel ----
-// What the four hf_directional_* entries share (hf_directional_rays passes spp 1, one light, albedo 1): the wavefront,
-// every light's checks and its unit direction, formed once, here, in double
-static int directional_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
-                            const float *t, const float *weight, uint32_t n_lights, const hf_directional_light_t *lights,
-                            float albedo, hf_directional_args &a) {
-    a = {};
-    if (!all3(sh_n) || !all3(d) || !t || !lights) return fail(HF_EINVAL, "%s: NULL argument", who);
+// The two checks of a rig that this row and the specular row share.  The sizes of the wavefront and of the rig:
+static int rig_sizes(const char *who, size_t n, uint32_t spp, uint32_t n_lights) {
     if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
     if (spp == 0 || n % spp != 0) return fail(HF_EINVAL, "%s: n (%zu) must be a multiple of spp (%u)", who, n, spp);
     if (n_lights == 0 || n_lights > HF_MAX_LIGHTS)
         return fail(HF_EINVAL, "%s: 1..%d lights supported (got %u)", who, HF_MAX_LIGHTS, n_lights);
-    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    return HF_OK;
+}
+// ... and every light's checks and its device block, the unit direction formed once, here, in double; ce = scale * irradiance
+static int rig_lights(const char *who, uint32_t n_lights, const hf_directional_light_t *lights, double scale,
+                      hf_directional_light_dev *L) {
     for (uint32_t l = 0; l < n_lights; ++l) {
         const hf_directional_light_t &s = lights[l];
-        hf_directional_light_dev &o = a.L[l];
+        hf_directional_light_dev &o = L[l];
         const double *v = s.to_light;
         if (!isfinite(v[0]) || !isfinite(v[1]) || !isfinite(v[2]) || !isfinite(s.irradiance))
             return fail(HF_EINVAL, "%s: light %u: to_light and irradiance must be finite", who, l);
@@ -1989,8 +1988,21 @@ static int directional_args(const char *who, size_t n, uint32_t spp, const float
             return fail(HF_EINVAL, "%s: light %u: to_light must have a finite length > 0", who, l);
         o.inv_len = 1.0 / len;
         for (int k = 0; k < 3; ++k) { o.l[k] = v[k] / len; o.lf[k] = (float) o.l[k]; }
-        o.ce = (double) albedo / 3.141592653589793 * (double) s.irradiance;
+        o.ce = scale * (double) s.irradiance;
     }
+    return HF_OK;
+}
+// What the four hf_directional_* entries share (hf_directional_rays passes spp 1, one light, albedo 1): the wavefront, the
+// rig's checks, ce = albedo / pi * irradiance
+static int directional_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                            const float *t, const float *weight, uint32_t n_lights, const hf_directional_light_t *lights,
+                            float albedo, hf_directional_args &a) {
+    a = {};
+    if (!all3(sh_n) || !all3(d) || !t || !lights) return fail(HF_EINVAL, "%s: NULL argument", who);
+    int rc = rig_sizes(who, n, spp, n_lights);
+    if (rc != HF_OK) return rc;
+    if (!isfinite(albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    if ((rc = rig_lights(who, n_lights, lights, (double) albedo / 3.141592653589793, a.L))) return rc;
     for (int k = 0; k < 3; ++k) { a.sh_n[k] = sh_n[k]; a.d[k] = d[k]; }
     a.n = n; a.spp = spp; a.n_lights = n_lights; a.t = t; a.weight = weight;
     a.albedo_pi = (double) albedo / 3.141592653589793;
@@ -2068,6 +2080,76 @@ extern "C" int hf_directional_lighting_tangent(size_t n, uint32_t spp, const flo
     a.d_lights = d_lights;
     if (n == 0) return HF_OK;
     return light_launch(hf_launch_directional, 2, a, stream);
+}
+
+// ---- specular highlights: the GGX lobe under the directional rig, the directional row's byte read ----
+// What the three hf_specular_* entries share: the wavefront, the rig's checks (rig_sizes, rig_lights: ce = irradiance),
+// the interface
+static int specular_args(const char *who, size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                         const float *weight, const float *alpha, float eta, uint32_t n_lights,
+                         const hf_directional_light_t *lights, const uint8_t *vis, hf_specular_args &a) {
+    a = {};
+    if (!all3(sh_n) || !all3(d) || !alpha || !lights || !vis) return fail(HF_EINVAL, "%s: NULL argument", who);
+    int rc = rig_sizes(who, n, spp, n_lights);
+    if (rc != HF_OK || (rc = rig_lights(who, n_lights, lights, 1.0, a.L)) || (rc = light_interface(who, eta, a))) return rc;
+    for (int k = 0; k < 3; ++k) { a.sh_n[k] = sh_n[k]; a.d[k] = d[k]; }
+    a.n = n; a.spp = spp; a.n_lights = n_lights; a.weight = weight; a.alpha = alpha; a.vis = vis;
+    return HF_OK;
+}
+
+extern "C" int hf_specular_lighting(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                    const float *weight, const float *alpha, float eta, uint32_t n_lights,
+                                    const hf_directional_light_t *lights, const uint8_t *vis, float *image, float *value,
+                                    hf_stream_t stream) {
+    const char *fn = "hf_specular_lighting";
+    hf_specular_args a;
+    const int rc = specular_args(fn, n, spp, sh_n, d, weight, alpha, eta, n_lights, lights, vis, a);
+    if (rc != HF_OK) return rc;
+    if (!image && !value) return fail(HF_EINVAL, "%s: image and value are both NULL", fn);
+    a.image = image; a.value = value;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_specular, 0, a, stream);
+}
+
+extern "C" size_t hf_specular_workspace_floats(uint32_t n_lights) {
+    return n_lights >= 1 && n_lights <= HF_MAX_LIGHTS ? 2u * hf_specular_slab_doubles(n_lights) : 0u;
+}
+
+extern "C" int hf_specular_lighting_adjoint(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                            const float *weight, const float *alpha, float eta, uint32_t n_lights,
+                                            const hf_directional_light_t *lights, const uint8_t *vis,
+                                            const float *grad_image, const float *grad_value, float *const grad_sh_n[3],
+                                            float *grad_weight, float *grad_alpha, float *grad_lights, float *workspace,
+                                            hf_stream_t stream) {
+    const char *fn = "hf_specular_lighting_adjoint";
+    hf_specular_args a;
+    const int rc = specular_args(fn, n, spp, sh_n, d, weight, alpha, eta, n_lights, lights, vis, a);
+    if (rc != HF_OK) return rc;
+    if (grad_sh_n && !all3(grad_sh_n)) return fail(HF_EINVAL, "%s: NULL grad_sh_n component array", fn);
+    if (grad_lights && !workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_lights && ((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    a.gimg = grad_image; a.gvalue = grad_value; a.gw = grad_weight; a.ga = grad_alpha;
+    for (int c = 0; c < 3; ++c) a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+    a.slab = grad_lights ? (double *) workspace : nullptr;
+    a.g_lights = grad_lights;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_specular, 1, a, stream);
+}
+
+extern "C" int hf_specular_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n[3], const float *const d[3],
+                                            const float *weight, const float *alpha, float eta, uint32_t n_lights,
+                                            const hf_directional_light_t *lights, const uint8_t *vis,
+                                            const float *const dsh_n[3], const float *dweight, const float *dalpha,
+                                            const float *d_lights, float *dimage, float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_specular_lighting_tangent";
+    hf_specular_args a;
+    int rc = specular_args(fn, n, spp, sh_n, d, weight, alpha, eta, n_lights, lights, vis, a);
+    if (rc != HF_OK) return rc;
+    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
+    if ((rc = light_tangent_io(fn, false, dsh_n, dweight, dimage, a, true))) return rc;
+    a.value = dvalue; a.da = dalpha; a.d_lights = d_lights;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_specular, 2, a, stream);
 }
 
 // ---- the sensor: the primary wavefront of a perspective or an orthographic camera ----

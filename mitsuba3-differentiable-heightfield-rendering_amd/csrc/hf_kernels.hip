@@ -8165,8 +8165,10 @@ __global__ __launch_bounds__(HF_BLOCK) void hf_directional_rays_kernel(hf_direct
     light_store_spawned(a, i, p, gn, lf, elig && dot3(sn, lf) > 0.f);
 }
 
-// the upstream of light k's value of sample i: grad_image[k][i / spp] / spp + grad_value[k][i] (NULL: zero)
-__device__ __forceinline__ float directional_value_seed(const hf_directional_args &a, uint32_t k, size_t i) {
+// the upstream of light k's value of sample i: grad_image[k][i / spp] / spp + grad_value[k][i] (NULL: zero); A: the
+// argument of a row with K images and K value rows (this row's, the specular row's)
+template <class A>
+__device__ __forceinline__ float directional_value_seed(const A &a, uint32_t k, size_t i) {
     return (a.gimg ? a.gimg[(size_t) k * (a.n / a.spp) + i / a.spp] * (1.0f / (float) a.spp) : 0.f) +
            (a.gvalue ? a.gvalue[(size_t) k * a.n + i] : 0.f);
 }
@@ -8296,6 +8298,255 @@ void hf_launch_directional(int mode, const hf_directional_args &a, hipStream_t s
     }
     launch_light(mode, a, a.n_lights, stream, hf_directional_kernel, hf_directional_adjoint_kernel,
                  hf_directional_tangent_kernel<false>, hf_directional_tangent_kernel<true>, hf_directional_rays_kernel);
+}
+
+// ---------------------------------------------------------------------------------
+// Specular highlights (include/hf.h hf_specular_*): the reflection lobe of a rough surface
+// (roughplastic.cpp:315-350, roughconductor.cpp's eval: F D G / (4 cos theta_i)) under the directional rig, for ALL
+// lights in ONE launch: hf_directional_kernel's skeleton without the walk.  Nothing is traced: bit k of the directional
+// row's visibility byte is light k's mask.
+//   value_k = weight E_k F(<wi, h>) D(c_h, a) G1(c_i, a) G1(c_o, a) / (4 c_i),   h = (wi + l_k) / |wi + l_k|.
+// The row's own text is the lobe with its partial derivatives (specular_lobe, one function for the three kernels) and
+// the reduction of the 4 numbers of every light; F and G1 are the glossy row's (reflect_vertex, glossy_smith), the film,
+// the seed, the stores, the launch and the reduction the lighting rows' and the sensor's shared functions.
+// ---------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) hf_specular_args *hf_specular_kargs;
+
+// The lobe of one sample under one light, per unit weight and irradiance: v = F R with R = D G1(c_i) G1(c_o) / (4 c_i), D
+// and the products in double; and (DERIV) its partial derivatives with every mask held:
+//   N = dv/dsh_n = v [ kD h + (dlnG1(c_i)/dc - 1/c_i) wi + (dlnG1(c_o)/dc) l ],      kD = dlnD/dc_h,
+//   A = dv/da    = v [ dlnD/da + dlnG1(c_i)/da + dlnG1(c_o)/da ],
+//   Ld = dv/dl   = v (dlnG1(c_o)/dc) sh_n + [ v kD (sh_n - h c_h) + R dF/du (wi - h u) ] / M   (l free; dh = (dl - h <h, dl>) / M)
+// with u = <wi, h>, M = |wi + l|.  A lane whose cosines are not positive: all zero.  Where both are, M > 0, c_h > 0 and
+// u > 0 (microfacet.h:206, :362 hold identically and are not tested).  P: where eta, rcp_eta are read (reflect_vertex)
+struct hf_specular_lobe {
+    double v, N[3], A, Ld[3];
+};
+// d ln G1 = dG1 / G1 of glossy_smith's float32 results in double; 0 if that is not finite
+__device__ __forceinline__ double specular_dln(float dg, float g) {
+    const double q = (double) dg / (double) g;
+    return __builtin_fabs(q) < (double) __builtin_inff() ? q : 0.0;
+}
+template <bool DERIV, class P>
+__device__ __forceinline__ hf_specular_lobe specular_lobe(P a, v3 sn, v3 d, float al, hf_d3 l) {
+    hf_specular_lobe r;
+    r.v = 0.0; r.A = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { r.N[c] = 0.0; r.Ld[c] = 0.0; }
+    const hf_d3 wi = hf_d3{ -(double) d.x, -(double) d.y, -(double) d.z };
+    const double ci = sky_dot_f64(sn, wi), co = sky_dot_f64(sn, l);
+    if (!(ci > 0.0) || !(co > 0.0)) return r;
+    const hf_d3 m = hf_d3{ wi.x + l.x, wi.y + l.y, wi.z + l.z };
+    const double iM = 1.0 / sqrt(m.x * m.x + m.y * m.y + m.z * m.z);
+    const hf_d3 h = hf_d3{ m.x * iM, m.y * iM, m.z * iM };
+    const double ch = sky_dot_f64(sn, h);
+    // F at the float32 cosine <wi, float32(h)> and G1 at the float32 cosines: the glossy row's functions
+    const hf_reflect_vertex rv = reflect_vertex(a, mk3((float) h.x, (float) h.y, (float) h.z), d);
+    const hf_glossy_smith gi = glossy_smith(al, (float) ci), go = glossy_smith(al, (float) co);
+    // D = 1 / (pi a^2 q^2), q = s^2 / a^2 + c_h^2 (microfacet.h:185-207, isotropic GGX)
+    const double ad = (double) al, ia2 = 1.0 / (ad * ad);
+    const double s2 = fmax(1.0 - ch * ch, 0.0);
+    const double q = s2 * ia2 + ch * ch;
+    const double D = ia2 / (3.141592653589793 * (q * q));
+    const double R = D * ((double) gi.G * (double) go.G) / (4.0 * ci);
+    r.v = (double) rv.F * R;
+    if (DERIV) {
+        const double kD = -4.0 * ch * (1.0 - (s2 > 0.0 ? ia2 : 0.0)) / q;
+        const double kDa = -2.0 / ad + 4.0 * s2 * ia2 / (ad * q);
+        // (d ln G1: 0 where the float32 G1 or its derivative left float32's range, a cosine below about 1e-13)
+        const double ki = specular_dln(gi.dc, gi.G) - 1.0 / ci, ko = specular_dln(go.dc, go.G);
+        const double ka = specular_dln(gi.da, gi.G) + specular_dln(go.da, go.G);
+        const double u = wi.x * h.x + wi.y * h.y + wi.z * h.z;
+        const double vD = r.v * kD, vi = r.v * ki, vo = r.v * ko, RF = R * (double) rv.dF;
+        r.N[0] = vD * h.x + vi * wi.x + vo * l.x;
+        r.N[1] = vD * h.y + vi * wi.y + vo * l.y;
+        r.N[2] = vD * h.z + vi * wi.z + vo * l.z;
+        r.A = r.v * (kDa + ka);
+        r.Ld[0] = vo * (double) sn.x + (vD * ((double) sn.x - h.x * ch) + RF * (wi.x - h.x * u)) * iM;
+        r.Ld[1] = vo * (double) sn.y + (vD * ((double) sn.y - h.y * ch) + RF * (wi.y - h.y * u)) * iM;
+        r.Ld[2] = vo * (double) sn.z + (vD * ((double) sn.z - h.z * ch) + RF * (wi.z - h.z * u)) * iM;
+    }
+    return r;
+}
+// a sample takes part when its roughness is finite (a = max(alpha, 1e-4)); its byte otherwise counts as zero
+__device__ __forceinline__ bool specular_finite(float alpha) { return __builtin_fabsf(alpha) < __builtin_inff(); }
+
+#ifndef HF_SPECULAR_WAVES
+#define HF_SPECULAR_WAVES 6 // resident waves per SIMD (the siblings'; profiles/specular/registers.txt)
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_SPECULAR_WAVES) void hf_specular_kernel(hf_specular_args a) {
+    // hf_directional_kernel's mapping: n < 2^32, one lane per sample
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    hf_specular_kargs ka = (hf_specular_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    // the sample's record: read once, held across the loop over the lights
+    const v3 sn = mk3(ka->sh_n[0][ii], ka->sh_n[1][ii], ka->sh_n[2][ii]);
+    const v3 d = mk3(ka->d[0][ii], ka->d[1][ii], ka->d[2][ii]);
+    const float alpha = ka->alpha[ii];
+    float wgt = 1.f;
+    {
+        const float *weight = ka->weight;
+        if (weight) wgt = weight[ii];
+    }
+    const uint32_t bits = (in && specular_finite(alpha)) ? (uint32_t) ka->vis[ii] : 0u;
+    const float al = fmaxf(alpha, 1e-4f);
+#pragma unroll 1
+    for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+        asm volatile("" : "+s"(ka)); // opaque per light: the kernarg loads stay inside the loop
+        const bool lit = ((bits >> k) & 1u) != 0u;
+        float val = 0.f;
+        if (__ballot(lit) != 0ull) { // wave-uniform: a batch without a sample lit by this light skips its lobe
+            if (lit) {
+                const hf_d3 l = hf_d3{ ka->L[k].l[0], ka->L[k].l[1], ka->L[k].l[2] };
+                val = (float) (((double) wgt * ka->L[k].ce) * specular_lobe<false>(ka, sn, d, al, l).v);
+            }
+        }
+        float *value = ka->value;
+        if (in && value) value[(size_t) k * ka->n + i] = val;
+        float *image = ka->image;
+        if (image) { // the film of light k: hf_point_lighting's layout, K images of n / spp
+            const uint32_t spp = ka->spp, g = spp < 64u ? spp : 64u;
+            film_pixel(image, val, k, ka->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+        }
+        if (k + 1u >= ka->n_lights) break;
+    }
+}
+
+// Reverse mode of hf_specular_kernel with respect to sh_n, weight, alpha and, per light, to_light and irradiance:
+// hf_directional_adjoint_kernel's two grid-stride passes.  First every sample's own gradients: the lights of its byte
+// summed in light order in double and rounded once, overwritten, no atomics.  Then, where grad_lights is wanted, light by
+// light (block-uniform): the 4 numbers of the light kept per lane in double across the grid-stride loop and reduced as
+// the sensor's 13.  dl = (dv - l <l, dv>) / L
+#define HF_SPECULAR_SUMS 4
+__global__ __launch_bounds__(HF_BLOCK) void hf_specular_adjoint_kernel(hf_specular_args a) {
+    hf_specular_kargs ka = (hf_specular_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    if (a.gn[0] || a.gn[1] || a.gn[2] || a.gw || a.ga) { // (launch-uniform)
+        for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+            const float alpha = a.alpha[i];
+            const uint32_t bits = specular_finite(alpha) ? (uint32_t) a.vis[i] : 0u;
+            double gn[3] = { 0.0, 0.0, 0.0 }, gw = 0.0, ga = 0.0;
+            if (bits) {
+                const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+                const double w = a.weight ? (double) a.weight[i] : 1.0;
+                const float al = fmaxf(alpha, 1e-4f);
+#pragma unroll 1
+                for (uint32_t k = 0; k < a.n_lights; ++k) {
+                    if (!((bits >> k) & 1u)) continue;
+                    const hf_d3 l = hf_d3{ ka->L[k].l[0], ka->L[k].l[1], ka->L[k].l[2] };
+                    const hf_specular_lobe s = specular_lobe<true>(ka, sn, d, al, l);
+                    const double gE = (double) directional_value_seed(a, k, i) * ka->L[k].ce, gwE = gE * w;
+                    gw += gE * s.v;
+                    gn[0] += gwE * s.N[0]; gn[1] += gwE * s.N[1]; gn[2] += gwE * s.N[2];
+                    ga += gwE * s.A;
+                }
+            }
+            light_store_grads(a, i, mk3((float) gn[0], (float) gn[1], (float) gn[2]), (float) gw);
+            if (a.ga) a.ga[i] = alpha > 1e-4f ? (float) ga : 0.f; // (the clamp a = 1e-4 is held)
+        }
+    }
+    if (!a.slab) return; // (launch-uniform: grad_lights is not wanted)
+#pragma unroll 1
+    for (uint32_t k = 0; k < a.n_lights; ++k) { // block-uniform
+        double M[HF_SPECULAR_SUMS];
+#pragma unroll
+        for (int j = 0; j < HF_SPECULAR_SUMS; ++j) M[j] = 0.0;
+        const hf_d3 l = hf_d3{ ka->L[k].l[0], ka->L[k].l[1], ka->L[k].l[2] };
+        const double E_l = ka->L[k].ce * ka->L[k].inv_len;
+        for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+            const float alpha = a.alpha[i];
+            if (!((a.vis[i] >> k) & 1u) || !specular_finite(alpha)) continue;
+            const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+            const hf_specular_lobe s = specular_lobe<true>(ka, sn, d, fmaxf(alpha, 1e-4f), l);
+            const double gw = (double) directional_value_seed(a, k, i) * (a.weight ? (double) a.weight[i] : 1.0);
+            const double lg = l.x * s.Ld[0] + l.y * s.Ld[1] + l.z * s.Ld[2], gl = gw * E_l;
+            M[0] += gl * (s.Ld[0] - l.x * lg); // dv/dl's part orthogonal to l, over |to_light|
+            M[1] += gl * (s.Ld[1] - l.y * lg);
+            M[2] += gl * (s.Ld[2] - l.z * lg);
+            M[3] += gw * s.v;
+        }
+        sensor_block_store<HF_SPECULAR_SUMS>(M, a.slab + (size_t) k * gridDim.x * HF_SPECULAR_SUMS);
+        __syncthreads(); // (the next light's sums go through the same LDS rows)
+    }
+}
+// block k: g_lights[k][j] += column j of light k's rows
+__global__ __launch_bounds__(HF_BLOCK) void hf_specular_sum_kernel(const double *__restrict__ slab, uint32_t rows,
+                                                                    float *__restrict__ g_lights) {
+    const double *const sum = sensor_slab_sums<HF_SPECULAR_SUMS>(slab + (size_t) blockIdx.x * rows * HF_SPECULAR_SUMS, rows);
+    const uint32_t t = threadIdx.x;
+    if (t < (uint32_t) HF_SPECULAR_SUMS) g_lights[blockIdx.x * HF_SPECULAR_SUMS + t] += (float) sum[t];
+}
+size_t hf_specular_slab_doubles(uint32_t n_lights) { return (size_t) HF_XFORM_GRID_CAP * HF_SPECULAR_SUMS * n_lights; }
+
+// forward mode, the transpose of the above: the tangent of light k's value of sample i for tangents dn of sh_n, dw of
+// weight, da of alpha and row k of d_lights (NULL: zero)
+template <class LP>
+__device__ __forceinline__ float specular_tangent_value(const hf_specular_args &a, LP L, uint32_t k, size_t i) {
+    const float alpha = a.alpha[i];
+    if (!((a.vis[i] >> k) & 1u) || !specular_finite(alpha)) return 0.f;
+    const v3 sn = mk3(a.sh_n[0][i], a.sh_n[1][i], a.sh_n[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    const hf_d3 l = hf_d3{ L->l[0], L->l[1], L->l[2] };
+    const hf_specular_lobe s = specular_lobe<true>(&a, sn, d, fmaxf(alpha, 1e-4f), l);
+    double dv = 0.0, dE = 0.0;
+    if (a.dn[0]) dv = s.N[0] * (double) a.dn[0][i] + s.N[1] * (double) a.dn[1][i] + s.N[2] * (double) a.dn[2][i];
+    if (a.da && alpha > 1e-4f) dv += s.A * (double) a.da[i];
+    if (a.d_lights) {
+        const float *dl = a.d_lights + k * HF_SPECULAR_SUMS;
+        const double q[3] = { (double) dl[0], (double) dl[1], (double) dl[2] };
+        const double lq = l.x * q[0] + l.y * q[1] + l.z * q[2];
+        dv += (s.Ld[0] * (q[0] - l.x * lq) + s.Ld[1] * (q[1] - l.y * lq) + s.Ld[2] * (q[2] - l.z * lq)) * L->inv_len;
+        dE = (double) dl[3];
+    }
+    const double w = a.weight ? (double) a.weight[i] : 1.0, dw = a.dw ? (double) a.dw[i] : 0.0;
+    return (float) ((dw * L->ce + w * dE) * s.v + (w * L->ce) * dv);
+}
+// hf_directional_tangent_kernel's two shapes: PIXEL = false: one lane per sample and the primal's film (spp a power of
+// two <= 64, or no image wanted); PIXEL = true: one lane per pixel adds its samples in order -- no atomics either way
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_specular_tangent_kernel(hf_specular_args a) {
+    hf_specular_kargs ka = (hf_specular_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    const size_t npix = a.n / spp;
+    if (PIXEL) {
+        if (i >= npix) return;
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.n_lights; ++k) {
+            float c = 0.f;
+            for (uint32_t s = 0; s < spp; ++s) {
+                const float dv = specular_tangent_value(a, &ka->L[k], k, i * spp + s);
+                if (a.value) a.value[(size_t) k * a.n + i * spp + s] = dv;
+                c += dv;
+            }
+            a.image[(size_t) k * npix + i] = c * (1.0f / (float) spp);
+        }
+    } else {
+        const bool in = i < a.n;
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.n_lights; ++k) { // wave-uniform
+            const float c = specular_tangent_value(a, &ka->L[k], k, in ? i : a.n - 1);
+            if (in && a.value) a.value[(size_t) k * a.n + i] = c;
+            if (a.image) film_pixel(a.image, in ? c : 0.f, k, npix, i, spp, in, true, spp, 1.0f / (float) spp);
+        }
+    }
+}
+
+// mode 0: forward, 1: adjoint (and, where grad_lights is wanted, the sum of the blocks' rows, one block per light),
+// 2: tangent; the row has no rays
+void hf_launch_specular(int mode, const hf_specular_args &a, hipStream_t stream) {
+    if (mode == 1) {
+        if (a.n == 0) return;
+        const int grid = grid_for(a.n, HF_XFORM_GRID_CAP); // the slab holds HF_XFORM_GRID_CAP rows per light
+        hipLaunchKernelGGL(hf_specular_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        if (a.slab)
+            hipLaunchKernelGGL(hf_specular_sum_kernel, dim3(a.n_lights), dim3(HF_BLOCK), 0, stream, a.slab, (uint32_t) grid,
+                               a.g_lights);
+        return;
+    }
+    launch_light(mode, a, a.n_lights, stream, hf_specular_kernel, hf_specular_adjoint_kernel,
+                 hf_specular_tangent_kernel<false>, hf_specular_tangent_kernel<true>,
+                 static_cast<void (*)(hf_specular_args)>(nullptr));
 }
 
 // ---------------------------------------------------------------------------------

@@ -416,6 +416,27 @@ struct hf_directional_args {
 // hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
 void hf_launch_directional(int mode, const hf_directional_args &a, hipStream_t stream);
 size_t hf_directional_slab_doubles(uint32_t n_lights);
+// ---- specular highlights (hf_specular_lighting / _adjoint / _tangent): the GGX lobe under the directional
+// rig, for all lights in one launch; nothing is traced, the directional row's visibility byte is read.  The lights are
+// hf_directional_light_dev with ce = irradiance (no albedo); eta, rcp_eta as in hf_reflect_args (reflect_vertex reads them) ----
+struct hf_specular_args {
+    size_t n;
+    uint32_t spp, n_lights;
+    float eta, rcp_eta;
+    hf_directional_light_dev L[HF_MAX_LIGHTS]; // the first n_lights are read
+    const float *sh_n[3], *d[3], *weight, *alpha;
+    const uint8_t *vis;                      // read by every mode; bit k: light k
+    float *image, *value;                    // forward: written, K rows each (NULL: not wanted); tangent: dimage, dvalue
+    const float *gimg, *gvalue;              // adjoint inputs, K rows each (NULL: zero)
+    float *gn[3], *gw, *ga;                  // adjoint outputs (NULL: not wanted)
+    double *slab;                            // adjoint: per light, 4 doubles per block (NULL: grad_lights is not wanted)
+    float *g_lights;                         // adjoint output [K][4], accumulated
+    const float *dn[3], *dw, *da;            // tangent inputs (NULL: zero)
+    const float *d_lights;                   // tangent input [K][4] device floats (NULL: zero)
+};
+// mode 0: forward, 1: adjoint (two launches where grad_lights is wanted), 2: tangent
+void hf_launch_specular(int mode, const hf_specular_args &a, hipStream_t stream);
+size_t hf_specular_slab_doubles(uint32_t n_lights);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
