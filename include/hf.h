@@ -1796,6 +1796,109 @@ int hf_specular_lighting_tangent(size_t n, uint32_t spp, const float *const sh_n
                                  const float *dweight, const float *dalpha, const float *d_lights, float *dimage,
                                  float *dvalue, hf_stream_t stream);
 
+/* ---- next row: a homogeneous medium, single scattering under the directional rig, the shadow rays of
+ * 1..32 points of every primary ray traced in the kernel ----
+ *
+ * The single-scattering emitter-sampling step of prbvolpath (src/python/python/ad/integrators/prbvolpath.py) for a
+ * `homogeneous` medium (src/media/homogeneous.cpp:139-175: sigma_s = albedo sigma_t) with the `hg` phase function
+ * (src/phase/hg.cpp:66-69) under 1 <= J <= HF_MAX_LIGHTS `directional` emitters, for a scene whose only occluder is this
+ * shape.  World space.  The medium fills the half space below a top plane; the rig of hf_directional_light_t lies
+ * outside it.  Every lighting row so far ends at the surface; this one lights the space between camera, terrain and
+ * light: its shadow rays start IN FREE SPACE (no spawn offset, no normal), and a sample that missed the terrain
+ * (t = inf) still contributes.
+ *   medium      hf_medium_t, HOST memory.  top_normal points out of the medium, any finite length > 0; the host forms
+ *               N = top_normal / |top_normal| once, in double.
+ *   segment     inputs o, d (3 device rows of n floats, the primary ray) and t (n floats, inf = a miss); geometry in
+ *               double from the float32 rows.  h = <o - top_origin, N>, c = <d, N>.
+ *                 c < 0:            u_in = max(0, h / -c), u_out = t;
+ *                 c > 0 and h < 0:  u_in = 0, u_out = min(t, -h / c);
+ *                 c == 0 and h < 0: u_in = 0, u_out = t;
+ *                 otherwise the segment is empty.
+ *               A sample is ELIGIBLE when t > 0, t is not NaN and u_out > u_in.  S = u_out - u_in (may be inf).  D, the
+ *               depth of the entry point below the top: -h when u_in = 0, else exactly 0.
+ *   points      K = num_steps, 1..32.  xi_k: the FIRST number of the stream (r0, r1) = sample_tea_32(sample_tea_32(seed,
+ *               k)[0], id_i), r0 >> 9 scaled by 2^-23 (hf_sky_lighting's convention, id_i = i or ray_id[i]; the second
+ *               number is unused).  a = 1 - exp(-sigma_t S) (1 for S = inf), tau_k = -log1p(-xi_k a), u_k = u_in +
+ *               tau_k / sigma_t: distance sampling in proportion to the transmittance (medium.cpp:71) truncated to the
+ *               segment and normalised; every draw is a medium interaction and moves smoothly with S and sigma_t.
+ *               xi < 1, so tau_k < sigma_t S.
+ *   shadow ray  light j has nu_j = <l_j, N>.  A light with nu_j <= 0 contributes exact zeros: no bit is set and nothing
+ *               is walked (decided on the host).  Otherwise o_ray = fmaf(float(u_k), d, o) per component, direction
+ *               float32(l_j), maxt = inf.  Interaction::spawn_ray of a medium interaction has n = 0, so offset_p adds
+ *               nothing (interaction.h:136-165).
+ *   vis_bits[j][i]  one uint32: bit k is set iff the sample is eligible, light j shines in and the any-hit walk from
+ *               point k found nothing.
+ *   value       sums in double, in k order, rounded once:
+ *                 p_ij  = (1 - g^2) / (4 pi temp^(3/2)),  temp = 1 + g^2 + 2 g <l_j, -d_i>     (hg.cpp:66-69, 99)
+ *                 x_ijk = (sigma_t D_i - tau_k c_i) / nu_j            (optical depth from point k up to the top)
+ *                 value[j][i] = weight_i albedo a_i p_ij E_j (1/K) sum_k bit_ijk exp(-x_ijk)
+ *               formed from tau_k in double, never from the rounded ray origin: only the ray is float32.
+ *   image[j][i / spp] = 1/spp * sum value[j][i]: hf_directional_lighting's box film and layout, overwritten.
+ * Differentiated with respect to weight, t (through which the gradient reaches the heights and to_world), sigma_t,
+ * albedo, g and every light's irradiance: HF_MEDIUM_PARAMS numbers, then one per light.  HELD: the bits and the branch
+ * of the segment (dS/dt = 1 where u_out = t, 0 where the ray leaves through the top).  With T = (1/K) sum bit exp(-x):
+ *   a_S = sigma_t exp(-sigma_t S),  a_sigma = S exp(-sigma_t S)  (both 0 for S = inf),  da = a_S dS + a_sigma dsigma,
+ *   dtau_k = xi_k / (1 - xi_k a) da,   dx = (dsigma D - dtau c) / nu,
+ *   dp/dg = (-2 g temp - 3 (1 - g^2)(g + cos)) / (4 pi temp^(5/2)).
+ * OUT OF SCOPE: gradients for to_light, the top plane, o and d; multiple scattering; a heterogeneous medium; RGB;
+ * emission; and the silhouette part of a moving shadow (hf_reparam_*'s, as in every row).
+ * All entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional, n >= 2^32,
+ * spp == 0 or n % spp != 0, num_steps outside 1..32 (hf_medium_rays: k >= 32), n_lights outside 1..HF_MAX_LIGHTS,
+ * sigma_t not finite or <= 0, albedo not finite, |g| >= 1 or g not finite, a zero or non-finite top_normal or
+ * top_origin, a non-finite field of a light, |to_light| zero.  Callers detect the entries by their symbols (HF_VERSION
+ * is unchanged). */
+typedef struct hf_medium {          /* HOST memory */
+    double top_origin[3];           /* a point of the top plane */
+    double top_normal[3];           /* out of the medium; any finite length > 0, the host normalises it once in double: N */
+    float  sigma_t, albedo, g;      /* homogeneous.cpp:139-175 (sigma_s = albedo sigma_t), hg.cpp:66-69 */
+} hf_medium_t;
+#define HF_MEDIUM_PARAMS 3          /* sigma_t, albedo, g: then one irradiance per light */
+/* hf_medium_rays materialises shadow ray k of every sample towards ONE light (out_o, out_d: 3 rows of n floats;
+ * out_maxt: n floats, inf for a traced lane; a lane that is not traced gets a zero origin and direction and maxt = -1, a
+ * miss): bit k of hf_medium_lighting's vis_bits row of that light equals hf_medium_rays + hf_ray_test bit for bit.
+ * Takes no field handle.  ray_id: n ids or NULL (i). */
+int hf_medium_rays(size_t n, const float *const o[3], const float *const d[3], const float *t, const hf_medium_t *medium,
+                   const hf_directional_light_t *light, uint32_t k, uint32_t seed, const uint32_t *ray_id,
+                   float *const out_o[3], float *const out_d[3], float *out_maxt, hf_stream_t stream);
+/* The fused launch (hf_sky_lighting's mapping: one lane per sample): reads a sample's o, d, t and weight once and holds
+ * them across the loop over its points, the wave-uniform loop over the lights inside it; draws, walks (any hit, per lane)
+ * and reduces the film; image (J rows of n / spp), value (J rows of n) and vis_bits (J rows of n uint32) may each be NULL
+ * (not wanted), not all of them; no ray and no hit byte goes to memory.  A batch of 64 samples with no eligible sample
+ * draws nothing.  hf_set_ray_coherence is neither read nor changed.  weight: n floats or NULL (1).  Allocates nothing,
+ * never synchronises the host, capturable. */
+int hf_medium_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const o[3], const float *const d[3],
+                       const float *t, const float *weight, const hf_medium_t *medium, uint32_t n_lights,
+                       const hf_directional_light_t *lights, uint32_t num_steps, uint32_t seed, const uint32_t *ray_id,
+                       float *image, float *value, uint32_t *vis_bits, hf_stream_t stream);
+/* the adjoint's workspace in floats for a rig of n_lights (0 for a count outside 1..HF_MAX_LIGHTS): a row of
+ * HF_MEDIUM_PARAMS + HF_MAX_LIGHTS doubles for every block the launch can get, whatever the count */
+size_t hf_medium_workspace_floats(uint32_t n_lights);
+/* Reverse mode.  Traces nothing: the points are drawn again and vis_bits (as hf_medium_lighting wrote it) is read.  With
+ * the upstream of light j g_j = grad_image[j][i / spp] / spp + grad_value[j][i] (either may be NULL = zero):
+ *   grad_weight = sum_j g_j d value_j / d weight,   grad_t = sum_j g_j d value_j / d t
+ * (n floats each) are OVERWRITTEN, one lane per sample, the lights summed in light order in double and rounded once,
+ * exact zeros where no bit is set, no atomics;
+ *   grad_params ([HF_MEDIUM_PARAMS + n_lights] device floats: sigma_t, albedo, g, then the irradiance of every light)
+ * is ACCUMULATED into without atomics: every block stores its partial sums in double to `workspace` --
+ * hf_medium_workspace_floats(n_lights) floats of device memory, 8-byte aligned, the caller's, this call's until it has
+ * completed; needed only when grad_params is wanted -- and one more launch adds them in a fixed order
+ * (hf_directional_lighting_adjoint's pattern; family 2 of hf_grid_blocks): bitwise the same from launch to launch.  Every
+ * output may be NULL (not wanted).  Takes no field handle. */
+int hf_medium_lighting_adjoint(size_t n, uint32_t spp, const float *const o[3], const float *const d[3], const float *t,
+                               const float *weight, const hf_medium_t *medium, uint32_t n_lights,
+                               const hf_directional_light_t *lights, uint32_t num_steps, uint32_t seed,
+                               const uint32_t *ray_id, const uint32_t *vis_bits, const float *grad_image,
+                               const float *grad_value, float *grad_weight, float *grad_t, float *grad_params,
+                               float *workspace, hf_stream_t stream);
+/* Forward mode, the exact transpose of the adjoint, for tangents dweight (n), dt (n) and d_params ([HF_MEDIUM_PARAMS +
+ * n_lights] device floats), each may be NULL (zero); dimage (J rows of n / spp) and / or dvalue (J rows of n) are
+ * overwritten (at least one).  No atomics for any spp: bitwise the same from launch to launch.  Takes no field handle. */
+int hf_medium_lighting_tangent(size_t n, uint32_t spp, const float *const o[3], const float *const d[3], const float *t,
+                               const float *weight, const hf_medium_t *medium, uint32_t n_lights,
+                               const hf_directional_light_t *lights, uint32_t num_steps, uint32_t seed,
+                               const uint32_t *ray_id, const uint32_t *vis_bits, const float *dweight, const float *dt,
+                               const float *d_params, float *dimage, float *dvalue, hf_stream_t stream);
+
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *
  * The bounce of prb_reparam (src/python/python/ad/integrators/prb.py:162-226) for diffuse surfaces under directional
@@ -2135,7 +2238,7 @@ int hf_invert_affine(const float in[12], float out[12]);
  * (adjoints, reparameterisation, Adam, area sampling, ...), 1 the cap of the streaming kernels (SI, hf_tangent, the
  * forward and tangent of attributes and of eval_parameterization, the sensor's rays, projection and their tangents), 2
  * the cap of the launches that sum dL/d(to_world), the sensor's adjoints, hf_projector_lighting_adjoint,
- * hf_spot_lighting_adjoint, hf_directional_lighting_adjoint and hf_specular_lighting_adjoint among them.
+ * hf_spot_lighting_adjoint, hf_directional_lighting_adjoint, hf_specular_lighting_adjoint and hf_medium_lighting_adjoint among them.
  * 0 for an unknown family.  Needs no device. */
 int hf_grid_blocks(size_t n, int family);
 const char *hf_last_error_string(void);

@@ -14,3 +14,4 @@ from .spot import SpotLight, spot_lighting, spot_rays  # noqa: F401
 from .directional import DirectionalLight, directional_lighting, directional_rays  # noqa: F401
 from .normalmap import NormalMap  # noqa: F401
 from .specular import specular_lighting  # noqa: F401
+from .medium import Medium, medium_attenuation, medium_lighting, medium_rays  # noqa: F401

@@ -129,10 +129,31 @@ _directional_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3
 _specular_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.c_float, C.c_uint32,
                 C.POINTER(hf_directional_light_t), _fp]
 
+class hf_medium_t(C.Structure):
+    _fields_ = [("top_origin", C.c_double * 3), ("top_normal", C.c_double * 3), ("sigma_t", C.c_float), ("albedo", C.c_float),
+                ("g", C.c_float)]
+
+
+HF_MEDIUM_PARAMS = 3
+# n, spp, o, d, t, weight, medium, n_lights, lights, num_steps, seed, ray_id, vis_bits
+_medium_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, _fp, C.POINTER(hf_medium_t), C.c_uint32,
+              C.POINTER(hf_directional_light_t), C.c_uint32, C.c_uint32, _fp, _fp]
+
 # n, uv, sh_n, dp_du, active, TW, TH, tex, wrap
-_normalmap_in = [C.c_size_t, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, *_bitmap_in]
+_normalmap_in =[C.c_size_t, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, *_bitmap_in]
 
 SYMBOLS = {
+    # n, o, d, t, medium, light, k, seed, ray_id, out_o, out_d, out_maxt
+    "hf_medium_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(hf_medium_t),
+                                 C.POINTER(hf_directional_light_t), C.c_uint32, C.c_uint32, _fp, C.POINTER(_fp * 3),
+                                 C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    # hf, n, spp, o, d, t, weight, medium, n_lights, lights, num_steps, seed, ray_id, image, value, vis_bits
+    "hf_medium_lighting": (C.c_int, [C.c_void_p, *_medium_in[:-1], _fp, _fp, _fp, C.c_void_p]),
+    "hf_medium_workspace_floats": (C.c_size_t, [C.c_uint32]),
+    # ..., grad_image, grad_value, grad_weight, grad_t, grad_params, workspace
+    "hf_medium_lighting_adjoint": (C.c_int, [*_medium_in, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]),
+    # ..., dweight, dt, d_params, dimage, dvalue
+    "hf_medium_lighting_tangent": (C.c_int, [*_medium_in, _fp, _fp, _fp, _fp, _fp, C.c_void_p]),
     # ..., out_n, mask
     "hf_normalmap_eval": (C.c_int, [*_normalmap_in, C.POINTER(_fp * 3), _fp, C.c_void_p]),
     # ..., dtex, duv, dsh_n, ddp_du, dout_n

@@ -2152,6 +2152,118 @@ extern "C" int hf_specular_lighting_tangent(size_t n, uint32_t spp, const float 
     return light_launch(hf_launch_specular, 2, a, stream);
 }
 
+// ---- homogeneous medium: single scattering below a top plane under the directional rig, the shadow rays of
+// every sample's points traced in the kernel ----
+// What the four hf_medium_* entries share (hf_medium_rays passes spp 1, one light, num_steps k + 1: its k must name one
+// of 32 points): the wavefront, the rig's checks (rig_sizes, rig_lights: ce = irradiance), the medium's, and the unit
+// top normal and every nu_j = <l_j, N>, formed once, here, in double
+static int medium_args(const char *who, size_t n, uint32_t spp, const float *const o[3], const float *const d[3],
+                       const float *t, const float *weight, const hf_medium_t *medium, uint32_t n_lights,
+                       const hf_directional_light_t *lights, uint32_t num_steps, uint32_t seed, const uint32_t *ray_id,
+                       hf_medium_args &a) {
+    a = {};
+    if (!all3(o) || !all3(d) || !t || !medium || !lights) return fail(HF_EINVAL, "%s: NULL argument", who);
+    int rc = rig_sizes(who, n, spp, n_lights);
+    if (rc != HF_OK) return rc;
+    if (num_steps == 0 || num_steps > 32) return fail(HF_EINVAL, "%s: 1..32 points per sample (got %u)", who, num_steps);
+    if (!isfinite(medium->sigma_t) || !(medium->sigma_t > 0.f))
+        return fail(HF_EINVAL, "%s: sigma_t must be finite and > 0 (got %g)", who, (double) medium->sigma_t);
+    if (!isfinite(medium->albedo)) return fail(HF_EINVAL, "%s: albedo must be finite", who);
+    if (!isfinite(medium->g) || !(fabsf(medium->g) < 1.f))
+        return fail(HF_EINVAL, "%s: g must lie in (-1, 1) (got %g)", who, (double) medium->g);
+    const double *v = medium->top_normal, *q = medium->top_origin;
+    if (!isfinite(q[0]) || !isfinite(q[1]) || !isfinite(q[2])) return fail(HF_EINVAL, "%s: top_origin must be finite", who);
+    const double len = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (!isfinite(v[0]) || !isfinite(v[1]) || !isfinite(v[2]) || !(len > 0.0) || !isfinite(len) || !isfinite(1.0 / len))
+        return fail(HF_EINVAL, "%s: top_normal must have a finite length > 0", who);
+    if ((rc = rig_lights(who, n_lights, lights, 1.0, a.L))) return rc;
+    for (int c = 0; c < 3; ++c) { a.N[c] = v[c] / len; a.top_o[c] = q[c]; a.o[c] = o[c]; a.d[c] = d[c]; }
+    for (uint32_t j = 0; j < n_lights; ++j) {
+        const double nu = a.L[j].l[0] * a.N[0] + a.L[j].l[1] * a.N[1] + a.L[j].l[2] * a.N[2];
+        if (nu > 0.0 && isfinite(1.0 / nu)) { a.on |= 1u << j; a.inv_nu[j] = 1.0 / nu; } // (else: the light does not shine in)
+    }
+    a.sigma_t = (double) medium->sigma_t; a.albedo = (double) medium->albedo; a.g = (double) medium->g;
+    a.n = n; a.spp = spp; a.n_lights = n_lights; a.num_steps = num_steps; a.seed = seed; a.ray_id = ray_id;
+    a.t = t; a.weight = weight;
+    return HF_OK;
+}
+
+extern "C" int hf_medium_rays(size_t n, const float *const o[3], const float *const d[3], const float *t,
+                              const hf_medium_t *medium, const hf_directional_light_t *light, uint32_t k, uint32_t seed,
+                              const uint32_t *ray_id, float *const out_o[3], float *const out_d[3], float *out_maxt,
+                              hf_stream_t stream) {
+    const char *fn = "hf_medium_rays";
+    hf_medium_args a;
+    if (k >= 32) return fail(HF_EINVAL, "%s: k must be below 32 (got %u)", fn, k);
+    const int rc = medium_args(fn, n, 1, o, d, t, nullptr, medium, 1, light, k + 1, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(out_o) || !all3(out_d) || !out_maxt) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    a.k = k; a.out_maxt = out_maxt;
+    for (int c = 0; c < 3; ++c) { a.out_o[c] = out_o[c]; a.out_d[c] = out_d[c]; }
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_medium, 3, a, stream);
+}
+
+extern "C" int hf_medium_lighting(const hf_field_t *hf, size_t n, uint32_t spp, const float *const o[3],
+                                  const float *const d[3], const float *t, const float *weight, const hf_medium_t *medium,
+                                  uint32_t n_lights, const hf_directional_light_t *lights, uint32_t num_steps,
+                                  uint32_t seed, const uint32_t *ray_id, float *image, float *value, uint32_t *vis_bits,
+                                  hf_stream_t stream) {
+    const char *fn = "hf_medium_lighting";
+    hf_medium_args a;
+    if (!hf) return fail(HF_EINVAL, "%s: NULL handle", fn);
+    int rc = medium_args(fn, n, spp, o, d, t, weight, medium, n_lights, lights, num_steps, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!image && !value && !vis_bits) return fail(HF_EINVAL, "%s: image, value and vis_bits are all NULL", fn);
+    if (n == 0) return HF_OK;
+    if ((rc = check_device(fn, hf))) return rc;
+    a.f = hf->dev; a.image = image; a.value = value; a.vis_bits = vis_bits;
+    return light_launch(hf_launch_medium, 0, a, stream);
+}
+
+extern "C" size_t hf_medium_workspace_floats(uint32_t n_lights) {
+    return n_lights >= 1 && n_lights <= HF_MAX_LIGHTS ? 2u * hf_medium_slab_doubles() : 0u;
+}
+
+extern "C" int hf_medium_lighting_adjoint(size_t n, uint32_t spp, const float *const o[3], const float *const d[3],
+                                          const float *t, const float *weight, const hf_medium_t *medium,
+                                          uint32_t n_lights, const hf_directional_light_t *lights, uint32_t num_steps,
+                                          uint32_t seed, const uint32_t *ray_id, const uint32_t *vis_bits,
+                                          const float *grad_image, const float *grad_value, float *grad_weight,
+                                          float *grad_t, float *grad_params, float *workspace, hf_stream_t stream) {
+    const char *fn = "hf_medium_lighting_adjoint";
+    hf_medium_args a;
+    const int rc = medium_args(fn, n, spp, o, d, t, weight, medium, n_lights, lights, num_steps, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_params && !workspace) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (grad_params && ((uintptr_t) workspace & 7u) != 0) return fail(HF_EINVAL, "%s: the workspace must be 8-byte aligned", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits);
+    a.gimg = grad_image; a.gvalue = grad_value; a.gw = grad_weight; a.gt = grad_t;
+    a.slab = grad_params ? (double *) workspace : nullptr;
+    a.g_params = grad_params;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_medium, 1, a, stream);
+}
+
+extern "C" int hf_medium_lighting_tangent(size_t n, uint32_t spp, const float *const o[3], const float *const d[3],
+                                          const float *t, const float *weight, const hf_medium_t *medium,
+                                          uint32_t n_lights, const hf_directional_light_t *lights, uint32_t num_steps,
+                                          uint32_t seed, const uint32_t *ray_id, const uint32_t *vis_bits,
+                                          const float *dweight, const float *dt, const float *d_params, float *dimage,
+                                          float *dvalue, hf_stream_t stream) {
+    const char *fn = "hf_medium_lighting_tangent";
+    hf_medium_args a;
+    const int rc = medium_args(fn, n, spp, o, d, t, weight, medium, n_lights, lights, num_steps, seed, ray_id, a);
+    if (rc != HF_OK) return rc;
+    if (!vis_bits) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if (!dimage && !dvalue) return fail(HF_EINVAL, "%s: dimage and dvalue are both NULL", fn);
+    a.vis_bits = const_cast<uint32_t *>(vis_bits);
+    a.image = dimage; a.value = dvalue; a.dw = dweight; a.dt = dt; a.d_params = d_params;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_medium, 2, a, stream);
+}
+
 // ---- the sensor: the primary wavefront of a perspective or an orthographic camera ----
 static int log2_or_minus1(uint32_t v) {
     if (v == 0 || (v & (v - 1u))) return -1;

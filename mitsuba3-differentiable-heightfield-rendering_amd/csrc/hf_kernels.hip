@@ -9182,3 +9182,332 @@ void hf_launch_normalmap(int mode, const hf_normalmap_args &a, hipStream_t strea
     hipLaunchKernelGGL(mode == 0 ? hf_normalmap_kernel : mode == 1 ? hf_normalmap_adjoint_kernel : hf_normalmap_tangent_kernel,
                        grid, block, 0, stream, a);
 }
+
+// ---------------------------------------------------------------------------------
+// Homogeneous medium (include/hf.h hf_medium_*): single scattering in the half space below a top plane
+// (`homogeneous` + `hg`, src/media/homogeneous.cpp, src/phase/hg.cpp) under the directional rig, which lies outside it.
+// One lane per sample; the sample's o, d, t are read once and held across the loop over its K = num_steps points, the
+// wave-uniform loop over the lights inside it: point k is drawn on the segment of the primary ray inside the medium in
+// proportion to the transmittance, its shadow ray starts IN FREE SPACE (no spawn offset, no normal) and is walked (any
+// hit, per lane); a sample that missed the terrain (t = inf) takes part.  The geometry of the segment, the draws and the
+// sums are in double; only the ray is float32.  The row's own text is the segment, the draw, the phase function and the
+// sums with their derivatives; the sample stream, the walk, the ray store, the film, the launch and the reduction of
+// the HF_MEDIUM_PARAMS + n_lights numbers are the lighting rows' and the sensor's shared functions.
+// ---------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) hf_medium_args *hf_medium_kargs;
+
+// the part of a primary ray inside the medium, [u_in, u_in + S]; c = <d, N>; D: the depth of its first point below the
+// top; at_t: it ends at t (dS/dt = 1), not at the top plane (dS/dt = 0)
+struct hf_medium_seg {
+    double u_in, S, D, c;
+    bool elig, at_t;
+};
+template <class P>
+__device__ __forceinline__ hf_medium_seg medium_segment(P a, v3 o, v3 d, float tf) {
+    hf_medium_seg s;
+    const double h = ((double) o.x - a->top_o[0]) * a->N[0] + ((double) o.y - a->top_o[1]) * a->N[1] +
+                     ((double) o.z - a->top_o[2]) * a->N[2];
+    const double t = (double) tf;
+    s.c = (double) d.x * a->N[0] + (double) d.y * a->N[1] + (double) d.z * a->N[2];
+    double u_out = 0.0;
+    bool some = false;
+    s.u_in = 0.0; s.at_t = true;
+    if (s.c < 0.0) {
+        s.u_in = fmax(0.0, h / -s.c); u_out = t; some = true;
+    } else if (h < 0.0) {
+        const double top = s.c > 0.0 ? -h / s.c : __builtin_inf();
+        s.at_t = t <= top; u_out = s.at_t ? t : top; some = true;
+    }
+    s.elig = some && tf > 0.f && u_out > s.u_in; // (t > 0: not NaN either)
+    s.S = u_out - s.u_in;
+    s.D = s.u_in == 0.0 ? -h : 0.0;
+    return s;
+}
+// a = 1 - exp(-sigma_t S), 1 for S = inf
+__device__ __forceinline__ double medium_a(double sigma_t, double S) { return -expm1(-sigma_t * S); }
+// point k of the sample with stream id `id`: the first number of sky_sample's stream and the optical depth from the
+// entry point, tau = -log1p(-xi a) < sigma_t S
+__device__ __forceinline__ double medium_tau(uint32_t seed, uint32_t k, uint32_t id, double av, double &xi) {
+    float sx, sy;
+    sky_sample(seed, k, id, sx, sy);
+    xi = (double) sx;
+    return -log1p(-xi * av);
+}
+// the origin of point k's shadow rays: the distance rounded once, then one fma per component
+__device__ __forceinline__ v3 medium_point(v3 o, v3 d, double u) {
+    const float uf = (float) u;
+    return mk3(__builtin_fmaf(uf, d.x, o.x), __builtin_fmaf(uf, d.y, o.y), __builtin_fmaf(uf, d.z, o.z));
+}
+// hg.cpp:66-69 with wi = -d, wo = l: p = (1 - g^2) / (4 pi temp^(3/2)), temp = 1 + g^2 + 2 g <l, -d>, and dp/dg
+struct hf_medium_phase { double p, dg; };
+__device__ __forceinline__ hf_medium_phase medium_phase(double g, v3 d, const double l[3]) {
+    const double cs = -((double) d.x * l[0] + (double) d.y * l[1] + (double) d.z * l[2]);
+    const double temp = 1.0 + g * g + 2.0 * g * cs, rt = sqrt(temp), q = 1.0 / (12.566370614359172 * temp * rt);
+    return hf_medium_phase{ (1.0 - g * g) * q, (-2.0 * g * temp - 3.0 * (1.0 - g * g) * (g + cs)) * q / temp };
+}
+
+#ifndef HF_MEDIUM_WAVES
+#define HF_MEDIUM_WAVES 4 // resident waves per SIMD: the siblings' walk plus the segment's doubles held across it
+#endif
+__global__ __launch_bounds__(HF_BLOCK, HF_MEDIUM_WAVES) void hf_medium_kernel(hf_medium_args a) {
+    // a lane's sums and bits of every light: its own column, no other lane reads it
+    __shared__ double s_acc[HF_MAX_LIGHTS][HF_BLOCK];
+    __shared__ uint32_t s_bits[HF_MAX_LIGHTS][HF_BLOCK];
+    const hf_dev_field &f = a.f;
+    // hf_sky_kernel's mapping: n < 2^32, the sample index is one register across the walk
+    const size_t i64 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i64 < a.n;
+    const uint32_t i = (uint32_t) i64;
+    const uint32_t ii = in ? i : (uint32_t) (a.n - 1);
+    hf_medium_kargs ka = (hf_medium_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    // the sample's record: read once, held across the loop over the points
+    const v3 o = mk3(ka->o[0][ii], ka->o[1][ii], ka->o[2][ii]);
+    const v3 d = mk3(ka->d[0][ii], ka->d[1][ii], ka->d[2][ii]);
+    const hf_medium_seg s = medium_segment(ka, o, d, ka->t[ii]);
+    const bool elig = in && s.elig;
+#pragma unroll 1
+    for (uint32_t j = 0; j < ka->n_lights; ++j) { s_acc[j][threadIdx.x] = 0.0; s_bits[j][threadIdx.x] = 0u; }
+    // wave-uniform: a batch without an eligible sample draws nothing; an eligible sample is traced towards every light
+    // that shines in (the host's decision), so no (k, j) of such a batch is without a traced lane
+    if (__ballot(elig) != 0ull) {
+        uint32_t id;
+        {
+            const uint32_t *ray_id = ka->ray_id;
+            id = ray_id ? ray_id[ii] : ii;
+        }
+        const double av = medium_a(ka->sigma_t, s.S);
+#pragma unroll 1
+        for (uint32_t k = 0;; ++k) { // wave-uniform loop, the lanes predicated inside
+            asm volatile("" : "+s"(ka)); // opaque per point: the kernarg loads stay inside the loop
+            double xi;
+            const double tau = medium_tau(ka->seed, k, id, av, xi);
+            const v3 ro = medium_point(o, d, s.u_in + tau / ka->sigma_t);
+            const double depth = ka->sigma_t * s.D - tau * s.c; // sigma_t x the depth of point k below the top
+#pragma unroll 1
+            for (uint32_t j = 0;; ++j) { // wave-uniform
+                asm volatile("" : "+s"(ka));
+                if ((ka->on >> j) & 1u) {
+                    const v3 lf = mk3(ka->L[j].lf[0], ka->L[j].lf[1], ka->L[j].lf[2]);
+                    hf_hit best;
+                    light_walk<true>(&ka->f, f, ro, lf, elig, best);
+                    if (elig && !best.hit) {
+                        s_bits[j][threadIdx.x] |= 1u << k;
+                        s_acc[j][threadIdx.x] += exp(-(depth * ka->inv_nu[j])); // in k order
+                    }
+                }
+                if (j + 1u >= ka->n_lights) break;
+            }
+            if (k + 1u >= ka->num_steps) break;
+        }
+    }
+    // (the output pointers: loaded here, not before the walk)
+    hf_medium_kargs ko = (hf_medium_kargs) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ko));
+    double scale = 0.0; // weight albedo a / K
+    if (elig) {
+        const float *weight = ko->weight;
+        scale = ko->albedo * medium_a(ko->sigma_t, s.S) / (double) ko->num_steps;
+        if (weight) scale *= (double) weight[i];
+    }
+#pragma unroll 1
+    for (uint32_t j = 0; j < ko->n_lights; ++j) { // wave-uniform
+        const uint32_t bits = s_bits[j][threadIdx.x];
+        float val = 0.f;
+        if (bits) { // (a bit: eligible, in range)
+            const double l[3] = { ko->L[j].l[0], ko->L[j].l[1], ko->L[j].l[2] };
+            val = (float) (scale * medium_phase(ko->g, d, l).p * ko->L[j].ce * s_acc[j][threadIdx.x]);
+        }
+        float *value = ko->value;
+        if (in && value) value[(size_t) j * ko->n + i] = val;
+        uint32_t *vis_bits = ko->vis_bits;
+        if (in && vis_bits) vis_bits[(size_t) j * ko->n + i] = bits;
+        float *image = ko->image;
+        if (image) { // the film of light j: hf_directional_lighting's layout, J images of n / spp
+            const uint32_t spp = ko->spp, g = spp < 64u ? spp : 64u;
+            film_pixel(image, val, j, ko->n / spp, i, spp, in, (spp & (spp - 1u)) == 0u, g, 1.0f / (float) spp, i);
+        }
+    }
+}
+
+// shadow ray a.k of every sample towards ONE light (L[0]), materialised: what hf_medium_kernel traces for it, bit for
+// bit (an untraced lane: a zero origin and direction, maxt = -1)
+__global__ __launch_bounds__(HF_BLOCK) void hf_medium_rays_kernel(hf_medium_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const v3 o = mk3(a.o[0][i], a.o[1][i], a.o[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    const hf_medium_seg s = medium_segment(&a, o, d, a.t[i]);
+    const bool traced = s.elig && (a.on & 1u);
+    v3 ro = mk3(0.f, 0.f, 0.f), w = ro;
+    if (traced) {
+        double xi;
+        const double tau = medium_tau(a.seed, a.k, light_id(a, i), medium_a(a.sigma_t, s.S), xi);
+        ro = medium_point(o, d, s.u_in + tau / a.sigma_t);
+        w = mk3(a.L[0].lf[0], a.L[0].lf[1], a.L[0].lf[2]);
+    }
+    light_store_ray(a, i, ro, w, traced);
+}
+
+// What the adjoint and the tangent form of sample i: the segment, a and its two partial derivatives, and per light the
+// sums over the points whose bit is set, A0 = sum exp(-x_k) and A1 = sum exp(-x_k) xi_k / (1 - xi_k a) (d tau_k / d a).
+// With T = A0 / K and the bits and branches held:
+//   value = w albedo a p E T,   dT = -(D dsigma A0 - c da A1) / (K nu),   da = a_S dS + a_sigma dsigma
+struct hf_medium_lane {
+    hf_medium_seg s;
+    double av, a_S, a_sigma;
+    double A0[HF_MAX_LIGHTS], A1[HF_MAX_LIGHTS];
+    uint32_t any;
+};
+// J: the lights whose sums are formed are [j0, j0 + J), a compile-time count (the arrays stay in registers)
+template <int J>
+__device__ __forceinline__ void medium_lane(const hf_medium_args &a, size_t i, v3 d, uint32_t j0, const uint32_t bits[J],
+                                            hf_medium_lane &q) {
+    q.any = 0u;
+#pragma unroll
+    for (int j = 0; j < J; ++j) { q.A0[j] = 0.0; q.A1[j] = 0.0; q.any |= bits[j]; }
+    if (!q.any) return;
+    const double S = q.s.S, eS = exp(-a.sigma_t * S);
+    q.av = medium_a(a.sigma_t, S);
+    q.a_S = a.sigma_t * eS;
+    q.a_sigma = S < __builtin_inf() ? S * eS : 0.0;
+    const uint32_t id = light_id(a, i);
+#pragma unroll 1
+    for (uint32_t k = 0; k < a.num_steps; ++k) {
+        if (!((q.any >> k) & 1u)) continue;
+        double xi;
+        const double tau = medium_tau(a.seed, k, id, q.av, xi);
+        const double r = xi / (1.0 - xi * q.av), depth = a.sigma_t * q.s.D - tau * q.s.c;
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+            if ((bits[j] >> k) & 1u) {
+                const double e = exp(-(depth * a.inv_nu[j0 + j]));
+                q.A0[j] += e; q.A1[j] += e * r;
+            }
+    }
+}
+// the upstream of light j's value of sample i: grad_image[j][i / spp] / spp + grad_value[j][i] (NULL: zero), in double
+__device__ __forceinline__ double medium_value_seed(const hf_medium_args &a, uint32_t j, size_t i) {
+    return (a.gimg ? (double) a.gimg[(size_t) j * (a.n / a.spp) + i / a.spp] / (double) a.spp : 0.0) +
+           (a.gvalue ? (double) a.gvalue[(size_t) j * a.n + i] : 0.0);
+}
+
+// Reverse mode of hf_medium_kernel with respect to weight, t, sigma_t, albedo, g and every light's irradiance: nothing is
+// traced, the points are drawn again and the bits read.  One lane per sample across a grid-stride loop: grad_weight and
+// grad_t overwritten, the lights summed in light order in double and rounded once, exact zeros where no bit is set; the
+// HF_MEDIUM_SUMS reduced numbers kept per lane in double and reduced as the sensor's 13: no atomics.
+#define HF_MEDIUM_SUMS (HF_MEDIUM_PARAMS + HF_MAX_LIGHTS)
+__global__ __launch_bounds__(HF_BLOCK) void hf_medium_adjoint_kernel(hf_medium_args a) {
+    double M[HF_MEDIUM_SUMS];
+#pragma unroll
+    for (int j = 0; j < HF_MEDIUM_SUMS; ++j) M[j] = 0.0;
+    const double inv_K = 1.0 / (double) a.num_steps;
+    for (size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x; i < a.n; i += (size_t) gridDim.x * HF_BLOCK) {
+        const v3 o = mk3(a.o[0][i], a.o[1][i], a.o[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+        hf_medium_lane q;
+        q.s = medium_segment(&a, o, d, a.t[i]);
+        double gw = 0.0, ga = 0.0; // dL/dweight; dL/da
+        uint32_t bits[HF_MAX_LIGHTS];
+#pragma unroll
+        for (int j = 0; j < HF_MAX_LIGHTS; ++j)
+            bits[j] = (q.s.elig && (uint32_t) j < a.n_lights && ((a.on >> j) & 1u)) ? a.vis_bits[(size_t) j * a.n + i] : 0u;
+        medium_lane<HF_MAX_LIGHTS>(a, i, d, 0u, bits, q);
+        if (q.any) {
+            const double w = a.weight ? (double) a.weight[i] : 1.0;
+#pragma unroll
+            for (int j = 0; j < HF_MAX_LIGHTS; ++j) {
+                if (!bits[j]) continue;
+                const hf_medium_phase ph = medium_phase(a.g, d, a.L[j].l);
+                const double gj = medium_value_seed(a, j, i), E = a.L[j].ce;
+                const double T = q.A0[j] * inv_K, aT = q.av * T, gwa = gj * w * aT;
+                gw += gj * a.albedo * ph.p * E * aT;
+                ga += gj * w * a.albedo * ph.p * E * (T + q.av * q.s.c * q.A1[j] * a.inv_nu[j] * inv_K);
+                M[0] -= gj * w * a.albedo * ph.p * E * q.av * (q.s.D * q.A0[j] * a.inv_nu[j] * inv_K);
+                M[1] += gwa * ph.p * E;
+                M[2] += gwa * a.albedo * E * ph.dg;
+                M[HF_MEDIUM_PARAMS + j] += gwa * a.albedo * ph.p;
+            }
+            M[0] += ga * q.a_sigma;
+        }
+        if (a.gw) a.gw[i] = (float) gw;
+        if (a.gt) a.gt[i] = (q.any && q.s.at_t) ? (float) (ga * q.a_S) : 0.f;
+    }
+    if (a.slab) sensor_block_store<HF_MEDIUM_SUMS>(M, a.slab); // (launch-uniform: grad_params is wanted)
+}
+// one block: g_params[j] += column j of the slab's rows, j < count
+__global__ __launch_bounds__(HF_BLOCK) void hf_medium_sum_kernel(const double *__restrict__ slab, uint32_t rows, uint32_t count,
+                                                                  float *__restrict__ g_params) {
+    const double *const sum = sensor_slab_sums<HF_MEDIUM_SUMS>(slab, rows);
+    const uint32_t t = threadIdx.x;
+    if (t < count) g_params[t] += (float) sum[t];
+}
+size_t hf_medium_slab_doubles(void) { return (size_t) HF_XFORM_GRID_CAP * HF_MEDIUM_SUMS; }
+
+// forward mode, the transpose of the above: the tangent of light j's value of sample i for tangents dw of weight, dt of
+// t and d_params (NULL: zero)
+__device__ __forceinline__ float medium_tangent_value(const hf_medium_args &a, uint32_t j, size_t i) {
+    if (!((a.on >> j) & 1u)) return 0.f;
+    uint32_t bits[1] = { a.vis_bits[(size_t) j * a.n + i] };
+    if (!bits[0]) return 0.f;
+    const v3 o = mk3(a.o[0][i], a.o[1][i], a.o[2][i]), d = mk3(a.d[0][i], a.d[1][i], a.d[2][i]);
+    hf_medium_lane q;
+    q.s = medium_segment(&a, o, d, a.t[i]);
+    if (!q.s.elig) return 0.f;
+    medium_lane<1>(a, i, d, j, bits, q);
+    const double *l = a.L[j].l;
+    const hf_medium_phase ph = medium_phase(a.g, d, l);
+    const float *dp = a.d_params;
+    const double dsigma = dp ? (double) dp[0] : 0.0, dalbedo = dp ? (double) dp[1] : 0.0, dg = dp ? (double) dp[2] : 0.0;
+    const double dE = dp ? (double) dp[HF_MEDIUM_PARAMS + j] : 0.0;
+    const double w = a.weight ? (double) a.weight[i] : 1.0, dw = a.dw ? (double) a.dw[i] : 0.0;
+    const double dS = (a.dt && q.s.at_t) ? (double) a.dt[i] : 0.0;
+    const double da = q.a_S * dS + q.a_sigma * dsigma;
+    const double inv_K = 1.0 / (double) a.num_steps, E = a.L[j].ce;
+    const double T = q.A0[0] * inv_K;
+    const double dT = -(q.s.D * dsigma * q.A0[0] - q.s.c * da * q.A1[0]) * a.inv_nu[j] * inv_K;
+    const double pE = ph.p * E;
+    return (float) ((dw * a.albedo + w * dalbedo) * q.av * pE * T + w * a.albedo * (da * pE * T + q.av * (ph.dg * dg * E + ph.p * dE) * T +
+                                                                                    q.av * pE * dT));
+}
+// light_tangent_image with a loop over the lights (hf_directional_tangent_kernel's shell)
+template <bool PIXEL>
+__global__ __launch_bounds__(HF_BLOCK) void hf_medium_tangent_kernel(hf_medium_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const uint32_t spp = a.spp;
+    const size_t npix = a.n / spp;
+    if (PIXEL) {
+        if (i >= npix) return;
+#pragma unroll 1
+        for (uint32_t j = 0; j < a.n_lights; ++j) {
+            float c = 0.f;
+            for (uint32_t s = 0; s < spp; ++s) {
+                const float dv = medium_tangent_value(a, j, i * spp + s);
+                if (a.value) a.value[(size_t) j * a.n + i * spp + s] = dv;
+                c += dv;
+            }
+            a.image[(size_t) j * npix + i] = c * (1.0f / (float) spp);
+        }
+    } else {
+        const bool in = i < a.n;
+#pragma unroll 1
+        for (uint32_t j = 0; j < a.n_lights; ++j) { // wave-uniform
+            const float c = medium_tangent_value(a, j, in ? i : a.n - 1);
+            if (in && a.value) a.value[(size_t) j * a.n + i] = c;
+            if (a.image) film_pixel(a.image, in ? c : 0.f, j, npix, i, spp, in, true, spp, 1.0f / (float) spp);
+        }
+    }
+}
+
+// mode 0: forward, 1: adjoint (and, where grad_params is wanted, the sum of the blocks' rows, one block), 2: tangent,
+// 3: rays
+void hf_launch_medium(int mode, const hf_medium_args &a, hipStream_t stream) {
+    if (mode == 1) {
+        if (a.n == 0) return;
+        const int grid = grid_for(a.n, HF_XFORM_GRID_CAP); // the slab holds HF_XFORM_GRID_CAP rows
+        hipLaunchKernelGGL(hf_medium_adjoint_kernel, dim3(grid), dim3(HF_BLOCK), 0, stream, a);
+        if (a.slab)
+            hipLaunchKernelGGL(hf_medium_sum_kernel, dim3(1), dim3(HF_BLOCK), 0, stream, a.slab, (uint32_t) grid,
+                               (uint32_t) HF_MEDIUM_PARAMS + a.n_lights, a.g_params);
+        return;
+    }
+    launch_light(mode, a, a.n_lights, stream, hf_medium_kernel, hf_medium_adjoint_kernel, hf_medium_tangent_kernel<false>,
+                 hf_medium_tangent_kernel<true>, hf_medium_rays_kernel);
+}

@@ -437,6 +437,36 @@ struct hf_specular_args {
 // mode 0: forward, 1: adjoint (two launches where grad_lights is wanted), 2: tangent
 void hf_launch_specular(int mode, const hf_specular_args &a, hipStream_t stream);
 size_t hf_specular_slab_doubles(uint32_t n_lights);
+// ---- homogeneous medium (hf_medium_rays, hf_medium_lighting / _adjoint / _tangent): single scattering in
+// the half space below a top plane under the directional rig, the shadow rays of 1..32 points of every primary ray
+// traced in the kernel.  The lights are hf_directional_light_dev with ce = irradiance; every constant formed on the host
+// in double ----
+struct hf_medium_args {
+    hf_dev_field f;                          // forward only (the walk)
+    size_t n;
+    uint32_t spp, n_lights, num_steps, seed;
+    uint32_t k;                              // rays: the point that is materialised (of light 0)
+    uint32_t on;                             // bit j: light j shines into the medium, nu_j > 0
+    double N[3], top_o[3];                   // the unit top normal and a point of the top plane: h = <o - top_o, N>
+    double sigma_t, albedo, g;
+    double inv_nu[HF_MAX_LIGHTS];            // 1 / <l_j, N> (0 where the light does not shine in)
+    hf_directional_light_dev L[HF_MAX_LIGHTS]; // the first n_lights are read
+    const float *o[3], *d[3], *t, *weight;
+    const uint32_t *ray_id;
+    float *image, *value;                    // forward: written, J rows each (NULL: not wanted); tangent: dimage, dvalue
+    uint32_t *vis_bits;                      // forward: written, J rows (NULL: not wanted); adjoint, tangent: read; bit k: point k
+    float *out_o[3], *out_d[3], *out_maxt;   // rays
+    const float *gimg, *gvalue;              // adjoint inputs, J rows each (NULL: zero)
+    float *gw, *gt;                          // adjoint outputs (NULL: not wanted)
+    double *slab;                            // adjoint: HF_MEDIUM_SUMS doubles per block (NULL: grad_params is not wanted)
+    float *g_params;                         // adjoint output [HF_MEDIUM_PARAMS + n_lights], accumulated
+    const float *dw, *dt;                    // tangent inputs (NULL: zero)
+    const float *d_params;                   // tangent input [HF_MEDIUM_PARAMS + n_lights] device floats (NULL: zero)
+};
+// mode 0: forward, 1: adjoint (two launches where grad_params is wanted), 2: tangent, 3: rays.  The forward launch is
+// hf_launch_sky's: the per-lane any-hit walk, no work counter, no scratch block
+void hf_launch_medium(int mode, const hf_medium_args &a, hipStream_t stream);
+size_t hf_medium_slab_doubles(void);
 // the sampling table of a map: three launches (row sums of the cell means, conditional rows, marginal + header)
 void hf_launch_envmap_build(uint32_t W, uint32_t H, const float *data, float u, float *table, hipStream_t stream);
 // ---- bounce lighting (hf_bounce_rays, hf_bounce_lighting / _adjoint / _tangent): the one argument of its kernels ----
