@@ -13,6 +13,11 @@ projector row (tests/projector_ref.py, both projectors, that test's three varian
 reflect row (tests/reflect_ref.py, the oblique view, eta 0 and 1.5, two maps) in the measures of tests/test_gpu_reflect.py, the
 refract row (tests/refract_ref.py, the caustic row's runs on a textured receiver, two variants of absorption, texture and wrap)
 and the glossy row (tests/glossy_ref.py, 4 draws, two roughness rows and maps, eta 0 and 1.5) in those of their own tests.
+The specular row (tests/specular_ref.py, the steep view, the directional row's rig and visibility, eta 1.5) is measured in
+specular_ref.errors() per roughness row ("row" on every case, "sharp" on affine with smooth normals: its maxima are a
+dict per roughness row); of the medium row (tests/medium_ref.py, the three media of row_scenes.MEDIA carried to world,
+4 points per sample) only the origin of a shadow ray has a float32 restatement: the measure of scripts/medium_f32_error.py,
+per (scene, medium), with the populations tests/test_row_scenes.py asserts -- its values keep the row's own rule.
 Per triple: the populations tests/test_row_scenes.py asserts and the error of every quantity (the rows' own errors());
 last, per row, the maxima over the triples.  The GPU is allowed four times the maxima (tests/test_gpu_row_scenes.py F32).
 usage: python scripts/row_scenes_f32_error.py [--out profiles/row_scenes/f32_error.json]"""
@@ -212,6 +217,44 @@ for name, face_normals in RS.CASES:
 ks = [k for k in e if k.startswith("err_")]
 out["glossy"]["maxima"] = {k: max(v[k] for v in out["glossy"].values()) for k in ks}
 print("glossy maxima", json.dumps(out["glossy"]["maxima"]))
+# ---- the specular row: specular_ref.errors() per roughness row, on the oracle's records and the directional row's visibility
+import specular_ref as SP  # noqa: E402
+out["specular"] = {}
+for name, face_normals in RS.CASES:
+    sc = RS.scene(name, "steep")
+    m = RS.specular_model(sc, O, face_normals)
+    RS.specular_conditions(sc, m.pop, m.lit)
+    x = SP.inputs(sc.n, RS.SPP, len(m.lights))
+    e = {"hits": int(np.isfinite(m.t).sum()), "eligible": int(m.pop.eligible.sum()), "unsure_union": m.pop.unsure_share, "lit": m.lit}
+    for akind in RS.specular_kinds(name, face_normals):
+        e[akind] = {}
+        for weighted in (True, False):
+            r64, r32 = (RS.specular_evaluate(m.lights, m.rec, sc.rays[3:6], x, akind, m.vis, dt, weighted) for dt in (np.float64, np.float32))
+            for k, err in SP.errors(r32, r64).items():
+                e[akind]["err_" + k] = max(e[akind].get("err_" + k, 0.0), err)
+        e[akind]["value_max"] = float(np.abs(r64.value).max())
+    key = "%s, %s normals" % (name, "face" if face_normals else "smooth")
+    out["specular"][key] = e
+    print("specular", key, json.dumps(e), flush=True)
+out["specular"]["maxima"] = {akind: {k: max(v[akind][k] for v in out["specular"].values() if akind in v) for k in e["row"] if k.startswith("err_")}
+                             for akind in ("row", "sharp")}
+print("specular maxima", json.dumps(out["specular"]["maxima"]))
+# ---- the medium row: scripts/medium_f32_error.py's measure of an origin (the point formed as the kernel forms it, the
+# distance rounded to float32 and one fused multiply-add per component, against the exact o + u_k d), every (scene, medium)
+out["medium"] = {}
+for name in RS.SCENES:
+    for mname in RS.MEDIUM_NAMES:
+        sc = RS.scene(name, RS.MEDIA[mname]["view"])
+        r = RS.medium_model(sc, O, mname)
+        RS.medium_conditions(sc, r)
+        e = dict(r.counts)
+        e.update(lights=r.shares, nu=[float(v) for v in r.nu], max_coordinate=float(np.abs(r.origins64[:, :, r.q.elig]).max()),
+                 err_origin=float(np.abs(r.origins32 - r.origins64)[:, :, r.q.elig].max()))
+        key = "%s, %s" % (name, mname)
+        out["medium"][key] = e
+        print("medium", key, json.dumps(e), flush=True)
+out["medium"]["maxima"] = {"err_origin": max(v["err_origin"] for v in out["medium"].values())}
+print("medium maxima", json.dumps(out["medium"]["maxima"]))
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(out, open(a.out, "w"), indent=1)

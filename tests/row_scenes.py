@@ -18,7 +18,10 @@ Rows: `directional` (rays with maxt = inf, the steep view), `spot` (rays that EN
 `projector` (rays that END at the projector, the steep view) and `reflect` (rays with maxt = inf whose direction and masks
 depend on the view, the oblique view), `refract` (the caustic row's rays onto a textured receiver) and `glossy` (4 mirror
 rays per sample about drawn microfacet normals, the oblique view); the sections of the last six are at the end of this
-file.  All eight rows that came after the environment map are here.  The
+file.  All eight rows that came after the environment map are here, and the two that came after the normal map:
+`specular` (the directional row's byte, masks and cosines from sh_n and -d, the steep view) and `medium` (shadow rays that
+START in free space, on the primary ray, under a world-space top plane; the steep view and, for the medium that holds the
+camera, the oblique one): ten rows, the last two sections of this file.  The
 spot rig here is spot_ref.RIG without `above` -- on `affine` it put the union of the samples that rounding may decide over
 row_helpers.UNSURE_CAP -- and with `inside` in its place: a point-like cone whose origin lies INSIDE the field's object-space
 bounding box, over the lowest vertex of the field, so that shadow rays end inside the bound: replacing their maxt by +inf
@@ -172,8 +175,17 @@ F32 = {"directional": {"image": 1.45e-7, "value": 1.84e-7, "dimage": 1.24e-7, "d
                    "grad_p": 1.76e-6, "grad_weight": 7.49e-7, "pos": 6.05e-5},
        # (tests/test_gpu_glossy.py's measures; ray_d, ray_h: the directions and microfacet normals, relative L2)
        "glossy": {"value": 2.44e-4, "image": 6.13e-5, "grad_data": 6.20e-6, "dimage": 1.60e-5, "dvalue": 1.64e-5, "grad_sh_n": 1.26e-5,
-                  "grad_weight": 3.76e-6, "grad_alpha": 2.28e-5, "ray_d": 8.49e-7, "ray_h": 4.24e-7}}
-TOL = {row: {k: 4 * v for k, v in d.items()} for row, d in F32.items()}
+                  "grad_weight": 3.76e-6, "grad_alpha": 2.28e-5, "ray_d": 8.49e-7, "ray_h": 4.24e-7},
+       # (specular_ref.errors(), per roughness row as in tests/test_gpu_specular.py: float32 cancels in s^2 / a^2 + c_h^2,
+       # which the kernels form in double)
+       "specular": {"row": {"image": 3.66e-5, "value": 9.73e-5, "dimage": 8.55e-5, "dvalue": 8.85e-5, "grad_sh_n": 1.11e-4,
+                            "grad_alpha": 1.62e-4, "grad4": 4.20e-5, "grad_weight": 5.87e-5},
+                    "sharp": {"image": 6.01e-4, "value": 6.89e-4, "dimage": 2.58e-4, "dvalue": 2.64e-4, "grad_sh_n": 9.98e-4,
+                              "grad_alpha": 1.78e-3, "grad4": 1.05e-3, "grad_weight": 6.89e-4}},
+       # (scripts/medium_f32_error.py's measure: the largest distance, per component, of the origin formed as the kernel
+       # forms it from the exact point; values, gradients and tangents keep the row's own rule, MEDIUM_RTOL and MEDIUM_ATOL)
+       "medium": {"origin": 5.76e-7}}
+TOL = {row: {k: ({a: 4 * b for a, b in v.items()} if isinstance(v, dict) else 4 * v) for k, v in d.items()} for row, d in F32.items()}
 # the relative L2 error the rows' own files allow their chain to the heights (tests/test_gpu_spot.py, test_gpu_directional.py)
 CHAIN = 4 * 3.62e-7 + 1e-5
 
@@ -798,3 +810,182 @@ def glossy_ray_errors(d, h, r, k, lanes):
     error of the ray directions and microfacet normals"""
     return (((d - r.wo[k])[:, lanes] ** 2).sum(), (r.wo[k][:, lanes] ** 2).sum(), ((h - r.h[k])[:, lanes] ** 2).sum(),
             (r.h[k][:, lanes] ** 2).sum())
+
+
+# ---- the specular row: traces nothing; the directional row's byte, masks and cosines from sh_n and -d, the steep view ---
+# The lights are rig("directional", sc) and the byte is the directional row's on the same scene.  What the scenes add over
+# tests/test_gpu_specular.py: sh_n changes sign under flip_normals (an unflipped one zeroes every sample), -d and l are
+# world-space directions (the object-space ones give another half vector), and the chain to the heights runs through the
+# flat or smooth normal's adjoint under to_world.  Roughness: specular_ref.alpha_row("row") on every case and "sharp" on
+# SPECULAR_SHARP_ON as well; eta = specular_ref.ETA; the inputs are specular_ref.inputs.  No sample is left out of a
+# comparison: every mask comes from the byte and from cosines both sides form in double from the same float32 rows.
+SPECULAR_SHARP_ON = ("affine", False)
+SPECULAR_BRIGHT = ("zenith", "high", "unnorm")      # the lights under which more than SPECULAR_BRIGHT_SHARE of the samples
+SPECULAR_BRIGHT_SHARE = 0.3                         # carry a highlight (tests/test_gpu_specular.py's floor)
+
+
+def specular_kinds(name, face_normals):
+    return ("row", "sharp") if (name, face_normals) == SPECULAR_SHARP_ON else ("row",)
+
+
+def specular_lit(names, value):
+    """{light: the share of samples with a value > 0} of a [K, n] value under the "row" roughness"""
+    return {k: float((np.asarray(value)[j] > 0).mean()) for j, k in enumerate(names)}
+
+
+def specular_evaluate(lights, rec, d, x, akind, vis, dtype=np.float64, weighted=True):
+    """forward, tangent and adjoint of the restatement on the records rec under x = specular_ref.inputs(): the namespace
+    specular_ref.errors takes"""
+    import specular_ref as SP
+    return SP.evaluate(lights, rec["sh_n"], d, x, SP.alpha_row(akind, rec["sh_n"].shape[1]), SP.ETA, vis, SPP, dtype, weighted)
+
+
+def specular_model(sc, oracle, face_normals):
+    """model("directional") of the scene with m.lit on it: specular_lit of the restatement's weighted value, the "row" roughness"""
+    import specular_ref as SP
+    m = model("directional", sc, oracle, face_normals)
+    x = SP.inputs(sc.n, SPP, len(m.lights))
+    _, value = SP.forward(m.lights, m.rec["sh_n"], sc.rays[3:6], x.w, SP.alpha_row("row", sc.n), SP.ETA, m.vis, SPP)
+    m.lit = specular_lit(m.names, value)
+    return m
+
+
+def specular_conditions(sc, pop, lit):
+    """what makes (specular, scene) a test: the directional row's conditions as they are, a highlight on more than
+    SPECULAR_BRIGHT_SHARE of the samples under the three high lights and on some sample under every light but `below`"""
+    conditions("directional", sc, pop)
+    for k in SPECULAR_BRIGHT:
+        assert lit[k] > SPECULAR_BRIGHT_SHARE, (sc.name, k, lit)
+    for k, v in lit.items():
+        assert v > 0 or k == "below", (sc.name, k, lit)
+
+
+def object_direction(sc, d):
+    """[3, n]: the unit object-space direction of the world directions d (what a kernel that forgot to_world would use)"""
+    q = np.linalg.inv(np.asarray(sc.to_world, np.float64)[:, :3]) @ np.asarray(d, np.float64)
+    return q / np.linalg.norm(q, axis=0)
+
+
+# ---- the medium row: shadow rays that START in free space, on the primary ray, under a world-space top plane -------------
+# Three media, defined once in OBJECT space and carried to world: the top origin as a point (for the view from below object
+# z becomes max_height - z: the mirror image about the middle of the slab), the top normal as a COVECTOR, through the
+# inverse transpose of to_world's linear part, as lighting_scenes.lights carries its lights (object z negated first for
+# the view from below).  Under common.affine(4) and common.mirror_shear() a normal carried as a vector is another plane.
+# The lights are rig("directional", sc), carried as vectors: <l, N> keeps its object-space sign, so `below` shines into no
+# medium and `graze` not into `tilted`.
+#   skim    a layer that just covers the relief (object z = max_height): the points lie close over it, raking lights
+#           shadow them; the steep view, camera above the plane (u_in > 0, D = 0)
+#   tilted  the plane through object (0, 0, 1.15 max_height) with the normal (0.3, -0.2, 2.0); the steep view
+#   inside  object z = 3.0 (absolute), over the camera of the oblique view (u_in = 0, D > 0): about a quarter of that view's
+#           rays miss the terrain and go on beside and below the sheet, so shadow rays meet it from outside and from underneath
+MEDIUM_K, MEDIUM_SEED = 4, 11
+MEDIA = {"skim": dict(view="steep", z=1.0, relative=True, normal=(0.0, 0.0, 1.0), sigma_t=1.0, albedo=0.75, g=0.3),
+         "tilted": dict(view="steep", z=1.15, relative=True, normal=(0.3, -0.2, 2.0), sigma_t=1.0, albedo=0.6, g=0.5),
+         "inside": dict(view="oblique", z=3.0, relative=False, normal=(0.0, 0.0, 1.0), sigma_t=0.5, albedo=0.9, g=-0.2)}
+MEDIUM_NAMES = tuple(MEDIA)
+MEDIUM_RTOL, MEDIUM_ATOL = 1e-5, 1e-7          # tests/test_gpu_medium.py's rule; the atol times max(1, largest |reference|)
+
+
+def medium_plane(sc, mname, covector=True):
+    """(top_origin, top_normal) of a medium in world space; covector=False carries the normal as a vector: the mistake the
+    scenes must tell apart"""
+    spec = MEDIA[mname]
+    A = np.asarray(sc.to_world, np.float64)
+    z = spec["z"] * sc.max_height if spec["relative"] else spec["z"]
+    o, nrm = np.array((0.0, 0.0, z)), np.array(spec["normal"], np.float64)
+    if sc.below:
+        o[2], nrm[2] = sc.max_height - z, -nrm[2]
+    return A[:, :3] @ o + A[:, 3], (np.linalg.inv(A[:, :3]).T if covector else A[:, :3]) @ nrm
+
+
+def medium_of(sc, mname, covector=True):
+    """the restatement's medium (medium_ref.medium) of the scene"""
+    import medium_ref as MR
+    spec = MEDIA[mname]
+    o, nrm = medium_plane(sc, mname, covector)
+    return MR.medium(spec["sigma_t"], spec["albedo"], spec["g"], o, nrm)
+
+
+def medium_run(sc, mname, o, d, t, field, words=None, origins=None):
+    """one medium on the primary rays (o, d, t) under the rig: the restatement's segment and masks, the K float32 origins
+    (`origins` [K, 3, n] = None: the restatement's, formed as the kernel forms them), the oracle's answer on those rays
+    (`words` [J, n] = None: the visibility IS the oracle's) and the counts the conditions are about"""
+    import medium_ref as MR
+    r = types.SimpleNamespace(mname=mname, M=medium_of(sc, mname), K=MEDIUM_K, field=field)
+    r.names, r.lights = rig("directional", sc)
+    J, n = len(r.lights), len(t)
+    o, d, t = np.asarray(o, np.float64), np.asarray(d, np.float64), np.asarray(t)
+    r.o, r.d, r.t = o, d, t
+    r.q = MR.segment(r.M, o, d, t)
+    r.hit = np.isfinite(t)
+    r.nu = np.array([MR.nu(r.M, L) for L in r.lights])
+    r.shines = r.nu > 0
+    first = r.lights[int(np.argmax(r.shines))]
+    r.origins64 = np.stack([MR.rays(r.M, first, o, d, t, k, MEDIUM_SEED)[0] for k in range(MEDIUM_K)])
+    r.origins32 = np.stack([MR.rays(r.M, first, o, d, t, k, MEDIUM_SEED, dtype=np.float32)[0] for k in range(MEDIUM_K)])
+    r.origins = r.origins32 if origins is None else np.asarray(origins, np.float64)
+    with np.errstate(invalid="ignore"):
+        p = o + np.where(r.hit, t, 0.0).astype(np.float64)[None] * d
+        r.near = (r.q.elig & r.hit)[None] & (np.sqrt(((r.origins - p[None]) ** 2).sum(1)) < MR.spawn_offset(p)[None])
+    r.p = p
+    r.traced = r.shines[:, None] & r.q.elig[None]                                   # [J, n]: the same for every k
+    r.oracle = np.zeros((J, MEDIUM_K, n), bool)                                     # visible by the oracle's ray_test
+    for j, L in enumerate(r.lights):
+        if not r.shines[j]:
+            continue
+        lf = MR.unit(L)[0].astype(np.float32)
+        tr = r.traced[j]
+        for k in range(MEDIUM_K):
+            r7 = np.concatenate([r.origins[k][:, tr], np.repeat(lf[:, None], int(tr.sum()), 1), np.full((1, int(tr.sum())), np.inf)])
+            r.oracle[j, k, tr] = ~field.ray_test(r7.astype(np.float32)).astype(bool)
+    r.bits = r.oracle if words is None else np.stack([MR.unpack(w, MEDIUM_K) for w in np.asarray(words)])
+    r.words = np.stack([MR.pack(b) for b in r.bits])
+    occ = r.traced[:, None] & ~r.bits                                               # [J, K, n]
+    r.shares = {}
+    for j, name in enumerate(r.names):
+        tr = MEDIUM_K * int(r.traced[j].sum())
+        r.shares[name] = {"traced": tr, "occluded": int(occ[j].sum()), "occluded_of_traced": float(occ[j].sum() / tr) if tr else 0.0,
+                          "occluded_on_misses": int(occ[j][:, ~r.hit].sum())}
+    r.counts = {"hit": float(r.hit.mean()), "eligible": float(r.q.elig.mean()), "near": float(r.near.mean()),
+                "near_lanes": int(r.near.sum())}
+    return r
+
+
+def medium_conditions(sc, r):
+    """what makes (medium, scene) a test; asserted before anything is compared.  The cap on the lanes left out of the
+    comparison with the oracle is row_helpers.UNSURE_CAP and is never raised"""
+    c, sh, name = r.counts, r.shares, (sc.name, r.mname)
+    assert c["near"] <= UNSURE_CAP, (name, c)
+    assert 0.05 <= c["hit"] <= 0.95, (name, c)
+    assert sh["below"]["traced"] == 0 and (r.mname != "tilted" or sh["graze"]["traced"] == 0), (name, sh)
+    lit = {k: v for k, v in sh.items() if v["traced"]}
+    assert len(lit) >= 6 and all(0 < v["occluded"] < v["traced"] for v in lit.values()), (name, sh)   # both outcomes
+    assert any(v["occluded_of_traced"] <= 0.03 for v in lit.values()), (name, sh)
+    if r.mname == "inside":
+        assert (r.q.u_in == 0).all() and (r.q.D > 0).all(), name
+        assert all(v["occluded_on_misses"] >= 40 for v in lit.values()), (name, sh)
+    else:
+        assert (r.q.u_in > 0).all(), name
+        mixed = [k for k, v in lit.items() if v["traced"] >= 1000 and 0.08 <= v["occluded_of_traced"] <= 0.9]
+        assert len(mixed) >= 2, (name, mixed, sh)
+
+
+def medium_describe(r):
+    return "hit %.2f eligible %.2f near %.2e (%d) | " % (r.counts["hit"], r.counts["eligible"], r.counts["near"], r.counts["near_lanes"]) \
+        + ", ".join("%s %d/%.3f/%d" % (k, v["traced"], v["occluded_of_traced"], v["occluded_on_misses"]) for k, v in r.shares.items())
+
+
+def medium_model(sc, oracle, mname):
+    """(the scene's medium through the oracle and the restatement only, the oracle's field): the scene must be of the
+    medium's view"""
+    assert sc.view == MEDIA[mname]["view"]
+    f = LS.oracle_field(sc, oracle)
+    t = f.ray_intersect_preliminary(sc.rays)[0]
+    return medium_run(sc, mname, sc.rays[0:3], sc.rays[3:6], t, f)
+
+
+def medium_close(got, ref):
+    """the row's own rule (tests/test_gpu_medium.py): |got - ref| <= rtol |ref| + atol max(1, largest |ref|); returns the
+    largest (|got - ref| - rtol |ref|) / (atol max(1, largest |ref|)): within the rule when <= 1"""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return float((np.abs(got - ref) - MEDIUM_RTOL * np.abs(ref)).max() / (MEDIUM_ATOL * max(1.0, np.abs(ref).max())))

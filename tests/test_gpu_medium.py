@@ -1,5 +1,5 @@
-"""The medium row on the device (hf_medium_rays, hf_medium_lighting, _adjoint, _tangent) against
-tests/medium_ref.py.  The scene: row_helpers.base_scene (sine_heights(96), max_height 0.5, the 64 x 64 x 4 orthographic
+"""The medium row on the device (hf_medium_rays, hf_medium_lighting, _adjoint, _tangent) against tests/medium_ref.py; under to_world, flip_normals and odd grids: tests/test_gpu_row_scenes.py.
+The scene here: row_helpers.base_scene (sine_heights(96), max_height 0.5, the 64 x 64 x 4 orthographic
 wavefront) from medium_ref.ORIGIN plus a second wavefront of the same direction centred over the terrain's +x edge, of
 which most passes beside the terrain (t = inf): 32768 samples, K = 4 points, 131072 shadow rays per light.  Two lights
 (medium_ref.RIG: a raking one and a high one) and three media (medium_ref.MEDIA): top plane z = 1.5 below the camera

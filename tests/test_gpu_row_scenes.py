@@ -1,10 +1,10 @@
-"""The eight lighting rows that came after the environment map -- directional, spot, caustic, refract, rect, projector,
-reflect and glossy (hf_directional_*, hf_spot_*, hf_caustic_*, hf_refract_*, hf_rect_*, hf_projector_*, hf_reflect_*,
-hf_glossy_*) -- on the GPU, on the scenes of tests/row_scenes.py: a general
+"""The ten lighting rows that came after the environment map -- directional, spot, caustic, refract, rect, projector,
+reflect, glossy, specular and medium (hf_directional_*, hf_spot_*, hf_caustic_*, hf_refract_*, hf_rect_*, hf_projector_*,
+hf_reflect_*, hf_glossy_*, hf_specular_*, hf_medium_*) -- on the GPU, on the scenes of tests/row_scenes.py: a general
 affine to_world, a mirror with flip_normals, flip_normals seen from below; rectangular grids that are no power of two,
 2300 samples (partial last wave and workgroup), the rows' rigs carried to world, the spot light `inside` ending its shadow
 rays inside the field's bound, as the rect lamp `side` does; the caustic receiver `cut` crosses the relief.  The rows' own
-files (tests/test_gpu_directional.py, _spot, _caustic, _refract, _rect, _projector, _reflect, _glossy) run on one identity-transformed square
+files (tests/test_gpu_directional.py, _spot, _caustic, _refract, _rect, _projector, _reflect, _glossy, _specular, _medium) run on one identity-transformed square
 field only; guard bands, odd n, NULL pointers and graphs do not depend on the transform and
 stay there.  Everything here goes through the public functions.  The directional and the spot row share the first three
 tests; the other rows have a section each below, with the same letters.  Per (row, scene, shading mode):
@@ -26,7 +26,15 @@ Tolerances of (d) and (e): row_scenes.TOL, four times the float32 error of the r
 on which rounding may decide a mask (a deciding quantity within the row's MARGIN; at most row_helpers.UNSURE_CAP of the
 samples over the union of the lights) are left out of the comparisons; for the spot row so are the lanes within KINK of
 theta = beam under the light concerned, where the slope of the falloff jumps: their upstream gradients are zero and their
-tangents are not compared."""
+tangents are not compared.
+
+The last two sections.  `specular` traces nothing: (d), (e), (g) in specular_ref.errors()' measures with no sample left out,
+its byte the directional row's launch of the same scene, and (f) through ray_intersect -> directional_lighting ->
+specular_lighting.  `medium`, per (case, medium of row_scenes.MEDIA), all eight lights in one launch with 4 points per
+sample: (a) to (g) with the letters above, where (c) leaves out only the lanes whose origin lies within the sky row's spawn
+offset of the primary hit (at most row_helpers.UNSURE_CAP), the origins are held to TOL[medium][origin] and values,
+gradients and tangents to the row's own rule (rtol 1e-5, atol 1e-7 max(1, largest |reference|)); its gradient reaches the
+heights through si.t alone."""
 import math
 import types
 
@@ -38,11 +46,13 @@ import torch.autograd.forward_ad as fwAD
 import caustic_ref as CR
 import film_ref
 import glossy_ref as GL
+import medium_ref as MR
 import projector_ref as PJ
 import rect_ref as AR
 import reflect_ref as RF
 import refract_ref as RR
 import row_scenes as RS
+import specular_ref as SP
 from row_helpers import _cu, _fold, _np, _rel, envmap, leaf_si, transposition_gap
 
 pytestmark = pytest.mark.gpu
@@ -1131,3 +1141,295 @@ def test_glossy_chain_to_the_heights(hf, oracle, name, face_normals):
     print("glossy", name, "face_normals", face_normals, "dL/dheight relative L2 error %.3g / %.3g" % (err, GTOL["grad_sh_n"] + 1e-5),
           "norm", np.linalg.norm(gh))
     assert np.linalg.norm(gh) > 0 and err <= GTOL["grad_sh_n"] + 1e-5, err
+
+
+# ---- the specular row: traces nothing; the directional row's byte, the steep view -----------------------------------------
+STOL = RS.TOL["specular"]
+_SPECULAR = {}
+
+
+def _specular(hf, oracle, name, face_normals):
+    """the directional row's launch of the scene (_rigged: its byte, its lights, its conditions), the roughness rows and the
+    K = 8 specular launch under "row" with a weight; (g) the conditions of tests/test_row_scenes.py on the GPU's own records,
+    byte and values, asserted before anything is compared"""
+    key = (name, face_normals)
+    if key not in _SPECULAR:
+        q = _rigged(hf, oracle, "directional", name, face_normals)
+        sc = q.sc
+        s = types.SimpleNamespace(q=q, sc=sc, x=SP.inputs(sc.n, SPP, q.K), byte=_cu(q.byte))
+        assert np.array_equal(s.x.w, q.x.w)
+        s.alpha = {kind: SP.alpha_row(kind, sc.n) for kind in RS.specular_kinds(name, face_normals)}
+        img, val = hf.specular_lighting(sc.si, sc.ray, q.lights, s.byte, _cu(s.alpha["row"]), eta=SP.ETA, spp=SPP, weight=_cu(s.x.w),
+                                        return_value=True)
+        s.img, s.val = _np(img).copy(), _np(val).copy()
+        s.lit = RS.specular_lit(q.names, s.val)
+        print("specular", name, "face" if face_normals else "smooth", "share of samples with a highlight", {k: round(v, 3) for k, v in s.lit.items()})
+        RS.specular_conditions(sc, q.pop, s.lit)                                    # (g)
+        _SPECULAR[key] = s
+    return _SPECULAR[key]
+
+
+@pytest.mark.parametrize("name,face_normals", RS.CASES)
+def test_specular_values_gradients_and_tangents_against_the_restatement_and_the_transposition_gap(hf, oracle, name, face_normals):
+    """(d), (e), (g): through the public function, backward() and forward_ad, every light's numbers and the roughness row
+    the user's own tensors; specular_ref.errors()' measures, NO sample left out"""
+    s = _specular(hf, oracle, name, face_normals)
+    sc, q, x = s.sc, s.q, s.x
+    K = q.K
+    for kind, alpha in s.alpha.items():
+        tol = STOL[kind]
+        worst = {k: 0.0 for k in tol}
+        for weighted in ((True, False) if kind == "row" else (True,)):
+            si = leaf_si(hf, sc)
+            wt = _cu(x.w).requires_grad_(True) if weighted else None
+            at = _cu(alpha).requires_grad_(True)
+            par = [[_f64(v).requires_grad_(True) for v in (L.to_light, L.irradiance)] for L in q.ref]
+            img, val = hf.specular_lighting(si, sc.ray, [hf.DirectionalLight(*p) for p in par], s.byte, at, eta=SP.ETA, spp=SPP, weight=wt,
+                                            return_value=True)
+            ((img * _cu(x.gi)).sum() + (val * _cu(x.gv)).sum()).backward()
+            got = types.SimpleNamespace(image=_np(img.detach()).copy(), value=_np(val.detach()).copy(), gn=_np(si.sh_frame.n.grad),
+                                        gw=_np(wt.grad) if weighted else None, ga=_np(at.grad),
+                                        g4=_np(torch.stack([_flat([t.grad for t in p]) for p in par])))
+            assert got.g4.shape == (K, SP.PARAMS)
+            if kind == "row" and weighted:
+                assert np.array_equal(got.image, s.img) and np.array_equal(got.value, s.val)
+            with fwAD.dual_level():
+                sid = leaf_si(hf, sc, fwAD.make_dual(sc.si.sh_frame.n.detach(), _cu(x.dn)))
+                dual = [hf.DirectionalLight(fwAD.make_dual(_f64(L.to_light), _f64(x.dl[k, :3])),
+                                            fwAD.make_dual(_f64(L.irradiance), _f64(x.dl[k, 3]))) for k, L in enumerate(q.ref)]
+                out = hf.specular_lighting(sid, sc.ray, dual, s.byte, fwAD.make_dual(_cu(alpha), _cu(x.da)), eta=SP.ETA, spp=SPP,
+                                           weight=fwAD.make_dual(_cu(x.w), _cu(x.dw)) if weighted else None, return_value=True)
+                got.dimage, got.dvalue = (_np(fwAD.unpack_dual(o).tangent).copy() for o in out)
+            ref = RS.specular_evaluate(q.ref, sc.np, sc.np["d"], x, kind, q.vis, weighted=weighted)
+            # every sample takes part: the masks of both sides are the byte and the double cosines
+            assert got.value.shape == ref.value.shape == (K, sc.n) and np.array_equal(got.value > 0, ref.value > 0)
+            assert not got.value[~q.vis].any() and not got.dvalue[~q.vis].any()     # exactly 0 where the byte's bit is clear
+            dark = ~q.vis.any(0)
+            for k in ("gn", "gw", "ga"):
+                assert getattr(got, k) is None or not getattr(got, k)[..., dark].any()
+            assert not got.g4[q.names.index("below")].any() or q.vis[q.names.index("below")].any()
+            assert ref.value.max() > 0.05 and np.abs(ref.ga).max() > 0 and (np.abs(ref.g4).max(1) > 0).sum() >= K - 1
+            err = SP.errors(got, ref)
+            print("specular", name, kind, "weighted" if weighted else "unweighted", {k: "%.3g" % v for k, v in err.items()})
+            for k, v in err.items():
+                worst[k] = max(worst[k], v)
+            if weighted:
+                # the bound of tests/test_gpu_specular.py: the device's own rounding, 8 ulp per element on the tangent side and
+                # the project's factor 4 for the adjoint side's regrouping, of the mass sum |tangent| |upstream|
+                gap = transposition_gap(((got.dimage, x.gi), (got.dvalue, x.gv)),
+                                        ((got.gn, x.dn), (got.gw, x.dw), (got.ga, x.da), (got.g4, x.dl)))
+                mass = np.abs(got.dvalue.astype(np.float64) * x.gv).sum() + np.abs(got.dimage.astype(np.float64) * x.gi).sum()
+                bound = (8 + 4 * 8) * 2.0 ** -24 * mass
+                print("specular", name, kind, "transposition gap %.3g / %.3g" % (gap, bound))
+                assert mass > 0 and gap <= bound, (gap, mass, bound)
+        print("specular", name, kind, "worst", {k: "%.3g / %.3g" % (worst[k], tol[k]) for k in tol})
+        for k in tol:
+            assert worst[k] <= tol[k], (name, kind, k, worst[k], tol[k])
+
+
+@pytest.mark.parametrize("name,face_normals", RS.CHAINS)
+def test_specular_chain_to_the_heights(hf, oracle, name, face_normals):
+    """(f): ray_intersect -> directional_lighting (visibility) -> specular_lighting -> loss -> backward() -> shape.heightfield.grad
+    against the restatement's grad_sh_n (fed with the GPU's records and byte) carried to the heights by _to_heights under the
+    scene's to_world and flip_normals.  Bound: RS.CHAIN, the directional row's for its chain"""
+    s = _specular(hf, oracle, name, face_normals)
+    sc, q, x = s.sc, s.q, s.x
+    shape = hf.Heightfield(heightfield=sc.ht.clone(), max_height=sc.max_height, to_world=sc.tw64, flip_normals=sc.flip,
+                           face_normals=face_normals)
+    shape.heightfield.requires_grad_(True)
+    si = shape.ray_intersect(sc.ray, hf.RayFlags.All)
+    _, vis = hf.directional_lighting(shape, si, sc.ray, q.lights, spp=SPP, return_visibility=True)
+    assert np.array_equal(_np(vis), q.byte)
+    img = hf.specular_lighting(si, sc.ray, q.lights, vis, _cu(s.alpha["row"]), eta=SP.ETA, spp=SPP)
+    (img * _cu(x.gi)).sum().backward()
+    got = _np(shape.heightfield.grad)
+    g = SP.adjoint(q.ref, _np(si.sh_frame.n), sc.np["d"], None, s.alpha["row"], SP.ETA, q.vis, SPP, x.gi)
+    gh = _to_heights(hf, oracle, sc, shape, g.gn, None, face_normals)
+    err = np.linalg.norm(got - gh) / np.linalg.norm(gh)
+    print("specular", name, "face_normals", face_normals, "dL/dheight relative L2 error %.3g / %.3g" % (err, RS.CHAIN), "norm", np.linalg.norm(gh))
+    assert got.shape == (sc.H, sc.W) and np.linalg.norm(gh) > 0 and err <= RS.CHAIN, err
+
+
+# ---- the medium row: shadow rays that start in free space, on the primary ray, under a world-space top plane --------------
+MTOL = RS.TOL["medium"]
+MK, MSEED = RS.MEDIUM_K, RS.MEDIUM_SEED
+MEDIUM_CASES = [(name, fn, mname) for name, fn in RS.CASES for mname in RS.MEDIUM_NAMES]
+_MEDIUM = {}
+
+
+def _medium_objects(hf, r, scalars=None, irradiances=None):
+    """(hf.Medium, the eight hf.DirectionalLights) of the run r; scalars, irradiances: the user's tensors in their place"""
+    M = r.M
+    med = hf.Medium(*((M.sigma_t, M.albedo, M.g) if scalars is None else scalars), top_origin=M.top_origin, top_normal=M.top_normal)
+    return med, [hf.DirectionalLight(L.to_light, L.irradiance if irradiances is None else irradiances[j]) for j, L in enumerate(r.lights)]
+
+
+def _medium(hf, oracle, name, face_normals, mname):
+    """a (case, medium), once: all eight lights in one fused launch with a weight, the 8 x MK materialised rays, the run of
+    tests/row_scenes.py on the GPU's own primary rays, origins and words; (g) its conditions, asserted before anything is
+    compared"""
+    key = (name, face_normals, mname)
+    if key not in _MEDIUM:
+        sc = _scene(hf, oracle, name, RS.MEDIA[mname]["view"], face_normals)
+        o, d, t = sc.rays[0:3], sc.np["d"], sc.np["t"]
+        assert np.array_equal(d, sc.rays[3:6])
+        r = RS.medium_run(sc, mname, o, d, t, sc.field)                              # (the restatement's origins: replaced below)
+        x = MR.inputs(sc.n, SPP, len(r.lights))
+        med, lights = _medium_objects(hf, r)
+        img, val, words = hf.medium_lighting(sc.shape, sc.si, sc.ray, lights, med, spp=SPP, num_steps=MK, seed=MSEED, weight=_cu(x.w),
+                                             return_value=True, return_visibility=True)
+        rays = [[hf.medium_rays(sc.si, sc.ray, lights[j], med, k, seed=MSEED) for k in range(MK)] for j in range(len(lights))]
+        first = int(np.argmax(r.shines))
+        for j in np.flatnonzero(r.shines):                                           # the point does not depend on the light
+            assert all(torch.equal(rays[j][k].o, rays[first][k].o) for k in range(MK)), r.names[j]
+        q = RS.medium_run(sc, mname, o, d, t, sc.field, words=_np(words).view(np.uint32), origins=np.stack([_np(rays[first][k].o) for k in range(MK)]))
+        q.sc, q.x, q.med, q.gpu_lights, q.rays, q.words_t = sc, x, med, lights, rays, words
+        q.img, q.val = _np(img).copy(), _np(val).copy()
+        print("medium", name, "face" if face_normals else "smooth", mname, RS.medium_describe(q))
+        RS.medium_conditions(sc, q)                                                  # (g)
+        _MEDIUM[key] = q
+    return _MEDIUM[key]
+
+
+@pytest.mark.parametrize("name,face_normals,mname", MEDIUM_CASES)
+def test_medium_rays_against_the_restatement_and_words_against_the_two_call_sequence_and_the_oracle(hf, oracle, name, face_normals, mname):
+    q = _medium(hf, oracle, name, face_normals, mname)
+    sc, J = q.sc, len(q.lights)
+    words = q.words
+    # (a) every (light, point): masks, directions and maxt exactly, origins within four times the float32 restatement's error
+    worst = 0.0
+    for j, L in enumerate(q.lights):
+        lf = MR.unit(L)[0].astype(np.float32)
+        for k in range(MK):
+            o, d, maxt = _np(q.rays[j][k].o), _np(q.rays[j][k].d), _np(q.rays[j][k].maxt)
+            ro, _, rmaxt, tr = MR.rays(q.M, L, q.o, q.d, q.t, k, MSEED)
+            assert np.array_equal(tr, q.traced[j]) and np.array_equal(maxt, rmaxt) and np.isin(maxt, (np.inf, -1.0)).all(), (q.names[j], k)
+            assert np.array_equal(d, np.where(tr[None], lf[:, None], np.float32(0))) and not o[:, ~tr].any(), (q.names[j], k)
+            if tr.any():
+                worst = max(worst, float(np.abs(o - ro)[:, tr].max()))
+    print("medium", name, mname, "largest origin difference %.3g / %.3g" % (worst, MTOL["origin"]))
+    assert 0 < worst <= MTOL["origin"], worst
+    # (b) the fused words against medium_rays + shape.ray_test, bit for bit, in both coherence modes; nothing where no light shines in
+    assert not (words >> np.uint32(MK)).any()                                        # no bit at or above num_steps
+    assert not words[q.names.index("below")].any() and (mname != "tilted" or not words[q.names.index("graze")].any())
+    old = sc.shape.ray_coherence()
+    for mode in (hf.Heightfield.COHERENCE_AUTO, hf.Heightfield.COHERENCE_INCOHERENT):
+        sc.shape.set_ray_coherence(mode)
+        try:
+            _, again = hf.medium_lighting(sc.shape, sc.si, sc.ray, q.gpu_lights, q.med, spp=SPP, num_steps=MK, seed=MSEED, return_visibility=True)
+            two = np.stack([np.stack([_np((q.rays[j][k].maxt >= 0) & ~sc.shape.ray_test(q.rays[j][k])) for k in range(MK)]) for j in range(J)])
+        finally:
+            sc.shape.set_ray_coherence(old)
+        assert torch.equal(again, q.words_t), mode
+        assert np.array_equal(two, q.bits), (mode, int((two != q.bits).sum()))
+    # (c) the words against the oracle's ray_test (the same to_world and flip_normals) on the GPU's own rays: exactly, but for
+    # the lanes whose origin lies closer to the primary hit than the sky row's spawn offset
+    keep = ~q.near[None]
+    assert np.array_equal((q.bits & keep), (q.oracle & keep)), int(((q.bits != q.oracle) & keep).sum())
+    print("medium", name, mname, "left out of the comparison with the oracle: %d lanes, share %.3g / %.3g; they differ on %d"
+          % (q.counts["near_lanes"], q.counts["near"], RS.UNSURE_CAP, int((q.bits != q.oracle).sum())))
+    assert q.counts["near"] <= RS.UNSURE_CAP
+
+
+def _medium_params_bound(ref, n):
+    """tests/test_gpu_medium.py's _check_params: the kernel adds n double terms in double and rounds the sum to float32 once"""
+    return 2.0 ** -23 * np.abs(ref.gp) + (n + 64) * 2.0 ** -53 * ref.gp_abs
+
+
+def _medium_slack(p):
+    """what the row's rule allows an element of the float32 result p: rtol |p| + atol max(1, largest |p|)"""
+    p = np.abs(np.asarray(p, np.float64))
+    return RS.MEDIUM_RTOL * p + RS.MEDIUM_ATOL * max(1.0, p.max())
+
+
+@pytest.mark.parametrize("name,face_normals,mname", MEDIUM_CASES)
+def test_medium_values_gradients_and_tangents_against_the_restatement_and_the_transposition_gap(hf, oracle, name, face_normals, mname):
+    """(d), (e): through the public function, backward() and forward_ad; sigma_t, albedo, g and the eight irradiances are
+    float64 host leaves (duals).  The row's own rule: rtol 1e-5, atol 1e-7 max(1, largest |reference|); the reduced numbers
+    within the bound of tests/test_gpu_medium.py's _check_params"""
+    q = _medium(hf, oracle, name, face_normals, mname)
+    sc, x, M, J, n = q.sc, q.x, q.M, len(q.lights), q.sc.n
+    a = (M, q.lights, q.o, q.d, q.t, x.w, q.words, MK, MSEED)
+    rimg, rval = MR.forward(*a, spp=SPP)
+    close = {"value": RS.medium_close(q.val, rval), "image": RS.medium_close(q.img, rimg)}
+    print("medium", name, mname, "largest |value| %.3g |image| %.3g" % (np.abs(rval).max(), np.abs(rimg).max()))
+    assert np.abs(rval).max() > 1e-3 and np.abs(rimg).max() > 1e-3
+    assert not q.val[q.words == 0].any() and (q.val[q.words != 0] > 0).all()         # exact zeros where no bit is set
+    # ---- backward()
+    si = hf.SurfaceInteraction3f()
+    si.p, si.n, si.sh_frame = sc.si.p.detach(), sc.si.n.detach(), sc.si.sh_frame
+    si.t = sc.si.t.detach().clone().requires_grad_(True)
+    wt = _cu(x.w).requires_grad_(True)
+    scal = [_f64(v).requires_grad_(True) for v in (M.sigma_t, M.albedo, M.g)]
+    E = [_f64(L.irradiance).requires_grad_(True) for L in q.lights]
+    med, lights = _medium_objects(hf, q, scal, E)
+    img, val, words = hf.medium_lighting(sc.shape, si, sc.ray, lights, med, spp=SPP, num_steps=MK, seed=MSEED, weight=wt, return_value=True,
+                                         return_visibility=True)
+    assert torch.equal(words, q.words_t) and np.array_equal(_np(val.detach()), q.val) and np.array_equal(_np(img.detach()), q.img)
+    ((img * _cu(x.gi)).sum() + (val * _cu(x.gv)).sum()).backward()
+    gw, gt = _np(wt.grad), _np(si.t.grad)
+    gp = np.array([float(v.grad) for v in scal + E])
+    ref = MR.adjoint(*a, spp=SPP, grad_image=x.gi, grad_value=x.gv)
+    close["grad_weight"], close["grad_t"] = RS.medium_close(gw, ref.gw), RS.medium_close(gt, ref.gt)
+    none = (q.words == 0).all(0)
+    assert not gw[none].any() and not gt[none].any() and not gt[~np.isfinite(q.t)].any()     # grad_t exactly zero where t = inf
+    assert np.abs(ref.gt).max() > 0 and np.abs(ref.gw).max() > 0
+    bound = _medium_params_bound(ref, n)
+    print("medium", name, mname, "the 3 + 8 reduced numbers", gp, "float64", ref.gp, "allowed", bound)
+    shines = np.concatenate([[True] * MR.PARAMS, q.shines])
+    assert (ref.gp_abs[shines] > 0).all() and not gp[~shines].any() and not ref.gp_abs[~shines].any()
+    assert (np.abs(gp - ref.gp) <= bound).all(), (gp, ref.gp, bound)
+    # ---- forward_ad
+    with fwAD.dual_level():
+        sid = hf.SurfaceInteraction3f()
+        sid.p, sid.n, sid.sh_frame = sc.si.p.detach(), sc.si.n.detach(), sc.si.sh_frame
+        sid.t = fwAD.make_dual(sc.si.t.detach(), _cu(x.dt))
+        dscal = [fwAD.make_dual(_f64(v), _f64(x.dp[i])) for i, v in enumerate((M.sigma_t, M.albedo, M.g))]
+        dE = [fwAD.make_dual(_f64(L.irradiance), _f64(x.dp[MR.PARAMS + j])) for j, L in enumerate(q.lights)]
+        med, lights = _medium_objects(hf, q, dscal, dE)
+        out = hf.medium_lighting(sc.shape, sid, sc.ray, lights, med, spp=SPP, num_steps=MK, seed=MSEED, weight=fwAD.make_dual(_cu(x.w), _cu(x.dw)),
+                                 return_value=True)
+        dimg, dval = (_np(fwAD.unpack_dual(v).tangent).copy() for v in out)
+    rdimg, rdval = MR.tangent(*a, spp=SPP, dw=x.dw, dt=x.dt, d_params=x.dp)
+    close["dimage"], close["dvalue"] = RS.medium_close(dimg, rdimg), RS.medium_close(dval, rdval)
+    assert not dval[q.words == 0].any() and np.abs(rdval).max() > 0
+    print("medium", name, mname, "worst (|difference| - rtol |reference|) / (atol max(1, largest |reference|)), allowed 1:",
+          {k: "%.3g" % v for k, v in close.items()})
+    for k, v in close.items():
+        assert v <= 1.0, (name, mname, k, v)
+    # ---- the transposition gap on the device, the bound built from the tolerances above
+    lhs = [(dimg, x.gi), (dval, x.gv)]
+    rhs = [(gt, x.dt), (gw, x.dw)]
+    gap = transposition_gap(lhs, rhs + [(gp, x.dp)])
+    allowed = sum((_medium_slack(p) * np.abs(v)).sum() for p, v in lhs + rhs) + (bound * np.abs(x.dp)).sum()
+    print("medium", name, mname, "transposition gap %.3g / %.3g" % (gap, allowed))
+    assert gap <= allowed, (gap, allowed)
+
+
+@pytest.mark.parametrize("name,face_normals", RS.CHAINS)
+def test_medium_chain_to_the_heights(hf, oracle, name, face_normals):
+    """(f): medium_lighting under `skim` -> loss -> backward() -> shape.heightfield.grad against the restatement's grad_t (fed
+    with the GPU's t and words) carried to the heights: by the oracle's adjoint of t under the scene's to_world and
+    flip_normals (flat shading) or by shape.adjoint with ybar[0] = grad_t (smooth).  Bound: RS.CHAIN"""
+    q = _medium(hf, oracle, name, face_normals, "skim")
+    sc, x = q.sc, q.x
+    shape = hf.Heightfield(heightfield=sc.ht.clone(), max_height=sc.max_height, to_world=sc.tw64, flip_normals=sc.flip,
+                           face_normals=face_normals)
+    shape.heightfield.requires_grad_(True)
+    si = shape.ray_intersect(sc.ray, hf.RayFlags.All)
+    img, words = hf.medium_lighting(shape, si, sc.ray, q.gpu_lights, q.med, spp=SPP, num_steps=MK, seed=MSEED, return_visibility=True)
+    assert torch.equal(words, q.words_t) and np.array_equal(_np(si.t), q.t)
+    (img * _cu(x.gi)).sum().backward()
+    got = _np(shape.heightfield.grad)
+    gt = MR.adjoint(q.M, q.lights, q.o, q.d, q.t, None, q.words, MK, MSEED, spp=SPP, grad_image=x.gi).gt
+    assert not gt[~sc.hit].any()
+    if face_normals:
+        t, u, v, prim = sc.pi_oracle
+        gh = sc.field.adjoint(sc.rays, t, u, v, prim, {"t": gt.astype(np.float32)[None]}, oracle.RAY_ALL)
+    else:
+        ybar = torch.zeros((18, sc.n), device="cuda")
+        ybar[0] = _cu(gt.astype(np.float32))
+        gh = _np(shape.adjoint(sc.ray, shape.ray_intersect_preliminary(sc.ray), ybar, ray_flags=int(hf.RayFlags.All)))
+    err = np.linalg.norm(got - gh) / np.linalg.norm(gh)
+    print("medium", name, "face_normals", face_normals, "dL/dheight relative L2 error %.3g / %.3g" % (err, RS.CHAIN), "norm", np.linalg.norm(gh))
+    assert got.shape == (sc.H, sc.W) and np.linalg.norm(gh) > 0 and err <= RS.CHAIN, err

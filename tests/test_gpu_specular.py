@@ -1,4 +1,4 @@
-"""Specular highlights on the GPU (hf_specular_lighting, _adjoint, _tangent) on row_helpers.base_scene: sine_heights(96),
+"""Specular highlights on the GPU (hf_specular_lighting, _adjoint, _tangent); under to_world, flip_normals and odd grids: tests/test_gpu_row_scenes.py.  Here row_helpers.base_scene: sine_heights(96),
 max_height 0.5, the 64 x 64 x 4 orthographic wavefront from (1.2, 0.3, 1.2) and from (0.6, 0.35, 2.0), both face_normals
 modes, under the rig of 8 lights of tests/directional_ref.py.  The visibility byte is the GPU's own
 hf_directional_lighting's; the roughness is a per-sample row spread over [0.05, 0.6] ("row") and, in one case per scene,
