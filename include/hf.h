@@ -1696,7 +1696,8 @@ int hf_directional_lighting_tangent(size_t n, uint32_t spp, const float *const s
  *   ds0  = (da - s0 <s0, da>) / A,   dt0 = db x s0 + b x ds0,
  *   dN   = ds0 m_x + dt0 m_y + db m_z + s0 dm_x + t0 dm_y + b dm_z.
  * The adjoint is the exact transpose.
- * OUT OF SCOPE: `bumpmap`; the BSDF-side test cos_theta(wo) cos_theta(perturbed_wo) > 0 (normalmap.cpp:148: the rows
+ * The reference's `bumpmap` is hf_bumpmap_eval (below the medium).
+ * OUT OF SCOPE: the BSDF-side test cos_theta(wo) cos_theta(perturbed_wo) > 0 (normalmap.cpp:148: the rows
  * decide on <sh_n, l> as before); nearest filtering; a gradient for s or t; the mirror wrap.
  * All three entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional,
  * n >= 2^32, TW == 0 or TH == 0, TW TH >= 2^31, a wrap that is neither constant.  n == 0 is legal and launches nothing.
@@ -1898,6 +1899,76 @@ int hf_medium_lighting_tangent(size_t n, uint32_t spp, const float *const o[3], 
                                const hf_directional_light_t *lights, uint32_t num_steps, uint32_t seed,
                                const uint32_t *ray_id, const uint32_t *vis_bits, const float *dweight, const float *dt,
                                const float *d_params, float *dimage, float *dvalue, hf_stream_t stream);
+
+/* ---- the bump map: the shading normal perturbed by the slopes of a height texture, fused, differentiable ----
+ *
+ * The reference's `bumpmap` (src/bsdfs/bumpmap.cpp:199-222, frame()) over Texture::eval_1_grad (src/textures/bitmap.cpp:
+ * 346-423, bilinear filter, identity uv transform) as a map of the shading normal: a scalar relief f(u, v) laid over the
+ * height grid, one float per texel.  Whatever it perturbs a normal to is the normal of a surface: the heightfield's own
+ * idea continued below the grid spacing.  The result is a new sh_n; every lighting row takes it as it takes any other.
+ * Everything is in WORLD space, in double from the float32 records, and each component of N is rounded ONCE.
+ * Per sample i:
+ *   inputs      uv (2 rows), b = sh_n (3 rows), n_geo = si.n (3 rows), dp_du, dp_dv (3 rows each) of n floats, active
+ *               (n bytes; NULL: every lane);
+ *   texture     tex[TH][TW], float32, ONE plane, the caller's device buffer: exactly a hf_bitmap_eval texture;
+ *               wrap = HF_WRAP_CLAMP or HF_WRAP_REPEAT;  scale: a HOST float, the gradient's multiplier (bumpmap.cpp:108);
+ *   lookup      pos = (float32(u TW), float32(v TH)), each product rounded once: the normal map's positions; (Lx, Ly) in
+ *               float32 is bit for bit the out_grad hf_bitmap_eval writes for pos;
+ *   gradient    g = scale (TW Lx, TH Ly)   (bitmap.cpp:399-418, bumpmap.cpp:201);
+ *   frame       P_u = dp_du + b (g_x - k <b, dp_du>),  P_v = dp_dv + b (g_y - k <b, dp_dv>),  k = 1 / <b, b>
+ *               (bumpmap.cpp:204-205, where the normal is unit and k = 1),
+ *               c = P_u x P_v,  sigma = -1 if <n_geo, c> < 0, else +1 (bumpmap.cpp:212),  N = sigma c / |c|.
+ * DEVIATION in k: the reference's formula is written for a unit normal.  A float32 b is unit only to rounding, |b|^2 = 1 + e,
+ * and with k = 1 the projected tangents keep a component -e <b, dp_du> along b: c leaves b's direction by about e tan(angle
+ * between b and the tangents' normal), which under smooth shading put a FLAT texture 1.125 x 2^-22 from b.  With k the
+ * projection is exact for the b that arrives; for a unit b nothing changes.  k is DIFFERENTIATED, not held: N does not
+ * depend on the length of b but through the term b g.
+ * A lane is PERTURBED when it is active, uv, b, n_geo, dp_du and dp_dv are finite, the lookup reads something (under
+ * HF_WRAP_REPEAT a coordinate beyond 2^23 texels reads nothing), |b|^2 > 0, |dp_du|^2 > 0, |dp_dv|^2 > 0 and |c|^2 >= 1e-12
+ * |dp_du|^2 |dp_dv|^2.  Every other lane PASSES THROUGH: N = b bit for bit, its derivative is the identity on sh_n and zero for
+ * everything else.  mask (n bytes, optional): 1 where perturbed, 0 elsewhere.
+ * A FLAT texture (g = 0) gives N = +-b / |b| only TO ROUNDING, not bit for bit: the cross product of the projected
+ * tangents is formed anew.  This differs from the normal map, whose flat map changes no bit.
+ * DEVIATION, the one the normal map makes: the reference converts N to the local frame and rebuilds s and t; here only the
+ * world-space N is returned, the one member of the frame a lighting row reads.
+ * Differentiated with respect to tex, uv, sh_n, dp_du and dp_dv.  HELD: the cell, the perturbed / pass-through decision,
+ * sigma and n_geo.  With f = (fx, fy) the position in the cell, the texels v00, v10, v01, v11, C = v11 - v10 - v01 + v00
+ * and dpos = (TW du, TH dv) -- the derivative of the SLOPES, not of the value:
+ *   dLx  = -(1 - fy) dv00 + (1 - fy) dv10 - fy dv01 + fy dv11 + C dpos_y,
+ *   dLy  = -(1 - fx) dv00 - fx dv10 + (1 - fx) dv01 + fx dv11 + C dpos_x,
+ *   dg   = scale (TW dLx, TH dLy),
+ *   dP_u = ddp_du + db (g_x - k <b, dp_du>) + b (dg_x - k (<db, dp_du> + <b, ddp_du> - 2 k <b, dp_du> <b, db>)),  dP_v likewise
+ *          (for a unit b and a db orthogonal to it -- the tangent of any normalised normal -- the last term is zero),
+ *   dc   = dP_u x P_v + P_u x dP_v,   dN = sigma (dc - ch <ch, dc>) / |c|,   ch = c / |c|.
+ * The adjoint is the exact transpose.
+ * OUT OF SCOPE: a gradient for scale (g is linear in scale tex: scale is redundant with the texels, and the reference
+ * marks it NonDifferentiable); a gradient for n_geo; the BSDF-side test cos_theta(wo) cos_theta(perturbed_wo) > 0
+ * (bumpmap.cpp:139-146: the rows decide on <sh_n, l> as before); nearest filtering; an RGB texture taken by its luminance;
+ * a uv transform; the mirror wrap; s and t.
+ * All three entries refuse with HF_EINVAL, before anything touches a device: a NULL pointer that is not optional,
+ * n >= 2^32, TW == 0 or TH == 0, TW TH >= 2^31, a wrap that is neither constant, a scale that is not finite.  n == 0 is legal
+ * and launches nothing.  They take no field handle, allocate nothing, never synchronise the host and are capturable; one
+ * launch each, one lane per sample.  Callers detect the entries by their symbols (HF_VERSION is unchanged). */
+int hf_bumpmap_eval(size_t n, const float *const uv[2], const float *const sh_n[3], const float *const n_geo[3],
+                    const float *const dp_du[3], const float *const dp_dv[3], const uint8_t *active, uint32_t TW, uint32_t TH,
+                    const float *tex, int wrap, float scale, float *const out_n[3], uint8_t *mask, hf_stream_t stream);
+/* Forward mode: dtex ([TH][TW]), duv (2 rows), dsh_n, ddp_du, ddp_dv (3 rows each) may each be NULL (zero); dout_n (3 rows)
+ * is overwritten.  Bitwise the same from launch to launch. */
+int hf_bumpmap_eval_tangent(size_t n, const float *const uv[2], const float *const sh_n[3], const float *const n_geo[3],
+                            const float *const dp_du[3], const float *const dp_dv[3], const uint8_t *active, uint32_t TW,
+                            uint32_t TH, const float *tex, int wrap, float scale, const float *dtex,
+                            const float *const duv[2], const float *const dsh_n[3], const float *const ddp_du[3],
+                            const float *const ddp_dv[3], float *const dout_n[3], hf_stream_t stream);
+/* Reverse mode: grad_out (3 rows) is dL/dN.  grad_tex ([TH][TW]) is ACCUMULATED into with float atomics, four per
+ * perturbed sample with the slopes' weights above -- fewer where consecutive lanes of a wave share a cell: they add theirs
+ * up first -- in a free order: repeatable to rounding; grad_uv (2 rows), grad_sh_n, grad_dp_du and grad_dp_dv (3 rows each)
+ * are OVERWRITTEN, with exact zeros where nothing flows; a pass-through lane hands grad_out to grad_sh_n.  Each output may
+ * be NULL (not wanted), not all of them. */
+int hf_bumpmap_eval_adjoint(size_t n, const float *const uv[2], const float *const sh_n[3], const float *const n_geo[3],
+                            const float *const dp_du[3], const float *const dp_dv[3], const uint8_t *active, uint32_t TW,
+                            uint32_t TH, const float *tex, int wrap, float scale, const float *const grad_out[3],
+                            float *grad_tex, float *const grad_uv[2], float *const grad_sh_n[3],
+                            float *const grad_dp_du[3], float *const grad_dp_dv[3], hf_stream_t stream);
 
 /* ---- next row: bounce lighting, one diffuse interreflection traced in the kernel ----
  *

@@ -13,5 +13,6 @@ from .projector import Projector, projector_lighting, projector_rays  # noqa: F4
 from .spot import SpotLight, spot_lighting, spot_rays  # noqa: F401
 from .directional import DirectionalLight, directional_lighting, directional_rays  # noqa: F401
 from .normalmap import NormalMap  # noqa: F401
+from .bumpmap import BumpMap  # noqa: F401
 from .specular import specular_lighting  # noqa: F401
 from .medium import Medium, medium_attenuation, medium_lighting, medium_rays  # noqa: F401

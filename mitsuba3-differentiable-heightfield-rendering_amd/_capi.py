@@ -141,8 +141,19 @@ _medium_in = [C.c_size_t, C.c_uint32, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _f
 
 # n, uv, sh_n, dp_du, active, TW, TH, tex, wrap
 _normalmap_in =[C.c_size_t, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, *_bitmap_in]
+# n, uv, sh_n, n_geo, dp_du, dp_dv, active, TW, TH, tex, wrap, scale
+_bumpmap_in = [C.c_size_t, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp,
+               *_bitmap_in, C.c_float]
 
 SYMBOLS = {
+    # ..., out_n, mask
+    "hf_bumpmap_eval": (C.c_int, [*_bumpmap_in, C.POINTER(_fp * 3), _fp, C.c_void_p]),
+    # ..., dtex, duv, dsh_n, ddp_du, ddp_dv, dout_n
+    "hf_bumpmap_eval_tangent": (C.c_int, [*_bumpmap_in, _fp, C.POINTER(_fp * 2), C.POINTER(_fp * 3), C.POINTER(_fp * 3),
+                                          C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p]),
+    # ..., grad_out, grad_tex, grad_uv, grad_sh_n, grad_dp_du, grad_dp_dv
+    "hf_bumpmap_eval_adjoint": (C.c_int, [*_bumpmap_in, C.POINTER(_fp * 3), _fp, C.POINTER(_fp * 2), C.POINTER(_fp * 3),
+                                          C.POINTER(_fp * 3), C.POINTER(_fp * 3), C.c_void_p]),
     # n, o, d, t, medium, light, k, seed, ray_id, out_o, out_d, out_maxt
     "hf_medium_rays": (C.c_int, [C.c_size_t, C.POINTER(_fp * 3), C.POINTER(_fp * 3), _fp, C.POINTER(hf_medium_t),
                                  C.POINTER(hf_directional_light_t), C.c_uint32, C.c_uint32, _fp, C.POINTER(_fp * 3),

@@ -1522,6 +1522,91 @@ extern "C" int hf_normalmap_eval_adjoint(size_t n, const float *const uv[2], con
     return light_launch(hf_launch_normalmap, 1, a, stream);
 }
 
+// ---- the bump map: the shading normal perturbed by the slopes of a one-plane texture, one launch per entry ----
+// What the three hf_bumpmap_* entries share: the rows of the record, the texture and the scale
+static int bumpmap_args(const char *who, size_t n, const float *const uv[2], const float *const sh_n[3],
+                        const float *const n_geo[3], const float *const dp_du[3], const float *const dp_dv[3],
+                        const uint8_t *active, uint32_t TW, uint32_t TH, const float *tex, int wrap, float scale,
+                        hf_bumpmap_args &a) {
+    a = {};
+    if (!uv || !uv[0] || !uv[1] || !all3(sh_n) || !all3(n_geo) || !all3(dp_du) || !all3(dp_dv))
+        return fail(HF_EINVAL, "%s: NULL argument", who);
+    if (n >= ((size_t) 1 << 32)) return fail(HF_EINVAL, "%s: more than 2^32 samples", who);
+    if (!isfinite(scale)) return fail(HF_EINVAL, "%s: scale must be finite (got %g)", who, (double) scale);
+    a.n = n; a.active = active; a.scale = scale;
+    for (int c = 0; c < 2; ++c) a.uv[c] = uv[c];
+    for (int c = 0; c < 3; ++c) { a.sh_n[c] = sh_n[c]; a.n_geo[c] = n_geo[c]; a.dp_du[c] = dp_du[c]; a.dp_dv[c] = dp_dv[c]; }
+    return bitmap_texture(who, TW, TH, tex, wrap, a);
+}
+
+extern "C" int hf_bumpmap_eval(size_t n, const float *const uv[2], const float *const sh_n[3], const float *const n_geo[3],
+                               const float *const dp_du[3], const float *const dp_dv[3], const uint8_t *active, uint32_t TW,
+                               uint32_t TH, const float *tex, int wrap, float scale, float *const out_n[3], uint8_t *mask,
+                               hf_stream_t stream) {
+    const char *fn = "hf_bumpmap_eval";
+    hf_bumpmap_args a;
+    const int rc = bumpmap_args(fn, n, uv, sh_n, n_geo, dp_du, dp_dv, active, TW, TH, tex, wrap, scale, a);
+    if (rc != HF_OK) return rc;
+    if (!out_n || !out_n[0] || !out_n[1] || !out_n[2]) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    for (int c = 0; c < 3; ++c) a.out_n[c] = out_n[c];
+    a.mask = mask;
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_bumpmap, 0, a, stream);
+}
+
+extern "C" int hf_bumpmap_eval_tangent(size_t n, const float *const uv[2], const float *const sh_n[3],
+                                       const float *const n_geo[3], const float *const dp_du[3], const float *const dp_dv[3],
+                                       const uint8_t *active, uint32_t TW, uint32_t TH, const float *tex, int wrap, float scale,
+                                       const float *dtex, const float *const duv[2], const float *const dsh_n[3],
+                                       const float *const ddp_du[3], const float *const ddp_dv[3], float *const dout_n[3],
+                                       hf_stream_t stream) {
+    const char *fn = "hf_bumpmap_eval_tangent";
+    hf_bumpmap_args a;
+    const int rc = bumpmap_args(fn, n, uv, sh_n, n_geo, dp_du, dp_dv, active, TW, TH, tex, wrap, scale, a);
+    if (rc != HF_OK) return rc;
+    if (!dout_n || !dout_n[0] || !dout_n[1] || !dout_n[2]) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if ((duv && (!duv[0] || !duv[1])) || (dsh_n && !all3(dsh_n)) || (ddp_du && !all3(ddp_du)) || (ddp_dv && !all3(ddp_dv)))
+        return fail(HF_EINVAL, "%s: NULL component array", fn);
+    a.dtex = dtex;
+    for (int c = 0; c < 2; ++c) a.duv[c] = duv ? duv[c] : nullptr;
+    for (int c = 0; c < 3; ++c) {
+        a.out_n[c] = dout_n[c];
+        a.dn[c] = dsh_n ? dsh_n[c] : nullptr;
+        a.dpu[c] = ddp_du ? ddp_du[c] : nullptr;
+        a.dpv[c] = ddp_dv ? ddp_dv[c] : nullptr;
+    }
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_bumpmap, 2, a, stream);
+}
+
+extern "C" int hf_bumpmap_eval_adjoint(size_t n, const float *const uv[2], const float *const sh_n[3],
+                                       const float *const n_geo[3], const float *const dp_du[3], const float *const dp_dv[3],
+                                       const uint8_t *active, uint32_t TW, uint32_t TH, const float *tex, int wrap, float scale,
+                                       const float *const grad_out[3], float *grad_tex, float *const grad_uv[2],
+                                       float *const grad_sh_n[3], float *const grad_dp_du[3], float *const grad_dp_dv[3],
+                                       hf_stream_t stream) {
+    const char *fn = "hf_bumpmap_eval_adjoint";
+    hf_bumpmap_args a;
+    const int rc = bumpmap_args(fn, n, uv, sh_n, n_geo, dp_du, dp_dv, active, TW, TH, tex, wrap, scale, a);
+    if (rc != HF_OK) return rc;
+    if (!all3(grad_out)) return fail(HF_EINVAL, "%s: NULL argument", fn);
+    if ((grad_uv && (!grad_uv[0] || !grad_uv[1])) || (grad_sh_n && !all3(grad_sh_n)) || (grad_dp_du && !all3(grad_dp_du)) ||
+        (grad_dp_dv && !all3(grad_dp_dv)))
+        return fail(HF_EINVAL, "%s: NULL component array", fn);
+    if (!grad_tex && !grad_uv && !grad_sh_n && !grad_dp_du && !grad_dp_dv)
+        return fail(HF_EINVAL, "%s: grad_tex, grad_uv, grad_sh_n, grad_dp_du and grad_dp_dv are all NULL", fn);
+    a.gtex = grad_tex;
+    for (int c = 0; c < 2; ++c) a.guv[c] = grad_uv ? grad_uv[c] : nullptr;
+    for (int c = 0; c < 3; ++c) {
+        a.gout[c] = grad_out[c];
+        a.gn[c] = grad_sh_n ? grad_sh_n[c] : nullptr;
+        a.gpu[c] = grad_dp_du ? grad_dp_du[c] : nullptr;
+        a.gpv[c] = grad_dp_dv ? grad_dp_dv[c] : nullptr;
+    }
+    if (n == 0) return HF_OK;
+    return light_launch(hf_launch_bumpmap, 1, a, stream);
+}
+
 // What the three hf_refract_* entries share: the caustic row's rows, interface and receiver, the film's sample count,
 // the texture and the medium
 static int refract_args(const char *who, size_t n, uint32_t spp, const float *const p[3], const float *const nrm[3],

@@ -9184,6 +9184,251 @@ void hf_launch_normalmap(int mode, const hf_normalmap_args &a, hipStream_t strea
 }
 
 // ---------------------------------------------------------------------------------
+// The bump map (include/hf.h hf_bumpmap_*): the reference's `bumpmap` (bumpmap.cpp:199-222 over
+// Texture::eval_1_grad, bitmap.cpp:346-423) as a map of the shading normal alone.  One lane per sample, the record read
+// once: the ONE plane of the texture is looked up at the normal map's pos = (u TW, v TH) by bitmap_cell, its slopes
+// (Lx, Ly) are hf_bitmap_cell::slopes' -- the out_grad of hf_bitmap_eval, bit for bit -- and the rest is in double:
+// g = scale (TW Lx, TH Ly), P_u = dp_du + b (g_x - <b, dp_du> / <b, b>), P_v likewise, c = P_u x P_v, N = sigma c / |c| with
+// sigma = -1 where <n_geo, c> < 0, rounded once per component.  The division by <b, b> makes the projection exact for the
+// b that arrives -- a float32 normal is unit only to rounding, and without it a flat texture leaves b's direction by
+// (|b|^2 - 1) tan(angle between b and the tangents' normal).  A lane that is not perturbed (inactive, a record that is
+// not finite, no lookup, b = 0, a degenerate dp_du, dp_dv or c) passes b through bit for bit.  The tangent and the adjoint rebuild
+// the same lane state (bumpmap_lane); they differentiate the SLOPES, so a texel's weight is -+(1 - f), -+f and uv enters
+// through the cross difference C = v11 - v10 - v01 + v00.  The adjoint's scatter (bumpmap_scatter) is four float atomics
+// per run of consecutive lanes that share a cell: the run sum is normalmap_scatter's scheme.
+// ---------------------------------------------------------------------------------
+#ifndef HF_BUMPMAP_WAVES
+#define HF_BUMPMAP_WAVES 8 // resident waves per SIMD of the forward kernel: it streams and walks nothing
+#endif
+#ifndef HF_BUMPMAP_AD_WAVES
+#define HF_BUMPMAP_AD_WAVES 5 // the tangent and the adjoint hold both projected tangents and their derivatives in double
+#endif
+// what the three kernels know of a perturbed lane: the cell, the four texels' cross difference C, the base normal b,
+// dp_du (u), dp_dv (v), the gradient g, the projected tangents, ch = c / |c|, rC = 1 / |c|, sigma, k = 1 / <b, b> and
+// bu = k <b, dp_du>, bv = k <b, dp_dv>
+struct hf_bumpmap_lane {
+    hf_bitmap_cell e;
+    float bf[3];
+    float t[4]; // v00, v10, v01, v11
+    double b[3], u[3], v[3], Pu[3], Pv[3], ch[3];
+    double g[2], k, bu, bv, rC, sigma;
+};
+// the lane's state; false: a pass-through lane (s.bf alone is then defined)
+__device__ __forceinline__ bool bumpmap_lane(const hf_bumpmap_args &a, size_t i, hf_bumpmap_lane &s) {
+    float uf[3], vf[3], nf[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        s.bf[c] = a.sh_n[c][i]; nf[c] = a.n_geo[c][i]; uf[c] = a.dp_du[c][i]; vf[c] = a.dp_dv[c][i];
+    }
+    const float u = a.uv[0][i], v = a.uv[1][i];
+    if (!(a.active ? a.active[i] != 0 : true)) return false;
+    bool fin = nm_finite(u) && nm_finite(v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) fin = fin && nm_finite(s.bf[c]) && nm_finite(nf[c]) && nm_finite(uf[c]) && nm_finite(vf[c]);
+    if (!fin) return false;
+    // the normal map's positions: one rounding each
+    s.e = bitmap_cell(&a, __fmul_rn(u, (float) a.TW), __fmul_rn(v, (float) a.TH));
+    if (!s.e.ok) return false;
+    float Lx, Ly;
+    s.e.slopes(a.tex, Lx, Ly);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s.t[j] = a.tex[s.e.j[j]];
+    s.g[0] = (double) a.scale * ((double) a.TW * (double) Lx);
+    s.g[1] = (double) a.scale * ((double) a.TH * (double) Ly);
+    double ng[3], c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        s.b[k] = (double) s.bf[k]; s.u[k] = (double) uf[k]; s.v[k] = (double) vf[k]; ng[k] = (double) nf[k];
+    }
+    const double B2 = nm_dot(s.b, s.b);
+    if (!(B2 > 0.0)) return false;
+    s.k = 1.0 / B2;
+    s.bu = nm_dot(s.b, s.u) * s.k;
+    s.bv = nm_dot(s.b, s.v) * s.k;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        s.Pu[k] = s.u[k] + s.b[k] * (s.g[0] - s.bu);
+        s.Pv[k] = s.v[k] + s.b[k] * (s.g[1] - s.bv);
+    }
+    nm_cross(s.Pu, s.Pv, c);
+    const double C2 = nm_dot(c, c), U2 = nm_dot(s.u, s.u), V2 = nm_dot(s.v, s.v);
+    if (!(U2 > 0.0) || !(V2 > 0.0) || !(C2 >= 1e-12 * U2 * V2)) return false;
+    s.rC = 1.0 / sqrt(C2);
+    s.sigma = nm_dot(ng, c) < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s.ch[k] = c[k] * s.rC;
+    return true;
+}
+
+__global__ __launch_bounds__(HF_BLOCK, HF_BUMPMAP_WAVES) void hf_bumpmap_kernel(hf_bumpmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    hf_bumpmap_lane s;
+    const bool pert = bumpmap_lane(a, i, s);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a.out_n[c][i] = pert ? (float) (s.sigma * s.ch[c]) : s.bf[c];
+    if (a.mask) a.mask[i] = pert ? 1 : 0;
+}
+
+// dN of the tangents dtex, duv, dsh_n, ddp_du, ddp_dv (each NULL: zero) with the cell, the decision and sigma held; a
+// pass-through lane: dN = dsh_n
+__global__ __launch_bounds__(HF_BLOCK, HF_BUMPMAP_AD_WAVES) void hf_bumpmap_tangent_kernel(hf_bumpmap_args a) {
+    const size_t i = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    hf_bumpmap_lane s;
+    const bool pert = bumpmap_lane(a, i, s);
+    float dbf[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dbf[c] = a.dn[c] ? a.dn[c][i] : 0.f;
+    if (!pert) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.out_n[c][i] = dbf[c];
+        return;
+    }
+    const double fx = (double) s.e.fx, fy = (double) s.e.fy, gx = (double) (1.f - s.e.fx), gy = (double) (1.f - s.e.fy);
+    double dLx = 0.0, dLy = 0.0;
+    if (a.dtex) {
+        const double d00 = (double) a.dtex[s.e.j[0]], d10 = (double) a.dtex[s.e.j[1]], d01 = (double) a.dtex[s.e.j[2]],
+                     d11 = (double) a.dtex[s.e.j[3]];
+        dLx = gy * (d10 - d00) + fy * (d11 - d01);
+        dLy = gx * (d01 - d00) + fx * (d11 - d10);
+    }
+    if (a.duv[0]) {
+        const double C = ((double) s.t[3] - (double) s.t[1]) - ((double) s.t[2] - (double) s.t[0]);
+        dLx += C * ((double) a.TH * (double) a.duv[1][i]);
+        dLy += C * ((double) a.TW * (double) a.duv[0][i]);
+    }
+    const double dg[2] = { (double) a.scale * ((double) a.TW * dLx), (double) a.scale * ((double) a.TH * dLy) };
+    double db[3], du[3], dv[3], dPu[3], dPv[3], x0[3], x1[3], dc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        db[k] = (double) dbf[k];
+        du[k] = a.dpu[k] ? (double) a.dpu[k][i] : 0.0;
+        dv[k] = a.dpv[k] ? (double) a.dpv[k][i] : 0.0;
+    }
+    // d(k <b, u>) = k (<db, u> + <b, du> - 2 bu <b, db>)
+    const double bdb = 2.0 * nm_dot(s.b, db);
+    const double dbu = (nm_dot(db, s.u) + nm_dot(s.b, du) - s.bu * bdb) * s.k;
+    const double dbv = (nm_dot(db, s.v) + nm_dot(s.b, dv) - s.bv * bdb) * s.k;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        dPu[k] = du[k] + db[k] * (s.g[0] - s.bu) + s.b[k] * (dg[0] - dbu);
+        dPv[k] = dv[k] + db[k] * (s.g[1] - s.bv) + s.b[k] * (dg[1] - dbv);
+    }
+    nm_cross(dPu, s.Pv, x0);
+    nm_cross(s.Pu, dPv, x1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dc[k] = x0[k] + x1[k];
+    const double cd = nm_dot(s.ch, dc);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.out_n[k][i] = (float) (s.sigma * ((dc[k] - s.ch[k] * cd) * s.rC));
+}
+
+// The adjoint's texel scatter: gtex[j] += qx wx_j + qy wy_j with the SLOPES' weights wx = (-(1 - fy), 1 - fy, -fy, fy),
+// wy = (-(1 - fx), -fx, 1 - fx, fx) and q = (dL/dLx, dL/dLy).  The lanes of a run -- consecutive perturbed lanes of the
+// wave with the same cell -- add their four products up first (normalmap_scatter's scheme, written again here: taking the
+// run sum out into a helper both maps call changed the instructions of hf_normalmap_adjoint_kernel) and the
+// run's first lane issues the four atomics.  HF_BUMPMAP_MERGE = 0 builds the plain form: four atomics per perturbed lane
+// (profiles/bumpmap).
+#ifndef HF_BUMPMAP_MERGE
+#define HF_BUMPMAP_MERGE 1
+#endif
+// every lane of the wave calls this (a lane past the end or a pass-through lane with pert = false: it adds nothing)
+__device__ __forceinline__ void bumpmap_scatter(const hf_bumpmap_args &a, const hf_bitmap_cell &e, bool pert, float qx, float qy) {
+    const float gx = 1.f - e.fx, gy = 1.f - e.fy;
+    float v[4] = { -(qx * gy) - qy * gx, qx * gy - qy * e.fx, qy * gx - qx * e.fy, qx * e.fy + qy * e.fx };
+#if HF_BUMPMAP_MERGE
+    const unsigned lane = __lane_id();
+    // a cell is named by its first and last texel (both below 2^31)
+    const unsigned long long key = pert ? ((unsigned long long) e.j[0] | ((unsigned long long) e.j[3] << 32)) : ~0ull;
+    const unsigned long long before = __shfl_up(key, 1);
+    const bool head = !pert || lane == 0 || before != key;
+    const unsigned long long heads = __ballot(head);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = pert ? v[j] : 0.f;
+    // after the step d a lane holds the sum of its run over [lane, lane + 2 d)
+    for (unsigned d = 1; d < 64u; d <<= 1) {
+        const bool join = lane + d < 64u && (((heads >> 1) >> lane) & ((1ull << d) - 1ull)) == 0ull;
+        if (__ballot(join) == 0ull) break; // wave-uniform: no run is longer than d
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float o = __shfl_down(v[j], d);
+            if (join) v[j] += o;
+        }
+    }
+    if (pert && head) {
+#else
+    if (pert) {
+#endif
+#pragma unroll
+        for (int j = 0; j < 4; ++j) atomicAdd(a.gtex + e.j[j], v[j]);
+    }
+}
+
+// the transpose: grad_uv, grad_sh_n, grad_dp_du, grad_dp_dv overwritten (exact zeros where nothing flows; a pass-through
+// lane hands grad_out to grad_sh_n), grad_tex accumulated into with float atomics (bumpmap_scatter).  No lane leaves before
+// the scatter: a lane past the end reads the last sample and stores nothing
+__global__ __launch_bounds__(HF_BLOCK, HF_BUMPMAP_AD_WAVES) void hf_bumpmap_adjoint_kernel(hf_bumpmap_args a) {
+    const size_t i0 = (size_t) blockIdx.x * HF_BLOCK + threadIdx.x;
+    const bool in = i0 < a.n;
+    const size_t i = in ? i0 : a.n - 1;
+    hf_bumpmap_lane s;
+    const bool pert = bumpmap_lane(a, i, s) && in;
+    float gf[3], qx = 0.f, qy = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) gf[c] = a.gout[c][i];
+    if (!pert) {
+        if (in) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (a.gn[0]) a.gn[c][i] = gf[c];
+                if (a.gpu[0]) a.gpu[c][i] = 0.f;
+                if (a.gpv[0]) a.gpv[c][i] = 0.f;
+            }
+            if (a.guv[0]) { a.guv[0][i] = 0.f; a.guv[1][i] = 0.f; }
+        }
+    } else {
+        double g[3], gc[3], gPu[3], gPv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g[c] = (double) gf[c];
+        // N = sigma c / |c|
+        const double cg = nm_dot(s.ch, g);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gc[c] = s.sigma * ((g[c] - s.ch[c] * cg) * s.rC);
+        // c = P_u x P_v
+        nm_cross(s.Pv, gc, gPu);
+        nm_cross(gc, s.Pu, gPv);
+        // P_u = u + b (g_x - k <b, u>), P_v = v + b (g_y - k <b, v>), k = 1 / <b, b>
+        const double su = nm_dot(gPu, s.b), sv = nm_dot(gPv, s.b), ku = s.k * su, kv = s.k * sv;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (a.gn[0])
+                a.gn[c][i] = (float) (gPu[c] * (s.g[0] - s.bu) - s.u[c] * ku + gPv[c] * (s.g[1] - s.bv) - s.v[c] * kv +
+                                      2.0 * s.b[c] * (s.bu * ku + s.bv * kv));
+            if (a.gpu[0]) a.gpu[c][i] = (float) (gPu[c] - s.b[c] * ku);
+            if (a.gpv[0]) a.gpv[c][i] = (float) (gPv[c] - s.b[c] * kv);
+        }
+        // g = scale (TW Lx, TH Ly)
+        const double gLx = (double) a.scale * ((double) a.TW * su), gLy = (double) a.scale * ((double) a.TH * sv);
+        if (a.guv[0]) {
+            const double C = ((double) s.t[3] - (double) s.t[1]) - ((double) s.t[2] - (double) s.t[0]);
+            a.guv[0][i] = (float) ((double) a.TW * (C * gLy));
+            a.guv[1][i] = (float) ((double) a.TH * (C * gLx));
+        }
+        qx = (float) gLx; qy = (float) gLy;
+    }
+    if (a.gtex) bumpmap_scatter(a, s.e, pert, qx, qy);
+}
+
+// mode 0: forward, 1: adjoint, 2: tangent
+void hf_launch_bumpmap(int mode, const hf_bumpmap_args &a, hipStream_t stream) {
+    if (a.n == 0) return;
+    const dim3 grid((unsigned) ((a.n + HF_BLOCK - 1) / HF_BLOCK)), block(HF_BLOCK);
+    hipLaunchKernelGGL(mode == 0 ? hf_bumpmap_kernel : mode == 1 ? hf_bumpmap_adjoint_kernel : hf_bumpmap_tangent_kernel,
+                       grid, block, 0, stream, a);
+}
+
+// ---------------------------------------------------------------------------------
 // Homogeneous medium (include/hf.h hf_medium_*): single scattering in the half space below a top plane
 // (`homogeneous` + `hg`, src/media/homogeneous.cpp, src/phase/hg.cpp) under the directional rig, which lies outside it.
 // One lane per sample; the sample's o, d, t are read once and held across the loop over its K = num_steps points, the

@@ -229,6 +229,24 @@ struct hf_normalmap_args {
 };
 // mode 0: forward, 1: adjoint, 2: tangent; one lane per sample, no grid stride, no scratch block
 void hf_launch_normalmap(int mode, const hf_normalmap_args &a, hipStream_t stream);
+// ---- the bump map (hf_bumpmap_eval / _tangent / _adjoint): the one argument of its three kernels; TW, TH, wrap as in
+// hf_bitmap_args (bitmap_cell reads either); tex is ONE plane, exactly a hf_bitmap_eval texture ----
+struct hf_bumpmap_args {
+    size_t n;
+    uint32_t TW, TH;
+    int32_t wrap;
+    float scale;                             // the gradient's multiplier (finite)
+    const float *tex;                        // [TH][TW]
+    const float *uv[2], *sh_n[3], *n_geo[3], *dp_du[3], *dp_dv[3];
+    const uint8_t *active;                   // optional (NULL: every lane)
+    float *out_n[3];                         // forward: N; tangent: dN
+    uint8_t *mask;                           // forward: written (NULL: not wanted)
+    const float *dtex, *duv[2], *dn[3], *dpu[3], *dpv[3]; // tangent inputs (NULL: zero); dtex: the texels'
+    const float *gout[3];                    // adjoint input: dL/dN
+    float *gtex, *guv[2], *gn[3], *gpu[3], *gpv[3]; // adjoint outputs (NULL: not wanted); gtex is accumulated
+};
+// mode 0: forward, 1: adjoint, 2: tangent; one lane per sample, no grid stride, no scratch block
+void hf_launch_bumpmap(int mode, const hf_bumpmap_args &a, hipStream_t stream);
 // ---- area-light lighting (hf_rect_rays, hf_rect_lighting / _adjoint / _tangent): the one argument of its four kernels;
 // TW, TH, wrap as in hf_bitmap_args (bitmap_cell reads either) ----
 struct hf_rect_args {

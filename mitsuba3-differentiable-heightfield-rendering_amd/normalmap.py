@@ -25,6 +25,27 @@ def _row_tangent(x):
     return x.to(dtype=torch.float32).contiguous() if x is not None else None
 
 
+def _with_normal(si, N):
+    """a shallow copy of ``si`` with the shading normal ``N`` (``NormalMap.perturb``, ``BumpMap.perturb``): ``sh_frame`` is
+    ``Frame3f(s, t, N)``, ``s`` and ``t`` the detached Gram-Schmidt of ``dp_du`` against ``N`` (the input's own ``s`` where that
+    degenerates), and ``wi``, where present, re-expressed in the new frame"""
+    out = copy.copy(si)
+    with torch.no_grad():
+        Nd, u = N.detach(), si.dp_du.detach()
+        a = u - Nd * (Nd * u).sum(0, keepdim=True)
+        len_a = torch.linalg.vector_norm(a, dim=0, keepdim=True)
+        ok = (len_a > 0) & torch.isfinite(len_a)
+        s = a / torch.where(ok, len_a, torch.ones_like(len_a))
+        if si.sh_frame.s is not None:
+            s = torch.where(ok, s, si.sh_frame.s.detach())
+        t = torch.linalg.cross(Nd, s, dim=0)
+    out.sh_frame = Frame3f(s, t, N)
+    if si.wi is not None and si.sh_frame.s is not None:
+        world = si.sh_frame.s * si.wi[0:1] + si.sh_frame.t * si.wi[1:2] + si.sh_frame.n * si.wi[2:3]
+        out.wi = out.sh_frame.to_local(world.detach())
+    return out
+
+
 class _NormalMapOp(torch.autograd.Function):
     """(N [3, n], mask bytes) of hf_normalmap_eval; backward = hf_normalmap_eval_adjoint (gradients of the texels, uv, sh_n
     and dp_du), jvp = hf_normalmap_eval_tangent.  Both hold the cell and the perturbed / pass-through decision."""
@@ -76,7 +97,8 @@ class NormalMap:
     texel ``data[:, iy, ix]`` is ``0.5 * (m + 1)`` for the unit normal ``m`` in the tangent space (s, t, n) of the surface,
     with its centre at ``uv = ((ix + 0.5) / TW, (iy + 0.5) / TH)``.  ``data``: [3, TH, TW] float32 device tensor, PLANAR,
     kept by reference -- it may require grad or be a dual.  ``wrap``: ``"repeat"`` (the reference bitmap's default) or
-    ``"clamp"``.  Out of scope: bumpmap, nearest filtering, the mirror wrap, a gradient for the frame's s and t."""
+    ``"clamp"``.  The reference's ``bumpmap`` is ``BumpMap`` (bumpmap.py).  Out of scope: nearest filtering, the
+    mirror wrap, a gradient for the frame's s and t."""
 
     def __init__(self, data, wrap="repeat"):
         if not isinstance(data, torch.Tensor) or data.dtype != torch.float32:
@@ -136,19 +158,4 @@ class NormalMap:
         are the detached Gram-Schmidt of ``dp_du`` against ``N`` (the input's own where that degenerates) and ``wi``, where
         present, is re-expressed in the new frame.  Host-side convenience in a few torch ops, not the hot path; only ``N``
         carries a gradient."""
-        N = self.normal(si, active)
-        out = copy.copy(si)
-        with torch.no_grad():
-            Nd, u = N.detach(), si.dp_du.detach()
-            a = u - Nd * (Nd * u).sum(0, keepdim=True)
-            len_a = torch.linalg.vector_norm(a, dim=0, keepdim=True)
-            ok = (len_a > 0) & torch.isfinite(len_a)
-            s = a / torch.where(ok, len_a, torch.ones_like(len_a))
-            if si.sh_frame.s is not None:
-                s = torch.where(ok, s, si.sh_frame.s.detach())
-            t = torch.linalg.cross(Nd, s, dim=0)
-        out.sh_frame = Frame3f(s, t, N)
-        if si.wi is not None and si.sh_frame.s is not None:
-            world = si.sh_frame.s * si.wi[0:1] + si.sh_frame.t * si.wi[1:2] + si.sh_frame.n * si.wi[2:3]
-            out.wi = out.sh_frame.to_local(world.detach())
-        return out
+        return _with_normal(si, self.normal(si, active))
